@@ -6,11 +6,16 @@ pBWT pass 1 + DP, traceback, segment merge, pass-2 boundary states) over one syn
 founder-mosaic alignment that is already resident in HBM (column-major, 2 bits per cell for
 sigma <= 4, 4 bits for sigma <= 16, else 1 B).
 Workload at N=1 [r5]: BASELINE.json configs[3]'s alignment (C4: m=100,000 x n=5,000,000, sigma=4, L=200) -- the
-configuration the metric's 1/2/4/8-GPU curve is quoted on; its 125 GB of packed cells fit one MI355X.  The other
-single-GPU configurations (C2, C3, C5) are measured in child processes of the same invocation and reported under
-config.other_workloads (a failure or a hang there cannot take the headline line with it).
+configuration the metric's 1/2/4/8-GPU curve is quoted on; its 125 GB of packed cells fit one MI355X.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line.  With --full it also times the CPU
+baseline (cpu_baseline) and, without --workload, measures the other single-GPU configurations (C2, C3, C5) in child
+processes of the same invocation under config.other_workloads (a failure or a hang there cannot take the headline
+line with it).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; the boundary
+states a fixed, seeded sample of them), so that two builds can be compared output for output on the same input.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -203,6 +208,52 @@ def cpu_baseline(ctx, w, threads):
                   % (ncols, n, m, r["t_pass1"], r["pass2_threads"], r["t_pass2"], os.cpu_count() or 0),
         "seconds": dt,
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all files together (the .npy headers included)
+DUMP_SEED = 0x5EED0D0D         # which boundary states are written when not all of them fit
+
+
+def dump_outputs(ctx, out_dir):
+    """What a caller of the path receives from the context's last run, as float64 arrays (exact for every index and
+    size below 2^53): the merged segments (reduced_traceback), the DP's traceback, max_segment_size, and the boundary
+    states (input_permutation, input_divergence) -- all of them when they fit the budget, else a fixed, seeded sample of
+    the boundaries (boundary_index says which).  Returns {name: shape}."""
+    import numpy as np
+    res = ctx.result
+    red = ctx.reduced_traceback()
+    tb = ctx.traceback()
+    arrays = {
+        "max_segment_size": np.array([res.max_segment_size], dtype=np.float64),
+        "segments_lb": red["lb"].astype(np.float64),
+        "segments_rb": red["rb"].astype(np.float64),
+        "segments_size": red["segment_size"].astype(np.float64),
+        "traceback_lb": tb["lb"].astype(np.float64),
+        "traceback_rb": tb["rb"].astype(np.float64),
+        "traceback_segment_max_size": tb["segment_max_size"].astype(np.float64),
+        "traceback_segment_size": tb["segment_size"].astype(np.float64),
+    }
+    header_bytes = 256                                   # an .npy header is 128 bytes (a few more for a long shape)
+    used = sum(v.nbytes + header_bytes for v in arrays.values()) + 3 * header_bytes
+    per_boundary = 2 * ctx.m * 8 + 8                     # a and d as float64, and its index
+    S = len(red)
+    k = min(S, max(0, (DUMP_BUDGET_BYTES - used) // per_boundary))
+    if S and not k:
+        raise SystemExit("--dump-outputs: the segments alone exceed %d bytes" % DUMP_BUDGET_BYTES)
+    if k == S:
+        idx = np.arange(S, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False))
+    a_out = np.zeros((k, ctx.m), dtype=np.float64)
+    d_out = np.zeros((k, ctx.m), dtype=np.float64)
+    for j, i in enumerate(idx):
+        a, d = ctx.boundary_state(int(i))
+        a_out[j], d_out[j] = a, d
+    arrays.update(boundary_index=idx.astype(np.float64), boundary_a=a_out, boundary_d=d_out)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
 
 
 def rowshard_leg(args, w, pkg, fdist, torch, dist, rank, world, local_rank, rehearsal):
@@ -418,7 +469,7 @@ def run_workload(pkg, fdist, torch, dist, name, steps, warmup, args, world, rank
                               "gloo via host (rehearsal: ranks share a GPU)" if rehearsal else "RCCL"),
             # strong scaling is judged against ONE GPU on the SAME workload: the N = 1 default of this script is C3, so the
             # committed single-GPU line of this workload is quoted here (python bench.py --workload C4 reproduces it; since
-            # round 4 the N = 1 line also carries it under config.other_workloads)
+            # round 4 the N = 1 line run with --full also carries it under config.other_workloads)
             "single_gpu_same_workload": single_gpu_reference(name) if world > 1 else None,
             "alignments_in_flight_per_gpu": max(1, args.concurrent),
             "cold_first_run_ms": round(cold_ms, 3),
@@ -469,7 +520,12 @@ def main():
     ap.add_argument("--concurrent", type=int, default=1,
                     help="alignments in flight per GPU (one context + host thread each); 1 = the headline single-alignment workload")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="N = 1 without --workload also measures C2, C3 and C5 in child processes (config.other_workloads); this skips them")
+                    help="with --full, N = 1 without --workload also measures C2, C3 and C5 in child processes (config.other_workloads); this skips them")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline (cpu_baseline) and, N = 1 without --workload, C2, C3 and C5 (config.other_workloads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most %d MB; one GPU)"
+                         % (DUMP_BUDGET_BYTES // 10**6))
     ap.add_argument("--rowshard-cols", type=int, default=0,
                     help="instead of the headline step: the north-star row split (fseq_rowshard_pbwt) over this many columns of the "
                          "workload, one JSON line of its own (columns/s; latency-bound by design, DESIGN.md section 6)")
@@ -486,6 +542,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus and world > 1:
         raise SystemExit("--gpus %d does not match WORLD_SIZE %d" % (args.gpus, world))
+    if args.dump_outputs and (world > 1 or args.rowshard_cols):
+        raise SystemExit("--dump-outputs writes the single-GPU path's outputs: run it with --gpus 1 and without --rowshard-cols")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the segmentation path has no CPU fallback")
     # rehearsal on a box with fewer GPUs than ranks (FSEQ_BENCH_REHEARSAL=1): ranks share the cards and the
@@ -515,6 +573,8 @@ def main():
         return
     run = run_workload(pkg, fdist, torch, dist, args.workload, args.steps, args.warmup, args, world, rank, local_rank, rehearsal)
     ctx, out = run["ctx"], run["line"]
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs)
     # secondary figure (not `value`): the DP of one alignment occupies one CU for ~2/3 of a step, so
     # several alignments (chromosomes) in flight share the chip; measured with 8 contexts / host threads
     if world == 1 and args.concurrent == 1 and args.batched:
@@ -534,18 +594,18 @@ def main():
                                      "note": "8 alignments of the same shape in flight on the one GPU through fseq_run_segmentation_batch (one context, two streams and one host thread each; GPU_MAX_HW_QUEUES=%s); not the headline metric" % os.environ.get("GPU_MAX_HW_QUEUES")}
         for e in others:
             e.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(ctx, w, args.cpu_threads or min(os.cpu_count() or 1, 16))
     else:
         out["cpu_baseline"] = None
     ctx.close()
     for e in run["extra"]:
         e.close()
-    # The other single-GPU configurations of BASELINE.json, each with its own step count, in the same invocation (only when
-    # the driver's plain command is run: no --workload given): C2 (configs[1]), C3 (configs[2]) and C5 (configs[4]'s
+    # The other single-GPU configurations of BASELINE.json, each with its own step count, in the same invocation (only with
+    # --full and no --workload given): C2 (configs[1]), C3 (configs[2]) and C5 (configs[4]'s
     # alignment on one GPU).  Each in a CHILD PROCESS of its own with a time limit: a failure, a hang or a GPU fault there
     # cannot take the headline line with it.  Not part of `value`.
-    if world == 1 and headline_default and not args.no_other_workloads and args.concurrent == 1:
+    if world == 1 and args.full and headline_default and not args.no_other_workloads and args.concurrent == 1:
         import subprocess
         others_out = {}
         for name, (k_steps, k_warm) in OTHER_WORKLOADS.items():

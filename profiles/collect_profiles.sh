@@ -19,5 +19,5 @@ rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_B
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $out/waits -- $BENCH > $out/bench_waits.json 2> $out/waits.err
 # the effective clock of every launch (round 4): GRBM_GUI_ACTIVE / 8 XCDs / dispatch duration (GRBM slots are independent of SQ / TCC)
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $out/grbm -- $BENCH > $out/bench_grbm.json 2> $out/grbm.err
-python3 bench.py --workload $wl --steps ${FSEQ_PROFILE_STEPS:-5} --warmup 2 --no-other-workloads > $out/bench.json 2> $out/bench.err
+python3 bench.py --workload $wl --steps ${FSEQ_PROFILE_STEPS:-5} --warmup 2 --full --no-other-workloads > $out/bench.json 2> $out/bench.err
 find $out -name '*.csv' | sort

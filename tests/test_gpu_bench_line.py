@@ -1,7 +1,8 @@
 """The driver's contract for bench.py: ONE JSON line on stdout with the metric, the roofline object (the path's accounting
 figure, the HBM traffic the PMC passes counted, the dominant phase with a bound that can be approached, frac <= 1), the
-cold first run and the CPU baseline.  Run as the driver runs it (a child process), on the small workload C2 so that it takes
-seconds; the headline test runs the driver's plain command (C4 and, in child processes, C2, C3, C5)."""
+cold first run and, with --full, the CPU baseline.  Run as the driver runs it (a child process), on the small workload C2 so
+that it takes seconds; the headline test runs the driver's command with --full (C4 and, in child processes, C2, C3, C5).  A
+plain run measures the headline alone, and --dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _bench(*args):
 
 
 def test_bench_line_contract():
-    d = _bench("--workload", "C2", "--steps", "3", "--warmup", "1")
+    d = _bench("--workload", "C2", "--steps", "3", "--warmup", "1", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in d, k
@@ -52,9 +53,9 @@ def test_bench_line_contract():
 
 
 def test_headline_line_carries_the_other_workloads():
-    """Without --workload the N = 1 line is the headline C4 -- the configuration the metric is quoted on -- and measures C2,
-    C3 and C5 beside it (child processes)."""
-    d = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    """Without --workload the N = 1 line is the headline C4 -- the configuration the metric is quoted on -- and, with --full,
+    measures C2, C3 and C5 beside it (child processes)."""
+    d = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full")
     assert "C4" in d["config"]["workload"] and d["steps"] == 3
     assert abs(d["value"] - 100000 * 5000000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
     assert d["config"]["cold_first_run_ms"] > 0 and d["config"]["reduced_blocks"] > 0
@@ -65,3 +66,27 @@ def test_headline_line_carries_the_other_workloads():
         assert v["value"] > 1e10 and v["ms_per_step"] > 0 and set(v["phases_ms"]) >= {"ms_phase_a", "ms_phase_c", "ms_dp", "ms_pass2"}, name
         assert v["cold_first_run_ms"] > 0
     assert d["roofline"]["dominant_kernel"].get("frac") is None or d["roofline"]["dominant_kernel"]["frac"] <= 1.0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing beside the headline; --dump-outputs writes what the last
+    timed step computed -- float64 arrays within 64 MB -- and, the input being seeded, the same files on every run."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = [_bench("--workload", "C2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(p)) for p in dirs]
+    d = lines[0]
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["cpu_baseline"] is None and "other_workloads" not in d["config"]
+    assert abs(d["value"] - 2500 * 100000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "segments_rb.npy" in names and "boundary_a.npy" in names
+    assert sum(os.path.getsize(dirs[0] / f) for f in names) <= 64 * 10**6
+    out = {f[:-4]: np.load(dirs[0] / f) for f in names}
+    for f in names:
+        assert out[f[:-4]].dtype == np.float64, f
+        assert np.array_equal(out[f[:-4]], np.load(dirs[1] / f)), f
+    assert out["max_segment_size"][0] == d["config"]["max_segment_size"] == out["segments_size"].max()
+    assert len(out["segments_rb"]) == d["config"]["segments"] and out["segments_rb"][-1] == 100000
+    k = len(out["boundary_index"])
+    assert k > 0 and out["boundary_a"].shape == out["boundary_d"].shape == (k, 2500)
+    for a in out["boundary_a"]:
+        assert np.array_equal(np.sort(a), np.arange(2500))

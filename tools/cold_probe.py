@@ -2,7 +2,8 @@
 import importlib, sys, time, os
 import torch
 torch.cuda.init()
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/oracle')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import bench
 pkg = importlib.import_module("founder-sequences_amd")
 name = sys.argv[1]
