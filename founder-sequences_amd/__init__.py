@@ -81,9 +81,11 @@ EXPORTS = [
     "fseq_set_device_columns_packed", "fseq_debug_dp_schedule", "fseq_run_segmentation_batch", "fseq_join_bipartite", "fseq_join_random", "fseq_bipartite_match_host", "fseq_random_join_host", "fseq_write_segments",
     "fseq_set_progress", "fseq_step_max", "fseq_current_step", "fseq_set_memory_budget", "fseq_write_segments_host", "fseq_get_join_profile", "fseq_debug_set_tuning",
     "fseq_shard_abort", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges",
+    "fseq_set_list_memory", "fseq_debug_list_windows",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
-DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning"]
+DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
+                 "fseq_debug_list_windows"]
 
 FSEQ_E_PEER = 6
 STAGE_TRACEBACK, STAGE_MERGE, STAGE_SAMPLES = 0, 1, 2
@@ -161,6 +163,8 @@ def load_library():
     L.fseq_current_step.restype = u64
     L.fseq_current_step.argtypes = [vp]
     L.fseq_set_memory_budget.argtypes = [vp, u64]
+    L.fseq_set_list_memory.argtypes = [vp, u64]
+    L.fseq_debug_list_windows.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.fseq_shard_abort.argtypes = [vp, C.c_int]
     L.fseq_debug_dp_owned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fseq_debug_clock.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
@@ -335,7 +339,7 @@ class SegmentationContext:
     segmentation_container (reduced_traceback, reduced_pbwt_samples via boundary_state(),
     max_segment_size)."""
 
-    def __init__(self, m, n, segment_length, pbwt_sample_rate=0, block_len=0, list_cap=0, device=0):
+    def __init__(self, m, n, segment_length, pbwt_sample_rate=0, block_len=0, list_cap=0, device=0, list_memory=0):
         self.L = load_library()
         self.m, self.n, self.segment_length = int(m), int(n), int(segment_length)
         p = Params(self.m, self.n, self.segment_length, int(pbwt_sample_rate), int(block_len), int(list_cap), int(device))
@@ -346,6 +350,8 @@ class SegmentationContext:
         self.h = h
         self.result = None
         self._keep = None
+        if list_memory:
+            self.set_list_memory(list_memory)
 
     def close(self):
         if getattr(self, "h", None):
@@ -388,6 +394,18 @@ class SegmentationContext:
     def set_memory_budget(self, nbytes):
         """Device memory this context may hold in all (ranks that share a card); 0 = whatever is free."""
         self._check(self.L.fseq_set_memory_budget(self.h, int(nbytes)))
+
+    def set_list_memory(self, nbytes):
+        """Device memory the per-column lists of a long-path run may occupy (fseq_set_list_memory); 0 = every list held.
+        Beyond it the run holds its lists in column windows, with the same results."""
+        self._check(self.L.fseq_set_list_memory(self.h, int(nbytes)))
+
+    def list_windows(self):
+        """What the last run did with its lists: {bytes_held, columns_per_window, windows, merge_windows}
+        (windows == 1: every list held)."""
+        b, cols, w, mw = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self.L.fseq_debug_list_windows(self.h, C.byref(b), C.byref(cols), C.byref(w), C.byref(mw)))
+        return {"bytes_held": b.value, "columns_per_window": cols.value, "windows": w.value, "merge_windows": mw.value}
 
     def set_progress(self, fn):
         """fn(stage, current_step, step_max) at the phase boundaries of run() (None: off); step_max() / current_step()

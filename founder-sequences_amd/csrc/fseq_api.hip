@@ -481,20 +481,23 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		}
 	}
 	uint64_t const k_lo = held_lo(c), k_cnt = held_hi(c) - k_lo;      // sharded: lists and stride states of my columns only
-	if (X && (!c->d_ent || c->X != X))
+	// (a list budget: the H + wb B columns of one window, plan_list_windows)
+	size_t const ent_count = c->lw.on ? ((size_t) c->lw.H + (size_t) c->lw.wb * c->B) * ((X + 3) & ~1u) + 256 : (size_t) k_cnt * ((X + 3) & ~1u) + 256;
+	if (X && (!c->d_ent || c->X != X || c->lw.ent_count != ent_count))
 	{
 		c->X = X;
 		c->stride = (X + 3) & ~1u;                // lump + up to X+1 entries, even
-		dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr;
-		rc = dev_alloc(c, &c->d_ent_alloc, (size_t) k_cnt * c->stride + 256);   // padded: the DP loads strips unconditionally
+		dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr; c->lw.ent_count = 0;
+		rc = dev_alloc(c, &c->d_ent_alloc, ent_count);   // padded: the DP loads strips unconditionally
 		if (rc == FSEQ_E_OOM && c->d_ss_a)
 		{
 			// the stride states were sized before the lists grew: give their memory back and size them again below
 			dev_free(c, &c->d_ss_a_alloc); dev_free(c, &c->d_ss_d_alloc); c->d_ss_a = c->d_ss_d = nullptr;
-			rc = dev_alloc(c, &c->d_ent_alloc, (size_t) k_cnt * c->stride + 256);
+			rc = dev_alloc(c, &c->d_ent_alloc, ent_count);
 		}
 		if (rc) return rc;
-		c->d_ent = c->d_ent_alloc - (size_t) k_lo * c->stride;   // list of column k at d_ent + k * stride
+		c->lw.ent_count = ent_count;
+		c->d_ent = c->d_ent_alloc - (size_t) k_lo * c->stride;   // list of column k at d_ent + k * stride (windows: set per window)
 	}
 	if (X && want_ss && !c->d_ss_a && p.n >= 2 * p.segment_length)
 	{
@@ -573,7 +576,7 @@ void free_work(fseq_ctx *c)
 	dev_free(c, &c->d_hrank); dev_free(c, &c->d_hkeyd); dev_free(c, &c->d_hnkeys); dev_free(c, &c->d_hstate_a); dev_free(c, &c->d_hstate_d);
 	for (auto &lv : c->levels) { dev_free(c, &lv.rank_alloc); dev_free(c, &lv.keyd_alloc); dev_free(c, &lv.nkeys_alloc); dev_free(c, &lv.state_a_alloc); dev_free(c, &lv.state_d_alloc); }
 	c->levels.clear();
-	dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr; dev_free(c, &c->d_hdr); dev_free(c, &c->d_flags); dev_free(c, &c->d_recent);
+	dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr; c->lw.ent_count = 0; c->lw.col_lo = c->lw.col_hi = 0; dev_free(c, &c->d_hdr); dev_free(c, &c->d_flags); dev_free(c, &c->d_recent);
 	dev_free(c, &c->d_chunk_r0); c->chunk_cap = 0; dev_free(c, &c->d_tau); c->tau_cap = 0;
 	dev_free(c, &c->d_bk); c->bk_blocks = 0; dev_free(c, &c->d_bkws); c->bkws_words = 0; dev_free(c, &c->d_todo); c->todo_cap = 0;
 	dev_free(c, &c->d_colmask_alloc); c->d_colmask = nullptr; c->colmask_ready = false;
@@ -822,9 +825,10 @@ int follow_traceback(fseq_ctx *c, hipStream_t st)
 	uint2 *const taup = pin_take<uint2>(c, guess);
 	std::vector<uint4> h;
 	// not sharded: the merge thresholds of the traceback boundaries (k_seg_tau_tb) ride along -- one workgroup per
-	// POSSIBLE entry, those behind the count return at once
+	// POSSIBLE entry, those behind the count return at once (list windows: the lists are gone, merge_windowed takes them)
 	c->tau_host.clear();
-	if (!c->sh.on)
+	bool const tau_tb = !c->sh.on && !c->lw.on;
+	if (tau_tb)
 	{
 		if (c->tau_cap < cap) { if ((rc = dev_alloc(c, &c->d_tau, cap))) return rc; c->tau_cap = cap; }
 		hipLaunchKernelGGL(k_seg_tau_tb, dim3((uint32_t) cap), dim3(64), 0, st, reinterpret_cast<uint4 const *>(c->d_tb), d_count, L, c->stride, c->d_ent, c->d_hdr, c->d_tau);
@@ -835,7 +839,7 @@ int follow_traceback(fseq_ctx *c, hipStream_t st)
 	HIP_TRY(c, hipStreamSynchronize(st));
 	HIP_TRY(c, hipGetLastError());
 	h.assign(hp, hp + std::min<size_t>(guess, cnt[0]));
-	if (!c->sh.on) c->tau_host.assign(taup, taup + std::min<size_t>(guess, cnt[0]));
+	if (tau_tb) c->tau_host.assign(taup, taup + std::min<size_t>(guess, cnt[0]));
 	if (cnt[1] != 1u || cnt[0] == 0 || cnt[0] > cap) return fail(c, FSEQ_E_HIP, "internal: the traceback chain does not descend to lb == 0");
 	size_t const S = cnt[0];
 	if (S > guess)
@@ -1648,6 +1652,8 @@ int long_list_capacity(fseq_ctx *c, LongRun &R)
 	return FSEQ_OK;
 }
 
+int merge_windowed(fseq_ctx *c, bool *overflow);
+
 // ---- one attempt with list capacity R.X: phase C (column updates + lists), phase D (the DP), traceback, merge walk.
 // *overflow_out: some DP cell or merge threshold needed more of a list than X entries hold (the caller retries).
 // ---- follow_traceback and find_segments_greedy for one attempt (the lists held their own so far): the traceback on
@@ -1672,7 +1678,11 @@ int long_traceback_and_merge(fseq_ctx *c, LongRun &R, double th0, bool *overflow
 		// holds exactly for current_lb >= tau_rb; tau comes from the list of column rb - 1 where that list lives
 		// (k_seg_tau: one number per traceback boundary instead of the lists; sharded: every rank for its columns).
 		c->segments.clear();
-		if (max_seg < m)
+		if (max_seg < m && c->lw.on)
+		{
+			if ((rc = merge_windowed(c, &overflow))) return rc;
+		}
+		else if (max_seg < m)
 		{
 			uint64_t const own_lo = held_lo(c), own_hi = sharded ? sh.c_hi : n;      // columns whose lists I answer for
 			std::vector<uint2> tau(S);
@@ -2022,6 +2032,270 @@ int red_columns(fseq_ctx *c)
 	return red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride);
 }
 
+// ---- phase C on all rows of the blocks b0 .. b0 + nb - 1
+// (list [r5]: workgroup i owns block list[i] instead of b0 + i -- the blocks the reduced phase C hands to the run on all rows)
+void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = nullptr, uint32_t epoch = 0, uint32_t const *list = nullptr)
+{
+	FSEQ_LONG_LOCALS(c);
+	// columns phase C covers here: all, or my blocks plus the halo block's first columns (the lists my last DP round reads)
+	uint64_t const n_c = sharded ? sh.c_end : n;
+	if (c->use_stream && c->s2.T)
+	{
+		uint32_t pack_abits = 0;
+		if (c->s2.pack) { pack_abits = 1; while ((1u << pack_abits) < m) ++pack_abits; }
+		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws_c, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
+		                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
+		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
+		             c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack | (c->ss_ids ? S2_SS_IDS : 0u), list);
+	}
+	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan)
+		hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
+		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
+	else if (c->use_stream)
+		hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
+		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
+	else
+		ks.columns(st, nb, c->lds_columns, c->d_msa, c->ld, m, n_c, c->B, c->N2, c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->npass, c->bsh,
+		           c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->colmask_ready && c->colmask_use ? c->d_colmask : (uint32_t const *) nullptr, list);
+}
+
+
+// ---- a list budget (fseq_set_list_memory): pass 1's lists in windows of wb consecutive column blocks.  Window w = blocks
+// [lo_w, hi_w) holds the lists of the columns [lo_w B - H, hi_w B) in one buffer (d_ent = d_ent_alloc - (lo_w B - H) stride:
+// the kernels address lists as they always do); phase C writes the window's own columns, the DP runs the rounds whose
+// lists are all there, and the last H columns move to the front for the next window.  H: the columns in front of a window
+// that its first DP round still reads.
+
+// DP rounds [.., r) that the lists of the columns < hi_w B feed: every regular round that reads no later column (its cells
+// read the lists of the columns e0 - 1 .. e0 + len - 2: dp_rounds_within); the drain round and the final cell wait for the
+// last window (the drain round's loads read column n - L, which an earlier window's buffer need not hold)
+uint32_t window_round_hi(fseq_ctx const *c, DpSchedule const &S, uint32_t hi_w)
+{
+	if (hi_w >= c->nblocks) return S.nrounds;
+	return std::min(dp_rounds_within(S, (uint64_t) hi_w * c->B), S.nreg);
+}
+
+// the window shape at list capacity X: the most blocks a window may have with the halo its rounds need beside them
+int plan_list_windows(fseq_ctx *c, uint32_t X)
+{
+	fseq_ctx::ListWindows &W = c->lw;
+	W.on = false;
+	W.merge_windows = 0;
+	uint64_t const n = c->p.n, L = c->p.segment_length, B = c->B, nb = c->nblocks;
+	if (!W.budget || c->sh.on || n < 2 * L) return FSEQ_OK;
+	uint64_t const stride = (X + 3) & ~1u, per_col = stride * sizeof(uint2), pad = 256 * sizeof(uint2);
+	if (n * per_col + pad <= W.budget) return FSEQ_OK;              // every list fits: the run as without a budget
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	uint64_t const cols = W.budget > pad ? (W.budget - pad) / per_col : 0;
+	uint64_t H = S.RL;                                              // (a first guess, raised to what the windows' rounds read)
+	for (int it = 0; it < 64; ++it)
+	{
+		uint64_t const wb = cols > H ? std::min<uint64_t>(nb, (cols - H) / B) : 0;
+		// (the halo moves to the front in one copy: a window must be at least as wide as the halo)
+		if (wb == 0 || wb * B < H)
+		{
+			uint64_t const wmin = std::max<uint64_t>(1, (H + B - 1) / B);
+			char what[320];
+			snprintf(what, sizeof(what), "list memory budget of %llu bytes holds no window: one window of %llu column block(s) of %llu columns plus a halo of %llu columns "
+			         "at list capacity %u needs %llu bytes", (unsigned long long) W.budget, (unsigned long long) wmin, (unsigned long long) B, (unsigned long long) H, X,
+			         (unsigned long long) ((H + wmin * B) * per_col + pad));
+			return fail(c, FSEQ_E_OOM, what);
+		}
+		uint64_t need = 0;
+		uint32_t r_lo = 0;
+		for (uint64_t lo = 0; lo < nb; lo += wb)
+		{
+			uint64_t const hi = std::min(nb, lo + wb);
+			uint32_t const r_hi = window_round_hi(c, S, (uint32_t) hi);
+			if (r_hi > r_lo)
+			{
+				uint64_t const first = (uint64_t) dp_round(S, r_lo).e0 - 1u;     // the lowest column the window's rounds read
+				if (lo * B > first) need = std::max(need, lo * B - first);
+				r_lo = r_hi;
+			}
+		}
+		if (need <= H)
+		{
+			W.on = true;
+			W.wb = (uint32_t) wb; W.H = (uint32_t) H;
+			W.nwin = (uint32_t) ((nb + wb - 1) / wb);
+			W.bytes = (H + wb * B) * per_col + pad;
+			return FSEQ_OK;
+		}
+		H = need;
+	}
+	return fail(c, FSEQ_E_HIP, "internal: no list window shape settles");
+}
+
+// the buffer holds window [lo_w, ..): column k at d_ent + k * stride
+void set_list_window(fseq_ctx *c, uint32_t lo_w)
+{
+	c->d_ent = c->d_ent_alloc + ((int64_t) c->lw.H - (int64_t) lo_w * c->B) * (int64_t) c->stride;
+}
+
+// phase C (lists, headers, stride states) of the blocks [lo, hi): on their representatives where this attempt's plan put
+// them (the plan's block lists ascend within every configuration, so a window's blocks are one stretch of each), else on
+// all rows
+int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
+{
+	if (!c->red_active)
+	{
+		launch_columns(c, lo, hi - lo);
+		return FSEQ_OK;
+	}
+	uint32_t const *const h_blocks = c->h_red_pin + c->nblocks;      // red_plan's host copy of d_red_blocks
+	auto stretch = [&](uint32_t first, uint32_t count) {
+		uint32_t const *const b = h_blocks + first, *const e = b + count;
+		uint32_t const *const a = std::lower_bound(b, e, lo), *const z = std::lower_bound(b, e, hi);
+		return std::make_pair(first + (uint32_t) (a - b), (uint32_t) (z - a));
+	};
+	RedArgs RA;
+	red_fill_args(c, RA);
+	std::vector<RedLaunch> ls;
+	for (auto const &bin : c->red_bins)
+	{
+		auto const r = stretch(bin.first, bin.count);
+		if (r.second) ls.push_back(RedLaunch{bin.config, r.first, r.second});
+	}
+	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
+	int rc;
+	if ((rc = red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride))) return rc;
+	auto const f = stretch(c->red_full_at, c->red_nfull);
+	if (f.second) launch_columns(c, 0, f.second, nullptr, 0, c->d_red_blocks + f.first);
+	return FSEQ_OK;
+}
+
+// pass 1 + the DP window by window (queued on the context's stream; overflow lands in d_flags as for the whole-array DP)
+int long_windows_cd(fseq_ctx *c, DpSchedule const &S)
+{
+	FSEQ_LONG_LOCALS(c);
+	fseq_ctx::ListWindows &W = c->lw;
+	while (W.ev.size() < 2 * (size_t) W.nwin)
+	{
+		hipEvent_t e = nullptr;
+		HIP_TRY(c, hipEventCreate(&e));
+		W.ev.push_back(e);
+	}
+	// (the entries no cell writes -- between the last regular cell and the final one -- read 0, as after dp_spec_reset)
+	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.SZ, 0, c->dp_size * 4, st));
+	uint32_t r_lo = 0, w = 0, lo = 0;
+	for (; lo < c->nblocks; lo += W.wb, ++w)
+	{
+		uint32_t const hi = std::min(c->nblocks, lo + W.wb);
+		if (lo && W.H)
+			HIP_TRY(c, hipMemcpyAsync(c->d_ent_alloc, c->d_ent_alloc + (size_t) W.wb * c->B * c->stride, (size_t) W.H * c->stride * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+		set_list_window(c, lo);
+		if ((rc = window_phase_c(c, lo, hi))) return rc;
+		uint32_t const r_hi = window_round_hi(c, S, hi);
+		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w], st));
+		if (r_hi > r_lo)
+		{
+			hipLaunchKernelGGL(k_dp<DP_PARTIAL>, dim3(1), dim3(1024), dp_lds_bytes(), st, c->dp, c->d_ent, c->d_hdr, c->stride, m, (uint32_t) n, (uint32_t) L,
+			                   c->d_flags, r_lo, r_hi, DpSpecArgs{});
+			r_lo = r_hi;
+		}
+		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w + 1], st));
+	}
+	HIP_TRY(c, hipGetLastError());
+	uint32_t const lo_last = (W.nwin - 1u) * W.wb;
+	W.col_lo = (uint64_t) lo_last * c->B; W.col_hi = n;
+	if (c->tune.debug)
+		fprintf(stderr, "[fseq] list windows: %u windows of %u blocks (%llu columns) + a halo of %u columns, %.2f GB of lists at X = %u\n", W.nwin, W.wb,
+		        (unsigned long long) W.wb * c->B, W.H, W.bytes / 1e9, c->X);
+	return FSEQ_OK;
+}
+
+// find_segments_greedy (lp.cc:335-390) when the lists are gone after a windowed pass 1: a second pass over the windows that
+// hold a traceback boundary's column rb - 1 writes their lists again (same plan, same kernels: the same lists), takes the
+// thresholds of the window's boundaries (k_seg_tau), advances the walk over them -- current_lb depends on earlier boundaries
+// only -- and counts the merged size at every boundary that joins the segment before it at the walk's current_lb
+// (k_seg_count; the last such count of a segment is its size).  *overflow: a list ended before a threshold could be told.
+int merge_windowed(fseq_ctx *c, bool *overflow)
+{
+	FSEQ_LONG_LOCALS(c);
+	fseq_ctx::ListWindows &W = c->lw;
+	size_t const S = c->traceback.size();
+	uint32_t const max_seg = c->traceback.back().segment_max_size;
+	if (c->cols_cap < 2 * S) { if ((rc = dev_alloc(c, &c->d_cols, 2 * S))) return rc; c->cols_cap = 2 * S; }
+	if (c->tau_cap < S) { if ((rc = dev_alloc(c, &c->d_tau, S))) return rc; c->tau_cap = S; }
+	if ((rc = pin_reserve(c, S * 28 + 256))) return rc;
+	uint64_t *const qc = pin_take<uint64_t>(c, 2 * S);
+	uint2 *const tau = pin_take<uint2>(c, S);
+	uint32_t *const cnt = pin_take<uint32_t>(c, S);
+	std::vector<uint32_t> size_at(S, 0);                 // merged size at boundary j (for the boundaries that join)
+	struct Pending { size_t seg, j; };
+	std::vector<Pending> ask;
+	uint64_t current_lb = 0;
+	uint64_t prev_size = c->traceback[0].segment_size;
+	bool prev_size_pending = false;
+	size_t prev = 0, j = 1;
+	auto emit = [&]() {
+		if (prev_size_pending) ask.push_back(Pending{c->segments.size(), prev});
+		c->segments.push_back(fseq_segment{current_lb, c->traceback[prev].rb, (uint32_t) prev_size, 0});
+	};
+	W.merge_windows = 0;
+	for (uint32_t lo = 0; lo < c->nblocks && j < S; lo += W.wb)
+	{
+		uint32_t const hi = std::min(c->nblocks, lo + W.wb);
+		uint64_t const col_lo = (uint64_t) lo * c->B, col_hi = std::min<uint64_t>(n, (uint64_t) hi * c->B);
+		size_t j_hi = j;
+		while (j_hi < S && c->traceback[j_hi].rb - 1 < col_hi) ++j_hi;
+		if (j_hi == j) continue;                          // (no boundary in this window: its lists are not needed)
+		set_list_window(c, lo);
+		W.col_lo = W.col_hi = 0;                          // (the buffer is being rewritten)
+		if ((rc = window_phase_c(c, lo, hi))) return rc;
+		++W.merge_windows;
+		size_t const q = j_hi - j;
+		for (size_t i = 0; i < q; ++i) qc[i] = c->traceback[j + i].rb - 1;
+		HIP_TRY(c, hipMemcpyAsync(c->d_cols, qc, q * 8, hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_seg_tau, dim3((uint32_t) q), dim3(64), 0, st, c->d_cols, col_lo, col_hi, max_seg, c->stride, c->d_ent, c->d_hdr, c->d_tau);
+		HIP_TRY(c, hipMemcpyAsync(tau, c->d_tau, q * sizeof(uint2), hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipStreamSynchronize(st));
+		HIP_TRY(c, hipGetLastError());
+		W.col_lo = col_lo; W.col_hi = col_hi;
+		// the walk over this window's boundaries; the joins ask for the count at their column with the current_lb of the moment
+		size_t nq = 0;
+		for (; j < j_hi; ++j)
+		{
+			uint2 const t = tau[j - (j_hi - q)];
+			bool const fits = t.y != SEG_TAU_NEVER && current_lb >= t.x;
+			if (!fits && t.y == SEG_TAU_OPEN) { *overflow = true; return FSEQ_OK; }     // the list ended before it could tell
+			if (fits)
+			{
+				prev_size_pending = true;                      // prev_size = the count at boundary j (:366)
+				qc[nq] = c->traceback[j].rb - 1; qc[S + nq] = current_lb; cnt[nq] = (uint32_t) j; ++nq;
+			}
+			else
+			{
+				emit();
+				prev_size = c->traceback[j].segment_size;
+				prev_size_pending = false;
+				current_lb = c->traceback[prev].rb;
+			}
+			prev = j;
+		}
+		if (nq)
+		{
+			std::vector<uint32_t> const js(cnt, cnt + nq);
+			HIP_TRY(c, hipMemcpyAsync(c->d_cols, qc, nq * 8, hipMemcpyHostToDevice, st));
+			HIP_TRY(c, hipMemcpyAsync(c->d_cols + nq, qc + S, nq * 8, hipMemcpyHostToDevice, st));
+			uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->d_tau);
+			hipLaunchKernelGGL(k_seg_count, dim3((uint32_t) nq), dim3(64), 0, st, c->d_cols, c->d_cols + nq, col_lo, col_hi, c->stride, c->d_ent, c->d_hdr, d_cnt);
+			HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, nq * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipStreamSynchronize(st));
+			HIP_TRY(c, hipGetLastError());
+			for (size_t i = 0; i < nq; ++i) size_at[js[i]] = cnt[i];
+		}
+	}
+	if (j < S) return fail(c, FSEQ_E_HIP, "internal: a traceback boundary lies in no list window");
+	emit();
+	for (Pending const &a : ask) c->segments[a.seg].segment_size = size_at[a.j];
+	if (c->tune.debug) fprintf(stderr, "[fseq] merge: %u of %u list windows written again\n", W.merge_windows, W.nwin);
+	return FSEQ_OK;
+}
+
 int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 {
 	FSEQ_LONG_LOCALS(c);
@@ -2033,6 +2307,9 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 	bool const red_candidate = !c->tune.no_reduced && n >= 2 * L;
 	double const t_att = now_ms();
 	auto mark = [&](char const *what) { if (c->tune.debug) fprintf(stderr, "[fseq]   attempt +%.3f ms %s\n", now_ms() - t_att, what); };
+	// a list budget the lists at this capacity exceed: pass 1 and the DP in column windows (long_windows_cd)
+	if ((rc = plan_list_windows(c, X))) return rc;
+	bool const windowed = c->lw.on;
 	if ((rc = ensure_work_buffers(c, X, !red_candidate))) return rc;
 	mark("lists allocated");
 	// ---- phase C + D
@@ -2044,7 +2321,7 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 	if (c->tune.poison_lists)
 	{
 		// tests of the DP-beside-phase-C forms: a list read before it is written must not look right by accident
-		HIP_TRY(c, hipMemsetAsync(c->d_ent_alloc, 0xFF, ((size_t) (held_hi(c) - held_lo(c)) * c->stride + 256) * sizeof(uint2), st));
+		HIP_TRY(c, hipMemsetAsync(c->d_ent_alloc, 0xFF, c->lw.ent_count * sizeof(uint2), st));
 		HIP_TRY(c, hipMemsetAsync(c->d_hdr, 0xFF, (size_t) n * sizeof(uint4), st));
 	}
 	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
@@ -2052,34 +2329,11 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 	// inputs too short for three chunks (and FSEQ_DP_SERIAL).  [r5] the forms that ran the serial DP beside phase C (in parts, or
 	// fed by host-visible flags) are gone: no default reached them
 	SpecPlan const spec = spec_plan(c, S);
-	bool const use_spec = sharded || spec.nchunks() > 0;
+	bool const use_spec = !windowed && (sharded || spec.nchunks() > 0);
 	if (sharded && spec.nchunks() < 1) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: no DP chunk plan");
-	// columns phase C covers here: all, or my blocks plus the halo block's first columns (the lists my last DP round reads)
-	uint64_t const n_c = sharded ? sh.c_end : n;
 	uint32_t spec_overflow = 0, spec_sweeps = 0;
 	HIP_TRY(c, hipEventRecord(c->ev[3], st));
 	RangeScope range_cd("fseq pass 1: phases C + D (column updates + lists, segmentation DP)");
-	// (list [r5]: workgroup i owns block list[i] instead of b0 + i -- the blocks the reduced phase C hands to the run on all rows)
-	auto launch_columns = [&](uint32_t b0, uint32_t nb, uint32_t *done = nullptr, uint32_t epoch = 0, uint32_t const *list = nullptr) {
-		if (c->use_stream && c->s2.T)
-		{
-			uint32_t pack_abits = 0;
-			if (c->s2.pack) { pack_abits = 1; while ((1u << pack_abits) < m) ++pack_abits; }
-			hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws_c, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
-			                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
-			c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
-			             c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack | (c->ss_ids ? S2_SS_IDS : 0u), list);
-		}
-		else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan)
-			hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
-			                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
-		else if (c->use_stream)
-			hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
-			                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
-		else
-			ks.columns(st, nb, c->lds_columns, c->d_msa, c->ld, m, n_c, c->B, c->N2, c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->npass, c->bsh,
-			           c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->colmask_ready && c->colmask_use ? c->d_colmask : (uint32_t const *) nullptr, list);
-	};
 	{
 		if (use_spec)
 		{
@@ -2096,22 +2350,27 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 			if (use)
 			{
 				c->red_active = true;
-				if ((rc = red_columns(c))) return rc;
-				mark("reduced columns queued");
-				// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
-				if (c->red_nfull) launch_columns(0, c->red_nfull, nullptr, 0, c->d_red_blocks + c->red_full_at);
-				// sharded: the block behind mine for as far as the halo reaches, on all rows (k_columns stops at n_c)
-				if (sharded && sh.c_end > sh.c_hi) launch_columns(b_hi, 1u);
+				if (!windowed)
+				{
+					if ((rc = red_columns(c))) return rc;
+					mark("reduced columns queued");
+					// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
+					if (c->red_nfull) launch_columns(c, 0, c->red_nfull, nullptr, 0, c->d_red_blocks + c->red_full_at);
+					// sharded: the block behind mine for as far as the halo reaches, on all rows (k_columns stops at n_c)
+					if (sharded && sh.c_end > sh.c_hi) launch_columns(c, b_hi, 1u);
+				}
 			}
 			else if ((rc = ensure_work_buffers(c, X, true))) return rc;      // (the stride states after all)
 		}
-		if (!sharded && !c->red_active) launch_columns(0, c->nblocks);
+		if (!sharded && !c->red_active && !windowed) launch_columns(c, 0, c->nblocks);
+		// (windows: phase C of a window, then the DP rounds its lists feed -- the DP is queued here, inside phase C's events)
+		if (windowed && (rc = long_windows_cd(c, S))) return rc;
 		if (sync_at(c, 'C')) { fprintf(stderr, "[fseq] phase C queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase C done\n"); }
 		if (sharded && my_blocks && !c->red_active)
 		{
 			// my blocks, and the block behind them for as far as the halo reaches (k_columns stops at n_c)
 			uint32_t const nb = my_blocks + ((sh.c_end > sh.c_hi) ? 1u : 0u);
-			launch_columns(b_lo, nb);
+			launch_columns(c, b_lo, nb);
 		}
 		if (sharded && red_candidate)
 		{
@@ -2156,7 +2415,7 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 			HIP_TRY(c, hipStreamWaitEvent(st, c->ev_part[15], 0));      // the DP arrays were reset beside phase C
 			if ((rc = run_dp_spec(c, S, spec, st, &spec_overflow, &spec_sweeps, true))) return rc;
 		}
-		else
+		else if (!windowed)
 			hipLaunchKernelGGL(k_dp<DP_WHOLE>, dim3(1), dim3(1024), dp_lds_bytes(), st, c->dp, c->d_ent, c->d_hdr, c->stride, m, (uint32_t) n, (uint32_t) L,
 			                   c->d_flags, 0u, S.nrounds, DpSpecArgs{});
 		HIP_TRY(c, hipEventRecord(c->ev_dp[1], st));
@@ -2212,6 +2471,12 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 		float f = 0;
 		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[3], c->ev[4])); ms_c += f;
 		HIP_TRY(c, hipEventElapsedTime(&f, c->ev_dp[0], c->ev_dp[1])); ms_dp += f;
+		for (uint32_t w = 0; windowed && w < c->lw.nwin; ++w)
+		{
+			// (the windows' DP launches ran between phase C's events)
+			HIP_TRY(c, hipEventElapsedTime(&f, c->lw.ev[2 * (size_t) w], c->lw.ev[2 * (size_t) w + 1]));
+			ms_c -= f; ms_dp += f;
+		}
 	}
 #ifdef FSEQ_DP_STAMPS
 	{
@@ -2827,6 +3092,7 @@ void fseq_destroy(fseq_ctx *c)
 	for (auto &e : c->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_part) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_dp) if (e) (void) hipEventDestroy(e);
+	for (auto &e : c->lw.ev) if (e) (void) hipEventDestroy(e);
 	if (c->h_pin) (void) hipHostFree(c->h_pin);
 	if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);
 	if (c->h_red_pin2) (void) hipHostFree(c->h_red_pin2);
@@ -2955,6 +3221,7 @@ int fseq_set_shard(fseq_ctx *c, uint32_t rank, uint32_t world, void *xbuf_device
 	if (!c || 0 == world || rank >= world) return FSEQ_E_ARG;
 	if (c->have_input) return fail(c, FSEQ_E_ARG, "fseq_set_shard must be called before the input is set");
 	if (1 == world) { c->sh = Shard{}; return FSEQ_OK; }
+	if (c->lw.budget) return fail(c, FSEQ_E_UNSUPPORTED, "a list memory budget (fseq_set_list_memory) holds one GPU's lists in windows: not for sharded runs");
 	if (!xbuf_device || !fn) return fail(c, FSEQ_E_ARG, "sharded run: exchange buffer and all-reduce function needed");
 	if (c->p.n < 2 * c->p.segment_length) return fail(c, FSEQ_E_UNSUPPORTED, "the short path (n < 2L) is one sweep and does not shard");
 	Shard sh;
@@ -3064,6 +3331,7 @@ int fseq_run_segmentation(fseq_ctx *c, fseq_result *res)
 	(void) hipSetDevice(c->p.device);
 	c->have_result = false;
 	c->sh.closed = false;
+	c->lw.on = false; c->lw.merge_windows = 0;
 	if (!c->kernels_ready)
 	{
 		int rc = prepare_geometry(c);
@@ -3113,6 +3381,14 @@ int fseq_set_memory_budget(fseq_ctx *c, uint64_t bytes)
 {
 	if (!c) return FSEQ_E_ARG;
 	c->mem_budget = bytes;
+	return FSEQ_OK;
+}
+
+int fseq_set_list_memory(fseq_ctx *c, uint64_t bytes)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "a list memory budget holds one GPU's lists in windows: not for sharded contexts");
+	c->lw.budget = bytes;
 	return FSEQ_OK;
 }
 
@@ -3247,6 +3523,7 @@ int fseq_debug_column_list(fseq_ctx *c, uint64_t col, uint32_t *values, uint32_t
                            uint32_t *n_entries, uint32_t *cnt0, uint32_t *complete)
 {
 	if (!c || !c->have_result || c->res.short_path || col >= c->p.n) return FSEQ_E_ARG;
+	if (c->lw.on && (col < c->lw.col_lo || col >= c->lw.col_hi)) return fail(c, FSEQ_E_ARG, "the list of this column is not held: the run kept its lists in windows (fseq_set_list_memory)");
 	(void) hipSetDevice(c->p.device);
 	uint4 h;
 	HIP_TRY(c, hipMemcpy(&h, c->d_hdr + col, sizeof(h), hipMemcpyDeviceToHost));
@@ -3260,6 +3537,18 @@ int fseq_debug_column_list(fseq_ctx *c, uint64_t col, uint32_t *values, uint32_t
 	if (n_entries) *n_entries = h.x;
 	if (cnt0) *cnt0 = h.y;
 	if (complete) *complete = h.z;
+	return FSEQ_OK;
+}
+
+int fseq_debug_list_windows(fseq_ctx *c, uint64_t *bytes_held, uint64_t *columns_per_window, uint32_t *windows, uint32_t *merge_windows)
+{
+	if (!c || !c->have_result) return FSEQ_E_ARG;
+	fseq_ctx::ListWindows const &W = c->lw;
+	bool const lists = !c->res.short_path;
+	if (bytes_held) *bytes_held = W.on ? W.bytes : lists ? (uint64_t) W.ent_count * sizeof(uint2) : 0;
+	if (columns_per_window) *columns_per_window = W.on ? (uint64_t) W.wb * c->B : lists ? held_hi(c) - held_lo(c) : 0;
+	if (windows) *windows = W.on ? W.nwin : lists ? 1u : 0u;
+	if (merge_windows) *merge_windows = W.on ? W.merge_windows : 0u;
 	return FSEQ_OK;
 }
 

@@ -238,6 +238,18 @@ struct fseq_ctx {
 	std::unordered_map<void *, size_t> alloc_sizes;   // device allocations of this context (dev_alloc / dev_free)
 	size_t alloc_total = 0;
 	uint64_t mem_budget = 0;                  // fseq_set_memory_budget: 0 = whatever is free on the device
+	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_api.hip, plan_list_windows).  The buffer
+	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent = d_ent_alloc - (lo_w B - H) stride.
+	struct ListWindows {
+		uint64_t budget = 0;                  // bytes (0: every list held, the default)
+		bool on = false;                      // the last long-path run went through windows
+		uint32_t wb = 0, H = 0, nwin = 0;     // blocks per window, halo columns, windows
+		uint32_t merge_windows = 0;           // windows the merge's second pass ran phase C on again
+		uint64_t bytes = 0;                   // the list buffer's size
+		uint64_t col_lo = 0, col_hi = 0;      // columns whose lists the buffer holds now (fseq_debug_column_list)
+		size_t ent_count = 0;                 // entries d_ent_alloc was allocated with
+		std::vector<hipEvent_t> ev;           // per window: DP begin / end
+	} lw;
 	std::atomic<uint64_t> step_max{0}, current_step{0};      // fseq_step_max / fseq_current_step (segmentation_lp_context.hh:122-127)
 	fseq_join_profile jp{};                  // the last joiner call (fseq_get_join_profile)
 	fseq_progress_fn progress_fn = nullptr;

@@ -11,6 +11,8 @@
 
 #include <getopt.h>
 
+#include <cctype>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +46,9 @@ char const *const USAGE =
 	"      --random-seed=LONG             Seed for the random number generator  (default=`0')\n"
 	"      --single-threaded              Use only one worker thread  (default=off)\n"
 	"      --print-invocation             Print the command line arguments to stderr  (default=off)\n"
-	"      --gpus=N                       Shard the alignment over the first N GPUs of this node (RCCL)  (default=`1')\n";
+	"      --gpus=N                       Shard the alignment over the first N GPUs of this node (RCCL)  (default=`1')\n"
+	"      --list-memory=MIB              Hold the per-column divergence lists in column windows of at most MIB MiB of device memory\n"
+	"                                     (one GPU only; results are the same)  (default=`0': every list held)\n";
 
 bool read_file(std::string const &path, std::string &out)
 {
@@ -106,6 +110,8 @@ int main(int argc, char **argv)
 	bool seg_len_given = false, single_threaded = false, print_invocation = false;
 	long gpus = 1;
 	bool gpus_given = false;
+	unsigned long long list_memory_mib = 0;
+	bool list_memory_bad = false;
 
 	static option const longopts[] = {
 		{"help", no_argument, nullptr, 'h'}, {"version", no_argument, nullptr, 'V'},
@@ -114,7 +120,7 @@ int main(int argc, char **argv)
 		{"segment-length-bound", required_argument, nullptr, 's'}, {"segment-joining", required_argument, nullptr, 'j'},
 		{"pbwt-sample-rate", required_argument, nullptr, 'm'}, {"random-seed", required_argument, nullptr, 1000},
 		{"single-threaded", no_argument, nullptr, 1001}, {"print-invocation", no_argument, nullptr, 1002},
-		{"gpus", required_argument, nullptr, 1003},
+		{"gpus", required_argument, nullptr, 1003}, {"list-memory", required_argument, nullptr, 1004},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -143,6 +149,15 @@ int main(int argc, char **argv)
 			case 1001: single_threaded = true; break;
 			case 1002: print_invocation = true; break;
 			case 1003: gpus = strtol(optarg, nullptr, 10); gpus_given = true; break;
+			case 1004:
+			{
+				// a whole number of MiB, digits only (strtoull would take "-1" as a huge value)
+				char *end = nullptr;
+				errno = 0;
+				list_memory_mib = strtoull(optarg, &end, 10);
+				list_memory_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || list_memory_mib > (~0ull >> 20);
+				break;
+			}
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -165,6 +180,8 @@ int main(int argc, char **argv)
 	{ std::cerr << "Random seed out of bounds." << std::endl; return EXIT_FAILURE; }
 	if (sample_rate <= 0) { std::cerr << "PBWT sample rate multiplier must be non-negative." << std::endl; return EXIT_FAILURE; }
 	if (gpus < 1 || gpus > 64) { std::cerr << "The number of GPUs must be positive." << std::endl; return EXIT_FAILURE; }
+	if (list_memory_bad) { std::cerr << "The list memory must be a non-negative number of MiB." << std::endl; return EXIT_FAILURE; }
+	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 
 	// generate_context.cc:64-106
 	std::cerr << "Loading the input…" << std::flush;
@@ -226,6 +243,7 @@ int main(int argc, char **argv)
 			if (FSEQ_OK != worst) return FSEQ_OK != rc_ ? rc_ : FSEQ_E_PEER;
 		}
 		else if (FSEQ_OK != rc_) return rc_;
+		if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(ctxs[r], (uint64_t) list_memory_mib << 20))) return rc_;
 		if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
 		return fseq_run_segmentation(ctxs[r], &results[r]);
 	};

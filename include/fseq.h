@@ -36,7 +36,9 @@ enum {
 	FSEQ_E_HIP          = 3,   /* HIP runtime error, see fseq_last_error */
 	FSEQ_E_OOM          = 4,   /* a device (or pinned host) allocation failed; fseq_last_error has the sizes.  Typically the
 	                            * per-column lists of a very diverse input: n x (X + 3) x 8 bytes at list capacity X (DESIGN.md
-	                            * section 7).  Nothing was written; other contexts of the process are not affected */
+	                            * section 7).  Nothing was written; other contexts of the process are not affected.
+	                            * fseq_set_list_memory bounds what the lists of a run may take (the run then holds them in column
+	                            * windows); a budget too small for one window fails with this code and names the bytes needed */
 	FSEQ_E_UNSUPPORTED  = 5,   /* shape outside what this build's kernels cover (fails loudly, no CPU fallback) */
 	FSEQ_E_PEER         = 6    /* sharded run: another rank failed; every rank returns from the same exchange */
 };
@@ -303,6 +305,23 @@ uint64_t fseq_current_step(fseq_ctx const *ctx);
 /* A context that shares its device with other contexts or ranks keeps its device allocations -- the pass-2 stride
  * states are sized from what is free -- inside `bytes` in all (0 = whatever is free on the device, the default). */
 int  fseq_set_memory_budget(fseq_ctx *ctx, uint64_t bytes);
+
+/* Device memory the per-column divergence lists of a long-path run may occupy: the list ring and its halo, not the
+ * per-column headers (16 bytes a column) or the DP arrays.  0 (the default): every list is held until the merge walk is
+ * done, n x (X + 3) x 8 bytes at list capacity X.  Otherwise, when those do not fit the budget, pass 1 and the DP run in
+ * windows of consecutive column blocks: a window's lists are written, the DP rounds they feed run, and the next window
+ * takes their place (the few columns the next rounds still read move to the front); the merge walk then takes its
+ * thresholds in a second pass over the windows, which writes the same lists again.  Results are the same bit for bit as
+ * without a budget; the time is that of about one more phase C plus the DP in one serial launch per window.  A budget that
+ * cannot hold one column block plus the halo at the list capacity in use -- also one grown by a retry -- makes the run
+ * return FSEQ_E_OOM with the bytes needed; the context stays usable.  The setting persists for later runs on the context;
+ * the short path (n < 2L) ignores it; a sharded context (fseq_set_shard, before or after) returns FSEQ_E_UNSUPPORTED.
+ * The reference's knob for memory against time is --pbwt-sample-rate (generate_context.cc:121-124): it keeps one
+ * column's divergence_value_counts live (segmentation_lp_context.cc:78,119) and a pBWT sample every q sqrt(n) columns,
+ * from which its later steps replay columns.  This engine keeps an exact (a, d) state every block_len columns whatever
+ * that rate is (fseq_params.pbwt_sample_rate is accepted and not used), so the samples are not the memory that grows with
+ * the input's diversity: the lists are, and this budget is what bounds them, at the price of replaying phase C once. */
+int  fseq_set_list_memory(fseq_ctx *ctx, uint64_t bytes);
 
 #ifdef __cplusplus
 }

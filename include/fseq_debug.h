@@ -27,6 +27,12 @@ int  fseq_debug_block_state(fseq_ctx *ctx, uint64_t block_idx, uint32_t *a_out, 
  * *n_entries, *cnt0 (count of value 0) and *complete (list reaches the smallest value). */
 int  fseq_debug_column_list(fseq_ctx *ctx, uint64_t c, uint32_t *values, uint32_t *counts,
                             uint32_t *n_entries, uint32_t *cnt0, uint32_t *complete);
+/* What the last run did with the lists (fseq_set_list_memory): bytes of device memory the list buffer held, columns of a
+ * window (n when every list was held), windows of pass 1 (1: every list held; 0: short path) and windows the merge's second
+ * pass ran again.  After a windowed run only the lists of the window last held are there: fseq_debug_column_list returns
+ * FSEQ_E_ARG for any other column. */
+int  fseq_debug_list_windows(fseq_ctx *ctx, uint64_t *bytes_held, uint64_t *columns_per_window, uint32_t *windows,
+                             uint32_t *merge_windows);
 
 /* The restated rmq.hh (rmq<..., 64>, include/founder_sequences/rmq.hh:61-118, quirks included) on caller-supplied
  * keys, straight on the device routines the DP uses (debug / tests): the stack masks and the sparse table are

@@ -8,6 +8,7 @@ whether the reference would give up (FSEQ_E_NO_REDUCTION, generate_context.cc:19
     python tools/diversity_sweep.py > profiles/r04_diversity_sweep.txt
     python tools/diversity_sweep.py C3 --quick      # fewer points
     python tools/diversity_sweep.py C4 --K=64,1024,4096 --mu=5e-5,1e-3      # chosen points (C4's shape with more founders)
+    python tools/diversity_sweep.py C4 --K=64,1024,4096 --mu=5e-5,2e-4,1e-3 --list-memory=64   # lists in windows of <= 64 GiB
 """
 import importlib
 import json
@@ -21,13 +22,27 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
         sys.path.insert(0, p)
 
 
+def windows_note(ctx):
+    try:
+        w = ctx.list_windows()
+    except Exception:                                              # (no result: the run failed)
+        return ""
+    return " | windows %d of %d columns, %.2f GB held, merge pass %d windows" % (w["windows"], w["columns_per_window"], w["bytes_held"] / 1e9, w["merge_windows"])
+
+
 def main():
     import torch
     import bench
     pkg = importlib.import_module("founder-sequences_amd")
     which = [a for a in sys.argv[1:] if not a.startswith("-")] or ["C3", "C5"]
     quick = "--quick" in sys.argv
+    list_memory = 0                                                # --list-memory=GB (GiB): fseq_set_list_memory
+    for a in sys.argv[1:]:
+        if a.startswith("--list-memory="):
+            list_memory = int(float(a[len("--list-memory="):]) * (1 << 30))
     print("# tools/diversity_sweep.py on kernel sources %s; one MI355X; step = pass 1 + DP + traceback + merge + pass 2 (bench.py's metric)" % bench.csrc_sha())
+    if list_memory:
+        print("# list budget %.0f GiB (fseq_set_list_memory): 'list GB' is what every list would take; 'windows' what the runs held" % (list_memory / (1 << 30)))
     print("# columns: workload K mu | ms/step (x the K = bench point) | A B C D pass2 host ms | X retries dp_sweeps phase_a_fallbacks, blocks the tree gave to the sweep / the trie gave to the tree | "
           "max_segment_size segments | list GB | status")
     for name in which:
@@ -45,7 +60,7 @@ def main():
         base_ms = None
         for K in Ks:
             for mu in mus:
-                ctx = pkg.SegmentationContext(m, n, L, device=0)
+                ctx = pkg.SegmentationContext(m, n, L, device=0, list_memory=list_memory)
                 ctx.generate_synthetic(w["seed"], K, w["B"], mu, w["kind"])
                 status = "ok"
                 t_first = time.perf_counter()
@@ -82,7 +97,8 @@ def main():
                       % (name, K, mu, ms, ms / base_ms if base_ms else float("nan"), first_ms,
                          acc.get("ms_phase_a", 0), acc.get("ms_phase_b", 0), acc.get("ms_phase_c", 0), acc.get("ms_dp", 0), acc.get("ms_pass2", 0), acc.get("ms_host", 0),
                          t["list_cap_used"], t_first_run["retries"], t["dp_sweeps"], t["phase_a_fallbacks"], t["phase_a_given_up"], t["phase_a_trie_given_up"],
-                         res.max_segment_size if res else -1, res.segment_count if res else -1, n * stride * 8 / 1e9, status), flush=True)
+                         res.max_segment_size if res else -1, res.segment_count if res else -1, n * stride * 8 / 1e9, status)
+                      + (windows_note(ctx) if list_memory else ""), flush=True)
                 ctx.close()
                 del ctx
                 torch.cuda.empty_cache()
