@@ -61,7 +61,8 @@ constexpr uint64_t STREAM_BLOCK_TARGET_ALL_ROWS = 1600;   // columns per block t
 // [r5] ... and when phase C runs on the blocks' representatives: a block of ~800 columns of BASELINE C4 has ~6,600 of them, and
 // the ~10,700 of a block in which the founders recombine still fit the largest configuration (11,264)
 constexpr uint64_t STREAM_BLOCK_TARGET_REDUCED = 800;
-#define STREAM_BLOCK_TARGET (c->tune.no_reduced ? STREAM_BLOCK_TARGET_ALL_ROWS : (c->tune.stream_block ? (uint64_t) c->tune.stream_block : STREAM_BLOCK_TARGET_REDUCED))
+constexpr size_t RED_SIDE_STREAMS = 3;                    // side streams the reduced configurations' launches may use (red_launch_all)
+#define STREAM_BLOCK_TARGET (c->tune.no_reduced ? STREAM_BLOCK_TARGET_ALL_ROWS : STREAM_BLOCK_TARGET_REDUCED)
 #ifndef FSEQ_X_FLOOR_VALUE
 #define FSEQ_X_FLOOR_VALUE 63u
 #endif
@@ -156,7 +157,7 @@ void block_geometry(fseq_ctx *c)
 		// (the second form of the streamed phase C runs -- and was tuned for -- two workgroups per CU: a rank's blocks are whole
 		// rounds of 2 x CUs workgroups, also when one workgroup per CU would hold its columns: BASELINE C4 on 8 ranks is 512
 		// blocks of 1,221 columns per rank, not 256 of 2,442 with every CU's second slot empty)
-		if ((k & 1u) && (uint64_t) p.m + 4096u < (1ull << 19) && !c->tune.stream_plain_scan && c->tune.stream2 != "0") ++k;
+		if ((k & 1u) && (uint64_t) p.m + 4096u < (1ull << 19) && !c->tune.stream_plain_scan) ++k;
 		uint64_t per = streamed ? (uint64_t) ncu * k : 1024u;
 		uint64_t b = (p.n + per * sh.world - 1) / (per * sh.world);
 		if (b < 16) b = 16;
@@ -227,7 +228,7 @@ void block_geometry(fseq_ctx *c)
 		// every chain's last on the way down: ~N (2g - 1) / (g - 1)) against the rounds of launches, (2g - 1) per level.
 		// BASELINE C4 (6,143 blocks, 100,000 rows), phase B: fan 3: 69.6 ms, 4: 61.6, 6: 56.5, 8: 54.1, 12: 50.9, 16: 53.7, 32: 57.5
 		KernelSet probe;
-		if (!select_kernels(p.m, c->sigma, &probe, c->tune.no_emitter_wave) && c->nblocks > 8)
+		if (!select_kernels(p.m, c->sigma, &probe) && c->nblocks > 8)
 		{
 			double best = 1e300;
 			for (uint32_t g = 2; g <= 64 && g < c->nblocks; ++g)
@@ -246,7 +247,6 @@ void block_geometry(fseq_ctx *c)
 			}
 		}
 		if (c->nblocks <= 8) best_g = std::max(1u, c->nblocks);        // one chain
-		if (c->tune.two_level_chain) best_g = std::max(2u, (uint32_t) std::ceil(std::sqrt((double) c->nblocks)));
 		if (c->tune.chain_fan) best_g = (uint32_t) c->tune.chain_fan;
 		c->chain_fan = best_g;
 		c->chain_G = best_g; c->n_super = (c->nblocks + best_g - 1) / best_g;      // (diagnostics)
@@ -269,7 +269,7 @@ int prepare_geometry(fseq_ctx *c)
 		c->npass = (bits + 1) / 2;               // 2-bit digit passes per column
 	}
 	if (c->sigma > 256) return fail(c, FSEQ_E_UNSUPPORTED, "alphabet larger than 256 symbols");
-	c->use_stream = !select_kernels(p.m, c->sigma, &c->ks, c->tune.no_emitter_wave);
+	c->use_stream = !select_kernels(p.m, c->sigma, &c->ks);
 	if (c->use_stream)
 	{
 		// rows beyond the LDS-resident configurations: the order streams through HBM / L2
@@ -284,20 +284,14 @@ int prepare_geometry(fseq_ctx *c)
 		HIP_TRY(c, allow_lds(k_colblock_stream<MODE_SNAP, true>, lds));
 		HIP_TRY(c, allow_lds(k_columns_stream<19>, lds));
 		HIP_TRY(c, allow_lds(k_columns_stream<0>, lds));
-		HIP_TRY(c, allow_lds(k_chain_stream<false>, stream_lds_bytes(0, true)));
-		HIP_TRY(c, allow_lds(k_chain_stream<true>, stream_lds_bytes(0, true)));
-		HIP_TRY(c, allow_lds(k_chain_stream_sort, chainsort_lds_bytes()));
 		HIP_TRY(c, allow_lds(k_chain_snap_stream, chainsort_lds_bytes()));
 		HIP_TRY(c, allow_lds(k_cm_emit, stream_lds_bytes(0, false)));
-		// phase C in its second form (fseq_stream2.hpp) while every value id (< m + B) fits the key shift of its tile
-		// (FSEQ_STREAM2=T,E[,0] picks another configuration [8-byte rows], FSEQ_STREAM2=0 and FSEQ_STREAM_PLAIN_SCAN keep the first form)
+		// phase C in its second form (fseq_stream2.hpp) while every value id (< m + B) fits the key shift of its tile and the
+		// column is staged (FSEQ_STREAM_PLAIN_SCAN keeps the first form)
 		c->s2 = Stream2Config{};
 		{
-			uint32_t T2 = 512, E2 = 8, P2 = 1;
-			bool off = c->tune.stream_plain_scan;
-			if (!c->tune.stream2.empty() && sscanf(c->tune.stream2.c_str(), "%u,%u,%u", &T2, &E2, &P2) < 2) off = true;
-			Stream2Config cfg;
-			if (!off && select_stream2(T2, E2, P2, &cfg) && (uint64_t) p.m + c->B < (1ull << cfg.key_shift) && c->stream_staged)
+			Stream2Config const cfg = stream2_config();
+			if (!c->tune.stream_plain_scan && (uint64_t) p.m + c->B < (1ull << cfg.key_shift) && c->stream_staged)
 			{
 				size_t const bytes = cfg.lds(sym_bytes(p.m, c->bsh));
 				if (bytes <= LDS_LIMIT)
@@ -473,12 +467,9 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		c->d_ws_c = c->d_ws - bl * columns_stream_ws_words(p.m, c->B);
 		// phase B spread over the chip: the digit histograms of every part of every chain of a launch (the widest launch of the
 		// recursion has a chain per chain_fan blocks; a sharded rank's own range the same)
-		if (!c->tune.chain_stream_passes && !c->tune.chain_stream_single && p.m < (1u << 20))
-		{
-			size_t const chains = std::max<size_t>(1, (bh - bl + std::max(2u, c->chain_fan) - 1) / std::max(2u, c->chain_fan) + 1);
-			c->cshist_words = chains * chainmulti_parts(p.m) * CS_BINS;
-			if ((rc = dev_alloc(c, &c->d_cshist, c->cshist_words))) return rc;
-		}
+		// (streamed rows are < 2^20: one packed column fits STREAM_MAX_COLBYTES, so m <= 4 x 147,456 = 589,824)
+		size_t const chains = std::max<size_t>(1, (bh - bl + std::max(2u, c->chain_fan) - 1) / std::max(2u, c->chain_fan) + 1);
+		if ((rc = dev_alloc(c, &c->d_cshist, chains * chainmulti_parts(p.m) * CS_BINS))) return rc;
 	}
 	uint64_t const k_lo = held_lo(c), k_cnt = held_hi(c) - k_lo;      // sharded: lists and stride states of my columns only
 	// (a list budget: the H + wb B columns of one window, plan_list_windows)
@@ -515,7 +506,7 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 			if (abits + dbits <= 40 && abits < 32) c->ss_pack = abits;
 			// second form of the streamed phase C on packed rows: the states in id form (its packed rows as they are: a row id and
 			// a value id below 2^19 always fit 40 bits), pass 2 on the same tile step
-			if (c->s2.T && c->s2.pack && c->s2.launch_snap && !c->tune.ss_absolute) { c->ss_pack = abits; c->ss_ids = true; }
+			if (c->s2.T && !c->tune.ss_absolute) { c->ss_pack = abits; c->ss_ids = true; }
 		}
 		if (c->ss_ids && !c->d_bs_w)
 		{
@@ -544,7 +535,6 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		// twice the price there, a state costs phase C the same: BASELINE C5 pass 2 4.3 -> 2.3 ms, phase C 36.7 -> 36.9;
 		// sigma <= 4: BASELINE C3 8.7 / 8.6 / 8.6 / 8.7 ms for 8 / 12 / 16 / 24)
 		uint64_t st_ = (c->npass >= 2 && !c->use_stream) ? 8 : 16;
-		if (c->tune.snap_stride) st_ = (uint64_t) c->tune.snap_stride;     // (experiments: first stride tried)
 		// the smallest stride >= 16 whose states fit (any number, not a power of two: pass 2 costs ~stride / 2 columns per boundary)
 		if ((k_cnt / st_ + 2) * state_bytes > budget) st_ = std::max<uint64_t>(st_, (k_cnt * state_bytes + budget - 1) / std::max<uint64_t>(1, budget - 2 * state_bytes));
 		while ((k_cnt / st_ + 2) * state_bytes > budget) ++st_;
@@ -587,7 +577,7 @@ void free_work(fseq_ctx *c)
 	dev_free(c, &c->d_cols); dev_free(c, &c->d_grp); dev_free(c, &c->d_src); dev_free(c, &c->d_ss_a_alloc); dev_free(c, &c->d_ss_d_alloc); c->d_ss_a = c->d_ss_d = nullptr;
 	dev_free(c, &c->d_bs_w_alloc); dev_free(c, &c->d_bs_h_alloc); c->d_bs_w = nullptr; c->d_bs_h = nullptr; dev_free(c, &c->d_wgblk); dev_free(c, &c->d_wggrp); c->wg_cap = 0;
 	dev_free(c, &c->d_gent); dev_free(c, &c->d_ghdr);
-	dev_free(c, &c->d_snap_a); dev_free(c, &c->d_snap_d); dev_free(c, &c->d_ws); c->d_ws_c = nullptr; dev_free(c, &c->d_cshist); c->cshist_words = 0;
+	dev_free(c, &c->d_snap_a); dev_free(c, &c->d_snap_d); dev_free(c, &c->d_ws); c->d_ws_c = nullptr; dev_free(c, &c->d_cshist);
 	c->cols_cap = c->gather_cap = c->snap_cap = c->grp_cap = c->src_cap = 0;
 	dev_free(c, &c->d_red_cnt); dev_free(c, &c->d_red_cnt_plan); c->red_plan_valid = false; c->red_declined = false; dev_free(c, &c->d_red_vmin); dev_free(c, &c->d_red_rows_alloc); dev_free(c, &c->d_red_leaf_alloc); dev_free(c, &c->d_red_a_alloc); dev_free(c, &c->d_red_d_alloc); c->d_red_rows = c->d_red_leaf = c->d_red_a = c->d_red_d = nullptr;
 	dev_free(c, &c->d_red_invalid); dev_free(c, &c->d_red_blocks); dev_free(c, &c->d_red_msa_alloc); c->d_red_msa = nullptr; c->red_cap = 0; c->red_blocks_cap = 0; c->red_ld = 0; c->red_msa_bytes = 0;
@@ -896,19 +886,19 @@ void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t con
                   uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t grp0 = 0)
 {
 	if (!grid) return;
-	// streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp) where the workspace holds its
-	// arrays for every workgroup of the launch; else (and with FSEQ_CHAIN_STREAM_PASSES) the two-bit digit passes
-	if (c->use_stream && !c->tune.chain_stream_passes && c->d_cshist && (size_t) grid * chainsort_ws_words(c->p.m) <= c->ws_words &&
-	    (size_t) grid * chainmulti_parts(c->p.m) * CS_BINS <= c->cshist_words)
+	// streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp), every sweep of a step a launch
+	// over (parts) x (chains): a chain of G blocks is G rounds of them.  ensure_work_buffers sized d_ws and d_cshist for the
+	// widest launch of phase B (a chain per chain_fan blocks, plus one, in d_cshist; chainsort_ws_words(m)
+	// <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
+	if (c->use_stream)
 	{
-		// ... every sweep of a step a launch over (parts) x (chains): a chain of G blocks is G rounds of them
 		uint32_t const m = c->p.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
 		ChainMultiArgs A;
 		A.rank = rank; A.keyd = keyd; A.nkeys = nkeys; A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block;
 		A.ws = c->d_ws; A.hist = c->d_cshist; A.start_a = start_a; A.start_d = start_d; A.out_state_a = out_a; A.out_state_d = out_d;
 		A.out_rank = out_rank; A.out_keyd = out_keyd; A.out_nkeys = out_nkeys; A.grp0 = grp0; A.step = 0; A.pass = 0;
-		A.nchains = grid; A.xcd_map = c->tune.chain_no_xcd_map ? 0u : 1u;
-		uint32_t const grid_y = A.xcd_map ? (grid + 7u) & ~7u : grid;       // (cm_wg: the workgroups of a chain on one XCD)
+		A.nchains = grid;
+		uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
 		dim3 const by_row((m + CM_WG - 1u) / CM_WG, grid_y), by_part((nparts + CM_WG / WAVE - 1u) / (CM_WG / WAVE), grid_y);
 		hipLaunchKernelGGL(k_cm_init, by_row, dim3(CM_WG), 0, c->stream, A);
 		for (uint32_t s_ = 0; s_ < G; ++s_)
@@ -925,12 +915,6 @@ void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t con
 		}
 		if (out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), c->stream, A, G);
 	}
-	else if (c->use_stream && !c->tune.chain_stream_passes && (size_t) grid * chainsort_ws_words(c->p.m) <= c->ws_words)
-		hipLaunchKernelGGL(k_chain_stream_sort, dim3(grid), dim3(ST), chainsort_lds_bytes(), c->stream, rank, keyd, nkeys, c->p.m, nb_total, G,
-		                   cols_per_block, c->d_ws, start_a, start_d, out_a, out_d, out_rank, out_keyd, out_nkeys, grp0);
-	else if (c->use_stream)
-		hipLaunchKernelGGL((stream_keyed(c) ? k_chain_stream<true> : k_chain_stream<false>), dim3(grid), dim3(ST), stream_lds_bytes(0, true), c->stream, rank, keyd, nkeys, c->p.m, nb_total, G,
-		                   cols_per_block, c->d_ws, 1u, start_a, start_d, out_a, out_d, out_rank, out_keyd, out_nkeys, grp0);
 	else
 		c->ks.chain(c->stream, grid, c->ks.lds_chain, rank, keyd, nkeys, c->p.m, nb_total, G, cols_per_block, start_a, start_d, out_a, out_d,
 		            out_rank, out_keyd, out_nkeys, grp0, scan_keyed(c));
@@ -1405,9 +1389,9 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	// The key-space tree hands the blocks whose merges would slice past their budget to the column sweep (fseq_blockkeys.hpp,
 	// BK_ABORT): per-block flags, the sweep launched over my blocks with the flags as its filter.  What the last run on this
 	// input saw decides what is launched now (the input has not changed, so neither has the outcome): no block given up ->
-	// the tree alone; most of them -> the sweep alone; else both.  FSEQ_BLOCKKEYS_CAP (tests of the slices) and
-	// FSEQ_BLOCKKEYS_NO_LIMIT: the tree slices as often as it takes.
-	bool const limited = keyspace && !c->tune.blockkeys_no_limit && !c->tune.blockkeys_cap;
+	// the tree alone; most of them -> the sweep alone; else both.  FSEQ_BLOCKKEYS_CAP (tests of the slices): the tree slices
+	// as often as it takes.
+	bool const limited = keyspace && !c->tune.blockkeys_cap;
 	bool const tree = keyspace && !(limited && c->bk_given_up >= 0 && 2u * (uint32_t) c->bk_given_up > my_blocks);
 	bool const sweep_after = limited && !(tree && c->bk_given_up == 0);
 	R.tree_alone = tree && limited && !sweep_after;
@@ -1877,11 +1861,11 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	{
 		(void) reduced_config(i, &sets[(size_t) i]);
 		ReducedSet const &rs = sets[(size_t) i];
-		// (small blocks: one-wave workgroups, or two with the list on a wave of its own: FSEQ_REDUCED_EW picks the latter; from 256
-		// threads on phase C takes the configurations with a list wave, pass 2's sweeps the others)
+		// (small blocks: one-wave workgroups for both; from 256 threads on phase C takes the configurations with a list wave,
+		// pass 2's sweeps the others)
 		bool const fit = columns_fit_reduced(c, rs, c->red_direct);
-		usable[(size_t) i] = fit && (rs.T > 128u ? rs.ew : rs.ew == c->tune.reduced_ew);
-		usable_snap[(size_t) i] = fit && (rs.T > 128u ? !rs.ew : rs.ew == c->tune.reduced_ew);
+		usable[(size_t) i] = fit && (rs.T <= 128u || rs.ew);
+		usable_snap[(size_t) i] = fit && !rs.ew;
 	}
 	std::vector<std::vector<uint32_t>> per((size_t) nconf);
 	uint32_t n_full = 0, max_rows = 0, listed = 0;
@@ -1989,10 +1973,9 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 {
 	FSEQ_LONG_LOCALS(c);
 	if (ls.empty()) return FSEQ_OK;
-	// (side streams: the context's second stream first -- every further hardware queue in use slows the dependent launches of
-	// phase B, measured on BASELINE C3: 0.71 ms with none, 0.97 with three)
-	size_t const want_side = c->tune.reduced_serial ? 0u : (c->tune.reduced_side >= 0 ? (size_t) c->tune.reduced_side : 3u);
-	size_t const nside = std::min<size_t>(ls.size() - 1, std::min<size_t>(want_side, 3));
+	// (up to RED_SIDE_STREAMS side streams, the context's second stream first -- every further hardware queue in use slows the
+	// dependent launches of phase B, measured on BASELINE C3: 0.71 ms with none, 0.97 with three)
+	size_t const nside = std::min<size_t>(ls.size() - 1, RED_SIDE_STREAMS);
 	if (nside) HIP_TRY(c, hipEventRecord(c->red_ev[3], st));
 	for (size_t i = 0; i < ls.size(); ++i)
 	{
@@ -2041,8 +2024,8 @@ void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = null
 	uint64_t const n_c = sharded ? sh.c_end : n;
 	if (c->use_stream && c->s2.T)
 	{
-		uint32_t pack_abits = 0;
-		if (c->s2.pack) { pack_abits = 1; while ((1u << pack_abits) < m) ++pack_abits; }
+		uint32_t pack_abits = 1;
+		while ((1u << pack_abits) < m) ++pack_abits;
 		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws_c, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
 		                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
 		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,

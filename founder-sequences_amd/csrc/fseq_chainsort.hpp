@@ -1,7 +1,7 @@
 // fseq_chainsort.hpp -- phase B for orders that do not fit LDS (m > 11,264 rows): one chain step as a stable radix
 // sort by the block rank plus range maxima, instead of ceil(log2(nkeys) / 2) two-bit partition passes.
 //
-// A chain step (k_chain / k_chain_stream, fseq_kernels.hpp) takes the order (a, d) in front of a key block
+// A chain step (k_chain, fseq_kernels.hpp, for LDS-resident rows) takes the order (a, d) in front of a key block
 // {rank[row], keyd[key], nkeys} to the order behind it: a' = the stable sort of a by rank[a]; the row at new position p
 // whose predecessor there has ANOTHER rank starts a block key and takes d' = keyd[rank]; a row whose predecessor has the
 // SAME rank was, in the old order, the next row of that rank behind it, at positions q < r, and takes
@@ -18,6 +18,8 @@
 //   3. every new position: its row, and keyd or the range maximum between the old positions of the two rows (two
 //      block-end look-ups and two table entries, or a scan of at most 63 values inside one block).
 // Everything but the histograms lives in the workgroup's workspace (L2-resident: a few MB).
+// Two forms of the step live here: chain_step_sorted, one step on one workgroup (pass 2's k_chain_snap_stream), and the
+// k_cm_* kernels, phase B's steps spread over the chip (launch_chain in fseq_api.hip, the only streamed phase B).
 #pragma once
 
 #include <type_traits>
@@ -246,56 +248,6 @@ __device__ __forceinline__ void chain_step_sorted(
 }
 
 // ------------------------------------------------------------------------------------------------
-// phase B, streamed, sorted form (same contract as k_chain_stream).  ws: [gridDim.x][chainsort_ws_words(m)] words.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ST) void k_chain_stream_sort(
-	uint32_t const *__restrict__ rank, uint32_t const *__restrict__ keyd, uint32_t const *__restrict__ nkeys,
-	uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t *ws,
-	uint32_t const *__restrict__ start_a, uint32_t const *__restrict__ start_d,
-	uint32_t *__restrict__ out_state_a, uint32_t *__restrict__ out_state_d,
-	uint32_t *__restrict__ out_rank, uint32_t *__restrict__ out_keyd, uint32_t *__restrict__ out_nkeys, uint32_t grp0)
-{
-	extern __shared__ __attribute__((aligned(16))) char smem[];
-	Carver cv{smem};
-	StreamLds &L = *cv.take<StreamLds>(1);
-	ChainSortLds &S = *cv.take<ChainSortLds>(1);
-	uint32_t const tid = threadIdx.x;
-	uint32_t *const w = ws + (size_t) blockIdx.x * chainsort_ws_words(m);
-	uint32_t const grp = blockIdx.x + grp0;                     // chain index (workspaces stay per workgroup)
-	uint32_t const b0 = grp * G;
-	uint32_t const b1 = min(nb_total, b0 + G);
-	uint32_t const kstart = (uint32_t) ((uint64_t) b0 * cols_per_block);
-	for (uint32_t i = tid; i < m; i += ST)
-	{
-		w[i] = start_a ? start_a[(size_t) grp * m + i] : i;
-		w[(size_t) m + i] = start_d ? start_d[(size_t) grp * m + i] : kstart;
-	}
-	__syncthreads();
-	uint32_t cur = 0;
-	for (uint32_t b = b0; b < b1; ++b)
-	{
-		uint32_t const *a = w + (size_t) cur * 2u * m, *d = a + m;
-		if (out_state_a)
-			for (uint32_t i = tid; i < m; i += ST) { out_state_a[(size_t) b * m + i] = a[i]; out_state_d[(size_t) b * m + i] = d[i]; }
-		if (b + 1 == b1 && !out_rank && b1 != nb_total) break;       // (an expansion's last step: k_chain, fseq_kernels.hpp)
-		{
-			uint32_t const nk = nkeys[b];
-			uint32_t kb = 1, pbits = 1;
-			while (kb < 32u && ((nk - 1u) >> kb) != 0u) ++kb;
-			while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
-			if (kb + pbits <= 32u) chain_step_sorted<true>(m, rank + (size_t) b * m, keyd + (size_t) b * m, nk, w, cur, S, L);
-			else chain_step_sorted<false>(m, rank + (size_t) b * m, keyd + (size_t) b * m, nk, w, cur, S, L);
-		}
-		cur ^= 1u;
-	}
-	uint32_t const *a = w + (size_t) cur * 2u * m, *d = a + m;
-	if (out_state_a && b1 == nb_total)
-		for (uint32_t i = tid; i < m; i += ST) { out_state_a[(size_t) nb_total * m + i] = a[i]; out_state_d[(size_t) nb_total * m + i] = d[i]; }
-	if (out_rank)
-		stream_emit_ranks(m, a, d, kstart, out_rank + (size_t) grp * m, out_keyd + (size_t) grp * m, out_nkeys + grp, L);
-}
-
-// ------------------------------------------------------------------------------------------------
 // [r5] Pass 2 behind the reduced phase C, streamed rows (fseq_reduced.hpp): a boundary inside a block is ONE such step from
 // the block's boundary state, keyed by the classes the block's representatives form at the boundary's column (the tables of
 // k_columns_red).  Workgroups take the tasks in turn, each in its own workspace.  ncls[t] == 0: the boundary is the block's
@@ -337,7 +289,7 @@ __global__ __launch_bounds__(ST) void k_chain_snap_stream(
 // The same step spread over the chip.  One workgroup per chain leaves 255 CUs idle on the levels of phase B's recursion
 // that matter for its length -- the top ones, a handful of chains of four steps each -- and a step is bound by what ONE
 // CU's texture path takes to gather and scatter 100,000 rows a dozen times (1.6 ms a step: BASELINE C4 phase B 95 -> 61 ms
-// with the single-workgroup form above).  Here every sweep of a step is a launch over (parts of 1,024 positions) x
+// against a chain on one workgroup).  Here every sweep of a step is a launch over (parts of 1,024 positions) x
 // (chains of the level): per radix pass  count  ->  offsets  ->  scatter, then the new order; a chain of G blocks is G
 // such rounds, the chains of a level side by side.  A wave owns a part (16 groups of 64 positions in order); the digit
 // histograms of the parts sit in a table of their own ([chain][part][bin]), whose prefix over (bin, part) one workgroup
@@ -360,8 +312,7 @@ struct ChainMultiArgs {
 	uint32_t grp0;
 	uint32_t step;                               // block b0 + step of every chain
 	uint32_t pass;                               // radix pass of the sweep kernels
-	uint32_t nchains;                            // chains of the launch (the grid's y is rounded up to the XCDs)
-	uint32_t xcd_map;                            // the workgroups of a chain on ONE XCD (cm_wg)
+	uint32_t nchains;                            // chains of the launch (the grid's y is rounded up to the XCDs: cm_wg)
 };
 
 // [r5] Which (part group, chain) a workgroup of the part / row kernels takes.  The hardware hands consecutive workgroups to
@@ -374,7 +325,6 @@ struct CmWg { uint32_t x, chain; bool ok; };
 __device__ __forceinline__ CmWg cm_wg(ChainMultiArgs const &A)
 {
 	CmWg w;
-	if (!A.xcd_map) { w.x = blockIdx.x; w.chain = blockIdx.y; w.ok = blockIdx.y < A.nchains; return w; }
 	uint32_t const nx = gridDim.x, L = blockIdx.y * nx + blockIdx.x;
 	uint32_t const xcd = L & 7u, slot = L >> 3;
 	w.chain = (slot / nx) * 8u + xcd;

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -52,11 +53,11 @@ inline hipError_t allow_lds(K kernel, size_t bytes)
 	return hipFuncSetAttribute(reinterpret_cast<void const *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
 }
 
-struct Stream2Config { uint32_t T, E, key_shift, pack; size_t (*lds)(uint32_t colbytes); hipError_t (*prepare)(size_t lds);
+struct Stream2Config { uint32_t T, E, key_shift; size_t (*lds)(uint32_t colbytes); hipError_t (*prepare)(size_t lds);
 	void (*launch)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *,
 	               uint32_t, uint32_t, uint32_t, uint2 *, uint4 *, uint32_t, uint32_t *, uint32_t *, uint32_t, uint32_t *, uint32_t, uint32_t, uint32_t const *blocklist);
 	uint32_t (*resident)(size_t lds);
-	// pass 2 on the same tile step (packed rows only; nullptr otherwise): k_columns_stream2<.., S2_SNAP>
+	// pass 2 on the same tile step: k_columns_stream2<.., S2_SNAP>
 	void (*launch_snap)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *,
 	                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &); };
 // [r5] phase C on representative rows (fseq_reduced.hpp; the kernels live in csrc/fseq_reduced.hip)
@@ -82,8 +83,8 @@ struct ChainSnapSet {
 bool select_chain_snap(uint32_t T, uint32_t E, ChainSnapSet *out);
 
 // the kernel configurations and their launchers (csrc/fseq_kernelsets.hip)
-bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out, bool no_emitter_wave);
-bool select_stream2(uint32_t T, uint32_t E, uint32_t pack, Stream2Config *out);
+bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out);
+Stream2Config stream2_config();
 void launch_blockkeys(uint32_t T, hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
                       uint32_t bsh, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0,
                       uint16_t *scratch, size_t scratch_per_block, uint32_t cap_words, uint32_t *sliced, uint32_t *todo, uint32_t const *only = nullptr);
@@ -118,22 +119,15 @@ struct Tuning {
 	bool occurrence_keys = false;        // FSEQ_OCCURRENCE_KEYS: ... scan occurrence keys even where row counts fit the keys
 	bool phase_a_classic = false;        // FSEQ_PHASE_A_CLASSIC: phase A as a column sweep
 	int  chain_fan = 0;                  // FSEQ_CHAIN_FAN: group size of phase B's recursion
-	bool two_level_chain = false;        // FSEQ_TWO_LEVEL_CHAIN
-	bool chain_stream_passes = false;    // FSEQ_CHAIN_STREAM_PASSES: streamed phase B as two-bit digit passes (the form before fseq_chainsort.hpp)
-	bool chain_stream_single = false;    // FSEQ_CHAIN_STREAM_SINGLE: ... as the sorted step on one workgroup per chain (not spread over the chip)
 	bool blockkeys_wide = false;         // FSEQ_BLOCKKEYS_WIDE: 32-bit ids in the streamed key-space tree from the start
 	bool blockkeys_single = false;       // FSEQ_BLOCKKEYS_SINGLE: its leaves one by one (no pair leaves)
 	bool no_dense_columns = false;       // FSEQ_NO_DENSE_COLUMNS: every column of 4-bit symbols in two digit passes (by itself: one pass where at most four codes are present)
 	bool no_blocktrie = false;           // FSEQ_NO_BLOCKTRIE: the streamed phase A without the trie over 16-column words (fseq_blocktrie.hpp): the key-space tree on every block
 	bool blocktrie_always = false;       // FSEQ_BLOCKTRIE_ALWAYS: the trie for LDS-resident rows of any count (by itself: from 6,145 rows on)
-	bool blockkeys_no_limit = false;     // FSEQ_BLOCKKEYS_NO_LIMIT: the key-space tree slices as often as it takes (never hands a block to the column sweep)
 	int  blockkeys_cap = 0;              // FSEQ_BLOCKKEYS_CAP: words of the key-space tree's LDS bitmap
-	std::string stream2;                 // FSEQ_STREAM2: "T,E[,pack]" configuration of the streamed phase C, "0" = first form
 	bool ss_unpacked = false;            // FSEQ_SS_UNPACKED: 8-byte stride states in the streamed regime
 	bool ss_absolute = false;            // FSEQ_SS_ABSOLUTE: stride states hold divergences and pass 2 runs the first form's tile step (the form before round 4)
-	int  snap_stride = 0;                // FSEQ_SNAP_STRIDE: first stride tried for the stride states
 	bool poison_lists = false;           // FSEQ_POISON_LISTS: lists and headers filled with 0xFF before phase C
-	bool no_emitter_wave = false;        // FSEQ_NO_EMITTER_WAVE: phase C without the list wave
 	bool join_host = false;              // FSEQ_JOIN_HOST: the greedy joiner's class tables and edges on the host
 	bool shard_dp_full = false;          // FSEQ_SHARD_DP_FULL: the sharded DP gathers the whole key array after every sweep (round 2-3 form)
 	int  shard_dp_window = 0;            // FSEQ_SHARD_DP_WINDOW: entries of the other ranks a rank holds in front of its own (tests: small windows)
@@ -143,76 +137,74 @@ struct Tuning {
 	bool no_reduced = false;             // FSEQ_NO_REDUCED: phase C and pass 2 on all rows of every block (the form before round 5)
 	int  reduced_margin = -1;            // FSEQ_REDUCED_MARGIN: counts beyond the list capacity the choice of vmin allows for (tests: 0 makes lists dig below it)
 	bool reduced_always = false;         // FSEQ_REDUCED_ALWAYS: the representatives whenever some block has fewer of them than rows (tests of the mixed runs)
-	int  reduced_side = -1;              // FSEQ_REDUCED_SIDE: side streams the configurations' launches may use (0 .. 3)
-	bool reduced_serial = false;         // FSEQ_REDUCED_SERIAL: the configurations' launches one after the other on the context's stream (by itself: side by side)
-	bool chain_no_xcd_map = false;       // FSEQ_CHAIN_NO_XCD_MAP: the streamed phase B's workgroups taken as they come (by itself: a chain's on one XCD)
 	bool reduced_msa_gather = false;     // FSEQ_REDUCED_MSA_GATHER: the reduced alignment by gathers from memory (by itself: the column through LDS where it fits)
-	bool reduced_ew = false;             // FSEQ_REDUCED_EW: small blocks on two-wave workgroups (the list on a wave of its own) instead of one wave
-	int  stream_block = 0;               // FSEQ_STREAM_BLOCK: columns per block the streamed regime aims for when phase C runs on representatives
 	int  reduced_cap = 0;                // FSEQ_REDUCED_CAP: most representatives a block may have (tests: small values send blocks to the run on all rows)
+
+	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
+	struct Knob {
+		char const *name;
+		bool Tuning::*flag;
+		int Tuning::*num;
+		int lo, off;
+		std::string Tuning::*str;
+	};
+	static std::vector<Knob> const &knobs()
+	{
+		static std::vector<Knob> const table = {
+			{"FSEQ_DEBUG", &Tuning::debug, nullptr, 0, 0, nullptr},
+			{"FSEQ_DP_SERIAL", &Tuning::dp_serial, nullptr, 0, 0, nullptr},
+			{"FSEQ_DP_SPEC_WIN", nullptr, &Tuning::dp_spec_win, 1, 0, nullptr},
+			{"FSEQ_DP_SPEC_ROUNDS", nullptr, &Tuning::dp_spec_rounds, 1, 0, nullptr},
+			{"FSEQ_DP_SPEC_MAX_SWEEPS", nullptr, &Tuning::dp_spec_max_sweeps, 1, 0, nullptr},
+			{"FSEQ_STREAM_PLAIN_SCAN", &Tuning::stream_plain_scan, nullptr, 0, 0, nullptr},
+			{"FSEQ_PLAIN_SCAN", &Tuning::plain_scan, nullptr, 0, 0, nullptr},
+			{"FSEQ_OCCURRENCE_KEYS", &Tuning::occurrence_keys, nullptr, 0, 0, nullptr},
+			{"FSEQ_PHASE_A_CLASSIC", &Tuning::phase_a_classic, nullptr, 0, 0, nullptr},
+			{"FSEQ_CHAIN_FAN", nullptr, &Tuning::chain_fan, 2, 0, nullptr},
+			{"FSEQ_BLOCKKEYS_WIDE", &Tuning::blockkeys_wide, nullptr, 0, 0, nullptr},
+			{"FSEQ_BLOCKKEYS_SINGLE", &Tuning::blockkeys_single, nullptr, 0, 0, nullptr},
+			{"FSEQ_NO_DENSE_COLUMNS", &Tuning::no_dense_columns, nullptr, 0, 0, nullptr},
+			{"FSEQ_NO_BLOCKTRIE", &Tuning::no_blocktrie, nullptr, 0, 0, nullptr},
+			{"FSEQ_BLOCKTRIE_ALWAYS", &Tuning::blocktrie_always, nullptr, 0, 0, nullptr},
+			{"FSEQ_BLOCKKEYS_CAP", nullptr, &Tuning::blockkeys_cap, 2048, 0, nullptr},
+			{"FSEQ_SS_UNPACKED", &Tuning::ss_unpacked, nullptr, 0, 0, nullptr},
+			{"FSEQ_SS_ABSOLUTE", &Tuning::ss_absolute, nullptr, 0, 0, nullptr},
+			{"FSEQ_POISON_LISTS", &Tuning::poison_lists, nullptr, 0, 0, nullptr},
+			{"FSEQ_JOIN_HOST", &Tuning::join_host, nullptr, 0, 0, nullptr},
+			{"FSEQ_SHARD_DP_FULL", &Tuning::shard_dp_full, nullptr, 0, 0, nullptr},
+			{"FSEQ_SHARD_DP_WINDOW", nullptr, &Tuning::shard_dp_window, 64, 0, nullptr},
+			{"FSEQ_INJECT_FAILURE_RANK", nullptr, &Tuning::inject_failure_rank, INT_MIN, -1, nullptr},
+			{"FSEQ_SYNC_PHASES", nullptr, nullptr, 0, 0, &Tuning::sync_phases},
+			{"FSEQ_CHECK_PHASE_A", &Tuning::check_phase_a, nullptr, 0, 0, nullptr},
+			{"FSEQ_NO_REDUCED", &Tuning::no_reduced, nullptr, 0, 0, nullptr},
+			{"FSEQ_REDUCED_MARGIN", nullptr, &Tuning::reduced_margin, 0, -1, nullptr},
+			{"FSEQ_REDUCED_ALWAYS", &Tuning::reduced_always, nullptr, 0, 0, nullptr},
+			{"FSEQ_REDUCED_MSA_GATHER", &Tuning::reduced_msa_gather, nullptr, 0, 0, nullptr},
+			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
+		};
+		return table;
+	}
+
+	void apply(Knob const &k, char const *value)
+	{
+		bool const on = value != nullptr;
+		if (k.flag) this->*k.flag = on;
+		else if (k.num) this->*k.num = on ? std::max(k.lo, atoi(value)) : k.off;
+		else this->*k.str = on ? value : "";
+	}
 
 	// returns false for a name it does not know
 	bool set(char const *name, char const *value)
 	{
-		std::string const n(name), v(value ? value : "");
-		bool const on = value != nullptr;
-		int const iv = atoi(v.c_str());
-		if (n == "FSEQ_DEBUG") debug = on;
-		else if (n == "FSEQ_DP_SERIAL") dp_serial = on;
-		else if (n == "FSEQ_DP_SPEC_WIN") dp_spec_win = on ? std::max(1, iv) : 0;
-		else if (n == "FSEQ_DP_SPEC_ROUNDS") dp_spec_rounds = on ? std::max(1, iv) : 0;
-		else if (n == "FSEQ_DP_SPEC_MAX_SWEEPS") dp_spec_max_sweeps = on ? std::max(1, iv) : 0;
-		else if (n == "FSEQ_STREAM_PLAIN_SCAN") stream_plain_scan = on;
-		else if (n == "FSEQ_PLAIN_SCAN") plain_scan = on;
-		else if (n == "FSEQ_OCCURRENCE_KEYS") occurrence_keys = on;
-		else if (n == "FSEQ_PHASE_A_CLASSIC") phase_a_classic = on;
-		else if (n == "FSEQ_CHAIN_FAN") chain_fan = on ? std::max(2, iv) : 0;
-		else if (n == "FSEQ_TWO_LEVEL_CHAIN") two_level_chain = on;
-		else if (n == "FSEQ_CHAIN_STREAM_PASSES") chain_stream_passes = on;
-		else if (n == "FSEQ_CHAIN_STREAM_SINGLE") chain_stream_single = on;
-		else if (n == "FSEQ_BLOCKKEYS_WIDE") blockkeys_wide = on;
-		else if (n == "FSEQ_BLOCKKEYS_SINGLE") blockkeys_single = on;
-		else if (n == "FSEQ_BLOCKKEYS_NO_LIMIT") blockkeys_no_limit = on;
-		else if (n == "FSEQ_NO_BLOCKTRIE") no_blocktrie = on;
-		else if (n == "FSEQ_NO_DENSE_COLUMNS") no_dense_columns = on;
-		else if (n == "FSEQ_BLOCKTRIE_ALWAYS") blocktrie_always = on;
-		else if (n == "FSEQ_BLOCKKEYS_CAP") blockkeys_cap = on ? std::max(2048, iv) : 0;
-		else if (n == "FSEQ_STREAM2") stream2 = v;
-		else if (n == "FSEQ_SS_UNPACKED") ss_unpacked = on;
-		else if (n == "FSEQ_SS_ABSOLUTE") ss_absolute = on;
-		else if (n == "FSEQ_SNAP_STRIDE") snap_stride = on ? std::max(1, iv) : 0;
-		else if (n == "FSEQ_POISON_LISTS") poison_lists = on;
-		else if (n == "FSEQ_NO_EMITTER_WAVE") no_emitter_wave = on;
-		else if (n == "FSEQ_JOIN_HOST") join_host = on;
-		else if (n == "FSEQ_SHARD_DP_FULL") shard_dp_full = on;
-		else if (n == "FSEQ_SHARD_DP_WINDOW") shard_dp_window = on ? std::max(64, iv) : 0;
-		else if (n == "FSEQ_INJECT_FAILURE_RANK") inject_failure_rank = on ? iv : -1;
-		else if (n == "FSEQ_SYNC_PHASES") sync_phases = v;
-		else if (n == "FSEQ_CHECK_PHASE_A") check_phase_a = on;
-		else if (n == "FSEQ_NO_REDUCED") no_reduced = on;
-		else if (n == "FSEQ_REDUCED_MARGIN") reduced_margin = on ? std::max(0, iv) : -1;
-		else if (n == "FSEQ_REDUCED_CAP") reduced_cap = on ? std::max(1, iv) : 0;
-		else if (n == "FSEQ_REDUCED_EW") reduced_ew = on;
-		else if (n == "FSEQ_REDUCED_ALWAYS") reduced_always = on;
-		else if (n == "FSEQ_REDUCED_SERIAL") reduced_serial = on;
-		else if (n == "FSEQ_REDUCED_SIDE") reduced_side = on ? std::max(0, std::min(3, iv)) : -1;
-		else if (n == "FSEQ_REDUCED_MSA_GATHER") reduced_msa_gather = on;
-		else if (n == "FSEQ_CHAIN_NO_XCD_MAP") chain_no_xcd_map = on;
-		else if (n == "FSEQ_STREAM_BLOCK") stream_block = on ? std::max(64, iv) : 0;
-		else return false;
-		return true;
+		for (Knob const &k : knobs())
+			if (!strcmp(k.name, name)) { apply(k, value); return true; }
+		return false;
 	}
 
 	void from_environment()
 	{
-		static char const *const names[] = {"FSEQ_DEBUG", "FSEQ_DP_SERIAL",
-			"FSEQ_DP_SPEC_WIN", "FSEQ_DP_SPEC_ROUNDS", "FSEQ_DP_SPEC_MAX_SWEEPS", "FSEQ_STREAM_PLAIN_SCAN", "FSEQ_PLAIN_SCAN", "FSEQ_OCCURRENCE_KEYS", "FSEQ_PHASE_A_CLASSIC",
-			"FSEQ_CHAIN_FAN", "FSEQ_TWO_LEVEL_CHAIN", "FSEQ_BLOCKKEYS_WIDE", "FSEQ_BLOCKKEYS_SINGLE", "FSEQ_BLOCKKEYS_CAP", "FSEQ_STREAM2", "FSEQ_SS_UNPACKED", "FSEQ_SNAP_STRIDE",
-			"FSEQ_POISON_LISTS", "FSEQ_NO_EMITTER_WAVE", "FSEQ_JOIN_HOST", "FSEQ_INJECT_FAILURE_RANK", "FSEQ_SYNC_PHASES", "FSEQ_CHECK_PHASE_A",
-			"FSEQ_SHARD_DP_FULL", "FSEQ_SHARD_DP_WINDOW", "FSEQ_BLOCKKEYS_NO_LIMIT", "FSEQ_CHAIN_STREAM_PASSES", "FSEQ_CHAIN_STREAM_SINGLE", "FSEQ_SS_ABSOLUTE",
-			"FSEQ_NO_BLOCKTRIE", "FSEQ_BLOCKTRIE_ALWAYS", "FSEQ_NO_DENSE_COLUMNS", "FSEQ_NO_REDUCED", "FSEQ_REDUCED_MARGIN", "FSEQ_REDUCED_CAP", "FSEQ_REDUCED_EW", "FSEQ_STREAM_BLOCK", "FSEQ_REDUCED_ALWAYS", "FSEQ_REDUCED_SERIAL", "FSEQ_REDUCED_SIDE", "FSEQ_REDUCED_MSA_GATHER", "FSEQ_CHAIN_NO_XCD_MAP"};
-		for (char const *nm : names)
-			if (char const *v = getenv(nm)) (void) set(nm, v);
+		for (Knob const &k : knobs())
+			if (char const *v = getenv(k.name)) apply(k, v);
 	}
 };
 
@@ -324,7 +316,6 @@ struct fseq_ctx {
 	uint32_t *d_bstate_a = nullptr, *d_bstate_d = nullptr;
 	uint32_t *d_rank_alloc = nullptr, *d_keyd_alloc = nullptr, *d_nkeys_alloc = nullptr, *d_bstate_a_alloc = nullptr, *d_bstate_d_alloc = nullptr;
 	uint32_t *d_cshist = nullptr;            // streamed phase B spread over the chip (fseq_chainsort.hpp): digit histograms [chain][part][bin]
-	size_t cshist_words = 0;
 	uint32_t *d_ws_c = nullptr;              // streamed phase C: the per-block workspaces, block b at d_ws_c + b * (words per block)
 	uint32_t *d_hrank = nullptr, *d_hkeyd = nullptr, *d_hnkeys = nullptr, *d_hstate_a = nullptr, *d_hstate_d = nullptr;
 	// not sharded: phase B over any number of levels (levels[i - 1] = the composites of chain_fan level-(i - 1) key blocks)

@@ -1,6 +1,6 @@
 // fseq_kernelsets.hip -- the kernel configurations of the path and their launchers: the LDS-resident column / chain / rank
 // kernels by row count (select_kernels); phase A's key-space tree and trie by workgroup size and the streamed phase C's tile
-// configurations (select_stream2) are csrc/fseq_kernelsets_stream.hip.  A translation unit of its own since round 5 (the review's "split fseq_api.hip"): these
+// configuration (stream2_config) are csrc/fseq_kernelsets_stream.hip.  A translation unit of its own since round 5 (the review's "split fseq_api.hip"): these
 // template instantiations were two thirds of what a rebuild of csrc/fseq_api.hip cost, and nothing in the orchestration
 // touches them but through the function tables of fseq_ctx.hpp (KernelSet, Stream2Config).
 #include "fseq_ctx.hpp"
@@ -95,14 +95,13 @@ KernelSet compose_kernels()
 
 } // namespace
 
-bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out, bool no_emitter_wave)
+bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out)
 {
 	if (sigma > 256) return false;
 	// 1024-thread configurations spare wave 0 for the per-column lists when the rows allow it (measured: C5 phase C
 	// 86 -> 75 ms with it, while 512-thread workgroups lose as much to the longer per-thread chunks as they gain)
-	bool const ew_ok = !no_emitter_wave;
 #define FSEQ_TRY_EW(T_, E_, PK_)                                                               \
-	if (ew_ok && m <= (uint32_t) ((T_) - 64) * (E_))                                           \
+	if (m <= (uint32_t) ((T_) - 64) * (E_))                                                    \
 	{                                                                                          \
 		*out = Launch<T_, E_, 4, PK_, true>::make();                                            \
 		return true;                                                                           \
@@ -123,12 +122,12 @@ bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out, bool no_emitter_
 	// registers by launch bounds put THREE workgroups on a CU -- a column step is a chain of three barriers and ~6 LDS round
 	// trips, and two workgroups left the SIMDs idle 43 % of the time (BASELINE C3: phase C 5.61 -> 5.08 ms; the unpacking
 	// costs less than the third workgroup brings)
-	if (ew_ok && m > 448u * 5u && m <= 448u * 6u && m <= 512u * 5u)
+	if (m > 448u * 5u && m <= 448u * 6u && m <= 512u * 5u)
 	{
 		*out = compose_kernels<Launch<512, 5, 4, false>, Launch<512, 6, 4, true, true>>();
 		return true;
 	}
-	if (ew_ok && m > 256u * 5u && m <= 448u * 5u)
+	if (m > 256u * 5u && m <= 448u * 5u)
 	{
 		*out = compose_kernels<Launch<512, 5, 4, false>, Launch<512, 5, 4, true, true>>();
 		return true;

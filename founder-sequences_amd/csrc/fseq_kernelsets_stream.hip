@@ -1,6 +1,6 @@
 // fseq_kernelsets_stream.hip -- launchers by configuration, second part (csrc/fseq_kernelsets.hip): phase A's key-space tree
 // (k_blockkeys) and trie (k_blocktrie) by workgroup size and bits per symbol, the streamed phase C's tile configurations
-// (k_columns_stream2, select_stream2).
+// (k_columns_stream2, stream2_config).
 #include "fseq_ctx.hpp"
 #include "fseq_kernels.hpp"
 #include "fseq_stream.hpp"
@@ -14,41 +14,36 @@ namespace fseq {
 
 namespace {
 
-// phase C, streamed rows, second form (fseq_stream2.hpp): <threads, rows per thread, 5-byte rows>
-#define FSEQ_S2_CONFIGS(X) X(512, 8, true) X(1024, 4, true) X(1024, 8, true) X(256, 8, true) X(256, 12, true) X(512, 8, false) X(1024, 6, false) X(1024, 8, false) X(256, 8, false) X(256, 12, false)
-template <int T, int E, bool PACK>
-struct LaunchS2 {
-	static size_t lds(uint32_t colbytes) { return stream2_lds_bytes<T, E, PACK>(colbytes); }
-	static hipError_t prepare(size_t bytes)
-	{
-		hipError_t const e = allow_lds(k_columns_stream2<T, E, PACK>, bytes);
-		if (e != hipSuccess) return e;
-		if constexpr (PACK) return allow_lds(k_columns_stream2<T, E, PACK, S2_SNAP>, bytes);
-		return hipSuccess;
-	}
-	static void launch_snap(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
-	                        uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &SN)
-	{
-		if constexpr (PACK)
-			hipLaunchKernelGGL((k_columns_stream2<T, E, PACK, S2_SNAP>), dim3(grid), dim3(T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, 0u, 0u, 0u, (uint2 *) nullptr, (uint4 *) nullptr,
-			                   snap_stride, ss_a, ss_d, 0u, (uint32_t *) nullptr, 0u, 0u, SN);
-	}
-	static void launch(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
-	                   uint32_t L, uint32_t X, uint32_t stride, uint2 *ent, uint4 *hdr, uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, uint32_t block0, uint32_t *done, uint32_t epoch, uint32_t ss_pack,
-	                   uint32_t const *blocklist)
-	{
-		S2SnapArgs SN{};
-		SN.wg_block = blocklist;
-		hipLaunchKernelGGL((k_columns_stream2<T, E, PACK>), dim3(grid), dim3(T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, L, X, stride, ent, hdr, snap_stride, ss_a, ss_d, block0, done, epoch, ss_pack, SN);
-	}
-	static uint32_t resident(size_t bytes)
-	{
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_columns_stream2<T, E, PACK>, T, bytes) != hipSuccess || nb < 1) nb = 1;
-		return (uint32_t) nb;
-	}
-	static Stream2Config make() { return Stream2Config{(uint32_t) T, (uint32_t) E, (uint32_t) s2_key_shift(T * E), PACK ? 1u : 0u, &lds, &prepare, &launch, &resident, PACK ? &launch_snap : nullptr}; }
-};
+// phase C, streamed rows, second form (fseq_stream2.hpp): T threads x E rows of 5 bytes (the one configuration; the 8-byte
+// rows and the other tile shapes are gone: no default decision picked them)
+constexpr int S2_T = 512, S2_E = 8;
+size_t s2_lds(uint32_t colbytes) { return stream2_lds_bytes<S2_T, S2_E>(colbytes); }
+hipError_t s2_prepare(size_t bytes)
+{
+	hipError_t const e = allow_lds(k_columns_stream2<S2_T, S2_E>, bytes);
+	if (e != hipSuccess) return e;
+	return allow_lds(k_columns_stream2<S2_T, S2_E, S2_SNAP>, bytes);
+}
+void s2_launch_snap(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
+                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &SN)
+{
+	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E, S2_SNAP>), dim3(grid), dim3(S2_T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, 0u, 0u, 0u, (uint2 *) nullptr, (uint4 *) nullptr,
+	                   snap_stride, ss_a, ss_d, 0u, (uint32_t *) nullptr, 0u, 0u, SN);
+}
+void s2_launch(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
+               uint32_t L, uint32_t X, uint32_t stride, uint2 *ent, uint4 *hdr, uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, uint32_t block0, uint32_t *done, uint32_t epoch, uint32_t ss_pack,
+               uint32_t const *blocklist)
+{
+	S2SnapArgs SN{};
+	SN.wg_block = blocklist;
+	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E>), dim3(grid), dim3(S2_T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, L, X, stride, ent, hdr, snap_stride, ss_a, ss_d, block0, done, epoch, ss_pack, SN);
+}
+uint32_t s2_resident(size_t bytes)
+{
+	int nb = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_columns_stream2<S2_T, S2_E>, S2_T, bytes) != hipSuccess || nb < 1) nb = 1;
+	return (uint32_t) nb;
+}
 } // namespace
 
 // phase A in key space, LDS-resident rows (fseq_blockkeys.hpp): the kernel has its own workgroup size, one thread
@@ -111,12 +106,9 @@ hipError_t launch_blocktrie(uint32_t bits, uint32_t T, hipStream_t st, uint32_t 
 	return hipErrorInvalidValue;
 }
 
-bool select_stream2(uint32_t T, uint32_t E, uint32_t pack, Stream2Config *out)
+Stream2Config stream2_config()
 {
-#define X(T_, E_, P_) if (T == T_ && E == E_ && (pack != 0) == P_) { *out = LaunchS2<T_, E_, P_>::make(); return true; }
-	FSEQ_S2_CONFIGS(X)
-#undef X
-	return false;
+	return Stream2Config{(uint32_t) S2_T, (uint32_t) S2_E, (uint32_t) s2_key_shift(S2_T * S2_E), &s2_lds, &s2_prepare, &s2_launch, &s2_resident, &s2_launch_snap};
 }
 
 

@@ -30,9 +30,10 @@ struct LaunchRed {
 
 // ascending by the rows they hold.  EW: wave 0 holds no rows and emits the lists while the row waves are in the next column (from 256
 // threads on: what phase C runs -- the lists of a block with thousands of representatives are a thousand entries long, and
-// on a wave that also holds rows they were 40 % of a column of BASELINE C4 --; pass 2's sweeps, which emit none, take the others)
+// on a wave that also holds rows they were 40 % of a column of BASELINE C4 --; pass 2's sweeps, which emit none, take the others).
+// Small blocks run one wave for both.
 #define FSEQ_RED_CONFIGS(X) \
-	X(64, 3, false, false) X(128, 3, false, true) X(64, 5, false, false) X(128, 5, false, true) X(64, 7, false, false) X(128, 7, false, true) \
+	X(64, 3, false, false) X(64, 5, false, false) X(64, 7, false, false) \
 	X(256, 3, false, true) X(256, 3, false, false) X(256, 5, false, true) X(256, 5, false, false) X(512, 5, false, true) X(512, 5, false, false) \
 	X(512, 7, false, true) X(512, 7, false, false) X(1024, 5, false, true) X(1024, 5, false, false) X(1024, 7, true, true) X(1024, 7, true, false) \
 	X(1024, 8, true, true) X(1024, 9, true, true) X(1024, 9, true, false) X(1024, 10, true, true) X(1024, 10, true, false) X(1024, 11, true, true) \

@@ -6,6 +6,8 @@
 // read and one write of a and d: SURVEY.md's 17 B/cell as real HBM traffic); a rank-digit or key pass
 // has a counting sweep over the order first.
 // Only the current column (m bytes) is staged in LDS.
+// Here: phase A's column sweep and pass 2 (k_colblock_stream) and phase C's first form (k_columns_stream).  The streamed
+// phase B is fseq_chainsort.hpp (k_cm_*), phase C's second form fseq_stream2.hpp.
 #pragma once
 
 #include "fseq_kernels.hpp"
@@ -25,8 +27,8 @@ struct StreamLds {
 	StepScratch<ST, 4> scr;
 	uint32_t red[4 * (ST / WAVE) + 8];
 	uint32_t sink[WAVE];                             // where stream_touch's loads land (never read)
-	uint32_t dh[64];                                 // rank_digit_counts: bucket sizes of up to 16 digit passes
-	uint32_t dhw[ST / WAVE][64];                     // ... per wave
+	uint32_t dh[64];                                 // (unused: the digit counts of phase B's former digit-pass form; kept so
+	uint32_t dhw[ST / WAVE][64];                     // that the LDS layout of the streamed kernels stays as measured)
 };
 
 // staged: plus the 2 x SCAP words in which stream_pass lays a tile out in output order
@@ -38,10 +40,6 @@ __host__ __device__ inline size_t stream_lds_bytes(uint32_t colbytes, bool stage
 struct DigitColumn {
 	uint8_t const *sym; uint32_t bsh, pass;
 	__device__ __forceinline__ uint32_t operator()(uint32_t a) const { return sym_digit(sym, a, bsh, pass); }
-};
-struct DigitRank {
-	uint32_t const *rank; uint32_t shift;
-	__device__ __forceinline__ uint32_t operator()(uint32_t a) const { return (rank[a] >> shift) & 3u; }
 };
 struct DigitKey {
 	uint32_t shift;
@@ -92,50 +90,6 @@ __device__ __forceinline__ void column_digit_counts(uint8_t const *sym, uint32_t
 		cnt[3] += (uint32_t) __popc(lo & hi);
 	}
 	block_sum4(cnt, red);
-}
-
-// Bucket sizes of ALL digit passes over a key block's ranks at once: they do not depend on the order, so one coalesced
-// sweep over rank[0 .. m) replaces the counting sweep in front of every pass (nd gathers of rk[a[i]] over all rows --
-// about 40 % of a pass).  Counts per (pass, digit) by ballot + popcount (uniform accumulators), L.dh[4 p + x] when done.
-__device__ __forceinline__ void rank_digit_counts(uint32_t const *__restrict__ rk, uint32_t m, uint32_t nd, StreamLds &L)
-{
-	uint32_t const tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
-	uint32_t c[16][3];
-#pragma unroll
-	for (int p = 0; p < 16; ++p) { c[p][0] = 0; c[p][1] = 0; c[p][2] = 0; }
-	uint32_t rows = 0;                                         // rows this wave has seen (digit 3 = the rest)
-	for (uint32_t base = 0; base < m; base += ST)
-	{
-		uint32_t const r = base + tid;
-		bool const in = r < m;
-		uint32_t const v = in ? rk[r] : 0u;
-		rows += (uint32_t) __popcll(__ballot(in));
-#pragma unroll
-		for (int p = 0; p < 16; ++p)
-			if ((uint32_t) p < nd)
-			{
-				uint32_t const g = (v >> (2 * p)) & 3u;
-#pragma unroll
-				for (int x = 0; x < 3; ++x) c[p][x] += (uint32_t) __popcll(__ballot(in && g == (uint32_t) x));
-			}
-	}
-	if (lane == 0)
-	{
-#pragma unroll
-		for (int p = 0; p < 16; ++p)
-		{
-			L.dhw[wave][4 * p] = c[p][0]; L.dhw[wave][4 * p + 1] = c[p][1]; L.dhw[wave][4 * p + 2] = c[p][2];
-			L.dhw[wave][4 * p + 3] = rows - c[p][0] - c[p][1] - c[p][2];
-		}
-	}
-	__syncthreads();
-	if (tid < 64u)
-	{
-		uint32_t t = 0;
-		for (uint32_t w = 0; w < ST / WAVE; ++w) t += L.dhw[w][tid];
-		L.dh[tid] = t;
-	}
-	__syncthreads();
 }
 
 // One stable 4-bucket partition pass over an order of m rows held in global memory:
@@ -320,7 +274,7 @@ __device__ __forceinline__ void stream_emit_ranks(
 // ------------------------------------------------------------------------------------------------
 // KO: every divergence is below 2^25 (n is): the partition steps scan occurrence keys (fseq_core.hpp) instead of {has, value}
 // (pass 2 at 64 registers, 19 spilled: two of these workgroups share a CU -- the staged column and the tile staging
-// are 58 KiB -- and hide each other's memory latency: BASELINE C4 pass 2 168 -> 157 ms; k_chain_stream the same way: 140 -> 150)
+// are 58 KiB -- and hide each other's memory latency: BASELINE C4 pass 2 168 -> 157 ms)
 template <int MODE, bool KO = false>
 __global__ __launch_bounds__(ST, MODE == MODE_SNAP ? 8 : 1) void k_colblock_stream(
 	uint8_t const *__restrict__ msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t nblocks, uint32_t npass, uint32_t bsh, uint32_t *ws, uint32_t staged,
@@ -402,67 +356,6 @@ __global__ __launch_bounds__(ST, MODE == MODE_SNAP ? 8 : 1) void k_colblock_stre
 	if (MODE == MODE_RANK)
 		stream_emit_ranks(m, buf[cur][0], buf[cur][1], (uint32_t) k0, rank + (size_t) blockIdx.x * m, keyd + (size_t) blockIdx.x * m,
 		                  nkeys + blockIdx.x, L);
-}
-
-// ------------------------------------------------------------------------------------------------
-// phase B, streamed (same contract as k_chain).  ws: [gridDim.x][4][m] words.
-// ------------------------------------------------------------------------------------------------
-template <bool KO = false>
-__global__ __launch_bounds__(ST) void k_chain_stream(
-	uint32_t const *__restrict__ rank, uint32_t const *__restrict__ keyd, uint32_t const *__restrict__ nkeys,
-	uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t *ws, uint32_t staged,
-	uint32_t const *__restrict__ start_a, uint32_t const *__restrict__ start_d,
-	uint32_t *__restrict__ out_state_a, uint32_t *__restrict__ out_state_d,
-	uint32_t *__restrict__ out_rank, uint32_t *__restrict__ out_keyd, uint32_t *__restrict__ out_nkeys, uint32_t grp0)
-{
-	extern __shared__ __attribute__((aligned(16))) char smem[];
-	Carver cv{smem};
-	StreamLds &L = *cv.take<StreamLds>(1);
-	uint32_t *const stage = staged ? cv.take<uint32_t>(2 * (size_t) SCAP) : nullptr;
-	uint32_t const tid = threadIdx.x;
-	uint32_t *buf[2][2];
-	{
-		uint32_t *w = ws + (size_t) blockIdx.x * 4u * m;
-		buf[0][0] = w; buf[0][1] = w + m; buf[1][0] = w + 2u * (size_t) m; buf[1][1] = w + 3u * (size_t) m;
-	}
-	uint32_t const grp = blockIdx.x + grp0;                     // chain index (workspaces stay per workgroup)
-	uint32_t const b0 = grp * G;
-	uint32_t const b1 = min(nb_total, b0 + G);
-	uint32_t const kstart = (uint32_t) ((uint64_t) b0 * cols_per_block);
-	for (uint32_t i = tid; i < m; i += ST)
-	{
-		buf[0][0][i] = start_a ? start_a[(size_t) grp * m + i] : i;
-		buf[0][1][i] = start_d ? start_d[(size_t) grp * m + i] : kstart;
-	}
-	__syncthreads();
-	uint32_t cur = 0;
-	for (uint32_t b = b0; b < b1; ++b)
-	{
-		uint32_t const *rk = rank + (size_t) b * m, *kd = keyd + (size_t) b * m;
-		if (out_state_a)
-			for (uint32_t i = tid; i < m; i += ST) { out_state_a[(size_t) b * m + i] = buf[cur][0][i]; out_state_d[(size_t) b * m + i] = buf[cur][1][i]; }
-		if (b + 1 == b1 && !out_rank && b1 != nb_total) break;       // (an expansion's last step: k_chain, fseq_kernels.hpp)
-		uint32_t const nd = rank_digits(nkeys[b]);
-		rank_digit_counts(rk, m, nd, L);
-		for (uint32_t p = 0; p < nd; ++p)
-		{
-			stream_pass<false, KO ? 25 : 0, KO>(m, buf[cur][0], buf[cur][1], buf[cur ^ 1u][0], buf[cur ^ 1u][1], 0u, DigitRank{rk, 2u * p}, NoHook{}, L, &L.dh[4u * p], stage);
-			cur ^= 1u;
-		}
-		// rows that start a new block key take the in-block divergence of that key
-		for (uint32_t pos = tid; pos < m; pos += ST)
-		{
-			uint32_t const r = rk[buf[cur][0][pos]];
-			uint32_t const rprev = pos ? rk[buf[cur][0][pos - 1u]] : PAD_KEY;
-			if (r != rprev) buf[cur][1][pos] = kd[r];
-		}
-		__syncthreads();
-	}
-	if (out_state_a && b1 == nb_total)
-		for (uint32_t i = tid; i < m; i += ST) { out_state_a[(size_t) nb_total * m + i] = buf[cur][0][i]; out_state_d[(size_t) nb_total * m + i] = buf[cur][1][i]; }
-	if (out_rank)
-		stream_emit_ranks(m, buf[cur][0], buf[cur][1], kstart, out_rank + (size_t) grp * m, out_keyd + (size_t) grp * m,
-		                  out_nkeys + grp, L);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -6,9 +6,9 @@
 // old step issues ~490 vector instructions per thread and tile of 4 rows -- 122 per cell, ~70 % of the SIMDs' issue
 // time at 4.2 cycles each -- among them 170 v_readlane / 70 v_writelane of spilled SGPRs, 145 64-bit address
 // computations and flat_ (not global_) memory instructions):
-//   * (a, d) of a row are ONE 8-byte pair in the workspace: one 16-byte load per two rows, one 8-byte LDS write
-//     and one 8-byte store per row, one address each;
-//   * T threads x E consecutive rows with E = 8 (fewer, longer threads: the scan and its second level over the
+//   * (a, d) of a row are packed into 5 bytes in the workspace (a word and a high byte, see stream2_lds_bytes): one
+//     16-byte load per four rows, wide stores per group of output slots, one address each;
+//   * T = 512 threads x E consecutive rows with E = 8 (fewer, longer threads: the scan and its second level over the
 //     waves cost the same per thread whatever E is);
 //   * loads and stores are buffer instructions on a descriptor of the workspace (uniform base + 32-bit offset:
 //     no per-lane 64-bit address arithmetic; rows behind m of the last tile read as zero);
@@ -28,7 +28,6 @@
 namespace fseq {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(void const *p, uint32_t bytes)
 {
@@ -47,8 +46,8 @@ constexpr int s2_key_shift(int tile)
 	return 32 - bits;
 }
 
-// -DFSEQ_S2_SKIP=bits: timing experiments (results are wrong): 1 no write-out stores, 2 no histogram atomics, 4 no list,
-// 8 no tile loads (the first tile's rows are reused), 16 no LDS staging
+// -DFSEQ_S2_SKIP=bits: timing experiments (results are wrong): 2 no histogram atomics, 4 no list, 8 no tile loads (the first
+// tile's rows are reused)
 #ifndef FSEQ_S2_SKIP
 #define FSEQ_S2_SKIP 0
 #endif
@@ -75,22 +74,21 @@ struct S2Lds {
 	uint32_t sel[4][T];                     // per thread: the four buckets' {slot, prefix maximum} words, read back per row
 };
 
-// PACK: a row of the order is 5 bytes in the workspace instead of 8 -- a word a | d << abits (abits = bits of a row id)
+// A row of the order is 5 bytes in the workspace -- a word a | d << abits (abits = bits of a row id)
 // and the byte d >> (32 - abits) in a second array: value ids are < 2^KS <= 2^19 and row ids < m <= 2^KS, so 40 bits
 // always hold both.  A CU moves ~10 bytes per cycle through its memory pipeline whatever the chip's HBM does, and the
-// order crosses it twice per column: 16 bytes per row were ~75 % of a column's time on the C4 rows.
-template <int T, int E, bool PACK>
+// order crosses it twice per column: 16 bytes per row (a and d as two words) were ~75 % of a column's time on the C4 rows.
+template <int T, int E>
 __host__ __device__ inline size_t stream2_lds_bytes(uint32_t colbytes)
 {
-	return carve_bytes((size_t) colbytes + 16, 1) + carve_bytes(1, sizeof(S2Lds<T>))
-	     + (PACK ? carve_bytes((size_t) T * E, 4) + carve_bytes((size_t) T * E, 1) : carve_bytes((size_t) T * E, 8));
+	return carve_bytes((size_t) colbytes + 16, 1) + carve_bytes(1, sizeof(S2Lds<T>)) + carve_bytes((size_t) T * E, 4) + carve_bytes((size_t) T * E, 1);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Prologue of every block (the old kernel's, on its own): sorted distinct boundary divergences -> V, their
 // counts -> cnt, the order as (a, value id) pairs -> pairs0, D0 -> w[9m + B].  ST threads.
 // Workspace (words): pairs0 2m | pairs1 2m | keys 2m | V m | Vpos m | cnt m + B | D0
-// pack_abits != 0 (PACK kernels): the first 4m words hold words0 m | words1 m | bytes0 m / 4 | .. | bytes1 m / 4 (at 3m) instead
+// pack_abits != 0 (k_columns_stream2's packed rows): the first 4m words hold words0 m | words1 m | bytes0 m / 4 | .. | bytes1 m / 4 (at 3m) instead
 // ------------------------------------------------------------------------------------------------
 static __global__ __launch_bounds__(ST) void k_columns_stream2_prologue(
 	uint32_t m, uint64_t n, uint32_t B, uint32_t *ws, uint32_t const *__restrict__ bstate_a, uint32_t const *__restrict__ bstate_d, uint32_t block0,
@@ -460,34 +458,30 @@ struct S2SnapArgs {
 	uint8_t const *bs_h;
 };
 
-template <int T, int E, bool PACK, int MODE = S2_COLUMNS>
+template <int T, int E, int MODE = S2_COLUMNS>
 __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 	uint8_t const *__restrict__ msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
 	uint32_t Lseg, uint32_t X, uint32_t stride, uint2 *__restrict__ ent, uint4 *__restrict__ hdr,
 	uint32_t snap_stride, uint32_t *__restrict__ ss_a, uint32_t *__restrict__ ss_d, uint32_t block0,
 	uint32_t *done_host, uint32_t epoch, uint32_t ss_pack, S2SnapArgs const SN)
 {
-	static_assert(MODE == S2_COLUMNS || PACK, "pass 2 on the tile step replays packed rows");
 	if (MODE == S2_COLUMNS) FSEQ_CLOCK_STAMP(blockIdx.x, 0);
 	constexpr int KS = s2_key_shift(T * E);
 	constexpr uint32_t TILE = (uint32_t) T * E;
-	static_assert(E % 2 == 0, "a thread loads its rows as 16-byte pieces of two (a, d) pairs");
-	static_assert(!PACK || E % 4 == 0, "packed rows: 16-byte pieces of four words, 4-byte pieces of four bytes");
+	static_assert(E % 4 == 0, "packed rows: 16-byte pieces of four words, 4-byte pieces of four bytes");
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	Carver cv{smem};
 	uint8_t *sym = cv.take<uint8_t>((size_t) sym_bytes(m, bsh) + 16);
 	S2Lds<T> &L = *cv.take<S2Lds<T>>(1);
-	uint2 *const stage = PACK ? nullptr : cv.take<uint2>(TILE);
-	uint32_t *const stage_w = PACK ? cv.take<uint32_t>(TILE) : nullptr;
-	uint8_t *const stage_h = PACK ? cv.take<uint8_t>(TILE) : nullptr;
+	uint32_t *const stage_w = cv.take<uint32_t>(TILE);
+	uint8_t *const stage_h = cv.take<uint8_t>(TILE);
 	uint32_t const tid = threadIdx.x;
 	uint32_t const lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	// (S2_COLUMNS with SN.wg_block set [r5]: the listed blocks -- what the reduced phase C hands to the run on all rows)
 	uint32_t const blk = (MODE == S2_SNAP || SN.wg_block) ? SN.wg_block[blockIdx.x] : blockIdx.x + block0;
 	uint32_t *w = ws + (size_t) blk * columns_stream_ws_words(m, B);
-	uint2 *pairs[2] = {reinterpret_cast<uint2 *>(w), reinterpret_cast<uint2 *>(w + 2u * (size_t) m)};
-	uint32_t *words[2] = {w, w + (size_t) m};                                 // PACK
+	uint32_t *words[2] = {w, w + (size_t) m};
 	uint8_t *highs[2] = {reinterpret_cast<uint8_t *>(w + 2u * (size_t) m), reinterpret_cast<uint8_t *>(w + 3u * (size_t) m)};
 	uint32_t abits = 1;
 	while ((1u << abits) < m) ++abits;
@@ -504,7 +498,7 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 	// block of BASELINE C4, D0 13,000 - 20,000 at 15 bits) never sets a high byte: they are neither loaded, nor staged, nor
 	// stored, nor copied into the stride states -- 8 instead of 10 bytes per row and column through HBM.  (Uniform per block, and
 	// the same in phase C and in pass 2: both read D0 from the block's workspace.)
-	bool const narrow = PACK && FSEQ_S2_NARROW && D0 + nb <= (1u << hshift);
+	bool const narrow = FSEQ_S2_NARROW && D0 + nb <= (1u << hshift);
 	bool const zero_present = (V[0] == 0u);
 	uint32_t const colbytes = sym_bytes(m, bsh);
 	uint32_t cur = 0;
@@ -589,50 +583,37 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 				for (int x = 0; x < 4; ++x) { tc.cnt[x] = 0; tc.val[x] = 0; tc.start[x] = acc; acc += cnt4[x]; }
 				tc.has = 0;
 			}
-			__amdgpu_buffer_rsrc_t const rs = PACK ? make_rsrc(words[cur], m * 4u) : make_rsrc(pairs[cur], m * 8u),
-			                             rd = PACK ? make_rsrc(words[cur ^ 1u], m * 4u) : make_rsrc(pairs[cur ^ 1u], m * 8u);
+			__amdgpu_buffer_rsrc_t const rs = make_rsrc(words[cur], m * 4u), rd = make_rsrc(words[cur ^ 1u], m * 4u);
 			// (bytes: the range rounded up to whole words -- a word that straddles the end of a descriptor's range reads as zero)
-			__amdgpu_buffer_rsrc_t const rsh = make_rsrc(highs[cur], (m + 3u) & ~3u), rdh = make_rsrc(highs[cur ^ 1u], (m + 3u) & ~3u);      // PACK
+			__amdgpu_buffer_rsrc_t const rsh = make_rsrc(highs[cur], (m + 3u) & ~3u), rdh = make_rsrc(highs[cur ^ 1u], (m + 3u) & ~3u);
 			uint32_t const first_val = D0 + j;
-			uint32_t const toff = tid * (uint32_t) (E * (PACK ? 4 : 8));          // byte offset of the thread's rows inside a tile
+			uint32_t const toff = tid * (uint32_t) (E * 4);          // byte offset of the thread's rows inside a tile
 			// rows of the tile at `base` (rows behind m read as zero)
 			uint32_t an[E], dn[E];
 			auto load_tile = [&](uint32_t base) {
-				if constexpr (PACK)
+				uint32_t hw[E / 4];
+#pragma unroll
+				for (int q = 0; q < E / 4; ++q)
 				{
-					uint32_t hw[E / 4];
+					u32x4 const v = __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16u * q, base * 4u, 0);
+					an[4 * q] = v.x; an[4 * q + 1] = v.y; an[4 * q + 2] = v.z; an[4 * q + 3] = v.w;
+					hw[q] = 0u;
+					if (!narrow) hw[q] = __builtin_amdgcn_raw_buffer_load_b32(rsh, tid * (uint32_t) E + 4u * q, base, 0);
+				}
+				// (unpacked where they arrive: dn = value id, an = row id)
+				if (narrow)
+				{
 #pragma unroll
-					for (int q = 0; q < E / 4; ++q)
-					{
-						u32x4 const v = __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16u * q, base * 4u, 0);
-						an[4 * q] = v.x; an[4 * q + 1] = v.y; an[4 * q + 2] = v.z; an[4 * q + 3] = v.w;
-						hw[q] = 0u;
-						if (!narrow) hw[q] = __builtin_amdgcn_raw_buffer_load_b32(rsh, tid * (uint32_t) E + 4u * q, base, 0);
-					}
-					// (unpacked where they arrive: dn = value id, an = row id)
-					if (narrow)
-					{
-#pragma unroll
-						for (int e = 0; e < E; ++e) { dn[e] = an[e] >> abits; an[e] &= amask; }
-					}
-					else
-					{
-#pragma unroll
-						for (int e = 0; e < E; ++e)
-						{
-							uint32_t const hb = (hw[e / 4] >> (8 * (e % 4))) & 255u;
-							dn[e] = (an[e] >> abits) | (hb << hshift);
-							an[e] &= amask;
-						}
-					}
+					for (int e = 0; e < E; ++e) { dn[e] = an[e] >> abits; an[e] &= amask; }
 				}
 				else
 				{
 #pragma unroll
-					for (int q = 0; q < E / 2; ++q)
+					for (int e = 0; e < E; ++e)
 					{
-						u32x4 const v = __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16u * q, base * 8u, 0);
-						an[2 * q] = v.x; dn[2 * q] = v.y; an[2 * q + 1] = v.z; dn[2 * q + 1] = v.w;
+						uint32_t const hb = (hw[e / 4] >> (8 * (e % 4))) & 255u;
+						dn[e] = (an[e] >> abits) | (hb << hshift);
+						an[e] &= amask;
 					}
 				}
 			};
@@ -660,12 +641,8 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 				{
 					if (FULL || base + tid * E + e < m)
 					{
-						if constexpr (PACK)
-						{
-							stage_w[lp[e]] = a[e] | (dnew[e] << abits);
-							if (!narrow) stage_h[lp[e]] = (uint8_t) (dnew[e] >> hshift);
-						}
-						else if (!(FSEQ_S2_SKIP & 16)) stage[lp[e]] = make_uint2(a[e], dnew[e]);
+						stage_w[lp[e]] = a[e] | (dnew[e] << abits);
+						if (!narrow) stage_h[lp[e]] = (uint8_t) (dnew[e] >> hshift);
 						if (MODE == S2_COLUMNS && !(FSEQ_S2_SKIP & 2) && d[e] != dnew[e])
 						{
 							(void) __hip_atomic_fetch_add(&cnt[d[e]], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -678,71 +655,24 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 				S2_STAMP(4);
 				uint32_t const tile_n = FULL ? TILE : m - base;
 				auto ge = [](uint32_t j, uint32_t l) -> uint32_t { return (l - 1u - j) >> 31; };      // j >= l as 0 / 1 (both < 2^31)
-				if constexpr (PACK)
-				{
-					// words: groups of 256 output slots (16 bytes per lane); bytes: groups of 64 (one byte per lane -- a run of a
-					// bucket starts at any byte of the array).  gb[x] = first group entirely behind the start of bucket x; a group
-					// that holds a bucket start strictly inside it takes the per-slot path.
-					uint32_t const gb1 = (lofs[1] + 255u) >> 8, gb2 = (lofs[2] + 255u) >> 8, gb3 = (lofs[3] + 255u) >> 8;
-					uint32_t const sg1 = (lofs[1] & 255u) ? (lofs[1] >> 8) : 0xFFFFFFFFu, sg2 = (lofs[2] & 255u) ? (lofs[2] >> 8) : 0xFFFFFFFFu,
-					               sg3 = (lofs[3] & 255u) ? (lofs[3] >> 8) : 0xFFFFFFFFu;
+				// words: groups of 256 output slots (16 bytes per lane); bytes: groups of 64 (one byte per lane -- a run of a
+				// bucket starts at any byte of the array).  gb[x] = first group entirely behind the start of bucket x; a group
+				// that holds a bucket start strictly inside it takes the per-slot path.
+				uint32_t const gb1 = (lofs[1] + 255u) >> 8, gb2 = (lofs[2] + 255u) >> 8, gb3 = (lofs[3] + 255u) >> 8;
+				uint32_t const sg1 = (lofs[1] & 255u) ? (lofs[1] >> 8) : 0xFFFFFFFFu, sg2 = (lofs[2] & 255u) ? (lofs[2] >> 8) : 0xFFFFFFFFu,
+				               sg3 = (lofs[3] & 255u) ? (lofs[3] >> 8) : 0xFFFFFFFFu;
 #pragma unroll
-					for (int e = 0; e < E / 4; ++e)
-					{
-						uint32_t const g = (uint32_t) e * (T / WAVE) + wave;
-						uint32_t const j0 = g * 256u;
-						if (!FULL && j0 >= tile_n) break;
-						uint4 const v = *reinterpret_cast<uint4 const *>(stage_w + j0 + 4u * lane);
-						// the high bytes of the same 256 slots: four per lane, one 4-byte store at whatever byte the run stands at (the
-						// memory pipeline takes unaligned dwords; one byte per lane and store instruction was 8 of a thread's 10 stores
-						// per tile, each with its own LDS read and scalar bucket selection)
-						uint32_t hv = 0u;
-						if (!narrow) hv = *reinterpret_cast<uint32_t const *>(stage_h + j0 + 4u * lane);
-						if (FULL && g != sg1 && g != sg2 && g != sg3)
-						{
-							uint32_t sh = gsh[0];
-							sh = ge(g, gb1) ? gsh[1] : sh;
-							sh = ge(g, gb2) ? gsh[2] : sh;
-							sh = ge(g, gb3) ? gsh[3] : sh;
-							u32x4 const vv = {v.x, v.y, v.z, v.w};
-							__builtin_amdgcn_raw_buffer_store_b128(vv, rd, lane * 16u, (j0 + sh) * 4u, 0);
-							if (!narrow) __builtin_amdgcn_raw_buffer_store_b32(hv, rdh, lane * 4u, j0 + sh, 0);
-						}
-						else
-						{
-							uint32_t const vq[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-							for (int h = 0; h < 4; ++h)
-							{
-								uint32_t const jj = j0 + 4u * lane + (uint32_t) h;
-								uint32_t sh = gsh[0];
-								sh = jj >= lofs[1] ? gsh[1] : sh;
-								sh = jj >= lofs[2] ? gsh[2] : sh;
-								sh = jj >= lofs[3] ? gsh[3] : sh;
-								if (FULL || jj < tile_n)
-								{
-									__builtin_amdgcn_raw_buffer_store_b32(vq[h], rd, (jj + sh) * 4u, 0u, 0);
-									if (!narrow) __builtin_amdgcn_raw_buffer_store_b8((uint8_t) (hv >> (8 * h)), rdh, jj + sh, 0u, 0);
-								}
-							}
-						}
-					}
-				}
-				else
+				for (int e = 0; e < E / 4; ++e)
 				{
-				// Output slots go out in groups of 128 (one 16-byte store per lane: the memory pipeline of a CU, ~10 bytes per
-				// cycle, takes wide stores at twice the rate of 8-byte ones).  gb[x] = first group that lies entirely behind the
-				// start of bucket x; a group that holds a bucket start strictly inside it takes the per-slot path.
-				uint32_t const gb1 = (lofs[1] + 127u) >> 7, gb2 = (lofs[2] + 127u) >> 7, gb3 = (lofs[3] + 127u) >> 7;
-				uint32_t const sg1 = (lofs[1] & 127u) ? (lofs[1] >> 7) : 0xFFFFFFFFu, sg2 = (lofs[2] & 127u) ? (lofs[2] >> 7) : 0xFFFFFFFFu,
-				               sg3 = (lofs[3] & 127u) ? (lofs[3] >> 7) : 0xFFFFFFFFu;
-#pragma unroll
-				for (int e = 0; e < E / 2; ++e)
-				{
-					uint32_t const g = (uint32_t) e * (T / WAVE) + wave;      // this store's group of 128 output slots: uniform
-					uint32_t const j0 = g * 128u;
+					uint32_t const g = (uint32_t) e * (T / WAVE) + wave;
+					uint32_t const j0 = g * 256u;
 					if (!FULL && j0 >= tile_n) break;
-					uint4 const v = *reinterpret_cast<uint4 const *>(stage + j0 + 2u * lane);
+					uint4 const v = *reinterpret_cast<uint4 const *>(stage_w + j0 + 4u * lane);
+					// the high bytes of the same 256 slots: four per lane, one 4-byte store at whatever byte the run stands at (the
+					// memory pipeline takes unaligned dwords; one byte per lane and store instruction was 8 of a thread's 10 stores
+					// per tile, each with its own LDS read and scalar bucket selection)
+					uint32_t hv = 0u;
+					if (!narrow) hv = *reinterpret_cast<uint32_t const *>(stage_h + j0 + 4u * lane);
 					if (FULL && g != sg1 && g != sg2 && g != sg3)
 					{
 						uint32_t sh = gsh[0];
@@ -750,25 +680,27 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 						sh = ge(g, gb2) ? gsh[2] : sh;
 						sh = ge(g, gb3) ? gsh[3] : sh;
 						u32x4 const vv = {v.x, v.y, v.z, v.w};
-						if (!(FSEQ_S2_SKIP & 1))
-						__builtin_amdgcn_raw_buffer_store_b128(vv, rd, lane * 16u, (j0 + sh) * 8u, 0);
+						__builtin_amdgcn_raw_buffer_store_b128(vv, rd, lane * 16u, (j0 + sh) * 4u, 0);
+						if (!narrow) __builtin_amdgcn_raw_buffer_store_b32(hv, rdh, lane * 4u, j0 + sh, 0);
 					}
 					else
 					{
+						uint32_t const vq[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-						for (int h = 0; h < 2; ++h)
+						for (int h = 0; h < 4; ++h)
 						{
-							uint32_t const jj = j0 + 2u * lane + (uint32_t) h;
+							uint32_t const jj = j0 + 4u * lane + (uint32_t) h;
 							uint32_t sh = gsh[0];
 							sh = jj >= lofs[1] ? gsh[1] : sh;
 							sh = jj >= lofs[2] ? gsh[2] : sh;
 							sh = jj >= lofs[3] ? gsh[3] : sh;
-							u32x2 const vv = {h ? v.z : v.x, h ? v.w : v.y};
 							if (FULL || jj < tile_n)
-								__builtin_amdgcn_raw_buffer_store_b64(vv, rd, (jj + sh) * 8u, 0u, 0);
+							{
+								__builtin_amdgcn_raw_buffer_store_b32(vq[h], rd, (jj + sh) * 4u, 0u, 0);
+								if (!narrow) __builtin_amdgcn_raw_buffer_store_b8((uint8_t) (hv >> (8 * h)), rdh, jj + sh, 0u, 0);
+							}
 						}
 					}
-				}
 				}
 				S2_STAMP(5);
 				// (no barrier here: the next tile's stage writes come behind its own barrier, which every wave reaches only
@@ -783,7 +715,6 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 			__syncthreads();
 			S2_STAMP(7);
 		}
-		uint2 const *P = pairs[cur];
 		uint32_t const *PW = words[cur];
 		uint8_t const *PH = highs[cur];
 		// ---- every snap_stride columns: drop the exact (a, d) for pass 2 (ids back to divergence values)
@@ -792,28 +723,25 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 			// (id form: the packed rows as they are -- pass 2 replays them in this block's id space)
 			size_t const q = (size_t) ((k0 + j + 1) / snap_stride), ob = q * m;
 			uint8_t *sh = reinterpret_cast<uint8_t *>(ss_d) + q * ss_high_stride(m);
-			if constexpr (PACK)
+			// (16 bytes per thread and step, four steps in flight: one word per step was a chain of ~200 dependent round trips,
+			// 4.6 % of a column on the C4 rows)
+			if ((m & 3u) == 0u)
 			{
-				// (16 bytes per thread and step, four steps in flight: one word per step was a chain of ~200 dependent round trips,
-				// 4.6 % of a column on the C4 rows)
-				if ((m & 3u) == 0u)
-				{
-					uint4 const *src = reinterpret_cast<uint4 const *>(PW);
-					uint4 *dst = reinterpret_cast<uint4 *>(ss_a + ob);
+				uint4 const *src = reinterpret_cast<uint4 const *>(PW);
+				uint4 *dst = reinterpret_cast<uint4 *>(ss_a + ob);
 #pragma unroll 4
-					for (uint32_t i = tid; i < m / 4u; i += T) dst[i] = src[i];
-				}
-				else
-					for (uint32_t i = tid; i < m; i += T) ss_a[ob + i] = PW[i];
-				if (!narrow)
-				{
-					// (whole words of four high bytes: both arrays are 4-byte aligned and padded past m)
-					uint32_t const *hs = reinterpret_cast<uint32_t const *>(PH);
-					uint32_t *hd = reinterpret_cast<uint32_t *>(sh);
-#pragma unroll 4
-					for (uint32_t i = tid; i < (m + 3u) / 4u; i += T) hd[i] = hs[i];
-				}
+				for (uint32_t i = tid; i < m / 4u; i += T) dst[i] = src[i];
 			}
+			else
+				for (uint32_t i = tid; i < m; i += T) ss_a[ob + i] = PW[i];
+			if (!narrow)
+			{
+				// (whole words of four high bytes: both arrays are 4-byte aligned and padded past m)
+				uint32_t const *hs = reinterpret_cast<uint32_t const *>(PH);
+				uint32_t *hd = reinterpret_cast<uint32_t *>(sh);
+#pragma unroll 4
+				for (uint32_t i = tid; i < (m + 3u) / 4u; i += T) hd[i] = hs[i];
+				}
 		}
 		else if (MODE == S2_COLUMNS && ss_a && (k0 + j + 1) % snap_stride == 0)
 		{
@@ -822,8 +750,7 @@ __global__ __launch_bounds__(T, 4) void k_columns_stream2(
 			for (uint32_t i = tid; i < m; i += T)
 			{
 				uint2 p;
-				if constexpr (PACK) { uint32_t const pw = PW[i]; p = make_uint2(pw & amask, (pw >> abits) | (narrow ? 0u : ((uint32_t) PH[i] << hshift))); }
-				else p = P[i];
+				uint32_t const pw = PW[i]; p = make_uint2(pw & amask, (pw >> abits) | (narrow ? 0u : ((uint32_t) PH[i] << hshift)));
 				uint32_t const dv = p.y < D0 ? V[p.y] : (uint32_t) (k0 + (p.y - D0) + 1u);
 				if (ss_pack) { ss_a[ob + i] = p.x | (dv << ss_pack); sh[i] = (uint8_t) (dv >> (32u - ss_pack)); }
 				else { ss_a[ob + i] = p.x; ss_d[ob + i] = dv; }

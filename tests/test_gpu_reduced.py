@@ -95,10 +95,7 @@ def _lists_match(ctx, msa, L, every=5):
             assert cnt0 == (c[0] if v[0] == 0 else 0), k
 
 
-@pytest.mark.parametrize("ew", [False, True])
-def test_reduced_lists_match_oracle(pkg, always, ew):
-    if ew:
-        always.setenv("FSEQ_REDUCED_EW", "1")            # small blocks on two waves: the list on a wave of its own
+def test_reduced_lists_match_oracle(pkg, always):
     for (m, n, L, K, Brec, mu, seed, kind, B) in [(200, 1500, 15, 6, 300, 2e-3, 71, 0, 100), (700, 1200, 25, 8, 400, 1e-3, 72, 1, 64),
                                                    (3000, 900, 30, 60, 300, 3e-4, 73, 0, 128)]:
         msa = fso.synth_msa(fso.synth_spec(seed, K, Brec, mu, kind), m, n)
