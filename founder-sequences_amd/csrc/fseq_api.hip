@@ -284,7 +284,7 @@ int prepare_geometry(fseq_ctx *c)
 		HIP_TRY(c, allow_lds(k_colblock_stream<MODE_SNAP, true>, lds));
 		HIP_TRY(c, allow_lds(k_columns_stream<19>, lds));
 		HIP_TRY(c, allow_lds(k_columns_stream<0>, lds));
-		HIP_TRY(c, allow_lds(k_chain_snap_stream, chainsort_lds_bytes()));
+		HIP_TRY(c, allow_lds(k_chain_snap_grouped, pass2_lds_bytes()));
 		HIP_TRY(c, allow_lds(k_cm_emit, stream_lds_bytes(0, false)));
 		// phase C in its second form (fseq_stream2.hpp) while every value id (< m + B) fits the key shift of its tile and the
 		// column is staged (FSEQ_STREAM_PLAIN_SCAN keeps the first form)
@@ -582,7 +582,7 @@ void free_work(fseq_ctx *c)
 	dev_free(c, &c->d_red_cnt); dev_free(c, &c->d_red_cnt_plan); c->red_plan_valid = false; c->red_declined = false; dev_free(c, &c->d_red_vmin); dev_free(c, &c->d_red_rows_alloc); dev_free(c, &c->d_red_leaf_alloc); dev_free(c, &c->d_red_a_alloc); dev_free(c, &c->d_red_d_alloc); c->d_red_rows = c->d_red_leaf = c->d_red_a = c->d_red_d = nullptr;
 	dev_free(c, &c->d_red_invalid); dev_free(c, &c->d_red_blocks); dev_free(c, &c->d_red_msa_alloc); c->d_red_msa = nullptr; c->red_cap = 0; c->red_blocks_cap = 0; c->red_ld = 0; c->red_msa_bytes = 0;
 	dev_free(c, &c->d_red_ss_a_alloc); dev_free(c, &c->d_red_ss_d_alloc); c->d_red_ss_a = c->d_red_ss_d = nullptr; c->red_ss_words = 0;
-	dev_free(c, &c->d_red_cls); dev_free(c, &c->d_red_headd); dev_free(c, &c->d_red_ncls); dev_free(c, &c->d_red_taskblk); dev_free(c, &c->d_red_wgtasks); c->red_task_cap = 0;
+	dev_free(c, &c->d_red_cls); dev_free(c, &c->d_red_headd); dev_free(c, &c->d_red_ncls); dev_free(c, &c->d_red_taskblk); dev_free(c, &c->d_red_wgtasks); dev_free(c, &c->d_red_p2grp); c->red_task_cap = 0;
 	c->red_active = false;
 }
 
@@ -2599,9 +2599,33 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		if ((rc = dev_alloc(c, &c->d_red_ncls, S2))) return rc;
 		if ((rc = dev_alloc(c, &c->d_red_taskblk, S2))) return rc;
 		if ((rc = dev_alloc(c, &c->d_red_wgtasks, 4 * S2 + 64))) return rc;
+		if ((rc = dev_alloc(c, &c->d_red_p2grp, 2 * S2 + 4))) return rc;
 		c->red_task_cap = S2;
 	}
 	if (c->cols_cap < S2) { if ((rc = dev_alloc(c, &c->d_cols, S2))) return rc; c->cols_cap = S2; }
+	// streamed rows: the groups of the chain-step kernel, a block's tasks each (blocks with tasks of that kernel only), the
+	// largest first, and behind them the counter the workgroups take them by
+	std::vector<uint32_t> p2grp;
+	if (c->use_stream)
+	{
+		std::vector<uint2> g;
+		for (size_t i = 0; i < S2; ++i)
+		{
+			if (i == 0 || task_blk[i] != task_blk[i - 1]) g.push_back(make_uint2((uint32_t) i, 0u));
+			++g.back().y;
+		}
+		size_t k = 0;
+		for (auto const &x : g)
+		{
+			bool mine = false;
+			for (uint32_t t = x.x; t < x.x + x.y; ++t) mine = mine || ncls0[t] == 0u;
+			if (mine) g[k++] = x;
+		}
+		g.resize(k);
+		std::stable_sort(g.begin(), g.end(), [](uint2 const &x, uint2 const &y) { return x.y > y.y; });
+		for (auto const &x : g) { p2grp.push_back(x.x); p2grp.push_back(x.y); }
+		p2grp.push_back(0u);
+	}
 	// the task lists through pinned memory of their own (live until the synchronisation behind the kernels)
 	std::vector<uint32_t> hb, hw;
 	std::vector<RedLaunch> ls;
@@ -2616,7 +2640,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 	}
 	{
-		size_t const need = S2 * 16 + hb.size() * 16 + 256;
+		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256;
 		if (c->red_pin2_bytes < need)
 		{
 			if (c->h_red_pin2) (void) hipHostFree(c->h_red_pin2);
@@ -2629,6 +2653,8 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		HIP_TRY(c, hipMemcpyAsync(c->d_cols, put(rbs.data(), S2 * 8), S2 * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(c->d_red_taskblk, put(task_blk.data(), S2 * 4), S2 * 4, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(c->d_red_ncls, put(ncls0.data(), S2 * 4), S2 * 4, hipMemcpyHostToDevice, st));
+		if (!p2grp.empty())
+			HIP_TRY(c, hipMemcpyAsync(c->d_red_p2grp, put(p2grp.data(), p2grp.size() * 4), p2grp.size() * 4, hipMemcpyHostToDevice, st));
 		if (!hb.empty())
 		{
 			HIP_TRY(c, hipMemcpyAsync(c->d_red_wgtasks + 3 * S2, put(hb.data(), hb.size() * 4), hb.size() * 4, hipMemcpyHostToDevice, st));
@@ -2654,15 +2680,21 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		          c->d_snap_a, c->d_snap_d, scan_keyed(c));
 	else
 	{
-		// streamed rows: the step as a radix sort + range maxima in a workspace per workgroup (fseq_chainsort.hpp), the workgroups
-		// take the tasks in turn
-		int ncu = 0;
-		(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
-		size_t const fit = c->ws_words / chainsort_ws_words(m);
-		uint32_t const grid = (uint32_t) std::min<size_t>(std::min<size_t>(S2, fit), (size_t) std::max(ncu, 1) * 2u);
-		if (!grid) return fail(c, FSEQ_E_OOM, "pass 2: the workspace holds no chain step");
-		hipLaunchKernelGGL(k_chain_snap_stream, dim3(grid), dim3(ST), chainsort_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
-		                   c->d_red_headd, c->d_red_ncls, c->red_cap, (uint32_t) S2, c->d_snap_a, c->d_snap_d, c->d_ws);
+		// streamed rows: the step as a radix sort + range maxima in a workspace per workgroup (fseq_chainsort.hpp), a block's
+		// tasks on one workgroup, the groups taken from a counter
+		uint32_t const ngrp = (uint32_t) (p2grp.size() / 2);
+		if (ngrp)
+		{
+			if (c->red_cap > P2_CLS_CAP) return fail(c, FSEQ_E_UNSUPPORTED, "pass 2: more representatives a block than the class table in LDS holds");
+			int ncu = 0;
+			(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
+			size_t const fit = c->ws_words / pass2_ws_words(m);
+			uint32_t const grid = (uint32_t) std::min<size_t>(std::min<size_t>(ngrp, fit), (size_t) std::max(ncu, 1) * 2u);
+			if (!grid) return fail(c, FSEQ_E_OOM, "pass 2: the workspace holds no chain step");
+			hipLaunchKernelGGL(k_chain_snap_grouped, dim3(grid), dim3(ST), pass2_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
+			                   c->d_red_headd, c->d_red_ncls, c->red_cap, reinterpret_cast<uint2 const *>(c->d_red_p2grp), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
+			                   c->d_snap_a, c->d_snap_d, c->d_ws);
+		}
 	}
 	for (size_t i = 0; i < S2; ++i)
 		if (ncls0[i] == 0u && rbs[i] % c->B != 0) cells += (uint64_t) m * 4u;      // (a step is ~4 digit passes over the rows)

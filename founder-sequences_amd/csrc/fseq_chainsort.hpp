@@ -18,8 +18,9 @@
 //   3. every new position: its row, and keyd or the range maximum between the old positions of the two rows (two
 //      block-end look-ups and two table entries, or a scan of at most 63 values inside one block).
 // Everything but the histograms lives in the workgroup's workspace (L2-resident: a few MB).
-// Two forms of the step live here: chain_step_sorted, one step on one workgroup (pass 2's k_chain_snap_stream), and the
-// k_cm_* kernels, phase B's steps spread over the chip (launch_chain in fseq_api.hip, the only streamed phase B).
+// Two forms of the step live here: pass2_step, one step on one workgroup (pass 2's k_chain_snap_grouped, which keeps its records
+// in a workspace of its own, pass2_ws_words), and the k_cm_* kernels, phase B's steps spread over the chip (launch_chain in
+// fseq_api.hip, the only streamed phase B).
 #pragma once
 
 #include <type_traits>
@@ -38,14 +39,6 @@ __host__ __device__ inline size_t chainsort_ws_words(uint32_t m)
 	size_t const nblk = ((size_t) m + 63) / 64;
 	return 8 * (size_t) m + CS_LEVELS * nblk + 64;
 }
-
-struct ChainSortLds {
-	uint32_t hist[ST / WAVE][CS_BINS];           // per wave: digit counts, then the wave's write offsets
-	uint32_t total[CS_BINS];
-	uint32_t scan[ST / WAVE + 1];
-};
-
-__host__ __device__ inline size_t chainsort_lds_bytes() { return carve_bytes(1, sizeof(StreamLds)) + carve_bytes(1, sizeof(ChainSortLds)); }
 
 // lanes of the wave whose digit equals mine (in = this lane holds a row), nbits digit bits
 __device__ __forceinline__ uint64_t cs_match(uint32_t dg, bool in, uint32_t nbits)
@@ -66,25 +59,55 @@ __device__ __forceinline__ uint32_t cs_below(uint64_t mask)
 	return (uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
 }
 
-// One step: (a0, d0) -> (a1, d1) through the key block (rk, kd, nkeys).  w: the workgroup's workspace with a0 d0 at
-// w + off0 .. and a1 d1 at w + off1 .. (each 2m words, off in {0, 2m}); ends with a barrier.
-// cls (pass 2 behind the reduced phase C, k_chain_snap_stream): the key of a row is cls[rk[row]] -- the class of its block
-// key at the boundary's column -- instead of rk[row]
-template <bool P4 = false>
-__device__ __forceinline__ void chain_step_sorted(
-	uint32_t m, uint32_t const *__restrict__ rk, uint32_t const *__restrict__ kd, uint32_t nkeys,
-	uint32_t *w, uint32_t cur, ChainSortLds &S, StreamLds &L, uint32_t const *__restrict__ cls = nullptr,
-	uint32_t const *__restrict__ src_a = nullptr, uint32_t const *__restrict__ src_d = nullptr, uint32_t *__restrict__ dst_a = nullptr, uint32_t *__restrict__ dst_d = nullptr)
+// ------------------------------------------------------------------------------------------------
+// Pass 2 behind the reduced phase C, streamed rows (fseq_reduced.hpp): a boundary inside a block is ONE such step from
+// the block's boundary state, keyed by the classes the block's representatives form at the boundary's column (the tables of
+// k_columns_red): the key of a row is cls[rank[row]].  ncls[t] == 0: the boundary is the block's border (a copy);
+// 0xFFFFFFFF: not this kernel's (k_colblock_stream<MODE_SNAP>).
+// The step is the one at the head of this file, arranged for the bytes it moves (the workspaces of 512 workgroups are far beyond L2 and the
+// Infinity Cache, so every sweep and every gather goes to HBM):
+//   * a workgroup takes all tasks of one block (a group: consecutive tasks with one task_blk) and gathers r[i] =
+//     rank[a0[i]] ONCE for them, as 16 bits (ranks index the task's class table of red_cap <= P2_CLS_CAP entries); every
+//     task of the block then reads r in order, 2 B a row, instead of its own chain of dependent gathers;
+//   * the task's class table (rank -> class, red_cap entries) sits in LDS: the key of a row is cls_lds[r[i]], in the
+//     counting and in the scatter sweep alike (no key buffer);
+//   * step 2 writes ONE 16-byte record per old position, {a0[i], d0[i], prefix max[i], suffix max[i + 1]}: step 3 gathers
+//     rec[hi] only, and takes the suffix maximum at lo = (the previous new position's hi) + 1 from that neighbour's record
+//     (the lane below; lane 0 reads it itself) -- one random access per row instead of four;
+//   * the divergence in front of a class (headd) and the sparse-table entries are loaded only by the rows that use them.
+// Groups are taken from a counter, largest first (the host orders them), so that blocks with many boundaries spread.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t P2_CLS_CAP = 11264;           // most representatives of a reduced block (red_plan's cap)
+
+struct Pass2Lds {
+	uint32_t hist[ST / WAVE][CS_BINS];           // per wave: digit counts, then the wave's write offsets
+	uint32_t total[CS_BINS];
+	uint32_t scan[ST / WAVE + 1];
+	uint32_t grp;                                // the group the workgroup took
+	uint16_t cls[P2_CLS_CAP];                    // the task's class of a rank
+};
+
+__host__ __device__ inline size_t pass2_lds_bytes() { return carve_bytes(1, sizeof(Pass2Lds)); }
+
+// workspace words of one workgroup: r (16-bit) | final pairs (up to 2 words each) | first-pass pairs, then the records
+// (4 words each) | sparse table; every part 16-byte aligned
+__host__ __device__ inline size_t pass2_ws_r(uint32_t m) { return (((size_t) m + 1) / 2 + 3) & ~size_t(3); }
+__host__ __device__ inline size_t pass2_ws_words(uint32_t m)
 {
-	// src_* / dst_* (pass 2): the order in front of the step is read where it lies, the order behind it written where it is wanted
-	// (the workspace then only holds the pairs and the range maxima)
+	size_t const nblk = ((size_t) m + 63) / 64;
+	return pass2_ws_r(m) + 2 * (size_t) m + 4 * (size_t) m + ((CS_LEVELS * nblk + 64 + 3) & ~size_t(3));
+}
+
+// One task: (a0, d0) -> (a1, d1), keys cls_lds[r[i]], D classes with divergences kd[class].  Ends with a barrier.
+template <bool P4>
+__device__ __forceinline__ void pass2_step(
+	uint32_t m, uint16_t const *__restrict__ r, uint32_t const *__restrict__ kd, uint32_t D, uint32_t *w, Pass2Lds &S,
+	uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+{
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	constexpr uint32_t NW = ST / WAVE;
-	uint32_t const *a0 = src_a ? src_a : w + (size_t) cur * 2u * m, *d0 = src_d ? src_d : w + (size_t) cur * 2u * m + m;
-	uint32_t *a1 = w + (size_t) (cur ^ 1u) * 2u * m, *d1 = a1 + m;
-	// P4 [r5]: a pair is ONE word, key << pb | position (pb = bits of m - 1; the caller has checked that the key's bits fit
-	// beside them) -- the sweeps of the sort and the new order move half the bytes
+	// P4: a pair is ONE word, key << pb | position (the caller has checked that the bits fit)
 	using PairT = std::conditional_t<P4, uint32_t, uint2>;
 	uint32_t pb = 1;
 	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
@@ -92,15 +115,16 @@ __device__ __forceinline__ void chain_step_sorted(
 	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
 	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
 	auto pos_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr & pmask; else return pr.y; };
-	PairT *const pairA = reinterpret_cast<PairT *>(a1);                 // (the output buffers are free until step 3)
-	if (dst_a) { a1 = dst_a; d1 = dst_d; }
-	PairT *const pairB = reinterpret_cast<PairT *>(w + 4u * (size_t) m);
-	uint32_t *const pm = w + 6u * (size_t) m, *const sm = w + 7u * (size_t) m, *const tab = w + 8u * (size_t) m;
+	PairT *const pairB = reinterpret_cast<PairT *>(w + pass2_ws_r(m));
+	uint32_t *const xr = w + pass2_ws_r(m) + 2u * (size_t) m;
+	PairT *const pairA = reinterpret_cast<PairT *>(xr);                   // (free once the sort is done: then the records)
+	uint4 *const rec = reinterpret_cast<uint4 *>(xr);
+	uint32_t *const tab = xr + 4u * (size_t) m;
 	uint32_t const nblk = (m + 63u) / 64u;
 
-	// ---- 1. the sort.  bits of a rank, passes of at most 9 bits, the last pass lands in pairB
+	// ---- 1. the sort.  bits of a class, passes of at most 9 bits, the last pass lands in pairB
 	uint32_t bits = 1;
-	while (bits < 32u && ((nkeys - 1u) >> bits) != 0u) ++bits;
+	while (bits < 32u && ((D - 1u) >> bits) != 0u) ++bits;
 	uint32_t const npass = (bits + CS_MAX_DIGIT_BITS - 1u) / CS_MAX_DIGIT_BITS;
 	uint32_t const db = (bits + npass - 1u) / npass, nbins = 1u << db;
 	// a wave's chunk: whole groups of 64 positions
@@ -112,26 +136,16 @@ __device__ __forceinline__ void chain_step_sorted(
 		bool const first = p == 0;
 		PairT const *src = ((npass - p) & 1u) ? pairA : pairB;          // (unused in the first pass)
 		PairT *dst = ((npass - p) & 1u) ? pairB : pairA;
-		// first pass: the pairs are made on the way (rank of the row at position i, i) -- a chain of dependent gathers
-		// (position -> row -> rank [-> class]), followed once: the counting sweep leaves the key in the suffix-maxima buffer
-		// (free until step 2), the scatter sweep reads it there
-		auto load_count = [&](uint32_t i) -> PairT {
-			if (!first) return src[i];
-			uint32_t const key = cls ? cls[rk[a0[i]]] : rk[a0[i]];
-			sm[i] = key;
-			return mk(key, i);
-		};
-		auto load = [&](uint32_t i) -> PairT { return first ? mk(sm[i], i) : src[i]; };
+		// first pass: the pairs are made on the way, in both sweeps, from r and the class table in LDS
+		auto load = [&](uint32_t i) -> PairT { return first ? mk((uint32_t) S.cls[r[i]], i) : src[i]; };
 		for (uint32_t b = lane; b < nbins; b += 64u) S.hist[wave][b] = 0;
 		// (a wave's histogram row is its own: no barrier between clearing and counting; LDS operations of a wave stay in order)
-		// U groups of 64 positions per iteration: their (dependent: position -> row -> rank) loads in flight together -- one
-		// workgroup has a CU to itself here, and a sweep of ~100 round trips to L2 per wave would be all latency
 		constexpr uint32_t U = 4;
 		for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * U)
 		{
 			PairT pr[U];
 #pragma unroll
-			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load_count(i) : mk(0u, 0u); }
+			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load(i) : mk(0u, 0u); }
 #pragma unroll
 			for (uint32_t u = 0; u < U; ++u)
 				if (i0 + u * 64u + lane < c_hi) atomicAdd(&S.hist[wave][(key_of(pr[u]) >> shift) & (nbins - 1u)], 1u);
@@ -168,19 +182,35 @@ __device__ __forceinline__ void chain_step_sorted(
 	}
 	PairT const *perm = pairB;
 
-	// ---- 2. range maxima of the old d: prefix / suffix maxima inside 64-blocks, sparse table over the block maxima
-	for (uint32_t blk = wave; blk < nblk; blk += NW)
+	// ---- 2. the records: prefix / suffix maxima of d0 inside 64-blocks beside a0 and d0, a sparse table over the block maxima
+	// (UB blocks a wave and iteration: their loads in flight together)
+	constexpr uint32_t UB = 4;
+	for (uint32_t b0 = wave; b0 < nblk; b0 += NW * UB)
 	{
-		uint32_t const i = blk * 64u + lane;
-		uint32_t const v = i < m ? d0[i] : 0u;
-		uint32_t const pre = wave_incl_max(v);
-		uint32_t const rev = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((63u - lane) << 2), (int) v);
-		uint32_t const sufr = wave_incl_max(rev);
-		uint32_t const suf = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((63u - lane) << 2), (int) sufr);
-		if (i < m) { pm[i] = pre; sm[i] = suf; }
-		if (lane == 63u) tab[blk] = pre;
+		uint32_t v[UB], a[UB];
+#pragma unroll
+		for (uint32_t u = 0; u < UB; ++u)
+		{
+			uint32_t const i = (b0 + u * NW) * 64u + lane;
+			v[u] = i < m ? d0[i] : 0u;
+			a[u] = i < m ? a0[i] : 0u;
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < UB; ++u)
+		{
+			uint32_t const blk = b0 + u * NW, i = blk * 64u + lane;
+			if (blk >= nblk) break;
+			uint32_t const pre = wave_incl_max(v[u]);
+			uint32_t const rev = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((63u - lane) << 2), (int) v[u]);
+			uint32_t const sufr = wave_incl_max(rev);
+			// the suffix maximum from i + 1: lane 62 - lane of the reversed scan (lane 63's is the next block's maximum, below)
+			uint32_t const sufn = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((62u - min(lane, 62u)) << 2), (int) sufr);
+			if (i < m) rec[i] = make_uint4(a[u], v[u], pre, lane == 63u ? 0u : sufn);
+			if (lane == 63u) tab[blk] = pre;
+		}
 	}
 	__syncthreads();
+	for (uint32_t j = tid; j + 1u < nblk; j += ST) rec[j * 64u + 63u].w = tab[j + 1u];
 	for (uint32_t k = 1; k < CS_LEVELS && (1u << k) <= nblk; ++k)
 	{
 		uint32_t const *lo = tab + (size_t) (k - 1u) * nblk;
@@ -188,9 +218,11 @@ __device__ __forceinline__ void chain_step_sorted(
 		for (uint32_t j = tid; j + (1u << k) <= nblk; j += ST) hi[j] = max(lo[j], lo[j + (1u << (k - 1u))]);
 		__syncthreads();
 	}
+	__syncthreads();
 
-	// ---- 3. the new order (U positions per thread and iteration, their loads side by side; the branches are selects on
-	// clamped look-ups, but for the rare range that lies inside one 64-block)
+	// ---- 3. the new order: position p takes the row of its record; the first of a class takes the class's divergence, any
+	// other the maximum of d0(lo .. hi] = max(suffix max at lo, the blocks between, prefix max at hi), or a scan of at most 63
+	// values where lo and hi share a 64-block.  The positions of a wave are consecutive: the record of p - 1 is the lane below.
 	{
 		constexpr uint32_t U = 4;
 		for (uint32_t p0 = tid; p0 < m; p0 += ST * U)
@@ -204,84 +236,126 @@ __device__ __forceinline__ void chain_step_sorted(
 				me[u] = make_uint2(key_of(pm_), pos_of(pm_));
 				pv[u] = make_uint2(key_of(pp_), pos_of(pp_));
 			}
-			uint32_t row[U], kdv[U], sv[U], pmv[U], t0[U], t1[U], dlast[U];
+			uint4 rc[U];
+			uint32_t z0[U], w0[U], kdv[U], t0[U], t1[U];
 #pragma unroll
 			for (uint32_t u = 0; u < U; ++u)
 			{
-				uint32_t const lo = min(pv[u].y + 1u, m - 1u), hi = me[u].y;
+				uint32_t const p = p0 + u * ST;
+				bool const first = p == 0u || pv[u].x != me[u].x;
+				uint32_t const lo = pv[u].y + 1u, hi = me[u].y;
 				uint32_t const bl = lo >> 6, bh = hi >> 6;
-				uint32_t const cnt = bh > bl + 1u ? bh - bl - 1u : 1u;
-				uint32_t const k = 31u - (uint32_t) __builtin_clz(cnt);
-				uint32_t const *t = tab + (size_t) k * nblk;
-				row[u] = a0[hi];
-				kdv[u] = kd[me[u].x];
-				sv[u] = sm[lo];
-				pmv[u] = pm[hi];
-				dlast[u] = d0[hi];
-				t0[u] = t[min(bl + 1u, nblk - 1u)];
-				t1[u] = t[bh >= (1u << k) ? bh - (1u << k) : 0u];
+				rc[u] = rec[hi];
+				z0[u] = 0u; w0[u] = 0u; kdv[u] = 0u; t0[u] = 0u; t1[u] = 0u;
+				if (lane == 0u && !first) { uint4 const q = rec[pv[u].y]; z0[u] = q.z; w0[u] = q.w; }
+				if (p < m && first) kdv[u] = kd[me[u].x];
+				if (p < m && !first && bh > bl + 1u)
+				{
+					uint32_t const k = 31u - (uint32_t) __builtin_clz(bh - bl - 1u);
+					uint32_t const *t = tab + (size_t) k * nblk;
+					t0[u] = t[bl + 1u];
+					t1[u] = t[bh - (1u << k)];
+				}
 			}
 #pragma unroll
 			for (uint32_t u = 0; u < U; ++u)
 			{
 				uint32_t const p = p0 + u * ST;
+				// the record of p - 1 (old position lo - 1): from the lane below; lane 0 keeps its own load
+				uint32_t const bz = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((lane - 1u) << 2), (int) rc[u].z);
+				uint32_t const bw = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((lane - 1u) << 2), (int) rc[u].w);
 				if (p < m)
 				{
 					bool const first = p == 0u || pv[u].x != me[u].x;
-					uint32_t const lo = pv[u].y + 1u, hi = me[u].y;      // (same rank:) max of d0[lo .. hi], lo <= hi
+					uint32_t const lo = pv[u].y + 1u, hi = me[u].y;      // (same class:) max of d0[lo .. hi], lo <= hi
 					uint32_t const bl = lo >> 6, bh = hi >> 6;
-					uint32_t dv = max(sv[u], pmv[u]);
+					uint32_t const pz = lane ? bz : z0[u], sv = lane ? bw : w0[u];   // prefix max at lo - 1, suffix max at lo
+					uint32_t dv = max(sv, rc[u].z);
 					if (bh > bl + 1u) dv = max(dv, max(t0[u], t1[u]));
 					if (!first && bl == bh)
 					{
-						dv = dlast[u];
-						for (uint32_t i = lo; i < hi; ++i) dv = max(dv, d0[i]);
+						// lo and hi in one 64-block: the prefix maximum at hi is the range's if it grew behind lo - 1 (or lo starts
+						// the block), the suffix maximum at lo if it is larger than the one behind hi (or hi ends the block); else a scan
+						if ((lo & 63u) == 0u || rc[u].z > pz) dv = rc[u].z;
+						else if ((hi & 63u) == 63u || sv > rc[u].w) dv = sv;
+						else
+						{
+							dv = rc[u].y;
+							for (uint32_t i = lo; i < hi; i += 4u)
+							{
+								uint32_t const x0 = d0[i], x1 = i + 1u < hi ? d0[i + 1u] : 0u;
+								uint32_t const x2 = i + 2u < hi ? d0[i + 2u] : 0u, x3 = i + 3u < hi ? d0[i + 3u] : 0u;
+								dv = max(dv, max(max(x0, x1), max(x2, x3)));
+							}
+						}
 					}
-					a1[p] = row[u];
+					a1[p] = rc[u].x;
 					d1[p] = first ? kdv[u] : dv;
 				}
 			}
 		}
 	}
-	(void) L;
 	__syncthreads();
 }
 
-// ------------------------------------------------------------------------------------------------
-// [r5] Pass 2 behind the reduced phase C, streamed rows (fseq_reduced.hpp): a boundary inside a block is ONE such step from
-// the block's boundary state, keyed by the classes the block's representatives form at the boundary's column (the tables of
-// k_columns_red).  Workgroups take the tasks in turn, each in its own workspace.  ncls[t] == 0: the boundary is the block's
-// border (a copy); 0xFFFFFFFF: not this kernel's.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ST) void k_chain_snap_stream(
+__global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 	uint32_t const *__restrict__ bstate_a, uint32_t const *__restrict__ bstate_d, uint32_t const *__restrict__ rank, uint32_t m,
 	uint32_t const *__restrict__ task_blk, uint32_t const *__restrict__ cls, uint32_t const *__restrict__ headd, uint32_t const *__restrict__ ncls,
-	uint32_t cap, uint32_t ntasks, uint32_t *__restrict__ snap_a, uint32_t *__restrict__ snap_d, uint32_t *ws)
+	uint32_t cap, uint2 const *__restrict__ grps, uint32_t ngrp, uint32_t *__restrict__ grp_next, uint32_t *__restrict__ snap_a,
+	uint32_t *__restrict__ snap_d, uint32_t *ws)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	Carver cv{smem};
-	StreamLds &L = *cv.take<StreamLds>(1);
-	ChainSortLds &S = *cv.take<ChainSortLds>(1);
+	Pass2Lds &S = *reinterpret_cast<Pass2Lds *>(smem);
 	uint32_t const tid = threadIdx.x;
-	uint32_t *const w = ws + (size_t) blockIdx.x * chainsort_ws_words(m);
-	for (uint32_t task = blockIdx.x; task < ntasks; task += gridDim.x)
+	uint32_t *const w = ws + (size_t) blockIdx.x * pass2_ws_words(m);
+	uint16_t *const r = reinterpret_cast<uint16_t *>(w);
+	uint32_t pbits = 1;
+	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
+	for (;;)
 	{
-		uint32_t const D = ncls[task];
-		if (D == 0xFFFFFFFFu) continue;
-		size_t const sb = (size_t) task_blk[task] * m, ob = (size_t) task * m;
-		if (D == 0u)
+		if (tid == 0) S.grp = atomicAdd(grp_next, 1u);
+		__syncthreads();
+		uint32_t const g = S.grp;
+		__syncthreads();                                                  // (S.grp is read by all before it is taken again)
+		if (g >= ngrp) break;
+		uint2 const gr = grps[g];
+		size_t const sb = (size_t) task_blk[gr.x] * m;
+		uint32_t const *a0 = bstate_a + sb, *d0 = bstate_d + sb;
+		bool have_r = false;
+		for (uint32_t task = gr.x; task < gr.x + gr.y; ++task)
 		{
-			for (uint32_t i = tid; i < m; i += ST) { snap_a[ob + i] = bstate_a[sb + i]; snap_d[ob + i] = bstate_d[sb + i]; }
-			continue;
+			uint32_t const D = ncls[task];
+			if (D == 0xFFFFFFFFu) continue;
+			size_t const ob = (size_t) task * m;
+			if (D == 0u)
+			{
+				for (uint32_t i = tid; i < m; i += ST) { snap_a[ob + i] = a0[i]; snap_d[ob + i] = d0[i]; }
+				continue;
+			}
+			if (!have_r)
+			{
+				// the block's ranks in the order in front of its boundaries, once for all of them (U loads in flight per thread)
+				constexpr uint32_t U = 4;
+				for (uint32_t i0 = tid; i0 < m; i0 += ST * U)
+				{
+					uint32_t rv[U];
+#pragma unroll
+					for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; rv[u] = i < m ? rank[sb + a0[i]] : 0u; }
+#pragma unroll
+					for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; if (i < m) r[i] = (uint16_t) rv[u]; }
+				}
+				have_r = true;
+			}
+			for (uint32_t j = tid; j < cap; j += ST) S.cls[j] = (uint16_t) cls[(size_t) task * cap + j];
+			__syncthreads();
+			// (the classes and the positions share a word where their bits fit: at most 11,264 classes, 2^18 rows)
+			uint32_t kb = 1;
+			while (kb < 32u && ((D - 1u) >> kb) != 0u) ++kb;
+			if (kb + pbits <= 32u)
+				pass2_step<true>(m, r, headd + (size_t) task * cap, D, w, S, a0, d0, snap_a + ob, snap_d + ob);
+			else
+				pass2_step<false>(m, r, headd + (size_t) task * cap, D, w, S, a0, d0, snap_a + ob, snap_d + ob);
 		}
-		// (the classes of a block's representatives and the positions share a word -- at most 12,288 classes, 2^18 rows)
-		uint32_t kb = 1, pbits = 1;
-		while (kb < 32u && ((D - 1u) >> kb) != 0u) ++kb;
-		while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
-		if (kb + pbits <= 32u)
-			chain_step_sorted<true>(m, rank + sb, headd + (size_t) task * cap, D, w, 0u, S, L, cls + (size_t) task * cap, bstate_a + sb, bstate_d + sb, snap_a + ob, snap_d + ob);
-		else
-			chain_step_sorted<false>(m, rank + sb, headd + (size_t) task * cap, D, w, 0u, S, L, cls + (size_t) task * cap, bstate_a + sb, bstate_d + sb, snap_a + ob, snap_d + ob);
 	}
 }
 

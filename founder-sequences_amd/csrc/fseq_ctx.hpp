@@ -371,6 +371,7 @@ struct fseq_ctx {
 	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives
 	bool red_active = false;                 // this run's phase C went through the representatives (pass 2 follows it)
 	uint32_t *d_red_cls = nullptr, *d_red_headd = nullptr, *d_red_ncls = nullptr, *d_red_taskblk = nullptr, *d_red_wgtasks = nullptr;
+	uint32_t *d_red_p2grp = nullptr;         // streamed pass 2: its groups {first task, count} and the counter they are taken by
 	size_t red_task_cap = 0;
 	uint32_t *d_red_ss_a_alloc = nullptr, *d_red_ss_d_alloc = nullptr;
 	uint32_t *d_red_ss_a = nullptr, *d_red_ss_d = nullptr;      // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
