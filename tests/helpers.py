@@ -64,3 +64,50 @@ def owned_dp_mask(ctx, n, L):
     if final_cell:
         mine[n - L] = True
     return written & mine
+
+
+def founder_mosaic(X, m, n, brec=100, seed=0, copies=None, alphabet=b"ACGT"):
+    """A row-major uint8 alignment [m, n] whose minimum max_segment_size is exactly X (for a segment length well below
+    brec): X random founders; the columns are cut into blocks of brec; every block picks a subset of k_b <= X founders
+    (all X in every third block), every row copies one founder of the subset over the block, and every member of the
+    subset is used by some row.  The segment counts therefore vary from block to block and some reach X.
+
+    copies: the tie-heavy form (m = copies * X).  Every block's subset has k_b founders with m % k_b == 0 (all X in every
+    third block) and every member is copied by exactly m / k_b rows, so all classes of a segment have equal sizes."""
+    rng = np.random.default_rng(seed)
+    assert 1 <= X <= m
+    if copies is not None:
+        assert m == copies * X
+    alpha = np.frombuffer(alphabet, dtype=np.uint8)
+    nb = (n + brec - 1) // brec
+    founders = alpha[rng.integers(0, len(alpha), size=(X, n), dtype=np.uint8)]
+    msa = np.empty((m, n), dtype=np.uint8)
+    divisors = [k for k in range(1, X + 1) if m % k == 0]
+    for b in range(nb):
+        c0, c1 = b * brec, min(n, (b + 1) * brec)
+        if copies is not None:
+            k = X if b % 3 == 0 else int(rng.choice(divisors))
+            subset = rng.choice(X, size=k, replace=False)
+            pick = rng.permutation(np.repeat(subset, m // k))
+        else:
+            k = X if b % 3 == 0 else int(rng.integers(1, X + 1))
+            subset = rng.choice(X, size=k, replace=False)
+            pick = np.concatenate([subset, subset[rng.integers(0, k, size=m - k)]])
+            rng.shuffle(pick)
+        msa[:, c0:c1] = founders[pick, c0:c1]
+    return msa
+
+
+def founder_mosaic_segments(X, m, S, L=20, brec=100, seed=0):
+    """founder_mosaic with exactly S merged segments (blocks whose subsets fit together merge into one segment, so the
+    block count is searched upwards from S).  Returns (msa, the oracle's segment_long result)."""
+    import fso
+    for s in range(seed, seed + 8):
+        for nb in range(S, 2 * S + 2):
+            msa = founder_mosaic(X, m, nb * brec, brec=brec, seed=s)
+            res = fso.segment_long(msa, L)
+            if len(res["reduced"]) == S and res["max_segment_size"] == X:
+                return msa, res
+            if len(res["reduced"]) > S:
+                break
+    raise AssertionError("no mosaic with X = %d and S = %d" % (X, S))

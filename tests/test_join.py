@@ -9,7 +9,7 @@ import pytest
 
 import fso
 import greedy_oracle as go
-from helpers import distinct_count
+from helpers import distinct_count, founder_mosaic
 
 
 @pytest.fixture(scope="module")
@@ -140,6 +140,59 @@ def test_kuhn_munkres_small_known_answer(pkg):
     perm, weights = pkg.bipartite_match_host(m, 3, [0, 10], [10, 20], a, d)
     assert weights.tolist() == [7]
     assert perm.tolist() == [[0, 3, 5], [0, 3, 5]]
+
+
+# ---- the host joiners at large max_segment_size: the reference the device joiners are held to ------------------------
+# Founder mosaics (helpers.founder_mosaic) whose max_segment_size is exactly X: the slot counts around the device kernels'
+# strip edges (64, 128), their LDS limit (181) and past it; the tie-heavy form makes every class of a segment equally large.
+MOSAIC_CASES = [(63, 200, 3300, None), (64, 200, 3300, None), (65, 200, 3300, None), (128, 300, 5000, None),
+                (129, 300, 5000, None), (181, 400, 8000, None), (182, 400, 8000, None),
+                (64, 192, 3300, 3), (130, 260, 3300, 2), (181, 362, 3300, 2)]
+
+
+def mosaic_segmentation(X, m, n, copies, seed=None):
+    msa = founder_mosaic(X, m, n, seed=X if seed is None else seed, copies=copies)
+    res = fso.segment_long(msa, 20)
+    assert res["status"] == 0 and res["max_segment_size"] == X
+    return msa, res
+
+
+def check_bipartite_host(pkg, m, X, res, pairs=None):
+    """bipartite_match_host on the oracle's boundary states: every slot shows a class representative, the copies follow
+    the reference's multiset, and every (sampled) adjacent pair's realised weight is both the returned weight and the
+    optimum of scipy's solver.  Returns the permutations."""
+    red = res["reduced"]
+    S = len(red)
+    perm, weights = pkg.bipartite_match_host(m, X, red["lb"], red["rb"], res["a"], res["d"])
+    assert perm.shape == (S, X) and len(weights) == S - 1
+    cls = [jo.classes(m, int(red["lb"][s]), res["a"][s], res["d"][s]) for s in range(S)]
+    slots = []
+    for s in range(S):
+        assert len(cls[s]) == red["segment_size"][s]
+        sl = jo.slot_classes(perm[s], cls[s])
+        cnt = Counter(sl)
+        assert set(cnt) == set(range(len(cls[s])))
+        assert Counter((len(cls[s][i]), c) for i, c in cnt.items()) == jo.bipartite_copy_multiset(m, X, cls[s])
+        slots.append(sl)
+    for s in (range(1, S) if pairs is None else pairs):
+        best, base = jo.optimal_weight(slots[s - 1], cls[s - 1], slots[s], cls[s])
+        realised = sum(int(base[l, r]) for l, r in zip(slots[s - 1], slots[s]))
+        assert realised == best == int(weights[s - 1]), s
+    return perm
+
+
+@pytest.mark.parametrize("X,m,n,copies", MOSAIC_CASES)
+def test_host_joiners_at_large_slot_counts(pkg, X, m, n, copies):
+    msa, res = mosaic_segmentation(X, m, n, copies)
+    red = res["reduced"]
+    S = len(red)
+    assert S > 20 and (red["segment_size"] == X).any()
+    if copies is None:
+        assert (red["segment_size"] < X).any()                  # texts sorted by size and placeholder copies too
+    segs = [(int(x["lb"]), int(x["rb"])) for x in red]
+    perm = pkg.greedy_match_host(m, X, red["lb"], red["rb"], res["a"], res["d"])
+    assert perm.tolist() == go.greedy_match(m, X, segs, res["a"], res["d"])
+    check_bipartite_host(pkg, m, X, res)
 
 
 @pytest.mark.gpu
