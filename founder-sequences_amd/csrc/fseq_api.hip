@@ -61,6 +61,7 @@ constexpr uint64_t STREAM_BLOCK_TARGET_ALL_ROWS = 1600;   // columns per block t
 // [r5] ... and when phase C runs on the blocks' representatives: a block of ~800 columns of BASELINE C4 has ~6,600 of them, and
 // the ~10,700 of a block in which the founders recombine still fit the largest configuration (11,264)
 constexpr uint64_t STREAM_BLOCK_TARGET_REDUCED = 800;
+constexpr uint8_t RED_FORCE_FULL = 1, RED_FORCE_WIDE = 2;    // fseq_ctx::red_force_full[b]
 constexpr size_t RED_SIDE_STREAMS = 3;                    // side streams the reduced configurations' launches may use (red_launch_all)
 #define STREAM_BLOCK_TARGET (c->tune.no_reduced ? STREAM_BLOCK_TARGET_ALL_ROWS : STREAM_BLOCK_TARGET_REDUCED)
 #ifndef FSEQ_X_FLOOR_VALUE
@@ -1879,12 +1880,14 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 			h_blocks[listed++] = b;
 			max_rows = std::max(max_rows, r);
 			int cf = -1, cs = -1;
-			for (int i = 0; i < nconf; ++i) if (usable[(size_t) i] && sets[(size_t) i].rows >= r) { cf = i; break; }
+			// (a block the slim configuration refused -- more distinct start values than its table holds -- skips it)
+			bool const wide = c->red_force_full[b] == RED_FORCE_WIDE;
+			for (int i = 0; i < nconf; ++i) if (usable[(size_t) i] && sets[(size_t) i].rows >= r && !(wide && sets[(size_t) i].values < sets[(size_t) i].rows)) { cf = i; break; }
 			for (int i = 0; i < nconf; ++i) if (usable_snap[(size_t) i] && sets[(size_t) i].rows >= r) { cs = i; break; }
 			c->red_config_of[b] = cf;
 			c->red_config_snap_of[b] = cs;
 		}
-		bool const full = r == RED_NONE || c->red_config_of[b] < 0 || c->red_force_full[b] || (uint64_t) r * 10u > (uint64_t) m * 7u;
+		bool const full = r == RED_NONE || c->red_config_of[b] < 0 || c->red_force_full[b] == RED_FORCE_FULL || (uint64_t) r * 10u > (uint64_t) m * 7u;
 		if (full) { c->red_full[b] = 1; ++n_full; }
 		else { per[(size_t) c->red_config_of[b]].push_back(b); sum_rows += r; }
 	}
@@ -1900,8 +1903,11 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 			{
 				uint64_t sr = 0;
 				for (uint32_t b : per[(size_t) i]) sr += c->red_cnt_host[b];
-				fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average\n", sets[(size_t) i].rows, per[(size_t) i].size(),
-				        (unsigned long long) (sr / per[(size_t) i].size()));
+				ReducedSet const &rs = sets[(size_t) i];
+				size_t const lds = rs.lds(c->B, red_symcap(c, rs, c->red_direct));
+				uint32_t const res = rs.prepare(lds) == hipSuccess ? rs.resident(lds) : 0u;
+				fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU)\n",
+				        rs.rows, per[(size_t) i].size(), (unsigned long long) (sr / per[(size_t) i].size()), rs.T, rs.E, rs.values, lds, res);
 			}
 	// worth it?  The run on all rows is the tuned one (three workgroups per CU, stride states for pass 2), and a row of a small
 	// reduced workgroup costs more than a row there: the representatives take over where they are clearly fewer -- rows to
@@ -1977,6 +1983,12 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 	// dependent launches of phase B, measured on BASELINE C3: 0.71 ms with none, 0.97 with three)
 	size_t const nside = std::min<size_t>(ls.size() - 1, RED_SIDE_STREAMS);
 	if (nside) HIP_TRY(c, hipEventRecord(c->red_ev[3], st));
+	// [r7] queued largest workgroups first (the blocks of ten thousand representatives are not the tail of the phase, as pass 2's
+	// largest groups are not); the launch with the most blocks stays on the context's stream, the others take the side streams
+	// in that order and, past those, the context's
+	size_t main_i = 0;
+	for (size_t i = 1; i < ls.size(); ++i) if (ls[i].count > ls[main_i].count) main_i = i;
+	size_t side = 0;
 	for (size_t i = 0; i < ls.size(); ++i)
 	{
 		ReducedSet rs;
@@ -1987,16 +1999,16 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 		HIP_TRY(c, rs.prepare(lds));
 		RA.blocks = blocks + ls[i].first;
 		if (wg_tasks) RA.wg_tasks = wg_tasks + 3 * (size_t) ls[i].first;
-		// the largest launches on the side streams, the rest in turn on the context's
-		hipStream_t s_ = (i >= 1 && i <= nside) ? (i == 1 ? c->stream2 : c->red_st[i - 2]) : st;
-		if (s_ != st && s_ == nullptr)
+		hipStream_t s_ = st;
+		size_t const slot = (i != main_i && side < nside) ? side++ : nside;      // (nside: the context's stream)
+		if (slot < nside)
 		{
-			HIP_TRY(c, hipStreamCreateWithFlags(&c->red_st[i - 2], hipStreamNonBlocking));
-			s_ = c->red_st[i - 2];
+			if (slot >= 1 && !c->red_st[slot - 1]) HIP_TRY(c, hipStreamCreateWithFlags(&c->red_st[slot - 1], hipStreamNonBlocking));
+			s_ = slot == 0 ? c->stream2 : c->red_st[slot - 1];
+			HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev[3], 0));
 		}
-		if (s_ != st) HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev[3], 0));
 		rs.launch(s_, ls[i].count, lds, c->red_direct ? c->d_msa : c->d_red_msa, c->red_direct ? c->ld : c->red_ld, n, c->B, (uint32_t) L, X, stride, ent, hdr, c->npass, c->bsh, RA);
-		if (s_ != st) HIP_TRY(c, hipEventRecord(c->red_ev[i - 1], s_));
+		if (slot < nside) HIP_TRY(c, hipEventRecord(c->red_ev[slot], s_));
 	}
 	for (size_t i = 0; i < nside; ++i) HIP_TRY(c, hipStreamWaitEvent(st, c->red_ev[i], 0));
 	HIP_TRY(c, hipGetLastError());
@@ -2010,8 +2022,8 @@ int red_columns(fseq_ctx *c)
 	red_fill_args(c, RA);
 	std::vector<RedLaunch> ls;
 	for (auto const &bin : c->red_bins) ls.push_back(RedLaunch{bin.config, bin.first, bin.count});
-	// (the configuration with the most blocks first: it stays on the context's stream)
-	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
+	// (the bins ascend by the rows a workgroup holds: the largest first)
+	std::reverse(ls.begin(), ls.end());
 	return red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride);
 }
 
@@ -2378,7 +2390,7 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 					std::vector<uint32_t> inv(c->nblocks);
 					HIP_TRY(c, hipMemcpy(inv.data(), c->d_red_invalid, (size_t) c->nblocks * 4, hipMemcpyDeviceToHost));
 					uint32_t cnt = 0;
-					for (uint32_t b = b_lo; b < b_hi; ++b) if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = 1; ++cnt; }
+					for (uint32_t b = b_lo; b < b_hi; ++b) if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = inv[b] == RED_WIDE ? RED_FORCE_WIDE : RED_FORCE_FULL; ++cnt; }
 					c->red_plan_valid = false;
 					R.redone += cnt;
 				}
@@ -2431,8 +2443,10 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 		std::vector<uint32_t> inv(c->nblocks);
 		HIP_TRY(c, hipMemcpy(inv.data(), c->d_red_invalid, (size_t) c->nblocks * 4, hipMemcpyDeviceToHost));
 		uint32_t cnt = 0;
-		for (uint32_t b = 0; b < c->nblocks; ++b) if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = 1; ++cnt; }
-		if (c->tune.debug) fprintf(stderr, "[fseq] reduced phase C: the lists of %u blocks reach below what their representatives vouch for: those blocks again on all rows\n", cnt);
+		uint32_t wide = 0;
+		for (uint32_t b = 0; b < c->nblocks; ++b) if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = inv[b] == RED_WIDE ? RED_FORCE_WIDE : RED_FORCE_FULL; ++cnt; wide += inv[b] == RED_WIDE ? 1u : 0u; }
+		if (c->tune.debug) fprintf(stderr, "[fseq] reduced phase C: the lists of %u blocks reach below what their representatives vouch for: those blocks again on all rows\n", cnt - wide);
+		if (c->tune.debug && wide) fprintf(stderr, "[fseq] reduced phase C: %u blocks hold more distinct start values than the slim configuration's table: those blocks again on the next configuration\n", wide);
 		if (cnt) { c->red_plan_valid = false; R.redo = true; R.redone += cnt; *overflow_out = false; return FSEQ_OK; }
 	}
 	if (keyspace)

@@ -62,7 +62,7 @@ struct Stream2Config { uint32_t T, E, key_shift; size_t (*lds)(uint32_t colbytes
 	                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &); };
 // [r5] phase C on representative rows (fseq_reduced.hpp; the kernels live in csrc/fseq_reduced.hip)
 struct ReducedSet {
-	uint32_t T, E, rows;                     // rows: representatives a workgroup holds
+	uint32_t T, E, rows, values;             // rows: representatives a workgroup holds; values: distinct start values (fewer than rows: the slim configuration)
 	bool pk, ew;
 	size_t (*lds)(uint32_t B, uint32_t symcap);   // symcap: bytes of each staged-column buffer (RedArgs)
 	hipError_t (*prepare)(size_t lds);
@@ -368,7 +368,8 @@ struct fseq_ctx {
 	size_t red_ld = 0, red_msa_bytes = 0;
 	std::vector<uint32_t> red_cnt_host;      // representatives per block of the last prep (RED_NONE: not reduced)
 	std::vector<uint8_t> red_full;           // blocks this run sends to the kernel on all rows
-	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives
+	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives (1); 2: the block
+	                                         // stays reduced but skips the slim configuration, which refused it
 	bool red_active = false;                 // this run's phase C went through the representatives (pass 2 follows it)
 	uint32_t *d_red_cls = nullptr, *d_red_headd = nullptr, *d_red_ncls = nullptr, *d_red_taskblk = nullptr, *d_red_wgtasks = nullptr;
 	uint32_t *d_red_p2grp = nullptr;         // streamed pass 2: its groups {first task, count} and the counter they are taken by

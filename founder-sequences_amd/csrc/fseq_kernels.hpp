@@ -690,18 +690,32 @@ __global__ __launch_bounds__(T) void k_chain(
 // (nine and ten rows of the 16-bit configurations: the two-level form, fseq_core.hpp)
 __host__ __device__ constexpr bool columns_pairwise(int T, int E, int SIGMA, bool PK = false)
 {
+	// (not the slim configuration, declared below: fifteen rows in two halves need 179 VGPRs, and its two workgroups per CU leave 128)
+	if (PK && T == 512 && E == 15) return false;
 	return SIGMA == 4 && ((E >= 2 && E <= FSEQ_PW_MAX_E && !(T >= 1024 && E >= 7 && !PK)) || (PK && E >= 9 && T * E <= 10240));
 }
 
 // the resolve of a step as a read of per-thread run slots (partition_step's FM): wherever 4 * T more words of LDS are to be had
 __host__ __device__ constexpr bool columns_lookup(int T, int E, int SIGMA, bool PK) { return columns_pairwise(T, E, SIGMA, PK) || (SIGMA == 4 && PK && T * E <= 10240); }
-__host__ __device__ constexpr size_t columns_run_words(int T, int E, int SIGMA, bool PK) { return columns_pairwise(T, E, SIGMA, PK) ? 5 * (size_t) T : columns_lookup(T, E, SIGMA, PK) ? 4 * (size_t) T : 0; }
+// (five slots per thread where a thread may hold an unused position, symbol 4: the pairwise pass writes it, the slim configuration's lookup reads it)
+__host__ __device__ constexpr size_t columns_run_words(int T, int E, int SIGMA, bool PK) { return (columns_pairwise(T, E, SIGMA, PK) || (PK && T == 512 && E == 15)) ? 5 * (size_t) T : columns_lookup(T, E, SIGMA, PK) ? 4 * (size_t) T : 0; }
+
+// [r7] the slim configuration (512 threads, fifteen rows each, 16-bit: the rows of 1024 x 7 with a list wave): two of its
+// workgroups share a CU -- four waves per SIMD, 128 VGPRs, 80 KB of LDS each -- so the value table and the id histogram are
+// sized for the distinct start values a block has (BASELINE C4: ~1,750 of ~6,600 rows), not for one per row.  A block with
+// more refuses (red.invalid = RED_WIDE) and the plan puts it on the next configuration.
+constexpr int SLIM_T = 512, SLIM_E = 15, SLIM_VALUES = 4096;
+__host__ __device__ constexpr bool columns_slim(int T, int E, bool PK) { return PK && T == SLIM_T && E == SLIM_E; }
+// distinct start values a workgroup holds (V_l, and with the block's columns the ids of cnt_l)
+__host__ __device__ constexpr size_t columns_value_cap(int T, int E, bool PK) { return columns_slim(T, E, PK) ? (size_t) SLIM_VALUES : (size_t) T * E; }
+// waves per SIMD the register budget is held to: the 16-bit 512-thread kernels three workgroups per CU, the slim one two
+__host__ __device__ constexpr int columns_min_waves(int T, int E, bool PK) { return columns_slim(T, E, PK) ? 4 : (PK && T == 512) ? 6 : 4; }
 
 template <int T, int E, int SIGMA, bool PK>
 __host__ __device__ inline size_t columns_lds_bytes(uint32_t B)
 {
-	constexpr size_t CAP = (size_t) T * E;
-	return 2 * carve_bytes(CAP, PK ? 2 : 4) + 2 * carve_bytes(CAP, 1) + carve_bytes(PK ? (CAP + B + 9) / 2 : CAP + B + 8, 4) + carve_bytes(CAP, 4)
+	constexpr size_t CAP = (size_t) T * E, VCAP = columns_value_cap(T, E, PK);
+	return 2 * carve_bytes(CAP, PK ? 2 : 4) + 2 * carve_bytes(CAP, 1) + carve_bytes(PK ? (VCAP + B + 9) / 2 : VCAP + B + 8, 4) + carve_bytes(VCAP, 4)
 	     + carve_bytes(1, sizeof(StepScratch<T, SIGMA>)) + carve_bytes(T / WAVE + 1, 4) + (columns_run_words(T, E, SIGMA, PK) ? carve_bytes(columns_run_words(T, E, SIGMA, PK), 4) : 0);
 }
 
@@ -770,7 +784,8 @@ __device__ __forceinline__ void columns_body(char *smem,
 	// colmask (4-bit symbols, or nullptr): the codes present in every column (k_column_presence)
 	// workgroup i of the launch owns column block block0 + i (phase C may be launched in several parts)
 	FSEQ_CLOCK_STAMP(blockIdx.x, 0);
-	constexpr uint32_t CAP = T * E;
+	constexpr uint32_t CAP = T * E, VCAP = (uint32_t) columns_value_cap(T, E, PK);
+	static_assert(VCAP == CAP || RED, "a value table smaller than the rows: the reduced kernel, which can refuse a block");
 	uint32_t const blk = RED ? red.blocks[blockIdx.x] : (blocklist ? blocklist[blockIdx.x] : blockIdx.x + block0);
 	uint32_t red_vmin = 0, red_deficit = 0, t_first = 0, t_count = 0, t_next = 0;
 	bool const red_snap = RED && red.cls != nullptr;
@@ -791,8 +806,8 @@ __device__ __forceinline__ void columns_body(char *smem,
 	AT *d_l = cv.take<AT>(CAP);
 	uint8_t *sym0 = cv.take<uint8_t>(RED ? red.symcap : CAP);
 	uint8_t *sym1 = cv.take<uint8_t>(RED ? red.symcap : CAP);
-	uint32_t *cnt_l = cv.take<uint32_t>(PK ? (CAP + B + 9) / 2 : CAP + B + 8);
-	uint32_t *V_l = cv.take<uint32_t>(CAP);
+	uint32_t *cnt_l = cv.take<uint32_t>(PK ? (VCAP + B + 9) / 2 : VCAP + B + 8);
+	uint32_t *V_l = cv.take<uint32_t>(VCAP);
 	StepScratch<T, SIGMA> &scr = *cv.take<StepScratch<T, SIGMA>>(1);
 	uint32_t *sscr = cv.take<uint32_t>(T / WAVE + 1);
 	constexpr bool PW = columns_pairwise(T, E, SIGMA, PK);
@@ -867,7 +882,7 @@ __device__ __forceinline__ void columns_body(char *smem,
 			uint32_t w = block_excl_add<T>(mine, sscr, &D0);
 			uint32_t N2s = 2;
 			while (N2s < D0) N2s <<= 1;
-			if (N2s <= CAP)
+			if (N2s <= VCAP)
 			{
 				for (uint32_t q = 0; q < per; ++q)
 					if (start + q < NT && sb[start + q] != PAD_KEY) V_l[w++] = sb[start + q];
@@ -878,6 +893,15 @@ __device__ __forceinline__ void columns_body(char *smem,
 			}
 		}
 		__syncthreads();
+		if constexpr (VCAP < CAP)
+		{
+			// (more distinct values than the table holds, or no slot for one: not a block for this configuration)
+			if (!have_values)
+			{
+				if (tid == 0) { red.invalid[blk] = RED_WIDE; red.any_invalid[0] = 1u; }
+				return;
+			}
+		}
 	}
 	if (!have_values)
 	{
@@ -965,8 +989,8 @@ __device__ __forceinline__ void columns_body(char *smem,
 	__syncthreads();
 
 	bool const zero_present = (V_l[0] == 0u);
-	// (see the pass loop; compiled into the nine-to-eleven-row kernels only -- the 512-thread 16-bit kernels have no register to spare)
-	constexpr bool CARRY_OK = PK && E >= 9;
+	// (see the pass loop; compiled into the nine-to-eleven-row kernels only -- the 512-thread 16-bit kernels, the slim one among them, have no register to spare)
+	constexpr bool CARRY_OK = PK && E >= 9 && !columns_slim(T, E, PK);
 	bool const carry = CARRY_OK && npass == 2u && bsh == 1u && ((RED && red.direct) ? red.m_true : m) <= 16384u;
 #ifdef FSEQ_KC_STAMPS
 	long long kc_work = 0, kc_wait = 0, kc_last = clock64();
@@ -1334,7 +1358,7 @@ __global__ __launch_bounds__(T, (PK && T == 512) ? 6 : 4) void k_columns(
 
 // [r5] the same on a block's representative rows (msa / ld: the reduced alignment; red: fseq_types.hpp)
 template <int T, int E, int SIGMA, bool PK, bool EW = false>
-__global__ __launch_bounds__(T, (PK && T == 512) ? 6 : 4) void k_columns_red(
+__global__ __launch_bounds__(T, columns_min_waves(T, E, PK)) void k_columns_red(
 	uint8_t const *__restrict__ msa, size_t ld, uint64_t n, uint32_t B,
 	uint32_t L, uint32_t X, uint32_t stride, uint2 *__restrict__ ent, uint4 *__restrict__ hdr, uint32_t npass, uint32_t bsh, RedArgs const red)
 {

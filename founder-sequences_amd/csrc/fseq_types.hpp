@@ -19,6 +19,7 @@ struct S2SnapArgs;                   // fseq_stream2.hpp: the boundaries of a pa
 // [r5] Phase C on a block's REPRESENTATIVE rows (fseq_reduced.hpp): what k_reduce_prep left for every block and where a
 // workgroup of the reduced column kernel finds it.  Plain pointers into device memory.
 constexpr uint32_t RED_NONE = 0xFFFFFFFFu;      // cnt[b]: block b is not reduced (more representatives than the kernel holds)
+constexpr uint32_t RED_WIDE = 2u;               // invalid[b]: the block has more distinct start values than its configuration's table holds
 struct RedArgs {
 	uint32_t const *cnt = nullptr;      // [block] representatives of the block
 	uint32_t const *vmin = nullptr;     // [block] the values >= vmin are those of the run on all rows (1: every value is)
@@ -26,7 +27,7 @@ struct RedArgs {
 	uint32_t const *d = nullptr;        // [block][cap] ... and the maximum of d0 over the positions skipped since the last kept row
 	uint32_t const *leaf = nullptr;     // [block][cap] block-key rank of representative i (pass 2)
 	uint32_t const *blocks = nullptr;   // [workgroup] block of workgroup i of the launch
-	uint32_t *invalid = nullptr;        // [block] set when a list of the block took an entry the representatives cannot vouch for
+	uint32_t *invalid = nullptr;        // [block] 1 when a list of the block took an entry the representatives cannot vouch for (RED_WIDE: see there)
 	uint32_t cap = 0;                   // row stride of a / d / leaf (and of cls / headd)
 	uint32_t m_true = 0;                // rows of the alignment
 	uint32_t direct = 0;                // 1: a[] holds ROW IDS and msa / ld are the alignment itself (its whole column is staged: colbytes);
