@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -98,10 +99,8 @@ U *pin_take(fseq_ctx *c, size_t count)
 
 void free_msa(fseq_ctx *c)
 {
-	if (c->own_msa) dev_free(c, &c->d_msa_alloc);
-	c->d_msa_alloc = nullptr;
+	c->d_msa_own.release(c);
 	c->d_msa = nullptr;
-	c->own_msa = false;
 	c->have_input = false;
 }
 
@@ -114,10 +113,9 @@ int alloc_msa(fseq_ctx *c)
 	free_msa(c);
 	c->bsh = c->sigma <= 4 ? 2u : c->sigma <= 16 ? 1u : 0u;
 	c->ld = ((size_t) sym_bytes(c->p.m, c->bsh) + 15) & ~size_t(15);
-	int rc = dev_alloc(c, &c->d_msa_alloc, c->ld * (held_hi(c) - held_lo(c)) + 16);
+	int rc = c->d_msa_own.alloc(c, c->ld * (held_hi(c) - held_lo(c)) + 16);
 	if (rc) return rc;
-	c->d_msa = c->d_msa_alloc - held_lo(c) * c->ld;          // column k at d_msa + k * ld for the held columns
-	c->own_msa = true;
+	c->d_msa = c->d_msa_own.base - held_lo(c) * c->ld;       // column k at d_msa + k * ld for the held columns
 	return FSEQ_OK;
 }
 
@@ -397,65 +395,84 @@ int prepare_geometry(fseq_ctx *c)
 	return FSEQ_OK;
 }
 
+void release_levels(fseq_ctx *c)
+{
+	for (auto &lv : c->levels) release_all(c, lv.rank, lv.keyd, lv.nkeys, lv.state_a, lv.state_d);
+	c->levels.clear();
+}
+
+// the buffers whose sizes follow from the geometry alone: per column block, per column, per DP entry
+int alloc_geometry_buffers(fseq_ctx *c)
+{
+	fseq_params const &p = c->p;
+	size_t const m = p.m;
+	int rc;
+	// my blocks [bl, bh) (all of them when not sharded); boundary states also behind my last block
+	size_t const bl = c->sh.on ? c->sh.b_lo : 0, bh = c->sh.on ? std::max(c->sh.b_hi, c->sh.b_lo) : c->nblocks;
+	if ((rc = c->d_rank.alloc_range(c, bl, bh, m))) return rc;
+	if ((rc = c->d_keyd.alloc_range(c, bl, bh, m))) return rc;
+	if ((rc = c->d_nkeys.alloc_range(c, bl, bh, 1))) return rc;
+	if ((rc = c->d_bstate_a.alloc_range(c, bl, bh + 1, m))) return rc;
+	if ((rc = c->d_bstate_d.alloc_range(c, bl, bh + 1, m))) return rc;
+	{
+		// the composites of phase B, level by level: until at most chain_fan are left, or -- sharded -- shard_k levels below
+		// the hyper key blocks (indexed like the blocks: by their place in the whole alignment; a rank holds its own range)
+		uint32_t cnt = c->nblocks;
+		uint64_t cols = c->B;
+		size_t lo = bl, hi = bh;
+		for (uint32_t i = 0; c->sh.on ? i < c->shard_k : cnt > c->chain_fan; ++i)
+		{
+			fseq_ctx::ChainLevel lv;
+			lv.count = (cnt + c->chain_fan - 1) / c->chain_fan;
+			lv.cols = cols * c->chain_fan;
+			lo = lo / c->chain_fan; hi = (hi + c->chain_fan - 1) / c->chain_fan;
+			c->levels.push_back(lv);                               // (pushed at once: release_levels releases what is there)
+			fseq_ctx::ChainLevel &L = c->levels.back();
+			if ((rc = L.rank.alloc_range(c, lo, hi, m))) return rc;
+			if ((rc = L.keyd.alloc_range(c, lo, hi, m))) return rc;
+			if ((rc = L.nkeys.alloc_range(c, lo, hi, 1))) return rc;
+			if ((rc = L.state_a.alloc_range(c, lo, hi + 1, m))) return rc;
+			if ((rc = L.state_d.alloc_range(c, lo, hi + 1, m))) return rc;
+			cnt = L.count; cols = L.cols;
+		}
+	}
+	if (c->sh.on && c->n_hyper)
+	{
+		if ((rc = c->d_hrank.alloc(c, (size_t) c->n_hyper * m))) return rc;
+		if ((rc = c->d_hkeyd.alloc(c, (size_t) c->n_hyper * m))) return rc;
+		if ((rc = c->d_hnkeys.alloc(c, c->n_hyper))) return rc;
+		if ((rc = c->d_hstate_a.alloc(c, ((size_t) c->n_hyper + 1) * m))) return rc;
+		if ((rc = c->d_hstate_d.alloc(c, ((size_t) c->n_hyper + 1) * m))) return rc;
+	}
+	if ((rc = c->d_hdr.alloc(c, p.n))) return rc;
+	if ((rc = c->d_flags.alloc(c, 256))) return rc;
+	if ((rc = c->d_recent.alloc(c, c->nblocks + 1))) return rc;
+	if (p.n >= 2 * p.segment_length)
+	{
+		c->dp_size = p.n - p.segment_length + 1;
+		c->dp.tstride = (uint32_t) (c->dp_size / 64 + 2);
+		if ((rc = c->dp.M.alloc(c, c->dp_size))) return rc;
+		if ((rc = c->dp.LB.alloc(c, c->dp_size))) return rc;
+		if ((rc = c->dp.SZ.alloc(c, c->dp_size))) return rc;
+		if ((rc = c->dp.K.alloc(c, c->dp_size + 64))) return rc;
+		if ((rc = c->dp.Tb.alloc(c, (size_t) 32 * c->dp.tstride))) return rc;
+		if ((rc = c->dp.Tbv.alloc(c, (size_t) 32 * c->dp.tstride))) return rc;
+		if ((rc = c->d_Mprev.alloc(c, c->dp_size))) return rc;
+	}
+	return FSEQ_OK;
+}
+
 int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 {
 	fseq_params const &p = c->p;
 	size_t const m = p.m;
 	int rc;
-	if (!c->d_rank)
+	if (!c->d_rank && (rc = alloc_geometry_buffers(c)))
 	{
-		// my blocks [bl, bh) (all of them when not sharded); boundary states also behind my last block
-		size_t const bl = c->sh.on ? c->sh.b_lo : 0, bh = c->sh.on ? std::max(c->sh.b_hi, c->sh.b_lo) : c->nblocks;
-		if ((rc = dev_alloc_range(c, &c->d_rank_alloc, &c->d_rank, bl, bh, m))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_keyd_alloc, &c->d_keyd, bl, bh, m))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_nkeys_alloc, &c->d_nkeys, bl, bh, 1))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_bstate_a_alloc, &c->d_bstate_a, bl, bh + 1, m))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_bstate_d_alloc, &c->d_bstate_d, bl, bh + 1, m))) return rc;
-		{
-			// the composites of phase B, level by level: until at most chain_fan are left, or -- sharded -- shard_k levels below
-			// the hyper key blocks (indexed like the blocks: by their place in the whole alignment; a rank holds its own range)
-			uint32_t cnt = c->nblocks;
-			uint64_t cols = c->B;
-			size_t lo = bl, hi = bh;
-			for (uint32_t i = 0; c->sh.on ? i < c->shard_k : cnt > c->chain_fan; ++i)
-			{
-				fseq_ctx::ChainLevel lv;
-				lv.count = (cnt + c->chain_fan - 1) / c->chain_fan;
-				lv.cols = cols * c->chain_fan;
-				lo = lo / c->chain_fan; hi = (hi + c->chain_fan - 1) / c->chain_fan;
-				c->levels.push_back(lv);                               // (pushed at once: free_work releases what is there)
-				fseq_ctx::ChainLevel &L = c->levels.back();
-				if ((rc = dev_alloc_range(c, &L.rank_alloc, &L.rank, lo, hi, m))) return rc;
-				if ((rc = dev_alloc_range(c, &L.keyd_alloc, &L.keyd, lo, hi, m))) return rc;
-				if ((rc = dev_alloc_range(c, &L.nkeys_alloc, &L.nkeys, lo, hi, 1))) return rc;
-				if ((rc = dev_alloc_range(c, &L.state_a_alloc, &L.state_a, lo, hi + 1, m))) return rc;
-				if ((rc = dev_alloc_range(c, &L.state_d_alloc, &L.state_d, lo, hi + 1, m))) return rc;
-				cnt = L.count; cols = L.cols;
-			}
-		}
-		if (c->sh.on && c->n_hyper)
-		{
-			if ((rc = dev_alloc(c, &c->d_hrank, (size_t) c->n_hyper * m))) return rc;
-			if ((rc = dev_alloc(c, &c->d_hkeyd, (size_t) c->n_hyper * m))) return rc;
-			if ((rc = dev_alloc(c, &c->d_hnkeys, c->n_hyper))) return rc;
-			if ((rc = dev_alloc(c, &c->d_hstate_a, ((size_t) c->n_hyper + 1) * m))) return rc;
-			if ((rc = dev_alloc(c, &c->d_hstate_d, ((size_t) c->n_hyper + 1) * m))) return rc;
-		}
-		if ((rc = dev_alloc(c, &c->d_hdr, p.n))) return rc;
-		if ((rc = dev_alloc(c, &c->d_flags, 256))) return rc;
-		if ((rc = dev_alloc(c, &c->d_recent, c->nblocks + 1))) return rc;
-		if (p.n >= 2 * p.segment_length)
-		{
-			c->dp_size = p.n - p.segment_length + 1;
-			c->dp.tstride = (uint32_t) (c->dp_size / 64 + 2);
-			if ((rc = dev_alloc(c, &c->dp.M, c->dp_size))) return rc;
-			if ((rc = dev_alloc(c, &c->dp.LB, c->dp_size))) return rc;
-			if ((rc = dev_alloc(c, &c->dp.SZ, c->dp_size))) return rc;
-			if ((rc = dev_alloc(c, &c->dp.K, c->dp_size + 64))) return rc;
-			if ((rc = dev_alloc(c, &c->dp.Tb, (size_t) 32 * c->dp.tstride))) return rc;
-			if ((rc = dev_alloc(c, &c->dp.Tbv, (size_t) 32 * c->dp.tstride))) return rc;
-			if ((rc = dev_alloc(c, &c->d_Mprev, c->dp_size))) return rc;
-		}
+		// (all of them or none: d_rank stands for the rest, and the levels are pushed as they are allocated)
+		release_levels(c);
+		c->d_rank.release(c);
+		return rc;
 	}
 	if (c->use_stream && !c->d_ws)
 	{
@@ -463,33 +480,30 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		// and pass 2 index the same memory by workgroup (4m words each)
 		size_t const per_block = std::max<size_t>(columns_stream_ws_words(p.m, c->B), (size_t) 4 * m);
 		size_t const bl = c->sh.on ? c->sh.b_lo : 0, bh = c->sh.on ? std::min<size_t>(c->nblocks, (size_t) std::max(c->sh.b_hi, c->sh.b_lo) + 1) : c->nblocks;
-		c->ws_words = per_block * std::max<size_t>(bh - bl, 1);
-		if ((rc = dev_alloc(c, &c->d_ws, c->ws_words))) return rc;
-		c->d_ws_c = c->d_ws - bl * columns_stream_ws_words(p.m, c->B);
+		if ((rc = c->d_ws.alloc(c, per_block * std::max<size_t>(bh - bl, 1)))) return rc;
+		c->d_ws.rebase((ptrdiff_t) (bl * columns_stream_ws_words(p.m, c->B)));
 		// phase B spread over the chip: the digit histograms of every part of every chain of a launch (the widest launch of the
 		// recursion has a chain per chain_fan blocks; a sharded rank's own range the same)
 		// (streamed rows are < 2^20: one packed column fits STREAM_MAX_COLBYTES, so m <= 4 x 147,456 = 589,824)
 		size_t const chains = std::max<size_t>(1, (bh - bl + std::max(2u, c->chain_fan) - 1) / std::max(2u, c->chain_fan) + 1);
-		if ((rc = dev_alloc(c, &c->d_cshist, chains * chainmulti_parts(p.m) * CS_BINS))) return rc;
+		if ((rc = c->d_cshist.alloc(c, chains * chainmulti_parts(p.m) * CS_BINS))) { c->d_ws.release(c); return rc; }
 	}
 	uint64_t const k_lo = held_lo(c), k_cnt = held_hi(c) - k_lo;      // sharded: lists and stride states of my columns only
 	// (a list budget: the H + wb B columns of one window, plan_list_windows)
 	size_t const ent_count = c->lw.on ? ((size_t) c->lw.H + (size_t) c->lw.wb * c->B) * ((X + 3) & ~1u) + 256 : (size_t) k_cnt * ((X + 3) & ~1u) + 256;
-	if (X && (!c->d_ent || c->X != X || c->lw.ent_count != ent_count))
+	if (X && (!c->d_ent || c->X != X || c->d_ent.cap != ent_count))
 	{
 		c->X = X;
 		c->stride = (X + 3) & ~1u;                // lump + up to X+1 entries, even
-		dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr; c->lw.ent_count = 0;
-		rc = dev_alloc(c, &c->d_ent_alloc, ent_count);   // padded: the DP loads strips unconditionally
+		rc = c->d_ent.alloc(c, ent_count);        // padded: the DP loads strips unconditionally
 		if (rc == FSEQ_E_OOM && c->d_ss_a)
 		{
 			// the stride states were sized before the lists grew: give their memory back and size them again below
-			dev_free(c, &c->d_ss_a_alloc); dev_free(c, &c->d_ss_d_alloc); c->d_ss_a = c->d_ss_d = nullptr;
-			rc = dev_alloc(c, &c->d_ent_alloc, ent_count);
+			release_all(c, c->d_ss_a, c->d_ss_d);
+			rc = c->d_ent.alloc(c, ent_count);
 		}
 		if (rc) return rc;
-		c->lw.ent_count = ent_count;
-		c->d_ent = c->d_ent_alloc - (size_t) k_lo * c->stride;   // list of column k at d_ent + k * stride (windows: set per window)
+		c->d_ent.rebase((ptrdiff_t) ((size_t) k_lo * c->stride));   // list of column k at d_ent + k * stride (windows: set per window)
 	}
 	if (X && want_ss && !c->d_ss_a && p.n >= 2 * p.segment_length)
 	{
@@ -513,8 +527,8 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		{
 			// every block's start state in id form (written by the prologue of phase C): my blocks and the halo block
 			size_t const bl = c->sh.on ? c->sh.b_lo : 0, bh = c->sh.on ? std::min<size_t>(c->nblocks, (size_t) std::max(c->sh.b_hi, c->sh.b_lo) + 1) : c->nblocks;
-			if ((rc = dev_alloc_range(c, &c->d_bs_w_alloc, &c->d_bs_w, bl, std::max(bh, bl + 1), m))) return rc;
-			if ((rc = dev_alloc_range(c, &c->d_bs_h_alloc, &c->d_bs_h, bl, std::max(bh, bl + 1), ss_high_stride(p.m)))) return rc;
+			if ((rc = c->d_bs_w.alloc_range(c, bl, std::max(bh, bl + 1), m))) return rc;
+			if ((rc = c->d_bs_h.alloc_range(c, bl, std::max(bh, bl + 1), ss_high_stride(p.m)))) { c->d_bs_w.release(c); return rc; }
 		}
 		uint64_t budget = 4ull << 30;
 		{
@@ -542,48 +556,29 @@ int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true)
 		c->snap_stride = (uint32_t) st_;
 		if (c->tune.debug) fprintf(stderr, "[fseq] stride states every %llu columns (budget %.1f GiB, %llu bytes per state)\n", (unsigned long long) st_, budget / 1073741824.0, (unsigned long long) state_bytes);
 		uint64_t const q_lo = k_lo / st_, q_hi = held_hi(c) / st_;
-		if ((rc = dev_alloc(c, &c->d_ss_a_alloc, (size_t) (q_hi - q_lo + 1) * m))) return rc;
-		c->d_ss_a = c->d_ss_a_alloc - (size_t) q_lo * m;         // state at column q * snap_stride at d_ss_* + q * m
-		if (c->ss_pack)
-		{
-			size_t const hs = ss_high_stride(p.m);
-			if ((rc = dev_alloc(c, &c->d_ss_d_alloc, ((size_t) (q_hi - q_lo + 1) * hs + 3) / 4))) return rc;
-			c->d_ss_d = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(c->d_ss_d_alloc) - (size_t) q_lo * hs);
-		}
-		else
-		{
-			if ((rc = dev_alloc(c, &c->d_ss_d_alloc, (size_t) (q_hi - q_lo + 1) * m))) return rc;
-			c->d_ss_d = c->d_ss_d_alloc - (size_t) q_lo * m;
-		}
+		// state at column q * snap_stride at d_ss_* + q * m (packed: the high bytes at d_ss_d + q * hs BYTES)
+		size_t const hs = ss_high_stride(p.m);
+		if ((rc = c->d_ss_a.alloc_range(c, q_lo, q_hi + 1, m))) return rc;
+		if (c->ss_pack) { rc = c->d_ss_d.alloc(c, ((size_t) (q_hi - q_lo + 1) * hs + 3) / 4); c->d_ss_d.shift = (ptrdiff_t) ((size_t) q_lo * hs); }
+		else rc = c->d_ss_d.alloc_range(c, q_lo, q_hi + 1, m);
+		if (rc) { c->d_ss_a.release(c); return rc; }      // (d_ss_a stands for both)
 	}
 	return FSEQ_OK;
 }
 
 void free_work(fseq_ctx *c)
 {
-	dev_free(c, &c->d_rank_alloc); dev_free(c, &c->d_keyd_alloc); dev_free(c, &c->d_nkeys_alloc);
-	dev_free(c, &c->d_bstate_a_alloc); dev_free(c, &c->d_bstate_d_alloc);
-	c->d_rank = c->d_keyd = c->d_nkeys = c->d_bstate_a = c->d_bstate_d = nullptr;
-	dev_free(c, &c->d_hrank); dev_free(c, &c->d_hkeyd); dev_free(c, &c->d_hnkeys); dev_free(c, &c->d_hstate_a); dev_free(c, &c->d_hstate_d);
-	for (auto &lv : c->levels) { dev_free(c, &lv.rank_alloc); dev_free(c, &lv.keyd_alloc); dev_free(c, &lv.nkeys_alloc); dev_free(c, &lv.state_a_alloc); dev_free(c, &lv.state_d_alloc); }
-	c->levels.clear();
-	dev_free(c, &c->d_ent_alloc); c->d_ent = nullptr; c->lw.ent_count = 0; c->lw.col_lo = c->lw.col_hi = 0; dev_free(c, &c->d_hdr); dev_free(c, &c->d_flags); dev_free(c, &c->d_recent);
-	dev_free(c, &c->d_chunk_r0); c->chunk_cap = 0; dev_free(c, &c->d_tau); c->tau_cap = 0;
-	dev_free(c, &c->d_bk); c->bk_blocks = 0; dev_free(c, &c->d_bkws); c->bkws_words = 0; dev_free(c, &c->d_todo); c->todo_cap = 0;
-	dev_free(c, &c->d_colmask_alloc); c->d_colmask = nullptr; c->colmask_ready = false;
-	dev_free(c, &c->d_btws); c->btws_words = 0; dev_free(c, &c->d_only); c->only_cap = 0;
-	dev_free(c, &c->d_tb); c->tb_cap = 0; c->tb_win = 0;
-	dev_free(c, &c->dp.M); dev_free(c, &c->dp.LB); dev_free(c, &c->dp.SZ); dev_free(c, &c->dp.K); dev_free(c, &c->dp.Tb); dev_free(c, &c->dp.Tbv);
-	dev_free(c, &c->d_Mprev); dev_free(c, &c->d_spec); c->spec_cap = 0;
-	dev_free(c, &c->d_cols); dev_free(c, &c->d_grp); dev_free(c, &c->d_src); dev_free(c, &c->d_ss_a_alloc); dev_free(c, &c->d_ss_d_alloc); c->d_ss_a = c->d_ss_d = nullptr;
-	dev_free(c, &c->d_bs_w_alloc); dev_free(c, &c->d_bs_h_alloc); c->d_bs_w = nullptr; c->d_bs_h = nullptr; dev_free(c, &c->d_wgblk); dev_free(c, &c->d_wggrp); c->wg_cap = 0;
-	dev_free(c, &c->d_gent); dev_free(c, &c->d_ghdr);
-	dev_free(c, &c->d_snap_a); dev_free(c, &c->d_snap_d); dev_free(c, &c->d_ws); c->d_ws_c = nullptr; dev_free(c, &c->d_cshist);
-	c->cols_cap = c->gather_cap = c->snap_cap = c->grp_cap = c->src_cap = 0;
-	dev_free(c, &c->d_red_cnt); dev_free(c, &c->d_red_cnt_plan); c->red_plan_valid = false; c->red_declined = false; dev_free(c, &c->d_red_vmin); dev_free(c, &c->d_red_rows_alloc); dev_free(c, &c->d_red_leaf_alloc); dev_free(c, &c->d_red_a_alloc); dev_free(c, &c->d_red_d_alloc); c->d_red_rows = c->d_red_leaf = c->d_red_a = c->d_red_d = nullptr;
-	dev_free(c, &c->d_red_invalid); dev_free(c, &c->d_red_blocks); dev_free(c, &c->d_red_msa_alloc); c->d_red_msa = nullptr; c->red_cap = 0; c->red_blocks_cap = 0; c->red_ld = 0; c->red_msa_bytes = 0;
-	dev_free(c, &c->d_red_ss_a_alloc); dev_free(c, &c->d_red_ss_d_alloc); c->d_red_ss_a = c->d_red_ss_d = nullptr; c->red_ss_words = 0;
-	dev_free(c, &c->d_red_cls); dev_free(c, &c->d_red_headd); dev_free(c, &c->d_red_ncls); dev_free(c, &c->d_red_taskblk); dev_free(c, &c->d_red_wgtasks); dev_free(c, &c->d_red_p2grp); c->red_task_cap = 0;
+	release_all(c, c->d_rank, c->d_keyd, c->d_nkeys, c->d_bstate_a, c->d_bstate_d, c->d_hrank, c->d_hkeyd, c->d_hnkeys, c->d_hstate_a, c->d_hstate_d);
+	release_levels(c);
+	release_all(c, c->d_ent, c->d_hdr, c->d_flags, c->d_recent, c->d_chunk_r0, c->d_tau, c->d_bk, c->d_bkws, c->d_todo, c->d_colmask, c->d_btws, c->d_only, c->d_tb);
+	release_all(c, c->dp.M, c->dp.LB, c->dp.SZ, c->dp.K, c->dp.Tb, c->dp.Tbv, c->d_Mprev, c->d_spec);
+	release_all(c, c->d_cols, c->d_grp, c->d_src, c->d_ss_a, c->d_ss_d, c->d_bs_w, c->d_bs_h, c->d_wgblk, c->d_wggrp, c->d_snap_a, c->d_snap_d, c->d_ws, c->d_cshist);
+	release_all(c, c->d_red_cnt, c->d_red_cnt_plan, c->d_red_vmin, c->d_red_rows, c->d_red_leaf, c->d_red_a, c->d_red_d, c->d_red_invalid, c->d_red_blocks, c->d_red_msa);
+	release_all(c, c->d_red_ss_a, c->d_red_ss_d, c->d_red_cls, c->d_red_headd, c->d_red_ncls, c->d_red_taskblk, c->d_red_wgtasks, c->d_red_p2grp);
+	// what was planned for the buffers that are gone
+	c->lw.col_lo = c->lw.col_hi = 0;
+	c->colmask_ready = false;
+	c->red_plan_valid = false; c->red_declined = false; c->red_cap = 0; c->red_ld = 0;
 	c->red_active = false;
 }
 
@@ -609,12 +604,10 @@ int upload_rows_device_impl(fseq_ctx *c, uint8_t const *const *rows)
 	fseq_params const &p = c->p;
 	uint64_t const k_lo = held_lo(c), nloc = held_hi(c) - k_lo;      // sharded: this rank's columns only
 	size_t const total = (size_t) p.m * nloc;
-	uint8_t *d_raw = nullptr;
-	uint32_t *d_present = nullptr;
+	DevTemp<uint8_t> d_raw(c);
+	DevTemp<uint32_t> d_present(c);
 	int rc;
-	if ((rc = dev_alloc(c, &d_raw, total + 16))) return rc;
-	if ((rc = dev_alloc(c, &d_present, 8))) { dev_free(c, &d_raw); return rc; }
-	auto cleanup = [&]() { dev_free(c, &d_raw); dev_free(c, &d_present); };
+	if ((rc = d_raw.alloc(total + 16)) || (rc = d_present.alloc(8))) return rc;
 	// (one copy per row from the caller's pageable memory: the runtime stages them at ~32 GB/s.  Measured and dropped in round 4:
 	// eight host threads filling pinned staging buffers of their own, each with its stream -- BASELINE C3's 2.5 GB in 77 - 86 ms
 	// against 78, C2's 250 MB in 39 against 30: the host copies into the pinned buffers are no faster than the runtime's own
@@ -622,24 +615,24 @@ int upload_rows_device_impl(fseq_ctx *c, uint8_t const *const *rows)
 	for (uint32_t r = 0; r < p.m && nloc; ++r)
 	{
 		hipError_t const e = hipMemcpyAsync(d_raw + (size_t) r * nloc, rows[r] + k_lo, nloc, hipMemcpyHostToDevice, c->stream);
-		if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "row upload", e); }
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "row upload", e);
 	}
 	(void) hipMemsetAsync(d_present, 0, 32, c->stream);
 	if (total) hipLaunchKernelGGL(k_presence, dim3(1024), dim3(256), 0, c->stream, d_raw, total, d_present);
 	uint32_t present[8];
 	hipError_t e = hipMemcpyAsync(present, d_present, 32, hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "alphabet scan", e); }
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "alphabet scan", e);
 	if (c->sh.on)
 	{
 		// the alphabet is that of the whole alignment: one presence word per byte value, max over the ranks
 		uint32_t pw[256];
 		for (int b = 0; b < 256; ++b) pw[b] = (present[b >> 5] >> (b & 31)) & 1u;
 		e = hipMemcpy(c->sh.xbuf, pw, sizeof(pw), hipMemcpyHostToDevice);
-		if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "alphabet exchange", e); }
-		if ((rc = shard_exchange(c, 256, 1))) { cleanup(); return rc; }
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "alphabet exchange", e);
+		if ((rc = shard_exchange(c, 256, 1))) return rc;
 		e = hipMemcpy(pw, c->sh.xbuf, sizeof(pw), hipMemcpyDeviceToHost);
-		if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "alphabet exchange", e); }
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "alphabet exchange", e);
 		memset(present, 0, sizeof(present));
 		for (int b = 0; b < 256; ++b) if (pw[b]) present[b >> 5] |= 1u << (b & 31);
 	}
@@ -649,15 +642,14 @@ int upload_rows_device_impl(fseq_ctx *c, uint8_t const *const *rows)
 	for (int b = 0; b < 256; ++b)
 		if ((present[b >> 5] >> (b & 31)) & 1u) { tab.code_of[b] = (uint8_t) sigma; c->code_to_byte[sigma] = (uint8_t) b; ++sigma; }
 	c->sigma = sigma;
-	if ((rc = alloc_msa(c))) { cleanup(); return rc; }
+	if ((rc = alloc_msa(c))) return rc;
 	if (nloc)
 	{
 		dim3 const grid((uint32_t) ((nloc + 63) / 64), (uint32_t) ((p.m + 63) / 64));
-		hipLaunchKernelGGL(k_encode_transpose, grid, dim3(256), 0, c->stream, d_raw, tab, p.m, nloc, c->d_msa_alloc, c->ld, c->bsh);
+		hipLaunchKernelGGL(k_encode_transpose, grid, dim3(256), 0, c->stream, d_raw, tab, p.m, nloc, c->d_msa_own, c->ld, c->bsh);
 	}
 	e = hipGetLastError();
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	cleanup();
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "encode + transpose", e);
 	c->have_input = true;
 	c->have_result = false;
@@ -724,14 +716,10 @@ int follow_traceback_sharded(fseq_ctx *c, hipStream_t st)
 	size_t const cap = (size_t) (c->p.n / L + 2);
 	uint32_t const nwin = (dp_size + TB_WIN - 1u) / TB_WIN;
 	int rc;
-	if (c->tb_cap < cap || c->tb_win < nwin)
-	{
-		if ((rc = dev_alloc(c, &c->d_tb, cap + nwin / 2 + 2))) return rc;
-		c->tb_cap = cap; c->tb_win = nwin;
-	}
+	if ((rc = c->d_tb.ensure(c, cap + nwin / 2 + 2))) return rc;
 	uint2 *d_head = reinterpret_cast<uint2 *>(c->d_tb + cap);
 	uint32_t *d_count = reinterpret_cast<uint32_t *>(d_head + nwin);
-	uint32_t *d_exit_next = c->d_Mprev, *d_exit_cnt = reinterpret_cast<uint32_t *>(c->dp.K);
+	uint32_t *d_exit_next = c->d_Mprev, *d_exit_cnt = c->dp.K.as<uint32_t>();
 	// my part: my entries, and the final cell's (the last entry of the array) on the last active rank
 	bool const have = sh.rank < sh.active && c->own_hi[sh.rank] > c->own_lo[sh.rank];
 	uint32_t const vlo = have ? c->own_lo[sh.rank] : 0u, vhi = have ? (sh.rank + 1u == sh.active ? dp_size : c->own_hi[sh.rank]) : 0u;
@@ -795,14 +783,10 @@ int follow_traceback(fseq_ctx *c, hipStream_t st)
 	size_t const cap = (size_t) (c->p.n / L + 2);           // a segment is at least L columns long
 	uint32_t const nwin = (dp_size + TB_WIN - 1u) / TB_WIN;
 	int rc;
-	if (c->tb_cap < cap || c->tb_win < nwin)
-	{
-		if ((rc = dev_alloc(c, &c->d_tb, cap + nwin / 2 + 2))) return rc;   // out[cap] | head[nwin] (uint2) | count[4]
-		c->tb_cap = cap; c->tb_win = nwin;
-	}
+	if ((rc = c->d_tb.ensure(c, cap + nwin / 2 + 2))) return rc;   // out[cap] | head[nwin] (uint2) | count[4]
 	uint2 *d_head = reinterpret_cast<uint2 *>(c->d_tb + cap);
 	uint32_t *d_count = reinterpret_cast<uint32_t *>(d_head + nwin);
-	uint32_t *d_exit_next = c->d_Mprev, *d_exit_cnt = reinterpret_cast<uint32_t *>(c->dp.K);
+	uint32_t *d_exit_next = c->d_Mprev, *d_exit_cnt = c->dp.K.as<uint32_t>();
 	HIP_TRY(c, hipMemsetAsync(d_count, 0, 16, st));
 	hipLaunchKernelGGL(k_tb_windows, dim3(nwin), dim3(256), 0, st, c->dp.LB, dp_size, L, d_exit_next, d_exit_cnt);
 	hipLaunchKernelGGL(k_tb_chain, dim3(1), dim3(64), 0, st, d_exit_next, d_exit_cnt, dp_size, d_head, nwin, d_count);
@@ -821,8 +805,8 @@ int follow_traceback(fseq_ctx *c, hipStream_t st)
 	bool const tau_tb = !c->sh.on && !c->lw.on;
 	if (tau_tb)
 	{
-		if (c->tau_cap < cap) { if ((rc = dev_alloc(c, &c->d_tau, cap))) return rc; c->tau_cap = cap; }
-		hipLaunchKernelGGL(k_seg_tau_tb, dim3((uint32_t) cap), dim3(64), 0, st, reinterpret_cast<uint4 const *>(c->d_tb), d_count, L, c->stride, c->d_ent, c->d_hdr, c->d_tau);
+		if ((rc = c->d_tau.ensure(c, cap))) return rc;
+		hipLaunchKernelGGL(k_seg_tau_tb, dim3((uint32_t) cap), dim3(64), 0, st, c->d_tb.as<uint4 const>(), d_count, L, c->stride, c->d_ent, c->d_hdr, c->d_tau);
 		HIP_TRY(c, hipMemcpyAsync(taup, c->d_tau, guess * sizeof(uint2), hipMemcpyDeviceToHost, st));
 	}
 	HIP_TRY(c, hipMemcpyAsync(cnt, d_count, 16, hipMemcpyDeviceToHost, st));
@@ -874,7 +858,7 @@ void launch_rank(fseq_ctx *c, uint32_t grid, uint32_t B, uint32_t nblocks, uint3
 	if (!grid) return;
 	if (c->use_stream)
 		hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE_RANK, true> : k_colblock_stream<MODE_RANK, false>), dim3(grid), dim3(ST), stream_lds_bytes(sym_bytes(p.m, c->bsh), c->stream_staged), c->stream, c->d_msa, c->ld, p.m, p.n, B, nblocks,
-		                   c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged, rank, keyd, nkeys, only, (uint32_t const *) nullptr, (uint64_t const *) nullptr,
+		                   c->npass, c->bsh, c->d_ws.base, (uint32_t) c->stream_staged, rank, keyd, nkeys, only, (uint32_t const *) nullptr, (uint64_t const *) nullptr,
 		                   (uint2 const *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint64_t const *) nullptr, 0u,
 		                   (uint32_t const *) nullptr, (uint32_t const *) nullptr, col0, 0u);
 	else
@@ -896,7 +880,7 @@ void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t con
 		uint32_t const m = c->p.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
 		ChainMultiArgs A;
 		A.rank = rank; A.keyd = keyd; A.nkeys = nkeys; A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block;
-		A.ws = c->d_ws; A.hist = c->d_cshist; A.start_a = start_a; A.start_d = start_d; A.out_state_a = out_a; A.out_state_d = out_d;
+		A.ws = c->d_ws.base; A.hist = c->d_cshist; A.start_a = start_a; A.start_d = start_d; A.out_state_a = out_a; A.out_state_d = out_d;
 		A.out_rank = out_rank; A.out_keyd = out_keyd; A.out_nkeys = out_nkeys; A.grp0 = grp0; A.step = 0; A.pass = 0;
 		A.nchains = grid;
 		uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
@@ -1057,16 +1041,8 @@ int dp_spec_reset(fseq_ctx *c, SpecPlan const &P, hipStream_t s)
 {
 	uint32_t const nch = P.nchunks();
 	int rc;
-	if (c->spec_cap < nch)
-	{
-		if ((rc = dev_alloc(c, &c->d_spec, (size_t) 7 * nch + 16))) return rc;
-		c->spec_cap = nch;
-	}
-	if (c->chunk_cap < nch + 1u)
-	{
-		if ((rc = dev_alloc(c, &c->d_chunk_r0, nch + 1u))) return rc;
-		c->chunk_cap = nch + 1u;
-	}
+	if ((rc = c->d_spec.ensure(c, (size_t) 7 * nch + 16))) return rc;
+	if ((rc = c->d_chunk_r0.ensure(c, nch + 1u))) return rc;
 	HIP_TRY(c, hipMemcpyAsync(c->d_chunk_r0, P.r0.data(), (size_t) (nch + 1u) * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, s));
 	HIP_TRY(c, hipMemsetAsync(c->d_Mprev, 0, c->dp_size * 4, s));
@@ -1368,10 +1344,10 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	// 4-bit symbols, LDS-resident rows: the codes present in every column I hold, once per input (k_columns takes a column with at
 	// most four of them in one digit pass)
 	if (c->bsh == 1u && c->npass == 2u && !c->use_stream && !c->tune.no_dense_columns && !c->colmask_ready && held_hi(c) > held_lo(c)
-	    && c->d_msa_alloc && (c->ld & 3u) == 0)                  // (own columns: padded past their last byte, whole words can be read)
+	    && c->d_msa_own && (c->ld & 3u) == 0)                  // (own columns: padded past their last byte, whole words can be read)
 	{
 		uint64_t const lo = held_lo(c), hi = held_hi(c);
-		if ((rc = dev_alloc_range(c, &c->d_colmask_alloc, &c->d_colmask, (size_t) lo, (size_t) hi, 1))) return rc;
+		if ((rc = c->d_colmask.alloc_range(c, (size_t) lo, (size_t) hi, 1))) return rc;
 		HIP_TRY(c, hipMemsetAsync(c->d_flags + 67, 0, 4, st));
 		hipLaunchKernelGGL(k_column_presence, dim3((uint32_t) std::min<uint64_t>(hi - lo, 8192)), dim3(256), 0, st, c->d_msa, c->ld, sym_bytes(m, c->bsh), lo, hi, c->d_colmask,
 		                   c->d_flags + 67);
@@ -1400,7 +1376,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	uint32_t *todo = nullptr;
 	if (limited)
 	{
-		if (c->todo_cap < my_blocks) { if ((rc = dev_alloc(c, &c->d_todo, my_blocks))) return rc; c->todo_cap = my_blocks; }
+		if ((rc = c->d_todo.ensure(c, my_blocks))) return rc;
 		todo = c->d_todo;
 		HIP_TRY(c, hipMemsetAsync(todo, tree ? 0 : 0x01, (size_t) my_blocks * 4, st));     // (no tree: every block is the sweep's)
 	}
@@ -1427,12 +1403,8 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		uint32_t const per_cu = (uint32_t) std::max<size_t>(1, std::min<size_t>(2048u / bt_T, (160u * 1024u) / blocktrie_lds(bt_T)));
 		uint32_t const groups = std::min<uint32_t>(my_blocks, (uint32_t) std::max(1, ncu) * per_cu);
 		size_t const per = (blocktrie_ws_words(m, c->B, bt_bits, bt_T) + 15) & ~size_t(15);
-		if (c->btws_words < per * groups)
-		{
-			if ((rc = dev_alloc(c, &c->d_btws, per * groups))) return rc;
-			c->btws_words = per * groups;
-		}
-		if (c->only_cap < my_blocks) { if ((rc = dev_alloc(c, &c->d_only, my_blocks))) return rc; c->only_cap = my_blocks; }
+		if ((rc = c->d_btws.ensure(c, per * groups))) return rc;
+		if ((rc = c->d_only.ensure(c, my_blocks))) return rc;
 		HIP_TRY(c, hipMemsetAsync(c->d_only, 0, (size_t) my_blocks * 4, st));
 		HIP_TRY(c, launch_blocktrie(bt_bits, bt_T, st, groups, c->d_msa, c->ld, m, n, c->B, my_blocks,
 		                            c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
@@ -1446,11 +1418,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
 		uint32_t const groups = std::min<uint32_t>(my_blocks, (uint32_t) std::max(1, ncu));
 		size_t const per = (blockkeys_stream_ws_words(m, c->B, c->bsh) + 15) & ~size_t(15);
-		if (c->bkws_words < per * groups)
-		{
-			if ((rc = dev_alloc(c, &c->d_bkws, per * groups))) return rc;
-			c->bkws_words = per * groups;
-		}
+		if ((rc = c->d_bkws.ensure(c, per * groups))) return rc;
 		hipLaunchKernelGGL(k_blockkeys_stream, dim3(groups), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, n, c->B, c->bsh, my_blocks,
 		                   c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
 		                   c->d_bkws, per, c->bk_cap_words, c->d_flags + 64, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), todo, only);
@@ -1459,11 +1427,9 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	{
 		// phase A in key space (fseq_blockkeys.hpp)
 		size_t const per = (blockkeys_scratch_halfwords(m, c->B, c->bsh) + 7) & ~size_t(7);
-		if (c->bk_per_block != per || c->bk_blocks < my_blocks)
-		{
-			if ((rc = dev_alloc(c, &c->d_bk, per * my_blocks))) return rc;
-			c->bk_per_block = per; c->bk_blocks = my_blocks;
-		}
+		if (c->bk_per_block != per) c->d_bk.release(c);
+		if ((rc = c->d_bk.ensure(c, per * my_blocks))) return rc;
+		c->bk_per_block = per;
 		launch_blockkeys(c->bk_T, st, my_blocks, c->bk_lds, c->d_msa, c->ld, m, n, c->B, c->bsh, c->d_rank + (size_t) b_lo * m,
 		                 c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B, c->d_bk, per, c->bk_cap_words, c->d_flags + 64, todo, only);
 	}
@@ -1675,8 +1641,8 @@ int long_traceback_and_merge(fseq_ctx *c, LongRun &R, double th0, bool *overflow
 				tau = c->tau_host;                                          // came back with the traceback
 			else if (S > 1)
 			{
-				if (c->cols_cap < 2 * S) { if ((rc = dev_alloc(c, &c->d_cols, 2 * S))) return rc; c->cols_cap = 2 * S; }
-				if (c->tau_cap < S) { if ((rc = dev_alloc(c, &c->d_tau, S))) return rc; c->tau_cap = S; }
+				if ((rc = c->d_cols.ensure(c, 2 * S))) return rc;
+				if ((rc = c->d_tau.ensure(c, S))) return rc;
 				std::vector<uint64_t> cols(S);
 				for (size_t j = 0; j < S; ++j) cols[j] = c->traceback[j].rb - 1;
 				HIP_TRY(c, hipMemcpyAsync(c->d_cols, cols.data(), S * 8, hipMemcpyHostToDevice, st));
@@ -1730,10 +1696,10 @@ int long_traceback_and_merge(fseq_ctx *c, LongRun &R, double th0, bool *overflow
 					uint64_t *const qc = pin_take<uint64_t>(c, 2 * Q);
 					for (size_t i = 0; i < Q; ++i) { qc[i] = ask[i].col; qc[Q + i] = ask[i].lb; }
 					uint32_t *const cnt = pin_take<uint32_t>(c, Q);
-					if (c->cols_cap < 2 * Q) { if ((rc = dev_alloc(c, &c->d_cols, 2 * Q))) return rc; c->cols_cap = 2 * Q; }
-					if (c->tau_cap < Q) { if ((rc = dev_alloc(c, &c->d_tau, Q))) return rc; c->tau_cap = Q; }
+					if ((rc = c->d_cols.ensure(c, 2 * Q))) return rc;
+					if ((rc = c->d_tau.ensure(c, Q))) return rc;
 					HIP_TRY(c, hipMemcpyAsync(c->d_cols, qc, 2 * Q * 8, hipMemcpyHostToDevice, st));
-					uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->d_tau);
+					uint32_t *d_cnt = c->d_tau.as<uint32_t>();
 					hipLaunchKernelGGL(k_seg_count, dim3((uint32_t) Q), dim3(64), 0, st, c->d_cols, c->d_cols + Q, own_lo, own_hi, c->stride, c->d_ent, c->d_hdr, d_cnt);
 					if (sharded)
 					{
@@ -1803,15 +1769,15 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	{
 		// (the small per-block words for every block of the alignment; the per-block rows for my blocks only -- a rank of a
 		// sharded run --, addressed by the block's place in the whole alignment like the key blocks and boundary states)
-		if ((rc = dev_alloc(c, &c->d_red_cnt, nbk))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_cnt_plan, nbk))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_vmin, nbk))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_invalid, nbk + 2))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_blocks, 3 * (size_t) nbk))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_red_rows_alloc, &c->d_red_rows, b_lo, b_hi, cap))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_red_leaf_alloc, &c->d_red_leaf, b_lo, b_hi, cap))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_red_a_alloc, &c->d_red_a, b_lo, b_hi, cap))) return rc;
-		if ((rc = dev_alloc_range(c, &c->d_red_d_alloc, &c->d_red_d, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_cnt.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_cnt_plan.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_vmin.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_invalid.alloc(c, nbk + 2))) return rc;
+		if ((rc = c->d_red_blocks.alloc(c, 3 * (size_t) nbk))) return rc;
+		if ((rc = c->d_red_rows.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_leaf.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_a.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_d.alloc_range(c, b_lo, b_hi, cap))) return rc;
 		c->red_cap = cap;
 		c->red_plan_valid = false;
 	}
@@ -1930,9 +1896,9 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 		size_t const ldr = ((size_t) sym_bytes(max_rows ? max_rows : 1u, c->bsh) + 15) & ~size_t(15);
 		uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
 		size_t const need = (size_t) (k_hi - k_lo) * ldr + 64;
-		if (c->red_msa_bytes < need) { if ((rc = dev_alloc(c, &c->d_red_msa_alloc, need))) return rc; c->red_msa_bytes = need; }
+		if ((rc = c->d_red_msa.ensure(c, need))) return rc;
 		c->red_ld = ldr;
-		c->d_red_msa = c->d_red_msa_alloc - (size_t) k_lo * ldr;
+		c->d_red_msa.rebase((ptrdiff_t) ((size_t) k_lo * ldr));
 	}
 	{
 		// the reduced states for pass 2: every 16 columns (32: streamed rows), rows for the most representatives of a block
@@ -1940,15 +1906,11 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 		uint32_t const scap = (std::max(max_rows, 1u) + 63u) & ~63u;
 		uint64_t const q_lo = (uint64_t) b_lo * c->B / stride_, q_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B) / stride_;
 		size_t const words = ((size_t) (q_hi - q_lo) + 2) * scap;
-		if (c->red_ss_words < words)
-		{
-			if ((rc = dev_alloc(c, &c->d_red_ss_a_alloc, words))) return rc;
-			if ((rc = dev_alloc(c, &c->d_red_ss_d_alloc, words))) return rc;
-			c->red_ss_words = words;
-		}
+		if ((rc = c->d_red_ss_a.ensure(c, words))) return rc;
+		if ((rc = c->d_red_ss_d.ensure(c, words))) return rc;
 		c->red_ss_stride = stride_; c->red_ss_cap = scap;
-		c->d_red_ss_a = c->d_red_ss_a_alloc - (size_t) q_lo * scap;       // (the state at column q * stride at [q][scap])
-		c->d_red_ss_d = c->d_red_ss_d_alloc - (size_t) q_lo * scap;
+		c->d_red_ss_a.rebase((ptrdiff_t) ((size_t) q_lo * scap));         // (the state at column q * stride at [q][scap])
+		c->d_red_ss_d.rebase((ptrdiff_t) ((size_t) q_lo * scap));
 	}
 	c->red_bins.clear();
 	uint32_t at = listed;
@@ -2038,16 +2000,16 @@ void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = null
 	{
 		uint32_t pack_abits = 1;
 		while ((1u << pack_abits) < m) ++pack_abits;
-		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws_c, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
+		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
 		                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
-		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
+		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
 		             c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack | (c->ss_ids ? S2_SS_IDS : 0u), list);
 	}
 	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan)
-		hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
+		hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
 		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
 	else if (c->use_stream)
-		hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws_c, (uint32_t) c->stream_staged,
+		hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
 		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
 	else
 		ks.columns(st, nb, c->lds_columns, c->d_msa, c->ld, m, n_c, c->B, c->N2, c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->npass, c->bsh,
@@ -2056,7 +2018,7 @@ void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = null
 
 
 // ---- a list budget (fseq_set_list_memory): pass 1's lists in windows of wb consecutive column blocks.  Window w = blocks
-// [lo_w, hi_w) holds the lists of the columns [lo_w B - H, hi_w B) in one buffer (d_ent = d_ent_alloc - (lo_w B - H) stride:
+// [lo_w, hi_w) holds the lists of the columns [lo_w B - H, hi_w B) in one buffer (d_ent rebased to (lo_w B - H) stride:
 // the kernels address lists as they always do); phase C writes the window's own columns, the DP runs the rounds whose
 // lists are all there, and the last H columns move to the front for the next window.  H: the columns in front of a window
 // that its first DP round still reads.
@@ -2125,7 +2087,7 @@ int plan_list_windows(fseq_ctx *c, uint32_t X)
 // the buffer holds window [lo_w, ..): column k at d_ent + k * stride
 void set_list_window(fseq_ctx *c, uint32_t lo_w)
 {
-	c->d_ent = c->d_ent_alloc + ((int64_t) c->lw.H - (int64_t) lo_w * c->B) * (int64_t) c->stride;
+	c->d_ent.rebase(((int64_t) lo_w * c->B - (int64_t) c->lw.H) * (int64_t) c->stride);
 }
 
 // phase C (lists, headers, stride states) of the blocks [lo, hi): on their representatives where this attempt's plan put
@@ -2180,7 +2142,7 @@ int long_windows_cd(fseq_ctx *c, DpSchedule const &S)
 	{
 		uint32_t const hi = std::min(c->nblocks, lo + W.wb);
 		if (lo && W.H)
-			HIP_TRY(c, hipMemcpyAsync(c->d_ent_alloc, c->d_ent_alloc + (size_t) W.wb * c->B * c->stride, (size_t) W.H * c->stride * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+			HIP_TRY(c, hipMemcpyAsync(c->d_ent.base, c->d_ent.base + (size_t) W.wb * c->B * c->stride, (size_t) W.H * c->stride * sizeof(uint2), hipMemcpyDeviceToDevice, st));
 		set_list_window(c, lo);
 		if ((rc = window_phase_c(c, lo, hi))) return rc;
 		uint32_t const r_hi = window_round_hi(c, S, hi);
@@ -2213,8 +2175,8 @@ int merge_windowed(fseq_ctx *c, bool *overflow)
 	fseq_ctx::ListWindows &W = c->lw;
 	size_t const S = c->traceback.size();
 	uint32_t const max_seg = c->traceback.back().segment_max_size;
-	if (c->cols_cap < 2 * S) { if ((rc = dev_alloc(c, &c->d_cols, 2 * S))) return rc; c->cols_cap = 2 * S; }
-	if (c->tau_cap < S) { if ((rc = dev_alloc(c, &c->d_tau, S))) return rc; c->tau_cap = S; }
+	if ((rc = c->d_cols.ensure(c, 2 * S))) return rc;
+	if ((rc = c->d_tau.ensure(c, S))) return rc;
 	if ((rc = pin_reserve(c, S * 28 + 256))) return rc;
 	uint64_t *const qc = pin_take<uint64_t>(c, 2 * S);
 	uint2 *const tau = pin_take<uint2>(c, S);
@@ -2276,7 +2238,7 @@ int merge_windowed(fseq_ctx *c, bool *overflow)
 			std::vector<uint32_t> const js(cnt, cnt + nq);
 			HIP_TRY(c, hipMemcpyAsync(c->d_cols, qc, nq * 8, hipMemcpyHostToDevice, st));
 			HIP_TRY(c, hipMemcpyAsync(c->d_cols + nq, qc + S, nq * 8, hipMemcpyHostToDevice, st));
-			uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->d_tau);
+			uint32_t *d_cnt = c->d_tau.as<uint32_t>();
 			hipLaunchKernelGGL(k_seg_count, dim3((uint32_t) nq), dim3(64), 0, st, c->d_cols, c->d_cols + nq, col_lo, col_hi, c->stride, c->d_ent, c->d_hdr, d_cnt);
 			HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, nq * 4, hipMemcpyDeviceToHost, st));
 			HIP_TRY(c, hipStreamSynchronize(st));
@@ -2316,7 +2278,7 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 	if (c->tune.poison_lists)
 	{
 		// tests of the DP-beside-phase-C forms: a list read before it is written must not look right by accident
-		HIP_TRY(c, hipMemsetAsync(c->d_ent_alloc, 0xFF, c->lw.ent_count * sizeof(uint2), st));
+		HIP_TRY(c, hipMemsetAsync(c->d_ent.base, 0xFF, c->d_ent.cap * sizeof(uint2), st));
 		HIP_TRY(c, hipMemsetAsync(c->d_hdr, 0xFF, (size_t) n * sizeof(uint4), st));
 	}
 	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
@@ -2520,6 +2482,25 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 }
 
 
+
+// sharded: R of SURVEY.md 8(d) is the sum of pass 2's cells over the ranks (one slot pair per rank); the run's last exchange
+int pass2_sum_cells(fseq_ctx *c, LongRun &R, hipStream_t st)
+{
+	Shard const &sh = c->sh;
+	if (!sh.on) return FSEQ_OK;
+	uint32_t slots[2] = {(uint32_t) R.pass2_cells, (uint32_t) (R.pass2_cells >> 32)};
+	std::vector<uint32_t> all(2 * sh.world);
+	HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, all.size() * 4, st));
+	HIP_TRY(c, hipMemcpyAsync(sh.xbuf + 2 * sh.rank, slots, 8, hipMemcpyHostToDevice, st));
+	int rc;
+	if ((rc = shard_exchange(c, all.size(), 0))) return rc;
+	HIP_TRY(c, hipMemcpy(all.data(), sh.xbuf, all.size() * 4, hipMemcpyDeviceToHost));
+	R.pass2_cells = 0;
+	for (uint32_t g = 0; g < sh.world; ++g) R.pass2_cells += (uint64_t) all[2 * g] | ((uint64_t) all[2 * g + 1] << 32);
+	c->sh.closed = true;
+	return FSEQ_OK;
+}
+
 // ---- [r5] pass 2 behind the reduced phase C: a boundary inside a block is ONE chain step from the block's boundary state
 // (k_chain_snap), keyed by the classes the block's representatives form at that column (k_columns_red with the class
 // tables as its output); a boundary on a block border is that border's state.  Blocks without representatives (more than a
@@ -2582,41 +2563,16 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 	}
 	size_t const S2 = rbs.size();
-	auto finish = [&]() -> int {
-		if (sharded)
-		{
-			// R of SURVEY.md 8(d) is the sum over the ranks: one slot pair per rank
-			uint32_t slots[2] = {(uint32_t) R.pass2_cells, (uint32_t) (R.pass2_cells >> 32)};
-			std::vector<uint32_t> all(2 * sh.world);
-			HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, all.size() * 4, st));
-			HIP_TRY(c, hipMemcpyAsync(sh.xbuf + 2 * sh.rank, slots, 8, hipMemcpyHostToDevice, st));
-			int rc2;
-			if ((rc2 = shard_exchange(c, all.size(), 0))) return rc2;
-			HIP_TRY(c, hipMemcpy(all.data(), sh.xbuf, all.size() * 4, hipMemcpyDeviceToHost));
-			R.pass2_cells = 0;
-			for (uint32_t g = 0; g < sh.world; ++g) R.pass2_cells += (uint64_t) all[2 * g] | ((uint64_t) all[2 * g + 1] << 32);
-			c->sh.closed = true;                                 // the last exchange of the run
-		}
-		return FSEQ_OK;
-	};
-	if (!S2) { R.pass2_cells = 0; return finish(); }
-	if (c->snap_cap < S2)
-	{
-		if ((rc = dev_alloc(c, &c->d_snap_a, S2 * (size_t) m))) return rc;
-		if ((rc = dev_alloc(c, &c->d_snap_d, S2 * (size_t) m))) return rc;
-		c->snap_cap = S2;
-	}
-	if (c->red_task_cap < S2)
-	{
-		if ((rc = dev_alloc(c, &c->d_red_cls, S2 * (size_t) c->red_cap))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_headd, S2 * (size_t) c->red_cap))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_ncls, S2))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_taskblk, S2))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_wgtasks, 4 * S2 + 64))) return rc;
-		if ((rc = dev_alloc(c, &c->d_red_p2grp, 2 * S2 + 4))) return rc;
-		c->red_task_cap = S2;
-	}
-	if (c->cols_cap < S2) { if ((rc = dev_alloc(c, &c->d_cols, S2))) return rc; c->cols_cap = S2; }
+	if (!S2) { R.pass2_cells = 0; return pass2_sum_cells(c, R, st); }
+	if ((rc = c->d_snap_a.ensure(c, S2 * (size_t) m))) return rc;
+	if ((rc = c->d_snap_d.ensure(c, S2 * (size_t) m))) return rc;
+	if ((rc = c->d_red_cls.ensure(c, S2 * (size_t) c->red_cap))) return rc;
+	if ((rc = c->d_red_headd.ensure(c, S2 * (size_t) c->red_cap))) return rc;
+	if ((rc = c->d_red_ncls.ensure(c, S2))) return rc;
+	if ((rc = c->d_red_taskblk.ensure(c, S2))) return rc;
+	if ((rc = c->d_red_wgtasks.ensure(c, 4 * S2 + 64))) return rc;
+	if ((rc = c->d_red_p2grp.ensure(c, 2 * S2 + 4))) return rc;
+	if ((rc = c->d_cols.ensure(c, S2))) return rc;
 	// streamed rows: the groups of the chain-step kernel, a block's tasks each (blocks with tasks of that kernel only), the
 	// largest first, and behind them the counter the workgroups take them by
 	std::vector<uint32_t> p2grp;
@@ -2683,7 +2639,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	{
 		RedArgs RA;
 		red_fill_args(c, RA);
-		RA.task_rb = reinterpret_cast<unsigned long long const *>(c->d_cols);
+		RA.task_rb = c->d_cols.as<unsigned long long const>();
 		RA.cls = c->d_red_cls; RA.headd = c->d_red_headd; RA.ncls = c->d_red_ncls;
 		std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
 		if ((rc = red_launch_all(c, ls, RA, c->d_red_wgtasks + 3 * S2, c->d_red_wgtasks, (uint2 *) nullptr, (uint4 *) nullptr, 0u, 0u))) return rc;
@@ -2702,12 +2658,12 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 			if (c->red_cap > P2_CLS_CAP) return fail(c, FSEQ_E_UNSUPPORTED, "pass 2: more representatives a block than the class table in LDS holds");
 			int ncu = 0;
 			(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
-			size_t const fit = c->ws_words / pass2_ws_words(m);
+			size_t const fit = c->d_ws.cap / pass2_ws_words(m);
 			uint32_t const grid = (uint32_t) std::min<size_t>(std::min<size_t>(ngrp, fit), (size_t) std::max(ncu, 1) * 2u);
 			if (!grid) return fail(c, FSEQ_E_OOM, "pass 2: the workspace holds no chain step");
 			hipLaunchKernelGGL(k_chain_snap_grouped, dim3(grid), dim3(ST), pass2_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
-			                   c->d_red_headd, c->d_red_ncls, c->red_cap, reinterpret_cast<uint2 const *>(c->d_red_p2grp), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
-			                   c->d_snap_a, c->d_snap_d, c->d_ws);
+			                   c->d_red_headd, c->d_red_ncls, c->red_cap, c->d_red_p2grp.as<uint2 const>(), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
+			                   c->d_snap_a, c->d_snap_d, c->d_ws.base);
 		}
 	}
 	for (size_t i = 0; i < S2; ++i)
@@ -2716,13 +2672,11 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	if (!o_grp.empty())
 	{
 		size_t const So = o_rbs.size();
-		uint32_t *tmp_a = nullptr, *tmp_d = nullptr;
-		uint64_t *d_orb = nullptr, *d_osrc = nullptr;
-		uint2 *d_ogrp = nullptr;
-		if ((rc = dev_alloc(c, &tmp_a, So * (size_t) m))) return rc;
-		if ((rc = dev_alloc(c, &tmp_d, So * (size_t) m))) { dev_free(c, &tmp_a); return rc; }
-		if ((rc = dev_alloc(c, &d_orb, So)) || (rc = dev_alloc(c, &d_osrc, o_srcs.size())) || (rc = dev_alloc(c, &d_ogrp, o_grp.size())))
-		{ dev_free(c, &tmp_a); dev_free(c, &tmp_d); dev_free(c, &d_orb); dev_free(c, &d_osrc); dev_free(c, &d_ogrp); return rc; }
+		DevTemp<uint32_t> tmp_a(c), tmp_d(c);
+		DevTemp<uint64_t> d_orb(c), d_osrc(c);
+		DevTemp<uint2> d_ogrp(c);
+		if ((rc = tmp_a.alloc(So * (size_t) m)) || (rc = tmp_d.alloc(So * (size_t) m)) ||
+		    (rc = d_orb.alloc(So)) || (rc = d_osrc.alloc(o_srcs.size())) || (rc = d_ogrp.alloc(o_grp.size()))) return rc;
 		HIP_TRY(c, hipMemcpyAsync(d_orb, o_rbs.data(), So * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(d_osrc, o_srcs.data(), o_srcs.size() * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(d_ogrp, o_grp.data(), o_grp.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
@@ -2732,12 +2686,12 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		else
 		{
 			// (the streamed sweep needs 4m workspace words per workgroup: as many groups per launch as d_ws holds)
-			size_t const capg = std::max<size_t>(1, c->ws_words / (4 * (size_t) m));
+			size_t const capg = std::max<size_t>(1, c->d_ws.cap / (4 * (size_t) m));
 			for (size_t g0 = 0; g0 < o_grp.size(); g0 += capg)
 			{
 				size_t const cntg = std::min(capg, o_grp.size() - g0);
 				hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE_SNAP, true> : k_colblock_stream<MODE_SNAP, false>), dim3((uint32_t) cntg), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n, c->B,
-				                   c->nblocks, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, c->d_bstate_a, c->d_bstate_d,
+				                   c->nblocks, c->npass, c->bsh, c->d_ws.base, (uint32_t) c->stream_staged, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, c->d_bstate_a, c->d_bstate_d,
 				                   d_orb, d_ogrp + g0, tmp_a, tmp_d, d_osrc + g0, c->snap_stride, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint64_t) 0, 0u);
 			}
 		}
@@ -2748,7 +2702,6 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 		for (size_t g = 0; g < o_grp.size(); ++g) cells += (o_rbs[o_grp[g].x + o_grp[g].y - 1] - o_srcs[g] * c->B) * m;
 		HIP_TRY(c, hipStreamSynchronize(st));
-		dev_free(c, &tmp_a); dev_free(c, &tmp_d); dev_free(c, &d_orb); dev_free(c, &d_osrc); dev_free(c, &d_ogrp);
 	}
 	HIP_TRY(c, hipEventRecord(c->ev[7], st));
 	HIP_TRY(c, hipGetLastError());
@@ -2758,7 +2711,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	float f = 0;
 	HIP_TRY(c, hipEventElapsedTime(&f, c->ev[6], c->ev[7])); R.ms_p2 = f;
 	R.pass2_cells = cells;
-	return finish();
+	return pass2_sum_cells(c, R, st);
 }
 
 // ---- pass 2: (a, d) at the merged boundaries
@@ -2772,7 +2725,7 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 	// ---- pass 2: (a,d) at the merged boundaries (update_pbwt_task.cc:13-35)
 	if (S2)
 	{
-		if (c->cols_cap < S2) { if ((rc = dev_alloc(c, &c->d_cols, S2))) return rc; c->cols_cap = S2; }
+		if ((rc = c->d_cols.ensure(c, S2))) return rc;
 		// every boundary starts from the nearest exact state at or below it: a block boundary state
 		// (phase B) or one of the states phase C dropped every snap_stride columns; boundaries that share
 		// a start state share one sweep (boundaries ascending)
@@ -2804,14 +2757,10 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 		for (size_t g = 0; g < grp.size(); ++g)
 			pass2_cells += (rbs[grp[g].x + grp[g].y - 1] - starts[g]) * m;
 		size_t const S2m = rbs.size();                            // boundaries that are mine (all of them when not sharded)
-		if (c->snap_cap < S2m)
-		{
-			if ((rc = dev_alloc(c, &c->d_snap_a, S2m * (size_t) m))) return rc;
-			if ((rc = dev_alloc(c, &c->d_snap_d, S2m * (size_t) m))) return rc;
-			c->snap_cap = S2m;
-		}
-		if (c->src_cap < srcs.size()) { if ((rc = dev_alloc(c, &c->d_src, srcs.size()))) return rc; c->src_cap = srcs.size(); }
-		if (c->grp_cap < grp.size()) { if ((rc = dev_alloc(c, &c->d_grp, grp.size()))) return rc; c->grp_cap = grp.size(); }
+		if ((rc = c->d_snap_a.ensure(c, S2m * (size_t) m))) return rc;
+		if ((rc = c->d_snap_d.ensure(c, S2m * (size_t) m))) return rc;
+		if ((rc = c->d_src.ensure(c, srcs.size()))) return rc;
+		if ((rc = c->d_grp.ensure(c, grp.size()))) return rc;
 		{
 			// (through the pinned stage: it stays untouched until the synchronisation behind the kernel)
 			if ((rc = pin_reserve(c, (srcs.size() + S2m + grp.size()) * 8 + 256))) return rc;
@@ -2854,30 +2803,26 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 				for (size_t i = 0; i < order.size(); ++i) { b2[i] = wgb[order[i]]; g2[i] = wgg[order[i]]; }
 				wgb.swap(b2); wgg.swap(g2);
 			}
-			if (c->wg_cap < wgb.size())
-			{
-				if ((rc = dev_alloc(c, &c->d_wgblk, wgb.size()))) return rc;
-				if ((rc = dev_alloc(c, &c->d_wggrp, wgb.size()))) return rc;
-				c->wg_cap = wgb.size();
-			}
+			if ((rc = c->d_wgblk.ensure(c, wgb.size()))) return rc;
+			if ((rc = c->d_wggrp.ensure(c, wgb.size()))) return rc;
 			// (pageable sources: the runtime stages them before the call returns)
 			HIP_TRY(c, hipMemcpyAsync(c->d_wgblk, wgb.data(), wgb.size() * 4, hipMemcpyHostToDevice, st));
 			HIP_TRY(c, hipMemcpyAsync(c->d_wggrp, wgg.data(), wgg.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
 			S2SnapArgs SN;
 			SN.wg_block = c->d_wgblk; SN.wg_groups = c->d_wggrp; SN.grp_tasks = c->d_grp; SN.grp_src = c->d_src; SN.task_rb = c->d_cols;
 			SN.snap_a = c->d_snap_a; SN.snap_d = c->d_snap_d; SN.bs_w = c->d_bs_w; SN.bs_h = c->d_bs_h;
-			c->s2.launch_snap(st, (uint32_t) wgb.size(), c->s2_lds, c->d_msa, c->ld, m, n, c->B, c->npass, c->bsh, c->d_ws_c, c->snap_stride, c->d_ss_a, c->d_ss_d, SN);
+			c->s2.launch_snap(st, (uint32_t) wgb.size(), c->s2_lds, c->d_msa, c->ld, m, n, c->B, c->npass, c->bsh, c->d_ws, c->snap_stride, c->d_ss_a, c->d_ss_d, SN);
 			HIP_TRY(c, hipStreamSynchronize(st));                 // (wgb / wgg must outlive their copies)
 		}
 		else if (c->use_stream)
 		{
 			// the streamed sweep needs 4m workspace words per workgroup: as many groups per launch as d_ws holds
-			size_t const cap = std::max<size_t>(1, c->ws_words / (4 * (size_t) m));
+			size_t const cap = std::max<size_t>(1, c->d_ws.cap / (4 * (size_t) m));
 			for (size_t g0 = 0; g0 < grp.size(); g0 += cap)
 			{
 				size_t const cnt = std::min(cap, grp.size() - g0);
 				hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE_SNAP, true> : k_colblock_stream<MODE_SNAP, false>), dim3((uint32_t) cnt), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n, c->B,
-				                   c->nblocks, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, c->d_bstate_a, c->d_bstate_d,
+				                   c->nblocks, c->npass, c->bsh, c->d_ws.base, (uint32_t) c->stream_staged, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, c->d_bstate_a, c->d_bstate_d,
 				                   c->d_cols, c->d_grp + g0, c->d_snap_a, c->d_snap_d, c->d_src + g0, c->snap_stride, c->d_ss_a, c->d_ss_d, (uint64_t) 0, c->ss_pack);
 			}
 		}
@@ -2891,19 +2836,7 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 		progress(c, FSEQ_STAGE_SAMPLES, S2, S2);
 		float f = 0;
 		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[6], c->ev[7])); ms_p2 = f;
-		if (sharded)
-		{
-			// R of SURVEY.md 8(d) is the sum over the ranks: one slot pair per rank
-			uint32_t slots[2] = {(uint32_t) pass2_cells, (uint32_t) (pass2_cells >> 32)};
-			std::vector<uint32_t> all(2 * sh.world);
-			HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, all.size() * 4, st));
-			HIP_TRY(c, hipMemcpyAsync(sh.xbuf + 2 * sh.rank, slots, 8, hipMemcpyHostToDevice, st));
-			if ((rc = shard_exchange(c, all.size(), 0))) return rc;
-			HIP_TRY(c, hipMemcpy(all.data(), sh.xbuf, all.size() * 4, hipMemcpyDeviceToHost));
-			pass2_cells = 0;
-			for (uint32_t g = 0; g < sh.world; ++g) pass2_cells += (uint64_t) all[2 * g] | ((uint64_t) all[2 * g + 1] << 32);
-			c->sh.closed = true;                                 // the last exchange of the run
-		}
+		if ((rc = pass2_sum_cells(c, R, st))) return rc;
 	}
 
 	return FSEQ_OK;
@@ -2986,38 +2919,25 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 	int rc;
 	c->tm = fseq_timings{};
 	double const t_begin = now_ms();
-	uint32_t *d_rank = nullptr, *d_keyd = nullptr, *d_nk = nullptr;
-	if ((rc = dev_alloc(c, &d_rank, m))) return rc;
-	if ((rc = dev_alloc(c, &d_keyd, m))) { dev_free(c, &d_rank); return rc; }
-	if ((rc = dev_alloc(c, &d_nk, 4))) { dev_free(c, &d_rank); dev_free(c, &d_keyd); return rc; }
-	if (c->use_stream && !c->d_ws)
-	{
-		c->ws_words = (size_t) 4 * m;
-		if ((rc = dev_alloc(c, &c->d_ws, c->ws_words))) { dev_free(c, &d_rank); dev_free(c, &d_keyd); dev_free(c, &d_nk); return rc; }
-		c->d_ws_c = c->d_ws;
-	}
+	DevTemp<uint32_t> d_rank(c), d_keyd(c), d_nk(c);
+	if ((rc = d_rank.alloc(m)) || (rc = d_keyd.alloc(m)) || (rc = d_nk.alloc(4))) return rc;
+	if (c->use_stream && !c->d_ws && (rc = c->d_ws.alloc(c, (size_t) 4 * m))) return rc;
 	// one block [0, n): ranked in key space (fseq_blockkeys.hpp); FSEQ_PHASE_A_CLASSIC: the per-column sweep
 	if (c->bk_cap_words && !c->tune.phase_a_classic)
 	{
 		if (c->use_stream)
 		{
 			size_t const per = (blockkeys_stream_ws_words(m, (uint32_t) p.n, c->bsh) + 15) & ~size_t(15);
-			if (c->bkws_words < per)
-			{
-				if ((rc = dev_alloc(c, &c->d_bkws, per))) { dev_free(c, &d_rank); dev_free(c, &d_keyd); dev_free(c, &d_nk); return rc; }
-				c->bkws_words = per;
-			}
+			if ((rc = c->d_bkws.ensure(c, per))) return rc;
 			hipLaunchKernelGGL(k_blockkeys_stream, dim3(1), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, 1u,
 			                   d_rank, d_keyd, d_nk, (uint64_t) 0, c->d_bkws, per, c->bk_cap_words, (uint32_t *) nullptr, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), (uint32_t *) nullptr);
 		}
 		else
 		{
 			size_t const per = (blockkeys_scratch_halfwords(m, (uint32_t) p.n, c->bsh) + 7) & ~size_t(7);
-			if (c->bk_per_block != per || c->bk_blocks < 1)
-			{
-				if ((rc = dev_alloc(c, &c->d_bk, per))) { dev_free(c, &d_rank); dev_free(c, &d_keyd); dev_free(c, &d_nk); return rc; }
-				c->bk_per_block = per; c->bk_blocks = 1;
-			}
+			if (c->bk_per_block != per) c->d_bk.release(c);
+			if ((rc = c->d_bk.ensure(c, per))) return rc;
+			c->bk_per_block = per;
 			launch_blockkeys(c->bk_T, st, 1, c->bk_lds, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, d_rank, d_keyd, d_nk, 0, c->d_bk, per, c->bk_cap_words, nullptr, nullptr);
 		}
 	}
@@ -3025,10 +2945,7 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 	{
 		// the 16-bit LDS kernels keep block-relative divergences in 16 bits: one block of 65536 columns or more would wrap
 		if (!c->use_stream && c->ks.cap > 7168u && p.n > 65535u)
-		{
-			dev_free(c, &d_rank); dev_free(c, &d_keyd); dev_free(c, &d_nk);
 			return fail(c, FSEQ_E_UNSUPPORTED, "short path by column sweep: more than 65535 columns with 16-bit LDS state (unset FSEQ_PHASE_A_CLASSIC)");
-		}
 		launch_rank(c, 1, (uint32_t) p.n, 1, d_rank, d_keyd, d_nk);
 	}
 	std::vector<uint32_t> rank(m);
@@ -3036,7 +2953,7 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 	hipError_t e1 = hipMemcpyAsync(rank.data(), d_rank, (size_t) m * 4, hipMemcpyDeviceToHost, st);
 	hipError_t e2 = hipMemcpyAsync(&nk, d_nk, 4, hipMemcpyDeviceToHost, st);
 	hipError_t e3 = hipStreamSynchronize(st);
-	dev_free(c, &d_rank); dev_free(c, &d_keyd); dev_free(c, &d_nk);
+	release_all(c, d_rank, d_keyd, d_nk);                          // (not held through the host's part below)
 	if (e1 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e1);
 	if (e2 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e2);
 	if (e3 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path sync", e3);
@@ -3118,6 +3035,7 @@ void fseq_destroy(fseq_ctx *c)
 	if (c->stream) (void) hipStreamSynchronize(c->stream);
 	free_msa(c);
 	free_work(c);
+	assert(c->alloc_sizes.empty() && c->alloc_total == 0);       // (a buffer free_work does not know of)
 	for (auto &e : c->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_part) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_dp) if (e) (void) hipEventDestroy(e);
@@ -3163,8 +3081,8 @@ static int check_borrowed_codes(fseq_ctx *c)
 	if (c->sigma >= (1u << (8u >> c->bsh))) return FSEQ_OK;          // every code the width can hold is allowed
 	uint64_t const ncols = held_hi(c) - held_lo(c);
 	if (!ncols) return FSEQ_OK;
-	uint32_t *d_mx = nullptr;
-	int rc = dev_alloc(c, &d_mx, 1);
+	DevTemp<uint32_t> d_mx(c);
+	int rc = d_mx.alloc(1);
 	if (rc) return rc;
 	uint32_t mx = 0;
 	uint32_t const col_bytes = sym_bytes(c->p.m, c->bsh), tail = c->p.m & ((1u << c->bsh) - 1u);
@@ -3176,7 +3094,6 @@ static int check_borrowed_codes(fseq_ctx *c)
 		e = hipMemcpyAsync(&mx, d_mx, 4, hipMemcpyDeviceToHost, c->stream);
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	dev_free(c, &d_mx);
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "checking the borrowed columns", e);
 	if (mx >= c->sigma)
 	{
@@ -3198,7 +3115,6 @@ int fseq_set_device_columns(fseq_ctx *c, void const *d_codes, size_t ld, uint32_
 	c->d_msa = const_cast<uint8_t *>(static_cast<uint8_t const *>(d_codes)) - held_lo(c) * ld;
 	c->ld = ld;
 	c->bsh = 0;                              // borrowed columns are one code per byte
-	c->own_msa = false;
 	c->sigma = sigma;
 	for (uint32_t i = 0; i < 256; ++i) c->code_to_byte[i] = (uint8_t) i;
 	c->have_input = true;
@@ -3222,7 +3138,6 @@ int fseq_set_device_columns_packed(fseq_ctx *c, void const *d_packed, size_t ld_
 	c->d_msa = const_cast<uint8_t *>(static_cast<uint8_t const *>(d_packed)) - held_lo(c) * ld_bytes;
 	c->ld = ld_bytes;
 	c->bsh = bsh;
-	c->own_msa = false;
 	c->sigma = sigma;
 	for (uint32_t i = 0; i < 256; ++i) c->code_to_byte[i] = (uint8_t) i;
 	c->have_input = true;
@@ -3574,7 +3489,7 @@ int fseq_debug_list_windows(fseq_ctx *c, uint64_t *bytes_held, uint64_t *columns
 	if (!c || !c->have_result) return FSEQ_E_ARG;
 	fseq_ctx::ListWindows const &W = c->lw;
 	bool const lists = !c->res.short_path;
-	if (bytes_held) *bytes_held = W.on ? W.bytes : lists ? (uint64_t) W.ent_count * sizeof(uint2) : 0;
+	if (bytes_held) *bytes_held = W.on ? W.bytes : lists ? (uint64_t) c->d_ent.cap * sizeof(uint2) : 0;
 	if (columns_per_window) *columns_per_window = W.on ? (uint64_t) W.wb * c->B : lists ? held_hi(c) - held_lo(c) : 0;
 	if (windows) *windows = W.on ? W.nwin : lists ? 1u : 0u;
 	if (merge_windows) *merge_windows = W.on ? W.merge_windows : 0u;

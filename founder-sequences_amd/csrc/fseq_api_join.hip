@@ -37,21 +37,19 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 	while (X <= JP_MAX_CLASSES && m <= 0xFFFFFFFFull && !c->tune.join_host)
 	{
 		hipStream_t st = c->stream;
-		uint16_t *d_of = nullptr;
-		uint32_t *d_rep = nullptr, *d_size = nullptr, *d_count = nullptr, *d_off = nullptr, *d_ne = nullptr;
-		uint64_t *d_rb = nullptr;
-		uint2 *d_edges = nullptr;
-		unsigned long long *d_cursor = nullptr;
+		// (temporaries: released on every way out of the loop's body)
+		DevTemp<uint16_t> d_of(c);
+		DevTemp<uint32_t> d_rep(c), d_size(c), d_count(c), d_off(c), d_ne(c);
+		DevTemp<uint64_t> d_rb(c);
+		DevTemp<uint2> d_edges(c);
+		DevTemp<unsigned long long> d_cursor(c);
 		// (offsets into the edge array are 32-bit words on the way to the host: the capacity stays below 2^32)
 		uint64_t const cap_total = std::min<uint64_t>((uint64_t) (S > 1 ? S - 1 : 0) * std::min<uint64_t>(m, (uint64_t) X * X) + 1, 0xFFFFFFFFull);
 		int rc;
-		auto cleanup = [&]() { dev_free(c, &d_of); dev_free(c, &d_rep); dev_free(c, &d_size); dev_free(c, &d_count); dev_free(c, &d_off); dev_free(c, &d_ne);
-		                       dev_free(c, &d_rb); dev_free(c, &d_edges); dev_free(c, &d_cursor); };
-		if ((rc = dev_alloc(c, &d_of, S * m)) || (rc = dev_alloc(c, &d_rep, S * X)) || (rc = dev_alloc(c, &d_size, S * X)) || (rc = dev_alloc(c, &d_count, S)) ||
-		    (rc = dev_alloc(c, &d_off, S)) || (rc = dev_alloc(c, &d_ne, S)) || (rc = dev_alloc(c, &d_rb, S)) || (rc = dev_alloc(c, &d_edges, cap_total)) ||
-		    (rc = dev_alloc(c, &d_cursor, 1)))
+		if ((rc = d_of.alloc(S * m)) || (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) ||
+		    (rc = d_off.alloc(S)) || (rc = d_ne.alloc(S)) || (rc = d_rb.alloc(S)) || (rc = d_edges.alloc(cap_total)) ||
+		    (rc = d_cursor.alloc(1)))
 		{
-			cleanup();
 			if (rc == FSEQ_E_OOM) { c->err.clear(); break; }       // no room for the device front: the host joiner needs none
 			return rc;
 		}
@@ -62,7 +60,7 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 		if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, S * X * 4, st);
 		size_t const lds = (size_t) X * X * 4;
 		if (e == hipSuccess) e = allow_lds(k_join_edges, lds);
-		if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "join preparation", e); }
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join preparation", e);
 		hipLaunchKernelGGL(k_join_classes, dim3((uint32_t) S), dim3(JP_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count);
 		if (S > 1)
 			hipLaunchKernelGGL(k_join_edges, dim3((uint32_t) (S - 1)), dim3(JP_T), lds, st, d_of, d_count, (uint32_t) m, X, d_edges, cap_total, d_off, d_ne, d_cursor);
@@ -80,7 +78,7 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 		for (size_t i = 0; sane && i < S; ++i) sane = count[i] >= 1 && count[i] <= X;
 		std::vector<uint32_t> edge_words(sane ? 2 * (size_t) total + 2 : 2);
 		if (sane && total) e = hipMemcpy(edge_words.data(), d_edges, (size_t) total * 8, hipMemcpyDeviceToHost);
-		cleanup();
+		release_all(c, d_of, d_rep, d_size, d_count, d_off, d_ne, d_rb, d_edges, d_cursor);      // (not held through the host's part)
 		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join preparation", e);
 		if (!sane) break;                                         // (the host joiner builds its own tables from the boundary states)
 		double const t1 = now_ms();
@@ -136,17 +134,14 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 		(void) hipSetDevice(c->p.device);
 		double const t0 = now_ms();
 		hipStream_t st = c->stream;
-		uint16_t *d_of = nullptr, *d_tpos = nullptr, *d_src = nullptr, *d_match = nullptr;
-		uint32_t *d_rep = nullptr, *d_size = nullptr, *d_count = nullptr, *d_min = nullptr, *d_reprow = nullptr, *d_perm = nullptr;
-		uint64_t *d_rb = nullptr;
+		DevTemp<uint16_t> d_of(c), d_tpos(c), d_src(c), d_match(c);
+		DevTemp<uint32_t> d_rep(c), d_size(c), d_count(c), d_min(c), d_reprow(c), d_perm(c);
+		DevTemp<uint64_t> d_rb(c);
 		int rc;
-		auto cleanup = [&]() { dev_free(c, &d_of); dev_free(c, &d_tpos); dev_free(c, &d_src); dev_free(c, &d_match); dev_free(c, &d_rep); dev_free(c, &d_size);
-		                       dev_free(c, &d_count); dev_free(c, &d_min); dev_free(c, &d_reprow); dev_free(c, &d_perm); dev_free(c, &d_rb); };
-		if ((rc = dev_alloc(c, &d_of, S * m)) || (rc = dev_alloc(c, &d_tpos, S * X)) || (rc = dev_alloc(c, &d_src, S * X)) || (rc = dev_alloc(c, &d_match, S * X)) ||
-		    (rc = dev_alloc(c, &d_rep, S * X)) || (rc = dev_alloc(c, &d_size, S * X)) || (rc = dev_alloc(c, &d_count, S)) || (rc = dev_alloc(c, &d_min, S * X)) ||
-		    (rc = dev_alloc(c, &d_reprow, S * X)) || (rc = dev_alloc(c, &d_perm, S * X)) || (rc = dev_alloc(c, &d_rb, S)))
+		if ((rc = d_of.alloc(S * m)) || (rc = d_tpos.alloc(S * X)) || (rc = d_src.alloc(S * X)) || (rc = d_match.alloc(S * X)) ||
+		    (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) || (rc = d_min.alloc(S * X)) ||
+		    (rc = d_reprow.alloc(S * X)) || (rc = d_perm.alloc(S * X)) || (rc = d_rb.alloc(S)))
 		{
-			cleanup();
 			if (rc == FSEQ_E_OOM) { c->err.clear(); break; }
 			return rc;
 		}
@@ -156,7 +151,7 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 		size_t const lds_match = bip_match_lds_bytes(X), lds_chain = bip_chain_lds_bytes(X);
 		if (e == hipSuccess) e = allow_lds(k_bip_match, lds_match);
 		if (e == hipSuccess) e = allow_lds(k_bip_chain, lds_chain);
-		if (e != hipSuccess) { cleanup(); return fail(c, FSEQ_E_HIP, "bipartite join preparation", e); }
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "bipartite join preparation", e);
 		// (a segment's classes: the rows that agree on [lb, rb), lb = the segment in front's rb -- the merged segments tile the columns)
 		hipLaunchKernelGGL(k_join_classes, dim3((uint32_t) S), dim3(JP_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count);
 		hipLaunchKernelGGL(k_bip_minrow, dim3((uint32_t) S), dim3(JP_T), 0, st, d_of, (uint32_t) m, X, d_min);
@@ -169,7 +164,6 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 		if (e == hipSuccess) e = hipMemcpyAsync(permutations, d_perm, S * X * 4, hipMemcpyDeviceToHost, st);
 		if (e == hipSuccess) e = hipStreamSynchronize(st);
 		if (e == hipSuccess) e = hipGetLastError();
-		cleanup();
 		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "bipartite join", e);
 		bool sane = true;
 		for (size_t i = 0; sane && i < S; ++i) sane = count[i] >= 1 && count[i] <= X;
@@ -374,16 +368,16 @@ int fseq_write_founders_device(fseq_ctx *c, uint32_t const *permutations, char c
 	hipStream_t st = c->stream;
 	size_t const line = (size_t) c->p.n + 1;
 	size_t const batch = std::max<size_t>(1, std::min<size_t>(X, (size_t) (256u << 20) / line));
-	uint32_t *d_perm = nullptr;
-	uint64_t *d_seg = nullptr;
-	uint8_t *d_lut = nullptr, *d_out = nullptr, *h_out = nullptr;
+	DevTemp<uint32_t> d_perm(c);
+	DevTemp<uint64_t> d_seg(c);
+	DevTemp<uint8_t> d_lut(c), d_out(c);
+	uint8_t *h_out = nullptr;
 	int rc = FSEQ_OK;
 	auto cleanup = [&]() {
-		dev_free(c, &d_perm); dev_free(c, &d_seg); dev_free(c, &d_lut); dev_free(c, &d_out);
 		if (h_out) (void) hipHostFree(h_out);
 		if (f != stdout) fclose(f);
 	};
-	if ((rc = dev_alloc(c, &d_perm, S * X)) || (rc = dev_alloc(c, &d_seg, 2 * S)) || (rc = dev_alloc(c, &d_lut, 256)) || (rc = dev_alloc(c, &d_out, batch * line))) { cleanup(); return rc; }
+	if ((rc = d_perm.alloc(S * X)) || (rc = d_seg.alloc(2 * S)) || (rc = d_lut.alloc(256)) || (rc = d_out.alloc(batch * line))) { cleanup(); return rc; }
 	if (hipHostMalloc(reinterpret_cast<void **>(&h_out), batch * line, hipHostMallocDefault) != hipSuccess) { h_out = nullptr; cleanup(); return fail(c, FSEQ_E_OOM, "founders output buffer"); }
 	std::vector<uint64_t> seg(2 * S);
 	for (size_t s = 0; s < S; ++s) { seg[s] = c->segments[s].lb; seg[S + s] = c->segments[s].rb; }

@@ -208,6 +208,50 @@ struct Tuning {
 	}
 };
 
+struct fseq_ctx;
+
+namespace fseq {
+
+// A device buffer of T that a context owns.  Every device allocation of a context is one of these: fseq_ctx::alloc_total is
+// what the context holds (the memory plan of the stride states stays inside fseq_set_memory_budget's figure when ranks share
+// a card), so an allocation is always of exactly the elements asked for.  A failed allocation leaves the buffer empty.
+// The buffer converts to the pointer its users address it by: `base`, or -- rebase / alloc_range -- a pointer below it, so
+// that item i of an array of which the context holds a range only sits at + i * per (a rank of a sharded run holds its own
+// column blocks, addressed by their place in the whole alignment).
+template <typename T>
+struct DevBuf {
+	T *base = nullptr;                       // what was allocated (nullptr: empty)
+	size_t cap = 0;                          // elements asked for
+	ptrdiff_t shift = 0;                     // bytes from the pointer handed out up to base
+	operator T *() const { return base ? reinterpret_cast<T *>(reinterpret_cast<char *>(base) - shift) : nullptr; }
+	template <typename U> U *as() const { return reinterpret_cast<U *>(static_cast<T *>(*this)); }
+	void rebase(ptrdiff_t elements) { shift = elements * (ptrdiff_t) sizeof(T); }
+	int alloc(fseq_ctx *c, size_t count);                     // exactly `count` elements in place of what is held
+	int ensure(fseq_ctx *c, size_t count) { return cap >= count ? FSEQ_OK : alloc(c, count); }      // grow-only
+	int alloc_range(fseq_ctx *c, size_t lo, size_t hi, size_t per)      // items [lo, hi) of `per` elements each
+	{
+		int const rc = alloc(c, (hi > lo ? hi - lo : 0) * per);
+		rebase((ptrdiff_t) (lo * per));
+		return rc;
+	}
+	void release(fseq_ctx *c);
+};
+
+// ... of one call: released on every way out of its scope
+template <typename T>
+struct DevTemp : DevBuf<T> {
+	fseq_ctx *const c;
+	explicit DevTemp(fseq_ctx *c_) : c(c_) {}
+	DevTemp(DevTemp const &) = delete;
+	~DevTemp() { this->release(c); }
+	int alloc(size_t count) { return DevBuf<T>::alloc(c, count); }
+};
+
+template <typename... B>
+inline void release_all(fseq_ctx *c, B &...bufs) { (bufs.release(c), ...); }
+
+} // namespace fseq
+
 // One alignment over several ranks (include/fseq.h, fseq_set_shard): which blocks / columns / DP chunks are mine
 struct Shard {
 	bool on = false;
@@ -227,11 +271,12 @@ struct Shard {
 struct fseq_ctx {
 	fseq_params p{};
 	Tuning tune;                             // read from the environment once, at fseq_create
-	std::unordered_map<void *, size_t> alloc_sizes;   // device allocations of this context (dev_alloc / dev_free)
+	template <typename T> using DevBuf = fseq::DevBuf<T>;
+	std::unordered_map<void *, size_t> alloc_sizes;   // device allocations of this context (DevBuf)
 	size_t alloc_total = 0;
 	uint64_t mem_budget = 0;                  // fseq_set_memory_budget: 0 = whatever is free on the device
 	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_api.hip, plan_list_windows).  The buffer
-	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent = d_ent_alloc - (lo_w B - H) stride.
+	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent is rebased to (lo_w B - H) stride.
 	struct ListWindows {
 		uint64_t budget = 0;                  // bytes (0: every list held, the default)
 		bool on = false;                      // the last long-path run went through windows
@@ -239,7 +284,6 @@ struct fseq_ctx {
 		uint32_t merge_windows = 0;           // windows the merge's second pass ran phase C on again
 		uint64_t bytes = 0;                   // the list buffer's size
 		uint64_t col_lo = 0, col_hi = 0;      // columns whose lists the buffer holds now (fseq_debug_column_list)
-		size_t ent_count = 0;                 // entries d_ent_alloc was allocated with
 		std::vector<hipEvent_t> ev;           // per window: DP begin / end
 	} lw;
 	std::atomic<uint64_t> step_max{0}, current_step{0};      // fseq_step_max / fseq_current_step (segmentation_lp_context.hh:122-127)
@@ -249,32 +293,23 @@ struct fseq_ctx {
 	hipStream_t stream = nullptr;
 	std::string err;
 	Shard sh;
-	uint8_t *d_msa_alloc = nullptr;          // what was allocated; d_msa = d_msa_alloc - c_lo * ld (column k at d_msa + k * ld)
-	uint2 *d_ent_alloc = nullptr;
-	uint32_t *d_ss_a_alloc = nullptr, *d_ss_d_alloc = nullptr;
-	uint32_t *d_bkws = nullptr;              // ... streamed rows: per-workgroup workspace (id arrays, group ids)
-	size_t bkws_words = 0;
-	uint16_t *d_bk = nullptr;                // phase A in key space (fseq_blockkeys.hpp): per-block scratch (leaf words, group ids)
-	size_t bk_per_block = 0, bk_blocks = 0;
+	DevBuf<uint8_t> d_msa_own;               // the alignment when the context allocated it; d_msa = d_msa_own.base - c_lo * ld (column k at d_msa + k * ld)
+	DevBuf<uint32_t> d_bkws;                 // ... streamed rows: per-workgroup workspace (id arrays, group ids)
+	DevBuf<uint16_t> d_bk;                   // phase A in key space (fseq_blockkeys.hpp): per-block scratch (leaf words, group ids)
+	size_t bk_per_block = 0;                 // ... halfwords of a block in it
 	uint32_t bk_cap_words = 0;
 	uint32_t bk_T = 0;                       // threads of k_blockkeys (LDS-resident rows)
-	uint32_t *d_todo = nullptr;              // phase A: blocks the key-space tree gave up on (the column sweep does them)
-	size_t todo_cap = 0;
+	DevBuf<uint32_t> d_todo;                 // phase A: blocks the key-space tree gave up on (the column sweep does them)
 	int bk_given_up = -1;                    // ... in the last run on this input (-1: not run yet): later runs skip the sweep's launch when
 	                                         // it was none, and the tree altogether when it was most blocks
 	size_t bk_lds = 0;
-	uint32_t *d_colmask_alloc = nullptr;     // 4-bit symbols: the codes present in every held column (k_column_presence), once per input;
-	uint32_t *d_colmask = nullptr;           // d_colmask = d_colmask_alloc - c_lo (column k at d_colmask[k])
+	DevBuf<uint32_t> d_colmask;              // 4-bit symbols: the codes present in every held column (k_column_presence), once per input (column k at d_colmask[k])
 	bool colmask_ready = false, colmask_use = false;      // ... computed for this input; ... enough dense columns for the kernel that looks at it
-	uint32_t *d_btws = nullptr;              // phase A, streamed rows, the trie (fseq_blocktrie.hpp): per-workgroup workspace (the nodes of the levels)
-	size_t btws_words = 0;
-	uint32_t *d_only = nullptr;              // ... blocks the trie gave up on (the key-space tree does them)
-	size_t only_cap = 0;
+	DevBuf<uint32_t> d_btws;                 // phase A, streamed rows, the trie (fseq_blocktrie.hpp): per-workgroup workspace (the nodes of the levels)
+	DevBuf<uint32_t> d_only;                 // ... blocks the trie gave up on (the key-space tree does them)
 	int bt_given_up = -1;                    // ... in the last run on this input (-1: not run yet)
-	uint32_t *d_chunk_r0 = nullptr;          // speculative DP: first round of every chunk (+ the end)
-	uint32_t chunk_cap = 0;
-	uint2 *d_tau = nullptr;                  // merge thresholds (k_seg_tau) / counts
-	size_t tau_cap = 0;
+	DevBuf<uint32_t> d_chunk_r0;             // speculative DP: first round of every chunk (+ the end)
+	DevBuf<uint2> d_tau;                     // merge thresholds (k_seg_tau) / counts
 	std::vector<int64_t> snap_slot;          // segment index -> slot in d_snap_* (-1: another rank's)
 	// sharded DP (run_dp_spec): the DP entries [own_lo[g], own_hi[g]) belong to rank g (the last active rank also owns the
 	// final cell's); dp_window_mode: a rank holds its own entries and a window of the others' in front of them, not the
@@ -285,9 +320,8 @@ struct fseq_ctx {
 	uint64_t dp_exchange_words = 0;          // words the DP's sweep exchanges moved in the last run (diagnostics)
 
 	// input
-	uint8_t *d_msa = nullptr;
+	uint8_t *d_msa = nullptr;                // (not a DevBuf: the caller's own columns when the input was borrowed, fseq_set_device_columns)
 	size_t ld = 0;
-	bool own_msa = false;
 	bool have_input = false;
 	uint32_t sigma = 0;
 	uint8_t code_to_byte[256]{};
@@ -304,80 +338,69 @@ struct fseq_ctx {
 	bool use_stream = false;             // m too large for an LDS-resident order: HBM-streamed kernels (fseq_stream.hpp)
 	size_t tb_guess = 0;                 // traceback entries of the last run (sizes the speculative copy of the next)
 	std::vector<uint2> tau_host;         // merge thresholds that came back with the traceback (not sharded)
-	uint32_t *d_ws = nullptr;            // their per-block workspaces
-	size_t ws_words = 0;
+	DevBuf<uint32_t> d_ws;               // their per-block workspaces: streamed phase C's of block b at d_ws + b * (words per block); phase A's column
+	                                     // sweep, phase B and pass 2 index the same memory by workgroup, from d_ws.base
 	size_t lds_columns = 0;
 
 	// device work buffers
 	// per column block: key blocks (phase A) and boundary states (phase B), indexed by the block's place in the whole
-	// alignment.  A rank of a sharded run allocates its own blocks [b_lo, b_hi] only (*_alloc) and shifts the pointer
+	// alignment.  A rank of a sharded run allocates its own blocks [b_lo, b_hi] only and shifts the pointer
 	// (block b at d_rank + b * m as before): memory per rank falls with the rank count
-	uint32_t *d_rank = nullptr, *d_keyd = nullptr, *d_nkeys = nullptr;
-	uint32_t *d_bstate_a = nullptr, *d_bstate_d = nullptr;
-	uint32_t *d_rank_alloc = nullptr, *d_keyd_alloc = nullptr, *d_nkeys_alloc = nullptr, *d_bstate_a_alloc = nullptr, *d_bstate_d_alloc = nullptr;
-	uint32_t *d_cshist = nullptr;            // streamed phase B spread over the chip (fseq_chainsort.hpp): digit histograms [chain][part][bin]
-	uint32_t *d_ws_c = nullptr;              // streamed phase C: the per-block workspaces, block b at d_ws_c + b * (words per block)
-	uint32_t *d_hrank = nullptr, *d_hkeyd = nullptr, *d_hnkeys = nullptr, *d_hstate_a = nullptr, *d_hstate_d = nullptr;
+	DevBuf<uint32_t> d_rank, d_keyd, d_nkeys;
+	DevBuf<uint32_t> d_bstate_a, d_bstate_d;
+	DevBuf<uint32_t> d_cshist;               // streamed phase B spread over the chip (fseq_chainsort.hpp): digit histograms [chain][part][bin]
+	DevBuf<uint32_t> d_hrank, d_hkeyd, d_hnkeys, d_hstate_a, d_hstate_d;
 	// not sharded: phase B over any number of levels (levels[i - 1] = the composites of chain_fan level-(i - 1) key blocks)
-	struct ChainLevel { uint32_t count = 0; uint64_t cols = 0; uint32_t *rank = nullptr, *keyd = nullptr, *nkeys = nullptr, *state_a = nullptr, *state_d = nullptr;
-	                    uint32_t *rank_alloc = nullptr, *keyd_alloc = nullptr, *nkeys_alloc = nullptr, *state_a_alloc = nullptr, *state_d_alloc = nullptr; };
+	struct ChainLevel { uint32_t count = 0; uint64_t cols = 0; DevBuf<uint32_t> rank, keyd, nkeys, state_a, state_d; };
 	std::vector<ChainLevel> levels;
 	uint32_t chain_fan = 0;
 	uint32_t shard_k = 0, shard_q = 0;       // sharded: a rank's hyper-block = shard_q groups of chain_fan^shard_k blocks
 	uint32_t chain_G = 0, n_super = 0;       // sharded: super-blocks of chain_G blocks
 	uint32_t chain_G2 = 0, n_hyper = 0;      // third level: hyper-blocks of chain_G2 super-blocks (0 = two levels only)
-	uint2 *d_ent = nullptr;
-	uint4 *d_hdr = nullptr;
+	DevBuf<uint2> d_ent;                     // the lists: column k at d_ent + k * stride
+	DevBuf<uint4> d_hdr;
 	uint32_t X = 0, stride = 0;
 	uint32_t X_hint = 0;                     // list capacity that worked on the last run of this input
-	fseq::DpArrays dp{};
-	uint32_t *d_Mprev = nullptr;             // chunk-speculative DP: the iterate the last sweep started from
-	uint32_t *d_spec = nullptr;              // its per-chunk words (active, changed, tailmin, floor, lift, 2 x ovf) + SpecCtl
-	uint32_t spec_cap = 0;
-	uint32_t *d_flags = nullptr;
-	uint32_t *d_recent = nullptr;            // k_boundary_recent counts, one per block boundary
+	struct Dp {                              // phase D's arrays; the kernels take them as DpArrays (fseq_types.hpp)
+		DevBuf<uint32_t> M, LB, SZ, Tb, Tbv;
+		DevBuf<unsigned long long> K;
+		uint32_t tstride = 0;
+		operator fseq::DpArrays() const { return fseq::DpArrays{M, LB, SZ, Tb, Tbv, K, tstride}; }
+	} dp;
+	DevBuf<uint32_t> d_Mprev;                // chunk-speculative DP: the iterate the last sweep started from
+	DevBuf<uint32_t> d_spec;                 // its per-chunk words (active, changed, tailmin, floor, lift, 2 x ovf) + SpecCtl
+	DevBuf<uint32_t> d_flags;
+	DevBuf<uint32_t> d_recent;               // k_boundary_recent counts, one per block boundary
 	uint64_t dp_size = 0;
-	uint64_t *d_cols = nullptr;           // scratch: column / rb lists
-	size_t cols_cap = 0;
-	uint2 *d_grp = nullptr;
-	size_t grp_cap = 0;
-	uint64_t *d_src = nullptr;
-	size_t src_cap = 0;
+	DevBuf<uint64_t> d_cols;                 // scratch: column / rb lists
+	DevBuf<uint2> d_grp;
+	DevBuf<uint64_t> d_src;
 	uint32_t snap_stride = 16;            // phase C drops the exact (a,d) every snap_stride columns for pass 2
-	uint32_t *d_ss_a = nullptr, *d_ss_d = nullptr;
+	DevBuf<uint32_t> d_ss_a, d_ss_d;      // the stride states: the state at column q * snap_stride at d_ss_* + q * (words of a state)
 	uint32_t ss_pack = 0;                 // streamed rows: stride states packed to 5 bytes per row (bits of a row id; fseq_stream.hpp)
 	bool ss_ids = false;                  // ... and in ID form: the packed rows of phase C's workspace; pass 2 replays them on the same tile step (fseq_stream2.hpp, S2_SNAP)
-	uint32_t *d_bs_w_alloc = nullptr, *d_bs_w = nullptr;      // ... with every block's start state in the same form (block b at d_bs_w + b * m)
-	uint8_t *d_bs_h_alloc = nullptr, *d_bs_h = nullptr;
-	uint32_t *d_wgblk = nullptr;          // pass 2 on the tile step: block and groups of every workgroup
-	uint2 *d_wggrp = nullptr;
-	size_t wg_cap = 0;
-	uint2 *d_gent = nullptr;
-	uint4 *d_ghdr = nullptr;
-	size_t gather_cap = 0, gather_stride = 0;
-	uint32_t *d_snap_a = nullptr, *d_snap_d = nullptr;
-	size_t snap_cap = 0;
+	DevBuf<uint32_t> d_bs_w;              // ... with every block's start state in the same form (block b at d_bs_w + b * m)
+	DevBuf<uint8_t> d_bs_h;
+	DevBuf<uint32_t> d_wgblk;             // pass 2 on the tile step: block and groups of every workgroup
+	DevBuf<uint2> d_wggrp;
+	DevBuf<uint32_t> d_snap_a, d_snap_d;
 
 	// [r5] phase C / pass 2 on representative rows (fseq_reduced.hpp): per block [red_cap] representatives (ascending row id),
 	// their block keys, the reduced start state; the reduced alignment (column k at d_red_msa + k * red_ld)
-	uint32_t *d_red_cnt = nullptr, *d_red_vmin = nullptr, *d_red_rows = nullptr, *d_red_leaf = nullptr, *d_red_a = nullptr, *d_red_d = nullptr;
-	uint32_t *d_red_rows_alloc = nullptr, *d_red_leaf_alloc = nullptr, *d_red_a_alloc = nullptr, *d_red_d_alloc = nullptr;      // (a rank holds its own blocks' rows)
-	uint32_t *d_red_invalid = nullptr, *d_red_blocks = nullptr;
-	uint32_t red_cap = 0, red_blocks_cap = 0;
-	uint8_t *d_red_msa = nullptr, *d_red_msa_alloc = nullptr;
-	size_t red_ld = 0, red_msa_bytes = 0;
+	DevBuf<uint32_t> d_red_cnt, d_red_vmin, d_red_rows, d_red_leaf, d_red_a, d_red_d;      // (a rank holds its own blocks' rows)
+	DevBuf<uint32_t> d_red_invalid, d_red_blocks;
+	uint32_t red_cap = 0;
+	DevBuf<uint8_t> d_red_msa;
+	size_t red_ld = 0;
 	std::vector<uint32_t> red_cnt_host;      // representatives per block of the last prep (RED_NONE: not reduced)
 	std::vector<uint8_t> red_full;           // blocks this run sends to the kernel on all rows
 	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives (1); 2: the block
 	                                         // stays reduced but skips the slim configuration, which refused it
 	bool red_active = false;                 // this run's phase C went through the representatives (pass 2 follows it)
-	uint32_t *d_red_cls = nullptr, *d_red_headd = nullptr, *d_red_ncls = nullptr, *d_red_taskblk = nullptr, *d_red_wgtasks = nullptr;
-	uint32_t *d_red_p2grp = nullptr;         // streamed pass 2: its groups {first task, count} and the counter they are taken by
-	size_t red_task_cap = 0;
-	uint32_t *d_red_ss_a_alloc = nullptr, *d_red_ss_d_alloc = nullptr;
-	uint32_t *d_red_ss_a = nullptr, *d_red_ss_d = nullptr;      // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
+	DevBuf<uint32_t> d_red_cls, d_red_headd, d_red_ncls, d_red_taskblk, d_red_wgtasks;
+	DevBuf<uint32_t> d_red_p2grp;            // streamed pass 2: its groups {first task, count} and the counter they are taken by
+	DevBuf<uint32_t> d_red_ss_a, d_red_ss_d; // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
 	uint32_t red_ss_stride = 0, red_ss_cap = 0;
-	size_t red_ss_words = 0;
 	uint32_t *h_red_pin = nullptr;           // pinned host staging of the plan (counts back, block lists out): its own buffer, live across the run
 	size_t red_pin_words = 0;
 	struct RedBin { int config; uint32_t first, count; };     // blocks [first, first + count) of d_red_blocks run on configuration `config`
@@ -393,7 +416,7 @@ struct fseq_ctx {
 	uint32_t red_declined_X = 0;
 	bool red_plan_valid = false;
 	uint32_t red_plan_X = 0, red_plan_blocks = 0, red_plan_rows_mean = 0;
-	uint32_t *d_red_cnt_plan = nullptr;
+	DevBuf<uint32_t> d_red_cnt_plan;
 	hipStream_t red_st[2]{};                 // the configurations' launches side by side: the context's second stream, then these
 	hipEvent_t red_ev[4]{};
 	uint8_t *h_red_pin2 = nullptr;           // pass 2's task lists (pinned)
@@ -402,9 +425,7 @@ struct fseq_ctx {
 	// results
 	bool have_result = false;
 	fseq_result res{};
-	uint4 *d_tb = nullptr;                   // the traceback kernels' output {entry, lb, key, size} per segment, window heads, counts
-	size_t tb_cap = 0;
-	uint32_t tb_win = 0;
+	DevBuf<uint4> d_tb;                      // the traceback kernels' output {entry, lb, key, size} per segment, window heads, counts
 	std::vector<fseq_dp_arg> traceback;
 	std::vector<fseq_segment> segments;
 	std::vector<uint32_t> sp_first, sp_len;
@@ -445,27 +466,27 @@ inline void progress(fseq_ctx *c, int stage, uint64_t current, uint64_t max)
 		if (e_ != hipSuccess) return fail((c), FSEQ_E_HIP, #expr, e_);     \
 	} while (0)
 
-template <typename U>
-inline void dev_free(fseq_ctx *c, U **p)
+template <typename T>
+void DevBuf<T>::release(fseq_ctx *c)
 {
-	if (!*p) return;
-	auto it = c->alloc_sizes.find(static_cast<void *>(*p));
-	if (it != c->alloc_sizes.end()) { c->alloc_total -= it->second; c->alloc_sizes.erase(it); }
-	(void) hipFree(*p);
-	*p = nullptr;
+	if (base)
+	{
+		auto it = c->alloc_sizes.find(static_cast<void *>(base));
+		if (it != c->alloc_sizes.end()) { c->alloc_total -= it->second; c->alloc_sizes.erase(it); }
+		(void) hipFree(base);
+	}
+	*this = DevBuf<T>{};
 }
 
-// every device allocation of a context goes through here: alloc_total is what the context holds (the memory plan of
-// the stride states stays inside fseq_set_memory_budget's figure when ranks share a card)
-template <typename U>
-inline int dev_alloc(fseq_ctx *c, U **p, size_t count)
+template <typename T>
+int DevBuf<T>::alloc(fseq_ctx *c, size_t count)
 {
-	dev_free(c, p);
-	size_t const bytes = std::max<size_t>(count, 1) * sizeof(U);
-	hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
+	release(c);
+	size_t const bytes = std::max<size_t>(count, 1) * sizeof(T);
+	hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), bytes);
 	if (e != hipSuccess)
 	{
-		*p = nullptr;
+		base = nullptr;
 		size_t free_b = 0, total_b = 0;
 		(void) hipMemGetInfo(&free_b, &total_b);
 		(void) hipGetLastError();          // the runtime remembers the failure: the checks behind later launches (of this or any
@@ -474,20 +495,10 @@ inline int dev_alloc(fseq_ctx *c, U **p, size_t count)
 		snprintf(what, sizeof(what), "hipMalloc of %zu bytes (%zu of %zu bytes free on the device)", bytes, free_b, total_b);
 		return fail(c, e == hipErrorOutOfMemory ? FSEQ_E_OOM : FSEQ_E_HIP, what, e);
 	}
-	c->alloc_sizes[static_cast<void *>(*p)] = bytes;
+	cap = count;
+	c->alloc_sizes[static_cast<void *>(base)] = bytes;
 	c->alloc_total += bytes;
 	return FSEQ_OK;
 }
-
-// items [lo, hi) of an array of `per` words per item: *alloc owns the memory, *view is shifted so that item i sits at
-// *view + i * per (a rank of a sharded run holds its own column blocks only, addressed by their place in the whole alignment)
-template <typename U>
-inline int dev_alloc_range(fseq_ctx *c, U **alloc, U **view, size_t lo, size_t hi, size_t per)
-{
-	int const rc = dev_alloc(c, alloc, (hi > lo ? hi - lo : 0) * per);
-	*view = rc ? nullptr : *alloc - lo * per;
-	return rc;
-}
-
 
 } // namespace fseq

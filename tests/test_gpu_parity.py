@@ -30,6 +30,12 @@ def compare_long(pkg, msa, L, check_dp=True, **kw):
     m, n = msa.shape
     ref = fso.segment_long(msa, L, keep_dp=check_dp, threads=4)
     ctx = run_gpu(pkg, msa, L, **kw)
+    check_long(ctx, ref, n, L, check_dp)
+    return ctx, ref
+
+
+def check_long(ctx, ref, n, L, check_dp=True):
+    """The result a context holds against the oracle's, bit for bit."""
     assert ctx.result.short_path == 0
     assert ctx.result.max_segment_size == ref["max_segment_size"]
     if check_dp:
@@ -46,7 +52,7 @@ def compare_long(pkg, msa, L, check_dp=True, **kw):
         assert np.array_equal(tb[f], ref["traceback"][f]), f
     if ref["status"] != 0:
         assert ctx.result.segment_count == 0
-        return ctx, ref
+        return
     red = ctx.reduced_traceback()
     assert len(red) == len(ref["reduced"])
     for f in ("lb", "rb", "segment_size"):
@@ -55,7 +61,6 @@ def compare_long(pkg, msa, L, check_dp=True, **kw):
         a, d = ctx.boundary_state(i)
         assert np.array_equal(a, ref["a"][i]), i
         assert np.array_equal(d, ref["d"][i]), i
-    return ctx, ref
 
 
 CASES = [
