@@ -67,6 +67,18 @@ class JoinProfile(C.Structure):
                 ("bytes_d2h", C.c_uint64)]
 
 
+class MatchPiece(C.Structure):
+    _fields_ = [("lb", C.c_uint64), ("rb", C.c_uint64), ("row", C.c_uint32), ("n_founders", C.c_uint32)]
+
+
+class MatchSummary(C.Structure):
+    _fields_ = [("pieces", C.c_uint64), ("uncovered_cells", C.c_uint64), ("short_pieces", C.c_uint64), ("max_pieces_per_row", C.c_uint64),
+                ("n_founders", C.c_uint32), ("set_words", C.c_uint32), ("ms_device", C.c_double)]
+
+
+MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
+MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
+
 SEGMENT_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("segment_size", "<u4"), ("reserved", "<u4")])
 DPARG_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("segment_max_size", "<u4"), ("segment_size", "<u4")])
 
@@ -82,6 +94,7 @@ EXPORTS = [
     "fseq_set_progress", "fseq_step_max", "fseq_current_step", "fseq_set_memory_budget", "fseq_write_segments_host", "fseq_get_join_profile", "fseq_debug_set_tuning",
     "fseq_shard_abort", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges",
     "fseq_set_list_memory", "fseq_debug_list_windows",
+    "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -169,6 +182,10 @@ def load_library():
     L.fseq_debug_dp_owned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fseq_debug_clock.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.fseq_debug_ranges.argtypes = [C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)]
+    L.fseq_match_founders.argtypes = [vp, vp, u64, C.POINTER(MatchSummary)]
+    L.fseq_match_founder_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
+    L.fseq_get_match.argtypes = [vp, vp, vp]
+    L.fseq_write_match.argtypes = [vp, C.c_char_p]
     _lib = L
     return L
 
@@ -528,6 +545,44 @@ class SegmentationContext:
         rows = (C.c_void_p * self.m)(*[msa.ctypes.data + r * msa.strides[0] for r in range(self.m)])
         perm = np.ascontiguousarray(permutations, dtype=np.uint32)
         self._check(self.L.fseq_write_founders(self.h, rows, perm.ctypes.data, path.encode() if path else None))
+
+    # ---- the founders checked against the input (match-sequences-to-founders, on the device)
+    def match_founders(self, permutations=None, founders=None, min_segment_length=0):
+        """Thread every input row through the founders greedily (fseq_match_founders / fseq_match_founder_rows).
+        permutations: those of a join on this context (the founders write_founders_device would write); or founders: a
+        C-contiguous uint8 array [K, n] of raw bytes (or a list of K bytes objects of length n).  Returns the summary as a
+        dict; match_pieces() has the pieces."""
+        if (permutations is None) == (founders is None):
+            raise ValueError("match_founders: give either permutations or founders")
+        sm = MatchSummary()
+        if permutations is not None:
+            perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+            self._check(self.L.fseq_match_founders(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
+        else:
+            if not isinstance(founders, np.ndarray):
+                founders = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in founders], dtype=np.uint8).reshape(len(founders), -1)
+            founders = np.ascontiguousarray(founders, dtype=np.uint8)
+            if founders.ndim != 2 or founders.shape[1] != self.n:
+                raise ValueError("match_founders: founders must be K rows of n = %d bytes" % self.n)
+            K = founders.shape[0]
+            rows = (C.c_void_p * max(K, 1))(*[founders.ctypes.data + r * founders.strides[0] for r in range(K)])
+            self._check(self.L.fseq_match_founder_rows(self.h, rows, K, int(min_segment_length), C.byref(sm)))
+        self._match = sm
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    def match_pieces(self):
+        """(pieces, sets) of the last match: pieces as MATCH_PIECE_DTYPE records ordered by row, then lb; sets[i] the founder
+        set of piece i as set_words uint32 words (founder f at bit f % 32 of word f // 32)."""
+        sm = getattr(self, "_match", None)
+        n_pieces, words = (sm.pieces, sm.set_words) if sm is not None else (0, 1)
+        pieces = np.zeros(n_pieces, dtype=MATCH_PIECE_DTYPE)
+        sets = np.zeros((n_pieces, words), dtype=np.uint32)
+        self._check(self.L.fseq_get_match(self.h, pieces.ctypes.data, sets.ctypes.data))
+        return pieces, sets
+
+    def write_match(self, path):
+        """The report of match-sequences-to-founders for the last match (SEQUENCE_INDEX LB RB FOUNDER_INDICES)."""
+        self._check(self.L.fseq_write_match(self.h, path.encode() if path else None))
 
     # ---- debug / parity of intermediate state
     def debug_dp(self):

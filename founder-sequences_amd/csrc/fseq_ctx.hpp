@@ -1,7 +1,7 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
 // shares: csrc/fseq_api.hip (the path: geometry, buffers, phases, sharding, the ABI's entry points) and
-// csrc/fseq_api_join.hip (the host joiners, their device front and the output writers).  Internal: nothing here is part of
-// the boundary.
+// csrc/fseq_api_join.hip (the host joiners, their device front and the output writers) and csrc/fseq_api_match.hip (the rows
+// matched against founders).  Internal: nothing here is part of the boundary.
 #pragma once
 
 #include "../../include/fseq.h"
@@ -436,6 +436,25 @@ struct fseq_ctx {
 	hipEvent_t ev_dp[2]{};                   // DP begin / end on stream2
 	uint8_t *h_pin = nullptr;                // pinned host staging of a step's small transfers (pin_reserve / pin_take)
 	size_t pin_cap = 0, pin_used = 0;
+
+	// matching the rows against founders (fseq_match_founders, csrc/fseq_api_match.hip): nothing is allocated before the first
+	// match; a run of the segmentation does not touch these
+	struct Match {
+		DevBuf<uint8_t> fcols;               // the founders as columns: the code of founder f at column k in fcols[k * Kp + f]
+		DevBuf<uint32_t> cnt;                // counting pass: pieces, uncovered cells, short pieces of every row ([3][m])
+		DevBuf<uint64_t> off;                // first piece of every row (+ the total), then the four totals of the summary
+		DevBuf<fseq_match_piece> pieces;     // the last match: pieces by row, then lb
+		DevBuf<uint32_t> sets;               // ... their founder sets, set_words each
+		bool have = false;
+		fseq_match_summary sum{};
+		hipEvent_t ev[4]{};
+	} match;
+	void free_match()
+	{
+		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets);
+		for (auto &e : match.ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+		match.have = false;
+	}
 };
 
 

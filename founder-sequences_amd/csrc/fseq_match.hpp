@@ -1,0 +1,347 @@
+// fseq_match.hpp -- the input rows matched against founders on the device (include/fseq.h, fseq_match_founders).
+//
+// replaces: match-sequences-to-founders (match_founder_sequences.cc:108-259): per input row, the loop of
+// match_context::match_sequence_and_report (:152-216) with the set of founders that still agree with the row held as a bit
+// set instead of an index vector -- one AND per 32 founders and cell instead of one byte compare per live founder.
+//
+//   k_match_founders_cols / k_match_founder_rows   the K founders as columns of one code per byte: founder f at column k in
+//       fcols[k * Kp + f], Kp = K rounded up to 64 (a tile of columns is one contiguous piece of memory).  From the
+//       permutations of a finished run and the resident alignment (founder r in segment s is row permutations[s][r]; a slot
+//       >= m is the byte '-', as k_founders prints it), or from K raw rows (bytes through the context's alphabet).
+//       A founder symbol no row can have is MT_NOCODE.  (One byte per code whatever the alignment's packing: at 2 bits a
+//       full alphabet has no code left for "matches nothing", and the walk reads 64 founders of a column as 64 lanes.)
+//   k_match_walk<WR, WRITE>   one LANE per input row, the columns in order.  Per tile of columns the workgroup lays out in
+//       LDS, for every column and code, the set of founders that carry the code there (64 founders = 64 lanes, one __ballot
+//       per code present among them), then every lane walks the tile: live &= set[column][my code], test for zero, on a
+//       close restart from set[column][my code].  The tile's founder codes and the workgroup's slice of the tile's alignment
+//       columns come in through registers, 16 bytes a lane and load, one tile ahead of the walk.
+//       The live set: WR words in registers (WR = 1, 2, 4, 8: up to 256 founders), or -- WR = 0 -- ceil(K / 32) words per lane
+//       in LDS, up to MT_MAX_FOUNDERS = 2,048 founders.
+//       The walk runs twice: WRITE = false counts the pieces, uncovered cells and short pieces of every row; after
+//       k_match_scan's exclusive scan over the rows WRITE = true stores the pieces and their sets where they belong.
+//
+// The walk is sequential along the columns: with m rows only ceil(m / 64) waves are in flight, and the time is a chain over n
+// columns, not throughput (DESIGN.md section 7 prices the split of a row's columns over workgroups; it is not built).
+#pragma once
+
+#include "../../include/fseq.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+namespace fseq {
+
+constexpr uint32_t MT_T = 256;                      // threads = rows of a walk workgroup
+constexpr uint32_t MT_MAX_FOUNDERS = 2048;          // the LDS variant's live sets: 64 words a lane
+constexpr uint32_t MT_TILE_MAX = 64;                // columns of a tile at most
+constexpr uint32_t MT_PREFETCH = 4;                 // 16-byte loads per lane and staged array: 16 KB of either a tile
+constexpr uint32_t MT_STAGE_BYTES = MT_T * MT_PREFETCH * 16;
+constexpr uint32_t MT_SET_BYTES = 64 * 1024;        // the tile's founder sets
+constexpr size_t   MT_LDS_BYTES = 152 * 1024;       // what a workgroup may take in all
+constexpr uint32_t MT_NOCODE = 0xFF;                // a founder symbol outside the alphabet (sigma < 256; with 256 codes there is none)
+constexpr uint32_t MT_SCAN_T = 1024;
+
+__host__ __device__ inline uint64_t mt_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
+__host__ __device__ inline uint64_t mt_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+
+struct MatchShape {
+	uint32_t K, Kp, W, WR, Wk, TC;                  // founders, padded to 64, words of a set, register words (0: LDS), words the kernel holds, tile
+	size_t lds;
+};
+
+inline size_t match_lds_bytes(uint32_t sigma, uint32_t bsh, MatchShape const &s)
+{
+	return (size_t) s.TC * s.Kp + (size_t) s.TC * (MT_T >> bsh) + ((size_t) s.TC * sigma + 1) * s.Wk * 4 + (s.WR ? 0 : (size_t) s.Wk * MT_T * 4);
+}
+
+// the variant and the tile for K founders (K <= MT_MAX_FOUNDERS)
+inline MatchShape match_shape(uint32_t K, uint32_t sigma, uint32_t bsh)
+{
+	MatchShape s{};
+	s.K = K; s.Kp = (K + 63u) & ~63u; s.W = (K + 31u) / 32u;
+	s.WR = s.W <= 1 ? 1u : s.W <= 2 ? 2u : s.W <= 4 ? 4u : s.W <= 8 ? 8u : 0u;
+	s.Wk = s.WR ? s.WR : s.W;
+	uint32_t tc = MT_TILE_MAX;
+	tc = std::min<uint32_t>(tc, MT_SET_BYTES / (sigma * s.Wk * 4u));
+	tc = std::min<uint32_t>(tc, MT_STAGE_BYTES / s.Kp);
+	tc = std::min<uint32_t>(tc, MT_STAGE_BYTES / (MT_T >> bsh));
+	s.TC = std::max<uint32_t>(tc, 1u);
+	while (s.TC > 1 && match_lds_bytes(sigma, bsh, s) > MT_LDS_BYTES) --s.TC;
+	s.lds = match_lds_bytes(sigma, bsh, s);
+	return s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// founders as columns, from the permutations of a run.  Workgroup: 64 columns; the segment of every column is found once
+// (seg_rb ascending, the segments tile [0, n)), then the lanes run along the founders (coalesced stores; the loads hit the
+// column's ld bytes).
+// ------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void k_match_founders_cols(
+	uint8_t const *__restrict__ msa, size_t ld, uint32_t m, uint64_t n, uint32_t bsh, uint32_t const *__restrict__ perm, uint32_t X,
+	uint64_t const *__restrict__ seg_rb, uint32_t S, uint32_t gap_code, uint32_t Kp, uint8_t *__restrict__ fcols)
+{
+	__shared__ uint32_t seg_of[64];
+	uint64_t const c0 = (uint64_t) blockIdx.x * 64u;
+	uint32_t const tc = (uint32_t) mt_min(64u, n - c0);
+	if (threadIdx.x < tc)
+	{
+		uint64_t const k = c0 + threadIdx.x;
+		uint32_t lo = 0, hi = S - 1u;                    // first segment whose rb is beyond k
+		while (lo < hi) { uint32_t const mid = (lo + hi) / 2u; if (seg_rb[mid] > k) hi = mid; else lo = mid + 1u; }
+		seg_of[threadIdx.x] = lo;
+	}
+	__syncthreads();
+	uint32_t const bits = 8u >> bsh, cmask = (1u << bits) - 1u;
+	for (uint32_t i = threadIdx.x; i < tc * Kp; i += 256u)
+	{
+		uint32_t const j = i / Kp, f = i - j * Kp;
+		uint64_t const k = c0 + j;
+		uint32_t code = MT_NOCODE;
+		if (f < X)
+		{
+			uint32_t const src = perm[(size_t) seg_of[j] * X + f];
+			code = src < m ? (msa[k * ld + (src >> bsh)] >> ((src & ((1u << bsh) - 1u)) * bits)) & cmask : gap_code;
+		}
+		fcols[k * Kp + f] = (uint8_t) code;
+	}
+}
+
+// ... from K raw rows (raw[f * n + k]): 64 x 64 tiles through LDS, loads along the columns, stores along the founders
+static __global__ __launch_bounds__(256) void k_match_founder_rows(
+	uint8_t const *__restrict__ raw, uint64_t n, uint32_t K, uint32_t Kp, uint8_t const *__restrict__ code_of, uint8_t *__restrict__ fcols)
+{
+	__shared__ uint8_t lut[256];
+	__shared__ uint8_t tile[64][65];
+	lut[threadIdx.x] = code_of[threadIdx.x];
+	uint64_t const c0 = (uint64_t) blockIdx.x * 64u;
+	uint32_t const x = threadIdx.x & 63u, y = threadIdx.x >> 6;
+	for (uint32_t f0 = 0; f0 < Kp; f0 += 64u)
+	{
+		__syncthreads();
+		for (uint32_t fy = y; fy < 64u; fy += 4u)
+			tile[fy][x] = (f0 + fy < K && c0 + x < n) ? lut[raw[(size_t) (f0 + fy) * n + c0 + x]] : (uint8_t) MT_NOCODE;
+		__syncthreads();
+		for (uint32_t cy = y; cy < 64u; cy += 4u)
+			if (c0 + cy < n) fcols[(c0 + cy) * Kp + f0 + x] = tile[x][cy];
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// the live set of a lane: WR words in registers, or (WR = 0) `words` words in LDS, word i of lane t at p[i * MT_T + t]
+// ------------------------------------------------------------------------------------------------
+template <uint32_t WR>
+struct MatchLive {
+	uint32_t w[WR];
+	__device__ __forceinline__ MatchLive(uint32_t *, uint32_t) {}
+	__device__ __forceinline__ uint32_t words() const { return WR; }
+	__device__ __forceinline__ uint32_t get(uint32_t i) const { return w[i]; }
+	__device__ __forceinline__ void set(uint32_t i, uint32_t v) { w[i] = v; }
+};
+template <>
+struct MatchLive<0> {
+	uint32_t *p;
+	uint32_t nw;
+	__device__ __forceinline__ MatchLive(uint32_t *p_, uint32_t nw_) : p(p_), nw(nw_) {}
+	__device__ __forceinline__ uint32_t words() const { return nw; }
+	__device__ __forceinline__ uint32_t get(uint32_t i) const { return p[i * MT_T]; }
+	__device__ __forceinline__ void set(uint32_t i, uint32_t v) { p[i * MT_T] = v; }
+};
+
+struct MatchWalkArgs {
+	uint8_t const *msa; size_t ld; uint32_t m; uint64_t n; uint32_t bsh, sigma;
+	uint8_t const *fcols;
+	uint32_t K, Kp, W, Wk, TC;
+	uint64_t min_len;
+	uint32_t *cnt;                                   // WRITE = false: [3][m]
+	uint64_t const *off;                             // WRITE = true: first piece of every row
+	fseq_match_piece *pieces;
+	uint32_t *sets;
+};
+
+// LDS: [TC x Kp founder codes][TC x (MT_T >> bsh) bytes of alignment columns][(TC x sigma + 1) sets of Wk words; the last one
+// stays empty][WR = 0: Wk x MT_T words of live sets]
+template <uint32_t WR, bool WRITE>
+static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const A)
+{
+	extern __shared__ uint4 mt_smem[];
+	uint32_t const tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+	uint32_t const bsh = A.bsh, bits = 8u >> bsh, cmask = (1u << bits) - 1u, smask = (1u << bsh) - 1u;
+	uint32_t const rowbytes = MT_T >> bsh, cpc = rowbytes / 16u;         // this workgroup's rows in a column: bytes, 16-byte chunks
+	uint32_t const Kp = A.Kp, K = A.K, Wk = A.Wk, TC = A.TC, sigma = A.sigma, groups = Kp / 64u;
+	uint8_t *const fst = reinterpret_cast<uint8_t *>(mt_smem);
+	uint8_t *const syms = fst + (size_t) TC * Kp;
+	uint32_t *const sets = reinterpret_cast<uint32_t *>(syms + (size_t) TC * rowbytes);
+	uint32_t *const empty_set = sets + (size_t) TC * sigma * Wk;
+	uint32_t *const live_lds = empty_set + Wk + tid;
+	size_t const slice = (size_t) blockIdx.x * rowbytes;                 // where the workgroup's rows start in a column
+	uint32_t const row = blockIdx.x * MT_T + tid;
+	bool const active = row < A.m;
+	uint64_t const n = A.n, min_len = A.min_len;
+
+	for (uint32_t i = tid; i < Wk; i += MT_T) empty_set[i] = 0u;
+
+	MatchLive<WR> live(live_lds, Wk);
+	for (uint32_t i = 0; i < live.words(); ++i)
+		live.set(i, K >= 32u * (i + 1u) ? ~0u : (K > 32u * i ? (1u << (K - 32u * i)) - 1u : 0u));
+	uint64_t lb = 0;
+	uint32_t npieces = 0, nunc = 0, nshort = 0;
+	bool alive = true;
+	uint64_t const out0 = (WRITE && active) ? A.off[row] : 0;
+
+	auto emit = [&](uint64_t rb) {
+		if (WRITE)
+		{
+			uint64_t const at = out0 + npieces;
+			uint32_t pc = 0;
+			for (uint32_t i = 0; i < live.words(); ++i)
+			{
+				uint32_t const v = live.get(i);
+				pc += __popc(v);
+				if (i < A.W) A.sets[at * A.W + i] = v;
+			}
+			fseq_match_piece *const p = A.pieces + at;
+			p->lb = lb; p->rb = rb; p->row = row; p->n_founders = pc;
+		}
+		++npieces;
+	};
+
+	uint4 rf[MT_PREFETCH], rs[MT_PREFETCH];
+	auto prefetch = [&](uint64_t c0, uint32_t tc) {
+		uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
+		uint4 const *const fsrc = reinterpret_cast<uint4 const *>(A.fcols + c0 * Kp);
+#pragma unroll
+		for (uint32_t j = 0; j < MT_PREFETCH; ++j)
+		{
+			uint32_t const q = tid + j * MT_T;
+			rf[j] = q < nf ? fsrc[q] : make_uint4(0, 0, 0, 0);
+			uint32_t const col = q / cpc, ch = q - col * cpc;
+			size_t const at = slice + (size_t) ch * 16u;                 // (ld is a multiple of 16: a chunk is inside the column or beyond it)
+			rs[j] = (q < ns && at < A.ld) ? *reinterpret_cast<uint4 const *>(A.msa + (c0 + col) * A.ld + at) : make_uint4(0, 0, 0, 0);
+		}
+	};
+
+	prefetch(0, (uint32_t) mt_min(TC, n));
+	for (uint64_t c0 = 0; c0 < n; c0 += TC)
+	{
+		uint32_t const tc = (uint32_t) mt_min(TC, n - c0);
+		// the tile's codes into LDS, its sets cleared
+		{
+			uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
+#pragma unroll
+			for (uint32_t j = 0; j < MT_PREFETCH; ++j)
+			{
+				uint32_t const q = tid + j * MT_T;
+				if (q < nf) reinterpret_cast<uint4 *>(fst)[q] = rf[j];
+				if (q < ns) reinterpret_cast<uint4 *>(syms)[q] = rs[j];
+			}
+			for (uint32_t i = tid; i < tc * sigma * Wk; i += MT_T) sets[i] = 0u;
+		}
+		__syncthreads();
+		if (c0 + TC < n) prefetch(c0 + TC, (uint32_t) mt_min(TC, n - c0 - TC));
+		// set[column][code]: 64 founders of a column are the lanes of a wave; one ballot per code present among them
+		for (uint32_t it = wv; it < tc * groups; it += MT_T / 64u)
+		{
+			uint32_t const j = it / groups, g = it - j * groups, f = g * 64u + lane;
+			uint32_t const code = fst[j * Kp + f];
+			bool const todo = f < K && code < sigma;
+			unsigned long long rem = __ballot(todo);
+			while (rem)
+			{
+				uint32_t const s = (uint32_t) __shfl((int) code, (int) (__ffsll((long long) rem) - 1));
+				unsigned long long const b = __ballot(todo && code == s);
+				rem &= ~b;
+				uint32_t *const dst = sets + ((size_t) j * sigma + s) * Wk;
+				if (lane == 0 && 2u * g < Wk) dst[2u * g] = (uint32_t) b;
+				if (lane == 1 && 2u * g + 1u < Wk) dst[2u * g + 1u] = (uint32_t) (b >> 32);
+			}
+		}
+		__syncthreads();
+		if (active)
+			for (uint32_t j = 0; j < tc; ++j)
+			{
+				uint64_t const k = c0 + j;
+				uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
+				uint32_t const *const M = code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set;
+				// match_founder_sequences.cc:166-208.  The AND is made once: kept in registers where the set is (WR words), and
+				// for the sets in LDS written over the live set only when the piece goes on (a close prints the set as it was)
+				bool recheck = false;
+				uint32_t any = 0;
+				uint32_t nv[WR ? WR : 1];
+				if (min_len != 0 && min_len <= k - lb) recheck = true;
+				else
+				{
+					if (WR)
+					{
+						for (uint32_t i = 0; i < live.words(); ++i) { nv[i] = live.get(i) & M[i]; any |= nv[i]; }
+					}
+					else
+					{
+						// (only whether a founder is left: stops at the first word that keeps one)
+						for (uint32_t i = 0; i < live.words() && !any; ++i) any = live.get(i) & M[i];
+					}
+					if (!any) { if (min_len != 0) ++nshort; recheck = true; }
+				}
+				if (recheck)
+				{
+					emit(k);
+					lb = k;
+					any = 0;
+					for (uint32_t i = 0; i < live.words(); ++i) { uint32_t const v = M[i]; live.set(i, v); any |= v; }
+					if (!any) ++nunc;
+				}
+				else if (WR)
+				{
+					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, nv[i]);
+				}
+				else
+				{
+					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, live.get(i) & M[i]);
+				}
+				alive = any != 0;
+			}
+		__syncthreads();
+	}
+	if (active)
+	{
+		if (alive) emit(n);
+		if (!WRITE) { A.cnt[row] = npieces; A.cnt[A.m + row] = nunc; A.cnt[2u * (size_t) A.m + row] = nshort; }
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// exclusive scan of the rows' piece counts (off[0 .. m], off[m] = all pieces) and the summary's totals:
+// tot = {pieces, uncovered cells, short pieces, most pieces in a row}.  One workgroup; a thread sums a run of rows.
+// ------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(MT_SCAN_T) void k_match_scan(uint32_t const *__restrict__ cnt, uint32_t m, uint64_t *__restrict__ off, uint64_t *__restrict__ tot)
+{
+	__shared__ uint64_t s_p[MT_SCAN_T], s_u[MT_SCAN_T], s_s[MT_SCAN_T], s_x[MT_SCAN_T];
+	uint32_t const t = threadIdx.x, per = (m + MT_SCAN_T - 1u) / MT_SCAN_T;
+	uint32_t const lo = min(m, t * per), hi = min(m, lo + per);
+	uint64_t p = 0, u = 0, s = 0, x = 0;
+	for (uint32_t r = lo; r < hi; ++r)
+	{
+		uint32_t const v = cnt[r];
+		p += v; u += cnt[m + r]; s += cnt[2u * (size_t) m + r];
+		x = mt_max(x, v);
+	}
+	s_p[t] = p; s_u[t] = u; s_s[t] = s; s_x[t] = x;
+	__syncthreads();
+	if (t == 0)
+	{
+		uint64_t run = 0, su = 0, ss = 0, mx = 0;
+		for (uint32_t i = 0; i < MT_SCAN_T; ++i)
+		{
+			uint64_t const v = s_p[i];
+			s_p[i] = run; run += v;
+			su += s_u[i]; ss += s_s[i]; mx = mt_max(mx, s_x[i]);
+		}
+		off[m] = run;
+		tot[0] = run; tot[1] = su; tot[2] = ss; tot[3] = mx;
+	}
+	__syncthreads();
+	uint64_t run = s_p[t];
+	for (uint32_t r = lo; r < hi; ++r) { off[r] = run; run += cnt[r]; }
+}
+
+} // namespace fseq

@@ -38,6 +38,9 @@ char const *const USAGE =
 	"  -f, --input-format=FORMAT          Input file format  (possible values=\"FASTA\", \"list-file\" default=`list-file')\n"
 	"  -e, --output-segments=PATH         Output segment co-ordinates in text format\n"
 	"  -o, --output-founders=PATH         Founder file path\n"
+	"      --output-matches=PATH          Match the input against the founders on the device and write the report of\n"
+	"                                     match-sequences-to-founders (SEQUENCE_INDEX LB RB FOUNDER_INDICES; one GPU only)\n"
+	"      --match-min-segment-length=N   ... closing a piece as soon as it has N columns  (default=`0': only where no founder continues)\n"
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
@@ -91,6 +94,16 @@ bool read_fasta(char const *path, std::vector<std::string> &seqs)
 	return true;
 }
 
+// --output-matches: the report of the match the context holds, and a summary line
+bool report_match(fseq_ctx *ctx, int rc, fseq_match_summary const &sm, char const *path)
+{
+	if (FSEQ_OK == rc) rc = fseq_write_match(ctx, path);
+	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return false; }
+	std::cerr << "Matched the input against " << sm.n_founders << " founders: " << sm.pieces << " pieces, at most " << sm.max_pieces_per_row
+	          << " in a sequence, " << sm.uncovered_cells << " uncovered cells." << std::endl;
+	return true;
+}
+
 std::ostream *open_out(char const *path, std::ofstream &file)
 {
 	if (!path || ('-' == path[0] && '\0' == path[1])) return &std::cout;
@@ -103,7 +116,9 @@ std::ostream *open_out(char const *path, std::ofstream &file)
 
 int main(int argc, char **argv)
 {
-	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr;
+	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr;
+	unsigned long long match_min_len = 0;
+	bool match_min_len_bad = false;
 	input_format fmt = input_format::LIST_FILE;
 	joining join = joining::BIPARTITE_MATCHING;
 	long seg_len = 0, sample_rate = 4, seed = 0;
@@ -121,6 +136,7 @@ int main(int argc, char **argv)
 		{"pbwt-sample-rate", required_argument, nullptr, 'm'}, {"random-seed", required_argument, nullptr, 1000},
 		{"single-threaded", no_argument, nullptr, 1001}, {"print-invocation", no_argument, nullptr, 1002},
 		{"gpus", required_argument, nullptr, 1003}, {"list-memory", required_argument, nullptr, 1004},
+		{"output-matches", required_argument, nullptr, 1005}, {"match-min-segment-length", required_argument, nullptr, 1006},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -158,6 +174,15 @@ int main(int argc, char **argv)
 				list_memory_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || list_memory_mib > (~0ull >> 20);
 				break;
 			}
+			case 1005: out_matches = optarg; break;
+			case 1006:
+			{
+				char *end = nullptr;
+				errno = 0;
+				match_min_len = strtoull(optarg, &end, 10);
+				match_min_len_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE;
+				break;
+			}
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -182,6 +207,8 @@ int main(int argc, char **argv)
 	if (gpus < 1 || gpus > 64) { std::cerr << "The number of GPUs must be positive." << std::endl; return EXIT_FAILURE; }
 	if (list_memory_bad) { std::cerr << "The list memory must be a non-negative number of MiB." << std::endl; return EXIT_FAILURE; }
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
+	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
+	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 
 	// generate_context.cc:64-106
 	std::cerr << "Loading the input…" << std::flush;
@@ -290,6 +317,16 @@ int main(int argc, char **argv)
 			for (uint32_t i = 0; i < res.max_segment_size; ++i) ss << len[i] << '\n';
 			ss << std::flush;
 		}
+		if (out_matches)
+		{
+			// (no permutations on this path: the founders are the distinct rows just written)
+			std::cerr << "Matching the input against the founders…" << std::endl;
+			std::vector<uint8_t const *> frows(res.max_segment_size);
+			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = rows[first[i]];
+			fseq_match_summary sm{};
+			rc = fseq_match_founder_rows(ctx, frows.data(), res.max_segment_size, match_min_len, &sm);
+			if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
+		}
 		std::cerr << "Done." << std::endl;
 		fseq_destroy(ctx);
 		return EXIT_SUCCESS;
@@ -345,6 +382,13 @@ int main(int argc, char **argv)
 		rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
 		             : fseq_write_segments(ctx, rows.data(), how, out_segments);
 		if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	}
+	if (out_matches)
+	{
+		std::cerr << "Matching the input against the founders…" << std::endl;
+		fseq_match_summary sm{};
+		rc = fseq_match_founders(ctx, perm.data(), match_min_len, &sm);
+		if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
 	}
 	std::cerr << "Done." << std::endl;
 	for (fseq_ctx *c_ : ctxs) if (c_) fseq_destroy(c_);

@@ -277,6 +277,37 @@ int  fseq_write_founders(fseq_ctx *ctx, uint8_t const *const *rows, uint32_t con
  * device and leave in one copy per batch of rows; no host rows needed.  Not for sharded runs (a rank holds its own columns). */
 int  fseq_write_founders_device(fseq_ctx *ctx, uint32_t const *permutations, char const *path);
 
+/* ---- matching the input rows against founders on the device ----
+ * replaces: match-sequences-to-founders (match_founder_sequences.cc:108-259, match-sequences-to-founders/cmdline.ggo): every
+ * input row is threaded through the founders greedily -- keep the set of founders that still agree with the row; when it would
+ * run empty, or, with min_segment_length != 0, as soon as the running piece has that length, close the piece [lb, rb) with the
+ * set as it was and start again from all founders.  A cell whose symbol no founder has at its column (an uncovered cell) closes
+ * the running piece and gives a one-column piece with an empty set, except in the last column, where the tool prints none; a
+ * piece that a mismatch closes while it is shorter than min_segment_length is a short piece (the tool's "under the given
+ * limit" line).  The corners are the tool's (an uncovered cell in column 0 first closes the piece [0, 0) of all founders).
+ * The alignment the context holds (uploaded, generated or borrowed) is the input; at most 2,048 founders
+ * (FSEQ_E_UNSUPPORTED beyond, csrc/fseq_match.hpp); not for sharded contexts (a rank holds its own columns only).  Pieces are
+ * ordered by row, then lb; a founder set is set_words = ceil(K / 32) words, founder f at bit f % 32 of word f / 32.  Nothing
+ * of the segmentation's state is touched, and nothing is allocated before the first match. */
+typedef struct fseq_match_piece { uint64_t lb, rb; uint32_t row, n_founders; } fseq_match_piece;     /* 24 bytes */
+typedef struct fseq_match_summary {
+	uint64_t pieces, uncovered_cells, short_pieces, max_pieces_per_row;
+	uint32_t n_founders, set_words;          /* K, W */
+	double   ms_device;                      /* HIP event time of the founders' columns + both walks */
+} fseq_match_summary;
+/* founders = what fseq_write_founders_device would write for these permutations (a slot >= m is a line of '-'); needs a
+ * finished long-path run (FSEQ_E_ARG before one and on a short-path result, which has no permutations: its founders are the
+ * rows fseq_short_path_runs names, to be handed to fseq_match_founder_rows) */
+int  fseq_match_founders(fseq_ctx *ctx, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out);
+/* founders = K caller-supplied rows of n raw bytes (--founders with --founders-format text, cmdline.ggo); needs only the
+ * alignment (no run).  A byte outside the alignment's alphabet matches no row. */
+int  fseq_match_founder_rows(fseq_ctx *ctx, uint8_t const *const *founders, uint32_t K, uint64_t min_segment_length, fseq_match_summary *out);
+/* result of the last match on the context: `pieces` entries, pieces x set_words mask words (either may be NULL) */
+int  fseq_get_match(fseq_ctx *ctx, fseq_match_piece *pieces, uint32_t *founder_sets);
+/* the tool's stdout, byte for byte (header line, then SEQUENCE_INDEX LB RB FOUNDER_INDICES per piece,
+ * match_founder_sequences.cc:125-136, :220); path NULL or "-" = stdout */
+int  fseq_write_match(fseq_ctx *ctx, char const *path);
+
 int  fseq_get_timings(fseq_ctx const *ctx, fseq_timings *out);
 
 /* Host time of the last fseq_join_* call on this context (wall, milliseconds): the boundary states' way to the host,
