@@ -76,6 +76,10 @@ class MatchSummary(C.Structure):
                 ("n_founders", C.c_uint32), ("set_words", C.c_uint32), ("ms_device", C.c_double)]
 
 
+class IdentitySummary(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("identity", C.c_uint64), ("kept", C.c_uint64), ("ms_device", C.c_double)]
+
+
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
 
@@ -95,6 +99,7 @@ EXPORTS = [
     "fseq_shard_abort", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges",
     "fseq_set_list_memory", "fseq_debug_list_windows",
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
+    "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -186,6 +191,11 @@ def load_library():
     L.fseq_match_founder_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
     L.fseq_get_match.argtypes = [vp, vp, vp]
     L.fseq_write_match.argtypes = [vp, C.c_char_p]
+    L.fseq_identity_columns.argtypes = [vp, vp, C.POINTER(IdentitySummary)]
+    L.fseq_create_without_identity_columns.argtypes = [vp, C.POINTER(Params), C.POINTER(vp), C.POINTER(IdentitySummary)]
+    L.fseq_get_identity_columns.argtypes = [vp, vp, vp]
+    L.fseq_write_identity_columns.argtypes = [vp, C.c_char_p]
+    L.fseq_write_founders_restored.argtypes = [vp, vp, C.c_char_p]
     _lib = L
     return L
 
@@ -365,6 +375,7 @@ class SegmentationContext:
         if rc != FSEQ_OK:
             raise FseqError(rc, self.L.fseq_strerror(rc).decode())
         self.h = h
+        self._device = int(device)
         self.result = None
         self._keep = None
         if list_memory:
@@ -583,6 +594,53 @@ class SegmentationContext:
     def write_match(self, path):
         """The report of match-sequences-to-founders for the last match (SEQUENCE_INDEX LB RB FOUNDER_INDICES)."""
         self._check(self.L.fseq_write_match(self.h, path.encode() if path else None))
+
+    # ---- identity columns (remove-identity-columns / insert-identity-columns, on the device)
+    def identity_columns(self):
+        """(mask, summary): mask[k] is True iff all rows carry the same symbol in column k (fseq_identity_columns);
+        summary = {n, identity, kept, ms_device}.  Needs the alignment only, no run."""
+        mask = np.zeros(self.n, dtype=np.uint8)
+        sm = IdentitySummary()
+        self._check(self.L.fseq_identity_columns(self.h, mask.ctypes.data, C.byref(sm)))
+        return mask.astype(bool), {k: getattr(sm, k) for k, _ in IdentitySummary._fields_}
+
+    def without_identity_columns(self, segment_length, block_len=0, list_cap=0, list_memory=0):
+        """A new SegmentationContext over the columns that are not identity columns (fseq_create_without_identity_columns);
+        its results are in reduced co-ordinates (kept_columns() maps them back).  This context may be closed afterwards."""
+        p = Params(0, 0, int(segment_length), 0, int(block_len), int(list_cap), int(self._device))
+        h = C.c_void_p()
+        sm = IdentitySummary()
+        self._check(self.L.fseq_create_without_identity_columns(self.h, C.byref(p), C.byref(h), C.byref(sm)))
+        new = SegmentationContext.__new__(SegmentationContext)
+        new.L, new.h = self.L, h
+        new.m, new.n, new.segment_length, new._device = self.m, int(sm.kept), int(segment_length), self._device
+        new.result, new._keep = None, None
+        new.source_n = int(sm.n)
+        new.identity_summary = {k: getattr(sm, k) for k, _ in IdentitySummary._fields_}
+        if list_memory:
+            new.set_list_memory(list_memory)
+        return new
+
+    def identity_mask(self):
+        """On a context made by without_identity_columns(): the mask over the source's columns."""
+        mask = np.zeros(getattr(self, "source_n", 0), dtype=np.uint8)
+        self._check(self.L.fseq_get_identity_columns(self.h, mask.ctypes.data, None))
+        return mask.astype(bool)
+
+    def kept_columns(self):
+        """... the source column of every column of this context (ascending)."""
+        kept = np.zeros(self.n, dtype=np.uint64)
+        self._check(self.L.fseq_get_identity_columns(self.h, None, kept.ctypes.data))
+        return kept
+
+    def write_identity_columns(self, path):
+        """... the stdout of remove-identity-columns: '0' / '1' per source column, then a newline."""
+        self._check(self.L.fseq_write_identity_columns(self.h, path.encode() if path else None))
+
+    def write_founders_restored(self, permutations, path):
+        """... --output-founders with the identity columns put back from input row 0 (lines of the source's length)."""
+        perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+        self._check(self.L.fseq_write_founders_restored(self.h, perm.ctypes.data, path.encode() if path else None))
 
     # ---- debug / parity of intermediate state
     def debug_dp(self):

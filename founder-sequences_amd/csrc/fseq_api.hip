@@ -3036,6 +3036,7 @@ void fseq_destroy(fseq_ctx *c)
 	free_msa(c);
 	free_work(c);
 	c->free_match();
+	c->free_identity();
 	assert(c->alloc_sizes.empty() && c->alloc_total == 0);       // (a buffer free_work does not know of)
 	for (auto &e : c->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_part) if (e) (void) hipEventDestroy(e);

@@ -1,7 +1,7 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
 // shares: csrc/fseq_api.hip (the path: geometry, buffers, phases, sharding, the ABI's entry points) and
 // csrc/fseq_api_join.hip (the host joiners, their device front and the output writers) and csrc/fseq_api_match.hip (the rows
-// matched against founders).  Internal: nothing here is part of the boundary.
+// matched against founders) and csrc/fseq_api_identity.hip (identity columns dropped and put back).  Internal: nothing here is part of the boundary.
 #pragma once
 
 #include "../../include/fseq.h"
@@ -454,6 +454,21 @@ struct fseq_ctx {
 		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets);
 		for (auto &e : match.ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
 		match.have = false;
+	}
+
+	// a context over the kept columns of another (fseq_create_without_identity_columns, csrc/fseq_api_identity.hip): what it
+	// needs to put the identity columns back after its source is gone.  Empty on every other context
+	struct Identity {
+		bool have = false;
+		uint64_t n_src = 0, identity = 0;    // columns of the source, identity columns among them
+		DevBuf<uint8_t> mask;                // [n_src] 1 = identity column
+		DevBuf<uint32_t> kept;               // [n]: source column of this context's column j (ascending)
+		DevBuf<uint8_t> ref;                 // [n_src] row 0 of the source as raw bytes
+	} idn;
+	void free_identity()
+	{
+		fseq::release_all(this, idn.mask, idn.kept, idn.ref);
+		idn.have = false;
 	}
 };
 

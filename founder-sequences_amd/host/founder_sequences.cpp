@@ -41,6 +41,10 @@ char const *const USAGE =
 	"      --output-matches=PATH          Match the input against the founders on the device and write the report of\n"
 	"                                     match-sequences-to-founders (SEQUENCE_INDEX LB RB FOUNDER_INDICES; one GPU only)\n"
 	"      --match-min-segment-length=N   ... closing a piece as soon as it has N columns  (default=`0': only where no founder continues)\n"
+	"      --remove-identity-columns      Segment only the columns in which the sequences differ and put the others back into the\n"
+	"                                     founders from the first sequence (remove-identity-columns | founder_sequences |\n"
+	"                                     insert-identity-columns in one run; segments in reduced co-ordinates; one GPU only)\n"
+	"      --output-identity-columns=PATH ... and write the identity columns as a string of 0 / 1 (implies --remove-identity-columns)\n"
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
@@ -116,7 +120,8 @@ std::ostream *open_out(char const *path, std::ofstream &file)
 
 int main(int argc, char **argv)
 {
-	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr;
+	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr;
+	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
 	bool match_min_len_bad = false;
 	input_format fmt = input_format::LIST_FILE;
@@ -137,6 +142,7 @@ int main(int argc, char **argv)
 		{"single-threaded", no_argument, nullptr, 1001}, {"print-invocation", no_argument, nullptr, 1002},
 		{"gpus", required_argument, nullptr, 1003}, {"list-memory", required_argument, nullptr, 1004},
 		{"output-matches", required_argument, nullptr, 1005}, {"match-min-segment-length", required_argument, nullptr, 1006},
+		{"remove-identity-columns", no_argument, nullptr, 1007}, {"output-identity-columns", required_argument, nullptr, 1008},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -183,6 +189,8 @@ int main(int argc, char **argv)
 				match_min_len_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE;
 				break;
 			}
+			case 1007: remove_identity = true; break;
+			case 1008: out_identity = optarg; remove_identity = true; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -209,6 +217,8 @@ int main(int argc, char **argv)
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
 	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 
 	// generate_context.cc:64-106
 	std::cerr << "Loading the input…" << std::flush;
@@ -272,6 +282,20 @@ int main(int argc, char **argv)
 		else if (FSEQ_OK != rc_) return rc_;
 		if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(ctxs[r], (uint64_t) list_memory_mib << 20))) return rc_;
 		if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
+		if (remove_identity)
+		{
+			// the uploaded alignment is the source; the run goes on on a context over the columns in which the sequences differ
+			fseq_params pk(pr);
+			pk.m = 0; pk.n = 0;
+			fseq_ctx *kept(nullptr);
+			fseq_identity_summary is{};
+			if (FSEQ_OK != (rc_ = fseq_create_without_identity_columns(ctxs[r], &pk, &kept, &is))) return rc_;
+			fseq_destroy(ctxs[r]);
+			ctxs[r] = kept;
+			std::cerr << "Removed " << is.identity << " of " << is.n << " columns in which all sequences agree." << std::endl;
+			if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(kept, (uint64_t) list_memory_mib << 20))) return rc_;
+			if (out_identity && FSEQ_OK != (rc_ = fseq_write_identity_columns(kept, out_identity))) return rc_;
+		}
 		return fseq_run_segmentation(ctxs[r], &results[r]);
 	};
 	if (sharded)
@@ -371,7 +395,8 @@ int main(int argc, char **argv)
 	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	std::cerr << "Outputting the founders…" << std::endl;
 	// (not sharded: the lines are put together where the alignment already is, on the device; sharded: a rank holds its own columns)
-	rc = sharded ? fseq_write_founders(ctx, rows.data(), perm.data(), out_founders) : fseq_write_founders_device(ctx, perm.data(), out_founders);
+	rc = sharded ? fseq_write_founders(ctx, rows.data(), perm.data(), out_founders)
+	   : remove_identity ? fseq_write_founders_restored(ctx, perm.data(), out_founders) : fseq_write_founders_device(ctx, perm.data(), out_founders);
 	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	if (out_segments)
 	{
@@ -379,6 +404,19 @@ int main(int argc, char **argv)
 		// header is written (join_context.cc:57-61, greedy_matcher.cc:468-476)
 		std::cerr << "Outputting the segments…" << std::endl;
 		int const how = joining::GREEDY == join ? FSEQ_JOIN_GREEDY : (joining::RANDOM == join ? FSEQ_JOIN_RANDOM : FSEQ_JOIN_BIPARTITE);
+		if (remove_identity)
+		{
+			// the segments are in reduced co-ordinates: the rows without their identity columns, as the chain of tools has them
+			std::vector<uint8_t> mask(seq_length);
+			if (FSEQ_OK != (rc = fseq_get_identity_columns(ctx, mask.data(), nullptr))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+			for (auto &s_ : seqs)
+			{
+				size_t k(0);
+				for (size_t i = 0; i < seq_length; ++i) if (!mask[i]) s_[k++] = s_[i];
+				s_.resize(k);
+			}
+			for (size_t i = 0; i < seqs.size(); ++i) rows[i] = reinterpret_cast<uint8_t const *>(seqs[i].data());
+		}
 		rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
 		             : fseq_write_segments(ctx, rows.data(), how, out_segments);
 		if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }

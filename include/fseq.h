@@ -308,6 +308,47 @@ int  fseq_get_match(fseq_ctx *ctx, fseq_match_piece *pieces, uint32_t *founder_s
  * match_founder_sequences.cc:125-136, :220); path NULL or "-" = stdout */
 int  fseq_write_match(fseq_ctx *ctx, char const *path);
 
+/* ---- identity columns dropped and put back on the device ----
+ * replaces: remove-identity-columns (remove-identity-columns/main.cc:105-153 the comparison of a chunk of every text,
+ * :157-227 the driver that writes m reduced files and the 0 / 1 string) in front of founder_sequences, and
+ * insert-identity-columns (insert-identity-columns/main.cc:138-195) behind it.  An identity column is one in which all m
+ * rows carry the same symbol (m == 1: every column).  The alignment the context holds is the input; the entry points are
+ * detected by symbol (FSEQ_ABI_VERSION is unchanged: no struct of the boundary changed). */
+typedef struct fseq_identity_summary {
+	uint64_t n, identity, kept;     /* columns of the source, identity columns, n - identity */
+	double   ms_device;             /* HIP event time of the mask pass (+ scan and gather when a context was made) */
+} fseq_identity_summary;
+/* replaces: main.cc:105-153 over the whole alignment.  mask[k] = 1 iff column k is an identity column; mask (n bytes) may
+ * be NULL (the summary alone).  The source is any context with a resident alignment -- uploaded, generated, borrowed one code
+ * per byte or borrowed packed -- and needs no run.  Read-only on the context: nothing of the segmentation's state is touched,
+ * and what the call allocates it frees.  A sharded context returns FSEQ_E_UNSUPPORTED (a rank holds its own columns only). */
+int  fseq_identity_columns(fseq_ctx *ctx, uint8_t *mask /* n bytes */, fseq_identity_summary *out);
+/* replaces: main.cc:157-227 without the m reduced files: a new, ordinary context over the kept columns only.
+ * params->n must be 0 and params->m 0 or the source's (FSEQ_E_ARG otherwise): n becomes `kept`, m is the source's;
+ * segment_length, block_len, list_cap and pbwt_sample_rate are taken from params, and params->device must be the source's
+ * device.  The new context owns its alignment (columns padded to 16 bytes, padding zeroed) and keeps the source's sigma,
+ * code table and code width as they are: a symbol that occurred only in identity columns keeps its code, and since the order
+ * of the codes is unchanged every result (segments, traceback, boundary states, permutations) is what the reduced rows give
+ * when uploaded afresh.  Segments, traceback, boundary states and the segments file of the new context are in REDUCED
+ * co-ordinates, as in the reference's chain of tools; kept_columns[j] (fseq_get_identity_columns) maps reduced column j back.
+ * It also keeps the mask, the kept-column list and row 0 of the source as raw bytes on the device, so src may be destroyed
+ * right afterwards.  Every column an identity column: FSEQ_E_ARG ("every column is an identity column"), nothing is created;
+ * none: a plain copy.  A failed allocation returns FSEQ_E_OOM with the sizes (fseq_last_error(src)), leaves nothing behind
+ * and src usable.  fseq_get_matrix, fseq_run_segmentation, the joiners, fseq_write_segments (given the reduced rows),
+ * fseq_write_founders_device (reduced founders) and the matcher work on the new context unchanged.  summary may be NULL. */
+int  fseq_create_without_identity_columns(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary);
+/* On a context made by the call above (FSEQ_E_ARG on any other): the mask over the source's columns (source n bytes) and
+ * the source column of every column of this context (`kept` entries, ascending); either may be NULL. */
+int  fseq_get_identity_columns(fseq_ctx *ctx, uint8_t *mask, uint64_t *kept_columns);
+/* ... the stdout of remove-identity-columns (main.cc:139-146, :225): '0' / '1' per source column ('1' = identity), then
+ * '\n'.  path NULL or "-" = stdout. */
+int  fseq_write_identity_columns(fseq_ctx *ctx, char const *path);
+/* replaces: insert-identity-columns (main.cc:138-195) with --reference = input row 0, on what fseq_write_founders_device
+ * writes: max_segment_size lines of source-n bytes plus '\n'; at a kept column the founder's byte ('-' for a slot >= m), at
+ * an identity column row 0's byte.  Needs a finished long-path run (FSEQ_E_ARG before one and on a short-path result, whose
+ * founders are input rows).  path NULL or "-" = stdout. */
+int  fseq_write_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, char const *path);
+
 int  fseq_get_timings(fseq_ctx const *ctx, fseq_timings *out);
 
 /* Host time of the last fseq_join_* call on this context (wall, milliseconds): the boundary states' way to the host,
