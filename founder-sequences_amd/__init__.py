@@ -99,7 +99,7 @@ EXPORTS = [
     "fseq_shard_abort", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges",
     "fseq_set_list_memory", "fseq_debug_list_windows",
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
-    "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored",
+    "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -196,6 +196,7 @@ def load_library():
     L.fseq_get_identity_columns.argtypes = [vp, vp, vp]
     L.fseq_write_identity_columns.argtypes = [vp, C.c_char_p]
     L.fseq_write_founders_restored.argtypes = [vp, vp, C.c_char_p]
+    L.fseq_match_founders_restored.argtypes = [vp, vp, u64, C.POINTER(MatchSummary)]
     _lib = L
     return L
 
@@ -641,6 +642,16 @@ class SegmentationContext:
         """... --output-founders with the identity columns put back from input row 0 (lines of the source's length)."""
         perm = np.ascontiguousarray(permutations, dtype=np.uint32)
         self._check(self.L.fseq_write_founders_restored(self.h, perm.ctypes.data, path.encode() if path else None))
+
+    def match_founders_restored(self, permutations, min_segment_length=0):
+        """... the source's full-length rows matched against the founders write_founders_restored would write
+        (fseq_match_founders_restored): the summary dict of match_founders, pieces in the source's co-ordinates;
+        match_pieces() and write_match() then serve this result."""
+        perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+        sm = MatchSummary()
+        self._check(self.L.fseq_match_founders_restored(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
+        self._match = sm
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
 
     # ---- debug / parity of intermediate state
     def debug_dp(self):

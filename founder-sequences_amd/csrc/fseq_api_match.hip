@@ -26,17 +26,18 @@ int refuse_common(fseq_ctx *c, uint32_t K)
 	return FSEQ_OK;
 }
 
-template <bool WRITE>
-hipError_t launch_walk(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
+// A.kept set: the restored form of the walk (source positions, gap steps), a kernel of its own per variant
+template <bool WRITE, bool RST>
+hipError_t launch_walk_as(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
 {
 	void (*k)(MatchWalkArgs) = nullptr;
 	switch (s.WR)
 	{
-		case 1: k = k_match_walk<1, WRITE>; break;
-		case 2: k = k_match_walk<2, WRITE>; break;
-		case 4: k = k_match_walk<4, WRITE>; break;
-		case 8: k = k_match_walk<8, WRITE>; break;
-		default: k = k_match_walk<0, WRITE>; break;
+		case 1: k = k_match_walk<1, WRITE, RST>; break;
+		case 2: k = k_match_walk<2, WRITE, RST>; break;
+		case 4: k = k_match_walk<4, WRITE, RST>; break;
+		case 8: k = k_match_walk<8, WRITE, RST>; break;
+		default: k = k_match_walk<0, WRITE, RST>; break;
 	}
 	hipError_t const e = allow_lds(k, s.lds);
 	if (e != hipSuccess) return e;
@@ -44,10 +45,17 @@ hipError_t launch_walk(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
 	return hipGetLastError();
 }
 
+template <bool WRITE>
+hipError_t launch_walk(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
+{
+	return A.kept ? launch_walk_as<WRITE, true>(c, s, A) : launch_walk_as<WRITE, false>(c, s, A);
+}
+
 // both walks over the founders' columns in c->match.fcols; ev[0] has been recorded in front of the kernel that wrote them.
 // ms_device = ev[0] .. ev[1] (the founders' columns, the counting walk, the scan) + ev[2] .. ev[3] (the writing walk): the host's
-// wait for the totals and the allocation of the output between the two are not in it
-int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out)
+// wait for the totals and the allocation of the output between the two are not in it.
+// restored: the pieces in the source's co-ordinates, the identity columns of c->idn between the kept columns accounted for
+int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out, bool restored = false)
 {
 	auto &mt = c->match;
 	hipStream_t st = c->stream;
@@ -59,6 +67,7 @@ int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_sum
 	A.msa = c->d_msa; A.ld = c->ld; A.m = m; A.n = c->p.n; A.bsh = c->bsh; A.sigma = c->sigma;
 	A.fcols = mt.fcols; A.K = s.K; A.Kp = s.Kp; A.W = s.W; A.Wk = s.Wk; A.TC = s.TC; A.min_len = min_len;
 	A.cnt = mt.cnt; A.off = mt.off;
+	if (restored) { A.kept = c->idn.kept; A.n_src = c->idn.n_src; }
 	hipError_t e = launch_walk<false>(c, s, A);
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: counting walk", e);
 	hipLaunchKernelGGL(k_match_scan, dim3(1), dim3(MT_SCAN_T), 0, st, mt.cnt, m, mt.off, d_tot);
@@ -105,19 +114,16 @@ inline char *put_u64(char *p, uint64_t v)
 	return p;
 }
 
-} // namespace
-
-extern "C" {
-
-int fseq_match_founders(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out)
+// fseq_match_founders and, restored, fseq_match_founders_restored: the founders' columns from the permutations of the run
+int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out, bool restored)
 {
-	if (!c || !permutations || !out) return FSEQ_E_ARG;
 	if (c->sh.on) return refuse_common(c, 0);
 	if (!c->have_result || c->res.short_path) return fail(c, FSEQ_E_ARG, "match: permutations need a finished long-path run (short path: hand the rows of fseq_short_path_runs to fseq_match_founder_rows)");
 	size_t const X = c->res.max_segment_size, S = c->segments.size();
 	if (!X || !S) return fail(c, FSEQ_E_ARG, "match: no segments (segmentation failed or was not run)");
 	int rc = refuse_common(c, (uint32_t) X);
 	if (rc) return rc;
+	if (restored && c->idn.n_src >= 0xFFFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "match: the per-row counters are 32 bits wide (source n < 2^32 - 1)");
 	for (size_t i = 0; i < S; ++i)
 		if (c->segments[i].lb != (i ? c->segments[i - 1].rb : 0u) || (i + 1 == S && c->segments[i].rb != c->p.n))
 			return fail(c, FSEQ_E_ARG, "match: the merged segments do not tile the columns");
@@ -139,7 +145,26 @@ int fseq_match_founders(fseq_ctx *c, uint32_t const *permutations, uint64_t min_
 	hipLaunchKernelGGL(k_match_founders_cols, dim3((uint32_t) ((c->p.n + 63) / 64)), dim3(256), 0, st, c->d_msa, c->ld, c->p.m, (uint64_t) c->p.n, c->bsh,
 	                   d_perm, (uint32_t) X, d_rb, (uint32_t) S, gap, s.Kp, c->match.fcols);
 	HIP_TRY(c, hipGetLastError());
-	return run_match(c, s, min_segment_length, out);
+	return run_match(c, s, min_segment_length, out, restored);
+}
+
+} // namespace
+
+extern "C" {
+
+int fseq_match_founders(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out)
+{
+	if (!c || !permutations || !out) return FSEQ_E_ARG;
+	return match_permutations(c, permutations, min_segment_length, out, false);
+}
+
+// the founders' columns are the reduced context's (k_match_founders_cols, n_kept x Kp): the identity columns, in which every
+// restored founder carries row 0's byte as every row does, exist only as the gaps between the source positions in idn.kept
+int fseq_match_founders_restored(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out)
+{
+	if (!c || !permutations || !out) return FSEQ_E_ARG;
+	if (!c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
+	return match_permutations(c, permutations, min_segment_length, out, true);
 }
 
 int fseq_match_founder_rows(fseq_ctx *c, uint8_t const *const *founders, uint32_t K, uint64_t min_segment_length, fseq_match_summary *out)

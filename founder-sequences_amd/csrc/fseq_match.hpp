@@ -19,6 +19,16 @@
 //       in LDS, up to MT_MAX_FOUNDERS = 2,048 founders.
 //       The walk runs twice: WRITE = false counts the pieces, uncovered cells and short pieces of every row; after
 //       k_match_scan's exclusive scan over the rows WRITE = true stores the pieces and their sets where they belong.
+//   k_match_walk<WR, WRITE, true>   the restored form (fseq_match_founders_restored): the context holds the kept columns of a
+//       longer source (fseq_create_without_identity_columns), and the rows and founders matched are the source-length ones, in
+//       which every founder agrees with every row in every identity column.  The walk still visits the kept columns only.  It
+//       reads the source position of every column of the tile (idn.kept, 64 words in LDS, staged with the tile), carries lb in
+//       source co-ordinates, and runs a gap step before every kept column and once after the last one, for the identity
+//       columns [g_lo, g_hi) between two kept columns: an empty live set (the kept cell before was uncovered) closes
+//       [lb, g_lo) and starts again from all founders; with min_len != 0 the piece is closed every min_len source columns
+//       while lb + min_len < g_hi, the first time with the live set as it is, then with all founders.  The counting pass takes
+//       the number of these closes from one division; the writing pass loops over the pieces it stores.  An empty gap costs one
+//       uniform compare.  The plain form (RST = false) is a kernel of its own and compiles as before.
 //
 // The walk is sequential along the columns: with m rows only ceil(m / 64) waves are in flight, and the time is a chain over n
 // columns, not throughput (DESIGN.md section 7 prices the split of a row's columns over workgroups; it is not built).
@@ -157,14 +167,17 @@ struct MatchWalkArgs {
 	uint64_t const *off;                             // WRITE = true: first piece of every row
 	fseq_match_piece *pieces;
 	uint32_t *sets;
+	uint32_t const *kept;                            // RST: source position of every column, ascending; n_src source columns
+	uint64_t n_src;
 };
 
 // LDS: [TC x Kp founder codes][TC x (MT_T >> bsh) bytes of alignment columns][(TC x sigma + 1) sets of Wk words; the last one
-// stays empty][WR = 0: Wk x MT_T words of live sets]
-template <uint32_t WR, bool WRITE>
+// stays empty][WR = 0: Wk x MT_T words of live sets]; RST: the tile's source positions in 64 words of their own
+template <uint32_t WR, bool WRITE, bool RST = false>
 static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const A)
 {
 	extern __shared__ uint4 mt_smem[];
+	__shared__ uint32_t mt_pos[RST ? MT_TILE_MAX : 1];
 	uint32_t const tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 	uint32_t const bsh = A.bsh, bits = 8u >> bsh, cmask = (1u << bits) - 1u, smask = (1u << bsh) - 1u;
 	uint32_t const rowbytes = MT_T >> bsh, cpc = rowbytes / 16u;         // this workgroup's rows in a column: bytes, 16-byte chunks
@@ -182,11 +195,15 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 	for (uint32_t i = tid; i < Wk; i += MT_T) empty_set[i] = 0u;
 
 	MatchLive<WR> live(live_lds, Wk);
-	for (uint32_t i = 0; i < live.words(); ++i)
-		live.set(i, K >= 32u * (i + 1u) ? ~0u : (K > 32u * i ? (1u << (K - 32u * i)) - 1u : 0u));
+	auto all_founders = [&]() {
+		for (uint32_t i = 0; i < live.words(); ++i)
+			live.set(i, K >= 32u * (i + 1u) ? ~0u : (K > 32u * i ? (1u << (K - 32u * i)) - 1u : 0u));
+	};
+	all_founders();
 	uint64_t lb = 0;
 	uint32_t npieces = 0, nunc = 0, nshort = 0;
 	bool alive = true;
+	uint64_t src_next = 0;                                               // RST: the source column behind the last kept column walked
 	uint64_t const out0 = (WRITE && active) ? A.off[row] : 0;
 
 	auto emit = [&](uint64_t rb) {
@@ -206,8 +223,48 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 		++npieces;
 	};
 
+	// RST: the identity columns [g_lo, g_hi) in front of a kept column, or behind the last one.  Every founder agrees with the
+	// row there, so match_founder_sequences.cc:166-208 over these columns comes to: an empty set closes at g_lo (the tool's
+	// "under the given limit" line where it prints one: the cell before was uncovered, so no founder is left at g_lo either),
+	// and a piece of min_len columns closes wherever it is reached before g_hi
+	auto gap_step = [&](uint64_t g_lo, uint64_t g_hi) {
+		if (g_lo >= g_hi) return;
+		if (!alive)
+		{
+			if (min_len != 0 && g_lo - lb < min_len) ++nshort;
+			emit(g_lo);
+			lb = g_lo;
+			all_founders();
+			alive = true;
+		}
+		if (min_len != 0)
+		{
+			// closes at lb + i * min_len < g_hi, i = 1 ..: (g_hi - lb - 1) / min_len of them (lb < g_hi < 2^32)
+			uint32_t const room = (uint32_t) (g_hi - lb - 1u);
+			uint32_t const closes = min_len > room ? 0u : room / (uint32_t) min_len;
+			if (closes)
+			{
+				if (WRITE)
+				{
+					emit(lb + min_len);
+					lb += min_len;
+					all_founders();
+					for (uint32_t i = 1; i < closes; ++i) { emit(lb + min_len); lb += min_len; }
+				}
+				else
+				{
+					npieces += closes;
+					lb += (uint64_t) closes * min_len;
+					all_founders();
+				}
+			}
+		}
+	};
+
 	uint4 rf[MT_PREFETCH], rs[MT_PREFETCH];
+	uint32_t rp = 0;
 	auto prefetch = [&](uint64_t c0, uint32_t tc) {
+		if (RST) rp = tid < tc ? A.kept[c0 + tid] : 0u;
 		uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
 		uint4 const *const fsrc = reinterpret_cast<uint4 const *>(A.fcols + c0 * Kp);
 #pragma unroll
@@ -235,6 +292,7 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 				if (q < nf) reinterpret_cast<uint4 *>(fst)[q] = rf[j];
 				if (q < ns) reinterpret_cast<uint4 *>(syms)[q] = rs[j];
 			}
+			if (RST && tid < MT_TILE_MAX) mt_pos[tid] = rp;
 			for (uint32_t i = tid; i < tc * sigma * Wk; i += MT_T) sets[i] = 0u;
 		}
 		__syncthreads();
@@ -260,7 +318,8 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 		if (active)
 			for (uint32_t j = 0; j < tc; ++j)
 			{
-				uint64_t const k = c0 + j;
+				uint64_t const k = RST ? (uint64_t) mt_pos[j] : c0 + j;
+				if (RST) { gap_step(src_next, k); src_next = k + 1u; }
 				uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
 				uint32_t const *const M = code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set;
 				// match_founder_sequences.cc:166-208.  The AND is made once: kept in registers where the set is (WR words), and
@@ -304,7 +363,8 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 	}
 	if (active)
 	{
-		if (alive) emit(n);
+		if (RST) gap_step(src_next, A.n_src);
+		if (alive) emit(RST ? A.n_src : n);
 		if (!WRITE) { A.cnt[row] = npieces; A.cnt[A.m + row] = nunc; A.cnt[2u * (size_t) A.m + row] = nshort; }
 	}
 }

@@ -45,6 +45,9 @@ char const *const USAGE =
 	"                                     founders from the first sequence (remove-identity-columns | founder_sequences |\n"
 	"                                     insert-identity-columns in one run; segments in reduced co-ordinates; one GPU only)\n"
 	"      --output-identity-columns=PATH ... and write the identity columns as a string of 0 / 1 (implies --remove-identity-columns)\n"
+	"      --output-restored-matches=PATH ... and match the full-length input against the restored founders on the device: the report\n"
+	"                                     of match-sequences-to-founders on the output of insert-identity-columns (requires\n"
+	"                                     --remove-identity-columns; honours --match-min-segment-length)\n"
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
@@ -98,7 +101,7 @@ bool read_fasta(char const *path, std::vector<std::string> &seqs)
 	return true;
 }
 
-// --output-matches: the report of the match the context holds, and a summary line
+// --output-matches, --output-restored-matches: the report of the match the context holds, and a summary line
 bool report_match(fseq_ctx *ctx, int rc, fseq_match_summary const &sm, char const *path)
 {
 	if (FSEQ_OK == rc) rc = fseq_write_match(ctx, path);
@@ -120,7 +123,7 @@ std::ostream *open_out(char const *path, std::ofstream &file)
 
 int main(int argc, char **argv)
 {
-	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr;
+	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
 	bool match_min_len_bad = false;
@@ -143,6 +146,7 @@ int main(int argc, char **argv)
 		{"gpus", required_argument, nullptr, 1003}, {"list-memory", required_argument, nullptr, 1004},
 		{"output-matches", required_argument, nullptr, 1005}, {"match-min-segment-length", required_argument, nullptr, 1006},
 		{"remove-identity-columns", no_argument, nullptr, 1007}, {"output-identity-columns", required_argument, nullptr, 1008},
+		{"output-restored-matches", required_argument, nullptr, 1009},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -191,6 +195,7 @@ int main(int argc, char **argv)
 			}
 			case 1007: remove_identity = true; break;
 			case 1008: out_identity = optarg; remove_identity = true; break;
+			case 1009: out_restored_matches = optarg; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -218,6 +223,7 @@ int main(int argc, char **argv)
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
 	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 
 	// generate_context.cc:64-106
@@ -351,6 +357,11 @@ int main(int argc, char **argv)
 			rc = fseq_match_founder_rows(ctx, frows.data(), res.max_segment_size, match_min_len, &sm);
 			if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
 		}
+		if (out_restored_matches)
+		{
+			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		std::cerr << "Done." << std::endl;
 		fseq_destroy(ctx);
 		return EXIT_SUCCESS;
@@ -427,6 +438,14 @@ int main(int argc, char **argv)
 		fseq_match_summary sm{};
 		rc = fseq_match_founders(ctx, perm.data(), match_min_len, &sm);
 		if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
+	}
+	if (out_restored_matches)
+	{
+		// the last step of the chain: the full-length input against the founders just written, in the source's co-ordinates
+		std::cerr << "Matching the input against the restored founders…" << std::endl;
+		fseq_match_summary sm{};
+		rc = fseq_match_founders_restored(ctx, perm.data(), match_min_len, &sm);
+		if (!report_match(ctx, rc, sm, out_restored_matches)) return EXIT_FAILURE;
 	}
 	std::cerr << "Done." << std::endl;
 	for (fseq_ctx *c_ : ctxs) if (c_) fseq_destroy(c_);

@@ -348,6 +348,21 @@ int  fseq_write_identity_columns(fseq_ctx *ctx, char const *path);
  * an identity column row 0's byte.  Needs a finished long-path run (FSEQ_E_ARG before one and on a short-path result, whose
  * founders are input rows).  path NULL or "-" = stdout. */
 int  fseq_write_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, char const *path);
+/* replaces: match-sequences-to-founders (match_founder_sequences.cc:108-259) as the last step of the reference's chain
+ * remove-identity-columns | founder_sequences | insert-identity-columns | match-sequences-to-founders: the FULL-LENGTH input
+ * rows matched against the FULL-LENGTH founders, on a context made by fseq_create_without_identity_columns (FSEQ_E_ARG on any
+ * other) after a long-path run.  The founders are what fseq_write_founders_restored writes for these permutations; the rows
+ * are the source's, that is the context's rows with row 0's byte in every identity column.  Neither is built: every founder
+ * agrees with every row in every identity column, so the walk of fseq_match_founders visits the kept columns only, at their
+ * source positions, and accounts for the identity columns between two of them in a closed form (csrc/fseq_match.hpp; DESIGN.md
+ * section 7).  Pieces, founder sets, uncovered cells, short pieces and the most pieces in a row are the tool's on those rows
+ * and founders, lb and rb in SOURCE co-ordinates: an uncovered cell in the last kept column gives its one-column piece when an
+ * identity column follows, and with min_segment_length != 0 a piece closes once it has that many source columns, inside a run
+ * of identity columns too.  Refusals as fseq_match_founders (before a run, short-path result, segments that do not tile the
+ * columns: FSEQ_E_ARG; more than 2,048 founders, a source of 2^32 - 1 columns or more: FSEQ_E_UNSUPPORTED).  The result
+ * replaces the context's last match: fseq_get_match and fseq_write_match serve it unchanged.  Detected by symbol, as the
+ * entry points above. */
+int  fseq_match_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out);
 
 int  fseq_get_timings(fseq_ctx const *ctx, fseq_timings *out);
 
