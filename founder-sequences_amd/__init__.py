@@ -100,10 +100,11 @@ EXPORTS = [
     "fseq_set_list_memory", "fseq_debug_list_windows",
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
+    "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
-                 "fseq_debug_list_windows"]
+                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns"]
 
 FSEQ_E_PEER = 6
 STAGE_TRACEBACK, STAGE_MERGE, STAGE_SAMPLES = 0, 1, 2
@@ -197,6 +198,15 @@ def load_library():
     L.fseq_write_identity_columns.argtypes = [vp, C.c_char_p]
     L.fseq_write_founders_restored.argtypes = [vp, vp, C.c_char_p]
     L.fseq_match_founders_restored.argtypes = [vp, vp, u64, C.POINTER(MatchSummary)]
+    L.fseq_input_begin.argtypes = [vp, vp, C.c_uint32, u64]
+    L.fseq_input_chunk_columns.restype = u64
+    L.fseq_input_chunk_columns.argtypes = [vp]
+    L.fseq_input_scan.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.fseq_input_columns.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.fseq_input_end.argtypes = [vp]
+    L.fseq_set_rows_streamed.argtypes = [vp, C.POINTER(vp), u64]
+    L.fseq_debug_device_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.c_int]
+    L.fseq_debug_packed_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -462,10 +472,68 @@ class SegmentationContext:
         return r.value
 
     # ---- input (delegate->sequences(), delegate->alphabet())
-    def set_sequences(self, msa):
-        """msa: uint8 array [m, n] of raw symbol bytes, any memory order."""
+    def set_sequences(self, msa, staging_bytes=None):
+        """msa: uint8 array [m, n] of raw symbol bytes, any memory order.  staging_bytes: None stages the whole alignment on the
+        device (fseq_set_matrix); a number sends it in column chunks through that much device staging (fseq_set_rows_streamed,
+        0 = 256 MiB), with the same results."""
         assert msa.dtype == np.uint8 and msa.shape == (self.m, self.n)
-        self._check(self.L.fseq_set_matrix(self.h, msa.ctypes.data, msa.strides[0], msa.strides[1]))
+        if staging_bytes is None:
+            self._check(self.L.fseq_set_matrix(self.h, msa.ctypes.data, msa.strides[0], msa.strides[1]))
+            return
+        if msa.strides[1] != 1:
+            msa = np.ascontiguousarray(msa)
+        rows = self._row_pointers(msa)
+        self._check(self.L.fseq_set_rows_streamed(self.h, rows, int(staging_bytes)))
+
+    # ---- the input in column chunks of bounded device memory (fseq_input_begin .. fseq_input_end)
+    def _row_pointers(self, chunk):
+        return (C.c_void_p * self.m)(*[chunk.ctypes.data + r * chunk.strides[0] for r in range(self.m)])
+
+    def _chunk(self, chunk):
+        chunk = np.asarray(chunk)
+        assert chunk.dtype == np.uint8 and chunk.ndim == 2 and chunk.shape[0] == self.m
+        return chunk if chunk.strides[1] == 1 or chunk.shape[1] <= 1 else np.ascontiguousarray(chunk)
+
+    def input_begin(self, alphabet=None, staging_bytes=0):
+        """Starts a chunked input.  alphabet: the byte values that may occur (bytes or an array; None: collect it with
+        input_scan).  staging_bytes: device memory of the two staging halves together (0 = 256 MiB)."""
+        if alphabet is None:
+            self._check(self.L.fseq_input_begin(self.h, None, 0, int(staging_bytes)))
+            return
+        alpha = np.ascontiguousarray(np.frombuffer(bytes(alphabet), dtype=np.uint8) if isinstance(alphabet, (bytes, bytearray)) else np.asarray(alphabet, dtype=np.uint8))
+        self._check(self.L.fseq_input_begin(self.h, alpha.ctypes.data, len(alpha), int(staging_bytes)))
+
+    def input_chunk_columns(self):
+        """The most columns one input_scan / input_columns call may carry (0 before input_begin)."""
+        return int(self.L.fseq_input_chunk_columns(self.h))
+
+    def input_scan(self, c0, chunk):
+        """chunk: uint8 [m, w], the columns [c0, c0 + w) of every row; the chunk may be reused when the call returns."""
+        chunk = self._chunk(chunk)
+        self._check(self.L.fseq_input_scan(self.h, int(c0), chunk.shape[1], self._row_pointers(chunk)))
+
+    def input_columns(self, c0, chunk):
+        chunk = self._chunk(chunk)
+        self._check(self.L.fseq_input_columns(self.h, int(c0), chunk.shape[1], self._row_pointers(chunk)))
+
+    def input_end(self):
+        self._check(self.L.fseq_input_end(self.h))
+
+    def packed_columns(self, c0=0, c1=None):
+        """(bytes [c1 - c0, ld], bits): the columns of the resident alignment as they are stored, padding included."""
+        c1 = self.n if c1 is None else c1
+        ld, bits = C.c_uint64(), C.c_uint32()
+        self._check(self.L.fseq_debug_packed_columns(self.h, c0, c1, None, C.byref(ld), C.byref(bits)))
+        out = np.zeros((c1 - c0, ld.value), dtype=np.uint8)
+        self._check(self.L.fseq_debug_packed_columns(self.h, c0, c1, out.ctypes.data, C.byref(ld), C.byref(bits)))
+        return out, bits.value
+
+    def device_bytes(self, reset_peak=False):
+        """(now, peak): device bytes this context's buffers hold and the most they have held (since the last reset_peak).
+        Accounting of the context's own allocations, not a measurement of the device."""
+        now, peak = C.c_uint64(), C.c_uint64()
+        self._check(self.L.fseq_debug_device_bytes(self.h, C.byref(now), C.byref(peak), 1 if reset_peak else 0))
+        return now.value, peak.value
 
     def set_device_columns(self, ptr, ld, sigma, keepalive=None):
         self._keep = keepalive

@@ -4,8 +4,8 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# translation units of the library: the path (kernels, geometry, phases, sharding, ABI), the joiners / writers, the matcher and the identity columns
-SRCS = [os.path.join(HERE, "csrc", "fseq_api.hip"), os.path.join(HERE, "csrc", "fseq_api_join.hip"), os.path.join(HERE, "csrc", "fseq_api_match.hip"), os.path.join(HERE, "csrc", "fseq_api_identity.hip"), os.path.join(HERE, "csrc", "fseq_reduced.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets_stream.hip")]
+# translation units of the library: the path (kernels, geometry, phases, sharding, ABI), the joiners / writers, the matcher, the identity columns and the chunked input
+SRCS = [os.path.join(HERE, "csrc", "fseq_api.hip"), os.path.join(HERE, "csrc", "fseq_api_join.hip"), os.path.join(HERE, "csrc", "fseq_api_match.hip"), os.path.join(HERE, "csrc", "fseq_api_identity.hip"), os.path.join(HERE, "csrc", "fseq_api_input.hip"), os.path.join(HERE, "csrc", "fseq_reduced.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets_stream.hip")]
 SRC = SRCS[0]
 import glob
 DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*"))) + [os.path.join(os.path.dirname(HERE), "include", "fseq.h"),

@@ -102,6 +102,7 @@ void free_msa(fseq_ctx *c)
 	c->d_msa_own.release(c);
 	c->d_msa = nullptr;
 	c->have_input = false;
+	if (c->in.open) c->free_input();         // (a chunked input under way ends where another input takes its place)
 }
 
 // columns this context holds: all of them, or the rank's share of a sharded run
@@ -2983,6 +2984,23 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 
 } // namespace
 
+// the chunked input (csrc/fseq_api_input.hip): the alignment, the work buffers and the result of the last input go before the
+// staging is allocated; what a run remembers of an input is forgotten as in every other upload
+void fseq::forget_input_history(fseq_ctx *c)
+{
+	c->have_result = false;
+	c->kernels_ready = false;
+	c->X_hint = 0;
+	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
+}
+
+void fseq::discard_input(fseq_ctx *c)
+{
+	free_msa(c);
+	free_work(c);
+	forget_input_history(c);
+}
+
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -3037,6 +3055,7 @@ void fseq_destroy(fseq_ctx *c)
 	free_work(c);
 	c->free_match();
 	c->free_identity();
+	c->free_input();
 	assert(c->alloc_sizes.empty() && c->alloc_total == 0);       // (a buffer free_work does not know of)
 	for (auto &e : c->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : c->ev_part) if (e) (void) hipEventDestroy(e);
@@ -3665,6 +3684,15 @@ int fseq_debug_rmq(int device, uint32_t const *keys, uint32_t count, uint32_t co
 	} while (false);
 	A_free();
 	return rc;
+}
+
+int fseq_debug_device_bytes(fseq_ctx *c, uint64_t *now, uint64_t *peak, int reset_peak)
+{
+	if (!c || !now || !peak) return FSEQ_E_ARG;
+	*now = c->alloc_total;
+	*peak = c->alloc_peak;
+	if (reset_peak) c->alloc_peak = c->alloc_total;
+	return FSEQ_OK;
 }
 
 int fseq_get_timings(fseq_ctx const *c, fseq_timings *out)

@@ -1,7 +1,8 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
 // shares: csrc/fseq_api.hip (the path: geometry, buffers, phases, sharding, the ABI's entry points) and
 // csrc/fseq_api_join.hip (the host joiners, their device front and the output writers) and csrc/fseq_api_match.hip (the rows
-// matched against founders) and csrc/fseq_api_identity.hip (identity columns dropped and put back).  Internal: nothing here is part of the boundary.
+// matched against founders) and csrc/fseq_api_identity.hip (identity columns dropped and put back) and
+// csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
 #pragma once
 
 #include "../../include/fseq.h"
@@ -274,6 +275,7 @@ struct fseq_ctx {
 	template <typename T> using DevBuf = fseq::DevBuf<T>;
 	std::unordered_map<void *, size_t> alloc_sizes;   // device allocations of this context (DevBuf)
 	size_t alloc_total = 0;
+	size_t alloc_peak = 0;                    // the most alloc_total has been (fseq_debug_device_bytes)
 	uint64_t mem_budget = 0;                  // fseq_set_memory_budget: 0 = whatever is free on the device
 	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_api.hip, plan_list_windows).  The buffer
 	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent is rebased to (lo_w B - H) stride.
@@ -470,6 +472,28 @@ struct fseq_ctx {
 		fseq::release_all(this, idn.mask, idn.kept, idn.ref);
 		idn.have = false;
 	}
+
+	// the input in column chunks (fseq_input_begin .. fseq_input_end, csrc/fseq_api_input.hip): alive between begin and end only
+	struct Input {
+		bool open = false;
+		bool given = false;                  // the alphabet came with begin (no scans)
+		bool table_ready = false;            // the first fseq_input_columns has fixed the code table and allocated the alignment
+		uint64_t half_bytes = 0, chunk_cols = 0;
+		uint64_t scanned = 0, encoded = 0;   // columns [0, scanned) have been scanned, [0, encoded) encoded
+		uint64_t calls = 0;                  // chunks so far: chunk i goes through half i & 1
+		uint32_t present[8]{};               // the alphabet: supplied, or what the scans have found
+		DevBuf<uint8_t> stage;               // the two halves
+		DevBuf<uint32_t> words;              // [0, 8): bytes the scans found; [8, 16): bytes outside the alphabet the encode met
+		DevBuf<uint8_t> table;               // [256] code of a byte (0xFF: not in the alphabet, where sigma < 256)
+		hipEvent_t copied[2]{}, used[2]{};   // per half: its copies are done; the kernel that read it is done
+	} in;
+	void free_input()
+	{
+		fseq::release_all(this, in.stage, in.words, in.table);
+		for (auto &e : in.copied) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+		for (auto &e : in.used) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+		in.open = false;
+	}
 };
 
 
@@ -493,6 +517,11 @@ inline void progress(fseq_ctx *c, int stage, uint64_t current, uint64_t max)
 	c->current_step.store(current, std::memory_order_relaxed);
 	if (c->progress_fn) c->progress_fn(c->progress_user, stage, current, max);
 }
+
+// csrc/fseq_api.hip: the alignment, the work buffers and the result a context holds are dropped (the chunked input's begin);
+// what runs remember of the last input is forgotten (every upload)
+void discard_input(fseq_ctx *c);
+void forget_input_history(fseq_ctx *c);
 
 #define HIP_TRY(c, expr)                                                   \
 	do {                                                                   \
@@ -532,6 +561,7 @@ int DevBuf<T>::alloc(fseq_ctx *c, size_t count)
 	cap = count;
 	c->alloc_sizes[static_cast<void *>(base)] = bytes;
 	c->alloc_total += bytes;
+	c->alloc_peak = std::max(c->alloc_peak, c->alloc_total);
 	return FSEQ_OK;
 }
 

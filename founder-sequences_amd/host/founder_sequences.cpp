@@ -9,7 +9,10 @@
 #include <fseq.h>
 #include "fseq_shard_rccl.hpp"
 
+#include <fcntl.h>
 #include <getopt.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <cctype>
 #include <cerrno>
@@ -58,7 +61,10 @@ char const *const USAGE =
 	"      --print-invocation             Print the command line arguments to stderr  (default=off)\n"
 	"      --gpus=N                       Shard the alignment over the first N GPUs of this node (RCCL)  (default=`1')\n"
 	"      --list-memory=MIB              Hold the per-column divergence lists in column windows of at most MIB MiB of device memory\n"
-	"                                     (one GPU only; results are the same)  (default=`0': every list held)\n";
+	"                                     (one GPU only; results are the same)  (default=`0': every list held)\n"
+	"      --upload-memory=MIB            Read the sequence files of a list-file input in column chunks through at most MIB MiB of host\n"
+	"                                     memory and as much device staging instead of loading them whole (list-file only; one GPU\n"
+	"                                     only; results are the same; --output-segments then needs greedy joining)\n";
 
 bool read_file(std::string const &path, std::string &out)
 {
@@ -82,6 +88,67 @@ bool read_list_file(char const *path, std::vector<std::string> &seqs)
 		seqs.emplace_back(std::move(content));
 	}
 	return true;
+}
+
+// --upload-memory: the paths only; a file's length is its size (read_file takes a file's bytes as the sequence)
+bool read_list_paths(char const *path, std::vector<std::string> &paths, std::vector<size_t> &lengths)
+{
+	std::ifstream f(path);
+	if (!f) { std::cerr << "Unable to open the input file '" << path << "'." << std::endl; return false; }
+	std::string line;
+	while (std::getline(f, line))
+	{
+		if (line.empty()) continue;
+		struct stat st;
+		if (0 != stat(line.c_str(), &st) || !S_ISREG(st.st_mode)) { std::cerr << "Unable to open the sequence file '" << line << "'." << std::endl; return false; }
+		paths.emplace_back(line);
+		lengths.push_back((size_t) st.st_size);
+	}
+	return true;
+}
+
+// ... and the columns [c0, c0 + w) of every file into buf (row r at buf + r * w); one descriptor at a time
+bool read_chunk(std::vector<std::string> const &paths, uint64_t c0, size_t w, uint8_t *buf, std::string &err)
+{
+	for (size_t r = 0; r < paths.size(); ++r)
+	{
+		int const fd(open(paths[r].c_str(), O_RDONLY));
+		if (fd < 0) { err = "Unable to open the sequence file '" + paths[r] + "'."; return false; }
+		size_t got(0);
+		while (got < w)
+		{
+			ssize_t const k(pread(fd, buf + r * w + got, w - got, (off_t) (c0 + got)));
+			if (k < 0 && EINTR == errno) continue;
+			if (k <= 0) break;
+			got += (size_t) k;
+		}
+		close(fd);
+		if (got < w) { err = "Unable to read the sequence file '" + paths[r] + "' (it is shorter than when it was measured)."; return false; }
+	}
+	return true;
+}
+
+// the scan pass, then the encode pass, chunk after chunk through one host buffer of at most `bytes` and as much device staging
+int upload_in_chunks(fseq_ctx *ctx, std::vector<std::string> const &paths, uint64_t n, uint64_t bytes, std::string &io_err)
+{
+	int rc(fseq_input_begin(ctx, nullptr, 0, bytes));
+	if (FSEQ_OK != rc) return rc;
+	size_t const m(paths.size());
+	uint64_t width(fseq_input_chunk_columns(ctx));                // (two halves of bytes / 2: m x width is at most half the host's share)
+	if ((width & ~63ull) >= 64) width &= ~63ull;
+	if (width > n) width = n;
+	std::vector<uint8_t> buf(m * (size_t) width);
+	std::vector<uint8_t const *> at(m);
+	for (int pass = 0; pass < 2; ++pass)
+		for (uint64_t c0 = 0; c0 < n; c0 += width)
+		{
+			size_t const w((size_t) (n - c0 < width ? n - c0 : width));
+			if (!read_chunk(paths, c0, w, buf.data(), io_err)) return FSEQ_E_ARG;
+			for (size_t r = 0; r < m; ++r) at[r] = buf.data() + r * w;
+			rc = pass ? fseq_input_columns(ctx, c0, w, at.data()) : fseq_input_scan(ctx, c0, w, at.data());
+			if (FSEQ_OK != rc) return rc;
+		}
+	return fseq_input_end(ctx);
 }
 
 // FASTA: '>' header lines, sequence lines concatenated (README.md:80)
@@ -135,6 +202,8 @@ int main(int argc, char **argv)
 	bool gpus_given = false;
 	unsigned long long list_memory_mib = 0;
 	bool list_memory_bad = false;
+	unsigned long long upload_mib = 0;
+	bool upload_given = false, upload_bad = false;
 
 	static option const longopts[] = {
 		{"help", no_argument, nullptr, 'h'}, {"version", no_argument, nullptr, 'V'},
@@ -146,7 +215,7 @@ int main(int argc, char **argv)
 		{"gpus", required_argument, nullptr, 1003}, {"list-memory", required_argument, nullptr, 1004},
 		{"output-matches", required_argument, nullptr, 1005}, {"match-min-segment-length", required_argument, nullptr, 1006},
 		{"remove-identity-columns", no_argument, nullptr, 1007}, {"output-identity-columns", required_argument, nullptr, 1008},
-		{"output-restored-matches", required_argument, nullptr, 1009},
+		{"output-restored-matches", required_argument, nullptr, 1009}, {"upload-memory", required_argument, nullptr, 1010},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -196,6 +265,16 @@ int main(int argc, char **argv)
 			case 1007: remove_identity = true; break;
 			case 1008: out_identity = optarg; remove_identity = true; break;
 			case 1009: out_restored_matches = optarg; break;
+			case 1010:
+			{
+				// as --list-memory, but a positive number: 0 MiB hold no chunk
+				char *end = nullptr;
+				errno = 0;
+				upload_mib = strtoull(optarg, &end, 10);
+				upload_given = true;
+				upload_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || 0 == upload_mib || upload_mib > (~0ull >> 20);
+				break;
+			}
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -226,21 +305,36 @@ int main(int argc, char **argv)
 	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 
+	if (upload_bad) { std::cerr << "The upload memory must be a positive number of MiB." << std::endl; return EXIT_FAILURE; }
+	if (upload_given && input_format::FASTA == fmt) { std::cerr << "--upload-memory is not supported together with --input-format=FASTA (a FASTA file holds the sequences one after another, so a column chunk is not a range of its bytes; use list-file input)." << std::endl; return EXIT_FAILURE; }
+	if (upload_given && gpus > 1) { std::cerr << "--upload-memory is not supported together with --gpus > 1 (the chunked input does not exchange the ranks' alphabets)." << std::endl; return EXIT_FAILURE; }
+	if (upload_given && out_segments && joining::GREEDY != join) { std::cerr << "--upload-memory is not supported together with --output-segments under bipartite-matching or random joining (the segment texts need the raw rows on the host; greedy joining writes the header only)." << std::endl; return EXIT_FAILURE; }
+
 	// generate_context.cc:64-106
 	std::cerr << "Loading the input…" << std::flush;
-	std::vector<std::string> seqs;
-	if (!(input_format::FASTA == fmt ? read_fasta(input, seqs) : read_list_file(input, seqs))) return EXIT_FAILURE;
-	if (seqs.empty()) { std::cerr << "\nThe input file contained no sequences." << std::endl; return EXIT_SUCCESS; }
-	size_t const seq_length = seqs.front().size();
+	std::vector<std::string> seqs, paths;
+	std::vector<size_t> lengths;
+	if (upload_given)
+	{
+		// the files stay where they are: their sizes now, their bytes chunk by chunk when the context exists
+		if (!read_list_paths(input, paths, lengths)) return EXIT_FAILURE;
+	}
+	else
+	{
+		if (!(input_format::FASTA == fmt ? read_fasta(input, seqs) : read_list_file(input, seqs))) return EXIT_FAILURE;
+		for (auto const &s_ : seqs) lengths.push_back(s_.size());
+	}
+	if (lengths.empty()) { std::cerr << "\nThe input file contained no sequences." << std::endl; return EXIT_SUCCESS; }
+	size_t const seq_length = lengths.front();
 	std::cerr << " length: " << seq_length << std::endl;
 	std::cerr << "Checking the input…" << std::endl;
 	{
 		bool stop = false;
-		for (size_t i = 1; i < seqs.size(); ++i)
-			if (seqs[i].size() != seq_length)
+		for (size_t i = 1; i < lengths.size(); ++i)
+			if (lengths[i] != seq_length)
 			{
 				stop = true;
-				std::cerr << "The length of the sequence at index " << i << " was " << seqs[i].size()
+				std::cerr << "The length of the sequence at index " << i << " was " << lengths[i]
 				          << " while that of the first one was " << seq_length << '.' << std::endl;
 			}
 		if (stop) return EXIT_FAILURE;
@@ -248,11 +342,12 @@ int main(int argc, char **argv)
 	if (0 == seq_length) { std::cerr << "The sequences are empty." << std::endl; return EXIT_FAILURE; }
 
 	fseq_params p{};
-	p.m = (uint32_t) seqs.size();
+	p.m = (uint32_t) lengths.size();
 	p.n = seq_length;
 	p.segment_length = (uint64_t) seg_len;
 	p.pbwt_sample_rate = (uint64_t) sample_rate;
-	std::vector<uint8_t const *> rows(seqs.size());
+	std::vector<uint8_t const *> rows(lengths.size(), nullptr);      // (--upload-memory: no rows on the host)
+	std::string io_err;
 	for (size_t i = 0; i < seqs.size(); ++i) rows[i] = reinterpret_cast<uint8_t const *>(seqs[i].data());
 	bool const sharded = gpus > 1 && p.n >= 2 * p.segment_length;      // (the short path is one sweep: it does not shard)
 	if (gpus > 1 && !sharded) std::cerr << "The sequences are shorter than two segments; using one GPU." << std::endl;
@@ -287,7 +382,8 @@ int main(int argc, char **argv)
 		}
 		else if (FSEQ_OK != rc_) return rc_;
 		if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(ctxs[r], (uint64_t) list_memory_mib << 20))) return rc_;
-		if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
+		if (upload_given) { if (FSEQ_OK != (rc_ = upload_in_chunks(ctxs[r], paths, p.n, (uint64_t) upload_mib << 20, io_err))) return rc_; }
+		else if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
 		if (remove_identity)
 		{
 			// the uploaded alignment is the source; the run goes on on a context over the columns in which the sequences differ
@@ -328,6 +424,7 @@ int main(int argc, char **argv)
 		std::cerr << "Unable to reduce the number of sequences; the maximum segment size is equal to the number of input sequences." << std::endl;
 		return EXIT_FAILURE;
 	}
+	if (!io_err.empty()) { std::cerr << io_err << std::endl; return EXIT_FAILURE; }
 	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 
 	std::ofstream founders_file, segments_file;
@@ -338,7 +435,17 @@ int main(int argc, char **argv)
 		fseq_short_path_runs(ctx, first.data(), len.data());
 		std::cerr << "Outputting…" << std::endl;
 		std::ostream &os = *open_out(out_founders, founders_file);
-		for (uint32_t i = 0; i < res.max_segment_size; ++i) { os.write(seqs[first[i]].data(), (std::streamsize) seq_length); os << '\n'; }
+		// (--upload-memory: the founders are input rows, read now from the files the runs name, one at a time)
+		std::vector<std::string> named(upload_given && out_matches ? res.max_segment_size : 0);
+		for (uint32_t i = 0; i < res.max_segment_size; ++i)
+		{
+			std::string one;
+			if (upload_given && (!read_file(paths[first[i]], one) || one.size() != seq_length))
+			{ std::cerr << "Unable to read the sequence file '" << paths[first[i]] << "'." << std::endl; return EXIT_FAILURE; }
+			os.write(upload_given ? one.data() : seqs[first[i]].data(), (std::streamsize) seq_length);
+			os << '\n';
+			if (!named.empty()) named[i] = std::move(one);
+		}
 		os << std::flush;
 		if (out_segments)
 		{
@@ -352,7 +459,7 @@ int main(int argc, char **argv)
 			// (no permutations on this path: the founders are the distinct rows just written)
 			std::cerr << "Matching the input against the founders…" << std::endl;
 			std::vector<uint8_t const *> frows(res.max_segment_size);
-			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = rows[first[i]];
+			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = upload_given ? reinterpret_cast<uint8_t const *>(named[i].data()) : rows[first[i]];
 			fseq_match_summary sm{};
 			rc = fseq_match_founder_rows(ctx, frows.data(), res.max_segment_size, match_min_len, &sm);
 			if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;

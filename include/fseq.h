@@ -410,6 +410,44 @@ int  fseq_set_memory_budget(fseq_ctx *ctx, uint64_t bytes);
  * the input's diversity: the lists are, and this budget is what bounds them, at the price of replaying phase C once. */
 int  fseq_set_list_memory(fseq_ctx *ctx, uint64_t bytes);
 
+/* The input rows in column chunks of bounded memory: the device holds the packed alignment and a fixed staging buffer, never
+ * the m x n raw bytes fseq_set_rows stages, and the host may hold one chunk at a time.  replaces: nothing of the reference,
+ * which reads every sequence whole (generate_context.cc:64-106); it is what lets an alignment whose raw bytes exceed the card
+ * be loaded when its packed form fits.
+ *   fseq_input_begin    discards the context's input and result (as a second fseq_set_rows does) and allocates the staging:
+ *                       two halves of staging_bytes / 2 (0 = 256 MiB in all).  alphabet: the byte values that may occur, in any
+ *                       order, no duplicates (else FSEQ_E_ARG), or NULL: the alphabet is collected by fseq_input_scan calls.
+ *                       A staging too small for 16 columns of m rows in a half returns FSEQ_E_ARG and names the bytes needed.
+ *   fseq_input_chunk_columns   the most columns one call below may carry: floor(staging_bytes / 2 / m), rounded down to whole
+ *                       16-byte pieces of a staged row; 0 before fseq_input_begin and on a NULL context.
+ *   fseq_input_scan     rows[r] points at the ncols bytes of row r from column c0 on.  The calls tile [0, n) in ascending,
+ *                       contiguous chunks; only without a supplied alphabet.
+ *   fseq_input_columns  the same chunks again (after the scans have covered [0, n) when there is no supplied alphabet).  The
+ *                       first call fixes the code table -- dense codes in ascending byte order, as fseq_set_rows; with a
+ *                       supplied alphabet a listed byte that never occurs keeps its code, which changes no result (the order
+ *                       of the codes is all the pBWT sees) but may widen the codes -- and allocates the packed alignment.
+ *                       Padding bytes and padding fields of every column are written as zeros.
+ *   fseq_input_end      after column n has arrived: the context holds the input, the staging is released.  A byte outside a
+ *                       supplied alphabet is recorded on the device (no round trip per chunk) and reported here: FSEQ_E_ARG,
+ *                       fseq_last_error names the byte value, and the context is left without an input (it takes a new
+ *                       fseq_input_begin or fseq_set_rows).
+ * When fseq_input_scan or fseq_input_columns returns, the host bytes of that call have been read (the copy is waited for, not
+ * the kernel: chunk i is encoded while chunk i + 1 is copied into the other half), so the caller may reuse its buffers.
+ * Between begin and end the context's device allocations stay within packed alignment + staging_bytes + 1 MiB.  A chunk out
+ * of order, overlapping, gapped or wider than fseq_input_chunk_columns, a scan after a supplied alphabet, columns before the
+ * scans are complete, an end before column n, and any of these calls without a begin return FSEQ_E_ARG.  NOT for sharded
+ * contexts (fseq_set_shard before or after fseq_input_begin): FSEQ_E_UNSUPPORTED -- a rank's alphabet exchange is not built
+ * for this path.  Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+int      fseq_input_begin(fseq_ctx *ctx, uint8_t const *alphabet, uint32_t alphabet_size, uint64_t staging_bytes);
+uint64_t fseq_input_chunk_columns(fseq_ctx const *ctx);
+int      fseq_input_scan(fseq_ctx *ctx, uint64_t c0, uint64_t ncols, uint8_t const *const *rows);
+int      fseq_input_columns(fseq_ctx *ctx, uint64_t c0, uint64_t ncols, uint8_t const *const *rows);
+int      fseq_input_end(fseq_ctx *ctx);
+/* All of the above for rows that are in host memory (rows[r]: the n bytes of row r): the scan pass, the encode pass and the
+ * end, in chunks of fseq_input_chunk_columns rounded down to a multiple of 64 where that leaves at least 64.  Results are
+ * those of fseq_set_rows on the same rows, bit for bit. */
+int      fseq_set_rows_streamed(fseq_ctx *ctx, uint8_t const *const *rows, uint64_t staging_bytes);
+
 #ifdef __cplusplus
 }
 #endif

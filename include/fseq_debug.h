@@ -57,6 +57,15 @@ int  fseq_debug_clock(fseq_ctx *ctx, double *ghz, uint32_t *workgroups);
  * every rank (FSEQ_E_ARG afterwards: the input is laid out for the block partition in force when it was set). */
 int  fseq_debug_set_tuning(fseq_ctx *ctx, char const *name, char const *value);
 
+/* Device memory the context holds through its own buffers now (*now) and the most it has held since it was made or since the
+ * last call with reset_peak != 0 (*peak; the reset happens after the report, to the bytes held now).  Accounting of the
+ * context's allocations, not a measurement of the device: borrowed columns and the runtime's own memory are not in it. */
+int  fseq_debug_device_bytes(fseq_ctx *ctx, uint64_t *now, uint64_t *peak, int reset_peak);
+
+/* The resident alignment as it is stored: the bytes of the columns [c0, c1), *ld bytes a column (padding included), codes of
+ * *bits bits.  out == NULL: *ld and *bits only.  Not for sharded contexts (a rank holds its own columns only). */
+int  fseq_debug_packed_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t *out, uint64_t *ld, uint32_t *bits);
+
 #ifdef __cplusplus
 }
 #endif
