@@ -579,6 +579,7 @@ void free_work(fseq_ctx *c)
 	// what was planned for the buffers that are gone
 	c->lw.col_lo = c->lw.col_hi = 0;
 	c->colmask_ready = false;
+	c->ss_pack = 0; c->ss_ids = false;       // (the form of the stride states: decided again where they are allocated)
 	c->red_plan_valid = false; c->red_declined = false; c->red_cap = 0; c->red_ld = 0;
 	c->red_active = false;
 }
@@ -653,10 +654,6 @@ int upload_rows_device_impl(fseq_ctx *c, uint8_t const *const *rows)
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "encode + transpose", e);
 	c->have_input = true;
-	c->have_result = false;
-	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
 	return FSEQ_OK;
 }
 
@@ -694,10 +691,6 @@ int set_alphabet_and_upload(fseq_ctx *c, uint8_t const *base, size_t rs, size_t 
 		HIP_TRY(c, hipMemcpy(c->d_msa + c0 * c->ld, buf.data(), (c1 - c0) * c->ld, hipMemcpyHostToDevice));
 	}
 	c->have_input = true;
-	c->have_result = false;
-	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
 	return FSEQ_OK;
 }
 
@@ -2984,21 +2977,47 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 
 } // namespace
 
-// the chunked input (csrc/fseq_api_input.hip): the alignment, the work buffers and the result of the last input go before the
-// staging is allocated; what a run remembers of an input is forgotten as in every other upload
-void fseq::forget_input_history(fseq_ctx *c)
+// What a run leaves behind for the next run in the same geometry: the result, the kernel choice, what phase A gave up, the plan of
+// the representatives.  A tuning knob forgets this much (the input is the same one) ...
+static void forget_run_history(fseq_ctx *c)
 {
 	c->have_result = false;
 	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
+	c->bk_given_up = -1; c->bt_given_up = -1; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
 }
 
-void fseq::discard_input(fseq_ctx *c)
+// ... and an input what was learnt of the input besides
+void fseq::forget_input_history(fseq_ctx *c)
 {
-	free_msa(c);
+	forget_run_history(c);
+	c->X_hint = 0;
+	c->colmask_ready = false; c->shard_dp_full_sticky = false;
+}
+
+// A new input takes this context: every input setter calls this once its arguments are in order and before it touches the
+// alignment.  The work buffers go, and with them everything ensure_work_buffers decides only where it allocates (the form and
+// packing of the stride states, their spacing, the workspace's rebase, the buffers sized by the block count): the next run
+// lays them out for the new alphabet and packing.  The result and the last match go too.  A context made by
+// fseq_create_without_identity_columns holds the relation of its columns to its source's: it refuses another input.
+int fseq::take_new_input(fseq_ctx *c)
+{
+	if (c->idn.have)
+		return fail(c, FSEQ_E_ARG, "a context made by fseq_create_without_identity_columns takes no other input (its identity relation belongs to the columns it was made from)");
+	(void) hipSetDevice(c->p.device);
+	if (c->stream) (void) hipStreamSynchronize(c->stream);
 	free_work(c);
+	c->free_match();
 	forget_input_history(c);
+	return FSEQ_OK;
+}
+
+// the chunked input's begin (csrc/fseq_api_input.hip): the alignment goes as well, before the staging is allocated
+int fseq::discard_input(fseq_ctx *c)
+{
+	int const rc = take_new_input(c);
+	if (rc) return rc;
+	free_msa(c);
+	return FSEQ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3076,7 +3095,7 @@ char const *fseq_last_error(fseq_ctx const *c) { return c ? c->err.c_str() : "nu
 int fseq_set_matrix(fseq_ctx *c, uint8_t const *base, size_t row_stride, size_t col_stride)
 {
 	if (!c || !base) return FSEQ_E_ARG;
-	(void) hipSetDevice(c->p.device);
+	if (int const rc = take_new_input(c)) return rc;
 	if (1 == col_stride)
 	{
 		// row-major view: the same device path as fseq_set_rows
@@ -3093,6 +3112,7 @@ int fseq_set_rows(fseq_ctx *c, uint8_t const *const *rows)
 	(void) hipSetDevice(c->p.device);
 	for (uint32_t r = 0; r < c->p.m; ++r)
 		if (!rows[r]) return fail(c, FSEQ_E_ARG, "null row pointer");
+	if (int const rc = take_new_input(c)) return rc;
 	return upload_rows_device(c, rows);
 }
 
@@ -3132,6 +3152,7 @@ int fseq_set_device_columns(fseq_ctx *c, void const *d_codes, size_t ld, uint32_
 	if (ld < c->p.m || (ld & 15) || (reinterpret_cast<uintptr_t>(d_codes) & 15))
 		return fail(c, FSEQ_E_ARG, "device columns: ld must be >= m and a multiple of 16, base 16-byte aligned");
 	if (sigma == 0 || sigma > 256) return fail(c, FSEQ_E_ARG, "sigma out of range");
+	if (int const rc = take_new_input(c)) return rc;
 	free_msa(c);
 	c->d_msa = const_cast<uint8_t *>(static_cast<uint8_t const *>(d_codes)) - held_lo(c) * ld;
 	c->ld = ld;
@@ -3139,11 +3160,6 @@ int fseq_set_device_columns(fseq_ctx *c, void const *d_codes, size_t ld, uint32_
 	c->sigma = sigma;
 	for (uint32_t i = 0; i < 256; ++i) c->code_to_byte[i] = (uint8_t) i;
 	c->have_input = true;
-	c->have_result = false;
-	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
-	(void) hipSetDevice(c->p.device);
 	return check_borrowed_codes(c);
 }
 
@@ -3155,6 +3171,7 @@ int fseq_set_device_columns_packed(fseq_ctx *c, void const *d_packed, size_t ld_
 	if (sigma == 0 || sigma > (1u << bits)) return fail(c, FSEQ_E_ARG, "sigma does not fit the code width");
 	if (ld_bytes < sym_bytes(c->p.m, bsh) || (ld_bytes & 15) || (reinterpret_cast<uintptr_t>(d_packed) & 15))
 		return fail(c, FSEQ_E_ARG, "packed device columns: ld_bytes must cover a column and be a multiple of 16, base 16-byte aligned");
+	if (int const rc = take_new_input(c)) return rc;
 	free_msa(c);
 	c->d_msa = const_cast<uint8_t *>(static_cast<uint8_t const *>(d_packed)) - held_lo(c) * ld_bytes;
 	c->ld = ld_bytes;
@@ -3162,11 +3179,6 @@ int fseq_set_device_columns_packed(fseq_ctx *c, void const *d_packed, size_t ld_
 	c->sigma = sigma;
 	for (uint32_t i = 0; i < 256; ++i) c->code_to_byte[i] = (uint8_t) i;
 	c->have_input = true;
-	c->have_result = false;
-	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
-	(void) hipSetDevice(c->p.device);
 	return check_borrowed_codes(c);
 }
 
@@ -3241,7 +3253,7 @@ int fseq_shard_owner(fseq_ctx const *c, uint64_t rb, uint32_t *rank)
 int fseq_generate_synthetic(fseq_ctx *c, fseq_synth_spec const *spec)
 {
 	if (!c || !spec || 0 == spec->n_founders || 0 == spec->block_len || spec->kind > 1) return FSEQ_E_ARG;
-	(void) hipSetDevice(c->p.device);
+	if (int const rc0 = take_new_input(c)) { shard_post_failure(c, rc0); return rc0; }
 	char const *alpha = spec->kind ? "ACGTRYSWKMBDHVN-" : "ACGT";
 	uint32_t const sigma = spec->kind ? 16u : 4u;
 	c->sigma = sigma;
@@ -3267,10 +3279,6 @@ int fseq_generate_synthetic(fseq_ctx *c, fseq_synth_spec const *spec)
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	c->have_input = true;
-	c->have_result = false;
-	c->kernels_ready = false;
-	c->X_hint = 0;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->colmask_ready = false; c->shard_dp_full_sticky = false; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
 	return FSEQ_OK;
 }
 
@@ -3326,10 +3334,8 @@ int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 	(void) hipSetDevice(c->p.device);
 	if (c->stream) (void) hipStreamSynchronize(c->stream);
 	free_work(c);
-	c->have_result = false;
-	c->kernels_ready = false;
 	// (what the last run saw belongs to the old geometry: a block the tree or the trie ranked then may be given up now)
-	c->bk_given_up = -1; c->bt_given_up = -1; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
+	forget_run_history(c);
 	return FSEQ_OK;
 }
 
@@ -3374,21 +3380,25 @@ int fseq_run_segmentation_batch(fseq_ctx *const *ctxs, size_t count, fseq_result
 
 int fseq_get_traceback(fseq_ctx *c, fseq_dp_arg *out)
 {
-	if (!c || !out || !c->have_result) return FSEQ_E_ARG;
+	if (!c || !out) return FSEQ_E_ARG;
+	if (int const rc = need_result(c, false)) return rc;
 	std::copy(c->traceback.begin(), c->traceback.end(), out);
 	return FSEQ_OK;
 }
 
 int fseq_get_segments(fseq_ctx *c, fseq_segment *out)
 {
-	if (!c || !out || !c->have_result) return FSEQ_E_ARG;
+	if (!c || !out) return FSEQ_E_ARG;
+	if (int const rc = need_result(c, false)) return rc;
 	std::copy(c->segments.begin(), c->segments.end(), out);
 	return FSEQ_OK;
 }
 
 int fseq_boundary_state(fseq_ctx *c, uint64_t i, uint32_t *a_out, uint32_t *d_out)
 {
-	if (!c || !c->have_result || i >= c->segments.size()) return FSEQ_E_ARG;
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c, false)) return rc;
+	if (i >= c->segments.size()) return FSEQ_E_ARG;
 	(void) hipSetDevice(c->p.device);
 	size_t const m = c->p.m;
 	if (i >= c->snap_slot.size() || c->snap_slot[i] < 0) return fail(c, FSEQ_E_ARG, "boundary state held by another rank (fseq_shard_owner)");
@@ -3400,7 +3410,9 @@ int fseq_boundary_state(fseq_ctx *c, uint64_t i, uint32_t *a_out, uint32_t *d_ou
 
 int fseq_short_path_runs(fseq_ctx *c, uint32_t *first_idx, uint32_t *run_len)
 {
-	if (!c || !c->have_result || !c->res.short_path) return FSEQ_E_ARG;
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c, false)) return rc;
+	if (!c->res.short_path) return FSEQ_E_ARG;
 	if (first_idx) std::copy(c->sp_first.begin(), c->sp_first.end(), first_idx);
 	if (run_len) std::copy(c->sp_len.begin(), c->sp_len.end(), run_len);
 	return FSEQ_OK;
@@ -3408,7 +3420,8 @@ int fseq_short_path_runs(fseq_ctx *c, uint32_t *first_idx, uint32_t *run_len)
 
 int fseq_debug_dp(fseq_ctx *c, uint32_t *lb, uint32_t *max_size, uint32_t *size)
 {
-	if (!c || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	(void) hipSetDevice(c->p.device);
 	if (lb) HIP_TRY(c, hipMemcpy(lb, c->dp.LB, c->dp_size * 4, hipMemcpyDeviceToHost));
 	if (max_size) HIP_TRY(c, hipMemcpy(max_size, c->dp.M, c->dp_size * 4, hipMemcpyDeviceToHost));

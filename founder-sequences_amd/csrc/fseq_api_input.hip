@@ -164,10 +164,10 @@ int fseq_input_begin(fseq_ctx *c, uint8_t const *alphabet, uint32_t alphabet_siz
 	}
 	(void) hipSetDevice(c->p.device);
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	discard_input(c);                                              // (ends a chunked input under way, too)
+	int rc;
+	if ((rc = discard_input(c))) return rc;                        // (ends a chunked input under way, too)
 	fseq_ctx::Input &in = c->in;
 	in = fseq_ctx::Input{};
-	int rc;
 	if ((rc = in.stage.alloc(c, (size_t) (2 * half))) || (rc = in.words.alloc(c, 16)) || (rc = in.table.alloc(c, 256))) { c->free_input(); return rc; }
 	for (int h = 0; h < 2; ++h)
 		if (hipEventCreateWithFlags(&in.copied[h], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&in.used[h], hipEventDisableTiming) != hipSuccess)

@@ -24,7 +24,8 @@ int fseq_get_join_profile(fseq_ctx const *c, fseq_join_profile *out)
 
 int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 {
-	if (!c || !permutations || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c || !permutations) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to join (segmentation failed or was not run)");
 	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: collect the boundary states (fseq_boundary_state on their owners) and use fseq_greedy_match_host");
 	(void) hipSetDevice(c->p.device);
@@ -103,7 +104,7 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 // boundary states of all merged segments on the host (what join_context reads from the pbwt samples)
 static int fetch_boundary_states(fseq_ctx *c, std::vector<uint32_t> &A, std::vector<uint32_t> &D, std::vector<JoinSegment> &segs)
 {
-	if (!c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to join (segmentation failed or was not run)");
 	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: collect the boundary states (fseq_boundary_state on their owners) and use the *_match_host entry points");
 	(void) hipSetDevice(c->p.device);
@@ -121,7 +122,7 @@ static int fetch_boundary_states(fseq_ctx *c, std::vector<uint32_t> &A, std::vec
 int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 {
 	if (!c || !permutations) return FSEQ_E_ARG;
-	if (!c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to join (segmentation failed or was not run)");
 	size_t const m = c->p.m, S = c->segments.size();
 	uint32_t const X = c->res.max_segment_size;
@@ -222,7 +223,8 @@ static int write_segments_impl(fseq_ctx *c, uint8_t const *const *rows, int join
 
 int fseq_write_segments(fseq_ctx *c, uint8_t const *const *rows, int joining, char const *path)
 {
-	if (!c || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (joining != FSEQ_JOIN_GREEDY && !rows) return FSEQ_E_ARG;
 	std::vector<uint32_t> A, D;
 	std::vector<JoinSegment> segs;
@@ -237,7 +239,8 @@ int fseq_write_segments(fseq_ctx *c, uint8_t const *const *rows, int joining, ch
 // the same with the boundary states supplied by the caller (a sharded run: collected from their owners)
 int fseq_write_segments_host(fseq_ctx *c, uint8_t const *const *rows, int joining, uint32_t const *a, uint32_t const *d, char const *path)
 {
-	if (!c || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (joining != FSEQ_JOIN_GREEDY && (!rows || !a || !d)) return FSEQ_E_ARG;
 	std::vector<JoinSegment> segs;
 	if (joining != FSEQ_JOIN_GREEDY)
@@ -311,7 +314,8 @@ int fseq_greedy_match_host(uint32_t m, uint32_t max_segment_size, uint64_t n_seg
 
 int fseq_write_founders(fseq_ctx *c, uint8_t const *const *rows, uint32_t const *permutations, char const *path)
 {
-	if (!c || !rows || !permutations || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c || !rows || !permutations) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
 	if (!f) return fail(c, FSEQ_E_ARG, "cannot open the founders output file");
 	size_t const X = c->res.max_segment_size, S = c->segments.size();
@@ -357,7 +361,8 @@ int fseq_write_founders(fseq_ctx *c, uint8_t const *const *rows, uint32_t const 
 // The lines are put together on the device, a batch of rows (<= 256 MB) at a time, and leave in one copy and one write per batch.
 int fseq_write_founders_device(fseq_ctx *c, uint32_t const *permutations, char const *path)
 {
-	if (!c || !permutations || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	if (!c || !permutations) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
 	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
 	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: a rank holds its own columns only (write the founders from host rows: fseq_write_founders)");
 	(void) hipSetDevice(c->p.device);

@@ -518,10 +518,22 @@ inline void progress(fseq_ctx *c, int stage, uint64_t current, uint64_t max)
 	if (c->progress_fn) c->progress_fn(c->progress_user, stage, current, max);
 }
 
-// csrc/fseq_api.hip: the alignment, the work buffers and the result a context holds are dropped (the chunked input's begin);
-// what runs remember of the last input is forgotten (every upload)
-void discard_input(fseq_ctx *c);
+// csrc/fseq_api.hip: a new input takes the context (every input setter, before it touches the alignment): the work buffers,
+// the result and the last match are dropped and what runs remember of the last input is forgotten; a context over the kept
+// columns of another refuses.  discard_input: the same and the alignment too (the chunked input's begin).
+int take_new_input(fseq_ctx *c);
+int discard_input(fseq_ctx *c);
 void forget_input_history(fseq_ctx *c);
+
+// what hands out a run's results asks this first: no run yet, or none since an input or a tuning knob was set
+inline int need_result(fseq_ctx *c, bool long_path = true)
+{
+	if (!c->have_result)
+		return fail(c, FSEQ_E_ARG, "no result on this context: no run has finished since its input or a tuning knob was set (fseq_run_segmentation)");
+	if (long_path && c->res.short_path)
+		return fail(c, FSEQ_E_ARG, "the last run took the short path (n < 2L): this call serves a long-path result");
+	return FSEQ_OK;
+}
 
 #define HIP_TRY(c, expr)                                                   \
 	do {                                                                   \

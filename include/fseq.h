@@ -122,7 +122,23 @@ int  fseq_create(fseq_params const *params, fseq_ctx **out);
 void fseq_destroy(fseq_ctx *ctx);
 char const *fseq_last_error(fseq_ctx const *ctx);
 
-/* Input = delegate->sequences() (m spans of n raw bytes, founder_sequences.hh:38-40) plus
+/* ---- a new input on a live context ----
+ * Every input setter -- fseq_set_rows, fseq_set_matrix, fseq_set_device_columns, fseq_set_device_columns_packed,
+ * fseq_generate_synthetic and the chunked input (fseq_input_begin .. fseq_input_end, fseq_set_rows_streamed) -- may be called
+ * again on a context that has run; m, n and the segment length stay those of fseq_create.  Once its arguments are in order the
+ * call takes the context for the new alignment:
+ *   - the result of the last run is dropped: until the next fseq_run_segmentation, fseq_get_traceback, fseq_get_segments,
+ *     fseq_boundary_state, fseq_short_path_runs, the joiners, fseq_write_segments, fseq_write_founders(_device) and
+ *     fseq_match_founders return FSEQ_E_ARG, and fseq_last_error says that no run has finished since the input was set;
+ *   - the last match is dropped: fseq_get_match and fseq_write_match return FSEQ_E_ARG until the next match;
+ *   - the device work buffers of the runs before are released (the next run lays them out for the new alphabet and packing:
+ *     a context that cycles through inputs holds no more after the third than after the second) and what runs had learnt of
+ *     the old input is forgotten, so the first run on the new input costs what a first run on a fresh context costs;
+ *   - a context made by fseq_create_without_identity_columns REFUSES (FSEQ_E_ARG, nothing it holds changes): its identity
+ *     relation belongs to the columns it was made from.  Make a new one from the new source.
+ * A setter that fails after this point leaves the context without a result, and without an input where it says so.
+ *
+ * Input = delegate->sequences() (m spans of n raw bytes, founder_sequences.hh:38-40) plus
  * delegate->alphabet() (generate_context.cc:135-147).  rows[r] points at n bytes.  The bytes
  * are mapped to dense codes in ascending byte order and stored column-major in HBM. */
 int  fseq_set_rows(fseq_ctx *ctx, uint8_t const *const *rows);
@@ -335,7 +351,9 @@ int  fseq_identity_columns(fseq_ctx *ctx, uint8_t *mask /* n bytes */, fseq_iden
  * right afterwards.  Every column an identity column: FSEQ_E_ARG ("every column is an identity column"), nothing is created;
  * none: a plain copy.  A failed allocation returns FSEQ_E_OOM with the sizes (fseq_last_error(src)), leaves nothing behind
  * and src usable.  fseq_get_matrix, fseq_run_segmentation, the joiners, fseq_write_segments (given the reduced rows),
- * fseq_write_founders_device (reduced founders) and the matcher work on the new context unchanged.  summary may be NULL. */
+ * fseq_write_founders_device (reduced founders) and the matcher work on the new context unchanged.  summary may be NULL.
+ * The new context takes no other input: every input setter returns FSEQ_E_ARG on it and leaves it as it is (the mask, the
+ * kept columns and the reference row describe the alignment it was made from; see "a new input on a live context"). */
 int  fseq_create_without_identity_columns(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary);
 /* On a context made by the call above (FSEQ_E_ARG on any other): the mask over the source's columns (source n bytes) and
  * the source column of every column of this context (`kept` entries, ascending); either may be NULL. */
