@@ -4,8 +4,23 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# translation units of the library: the path (kernels, geometry, phases, sharding, ABI), the joiners / writers, the matcher, the identity columns and the chunked input
-SRCS = [os.path.join(HERE, "csrc", "fseq_api.hip"), os.path.join(HERE, "csrc", "fseq_api_join.hip"), os.path.join(HERE, "csrc", "fseq_api_match.hip"), os.path.join(HERE, "csrc", "fseq_api_identity.hip"), os.path.join(HERE, "csrc", "fseq_api_input.hip"), os.path.join(HERE, "csrc", "fseq_reduced.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets.hip"), os.path.join(HERE, "csrc", "fseq_kernelsets_stream.hip")]
+# translation units of the library: the ABI's entry points, the segmentation path by phase (csrc/fseq_path.hpp lists what each holds),
+# the joiners / writers, the matcher, the identity columns, the chunked input, and the kernel configurations
+SRCS = [os.path.join(HERE, "csrc", name) for name in (
+    "fseq_api.hip",
+    "fseq_api_debug.hip",
+    "fseq_path_setup.hip",
+    "fseq_path_dp.hip",
+    "fseq_path_pass1.hip",
+    "fseq_path_pass2.hip",
+    "fseq_api_join.hip",
+    "fseq_api_match.hip",
+    "fseq_api_identity.hip",
+    "fseq_api_input.hip",
+    "fseq_reduced.hip",
+    "fseq_kernelsets.hip",
+    "fseq_kernelsets_stream.hip",
+)]
 SRC = SRCS[0]
 import glob
 DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*"))) + [os.path.join(os.path.dirname(HERE), "include", "fseq.h"),
@@ -58,7 +73,7 @@ def build(force=False, verbose=False):
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra_flags() + (["-DFSEQ_WITH_ROCTX"] if have_roctx else [])
     ldflags = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"] if have_roctx else []
     os.makedirs(OBJ_DIR, exist_ok=True)
-    # the translation units side by side (the kernel TU is ~50 s of hipcc, the joiners a few)
+    # the translation units side by side (the kernel TU is ~40 s of hipcc, the path's largest unit -- pass 1 -- ~20 s, the others ten or fewer)
     procs = []
     objs = []
     for src in SRCS:

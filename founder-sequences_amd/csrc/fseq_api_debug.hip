@@ -1,0 +1,266 @@
+// fseq_api_debug.hip -- the entry points of include/fseq_debug.h (what the tests and tools look at behind a run; the
+// range-minimum query's is with the DP, csrc/fseq_path_dp.hip) and the row-sharded conformance sweep of include/fseq.h.
+// The one unit that includes fseq_rowshard.hpp.
+#include "fseq_path.hpp"
+#include "fseq_dp.hpp"           // the round schedule (fseq_debug_dp_schedule)
+#include "fseq_rowshard.hpp"
+
+using namespace fseq;
+
+extern "C" {
+
+int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
+{
+	if (!c || !name) return FSEQ_E_ARG;
+	// sharded: the input was laid out for the block partition of the knobs in force when it was set, and every rank must
+	// plan the same partition -- the knobs of a sharded run are set (identically on every rank) before the input
+	if (c->sh.on && c->have_input) return fail(c, FSEQ_E_ARG, "sharded run: set tuning knobs before the input is set (identically on every rank)");
+	if (!c->tune.set(name, value)) return fail(c, FSEQ_E_ARG, "unknown tuning knob");
+	// (the geometry and the kernel choice may depend on it: the work buffers of an earlier run were sized for the old one)
+	(void) hipSetDevice(c->p.device);
+	if (c->stream) (void) hipStreamSynchronize(c->stream);
+	free_work(c);
+	// (what the last run saw belongs to the old geometry: a block the tree or the trie ranked then may be given up now)
+	forget_run_history(c);
+	return FSEQ_OK;
+}
+
+int fseq_debug_dp(fseq_ctx *c, uint32_t *lb, uint32_t *max_size, uint32_t *size)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	if (lb) HIP_TRY(c, hipMemcpy(lb, c->dp.LB, c->dp_size * 4, hipMemcpyDeviceToHost));
+	if (max_size) HIP_TRY(c, hipMemcpy(max_size, c->dp.M, c->dp_size * 4, hipMemcpyDeviceToHost));
+	if (size) HIP_TRY(c, hipMemcpy(size, c->dp.SZ, c->dp_size * 4, hipMemcpyDeviceToHost));
+	return FSEQ_OK;
+}
+
+int fseq_debug_dp_owned(fseq_ctx *c, uint64_t *first, uint64_t *last, int *final_cell, int *whole_arrays)
+{
+	if (!c || !c->have_result || c->res.short_path) return FSEQ_E_ARG;
+	uint64_t lo = 0, hi = c->dp_size;
+	int fin = 1, whole = 1;
+	if (c->sh.on)
+	{
+		Shard const &sh = c->sh;
+		bool const have = sh.rank < sh.active && sh.rank < c->own_lo.size();
+		lo = have ? c->own_lo[sh.rank] : 0; hi = have ? c->own_hi[sh.rank] : 0;
+		fin = have && sh.rank + 1u == sh.active ? 1 : 0;
+		whole = c->dp_window_mode ? 0 : 1;
+	}
+	if (first) *first = lo;
+	if (last) *last = hi;
+	if (final_cell) *final_cell = fin;
+	if (whole_arrays) *whole_arrays = whole;
+	return FSEQ_OK;
+}
+
+int fseq_debug_ranges(uint64_t *pushes, uint64_t *pops, int *with_roctx)
+{
+	if (pushes) *pushes = g_range_pushes.load(std::memory_order_relaxed);
+	if (pops) *pops = g_range_pops.load(std::memory_order_relaxed);
+#ifdef FSEQ_WITH_ROCTX
+	if (with_roctx) *with_roctx = 1;
+#else
+	if (with_roctx) *with_roctx = 0;
+#endif
+	return FSEQ_OK;
+}
+
+int fseq_debug_clock(fseq_ctx *c, double *ghz, uint32_t *workgroups)
+{
+	if (!c || !ghz) return FSEQ_E_ARG;
+#ifdef FSEQ_CLOCK_STAMPS
+	(void) hipSetDevice(c->p.device);
+	std::vector<unsigned long long> st((size_t) FSEQ_CLOCK_SLOTS * 4);
+	HIP_TRY(c, hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_clock_stamps), st.size() * 8));
+	std::vector<double> f;
+	for (uint32_t i = 0; i < FSEQ_CLOCK_SLOTS; ++i)
+	{
+		unsigned long long const t0 = st[4 * i], r0 = st[4 * i + 1], t1 = st[4 * i + 2], r1 = st[4 * i + 3];
+		if (t1 > t0 && r1 > r0) f.push_back((double) (t1 - t0) / (double) (r1 - r0) * 0.1);      // cycles per 10 ns = GHz x 10
+	}
+	if (f.empty()) return fail(c, FSEQ_E_ARG, "no clock stamps: run a long-path segmentation first");
+	std::nth_element(f.begin(), f.begin() + f.size() / 2, f.end());
+	*ghz = f[f.size() / 2];
+	if (workgroups) *workgroups = (uint32_t) f.size();
+	return FSEQ_OK;
+#else
+	(void) workgroups;
+	*ghz = 0.0;
+	return fail(c, FSEQ_E_UNSUPPORTED, "built without -DFSEQ_CLOCK_STAMPS (the product kernels execute no stamp)");
+#endif
+}
+
+int fseq_debug_block_state(fseq_ctx *c, uint64_t block_idx, uint32_t *a_out, uint32_t *d_out)
+{
+	if (!c || !c->have_result || c->res.short_path || block_idx > c->nblocks) return FSEQ_E_ARG;
+	if (c->sh.on && (block_idx < c->sh.b_lo || block_idx > c->sh.b_hi)) return fail(c, FSEQ_E_ARG, "block state held by another rank");
+	(void) hipSetDevice(c->p.device);
+	size_t const m = c->p.m;
+	if (a_out) HIP_TRY(c, hipMemcpy(a_out, c->d_bstate_a + block_idx * m, m * 4, hipMemcpyDeviceToHost));
+	if (d_out) HIP_TRY(c, hipMemcpy(d_out, c->d_bstate_d + block_idx * m, m * 4, hipMemcpyDeviceToHost));
+	return FSEQ_OK;
+}
+
+int fseq_debug_column_list(fseq_ctx *c, uint64_t col, uint32_t *values, uint32_t *counts,
+                           uint32_t *n_entries, uint32_t *cnt0, uint32_t *complete)
+{
+	if (!c || !c->have_result || c->res.short_path || col >= c->p.n) return FSEQ_E_ARG;
+	if (c->lw.on && (col < c->lw.col_lo || col >= c->lw.col_hi)) return fail(c, FSEQ_E_ARG, "the list of this column is not held: the run kept its lists in windows (fseq_set_list_memory)");
+	(void) hipSetDevice(c->p.device);
+	uint4 h;
+	HIP_TRY(c, hipMemcpy(&h, c->d_hdr + col, sizeof(h), hipMemcpyDeviceToHost));
+	std::vector<uint2> e(h.x);
+	if (h.x) HIP_TRY(c, hipMemcpy(e.data(), c->d_ent + col * (size_t) c->stride, h.x * sizeof(uint2), hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < h.x; ++i)
+	{
+		if (values) values[i] = e[i].x;
+		if (counts) counts[i] = e[i].y;
+	}
+	if (n_entries) *n_entries = h.x;
+	if (cnt0) *cnt0 = h.y;
+	if (complete) *complete = h.z;
+	return FSEQ_OK;
+}
+
+int fseq_debug_list_windows(fseq_ctx *c, uint64_t *bytes_held, uint64_t *columns_per_window, uint32_t *windows, uint32_t *merge_windows)
+{
+	if (!c || !c->have_result) return FSEQ_E_ARG;
+	fseq_ctx::ListWindows const &W = c->lw;
+	bool const lists = !c->res.short_path;
+	if (bytes_held) *bytes_held = W.on ? W.bytes : lists ? (uint64_t) c->d_ent.cap * sizeof(uint2) : 0;
+	if (columns_per_window) *columns_per_window = W.on ? (uint64_t) W.wb * c->B : lists ? held_hi(c) - held_lo(c) : 0;
+	if (windows) *windows = W.on ? W.nwin : lists ? 1u : 0u;
+	if (merge_windows) *merge_windows = W.on ? W.merge_windows : 0u;
+	return FSEQ_OK;
+}
+
+int fseq_debug_dp_schedule(uint64_t segment_length, uint64_t n, uint64_t col_hi, uint32_t *n_rounds, uint32_t *cells_per_round,
+                           uint32_t *rounds_within, int *pipelined)
+{
+	if (0 == segment_length || n < 2 * segment_length || n >= 0xFFFFFFF0ull) return FSEQ_E_ARG;
+	DpSchedule const S = dp_schedule((uint32_t) segment_length, (uint32_t) n);
+	if (n_rounds) *n_rounds = S.nrounds;
+	if (cells_per_round) *cells_per_round = S.RL;
+	if (rounds_within) *rounds_within = dp_rounds_within(S, col_hi);
+	if (pipelined) *pipelined = S.pipe ? 1 : 0;
+	return FSEQ_OK;
+}
+
+// ---- row-sharded pBWT sweep: the north-star partition as a conformance path (fseq_rowshard.hpp) ------------------
+uint64_t fseq_rowshard_xbuf_words(uint32_t m, uint32_t bits, uint32_t world)
+{
+	if (!m || !world || (bits != 2 && bits != 4 && bits != 8)) return 0;
+	uint32_t const bsh = bits == 2 ? 2u : bits == 4 ? 1u : 0u;
+	uint64_t const cw = (sym_bytes(m, bsh) + 3u) / 4u;
+	return 2 * (cw + 2ull * m) + (uint64_t) RS_SLOT * world + 64;
+}
+
+int fseq_rowshard_rows(uint32_t m, uint32_t bits, uint32_t rank, uint32_t world, uint32_t *row_lo, uint32_t *row_hi)
+{
+	if (!m || !world || rank >= world || !row_lo || !row_hi || (bits != 2 && bits != 4 && bits != 8)) return FSEQ_E_ARG;
+	uint32_t const bsh = bits == 2 ? 2u : bits == 4 ? 1u : 0u;
+	uint64_t const cw = (sym_bytes(m, bsh) + 3u) / 4u, rpw = 32u / bits;
+	*row_lo = (uint32_t) std::min<uint64_t>(m, cw * rank / world * rpw);
+	*row_hi = (uint32_t) std::min<uint64_t>(m, cw * (rank + 1) / world * rpw);
+	return FSEQ_OK;
+}
+
+int fseq_rowshard_pbwt(fseq_rowshard const *A, uint32_t *a_out, uint32_t *d_out, uint32_t *pos_lo, uint32_t *pos_hi,
+                       double *ms, uint64_t *n_exchanges)
+{
+	if (!A || !A->m || !A->world || A->rank >= A->world || !A->d_cols || !a_out || !d_out) return FSEQ_E_ARG;
+	if ((A->bits != 2 && A->bits != 4 && A->bits != 8) || A->sigma < 1 || A->sigma > (1u << A->bits)) return FSEQ_E_ARG;
+	uint32_t const m = A->m, G = A->world, g = A->rank;
+	uint32_t const bsh = A->bits == 2 ? 2u : A->bits == 4 ? 1u : 0u;
+	uint64_t const cw = (sym_bytes(m, bsh) + 3u) / 4u;
+	if (A->ld % 4 || A->ld < cw * 4) return FSEQ_E_ARG;
+	if (A->ncols > 0xFFFFFFFEull) return FSEQ_E_ARG;
+	if (G > 1 && (!A->xbuf || !A->fn)) return FSEQ_E_ARG;
+	if (!A->xbuf || A->xbuf_words < fseq_rowshard_xbuf_words(m, A->bits, G)) return FSEQ_E_ARG;
+	if (hipSetDevice(A->device) != hipSuccess) return FSEQ_E_HIP;
+	uint32_t nbits = 1;
+	while ((1u << nbits) < A->sigma) ++nbits;
+	uint32_t const npass = (nbits + 1) / 2;
+	uint64_t const reg = cw + 2ull * m;
+	uint32_t *const xb = static_cast<uint32_t *>(A->xbuf);
+	uint32_t *const slots = xb + 2 * reg;
+	auto C_ = [&](uint32_t r) { return xb + r * reg; };
+	auto A_ = [&](uint32_t r) { return xb + r * reg + cw; };
+	auto D_ = [&](uint32_t r) { return xb + r * reg + cw + m; };
+	uint32_t const p_lo = (uint32_t) ((uint64_t) m * g / G), p_hi = (uint32_t) ((uint64_t) m * (g + 1) / G), ml = p_hi - p_lo;
+	uint32_t const w_lo = (uint32_t) (cw * g / G), w_hi = (uint32_t) (cw * (g + 1) / G);
+	hipStream_t st = nullptr;
+	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return FSEQ_E_HIP;
+	uint64_t nex = 0;
+	bool ok = true;
+	auto H = [&](hipError_t e) { if (e != hipSuccess) ok = false; return e == hipSuccess; };
+	auto xch = [&](uint64_t off, uint64_t count) {
+		++nex;
+		if (G == 1 || !ok) return;
+		if (!H(hipStreamSynchronize(st))) return;
+		if (A->fn(A->user, off, count, 0) != 0) ok = false;
+	};
+	auto contrib = [&](uint64_t k, uint32_t r) {
+		H(hipMemsetAsync(C_(r), 0, cw * 4, st));
+		if (w_hi > w_lo)
+			hipLaunchKernelGGL(k_rs_contrib, dim3((w_hi - w_lo + 255u) / 256u), dim3(256), 0, st,
+			                   reinterpret_cast<uint32_t const *>(static_cast<uint8_t const *>(A->d_cols) + k * A->ld), w_lo, w_hi, C_(r));
+	};
+	double const t0 = now_ms();
+	hipLaunchKernelGGL(k_rs_init, dim3((m + 255u) / 256u), dim3(256), 0, st, A_(0), D_(0), m);
+	uint32_t colreg = 0, adreg = 0;
+	if (A->ncols)
+	{
+		contrib(0, 0);
+		xch(0, cw);                                              // X0 of column 0
+	}
+	for (uint64_t k = 0; k < A->ncols && ok; ++k)
+		for (uint32_t pass = 0; pass < npass && ok; ++pass)
+		{
+			uint8_t const *col = reinterpret_cast<uint8_t const *>(C_(colreg));
+			H(hipMemsetAsync(slots, 0, (size_t) RS_SLOT * G * 4, st));
+			hipLaunchKernelGGL(k_rs_sweep<false>, dim3(1), dim3(ST), 0, st, col, A_(adreg) + p_lo, D_(adreg) + p_lo, ml, bsh, pass,
+			                   (uint32_t) (k + 1), slots, g, G, (uint32_t *) nullptr, (uint32_t *) nullptr);
+			xch(2 * reg, (uint64_t) RS_SLOT * G);                   // X1 + X2
+			uint32_t const r2 = 1u - adreg;
+			H(hipMemsetAsync(A_(r2), 0, (size_t) 2 * m * 4, st));
+			hipLaunchKernelGGL(k_rs_sweep<true>, dim3(1), dim3(ST), 0, st, col, A_(adreg) + p_lo, D_(adreg) + p_lo, ml, bsh, pass,
+			                   (uint32_t) (k + 1), slots, g, G, A_(r2), D_(r2));
+			if (pass + 1 == npass && k + 1 < A->ncols)
+			{
+				contrib(k + 1, r2);
+				xch(r2 * reg, reg);                                  // X3 + X0 of the next column
+				colreg = r2;
+			}
+			else
+				xch(r2 * reg + cw, 2ull * m);                        // X3
+			adreg = r2;
+		}
+	if (ok) H(hipStreamSynchronize(st));
+	double const t1 = now_ms();
+	if (ok && ml)
+	{
+		H(hipMemcpy(a_out + p_lo, A_(adreg) + p_lo, (size_t) ml * 4, hipMemcpyDeviceToHost));
+		H(hipMemcpy(d_out + p_lo, D_(adreg) + p_lo, (size_t) ml * 4, hipMemcpyDeviceToHost));
+	}
+	(void) hipStreamDestroy(st);
+	if (pos_lo) *pos_lo = p_lo;
+	if (pos_hi) *pos_hi = p_hi;
+	if (ms) *ms = t1 - t0;
+	if (n_exchanges) *n_exchanges = nex;
+	return ok ? FSEQ_OK : FSEQ_E_HIP;
+}
+
+int fseq_debug_device_bytes(fseq_ctx *c, uint64_t *now, uint64_t *peak, int reset_peak)
+{
+	if (!c || !now || !peak) return FSEQ_E_ARG;
+	*now = c->alloc_total;
+	*peak = c->alloc_peak;
+	if (reset_peak) c->alloc_peak = c->alloc_total;
+	return FSEQ_OK;
+}
+
+} // extern "C"

@@ -1,7 +1,7 @@
 // fseq_api_input.hip -- the part of the C ABI (include/fseq.h) that takes the input rows in column chunks of bounded memory:
 // fseq_input_begin, fseq_input_chunk_columns, fseq_input_scan, fseq_input_columns, fseq_input_end and fseq_set_rows_streamed.
 //
-// fseq_set_rows (csrc/fseq_api.hip, upload_rows_device_impl) stages the m x n raw bytes on the device beside the packed
+// fseq_set_rows (csrc/fseq_path_setup.hip, upload_rows_device_impl) stages the m x n raw bytes on the device beside the packed
 // alignment; here the device holds the packed alignment and two staging halves.  Chunk i is copied into half i & 1 on the
 // context's second stream while the kernel of chunk i - 1 reads the other half on the first; an event per half and direction
 // orders them (copied: the kernel may read; used: the next copy may overwrite).  A call returns when its copies are done, not
@@ -104,7 +104,7 @@ int fix_table(fseq_ctx *c)
 		if ((in.present[b >> 5] >> (b & 31u)) & 1u) { table[b] = (uint8_t) code; c->code_to_byte[code] = (uint8_t) b; ++code; }
 		else table[b] = 0xFF;
 	c->sigma = sigma;
-	c->bsh = sigma <= 4 ? 2u : sigma <= 16 ? 1u : 0u;              // (as alloc_msa, csrc/fseq_api.hip)
+	c->bsh = sigma <= 4 ? 2u : sigma <= 16 ? 1u : 0u;              // (as alloc_msa, csrc/fseq_path_setup.hip)
 	uint32_t const col_bytes = (uint32_t) (((uint64_t) c->p.m + (1u << c->bsh) - 1u) >> c->bsh);
 	c->ld = ((size_t) col_bytes + 15) & ~size_t(15);
 	drop_alignment(c);

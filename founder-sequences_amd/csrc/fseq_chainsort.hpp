@@ -20,7 +20,7 @@
 // Everything but the histograms lives in the workgroup's workspace (L2-resident: a few MB).
 // Two forms of the step live here: pass2_step, one step on one workgroup (pass 2's k_chain_snap_grouped, which keeps its records
 // in a workspace of its own, pass2_ws_words), and the k_cm_* kernels, phase B's steps spread over the chip (launch_chain in
-// fseq_api.hip, the only streamed phase B).
+// fseq_path_pass1.hip, the only streamed phase B).
 #pragma once
 
 #include <type_traits>

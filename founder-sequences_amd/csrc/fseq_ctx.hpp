@@ -1,8 +1,9 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
-// shares: csrc/fseq_api.hip (the path: geometry, buffers, phases, sharding, the ABI's entry points) and
-// csrc/fseq_api_join.hip (the host joiners, their device front and the output writers) and csrc/fseq_api_match.hip (the rows
-// matched against founders) and csrc/fseq_api_identity.hip (identity columns dropped and put back) and
-// csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
+// shares: csrc/fseq_api.hip (the ABI's entry points) and csrc/fseq_api_debug.hip (the debug entry points, the row-sharded sweep),
+// the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _pass2: geometry, buffers, phases, sharding; what
+// only they share is csrc/fseq_path.hpp), csrc/fseq_api_join.hip (the host joiners, their device front and the output
+// writers), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
+// and put back) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
 #pragma once
 
 #include "../../include/fseq.h"
@@ -277,7 +278,7 @@ struct fseq_ctx {
 	size_t alloc_total = 0;
 	size_t alloc_peak = 0;                    // the most alloc_total has been (fseq_debug_device_bytes)
 	uint64_t mem_budget = 0;                  // fseq_set_memory_budget: 0 = whatever is free on the device
-	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_api.hip, plan_list_windows).  The buffer
+	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_path_pass1.hip, plan_list_windows).  The buffer
 	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent is rebased to (lo_w B - H) stride.
 	struct ListWindows {
 		uint64_t budget = 0;                  // bytes (0: every list held, the default)

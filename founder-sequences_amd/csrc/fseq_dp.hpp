@@ -802,7 +802,7 @@ __global__ __launch_bounds__(1024) void k_dp(
 
 	if (MODE == DP_SPEC && threadIdx.x == 0) { flags[0] = 0u; flags[1] = 0xFFFFFFFFu; }
 	// lowest DP entry a query of this lane reads: a rank of a sharded run holds the entries of the other ranks only for a
-	// window in front of its own (fseq_api.hip, run_dp_spec) and must know when a sweep looked below it
+	// window in front of its own (fseq_path_dp.hip, run_dp_spec) and must know when a sweep looked below it
 	uint32_t reach = 0xFFFFFFFFu;
 	if (PARTIAL && r_begin > 0u && !fresh)
 	{

@@ -1488,7 +1488,7 @@ static __global__ __launch_bounds__(64) void k_tb_chain(uint32_t const *__restri
 // The chain of one rank of a sharded run: from entry `start` (inside the rank's part [vlo, ..)) window by window until the
 // chain ends or leaves the part; the rank's output begins at offset off0 of the whole traceback.
 // count[0] = entries of this rank, count[2] = its windows; word[0] = 1 + the entry the chain continues at (0: it ended
-// here), word[1] = entries of this rank -- what the other ranks need to carry on (fseq_api.hip, follow_traceback_sharded)
+// here), word[1] = entries of this rank -- what the other ranks need to carry on (fseq_path_dp.hip, follow_traceback_sharded)
 static __global__ __launch_bounds__(64) void k_tb_chain_part(uint32_t const *__restrict__ exit_next, uint32_t const *__restrict__ exit_cnt, uint32_t start, uint32_t off0,
                                                       uint32_t vlo, uint2 *__restrict__ head, uint32_t max_windows, uint32_t *__restrict__ count, uint32_t *__restrict__ word)
 {

@@ -1,0 +1,165 @@
+// fseq_path.hpp -- what the units of the segmentation path share, and nothing else of the library needs: the state of one
+// long-path run, the aliases and ranges of its phases, the path's constants, and the functions that cross a unit.
+//   csrc/fseq_api.hip         the entry points of include/fseq.h, what a new input or knob makes a context forget
+//   csrc/fseq_api_debug.hip   the entry points of include/fseq_debug.h, the row-sharded conformance sweep
+//   csrc/fseq_path_setup.hip  pinned staging, geometry, work buffers, the row upload, the shard exchange
+//   csrc/fseq_path_dp.hip     the DP drivers, the tracebacks, the merge (the one unit that instantiates k_dp<>)
+//   csrc/fseq_path_pass1.hip  phases A - C, the list capacity, the reduced plan, the list windows, the attempt loop (the one unit
+//                             that instantiates k_colblock_stream<> / k_columns_stream<> and includes fseq_chainsort.hpp)
+//   csrc/fseq_path_pass2.hip  the boundary states at the merged boundaries
+// A kernel template is instantiated, and a header that defines plain __global__ kernels (fseq_dpspec.hpp, fseq_chainsort.hpp,
+// fseq_rowshard.hpp) is included, by one unit only: the others reach those kernels through the launchers declared here.  A unit
+// may include a header of templates for the sizes and schedules it computes on the host (dp_schedule, stream_lds_bytes, ...).
+// Everything a unit does not declare here is in its anonymous namespace.  Internal: none of this is exported.
+#pragma once
+
+#include "fseq_ctx.hpp"
+
+#ifdef FSEQ_WITH_ROCTX
+#include <rocprofiler-sdk-roctx/roctx.h>
+#endif
+
+namespace fseq { struct DpSchedule; }          // fseq_dp.hpp
+
+#pragma GCC visibility push(hidden)
+
+namespace fseq {
+
+// One range per phase (rocprofv3 --marker-trace shows them when the library is built against roctx).  The pushes and pops
+// are counted, so a test can tell that the ranges are there and balanced without a profiler (fseq_debug_ranges).
+extern std::atomic<uint64_t> g_range_pushes, g_range_pops;       // (csrc/fseq_path_pass1.hip)
+#ifdef FSEQ_WITH_ROCTX
+#define FSEQ_RANGE_PUSH(name) do { fseq::g_range_pushes.fetch_add(1, std::memory_order_relaxed); (void) roctxRangePushA(name); } while (0)
+#define FSEQ_RANGE_POP() do { fseq::g_range_pops.fetch_add(1, std::memory_order_relaxed); (void) roctxRangePop(); } while (0)
+#else
+#define FSEQ_RANGE_PUSH(name) do { fseq::g_range_pushes.fetch_add(1, std::memory_order_relaxed); } while (0)
+#define FSEQ_RANGE_POP() do { fseq::g_range_pops.fetch_add(1, std::memory_order_relaxed); } while (0)
+#endif
+
+// a phase's range: popped where the phase ends -- or where the function leaves early (a retry with a larger list capacity, an
+// attempt that runs again, an error), so that pushes and pops stay balanced on every path
+struct RangeScope {
+	bool open = true;
+	explicit RangeScope(char const *name) { FSEQ_RANGE_PUSH(name); (void) name; }
+	void end() { if (open) { FSEQ_RANGE_POP(); open = false; } }
+	~RangeScope() { end(); }
+	RangeScope(RangeScope const &) = delete;
+	RangeScope &operator=(RangeScope const &) = delete;
+};
+
+constexpr size_t LDS_LIMIT = 160 * 1024;
+constexpr uint64_t STREAM_BLOCK_TARGET_ALL_ROWS = 1600;   // columns per block the streamed regime aims for (prepare_geometry / block_geometry) ...
+// [r5] ... and when phase C runs on the blocks' representatives: a block of ~800 columns of BASELINE C4 has ~6,600 of them, and
+// the ~10,700 of a block in which the founders recombine still fit the largest configuration (11,264)
+constexpr uint64_t STREAM_BLOCK_TARGET_REDUCED = 800;
+constexpr uint8_t RED_FORCE_FULL = 1, RED_FORCE_WIDE = 2;    // fseq_ctx::red_force_full[b]
+constexpr size_t RED_SIDE_STREAMS = 3;                    // side streams the reduced configurations' launches may use (red_launch_all)
+#define STREAM_BLOCK_TARGET (c->tune.no_reduced ? STREAM_BLOCK_TARGET_ALL_ROWS : STREAM_BLOCK_TARGET_REDUCED)
+#ifndef FSEQ_X_FLOOR_VALUE
+#define FSEQ_X_FLOOR_VALUE 63u
+#endif
+constexpr uint32_t FSEQ_X_FLOOR = FSEQ_X_FLOOR_VALUE;   // smallest per-column list capacity tried (the estimate and the retries raise it)
+
+// what the phases of one long-path run share (run_long_path)
+struct LongRun {
+	uint32_t X = 0, retries = 0;
+	double ms_c = 0, ms_dp = 0, ms_host = 0, ms_p2 = 0;
+	uint64_t pass2_cells = 0;
+	bool keyspace = false;
+	bool tree_ran = false;                   // phase A ran the key-space tree at all (else: the column sweep did every block, as last time)
+	bool tree_alone = false;                 // phase A ran the key-space tree without the column sweep behind it (no block was given up last time)
+	bool trie_ran = false, trie_alone = false;   // ... the trie over 16-column words (streamed rows); ... without the key-space tree behind it
+	bool redo = false;                       // [r5] lists of some blocks could not be proven on their representatives: the attempt runs again, those blocks on all rows
+	uint32_t redone = 0;
+	bool range_ab_open = false;              // the roctx range of phases A + B spans two functions
+};
+
+// the aliases every phase uses
+#define FSEQ_LONG_LOCALS(c)                                                                           \
+	fseq_params const &p = (c)->p;                                                                    \
+	uint32_t const m = p.m;                                                                           \
+	uint64_t const n = p.n;                                                                           \
+	uint64_t const L = p.segment_length;                                                              \
+	hipStream_t st = (c)->stream;                                                                     \
+	KernelSet const &ks = (c)->ks;                                                                    \
+	Shard const &sh = (c)->sh;                                                                        \
+	bool const sharded = sh.on;                                                                       \
+	uint32_t const b_lo = sharded ? sh.b_lo : 0u, b_hi = sharded ? sh.b_hi : (c)->nblocks;            \
+	uint32_t const my_blocks = b_hi - b_lo;                                                           \
+	int rc = FSEQ_OK;                                                                                 \
+	(void) m; (void) n; (void) L; (void) st; (void) ks; (void) sharded; (void) b_lo; (void) my_blocks; (void) rc
+
+// columns this context holds: all of them, or the rank's share of a sharded run
+inline uint64_t held_lo(fseq_ctx const *c) { return c->sh.on ? c->sh.c_lo : 0; }
+inline uint64_t held_hi(fseq_ctx const *c) { return c->sh.on ? c->sh.c_end : c->p.n; }
+
+// ---- csrc/fseq_api.hip
+void forget_run_history(fseq_ctx *c);
+
+// ---- csrc/fseq_path_setup.hip
+// Pinned host staging.  A copy between the device and pageable host memory is staged by the runtime -- one blocking round
+// trip of 20-50 microseconds each, and a step had a dozen of them (flags, counts, the traceback, thresholds: a fifth of a
+// BASELINE C2 step).  pin_reserve(bytes) opens a stage (what the previous one handed out is dead), pin_take carves it.
+int pin_reserve(fseq_ctx *c, size_t bytes);
+template <typename U>
+U *pin_take(fseq_ctx *c, size_t count)
+{
+	size_t const at = (c->pin_used + 15) & ~size_t(15);
+	c->pin_used = at + count * sizeof(U);
+	return c->pin_used <= c->pin_cap ? reinterpret_cast<U *>(c->h_pin + at) : nullptr;      // (nullptr: the stage was reserved too small -- a bug)
+}
+void free_msa(fseq_ctx *c);
+int alloc_msa(fseq_ctx *c);
+void block_geometry(fseq_ctx *c);
+int prepare_geometry(fseq_ctx *c);
+int ensure_work_buffers(fseq_ctx *c, uint32_t X, bool want_ss = true);
+void free_work(fseq_ctx *c);
+int upload_rows_device(fseq_ctx *c, uint8_t const *const *rows);
+int set_alphabet_and_upload(fseq_ctx *c, uint8_t const *base, size_t rs, size_t cs);
+int shard_exchange(fseq_ctx *c, uint64_t words, int op);
+void shard_post_failure(fseq_ctx *c, int code);
+
+// ---- csrc/fseq_path_dp.hip
+// The chunk plan of the speculative DP (fseq_dpspec.hpp): chunk k runs the rounds [r0[k], r0[k + 1]) (the last one
+// also the drain round and the final cell); no chunks = use the serial kernel.  Sharded: a round belongs to the
+// rank that owns its first column; every rank cuts its own rounds into chunks and every rank computes the same table.
+struct SpecPlan {
+	std::vector<uint32_t> r0;                // nchunks + 1 entries
+	uint32_t mine_lo = 0, mine_hi = 0;       // my chunks
+	std::vector<uint32_t> rank_lo;           // sharded: rank g runs the chunks [rank_lo[g], rank_lo[g + 1]) (active + 1 entries)
+	uint32_t nchunks() const { return r0.empty() ? 0u : (uint32_t) r0.size() - 1u; }
+};
+SpecPlan spec_plan(fseq_ctx *c, DpSchedule const &S);
+bool shard_dp_plan_ok(fseq_ctx *c);          // fseq_set_shard: every rank that owns blocks owns DP rounds
+int dp_spec_reset(fseq_ctx *c, SpecPlan const &P, hipStream_t s);
+int run_dp_spec(fseq_ctx *c, DpSchedule const &S, SpecPlan const &P, hipStream_t st, uint32_t *overflow, uint32_t *sweeps_out, bool reset_done = false);
+int prepare_dp_kernels(fseq_ctx *c);         // prepare_geometry: the LDS of every k_dp<>
+// the serial DP over the rounds [r_lo, r_hi): k_dp<DP_WHOLE> or k_dp<DP_PARTIAL> (fseq_dp.hpp)
+void launch_dp_serial(fseq_ctx *c, int mode, hipStream_t st, uint32_t r_lo, uint32_t r_hi);
+int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out);
+
+// ---- csrc/fseq_path_pass1.hip
+uint32_t scan_keyed(fseq_ctx const *c);
+int prepare_stream_kernels(fseq_ctx *c, size_t lds);  // prepare_geometry: the LDS of the streamed kernels this unit instantiates ...
+int prepare_stream2_prologue(fseq_ctx *c);            // ... and of the static kernels it launches (an attribute set on another unit's
+int prepare_blockkeys_stream(fseq_ctx *c);            //     copy of a static kernel would not reach the one launched)
+size_t chain_hist_words(uint32_t m);                 // digit histogram words of one chain of the streamed phase B (fseq_chainsort.hpp)
+// the streamed replay sweep of pass 2 (k_colblock_stream<MODE_SNAP>): the groups [0, groups) of d_grp / d_src, as many per
+// launch as the workspace holds
+void launch_replay_stream(fseq_ctx *c, size_t groups, uint64_t const *d_rb, uint2 const *d_grp, uint64_t const *d_src, uint32_t *out_a, uint32_t *out_d,
+                          uint32_t const *ss_a, uint32_t const *ss_d, uint32_t ss_pack);
+int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp);       // pass 2 behind the reduced phase C, streamed rows: the chain steps
+void red_fill_args(fseq_ctx *c, RedArgs &RA);
+struct RedLaunch { int config; uint32_t first, count; };
+int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, uint32_t const *blocks, uint32_t const *wg_tasks, uint2 *ent, uint4 *hdr, uint32_t X, uint32_t stride);
+void set_list_window(fseq_ctx *c, uint32_t lo_w);
+int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi);
+int run_long_path(fseq_ctx *c, fseq_result *res);
+int run_short_path(fseq_ctx *c, fseq_result *res);
+
+// ---- csrc/fseq_path_pass2.hip
+int long_pass2(fseq_ctx *c, LongRun &R);
+
+} // namespace fseq
+
+#pragma GCC visibility pop

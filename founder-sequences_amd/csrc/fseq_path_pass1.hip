@@ -1,0 +1,1243 @@
+// fseq_path_pass1.hip -- the segmentation path, pass 1: phase A (the key blocks), phase B (the boundary states), the list
+// capacity, phase C on the blocks' representatives (the plan of an attempt) or on all rows, the list windows, one attempt and
+// the loop over attempts; the short path.  The one unit that instantiates k_colblock_stream<> and k_columns_stream<> and that
+// includes fseq_chainsort.hpp: pass 2 replays columns and takes its streamed chain steps through the launchers here.
+// (The units of the path and what crosses them: fseq_path.hpp.)
+#include "fseq_path.hpp"
+#include "fseq_kernels.hpp"
+#include "fseq_dp.hpp"           // the round schedule (list windows, the attempt)
+#include "fseq_stream.hpp"
+#include "fseq_stream2.hpp"
+#include "fseq_chainsort.hpp"
+#include "fseq_blockkeys.hpp"
+#include "fseq_blocktrie.hpp"
+
+namespace fseq {
+
+std::atomic<uint64_t> g_range_pushes{0}, g_range_pops{0};
+
+// ---- launches: LDS-resident kernels, or their HBM-streamed counterparts for large m
+// grid workgroups = the blocks starting at column col0, col0 + B, ...; rank / keyd / nkeys point at the first of them
+// phase B and pass 2 work on absolute divergences (column numbers <= n): their partition steps scan keys while n fits
+// the configuration's key shift (FSEQ_PLAIN_SCAN: never)
+uint32_t scan_keyed(fseq_ctx const *c)
+{
+	if (c->use_stream || c->tune.plain_scan) return 0u;
+	return (c->p.n < (1ull << c->ks.scan_shift) && !c->tune.occurrence_keys) ? 1u : c->p.n < (1ull << 25) ? 2u : 0u;       // row-count keys, occurrence keys, has-based scan
+}
+
+namespace {
+
+// streamed rows: occurrence keys while every column number fits 25 bits (FSEQ_PLAIN_SCAN: the has-based scan)
+bool stream_keyed(fseq_ctx const *c) { return c->p.n < (1ull << 25) && !c->tune.plain_scan; }
+
+// one launch of the streamed column sweep, the context's configuration and workspace in front of what the mode takes
+// (MODE_RANK, phase A: the key blocks out, bstate_a the per-block filter; MODE_SNAP, pass 2: the states at the boundaries task_rb out)
+template <int MODE>
+void launch_colblock_stream(fseq_ctx *c, uint32_t grid, uint32_t B, uint32_t nblocks, uint32_t *rank, uint32_t *keyd, uint32_t *nkeys, uint32_t const *bstate_a, uint32_t const *bstate_d,
+                            uint64_t const *task_rb, uint2 const *task_grp, uint32_t *snap_a, uint32_t *snap_d, uint64_t const *task_src, uint32_t snap_stride,
+                            uint32_t const *ss_a, uint32_t const *ss_d, uint64_t col0, uint32_t ss_pack)
+{
+	fseq_params const &p = c->p;
+	hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE, true> : k_colblock_stream<MODE, false>), dim3(grid), dim3(ST), stream_lds_bytes(sym_bytes(p.m, c->bsh), c->stream_staged), c->stream, c->d_msa, c->ld, p.m, p.n, B, nblocks,
+	                   c->npass, c->bsh, c->d_ws.base, (uint32_t) c->stream_staged, rank, keyd, nkeys, bstate_a, bstate_d, task_rb, task_grp, snap_a, snap_d, task_src, snap_stride, ss_a, ss_d, col0, ss_pack);
+}
+
+// only: per-block filter (blocks whose word is zero are skipped), or nullptr
+void launch_rank(fseq_ctx *c, uint32_t grid, uint32_t B, uint32_t nblocks, uint32_t *rank, uint32_t *keyd, uint32_t *nkeys, uint64_t col0 = 0, uint32_t const *only = nullptr)
+{
+	fseq_params const &p = c->p;
+	if (!grid) return;
+	if (c->use_stream)
+		launch_colblock_stream<MODE_RANK>(c, grid, B, nblocks, rank, keyd, nkeys, only, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, col0, 0u);
+	else
+		c->ks.rank(c->stream, grid, c->ks.lds_colblock, c->d_msa, c->ld, p.m, p.n, B, nblocks, c->npass, c->bsh, rank, keyd, nkeys, col0, only);
+}
+
+} // namespace
+
+void launch_replay_stream(fseq_ctx *c, size_t groups, uint64_t const *d_rb, uint2 const *d_grp, uint64_t const *d_src, uint32_t *out_a, uint32_t *out_d,
+                          uint32_t const *ss_a, uint32_t const *ss_d, uint32_t ss_pack)
+{
+	// the streamed sweep needs 4m workspace words per workgroup: as many groups per launch as d_ws holds
+	size_t const cap = std::max<size_t>(1, c->d_ws.cap / (4 * (size_t) c->p.m));
+	for (size_t g0 = 0; g0 < groups; g0 += cap)
+		launch_colblock_stream<MODE_SNAP>(c, (uint32_t) std::min(cap, groups - g0), c->B, c->nblocks, nullptr, nullptr, nullptr, c->d_bstate_a, c->d_bstate_d, d_rb, d_grp + g0,
+		                                  out_a, out_d, d_src + g0, c->snap_stride, ss_a, ss_d, 0, ss_pack);
+}
+
+namespace {
+
+// grid chains grp0 .. grp0 + grid - 1, chain g over the key blocks [g * G, min(nb_total, (g + 1) * G))
+void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t const *keyd, uint32_t const *nkeys, uint32_t nb_total, uint32_t G,
+                  uint64_t cols_per_block, uint32_t const *start_a, uint32_t const *start_d, uint32_t *out_a, uint32_t *out_d,
+                  uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t grp0 = 0)
+{
+	if (!grid) return;
+	// streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp), every sweep of a step a launch
+	// over (parts) x (chains): a chain of G blocks is G rounds of them.  ensure_work_buffers sized d_ws and d_cshist for the
+	// widest launch of phase B (a chain per chain_fan blocks, plus one, in d_cshist; chainsort_ws_words(m)
+	// <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
+	if (c->use_stream)
+	{
+		uint32_t const m = c->p.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
+		ChainMultiArgs A;
+		A.rank = rank; A.keyd = keyd; A.nkeys = nkeys; A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block;
+		A.ws = c->d_ws.base; A.hist = c->d_cshist; A.start_a = start_a; A.start_d = start_d; A.out_state_a = out_a; A.out_state_d = out_d;
+		A.out_rank = out_rank; A.out_keyd = out_keyd; A.out_nkeys = out_nkeys; A.grp0 = grp0; A.step = 0; A.pass = 0;
+		A.nchains = grid;
+		uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
+		dim3 const by_row((m + CM_WG - 1u) / CM_WG, grid_y), by_part((nparts + CM_WG / WAVE - 1u) / (CM_WG / WAVE), grid_y);
+		hipLaunchKernelGGL(k_cm_init, by_row, dim3(CM_WG), 0, c->stream, A);
+		for (uint32_t s_ = 0; s_ < G; ++s_)
+		{
+			A.step = s_;
+			for (uint32_t ps = 0; ps < npass; ++ps)
+			{
+				A.pass = ps;
+				hipLaunchKernelGGL(k_cm_count, by_part, dim3(CM_WG), 0, c->stream, A);
+				hipLaunchKernelGGL(k_cm_offsets, dim3(grid), dim3(ST), 0, c->stream, A);
+				hipLaunchKernelGGL(k_cm_scatter, by_part, dim3(CM_WG), 0, c->stream, A);
+			}
+			hipLaunchKernelGGL(k_cm_output, by_row, dim3(CM_WG), 0, c->stream, A);
+		}
+		if (out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), c->stream, A, G);
+	}
+	else
+		c->ks.chain(c->stream, grid, c->ks.lds_chain, rank, keyd, nkeys, c->p.m, nb_total, G, cols_per_block, start_a, start_d, out_a, out_d,
+		            out_rank, out_keyd, out_nkeys, grp0, scan_keyed(c));
+}
+
+} // namespace
+
+int prepare_stream_kernels(fseq_ctx *c, size_t lds)
+{
+	HIP_TRY(c, allow_lds(k_colblock_stream<MODE_RANK>, lds));
+	HIP_TRY(c, allow_lds(k_colblock_stream<MODE_SNAP>, lds));
+	HIP_TRY(c, allow_lds(k_colblock_stream<MODE_RANK, true>, lds));
+	HIP_TRY(c, allow_lds(k_colblock_stream<MODE_SNAP, true>, lds));
+	HIP_TRY(c, allow_lds(k_columns_stream<19>, lds));
+	HIP_TRY(c, allow_lds(k_columns_stream<0>, lds));
+	HIP_TRY(c, allow_lds(k_chain_snap_grouped, pass2_lds_bytes()));
+	HIP_TRY(c, allow_lds(k_cm_emit, stream_lds_bytes(0, false)));
+	return FSEQ_OK;
+}
+int prepare_stream2_prologue(fseq_ctx *c)
+{
+	HIP_TRY(c, allow_lds(k_columns_stream2_prologue, stream_lds_bytes(0, true)));
+	return FSEQ_OK;
+}
+int prepare_blockkeys_stream(fseq_ctx *c)
+{
+	HIP_TRY(c, allow_lds(k_blockkeys_stream, c->bk_lds));
+	return FSEQ_OK;
+}
+size_t chain_hist_words(uint32_t m) { return (size_t) chainmulti_parts(m) * CS_BINS; }
+
+// streamed rows: pass 2's chain step as a radix sort + range maxima in a workspace per workgroup (fseq_chainsort.hpp), a block's
+// tasks on one workgroup, the ngrp groups of d_red_p2grp taken from the counter behind them
+int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp)
+{
+	uint32_t const m = c->p.m;
+	hipStream_t st = c->stream;
+	if (c->red_cap > P2_CLS_CAP) return fail(c, FSEQ_E_UNSUPPORTED, "pass 2: more representatives a block than the class table in LDS holds");
+	int ncu = 0;
+	(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
+	size_t const fit = c->d_ws.cap / pass2_ws_words(m);
+	uint32_t const grid = (uint32_t) std::min<size_t>(std::min<size_t>(ngrp, fit), (size_t) std::max(ncu, 1) * 2u);
+	if (!grid) return fail(c, FSEQ_E_OOM, "pass 2: the workspace holds no chain step");
+	hipLaunchKernelGGL(k_chain_snap_grouped, dim3(grid), dim3(ST), pass2_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
+	                   c->d_red_headd, c->d_red_ncls, c->red_cap, c->d_red_p2grp.as<uint2 const>(), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
+	                   c->d_snap_a, c->d_snap_d, c->d_ws.base);
+	return FSEQ_OK;
+}
+
+namespace {
+
+// diagnostic ("ABC" in FSEQ_SYNC_PHASES): synchronise behind a phase, so that a fault shows up at the phase that caused it
+bool sync_at(fseq_ctx const *c, char ph) { return c->tune.sync_phases.find(ph) != std::string::npos; }
+
+// ---- phase A: the key blocks of my column blocks (independent of the list capacity)
+int long_phase_a(fseq_ctx *c, LongRun &R)
+{
+	FSEQ_LONG_LOCALS(c);
+	// 4-bit symbols, LDS-resident rows: the codes present in every column I hold, once per input (k_columns takes a column with at
+	// most four of them in one digit pass)
+	if (c->bsh == 1u && c->npass == 2u && !c->use_stream && !c->tune.no_dense_columns && !c->colmask_ready && held_hi(c) > held_lo(c)
+	    && c->d_msa_own && (c->ld & 3u) == 0)                  // (own columns: padded past their last byte, whole words can be read)
+	{
+		uint64_t const lo = held_lo(c), hi = held_hi(c);
+		if ((rc = c->d_colmask.alloc_range(c, (size_t) lo, (size_t) hi, 1))) return rc;
+		HIP_TRY(c, hipMemsetAsync(c->d_flags + 67, 0, 4, st));
+		hipLaunchKernelGGL(k_column_presence, dim3((uint32_t) std::min<uint64_t>(hi - lo, 8192)), dim3(256), 0, st, c->d_msa, c->ld, sym_bytes(m, c->bsh), lo, hi, c->d_colmask,
+		                   c->d_flags + 67);
+		// (once per input: one column in twenty with at most four codes, and phase C is the kernel with the one-pass branch)
+		uint32_t n_dense = 0;
+		HIP_TRY(c, hipMemcpyAsync(&n_dense, c->d_flags + 67, 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipStreamSynchronize(st));
+		c->colmask_use = (uint64_t) n_dense * 20u >= hi - lo;
+		c->colmask_ready = true;
+	}
+	HIP_TRY(c, hipEventRecord(c->ev[0], st));
+	progress(c, FSEQ_STAGE_TRACEBACK, 0, n);
+	FSEQ_RANGE_PUSH("fseq pass 1: phases A + B (block keys, boundary states)");
+	R.range_ab_open = true;                  // (popped in long_phase_b; run_long_path pops it when a phase fails in between)
+	bool const keyspace = R.keyspace = c->bk_cap_words && my_blocks && !c->tune.phase_a_classic;
+	// The key-space tree hands the blocks whose merges would slice past their budget to the column sweep (fseq_blockkeys.hpp,
+	// BK_ABORT): per-block flags, the sweep launched over my blocks with the flags as its filter.  What the last run on this
+	// input saw decides what is launched now (the input has not changed, so neither has the outcome): no block given up ->
+	// the tree alone; most of them -> the sweep alone; else both.  FSEQ_BLOCKKEYS_CAP (tests of the slices): the tree slices
+	// as often as it takes.
+	bool const limited = keyspace && !c->tune.blockkeys_cap;
+	bool const tree = keyspace && !(limited && c->bk_given_up >= 0 && 2u * (uint32_t) c->bk_given_up > my_blocks);
+	bool const sweep_after = limited && !(tree && c->bk_given_up == 0);
+	R.tree_alone = tree && limited && !sweep_after;
+	R.tree_ran = tree;
+	uint32_t *todo = nullptr;
+	if (limited)
+	{
+		if ((rc = c->d_todo.ensure(c, my_blocks))) return rc;
+		todo = c->d_todo;
+		HIP_TRY(c, hipMemsetAsync(todo, tree ? 0 : 0x01, (size_t) my_blocks * 4, st));     // (no tree: every block is the sweep's)
+	}
+	if (keyspace) HIP_TRY(c, hipMemsetAsync(c->d_flags + 64, 0, 12, st));
+	// The trie over 32-bit group words first (fseq_blocktrie.hpp) -- it reads the block once and ranks only its distinct keys --
+	// and the key-space tree for the blocks it gives up (too many distinct keys for its tables).  As with the tree and the
+	// sweep, what the last run on this input saw decides what is launched: nothing given up -> the trie alone; most blocks ->
+	// no trie.  The tests of the tree's slices (FSEQ_BLOCKKEYS_CAP, _NO_LIMIT) keep the tree.
+	uint32_t const bt_bits = 8u >> c->bsh, bt_T = blocktrie_threads(m, c->use_stream);
+	// (LDS-resident rows: from 6,145 rows on -- BASELINE C5's 10,000: phase A 7.3 -> 5.9 ms; on C3's 2,504 rows a level of the trie is
+	// a dozen barriers for 157 busy threads and the tree is as fast, 1.31 against 1.36 ms; FSEQ_BLOCKTRIE_ALWAYS: tests)
+	bool const trie = tree && limited && (uint64_t) m <= (uint64_t) (32u / bt_bits) * bt_T * 32u && c->B < 65536u && !c->tune.no_blocktrie
+	                  && (c->use_stream || m > 12u * 512u || c->tune.blocktrie_always)
+	                  && (c->ld & 3u) == 0 && (reinterpret_cast<uintptr_t>(c->d_msa) & 3u) == 0
+	                  && !(c->bt_given_up >= 0 && 2u * (uint32_t) c->bt_given_up > my_blocks);
+	bool const tree_after = tree && !(trie && c->bt_given_up == 0);
+	R.trie_ran = trie;
+	R.trie_alone = trie && !tree_after;
+	uint32_t const *only = nullptr;
+	if (trie)
+	{
+		int ncu = 0;
+		(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
+		uint32_t const per_cu = (uint32_t) std::max<size_t>(1, std::min<size_t>(2048u / bt_T, (160u * 1024u) / blocktrie_lds(bt_T)));
+		uint32_t const groups = std::min<uint32_t>(my_blocks, (uint32_t) std::max(1, ncu) * per_cu);
+		size_t const per = (blocktrie_ws_words(m, c->B, bt_bits, bt_T) + 15) & ~size_t(15);
+		if ((rc = c->d_btws.ensure(c, per * groups))) return rc;
+		if ((rc = c->d_only.ensure(c, my_blocks))) return rc;
+		HIP_TRY(c, hipMemsetAsync(c->d_only, 0, (size_t) my_blocks * 4, st));
+		HIP_TRY(c, launch_blocktrie(bt_bits, bt_T, st, groups, c->d_msa, c->ld, m, n, c->B, my_blocks,
+		                            c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
+		                            c->d_btws, per, c->d_flags + 66, c->d_only));
+		only = c->d_only;
+	}
+	if (tree_after && c->use_stream)
+	{
+		// phase A in key space, streamed rows: one workgroup per CU with its own workspace, blocks round-robin
+		int ncu = 0;
+		(void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device);
+		uint32_t const groups = std::min<uint32_t>(my_blocks, (uint32_t) std::max(1, ncu));
+		size_t const per = (blockkeys_stream_ws_words(m, c->B, c->bsh) + 15) & ~size_t(15);
+		if ((rc = c->d_bkws.ensure(c, per * groups))) return rc;
+		hipLaunchKernelGGL(k_blockkeys_stream, dim3(groups), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, n, c->B, c->bsh, my_blocks,
+		                   c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
+		                   c->d_bkws, per, c->bk_cap_words, c->d_flags + 64, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), todo, only);
+	}
+	else if (tree_after)
+	{
+		// phase A in key space (fseq_blockkeys.hpp)
+		size_t const per = (blockkeys_scratch_halfwords(m, c->B, c->bsh) + 7) & ~size_t(7);
+		if (c->bk_per_block != per) c->d_bk.release(c);
+		if ((rc = c->d_bk.ensure(c, per * my_blocks))) return rc;
+		c->bk_per_block = per;
+		launch_blockkeys(c->bk_T, st, my_blocks, c->bk_lds, c->d_msa, c->ld, m, n, c->B, c->bsh, c->d_rank + (size_t) b_lo * m,
+		                 c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B, c->d_bk, per, c->bk_cap_words, c->d_flags + 64, todo, only);
+	}
+	if (!keyspace || sweep_after)
+		launch_rank(c, my_blocks, c->B, c->nblocks, c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
+		            keyspace && tree ? todo : nullptr);
+	HIP_TRY(c, hipEventRecord(c->ev[1], st));
+	if (sharded && c->tune.inject_failure_rank >= 0 && (uint32_t) c->tune.inject_failure_rank == sh.rank)
+		return fail(c, FSEQ_E_OOM, "injected failure (FSEQ_INJECT_FAILURE_RANK)");
+	if (sync_at(c, 'A')) { fprintf(stderr, "[fseq] phase A queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase A done\n"); }
+	if (c->tune.check_phase_a)
+	{
+		// diagnostic: the key blocks must be well-formed before anything indexes with them (ranks < nkeys <= m, the
+		// divergence in front of a key inside the block's columns)
+		HIP_TRY(c, hipStreamSynchronize(st));
+		std::vector<uint32_t> rk(m), kd(m);
+		for (uint32_t b = b_lo; b < b_hi; ++b)
+		{
+			uint32_t nk = 0;
+			HIP_TRY(c, hipMemcpy(&nk, c->d_nkeys + b, 4, hipMemcpyDeviceToHost));
+			HIP_TRY(c, hipMemcpy(rk.data(), c->d_rank + (size_t) b * m, (size_t) m * 4, hipMemcpyDeviceToHost));
+			HIP_TRY(c, hipMemcpy(kd.data(), c->d_keyd + (size_t) b * m, (size_t) m * 4, hipMemcpyDeviceToHost));
+			uint64_t const k0 = (uint64_t) b * c->B, k1 = std::min<uint64_t>(n, k0 + c->B);
+			uint32_t bad_r = 0, bad_k = 0;
+			for (uint32_t i = 0; i < m; ++i) if (rk[i] >= nk) ++bad_r;
+			for (uint32_t j = 0; j < nk && j < m; ++j) if (kd[j] <= k0 || kd[j] > k1) ++bad_k;
+			if (nk == 0 || nk > m || bad_r || bad_k)
+			{
+				char what[200];
+				snprintf(what, sizeof(what), "phase A check: block %u has %u keys (m = %u), %u ranks out of range, %u key divergences outside (%llu, %llu]",
+				         b, nk, m, bad_r, bad_k, (unsigned long long) k0, (unsigned long long) k1);
+				return fail(c, FSEQ_E_HIP, what);
+			}
+		}
+	}
+	return FSEQ_OK;
+}
+
+// ---- phase B: the exact boundary state of every block
+int long_phase_b(fseq_ctx *c, LongRun &R)
+{
+	FSEQ_LONG_LOCALS(c);
+	(void) R;
+	auto rank_of = [&](size_t i) { return i ? c->levels[i - 1].rank : c->d_rank; };
+	auto keyd_of = [&](size_t i) { return i ? c->levels[i - 1].keyd : c->d_keyd; };
+	auto nkeys_of = [&](size_t i) { return i ? c->levels[i - 1].nkeys : c->d_nkeys; };
+	auto sa_of = [&](size_t i) { return i ? c->levels[i - 1].state_a : c->d_bstate_a; };
+	auto sd_of = [&](size_t i) { return i ? c->levels[i - 1].state_d : c->d_bstate_d; };
+	auto count_of = [&](size_t i) { return i ? c->levels[i - 1].count : c->nblocks; };
+	auto cols_of = [&](size_t i) { return i ? c->levels[i - 1].cols : (uint64_t) c->B; };
+	if (!sharded)
+	{
+		// phase B: up the levels -- compose groups of G key blocks of a level into one key block of the next
+		// (parallel, from the identity) --, chain the few key blocks of the top level (one workgroup), down the levels --
+		// expand every group from the boundary state the level above gave it (parallel)
+		uint32_t const G = c->chain_fan;
+		size_t const top = c->levels.size();
+		for (size_t i = 1; i <= top; ++i)
+			launch_chain(c, count_of(i), rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), G, cols_of(i - 1), nullptr, nullptr,
+			             nullptr, nullptr, rank_of(i), keyd_of(i), nkeys_of(i));
+		launch_chain(c, 1, rank_of(top), keyd_of(top), nkeys_of(top), count_of(top), count_of(top), cols_of(top), nullptr, nullptr,
+		             sa_of(top), sd_of(top), nullptr, nullptr, nullptr);
+		for (size_t i = top; i-- > 0;)
+			launch_chain(c, count_of(i + 1), rank_of(i), keyd_of(i), nkeys_of(i), count_of(i), G, cols_of(i), sa_of(i + 1), sd_of(i + 1),
+			             sa_of(i), sd_of(i), nullptr, nullptr, nullptr);
+	}
+	else
+	{
+		// Sharded phase B: rank r is hyper-block r.  Up the levels over my own block range (fan F, as on one GPU), my
+		// last composites into my hyper key block, exchange the W hyper key blocks (the one collective of pass 1's column
+		// work), chain them (every rank, same result), then down again from the state in front of my hyper-block.
+		uint32_t const F = c->chain_fan, NH = c->n_hyper, K = c->shard_k, Q = c->shard_q;
+		bool const have = sh.rank < NH;
+		// my items of level i: [lo_i, hi_i) (rank boundaries are multiples of F^K blocks)
+		std::vector<uint32_t> lo(K + 1), hi(K + 1);
+		lo[0] = b_lo; hi[0] = b_hi;
+		for (uint32_t i = 1; i <= K; ++i) { lo[i] = lo[i - 1] / F; hi[i] = (hi[i - 1] + F - 1) / F; }
+		for (uint32_t i = 1; have && i <= K; ++i)
+			launch_chain(c, hi[i] - lo[i], rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), F, cols_of(i - 1), nullptr, nullptr,
+			             nullptr, nullptr, rank_of(i), keyd_of(i), nkeys_of(i), lo[i]);
+		if (have)
+			launch_chain(c, 1, rank_of(K), keyd_of(K), nkeys_of(K), count_of(K), Q, cols_of(K), nullptr, nullptr,
+			             nullptr, nullptr, c->d_hrank, c->d_hkeyd, c->d_hnkeys, sh.rank);
+		{
+			// xbuf: [hrank NH x m][hkeyd NH x m][hnkeys NH]
+			size_t const w = (size_t) NH * m;
+			HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, (2 * w + NH) * 4, st));
+			if (have)
+			{
+				HIP_TRY(c, hipMemcpyAsync(sh.xbuf + (size_t) sh.rank * m, c->d_hrank + (size_t) sh.rank * m, (size_t) m * 4, hipMemcpyDeviceToDevice, st));
+				HIP_TRY(c, hipMemcpyAsync(sh.xbuf + w + (size_t) sh.rank * m, c->d_hkeyd + (size_t) sh.rank * m, (size_t) m * 4, hipMemcpyDeviceToDevice, st));
+				HIP_TRY(c, hipMemcpyAsync(sh.xbuf + 2 * w + sh.rank, c->d_hnkeys + sh.rank, 4, hipMemcpyDeviceToDevice, st));
+			}
+			if ((rc = shard_exchange(c, 2 * w + NH, 0))) return rc;
+			HIP_TRY(c, hipMemcpyAsync(c->d_hrank, sh.xbuf, w * 4, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(c, hipMemcpyAsync(c->d_hkeyd, sh.xbuf + w, w * 4, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(c, hipMemcpyAsync(c->d_hnkeys, sh.xbuf + 2 * w, (size_t) NH * 4, hipMemcpyDeviceToDevice, st));
+		}
+		launch_chain(c, 1, c->d_hrank, c->d_hkeyd, c->d_hnkeys, NH, NH, (uint64_t) sh.bpr * c->B, nullptr, nullptr,
+		             c->d_hstate_a, c->d_hstate_d, nullptr, nullptr, nullptr);
+		if (have)
+		{
+			launch_chain(c, 1, rank_of(K), keyd_of(K), nkeys_of(K), count_of(K), Q, cols_of(K), c->d_hstate_a, c->d_hstate_d,
+			             sa_of(K), sd_of(K), nullptr, nullptr, nullptr, sh.rank);
+			for (uint32_t i = K; i >= 1; --i)
+				launch_chain(c, hi[i] - lo[i], rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), F, cols_of(i - 1), sa_of(i), sd_of(i),
+				             sa_of(i - 1), sd_of(i - 1), nullptr, nullptr, nullptr, lo[i]);
+			// the state behind my last block = in front of the next rank's hyper-block (or behind the whole alignment,
+			// which the expansion has written itself): my halo block starts from it
+			if (b_hi < c->nblocks)
+			{
+				HIP_TRY(c, hipMemcpyAsync(c->d_bstate_a + (size_t) b_hi * m, c->d_hstate_a + (size_t) (sh.rank + 1u) * m, (size_t) m * 4, hipMemcpyDeviceToDevice, st));
+				HIP_TRY(c, hipMemcpyAsync(c->d_bstate_d + (size_t) b_hi * m, c->d_hstate_d + (size_t) (sh.rank + 1u) * m, (size_t) m * 4, hipMemcpyDeviceToDevice, st));
+			}
+		}
+	}
+	HIP_TRY(c, hipEventRecord(c->ev[2], st));
+	HIP_TRY(c, hipGetLastError());
+	FSEQ_RANGE_POP();
+	R.range_ab_open = false;
+	progress(c, FSEQ_STAGE_TRACEBACK, n / 5, n);                  // (phases A and B queued: about a fifth of pass 1)
+	if (sync_at(c, 'B')) { fprintf(stderr, "[fseq] phase B queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase B done\n"); }
+	return FSEQ_OK;
+}
+
+// ---- the list capacity X: what the caller asked for, what worked last time, or an estimate from the boundary states
+int long_list_capacity(fseq_ctx *c, LongRun &R)
+{
+	FSEQ_LONG_LOCALS(c);
+	uint32_t &X = R.X;
+	if (!p.list_cap && !c->X_hint)
+	{
+		// first run on this input: size the lists from the block boundary states (k_boundary_recent)
+		// (sharded: every rank looks at its own boundaries, the ranks then agree on the largest estimate)
+		std::vector<uint32_t> recent(my_blocks ? my_blocks + 1 : 0);
+		if (my_blocks)
+		{
+			hipLaunchKernelGGL(k_boundary_recent, dim3(my_blocks + 1), dim3(256), 0, st, c->d_bstate_d, m, n, c->B, (uint32_t) L, c->d_recent, b_lo);
+			HIP_TRY(c, hipMemcpyAsync(recent.data(), c->d_recent, recent.size() * 4, hipMemcpyDeviceToHost, st));
+		}
+		HIP_TRY(c, hipStreamSynchronize(st));
+		recent.erase(std::remove(recent.begin(), recent.end(), 0xFFFFFFFFu), recent.end());
+		if (!recent.empty())
+		{
+			std::nth_element(recent.begin(), recent.begin() + recent.size() / 2, recent.end());
+			uint64_t const med = recent[recent.size() / 2];
+			// (a quarter above the median, to the next multiple of 64 -- not the next 2^k - 1: the lists of BASELINE C4 are
+			// 5,000,000 x (X + 3) x 8 bytes, and what they do not take goes to the stride states of pass 2)
+			uint64_t const want = med + med / 4;
+			if (X < want) X = (uint32_t) (((want + 63) & ~63ull) - 1);
+			if (c->tune.debug)
+				fprintf(stderr, "[fseq] list capacity estimate: %zu boundaries, median recent count %llu -> X = %u\n",
+				        recent.size(), (unsigned long long) med, X);
+		}
+	}
+	if (sharded)
+	{
+		HIP_TRY(c, hipMemcpyAsync(sh.xbuf, &X, 4, hipMemcpyHostToDevice, st));
+		if ((rc = shard_exchange(c, 1, 1))) return rc;
+		HIP_TRY(c, hipMemcpy(&X, sh.xbuf, 4, hipMemcpyDeviceToHost));
+	}
+	if (X >= m) X = m;
+
+	return FSEQ_OK;
+}
+
+// bytes of each staged-column buffer of a reduced configuration
+uint32_t red_symcap(fseq_ctx const *c, ReducedSet const &rs, bool direct)
+{
+	uint32_t const bytes = direct ? sym_bytes(c->p.m, c->bsh) : sym_bytes(rs.rows, c->bsh);
+	(void) rs;
+	return (bytes + 1023u) & ~1023u;                           // whole kilobytes: a wave stages sixteen bytes per lane
+}
+
+bool columns_fit_reduced(fseq_ctx const *c, ReducedSet const &rs, bool direct)
+{
+	// (value ids of a block -- its boundary values and one per column -- are 16-bit keys of the partition step)
+	return rs.lds(c->B, red_symcap(c, rs, direct)) <= LDS_LIMIT && (uint64_t) rs.rows + c->B + 1u <= 65535u;
+}
+
+} // namespace
+
+void red_fill_args(fseq_ctx *c, RedArgs &RA)
+{
+	RA.cnt = c->d_red_cnt; RA.vmin = c->d_red_vmin; RA.a = c->d_red_a; RA.d = c->d_red_d; RA.leaf = c->d_red_leaf;
+	RA.invalid = c->d_red_invalid; RA.any_invalid = c->d_red_invalid + c->nblocks; RA.cap = c->red_cap; RA.m_true = c->p.m;
+	RA.direct = c->red_direct ? 1u : 0u; RA.colbytes = sym_bytes(c->p.m, c->bsh); RA.rank = c->d_rank;
+	RA.ss_a = c->d_red_ss_a; RA.ss_d = c->d_red_ss_d; RA.ss_stride = c->red_ss_stride; RA.ss_cap = c->red_ss_cap;
+}
+
+namespace {
+
+// ---- [r5] phase C on representative rows (fseq_reduced.hpp): the plan of one attempt.
+// k_reduce_prep leaves, per block, the representatives and the reduced start state.  The blocks are sorted into the
+// configurations that hold them (a launch per configuration in use, side by side on their own streams) and the blocks
+// that run on all rows: more representatives than any configuration holds (or than pay: > 70 % of the rows), or lists an
+// earlier run on this input could not prove on the representatives.  The first run on an input (or at a new capacity) reads
+// the counts back and plans; later runs launch by the same plan without waiting and have the device check that the counts
+// are the ones the plan was made from (flags word 1; the attempt is repeated with a fresh plan if not).
+// *use: false when more than a quarter of the blocks would run on all rows anyway -- the attempt then takes the run on
+// all rows with its stride states (diverse inputs).
+int red_plan(fseq_ctx *c, uint32_t X, bool *use)
+{
+	FSEQ_LONG_LOCALS(c);
+	*use = false;
+	uint32_t cap = std::min<uint32_t>(m, 11264u);
+	if (c->tune.reduced_cap) cap = std::min<uint32_t>(cap, (uint32_t) c->tune.reduced_cap);
+	uint32_t const nbk = c->nblocks;
+	if (!c->d_red_cnt || c->red_cap != cap)
+	{
+		// (the small per-block words for every block of the alignment; the per-block rows for my blocks only -- a rank of a
+		// sharded run --, addressed by the block's place in the whole alignment like the key blocks and boundary states)
+		if ((rc = c->d_red_cnt.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_cnt_plan.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_vmin.alloc(c, nbk))) return rc;
+		if ((rc = c->d_red_invalid.alloc(c, nbk + 2))) return rc;
+		if ((rc = c->d_red_blocks.alloc(c, 3 * (size_t) nbk))) return rc;
+		if ((rc = c->d_red_rows.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_leaf.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_a.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		if ((rc = c->d_red_d.alloc_range(c, b_lo, b_hi, cap))) return rc;
+		c->red_cap = cap;
+		c->red_plan_valid = false;
+	}
+	if (!my_blocks) return FSEQ_OK;                            // (a rank without blocks)
+	// (the last run on this input at this capacity found the representatives not worth it: the same input gives the same answer)
+	if (c->red_declined && c->red_declined_X == X && !c->tune.reduced_always) return FSEQ_OK;
+	if (c->red_pin_words < 4 * (size_t) nbk + 64)
+	{
+		if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);
+		c->h_red_pin = nullptr; c->red_pin_words = 0;
+		HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_red_pin), (4 * (size_t) nbk + 64) * 4, hipHostMallocDefault));
+		c->red_pin_words = 4 * (size_t) nbk + 64;
+	}
+	if (!c->red_ev[0])
+		for (auto &evt : c->red_ev) HIP_TRY(c, hipEventCreateWithFlags(&evt, hipEventDisableTiming));
+	// LDS-resident row counts: the representatives' symbols come from the alignment's own columns (a block stages whole columns)
+	c->red_direct = !c->use_stream;
+	RedPrepArgs A{};
+	A.bstate_a = c->d_bstate_a; A.bstate_d = c->d_bstate_d; A.rank = c->d_rank; A.blocks = nullptr;
+	A.m = m; A.B = c->B; A.L = (uint32_t) L; A.cap = cap; A.block0 = b_lo; A.leaf_only = 0; A.n = n; A.direct = c->red_direct ? 1u : 0u;
+	A.Xp = X + (c->tune.reduced_margin >= 0 ? (uint32_t) c->tune.reduced_margin : X / 4u + 8u);
+	A.cnt = c->d_red_cnt; A.vmin = c->d_red_vmin; A.rows = c->d_red_rows; A.leaf = c->d_red_leaf; A.a = c->d_red_a; A.d = c->d_red_d;
+	A.invalid = c->d_red_invalid; A.flags = c->d_red_invalid + nbk;
+	HIP_TRY(c, launch_reduce_prep(st, my_blocks, A));
+	if (c->red_plan_valid && c->red_plan_X == X && c->red_force_full.size() == nbk)
+	{
+		launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, c->d_red_invalid + nbk);
+		if (!c->red_direct)
+			launch_reduce_msa(st, c->red_listed, c->red_max_rows, c->d_msa, c->ld, c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, n, c->B, c->bsh, c->d_red_blocks, m, c->tune.reduced_msa_gather);
+		c->tm.reduced_blocks = c->red_plan_blocks; c->tm.reduced_rows_mean = c->red_plan_rows_mean;
+		*use = true;
+		return FSEQ_OK;
+	}
+	uint32_t *const h_cnt = c->h_red_pin;
+	HIP_TRY(c, hipMemcpyAsync(h_cnt + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(c->d_red_cnt_plan + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	c->red_cnt_host.assign(nbk, RED_NONE);
+	std::copy(h_cnt + b_lo, h_cnt + b_hi, c->red_cnt_host.begin() + b_lo);
+	if (c->red_force_full.size() != nbk) c->red_force_full.assign(nbk, 0);
+	c->red_full.assign(nbk, 0);
+	c->red_config_of.assign(nbk, -1);
+	c->red_config_snap_of.assign(nbk, -1);
+	int const nconf = reduced_config_count();
+	std::vector<ReducedSet> sets((size_t) nconf);
+	std::vector<uint8_t> usable((size_t) nconf), usable_snap((size_t) nconf);
+	for (int i = 0; i < nconf; ++i)
+	{
+		(void) reduced_config(i, &sets[(size_t) i]);
+		ReducedSet const &rs = sets[(size_t) i];
+		// (small blocks: one-wave workgroups for both; from 256 threads on phase C takes the configurations with a list wave,
+		// pass 2's sweeps the others)
+		bool const fit = columns_fit_reduced(c, rs, c->red_direct);
+		usable[(size_t) i] = fit && (rs.T <= 128u || rs.ew);
+		usable_snap[(size_t) i] = fit && !rs.ew;
+	}
+	std::vector<std::vector<uint32_t>> per((size_t) nconf);
+	uint32_t n_full = 0, max_rows = 0, listed = 0;
+	uint64_t sum_rows = 0;
+	uint32_t *const h_blocks = c->h_red_pin + nbk;             // [0, listed): every reduced block; then the configurations' lists
+	for (uint32_t b = b_lo; b < b_hi; ++b)
+	{
+		uint32_t const r = c->red_cnt_host[b];
+		if (r != RED_NONE)
+		{
+			h_blocks[listed++] = b;
+			max_rows = std::max(max_rows, r);
+			int cf = -1, cs = -1;
+			// (a block the slim configuration refused -- more distinct start values than its table holds -- skips it)
+			bool const wide = c->red_force_full[b] == RED_FORCE_WIDE;
+			for (int i = 0; i < nconf; ++i) if (usable[(size_t) i] && sets[(size_t) i].rows >= r && !(wide && sets[(size_t) i].values < sets[(size_t) i].rows)) { cf = i; break; }
+			for (int i = 0; i < nconf; ++i) if (usable_snap[(size_t) i] && sets[(size_t) i].rows >= r) { cs = i; break; }
+			c->red_config_of[b] = cf;
+			c->red_config_snap_of[b] = cs;
+		}
+		bool const full = r == RED_NONE || c->red_config_of[b] < 0 || c->red_force_full[b] == RED_FORCE_FULL || (uint64_t) r * 10u > (uint64_t) m * 7u;
+		if (full) { c->red_full[b] = 1; ++n_full; }
+		else { per[(size_t) c->red_config_of[b]].push_back(b); sum_rows += r; }
+	}
+	c->red_listed = listed; c->red_max_rows = max_rows;
+	c->tm.reduced_blocks = my_blocks - n_full;
+	c->tm.reduced_rows_mean = my_blocks > n_full ? (uint32_t) (sum_rows / (my_blocks - n_full)) : 0u;
+	if (c->tune.debug)
+		fprintf(stderr, "[fseq] reduced phase C: %u of %u blocks on their representatives (mean %u of %u rows, most %u), %u on all rows\n", my_blocks - n_full, my_blocks,
+		        c->tm.reduced_rows_mean, m, max_rows, n_full);
+	if (c->tune.debug)
+		for (int i = 0; i < nconf; ++i)
+			if (!per[(size_t) i].empty())
+			{
+				uint64_t sr = 0;
+				for (uint32_t b : per[(size_t) i]) sr += c->red_cnt_host[b];
+				ReducedSet const &rs = sets[(size_t) i];
+				size_t const lds = rs.lds(c->B, red_symcap(c, rs, c->red_direct));
+				uint32_t const res = rs.prepare(lds) == hipSuccess ? rs.resident(lds) : 0u;
+				fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU)\n",
+				        rs.rows, per[(size_t) i].size(), (unsigned long long) (sr / per[(size_t) i].size()), rs.T, rs.E, rs.values, lds, res);
+			}
+	// worth it?  The run on all rows is the tuned one (three workgroups per CU, stride states for pass 2), and a row of a small
+	// reduced workgroup costs more than a row there: the representatives take over where they are clearly fewer -- rows to
+	// update in all, a block on all rows counted as one and a half (its boundaries are reached from the block's start) -- below
+	// a fifth of the rows (BASELINE C3 / C4 / C5: 8 / 7 / 6 %; C3's shape with ten times the mutations, 40 %: 11.4 ms against
+	// 9.4 on all rows, tools/diversity_sweep.py; FSEQ_REDUCED_ALWAYS: tests)
+	{
+		uint64_t const rows_all = sum_rows + (uint64_t) n_full * m * 3u / 2u;
+		if ((!c->tune.reduced_always && (rows_all * 5u > (uint64_t) my_blocks * m || (uint64_t) n_full * 4u > my_blocks)) || (uint64_t) n_full >= my_blocks)
+		{
+			c->red_declined = true; c->red_declined_X = X;
+			return FSEQ_OK;
+		}
+	}
+	if (n_full && c->use_stream && !c->s2.T) return FSEQ_OK;     // (the first form of the streamed kernel takes no block list)
+	if (!c->red_direct)
+	{
+		// the reduced alignment: column k at d_red_msa + k * red_ld
+		// (my columns only: column k at d_red_msa + k * red_ld)
+		size_t const ldr = ((size_t) sym_bytes(max_rows ? max_rows : 1u, c->bsh) + 15) & ~size_t(15);
+		uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
+		size_t const need = (size_t) (k_hi - k_lo) * ldr + 64;
+		if ((rc = c->d_red_msa.ensure(c, need))) return rc;
+		c->red_ld = ldr;
+		c->d_red_msa.rebase((ptrdiff_t) ((size_t) k_lo * ldr));
+	}
+	{
+		// the reduced states for pass 2: every 16 columns (32: streamed rows), rows for the most representatives of a block
+		uint32_t const stride_ = c->use_stream ? 32u : 16u;
+		uint32_t const scap = (std::max(max_rows, 1u) + 63u) & ~63u;
+		uint64_t const q_lo = (uint64_t) b_lo * c->B / stride_, q_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B) / stride_;
+		size_t const words = ((size_t) (q_hi - q_lo) + 2) * scap;
+		if ((rc = c->d_red_ss_a.ensure(c, words))) return rc;
+		if ((rc = c->d_red_ss_d.ensure(c, words))) return rc;
+		c->red_ss_stride = stride_; c->red_ss_cap = scap;
+		c->d_red_ss_a.rebase((ptrdiff_t) ((size_t) q_lo * scap));         // (the state at column q * stride at [q][scap])
+		c->d_red_ss_d.rebase((ptrdiff_t) ((size_t) q_lo * scap));
+	}
+	c->red_bins.clear();
+	uint32_t at = listed;
+	for (int i = 0; i < nconf; ++i)
+	{
+		auto const &v = per[(size_t) i];
+		if (v.empty()) continue;
+		std::copy(v.begin(), v.end(), h_blocks + at);
+		c->red_bins.push_back(fseq_ctx::RedBin{i, at, (uint32_t) v.size()});
+		at += (uint32_t) v.size();
+	}
+	c->red_full_at = at; c->red_nfull = 0;
+	for (uint32_t b = b_lo; b < b_hi; ++b) if (c->red_full[b]) h_blocks[at + c->red_nfull++] = b;
+	at += c->red_nfull;
+	HIP_TRY(c, hipMemcpyAsync(c->d_red_blocks, h_blocks, (size_t) at * 4, hipMemcpyHostToDevice, st));
+	if (!c->red_direct)
+		launch_reduce_msa(st, listed, max_rows, c->d_msa, c->ld, c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, n, c->B, c->bsh, c->d_red_blocks, m, c->tune.reduced_msa_gather);
+	c->red_plan_valid = true; c->red_plan_X = X;
+	c->red_plan_blocks = c->tm.reduced_blocks; c->red_plan_rows_mean = c->tm.reduced_rows_mean;
+	*use = true;
+	return FSEQ_OK;
+}
+
+} // namespace
+
+// launches of the reduced column kernel over lists of workgroups, one per configuration, side by side: the first on the
+// context's stream, the others on streams of their own that wait for it and that it waits for
+
+int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, uint32_t const *blocks, uint32_t const *wg_tasks, uint2 *ent, uint4 *hdr, uint32_t X, uint32_t stride)
+{
+	FSEQ_LONG_LOCALS(c);
+	if (ls.empty()) return FSEQ_OK;
+	// (up to RED_SIDE_STREAMS side streams, the context's second stream first -- every further hardware queue in use slows the
+	// dependent launches of phase B, measured on BASELINE C3: 0.71 ms with none, 0.97 with three)
+	size_t const nside = std::min<size_t>(ls.size() - 1, RED_SIDE_STREAMS);
+	if (nside) HIP_TRY(c, hipEventRecord(c->red_ev[3], st));
+	// [r7] queued largest workgroups first (the blocks of ten thousand representatives are not the tail of the phase, as pass 2's
+	// largest groups are not); the launch with the most blocks stays on the context's stream, the others take the side streams
+	// in that order and, past those, the context's
+	size_t main_i = 0;
+	for (size_t i = 1; i < ls.size(); ++i) if (ls[i].count > ls[main_i].count) main_i = i;
+	size_t side = 0;
+	for (size_t i = 0; i < ls.size(); ++i)
+	{
+		ReducedSet rs;
+		(void) reduced_config(ls[i].config, &rs);
+		RedArgs RA = base;
+		RA.symcap = red_symcap(c, rs, c->red_direct);
+		size_t const lds = rs.lds(c->B, RA.symcap);
+		HIP_TRY(c, rs.prepare(lds));
+		RA.blocks = blocks + ls[i].first;
+		if (wg_tasks) RA.wg_tasks = wg_tasks + 3 * (size_t) ls[i].first;
+		hipStream_t s_ = st;
+		size_t const slot = (i != main_i && side < nside) ? side++ : nside;      // (nside: the context's stream)
+		if (slot < nside)
+		{
+			if (slot >= 1 && !c->red_st[slot - 1]) HIP_TRY(c, hipStreamCreateWithFlags(&c->red_st[slot - 1], hipStreamNonBlocking));
+			s_ = slot == 0 ? c->stream2 : c->red_st[slot - 1];
+			HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev[3], 0));
+		}
+		rs.launch(s_, ls[i].count, lds, c->red_direct ? c->d_msa : c->d_red_msa, c->red_direct ? c->ld : c->red_ld, n, c->B, (uint32_t) L, X, stride, ent, hdr, c->npass, c->bsh, RA);
+		if (slot < nside) HIP_TRY(c, hipEventRecord(c->red_ev[slot], s_));
+	}
+	for (size_t i = 0; i < nside; ++i) HIP_TRY(c, hipStreamWaitEvent(st, c->red_ev[i], 0));
+	HIP_TRY(c, hipGetLastError());
+	return FSEQ_OK;
+}
+
+namespace {
+
+// the lists of the reduced blocks
+int red_columns(fseq_ctx *c)
+{
+	RedArgs RA;
+	red_fill_args(c, RA);
+	std::vector<RedLaunch> ls;
+	for (auto const &bin : c->red_bins) ls.push_back(RedLaunch{bin.config, bin.first, bin.count});
+	// (the bins ascend by the rows a workgroup holds: the largest first)
+	std::reverse(ls.begin(), ls.end());
+	return red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride);
+}
+
+// ---- phase C on all rows of the blocks b0 .. b0 + nb - 1
+// (list [r5]: workgroup i owns block list[i] instead of b0 + i -- the blocks the reduced phase C hands to the run on all rows)
+void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = nullptr, uint32_t epoch = 0, uint32_t const *list = nullptr)
+{
+	FSEQ_LONG_LOCALS(c);
+	// columns phase C covers here: all, or my blocks plus the halo block's first columns (the lists my last DP round reads)
+	uint64_t const n_c = sharded ? sh.c_end : n;
+	if (c->use_stream && c->s2.T)
+	{
+		uint32_t pack_abits = 1;
+		while ((1u << pack_abits) < m) ++pack_abits;
+		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
+		                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
+		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
+		             c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack | (c->ss_ids ? S2_SS_IDS : 0u), list);
+	}
+	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan)
+		hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
+		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
+	else if (c->use_stream)
+		hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
+		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
+	else
+		ks.columns(st, nb, c->lds_columns, c->d_msa, c->ld, m, n_c, c->B, c->N2, c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->npass, c->bsh,
+		           c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->colmask_ready && c->colmask_use ? c->d_colmask : (uint32_t const *) nullptr, list);
+}
+
+// ---- a list budget (fseq_set_list_memory): pass 1's lists in windows of wb consecutive column blocks.  Window w = blocks
+// [lo_w, hi_w) holds the lists of the columns [lo_w B - H, hi_w B) in one buffer (d_ent rebased to (lo_w B - H) stride:
+// the kernels address lists as they always do); phase C writes the window's own columns, the DP runs the rounds whose
+// lists are all there, and the last H columns move to the front for the next window.  H: the columns in front of a window
+// that its first DP round still reads.
+
+// DP rounds [.., r) that the lists of the columns < hi_w B feed: every regular round that reads no later column (its cells
+// read the lists of the columns e0 - 1 .. e0 + len - 2: dp_rounds_within); the drain round and the final cell wait for the
+// last window (the drain round's loads read column n - L, which an earlier window's buffer need not hold)
+uint32_t window_round_hi(fseq_ctx const *c, DpSchedule const &S, uint32_t hi_w)
+{
+	if (hi_w >= c->nblocks) return S.nrounds;
+	return std::min(dp_rounds_within(S, (uint64_t) hi_w * c->B), S.nreg);
+}
+
+// the window shape at list capacity X: the most blocks a window may have with the halo its rounds need beside them
+int plan_list_windows(fseq_ctx *c, uint32_t X)
+{
+	fseq_ctx::ListWindows &W = c->lw;
+	W.on = false;
+	W.merge_windows = 0;
+	uint64_t const n = c->p.n, L = c->p.segment_length, B = c->B, nb = c->nblocks;
+	if (!W.budget || c->sh.on || n < 2 * L) return FSEQ_OK;
+	uint64_t const stride = (X + 3) & ~1u, per_col = stride * sizeof(uint2), pad = 256 * sizeof(uint2);
+	if (n * per_col + pad <= W.budget) return FSEQ_OK;              // every list fits: the run as without a budget
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	uint64_t const cols = W.budget > pad ? (W.budget - pad) / per_col : 0;
+	uint64_t H = S.RL;                                              // (a first guess, raised to what the windows' rounds read)
+	for (int it = 0; it < 64; ++it)
+	{
+		uint64_t const wb = cols > H ? std::min<uint64_t>(nb, (cols - H) / B) : 0;
+		// (the halo moves to the front in one copy: a window must be at least as wide as the halo)
+		if (wb == 0 || wb * B < H)
+		{
+			uint64_t const wmin = std::max<uint64_t>(1, (H + B - 1) / B);
+			char what[320];
+			snprintf(what, sizeof(what), "list memory budget of %llu bytes holds no window: one window of %llu column block(s) of %llu columns plus a halo of %llu columns "
+			         "at list capacity %u needs %llu bytes", (unsigned long long) W.budget, (unsigned long long) wmin, (unsigned long long) B, (unsigned long long) H, X,
+			         (unsigned long long) ((H + wmin * B) * per_col + pad));
+			return fail(c, FSEQ_E_OOM, what);
+		}
+		uint64_t need = 0;
+		uint32_t r_lo = 0;
+		for (uint64_t lo = 0; lo < nb; lo += wb)
+		{
+			uint64_t const hi = std::min(nb, lo + wb);
+			uint32_t const r_hi = window_round_hi(c, S, (uint32_t) hi);
+			if (r_hi > r_lo)
+			{
+				uint64_t const first = (uint64_t) dp_round(S, r_lo).e0 - 1u;     // the lowest column the window's rounds read
+				if (lo * B > first) need = std::max(need, lo * B - first);
+				r_lo = r_hi;
+			}
+		}
+		if (need <= H)
+		{
+			W.on = true;
+			W.wb = (uint32_t) wb; W.H = (uint32_t) H;
+			W.nwin = (uint32_t) ((nb + wb - 1) / wb);
+			W.bytes = (H + wb * B) * per_col + pad;
+			return FSEQ_OK;
+		}
+		H = need;
+	}
+	return fail(c, FSEQ_E_HIP, "internal: no list window shape settles");
+}
+
+} // namespace
+
+// the buffer holds window [lo_w, ..): column k at d_ent + k * stride
+void set_list_window(fseq_ctx *c, uint32_t lo_w)
+{
+	c->d_ent.rebase(((int64_t) lo_w * c->B - (int64_t) c->lw.H) * (int64_t) c->stride);
+}
+
+// phase C (lists, headers, stride states) of the blocks [lo, hi): on their representatives where this attempt's plan put
+// them (the plan's block lists ascend within every configuration, so a window's blocks are one stretch of each), else on
+// all rows
+int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
+{
+	if (!c->red_active)
+	{
+		launch_columns(c, lo, hi - lo);
+		return FSEQ_OK;
+	}
+	uint32_t const *const h_blocks = c->h_red_pin + c->nblocks;      // red_plan's host copy of d_red_blocks
+	auto stretch = [&](uint32_t first, uint32_t count) {
+		uint32_t const *const b = h_blocks + first, *const e = b + count;
+		uint32_t const *const a = std::lower_bound(b, e, lo), *const z = std::lower_bound(b, e, hi);
+		return std::make_pair(first + (uint32_t) (a - b), (uint32_t) (z - a));
+	};
+	RedArgs RA;
+	red_fill_args(c, RA);
+	std::vector<RedLaunch> ls;
+	for (auto const &bin : c->red_bins)
+	{
+		auto const r = stretch(bin.first, bin.count);
+		if (r.second) ls.push_back(RedLaunch{bin.config, r.first, r.second});
+	}
+	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
+	int rc;
+	if ((rc = red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride))) return rc;
+	auto const f = stretch(c->red_full_at, c->red_nfull);
+	if (f.second) launch_columns(c, 0, f.second, nullptr, 0, c->d_red_blocks + f.first);
+	return FSEQ_OK;
+}
+
+namespace {
+
+// pass 1 + the DP window by window (queued on the context's stream; overflow lands in d_flags as for the whole-array DP)
+int long_windows_cd(fseq_ctx *c, DpSchedule const &S)
+{
+	FSEQ_LONG_LOCALS(c);
+	fseq_ctx::ListWindows &W = c->lw;
+	while (W.ev.size() < 2 * (size_t) W.nwin)
+	{
+		hipEvent_t e = nullptr;
+		HIP_TRY(c, hipEventCreate(&e));
+		W.ev.push_back(e);
+	}
+	// (the entries no cell writes -- between the last regular cell and the final one -- read 0, as after dp_spec_reset)
+	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.SZ, 0, c->dp_size * 4, st));
+	uint32_t r_lo = 0, w = 0, lo = 0;
+	for (; lo < c->nblocks; lo += W.wb, ++w)
+	{
+		uint32_t const hi = std::min(c->nblocks, lo + W.wb);
+		if (lo && W.H)
+			HIP_TRY(c, hipMemcpyAsync(c->d_ent.base, c->d_ent.base + (size_t) W.wb * c->B * c->stride, (size_t) W.H * c->stride * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+		set_list_window(c, lo);
+		if ((rc = window_phase_c(c, lo, hi))) return rc;
+		uint32_t const r_hi = window_round_hi(c, S, hi);
+		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w], st));
+		if (r_hi > r_lo)
+		{
+			launch_dp_serial(c, DP_PARTIAL, st, r_lo, r_hi);
+			r_lo = r_hi;
+		}
+		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w + 1], st));
+	}
+	HIP_TRY(c, hipGetLastError());
+	uint32_t const lo_last = (W.nwin - 1u) * W.wb;
+	W.col_lo = (uint64_t) lo_last * c->B; W.col_hi = n;
+	if (c->tune.debug)
+		fprintf(stderr, "[fseq] list windows: %u windows of %u blocks (%llu columns) + a halo of %u columns, %.2f GB of lists at X = %u\n", W.nwin, W.wb,
+		        (unsigned long long) W.wb * c->B, W.H, W.bytes / 1e9, c->X);
+	return FSEQ_OK;
+}
+
+// the redo marking: the blocks of [b_lo, b_hi) whose lists the reduced phase C could not vouch for (d_red_invalid) run on all
+// rows -- or, RED_WIDE, on the next configuration -- when the attempt runs again, and the plan goes with them.
+// *count: the blocks marked; *wide: those of them that stay reduced
+int red_take_invalid(fseq_ctx *c, uint32_t b_lo, uint32_t b_hi, uint32_t *count, uint32_t *wide)
+{
+	std::vector<uint32_t> inv(c->nblocks);
+	HIP_TRY(c, hipMemcpy(inv.data(), c->d_red_invalid, (size_t) c->nblocks * 4, hipMemcpyDeviceToHost));
+	*count = *wide = 0;
+	for (uint32_t b = b_lo; b < b_hi; ++b)
+		if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = inv[b] == RED_WIDE ? RED_FORCE_WIDE : RED_FORCE_FULL; ++*count; *wide += inv[b] == RED_WIDE ? 1u : 0u; }
+	if (*count) c->red_plan_valid = false;
+	return FSEQ_OK;
+}
+
+int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
+{
+	FSEQ_LONG_LOCALS(c);
+	uint32_t &X = R.X;
+	double &ms_c = R.ms_c, &ms_dp = R.ms_dp, &ms_host = R.ms_host;
+	bool const keyspace = R.keyspace;
+	// [r5] phase C on representative rows: the default wherever the lists are consumed by the speculative DP behind phase C
+	// (sharded: a rank's own blocks; its halo block has no state behind it to take the classes from and runs on all rows)
+	bool const red_candidate = !c->tune.no_reduced && n >= 2 * L;
+	double const t_att = now_ms();
+	auto mark = [&](char const *what) { if (c->tune.debug) fprintf(stderr, "[fseq]   attempt +%.3f ms %s\n", now_ms() - t_att, what); };
+	// a list budget the lists at this capacity exceed: pass 1 and the DP in column windows (long_windows_cd)
+	if ((rc = plan_list_windows(c, X))) return rc;
+	bool const windowed = c->lw.on;
+	if ((rc = ensure_work_buffers(c, X, !red_candidate))) return rc;
+	mark("lists allocated");
+	// ---- phase C + D
+#if defined(FSEQ_DP_STAMPS) || defined(FSEQ_DP_STATS)
+	HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 1024, st));
+#else
+	HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 16, st));
+#endif
+	if (c->tune.poison_lists)
+	{
+		// tests of the DP-beside-phase-C forms: a list read before it is written must not look right by accident
+		HIP_TRY(c, hipMemsetAsync(c->d_ent.base, 0xFF, c->d_ent.cap * sizeof(uint2), st));
+		HIP_TRY(c, hipMemsetAsync(c->d_hdr, 0xFF, (size_t) n * sizeof(uint4), st));
+	}
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	// the DP as chunk-speculative sweeps over the whole chip once every list is written (fseq_dpspec.hpp); the serial kernel for
+	// inputs too short for three chunks (and FSEQ_DP_SERIAL).  [r5] the forms that ran the serial DP beside phase C (in parts, or
+	// fed by host-visible flags) are gone: no default reached them
+	SpecPlan const spec = spec_plan(c, S);
+	bool const use_spec = !windowed && (sharded || spec.nchunks() > 0);
+	if (sharded && spec.nchunks() < 1) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: no DP chunk plan");
+	uint32_t spec_overflow = 0, spec_sweeps = 0;
+	HIP_TRY(c, hipEventRecord(c->ev[3], st));
+	RangeScope range_cd("fseq pass 1: phases C + D (column updates + lists, segmentation DP)");
+	{
+		if (use_spec)
+		{
+			// the arrays the speculative DP starts from are reset on the second stream while phase C runs
+			if ((rc = dp_spec_reset(c, spec, c->stream2))) return rc;
+			HIP_TRY(c, hipEventRecord(c->ev_part[15], c->stream2));
+		}
+		c->red_active = false;
+		if (red_candidate)
+		{
+			bool use = false;
+			if ((rc = red_plan(c, X, &use))) return rc;
+			mark("reduced plan");
+			if (use)
+			{
+				c->red_active = true;
+				if (!windowed)
+				{
+					if ((rc = red_columns(c))) return rc;
+					mark("reduced columns queued");
+					// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
+					if (c->red_nfull) launch_columns(c, 0, c->red_nfull, nullptr, 0, c->d_red_blocks + c->red_full_at);
+					// sharded: the block behind mine for as far as the halo reaches, on all rows (k_columns stops at n_c)
+					if (sharded && sh.c_end > sh.c_hi) launch_columns(c, b_hi, 1u);
+				}
+			}
+			else if ((rc = ensure_work_buffers(c, X, true))) return rc;      // (the stride states after all)
+		}
+		if (!sharded && !c->red_active && !windowed) launch_columns(c, 0, c->nblocks);
+		// (windows: phase C of a window, then the DP rounds its lists feed -- the DP is queued here, inside phase C's events)
+		if (windowed && (rc = long_windows_cd(c, S))) return rc;
+		if (sync_at(c, 'C')) { fprintf(stderr, "[fseq] phase C queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase C done\n"); }
+		if (sharded && my_blocks && !c->red_active)
+		{
+			// my blocks, and the block behind them for as far as the halo reaches (k_columns stops at n_c)
+			uint32_t const nb = my_blocks + ((sh.c_end > sh.c_hi) ? 1u : 0u);
+			launch_columns(c, b_lo, nb);
+		}
+		if (sharded && red_candidate)
+		{
+			// the ranks agree on whether the attempt stands BEFORE the DP's exchanges: a rank whose lists could not be proven
+			// on the representatives (or whose plan's counts have changed) makes every rank run the attempt again
+			uint32_t mine[2] = {0u, 0u};
+			if (c->red_active)
+			{
+				HIP_TRY(c, hipMemcpyAsync(mine, c->d_red_invalid + c->nblocks, 8, hipMemcpyDeviceToHost, st));
+				HIP_TRY(c, hipStreamSynchronize(st));
+			}
+			uint32_t word = (mine[0] ? 1u : 0u) | (mine[1] ? 2u : 0u);
+			HIP_TRY(c, hipMemcpyAsync(sh.xbuf, &word, 4, hipMemcpyHostToDevice, st));
+			if ((rc = shard_exchange(c, 1, 1))) return rc;
+			uint32_t all = 0;
+			HIP_TRY(c, hipMemcpy(&all, sh.xbuf, 4, hipMemcpyDeviceToHost));
+			if (all)
+			{
+				if (mine[1]) c->red_plan_valid = false;
+				if (mine[0])
+				{
+					uint32_t cnt = 0, wide = 0;
+					if ((rc = red_take_invalid(c, b_lo, b_hi, &cnt, &wide))) return rc;
+					c->red_plan_valid = false;
+					R.redone += cnt;
+				}
+				R.redo = true; *overflow_out = false;
+				HIP_TRY(c, hipEventRecord(c->ev[4], st));
+				HIP_TRY(c, hipEventRecord(c->ev_dp[0], st));
+				HIP_TRY(c, hipEventRecord(c->ev_dp[1], st));
+				HIP_TRY(c, hipStreamWaitEvent(st, c->ev_part[15], 0));
+				{ float f = 0; HIP_TRY(c, hipEventSynchronize(c->ev[4])); HIP_TRY(c, hipEventElapsedTime(&f, c->ev[3], c->ev[4])); R.ms_c += f; }
+				return FSEQ_OK;
+			}
+		}
+		HIP_TRY(c, hipEventRecord(c->ev[4], st));
+		HIP_TRY(c, hipEventRecord(c->ev_dp[0], st));
+		if (use_spec)
+		{
+			HIP_TRY(c, hipStreamWaitEvent(st, c->ev_part[15], 0));      // the DP arrays were reset beside phase C
+			if ((rc = run_dp_spec(c, S, spec, st, &spec_overflow, &spec_sweeps, true))) return rc;
+		}
+		else if (!windowed)
+			launch_dp_serial(c, DP_WHOLE, st, 0u, S.nrounds);
+		HIP_TRY(c, hipEventRecord(c->ev_dp[1], st));
+	}
+	HIP_TRY(c, hipEventRecord(c->ev[5], st));
+	HIP_TRY(c, hipGetLastError());
+	mark("DP queued");
+
+	if ((rc = pin_reserve(c, 64))) return rc;
+	uint32_t *const h_flags = pin_take<uint32_t>(c, 12);
+	h_flags[4] = 0;
+	HIP_TRY(c, hipMemcpyAsync(h_flags, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+	h_flags[5] = 0;
+	h_flags[6] = 0;
+	if (keyspace) HIP_TRY(c, hipMemcpyAsync(h_flags + 4, c->d_flags + 64, 12, hipMemcpyDeviceToHost, st));
+	h_flags[6 + 1] = 0; h_flags[6 + 2] = 0;
+	uint32_t *const h_red = h_flags + 7;                         // {a block's lists not proven, the plan's counts have changed}
+	if (c->red_active && !sharded) HIP_TRY(c, hipMemcpyAsync(h_red, c->d_red_invalid + c->nblocks, 8, hipMemcpyDeviceToHost, st));      // (sharded: agreed on before the DP)
+	HIP_TRY(c, hipStreamSynchronize(st));
+	R.redo = false;
+	if (c->red_active && h_red[1])
+	{
+		// (the counts are not what the plan was made from: plan afresh)
+		c->red_plan_valid = false;
+		R.redo = true; *overflow_out = false;
+		return FSEQ_OK;
+	}
+	if (c->red_active && h_red[0])
+	{
+		uint32_t cnt = 0, wide = 0;
+		if ((rc = red_take_invalid(c, 0, c->nblocks, &cnt, &wide))) return rc;
+		if (c->tune.debug) fprintf(stderr, "[fseq] reduced phase C: the lists of %u blocks reach below what their representatives vouch for: those blocks again on all rows\n", cnt - wide);
+		if (c->tune.debug && wide) fprintf(stderr, "[fseq] reduced phase C: %u blocks hold more distinct start values than the slim configuration's table: those blocks again on the next configuration\n", wide);
+		if (cnt) { R.redo = true; R.redone += cnt; *overflow_out = false; return FSEQ_OK; }
+	}
+	if (keyspace)
+	{
+		if (!R.tree_ran) h_flags[5] = my_blocks;               // (no tree this time: every block went to the column sweep, as last time)
+		c->tm.phase_a_fallbacks = h_flags[4];
+		c->tm.phase_a_given_up = h_flags[5];
+		// (the tree ran alone because no block was given up last time; the same input gives the same outcome)
+		if (R.tree_alone && h_flags[5] != 0u) return fail(c, FSEQ_E_HIP, "internal: the key-space tree gave up blocks it ranked in the run before");
+		c->bk_given_up = (int) h_flags[5];
+		if (R.trie_ran)
+		{
+			if (R.trie_alone && h_flags[6] != 0u) return fail(c, FSEQ_E_HIP, "internal: the block trie gave up blocks it ranked in the run before");
+			c->bt_given_up = (int) h_flags[6];
+			c->tm.phase_a_trie_given_up = h_flags[6];
+		}
+	}
+	{
+		float f = 0;
+		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[3], c->ev[4])); ms_c += f;
+		HIP_TRY(c, hipEventElapsedTime(&f, c->ev_dp[0], c->ev_dp[1])); ms_dp += f;
+		for (uint32_t w = 0; windowed && w < c->lw.nwin; ++w)
+		{
+			// (the windows' DP launches ran between phase C's events)
+			HIP_TRY(c, hipEventElapsedTime(&f, c->lw.ev[2 * (size_t) w], c->lw.ev[2 * (size_t) w + 1]));
+			ms_c -= f; ms_dp += f;
+		}
+	}
+#ifdef FSEQ_DP_STAMPS
+	{
+		unsigned long long stamps[96];
+		HIP_TRY(c, hipMemcpy(stamps, c->d_flags + 8, sizeof(stamps), hipMemcpyDeviceToHost));
+		for (int w = 0; w < 16; ++w)
+		{
+			unsigned long long const *q = stamps + 48 + 3 * w;
+			double const nr = (double) (stamps[3 * w + 2] ? stamps[3 * w + 2] : 1);
+			fprintf(stderr, "[dp stamps] wave %2d cycles/round: barrier 1 = %.0f, update = %.0f, barrier 2 = %.0f\n", w, q[0] / nr, q[1] / nr, q[2] / nr);
+		}
+		for (int w = 0; w < 16; ++w)
+		{
+			unsigned long long const *q = stamps + 3 * w;
+			double const nr = (double) (q[2] ? q[2] : 1);
+			fprintf(stderr, "[dp stamps] wave %2d rounds=%llu cycles/round: work=%.0f waits=%.0f\n", w, q[2], q[0] / nr, q[1] / nr);
+		}
+	}
+#endif
+#ifdef FSEQ_DP_STATS
+	{
+		uint32_t hist[34];
+		HIP_TRY(c, hipMemcpy(hist, c->d_flags + 128, sizeof(hist), hipMemcpyDeviceToHost));
+		fprintf(stderr, "[dp stats] list entries a cell needed (cell-pair path; last = more than 32):");
+		for (int i = 0; i < 34; ++i) fprintf(stderr, " %u", hist[i]);
+		fprintf(stderr, "\n");
+	}
+#endif
+	range_cd.end();
+	progress(c, FSEQ_STAGE_TRACEBACK, n, n);
+	RangeScope range_tb("fseq traceback + find_segments_greedy");
+	double const th0 = now_ms();
+	bool overflow = (h_flags[0] & 1u) != 0 || spec_overflow != 0;
+	c->tm.dp_sweeps = spec_sweeps;
+	c->tm.dp_chunks = use_spec ? spec.nchunks() : 0u;
+
+	if (!overflow && (rc = long_traceback_and_merge(c, th0, &overflow))) return rc;
+	ms_host += now_ms() - th0;
+	range_tb.end();
+	if (!overflow) progress(c, FSEQ_STAGE_MERGE, c->traceback.size(), c->traceback.size());
+	if (c->tune.debug) fprintf(stderr, "[fseq] host: traceback + merge %.3f ms\n", now_ms() - th0);
+	*overflow_out = overflow;
+	return FSEQ_OK;
+}
+
+} // namespace
+
+int run_long_path(fseq_ctx *c, fseq_result *res)
+{
+	FSEQ_LONG_LOCALS(c);
+	LongRun R;
+	R.X = p.list_cap ? p.list_cap : std::max(FSEQ_X_FLOOR, c->X_hint);
+	c->tm = fseq_timings{};
+	c->tm.block_len = c->B;
+	c->tm.n_blocks = c->nblocks;
+	double const t_begin = now_ms();
+
+	// (FSEQ_DEBUG: where the host's wall time of a run goes -- a first run on a context allocates, loads code objects, plans)
+	auto mark = [&](char const *what) { if (c->tune.debug) fprintf(stderr, "[fseq] +%.3f ms %s\n", now_ms() - t_begin, what); };
+	if ((rc = ensure_work_buffers(c, 0))) return rc;
+	mark("work buffers");
+	auto close_ab = [&](int code) { if (R.range_ab_open) { FSEQ_RANGE_POP(); R.range_ab_open = false; } return code; };
+	if ((rc = long_phase_a(c, R))) return close_ab(rc);
+	mark("phase A queued");
+	if ((rc = long_phase_b(c, R))) return close_ab(rc);
+	mark("phase B queued");
+	if ((rc = long_list_capacity(c, R))) return rc;
+	mark("list capacity");
+	while (true)
+	{
+		bool overflow = false;
+		if ((rc = long_attempt(c, R, &overflow))) return rc;
+		mark("attempt done");
+		if (R.redo) continue;                  // (the same capacity; the blocks that were flagged run on all rows now)
+		// (sharded: the thresholds are the same on every rank, so every rank takes the same way here)
+		if (!overflow) break;
+		if (R.X >= m) return fail(c, FSEQ_E_HIP, "internal: divergence lists complete but DP flagged overflow");
+		R.X = (uint32_t) std::min<uint64_t>(m, (uint64_t) R.X * 2 + 1);
+		++R.retries;
+		if (c->tune.debug) fprintf(stderr, "[fseq] divergence lists too short, retry %u with X = %u\n", R.retries, R.X);
+	}
+	c->X_hint = R.X;                         // later runs on this context start with the capacity that worked
+	c->res.segment_count = c->segments.size();
+	if ((rc = long_pass2(c, R))) return rc;
+	mark("pass 2 done");
+	uint32_t const X = R.X, retries = R.retries;
+	double const ms_c = R.ms_c, ms_dp = R.ms_dp, ms_host = R.ms_host, ms_p2 = R.ms_p2;
+	uint64_t const pass2_cells = R.pass2_cells;
+	size_t const S2 = c->segments.size();
+	{
+		float f = 0;
+		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[0], c->ev[1])); c->tm.ms_phase_a = f;
+		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[1], c->ev[2])); c->tm.ms_phase_b = f;
+	}
+	c->tm.ms_phase_c = ms_c;
+	c->tm.ms_dp = ms_dp;
+	c->tm.ms_pass2 = ms_p2;
+	c->tm.ms_host = ms_host;
+	c->tm.ms_colstep_kernels = c->tm.ms_phase_a + ms_c + ms_p2;
+	c->tm.colstep_launches = 2 + retries + (S2 ? 1 : 0);
+	c->tm.colstep_cells = (uint64_t) m * n * (2 + retries) + pass2_cells;
+	c->tm.pass2_cells = pass2_cells;
+	c->tm.list_cap_used = X;
+	c->tm.retries = retries;
+	c->tm.reduced_redone = R.redone;
+	if (!c->red_active) { c->tm.reduced_blocks = 0; c->tm.reduced_rows_mean = 0; }
+	c->tm.ms_total = now_ms() - t_begin;
+	c->have_result = true;
+	*res = c->res;
+	if (!(c->res.max_segment_size < m))
+		return fail(c, FSEQ_E_NO_REDUCTION, "Unable to reduce the number of sequences; the maximum segment size is equal to the number of input sequences.");
+	return FSEQ_OK;
+}
+
+// segmentation_sp_context::process (segmentation_sp_context.cc:21-28): one sweep over all n columns
+// from the identity; the distinct rows are the block keys of a single block [0, n).
+int run_short_path(fseq_ctx *c, fseq_result *res)
+{
+	fseq_params const &p = c->p;
+	uint32_t const m = p.m;
+	hipStream_t st = c->stream;
+	int rc;
+	c->tm = fseq_timings{};
+	double const t_begin = now_ms();
+	DevTemp<uint32_t> d_rank(c), d_keyd(c), d_nk(c);
+	if ((rc = d_rank.alloc(m)) || (rc = d_keyd.alloc(m)) || (rc = d_nk.alloc(4))) return rc;
+	if (c->use_stream && !c->d_ws && (rc = c->d_ws.alloc(c, (size_t) 4 * m))) return rc;
+	// one block [0, n): ranked in key space (fseq_blockkeys.hpp); FSEQ_PHASE_A_CLASSIC: the per-column sweep
+	if (c->bk_cap_words && !c->tune.phase_a_classic)
+	{
+		if (c->use_stream)
+		{
+			size_t const per = (blockkeys_stream_ws_words(m, (uint32_t) p.n, c->bsh) + 15) & ~size_t(15);
+			if ((rc = c->d_bkws.ensure(c, per))) return rc;
+			hipLaunchKernelGGL(k_blockkeys_stream, dim3(1), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, 1u,
+			                   d_rank, d_keyd, d_nk, (uint64_t) 0, c->d_bkws, per, c->bk_cap_words, (uint32_t *) nullptr, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), (uint32_t *) nullptr);
+		}
+		else
+		{
+			size_t const per = (blockkeys_scratch_halfwords(m, (uint32_t) p.n, c->bsh) + 7) & ~size_t(7);
+			if (c->bk_per_block != per) c->d_bk.release(c);
+			if ((rc = c->d_bk.ensure(c, per))) return rc;
+			c->bk_per_block = per;
+			launch_blockkeys(c->bk_T, st, 1, c->bk_lds, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, d_rank, d_keyd, d_nk, 0, c->d_bk, per, c->bk_cap_words, nullptr, nullptr);
+		}
+	}
+	else
+	{
+		// the 16-bit LDS kernels keep block-relative divergences in 16 bits: one block of 65536 columns or more would wrap
+		if (!c->use_stream && c->ks.cap > 7168u && p.n > 65535u)
+			return fail(c, FSEQ_E_UNSUPPORTED, "short path by column sweep: more than 65535 columns with 16-bit LDS state (unset FSEQ_PHASE_A_CLASSIC)");
+		launch_rank(c, 1, (uint32_t) p.n, 1, d_rank, d_keyd, d_nk);
+	}
+	std::vector<uint32_t> rank(m);
+	uint32_t nk = 0;
+	hipError_t e1 = hipMemcpyAsync(rank.data(), d_rank, (size_t) m * 4, hipMemcpyDeviceToHost, st);
+	hipError_t e2 = hipMemcpyAsync(&nk, d_nk, 4, hipMemcpyDeviceToHost, st);
+	hipError_t e3 = hipStreamSynchronize(st);
+	release_all(c, d_rank, d_keyd, d_nk);                          // (not held through the host's part below)
+	if (e1 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e1);
+	if (e2 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e2);
+	if (e3 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path sync", e3);
+	// identical rows keep ascending row-id order in the pBWT, so a run's first row is its smallest id
+	c->sp_first.assign(nk, 0xFFFFFFFFu);
+	c->sp_len.assign(nk, 0);
+	for (uint32_t r = 0; r < m; ++r)
+	{
+		uint32_t const k = rank[r];
+		if (c->sp_first[k] == 0xFFFFFFFFu) c->sp_first[k] = r;
+		++c->sp_len[k];
+	}
+	c->res = fseq_result{};
+	c->res.max_segment_size = nk;
+	c->res.short_path = 1;
+	c->traceback.clear();
+	c->segments.clear();
+	c->tm.colstep_launches = 1;
+	c->tm.colstep_cells = (uint64_t) m * p.n;
+	c->tm.ms_total = now_ms() - t_begin;
+	c->have_result = true;
+	*res = c->res;
+	if (!(nk < m))
+		return fail(c, FSEQ_E_NO_REDUCTION, "Unable to reduce the number of sequences; the maximum segment size is equal to the number of input sequences.");
+	return FSEQ_OK;
+}
+
+} // namespace fseq

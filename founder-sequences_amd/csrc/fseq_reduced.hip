@@ -1,5 +1,5 @@
 // fseq_reduced.hip -- [r5] the kernels of phase C / pass 2 on representative rows (fseq_reduced.hpp) and their launchers: a
-// translation unit of its own, compiled beside fseq_api.hip (which reaches them through the function tables below).
+// translation unit of its own, compiled beside the units of the path (which reach them through the function tables below).
 #include "fseq_ctx.hpp"
 #include "fseq_reduced.hpp"
 
@@ -52,7 +52,7 @@ struct LaunchChainSnap {
 	static ChainSnapSet make() { return ChainSnapSet{chain_snap_lds_bytes<T, E, PK>(), &prepare, &launch}; }
 };
 
-// the base configurations of select_kernels (fseq_api.hip)
+// the base configurations of select_kernels (fseq_kernelsets.hip)
 #define FSEQ_CHAIN_SNAP_CONFIGS(X) \
 	X(64, 1, false) X(64, 7, false) X(256, 5, false) X(512, 5, false) X(512, 7, false) X(1024, 5, false) X(1024, 7, false) X(1024, 9, true) X(1024, 10, true) X(1024, 11, true)
 

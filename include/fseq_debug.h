@@ -50,7 +50,7 @@ int  fseq_debug_ranges(uint64_t *pushes, uint64_t *pops, int *with_roctx);
  * (MI355X_MICROARCH.md, "DVFS give-back" item 6).  tools/clock_probe.py. */
 int  fseq_debug_clock(fseq_ctx *ctx, double *ghz, uint32_t *workgroups);
 
-/* The library's diagnostic knobs (FSEQ_* names, listed in csrc/fseq_api.hip `struct Tuning`): a context reads them
+/* The library's diagnostic knobs (FSEQ_* names, listed in csrc/fseq_ctx.hpp `struct Tuning`): a context reads them
  * from the environment once, at fseq_create; this sets one afterwards (value NULL = off).  Every knob selects among
  * exact alternatives; results never depend on them.  Call before the first fseq_run_segmentation (a later call drops the work buffers and
  * the result of the context: the geometry may change); on a sharded context before the input is set, identically on

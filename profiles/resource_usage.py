@@ -9,7 +9,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 prefix = sys.argv[1] if len(sys.argv) > 1 else "r02"
 # the library's translation units (founder-sequences_amd/build.py SRCS)
-units = ["fseq_api.hip", "fseq_api_join.hip", "fseq_reduced.hip", "fseq_kernelsets.hip", "fseq_kernelsets_stream.hip"]
+units = ["fseq_api.hip", "fseq_api_debug.hip", "fseq_path_setup.hip", "fseq_path_dp.hip", "fseq_path_pass1.hip", "fseq_path_pass2.hip", "fseq_api_join.hip", "fseq_reduced.hip",
+         "fseq_kernelsets.hip", "fseq_kernelsets_stream.hip"]
 txt = ""
 for u in units:
     src = os.path.join(ROOT, "founder-sequences_amd", "csrc", u)

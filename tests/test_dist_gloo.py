@@ -2,7 +2,7 @@
 
 The real shard arithmetic -- block range per rank, hyper key block exchange, sharded speculative DP with its
 per-sweep key exchange, threshold merge, pass 2 on the owners -- runs here as its Python model
-(tests/proto_shard.py, the statement of what csrc/fseq_api.hip does with sh.on) in two processes whose ONLY
+(tests/proto_shard.py, the statement of what the path's units, csrc/fseq_path_*.hip, do with sh.on) in two processes whose ONLY
 connection is torch.distributed all_reduce over gloo, the same primitive (fseq_allreduce_fn) the library asks
 bench.py's ShardTransport for on the GPUs.  Every rank's result must equal the oracle's serial walk.  Also the
 launcher logic bench.py uses: env ranks, barrier + max-over-ranks timing."""
