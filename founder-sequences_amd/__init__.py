@@ -101,10 +101,11 @@ EXPORTS = [
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
+    "fseq_debug_join_path",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
-                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns"]
+                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path"]
 
 FSEQ_E_PEER = 6
 STAGE_TRACEBACK, STAGE_MERGE, STAGE_SAMPLES = 0, 1, 2
@@ -207,6 +208,7 @@ def load_library():
     L.fseq_set_rows_streamed.argtypes = [vp, C.POINTER(vp), u64]
     L.fseq_debug_device_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.c_int]
     L.fseq_debug_packed_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.fseq_debug_join_path.argtypes = [vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -768,6 +770,12 @@ class SegmentationContext:
         jp = JoinProfile()
         self._check(self.L.fseq_get_join_profile(self.h, C.byref(jp)))
         return {k: getattr(jp, k) for k, _ in JoinProfile._fields_}
+
+    def join_path(self):
+        """Which way the last join_greedy() went: 0 the all-host joiner, 1 the LDS device front, 2 the wide device front."""
+        path = C.c_int()
+        self._check(self.L.fseq_debug_join_path(self.h, C.byref(path)))
+        return path.value
 
     def timings(self):
         t = Timings()

@@ -13,6 +13,76 @@
 
 using namespace fseq;
 
+// Boundary states (segments x m x 8 bytes) from which fseq_join_greedy takes the wide front by itself when max_segment_size is
+// above JP_MAX_CLASSES: the smallest swept size from which it beat the host joiner at every larger one, and never below
+// 16 MiB (profiles/join_wide.txt, tools/join_wide_probe.py).
+static constexpr uint64_t JOIN_WIDE_MIN_BYTES = 16ull << 20;
+
+// The wide device front of fseq_join_greedy (fseq_joinprep.hpp): what greedy_match_prepared takes, for any X up to 65,535.
+// *done = false with FSEQ_OK: the caller goes on to the host joiner (a failed device allocation, implausible tables, a right
+// segment of more than JW_CELLS classes, 2^32 edges or more -- the offsets are 32-bit words), with the error text cleared.
+static int join_greedy_wide(fseq_ctx *c, uint32_t *permutations, double t0, bool *done)
+{
+	*done = false;
+	size_t const m = c->p.m, S = c->segments.size();
+	uint32_t const X = c->res.max_segment_size;
+	hipStream_t st = c->stream;
+	DevTemp<uint16_t> d_of(c);
+	DevTemp<uint32_t> d_rep(c), d_size(c), d_count(c), d_start(c), d_off(c), d_ne(c);
+	DevTemp<uint64_t> d_rb(c);
+	DevTemp<unsigned long long> d_total(c);
+	DevTemp<uint2> d_edges(c);
+	auto no_room = [&](int rc) { if (rc == FSEQ_E_OOM) { c->err.clear(); return (int) FSEQ_OK; } return rc; };      // (the host joiner needs no device memory)
+	int rc;
+	if ((rc = d_of.alloc(S * m)) || (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) ||
+	    (rc = d_start.alloc(S * ((size_t) X + 1))) || (rc = d_off.alloc(S)) || (rc = d_ne.alloc(S)) || (rc = d_rb.alloc(S)) || (rc = d_total.alloc(1)))
+		return no_room(rc);
+	std::vector<uint64_t> rbs(S);
+	for (size_t i = 0; i < S; ++i) rbs[i] = c->segments[i].rb;
+	size_t const lds = (size_t) JW_CELLS * 4;
+	uint32_t const pairs = (uint32_t) (S - 1);
+	hipError_t e = hipMemcpyAsync(d_rb, rbs.data(), S * 8, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, S * X * 4, st);
+	if (e == hipSuccess) e = allow_lds(k_join_edges_wide<false>, lds);
+	if (e == hipSuccess) e = allow_lds(k_join_edges_wide<true>, lds);
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join preparation", e);
+	hipLaunchKernelGGL(k_join_classes_wide, dim3((uint32_t) S), dim3(JW_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count, d_start);
+	// the counting pass and the scan: the edge array is allocated at exactly the total
+	if (pairs)
+		hipLaunchKernelGGL(k_join_edges_wide<false>, dim3(pairs), dim3(JW_T), lds, st, c->d_snap_a, d_of, d_count, d_start, (uint32_t) m, X, d_ne, d_off, (uint2 *) nullptr, (uint64_t) 0);
+	hipLaunchKernelGGL(k_join_scan, dim3(1), dim3(JW_T), 0, st, d_ne, pairs, d_off, d_total);
+	std::vector<uint32_t> count(S);
+	unsigned long long total = 0;
+	e = hipMemcpyAsync(count.data(), d_count, S * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join preparation", e);
+	bool sane = total <= 0xFFFFFFFFull;
+	for (size_t i = 0; sane && i < S; ++i) sane = count[i] >= 1 && count[i] <= X && (0 == i || count[i] <= JW_CELLS);
+	if (!sane) return FSEQ_OK;                                // (the host joiner builds its own tables from the boundary states)
+	if ((rc = d_edges.alloc((size_t) total))) return no_room(rc);
+	if (pairs && total)
+		hipLaunchKernelGGL(k_join_edges_wide<true>, dim3(pairs), dim3(JW_T), lds, st, c->d_snap_a, d_of, d_count, d_start, (uint32_t) m, X, d_ne, d_off, d_edges, (uint64_t) total);
+	std::vector<uint32_t> rep(S * X), size(S * X), off(S), ne(S), edge_words(2 * (size_t) total + 2);
+	e = hipMemcpyAsync(rep.data(), d_rep, S * X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(size.data(), d_size, S * X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && pairs) e = hipMemcpyAsync(off.data(), d_off, (size_t) pairs * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && pairs) e = hipMemcpyAsync(ne.data(), d_ne, (size_t) pairs * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && total) e = hipMemcpyAsync(edge_words.data(), d_edges, (size_t) total * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess) e = hipGetLastError();
+	release_all(c, d_of, d_rep, d_size, d_count, d_start, d_off, d_ne, d_rb, d_total, d_edges);      // (not held through the host's part)
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join preparation", e);
+	double const t1 = now_ms();
+	JoinProfile prof;
+	greedy_match_prepared(c->p.m, X, S, count.data(), rep.data(), size.data(), edge_words.data(), off.data(), ne.data(), permutations, &prof);
+	c->jp = fseq_join_profile{t1 - t0, prof.ms_classes, prof.ms_edges, prof.ms_draw, now_ms() - t0,
+	                          (uint64_t) S * (2ull * X + 3) * 4 + (uint64_t) total * 8};
+	*done = true;
+	return FSEQ_OK;
+}
+
 extern "C" {
 
 int fseq_get_join_profile(fseq_ctx const *c, fseq_join_profile *out)
@@ -32,10 +102,20 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 	size_t const m = c->p.m, S = c->segments.size();
 	double const t0 = now_ms();
 	uint32_t const X = c->res.max_segment_size;
+	// The wide front: forced (FSEQ_JOIN_WIDE) at any X; by itself above the LDS front's limit, from JOIN_WIDE_MIN_BYTES of
+	// boundary states on.  Falls through to the all-host joiner as the LDS front does.
+	bool const wide = !c->tune.join_host && X >= 1 && X <= 0xFFFFu && m <= 0xFFFFFFFFull && S <= 0x7FFFFFFFull &&
+	                  (c->tune.join_wide || (X > JP_MAX_CLASSES && (uint64_t) S * m * 8ull >= JOIN_WIDE_MIN_BYTES));
+	if (wide)
+	{
+		bool done = false;
+		if (int const rc = join_greedy_wide(c, permutations, t0, &done)) return rc;
+		if (done) { c->join_path = 2; return FSEQ_OK; }
+	}
 	// class tables and co-occurrence edges where the boundary states are (fseq_joinprep.hpp); the host hands out
 	// the copies and draws the edges (the serial part of greedy_matcher.cc).  Falls through to the all-host joiner
 	// below when the edge array cannot be allocated or the tables come back implausible.
-	while (X <= JP_MAX_CLASSES && m <= 0xFFFFFFFFull && !c->tune.join_host)
+	while (!wide && X <= JP_MAX_CLASSES && m <= 0xFFFFFFFFull && !c->tune.join_host)
 	{
 		hipStream_t st = c->stream;
 		// (temporaries: released on every way out of the loop's body)
@@ -87,6 +167,7 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 		greedy_match_prepared(c->p.m, X, S, count.data(), rep.data(), size.data(), edge_words.data(), off.data(), ne.data(), permutations, &prof);
 		c->jp = fseq_join_profile{t1 - t0, prof.ms_classes, prof.ms_edges, prof.ms_draw, now_ms() - t0,
 		                          (uint64_t) S * (2ull * X + 3) * 4 + (uint64_t) total * 8};
+		c->join_path = 1;
 		return FSEQ_OK;
 	}
 	std::vector<uint32_t> A(S * m), D(S * m);
@@ -98,6 +179,15 @@ int fseq_join_greedy(fseq_ctx *c, uint32_t *permutations)
 	JoinProfile prof;
 	greedy_match(c->p.m, c->res.max_segment_size, segs, A.data(), D.data(), permutations, &prof);
 	c->jp = fseq_join_profile{t1 - t0, prof.ms_classes, prof.ms_edges, prof.ms_draw, now_ms() - t0, (uint64_t) S * m * 8ull};
+	c->join_path = 0;
+	return FSEQ_OK;
+}
+
+int fseq_debug_join_path(fseq_ctx *c, int *path)
+{
+	if (!c || !path) return FSEQ_E_ARG;
+	if (c->join_path < 0) return fail(c, FSEQ_E_ARG, "no fseq_join_greedy has finished on this context");
+	*path = c->join_path;
 	return FSEQ_OK;
 }
 

@@ -251,7 +251,12 @@ int  fseq_short_path_runs(fseq_ctx *ctx, uint32_t *first_idx, uint32_t *run_len)
  * replaces: join_context::join_greedy -> greedy_matcher::match (join_context.cc:211-229,
  * greedy_matcher.cc:204-465).  permutations: segment_count x max_segment_size uint32, row-major;
  * permutations[s][r] = index of the input sequence whose [lb_s, rb_s) substring is founder r's
- * content in segment s. */
+ * content in segment s.
+ * The class tables and the co-occurrence edges are built on the device, where the boundary states are, and the host hands out
+ * the copies and draws the edges: up to 181 classes a segment with the pair's counters in one LDS matrix, above that (up to
+ * 65,535), from 16 MiB of boundary states on, in strips of left classes.  Everything else -- smaller inputs above 181 classes,
+ * a failed device allocation -- goes through the all-host joiner; the permutations are the same entry for entry
+ * (fseq_debug_join_path tells which ran). */
 int  fseq_join_greedy(fseq_ctx *ctx, uint32_t *permutations);
 /* The same matcher on caller-supplied boundary states (no context, no device): segments given as
  * lb[i], rb[i]; a, d: n_segments x m.  Used by the CPU tests of the host logic. */

@@ -57,6 +57,11 @@ int  fseq_debug_clock(fseq_ctx *ctx, double *ghz, uint32_t *workgroups);
  * every rank (FSEQ_E_ARG afterwards: the input is laid out for the block partition in force when it was set). */
 int  fseq_debug_set_tuning(fseq_ctx *ctx, char const *name, char const *value);
 
+/* Which way the last fseq_join_greedy of the context went (*path): 0 the all-host joiner, 1 the device front with the pair's
+ * counters in one LDS matrix (up to 181 classes), 2 the wide device front (strips of left classes; FSEQ_JOIN_WIDE forces it).
+ * FSEQ_E_ARG before any fseq_join_greedy has finished. */
+int  fseq_debug_join_path(fseq_ctx *ctx, int *path);
+
 /* Device memory the context holds through its own buffers now (*now) and the most it has held since it was made or since the
  * last call with reset_peak != 0 (*peak; the reset happens after the report, to the bytes held now).  Accounting of the
  * context's allocations, not a measurement of the device: borrowed columns and the runtime's own memory are not in it. */
