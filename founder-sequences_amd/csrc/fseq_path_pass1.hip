@@ -740,20 +740,8 @@ int plan_list_windows(fseq_ctx *c, uint32_t X)
 	if (n * per_col + pad <= W.budget) return FSEQ_OK;              // every list fits: the run as without a budget
 	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
 	uint64_t const cols = W.budget > pad ? (W.budget - pad) / per_col : 0;
-	uint64_t H = S.RL;                                              // (a first guess, raised to what the windows' rounds read)
-	for (int it = 0; it < 64; ++it)
-	{
-		uint64_t const wb = cols > H ? std::min<uint64_t>(nb, (cols - H) / B) : 0;
-		// (the halo moves to the front in one copy: a window must be at least as wide as the halo)
-		if (wb == 0 || wb * B < H)
-		{
-			uint64_t const wmin = std::max<uint64_t>(1, (H + B - 1) / B);
-			char what[320];
-			snprintf(what, sizeof(what), "list memory budget of %llu bytes holds no window: one window of %llu column block(s) of %llu columns plus a halo of %llu columns "
-			         "at list capacity %u needs %llu bytes", (unsigned long long) W.budget, (unsigned long long) wmin, (unsigned long long) B, (unsigned long long) H, X,
-			         (unsigned long long) ((H + wmin * B) * per_col + pad));
-			return fail(c, FSEQ_E_OOM, what);
-		}
+	// the halo that windows of wb blocks need: how far in front of a window the lowest column lies that its rounds read
+	auto halo_of = [&](uint64_t wb) {
 		uint64_t need = 0;
 		uint32_t r_lo = 0;
 		for (uint64_t lo = 0; lo < nb; lo += wb)
@@ -767,17 +755,47 @@ int plan_list_windows(fseq_ctx *c, uint32_t X)
 				r_lo = r_hi;
 			}
 		}
-		if (need <= H)
-		{
-			W.on = true;
-			W.wb = (uint32_t) wb; W.H = (uint32_t) H;
-			W.nwin = (uint32_t) ((nb + wb - 1) / wb);
-			W.bytes = (H + wb * B) * per_col + pad;
-			return FSEQ_OK;
-		}
+		return need;
+	};
+	auto take = [&](uint64_t wb, uint64_t H) {
+		W.on = true;
+		W.wb = (uint32_t) wb; W.H = (uint32_t) H;
+		W.nwin = (uint32_t) ((nb + wb - 1) / wb);
+		W.bytes = (H + wb * B) * per_col + pad;
+		return FSEQ_OK;
+	};
+	uint64_t H = S.RL;                                              // (a first guess, raised to what the windows' rounds read)
+	for (int it = 0; it < 64; ++it)
+	{
+		uint64_t const wb = cols > H ? std::min<uint64_t>(nb, (cols - H) / B) : 0;
+		// (the halo moves to the front in one copy: a window must be at least as wide as the halo)
+		if (wb == 0 || wb * B < H) break;
+		uint64_t const need = halo_of(wb);
+		if (need <= H) return take(wb, H);
 		H = need;
 	}
-	return fail(c, FSEQ_E_HIP, "internal: no list window shape settles");
+	// The halo is no monotonic function of the window width: the drain round and the final cell wait for the last window and
+	// read from column n - L on, so the last window's halo is its start minus n - L -- up to L columns, and a few blocks more
+	// or less per window move that start anywhere.  Where the iteration above has run into a halo that leaves no window (or
+	// has not settled), every width is tried, the widest first.
+	uint64_t const wb_most = cols > S.RL ? std::min<uint64_t>(nb, (cols - S.RL) / B) : 0;
+	for (uint64_t wb = wb_most; wb >= 1; --wb)
+	{
+		uint64_t const Hw = std::max<uint64_t>(S.RL, halo_of(wb));
+		if (Hw + wb * B <= cols && wb * B >= Hw) return take(wb, Hw);
+	}
+	// no width fits: the refusal names the least shape that would (one window of all blocks is a shape, so there is one)
+	uint64_t wb_least = nb, H_least = S.RL;
+	for (uint64_t wb = 1; wb < nb; ++wb)
+	{
+		uint64_t const Hw = std::max<uint64_t>(S.RL, halo_of(wb));
+		if (wb * B >= Hw && Hw + wb * B < H_least + wb_least * B) { wb_least = wb; H_least = Hw; }
+	}
+	char what[320];
+	snprintf(what, sizeof(what), "list memory budget of %llu bytes holds no window: one window of %llu column block(s) of %llu columns plus a halo of %llu columns "
+	         "at list capacity %u needs %llu bytes", (unsigned long long) W.budget, (unsigned long long) wb_least, (unsigned long long) B, (unsigned long long) H_least, X,
+	         (unsigned long long) ((H_least + wb_least * B) * per_col + pad));
+	return fail(c, FSEQ_E_OOM, what);
 }
 
 } // namespace

@@ -33,10 +33,14 @@ def lists_of(codes, L, B, X):
 
 
 @pytest.mark.parametrize("m,n,L,seed,forced", [(12, 700, 5, 3, 1), (12, 700, 5, 3, 4), (20, 900, 10, 4, 3), (30, 600, 7, 5, 2),
-                                              (16, 1300, 100, 6, 1), (8, 1000, 10, 0x5EED0001, 5)])
+                                              (16, 1300, 100, 6, 1), (8, 1000, 10, 0x5EED0001, 5),
+                                              (12, 1700, 130, 7, 4),           # pipelined rounds (L >= 96), chunks of four
+                                              (10, 12400, 4097, 8, 30)])       # L beyond the DP's ring of 4,096 entries
 def test_speculative_dp_equals_serial_walk(m, n, L, seed, forced):
-    """Whatever the chunk length: the fixed point of the sweeps is the oracle's DP array (max, lb, size)."""
-    msa = fso.synth_msa(fso.synth_spec(seed, 3, 60, 5e-3, 0), m, n)
+    """Whatever the chunk length: the fixed point of the sweeps is the oracle's DP array (max, lb, size).  (From L = 130 on
+    the mosaic recombines every 3 L columns and mutates at 0.02 / L, as tests/segment_length_cases.py: several segments.)"""
+    Brec, mu = (60, 5e-3) if L < 130 else (3 * L, 0.02 / L)
+    msa = fso.synth_msa(fso.synth_spec(seed, 3, Brec, mu, 0), m, n)
     codes = codes_of(msa)
     ref = oracle(msa, L)
     S = ps.dp_schedule(L, n)
