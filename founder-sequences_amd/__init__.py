@@ -101,13 +101,14 @@ EXPORTS = [
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
-    "fseq_debug_join_path",
+    "fseq_debug_join_path", "fseq_debug_pass2_paths",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
-                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path"]
+                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths"]
 
 FSEQ_E_PEER = 6
+P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
 STAGE_TRACEBACK, STAGE_MERGE, STAGE_SAMPLES = 0, 1, 2
 # fseq_progress_fn (include/fseq.h): (user, stage, current_step, step_max)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64)
@@ -209,6 +210,7 @@ def load_library():
     L.fseq_debug_device_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.c_int]
     L.fseq_debug_packed_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_join_path.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
     _lib = L
     return L
 
@@ -776,6 +778,16 @@ class SegmentationContext:
         path = C.c_int()
         self._check(self.L.fseq_debug_join_path(self.h, C.byref(path)))
         return path.value
+
+    def pass2_paths(self):
+        """The last run's boundaries through pass 2's streamed chain step: {by_runs, by_sort, copies, max_runs, runs_hist} (all
+        zero where the run did not go through that kernel); runs_hist[b]: boundaries of more than 2^(b - 1) and at most 2^b runs."""
+        v = [C.c_uint32() for _ in range(4)]
+        hist = np.zeros(19, dtype=np.uint32)
+        self._check(self.L.fseq_debug_pass2_paths(self.h, *[C.byref(x) for x in v], hist.ctypes.data))
+        out = dict(zip(("by_runs", "by_sort", "copies", "max_runs"), (x.value for x in v)))
+        out["runs_hist"] = [int(x) for x in hist]
+        return out
 
     def timings(self):
         t = Timings()

@@ -25,6 +25,20 @@ int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 	return FSEQ_OK;
 }
 
+int fseq_debug_pass2_paths(fseq_ctx *c, uint32_t *by_runs, uint32_t *by_sort, uint32_t *copies, uint32_t *max_runs, uint32_t *runs_hist)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	uint32_t const none[P2_STATS] = {};
+	uint32_t const *s = c->p2_stats_have ? c->p2_stats : none;
+	if (by_runs) *by_runs = s[0];
+	if (by_sort) *by_sort = s[1];
+	if (copies) *copies = s[2];
+	if (max_runs) *max_runs = s[3];
+	if (runs_hist) std::copy(s + 4, s + 4 + P2_HIST, runs_hist);
+	return FSEQ_OK;
+}
+
 int fseq_debug_dp(fseq_ctx *c, uint32_t *lb, uint32_t *max_size, uint32_t *size)
 {
 	if (!c) return FSEQ_E_ARG;

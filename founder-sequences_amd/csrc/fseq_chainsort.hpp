@@ -18,14 +18,15 @@
 //   3. every new position: its row, and keyd or the range maximum between the old positions of the two rows (two
 //      block-end look-ups and two table entries, or a scan of at most 63 values inside one block).
 // Everything but the histograms lives in the workgroup's workspace (L2-resident: a few MB).
-// Two forms of the step live here: pass2_step, one step on one workgroup (pass 2's k_chain_snap_grouped, which keeps its records
-// in a workspace of its own, pass2_ws_words), and the k_cm_* kernels, phase B's steps spread over the chip (launch_chain in
-// fseq_path_pass1.hip, the only streamed phase B).
+// Two forms of the step live here: one step on one workgroup (pass 2's k_chain_snap_grouped, which keeps its records in a
+// workspace of its own, pass2_ws_words: pass2_step sorts the rows, pass2_runs the runs of equal class they form), and the k_cm_*
+// kernels, phase B's steps spread over the chip (launch_chain in fseq_path_pass1.hip, the only streamed phase B).
 #pragma once
 
 #include <type_traits>
 
 #include "fseq_stream.hpp"
+#include "fseq_types.hpp"
 
 namespace fseq {
 
@@ -73,71 +74,96 @@ __device__ __forceinline__ uint32_t cs_below(uint64_t mask)
 //     counting and in the scatter sweep alike (no key buffer);
 //   * step 2 writes ONE 16-byte record per old position, {a0[i], d0[i], prefix max[i], suffix max[i + 1]}: step 3 gathers
 //     rec[hi] only, and takes the suffix maximum at lo = (the previous new position's hi) + 1 from that neighbour's record
-//     (the lane below; lane 0 reads it itself) -- one random access per row instead of four;
+//     (the lane below; lane 0 reads it itself) -- one random access per row instead of four.  The records and the sparse table
+//     depend on the block's boundary state only: they are built ONCE for the block's tasks, beside r (pass2_records);
 //   * the divergence in front of a class (headd) and the sparse-table entries are loaded only by the rows that use them.
 // Groups are taken from a counter, largest first (the host orders them), so that blocks with many boundaries spread.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t P2_CLS_CAP = 11264;           // most representatives of a reduced block (red_plan's cap)
 
+// [r8] Runs.  The state in front of a block is a pBWT order: rows that agree over the block's next columns already lie together
+// in it, so the positions of one class form a few runs of consecutive positions (about two a class where no recombination
+// boundary of the founders lies between the block's start and the boundary's column) and the sort by class moves runs, not rows.
+// A task whose classes form at most run_cap runs takes the run path (pass2_runs): one descriptor per run, the descriptors sorted
+// by class, the new order written run by run -- inside a run a copy of consecutive old positions, whose divergences are their
+// own; only a run's head takes headd or a range maximum.  Every other task takes the radix path (pass2_step) as before.
+constexpr uint32_t P2_RUN_CAP = 8832;            // most runs of a task on the run path (138 x 64: about two a class for 4,352 classes)
+constexpr uint32_t P2_CLS_BITS = 14;             // bits of a class in a run's descriptor, class << position bits | start: up to 2^18 rows
+static_assert(P2_CLS_CAP <= (1u << P2_CLS_BITS), "a class of a reduced block fits a descriptor");
+
 struct Pass2Lds {
-	uint32_t hist[ST / WAVE][CS_BINS];           // per wave: digit counts, then the wave's write offsets
-	uint32_t total[CS_BINS];
 	uint32_t scan[ST / WAVE + 1];
 	uint32_t grp;                                // the group the workgroup took
-	uint16_t cls[P2_CLS_CAP];                    // the task's class of a rank
+	union {
+		struct {
+			uint32_t hist[ST / WAVE][CS_BINS];   // per wave: digit counts, then the wave's write offsets
+			uint32_t total[CS_BINS];
+			uint16_t cls[P2_CLS_CAP];            // the task's class of a rank
+		};
+		struct {                                 // the run path's output sweep (the sort is done, the classes are in the descriptors)
+			uint32_t off[P2_RUN_CAP + 1];        // first new position of the run, runs by (class, start); m behind the last
+			uint32_t dsc[P2_RUN_CAP];            // its descriptor, class << position bits | start
+		};
+	};
 };
 
 __host__ __device__ inline size_t pass2_lds_bytes() { return carve_bytes(1, sizeof(Pass2Lds)); }
 
-// workspace words of one workgroup: r (16-bit) | final pairs (up to 2 words each) | first-pass pairs, then the records
-// (4 words each) | sparse table; every part 16-byte aligned
+// workspace words of one workgroup: r (16-bit) | final pairs (up to 2 words each) | first-pass pairs (the same) | the block's
+// records (4 words each) | sparse table; every part 16-byte aligned.  The records and the table are the block's (built once for
+// its tasks); the pair buffers are a task's, and hold the run descriptors of a task on the run path (2 words a run, runs <= m).
 __host__ __device__ inline size_t pass2_ws_r(uint32_t m) { return (((size_t) m + 1) / 2 + 3) & ~size_t(3); }
 __host__ __device__ inline size_t pass2_ws_words(uint32_t m)
 {
 	size_t const nblk = ((size_t) m + 63) / 64;
-	return pass2_ws_r(m) + 2 * (size_t) m + 4 * (size_t) m + ((CS_LEVELS * nblk + 64 + 3) & ~size_t(3));
+	return pass2_ws_r(m) + 2 * (size_t) m + 2 * (size_t) m + 4 * (size_t) m + ((CS_LEVELS * nblk + 64 + 3) & ~size_t(3));
+}
+struct Pass2Ws {
+	uint16_t *r;
+	uint32_t *bufB, *bufA;                       // 2 m words each
+	uint4 *rec;
+	uint32_t *tab;
+};
+__device__ __forceinline__ Pass2Ws pass2_ws(uint32_t *w, uint32_t m)
+{
+	Pass2Ws W;
+	W.r = reinterpret_cast<uint16_t *>(w);
+	W.bufB = w + pass2_ws_r(m);
+	W.bufA = W.bufB + 2u * (size_t) m;
+	W.rec = reinterpret_cast<uint4 *>(W.bufA + 2u * (size_t) m);
+	W.tab = W.bufA + 6u * (size_t) m;
+	return W;
 }
 
-// One task: (a0, d0) -> (a1, d1), keys cls_lds[r[i]], D classes with divergences kd[class].  Ends with a barrier.
-template <bool P4>
-__device__ __forceinline__ void pass2_step(
-	uint32_t m, uint16_t const *__restrict__ r, uint32_t const *__restrict__ kd, uint32_t D, uint32_t *w, Pass2Lds &S,
-	uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+// digit passes of a sort by class: npass passes of db bits each
+__device__ __forceinline__ void pass2_digits(uint32_t D, uint32_t &npass, uint32_t &db)
+{
+	uint32_t bits = 1;
+	while (bits < 32u && ((D - 1u) >> bits) != 0u) ++bits;
+	npass = (bits + CS_MAX_DIGIT_BITS - 1u) / CS_MAX_DIGIT_BITS;
+	db = (bits + npass - 1u) / npass;
+}
+
+// The stable LSD radix sort of cnt items by key_of(item), npass passes of db bits.  Item i of the first pass is load0(i); the last
+// pass lands in bufB (pass p writes bufB where npass - p is odd, else bufA, and reads the other).  Ends with a barrier.
+template <typename PairT, typename Load0, typename KeyOf>
+__device__ __forceinline__ void pass2_sort(uint32_t cnt, uint32_t npass, uint32_t db, Load0 load0, KeyOf key_of, PairT none, PairT *bufA, PairT *bufB, Pass2Lds &S)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	constexpr uint32_t NW = ST / WAVE;
-	// P4: a pair is ONE word, key << pb | position (the caller has checked that the bits fit)
-	using PairT = std::conditional_t<P4, uint32_t, uint2>;
-	uint32_t pb = 1;
-	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
-	uint32_t const pmask = pb < 32u ? (1u << pb) - 1u : 0xFFFFFFFFu;
-	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
-	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
-	auto pos_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr & pmask; else return pr.y; };
-	PairT *const pairB = reinterpret_cast<PairT *>(w + pass2_ws_r(m));
-	uint32_t *const xr = w + pass2_ws_r(m) + 2u * (size_t) m;
-	PairT *const pairA = reinterpret_cast<PairT *>(xr);                   // (free once the sort is done: then the records)
-	uint4 *const rec = reinterpret_cast<uint4 *>(xr);
-	uint32_t *const tab = xr + 4u * (size_t) m;
-	uint32_t const nblk = (m + 63u) / 64u;
-
-	// ---- 1. the sort.  bits of a class, passes of at most 9 bits, the last pass lands in pairB
-	uint32_t bits = 1;
-	while (bits < 32u && ((D - 1u) >> bits) != 0u) ++bits;
-	uint32_t const npass = (bits + CS_MAX_DIGIT_BITS - 1u) / CS_MAX_DIGIT_BITS;
-	uint32_t const db = (bits + npass - 1u) / npass, nbins = 1u << db;
+	uint32_t const nbins = 1u << db;
 	// a wave's chunk: whole groups of 64 positions
-	uint32_t const per = ((m + NW - 1u) / NW + 63u) & ~63u;
-	uint32_t const c_lo = min(m, wave * per), c_hi = min(m, c_lo + per);
+	uint32_t const per = ((cnt + NW - 1u) / NW + 63u) & ~63u;
+	uint32_t const c_lo = min(cnt, wave * per), c_hi = min(cnt, c_lo + per);
 	for (uint32_t p = 0; p < npass; ++p)
 	{
 		uint32_t const shift = p * db;
 		bool const first = p == 0;
-		PairT const *src = ((npass - p) & 1u) ? pairA : pairB;          // (unused in the first pass)
-		PairT *dst = ((npass - p) & 1u) ? pairB : pairA;
-		// first pass: the pairs are made on the way, in both sweeps, from r and the class table in LDS
-		auto load = [&](uint32_t i) -> PairT { return first ? mk((uint32_t) S.cls[r[i]], i) : src[i]; };
+		PairT const *src = ((npass - p) & 1u) ? bufA : bufB;            // (unused in the first pass)
+		PairT *dst = ((npass - p) & 1u) ? bufB : bufA;
+		// first pass: the items are made on the way, in both sweeps
+		auto load = [&](uint32_t i) -> PairT { return first ? load0(i) : src[i]; };
 		for (uint32_t b = lane; b < nbins; b += 64u) S.hist[wave][b] = 0;
 		// (a wave's histogram row is its own: no barrier between clearing and counting; LDS operations of a wave stay in order)
 		constexpr uint32_t U = 4;
@@ -145,7 +171,7 @@ __device__ __forceinline__ void pass2_step(
 		{
 			PairT pr[U];
 #pragma unroll
-			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load(i) : mk(0u, 0u); }
+			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load(i) : none; }
 #pragma unroll
 			for (uint32_t u = 0; u < U; ++u)
 				if (i0 + u * 64u + lane < c_hi) atomicAdd(&S.hist[wave][(key_of(pr[u]) >> shift) & (nbins - 1u)], 1u);
@@ -164,7 +190,7 @@ __device__ __forceinline__ void pass2_step(
 		{
 			PairT pr[U];
 #pragma unroll
-			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load(i) : mk(0u, 0u); }
+			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; pr[u] = i < c_hi ? load(i) : none; }
 #pragma unroll
 			for (uint32_t u = 0; u < U; ++u)
 			{
@@ -180,10 +206,18 @@ __device__ __forceinline__ void pass2_step(
 		}
 		__syncthreads();
 	}
-	PairT const *perm = pairB;
+}
 
-	// ---- 2. the records: prefix / suffix maxima of d0 inside 64-blocks beside a0 and d0, a sparse table over the block maxima
-	// (UB blocks a wave and iteration: their loads in flight together)
+// The records of a block's boundary state (a0, d0), once for all its tasks: rec[i] = {a0[i], d0[i], the prefix maximum of d0
+// inside i's 64-block up to i, the suffix maximum from i + 1 (at a block's last position: the next block's maximum)}, and a
+// sparse table over the block maxima.  Ends with a barrier.
+// (UB blocks a wave and iteration: their loads in flight together)
+__device__ __forceinline__ void pass2_records(uint32_t m, uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint4 *rec, uint32_t *tab)
+{
+	uint32_t const tid = threadIdx.x, lane = lane_id();
+	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	constexpr uint32_t NW = ST / WAVE;
+	uint32_t const nblk = (m + 63u) / 64u;
 	constexpr uint32_t UB = 4;
 	for (uint32_t b0 = wave; b0 < nblk; b0 += NW * UB)
 	{
@@ -209,7 +243,7 @@ __device__ __forceinline__ void pass2_step(
 			if (lane == 63u) tab[blk] = pre;
 		}
 	}
-	__syncthreads();
+	__syncthreads();                                                      // (the records and level 0 of the table are whole)
 	for (uint32_t j = tid; j + 1u < nblk; j += ST) rec[j * 64u + 63u].w = tab[j + 1u];
 	for (uint32_t k = 1; k < CS_LEVELS && (1u << k) <= nblk; ++k)
 	{
@@ -219,6 +253,186 @@ __device__ __forceinline__ void pass2_step(
 		__syncthreads();
 	}
 	__syncthreads();
+}
+
+// max d0[lo .. hi], 1 <= lo <= hi, from the records: the suffix maximum at lo, the blocks between, the prefix maximum at hi, or,
+// where lo and hi share a 64-block, one of the two where it is the range's, else a scan of at most 63 values
+__device__ __forceinline__ uint32_t pass2_range_max(uint32_t lo, uint32_t hi, uint4 const *rec, uint32_t const *tab, uint32_t nblk, uint32_t const *__restrict__ d0)
+{
+	uint32_t const bl = lo >> 6, bh = hi >> 6;
+	uint4 const rc = rec[hi], q = rec[lo - 1u];
+	uint32_t const pz = q.z, sv = q.w;                                    // prefix max at lo - 1, suffix max at lo
+	uint32_t dv = max(sv, rc.z);
+	if (bh > bl + 1u)
+	{
+		uint32_t const k = 31u - (uint32_t) __builtin_clz(bh - bl - 1u);
+		uint32_t const *t = tab + (size_t) k * nblk;
+		dv = max(dv, max(t[bl + 1u], t[bh - (1u << k)]));
+	}
+	if (bl == bh)
+	{
+		if ((lo & 63u) == 0u || rc.z > pz) dv = rc.z;
+		else if ((hi & 63u) == 63u || sv > rc.w) dv = sv;
+		else
+		{
+			dv = rc.y;
+			for (uint32_t i = lo; i < hi; ++i) dv = max(dv, d0[i]);
+		}
+	}
+	return dv;
+}
+
+// One task by runs: (a0, d0) -> (a1, d1), keys S.cls[r[i]], D classes with divergences kd[class]; the caller has checked that a
+// class (P2_CLS_BITS) and a position share a word.  Returns false, having written nothing, where the classes form more than run_cap runs
+// (*nrun: how many); else ends with a barrier.  LDS: the class table is gone afterwards.
+__device__ __forceinline__ bool pass2_runs(
+	uint32_t m, uint32_t const *__restrict__ kd, uint32_t D, Pass2Ws const &W, Pass2Lds &S, uint32_t run_cap, uint32_t *nrun,
+	uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+{
+	uint32_t const tid = threadIdx.x, lane = lane_id();
+	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	constexpr uint32_t NW = ST / WAVE;
+	uint16_t const *__restrict__ r = W.r;
+	uint32_t pb = 1;
+	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
+	uint32_t const pmask = (1u << pb) - 1u;                               // (pb < 32: a class shares the word)
+	uint32_t const nblk = (m + 63u) / 64u;
+	uint32_t const per = ((m + NW - 1u) / NW + 63u) & ~63u;
+	uint32_t const c_lo = min(m, wave * per), c_hi = min(m, c_lo + per);
+	constexpr uint32_t U = 4;
+
+	// ---- a. the runs: position i starts one where its class is not the class at i - 1.  A wave sweeps its chunk in order (the
+	// class in front of a group of 64: the last lane of the group before, in front of the chunk: looked up); sweep 0 counts the
+	// starts, sweep 1 writes the descriptors {class << pb | start, end} in position order
+	uint32_t npass, db;
+	pass2_digits(D, npass, db);
+	uint2 *const bufA = reinterpret_cast<uint2 *>(W.bufA), *const bufB = reinterpret_cast<uint2 *>(W.bufB);
+	uint32_t *const pos_order = reinterpret_cast<uint32_t *>((npass & 1u) ? bufA : bufB);      // (the buffer the first pass of the sort does not write)
+	uint32_t R = 0, wbase = 0;
+	for (uint32_t sweep = 0; sweep < 2u; ++sweep)
+	{
+		uint32_t prev = 0xFFFFFFFFu;                                      // (no class: position 0 starts a run)
+		if (c_lo > 0u && c_lo < c_hi) prev = (uint32_t) S.cls[r[c_lo - 1u]];
+		uint32_t k0 = wbase;
+		for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * U)
+		{
+			uint32_t rv[U];
+#pragma unroll
+			for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * 64u + lane; rv[u] = i < c_hi ? (uint32_t) r[i] : 0u; }
+#pragma unroll
+			for (uint32_t u = 0; u < U; ++u)
+			{
+				uint32_t const i = i0 + u * 64u + lane;
+				if (i0 + u * 64u >= c_hi) break;
+				bool const in = i < c_hi;
+				uint32_t const cl = (uint32_t) S.cls[rv[u]];
+				uint32_t const up = shfl_up_u32(cl, 1);
+				bool const head = in && cl != (lane ? up : prev);
+				uint64_t const heads = __ballot(head);
+				if (sweep)
+				{
+					uint32_t const k = k0 + cs_below(heads);
+					if (head)
+					{
+						pos_order[2u * k] = (cl << pb) | i;
+						if (k) pos_order[2u * k - 1u] = i;                // (the run before ends here)
+					}
+				}
+				k0 += (uint32_t) __popcll(heads);
+				prev = readlane_u32(cl, 63);                              // (a group that is not whole is the chunk's last)
+			}
+		}
+		if (sweep) break;
+		uint32_t const before = block_excl_add<ST>(lane == 0u ? k0 : 0u, S.scan, &R);
+		wbase = __builtin_amdgcn_readfirstlane(before);
+		*nrun = R;
+		if (R > run_cap) return false;
+	}
+	if (tid == 0u) pos_order[2u * R - 1u] = m;
+	__syncthreads();
+
+	// ---- b. the runs by (class, start): a stable sort by class of descriptors that are in start order
+	pass2_sort<uint2>(R, npass, db, [&](uint32_t i) -> uint2 { return reinterpret_cast<uint2 const *>(pos_order)[i]; },
+	                  [&](uint2 x) -> uint32_t { return x.x >> pb; }, make_uint2(0u, 0u), bufA, bufB, S);
+	// their first new positions: the prefix sum of their lengths (a thread takes consecutive runs)
+	{
+		uint32_t const q = (R + ST - 1u) / ST, j0 = min(R, tid * q), j1 = min(R, j0 + q);
+		uint32_t sum = 0;
+		for (uint32_t j = j0; j < j1; ++j) { uint2 const x = bufB[j]; sum += x.y - (x.x & pmask); }
+		uint32_t all;
+		uint32_t at = block_excl_add<ST>(sum, S.scan, &all);
+		// (the sort's last barrier is behind every use of the histograms and of the class table, which these arrays lie over)
+		for (uint32_t j = j0; j < j1; ++j) { uint2 const x = bufB[j]; S.off[j] = at; S.dsc[j] = x.x; at += x.y - (x.x & pmask); }
+		if (tid == 0u) S.off[R] = m;
+	}
+	__syncthreads();
+
+	// ---- c. the new order: position p lies in the run j with off[j] <= p < off[j + 1] and takes the row at old position
+	// hi = start + (p - off[j]); behind the run's head its divergence too.  A head takes the class's divergence where the run is
+	// the class's first, else the maximum of d0 from behind the end of the run before it (same class) up to hi
+	uint32_t top = 1;
+	while (top * 2u < R) top *= 2u;
+	for (uint32_t p0 = tid; p0 < m; p0 += ST * U)
+	{
+		uint32_t jj[U], hh[U], av[U], dv[U];
+#pragma unroll
+		for (uint32_t u = 0; u < U; ++u)
+		{
+			uint32_t const p = min(p0 + u * ST, m - 1u);
+			uint32_t j = 0;
+			for (uint32_t step = top; step; step >>= 1) { uint32_t const t = j + step; if (t < R && S.off[t] <= p) j = t; }
+			jj[u] = j;
+			hh[u] = (S.dsc[j] & pmask) + (p - S.off[j]);
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < U; ++u) { av[u] = a0[hh[u]]; dv[u] = d0[hh[u]]; }
+#pragma unroll
+		for (uint32_t u = 0; u < U; ++u)
+		{
+			uint32_t const p = p0 + u * ST, j = jj[u];
+			if (p >= m) break;
+			if (S.off[j] == p)
+			{
+				uint32_t const me = S.dsc[j], pv = j ? S.dsc[j - 1u] : 0u;
+				if (j == 0u || (pv >> pb) != (me >> pb)) dv[u] = kd[me >> pb];
+				else dv[u] = pass2_range_max((pv & pmask) + (p - S.off[j - 1u]), hh[u], W.rec, W.tab, nblk, d0);
+			}
+			a1[p] = av[u];
+			d1[p] = dv[u];
+		}
+	}
+	__syncthreads();
+	return true;
+}
+
+// One task by the sort of all its rows: (a0, d0) -> (a1, d1), keys S.cls[r[i]], D classes with divergences kd[class].  Ends with a barrier.
+template <bool P4>
+__device__ __forceinline__ void pass2_step(
+	uint32_t m, uint32_t const *__restrict__ kd, uint32_t D, Pass2Ws const &W, Pass2Lds &S,
+	uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+{
+	uint32_t const tid = threadIdx.x, lane = lane_id();
+	// P4: a pair is ONE word, key << pb | position (the caller has checked that the bits fit)
+	using PairT = std::conditional_t<P4, uint32_t, uint2>;
+	uint32_t pb = 1;
+	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
+	uint32_t const pmask = pb < 32u ? (1u << pb) - 1u : 0xFFFFFFFFu;
+	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
+	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
+	auto pos_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr & pmask; else return pr.y; };
+	uint16_t const *__restrict__ r = W.r;
+	uint4 const *const rec = W.rec;
+	uint32_t const *const tab = W.tab;
+	uint32_t const nblk = (m + 63u) / 64u;
+
+	// ---- 1. the sort: the pairs are made on the way from r and the class table in LDS
+	uint32_t npass, db;
+	pass2_digits(D, npass, db);
+	pass2_sort<PairT>(m, npass, db, [&](uint32_t i) -> PairT { return mk((uint32_t) S.cls[r[i]], i); }, key_of, mk(0u, 0u),
+	                  reinterpret_cast<PairT *>(W.bufA), reinterpret_cast<PairT *>(W.bufB), S);
+	PairT const *perm = reinterpret_cast<PairT const *>(W.bufB);
+
+	// ---- 2. (the records: pass2_records, once for the block)
 
 	// ---- 3. the new order: position p takes the row of its record; the first of a class takes the class's divergence, any
 	// other the maximum of d0(lo .. hi] = max(suffix max at lo, the blocks between, prefix max at hi), or a scan of at most 63
@@ -298,17 +512,19 @@ __device__ __forceinline__ void pass2_step(
 	__syncthreads();
 }
 
+// stats (P2_STATS words, fseq_types.hpp): tasks on the run path, tasks on the radix path, border copies, the most runs a task had
+// (of the tasks that counted theirs), those tasks by the power of two their run count reaches (P2_HIST buckets)
 __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 	uint32_t const *__restrict__ bstate_a, uint32_t const *__restrict__ bstate_d, uint32_t const *__restrict__ rank, uint32_t m,
 	uint32_t const *__restrict__ task_blk, uint32_t const *__restrict__ cls, uint32_t const *__restrict__ headd, uint32_t const *__restrict__ ncls,
 	uint32_t cap, uint2 const *__restrict__ grps, uint32_t ngrp, uint32_t *__restrict__ grp_next, uint32_t *__restrict__ snap_a,
-	uint32_t *__restrict__ snap_d, uint32_t *ws)
+	uint32_t *__restrict__ snap_d, uint32_t *ws, uint32_t run_cap, uint32_t *__restrict__ stats)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	Pass2Lds &S = *reinterpret_cast<Pass2Lds *>(smem);
 	uint32_t const tid = threadIdx.x;
-	uint32_t *const w = ws + (size_t) blockIdx.x * pass2_ws_words(m);
-	uint16_t *const r = reinterpret_cast<uint16_t *>(w);
+	Pass2Ws const W = pass2_ws(ws + (size_t) blockIdx.x * pass2_ws_words(m), m);
+	uint16_t *const r = W.r;
 	uint32_t pbits = 1;
 	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
 	for (;;)
@@ -330,6 +546,7 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 			if (D == 0u)
 			{
 				for (uint32_t i = tid; i < m; i += ST) { snap_a[ob + i] = a0[i]; snap_d[ob + i] = d0[i]; }
+				if (tid == 0) atomicAdd(stats + 2, 1u);
 				continue;
 			}
 			if (!have_r)
@@ -344,6 +561,8 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 #pragma unroll
 					for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; if (i < m) r[i] = (uint16_t) rv[u]; }
 				}
+				// ... and the records and the table of its boundary state
+				pass2_records(m, a0, d0, W.rec, W.tab);
 				have_r = true;
 			}
 			for (uint32_t j = tid; j < cap; j += ST) S.cls[j] = (uint16_t) cls[(size_t) task * cap + j];
@@ -351,10 +570,25 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 			// (the classes and the positions share a word where their bits fit: at most 11,264 classes, 2^18 rows)
 			uint32_t kb = 1;
 			while (kb < 32u && ((D - 1u) >> kb) != 0u) ++kb;
-			if (kb + pbits <= 32u)
-				pass2_step<true>(m, r, headd + (size_t) task * cap, D, w, S, a0, d0, snap_a + ob, snap_d + ob);
-			else
-				pass2_step<false>(m, r, headd + (size_t) task * cap, D, w, S, a0, d0, snap_a + ob, snap_d + ob);
+			bool const p4 = kb + pbits <= 32u;
+			uint32_t const *kd = headd + (size_t) task * cap;
+			uint32_t nrun = 0;
+			// (a run's descriptor is a word of P2_CLS_BITS class bits over a position: with more than 2^18 rows every task sorts its rows)
+			bool const by_runs = run_cap != 0u && P2_CLS_BITS + pbits <= 32u && pass2_runs(m, kd, D, W, S, run_cap, &nrun, a0, d0, snap_a + ob, snap_d + ob);
+			if (!by_runs)
+			{
+				if (p4) pass2_step<true>(m, kd, D, W, S, d0, snap_a + ob, snap_d + ob);
+				else pass2_step<false>(m, kd, D, W, S, d0, snap_a + ob, snap_d + ob);
+			}
+			if (tid == 0)
+			{
+				atomicAdd(stats + (by_runs ? 0 : 1), 1u);
+				if (nrun)
+				{
+					atomicMax(stats + 3, nrun);
+					atomicAdd(stats + 4 + min(P2_HIST - 1u, nrun > 1u ? 32u - (uint32_t) __builtin_clz(nrun - 1u) : 0u), 1u);
+				}
+			}
 		}
 	}
 }

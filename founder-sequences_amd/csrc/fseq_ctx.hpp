@@ -142,6 +142,7 @@ struct Tuning {
 	bool reduced_always = false;         // FSEQ_REDUCED_ALWAYS: the representatives whenever some block has fewer of them than rows (tests of the mixed runs)
 	bool reduced_msa_gather = false;     // FSEQ_REDUCED_MSA_GATHER: the reduced alignment by gathers from memory (by itself: the column through LDS where it fits)
 	int  reduced_cap = 0;                // FSEQ_REDUCED_CAP: most representatives a block may have (tests: small values send blocks to the run on all rows)
+	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -185,6 +186,7 @@ struct Tuning {
 			{"FSEQ_REDUCED_ALWAYS", &Tuning::reduced_always, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_MSA_GATHER", &Tuning::reduced_msa_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
+			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
 		};
 		return table;
 	}
@@ -404,7 +406,9 @@ struct fseq_ctx {
 	                                         // stays reduced but skips the slim configuration, which refused it
 	bool red_active = false;                 // this run's phase C went through the representatives (pass 2 follows it)
 	DevBuf<uint32_t> d_red_cls, d_red_headd, d_red_ncls, d_red_taskblk, d_red_wgtasks;
-	DevBuf<uint32_t> d_red_p2grp;            // streamed pass 2: its groups {first task, count} and the counter they are taken by
+	DevBuf<uint32_t> d_red_p2grp;            // streamed pass 2: its groups {first task, count}, the counter they are taken by and the kernel's counters
+	uint32_t p2_stats[fseq::P2_STATS]{};                // ... of the last run (fseq_debug_pass2_paths): tasks by runs, tasks by the sort of all rows, border copies, most runs, tasks by run count
+	bool p2_stats_have = false;              // the last run went through that kernel
 	DevBuf<uint32_t> d_red_ss_a, d_red_ss_d; // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
 	uint32_t red_ss_stride = 0, red_ss_cap = 0;
 	uint32_t *h_red_pin = nullptr;           // pinned host staging of the plan (counts back, block lists out): its own buffer, live across the run

@@ -148,7 +148,7 @@ size_t chain_hist_words(uint32_t m);                 // digit histogram words of
 // launch as the workspace holds
 void launch_replay_stream(fseq_ctx *c, size_t groups, uint64_t const *d_rb, uint2 const *d_grp, uint64_t const *d_src, uint32_t *out_a, uint32_t *out_d,
                           uint32_t const *ss_a, uint32_t const *ss_d, uint32_t ss_pack);
-int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp);       // pass 2 behind the reduced phase C, streamed rows: the chain steps
+int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats);       // pass 2 behind the reduced phase C, streamed rows: the chain steps
 void red_fill_args(fseq_ctx *c, RedArgs &RA);
 struct RedLaunch { int config; uint32_t first, count; };
 int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, uint32_t const *blocks, uint32_t const *wg_tasks, uint2 *ent, uint4 *hdr, uint32_t X, uint32_t stride);

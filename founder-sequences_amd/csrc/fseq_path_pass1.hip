@@ -134,9 +134,17 @@ int prepare_blockkeys_stream(fseq_ctx *c)
 }
 size_t chain_hist_words(uint32_t m) { return (size_t) chainmulti_parts(m) * CS_BINS; }
 
-// streamed rows: pass 2's chain step as a radix sort + range maxima in a workspace per workgroup (fseq_chainsort.hpp), a block's
-// tasks on one workgroup, the ngrp groups of d_red_p2grp taken from the counter behind them
-int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp)
+// FSEQ_P2_RUN_CAP: the most runs of equal class a task of pass 2's streamed chain step may form and still be moved by runs
+// (0: every task sorts its rows; unset: what the kernel's LDS holds)
+uint32_t pass2_run_cap(fseq_ctx const *c)
+{
+	return c->tune.p2_run_cap < 0 ? P2_RUN_CAP : std::min<uint32_t>((uint32_t) c->tune.p2_run_cap, P2_RUN_CAP);
+}
+
+// streamed rows: pass 2's chain step by runs or as a radix sort, + range maxima, in a workspace per workgroup (fseq_chainsort.hpp),
+// a block's tasks on one workgroup, the ngrp groups of d_red_p2grp taken from the counter behind them; stats: P2_STATS zeroed
+// device words (fseq_debug_pass2_paths)
+int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats)
 {
 	uint32_t const m = c->p.m;
 	hipStream_t st = c->stream;
@@ -146,9 +154,16 @@ int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp)
 	size_t const fit = c->d_ws.cap / pass2_ws_words(m);
 	uint32_t const grid = (uint32_t) std::min<size_t>(std::min<size_t>(ngrp, fit), (size_t) std::max(ncu, 1) * 2u);
 	if (!grid) return fail(c, FSEQ_E_OOM, "pass 2: the workspace holds no chain step");
+	if (c->tune.debug)
+	{
+		int resident = 0;
+		(void) hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, k_chain_snap_grouped, (int) ST, pass2_lds_bytes());
+		fprintf(stderr, "[fseq] pass 2 chain steps: %u groups on %u workgroups (the workspace holds %zu, a CU %d), %zu bytes of LDS, at most %u runs\n", ngrp, grid, fit,
+		        resident, pass2_lds_bytes(), pass2_run_cap(c));
+	}
 	hipLaunchKernelGGL(k_chain_snap_grouped, dim3(grid), dim3(ST), pass2_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
 	                   c->d_red_headd, c->d_red_ncls, c->red_cap, c->d_red_p2grp.as<uint2 const>(), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
-	                   c->d_snap_a, c->d_snap_d, c->d_ws.base);
+	                   c->d_snap_a, c->d_snap_d, c->d_ws.base, pass2_run_cap(c), stats);
 	return FSEQ_OK;
 }
 

@@ -97,7 +97,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	if ((rc = c->d_red_ncls.ensure(c, S2))) return rc;
 	if ((rc = c->d_red_taskblk.ensure(c, S2))) return rc;
 	if ((rc = c->d_red_wgtasks.ensure(c, 4 * S2 + 64))) return rc;
-	if ((rc = c->d_red_p2grp.ensure(c, 2 * S2 + 4))) return rc;
+	if ((rc = c->d_red_p2grp.ensure(c, 2 * S2 + 2 + P2_STATS))) return rc;
 	if ((rc = c->d_cols.ensure(c, S2))) return rc;
 	// streamed rows: the groups of the chain-step kernel, a block's tasks each (blocks with tasks of that kernel only), the
 	// largest first, and behind them the counter the workgroups take them by
@@ -121,6 +121,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		std::stable_sort(g.begin(), g.end(), [](uint2 const &x, uint2 const &y) { return x.y > y.y; });
 		for (auto const &x : g) { p2grp.push_back(x.x); p2grp.push_back(x.y); }
 		p2grp.push_back(0u);
+		p2grp.insert(p2grp.end(), P2_STATS, 0u);                   // (the kernel's counters, zeroed with the counter)
 	}
 	// the task lists through pinned memory of their own (live until the synchronisation behind the kernels)
 	std::vector<uint32_t> hb, hw;
@@ -136,7 +137,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 	}
 	{
-		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256;
+		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256 + P2_STATS * 4;
 		if (c->red_pin2_bytes < need)
 		{
 			if (c->h_red_pin2) (void) hipHostFree(c->h_red_pin2);
@@ -157,6 +158,8 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 			HIP_TRY(c, hipMemcpyAsync(c->d_red_wgtasks, put(hw.data(), hw.size() * 4), hw.size() * 4, hipMemcpyHostToDevice, st));
 		}
 	}
+	uint32_t *const pin_stats = reinterpret_cast<uint32_t *>(c->h_red_pin2 + c->red_pin2_bytes - P2_STATS * 4);      // (behind the task lists)
+	c->p2_stats_have = false;
 	HIP_TRY(c, hipEventRecord(c->ev[6], st));
 	progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 	RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
@@ -177,8 +180,15 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	else
 	{
 		// streamed rows: a block's tasks on one workgroup, the groups taken from a counter
-		uint32_t const ngrp = (uint32_t) (p2grp.size() / 2);
-		if (ngrp && (rc = launch_chain_snap_grouped(c, ngrp))) return rc;
+		uint32_t const ngrp = (uint32_t) ((p2grp.size() - 1 - P2_STATS) / 2);
+		if (ngrp)
+		{
+			uint32_t *const stats = c->d_red_p2grp + 2 * (size_t) ngrp + 1;
+			if ((rc = launch_chain_snap_grouped(c, ngrp, stats))) return rc;
+			// (its counters come back with the synchronisation behind pass 2)
+			HIP_TRY(c, hipMemcpyAsync(pin_stats, stats, P2_STATS * 4, hipMemcpyDeviceToHost, st));
+			c->p2_stats_have = true;
+		}
 	}
 	for (size_t i = 0; i < S2; ++i)
 		if (ncls0[i] == 0u && rbs[i] % c->B != 0) cells += (uint64_t) m * 4u;      // (a step is ~4 digit passes over the rows)
@@ -211,6 +221,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(st));
 	range_p2.end();
+	if (c->p2_stats_have) memcpy(c->p2_stats, pin_stats, sizeof(c->p2_stats));
 	progress(c, FSEQ_STAGE_SAMPLES, S2, S2);
 	float f = 0;
 	HIP_TRY(c, hipEventElapsedTime(&f, c->ev[6], c->ev[7])); R.ms_p2 = f;
@@ -224,6 +235,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 int long_pass2(fseq_ctx *c, LongRun &R)
 {
 	FSEQ_LONG_LOCALS(c);
+	c->p2_stats_have = false;
 	if (c->red_active) return long_pass2_reduced(c, R);
 	uint64_t &pass2_cells = R.pass2_cells;
 	double &ms_p2 = R.ms_p2;

@@ -71,6 +71,14 @@ int  fseq_debug_device_bytes(fseq_ctx *ctx, uint64_t *now, uint64_t *peak, int r
  * *bits bits.  out == NULL: *ld and *bits only.  Not for sharded contexts (a rank holds its own columns only). */
 int  fseq_debug_packed_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t *out, uint64_t *ld, uint32_t *bits);
 
+/* Which way the boundaries of the last run went through pass 2's chain step on streamed rows behind the reduced phase C
+ * (k_chain_snap_grouped): boundaries moved as runs of equal class (*by_runs), boundaries whose rows were all sorted
+ * (*by_sort: more runs than FSEQ_P2_RUN_CAP, the knob at 0, or a class and a position that do not share a 32-bit word),
+ * boundaries on a block border (*copies) and the most runs a boundary formed, over those that counted theirs (*max_runs);
+ * runs_hist (19 words, or NULL): those boundaries by run count, [b] = how many formed more than 2^(b - 1) and at most 2^b
+ * runs ([0]: one run).  All zero where the last run did not go through that kernel (LDS-resident rows, no representatives). */
+int  fseq_debug_pass2_paths(fseq_ctx *ctx, uint32_t *by_runs, uint32_t *by_sort, uint32_t *copies, uint32_t *max_runs, uint32_t *runs_hist);
+
 #ifdef __cplusplus
 }
 #endif
