@@ -609,19 +609,7 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 constexpr uint32_t CM_PART = 1024;               // positions per part (one wave: 16 groups of 64)
 constexpr uint32_t CM_WG = 256;                  // threads per workgroup of the part kernels: four parts
 
-struct ChainMultiArgs {
-	uint32_t const *rank, *keyd, *nkeys;         // the key blocks of the level below
-	uint32_t m, nb_total, G;
-	uint64_t cols_per_block;
-	uint32_t *ws;                                // [chains of the launch][chainsort_ws_words(m)]
-	uint32_t *hist;                              // [chains of the launch][parts][CS_BINS]
-	uint32_t const *start_a, *start_d;
-	uint32_t *out_state_a, *out_state_d, *out_rank, *out_keyd, *out_nkeys;
-	uint32_t grp0;
-	uint32_t step;                               // block b0 + step of every chain
-	uint32_t pass;                               // radix pass of the sweep kernels
-	uint32_t nchains;                            // chains of the launch (the grid's y is rounded up to the XCDs: cm_wg)
-};
+// (ChainMultiArgs: fseq_types.hpp -- phase B builds one per chain launch, the kernels here take it as it is)
 
 // [r5] Which (part group, chain) a workgroup of the part / row kernels takes.  The hardware hands consecutive workgroups to
 // the eight XCDs in turn, so with (x, y) = (part group, chain) taken as they come the twenty-five workgroups of a chain land

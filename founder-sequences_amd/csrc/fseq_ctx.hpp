@@ -30,21 +30,15 @@ struct KernelSet {
 	uint32_t T, E, sigma, cap;
 	size_t lds_colblock, lds_snap;
 	uint32_t scan_shift;                     // partition steps of this configuration may scan keys while every divergence is < 2^scan_shift
-	void (*rank)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t npass, uint32_t bsh,
-	             uint32_t *, uint32_t *, uint32_t *, uint64_t col0, uint32_t const *only);
-	void (*snap)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t npass, uint32_t bsh,
-	             uint32_t const *, uint32_t const *, uint64_t const *, uint2 const *, uint32_t *, uint32_t *,
-	             uint64_t const *task_src, uint32_t snap_stride, uint32_t const *ss_a, uint32_t const *ss_d, uint32_t keyed);
+	// (the launchers take the views of fseq_types.hpp and write out the kernel's parameter list)
+	void (*rank)(hipStream_t st, uint32_t grid, size_t lds, PhaseAArgs const &keys);
+	void (*snap)(hipStream_t st, uint32_t grid, size_t lds, SnapArgs const &tasks);
 	size_t (*columns_lds)(uint32_t B);
-	void (*columns)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t,
-	                uint32_t const *, uint32_t const *, uint32_t, uint32_t, uint32_t, uint2 *, uint4 *, uint32_t npass, uint32_t bsh,
-	                uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, uint32_t block0, uint32_t *done_host, uint32_t epoch, uint32_t const *colmask, uint32_t const *blocklist);
+	void (*columns)(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &cols);      // (cols.colmask: the kernel that takes dense columns in one digit pass)
 	uint32_t (*columns_resident)(size_t lds);                 // workgroups of k_columns one CU holds
 	size_t lds_chain;
-	void (*chain)(hipStream_t, uint32_t grid, size_t lds, uint32_t const *rank, uint32_t const *keyd, uint32_t const *nkeys, uint32_t m,
-	              uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *start_a, uint32_t const *start_d,
-	              uint32_t *out_a, uint32_t *out_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t grp0, uint32_t keyed);
-	hipError_t (*prepare)(size_t lds_columns);
+	void (*chain)(hipStream_t st, uint32_t grid, size_t lds, ChainMultiArgs const &chains, uint32_t keyed);
+	hipError_t (*prepare)();
 	hipError_t (*prepare_columns)(size_t lds_columns);
 };
 
@@ -56,20 +50,18 @@ inline hipError_t allow_lds(K kernel, size_t bytes)
 }
 
 struct Stream2Config { uint32_t T, E, key_shift; size_t (*lds)(uint32_t colbytes); hipError_t (*prepare)(size_t lds);
-	void (*launch)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *,
-	               uint32_t, uint32_t, uint32_t, uint2 *, uint4 *, uint32_t, uint32_t *, uint32_t *, uint32_t, uint32_t *, uint32_t, uint32_t, uint32_t const *blocklist);
+	void (*launch)(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &cols);
 	uint32_t (*resident)(size_t lds);
 	// pass 2 on the same tile step: k_columns_stream2<.., S2_SNAP>
-	void (*launch_snap)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *, size_t, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *,
-	                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &); };
+	void (*launch_snap)(hipStream_t st, uint32_t grid, size_t lds, SnapArgs const &tasks); };
 // [r5] phase C on representative rows (fseq_reduced.hpp; the kernels live in csrc/fseq_reduced.hip)
 struct ReducedSet {
 	uint32_t T, E, rows, values;             // rows: representatives a workgroup holds; values: distinct start values (fewer than rows: the slim configuration)
 	bool pk, ew;
 	size_t (*lds)(uint32_t B, uint32_t symcap);   // symcap: bytes of each staged-column buffer (RedArgs)
 	hipError_t (*prepare)(size_t lds);
-	void (*launch)(hipStream_t, uint32_t grid, size_t lds, uint8_t const *red_msa, size_t red_ld, uint64_t n, uint32_t B, uint32_t L, uint32_t X, uint32_t stride,
-	               uint2 *ent, uint4 *hdr, uint32_t npass, uint32_t bsh, RedArgs const &);
+	// (cols: the alignment the representatives' symbols are read from -- RedArgs::direct -- and the lists; the rest comes with red)
+	void (*launch)(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &cols, RedArgs const &red);
 	uint32_t (*resident)(size_t lds);
 };
 // the smallest configuration that holds `rows` representatives (index into the list; -1: none)
@@ -79,26 +71,22 @@ bool reduced_config(int index, ReducedSet *out);
 struct ChainSnapSet {
 	size_t lds;
 	hipError_t (*prepare)();
-	void (*launch)(hipStream_t, uint32_t grid, size_t lds, uint32_t const *bstate_a, uint32_t const *bstate_d, uint32_t const *rank, uint32_t m,
-	               uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls, uint32_t cap, uint32_t *snap_a, uint32_t *snap_d, uint32_t keyed);
+	// (tasks: the blocks' boundary states, task_blk, the snapshots, keyed; red: rank, m_true, cap and the class tables)
+	void (*launch)(hipStream_t st, uint32_t grid, size_t lds, SnapArgs const &tasks, RedArgs const &red);
 };
 bool select_chain_snap(uint32_t T, uint32_t E, ChainSnapSet *out);
 
 // the kernel configurations and their launchers (csrc/fseq_kernelsets.hip)
 bool select_kernels(uint32_t m, uint32_t sigma, KernelSet *out);
 Stream2Config stream2_config();
-void launch_blockkeys(uint32_t T, hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-                      uint32_t bsh, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0,
-                      uint16_t *scratch, size_t scratch_per_block, uint32_t cap_words, uint32_t *sliced, uint32_t *todo, uint32_t const *only = nullptr);
+void launch_blockkeys(hipStream_t st, uint32_t grid, size_t lds, PhaseAArgs const &keys);       // (k_blockkeys<keys.T>)
 hipError_t prepare_blockkeys(uint32_t T, size_t lds, bool debug);
 uint32_t blocktrie_threads(uint32_t m, bool stream);
 size_t blocktrie_lds(uint32_t T);
-hipError_t launch_blocktrie(uint32_t bits, uint32_t T, hipStream_t st, uint32_t groups, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-                            uint32_t nblk, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0, uint32_t *ws, size_t per, uint32_t *given_up, uint32_t *todo);
+hipError_t launch_blocktrie(hipStream_t st, uint32_t groups, PhaseAArgs const &keys);           // (k_blocktrie<8 >> bsh, keys.T>)
 hipError_t launch_reduce_prep(hipStream_t, uint32_t grid, RedPrepArgs const &);
 void launch_reduce_check(hipStream_t, uint32_t const *cnt, uint32_t const *planned, uint32_t count, uint32_t *flags);
-void launch_reduce_msa(hipStream_t, uint32_t nblocks_listed, uint32_t max_rows, uint8_t const *msa, size_t ld, uint8_t *red, size_t ldr, uint32_t const *cnt,
-                       uint32_t const *rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t bsh, uint32_t const *blocks, uint32_t m, bool gather_only);
+void launch_reduce_msa(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &red, bool gather_only);
 
 inline double now_ms()
 {

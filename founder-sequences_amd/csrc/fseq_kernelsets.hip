@@ -2,7 +2,8 @@
 // kernels by row count (select_kernels); phase A's key-space tree and trie by workgroup size and the streamed phase C's tile
 // configuration (stream2_config) are csrc/fseq_kernelsets_stream.hip.  A translation unit of its own since round 5 (the review's "split fseq_api.hip"): these
 // template instantiations were two thirds of what a rebuild of csrc/fseq_api.hip cost, and nothing in the orchestration
-// touches them but through the function tables of fseq_ctx.hpp (KernelSet, Stream2Config).
+// touches them but through the function tables of fseq_ctx.hpp (KernelSet, Stream2Config).  A launcher takes the views of
+// fseq_types.hpp (the alignment, the key blocks, the lists, ...) and is the one place that writes out its kernel's parameter list.
 #include "fseq_ctx.hpp"
 #include "fseq_kernels.hpp"
 
@@ -15,33 +16,35 @@ namespace {
 // EW: phase C keeps wave 0 free of rows for the per-column list (k_columns, fseq_kernels.hpp): m <= (T - 64) * E
 template <int T, int E, int SIGMA, bool PK, bool EW = false>
 struct Launch {
-	static void rank(hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-	                 uint32_t nblocks, uint32_t npass, uint32_t bsh, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0, uint32_t const *only)
+	static void rank(hipStream_t st, uint32_t grid, size_t lds, PhaseAArgs const &K)
 	{
-		// (only: per-block filter, passed in the start-state slot the rank mode does not use -- k_colblock)
-		hipLaunchKernelGGL((k_colblock<T, E, SIGMA, MODE_RANK, PK>), dim3(grid), dim3(T), lds, st, msa, ld, m, n, B, nblocks, npass, bsh, rank_, keyd, nkeys,
-		                   only, (uint32_t const *) nullptr, (uint64_t const *) nullptr, (uint2 const *) nullptr,
-		                   (uint32_t *) nullptr, (uint32_t *) nullptr, (uint64_t const *) nullptr, 0u, (uint32_t const *) nullptr, (uint32_t const *) nullptr, col0,
-		                   (uint64_t) B < (1ull << scan_shift_for(T, E)) ? 1u : 0u);      // (divergences relative to the block start: <= B)
+		MsaArgs const &A = K.A;
+		// (only: the per-block filter goes in the start-state slot, which the rank mode does not use otherwise -- k_colblock)
+		hipLaunchKernelGGL((k_colblock<T, E, SIGMA, MODE_RANK, PK>), dim3(grid), dim3(T), lds, st, A.msa, A.ld, A.m, A.n, A.B, A.nblocks, A.npass, A.bsh, K.rank, K.keyd, K.nkeys,
+		                   K.only, (uint32_t const *) nullptr, (uint64_t const *) nullptr, (uint2 const *) nullptr,
+		                   (uint32_t *) nullptr, (uint32_t *) nullptr, (uint64_t const *) nullptr, 0u, (uint32_t const *) nullptr, (uint32_t const *) nullptr, K.col0,
+		                   (uint64_t) A.B < (1ull << scan_shift_for(T, E)) ? 1u : 0u);      // (divergences relative to the block start: <= B)
 	}
-	static void snap(hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-	                 uint32_t nblocks, uint32_t npass, uint32_t bsh, uint32_t const *ba, uint32_t const *bd, uint64_t const *rb, uint2 const *grp, uint32_t *sa, uint32_t *sd,
-	                 uint64_t const *task_src, uint32_t snap_stride, uint32_t const *ss_a, uint32_t const *ss_d, uint32_t keyed)
+	static void snap(hipStream_t st, uint32_t grid, size_t lds, SnapArgs const &S)
 	{
-		hipLaunchKernelGGL((k_colblock<T, E, SIGMA, MODE_SNAP, PK>), dim3(grid), dim3(T), lds, st, msa, ld, m, n, B, nblocks, npass, bsh,
-		                   (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, ba, bd, rb, grp, sa, sd, task_src, snap_stride, ss_a, ss_d, (uint64_t) 0, keyed);
+		MsaArgs const &A = S.A;
+		hipLaunchKernelGGL((k_colblock<T, E, SIGMA, MODE_SNAP, PK>), dim3(grid), dim3(T), lds, st, A.msa, A.ld, A.m, A.n, A.B, A.nblocks, A.npass, A.bsh,
+		                   (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, S.bstate_a, S.bstate_d, S.task_rb, S.task_grp, S.snap_a, S.snap_d,
+		                   S.task_src, S.ss.snap_stride, (uint32_t const *) S.ss.ss_a, (uint32_t const *) S.ss.ss_d, (uint64_t) 0, S.keyed);
 	}
 	static size_t columns_lds(uint32_t B) { return columns_lds_bytes<T, E, SIGMA, PK>(B); }
-	static void columns(hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-	                    uint32_t N2, uint32_t const *ba, uint32_t const *bd, uint32_t L, uint32_t X, uint32_t stride, uint2 *ent, uint4 *hdr, uint32_t npass, uint32_t bsh,
-	                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, uint32_t block0, uint32_t *done_host, uint32_t epoch, uint32_t const *colmask, uint32_t const *blocklist)
+	template <bool DENSE>
+	static void columns_as(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &C)
 	{
-		if (colmask)
-			hipLaunchKernelGGL((k_columns<T, E, SIGMA, PK, EW, true>), dim3(grid), dim3(T), lds, st, msa, ld, m, n, B, N2, ba, bd, L, X, stride, ent, hdr, npass, bsh,
-			                   snap_stride, ss_a, ss_d, block0, done_host, epoch, colmask, blocklist);
-		else
-			hipLaunchKernelGGL((k_columns<T, E, SIGMA, PK, EW, false>), dim3(grid), dim3(T), lds, st, msa, ld, m, n, B, N2, ba, bd, L, X, stride, ent, hdr, npass, bsh,
-			                   snap_stride, ss_a, ss_d, block0, done_host, epoch, (uint32_t const *) nullptr, blocklist);
+		MsaArgs const &A = C.A;
+		hipLaunchKernelGGL((k_columns<T, E, SIGMA, PK, EW, DENSE>), dim3(grid), dim3(T), lds, st, A.msa, A.ld, A.m, A.n, A.B, A.N2, C.bstate_a, C.bstate_d,
+		                   C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr, A.npass, A.bsh, C.ss.snap_stride, C.ss.ss_a, C.ss.ss_d,
+		                   C.block0, C.done_host, C.epoch, C.colmask, C.blocklist);
+	}
+	static void columns(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &C)
+	{
+		if (C.colmask) columns_as<true>(st, grid, lds, C);
+		else columns_as<false>(st, grid, lds, C);
 	}
 	static uint32_t columns_resident(size_t lds)
 	{
@@ -49,21 +52,17 @@ struct Launch {
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_columns<T, E, SIGMA, PK, EW>, T, lds) != hipSuccess || nb < 1) nb = 1;
 		return (uint32_t) nb;
 	}
-	static void chain(hipStream_t st, uint32_t grid, size_t lds, uint32_t const *rank_, uint32_t const *keyd, uint32_t const *nkeys, uint32_t m,
-	                  uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *start_a, uint32_t const *start_d,
-	                  uint32_t *out_a, uint32_t *out_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t grp0, uint32_t keyed)
+	static void chain(hipStream_t st, uint32_t grid, size_t lds, ChainMultiArgs const &C, uint32_t keyed)
 	{
-		hipLaunchKernelGGL((k_chain<T, E, PK>), dim3(grid), dim3(T), lds, st, rank_, keyd, nkeys, m, nb_total, G, cols_per_block,
-		                   start_a, start_d, out_a, out_d, out_rank, out_keyd, out_nkeys, grp0, keyed);
+		hipLaunchKernelGGL((k_chain<T, E, PK>), dim3(grid), dim3(T), lds, st, C.rank, C.keyd, C.nkeys, C.m, C.nb_total, C.G, C.cols_per_block,
+		                   C.start_a, C.start_d, C.out_state_a, C.out_state_d, C.out_rank, C.out_keyd, C.out_nkeys, C.grp0, keyed);
 	}
-	static hipError_t prepare(size_t lds_columns)
+	static hipError_t prepare()
 	{
 		hipError_t e;
 		if ((e = allow_lds(k_colblock<T, E, SIGMA, MODE_RANK, PK>, colblock_lds_bytes<T, E, SIGMA, MODE_RANK, PK>())) != hipSuccess) return e;
 		if ((e = allow_lds(k_colblock<T, E, SIGMA, MODE_SNAP, PK>, colblock_lds_bytes<T, E, SIGMA, MODE_SNAP, PK>())) != hipSuccess) return e;
-		if ((e = allow_lds(k_chain<T, E, PK>, chain_lds_bytes<T, E, PK>())) != hipSuccess) return e;
-		(void) lds_columns;
-		return hipSuccess;
+		return allow_lds(k_chain<T, E, PK>, chain_lds_bytes<T, E, PK>());
 	}
 	static hipError_t prepare_columns(size_t lds_columns)
 	{

@@ -1,6 +1,6 @@
 // fseq_kernelsets_stream.hip -- launchers by configuration, second part (csrc/fseq_kernelsets.hip): phase A's key-space tree
 // (k_blockkeys) and trie (k_blocktrie) by workgroup size and bits per symbol, the streamed phase C's tile configurations
-// (k_columns_stream2, stream2_config).
+// (k_columns_stream2, stream2_config).  They take the views of fseq_types.hpp, as the launchers of the first part do.
 #include "fseq_ctx.hpp"
 #include "fseq_kernels.hpp"
 #include "fseq_stream.hpp"
@@ -24,19 +24,23 @@ hipError_t s2_prepare(size_t bytes)
 	if (e != hipSuccess) return e;
 	return allow_lds(k_columns_stream2<S2_T, S2_E, S2_SNAP>, bytes);
 }
-void s2_launch_snap(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
-                    uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, S2SnapArgs const &SN)
+void s2_launch_snap(hipStream_t st, uint32_t grid, size_t bytes, SnapArgs const &S)
 {
-	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E, S2_SNAP>), dim3(grid), dim3(S2_T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, 0u, 0u, 0u, (uint2 *) nullptr, (uint4 *) nullptr,
-	                   snap_stride, ss_a, ss_d, 0u, (uint32_t *) nullptr, 0u, 0u, SN);
-}
-void s2_launch(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t npass, uint32_t bsh, uint32_t *ws,
-               uint32_t L, uint32_t X, uint32_t stride, uint2 *ent, uint4 *hdr, uint32_t snap_stride, uint32_t *ss_a, uint32_t *ss_d, uint32_t block0, uint32_t *done, uint32_t epoch, uint32_t ss_pack,
-               uint32_t const *blocklist)
-{
+	MsaArgs const &A = S.A;
 	S2SnapArgs SN{};
-	SN.wg_block = blocklist;
-	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E>), dim3(grid), dim3(S2_T), bytes, st, msa, ld, m, n, B, npass, bsh, ws, L, X, stride, ent, hdr, snap_stride, ss_a, ss_d, block0, done, epoch, ss_pack, SN);
+	SN.wg_block = S.wg_block; SN.wg_groups = S.wg_groups; SN.grp_tasks = S.task_grp; SN.grp_src = S.task_src; SN.task_rb = S.task_rb;
+	SN.snap_a = S.snap_a; SN.snap_d = S.snap_d; SN.bs_w = S.bs_w; SN.bs_h = S.bs_h;
+	// (no lists, no launch window)
+	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E, S2_SNAP>), dim3(grid), dim3(S2_T), bytes, st, A.msa, A.ld, A.m, A.n, A.B, A.npass, A.bsh, S.ws, 0u, 0u, 0u, (uint2 *) nullptr, (uint4 *) nullptr,
+	                   S.ss.snap_stride, S.ss.ss_a, S.ss.ss_d, 0u, (uint32_t *) nullptr, 0u, 0u, SN);
+}
+void s2_launch(hipStream_t st, uint32_t grid, size_t bytes, ColumnsArgs const &C)
+{
+	MsaArgs const &A = C.A;
+	S2SnapArgs SN{};
+	SN.wg_block = C.blocklist;
+	hipLaunchKernelGGL((k_columns_stream2<S2_T, S2_E>), dim3(grid), dim3(S2_T), bytes, st, A.msa, A.ld, A.m, A.n, A.B, A.npass, A.bsh, C.ws, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr,
+	                   C.ss.snap_stride, C.ss.ss_a, C.ss.ss_d, C.block0, C.done_host, C.epoch, C.ss.ss_pack | (C.ss.ids ? S2_SS_IDS : 0u), SN);
 }
 uint32_t s2_resident(size_t bytes)
 {
@@ -49,14 +53,13 @@ uint32_t s2_resident(size_t bytes)
 // phase A in key space, LDS-resident rows (fseq_blockkeys.hpp): the kernel has its own workgroup size, one thread
 // per 8 rows where that fits (blockkeys_threads)
 #define FSEQ_BK_SIZES(X) X(256) X(320) X(512) X(768) X(1024)
-void launch_blockkeys(uint32_t T, hipStream_t st, uint32_t grid, size_t lds, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-                      uint32_t bsh, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0,
-                      uint16_t *scratch, size_t scratch_per_block, uint32_t cap_words, uint32_t *sliced, uint32_t *todo, uint32_t const *only)
+void launch_blockkeys(hipStream_t st, uint32_t grid, size_t lds, PhaseAArgs const &K)
 {
-	switch (T)
+	MsaArgs const &A = K.A;
+	switch (K.T)
 	{
-#define X(T_) case T_: hipLaunchKernelGGL((k_blockkeys<T_>), dim3(grid), dim3(T_), lds, st, msa, ld, m, n, B, bsh, rank_, keyd, nkeys, col0, \
-	                                          scratch, scratch_per_block, cap_words, sliced, todo, only); break;
+#define X(T_) case T_: hipLaunchKernelGGL((k_blockkeys<T_>), dim3(grid), dim3(T_), lds, st, A.msa, A.ld, A.m, A.n, A.B, A.bsh, K.rank, K.keyd, K.nkeys, K.col0, \
+	                                          static_cast<uint16_t *>(K.work), K.work_per, K.cap_words, K.counters, K.todo, K.only); break;
 		FSEQ_BK_SIZES(X)
 #undef X
 		default: break;
@@ -88,15 +91,17 @@ hipError_t prepare_blockkeys(uint32_t T, size_t lds, bool debug)
 // phase A, the trie over 32-bit group words (fseq_blocktrie.hpp): T threads by the row count (12 T classes fit), bits per symbol
 uint32_t blocktrie_threads(uint32_t m, bool stream) { return stream || m > 12u * 512u ? 1024u : m > 12u * 256u ? 512u : 256u; }
 size_t blocktrie_lds(uint32_t T) { return T == 256u ? BtGeom<256>::LDS_BYTES : T == 512u ? BtGeom<512>::LDS_BYTES : BtGeom<1024>::LDS_BYTES; }
-hipError_t launch_blocktrie(uint32_t bits, uint32_t T, hipStream_t st, uint32_t groups, uint8_t const *msa, size_t ld, uint32_t m, uint64_t n, uint32_t B,
-                            uint32_t nblk, uint32_t *rank_, uint32_t *keyd, uint32_t *nkeys, uint64_t col0, uint32_t *ws, size_t per, uint32_t *given_up, uint32_t *todo)
+hipError_t launch_blocktrie(hipStream_t st, uint32_t groups, PhaseAArgs const &K)
 {
+	MsaArgs const &A = K.A;
+	uint32_t const bits = 8u >> A.bsh;
 #define FSEQ_BT_CASE(BITS_, T_) \
-	if (bits == BITS_ && T == T_) \
+	if (bits == BITS_ && K.T == T_) \
 	{ \
 		hipError_t const e = allow_lds(k_blocktrie<BITS_, T_>, BtGeom<T_>::LDS_BYTES); \
 		if (e != hipSuccess) return e; \
-		hipLaunchKernelGGL((k_blocktrie<BITS_, T_>), dim3(groups), dim3(T_), BtGeom<T_>::LDS_BYTES, st, msa, ld, m, n, B, nblk, rank_, keyd, nkeys, col0, ws, per, given_up, todo); \
+		hipLaunchKernelGGL((k_blocktrie<BITS_, T_>), dim3(groups), dim3(T_), BtGeom<T_>::LDS_BYTES, st, A.msa, A.ld, A.m, A.n, A.B, K.nblk, K.rank, K.keyd, K.nkeys, K.col0, \
+		                   static_cast<uint32_t *>(K.work), K.work_per, K.counters, K.todo); \
 		return hipSuccess; \
 	}
 	FSEQ_BT_CASE(2, 256) FSEQ_BT_CASE(2, 512) FSEQ_BT_CASE(2, 1024)

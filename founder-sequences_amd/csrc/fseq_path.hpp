@@ -1,5 +1,6 @@
 // fseq_path.hpp -- what the units of the segmentation path share, and nothing else of the library needs: the state of one
-// long-path run, the aliases and ranges of its phases, the path's constants, and the functions that cross a unit.
+// long-path run, the aliases and ranges of its phases, the path's constants, the views of a context that the launchers take
+// (msa_args, list_args, stride_states), and the functions that cross a unit.
 //   csrc/fseq_api.hip         the entry points of include/fseq.h, what a new input or knob makes a context forget
 //   csrc/fseq_api_debug.hip   the entry points of include/fseq_debug.h, the row-sharded conformance sweep
 //   csrc/fseq_path_setup.hip  pinned staging, geometry, work buffers, the row upload, the shard exchange
@@ -93,6 +94,19 @@ struct LongRun {
 inline uint64_t held_lo(fseq_ctx const *c) { return c->sh.on ? c->sh.c_lo : 0; }
 inline uint64_t held_hi(fseq_ctx const *c) { return c->sh.on ? c->sh.c_end : c->p.n; }
 
+// ---- the views of a context that the launchers take (fseq_types.hpp)
+// the alignment: all of it in the context's blocks, or the columns [0, n) in nblocks blocks of B (a rank of a sharded run
+// covers its own columns and the halo; the short path takes all columns as one block)
+inline MsaArgs msa_args(fseq_ctx const *c, uint64_t n, uint32_t B, uint32_t nblocks)
+{
+	MsaArgs A;
+	A.msa = c->d_msa; A.ld = c->ld; A.m = c->p.m; A.n = n; A.B = B; A.nblocks = nblocks; A.N2 = c->N2; A.npass = c->npass; A.bsh = c->bsh;
+	return A;
+}
+inline MsaArgs msa_args(fseq_ctx const *c) { return msa_args(c, c->p.n, c->B, c->nblocks); }
+inline ListArgs list_args(fseq_ctx const *c) { return ListArgs{(uint32_t) c->p.segment_length, c->X, c->stride, c->d_ent, c->d_hdr}; }
+inline StrideStates stride_states(fseq_ctx const *c) { return StrideStates{c->snap_stride, c->d_ss_a, c->d_ss_d, c->ss_pack, c->ss_ids}; }
+
 // ---- csrc/fseq_api.hip
 void forget_run_history(fseq_ctx *c);
 
@@ -144,14 +158,14 @@ int prepare_stream_kernels(fseq_ctx *c, size_t lds);  // prepare_geometry: the L
 int prepare_stream2_prologue(fseq_ctx *c);            // ... and of the static kernels it launches (an attribute set on another unit's
 int prepare_blockkeys_stream(fseq_ctx *c);            //     copy of a static kernel would not reach the one launched)
 size_t chain_hist_words(uint32_t m);                 // digit histogram words of one chain of the streamed phase B (fseq_chainsort.hpp)
-// the streamed replay sweep of pass 2 (k_colblock_stream<MODE_SNAP>): the groups [0, groups) of d_grp / d_src, as many per
-// launch as the workspace holds
-void launch_replay_stream(fseq_ctx *c, size_t groups, uint64_t const *d_rb, uint2 const *d_grp, uint64_t const *d_src, uint32_t *out_a, uint32_t *out_d,
-                          uint32_t const *ss_a, uint32_t const *ss_d, uint32_t ss_pack);
+// the streamed replay sweep of pass 2 (k_colblock_stream<MODE_SNAP>): the groups [0, groups) of tasks.task_grp / task_src, as
+// many per launch as the workspace holds
+void launch_replay_stream(fseq_ctx *c, size_t groups, SnapArgs const &tasks);
 int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats);       // pass 2 behind the reduced phase C, streamed rows: the chain steps
 void red_fill_args(fseq_ctx *c, RedArgs &RA);
 struct RedLaunch { int config; uint32_t first, count; };
-int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, uint32_t const *blocks, uint32_t const *wg_tasks, uint2 *ent, uint4 *hdr, uint32_t X, uint32_t stride);
+// (base.blocks / base.wg_tasks: the lists the launches' [first, first + count) index; lists: the segment length alone in pass 2)
+int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists);
 void set_list_window(fseq_ctx *c, uint32_t lo_w);
 int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi);
 int run_long_path(fseq_ctx *c, fseq_result *res);

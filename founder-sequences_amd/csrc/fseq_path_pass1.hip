@@ -31,65 +31,68 @@ namespace {
 // streamed rows: occurrence keys while every column number fits 25 bits (FSEQ_PLAIN_SCAN: the has-based scan)
 bool stream_keyed(fseq_ctx const *c) { return c->p.n < (1ull << 25) && !c->tune.plain_scan; }
 
-// one launch of the streamed column sweep, the context's configuration and workspace in front of what the mode takes
-// (MODE_RANK, phase A: the key blocks out, bstate_a the per-block filter; MODE_SNAP, pass 2: the states at the boundaries task_rb out)
+// one launch of the streamed column sweep, the context's workspace behind the alignment: MODE_RANK (phase A) writes the key
+// blocks, MODE_SNAP (pass 2) the states at the boundaries tasks.task_rb
 template <int MODE>
-void launch_colblock_stream(fseq_ctx *c, uint32_t grid, uint32_t B, uint32_t nblocks, uint32_t *rank, uint32_t *keyd, uint32_t *nkeys, uint32_t const *bstate_a, uint32_t const *bstate_d,
-                            uint64_t const *task_rb, uint2 const *task_grp, uint32_t *snap_a, uint32_t *snap_d, uint64_t const *task_src, uint32_t snap_stride,
-                            uint32_t const *ss_a, uint32_t const *ss_d, uint64_t col0, uint32_t ss_pack)
+void launch_colblock_stream(fseq_ctx *c, uint32_t grid, MsaArgs const &A, PhaseAArgs const &K, SnapArgs const &S)
 {
-	fseq_params const &p = c->p;
-	hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE, true> : k_colblock_stream<MODE, false>), dim3(grid), dim3(ST), stream_lds_bytes(sym_bytes(p.m, c->bsh), c->stream_staged), c->stream, c->d_msa, c->ld, p.m, p.n, B, nblocks,
-	                   c->npass, c->bsh, c->d_ws.base, (uint32_t) c->stream_staged, rank, keyd, nkeys, bstate_a, bstate_d, task_rb, task_grp, snap_a, snap_d, task_src, snap_stride, ss_a, ss_d, col0, ss_pack);
+	// (K.only: the per-block filter goes in the start-state slot, which the rank mode does not use otherwise)
+	hipLaunchKernelGGL((stream_keyed(c) ? k_colblock_stream<MODE, true> : k_colblock_stream<MODE, false>), dim3(grid), dim3(ST), stream_lds_bytes(sym_bytes(A.m, A.bsh), c->stream_staged), c->stream,
+	                   A.msa, A.ld, A.m, A.n, A.B, A.nblocks, A.npass, A.bsh, c->d_ws.base, (uint32_t) c->stream_staged, K.rank, K.keyd, K.nkeys, MODE == MODE_RANK ? K.only : S.bstate_a, S.bstate_d,
+	                   S.task_rb, S.task_grp, S.snap_a, S.snap_d, S.task_src, S.ss.snap_stride, (uint32_t const *) S.ss.ss_a, (uint32_t const *) S.ss.ss_d, K.col0, S.ss.ss_pack);
 }
 
-// only: per-block filter (blocks whose word is zero are skipped), or nullptr
-void launch_rank(fseq_ctx *c, uint32_t grid, uint32_t B, uint32_t nblocks, uint32_t *rank, uint32_t *keyd, uint32_t *nkeys, uint64_t col0 = 0, uint32_t const *only = nullptr)
+// phase A as a column sweep over the blocks of K
+void launch_rank(fseq_ctx *c, PhaseAArgs const &K)
 {
-	fseq_params const &p = c->p;
-	if (!grid) return;
-	if (c->use_stream)
-		launch_colblock_stream<MODE_RANK>(c, grid, B, nblocks, rank, keyd, nkeys, only, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, col0, 0u);
-	else
-		c->ks.rank(c->stream, grid, c->ks.lds_colblock, c->d_msa, c->ld, p.m, p.n, B, nblocks, c->npass, c->bsh, rank, keyd, nkeys, col0, only);
+	if (!K.nblk) return;
+	if (c->use_stream) launch_colblock_stream<MODE_RANK>(c, K.nblk, K.A, K, SnapArgs{});
+	else c->ks.rank(c->stream, K.nblk, c->ks.lds_colblock, K);
+}
+
+// phase A in key space, streamed rows (fseq_blockkeys.hpp): the blocks of K in turn on `groups` workgroups
+void launch_blockkeys_stream(fseq_ctx *c, uint32_t groups, PhaseAArgs const &K)
+{
+	MsaArgs const &A = K.A;
+	hipLaunchKernelGGL(k_blockkeys_stream, dim3(groups), dim3(1024), c->bk_lds, c->stream, A.msa, A.ld, A.m, A.n, A.B, A.bsh, K.nblk, K.rank, K.keyd, K.nkeys, K.col0,
+	                   static_cast<uint32_t *>(K.work), K.work_per, K.cap_words, K.counters, K.wide, K.todo, K.only);
 }
 
 } // namespace
 
-void launch_replay_stream(fseq_ctx *c, size_t groups, uint64_t const *d_rb, uint2 const *d_grp, uint64_t const *d_src, uint32_t *out_a, uint32_t *out_d,
-                          uint32_t const *ss_a, uint32_t const *ss_d, uint32_t ss_pack)
+void launch_replay_stream(fseq_ctx *c, size_t groups, SnapArgs const &tasks)
 {
 	// the streamed sweep needs 4m workspace words per workgroup: as many groups per launch as d_ws holds
 	size_t const cap = std::max<size_t>(1, c->d_ws.cap / (4 * (size_t) c->p.m));
+	SnapArgs S = tasks;
 	for (size_t g0 = 0; g0 < groups; g0 += cap)
-		launch_colblock_stream<MODE_SNAP>(c, (uint32_t) std::min(cap, groups - g0), c->B, c->nblocks, nullptr, nullptr, nullptr, c->d_bstate_a, c->d_bstate_d, d_rb, d_grp + g0,
-		                                  out_a, out_d, d_src + g0, c->snap_stride, ss_a, ss_d, 0, ss_pack);
+	{
+		S.task_grp = tasks.task_grp + g0; S.task_src = tasks.task_src + g0;
+		launch_colblock_stream<MODE_SNAP>(c, (uint32_t) std::min(cap, groups - g0), S.A, PhaseAArgs{}, S);
+	}
 }
 
 namespace {
 
-// grid chains grp0 .. grp0 + grid - 1, chain g over the key blocks [g * G, min(nb_total, (g + 1) * G))
-void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t const *keyd, uint32_t const *nkeys, uint32_t nb_total, uint32_t G,
-                  uint64_t cols_per_block, uint32_t const *start_a, uint32_t const *start_d, uint32_t *out_a, uint32_t *out_d,
-                  uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t grp0 = 0)
+// one chain launch of phase B (A: the level's key blocks, the start states, what comes out -- ChainMultiArgs); the launch
+// adds the rows and, streamed rows, its workspace
+void launch_chain(fseq_ctx *c, uint32_t grid, ChainMultiArgs A)
 {
 	if (!grid) return;
+	A.m = c->p.m;
 	// streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp), every sweep of a step a launch
 	// over (parts) x (chains): a chain of G blocks is G rounds of them.  ensure_work_buffers sized d_ws and d_cshist for the
 	// widest launch of phase B (a chain per chain_fan blocks, plus one, in d_cshist; chainsort_ws_words(m)
 	// <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
 	if (c->use_stream)
 	{
-		uint32_t const m = c->p.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
-		ChainMultiArgs A;
-		A.rank = rank; A.keyd = keyd; A.nkeys = nkeys; A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block;
-		A.ws = c->d_ws.base; A.hist = c->d_cshist; A.start_a = start_a; A.start_d = start_d; A.out_state_a = out_a; A.out_state_d = out_d;
-		A.out_rank = out_rank; A.out_keyd = out_keyd; A.out_nkeys = out_nkeys; A.grp0 = grp0; A.step = 0; A.pass = 0;
+		uint32_t const m = A.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
+		A.ws = c->d_ws.base; A.hist = c->d_cshist; A.step = 0; A.pass = 0;
 		A.nchains = grid;
 		uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
 		dim3 const by_row((m + CM_WG - 1u) / CM_WG, grid_y), by_part((nparts + CM_WG / WAVE - 1u) / (CM_WG / WAVE), grid_y);
 		hipLaunchKernelGGL(k_cm_init, by_row, dim3(CM_WG), 0, c->stream, A);
-		for (uint32_t s_ = 0; s_ < G; ++s_)
+		for (uint32_t s_ = 0; s_ < A.G; ++s_)
 		{
 			A.step = s_;
 			for (uint32_t ps = 0; ps < npass; ++ps)
@@ -101,11 +104,10 @@ void launch_chain(fseq_ctx *c, uint32_t grid, uint32_t const *rank, uint32_t con
 			}
 			hipLaunchKernelGGL(k_cm_output, by_row, dim3(CM_WG), 0, c->stream, A);
 		}
-		if (out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), c->stream, A, G);
+		if (A.out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), c->stream, A, A.G);
 	}
 	else
-		c->ks.chain(c->stream, grid, c->ks.lds_chain, rank, keyd, nkeys, c->p.m, nb_total, G, cols_per_block, start_a, start_d, out_a, out_d,
-		            out_rank, out_keyd, out_nkeys, grp0, scan_keyed(c));
+		c->ks.chain(c->stream, grid, c->ks.lds_chain, A, scan_keyed(c));
 }
 
 } // namespace
@@ -230,7 +232,13 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	bool const tree_after = tree && !(trie && c->bt_given_up == 0);
 	R.trie_ran = trie;
 	R.trie_alone = trie && !tree_after;
-	uint32_t const *only = nullptr;
+	// my key blocks, and what the key-space tree works with; the trie hands the tree its blocks, the tree hands the sweep its own
+	PhaseAArgs keys;
+	keys.A = msa_args(c);
+	keys.rank = c->d_rank + (size_t) b_lo * m; keys.keyd = c->d_keyd + (size_t) b_lo * m; keys.nkeys = c->d_nkeys + b_lo;
+	keys.col0 = (uint64_t) b_lo * c->B; keys.nblk = my_blocks;
+	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words; keys.counters = c->d_flags + 64; keys.todo = todo;
+	keys.wide = (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u);
 	if (trie)
 	{
 		int ncu = 0;
@@ -241,10 +249,10 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		if ((rc = c->d_btws.ensure(c, per * groups))) return rc;
 		if ((rc = c->d_only.ensure(c, my_blocks))) return rc;
 		HIP_TRY(c, hipMemsetAsync(c->d_only, 0, (size_t) my_blocks * 4, st));
-		HIP_TRY(c, launch_blocktrie(bt_bits, bt_T, st, groups, c->d_msa, c->ld, m, n, c->B, my_blocks,
-		                            c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
-		                            c->d_btws, per, c->d_flags + 66, c->d_only));
-		only = c->d_only;
+		PhaseAArgs T = keys;
+		T.T = bt_T; T.work = c->d_btws; T.work_per = per; T.counters = c->d_flags + 66; T.todo = c->d_only;
+		HIP_TRY(c, launch_blocktrie(st, groups, T));
+		keys.only = c->d_only;
 	}
 	if (tree_after && c->use_stream)
 	{
@@ -254,9 +262,8 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		uint32_t const groups = std::min<uint32_t>(my_blocks, (uint32_t) std::max(1, ncu));
 		size_t const per = (blockkeys_stream_ws_words(m, c->B, c->bsh) + 15) & ~size_t(15);
 		if ((rc = c->d_bkws.ensure(c, per * groups))) return rc;
-		hipLaunchKernelGGL(k_blockkeys_stream, dim3(groups), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, n, c->B, c->bsh, my_blocks,
-		                   c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
-		                   c->d_bkws, per, c->bk_cap_words, c->d_flags + 64, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), todo, only);
+		keys.work = c->d_bkws; keys.work_per = per;
+		launch_blockkeys_stream(c, groups, keys);
 	}
 	else if (tree_after)
 	{
@@ -265,12 +272,15 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		if (c->bk_per_block != per) c->d_bk.release(c);
 		if ((rc = c->d_bk.ensure(c, per * my_blocks))) return rc;
 		c->bk_per_block = per;
-		launch_blockkeys(c->bk_T, st, my_blocks, c->bk_lds, c->d_msa, c->ld, m, n, c->B, c->bsh, c->d_rank + (size_t) b_lo * m,
-		                 c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B, c->d_bk, per, c->bk_cap_words, c->d_flags + 64, todo, only);
+		keys.work = c->d_bk; keys.work_per = per;
+		launch_blockkeys(st, my_blocks, c->bk_lds, keys);
 	}
 	if (!keyspace || sweep_after)
-		launch_rank(c, my_blocks, c->B, c->nblocks, c->d_rank + (size_t) b_lo * m, c->d_keyd + (size_t) b_lo * m, c->d_nkeys + b_lo, (uint64_t) b_lo * c->B,
-		            keyspace && tree ? todo : nullptr);
+	{
+		// (the sweep takes what the tree gave up; without a tree, every block)
+		keys.only = keyspace && tree ? todo : nullptr;
+		launch_rank(c, keys);
+	}
 	HIP_TRY(c, hipEventRecord(c->ev[1], st));
 	if (sharded && c->tune.inject_failure_rank >= 0 && (uint32_t) c->tune.inject_failure_rank == sh.rank)
 		return fail(c, FSEQ_E_OOM, "injected failure (FSEQ_INJECT_FAILURE_RANK)");
@@ -308,13 +318,34 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 {
 	FSEQ_LONG_LOCALS(c);
 	(void) R;
+	// level 0: my key blocks and boundary states; level i: the composites of chain_fan key blocks of level i - 1 (fseq_ctx::levels)
 	auto rank_of = [&](size_t i) { return i ? c->levels[i - 1].rank : c->d_rank; };
 	auto keyd_of = [&](size_t i) { return i ? c->levels[i - 1].keyd : c->d_keyd; };
 	auto nkeys_of = [&](size_t i) { return i ? c->levels[i - 1].nkeys : c->d_nkeys; };
 	auto sa_of = [&](size_t i) { return i ? c->levels[i - 1].state_a : c->d_bstate_a; };
 	auto sd_of = [&](size_t i) { return i ? c->levels[i - 1].state_d : c->d_bstate_d; };
 	auto count_of = [&](size_t i) { return i ? c->levels[i - 1].count : c->nblocks; };
-	auto cols_of = [&](size_t i) { return i ? c->levels[i - 1].cols : (uint64_t) c->B; };
+	// the key blocks of level i in chains of G, the launch's first chain grp0
+	auto chains_of = [&](size_t i, uint32_t G, uint32_t grp0) {
+		ChainMultiArgs A{};
+		A.rank = rank_of(i); A.keyd = keyd_of(i); A.nkeys = nkeys_of(i); A.nb_total = count_of(i); A.G = G;
+		A.cols_per_block = i ? c->levels[i - 1].cols : (uint64_t) c->B; A.grp0 = grp0;
+		return A;
+	};
+	// compose level i: every chain, from the identity, into one key block of level i + 1
+	auto compose = [&](size_t i, uint32_t G, uint32_t grp0 = 0) {
+		ChainMultiArgs A = chains_of(i, G, grp0);
+		A.out_rank = rank_of(i + 1); A.out_keyd = keyd_of(i + 1); A.out_nkeys = nkeys_of(i + 1);
+		return A;
+	};
+	// expand level i: the state in front of each of its key blocks, every chain from the state level i + 1 holds for it (the
+	// top level: from the identity, unless the caller names a start)
+	auto expand = [&](size_t i, uint32_t G, uint32_t grp0 = 0) {
+		ChainMultiArgs A = chains_of(i, G, grp0);
+		if (i < c->levels.size()) { A.start_a = sa_of(i + 1); A.start_d = sd_of(i + 1); }
+		A.out_state_a = sa_of(i); A.out_state_d = sd_of(i);
+		return A;
+	};
 	if (!sharded)
 	{
 		// phase B: up the levels -- compose groups of G key blocks of a level into one key block of the next
@@ -322,14 +353,9 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		// expand every group from the boundary state the level above gave it (parallel)
 		uint32_t const G = c->chain_fan;
 		size_t const top = c->levels.size();
-		for (size_t i = 1; i <= top; ++i)
-			launch_chain(c, count_of(i), rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), G, cols_of(i - 1), nullptr, nullptr,
-			             nullptr, nullptr, rank_of(i), keyd_of(i), nkeys_of(i));
-		launch_chain(c, 1, rank_of(top), keyd_of(top), nkeys_of(top), count_of(top), count_of(top), cols_of(top), nullptr, nullptr,
-		             sa_of(top), sd_of(top), nullptr, nullptr, nullptr);
-		for (size_t i = top; i-- > 0;)
-			launch_chain(c, count_of(i + 1), rank_of(i), keyd_of(i), nkeys_of(i), count_of(i), G, cols_of(i), sa_of(i + 1), sd_of(i + 1),
-			             sa_of(i), sd_of(i), nullptr, nullptr, nullptr);
+		for (size_t i = 0; i < top; ++i) launch_chain(c, count_of(i + 1), compose(i, G));
+		launch_chain(c, 1, expand(top, count_of(top)));
+		for (size_t i = top; i-- > 0;) launch_chain(c, count_of(i + 1), expand(i, G));
 	}
 	else
 	{
@@ -342,12 +368,13 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		std::vector<uint32_t> lo(K + 1), hi(K + 1);
 		lo[0] = b_lo; hi[0] = b_hi;
 		for (uint32_t i = 1; i <= K; ++i) { lo[i] = lo[i - 1] / F; hi[i] = (hi[i - 1] + F - 1) / F; }
-		for (uint32_t i = 1; have && i <= K; ++i)
-			launch_chain(c, hi[i] - lo[i], rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), F, cols_of(i - 1), nullptr, nullptr,
-			             nullptr, nullptr, rank_of(i), keyd_of(i), nkeys_of(i), lo[i]);
-		if (have)
-			launch_chain(c, 1, rank_of(K), keyd_of(K), nkeys_of(K), count_of(K), Q, cols_of(K), nullptr, nullptr,
-			             nullptr, nullptr, c->d_hrank, c->d_hkeyd, c->d_hnkeys, sh.rank);
+		// the hyper key blocks (d_h*): Q composites of level K into mine, and -- every rank -- the chain over all NH of them
+		ChainMultiArgs mine = chains_of(K, Q, sh.rank), hyper{};
+		mine.out_rank = c->d_hrank; mine.out_keyd = c->d_hkeyd; mine.out_nkeys = c->d_hnkeys;
+		hyper.rank = c->d_hrank; hyper.keyd = c->d_hkeyd; hyper.nkeys = c->d_hnkeys; hyper.nb_total = hyper.G = NH; hyper.cols_per_block = (uint64_t) sh.bpr * c->B;
+		hyper.out_state_a = c->d_hstate_a; hyper.out_state_d = c->d_hstate_d;
+		for (uint32_t i = 0; have && i < K; ++i) launch_chain(c, hi[i + 1] - lo[i + 1], compose(i, F, lo[i + 1]));
+		if (have) launch_chain(c, 1, mine);
 		{
 			// xbuf: [hrank NH x m][hkeyd NH x m][hnkeys NH]
 			size_t const w = (size_t) NH * m;
@@ -363,15 +390,14 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 			HIP_TRY(c, hipMemcpyAsync(c->d_hkeyd, sh.xbuf + w, w * 4, hipMemcpyDeviceToDevice, st));
 			HIP_TRY(c, hipMemcpyAsync(c->d_hnkeys, sh.xbuf + 2 * w, (size_t) NH * 4, hipMemcpyDeviceToDevice, st));
 		}
-		launch_chain(c, 1, c->d_hrank, c->d_hkeyd, c->d_hnkeys, NH, NH, (uint64_t) sh.bpr * c->B, nullptr, nullptr,
-		             c->d_hstate_a, c->d_hstate_d, nullptr, nullptr, nullptr);
+		launch_chain(c, 1, hyper);
 		if (have)
 		{
-			launch_chain(c, 1, rank_of(K), keyd_of(K), nkeys_of(K), count_of(K), Q, cols_of(K), c->d_hstate_a, c->d_hstate_d,
-			             sa_of(K), sd_of(K), nullptr, nullptr, nullptr, sh.rank);
-			for (uint32_t i = K; i >= 1; --i)
-				launch_chain(c, hi[i] - lo[i], rank_of(i - 1), keyd_of(i - 1), nkeys_of(i - 1), count_of(i - 1), F, cols_of(i - 1), sa_of(i), sd_of(i),
-				             sa_of(i - 1), sd_of(i - 1), nullptr, nullptr, nullptr, lo[i]);
+			// (my hyper-block starts from the state the chain over the hyper key blocks left in front of it)
+			ChainMultiArgs top = expand(K, Q, sh.rank);
+			top.start_a = c->d_hstate_a; top.start_d = c->d_hstate_d;
+			launch_chain(c, 1, top);
+			for (uint32_t i = K; i-- > 0;) launch_chain(c, hi[i + 1] - lo[i + 1], expand(i, F, lo[i + 1]));
 			// the state behind my last block = in front of the next rank's hyper-block (or behind the whole alignment,
 			// which the expansion has written itself): my halo block starts from it
 			if (b_hi < c->nblocks)
@@ -453,6 +479,7 @@ void red_fill_args(fseq_ctx *c, RedArgs &RA)
 	RA.invalid = c->d_red_invalid; RA.any_invalid = c->d_red_invalid + c->nblocks; RA.cap = c->red_cap; RA.m_true = c->p.m;
 	RA.direct = c->red_direct ? 1u : 0u; RA.colbytes = sym_bytes(c->p.m, c->bsh); RA.rank = c->d_rank;
 	RA.ss_a = c->d_red_ss_a; RA.ss_d = c->d_red_ss_d; RA.ss_stride = c->red_ss_stride; RA.ss_cap = c->red_ss_cap;
+	RA.blocks = c->d_red_blocks;                               // (the plan's block lists: red_launch_all indexes them; pass 2 brings its own)
 }
 
 namespace {
@@ -510,11 +537,16 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	A.cnt = c->d_red_cnt; A.vmin = c->d_red_vmin; A.rows = c->d_red_rows; A.leaf = c->d_red_leaf; A.a = c->d_red_a; A.d = c->d_red_d;
 	A.invalid = c->d_red_invalid; A.flags = c->d_red_invalid + nbk;
 	HIP_TRY(c, launch_reduce_prep(st, my_blocks, A));
+	// the reduced alignment of the listed blocks (streamed rows), by the plan in force when it is queued
+	auto reduce_msa = [&] {
+		launch_reduce_msa(st, msa_args(c), ReducedMsaArgs{c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, c->d_red_blocks, c->red_listed, c->red_max_rows},
+		                  c->tune.reduced_msa_gather);
+	};
 	if (c->red_plan_valid && c->red_plan_X == X && c->red_force_full.size() == nbk)
 	{
 		launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, c->d_red_invalid + nbk);
 		if (!c->red_direct)
-			launch_reduce_msa(st, c->red_listed, c->red_max_rows, c->d_msa, c->ld, c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, n, c->B, c->bsh, c->d_red_blocks, m, c->tune.reduced_msa_gather);
+			reduce_msa();
 		c->tm.reduced_blocks = c->red_plan_blocks; c->tm.reduced_rows_mean = c->red_plan_rows_mean;
 		*use = true;
 		return FSEQ_OK;
@@ -635,7 +667,7 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	at += c->red_nfull;
 	HIP_TRY(c, hipMemcpyAsync(c->d_red_blocks, h_blocks, (size_t) at * 4, hipMemcpyHostToDevice, st));
 	if (!c->red_direct)
-		launch_reduce_msa(st, listed, max_rows, c->d_msa, c->ld, c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, n, c->B, c->bsh, c->d_red_blocks, m, c->tune.reduced_msa_gather);
+		reduce_msa();
 	c->red_plan_valid = true; c->red_plan_X = X;
 	c->red_plan_blocks = c->tm.reduced_blocks; c->red_plan_rows_mean = c->tm.reduced_rows_mean;
 	*use = true;
@@ -647,7 +679,7 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 // launches of the reduced column kernel over lists of workgroups, one per configuration, side by side: the first on the
 // context's stream, the others on streams of their own that wait for it and that it waits for
 
-int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, uint32_t const *blocks, uint32_t const *wg_tasks, uint2 *ent, uint4 *hdr, uint32_t X, uint32_t stride)
+int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists)
 {
 	FSEQ_LONG_LOCALS(c);
 	if (ls.empty()) return FSEQ_OK;
@@ -661,6 +693,11 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 	size_t main_i = 0;
 	for (size_t i = 1; i < ls.size(); ++i) if (ls[i].count > ls[main_i].count) main_i = i;
 	size_t side = 0;
+	// the representatives' symbols: the alignment's own columns (LDS-resident row counts), or the reduced alignment
+	ColumnsArgs C;
+	C.A = msa_args(c);
+	if (!c->red_direct) { C.A.msa = c->d_red_msa; C.A.ld = c->red_ld; }
+	C.lists = lists;
 	for (size_t i = 0; i < ls.size(); ++i)
 	{
 		ReducedSet rs;
@@ -669,8 +706,8 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 		RA.symcap = red_symcap(c, rs, c->red_direct);
 		size_t const lds = rs.lds(c->B, RA.symcap);
 		HIP_TRY(c, rs.prepare(lds));
-		RA.blocks = blocks + ls[i].first;
-		if (wg_tasks) RA.wg_tasks = wg_tasks + 3 * (size_t) ls[i].first;
+		RA.blocks = base.blocks + ls[i].first;
+		if (base.wg_tasks) RA.wg_tasks = base.wg_tasks + 3 * (size_t) ls[i].first;
 		hipStream_t s_ = st;
 		size_t const slot = (i != main_i && side < nside) ? side++ : nside;      // (nside: the context's stream)
 		if (slot < nside)
@@ -679,7 +716,7 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 			s_ = slot == 0 ? c->stream2 : c->red_st[slot - 1];
 			HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev[3], 0));
 		}
-		rs.launch(s_, ls[i].count, lds, c->red_direct ? c->d_msa : c->d_red_msa, c->red_direct ? c->ld : c->red_ld, n, c->B, (uint32_t) L, X, stride, ent, hdr, c->npass, c->bsh, RA);
+		rs.launch(s_, ls[i].count, lds, C, RA);
 		if (slot < nside) HIP_TRY(c, hipEventRecord(c->red_ev[slot], s_));
 	}
 	for (size_t i = 0; i < nside; ++i) HIP_TRY(c, hipStreamWaitEvent(st, c->red_ev[i], 0));
@@ -698,34 +735,40 @@ int red_columns(fseq_ctx *c)
 	for (auto const &bin : c->red_bins) ls.push_back(RedLaunch{bin.config, bin.first, bin.count});
 	// (the bins ascend by the rows a workgroup holds: the largest first)
 	std::reverse(ls.begin(), ls.end());
-	return red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride);
+	return red_launch_all(c, ls, RA, list_args(c));
+}
+
+// streamed rows, the first form of the column kernel (KS: bits of the keys its partition steps scan; 0: the has-based scan)
+template <int KS>
+void launch_columns_stream(fseq_ctx *c, uint32_t grid, ColumnsArgs const &C)
+{
+	MsaArgs const &A = C.A;
+	hipLaunchKernelGGL(k_columns_stream<KS>, dim3(grid), dim3(ST), stream_lds_bytes(sym_bytes(A.m, A.bsh), c->stream_staged), c->stream, A.msa, A.ld, A.m, A.n, A.B, A.npass, A.bsh, C.ws, (uint32_t) c->stream_staged,
+	                   C.bstate_a, C.bstate_d, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr, C.ss.snap_stride, C.ss.ss_a, C.ss.ss_d, C.block0, C.done_host, C.epoch, C.ss.ss_pack);
 }
 
 // ---- phase C on all rows of the blocks b0 .. b0 + nb - 1
 // (list [r5]: workgroup i owns block list[i] instead of b0 + i -- the blocks the reduced phase C hands to the run on all rows)
-void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t *done = nullptr, uint32_t epoch = 0, uint32_t const *list = nullptr)
+void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list = nullptr)
 {
 	FSEQ_LONG_LOCALS(c);
 	// columns phase C covers here: all, or my blocks plus the halo block's first columns (the lists my last DP round reads)
-	uint64_t const n_c = sharded ? sh.c_end : n;
+	ColumnsArgs C;
+	C.A = msa_args(c, sharded ? sh.c_end : n, c->B, c->nblocks);
+	C.bstate_a = c->d_bstate_a; C.bstate_d = c->d_bstate_d; C.lists = list_args(c); C.ss = stride_states(c); C.ws = c->d_ws;
+	C.block0 = b0; C.blocklist = list;                         // (done_host, epoch: nothing on the path waits for single blocks from the host)
+	if (c->colmask_ready && c->colmask_use) C.colmask = c->d_colmask;
 	if (c->use_stream && c->s2.T)
 	{
 		uint32_t pack_abits = 1;
 		while ((1u << pack_abits) < m) ++pack_abits;
-		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, n_c, c->B, c->d_ws, c->d_bstate_a, c->d_bstate_d, b0, pack_abits,
+		hipLaunchKernelGGL(k_columns_stream2_prologue, dim3(nb), dim3(ST), stream_lds_bytes(0, true), st, m, C.A.n, C.A.B, C.ws, C.bstate_a, C.bstate_d, b0, pack_abits,
 		                   c->ss_ids ? c->d_bs_w : (uint32_t *) nullptr, c->ss_ids ? c->d_bs_h : (uint8_t *) nullptr, list);
-		c->s2.launch(st, nb, c->s2_lds, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr,
-		             c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack | (c->ss_ids ? S2_SS_IDS : 0u), list);
+		c->s2.launch(st, nb, c->s2_lds, C);
 	}
-	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan)
-		hipLaunchKernelGGL(k_columns_stream<19>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
-		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
-	else if (c->use_stream)
-		hipLaunchKernelGGL(k_columns_stream<0>, dim3(nb), dim3(ST), stream_lds_bytes(sym_bytes(m, c->bsh), c->stream_staged), st, c->d_msa, c->ld, m, n_c, c->B, c->npass, c->bsh, c->d_ws, (uint32_t) c->stream_staged,
-		                   c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->ss_pack);
-	else
-		ks.columns(st, nb, c->lds_columns, c->d_msa, c->ld, m, n_c, c->B, c->N2, c->d_bstate_a, c->d_bstate_d, (uint32_t) L, c->X, c->stride, c->d_ent, c->d_hdr, c->npass, c->bsh,
-		           c->snap_stride, c->d_ss_a, c->d_ss_d, b0, done, epoch, c->colmask_ready && c->colmask_use ? c->d_colmask : (uint32_t const *) nullptr, list);
+	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan) launch_columns_stream<19>(c, nb, C);
+	else if (c->use_stream) launch_columns_stream<0>(c, nb, C);
+	else ks.columns(st, nb, c->lds_columns, C);
 }
 
 // ---- a list budget (fseq_set_list_memory): pass 1's lists in windows of wb consecutive column blocks.  Window w = blocks
@@ -847,9 +890,9 @@ int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
 	}
 	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
 	int rc;
-	if ((rc = red_launch_all(c, ls, RA, c->d_red_blocks, nullptr, c->d_ent, c->d_hdr, c->X, c->stride))) return rc;
+	if ((rc = red_launch_all(c, ls, RA, list_args(c)))) return rc;
 	auto const f = stretch(c->red_full_at, c->red_nfull);
-	if (f.second) launch_columns(c, 0, f.second, nullptr, 0, c->d_red_blocks + f.first);
+	if (f.second) launch_columns(c, 0, f.second, c->d_red_blocks + f.first);
 	return FSEQ_OK;
 }
 
@@ -969,7 +1012,7 @@ int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
 					if ((rc = red_columns(c))) return rc;
 					mark("reduced columns queued");
 					// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
-					if (c->red_nfull) launch_columns(c, 0, c->red_nfull, nullptr, 0, c->d_red_blocks + c->red_full_at);
+					if (c->red_nfull) launch_columns(c, 0, c->red_nfull, c->d_red_blocks + c->red_full_at);
 					// sharded: the block behind mine for as far as the halo reaches, on all rows (k_columns stops at n_c)
 					if (sharded && sh.c_end > sh.c_hi) launch_columns(c, b_hi, 1u);
 				}
@@ -1215,14 +1258,19 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 	if ((rc = d_rank.alloc(m)) || (rc = d_keyd.alloc(m)) || (rc = d_nk.alloc(4))) return rc;
 	if (c->use_stream && !c->d_ws && (rc = c->d_ws.alloc(c, (size_t) 4 * m))) return rc;
 	// one block [0, n): ranked in key space (fseq_blockkeys.hpp); FSEQ_PHASE_A_CLASSIC: the per-column sweep
+	PhaseAArgs keys;
+	keys.A = msa_args(c, p.n, (uint32_t) p.n, 1);
+	keys.rank = d_rank; keys.keyd = d_keyd; keys.nkeys = d_nk; keys.nblk = 1;
+	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words;
+	keys.wide = (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u);
 	if (c->bk_cap_words && !c->tune.phase_a_classic)
 	{
 		if (c->use_stream)
 		{
 			size_t const per = (blockkeys_stream_ws_words(m, (uint32_t) p.n, c->bsh) + 15) & ~size_t(15);
 			if ((rc = c->d_bkws.ensure(c, per))) return rc;
-			hipLaunchKernelGGL(k_blockkeys_stream, dim3(1), dim3(1024), c->bk_lds, st, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, 1u,
-			                   d_rank, d_keyd, d_nk, (uint64_t) 0, c->d_bkws, per, c->bk_cap_words, (uint32_t *) nullptr, (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u), (uint32_t *) nullptr);
+			keys.work = c->d_bkws; keys.work_per = per;
+			launch_blockkeys_stream(c, 1, keys);
 		}
 		else
 		{
@@ -1230,7 +1278,8 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 			if (c->bk_per_block != per) c->d_bk.release(c);
 			if ((rc = c->d_bk.ensure(c, per))) return rc;
 			c->bk_per_block = per;
-			launch_blockkeys(c->bk_T, st, 1, c->bk_lds, c->d_msa, c->ld, m, p.n, (uint32_t) p.n, c->bsh, d_rank, d_keyd, d_nk, 0, c->d_bk, per, c->bk_cap_words, nullptr, nullptr);
+			keys.work = c->d_bk; keys.work_per = per;
+			launch_blockkeys(st, 1, c->bk_lds, keys);
 		}
 	}
 	else
@@ -1238,7 +1287,7 @@ int run_short_path(fseq_ctx *c, fseq_result *res)
 		// the 16-bit LDS kernels keep block-relative divergences in 16 bits: one block of 65536 columns or more would wrap
 		if (!c->use_stream && c->ks.cap > 7168u && p.n > 65535u)
 			return fail(c, FSEQ_E_UNSUPPORTED, "short path by column sweep: more than 65535 columns with 16-bit LDS state (unset FSEQ_PHASE_A_CLASSIC)");
-		launch_rank(c, 1, (uint32_t) p.n, 1, d_rank, d_keyd, d_nk);
+		launch_rank(c, keys);
 	}
 	std::vector<uint32_t> rank(m);
 	uint32_t nk = 0;

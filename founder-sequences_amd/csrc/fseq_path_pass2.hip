@@ -1,9 +1,9 @@
 // fseq_path_pass2.hip -- the segmentation path, pass 2: the (a, d) states at the merged boundaries, behind phase C on all rows
 // (from the stride states) or behind the reduced phase C (one chain step from the block's boundary state).  It launches through
-// KernelSet, Stream2Config, ChainSnapSet and the launchers of fseq_path_pass1.hip.
+// KernelSet, Stream2Config, ChainSnapSet and the launchers of fseq_path_pass1.hip, which all take the boundaries as one SnapArgs.
 // (The units of the path and what crosses them: fseq_path.hpp.)
 #include "fseq_path.hpp"
-#include "fseq_stream2.hpp"      // S2SnapArgs
+#include "fseq_stream2.hpp"      // (no name of it is used here since the launchers take SnapArgs; kept so that the unit's device code stays what it was)
 
 namespace fseq {
 
@@ -164,19 +164,24 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 	RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
 	// the class tables at the task columns, configuration by configuration
+	RedArgs RA;
+	red_fill_args(c, RA);
+	RA.task_rb = c->d_cols.as<unsigned long long const>();
+	RA.cls = c->d_red_cls; RA.headd = c->d_red_headd; RA.ncls = c->d_red_ncls;
+	RA.blocks = c->d_red_wgtasks + 3 * S2; RA.wg_tasks = c->d_red_wgtasks;
 	if (!ls.empty())
 	{
-		RedArgs RA;
-		red_fill_args(c, RA);
-		RA.task_rb = c->d_cols.as<unsigned long long const>();
-		RA.cls = c->d_red_cls; RA.headd = c->d_red_headd; RA.ncls = c->d_red_ncls;
 		std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
-		if ((rc = red_launch_all(c, ls, RA, c->d_red_wgtasks + 3 * S2, c->d_red_wgtasks, (uint2 *) nullptr, (uint4 *) nullptr, 0u, 0u))) return rc;
+		if ((rc = red_launch_all(c, ls, RA, ListArgs{(uint32_t) L}))) return rc;       // (no lists: the segment length alone)
 	}
+	// the states at my boundaries, from the blocks' boundary states
+	SnapArgs tasks;
+	tasks.A = msa_args(c);
+	tasks.bstate_a = c->d_bstate_a; tasks.bstate_d = c->d_bstate_d; tasks.task_blk = c->d_red_taskblk;
+	tasks.snap_a = c->d_snap_a; tasks.snap_d = c->d_snap_d; tasks.ss.snap_stride = c->snap_stride; tasks.keyed = scan_keyed(c);
 	// one chain step per boundary (a copy for the borders)
 	if (!c->use_stream)
-		cs.launch(st, (uint32_t) S2, cs.lds, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls, c->d_red_headd, c->d_red_ncls, c->red_cap,
-		          c->d_snap_a, c->d_snap_d, scan_keyed(c));
+		cs.launch(st, (uint32_t) S2, cs.lds, tasks, RA);
 	else
 	{
 		// streamed rows: a block's tasks on one workgroup, the groups taken from a counter
@@ -204,11 +209,10 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		HIP_TRY(c, hipMemcpyAsync(d_orb, o_rbs.data(), So * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(d_osrc, o_srcs.data(), o_srcs.size() * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipMemcpyAsync(d_ogrp, o_grp.data(), o_grp.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-		if (!c->use_stream)
-			ks.snap(st, (uint32_t) o_grp.size(), ks.lds_snap, c->d_msa, c->ld, m, n, c->B, c->nblocks, c->npass, c->bsh, c->d_bstate_a, c->d_bstate_d, d_orb, d_ogrp,
-			        tmp_a, tmp_d, d_osrc, c->snap_stride, (uint32_t const *) nullptr, (uint32_t const *) nullptr, scan_keyed(c));
-		else
-			launch_replay_stream(c, o_grp.size(), d_orb, d_ogrp, d_osrc, tmp_a, tmp_d, nullptr, nullptr, 0u);
+		// (from the blocks' start states: no stride states here)
+		tasks.task_rb = d_orb; tasks.task_grp = d_ogrp; tasks.task_src = d_osrc; tasks.snap_a = tmp_a; tasks.snap_d = tmp_d;
+		if (!c->use_stream) ks.snap(st, (uint32_t) o_grp.size(), ks.lds_snap, tasks);
+		else launch_replay_stream(c, o_grp.size(), tasks);
 		for (size_t j = 0; j < So; ++j)
 		{
 			HIP_TRY(c, hipMemcpyAsync(c->d_snap_a + (size_t) o_slot[j] * m, tmp_a + j * (size_t) m, (size_t) m * 4, hipMemcpyDeviceToDevice, st));
@@ -295,6 +299,11 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 		HIP_TRY(c, hipEventRecord(c->ev[6], st));
 		progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 		RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
+		// the states at my boundaries, every group swept from its block's boundary state or a stride state
+		SnapArgs tasks;
+		tasks.A = msa_args(c);
+		tasks.bstate_a = c->d_bstate_a; tasks.bstate_d = c->d_bstate_d; tasks.task_rb = c->d_cols; tasks.task_grp = c->d_grp; tasks.task_src = c->d_src;
+		tasks.snap_a = c->d_snap_a; tasks.snap_d = c->d_snap_d; tasks.ss = stride_states(c); tasks.keyed = scan_keyed(c);
 		if (!grp.empty() && c->use_stream && c->ss_ids)
 		{
 			// pass 2 on phase C's tile step (fseq_stream2.hpp, S2_SNAP): one workgroup per block that has boundaries, the block's
@@ -323,17 +332,12 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 			// (pageable sources: the runtime stages them before the call returns)
 			HIP_TRY(c, hipMemcpyAsync(c->d_wgblk, wgb.data(), wgb.size() * 4, hipMemcpyHostToDevice, st));
 			HIP_TRY(c, hipMemcpyAsync(c->d_wggrp, wgg.data(), wgg.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-			S2SnapArgs SN;
-			SN.wg_block = c->d_wgblk; SN.wg_groups = c->d_wggrp; SN.grp_tasks = c->d_grp; SN.grp_src = c->d_src; SN.task_rb = c->d_cols;
-			SN.snap_a = c->d_snap_a; SN.snap_d = c->d_snap_d; SN.bs_w = c->d_bs_w; SN.bs_h = c->d_bs_h;
-			c->s2.launch_snap(st, (uint32_t) wgb.size(), c->s2_lds, c->d_msa, c->ld, m, n, c->B, c->npass, c->bsh, c->d_ws, c->snap_stride, c->d_ss_a, c->d_ss_d, SN);
+			tasks.ws = c->d_ws; tasks.wg_block = c->d_wgblk; tasks.wg_groups = c->d_wggrp; tasks.bs_w = c->d_bs_w; tasks.bs_h = c->d_bs_h;
+			c->s2.launch_snap(st, (uint32_t) wgb.size(), c->s2_lds, tasks);
 			HIP_TRY(c, hipStreamSynchronize(st));                 // (wgb / wgg must outlive their copies)
 		}
-		else if (c->use_stream)
-			launch_replay_stream(c, grp.size(), c->d_cols, c->d_grp, c->d_src, c->d_snap_a, c->d_snap_d, c->d_ss_a, c->d_ss_d, c->ss_pack);
-		else if (!grp.empty())
-			ks.snap(st, (uint32_t) grp.size(), ks.lds_snap, c->d_msa, c->ld, m, n, c->B, c->nblocks, c->npass, c->bsh, c->d_bstate_a, c->d_bstate_d, c->d_cols, c->d_grp,
-			        c->d_snap_a, c->d_snap_d, c->d_src, c->snap_stride, c->d_ss_a, c->d_ss_d, scan_keyed(c));
+		else if (c->use_stream) launch_replay_stream(c, grp.size(), tasks);
+		else if (!grp.empty()) ks.snap(st, (uint32_t) grp.size(), ks.lds_snap, tasks);
 		HIP_TRY(c, hipEventRecord(c->ev[7], st));
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipStreamSynchronize(st));

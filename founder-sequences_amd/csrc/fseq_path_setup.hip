@@ -257,7 +257,7 @@ int prepare_geometry(fseq_ctx *c)
 			return fail(c, FSEQ_E_UNSUPPORTED, "block state does not fit the 160 KiB LDS of one CU");
 		// phase C works on value ids < m + B in 16-bit keys (partition_step<.., KEY16>); the LDS check above implies it
 		if ((uint64_t) p.m + c->B > 65535u) return fail(c, FSEQ_E_UNSUPPORTED, "block length too large for the 16-bit value ids of phase C");
-		HIP_TRY(c, c->ks.prepare(c->lds_columns));
+		HIP_TRY(c, c->ks.prepare());
 		HIP_TRY(c, c->ks.prepare_columns(c->lds_columns));
 		// Short inputs: phase C is a few rounds of (CUs x workgroups per CU) blocks, and a last round that is a third full
 		// costs a whole one (BASELINE C2: 1,021 blocks on 768 slots; 764 blocks of 131 columns: phase C 0.65 -> 0.59 ms).

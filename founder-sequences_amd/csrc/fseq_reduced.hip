@@ -14,10 +14,11 @@ struct LaunchRed {
 		return columns_lds_bytes<T, E, 4, PK>(B) - 2 * carve_bytes((size_t) T * E, 1) + 2 * carve_bytes(symcap, 1);
 	}
 	static hipError_t prepare(size_t bytes) { return allow_lds(k_columns_red<T, E, 4, PK, EW>, bytes); }
-	static void launch(hipStream_t st, uint32_t grid, size_t bytes, uint8_t const *msa, size_t ld, uint64_t n, uint32_t B, uint32_t L, uint32_t X, uint32_t stride,
-	                   uint2 *ent, uint4 *hdr, uint32_t npass, uint32_t bsh, RedArgs const &red)
+	static void launch(hipStream_t st, uint32_t grid, size_t bytes, ColumnsArgs const &C, RedArgs const &red)
 	{
-		hipLaunchKernelGGL((k_columns_red<T, E, 4, PK, EW>), dim3(grid), dim3(T), bytes, st, msa, ld, n, B, L, X, stride, ent, hdr, npass, bsh, red);
+		MsaArgs const &A = C.A;
+		hipLaunchKernelGGL((k_columns_red<T, E, 4, PK, EW>), dim3(grid), dim3(T), bytes, st, A.msa, A.ld, A.n, A.B, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr,
+		                   A.npass, A.bsh, red);
 	}
 	static uint32_t resident(size_t bytes)
 	{
@@ -44,10 +45,10 @@ struct LaunchRed {
 template <int T, int E, bool PK>
 struct LaunchChainSnap {
 	static hipError_t prepare() { return allow_lds(k_chain_snap<T, E, PK>, chain_snap_lds_bytes<T, E, PK>()); }
-	static void launch(hipStream_t st, uint32_t grid, size_t bytes, uint32_t const *ba, uint32_t const *bd, uint32_t const *rank, uint32_t m, uint32_t const *task_blk,
-	                   uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls, uint32_t cap, uint32_t *snap_a, uint32_t *snap_d, uint32_t keyed)
+	static void launch(hipStream_t st, uint32_t grid, size_t bytes, SnapArgs const &S, RedArgs const &red)
 	{
-		hipLaunchKernelGGL((k_chain_snap<T, E, PK>), dim3(grid), dim3(T), bytes, st, ba, bd, rank, m, task_blk, cls, headd, ncls, cap, snap_a, snap_d, keyed);
+		hipLaunchKernelGGL((k_chain_snap<T, E, PK>), dim3(grid), dim3(T), bytes, st, S.bstate_a, S.bstate_d, red.rank, red.m_true, S.task_blk, (uint32_t const *) red.cls,
+		                   (uint32_t const *) red.headd, (uint32_t const *) red.ncls, red.cap, S.snap_a, S.snap_d, S.keyed);
 	}
 	static ChainSnapSet make() { return ChainSnapSet{chain_snap_lds_bytes<T, E, PK>(), &prepare, &launch}; }
 };
@@ -100,8 +101,7 @@ void launch_reduce_check(hipStream_t st, uint32_t const *cnt, uint32_t const *pl
 }
 
 template <int BSH, int R>
-static bool launch_reduce_msa_lds(hipStream_t st, uint32_t nlisted, uint8_t const *msa, size_t ld, uint8_t *red, size_t ldr, uint32_t const *cnt,
-                                  uint32_t const *rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t const *blocks, uint32_t colbytes)
+static bool launch_reduce_msa_lds(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &D, uint32_t colbytes)
 {
 	static bool prepared = false;
 	size_t const lds = (size_t) 2 * R * 16384;
@@ -115,31 +115,30 @@ static bool launch_reduce_msa_lds(hipStream_t st, uint32_t nlisted, uint8_t cons
 		prepared = true;
 	}
 	// (a quarter of a block's columns per workgroup: the rows are read four times, the blocks' columns are enough workgroups)
-	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(nlisted, 4), dim3(1024), lds, st, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes);
+	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(D.nlisted, 4), dim3(1024), lds, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, D.blocks, colbytes);
 	return true;
 }
 
-void launch_reduce_msa(hipStream_t st, uint32_t nlisted, uint32_t max_rows, uint8_t const *msa, size_t ld, uint8_t *red, size_t ldr, uint32_t const *cnt,
-                       uint32_t const *rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t bsh, uint32_t const *blocks, uint32_t m, bool gather_only)
+void launch_reduce_msa(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &D, bool gather_only)
 {
-	if (!nlisted) return;
-	uint32_t const colbytes = sym_bytes(m, bsh);
+	if (!D.nlisted) return;
+	uint32_t const colbytes = sym_bytes(A.m, A.bsh);
 	// the column through LDS where it fits two buffers of at most 32 KB and the representatives the registers of 1,024 threads
-	if (!gather_only && colbytes <= 32768u && cap <= 12288u)
+	if (!gather_only && colbytes <= 32768u && D.cap <= 12288u)
 	{
 		bool const one = colbytes <= 16384u;
 		bool ok = false;
-		switch (bsh)
+		switch (A.bsh)
 		{
-		case 0: ok = one ? launch_reduce_msa_lds<0, 1>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes) : launch_reduce_msa_lds<0, 2>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes); break;
-		case 1: ok = one ? launch_reduce_msa_lds<1, 1>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes) : launch_reduce_msa_lds<1, 2>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes); break;
-		case 2: ok = one ? launch_reduce_msa_lds<2, 1>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes) : launch_reduce_msa_lds<2, 2>(st, nlisted, msa, ld, red, ldr, cnt, rows, cap, n, B, blocks, colbytes); break;
+		case 0: ok = one ? launch_reduce_msa_lds<0, 1>(st, A, D, colbytes) : launch_reduce_msa_lds<0, 2>(st, A, D, colbytes); break;
+		case 1: ok = one ? launch_reduce_msa_lds<1, 1>(st, A, D, colbytes) : launch_reduce_msa_lds<1, 2>(st, A, D, colbytes); break;
+		case 2: ok = one ? launch_reduce_msa_lds<2, 1>(st, A, D, colbytes) : launch_reduce_msa_lds<2, 2>(st, A, D, colbytes); break;
 		default: break;
 		}
 		if (ok) return;
 	}
-	uint32_t const nq = (max_rows + (1u << bsh) - 1u) >> bsh;
-	hipLaunchKernelGGL(k_reduce_msa, dim3(nlisted, (nq + 63u) / 64u), dim3(256), 0, st, msa, ld, red, ldr, cnt, rows, cap, n, B, bsh, blocks);
+	uint32_t const nq = (D.max_rows + (1u << A.bsh) - 1u) >> A.bsh;
+	hipLaunchKernelGGL(k_reduce_msa, dim3(D.nlisted, (nq + 63u) / 64u), dim3(256), 0, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, A.bsh, D.blocks);
 }
 
 } // namespace fseq

@@ -2,6 +2,7 @@
 // kernel headers that use them.
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace fseq {
@@ -14,7 +15,114 @@ struct DpArrays {
 	uint32_t tstride;
 };
 
-struct S2SnapArgs;                   // fseq_stream2.hpp: the boundaries of a pass-2 launch on the streamed tile step
+// ---- What the launchers of the path take (the kernel tables of fseq_ctx.hpp, the launch_* functions): plain host-side views
+// of a context's buffers and geometry.  A kernel's positional parameter list is written out at one place, its launcher, from
+// these by name; the kernels themselves keep their scalar and __restrict__ pointer parameters (fseq_path.hpp builds the
+// views of a context).
+
+// the alignment as a kernel sees it: column k at msa + k * ld, in nblocks blocks of B columns
+struct MsaArgs {
+	uint8_t const *msa = nullptr;
+	size_t ld = 0;
+	uint32_t m = 0;
+	uint64_t n = 0;
+	uint32_t B = 0, nblocks = 0;
+	uint32_t N2 = 0;                     // slots of the sort in k_columns' prologue (the power of two above m)
+	uint32_t npass = 1, bsh = 0;         // digit passes of a column; packing: 8 >> bsh bits per symbol
+};
+
+// the lists of phase C: column k at ent + k * stride, its header at hdr + k
+struct ListArgs {
+	uint32_t L = 0, X = 0, stride = 0;   // segment length, list capacity, entries between two columns' lists
+	uint2 *ent = nullptr;
+	uint4 *hdr = nullptr;
+};
+
+// the stride states: the state at column q * snap_stride at ss_* + q * (words of a state); phase C drops them, pass 2 starts from them
+struct StrideStates {
+	uint32_t snap_stride = 0;
+	uint32_t *ss_a = nullptr, *ss_d = nullptr;
+	uint32_t ss_pack = 0;                // streamed rows: bits of a row id when the states are packed to 5 bytes per row
+	bool ids = false;                    // ... and hold value ids, not divergences (the tile step, fseq_stream2.hpp)
+};
+
+// phase A: the key blocks a launch writes -- its first block starts at column col0; rank / keyd / nkeys point at that block --
+// and what the kernel that writes them works in
+struct PhaseAArgs {
+	MsaArgs A;
+	uint32_t *rank = nullptr, *keyd = nullptr, *nkeys = nullptr;
+	uint64_t col0 = 0;
+	uint32_t nblk = 0;                   // blocks of the launch (the trie and the streamed tree hand them to their workgroups in turn)
+	uint32_t const *only = nullptr;      // per-block filter: a block whose word is zero is skipped (nullptr: every block)
+	uint32_t *todo = nullptr;            // per block: set where the kernel gives the block up (the next kernel's `only`)
+	uint32_t T = 0;                      // the key-space tree and the trie: threads of a workgroup
+	void *work = nullptr;                // ... their scratch (the tree on LDS-resident rows: halfwords; else words), work_per elements a block / a workgroup
+	size_t work_per = 0;
+	uint32_t cap_words = 0;              // the tree: words of its LDS bitmap
+	uint32_t wide = 0;                   // the streamed tree: bit 0 = 32-bit ids from the start, bit 1 = leaves one by one
+	uint32_t *counters = nullptr;        // blocks sliced (the tree) / given up (the trie)
+};
+
+// pass 2: the states at the boundaries task_rb, each group of boundaries (task_grp: {first, count}) swept from one start state
+// (task_src: a block's boundary state, or -- bit 63 -- a stride state)
+struct SnapArgs {
+	MsaArgs A;
+	uint32_t const *bstate_a = nullptr, *bstate_d = nullptr;
+	uint64_t const *task_rb = nullptr;
+	uint2 const *task_grp = nullptr;
+	uint64_t const *task_src = nullptr;
+	uint32_t *snap_a = nullptr, *snap_d = nullptr;       // [boundary][m]
+	StrideStates ss;
+	uint32_t keyed = 0;                  // LDS-resident rows: what the partition steps scan (scan_keyed)
+	uint32_t const *task_blk = nullptr;  // behind the reduced phase C: [boundary] its block (the chain step, k_chain_snap)
+	// on the streamed tile step (S2SnapArgs, fseq_stream2.hpp): a workgroup per block that has boundaries
+	uint32_t *ws = nullptr;              // the blocks' workspaces (block b at ws + b * words per block)
+	uint32_t const *wg_block = nullptr;  // [grid] block of every workgroup
+	uint2 const *wg_groups = nullptr;    // [grid] {first group, groups}
+	uint32_t const *bs_w = nullptr;      // the blocks' start states in id form
+	uint8_t const *bs_h = nullptr;
+};
+
+// one launch of phase C on all rows: the blocks block0 .. (or blocklist[i]), from their boundary states
+struct ColumnsArgs {
+	MsaArgs A;
+	uint32_t const *bstate_a = nullptr, *bstate_d = nullptr;
+	ListArgs lists;
+	StrideStates ss;
+	uint32_t *ws = nullptr;              // streamed rows: the blocks' workspaces (block b at ws + b * words per block)
+	uint32_t block0 = 0;
+	uint32_t *done_host = nullptr;
+	uint32_t epoch = 0;
+	uint32_t const *blocklist = nullptr; // workgroup i owns block blocklist[i] instead of block0 + i
+	uint32_t const *colmask = nullptr;   // 4-bit symbols: the codes present in every column (k_column_presence), or nullptr
+};
+
+// One chain launch of phase B: grid chains grp0 .. grp0 + grid - 1, chain g over the key blocks [g * G, min(nb_total, (g + 1) * G))
+// of a level; from start_* (nullptr: the identity) to the states in front of every key block (out_state_*) and / or the
+// chain's composite key block (out_rank / out_keyd / out_nkeys).  The streamed chain kernels take it as it is (fseq_chainsort.hpp).
+struct ChainMultiArgs {
+	uint32_t const *rank, *keyd, *nkeys;         // the key blocks of the level below
+	uint32_t m, nb_total, G;
+	uint64_t cols_per_block;
+	uint32_t *ws;                                // [chains of the launch][chainsort_ws_words(m)]
+	uint32_t *hist;                              // [chains of the launch][parts][CS_BINS]
+	uint32_t const *start_a, *start_d;
+	uint32_t *out_state_a, *out_state_d, *out_rank, *out_keyd, *out_nkeys;
+	uint32_t grp0;
+	uint32_t step;                               // block b0 + step of every chain
+	uint32_t pass;                               // radix pass of the sweep kernels
+	uint32_t nchains;                            // chains of the launch (the grid's y is rounded up to the XCDs: cm_wg)
+};
+
+// the reduced alignment k_reduce_msa writes: the listed blocks' representative rows (rows[block][cap], cnt[block] of them), column k at red + k * ldr
+struct ReducedMsaArgs {
+	uint8_t *red = nullptr;
+	size_t ldr = 0;
+	uint32_t const *cnt = nullptr, *rows = nullptr;
+	uint32_t cap = 0;
+	uint32_t const *blocks = nullptr;    // [nlisted] the reduced blocks
+	uint32_t nlisted = 0, max_rows = 0;  // ... and the most representatives among them
+};
 
 // [r5] Phase C on a block's REPRESENTATIVE rows (fseq_reduced.hpp): what k_reduce_prep left for every block and where a
 // workgroup of the reduced column kernel finds it.  Plain pointers into device memory.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """profiles/<prefix>_kernel_resource_usage.txt: registers, scratch, spills and occupancy of every kernel instantiation,
 from hipcc's own remarks (no GPU needed):  python profiles/resource_usage.py r02"""
+import importlib.util
 import os
 import re
 import subprocess
@@ -8,9 +9,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 prefix = sys.argv[1] if len(sys.argv) > 1 else "r02"
-# the library's translation units (founder-sequences_amd/build.py SRCS)
-units = ["fseq_api.hip", "fseq_api_debug.hip", "fseq_path_setup.hip", "fseq_path_dp.hip", "fseq_path_pass1.hip", "fseq_path_pass2.hip", "fseq_api_join.hip", "fseq_reduced.hip",
-         "fseq_kernelsets.hip", "fseq_kernelsets_stream.hip"]
+# the library's translation units: the list the build compiles (founder-sequences_amd/build.py, SRCS)
+_spec = importlib.util.spec_from_file_location("fseq_build", os.path.join(ROOT, "founder-sequences_amd", "build.py"))
+_build = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_build)
+units = [os.path.basename(src) for src in _build.SRCS]
 txt = ""
 for u in units:
     src = os.path.join(ROOT, "founder-sequences_amd", "csrc", u)
@@ -30,7 +33,7 @@ for b in re.split(r"(?=remark: Function Name:)", txt):
     dem = re.sub(r"^void ", "", re.sub(r"\(.*", "", dem))
     rows.append([dem, g("VGPRs"), g("AGPRs"), g("TotalSGPRs"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"),
                  g("VGPRs Spill"), g("SGPRs Spill"), g("LDS Size [bytes/block]")])
-out = ["# hipcc --offload-arch=gfx950 -O3 -std=c++17 -Rpass-analysis=kernel-resource-usage founder-sequences_amd/csrc/{fseq_api,fseq_api_join}.hip",
+out = ["# hipcc --offload-arch=gfx950 -O3 -std=c++17 -Rpass-analysis=kernel-resource-usage founder-sequences_amd/csrc/{%s}" % ",".join(units),
        "# kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | occupancy waves/SIMD | VGPR spill | SGPR spill | static LDS B (dynamic LDS not included)"]
 out += [" | ".join(r_) for r_ in sorted(rows)]
 path = os.path.join(ROOT, "profiles", "%s_kernel_resource_usage.txt" % prefix)

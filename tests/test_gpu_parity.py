@@ -280,6 +280,16 @@ def test_columns_with_at_most_four_codes_take_one_pass(pkg, monkeypatch, m, n, L
     assert np.array_equal(ctx2.traceback(), tb)
 
 
+def test_dense_columns_on_all_rows(pkg, monkeypatch):
+    """Reaches KernelSet::columns with the column mask (k_columns<.., DENSE>).  The shapes of
+    test_columns_with_at_most_four_codes_take_one_pass run every block on its representatives, where no kernel looks at the
+    mask; FSEQ_NO_REDUCED keeps phase C on all rows, and half of the columns carry at most four codes."""
+    monkeypatch.setenv("FSEQ_NO_REDUCED", "1")
+    msa = _gapped_sigma16(3000, 700, 303, 0.5)
+    ctx, _ = compare_long(pkg, msa, 12, block_len=64)
+    assert ctx.timings()["reduced_blocks"] == 0
+
+
 def test_streamed_phase_a_trie_gives_blocks_up(pkg):
     """What does not fit the trie's table goes to the key-space tree, block by block: columns 0..95 of 30,000 rows are a
     mosaic of few founders (the trie's), columns 96..191 random (every row its own key after eight columns: more than 12,288
@@ -377,6 +387,29 @@ def test_streamed_phase_c_with_the_plain_scan(pkg, monkeypatch):
     for (m, n, L, K, Brec, mu, seed, kind, B) in [(12000, 500, 20, 12, 120, 3e-4, 41, 0, 64), (20000, 300, 15, 16, 100, 2e-4, 42, 1, 50)]:
         msa = fso.synth_msa(fso.synth_spec(seed, K, Brec, mu, kind), m, n)
         compare_long(pkg, msa, L, block_len=B)
+
+
+@pytest.mark.parametrize("knobs", [("FSEQ_PHASE_A_CLASSIC", "FSEQ_NO_REDUCED", "FSEQ_SS_ABSOLUTE"), ("FSEQ_REDUCED_ALWAYS",)], ids=["from_stride_states", "beside_reduced_blocks"])
+def test_streamed_sweeps_with_the_plain_scan(pkg, monkeypatch, knobs):
+    """Reaches k_colblock_stream<MODE_RANK, false> and k_colblock_stream<MODE_SNAP, false>, the streamed column sweep with the
+    has-based scan (FSEQ_PLAIN_SCAN), which the default streamed run no longer launches: phase A as a sweep (FSEQ_PHASE_A_CLASSIC) and
+    pass 2 replaying columns from stride states that hold divergences (launch_replay_stream from long_pass2); then, beside blocks
+    on their representatives, the boundaries of the blocks that have too many (FSEQ_REDUCED_CAP at the mean) replayed from the
+    block's start (launch_replay_stream from long_pass2_reduced).  m = 11,265: the fewest rows that stream."""
+    m, n, L, B = 11265, 2000, 20, 100
+    msa = fso.synth_msa(fso.synth_spec(92, 10, 500, 2e-4, 0), m, n)
+    monkeypatch.setenv("FSEQ_PLAIN_SCAN", "1")
+    for k in knobs:
+        monkeypatch.setenv(k, "1")
+    if "FSEQ_REDUCED_ALWAYS" in knobs:
+        mean = run_gpu(pkg, msa, L, block_len=B).timings()["reduced_rows_mean"]
+        monkeypatch.setenv("FSEQ_REDUCED_CAP", str(mean))    # about half of the blocks have more
+    ctx, _ = compare_long(pkg, msa, L, check_dp=False, block_len=B)
+    t = ctx.timings()
+    if "FSEQ_REDUCED_ALWAYS" in knobs:
+        assert 0 < t["reduced_blocks"] < t["n_blocks"], t
+    else:
+        assert t["reduced_blocks"] == 0, t
 
 
 def test_unsupported_shape_fails_loudly(pkg):
