@@ -101,11 +101,12 @@ EXPORTS = [
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
-    "fseq_debug_join_path", "fseq_debug_pass2_paths",
+    "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
-                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths"]
+                 "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
+                 "fseq_debug_class_columns"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -211,6 +212,7 @@ def load_library():
     L.fseq_debug_packed_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_join_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
+    L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
     _lib = L
     return L
 
@@ -788,6 +790,26 @@ class SegmentationContext:
         out = dict(zip(("by_runs", "by_sort", "copies", "max_runs"), (x.value for x in v)))
         out["runs_hist"] = [int(x) for x in hist]
         return out
+
+    def class_column_sources(self):
+        """Where the last run's reduced alignment came from: {from_classes, from_alignment} blocks (phase A's class columns / the
+        alignment itself); both zero where the run built none."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self.L.fseq_debug_class_columns(self.h, C.byref(a), C.byref(b), 0xFFFFFFFF, None, None, None, None, 0))
+        return {"from_classes": a.value, "from_alignment": b.value}
+
+    def class_columns(self, block):
+        """Phase A's class columns of a block of the last run: (packed, ldc, nkeys) -- packed[j] the ldc bytes of the block's column j, row
+        rho of it the symbol of the block key of rank rho in the alignment's packing -- or (None, ldc, nkeys) where the block has none."""
+        have, nkeys, ldc = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self.L.fseq_debug_class_columns(self.h, None, None, block, C.byref(have), C.byref(nkeys), C.byref(ldc), None, 0))
+        if not have.value:
+            return None, ldc.value, nkeys.value
+        t = self.timings()
+        cols = min(t["block_len"], self.n - block * t["block_len"])
+        out = np.zeros((cols, ldc.value), dtype=np.uint8)
+        self._check(self.L.fseq_debug_class_columns(self.h, None, None, block, C.byref(have), C.byref(nkeys), C.byref(ldc), out.ctypes.data, out.nbytes))
+        return out, ldc.value, nkeys.value
 
     def timings(self):
         t = Timings()

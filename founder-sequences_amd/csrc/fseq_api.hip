@@ -23,7 +23,7 @@ void fseq::forget_run_history(fseq_ctx *c)
 {
 	c->have_result = false;
 	c->kernels_ready = false;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false;
+	c->bk_given_up = -1; c->bt_given_up = -1; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false; c->cls_unread = false;
 }
 
 // ... and an input what was learnt of the input besides

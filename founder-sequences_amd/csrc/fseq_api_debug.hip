@@ -39,6 +39,41 @@ int fseq_debug_pass2_paths(fseq_ctx *c, uint32_t *by_runs, uint32_t *by_sort, ui
 	return FSEQ_OK;
 }
 
+int fseq_debug_class_columns(fseq_ctx *c, uint32_t *from_classes, uint32_t *from_alignment, uint32_t block, uint32_t *have, uint32_t *nkeys, uint64_t *ldc,
+                             uint8_t *out, uint64_t out_bytes)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	uint32_t const b_lo = c->sh.on ? c->sh.b_lo : 0u, b_hi = c->sh.on ? c->sh.b_hi : c->nblocks;
+	std::vector<uint32_t> flags;
+	if (c->cls_read)
+	{
+		flags.assign(c->nblocks, 0u);
+		if (b_hi > b_lo) HIP_TRY(c, hipMemcpy(flags.data() + b_lo, c->d_cls_have + b_lo, (size_t) (b_hi - b_lo) * 4, hipMemcpyDeviceToHost));
+	}
+	uint32_t n_cls = 0, n_msa = 0;
+	if (c->red_active && !c->red_direct && c->red_cnt_host.size() == c->nblocks)
+		for (uint32_t b = b_lo; b < b_hi; ++b)
+			if (c->red_cnt_host[b] != RED_NONE) ++(c->cls_read && flags[b] ? n_cls : n_msa);
+	if (from_classes) *from_classes = n_cls;
+	if (from_alignment) *from_alignment = n_msa;
+	if (block == UINT32_MAX) return FSEQ_OK;
+	if (block < b_lo || block >= b_hi) return fail(c, FSEQ_E_ARG, "fseq_debug_class_columns: not a block of this context");
+	uint32_t h = 0;
+	if (c->cls_on && c->d_cls && c->d_cls_have) HIP_TRY(c, hipMemcpy(&h, c->d_cls_have + block, 4, hipMemcpyDeviceToHost));
+	if (have) *have = h;
+	if (nkeys) { *nkeys = 0; if (c->d_nkeys) HIP_TRY(c, hipMemcpy(nkeys, c->d_nkeys + block, 4, hipMemcpyDeviceToHost)); }
+	if (ldc) *ldc = c->cls_on ? c->cls_ld : 0;
+	if (out && h)
+	{
+		uint64_t const k0 = (uint64_t) block * c->B, k1 = std::min<uint64_t>(c->p.n, k0 + c->B);
+		if (out_bytes < (k1 - k0) * c->cls_ld) return fail(c, FSEQ_E_ARG, "fseq_debug_class_columns: the buffer is smaller than the block's class columns");
+		HIP_TRY(c, hipMemcpy(out, c->d_cls + (size_t) k0 * c->cls_ld, (size_t) (k1 - k0) * c->cls_ld, hipMemcpyDeviceToHost));
+	}
+	return FSEQ_OK;
+}
+
 int fseq_debug_dp(fseq_ctx *c, uint32_t *lb, uint32_t *max_size, uint32_t *size)
 {
 	if (!c) return FSEQ_E_ARG;

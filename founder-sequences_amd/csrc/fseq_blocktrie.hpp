@@ -179,11 +179,81 @@ __device__ __forceinline__ void bt_store_ids(uint32_t *__restrict__ idw, size_t 
 	else *reinterpret_cast<uint2 *>(idw + (size_t) IW * wi) = make_uint2(cur[0], cur[1]);
 }
 
+// Phase 3 of k_blocktrie (see there): the class columns of a ranked block.
 template <int BITS, int BT_T>
+__device__ __forceinline__ void bt_class_columns(char *smem, uint2 const *nodes, uint32_t const *hdr, uint32_t level_base, uint32_t nprev, uint16_t const *Rp,
+                                                          uint32_t levels, uint64_t k0, uint64_t kend, uint8_t *cls, size_t ldc)
+{
+	using G = BtGeom<BT_T>;
+	constexpr int N = 32 / BITS;
+	uint32_t const tid = threadIdx.x;
+	uint16_t *const cnt = reinterpret_cast<uint16_t *>(smem + G::OFF_CNT);
+	constexpr int P3 = (BT_PER + N - 1) / N;           // packed words of a column per thread: 12 T ranks at most
+	uint16_t *const idr = cnt;                         // id by rank (cnt[] is history; the table lies over RA .. DB, in front of it)
+	uint2 *const tab = reinterpret_cast<uint2 *>(smem);
+	uint32_t lb = level_base;                          // (behind the last level's nodes)
+	{
+		uint2 const *const nd = nodes + (lb - nprev);
+		for (uint32_t i = tid; i < nprev; i += BT_T) { uint32_t const id = nd[i].x & 0x3FFFu; idr[Rp[id]] = (uint16_t) id; }
+	}
+	__syncthreads();
+	uint32_t anc[P3][N / 2];                           // the ancestors of my ranks' classes at the level at hand, two to a word
+#pragma unroll
+	for (int p = 0; p < P3; ++p)
+#pragma unroll
+		for (int q = 0; q < N / 2; ++q)
+		{
+			uint32_t const rho = (tid + (uint32_t) p * BT_T) * (uint32_t) N + 2u * (uint32_t) q;
+			anc[p][q] = (rho < nprev ? (uint32_t) idr[rho] : 0u) | (rho + 1u < nprev ? (uint32_t) idr[rho + 1u] << 16 : 0u);
+		}
+#pragma unroll 1
+	for (uint32_t t = levels; t-- > 0u;)
+	{
+		uint32_t const nt = hdr[t];
+		lb -= nt;
+		uint64_t const kc = k0 + (uint64_t) N * (levels - 1u - t);
+		uint32_t const ncol = (uint32_t) min((uint64_t) N, kend - kc);      // (a partial last group: the columns from kend on are not stored)
+		__syncthreads();                               // (the level before is looked up; the first time: the outputs have read Rp)
+		for (uint32_t i = tid; i < nt; i += BT_T)
+		{
+			uint2 const v = nodes[lb + i];
+			tab[v.x & 0x3FFFu] = make_uint2((v.x >> 16) & 0x3FFFu, v.y);
+		}
+		__syncthreads();
+		uint8_t *const colp = cls + kc * ldc;          // (uniform: the stores are base + a thread's 32-bit offset)
+#pragma unroll
+		for (int p = 0; p < P3; ++p)
+		{
+			uint32_t const j = tid + (uint32_t) p * BT_T;
+			if (j * (uint32_t) N < nprev)
+			{
+				uint32_t x[N];
+#pragma unroll
+				for (int q = 0; q < N / 2; ++q)
+				{
+					// (ranks >= nkeys in the last word: zero)
+					bool const in0 = j * (uint32_t) N + 2u * (uint32_t) q < nprev, in1 = j * (uint32_t) N + 2u * (uint32_t) q + 1u < nprev;
+					uint2 const e0 = in0 ? tab[anc[p][q] & 0xFFFFu] : make_uint2(0u, 0u);
+					uint2 const e1 = in1 ? tab[anc[p][q] >> 16] : make_uint2(0u, 0u);
+					x[2 * q] = e0.y; x[2 * q + 1] = e1.y;
+					anc[p][q] = e0.x | (e1.x << 16);
+				}
+				bt_transpose<BITS>(x);
+				uint32_t const off = 4u * j;
+#pragma unroll
+				for (int c = 0; c < N; ++c)
+					if ((uint32_t) c < ncol) *reinterpret_cast<uint32_t *>(colp + (size_t) c * ldc + off) = x[c];
+			}
+		}
+	}
+}
+
+template <int BITS, int BT_T, bool CLS>
 __global__ __launch_bounds__(BT_T) void k_blocktrie(
 	uint8_t const *__restrict__ msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t nblk,
 	uint32_t *__restrict__ rank, uint32_t *__restrict__ keyd, uint32_t *__restrict__ nkeys, uint64_t col0,
-	uint32_t *__restrict__ ws, size_t ws_per_group, uint32_t *__restrict__ given_up /* [0]: blocks given up */, uint32_t *__restrict__ todo)
+	uint32_t *__restrict__ ws, size_t ws_per_group, uint32_t *__restrict__ given_up /* [0]: blocks given up */, uint32_t *__restrict__ todo,
+	uint8_t *__restrict__ cls /* the class columns (column k at cls + k * ldc), or nullptr: nobody reads them */, size_t ldc, uint32_t *__restrict__ cls_have)
 {
 	using G = BtGeom<BT_T>;
 	constexpr int N = 32 / BITS, IW = N / 2;                               // rows per packed word = columns per group; id words per packed word
@@ -501,6 +571,18 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 		}
 		for (uint32_t j = tid; j < nprev; j += BT_T) keyd[ob + j] = (uint32_t) (k0 + Dp[j]);
 		if (tid == 0) nkeys[b] = nprev;
+
+		// ---------------- phase 3: the class columns -- column k of the block with the symbol of the key of rank rho at row rho, packed
+		// like the alignment: what the representatives' columns are gathered from (k_reduce_msa_lds on this source, fseq_reduced.hpp) instead of from
+		// the alignment.  The chain leaf class -> parent -> .. -> root spells the key out group by group: the ranks' leaf ids are
+		// looked up (the final ranks inverted), then level by level from the last one (= the block's FIRST group) a table
+		// {parent, word} by id over the dead arrays of phase 2; a thread owns N consecutive ranks (one packed word of a column),
+		// takes their words of the group, steps to the parents and transposes the words into the group's N column words.
+		if constexpr (CLS)
+		{
+			bt_class_columns<BITS, BT_T>(smem, nodes, hdr, level_base, nprev, Rp, levels, k0, kend, cls, ldc);
+			if (tid == 0) cls_have[b] = 1u;
+		}
 		__syncthreads();                                       // (LDS and the workspace are the next block's)
 #ifdef FSEQ_BT_STAMPS
 		BT_STAMP(5);

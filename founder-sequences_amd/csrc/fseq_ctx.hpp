@@ -87,6 +87,7 @@ hipError_t launch_blocktrie(hipStream_t st, uint32_t groups, PhaseAArgs const &k
 hipError_t launch_reduce_prep(hipStream_t, uint32_t grid, RedPrepArgs const &);
 void launch_reduce_check(hipStream_t, uint32_t const *cnt, uint32_t const *planned, uint32_t count, uint32_t *flags);
 void launch_reduce_msa(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &red, bool gather_only);
+bool launch_reduce_cls(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &red, ClassColumnArgs const &classes);      // (false: not this shape, nothing launched)
 
 inline double now_ms()
 {
@@ -130,6 +131,7 @@ struct Tuning {
 	bool reduced_always = false;         // FSEQ_REDUCED_ALWAYS: the representatives whenever some block has fewer of them than rows (tests of the mixed runs)
 	bool reduced_msa_gather = false;     // FSEQ_REDUCED_MSA_GATHER: the reduced alignment by gathers from memory (by itself: the column through LDS where it fits)
 	int  reduced_cap = 0;                // FSEQ_REDUCED_CAP: most representatives a block may have (tests: small values send blocks to the run on all rows)
+	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
@@ -175,6 +177,7 @@ struct Tuning {
 			{"FSEQ_REDUCED_MSA_GATHER", &Tuning::reduced_msa_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
+			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
 		};
 		return table;
 	}
@@ -221,6 +224,7 @@ struct DevBuf {
 	template <typename U> U *as() const { return reinterpret_cast<U *>(static_cast<T *>(*this)); }
 	void rebase(ptrdiff_t elements) { shift = elements * (ptrdiff_t) sizeof(T); }
 	int alloc(fseq_ctx *c, size_t count);                     // exactly `count` elements in place of what is held
+	bool try_alloc(fseq_ctx *c, size_t count);                // the same for a buffer the run can do without: false, and no error on the context, where the device has no room
 	int ensure(fseq_ctx *c, size_t count) { return cap >= count ? FSEQ_OK : alloc(c, count); }      // grow-only
 	int alloc_range(fseq_ctx *c, size_t lo, size_t hi, size_t per)      // items [lo, hi) of `per` elements each
 	{
@@ -388,6 +392,15 @@ struct fseq_ctx {
 	uint32_t red_cap = 0;
 	DevBuf<uint8_t> d_red_msa;
 	size_t red_ld = 0;
+	// phase A's class columns (fseq_blocktrie.hpp, phase 3), what the reduced alignment of a block the trie ranked is gathered from: column k at
+	// d_cls + k * cls_ld (a rank holds its own columns), d_cls_have[block] = 1 where this run's phase A wrote them
+	DevBuf<uint8_t> d_cls;
+	DevBuf<uint32_t> d_cls_have;
+	size_t cls_ld = 0;
+	bool cls_on = false;                     // this run's phase A wrote class columns
+	bool cls_every = false;                  // ... for every block of mine (the trie ran alone: it gave no block up in the run before on this input)
+	bool cls_unread = false;                 // the plan of this input takes a path that reads no reduced alignment: phase A writes no class columns for it
+	bool cls_read = false;                   // this run's reduced alignment took them where a block has them (fseq_debug_class_columns)
 	std::vector<uint32_t> red_cnt_host;      // representatives per block of the last prep (RED_NONE: not reduced)
 	std::vector<uint8_t> red_full;           // blocks this run sends to the kernel on all rows
 	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives (1); 2: the block
@@ -547,6 +560,24 @@ void DevBuf<T>::release(fseq_ctx *c)
 		(void) hipFree(base);
 	}
 	*this = DevBuf<T>{};
+}
+
+template <typename T>
+bool DevBuf<T>::try_alloc(fseq_ctx *c, size_t count)
+{
+	release(c);
+	size_t const bytes = std::max<size_t>(count, 1) * sizeof(T);
+	if (hipMalloc(reinterpret_cast<void **>(&base), bytes) != hipSuccess)
+	{
+		base = nullptr;
+		(void) hipGetLastError();          // (as in alloc: the runtime must not remember the failure)
+		return false;
+	}
+	cap = count;
+	c->alloc_sizes[static_cast<void *>(base)] = bytes;
+	c->alloc_total += bytes;
+	c->alloc_peak = std::max(c->alloc_peak, c->alloc_total);
+	return true;
 }
 
 template <typename T>

@@ -95,19 +95,28 @@ hipError_t launch_blocktrie(hipStream_t st, uint32_t groups, PhaseAArgs const &K
 {
 	MsaArgs const &A = K.A;
 	uint32_t const bits = 8u >> A.bsh;
+#define FSEQ_BT_LAUNCH(BITS_, T_, CLS_) \
+	{ \
+		hipError_t const e = allow_lds(k_blocktrie<BITS_, T_, CLS_>, BtGeom<T_>::LDS_BYTES); \
+		if (e != hipSuccess) return e; \
+		hipLaunchKernelGGL((k_blocktrie<BITS_, T_, CLS_>), dim3(groups), dim3(T_), BtGeom<T_>::LDS_BYTES, st, A.msa, A.ld, A.m, A.n, A.B, K.nblk, K.rank, K.keyd, K.nkeys, K.col0, \
+		                   static_cast<uint32_t *>(K.work), K.work_per, K.counters, K.todo, K.cls, K.ldc, K.cls_have); \
+		return hipSuccess; \
+	}
+	// (the kernel with the class columns' phase is an instantiation of its own: where nobody reads them -- K.cls == nullptr -- the kernel is
+	// instruction for instruction the one without that phase.  Class columns are written for streamed rows only, and those run 1,024 threads)
 #define FSEQ_BT_CASE(BITS_, T_) \
 	if (bits == BITS_ && K.T == T_) \
 	{ \
-		hipError_t const e = allow_lds(k_blocktrie<BITS_, T_>, BtGeom<T_>::LDS_BYTES); \
-		if (e != hipSuccess) return e; \
-		hipLaunchKernelGGL((k_blocktrie<BITS_, T_>), dim3(groups), dim3(T_), BtGeom<T_>::LDS_BYTES, st, A.msa, A.ld, A.m, A.n, A.B, K.nblk, K.rank, K.keyd, K.nkeys, K.col0, \
-		                   static_cast<uint32_t *>(K.work), K.work_per, K.counters, K.todo); \
-		return hipSuccess; \
+		if constexpr (T_ == 1024) { if (K.cls) FSEQ_BT_LAUNCH(BITS_, T_, true) } \
+		else if (K.cls) return hipErrorInvalidValue; \
+		FSEQ_BT_LAUNCH(BITS_, T_, false) \
 	}
 	FSEQ_BT_CASE(2, 256) FSEQ_BT_CASE(2, 512) FSEQ_BT_CASE(2, 1024)
 	FSEQ_BT_CASE(4, 256) FSEQ_BT_CASE(4, 512) FSEQ_BT_CASE(4, 1024)
 	FSEQ_BT_CASE(8, 256) FSEQ_BT_CASE(8, 512) FSEQ_BT_CASE(8, 1024)
 #undef FSEQ_BT_CASE
+#undef FSEQ_BT_LAUNCH
 	return hipErrorInvalidValue;
 }
 

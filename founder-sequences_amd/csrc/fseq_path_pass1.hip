@@ -230,6 +230,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	                  && (c->ld & 3u) == 0 && (reinterpret_cast<uintptr_t>(c->d_msa) & 3u) == 0
 	                  && !(c->bt_given_up >= 0 && 2u * (uint32_t) c->bt_given_up > my_blocks);
 	bool const tree_after = tree && !(trie && c->bt_given_up == 0);
+	c->cls_on = c->cls_every = c->cls_read = false;
 	R.trie_ran = trie;
 	R.trie_alone = trie && !tree_after;
 	// my key blocks, and what the key-space tree works with; the trie hands the tree its blocks, the tree hands the sweep its own
@@ -251,6 +252,38 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		HIP_TRY(c, hipMemsetAsync(c->d_only, 0, (size_t) my_blocks * 4, st));
 		PhaseAArgs T = keys;
 		T.T = bt_T; T.work = c->d_btws; T.work_per = per; T.counters = c->d_flags + 66; T.todo = c->d_only;
+		// The class columns of the blocks the trie ranks (its phase 3): what phase C's reduced alignment is gathered from instead of
+		// reading the alignment a second time.  Only where somebody will read them: streamed rows (LDS-resident row counts take the
+		// representatives' symbols from the alignment's own columns), the reduced phase C not switched off or declined on this input.
+		// The buffer is the largest the reduced path adds (12 T classes a column: 3 KB at 2 bits, 15 GB on BASELINE C4), so it must fit
+		// the context's memory budget and, without one, a quarter of what is free -- the lists and the reduced states are allocated
+		// after it and must not fail for it.  Where it does not fit, or the allocation fails, the alignment is read as before.
+		if (c->use_stream && c->tune.class_columns && !c->tune.no_reduced && n >= 2 * L && !(c->red_declined && !c->tune.reduced_always) && !c->cls_unread)
+		{
+			size_t const ldc = ((size_t) sym_bytes((uint32_t) BT_PER * bt_T, c->bsh) + 15) & ~size_t(15);
+			uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
+			size_t const need = (size_t) (k_hi - k_lo) * ldc + 64;
+			bool ok = c->d_cls.cap >= need;
+			if (!ok)
+			{
+				size_t const held = c->d_cls.base ? c->d_cls.cap : 0;
+				size_t free_b = 0, total_b = 0;
+				bool fits = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= (free_b + held) / 4;
+				if (c->mem_budget && c->alloc_total - std::min(c->alloc_total, held) + need > c->mem_budget) fits = false;
+				if (fits) ok = c->d_cls.try_alloc(c, need);        // (no room after all: not an error of the run)
+				else if (c->d_cls.base) c->d_cls.release(c);
+				if (c->tune.debug && !ok) fprintf(stderr, "[fseq] phase A: no room for %zu bytes of class columns: the reduced alignment from the alignment\n", need);
+			}
+			if (ok && (rc = c->d_cls_have.ensure(c, c->nblocks))) return rc;
+			if (ok)
+			{
+				c->cls_ld = ldc;
+				c->d_cls.rebase((ptrdiff_t) ((size_t) k_lo * ldc));
+				HIP_TRY(c, hipMemsetAsync(c->d_cls_have + b_lo, 0, (size_t) my_blocks * 4, st));
+				T.cls = c->d_cls; T.ldc = ldc; T.cls_have = c->d_cls_have + b_lo;
+				c->cls_on = true; c->cls_every = !tree_after;
+			}
+		}
 		HIP_TRY(c, launch_blocktrie(st, groups, T));
 		keys.only = c->d_only;
 	}
@@ -538,9 +571,17 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	A.invalid = c->d_red_invalid; A.flags = c->d_red_invalid + nbk;
 	HIP_TRY(c, launch_reduce_prep(st, my_blocks, A));
 	// the reduced alignment of the listed blocks (streamed rows), by the plan in force when it is queued
+	// The listed blocks are two lists by where their columns come from: the blocks with class columns (phase A's trie ranked them: d_cls_have) are
+	// gathered from those, the others (the trie gave them up) from the alignment as before.  Which block is which is known on the device when the
+	// launches are queued -- and a later run launches by its plan without waiting --, so both launches take the whole list and a workgroup
+	// of either leaves at once where the block is the other's; where the trie ran alone every block has class columns and the launch
+	// on the alignment is not made.
 	auto reduce_msa = [&] {
-		launch_reduce_msa(st, msa_args(c), ReducedMsaArgs{c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, c->d_red_blocks, c->red_listed, c->red_max_rows},
-		                  c->tune.reduced_msa_gather);
+		ReducedMsaArgs D{c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, c->d_red_blocks, c->red_listed, c->red_max_rows};
+		c->cls_read = c->cls_on && launch_reduce_cls(st, msa_args(c), D, ClassColumnArgs{c->d_cls, c->cls_ld, c->d_cls_have, c->d_red_leaf, c->d_rank});
+		if (c->cls_read && c->cls_every) return;
+		if (c->cls_read) { D.flag = c->d_cls_have; D.want = 0u; }
+		launch_reduce_msa(st, msa_args(c), D, c->tune.reduced_msa_gather);
 	};
 	if (c->red_plan_valid && c->red_plan_X == X && c->red_force_full.size() == nbk)
 	{
@@ -625,10 +666,16 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 		if ((!c->tune.reduced_always && (rows_all * 5u > (uint64_t) my_blocks * m || (uint64_t) n_full * 4u > my_blocks)) || (uint64_t) n_full >= my_blocks)
 		{
 			c->red_declined = true; c->red_declined_X = X;
+			c->d_cls.release(c); c->cls_on = false;          // (phase A writes no class columns while the input stays declined)
 			return FSEQ_OK;
 		}
 	}
-	if (n_full && c->use_stream && !c->s2.T) return FSEQ_OK;     // (the first form of the streamed kernel takes no block list)
+	if (n_full && c->use_stream && !c->s2.T)                     // (the first form of the streamed kernel takes no block list)
+	{
+		// (nobody reads the class columns, and the same input gives the same answer next time: phase A writes none for it again)
+		c->d_cls.release(c); c->cls_on = false; c->cls_unread = true;
+		return FSEQ_OK;
+	}
 	if (!c->red_direct)
 	{
 		// the reduced alignment: column k at d_red_msa + k * red_ld

@@ -115,7 +115,7 @@ static bool launch_reduce_msa_lds(hipStream_t st, MsaArgs const &A, ReducedMsaAr
 		prepared = true;
 	}
 	// (a quarter of a block's columns per workgroup: the rows are read four times, the blocks' columns are enough workgroups)
-	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(D.nlisted, 4), dim3(1024), lds, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, D.blocks, colbytes);
+	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(D.nlisted, 4), dim3(1024), lds, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, D.blocks, colbytes, D.flag, D.want, D.pad, D.pad_per);
 	return true;
 }
 
@@ -138,7 +138,25 @@ void launch_reduce_msa(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &D
 		if (ok) return;
 	}
 	uint32_t const nq = (D.max_rows + (1u << A.bsh) - 1u) >> A.bsh;
-	hipLaunchKernelGGL(k_reduce_msa, dim3(D.nlisted, (nq + 63u) / 64u), dim3(256), 0, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, A.bsh, D.blocks);
+	hipLaunchKernelGGL(k_reduce_msa, dim3(D.nlisted, (nq + 63u) / 64u), dim3(256), 0, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, A.bsh, D.blocks, D.flag, D.want);
+}
+
+// the listed blocks that have class columns, from those: k_reduce_msa_lds with the class columns as its alignment and the representatives' leaf
+// ranks as its rows (false: a shape that kernel does not take -- nothing is launched, the caller reads the alignment)
+bool launch_reduce_cls(hipStream_t st, MsaArgs const &A, ReducedMsaArgs const &D, ClassColumnArgs const &K)
+{
+	if (!D.nlisted) return true;
+	if (K.ldc > 16384u || D.cap > 12288u || A.bsh > 2u) return false;
+	MsaArgs S = A;
+	S.msa = K.cls; S.ld = K.ldc;
+	ReducedMsaArgs E = D;
+	E.rows = K.leaf; E.flag = K.have; E.want = 1u; E.pad = K.rank; E.pad_per = A.m;
+	switch (A.bsh)
+	{
+	case 0: return launch_reduce_msa_lds<0, 1>(st, S, E, (uint32_t) K.ldc);
+	case 1: return launch_reduce_msa_lds<1, 1>(st, S, E, (uint32_t) K.ldc);
+	default: return launch_reduce_msa_lds<2, 1>(st, S, E, (uint32_t) K.ldc);
+	}
 }
 
 } // namespace fseq

@@ -223,11 +223,13 @@ static __global__ __launch_bounds__(256) void k_reduce_check(uint32_t const *__r
 // waves take the block's columns in turn.
 static __global__ __launch_bounds__(256) void k_reduce_msa(
 	uint8_t const *__restrict__ msa, size_t ld, uint8_t *__restrict__ red, size_t ldr, uint32_t const *__restrict__ cnt,
-	uint32_t const *__restrict__ rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t bsh, uint32_t const *__restrict__ blocks)
+	uint32_t const *__restrict__ rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t bsh, uint32_t const *__restrict__ blocks,
+	uint32_t const *__restrict__ flag /* per block, or nullptr: every block */, uint32_t want)
 {
 	uint32_t const blk = blocks[blockIdx.x];
 	uint32_t const Lr = cnt[blk];
 	if (Lr == RED_NONE) return;
+	if (flag && flag[blk] != want) return;                 // (the blocks whose columns come from the other source)
 	uint32_t const rpb = 1u << bsh, bits = 8u >> bsh, cmask = (1u << bits) - 1u;
 	uint32_t const nq = (Lr + rpb - 1u) >> bsh;
 	uint32_t const q = blockIdx.y * 64u + lane_id();
@@ -278,10 +280,18 @@ static __global__ __launch_bounds__(256) void k_reduce_msa(
 // R LDS-DMA pieces per lane, contiguous, one column ahead of the one being gathered (s_waitcnt vmcnt(R): the pieces of the
 // column in front have landed, the next one's stay in flight -- loads return in order); the representatives' rows stay in
 // registers (output byte q = thread + 1024 i, its 1 << BSH rows), the gathers are LDS byte reads.
+// The same kernel takes phase A's CLASS COLUMNS (k_blocktrie's phase 3, fseq_blocktrie.hpp) as its alignment for the blocks that have them
+// (flag / want): column k of the block holds, at row rho, the symbol every row whose block key has rank rho carries there, and leaf[i]
+// is that rank for representative i (`rows`; neither ascending nor free of repeats, which an LDS byte gather does not mind) --
+// cls[k][leaf[i]] == msa[k][rows[i]], whatever the data.  A class column is 3 KB (12,288 classes of 2 bits) where the alignment's
+// is 25 KB on BASELINE C4.  On that source the kernel is bound by its LDS byte gathers (192 wave instructions a column whose
+// lanes fall on the banks at random), not by memory or its two barriers a column: 9.2 ms a step on BASELINE C4, where a form that
+// staged eight class columns per barrier through registers and stored words took 10.0 ms and was not kept.
 template <int BSH, int R>
 __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 	uint8_t const *__restrict__ msa, size_t ld, uint8_t *__restrict__ red, size_t ldr, uint32_t const *__restrict__ cnt,
-	uint32_t const *__restrict__ rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t const *__restrict__ blocks, uint32_t colbytes)
+	uint32_t const *__restrict__ rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t const *__restrict__ blocks, uint32_t colbytes,
+	uint32_t const *__restrict__ flag /* per block, or nullptr: every block */, uint32_t want, uint32_t const *__restrict__ pad, size_t pad_per)
 {
 	constexpr uint32_t RPB = 1u << BSH, BITS = 8u >> BSH, CMASK = (1u << BITS) - 1u;
 	constexpr uint32_t NOUT = (12288u / RPB + 1023u) / 1024u;          // output bytes per thread: 12,288 representatives at most
@@ -290,6 +300,7 @@ __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 	uint32_t const blk = blocks[blockIdx.x];
 	uint32_t const Lr = cnt[blk];
 	if (Lr == RED_NONE) return;
+	if (flag && flag[blk] != want) return;
 	uint32_t const tid = threadIdx.x;
 	uint32_t const nq = (Lr + RPB - 1u) >> BSH;
 	uint64_t const k0 = (uint64_t) blk * B;
@@ -297,6 +308,8 @@ __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 	uint32_t const per = (nb + gridDim.y - 1u) / gridDim.y;
 	uint32_t const j_lo = min(nb, blockIdx.y * per), j_hi = min(nb, j_lo + per);
 	if (j_lo >= j_hi) return;
+	// (the positions behind the last representative in its byte carry row 0's symbol; from the class columns: that of row 0's class, pad[blk * pad_per])
+	uint32_t const row_pad = pad ? pad[(size_t) blk * pad_per] : 0u;
 	uint32_t row[NOUT][RPB];
 #pragma unroll
 	for (uint32_t i = 0; i < NOUT; ++i)
@@ -304,7 +317,7 @@ __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 		for (uint32_t r = 0; r < RPB; ++r)
 		{
 			uint32_t const idx = (tid + 1024u * i) * RPB + r;
-			row[i][r] = idx < Lr ? rows[(size_t) blk * cap + idx] : 0u;
+			row[i][r] = idx < Lr ? rows[(size_t) blk * cap + idx] : row_pad;
 		}
 	uint32_t const base = (uint32_t) (uintptr_t) smem;
 	auto stage = [&](uint64_t k, uint32_t buf) {

@@ -61,6 +61,9 @@ struct PhaseAArgs {
 	uint32_t cap_words = 0;              // the tree: words of its LDS bitmap
 	uint32_t wide = 0;                   // the streamed tree: bit 0 = 32-bit ids from the start, bit 1 = leaves one by one
 	uint32_t *counters = nullptr;        // blocks sliced (the tree) / given up (the trie)
+	uint8_t *cls = nullptr;              // the trie: the class columns it writes for the blocks it ranks (column k at cls + k * ldc; nullptr: none) ...
+	size_t ldc = 0;
+	uint32_t *cls_have = nullptr;        // ... and, per block of the launch, 1 where it wrote them
 };
 
 // pass 2: the states at the boundaries task_rb, each group of boundaries (task_grp: {first, count}) swept from one start state
@@ -122,6 +125,19 @@ struct ReducedMsaArgs {
 	uint32_t cap = 0;
 	uint32_t const *blocks = nullptr;    // [nlisted] the reduced blocks
 	uint32_t nlisted = 0, max_rows = 0;  // ... and the most representatives among them
+	uint32_t const *flag = nullptr;      // per block, or nullptr: only the listed blocks with flag[block] == want (the others take the other source)
+	uint32_t want = 0;
+	uint32_t const *pad = nullptr;       // the row whose symbol fills the last byte behind the last representative: pad[block * pad_per] (nullptr: row 0)
+	size_t pad_per = 0;
+};
+
+// phase A's class columns (k_blocktrie, fseq_blocktrie.hpp), the other source of the reduced alignment: column k at cls + k * ldc holds at row rho the
+// symbol of the block key of rank rho; have[block] = 1 where the block has them; leaf[block][cap]: the rank of every representative's key
+struct ClassColumnArgs {
+	uint8_t const *cls = nullptr;
+	size_t ldc = 0;
+	uint32_t const *have = nullptr, *leaf = nullptr;
+	uint32_t const *rank = nullptr;      // [block][m]: block-key rank of every row
 };
 
 // [r5] Phase C on a block's REPRESENTATIVE rows (fseq_reduced.hpp): what k_reduce_prep left for every block and where a

@@ -79,6 +79,17 @@ int  fseq_debug_packed_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t 
  * runs ([0]: one run).  All zero where the last run did not go through that kernel (LDS-resident rows, no representatives). */
 int  fseq_debug_pass2_paths(fseq_ctx *ctx, uint32_t *by_runs, uint32_t *by_sort, uint32_t *copies, uint32_t *max_runs, uint32_t *runs_hist);
 
+/* Where the reduced alignment of the last run came from (streamed rows behind the reduced phase C): *from_classes blocks took their
+ * representatives' columns from phase A's class columns (the block trie's, csrc/fseq_blocktrie.hpp), *from_alignment blocks
+ * from the alignment itself (blocks the trie gave up; every block with FSEQ_CLASS_COLUMNS=0, or where the class columns did not
+ * fit the memory budget).  Both zero where the run built no reduced alignment (LDS-resident rows, no representatives).
+ * block != UINT32_MAX: that block's class columns as well -- *have (1: it has them), *nkeys (its distinct keys), *ldc (bytes a class
+ * column) and, where out != NULL and it has them, the columns of the block one after the other, *ldc bytes each, into out
+ * (out_bytes: its size; FSEQ_E_ARG when too small): row rho of a column is the symbol of the key of rank rho, packed like the
+ * alignment. */
+int  fseq_debug_class_columns(fseq_ctx *ctx, uint32_t *from_classes, uint32_t *from_alignment, uint32_t block, uint32_t *have, uint32_t *nkeys,
+                              uint64_t *ldc, uint8_t *out, uint64_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
