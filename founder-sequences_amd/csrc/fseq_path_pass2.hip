@@ -135,6 +135,16 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 			hb.push_back(w.blk); hw.push_back(w.first); hw.push_back(w.count); hw.push_back(w.start);
 			cells += (rbs[w.first + w.count - 1u] - (uint64_t) w.start) * c->red_cnt_host[w.blk];
 		}
+		if (c->tune.debug)
+		{
+			// (worded like red_plan's report of phase C; a workgroup sweeps one block's tasks that share a start column)
+			ReducedSet rs{};
+			(void) reduced_config((int) cf, &rs);
+			uint32_t tasks = 0;
+			for (auto const &w : wgs[cf]) tasks += w.count;
+			fprintf(stderr, "[fseq]   reduced pass 2: configuration of %u rows: %zu workgroups, %u tasks in blocks %u to %u (%u threads x %u rows)\n", rs.rows, wgs[cf].size(), tasks,
+			        wgs[cf].front().blk, wgs[cf].back().blk, rs.T, rs.E);
+		}
 	}
 	{
 		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256 + P2_STATS * 4;

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import fso
+from reduced_capacity_cases import lists_match as _lists_match
 from test_gpu_parity import compare_long, run_gpu
 from test_gpu_shard import run_world, check_against_oracle
 
@@ -72,27 +73,6 @@ def test_reduced_alignment_by_gathers(pkg, always):
         msa = fso.synth_msa(fso.synth_spec(seed, K, Brec, mu, kind), m, n)
         ctx, _ = compare_long(pkg, msa, L, block_len=B)
         assert ctx.timings()["reduced_blocks"] > 0
-
-
-def _lists_match(ctx, msa, L, every=5):
-    m, n = msa.shape
-    p = fso.Pbwt(msa, debug=False)
-    X = ctx.timings()["list_cap_used"]
-    for k in range(n):
-        p.step()
-        if k % every and k < n - 3:
-            continue
-        v, c = p.counts()
-        gv, gc, cnt0, complete = ctx.debug_column_list(k)
-        thr = max(0, k + 2 - L)
-        rec = v >= thr
-        ev = np.concatenate([[k + 1], v[~rec][::-1]])
-        ec = np.concatenate([[c[rec].sum()], c[~rec][::-1]])
-        assert complete or gc[1:].sum() > X, k
-        assert np.array_equal(gv, ev[:len(gv)]) and np.array_equal(gc, ec[:len(gc)]), k
-        assert complete == (len(gv) == len(ev)), k
-        if complete:
-            assert cnt0 == (c[0] if v[0] == 0 else 0), k
 
 
 def test_reduced_lists_match_oracle(pkg, always):
