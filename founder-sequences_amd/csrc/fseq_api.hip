@@ -95,12 +95,9 @@ int fseq_create(fseq_params const *params, fseq_ctx **out)
 	c->tune.from_environment();                  // the only look at the environment: fseq_debug_set_tuning changes a knob afterwards
 	if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
 	if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
-	for (auto &e : c->ev_part)
-		if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
-	for (auto &e : c->ev_dp)
-		if (hipEventCreate(&e) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
-	for (auto &e : c->ev)
-		if (hipEventCreate(&e) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
+	if (hipEventCreateWithFlags(&c->ev.dp_reset, hipEventDisableTiming) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
+	for (hipEvent_t *e : c->ev.timed())
+		if (hipEventCreate(e) != hipSuccess) { fseq_destroy(c); return FSEQ_E_HIP; }
 	*out = c;
 	return FSEQ_OK;
 }
@@ -116,9 +113,8 @@ void fseq_destroy(fseq_ctx *c)
 	c->free_identity();
 	c->free_input();
 	assert(c->alloc_sizes.empty() && c->alloc_total == 0);       // (a buffer free_work does not know of)
-	for (auto &e : c->ev) if (e) (void) hipEventDestroy(e);
-	for (auto &e : c->ev_part) if (e) (void) hipEventDestroy(e);
-	for (auto &e : c->ev_dp) if (e) (void) hipEventDestroy(e);
+	for (hipEvent_t *e : c->ev.timed()) if (*e) (void) hipEventDestroy(*e);
+	if (c->ev.dp_reset) (void) hipEventDestroy(c->ev.dp_reset);
 	for (auto &e : c->lw.ev) if (e) (void) hipEventDestroy(e);
 	if (c->h_pin) (void) hipHostFree(c->h_pin);
 	if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);

@@ -1,6 +1,6 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
 // shares: csrc/fseq_api.hip (the ABI's entry points) and csrc/fseq_api_debug.hip (the debug entry points, the row-sharded sweep),
-// the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _pass2: geometry, buffers, phases, sharding; what
+// the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _attempt, _pass2: geometry, buffers, phases, sharding; what
 // only they share is csrc/fseq_path.hpp), csrc/fseq_api_join.hip (the host joiners, their device front and the output
 // writers), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
 // and put back) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <climits>
@@ -274,7 +275,7 @@ struct fseq_ctx {
 	size_t alloc_total = 0;
 	size_t alloc_peak = 0;                    // the most alloc_total has been (fseq_debug_device_bytes)
 	uint64_t mem_budget = 0;                  // fseq_set_memory_budget: 0 = whatever is free on the device
-	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_path_pass1.hip, plan_list_windows).  The buffer
+	// fseq_set_list_memory: the lists of a long-path run in column windows (csrc/fseq_path_attempt.hip, plan_list_windows).  The buffer
 	// holds the columns [lo_w B - H, hi_w B) of window w: d_ent is rebased to (lo_w B - H) stride.
 	struct ListWindows {
 		uint64_t budget = 0;                  // bytes (0: every list held, the default)
@@ -369,7 +370,7 @@ struct fseq_ctx {
 	} dp;
 	DevBuf<uint32_t> d_Mprev;                // chunk-speculative DP: the iterate the last sweep started from
 	DevBuf<uint32_t> d_spec;                 // its per-chunk words (active, changed, tailmin, floor, lift, 2 x ovf) + SpecCtl
-	DevBuf<uint32_t> d_flags;
+	DevBuf<fseq::PathWords> d_flags;        // the path's device words, one PathWords (fseq_types.hpp; path_words in fseq_path.hpp)
 	DevBuf<uint32_t> d_recent;               // k_boundary_recent counts, one per block boundary
 	uint64_t dp_size = 0;
 	DevBuf<uint64_t> d_cols;                 // scratch: column / rb lists
@@ -441,10 +442,16 @@ struct fseq_ctx {
 	std::vector<fseq_segment> segments;
 	std::vector<uint32_t> sp_first, sp_len;
 	fseq_timings tm{};
-	hipEvent_t ev[8]{};
-	hipStream_t stream2 = nullptr;           // the DP, while phase C is still producing lists for later columns
-	hipEvent_t ev_part[16]{};                // part c of phase C done
-	hipEvent_t ev_dp[2]{};                   // DP begin / end on stream2
+	// the path's events, by what they bracket; all on the context's stream but dp_reset
+	struct PathEvents {
+		hipEvent_t a_begin = nullptr, a_end_b_begin = nullptr, b_end = nullptr;      // phases A and B (once a run)
+		hipEvent_t c_begin = nullptr, c_end = nullptr, dp_begin = nullptr, dp_end = nullptr;     // phase C and the DP of an attempt
+		hipEvent_t pass2_begin = nullptr, pass2_end = nullptr;
+		hipEvent_t dp_reset = nullptr;       // (no timing) the arrays of the speculative DP were reset on stream2
+		std::array<hipEvent_t *, 9> timed() { return {&a_begin, &a_end_b_begin, &b_end, &c_begin, &c_end, &dp_begin, &dp_end, &pass2_begin, &pass2_end}; }
+	} ev;
+	hipStream_t stream2 = nullptr;           // beside the context's stream: the reset of the DP's arrays while phase C runs, the first side
+	                                         // stream of the reduced configurations' launches, the chunked input's copies
 	uint8_t *h_pin = nullptr;                // pinned host staging of a step's small transfers (pin_reserve / pin_take)
 	size_t pin_cap = 0, pin_used = 0;
 

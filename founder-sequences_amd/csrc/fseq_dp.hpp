@@ -6,6 +6,7 @@
 
 #include "fseq_kernels.hpp"
 #include "fseq_types.hpp"
+#include "fseq_dpschedule.hpp"
 
 namespace fseq {
 
@@ -29,7 +30,6 @@ namespace fseq {
 // memory round trip costs ~1.5 us here, a round must cost about that in total, so no wave that
 // the round barriers wait for may ever wait on HBM.
 constexpr uint32_t DPW = 4096;            // DP entries mirrored in LDS (ring, slot = index mod DPW)
-constexpr uint32_t DP_RL = 56;            // cells per round (<= L)
 constexpr uint32_t DP_NWC = 14;           // compute waves
 constexpr int      DP_G = 4;              // cells per compute wave per round (14 * 4 = 56)
 constexpr uint32_t DP_STG = 512;          // staging ring for LB / SZ
@@ -270,11 +270,6 @@ __device__ __forceinline__ CellState dp_cell_sequential(
 	return st;
 }
 
-struct DpRound {
-	uint32_t e0, len, t0, t1;
-	bool final_round;
-};
-
 // The two 32-lane halves of a wave as independent scans / reductions
 __device__ __forceinline__ uint32_t half_incl_add(uint32_t v)
 {
@@ -367,10 +362,10 @@ __device__ __forceinline__ uint64_t dp_cell_pair(
 #ifdef FSEQ_DP_STATS
 	{
 		// diagnostic build: histogram of the list entries a cell needed before the pruning bound was
-		// reached, in flags[128 + n] (n = 33: more than the 32 of a half wave)
+		// reached, in flags[DP_HIST_AT + n] (n = 33: more than the 32 of a half wave)
 		uint64_t const need = __ballot(valid && (cum <= best_v || best_v == 0xFFFFFFFFu));
 		uint32_t const nh = (uint32_t) __popc((uint32_t) (need >> (half * 32u)));
-		if (sub == 0u && has) atomicAdd(flags + 128 + (more ? 33u : nh), 1u);
+		if (sub == 0u && has) atomicAdd(flags + DP_HIST_AT + (more ? 33u : nh), 1u);
 	}
 #endif
 	if (!more)
@@ -438,65 +433,6 @@ __device__ __forceinline__ void dp_wait_all_but(uint32_t n)
 		default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
 	}
 #undef FSEQ_W
-}
-
-// Round schedule.  nreg regular rounds of <= RL cells (end = L + r*RL + i), then -- pipelined mode
-// only -- one empty drain round (the update of the last regular round), then the final cell at
-// rb = n (lp.cc:165-183).
-struct DpSchedule {
-	uint32_t L, n, RL, nreg, nrounds;
-	bool pipe;
-};
-
-__host__ __device__ inline DpRound dp_round(DpSchedule const &S, uint32_t r)
-{
-	DpRound R;
-	uint32_t const last_end = S.n - S.L;
-	R.final_round = (r + 1u == S.nrounds);
-	bool const regular = r < S.nreg;
-	R.e0 = R.final_round ? S.n : (regular ? S.L + r * S.RL : last_end + 1u);
-	uint32_t const rest = last_end - R.e0 + 1u;
-	R.len = R.final_round ? 1u : (regular ? (S.RL < rest ? S.RL : rest) : 0u);
-	R.t0 = R.e0 - S.L;
-	R.t1 = R.t0 + R.len;
-	return R;
-}
-
-// Two schedules.  Classic: rounds of <= min(L, DP_RL) cells, the rmq.update of a round between two
-// barriers.  Pipelined (L >= 96): rounds of 48 cells -- a round then never reads what the previous
-// round wrote (a cell reads entries <= end - 2L), so two dedicated waves do the update of round r-1
-// while the compute waves are already in round r: one barrier a round.
-__host__ __device__ inline DpSchedule dp_schedule(uint32_t L, uint32_t n)
-{
-	DpSchedule S;
-	S.L = L; S.n = n;
-#ifndef FSEQ_DP_PIPE_MIN_L
-#define FSEQ_DP_PIPE_MIN_L 96u
-#endif
-	S.pipe = L >= FSEQ_DP_PIPE_MIN_L;                         // measured: pays only with 4 cells per compute wave
-	uint32_t const half = L / 2u < 48u ? L / 2u : 48u;
-	S.RL = S.pipe ? (half / 12u) * 12u : (L < DP_RL ? L : DP_RL);   // pipelined: whole cells per compute wave
-	S.nreg = ((n - L) - L) / S.RL + 1u;
-	S.nrounds = S.nreg + (S.pipe ? 2u : 1u);
-	return S;
-}
-
-// Rounds of the schedule whose cells only need the lists of columns < col_hi (a cell `end` reads the list
-// of column end - 1): the DP of a column prefix can run while later columns are still being produced.
-__host__ __device__ inline uint32_t dp_rounds_within(DpSchedule const &S, uint64_t col_hi)
-{
-	if (col_hi >= S.n) return S.nrounds;
-	// the regular rounds need ascending columns (the drain round needs none, the final cell needs column n - 1):
-	// first regular round that needs a column >= col_hi
-	uint32_t lo = 0, hi = S.nreg;
-	while (lo < hi)
-	{
-		uint32_t const mid = (lo + hi) / 2u;
-		DpRound const R = dp_round(S, mid);
-		bool const needs = (uint64_t) R.e0 + R.len - 2u >= col_hi;
-		if (needs) hi = mid; else lo = mid + 1u;
-	}
-	return lo < S.nreg ? lo : S.nrounds - 1u;                  // all regular rounds (and the drain): everything but the final cell
 }
 
 __device__ __forceinline__ void dp_barrier()
@@ -669,9 +605,6 @@ struct DpSpecArgs {
 	uint32_t const *ctl;                  // ctl[0] != 0: the iteration has converged, nothing to do
 };
 
-// MODE 0: the whole schedule in one launch (r_begin_arg / r_end_arg ignored: the common case keeps its registers).
-// MODE 1: rounds [r_begin_arg, r_end_arg).  MODE 2: workgroup = chunk of the speculative iteration.
-enum { DP_WHOLE = 0, DP_PARTIAL = 1, DP_SPEC = 2 };
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_dp(
 	DpArrays const A, uint2 const *__restrict__ ent, uint4 const *__restrict__ hdr, uint32_t stride,
@@ -1024,9 +957,9 @@ __global__ __launch_bounds__(1024) void k_dp(
 #ifdef FSEQ_DP_STAMPS
 	if (lane == 0)
 	{
-		unsigned long long *o = reinterpret_cast<unsigned long long *>(flags + 8) + wave * 3u;
+		unsigned long long *o = reinterpret_cast<unsigned long long *>(flags + DP_STAMPS_AT) + wave * 3u;
 		o[0] = acc[0]; o[1] = acc[1] + acc[2] + acc[3]; o[2] = acc[4];
-		unsigned long long *q = reinterpret_cast<unsigned long long *>(flags + 8) + 48 + wave * 3u;   // classic schedule: barrier 1, update, barrier 2
+		unsigned long long *q = reinterpret_cast<unsigned long long *>(flags + DP_STAMPS_AT) + 48 + wave * 3u;   // classic schedule: barrier 1, update, barrier 2
 		q[0] = acc[1]; q[1] = acc[2]; q[2] = acc[3];
 	}
 #endif

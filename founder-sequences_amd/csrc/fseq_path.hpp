@@ -5,12 +5,15 @@
 //   csrc/fseq_api_debug.hip   the entry points of include/fseq_debug.h, the row-sharded conformance sweep
 //   csrc/fseq_path_setup.hip  pinned staging, geometry, work buffers, the row upload, the shard exchange
 //   csrc/fseq_path_dp.hip     the DP drivers, the tracebacks, the merge (the one unit that instantiates k_dp<>)
-//   csrc/fseq_path_pass1.hip  phases A - C, the list capacity, the reduced plan, the list windows, the attempt loop (the one unit
-//                             that instantiates k_colblock_stream<> / k_columns_stream<> and includes fseq_chainsort.hpp)
+//   csrc/fseq_path_pass1.hip  phases A and B, the list capacity, the reduced plan, phase C's launchers (the one unit that instantiates
+//                             k_colblock_stream<> / k_columns_stream<> and includes fseq_chainsort.hpp)
+//   csrc/fseq_path_attempt.hip  one attempt at a list capacity as stages with one verdict, the list windows, the loop over attempts,
+//                             the short path (instantiates no kernel)
 //   csrc/fseq_path_pass2.hip  the boundary states at the merged boundaries
 // A kernel template is instantiated, and a header that defines plain __global__ kernels (fseq_dpspec.hpp, fseq_chainsort.hpp,
 // fseq_rowshard.hpp) is included, by one unit only: the others reach those kernels through the launchers declared here.  A unit
-// may include a header of templates for the sizes and schedules it computes on the host (dp_schedule, stream_lds_bytes, ...).
+// may include a header of templates for the sizes and schedules it computes on the host (stream_lds_bytes, ...); the DP's round
+// schedule is a header without kernels (fseq_dpschedule.hpp).
 // Everything a unit does not declare here is in its anonymous namespace.  Internal: none of this is exported.
 #pragma once
 
@@ -20,7 +23,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 #endif
 
-namespace fseq { struct DpSchedule; }          // fseq_dp.hpp
+namespace fseq { struct DpSchedule; }          // fseq_dpschedule.hpp
 
 #pragma GCC visibility push(hidden)
 
@@ -70,8 +73,7 @@ struct LongRun {
 	bool tree_ran = false;                   // phase A ran the key-space tree at all (else: the column sweep did every block, as last time)
 	bool tree_alone = false;                 // phase A ran the key-space tree without the column sweep behind it (no block was given up last time)
 	bool trie_ran = false, trie_alone = false;   // ... the trie over 16-column words (streamed rows); ... without the key-space tree behind it
-	bool redo = false;                       // [r5] lists of some blocks could not be proven on their representatives: the attempt runs again, those blocks on all rows
-	uint32_t redone = 0;
+	uint32_t redone = 0;                     // blocks whose lists could not be proven on their representatives: their attempt ran again, they on all rows
 	bool range_ab_open = false;              // the roctx range of phases A + B spans two functions
 };
 
@@ -93,6 +95,13 @@ struct LongRun {
 // columns this context holds: all of them, or the rank's share of a sharded run
 inline uint64_t held_lo(fseq_ctx const *c) { return c->sh.on ? c->sh.c_lo : 0; }
 inline uint64_t held_hi(fseq_ctx const *c) { return c->sh.on ? c->sh.c_end : c->p.n; }
+
+// the path's device words and the two behind d_red_invalid[nblocks] (fseq_types.hpp); device addresses: for their members' addresses only
+inline PathWords *path_words(fseq_ctx const *c) { return c->d_flags; }
+inline RedFlags *red_flags(fseq_ctx const *c) { return reinterpret_cast<RedFlags *>(c->d_red_invalid + c->nblocks); }
+
+// diagnostic ("ABC" in FSEQ_SYNC_PHASES): synchronise behind a phase, so that a fault shows up at the phase that caused it
+inline bool sync_at(fseq_ctx const *c, char ph) { return c->tune.sync_phases.find(ph) != std::string::npos; }
 
 // ---- the views of a context that the launchers take (fseq_types.hpp)
 // the alignment: all of it in the context's blocks, or the columns [0, n) in nblocks blocks of B (a rank of a sharded run
@@ -166,6 +175,17 @@ void red_fill_args(fseq_ctx *c, RedArgs &RA);
 struct RedLaunch { int config; uint32_t first, count; };
 // (base.blocks / base.wg_tasks: the lists the launches' [first, first + count) index; lists: the segment length alone in pass 2)
 int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists);
+int long_phase_a(fseq_ctx *c, LongRun &R);
+int phase_a_take_counts(fseq_ctx *c, LongRun const &R, PhaseACounters counts);    // what an attempt read back of phase A's counters
+int long_phase_b(fseq_ctx *c, LongRun &R);
+int long_list_capacity(fseq_ctx *c, LongRun &R);
+int short_phase_a(fseq_ctx *c, uint32_t *d_rank, uint32_t *d_keyd, uint32_t *d_nkeys);      // the short path's one block [0, n), ranked
+int red_plan(fseq_ctx *c, uint32_t X, bool *use);
+int red_columns(fseq_ctx *c);                         // the lists of the plan's reduced blocks, the largest configurations first
+// phase C on all rows of the blocks b0 .. b0 + nb - 1 (list: workgroup i owns block list[i] -- the blocks the plan hands to all rows)
+void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list = nullptr);
+
+// ---- csrc/fseq_path_attempt.hip
 void set_list_window(fseq_ctx *c, uint32_t lo_w);
 int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi);
 int run_long_path(fseq_ctx *c, fseq_result *res);

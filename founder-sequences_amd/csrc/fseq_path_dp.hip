@@ -282,7 +282,7 @@ int run_dp_spec(fseq_ctx *c, DpSchedule const &S, SpecPlan const &P, hipStream_t
 		SP.fresh = fresh ? 1u : 0u;
 		if (mine)
 			hipLaunchKernelGGL(k_dp<DP_SPEC>, dim3(mine), dim3(1024), dp_lds_bytes(), st, c->dp, c->d_ent, c->d_hdr, c->stride, m, n, L,
-			                   c->d_flags, 0u, 0u, SP);
+			                   path_words(c)->dp, 0u, 0u, SP);
 	};
 	auto compare = [&](bool first) {
 		hipLaunchKernelGGL(k_spec_scan, dim3(nch), dim3(256), 0, st, c->dp.M, c->d_Mprev, G, d_active, d_changed, d_tailmin, d_ctl);
@@ -445,13 +445,13 @@ int run_dp_spec(fseq_ctx *c, DpSchedule const &S, SpecPlan const &P, hipStream_t
 		rebuild();
 		uint32_t const first_dirty = std::min(h.first_changed + 1u, nch);
 		uint32_t const r0 = first_dirty < nch ? P.r0[first_dirty] : S.nreg;
-		HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 16, st));
+		HIP_TRY(c, hipMemsetAsync(path_words(c)->dp, 0, sizeof(PathWords::dp), st));
 		launch_dp_serial(c, DP_PARTIAL, st, r0, S.nrounds);
 		// overflow: the serial part reports through d_flags, the frozen chunks through their own words
 		std::vector<uint32_t> ovf(2 * (size_t) nch);
 		uint32_t fl[4] = {0, 0, 0, 0};
 		HIP_TRY(c, hipMemcpyAsync(ovf.data(), d_ovf, (size_t) nch * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(c, hipMemcpyAsync(fl, c->d_flags, 16, hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipMemcpyAsync(fl, path_words(c)->dp, sizeof(fl), hipMemcpyDeviceToHost, st));
 		HIP_TRY(c, hipStreamSynchronize(st));
 		HIP_TRY(c, hipGetLastError());
 		*overflow = (fl[0] & 1u) | own_overflow(ovf, P.mine_lo, std::min(P.mine_hi, h.first_changed + 1u));
@@ -502,7 +502,7 @@ int prepare_dp_kernels(fseq_ctx *c)
 void launch_dp_serial(fseq_ctx *c, int mode, hipStream_t st, uint32_t r_lo, uint32_t r_hi)
 {
 	hipLaunchKernelGGL((mode == DP_WHOLE ? k_dp<DP_WHOLE> : k_dp<DP_PARTIAL>), dim3(1), dim3(1024), dp_lds_bytes(), st, c->dp, c->d_ent, c->d_hdr, c->stride, c->p.m, (uint32_t) c->p.n,
-	                   (uint32_t) c->p.segment_length, c->d_flags, r_lo, r_hi, DpSpecArgs{});
+	                   (uint32_t) c->p.segment_length, path_words(c)->dp, r_lo, r_hi, DpSpecArgs{});
 }
 
 bool shard_dp_plan_ok(fseq_ctx *c)

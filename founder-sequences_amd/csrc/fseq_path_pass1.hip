@@ -1,11 +1,11 @@
-// fseq_path_pass1.hip -- the segmentation path, pass 1: phase A (the key blocks), phase B (the boundary states), the list
-// capacity, phase C on the blocks' representatives (the plan of an attempt) or on all rows, the list windows, one attempt and
-// the loop over attempts; the short path.  The one unit that instantiates k_colblock_stream<> and k_columns_stream<> and that
-// includes fseq_chainsort.hpp: pass 2 replays columns and takes its streamed chain steps through the launchers here.
+// fseq_path_pass1.hip -- the segmentation path, pass 1: phase A (the key blocks; the short path's one block), phase B (the
+// boundary states), the list capacity, phase C's launchers: on the blocks' representatives (the plan of an attempt) or on all
+// rows.  The attempt that queues them is csrc/fseq_path_attempt.hip.  The one unit that instantiates k_colblock_stream<> and
+// k_columns_stream<> and that includes fseq_chainsort.hpp: pass 2 replays columns and takes its streamed chain steps through
+// the launchers here.
 // (The units of the path and what crosses them: fseq_path.hpp.)
 #include "fseq_path.hpp"
 #include "fseq_kernels.hpp"
-#include "fseq_dp.hpp"           // the round schedule (list windows, the attempt)
 #include "fseq_stream.hpp"
 #include "fseq_stream2.hpp"
 #include "fseq_chainsort.hpp"
@@ -169,11 +169,6 @@ int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats)
 	return FSEQ_OK;
 }
 
-namespace {
-
-// diagnostic ("ABC" in FSEQ_SYNC_PHASES): synchronise behind a phase, so that a fault shows up at the phase that caused it
-bool sync_at(fseq_ctx const *c, char ph) { return c->tune.sync_phases.find(ph) != std::string::npos; }
-
 // ---- phase A: the key blocks of my column blocks (independent of the list capacity)
 int long_phase_a(fseq_ctx *c, LongRun &R)
 {
@@ -185,17 +180,17 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	{
 		uint64_t const lo = held_lo(c), hi = held_hi(c);
 		if ((rc = c->d_colmask.alloc_range(c, (size_t) lo, (size_t) hi, 1))) return rc;
-		HIP_TRY(c, hipMemsetAsync(c->d_flags + 67, 0, 4, st));
+		HIP_TRY(c, hipMemsetAsync(&path_words(c)->dense_columns, 0, 4, st));
 		hipLaunchKernelGGL(k_column_presence, dim3((uint32_t) std::min<uint64_t>(hi - lo, 8192)), dim3(256), 0, st, c->d_msa, c->ld, sym_bytes(m, c->bsh), lo, hi, c->d_colmask,
-		                   c->d_flags + 67);
+		                   &path_words(c)->dense_columns);
 		// (once per input: one column in twenty with at most four codes, and phase C is the kernel with the one-pass branch)
 		uint32_t n_dense = 0;
-		HIP_TRY(c, hipMemcpyAsync(&n_dense, c->d_flags + 67, 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipMemcpyAsync(&n_dense, &path_words(c)->dense_columns, 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(c, hipStreamSynchronize(st));
 		c->colmask_use = (uint64_t) n_dense * 20u >= hi - lo;
 		c->colmask_ready = true;
 	}
-	HIP_TRY(c, hipEventRecord(c->ev[0], st));
+	HIP_TRY(c, hipEventRecord(c->ev.a_begin, st));
 	progress(c, FSEQ_STAGE_TRACEBACK, 0, n);
 	FSEQ_RANGE_PUSH("fseq pass 1: phases A + B (block keys, boundary states)");
 	R.range_ab_open = true;                  // (popped in long_phase_b; run_long_path pops it when a phase fails in between)
@@ -217,7 +212,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		todo = c->d_todo;
 		HIP_TRY(c, hipMemsetAsync(todo, tree ? 0 : 0x01, (size_t) my_blocks * 4, st));     // (no tree: every block is the sweep's)
 	}
-	if (keyspace) HIP_TRY(c, hipMemsetAsync(c->d_flags + 64, 0, 12, st));
+	if (keyspace) HIP_TRY(c, hipMemsetAsync(&path_words(c)->phase_a, 0, sizeof(PhaseACounters), st));
 	// The trie over 32-bit group words first (fseq_blocktrie.hpp) -- it reads the block once and ranks only its distinct keys --
 	// and the key-space tree for the blocks it gives up (too many distinct keys for its tables).  As with the tree and the
 	// sweep, what the last run on this input saw decides what is launched: nothing given up -> the trie alone; most blocks ->
@@ -238,7 +233,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	keys.A = msa_args(c);
 	keys.rank = c->d_rank + (size_t) b_lo * m; keys.keyd = c->d_keyd + (size_t) b_lo * m; keys.nkeys = c->d_nkeys + b_lo;
 	keys.col0 = (uint64_t) b_lo * c->B; keys.nblk = my_blocks;
-	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words; keys.counters = c->d_flags + 64; keys.todo = todo;
+	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words; keys.counters = &path_words(c)->phase_a.tree_sliced; keys.todo = todo;
 	keys.wide = (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u);
 	if (trie)
 	{
@@ -251,7 +246,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		if ((rc = c->d_only.ensure(c, my_blocks))) return rc;
 		HIP_TRY(c, hipMemsetAsync(c->d_only, 0, (size_t) my_blocks * 4, st));
 		PhaseAArgs T = keys;
-		T.T = bt_T; T.work = c->d_btws; T.work_per = per; T.counters = c->d_flags + 66; T.todo = c->d_only;
+		T.T = bt_T; T.work = c->d_btws; T.work_per = per; T.counters = &path_words(c)->phase_a.trie_given_up; T.todo = c->d_only;
 		// The class columns of the blocks the trie ranks (its phase 3): what phase C's reduced alignment is gathered from instead of
 		// reading the alignment a second time.  Only where somebody will read them: streamed rows (LDS-resident row counts take the
 		// representatives' symbols from the alignment's own columns), the reduced phase C not switched off or declined on this input.
@@ -314,7 +309,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		keys.only = keyspace && tree ? todo : nullptr;
 		launch_rank(c, keys);
 	}
-	HIP_TRY(c, hipEventRecord(c->ev[1], st));
+	HIP_TRY(c, hipEventRecord(c->ev.a_end_b_begin, st));
 	if (sharded && c->tune.inject_failure_rank >= 0 && (uint32_t) c->tune.inject_failure_rank == sh.rank)
 		return fail(c, FSEQ_E_OOM, "injected failure (FSEQ_INJECT_FAILURE_RANK)");
 	if (sync_at(c, 'A')) { fprintf(stderr, "[fseq] phase A queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase A done\n"); }
@@ -342,6 +337,67 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 				return fail(c, FSEQ_E_HIP, what);
 			}
 		}
+	}
+	return FSEQ_OK;
+}
+
+// What an attempt read back of phase A's counters (fseq_path_attempt.hip: every attempt, whatever its verdict -- phase A runs once
+// a run, so every attempt of a run reads the same): the run's figures, and what the next run's phase A launches
+int phase_a_take_counts(fseq_ctx *c, LongRun const &R, PhaseACounters counts)
+{
+	FSEQ_LONG_LOCALS(c);
+	if (!R.keyspace) return FSEQ_OK;
+	if (!R.tree_ran) counts.tree_given_up = my_blocks;       // (no tree this time: every block went to the column sweep, as last time)
+	c->tm.phase_a_fallbacks = counts.tree_sliced;
+	c->tm.phase_a_given_up = counts.tree_given_up;
+	// (the tree ran alone because no block was given up last time; the same input gives the same outcome)
+	if (R.tree_alone && counts.tree_given_up != 0u) return fail(c, FSEQ_E_HIP, "internal: the key-space tree gave up blocks it ranked in the run before");
+	c->bk_given_up = (int) counts.tree_given_up;
+	if (R.trie_ran)
+	{
+		if (R.trie_alone && counts.trie_given_up != 0u) return fail(c, FSEQ_E_HIP, "internal: the block trie gave up blocks it ranked in the run before");
+		c->bt_given_up = (int) counts.trie_given_up;
+		c->tm.phase_a_trie_given_up = counts.trie_given_up;
+	}
+	return FSEQ_OK;
+}
+
+// the short path's phase A: one block [0, n), ranked in key space (fseq_blockkeys.hpp); FSEQ_PHASE_A_CLASSIC: the per-column sweep
+int short_phase_a(fseq_ctx *c, uint32_t *d_rank, uint32_t *d_keyd, uint32_t *d_nkeys)
+{
+	fseq_params const &p = c->p;
+	uint32_t const m = p.m;
+	int rc;
+	PhaseAArgs keys;
+	keys.A = msa_args(c, p.n, (uint32_t) p.n, 1);
+	keys.rank = d_rank; keys.keyd = d_keyd; keys.nkeys = d_nkeys; keys.nblk = 1;
+	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words;
+	keys.wide = (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u);
+	if (c->bk_cap_words && !c->tune.phase_a_classic)
+	{
+		if (c->use_stream)
+		{
+			size_t const per = (blockkeys_stream_ws_words(m, (uint32_t) p.n, c->bsh) + 15) & ~size_t(15);
+			if ((rc = c->d_bkws.ensure(c, per))) return rc;
+			keys.work = c->d_bkws; keys.work_per = per;
+			launch_blockkeys_stream(c, 1, keys);
+		}
+		else
+		{
+			size_t const per = (blockkeys_scratch_halfwords(m, (uint32_t) p.n, c->bsh) + 7) & ~size_t(7);
+			if (c->bk_per_block != per) c->d_bk.release(c);
+			if ((rc = c->d_bk.ensure(c, per))) return rc;
+			c->bk_per_block = per;
+			keys.work = c->d_bk; keys.work_per = per;
+			launch_blockkeys(c->stream, 1, c->bk_lds, keys);
+		}
+	}
+	else
+	{
+		// the 16-bit LDS kernels keep block-relative divergences in 16 bits: one block of 65536 columns or more would wrap
+		if (!c->use_stream && c->ks.cap > 7168u && p.n > 65535u)
+			return fail(c, FSEQ_E_UNSUPPORTED, "short path by column sweep: more than 65535 columns with 16-bit LDS state (unset FSEQ_PHASE_A_CLASSIC)");
+		launch_rank(c, keys);
 	}
 	return FSEQ_OK;
 }
@@ -440,7 +496,7 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 			}
 		}
 	}
-	HIP_TRY(c, hipEventRecord(c->ev[2], st));
+	HIP_TRY(c, hipEventRecord(c->ev.b_end, st));
 	HIP_TRY(c, hipGetLastError());
 	FSEQ_RANGE_POP();
 	R.range_ab_open = false;
@@ -490,6 +546,8 @@ int long_list_capacity(fseq_ctx *c, LongRun &R)
 	return FSEQ_OK;
 }
 
+namespace {
+
 // bytes of each staged-column buffer of a reduced configuration
 uint32_t red_symcap(fseq_ctx const *c, ReducedSet const &rs, bool direct)
 {
@@ -509,13 +567,11 @@ bool columns_fit_reduced(fseq_ctx const *c, ReducedSet const &rs, bool direct)
 void red_fill_args(fseq_ctx *c, RedArgs &RA)
 {
 	RA.cnt = c->d_red_cnt; RA.vmin = c->d_red_vmin; RA.a = c->d_red_a; RA.d = c->d_red_d; RA.leaf = c->d_red_leaf;
-	RA.invalid = c->d_red_invalid; RA.any_invalid = c->d_red_invalid + c->nblocks; RA.cap = c->red_cap; RA.m_true = c->p.m;
+	RA.invalid = c->d_red_invalid; RA.any_invalid = &red_flags(c)->unproven; RA.cap = c->red_cap; RA.m_true = c->p.m;
 	RA.direct = c->red_direct ? 1u : 0u; RA.colbytes = sym_bytes(c->p.m, c->bsh); RA.rank = c->d_rank;
 	RA.ss_a = c->d_red_ss_a; RA.ss_d = c->d_red_ss_d; RA.ss_stride = c->red_ss_stride; RA.ss_cap = c->red_ss_cap;
 	RA.blocks = c->d_red_blocks;                               // (the plan's block lists: red_launch_all indexes them; pass 2 brings its own)
 }
-
-namespace {
 
 // ---- [r5] phase C on representative rows (fseq_reduced.hpp): the plan of one attempt.
 // k_reduce_prep leaves, per block, the representatives and the reduced start state.  The blocks are sorted into the
@@ -568,7 +624,7 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	A.m = m; A.B = c->B; A.L = (uint32_t) L; A.cap = cap; A.block0 = b_lo; A.leaf_only = 0; A.n = n; A.direct = c->red_direct ? 1u : 0u;
 	A.Xp = X + (c->tune.reduced_margin >= 0 ? (uint32_t) c->tune.reduced_margin : X / 4u + 8u);
 	A.cnt = c->d_red_cnt; A.vmin = c->d_red_vmin; A.rows = c->d_red_rows; A.leaf = c->d_red_leaf; A.a = c->d_red_a; A.d = c->d_red_d;
-	A.invalid = c->d_red_invalid; A.flags = c->d_red_invalid + nbk;
+	A.invalid = c->d_red_invalid; A.flags = &red_flags(c)->unproven;      // (both words)
 	HIP_TRY(c, launch_reduce_prep(st, my_blocks, A));
 	// the reduced alignment of the listed blocks (streamed rows), by the plan in force when it is queued
 	// The listed blocks are two lists by where their columns come from: the blocks with class columns (phase A's trie ranked them: d_cls_have) are
@@ -585,7 +641,7 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	};
 	if (c->red_plan_valid && c->red_plan_X == X && c->red_force_full.size() == nbk)
 	{
-		launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, c->d_red_invalid + nbk);
+		launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, &red_flags(c)->unproven);      // (it sets the second word)
 		if (!c->red_direct)
 			reduce_msa();
 		c->tm.reduced_blocks = c->red_plan_blocks; c->tm.reduced_rows_mean = c->red_plan_rows_mean;
@@ -721,8 +777,6 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	return FSEQ_OK;
 }
 
-} // namespace
-
 // launches of the reduced column kernel over lists of workgroups, one per configuration, side by side: the first on the
 // context's stream, the others on streams of their own that wait for it and that it waits for
 
@@ -771,8 +825,6 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 	return FSEQ_OK;
 }
 
-namespace {
-
 // the lists of the reduced blocks
 int red_columns(fseq_ctx *c)
 {
@@ -785,6 +837,8 @@ int red_columns(fseq_ctx *c)
 	return red_launch_all(c, ls, RA, list_args(c));
 }
 
+namespace {
+
 // streamed rows, the first form of the column kernel (KS: bits of the keys its partition steps scan; 0: the has-based scan)
 template <int KS>
 void launch_columns_stream(fseq_ctx *c, uint32_t grid, ColumnsArgs const &C)
@@ -794,9 +848,11 @@ void launch_columns_stream(fseq_ctx *c, uint32_t grid, ColumnsArgs const &C)
 	                   C.bstate_a, C.bstate_d, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr, C.ss.snap_stride, C.ss.ss_a, C.ss.ss_d, C.block0, C.done_host, C.epoch, C.ss.ss_pack);
 }
 
+} // namespace
+
 // ---- phase C on all rows of the blocks b0 .. b0 + nb - 1
 // (list [r5]: workgroup i owns block list[i] instead of b0 + i -- the blocks the reduced phase C hands to the run on all rows)
-void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list = nullptr)
+void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list)
 {
 	FSEQ_LONG_LOCALS(c);
 	// columns phase C covers here: all, or my blocks plus the halo block's first columns (the lists my last DP round reads)
@@ -816,557 +872,6 @@ void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list 
 	else if (c->use_stream && (uint64_t) m + c->B < (1u << 19) && !c->tune.stream_plain_scan) launch_columns_stream<19>(c, nb, C);
 	else if (c->use_stream) launch_columns_stream<0>(c, nb, C);
 	else ks.columns(st, nb, c->lds_columns, C);
-}
-
-// ---- a list budget (fseq_set_list_memory): pass 1's lists in windows of wb consecutive column blocks.  Window w = blocks
-// [lo_w, hi_w) holds the lists of the columns [lo_w B - H, hi_w B) in one buffer (d_ent rebased to (lo_w B - H) stride:
-// the kernels address lists as they always do); phase C writes the window's own columns, the DP runs the rounds whose
-// lists are all there, and the last H columns move to the front for the next window.  H: the columns in front of a window
-// that its first DP round still reads.
-
-// DP rounds [.., r) that the lists of the columns < hi_w B feed: every regular round that reads no later column (its cells
-// read the lists of the columns e0 - 1 .. e0 + len - 2: dp_rounds_within); the drain round and the final cell wait for the
-// last window (the drain round's loads read column n - L, which an earlier window's buffer need not hold)
-uint32_t window_round_hi(fseq_ctx const *c, DpSchedule const &S, uint32_t hi_w)
-{
-	if (hi_w >= c->nblocks) return S.nrounds;
-	return std::min(dp_rounds_within(S, (uint64_t) hi_w * c->B), S.nreg);
-}
-
-// the window shape at list capacity X: the most blocks a window may have with the halo its rounds need beside them
-int plan_list_windows(fseq_ctx *c, uint32_t X)
-{
-	fseq_ctx::ListWindows &W = c->lw;
-	W.on = false;
-	W.merge_windows = 0;
-	uint64_t const n = c->p.n, L = c->p.segment_length, B = c->B, nb = c->nblocks;
-	if (!W.budget || c->sh.on || n < 2 * L) return FSEQ_OK;
-	uint64_t const stride = (X + 3) & ~1u, per_col = stride * sizeof(uint2), pad = 256 * sizeof(uint2);
-	if (n * per_col + pad <= W.budget) return FSEQ_OK;              // every list fits: the run as without a budget
-	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
-	uint64_t const cols = W.budget > pad ? (W.budget - pad) / per_col : 0;
-	// the halo that windows of wb blocks need: how far in front of a window the lowest column lies that its rounds read
-	auto halo_of = [&](uint64_t wb) {
-		uint64_t need = 0;
-		uint32_t r_lo = 0;
-		for (uint64_t lo = 0; lo < nb; lo += wb)
-		{
-			uint64_t const hi = std::min(nb, lo + wb);
-			uint32_t const r_hi = window_round_hi(c, S, (uint32_t) hi);
-			if (r_hi > r_lo)
-			{
-				uint64_t const first = (uint64_t) dp_round(S, r_lo).e0 - 1u;     // the lowest column the window's rounds read
-				if (lo * B > first) need = std::max(need, lo * B - first);
-				r_lo = r_hi;
-			}
-		}
-		return need;
-	};
-	auto take = [&](uint64_t wb, uint64_t H) {
-		W.on = true;
-		W.wb = (uint32_t) wb; W.H = (uint32_t) H;
-		W.nwin = (uint32_t) ((nb + wb - 1) / wb);
-		W.bytes = (H + wb * B) * per_col + pad;
-		return FSEQ_OK;
-	};
-	uint64_t H = S.RL;                                              // (a first guess, raised to what the windows' rounds read)
-	for (int it = 0; it < 64; ++it)
-	{
-		uint64_t const wb = cols > H ? std::min<uint64_t>(nb, (cols - H) / B) : 0;
-		// (the halo moves to the front in one copy: a window must be at least as wide as the halo)
-		if (wb == 0 || wb * B < H) break;
-		uint64_t const need = halo_of(wb);
-		if (need <= H) return take(wb, H);
-		H = need;
-	}
-	// The halo is no monotonic function of the window width: the drain round and the final cell wait for the last window and
-	// read from column n - L on, so the last window's halo is its start minus n - L -- up to L columns, and a few blocks more
-	// or less per window move that start anywhere.  Where the iteration above has run into a halo that leaves no window (or
-	// has not settled), every width is tried, the widest first.
-	uint64_t const wb_most = cols > S.RL ? std::min<uint64_t>(nb, (cols - S.RL) / B) : 0;
-	for (uint64_t wb = wb_most; wb >= 1; --wb)
-	{
-		uint64_t const Hw = std::max<uint64_t>(S.RL, halo_of(wb));
-		if (Hw + wb * B <= cols && wb * B >= Hw) return take(wb, Hw);
-	}
-	// no width fits: the refusal names the least shape that would (one window of all blocks is a shape, so there is one)
-	uint64_t wb_least = nb, H_least = S.RL;
-	for (uint64_t wb = 1; wb < nb; ++wb)
-	{
-		uint64_t const Hw = std::max<uint64_t>(S.RL, halo_of(wb));
-		if (wb * B >= Hw && Hw + wb * B < H_least + wb_least * B) { wb_least = wb; H_least = Hw; }
-	}
-	char what[320];
-	snprintf(what, sizeof(what), "list memory budget of %llu bytes holds no window: one window of %llu column block(s) of %llu columns plus a halo of %llu columns "
-	         "at list capacity %u needs %llu bytes", (unsigned long long) W.budget, (unsigned long long) wb_least, (unsigned long long) B, (unsigned long long) H_least, X,
-	         (unsigned long long) ((H_least + wb_least * B) * per_col + pad));
-	return fail(c, FSEQ_E_OOM, what);
-}
-
-} // namespace
-
-// the buffer holds window [lo_w, ..): column k at d_ent + k * stride
-void set_list_window(fseq_ctx *c, uint32_t lo_w)
-{
-	c->d_ent.rebase(((int64_t) lo_w * c->B - (int64_t) c->lw.H) * (int64_t) c->stride);
-}
-
-// phase C (lists, headers, stride states) of the blocks [lo, hi): on their representatives where this attempt's plan put
-// them (the plan's block lists ascend within every configuration, so a window's blocks are one stretch of each), else on
-// all rows
-int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
-{
-	if (!c->red_active)
-	{
-		launch_columns(c, lo, hi - lo);
-		return FSEQ_OK;
-	}
-	uint32_t const *const h_blocks = c->h_red_pin + c->nblocks;      // red_plan's host copy of d_red_blocks
-	auto stretch = [&](uint32_t first, uint32_t count) {
-		uint32_t const *const b = h_blocks + first, *const e = b + count;
-		uint32_t const *const a = std::lower_bound(b, e, lo), *const z = std::lower_bound(b, e, hi);
-		return std::make_pair(first + (uint32_t) (a - b), (uint32_t) (z - a));
-	};
-	RedArgs RA;
-	red_fill_args(c, RA);
-	std::vector<RedLaunch> ls;
-	for (auto const &bin : c->red_bins)
-	{
-		auto const r = stretch(bin.first, bin.count);
-		if (r.second) ls.push_back(RedLaunch{bin.config, r.first, r.second});
-	}
-	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
-	int rc;
-	if ((rc = red_launch_all(c, ls, RA, list_args(c)))) return rc;
-	auto const f = stretch(c->red_full_at, c->red_nfull);
-	if (f.second) launch_columns(c, 0, f.second, c->d_red_blocks + f.first);
-	return FSEQ_OK;
-}
-
-namespace {
-
-// pass 1 + the DP window by window (queued on the context's stream; overflow lands in d_flags as for the whole-array DP)
-int long_windows_cd(fseq_ctx *c, DpSchedule const &S)
-{
-	FSEQ_LONG_LOCALS(c);
-	fseq_ctx::ListWindows &W = c->lw;
-	while (W.ev.size() < 2 * (size_t) W.nwin)
-	{
-		hipEvent_t e = nullptr;
-		HIP_TRY(c, hipEventCreate(&e));
-		W.ev.push_back(e);
-	}
-	// (the entries no cell writes -- between the last regular cell and the final one -- read 0, as after dp_spec_reset)
-	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
-	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
-	HIP_TRY(c, hipMemsetAsync(c->dp.SZ, 0, c->dp_size * 4, st));
-	uint32_t r_lo = 0, w = 0, lo = 0;
-	for (; lo < c->nblocks; lo += W.wb, ++w)
-	{
-		uint32_t const hi = std::min(c->nblocks, lo + W.wb);
-		if (lo && W.H)
-			HIP_TRY(c, hipMemcpyAsync(c->d_ent.base, c->d_ent.base + (size_t) W.wb * c->B * c->stride, (size_t) W.H * c->stride * sizeof(uint2), hipMemcpyDeviceToDevice, st));
-		set_list_window(c, lo);
-		if ((rc = window_phase_c(c, lo, hi))) return rc;
-		uint32_t const r_hi = window_round_hi(c, S, hi);
-		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w], st));
-		if (r_hi > r_lo)
-		{
-			launch_dp_serial(c, DP_PARTIAL, st, r_lo, r_hi);
-			r_lo = r_hi;
-		}
-		HIP_TRY(c, hipEventRecord(W.ev[2 * (size_t) w + 1], st));
-	}
-	HIP_TRY(c, hipGetLastError());
-	uint32_t const lo_last = (W.nwin - 1u) * W.wb;
-	W.col_lo = (uint64_t) lo_last * c->B; W.col_hi = n;
-	if (c->tune.debug)
-		fprintf(stderr, "[fseq] list windows: %u windows of %u blocks (%llu columns) + a halo of %u columns, %.2f GB of lists at X = %u\n", W.nwin, W.wb,
-		        (unsigned long long) W.wb * c->B, W.H, W.bytes / 1e9, c->X);
-	return FSEQ_OK;
-}
-
-// the redo marking: the blocks of [b_lo, b_hi) whose lists the reduced phase C could not vouch for (d_red_invalid) run on all
-// rows -- or, RED_WIDE, on the next configuration -- when the attempt runs again, and the plan goes with them.
-// *count: the blocks marked; *wide: those of them that stay reduced
-int red_take_invalid(fseq_ctx *c, uint32_t b_lo, uint32_t b_hi, uint32_t *count, uint32_t *wide)
-{
-	std::vector<uint32_t> inv(c->nblocks);
-	HIP_TRY(c, hipMemcpy(inv.data(), c->d_red_invalid, (size_t) c->nblocks * 4, hipMemcpyDeviceToHost));
-	*count = *wide = 0;
-	for (uint32_t b = b_lo; b < b_hi; ++b)
-		if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = inv[b] == RED_WIDE ? RED_FORCE_WIDE : RED_FORCE_FULL; ++*count; *wide += inv[b] == RED_WIDE ? 1u : 0u; }
-	if (*count) c->red_plan_valid = false;
-	return FSEQ_OK;
-}
-
-int long_attempt(fseq_ctx *c, LongRun &R, bool *overflow_out)
-{
-	FSEQ_LONG_LOCALS(c);
-	uint32_t &X = R.X;
-	double &ms_c = R.ms_c, &ms_dp = R.ms_dp, &ms_host = R.ms_host;
-	bool const keyspace = R.keyspace;
-	// [r5] phase C on representative rows: the default wherever the lists are consumed by the speculative DP behind phase C
-	// (sharded: a rank's own blocks; its halo block has no state behind it to take the classes from and runs on all rows)
-	bool const red_candidate = !c->tune.no_reduced && n >= 2 * L;
-	double const t_att = now_ms();
-	auto mark = [&](char const *what) { if (c->tune.debug) fprintf(stderr, "[fseq]   attempt +%.3f ms %s\n", now_ms() - t_att, what); };
-	// a list budget the lists at this capacity exceed: pass 1 and the DP in column windows (long_windows_cd)
-	if ((rc = plan_list_windows(c, X))) return rc;
-	bool const windowed = c->lw.on;
-	if ((rc = ensure_work_buffers(c, X, !red_candidate))) return rc;
-	mark("lists allocated");
-	// ---- phase C + D
-#if defined(FSEQ_DP_STAMPS) || defined(FSEQ_DP_STATS)
-	HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 1024, st));
-#else
-	HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 16, st));
-#endif
-	if (c->tune.poison_lists)
-	{
-		// tests of the DP-beside-phase-C forms: a list read before it is written must not look right by accident
-		HIP_TRY(c, hipMemsetAsync(c->d_ent.base, 0xFF, c->d_ent.cap * sizeof(uint2), st));
-		HIP_TRY(c, hipMemsetAsync(c->d_hdr, 0xFF, (size_t) n * sizeof(uint4), st));
-	}
-	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
-	// the DP as chunk-speculative sweeps over the whole chip once every list is written (fseq_dpspec.hpp); the serial kernel for
-	// inputs too short for three chunks (and FSEQ_DP_SERIAL).  [r5] the forms that ran the serial DP beside phase C (in parts, or
-	// fed by host-visible flags) are gone: no default reached them
-	SpecPlan const spec = spec_plan(c, S);
-	bool const use_spec = !windowed && (sharded || spec.nchunks() > 0);
-	if (sharded && spec.nchunks() < 1) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: no DP chunk plan");
-	uint32_t spec_overflow = 0, spec_sweeps = 0;
-	HIP_TRY(c, hipEventRecord(c->ev[3], st));
-	RangeScope range_cd("fseq pass 1: phases C + D (column updates + lists, segmentation DP)");
-	{
-		if (use_spec)
-		{
-			// the arrays the speculative DP starts from are reset on the second stream while phase C runs
-			if ((rc = dp_spec_reset(c, spec, c->stream2))) return rc;
-			HIP_TRY(c, hipEventRecord(c->ev_part[15], c->stream2));
-		}
-		c->red_active = false;
-		if (red_candidate)
-		{
-			bool use = false;
-			if ((rc = red_plan(c, X, &use))) return rc;
-			mark("reduced plan");
-			if (use)
-			{
-				c->red_active = true;
-				if (!windowed)
-				{
-					if ((rc = red_columns(c))) return rc;
-					mark("reduced columns queued");
-					// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
-					if (c->red_nfull) launch_columns(c, 0, c->red_nfull, c->d_red_blocks + c->red_full_at);
-					// sharded: the block behind mine for as far as the halo reaches, on all rows (k_columns stops at n_c)
-					if (sharded && sh.c_end > sh.c_hi) launch_columns(c, b_hi, 1u);
-				}
-			}
-			else if ((rc = ensure_work_buffers(c, X, true))) return rc;      // (the stride states after all)
-		}
-		if (!sharded && !c->red_active && !windowed) launch_columns(c, 0, c->nblocks);
-		// (windows: phase C of a window, then the DP rounds its lists feed -- the DP is queued here, inside phase C's events)
-		if (windowed && (rc = long_windows_cd(c, S))) return rc;
-		if (sync_at(c, 'C')) { fprintf(stderr, "[fseq] phase C queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase C done\n"); }
-		if (sharded && my_blocks && !c->red_active)
-		{
-			// my blocks, and the block behind them for as far as the halo reaches (k_columns stops at n_c)
-			uint32_t const nb = my_blocks + ((sh.c_end > sh.c_hi) ? 1u : 0u);
-			launch_columns(c, b_lo, nb);
-		}
-		if (sharded && red_candidate)
-		{
-			// the ranks agree on whether the attempt stands BEFORE the DP's exchanges: a rank whose lists could not be proven
-			// on the representatives (or whose plan's counts have changed) makes every rank run the attempt again
-			uint32_t mine[2] = {0u, 0u};
-			if (c->red_active)
-			{
-				HIP_TRY(c, hipMemcpyAsync(mine, c->d_red_invalid + c->nblocks, 8, hipMemcpyDeviceToHost, st));
-				HIP_TRY(c, hipStreamSynchronize(st));
-			}
-			uint32_t word = (mine[0] ? 1u : 0u) | (mine[1] ? 2u : 0u);
-			HIP_TRY(c, hipMemcpyAsync(sh.xbuf, &word, 4, hipMemcpyHostToDevice, st));
-			if ((rc = shard_exchange(c, 1, 1))) return rc;
-			uint32_t all = 0;
-			HIP_TRY(c, hipMemcpy(&all, sh.xbuf, 4, hipMemcpyDeviceToHost));
-			if (all)
-			{
-				if (mine[1]) c->red_plan_valid = false;
-				if (mine[0])
-				{
-					uint32_t cnt = 0, wide = 0;
-					if ((rc = red_take_invalid(c, b_lo, b_hi, &cnt, &wide))) return rc;
-					c->red_plan_valid = false;
-					R.redone += cnt;
-				}
-				R.redo = true; *overflow_out = false;
-				HIP_TRY(c, hipEventRecord(c->ev[4], st));
-				HIP_TRY(c, hipEventRecord(c->ev_dp[0], st));
-				HIP_TRY(c, hipEventRecord(c->ev_dp[1], st));
-				HIP_TRY(c, hipStreamWaitEvent(st, c->ev_part[15], 0));
-				{ float f = 0; HIP_TRY(c, hipEventSynchronize(c->ev[4])); HIP_TRY(c, hipEventElapsedTime(&f, c->ev[3], c->ev[4])); R.ms_c += f; }
-				return FSEQ_OK;
-			}
-		}
-		HIP_TRY(c, hipEventRecord(c->ev[4], st));
-		HIP_TRY(c, hipEventRecord(c->ev_dp[0], st));
-		if (use_spec)
-		{
-			HIP_TRY(c, hipStreamWaitEvent(st, c->ev_part[15], 0));      // the DP arrays were reset beside phase C
-			if ((rc = run_dp_spec(c, S, spec, st, &spec_overflow, &spec_sweeps, true))) return rc;
-		}
-		else if (!windowed)
-			launch_dp_serial(c, DP_WHOLE, st, 0u, S.nrounds);
-		HIP_TRY(c, hipEventRecord(c->ev_dp[1], st));
-	}
-	HIP_TRY(c, hipEventRecord(c->ev[5], st));
-	HIP_TRY(c, hipGetLastError());
-	mark("DP queued");
-
-	if ((rc = pin_reserve(c, 64))) return rc;
-	uint32_t *const h_flags = pin_take<uint32_t>(c, 12);
-	h_flags[4] = 0;
-	HIP_TRY(c, hipMemcpyAsync(h_flags, c->d_flags, 16, hipMemcpyDeviceToHost, st));
-	h_flags[5] = 0;
-	h_flags[6] = 0;
-	if (keyspace) HIP_TRY(c, hipMemcpyAsync(h_flags + 4, c->d_flags + 64, 12, hipMemcpyDeviceToHost, st));
-	h_flags[6 + 1] = 0; h_flags[6 + 2] = 0;
-	uint32_t *const h_red = h_flags + 7;                         // {a block's lists not proven, the plan's counts have changed}
-	if (c->red_active && !sharded) HIP_TRY(c, hipMemcpyAsync(h_red, c->d_red_invalid + c->nblocks, 8, hipMemcpyDeviceToHost, st));      // (sharded: agreed on before the DP)
-	HIP_TRY(c, hipStreamSynchronize(st));
-	R.redo = false;
-	if (c->red_active && h_red[1])
-	{
-		// (the counts are not what the plan was made from: plan afresh)
-		c->red_plan_valid = false;
-		R.redo = true; *overflow_out = false;
-		return FSEQ_OK;
-	}
-	if (c->red_active && h_red[0])
-	{
-		uint32_t cnt = 0, wide = 0;
-		if ((rc = red_take_invalid(c, 0, c->nblocks, &cnt, &wide))) return rc;
-		if (c->tune.debug) fprintf(stderr, "[fseq] reduced phase C: the lists of %u blocks reach below what their representatives vouch for: those blocks again on all rows\n", cnt - wide);
-		if (c->tune.debug && wide) fprintf(stderr, "[fseq] reduced phase C: %u blocks hold more distinct start values than the slim configuration's table: those blocks again on the next configuration\n", wide);
-		if (cnt) { R.redo = true; R.redone += cnt; *overflow_out = false; return FSEQ_OK; }
-	}
-	if (keyspace)
-	{
-		if (!R.tree_ran) h_flags[5] = my_blocks;               // (no tree this time: every block went to the column sweep, as last time)
-		c->tm.phase_a_fallbacks = h_flags[4];
-		c->tm.phase_a_given_up = h_flags[5];
-		// (the tree ran alone because no block was given up last time; the same input gives the same outcome)
-		if (R.tree_alone && h_flags[5] != 0u) return fail(c, FSEQ_E_HIP, "internal: the key-space tree gave up blocks it ranked in the run before");
-		c->bk_given_up = (int) h_flags[5];
-		if (R.trie_ran)
-		{
-			if (R.trie_alone && h_flags[6] != 0u) return fail(c, FSEQ_E_HIP, "internal: the block trie gave up blocks it ranked in the run before");
-			c->bt_given_up = (int) h_flags[6];
-			c->tm.phase_a_trie_given_up = h_flags[6];
-		}
-	}
-	{
-		float f = 0;
-		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[3], c->ev[4])); ms_c += f;
-		HIP_TRY(c, hipEventElapsedTime(&f, c->ev_dp[0], c->ev_dp[1])); ms_dp += f;
-		for (uint32_t w = 0; windowed && w < c->lw.nwin; ++w)
-		{
-			// (the windows' DP launches ran between phase C's events)
-			HIP_TRY(c, hipEventElapsedTime(&f, c->lw.ev[2 * (size_t) w], c->lw.ev[2 * (size_t) w + 1]));
-			ms_c -= f; ms_dp += f;
-		}
-	}
-#ifdef FSEQ_DP_STAMPS
-	{
-		unsigned long long stamps[96];
-		HIP_TRY(c, hipMemcpy(stamps, c->d_flags + 8, sizeof(stamps), hipMemcpyDeviceToHost));
-		for (int w = 0; w < 16; ++w)
-		{
-			unsigned long long const *q = stamps + 48 + 3 * w;
-			double const nr = (double) (stamps[3 * w + 2] ? stamps[3 * w + 2] : 1);
-			fprintf(stderr, "[dp stamps] wave %2d cycles/round: barrier 1 = %.0f, update = %.0f, barrier 2 = %.0f\n", w, q[0] / nr, q[1] / nr, q[2] / nr);
-		}
-		for (int w = 0; w < 16; ++w)
-		{
-			unsigned long long const *q = stamps + 3 * w;
-			double const nr = (double) (q[2] ? q[2] : 1);
-			fprintf(stderr, "[dp stamps] wave %2d rounds=%llu cycles/round: work=%.0f waits=%.0f\n", w, q[2], q[0] / nr, q[1] / nr);
-		}
-	}
-#endif
-#ifdef FSEQ_DP_STATS
-	{
-		uint32_t hist[34];
-		HIP_TRY(c, hipMemcpy(hist, c->d_flags + 128, sizeof(hist), hipMemcpyDeviceToHost));
-		fprintf(stderr, "[dp stats] list entries a cell needed (cell-pair path; last = more than 32):");
-		for (int i = 0; i < 34; ++i) fprintf(stderr, " %u", hist[i]);
-		fprintf(stderr, "\n");
-	}
-#endif
-	range_cd.end();
-	progress(c, FSEQ_STAGE_TRACEBACK, n, n);
-	RangeScope range_tb("fseq traceback + find_segments_greedy");
-	double const th0 = now_ms();
-	bool overflow = (h_flags[0] & 1u) != 0 || spec_overflow != 0;
-	c->tm.dp_sweeps = spec_sweeps;
-	c->tm.dp_chunks = use_spec ? spec.nchunks() : 0u;
-
-	if (!overflow && (rc = long_traceback_and_merge(c, th0, &overflow))) return rc;
-	ms_host += now_ms() - th0;
-	range_tb.end();
-	if (!overflow) progress(c, FSEQ_STAGE_MERGE, c->traceback.size(), c->traceback.size());
-	if (c->tune.debug) fprintf(stderr, "[fseq] host: traceback + merge %.3f ms\n", now_ms() - th0);
-	*overflow_out = overflow;
-	return FSEQ_OK;
-}
-
-} // namespace
-
-int run_long_path(fseq_ctx *c, fseq_result *res)
-{
-	FSEQ_LONG_LOCALS(c);
-	LongRun R;
-	R.X = p.list_cap ? p.list_cap : std::max(FSEQ_X_FLOOR, c->X_hint);
-	c->tm = fseq_timings{};
-	c->tm.block_len = c->B;
-	c->tm.n_blocks = c->nblocks;
-	double const t_begin = now_ms();
-
-	// (FSEQ_DEBUG: where the host's wall time of a run goes -- a first run on a context allocates, loads code objects, plans)
-	auto mark = [&](char const *what) { if (c->tune.debug) fprintf(stderr, "[fseq] +%.3f ms %s\n", now_ms() - t_begin, what); };
-	if ((rc = ensure_work_buffers(c, 0))) return rc;
-	mark("work buffers");
-	auto close_ab = [&](int code) { if (R.range_ab_open) { FSEQ_RANGE_POP(); R.range_ab_open = false; } return code; };
-	if ((rc = long_phase_a(c, R))) return close_ab(rc);
-	mark("phase A queued");
-	if ((rc = long_phase_b(c, R))) return close_ab(rc);
-	mark("phase B queued");
-	if ((rc = long_list_capacity(c, R))) return rc;
-	mark("list capacity");
-	while (true)
-	{
-		bool overflow = false;
-		if ((rc = long_attempt(c, R, &overflow))) return rc;
-		mark("attempt done");
-		if (R.redo) continue;                  // (the same capacity; the blocks that were flagged run on all rows now)
-		// (sharded: the thresholds are the same on every rank, so every rank takes the same way here)
-		if (!overflow) break;
-		if (R.X >= m) return fail(c, FSEQ_E_HIP, "internal: divergence lists complete but DP flagged overflow");
-		R.X = (uint32_t) std::min<uint64_t>(m, (uint64_t) R.X * 2 + 1);
-		++R.retries;
-		if (c->tune.debug) fprintf(stderr, "[fseq] divergence lists too short, retry %u with X = %u\n", R.retries, R.X);
-	}
-	c->X_hint = R.X;                         // later runs on this context start with the capacity that worked
-	c->res.segment_count = c->segments.size();
-	if ((rc = long_pass2(c, R))) return rc;
-	mark("pass 2 done");
-	uint32_t const X = R.X, retries = R.retries;
-	double const ms_c = R.ms_c, ms_dp = R.ms_dp, ms_host = R.ms_host, ms_p2 = R.ms_p2;
-	uint64_t const pass2_cells = R.pass2_cells;
-	size_t const S2 = c->segments.size();
-	{
-		float f = 0;
-		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[0], c->ev[1])); c->tm.ms_phase_a = f;
-		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[1], c->ev[2])); c->tm.ms_phase_b = f;
-	}
-	c->tm.ms_phase_c = ms_c;
-	c->tm.ms_dp = ms_dp;
-	c->tm.ms_pass2 = ms_p2;
-	c->tm.ms_host = ms_host;
-	c->tm.ms_colstep_kernels = c->tm.ms_phase_a + ms_c + ms_p2;
-	c->tm.colstep_launches = 2 + retries + (S2 ? 1 : 0);
-	c->tm.colstep_cells = (uint64_t) m * n * (2 + retries) + pass2_cells;
-	c->tm.pass2_cells = pass2_cells;
-	c->tm.list_cap_used = X;
-	c->tm.retries = retries;
-	c->tm.reduced_redone = R.redone;
-	if (!c->red_active) { c->tm.reduced_blocks = 0; c->tm.reduced_rows_mean = 0; }
-	c->tm.ms_total = now_ms() - t_begin;
-	c->have_result = true;
-	*res = c->res;
-	if (!(c->res.max_segment_size < m))
-		return fail(c, FSEQ_E_NO_REDUCTION, "Unable to reduce the number of sequences; the maximum segment size is equal to the number of input sequences.");
-	return FSEQ_OK;
-}
-
-// segmentation_sp_context::process (segmentation_sp_context.cc:21-28): one sweep over all n columns
-// from the identity; the distinct rows are the block keys of a single block [0, n).
-int run_short_path(fseq_ctx *c, fseq_result *res)
-{
-	fseq_params const &p = c->p;
-	uint32_t const m = p.m;
-	hipStream_t st = c->stream;
-	int rc;
-	c->tm = fseq_timings{};
-	double const t_begin = now_ms();
-	DevTemp<uint32_t> d_rank(c), d_keyd(c), d_nk(c);
-	if ((rc = d_rank.alloc(m)) || (rc = d_keyd.alloc(m)) || (rc = d_nk.alloc(4))) return rc;
-	if (c->use_stream && !c->d_ws && (rc = c->d_ws.alloc(c, (size_t) 4 * m))) return rc;
-	// one block [0, n): ranked in key space (fseq_blockkeys.hpp); FSEQ_PHASE_A_CLASSIC: the per-column sweep
-	PhaseAArgs keys;
-	keys.A = msa_args(c, p.n, (uint32_t) p.n, 1);
-	keys.rank = d_rank; keys.keyd = d_keyd; keys.nkeys = d_nk; keys.nblk = 1;
-	keys.T = c->bk_T; keys.cap_words = c->bk_cap_words;
-	keys.wide = (c->tune.blockkeys_wide ? 1u : 0u) | (c->tune.blockkeys_single ? 2u : 0u);
-	if (c->bk_cap_words && !c->tune.phase_a_classic)
-	{
-		if (c->use_stream)
-		{
-			size_t const per = (blockkeys_stream_ws_words(m, (uint32_t) p.n, c->bsh) + 15) & ~size_t(15);
-			if ((rc = c->d_bkws.ensure(c, per))) return rc;
-			keys.work = c->d_bkws; keys.work_per = per;
-			launch_blockkeys_stream(c, 1, keys);
-		}
-		else
-		{
-			size_t const per = (blockkeys_scratch_halfwords(m, (uint32_t) p.n, c->bsh) + 7) & ~size_t(7);
-			if (c->bk_per_block != per) c->d_bk.release(c);
-			if ((rc = c->d_bk.ensure(c, per))) return rc;
-			c->bk_per_block = per;
-			keys.work = c->d_bk; keys.work_per = per;
-			launch_blockkeys(st, 1, c->bk_lds, keys);
-		}
-	}
-	else
-	{
-		// the 16-bit LDS kernels keep block-relative divergences in 16 bits: one block of 65536 columns or more would wrap
-		if (!c->use_stream && c->ks.cap > 7168u && p.n > 65535u)
-			return fail(c, FSEQ_E_UNSUPPORTED, "short path by column sweep: more than 65535 columns with 16-bit LDS state (unset FSEQ_PHASE_A_CLASSIC)");
-		launch_rank(c, keys);
-	}
-	std::vector<uint32_t> rank(m);
-	uint32_t nk = 0;
-	hipError_t e1 = hipMemcpyAsync(rank.data(), d_rank, (size_t) m * 4, hipMemcpyDeviceToHost, st);
-	hipError_t e2 = hipMemcpyAsync(&nk, d_nk, 4, hipMemcpyDeviceToHost, st);
-	hipError_t e3 = hipStreamSynchronize(st);
-	release_all(c, d_rank, d_keyd, d_nk);                          // (not held through the host's part below)
-	if (e1 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e1);
-	if (e2 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path copy", e2);
-	if (e3 != hipSuccess) return fail(c, FSEQ_E_HIP, "short path sync", e3);
-	// identical rows keep ascending row-id order in the pBWT, so a run's first row is its smallest id
-	c->sp_first.assign(nk, 0xFFFFFFFFu);
-	c->sp_len.assign(nk, 0);
-	for (uint32_t r = 0; r < m; ++r)
-	{
-		uint32_t const k = rank[r];
-		if (c->sp_first[k] == 0xFFFFFFFFu) c->sp_first[k] = r;
-		++c->sp_len[k];
-	}
-	c->res = fseq_result{};
-	c->res.max_segment_size = nk;
-	c->res.short_path = 1;
-	c->traceback.clear();
-	c->segments.clear();
-	c->tm.colstep_launches = 1;
-	c->tm.colstep_cells = (uint64_t) m * p.n;
-	c->tm.ms_total = now_ms() - t_begin;
-	c->have_result = true;
-	*res = c->res;
-	if (!(nk < m))
-		return fail(c, FSEQ_E_NO_REDUCTION, "Unable to reduce the number of sequences; the maximum segment size is equal to the number of input sequences.");
-	return FSEQ_OK;
 }
 
 } // namespace fseq

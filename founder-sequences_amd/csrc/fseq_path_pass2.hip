@@ -170,7 +170,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	}
 	uint32_t *const pin_stats = reinterpret_cast<uint32_t *>(c->h_red_pin2 + c->red_pin2_bytes - P2_STATS * 4);      // (behind the task lists)
 	c->p2_stats_have = false;
-	HIP_TRY(c, hipEventRecord(c->ev[6], st));
+	HIP_TRY(c, hipEventRecord(c->ev.pass2_begin, st));
 	progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 	RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
 	// the class tables at the task columns, configuration by configuration
@@ -231,14 +231,14 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		for (size_t g = 0; g < o_grp.size(); ++g) cells += (o_rbs[o_grp[g].x + o_grp[g].y - 1] - o_srcs[g] * c->B) * m;
 		HIP_TRY(c, hipStreamSynchronize(st));
 	}
-	HIP_TRY(c, hipEventRecord(c->ev[7], st));
+	HIP_TRY(c, hipEventRecord(c->ev.pass2_end, st));
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(st));
 	range_p2.end();
 	if (c->p2_stats_have) memcpy(c->p2_stats, pin_stats, sizeof(c->p2_stats));
 	progress(c, FSEQ_STAGE_SAMPLES, S2, S2);
 	float f = 0;
-	HIP_TRY(c, hipEventElapsedTime(&f, c->ev[6], c->ev[7])); R.ms_p2 = f;
+	HIP_TRY(c, hipEventElapsedTime(&f, c->ev.pass2_begin, c->ev.pass2_end)); R.ms_p2 = f;
 	R.pass2_cells = cells;
 	return pass2_sum_cells(c, R, st);
 }
@@ -306,7 +306,7 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 			if (S2m) HIP_TRY(c, hipMemcpyAsync(c->d_cols, prb, S2m * 8, hipMemcpyHostToDevice, st));
 			if (!grp.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_grp, pgrp, grp.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
 		}
-		HIP_TRY(c, hipEventRecord(c->ev[6], st));
+		HIP_TRY(c, hipEventRecord(c->ev.pass2_begin, st));
 		progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 		RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
 		// the states at my boundaries, every group swept from its block's boundary state or a stride state
@@ -348,13 +348,13 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 		}
 		else if (c->use_stream) launch_replay_stream(c, grp.size(), tasks);
 		else if (!grp.empty()) ks.snap(st, (uint32_t) grp.size(), ks.lds_snap, tasks);
-		HIP_TRY(c, hipEventRecord(c->ev[7], st));
+		HIP_TRY(c, hipEventRecord(c->ev.pass2_end, st));
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipStreamSynchronize(st));
 		range_p2.end();
 		progress(c, FSEQ_STAGE_SAMPLES, S2, S2);
 		float f = 0;
-		HIP_TRY(c, hipEventElapsedTime(&f, c->ev[6], c->ev[7])); ms_p2 = f;
+		HIP_TRY(c, hipEventElapsedTime(&f, c->ev.pass2_begin, c->ev.pass2_end)); ms_p2 = f;
 		if ((rc = pass2_sum_cells(c, R, st))) return rc;
 	}
 

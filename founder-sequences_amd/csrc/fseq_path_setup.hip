@@ -363,7 +363,7 @@ int alloc_geometry_buffers(fseq_ctx *c)
 		if ((rc = c->d_hstate_d.alloc(c, ((size_t) c->n_hyper + 1) * m))) return rc;
 	}
 	if ((rc = c->d_hdr.alloc(c, p.n))) return rc;
-	if ((rc = c->d_flags.alloc(c, 256))) return rc;
+	if ((rc = c->d_flags.alloc(c, 1))) return rc;
 	if ((rc = c->d_recent.alloc(c, c->nblocks + 1))) return rc;
 	if (p.n >= 2 * p.segment_length)
 	{

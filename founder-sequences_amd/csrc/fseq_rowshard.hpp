@@ -1,7 +1,7 @@
 // fseq_rowshard.hpp -- the pBWT column update with the POSITIONS of the order sharded over ranks: the partition
 // BASELINE.json's north_star names ("rows shard across the GPUs with a per-column sigma-bucket-histogram all-reduce
 // and a boundary exchange for the divergence scan").  This is the conformance
-// path beside the column-block split of fseq_path_pass1.hip (which needs one exchange per PHASE, not per column): every
+// path beside the column-block split of fseq_path_attempt.hip (which needs one exchange per PHASE, not per column): every
 // column costs two all-reduces here, so the sweep runs at the latency of the collective, not at the speed of the
 // arithmetic -- DESIGN.md section 6 holds the measured curve.
 //

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace fseq {
@@ -13,6 +14,47 @@ struct DpArrays {
 	uint32_t *M, *LB, *SZ, *Tb, *Tbv;
 	unsigned long long *K;
 	uint32_t tstride;
+};
+
+// ---- The path's device words (fseq_ctx::d_flags): what the kernels of a run report in single words, every region named here
+// and nowhere else.  A kernel keeps its pointer parameter and is handed the address of its own region.
+// phase A's counters: the key-space tree's `counters` are the first two, the trie's the third
+struct PhaseACounters {
+	uint32_t tree_sliced;                // blocks whose merges the key-space tree sliced
+	uint32_t tree_given_up;              // blocks it handed to the column sweep
+	uint32_t trie_given_up;              // blocks the trie handed to the tree
+};
+struct PathWords {
+	uint32_t dp[4];                      // k_dp's `flags`: bit 0 of [0] = a list too short to prove a cell, [1] = the lowest entry read; cleared and read as 16 bytes
+	PhaseACounters phase_a;
+	uint32_t dense_columns;              // k_column_presence: columns with at most four codes
+	// diagnostic builds, behind the production words: -DFSEQ_DP_STAMPS (cycle stamps, 3 per wave: the waves' own schedule, then
+	// the classic one), -DFSEQ_DP_STATS (list entries a cell needed: 0 .. 32, more)
+	unsigned long long dp_stamps[96];
+	uint32_t dp_hist[34];
+};
+// what the diagnostic k_dp adds to its `flags` (= PathWords::dp), in words: the kernel and the host's read-back use these
+constexpr uint32_t DP_STAMPS_AT = (uint32_t) ((offsetof(PathWords, dp_stamps) - offsetof(PathWords, dp)) / 4);
+constexpr uint32_t DP_HIST_AT = (uint32_t) ((offsetof(PathWords, dp_hist) - offsetof(PathWords, dp)) / 4);
+static_assert(offsetof(PathWords, dp) + sizeof(PathWords::dp) <= offsetof(PathWords, phase_a)
+              && offsetof(PathWords, phase_a) + sizeof(PhaseACounters) <= offsetof(PathWords, dense_columns)
+              && offsetof(PathWords, dense_columns) + 4 <= offsetof(PathWords, dp_stamps)
+              && offsetof(PathWords, dp_stamps) + sizeof(PathWords::dp_stamps) <= offsetof(PathWords, dp_hist)
+              && offsetof(PathWords, dp_hist) + sizeof(PathWords::dp_hist) <= sizeof(PathWords)
+              && offsetof(PathWords, dp_stamps) % 8 == 0, "the path's device words: no region overlaps another");
+
+// the two words behind d_red_invalid[nblocks] (red_flags, fseq_path.hpp): k_reduce_prep clears both, the reduced column kernels
+// set the first with invalid[b], k_reduce_check the second
+struct RedFlags {
+	uint32_t unproven;                   // a block's lists took an entry its representatives cannot vouch for
+	uint32_t plan_stale;                 // the counts are not the ones the plan was made from
+};
+
+// what an attempt reads back at its end (pinned, run_long_path)
+struct AttemptWords {
+	uint32_t dp[4];
+	PhaseACounters phase_a;
+	RedFlags red;
 };
 
 // ---- What the launchers of the path take (the kernel tables of fseq_ctx.hpp, the launch_* functions): plain host-side views

@@ -4,7 +4,7 @@ oracle; the product never imports it):
 
 * the chunk-speculative DP (founder-sequences_amd/csrc/fseq_dpspec.hpp): fresh chunk sweeps, the (min,max)-linear
   floor lift, verify sweeps until no key changes;
-* ONE alignment over several ranks (fseq_set_shard, csrc/fseq_path_pass1.hip run_long_path): contiguous column-block
+* ONE alignment over several ranks (fseq_set_shard, csrc/fseq_path_attempt.hip run_long_path): contiguous column-block
   shares, the hyper key block exchange of phase B, the per-sweep key exchange of the DP, the merge by
   per-boundary thresholds (k_seg_tau), pass 2 on the owners.  Every exchange goes through ONE callback
   allreduce(np.int64 array, op) -> array, exactly the primitive the library asks its caller for.

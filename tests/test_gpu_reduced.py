@@ -146,3 +146,29 @@ def test_sharded_reduced_run_matches_oracle(pkg, always, world):
         ctxs = run_world(pkg, world, lambda c: c.set_sequences(msa), m, n, L, block_len=B)
         check_against_oracle(pkg, ctxs, msa, L)
         assert all(c.timings()["reduced_blocks"] > 0 for c in ctxs)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_agreement_sends_every_rank_round_again(pkg, always, world):
+    """No margin in a sharded world: a rank whose lists reach below what its representatives vouch for makes every rank run the
+    attempt again, agreed on before the DP's exchanges (csrc/fseq_path_attempt.hip).  The shapes of
+    test_lists_below_the_floor_send_the_block_to_all_rows; both reach a redo in worlds of 2 and of 3 ranks."""
+    always.setenv("FSEQ_REDUCED_MARGIN", "0")
+    redone = 0
+    for (m, n, L, K, Brec, mu, seed, B, cap) in [(400, 4000, 20, 6, 150, 3e-3, 81, 100, 8), (1200, 3000, 30, 10, 200, 2e-3, 82, 128, 24)]:
+        msa = fso.synth_msa(fso.synth_spec(seed, K, Brec, mu, 0), m, n)
+        ctxs = run_world(pkg, world, lambda c: c.set_sequences(msa), m, n, L, block_len=B, list_cap=cap)
+        check_against_oracle(pkg, ctxs, msa, L)
+        ts = [c.timings() for c in ctxs]
+        print("m = %d, world = %d: redone %s, retries %s, ms_phase_c %s, ms_dp %s" % (
+            m, world, [t["reduced_redone"] for t in ts], [t["retries"] for t in ts], [t["ms_phase_c"] for t in ts], [t["ms_dp"] for t in ts]))
+        shape_redone = sum(t["reduced_redone"] for t in ts)
+        assert shape_redone > 0, ts                          # (every shape kept here reaches a redo at this world size)
+        redone += shape_redone
+        assert len({t["retries"] for t in ts}) == 1, ts      # every rank took the same way through the attempts
+        for t in ts:
+            # the phases' times cover every attempt, the ones sent round again too
+            assert np.isfinite(t["ms_phase_c"]) and t["ms_phase_c"] >= 0 and np.isfinite(t["ms_dp"]) and t["ms_dp"] >= 0, t
+    assert redone > 0
+    pushes, pops, _ = pkg.debug_ranges()
+    assert pushes == pops
