@@ -101,12 +101,12 @@ EXPORTS = [
     "fseq_match_founders", "fseq_match_founder_rows", "fseq_get_match", "fseq_write_match",
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
-    "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns",
+    "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns"]
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -211,6 +211,7 @@ def load_library():
     L.fseq_debug_device_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.c_int]
     L.fseq_debug_packed_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_join_path.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fseq_debug_bipartite_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
     L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
     _lib = L
@@ -779,6 +780,12 @@ class SegmentationContext:
         """Which way the last join_greedy() went: 0 the all-host joiner, 1 the LDS device front, 2 the wide device front."""
         path = C.c_int()
         self._check(self.L.fseq_debug_join_path(self.h, C.byref(path)))
+        return path.value
+
+    def bipartite_path(self):
+        """Which way the last join_bipartite() went: 0 the host joiner, 1 the LDS device form, 2 the wide device form."""
+        path = C.c_int()
+        self._check(self.L.fseq_debug_bipartite_path(self.h, C.byref(path)))
         return path.value
 
     def pass2_paths(self):

@@ -10,6 +10,7 @@
 #include "fseq_join.hpp"
 #include "fseq_joinprep.hpp"
 #include "fseq_joinbip.hpp"
+#include "fseq_joinbipw.hpp"
 
 using namespace fseq;
 
@@ -79,6 +80,80 @@ static int join_greedy_wide(fseq_ctx *c, uint32_t *permutations, double t0, bool
 	greedy_match_prepared(c->p.m, X, S, count.data(), rep.data(), size.data(), edge_words.data(), off.data(), ne.data(), permutations, &prof);
 	c->jp = fseq_join_profile{t1 - t0, prof.ms_classes, prof.ms_edges, prof.ms_draw, now_ms() - t0,
 	                          (uint64_t) S * (2ull * X + 3) * 4 + (uint64_t) total * 8};
+	*done = true;
+	return FSEQ_OK;
+}
+
+// Boundary states from which fseq_join_bipartite takes the wide form by itself when max_segment_size is above JP_MAX_CLASSES:
+// the smallest swept size from which it beat the host joiner at every larger one was 4.2 MB, so the floor of 16 MiB decides
+// (profiles/join_bip_wide.txt, tools/join_bip_wide_probe.py; the sweep ends at 17 MB, BASELINE C4 ran through the wide form alone).
+static constexpr uint64_t JOIN_BIP_WIDE_MIN_BYTES = 16ull << 20;
+
+// The wide device form of fseq_join_bipartite (fseq_joinbipw.hpp), for any X up to JBW_MAX_TEXTS.  *done = false with
+// FSEQ_OK: the caller goes on to the host joiner (a failed device allocation -- not one slab --, implausible class counts),
+// with the error text cleared.
+static int join_bipartite_wide(fseq_ctx *c, uint32_t *permutations, bool *done)
+{
+	*done = false;
+	(void) hipSetDevice(c->p.device);
+	double const t0 = now_ms();
+	size_t const m = c->p.m, S = c->segments.size();
+	uint32_t const X = c->res.max_segment_size;
+	uint32_t const pairs = (uint32_t) (S - 1);
+	hipStream_t st = c->stream;
+	DevTemp<uint16_t> d_of(c), d_tpos(c), d_src(c), d_match(c);
+	DevTemp<uint32_t> d_rep(c), d_size(c), d_count(c), d_start(c), d_min(c), d_reprow(c), d_perm(c), d_slabs(c);
+	DevTemp<uint64_t> d_rb(c);
+	auto no_room = [&](int rc) { if (rc == FSEQ_E_OOM) { c->err.clear(); return (int) FSEQ_OK; } return rc; };      // (the host joiner needs no device memory)
+	int rc;
+	if ((rc = d_of.alloc(S * m)) || (rc = d_tpos.alloc(S * X)) || (rc = d_src.alloc(S * X)) || (rc = d_match.alloc(S * X)) ||
+	    (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) || (rc = d_start.alloc(S * ((size_t) X + 1))) ||
+	    (rc = d_min.alloc(S * X)) || (rc = d_reprow.alloc(S * X)) || (rc = d_perm.alloc(S * X)) || (rc = d_rb.alloc(S)))
+		return no_room(rc);
+	size_t const lds_texts = bip_texts_wide_lds_bytes(X), lds_match = bip_match_wide_lds_bytes(X);
+	// G slabs = persistent workgroups: the pairs, what the CUs hold at once (two workgroups a CU while their LDS allows it),
+	// FSEQ_JOIN_BIP_SLABS, and half of what is free on the device and of what is left of the context's memory budget
+	uint32_t G = 0;
+	if (pairs)
+	{
+		int ncu = 0;
+		if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->p.device) != hipSuccess || ncu < 1) { (void) hipGetLastError(); ncu = 1; }
+		size_t const slab = (size_t) X * X * 4;
+		size_t free_b = 0, total_b = 0;
+		if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = slab; }
+		uint64_t room = free_b / 2;
+		if (c->mem_budget) room = std::min<uint64_t>(room, (c->mem_budget > c->alloc_total ? c->mem_budget - c->alloc_total : 0) / 2);
+		uint64_t g = std::min<uint64_t>(pairs, (uint64_t) ncu * (2 * lds_match <= JBW_LDS_CU ? 2u : 1u));
+		if (c->tune.join_bip_slabs > 0) g = std::min<uint64_t>(g, (uint64_t) c->tune.join_bip_slabs);
+		g = std::max<uint64_t>(1, std::min<uint64_t>(g, room / slab));
+		while (g && !d_slabs.try_alloc(c, (size_t) g * X * X)) g /= 2;
+		if (!g) return FSEQ_OK;                                   // (no slab: the host joiner)
+		G = (uint32_t) g;
+		if (c->tune.debug) fprintf(stderr, "[fseq] bipartite join, wide form: %u pairs on %u slabs of %zu bytes\n", pairs, G, slab);
+	}
+	std::vector<uint64_t> rbs(S);
+	for (size_t i = 0; i < S; ++i) rbs[i] = c->segments[i].rb;
+	hipError_t e = hipMemcpyAsync(d_rb, rbs.data(), S * 8, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, S * X * 4, st);
+	if (e == hipSuccess) e = allow_lds(k_bip_texts_wide, lds_texts);
+	if (e == hipSuccess) e = allow_lds(k_bip_match_wide, lds_match);
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "bipartite join preparation", e);
+	hipLaunchKernelGGL(k_join_classes_wide, dim3((uint32_t) S), dim3(JW_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count, d_start);
+	hipLaunchKernelGGL(k_bip_minrow_wide, dim3((uint32_t) S), dim3(JBW_T), 0, st, d_of, (uint32_t) m, X, d_min);
+	hipLaunchKernelGGL(k_bip_texts_wide, dim3((uint32_t) S), dim3(JBW_T), lds_texts, st, d_count, d_size, d_min, (uint32_t) m, X, d_tpos, d_src, d_reprow);
+	if (pairs)
+		hipLaunchKernelGGL(k_bip_match_wide, dim3(G), dim3(JBW_T), lds_match, st, d_of, d_count, d_tpos, d_src, (uint32_t) m, X, pairs, d_slabs, d_match);
+	hipLaunchKernelGGL(k_bip_chain_wide, dim3((X + JBW_T - 1) / JBW_T), dim3(JBW_T), 0, st, d_match, d_reprow, (uint32_t) S, X, d_perm);
+	std::vector<uint32_t> count(S);
+	e = hipMemcpyAsync(count.data(), d_count, S * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(permutations, d_perm, S * X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "bipartite join", e);
+	for (size_t i = 0; i < S; ++i)
+		if (count[i] < 1 || count[i] > X) return FSEQ_OK;         // (implausible class tables: the host joiner builds its own)
+	double const t1 = now_ms();
+	c->jp = fseq_join_profile{0.0, 0.0, 0.0, t1 - t0, t1 - t0, (uint64_t) S * X * 4ull + (uint64_t) S * 4ull};
 	*done = true;
 	return FSEQ_OK;
 }
@@ -209,6 +284,14 @@ static int fetch_boundary_states(fseq_ctx *c, std::vector<uint32_t> &A, std::vec
 	return FSEQ_OK;
 }
 
+int fseq_debug_bipartite_path(fseq_ctx *c, int *path)
+{
+	if (!c || !path) return FSEQ_E_ARG;
+	if (c->bip_path < 0) return fail(c, FSEQ_E_ARG, "no fseq_join_bipartite has finished on this context since its input was set");
+	*path = c->bip_path;
+	return FSEQ_OK;
+}
+
 int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 {
 	if (!c || !permutations) return FSEQ_E_ARG;
@@ -220,7 +303,18 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 	// falls through to the host joiner when the tables do not fit a workgroup's LDS or cannot be allocated
 	bool tiled = true;                                           // (lb of a segment = rb of the one in front: what k_join_classes goes by)
 	for (size_t i = 0; tiled && i < S; ++i) tiled = c->segments[i].lb == (i ? c->segments[i - 1].rb : 0u);
-	while (tiled && !c->sh.on && X >= 1 && X <= JP_MAX_CLASSES && m <= 0xFFFFFFFFull && S <= 0xFFFFFFFFull && !c->tune.join_host)
+	bool const device = tiled && !c->sh.on && X >= 1 && m <= 0xFFFFFFFFull && S <= 0xFFFFFFFFull && !c->tune.join_host;
+	// The wide form (fseq_joinbipw.hpp): forced (FSEQ_JOIN_BIP_WIDE) at any X up to its cap; by itself above the LDS form's
+	// limit, from JOIN_BIP_WIDE_MIN_BYTES of boundary states on.  Falls through to the host joiner as the LDS form does.
+	bool const wide = device && X <= JBW_MAX_TEXTS &&
+	                  (c->tune.join_bip_wide || (X > JP_MAX_CLASSES && (uint64_t) S * m * 8ull >= JOIN_BIP_WIDE_MIN_BYTES));
+	if (wide)
+	{
+		bool done = false;
+		if (int const rc = join_bipartite_wide(c, permutations, &done)) return rc;
+		if (done) { c->bip_path = 2; return FSEQ_OK; }
+	}
+	while (device && !wide && X <= JP_MAX_CLASSES)
 	{
 		(void) hipSetDevice(c->p.device);
 		double const t0 = now_ms();
@@ -261,6 +355,7 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 		if (!sane) break;                                         // (implausible class tables: the host joiner builds its own)
 		double const t1 = now_ms();
 		c->jp = fseq_join_profile{0.0, 0.0, 0.0, t1 - t0, t1 - t0, (uint64_t) S * X * 4ull + (uint64_t) S * 4ull};
+		c->bip_path = 1;
 		return FSEQ_OK;
 	}
 	std::vector<uint32_t> A, D;
@@ -270,6 +365,7 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 	double const t0 = now_ms();
 	bipartite_match(c->p.m, c->res.max_segment_size, segs, A.data(), D.data(), permutations);
 	c->jp.ms_draw = now_ms() - t0; c->jp.ms_total = c->jp.ms_d2h + c->jp.ms_draw;
+	c->bip_path = 0;
 	return FSEQ_OK;
 }
 

@@ -269,8 +269,15 @@ int  fseq_greedy_match_host(uint32_t m, uint32_t max_segment_size, uint64_t n_se
  * Kuhn-Munkres: every matching has the optimal total weight; which optimal matching Lemon picks is
  * not reproduced (parity unpinned).  Texts of equal size keep their classes' pBWT order
  * (the reference's std::sort leaves it to its standard library).  [r5] fseq_join_bipartite runs on the
- * device where the boundary states are (csrc/fseq_joinbip.hpp) while a segment has at most 181 texts and
- * the run is not sharded -- the same permutations, entry for entry, as the host form below. */
+ * device where the boundary states are while the run is not sharded and the merged segments tile the columns -- the same
+ * permutations, entry for entry, as the host form below.  Up to 181 texts a segment a pair's weight matrix and its
+ * Kuhn-Munkres state are one workgroup's LDS (csrc/fseq_joinbip.hpp).  Above that and up to 4,096 texts, from 16 MiB of
+ * boundary states (segments x m x 8 bytes) on, the wide form runs (csrc/fseq_joinbipw.hpp): the weights of a pair in a slab
+ * of max_segment_size^2 words of device memory, one slab per persistent workgroup, which solves its pairs one after the
+ * other with 64-bit potentials in LDS; as many slabs as the pairs, the CUs, half of the free device memory and of what is left
+ * of fseq_set_memory_budget allow.  Everything else goes through the host joiner, which copies every boundary state to the
+ * host: more than 4,096 texts, smaller inputs above 181 texts, a failed device allocation (not one slab fits), implausible
+ * class counts (a sharded run is refused there, as before).  fseq_debug_bipartite_path (fseq_debug.h) tells which ran. */
 int  fseq_join_bipartite(fseq_ctx *ctx, uint32_t *permutations);
 /* replaces: join_context::join_random_order_and_output (join_context.cc:259-289): std::mt19937(seed),
  * one std::shuffle per segment. */

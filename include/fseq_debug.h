@@ -62,6 +62,12 @@ int  fseq_debug_set_tuning(fseq_ctx *ctx, char const *name, char const *value);
  * FSEQ_E_ARG before any fseq_join_greedy has finished. */
 int  fseq_debug_join_path(fseq_ctx *ctx, int *path);
 
+/* Which way the last fseq_join_bipartite of the context went (*path): 0 the host joiner, 1 the device form with the pair's
+ * weights in LDS (up to 181 texts a segment), 2 the wide device form (weights in slabs of device memory, up to 4,096 texts;
+ * FSEQ_JOIN_BIP_WIDE forces it at any count up to that, FSEQ_JOIN_BIP_SLABS caps its slabs = persistent workgroups).
+ * FSEQ_E_ARG before any fseq_join_bipartite has finished since the context's input was set: a new input clears it. */
+int  fseq_debug_bipartite_path(fseq_ctx *ctx, int *path);
+
 /* Device memory the context holds through its own buffers now (*now) and the most it has held since it was made or since the
  * last call with reset_peak != 0 (*peak; the reset happens after the report, to the bytes held now).  Accounting of the
  * context's allocations, not a measurement of the device: borrowed columns and the runtime's own memory are not in it. */
