@@ -102,11 +102,12 @@ EXPORTS = [
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
+    "fseq_debug_pass2_step", "fseq_debug_chain_launch",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns", "fseq_debug_bipartite_path"]
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -214,6 +215,8 @@ def load_library():
     L.fseq_debug_bipartite_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
     L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
+    L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -260,6 +263,74 @@ def debug_rmq(keys, beg, end, device=0):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return a, b
+
+
+P2_STATS = 23          # csrc/fseq_types.hpp: by runs, by sort, copies, the most runs, 19 words of the run counts' histogram
+NOT_WRITTEN = 0xFFFFFFFF
+
+
+def pass2_step(a0, d0, rank, task_blk, cls, headd, ncls, run_cap=P2_RUN_CAP, workgroups=1, device=0):
+    """One launch of pass 2's streamed chain step (k_chain_snap_grouped) on constructed states: a0 / d0 / rank [nblocks][m],
+    task_blk / ncls [ntasks], cls / headd [ntasks][cap].  Returns (snap_a, snap_d) [ntasks][m] (NOT_WRITTEN where the kernel wrote
+    nothing) and the kernel's P2_STATS counters.  FseqError(FSEQ_E_ARG) where an input could take the kernel out of bounds."""
+    L = load_library()
+    a0 = np.ascontiguousarray(np.atleast_2d(a0), dtype=np.uint32)
+    d0 = np.ascontiguousarray(np.atleast_2d(d0), dtype=np.uint32)
+    rank = np.ascontiguousarray(np.atleast_2d(rank), dtype=np.uint32)
+    task_blk = np.ascontiguousarray(task_blk, dtype=np.uint32)
+    ncls = np.ascontiguousarray(ncls, dtype=np.uint32)
+    cls = np.ascontiguousarray(np.atleast_2d(cls), dtype=np.uint32)
+    headd = np.ascontiguousarray(np.atleast_2d(headd), dtype=np.uint32)
+    nblocks, m = a0.shape
+    ntasks, cap = cls.shape
+    if d0.shape != a0.shape or rank.shape != a0.shape or headd.shape != cls.shape or task_blk.shape != (ntasks,) or ncls.shape != (ntasks,):
+        raise FseqError(FSEQ_E_ARG, "pass2_step: shapes disagree")
+    snap_a = np.zeros((ntasks, m), dtype=np.uint32)
+    snap_d = np.zeros((ntasks, m), dtype=np.uint32)
+    stats = np.zeros(P2_STATS, dtype=np.uint32)
+    rc = L.fseq_debug_pass2_step(device, m, nblocks, a0.ctypes.data, d0.ctypes.data, rank.ctypes.data, cap, ntasks, task_blk.ctypes.data, cls.ctypes.data,
+                                 headd.ctypes.data, ncls.ctypes.data, run_cap, workgroups, snap_a.ctypes.data, snap_d.ctypes.data, stats.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return snap_a, snap_d, stats
+
+
+def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0):
+    """One chain launch of phase B on streamed rows (k_cm_*) on constructed key blocks rank / keyd [nb_total][m], nkeys[nb_total]:
+    the chains first_chain .. first_chain + chains - 1 (default: all behind first_chain) of G blocks, from start_a / start_d
+    [chains][m] (None: the identity).  Returns a dict with state_a / state_d [nb_total + 1][m] where states, rank / keyd
+    [chains][m] and nkeys [chains] where keys; NOT_WRITTEN where the launch wrote nothing."""
+    L = load_library()
+    rank = np.ascontiguousarray(np.atleast_2d(rank), dtype=np.uint32)
+    keyd = np.ascontiguousarray(np.atleast_2d(keyd), dtype=np.uint32)
+    nkeys = np.ascontiguousarray(nkeys, dtype=np.uint32)
+    nb_total, m = rank.shape
+    if keyd.shape != rank.shape or nkeys.shape != (nb_total,):
+        raise FseqError(FSEQ_E_ARG, "chain_launch: shapes disagree")
+    if chains is None:
+        chains = max(0, (nb_total + G - 1) // G - first_chain) if G else 0
+    if (start_a is None) != (start_d is None):
+        raise FseqError(FSEQ_E_ARG, "chain_launch: start_a and start_d go together")
+    if start_a is not None:
+        start_a = np.ascontiguousarray(np.atleast_2d(start_a), dtype=np.uint32)
+        start_d = np.ascontiguousarray(np.atleast_2d(start_d), dtype=np.uint32)
+        if start_a.shape != (chains, m) or start_d.shape != (chains, m):
+            raise FseqError(FSEQ_E_ARG, "chain_launch: start states are [chains][m]")
+    out = {}
+    if states:
+        out["state_a"] = np.zeros((nb_total + 1, m), dtype=np.uint32)
+        out["state_d"] = np.zeros((nb_total + 1, m), dtype=np.uint32)
+    if keys:
+        out["rank"] = np.zeros((chains, m), dtype=np.uint32)
+        out["keyd"] = np.zeros((chains, m), dtype=np.uint32)
+        out["nkeys"] = np.zeros(chains, dtype=np.uint32)
+    ptr = lambda name: out[name].ctypes.data if name in out else None
+    rc = L.fseq_debug_chain_launch(device, m, nb_total, G, cols_per_block, rank.ctypes.data, keyd.ctypes.data, nkeys.ctypes.data, first_chain, chains,
+                                   None if start_a is None else start_a.ctypes.data, None if start_a is None else start_d.ctypes.data,
+                                   ptr("state_a"), ptr("state_d"), ptr("rank"), ptr("keyd"), ptr("nkeys"))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return out
 
 
 class RowShard(C.Structure):

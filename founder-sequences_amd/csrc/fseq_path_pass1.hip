@@ -2,7 +2,8 @@
 // boundary states), the list capacity, phase C's launchers: on the blocks' representatives (the plan of an attempt) or on all
 // rows.  The attempt that queues them is csrc/fseq_path_attempt.hip.  The one unit that instantiates k_colblock_stream<> and
 // k_columns_stream<> and that includes fseq_chainsort.hpp: pass 2 replays columns and takes its streamed chain steps through
-// the launchers here.
+// the launchers here -- and so do the two debug entries at the end, which run those steps' kernels on constructed states
+// (fseq_debug_pass2_step, fseq_debug_chain_launch, include/fseq_debug.h: the kernels of a header are one unit's).
 // (The units of the path and what crosses them: fseq_path.hpp.)
 #include "fseq_path.hpp"
 #include "fseq_kernels.hpp"
@@ -74,37 +75,45 @@ void launch_replay_stream(fseq_ctx *c, size_t groups, SnapArgs const &tasks)
 
 namespace {
 
+// one chain launch on streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp), every sweep of a
+// step a launch over (parts) x (chains): a chain of G blocks is G rounds of them.  A is complete but for the step, the pass and
+// the chain count: the rows (m), the workspace of `grid` chains (ws) and their histograms (hist) are the caller's
+// (phase B: launch_chain; tests: fseq_debug_chain_launch)
+void launch_chain_stream(hipStream_t st, uint32_t grid, ChainMultiArgs A)
+{
+	uint32_t const m = A.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
+	A.step = 0; A.pass = 0;
+	A.nchains = grid;
+	uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
+	dim3 const by_row((m + CM_WG - 1u) / CM_WG, grid_y), by_part((nparts + CM_WG / WAVE - 1u) / (CM_WG / WAVE), grid_y);
+	hipLaunchKernelGGL(k_cm_init, by_row, dim3(CM_WG), 0, st, A);
+	for (uint32_t s_ = 0; s_ < A.G; ++s_)
+	{
+		A.step = s_;
+		for (uint32_t ps = 0; ps < npass; ++ps)
+		{
+			A.pass = ps;
+			hipLaunchKernelGGL(k_cm_count, by_part, dim3(CM_WG), 0, st, A);
+			hipLaunchKernelGGL(k_cm_offsets, dim3(grid), dim3(ST), 0, st, A);
+			hipLaunchKernelGGL(k_cm_scatter, by_part, dim3(CM_WG), 0, st, A);
+		}
+		hipLaunchKernelGGL(k_cm_output, by_row, dim3(CM_WG), 0, st, A);
+	}
+	if (A.out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), st, A, A.G);
+}
+
 // one chain launch of phase B (A: the level's key blocks, the start states, what comes out -- ChainMultiArgs); the launch
 // adds the rows and, streamed rows, its workspace
 void launch_chain(fseq_ctx *c, uint32_t grid, ChainMultiArgs A)
 {
 	if (!grid) return;
 	A.m = c->p.m;
-	// streamed rows: a chain step as a radix sort by rank + range maxima (fseq_chainsort.hpp), every sweep of a step a launch
-	// over (parts) x (chains): a chain of G blocks is G rounds of them.  ensure_work_buffers sized d_ws and d_cshist for the
-	// widest launch of phase B (a chain per chain_fan blocks, plus one, in d_cshist; chainsort_ws_words(m)
-	// <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
+	// streamed rows: ensure_work_buffers sized d_ws and d_cshist for the widest launch of phase B (a chain per chain_fan blocks,
+	// plus one, in d_cshist; chainsort_ws_words(m) <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
 	if (c->use_stream)
 	{
-		uint32_t const m = A.m, nparts = chainmulti_parts(m), npass = chainmulti_passes(m);
-		A.ws = c->d_ws.base; A.hist = c->d_cshist; A.step = 0; A.pass = 0;
-		A.nchains = grid;
-		uint32_t const grid_y = (grid + 7u) & ~7u;       // (cm_wg: the workgroups of a chain on one XCD)
-		dim3 const by_row((m + CM_WG - 1u) / CM_WG, grid_y), by_part((nparts + CM_WG / WAVE - 1u) / (CM_WG / WAVE), grid_y);
-		hipLaunchKernelGGL(k_cm_init, by_row, dim3(CM_WG), 0, c->stream, A);
-		for (uint32_t s_ = 0; s_ < A.G; ++s_)
-		{
-			A.step = s_;
-			for (uint32_t ps = 0; ps < npass; ++ps)
-			{
-				A.pass = ps;
-				hipLaunchKernelGGL(k_cm_count, by_part, dim3(CM_WG), 0, c->stream, A);
-				hipLaunchKernelGGL(k_cm_offsets, dim3(grid), dim3(ST), 0, c->stream, A);
-				hipLaunchKernelGGL(k_cm_scatter, by_part, dim3(CM_WG), 0, c->stream, A);
-			}
-			hipLaunchKernelGGL(k_cm_output, by_row, dim3(CM_WG), 0, c->stream, A);
-		}
-		if (A.out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), c->stream, A, A.G);
+		A.ws = c->d_ws.base; A.hist = c->d_cshist;
+		launch_chain_stream(c->stream, grid, A);
 	}
 	else
 		c->ks.chain(c->stream, grid, c->ks.lds_chain, A, scan_keyed(c));
@@ -875,3 +884,170 @@ void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list)
 }
 
 } // namespace fseq
+
+using namespace fseq;
+
+namespace {
+
+// the device buffers of one debug call: freed when the call returns, whichever way
+struct DebugBuffers {
+	std::vector<void *> held;
+	~DebugBuffers() { for (void *p : held) (void) hipFree(p); }
+	// `words` device words, every byte `fill` (0 or 0xFF); nullptr where the allocation or the fill fails
+	uint32_t *words(size_t words, int fill)
+	{
+		void *p = nullptr;
+		if (hipMalloc(&p, std::max<size_t>(1, words) * 4) != hipSuccess) return nullptr;
+		held.push_back(p);
+		if (hipMemset(p, fill, std::max<size_t>(1, words) * 4) != hipSuccess) return nullptr;
+		return static_cast<uint32_t *>(p);
+	}
+	uint32_t *copy(uint32_t const *src, size_t n, size_t at = 0, size_t total = 0)
+	{
+		uint32_t *p = words(std::max(total, at + n), 0);
+		if (p && n && hipMemcpy(p + at, src, n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+		return p;
+	}
+};
+
+constexpr uint32_t DEBUG_M_MIN = 11265, DEBUG_M_MAX = 589824;      // streamed rows: more than the LDS kernels hold, up to what the build accepts
+
+// count rows of m words, every one a permutation of 0 .. m - 1
+bool rows_are_permutations(uint32_t const *a, size_t count, uint32_t m)
+{
+	std::vector<uint8_t> seen(m);
+	for (size_t b = 0; b < count; ++b)
+	{
+		std::fill(seen.begin(), seen.end(), 0);
+		for (uint32_t i = 0; i < m; ++i)
+		{
+			uint32_t const v = a[b * m + i];
+			if (v >= m || seen[v]) return false;
+			seen[v] = 1;
+		}
+	}
+	return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int fseq_debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                          uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                          uint32_t run_cap, uint32_t workgroups, uint32_t *snap_a, uint32_t *snap_d, uint32_t *stats)
+{
+	// ---- everything an index is formed from, before the first HIP call
+	if (!a0 || !d0 || !rank || !task_blk || !cls || !headd || !ncls || !snap_a || !snap_d || !stats) return FSEQ_E_ARG;
+	if (m < DEBUG_M_MIN || m > DEBUG_M_MAX || !nblocks || nblocks > 4096u || !ntasks || ntasks > 4096u) return FSEQ_E_ARG;
+	if (!cap || cap > P2_CLS_CAP || run_cap > P2_RUN_CAP || !workgroups || workgroups > 1024u) return FSEQ_E_ARG;
+	if (!rows_are_permutations(a0, nblocks, m)) return FSEQ_E_ARG;
+	for (size_t i = 0; i < (size_t) nblocks * m; ++i)
+		if (rank[i] >= cap) return FSEQ_E_ARG;
+	// the groups: consecutive tasks of one block (a block's tasks lie together: it forms one group)
+	std::vector<uint2> groups;
+	{
+		std::vector<uint8_t> block_seen(nblocks);
+		for (uint32_t t = 0; t < ntasks; ++t)
+		{
+			if (task_blk[t] >= nblocks) return FSEQ_E_ARG;
+			if (t && task_blk[t] == task_blk[t - 1]) { ++groups.back().y; continue; }
+			if (block_seen[task_blk[t]]) return FSEQ_E_ARG;
+			block_seen[task_blk[t]] = 1;
+			groups.push_back(make_uint2(t, 1u));
+		}
+	}
+	for (uint32_t t = 0; t < ntasks; ++t)
+	{
+		uint32_t const D = ncls[t];
+		if (D == 0u || D == 0xFFFFFFFFu) continue;
+		if (D > cap) return FSEQ_E_ARG;
+		// (the kernel loads all cap entries of the class table into LDS and looks any of them up)
+		for (uint32_t j = 0; j < cap; ++j)
+			if (cls[(size_t) t * cap + j] >= D) return FSEQ_E_ARG;
+	}
+	// largest first, the counter behind them (long_pass2_reduced)
+	std::stable_sort(groups.begin(), groups.end(), [](uint2 x, uint2 y) { return x.y > y.y; });
+	uint32_t const ngrp = (uint32_t) groups.size();
+	std::vector<uint32_t> grp_words(2 * (size_t) ngrp + 1, 0u);
+	for (uint32_t g = 0; g < ngrp; ++g) { grp_words[2 * g] = groups[g].x; grp_words[2 * g + 1] = groups[g].y; }
+
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	DebugBuffers B;
+	size_t const states = (size_t) nblocks * m, outs = (size_t) ntasks * m, tables = (size_t) ntasks * cap;
+	uint32_t *d_a0 = B.copy(a0, states), *d_d0 = B.copy(d0, states), *d_rank = B.copy(rank, states);
+	uint32_t *d_blk = B.copy(task_blk, ntasks), *d_cls = B.copy(cls, tables), *d_headd = B.copy(headd, tables), *d_ncls = B.copy(ncls, ntasks);
+	uint32_t *d_grp = B.copy(grp_words.data(), grp_words.size());
+	uint32_t *d_sa = B.words(outs, 0xFF), *d_sd = B.words(outs, 0xFF), *d_stats = B.words(P2_STATS, 0);
+	uint32_t *d_ws = B.words((size_t) workgroups * pass2_ws_words(m), 0);
+	if (!d_a0 || !d_d0 || !d_rank || !d_blk || !d_cls || !d_headd || !d_ncls || !d_grp || !d_sa || !d_sd || !d_stats || !d_ws) return FSEQ_E_OOM;
+	if (allow_lds(k_chain_snap_grouped, pass2_lds_bytes()) != hipSuccess) return FSEQ_E_HIP;
+	hipLaunchKernelGGL(k_chain_snap_grouped, dim3(workgroups), dim3(ST), pass2_lds_bytes(), 0, d_a0, d_d0, d_rank, m, d_blk, d_cls, d_headd, d_ncls, cap,
+	                   reinterpret_cast<uint2 const *>(d_grp), ngrp, d_grp + 2 * (size_t) ngrp, d_sa, d_sd, d_ws, run_cap, d_stats);
+	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
+	if (hipMemcpy(snap_a, d_sa, outs * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(snap_d, d_sd, outs * 4, hipMemcpyDeviceToHost) != hipSuccess
+	    || hipMemcpy(stats, d_stats, P2_STATS * 4, hipMemcpyDeviceToHost) != hipSuccess)
+		return FSEQ_E_HIP;
+	return FSEQ_OK;
+}
+
+int fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
+                            uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
+                            uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys)
+{
+	// ---- everything an index is formed from, before the first HIP call
+	bool const want_states = out_state_a != nullptr, want_keys = out_rank != nullptr;
+	if (!rank || !keyd || !nkeys || (!want_states && !want_keys)) return FSEQ_E_ARG;
+	if (want_states != (out_state_d != nullptr) || want_keys != (out_keyd != nullptr) || want_keys != (out_nkeys != nullptr)) return FSEQ_E_ARG;
+	if ((start_a != nullptr) != (start_d != nullptr)) return FSEQ_E_ARG;
+	if (m < DEBUG_M_MIN || m > DEBUG_M_MAX || !nb_total || nb_total > 4096u) return FSEQ_E_ARG;
+	if (!G || G > nb_total) return FSEQ_E_ARG;                            // (a chain of more steps than blocks only queues idle launches)
+	uint32_t const nchains_all = (nb_total + G - 1u) / G;
+	if (!chains || first_chain >= nchains_all || chains > nchains_all - first_chain) return FSEQ_E_ARG;
+	for (uint32_t b = 0; b < nb_total; ++b)
+	{
+		if (!nkeys[b] || nkeys[b] > m) return FSEQ_E_ARG;
+		for (uint32_t i = 0; i < m; ++i)
+			if (rank[(size_t) b * m + i] >= nkeys[b]) return FSEQ_E_ARG;
+	}
+	if (start_a && !rows_are_permutations(start_a, chains, m)) return FSEQ_E_ARG;
+
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	DebugBuffers B;
+	// (the kernels index start states and composite key blocks by the chain's number in the level, first_chain + its number in the launch)
+	size_t const blocks = (size_t) nb_total * m, per_chain = (size_t) (first_chain + chains) * m, at = (size_t) first_chain * m;
+	ChainMultiArgs A{};
+	A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block; A.grp0 = first_chain;
+	A.rank = B.copy(rank, blocks); A.keyd = B.copy(keyd, blocks); A.nkeys = B.copy(nkeys, nb_total);
+	A.ws = B.words((size_t) chains * chainsort_ws_words(m), 0);
+	A.hist = B.words((size_t) chains * chainmulti_parts(m) * CS_BINS, 0);
+	if (!A.rank || !A.keyd || !A.nkeys || !A.ws || !A.hist) return FSEQ_E_OOM;
+	if (start_a)
+	{
+		A.start_a = B.copy(start_a, (size_t) chains * m, at); A.start_d = B.copy(start_d, (size_t) chains * m, at);
+		if (!A.start_a || !A.start_d) return FSEQ_E_OOM;
+	}
+	if (want_states)
+	{
+		A.out_state_a = B.words(blocks + m, 0xFF); A.out_state_d = B.words(blocks + m, 0xFF);
+		if (!A.out_state_a || !A.out_state_d) return FSEQ_E_OOM;
+	}
+	if (want_keys)
+	{
+		A.out_rank = B.words(per_chain, 0xFF); A.out_keyd = B.words(per_chain, 0xFF); A.out_nkeys = B.words(first_chain + chains, 0xFF);
+		if (!A.out_rank || !A.out_keyd || !A.out_nkeys) return FSEQ_E_OOM;
+		if (allow_lds(k_cm_emit, stream_lds_bytes(0, false)) != hipSuccess) return FSEQ_E_HIP;
+	}
+	launch_chain_stream(0, chains, A);
+	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
+	if (want_states && (hipMemcpy(out_state_a, A.out_state_a, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                    || hipMemcpy(out_state_d, A.out_state_d, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
+	if (want_keys && (hipMemcpy(out_rank, A.out_rank + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                  || hipMemcpy(out_keyd, A.out_keyd + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                  || hipMemcpy(out_nkeys, A.out_nkeys + first_chain, (size_t) chains * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
+	return FSEQ_OK;
+}
+
+} // extern "C"

@@ -96,6 +96,36 @@ int  fseq_debug_pass2_paths(fseq_ctx *ctx, uint32_t *by_runs, uint32_t *by_sort,
 int  fseq_debug_class_columns(fseq_ctx *ctx, uint32_t *from_classes, uint32_t *from_alignment, uint32_t block, uint32_t *have, uint32_t *nkeys,
                               uint64_t *ldc, uint8_t *out, uint64_t out_bytes);
 
+/* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
+ * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
+ * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
+ * the divergence in front of a class headd[t][class] (cls / headd [ntasks][cap]), ncls[t] classes: 0 is a border copy, 0xFFFFFFFF a
+ * task the kernel leaves alone.  The tasks of a block are consecutive and form one group; the groups go to the kernel largest
+ * first, taken from a counter by `workgroups` workgroups.  run_cap: the most runs of equal class a task may form and still be moved
+ * by runs (0: every task sorts its rows).  Out: snap_a / snap_d [ntasks][m] (0xFFFFFFFF where the kernel wrote nothing) and the
+ * kernel's counters, stats[23]: tasks by runs, tasks by sort, copies, the most runs, 19 words of runs_hist (fseq_debug_pass2_paths).
+ * Everything an index is formed from is checked on the host before the first call of the runtime, FSEQ_E_ARG otherwise:
+ * 11,265 <= m <= 589,824; every a0 a permutation of 0 .. m - 1; rank < cap <= 11,264; task_blk < nblocks, a block's tasks
+ * together; ncls <= cap and all cap entries of such a task's cls below its ncls; run_cap <= 8,832; 1 <= workgroups <= 1,024;
+ * at most 4,096 blocks and tasks. */
+int  fseq_debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                           uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                           uint32_t run_cap, uint32_t workgroups, uint32_t *snap_a, uint32_t *snap_d, uint32_t *stats);
+
+/* One chain launch of phase B on streamed rows (k_cm_*, csrc/fseq_chainsort.hpp, through the launcher phase B itself uses) on
+ * caller-supplied key blocks (debug / tests; needs no context): the level's key blocks rank[nb_total][m], keyd[nb_total][m],
+ * nkeys[nb_total], cols_per_block columns each; the chains first_chain .. first_chain + chains - 1 of G blocks each, from
+ * start_a / start_d [chains][m] (both NULL: the identity, every divergence the chain's first column).  Out, either or both:
+ * the states in front of every block and behind the last, out_state_a / out_state_d [nb_total + 1][m] (0xFFFFFFFF where the
+ * launch wrote nothing; without composite keys a chain does not step through its last block unless that is the last of all),
+ * and the chains' composite key blocks out_rank / out_keyd [chains][m], out_nkeys[chains] (out_keyd: 0xFFFFFFFF behind the keys).
+ * Checked on the host before the first call of the runtime, FSEQ_E_ARG otherwise: 11,265 <= m <= 589,824; 1 <= nkeys[b] <= m and
+ * rank[b][row] < nkeys[b]; 1 <= G <= nb_total <= 4,096; the chains inside ceil(nb_total / G); every start_a a permutation of
+ * 0 .. m - 1; start_a and start_d, and the outputs of a kind, together. */
+int  fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
+                             uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
+                             uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys);
+
 #ifdef __cplusplus
 }
 #endif
