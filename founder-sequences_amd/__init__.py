@@ -102,12 +102,12 @@ EXPORTS = [
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
-    "fseq_debug_pass2_step", "fseq_debug_chain_launch",
+    "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch"]
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -217,6 +217,7 @@ def load_library():
     L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
     L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+    L.fseq_debug_red_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.c_int] + [vp] * 11
     _lib = L
     return L
 
@@ -330,6 +331,50 @@ def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=Non
                                    ptr("state_a"), ptr("state_d"), ptr("rank"), ptr("keyd"), ptr("nkeys"))
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return out
+
+
+RED_NONE = 0xFFFFFFFF                       # csrc/fseq_redplan.hpp: a block that is not reduced
+RED_FORCE_FULL, RED_FORCE_WIDE = 1, 2       # ... the force marks
+RED_USE, RED_DECLINED, RED_NO_BLOCK_LIST = 0, 1, 2      # ... RedVerdict
+RED_CONFIGS_MAX = 64                        # include/fseq_debug.h, FSEQ_DEBUG_RED_CONFIGS
+
+
+def red_plan_host(m, B, bits, direct, cnt, force=None, b_lo=0, b_hi=None, reduced_always=False, no_block_list=False):
+    """The plan of phase C on representative rows (plan_reduced, csrc/fseq_redplan.hpp) for the counts cnt[nblocks] (RED_NONE: not
+    reduced) and the force marks force[nblocks], as a run of m rows in blocks of B columns at `bits` bits a symbol would make it
+    (direct: LDS-resident rows).  No device is touched.  Returns a dict: verdict, full / config_of / config_snap_of [nblocks],
+    blocks (the list that goes to the device), bins [(configuration, first, count)], full_at, nfull, listed, max_rows,
+    reduced_blocks, rows_mean, and configs, the library's configurations as [(rows, values, T, E, ew, fits)].
+    FseqError(FSEQ_E_ARG) where an argument could take an index out of bounds."""
+    L = load_library()
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    if cnt.ndim != 1:
+        raise FseqError(FSEQ_E_ARG, "red_plan_host: cnt is one count per block")
+    nb = len(cnt)
+    if force is not None:
+        force = np.ascontiguousarray(force, dtype=np.uint8)
+        if force.shape != cnt.shape:
+            raise FseqError(FSEQ_E_ARG, "red_plan_host: one force mark per block")
+    configs = np.zeros((RED_CONFIGS_MAX, 6), dtype=np.uint32)
+    full = np.zeros(nb, dtype=np.uint8)
+    config_of = np.zeros(nb, dtype=np.int32)
+    config_snap_of = np.zeros(nb, dtype=np.int32)
+    blocks = np.zeros(3 * nb, dtype=np.uint32)
+    bins = np.zeros((RED_CONFIGS_MAX, 3), dtype=np.uint32)
+    summary = np.zeros(6, dtype=np.uint32)
+    n_configs, n_blocks, n_bins, verdict = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int()
+    rc = L.fseq_debug_red_plan(m, B, bits, int(bool(direct)), nb, b_lo, nb if b_hi is None else b_hi, cnt.ctypes.data,
+                               None if force is None else force.ctypes.data, int(bool(reduced_always)), int(bool(no_block_list)),
+                               configs.ctypes.data, C.addressof(n_configs), C.addressof(verdict), full.ctypes.data, config_of.ctypes.data,
+                               config_snap_of.ctypes.data, blocks.ctypes.data, C.addressof(n_blocks), bins.ctypes.data, C.addressof(n_bins),
+                               summary.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    out = dict(zip(("full_at", "nfull", "listed", "max_rows", "reduced_blocks", "rows_mean"), (int(x) for x in summary)))
+    out.update(verdict=verdict.value, full=full, config_of=config_of, config_snap_of=config_snap_of, blocks=blocks[:n_blocks.value],
+               bins=[tuple(int(x) for x in row) for row in bins[:n_bins.value]],
+               configs=[(int(r), int(v), int(T), int(E), bool(ew), bool(fits)) for r, v, T, E, ew, fits in configs[:n_configs.value]])
     return out
 
 

@@ -12,6 +12,7 @@ SRCS = [os.path.join(HERE, "csrc", name) for name in (
     "fseq_path_setup.hip",
     "fseq_path_dp.hip",
     "fseq_path_pass1.hip",
+    "fseq_path_reduced.hip",
     "fseq_path_attempt.hip",
     "fseq_path_pass2.hip",
     "fseq_api_join.hip",

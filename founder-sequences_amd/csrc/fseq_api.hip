@@ -6,7 +6,7 @@
 // There is deliberately NO CPU fallback for the column work: if the device or a kernel shape is
 // unavailable the call fails with an error code.
 // The context and the helpers every translation unit shares are in fseq_ctx.hpp.  The orchestration behind these entry points
-// is in the path's units (fseq_path.hpp lists them: csrc/fseq_path_setup.hip, _dp, _pass1, _pass2), the debug entry points
+// is in the path's units (fseq_path.hpp lists them: csrc/fseq_path_setup.hip, _dp, _pass1, _reduced, _attempt, _pass2), the debug entry points
 // and the row-sharded sweep in csrc/fseq_api_debug.hip; the host joiners, their device front and the output writers are
 // csrc/fseq_api_join.hip, the matcher csrc/fseq_api_match.hip, the identity columns csrc/fseq_api_identity.hip and the chunked
 // input csrc/fseq_api_input.hip.
@@ -23,7 +23,7 @@ void fseq::forget_run_history(fseq_ctx *c)
 {
 	c->have_result = false;
 	c->kernels_ready = false;
-	c->bk_given_up = -1; c->bt_given_up = -1; c->red_force_full.clear(); c->red_plan_valid = false; c->red_declined = false; c->cls_unread = false;
+	c->bk_given_up = -1; c->bt_given_up = -1; c->red.memory.forget_input();
 }
 
 // ... and an input what was learnt of the input besides
@@ -121,7 +121,7 @@ void fseq_destroy(fseq_ctx *c)
 	if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);
 	if (c->h_red_pin2) (void) hipHostFree(c->h_red_pin2);
 	for (auto &s_ : c->red_st) if (s_) (void) hipStreamDestroy(s_);
-	for (auto &e_ : c->red_ev) if (e_) (void) hipEventDestroy(e_);
+	for (hipEvent_t *e_ : c->red_ev.all()) if (*e_) (void) hipEventDestroy(*e_);
 	if (c->stream2) (void) hipStreamDestroy(c->stream2);
 	if (c->stream) (void) hipStreamDestroy(c->stream);
 	delete c;

@@ -53,9 +53,9 @@ int fseq_debug_class_columns(fseq_ctx *c, uint32_t *from_classes, uint32_t *from
 		if (b_hi > b_lo) HIP_TRY(c, hipMemcpy(flags.data() + b_lo, c->d_cls_have + b_lo, (size_t) (b_hi - b_lo) * 4, hipMemcpyDeviceToHost));
 	}
 	uint32_t n_cls = 0, n_msa = 0;
-	if (c->red_active && !c->red_direct && c->red_cnt_host.size() == c->nblocks)
+	if (c->red_active && !c->red_direct && c->red.plan.cnt.size() == c->nblocks)
 		for (uint32_t b = b_lo; b < b_hi; ++b)
-			if (c->red_cnt_host[b] != RED_NONE) ++(c->cls_read && flags[b] ? n_cls : n_msa);
+			if (c->red.plan.cnt[b] != RED_NONE) ++(c->cls_read && flags[b] ? n_cls : n_msa);
 	if (from_classes) *from_classes = n_cls;
 	if (from_alignment) *from_alignment = n_msa;
 	if (block == UINT32_MAX) return FSEQ_OK;

@@ -1,6 +1,6 @@
 // fseq_ctx.hpp -- the context behind the C ABI (include/fseq.h) and the small helpers every translation unit of the library
 // shares: csrc/fseq_api.hip (the ABI's entry points) and csrc/fseq_api_debug.hip (the debug entry points, the row-sharded sweep),
-// the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _attempt, _pass2: geometry, buffers, phases, sharding; what
+// the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _reduced, _attempt, _pass2: geometry, buffers, phases, sharding; what
 // only they share is csrc/fseq_path.hpp), csrc/fseq_api_join.hip (the host joiners, their device front and the output
 // writers), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
 // and put back) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
@@ -405,12 +405,26 @@ struct fseq_ctx {
 	size_t cls_ld = 0;
 	bool cls_on = false;                     // this run's phase A wrote class columns
 	bool cls_every = false;                  // ... for every block of mine (the trie ran alone: it gave no block up in the run before on this input)
-	bool cls_unread = false;                 // the plan of this input takes a path that reads no reduced alignment: phase A writes no class columns for it
 	bool cls_read = false;                   // this run's reduced alignment took them where a block has them (fseq_debug_class_columns)
-	std::vector<uint32_t> red_cnt_host;      // representatives per block of the last prep (RED_NONE: not reduced)
-	std::vector<uint8_t> red_full;           // blocks this run sends to the kernel on all rows
-	std::vector<uint8_t> red_force_full;     // ... because an earlier run on this input could not prove their lists on the representatives (1); 2: the block
-	                                         // stays reduced but skips the slim configuration, which refused it
+	// the plan of the representatives (fseq_redplan.hpp; red_plan, csrc/fseq_path_reduced.hip): every result of a planning is in
+	// `plan`, everything a run remembers of this input for the next in `memory` (DESIGN.md section 1 has the table of what each
+	// forget_* clears, by the site that calls it)
+	struct Red {
+		fseq::RedPlan plan;                  // of the last planning: read where red_active says this run's phase C went by it
+		struct Memory {
+			std::vector<uint8_t> force;      // [block] RED_FORCE_FULL / RED_FORCE_WIDE marks (RedPlanInput::force); of another input's size: none
+			// `plan` is the plan (which block on which configuration) of the last run on this input at capacity plan_X: the next run
+			// launches by it without waiting for the counts, and checks on the device that they are what the plan was made from
+			bool plan_holds = false;
+			uint32_t plan_X = 0;
+			bool declined = false;           // the last run on this input (at capacity declined_X) found too many representatives: no prep this time
+			uint32_t declined_X = 0;
+			bool cls_unread = false;         // the plan of this input takes a path that reads no reduced alignment: phase A writes no class columns for it
+			void forget_plan() { plan_holds = false; }                                     // the next attempt plans afresh
+			void forget_verdicts() { plan_holds = false; declined = false; cls_unread = false; }      // ... and asks again whether the representatives pay (the buffers are gone)
+			void forget_input() { forget_verdicts(); force.clear(); }                      // ... with no block marked (another input, or another geometry)
+		} memory;
+	} red;
 	bool red_active = false;                 // this run's phase C went through the representatives (pass 2 follows it)
 	DevBuf<uint32_t> d_red_cls, d_red_headd, d_red_ncls, d_red_taskblk, d_red_wgtasks;
 	DevBuf<uint32_t> d_red_p2grp;            // streamed pass 2: its groups {first task, count}, the counter they are taken by and the kernel's counters
@@ -418,24 +432,17 @@ struct fseq_ctx {
 	bool p2_stats_have = false;              // the last run went through that kernel
 	DevBuf<uint32_t> d_red_ss_a, d_red_ss_d; // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
 	uint32_t red_ss_stride = 0, red_ss_cap = 0;
-	uint32_t *h_red_pin = nullptr;           // pinned host staging of the plan (counts back, block lists out): its own buffer, live across the run
+	uint32_t *h_red_pin = nullptr;           // pinned host staging of a planning's two copies (counts back, red.plan.blocks out): nothing reads it afterwards
 	size_t red_pin_words = 0;
-	struct RedBin { int config; uint32_t first, count; };     // blocks [first, first + count) of d_red_blocks run on configuration `config`
-	std::vector<RedBin> red_bins;
-	std::vector<int> red_config_of;          // [block] configuration of a reduced block's phase C (-1: not reduced)
-	std::vector<int> red_config_snap_of;     // ... and of its sweeps in pass 2 (no lists: no list wave)
-	uint32_t red_full_at = 0, red_nfull = 0;     // d_red_blocks[red_full_at .. + red_nfull): the blocks that run on all rows
-	uint32_t red_listed = 0, red_max_rows = 0;   // d_red_blocks[0 .. red_listed): every reduced block; the most representatives among them
 	bool red_direct = false;                 // the representatives' symbols are read from the alignment's own columns (LDS-resident row counts): no reduced alignment
-	// the plan (which block on which configuration) of the last run on this input at capacity red_plan_X: the next run launches
-	// by it without waiting for the counts, and checks on the device that they are what the plan was made from
-	bool red_declined = false;               // the last run on this input (at capacity red_declined_X) found too many representatives: no prep this time
-	uint32_t red_declined_X = 0;
-	bool red_plan_valid = false;
-	uint32_t red_plan_X = 0, red_plan_blocks = 0, red_plan_rows_mean = 0;
-	DevBuf<uint32_t> d_red_cnt_plan;
+	DevBuf<uint32_t> d_red_cnt_plan;         // the counts red.plan was made from (k_reduce_check)
 	hipStream_t red_st[2]{};                 // the configurations' launches side by side: the context's second stream, then these
-	hipEvent_t red_ev[4]{};
+	struct RedEvents {                       // (no timing)
+		hipEvent_t fork = nullptr;           // the context's stream has reached the launches: the side streams wait for it
+		hipEvent_t join_stream2 = nullptr, join_side0 = nullptr, join_side1 = nullptr;     // a side stream's launch is queued: the context's stream waits for it
+		std::array<hipEvent_t *, 3> joins() { return {&join_stream2, &join_side0, &join_side1}; }      // by side stream: stream2, red_st[0], red_st[1]
+		std::array<hipEvent_t *, 4> all() { return {&fork, &join_stream2, &join_side0, &join_side1}; }
+	} red_ev;
 	uint8_t *h_red_pin2 = nullptr;           // pass 2's task lists (pinned)
 	size_t red_pin2_bytes = 0;
 

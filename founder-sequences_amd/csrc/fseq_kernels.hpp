@@ -18,6 +18,7 @@
 #pragma once
 
 #include "fseq_core.hpp"
+#include "fseq_types.hpp"
 
 #include <type_traits>
 
@@ -74,7 +75,7 @@ __device__ __forceinline__ uint32_t synth_pick(uint32_t kind, uint64_t h)
 
 // Alignment storage in HBM: column-major, 8 >> bsh bits per dense symbol code (bsh = 2 when sigma <= 4,
 // 1 when sigma <= 16, else 0); row r of a column sits in byte r >> bsh at bit (r & (2^bsh - 1)) * (8 >> bsh).
-__host__ __device__ inline uint32_t sym_bytes(uint32_t m, uint32_t bsh) { return (m + (1u << bsh) - 1u) >> bsh; }
+// (sym_bytes, the bytes of m rows of a column: fseq_types.hpp, for the host units that include no kernel header)
 
 // 2-bit digit `pass` of the code of row `a` in a (staged) packed column
 __device__ __forceinline__ uint32_t sym_digit(uint8_t const *col, uint32_t a, uint32_t bsh, uint32_t pass)

@@ -5,8 +5,10 @@
 //   csrc/fseq_api_debug.hip   the entry points of include/fseq_debug.h, the row-sharded conformance sweep
 //   csrc/fseq_path_setup.hip  pinned staging, geometry, work buffers, the row upload, the shard exchange
 //   csrc/fseq_path_dp.hip     the DP drivers, the tracebacks, the merge (the one unit that instantiates k_dp<>)
-//   csrc/fseq_path_pass1.hip  phases A and B, the list capacity, the reduced plan, phase C's launchers (the one unit that instantiates
+//   csrc/fseq_path_pass1.hip  phases A and B, the list capacity, phase C's launchers on all rows (the one unit that instantiates
 //                             k_colblock_stream<> / k_columns_stream<> and includes fseq_chainsort.hpp)
+//   csrc/fseq_path_reduced.hip  phase C on representative rows: the stages around the plan (plan_reduced, fseq_redplan.hpp), the
+//                             configurations' launches side by side, the redo marking (instantiates no kernel)
 //   csrc/fseq_path_attempt.hip  one attempt at a list capacity as stages with one verdict, the list windows, the loop over attempts,
 //                             the short path (instantiates no kernel)
 //   csrc/fseq_path_pass2.hip  the boundary states at the merged boundaries
@@ -56,7 +58,6 @@ constexpr uint64_t STREAM_BLOCK_TARGET_ALL_ROWS = 1600;   // columns per block t
 // [r5] ... and when phase C runs on the blocks' representatives: a block of ~800 columns of BASELINE C4 has ~6,600 of them, and
 // the ~10,700 of a block in which the founders recombine still fit the largest configuration (11,264)
 constexpr uint64_t STREAM_BLOCK_TARGET_REDUCED = 800;
-constexpr uint8_t RED_FORCE_FULL = 1, RED_FORCE_WIDE = 2;    // fseq_ctx::red_force_full[b]
 constexpr size_t RED_SIDE_STREAMS = 3;                    // side streams the reduced configurations' launches may use (red_launch_all)
 #define STREAM_BLOCK_TARGET (c->tune.no_reduced ? STREAM_BLOCK_TARGET_ALL_ROWS : STREAM_BLOCK_TARGET_REDUCED)
 #ifndef FSEQ_X_FLOOR_VALUE
@@ -171,19 +172,24 @@ size_t chain_hist_words(uint32_t m);                 // digit histogram words of
 // many per launch as the workspace holds
 void launch_replay_stream(fseq_ctx *c, size_t groups, SnapArgs const &tasks);
 int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats);       // pass 2 behind the reduced phase C, streamed rows: the chain steps
-void red_fill_args(fseq_ctx *c, RedArgs &RA);
-struct RedLaunch { int config; uint32_t first, count; };
-// (base.blocks / base.wg_tasks: the lists the launches' [first, first + count) index; lists: the segment length alone in pass 2)
-int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists);
 int long_phase_a(fseq_ctx *c, LongRun &R);
 int phase_a_take_counts(fseq_ctx *c, LongRun const &R, PhaseACounters counts);    // what an attempt read back of phase A's counters
 int long_phase_b(fseq_ctx *c, LongRun &R);
 int long_list_capacity(fseq_ctx *c, LongRun &R);
 int short_phase_a(fseq_ctx *c, uint32_t *d_rank, uint32_t *d_keyd, uint32_t *d_nkeys);      // the short path's one block [0, n), ranked
-int red_plan(fseq_ctx *c, uint32_t X, bool *use);
-int red_columns(fseq_ctx *c);                         // the lists of the plan's reduced blocks, the largest configurations first
 // phase C on all rows of the blocks b0 .. b0 + nb - 1 (list: workgroup i owns block list[i] -- the blocks the plan hands to all rows)
 void launch_columns(fseq_ctx *c, uint32_t b0, uint32_t nb, uint32_t const *list = nullptr);
+
+// ---- csrc/fseq_path_reduced.hip
+// the plan of an attempt at list capacity X into c->red.plan (*use: phase C goes by it); what later runs need of it into c->red.memory
+int red_plan(fseq_ctx *c, uint32_t X, bool *use);
+int red_columns(fseq_ctx *c);                         // the lists of the plan's reduced blocks, the largest configurations first
+void red_fill_args(fseq_ctx *c, RedArgs &RA);
+struct RedLaunch { int config; uint32_t first, count; };
+// (base.blocks / base.wg_tasks: the lists the launches' [first, first + count) index; lists: the segment length alone in pass 2)
+int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists);
+// the blocks of [b_lo, b_hi) whose lists could not be proven on their representatives get their force marks (*count; *wide: of them, reduced still)
+int red_take_invalid(fseq_ctx *c, uint32_t b_lo, uint32_t b_hi, uint32_t *count, uint32_t *wide);
 
 // ---- csrc/fseq_path_attempt.hip
 void set_list_window(fseq_ctx *c, uint32_t lo_w);

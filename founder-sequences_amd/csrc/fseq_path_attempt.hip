@@ -112,7 +112,8 @@ int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
 		launch_columns(c, lo, hi - lo);
 		return FSEQ_OK;
 	}
-	uint32_t const *const h_blocks = c->h_red_pin + c->nblocks;      // red_plan's host copy of d_red_blocks
+	RedPlan const &plan = c->red.plan;
+	uint32_t const *const h_blocks = plan.blocks.data();             // (what d_red_blocks holds)
 	auto stretch = [&](uint32_t first, uint32_t count) {
 		uint32_t const *const b = h_blocks + first, *const e = b + count;
 		uint32_t const *const a = std::lower_bound(b, e, lo), *const z = std::lower_bound(b, e, hi);
@@ -121,7 +122,7 @@ int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
 	RedArgs RA;
 	red_fill_args(c, RA);
 	std::vector<RedLaunch> ls;
-	for (auto const &bin : c->red_bins)
+	for (auto const &bin : plan.bins)
 	{
 		auto const r = stretch(bin.first, bin.count);
 		if (r.second) ls.push_back(RedLaunch{bin.config, r.first, r.second});
@@ -129,7 +130,7 @@ int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi)
 	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
 	int rc;
 	if ((rc = red_launch_all(c, ls, RA, list_args(c)))) return rc;
-	auto const f = stretch(c->red_full_at, c->red_nfull);
+	auto const f = stretch(plan.full_at, plan.nfull);
 	if (f.second) launch_columns(c, 0, f.second, c->d_red_blocks + f.first);
 	return FSEQ_OK;
 }
@@ -174,20 +175,6 @@ int long_windows_cd(fseq_ctx *c, DpSchedule const &S)
 	if (c->tune.debug)
 		fprintf(stderr, "[fseq] list windows: %u windows of %u blocks (%llu columns) + a halo of %u columns, %.2f GB of lists at X = %u\n", W.nwin, W.wb,
 		        (unsigned long long) W.wb * c->B, W.H, W.bytes / 1e9, c->X);
-	return FSEQ_OK;
-}
-
-// the redo marking: the blocks of [b_lo, b_hi) whose lists the reduced phase C could not vouch for (d_red_invalid) run on all
-// rows -- or, RED_WIDE, on the next configuration -- when the attempt runs again, and the plan goes with them.
-// *count: the blocks marked; *wide: those of them that stay reduced
-int red_take_invalid(fseq_ctx *c, uint32_t b_lo, uint32_t b_hi, uint32_t *count, uint32_t *wide)
-{
-	std::vector<uint32_t> inv(c->nblocks);
-	HIP_TRY(c, hipMemcpy(inv.data(), c->d_red_invalid, (size_t) c->nblocks * 4, hipMemcpyDeviceToHost));
-	*count = *wide = 0;
-	for (uint32_t b = b_lo; b < b_hi; ++b)
-		if (inv[b] && !c->red_full[b]) { c->red_force_full[b] = inv[b] == RED_WIDE ? RED_FORCE_WIDE : RED_FORCE_FULL; ++*count; *wide += inv[b] == RED_WIDE ? 1u : 0u; }
-	if (*count) c->red_plan_valid = false;
 	return FSEQ_OK;
 }
 
@@ -283,7 +270,7 @@ int attempt_phase_c(fseq_ctx *c, LongRun const &R, AttemptState const &A)
 		if ((rc = red_columns(c))) return rc;
 		mark(c, A, "reduced columns queued");
 		// the blocks that run on all rows, in one launch (no stride states: pass 2 reaches their boundaries from the block's start)
-		if (c->red_nfull) launch_columns(c, 0, c->red_nfull, c->d_red_blocks + c->red_full_at);
+		if (c->red.plan.nfull) launch_columns(c, 0, c->red.plan.nfull, c->d_red_blocks + c->red.plan.full_at);
 		if (halo) launch_columns(c, b_hi, 1u);
 	}
 	else if (!sharded)
@@ -314,12 +301,12 @@ int attempt_shard_agreement(fseq_ctx *c, LongRun &R, bool *again)
 	HIP_TRY(c, hipMemcpy(&all, sh.xbuf, 4, hipMemcpyDeviceToHost));
 	*again = all != 0;
 	if (!all) return FSEQ_OK;
-	if (mine.plan_stale) c->red_plan_valid = false;
+	if (mine.plan_stale) c->red.memory.forget_plan();
 	if (mine.unproven)
 	{
 		uint32_t cnt = 0, wide = 0;
 		if ((rc = red_take_invalid(c, b_lo, b_hi, &cnt, &wide))) return rc;
-		c->red_plan_valid = false;
+		c->red.memory.forget_plan();
 		R.redone += cnt;
 	}
 	return FSEQ_OK;
@@ -369,7 +356,7 @@ int attempt_decide(fseq_ctx *c, LongRun &R, AttemptState const &A, bool agreed_a
 	if (c->red_active && h->red.plan_stale)
 	{
 		// (the counts are not what the plan was made from: plan afresh)
-		c->red_plan_valid = false;
+		c->red.memory.forget_plan();
 		*verdict = Attempt::Again;
 	}
 	else if (c->red_active && h->red.unproven)

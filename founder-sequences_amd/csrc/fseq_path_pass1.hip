@@ -1,6 +1,6 @@
 // fseq_path_pass1.hip -- the segmentation path, pass 1: phase A (the key blocks; the short path's one block), phase B (the
-// boundary states), the list capacity, phase C's launchers: on the blocks' representatives (the plan of an attempt) or on all
-// rows.  The attempt that queues them is csrc/fseq_path_attempt.hip.  The one unit that instantiates k_colblock_stream<> and
+// boundary states), the list capacity, phase C's launchers on all rows (on the blocks' representatives: csrc/fseq_path_reduced.hip).
+// The attempt that queues them is csrc/fseq_path_attempt.hip.  The one unit that instantiates k_colblock_stream<> and
 // k_columns_stream<> and that includes fseq_chainsort.hpp: pass 2 replays columns and takes its streamed chain steps through
 // the launchers here -- and so do the two debug entries at the end, which run those steps' kernels on constructed states
 // (fseq_debug_pass2_step, fseq_debug_chain_launch, include/fseq_debug.h: the kernels of a header are one unit's).
@@ -262,7 +262,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 		// The buffer is the largest the reduced path adds (12 T classes a column: 3 KB at 2 bits, 15 GB on BASELINE C4), so it must fit
 		// the context's memory budget and, without one, a quarter of what is free -- the lists and the reduced states are allocated
 		// after it and must not fail for it.  Where it does not fit, or the allocation fails, the alignment is read as before.
-		if (c->use_stream && c->tune.class_columns && !c->tune.no_reduced && n >= 2 * L && !(c->red_declined && !c->tune.reduced_always) && !c->cls_unread)
+		if (c->use_stream && c->tune.class_columns && !c->tune.no_reduced && n >= 2 * L && !(c->red.memory.declined && !c->tune.reduced_always) && !c->red.memory.cls_unread)
 		{
 			size_t const ldc = ((size_t) sym_bytes((uint32_t) BT_PER * bt_T, c->bsh) + 15) & ~size_t(15);
 			uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
@@ -553,297 +553,6 @@ int long_list_capacity(fseq_ctx *c, LongRun &R)
 	if (X >= m) X = m;
 
 	return FSEQ_OK;
-}
-
-namespace {
-
-// bytes of each staged-column buffer of a reduced configuration
-uint32_t red_symcap(fseq_ctx const *c, ReducedSet const &rs, bool direct)
-{
-	uint32_t const bytes = direct ? sym_bytes(c->p.m, c->bsh) : sym_bytes(rs.rows, c->bsh);
-	(void) rs;
-	return (bytes + 1023u) & ~1023u;                           // whole kilobytes: a wave stages sixteen bytes per lane
-}
-
-bool columns_fit_reduced(fseq_ctx const *c, ReducedSet const &rs, bool direct)
-{
-	// (value ids of a block -- its boundary values and one per column -- are 16-bit keys of the partition step)
-	return rs.lds(c->B, red_symcap(c, rs, direct)) <= LDS_LIMIT && (uint64_t) rs.rows + c->B + 1u <= 65535u;
-}
-
-} // namespace
-
-void red_fill_args(fseq_ctx *c, RedArgs &RA)
-{
-	RA.cnt = c->d_red_cnt; RA.vmin = c->d_red_vmin; RA.a = c->d_red_a; RA.d = c->d_red_d; RA.leaf = c->d_red_leaf;
-	RA.invalid = c->d_red_invalid; RA.any_invalid = &red_flags(c)->unproven; RA.cap = c->red_cap; RA.m_true = c->p.m;
-	RA.direct = c->red_direct ? 1u : 0u; RA.colbytes = sym_bytes(c->p.m, c->bsh); RA.rank = c->d_rank;
-	RA.ss_a = c->d_red_ss_a; RA.ss_d = c->d_red_ss_d; RA.ss_stride = c->red_ss_stride; RA.ss_cap = c->red_ss_cap;
-	RA.blocks = c->d_red_blocks;                               // (the plan's block lists: red_launch_all indexes them; pass 2 brings its own)
-}
-
-// ---- [r5] phase C on representative rows (fseq_reduced.hpp): the plan of one attempt.
-// k_reduce_prep leaves, per block, the representatives and the reduced start state.  The blocks are sorted into the
-// configurations that hold them (a launch per configuration in use, side by side on their own streams) and the blocks
-// that run on all rows: more representatives than any configuration holds (or than pay: > 70 % of the rows), or lists an
-// earlier run on this input could not prove on the representatives.  The first run on an input (or at a new capacity) reads
-// the counts back and plans; later runs launch by the same plan without waiting and have the device check that the counts
-// are the ones the plan was made from (flags word 1; the attempt is repeated with a fresh plan if not).
-// *use: false when more than a quarter of the blocks would run on all rows anyway -- the attempt then takes the run on
-// all rows with its stride states (diverse inputs).
-int red_plan(fseq_ctx *c, uint32_t X, bool *use)
-{
-	FSEQ_LONG_LOCALS(c);
-	*use = false;
-	uint32_t cap = std::min<uint32_t>(m, 11264u);
-	if (c->tune.reduced_cap) cap = std::min<uint32_t>(cap, (uint32_t) c->tune.reduced_cap);
-	uint32_t const nbk = c->nblocks;
-	if (!c->d_red_cnt || c->red_cap != cap)
-	{
-		// (the small per-block words for every block of the alignment; the per-block rows for my blocks only -- a rank of a
-		// sharded run --, addressed by the block's place in the whole alignment like the key blocks and boundary states)
-		if ((rc = c->d_red_cnt.alloc(c, nbk))) return rc;
-		if ((rc = c->d_red_cnt_plan.alloc(c, nbk))) return rc;
-		if ((rc = c->d_red_vmin.alloc(c, nbk))) return rc;
-		if ((rc = c->d_red_invalid.alloc(c, nbk + 2))) return rc;
-		if ((rc = c->d_red_blocks.alloc(c, 3 * (size_t) nbk))) return rc;
-		if ((rc = c->d_red_rows.alloc_range(c, b_lo, b_hi, cap))) return rc;
-		if ((rc = c->d_red_leaf.alloc_range(c, b_lo, b_hi, cap))) return rc;
-		if ((rc = c->d_red_a.alloc_range(c, b_lo, b_hi, cap))) return rc;
-		if ((rc = c->d_red_d.alloc_range(c, b_lo, b_hi, cap))) return rc;
-		c->red_cap = cap;
-		c->red_plan_valid = false;
-	}
-	if (!my_blocks) return FSEQ_OK;                            // (a rank without blocks)
-	// (the last run on this input at this capacity found the representatives not worth it: the same input gives the same answer)
-	if (c->red_declined && c->red_declined_X == X && !c->tune.reduced_always) return FSEQ_OK;
-	if (c->red_pin_words < 4 * (size_t) nbk + 64)
-	{
-		if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);
-		c->h_red_pin = nullptr; c->red_pin_words = 0;
-		HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_red_pin), (4 * (size_t) nbk + 64) * 4, hipHostMallocDefault));
-		c->red_pin_words = 4 * (size_t) nbk + 64;
-	}
-	if (!c->red_ev[0])
-		for (auto &evt : c->red_ev) HIP_TRY(c, hipEventCreateWithFlags(&evt, hipEventDisableTiming));
-	// LDS-resident row counts: the representatives' symbols come from the alignment's own columns (a block stages whole columns)
-	c->red_direct = !c->use_stream;
-	RedPrepArgs A{};
-	A.bstate_a = c->d_bstate_a; A.bstate_d = c->d_bstate_d; A.rank = c->d_rank; A.blocks = nullptr;
-	A.m = m; A.B = c->B; A.L = (uint32_t) L; A.cap = cap; A.block0 = b_lo; A.leaf_only = 0; A.n = n; A.direct = c->red_direct ? 1u : 0u;
-	A.Xp = X + (c->tune.reduced_margin >= 0 ? (uint32_t) c->tune.reduced_margin : X / 4u + 8u);
-	A.cnt = c->d_red_cnt; A.vmin = c->d_red_vmin; A.rows = c->d_red_rows; A.leaf = c->d_red_leaf; A.a = c->d_red_a; A.d = c->d_red_d;
-	A.invalid = c->d_red_invalid; A.flags = &red_flags(c)->unproven;      // (both words)
-	HIP_TRY(c, launch_reduce_prep(st, my_blocks, A));
-	// the reduced alignment of the listed blocks (streamed rows), by the plan in force when it is queued
-	// The listed blocks are two lists by where their columns come from: the blocks with class columns (phase A's trie ranked them: d_cls_have) are
-	// gathered from those, the others (the trie gave them up) from the alignment as before.  Which block is which is known on the device when the
-	// launches are queued -- and a later run launches by its plan without waiting --, so both launches take the whole list and a workgroup
-	// of either leaves at once where the block is the other's; where the trie ran alone every block has class columns and the launch
-	// on the alignment is not made.
-	auto reduce_msa = [&] {
-		ReducedMsaArgs D{c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, cap, c->d_red_blocks, c->red_listed, c->red_max_rows};
-		c->cls_read = c->cls_on && launch_reduce_cls(st, msa_args(c), D, ClassColumnArgs{c->d_cls, c->cls_ld, c->d_cls_have, c->d_red_leaf, c->d_rank});
-		if (c->cls_read && c->cls_every) return;
-		if (c->cls_read) { D.flag = c->d_cls_have; D.want = 0u; }
-		launch_reduce_msa(st, msa_args(c), D, c->tune.reduced_msa_gather);
-	};
-	if (c->red_plan_valid && c->red_plan_X == X && c->red_force_full.size() == nbk)
-	{
-		launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, &red_flags(c)->unproven);      // (it sets the second word)
-		if (!c->red_direct)
-			reduce_msa();
-		c->tm.reduced_blocks = c->red_plan_blocks; c->tm.reduced_rows_mean = c->red_plan_rows_mean;
-		*use = true;
-		return FSEQ_OK;
-	}
-	uint32_t *const h_cnt = c->h_red_pin;
-	HIP_TRY(c, hipMemcpyAsync(h_cnt + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToHost, st));
-	HIP_TRY(c, hipMemcpyAsync(c->d_red_cnt_plan + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToDevice, st));
-	HIP_TRY(c, hipStreamSynchronize(st));
-	c->red_cnt_host.assign(nbk, RED_NONE);
-	std::copy(h_cnt + b_lo, h_cnt + b_hi, c->red_cnt_host.begin() + b_lo);
-	if (c->red_force_full.size() != nbk) c->red_force_full.assign(nbk, 0);
-	c->red_full.assign(nbk, 0);
-	c->red_config_of.assign(nbk, -1);
-	c->red_config_snap_of.assign(nbk, -1);
-	int const nconf = reduced_config_count();
-	std::vector<ReducedSet> sets((size_t) nconf);
-	std::vector<uint8_t> usable((size_t) nconf), usable_snap((size_t) nconf);
-	for (int i = 0; i < nconf; ++i)
-	{
-		(void) reduced_config(i, &sets[(size_t) i]);
-		ReducedSet const &rs = sets[(size_t) i];
-		// (small blocks: one-wave workgroups for both; from 256 threads on phase C takes the configurations with a list wave,
-		// pass 2's sweeps the others)
-		bool const fit = columns_fit_reduced(c, rs, c->red_direct);
-		usable[(size_t) i] = fit && (rs.T <= 128u || rs.ew);
-		usable_snap[(size_t) i] = fit && !rs.ew;
-	}
-	std::vector<std::vector<uint32_t>> per((size_t) nconf);
-	uint32_t n_full = 0, max_rows = 0, listed = 0;
-	uint64_t sum_rows = 0;
-	uint32_t *const h_blocks = c->h_red_pin + nbk;             // [0, listed): every reduced block; then the configurations' lists
-	for (uint32_t b = b_lo; b < b_hi; ++b)
-	{
-		uint32_t const r = c->red_cnt_host[b];
-		if (r != RED_NONE)
-		{
-			h_blocks[listed++] = b;
-			max_rows = std::max(max_rows, r);
-			int cf = -1, cs = -1;
-			// (a block the slim configuration refused -- more distinct start values than its table holds -- skips it)
-			bool const wide = c->red_force_full[b] == RED_FORCE_WIDE;
-			for (int i = 0; i < nconf; ++i) if (usable[(size_t) i] && sets[(size_t) i].rows >= r && !(wide && sets[(size_t) i].values < sets[(size_t) i].rows)) { cf = i; break; }
-			for (int i = 0; i < nconf; ++i) if (usable_snap[(size_t) i] && sets[(size_t) i].rows >= r) { cs = i; break; }
-			c->red_config_of[b] = cf;
-			c->red_config_snap_of[b] = cs;
-		}
-		bool const full = r == RED_NONE || c->red_config_of[b] < 0 || c->red_force_full[b] == RED_FORCE_FULL || (uint64_t) r * 10u > (uint64_t) m * 7u;
-		if (full) { c->red_full[b] = 1; ++n_full; }
-		else { per[(size_t) c->red_config_of[b]].push_back(b); sum_rows += r; }
-	}
-	c->red_listed = listed; c->red_max_rows = max_rows;
-	c->tm.reduced_blocks = my_blocks - n_full;
-	c->tm.reduced_rows_mean = my_blocks > n_full ? (uint32_t) (sum_rows / (my_blocks - n_full)) : 0u;
-	if (c->tune.debug)
-		fprintf(stderr, "[fseq] reduced phase C: %u of %u blocks on their representatives (mean %u of %u rows, most %u), %u on all rows\n", my_blocks - n_full, my_blocks,
-		        c->tm.reduced_rows_mean, m, max_rows, n_full);
-	if (c->tune.debug)
-		for (int i = 0; i < nconf; ++i)
-			if (!per[(size_t) i].empty())
-			{
-				uint64_t sr = 0;
-				for (uint32_t b : per[(size_t) i]) sr += c->red_cnt_host[b];
-				ReducedSet const &rs = sets[(size_t) i];
-				size_t const lds = rs.lds(c->B, red_symcap(c, rs, c->red_direct));
-				uint32_t const res = rs.prepare(lds) == hipSuccess ? rs.resident(lds) : 0u;
-				fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU)\n",
-				        rs.rows, per[(size_t) i].size(), (unsigned long long) (sr / per[(size_t) i].size()), rs.T, rs.E, rs.values, lds, res);
-			}
-	// worth it?  The run on all rows is the tuned one (three workgroups per CU, stride states for pass 2), and a row of a small
-	// reduced workgroup costs more than a row there: the representatives take over where they are clearly fewer -- rows to
-	// update in all, a block on all rows counted as one and a half (its boundaries are reached from the block's start) -- below
-	// a fifth of the rows (BASELINE C3 / C4 / C5: 8 / 7 / 6 %; C3's shape with ten times the mutations, 40 %: 11.4 ms against
-	// 9.4 on all rows, tools/diversity_sweep.py; FSEQ_REDUCED_ALWAYS: tests)
-	{
-		uint64_t const rows_all = sum_rows + (uint64_t) n_full * m * 3u / 2u;
-		if ((!c->tune.reduced_always && (rows_all * 5u > (uint64_t) my_blocks * m || (uint64_t) n_full * 4u > my_blocks)) || (uint64_t) n_full >= my_blocks)
-		{
-			c->red_declined = true; c->red_declined_X = X;
-			c->d_cls.release(c); c->cls_on = false;          // (phase A writes no class columns while the input stays declined)
-			return FSEQ_OK;
-		}
-	}
-	if (n_full && c->use_stream && !c->s2.T)                     // (the first form of the streamed kernel takes no block list)
-	{
-		// (nobody reads the class columns, and the same input gives the same answer next time: phase A writes none for it again)
-		c->d_cls.release(c); c->cls_on = false; c->cls_unread = true;
-		return FSEQ_OK;
-	}
-	if (!c->red_direct)
-	{
-		// the reduced alignment: column k at d_red_msa + k * red_ld
-		// (my columns only: column k at d_red_msa + k * red_ld)
-		size_t const ldr = ((size_t) sym_bytes(max_rows ? max_rows : 1u, c->bsh) + 15) & ~size_t(15);
-		uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
-		size_t const need = (size_t) (k_hi - k_lo) * ldr + 64;
-		if ((rc = c->d_red_msa.ensure(c, need))) return rc;
-		c->red_ld = ldr;
-		c->d_red_msa.rebase((ptrdiff_t) ((size_t) k_lo * ldr));
-	}
-	{
-		// the reduced states for pass 2: every 16 columns (32: streamed rows), rows for the most representatives of a block
-		uint32_t const stride_ = c->use_stream ? 32u : 16u;
-		uint32_t const scap = (std::max(max_rows, 1u) + 63u) & ~63u;
-		uint64_t const q_lo = (uint64_t) b_lo * c->B / stride_, q_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B) / stride_;
-		size_t const words = ((size_t) (q_hi - q_lo) + 2) * scap;
-		if ((rc = c->d_red_ss_a.ensure(c, words))) return rc;
-		if ((rc = c->d_red_ss_d.ensure(c, words))) return rc;
-		c->red_ss_stride = stride_; c->red_ss_cap = scap;
-		c->d_red_ss_a.rebase((ptrdiff_t) ((size_t) q_lo * scap));         // (the state at column q * stride at [q][scap])
-		c->d_red_ss_d.rebase((ptrdiff_t) ((size_t) q_lo * scap));
-	}
-	c->red_bins.clear();
-	uint32_t at = listed;
-	for (int i = 0; i < nconf; ++i)
-	{
-		auto const &v = per[(size_t) i];
-		if (v.empty()) continue;
-		std::copy(v.begin(), v.end(), h_blocks + at);
-		c->red_bins.push_back(fseq_ctx::RedBin{i, at, (uint32_t) v.size()});
-		at += (uint32_t) v.size();
-	}
-	c->red_full_at = at; c->red_nfull = 0;
-	for (uint32_t b = b_lo; b < b_hi; ++b) if (c->red_full[b]) h_blocks[at + c->red_nfull++] = b;
-	at += c->red_nfull;
-	HIP_TRY(c, hipMemcpyAsync(c->d_red_blocks, h_blocks, (size_t) at * 4, hipMemcpyHostToDevice, st));
-	if (!c->red_direct)
-		reduce_msa();
-	c->red_plan_valid = true; c->red_plan_X = X;
-	c->red_plan_blocks = c->tm.reduced_blocks; c->red_plan_rows_mean = c->tm.reduced_rows_mean;
-	*use = true;
-	return FSEQ_OK;
-}
-
-// launches of the reduced column kernel over lists of workgroups, one per configuration, side by side: the first on the
-// context's stream, the others on streams of their own that wait for it and that it waits for
-
-int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const &base, ListArgs const &lists)
-{
-	FSEQ_LONG_LOCALS(c);
-	if (ls.empty()) return FSEQ_OK;
-	// (up to RED_SIDE_STREAMS side streams, the context's second stream first -- every further hardware queue in use slows the
-	// dependent launches of phase B, measured on BASELINE C3: 0.71 ms with none, 0.97 with three)
-	size_t const nside = std::min<size_t>(ls.size() - 1, RED_SIDE_STREAMS);
-	if (nside) HIP_TRY(c, hipEventRecord(c->red_ev[3], st));
-	// [r7] queued largest workgroups first (the blocks of ten thousand representatives are not the tail of the phase, as pass 2's
-	// largest groups are not); the launch with the most blocks stays on the context's stream, the others take the side streams
-	// in that order and, past those, the context's
-	size_t main_i = 0;
-	for (size_t i = 1; i < ls.size(); ++i) if (ls[i].count > ls[main_i].count) main_i = i;
-	size_t side = 0;
-	// the representatives' symbols: the alignment's own columns (LDS-resident row counts), or the reduced alignment
-	ColumnsArgs C;
-	C.A = msa_args(c);
-	if (!c->red_direct) { C.A.msa = c->d_red_msa; C.A.ld = c->red_ld; }
-	C.lists = lists;
-	for (size_t i = 0; i < ls.size(); ++i)
-	{
-		ReducedSet rs;
-		(void) reduced_config(ls[i].config, &rs);
-		RedArgs RA = base;
-		RA.symcap = red_symcap(c, rs, c->red_direct);
-		size_t const lds = rs.lds(c->B, RA.symcap);
-		HIP_TRY(c, rs.prepare(lds));
-		RA.blocks = base.blocks + ls[i].first;
-		if (base.wg_tasks) RA.wg_tasks = base.wg_tasks + 3 * (size_t) ls[i].first;
-		hipStream_t s_ = st;
-		size_t const slot = (i != main_i && side < nside) ? side++ : nside;      // (nside: the context's stream)
-		if (slot < nside)
-		{
-			if (slot >= 1 && !c->red_st[slot - 1]) HIP_TRY(c, hipStreamCreateWithFlags(&c->red_st[slot - 1], hipStreamNonBlocking));
-			s_ = slot == 0 ? c->stream2 : c->red_st[slot - 1];
-			HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev[3], 0));
-		}
-		rs.launch(s_, ls[i].count, lds, C, RA);
-		if (slot < nside) HIP_TRY(c, hipEventRecord(c->red_ev[slot], s_));
-	}
-	for (size_t i = 0; i < nside; ++i) HIP_TRY(c, hipStreamWaitEvent(st, c->red_ev[i], 0));
-	HIP_TRY(c, hipGetLastError());
-	return FSEQ_OK;
-}
-
-// the lists of the reduced blocks
-int red_columns(fseq_ctx *c)
-{
-	RedArgs RA;
-	red_fill_args(c, RA);
-	std::vector<RedLaunch> ls;
-	for (auto const &bin : c->red_bins) ls.push_back(RedLaunch{bin.config, bin.first, bin.count});
-	// (the bins ascend by the rows a workgroup holds: the largest first)
-	std::reverse(ls.begin(), ls.end());
-	return red_launch_all(c, ls, RA, list_args(c));
 }
 
 namespace {

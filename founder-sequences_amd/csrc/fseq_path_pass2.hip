@@ -1,6 +1,6 @@
 // fseq_path_pass2.hip -- the segmentation path, pass 2: the (a, d) states at the merged boundaries, behind phase C on all rows
 // (from the stride states) or behind the reduced phase C (one chain step from the block's boundary state).  It launches through
-// KernelSet, Stream2Config, ChainSnapSet and the launchers of fseq_path_pass1.hip, which all take the boundaries as one SnapArgs.
+// KernelSet, Stream2Config, ChainSnapSet and the launchers of fseq_path_pass1.hip and fseq_path_reduced.hip, which all take the boundaries as one SnapArgs.
 // (The units of the path and what crosses them: fseq_path.hpp.)
 #include "fseq_path.hpp"
 #include "fseq_stream2.hpp"      // (no name of it is used here since the launchers take SnapArgs; kept so that the unit's device code stays what it was)
@@ -36,6 +36,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	FSEQ_LONG_LOCALS(c);
 	size_t const S2all = c->segments.size();
 	if (!S2all) return FSEQ_OK;
+	RedPlan const &plan = c->red.plan;
 	ChainSnapSet cs{};
 	if (!c->use_stream)
 	{
@@ -69,13 +70,13 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		task_blk.push_back(blk);
 		ncls0.push_back(0u);                                       // a border: the copy; else the sweep fills it in
 		if (border) continue;
-		int const cf = blk < c->red_config_snap_of.size() ? c->red_config_snap_of[blk] : -1;
-		if (cf >= 0 && c->red_cnt_host[blk] != RED_NONE)
+		int const cf = blk < plan.config_snap_of.size() ? plan.config_snap_of[blk] : -1;
+		if (cf >= 0 && plan.cnt[blk] != RED_NONE)
 		{
 			// the sweep starts at the last state phase C dropped in front of the boundary (or at the block's first column)
 			uint64_t start = c->red_ss_stride ? (rb - 1u) / c->red_ss_stride * c->red_ss_stride : 0u;
 			// (a block that ran on all rows dropped none)
-			if (start <= (uint64_t) blk * c->B || c->red_full[blk]) start = (uint64_t) blk * c->B;
+			if (start <= (uint64_t) blk * c->B || plan.full[blk]) start = (uint64_t) blk * c->B;
 			auto &v = wgs[(size_t) cf];
 			if (!v.empty() && v.back().blk == blk && v.back().start == (uint32_t) start) ++v.back().count;
 			else v.push_back(Wg{blk, (uint32_t) i, 1u, (uint32_t) start});
@@ -133,7 +134,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		for (auto const &w : wgs[cf])
 		{
 			hb.push_back(w.blk); hw.push_back(w.first); hw.push_back(w.count); hw.push_back(w.start);
-			cells += (rbs[w.first + w.count - 1u] - (uint64_t) w.start) * c->red_cnt_host[w.blk];
+			cells += (rbs[w.first + w.count - 1u] - (uint64_t) w.start) * plan.cnt[w.blk];
 		}
 		if (c->tune.debug)
 		{

@@ -499,9 +499,10 @@ void free_work(fseq_ctx *c)
 	c->lw.col_lo = c->lw.col_hi = 0;
 	c->colmask_ready = false;
 	c->ss_pack = 0; c->ss_ids = false;       // (the form of the stride states: decided again where they are allocated)
-	c->red_plan_valid = false; c->red_declined = false; c->red_cap = 0; c->red_ld = 0;
+	c->red.memory.forget_verdicts();
+	c->red_cap = 0; c->red_ld = 0;
 	c->red_active = false;
-	c->cls_on = c->cls_every = c->cls_read = c->cls_unread = false; c->cls_ld = 0;
+	c->cls_on = c->cls_every = c->cls_read = false; c->cls_ld = 0;
 }
 
 namespace {

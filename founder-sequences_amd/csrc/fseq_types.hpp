@@ -2,6 +2,8 @@
 // kernel headers that use them.
 #pragma once
 
+#include "fseq_redplan.hpp"     // RED_NONE, and the plan the context holds by value
+
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -61,6 +63,9 @@ struct AttemptWords {
 // of a context's buffers and geometry.  A kernel's positional parameter list is written out at one place, its launcher, from
 // these by name; the kernels themselves keep their scalar and __restrict__ pointer parameters (fseq_path.hpp builds the
 // views of a context).
+
+// bytes of m rows of a packed column: 8 >> bsh bits per dense symbol code (the storage: fseq_kernels.hpp)
+__host__ __device__ inline uint32_t sym_bytes(uint32_t m, uint32_t bsh) { return (m + (1u << bsh) - 1u) >> bsh; }
 
 // the alignment as a kernel sees it: column k at msa + k * ld, in nblocks blocks of B columns
 struct MsaArgs {
@@ -186,7 +191,6 @@ struct ClassColumnArgs {
 // workgroup of the reduced column kernel finds it.  Plain pointers into device memory.
 constexpr uint32_t P2_HIST = 19;                 // ... tasks by run count: bucket b counts those with more than 2^(b - 1) and at most 2^b runs (bucket 0: one run)
 constexpr uint32_t P2_STATS = 4 + P2_HIST;       // counters of pass 2's streamed chain step (k_chain_snap_grouped; fseq_debug_pass2_paths)
-constexpr uint32_t RED_NONE = 0xFFFFFFFFu;      // cnt[b]: block b is not reduced (more representatives than the kernel holds)
 constexpr uint32_t RED_WIDE = 2u;               // invalid[b]: the block has more distinct start values than its configuration's table holds
 struct RedArgs {
 	uint32_t const *cnt = nullptr;      // [block] representatives of the block

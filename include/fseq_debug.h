@@ -126,6 +126,22 @@ int  fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t
                              uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
                              uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys);
 
+/* The plan of phase C on representative rows (plan_reduced, csrc/fseq_redplan.hpp) on caller-supplied counts (debug / tests; touches
+ * no device).  The configurations are the library's, judged as a run of m rows in blocks of B columns at `bits` bits a symbol would
+ * judge them (direct != 0: LDS-resident rows, which stage the alignment's own columns).  cnt[nblocks]: the representatives of every
+ * block (0xFFFFFFFF: not reduced); force[nblocks] or NULL: 0, 1 (the block on all rows) or 2 (the block skips the slim
+ * configuration); [b_lo, b_hi): the blocks planned for; no_block_list: the kernel on all rows takes no block list.
+ * Out, each or NULL: configs[FSEQ_DEBUG_RED_CONFIGS][6] = {rows, values, threads, rows per thread, list wave, fits} and *n_configs;
+ * *verdict (0 use, 1 declined, 2 no block list); full / config_of / config_snap_of [nblocks]; blocks[3 nblocks], the list that goes to
+ * the device, and *n_blocks; bins[n_configs][3] = {configuration, first, count} into blocks and *n_bins; summary[6] = {full_at,
+ * nfull, listed, max_rows, reduced_blocks, rows_mean}.  Checked before anything is indexed, FSEQ_E_ARG otherwise: m, B >= 1; bits 2,
+ * 4 or 8; b_lo <= b_hi <= nblocks <= 2^24; every count <= m or 0xFFFFFFFF; every force mark 0, 1 or 2. */
+#define FSEQ_DEBUG_RED_CONFIGS 64
+int  fseq_debug_red_plan(uint32_t m, uint32_t B, uint32_t bits, int direct, uint32_t nblocks, uint32_t b_lo, uint32_t b_hi, uint32_t const *cnt,
+                         uint8_t const *force, int reduced_always, int no_block_list, uint32_t *configs, uint32_t *n_configs, int *verdict,
+                         uint8_t *full, int32_t *config_of, int32_t *config_snap_of, uint32_t *blocks, uint32_t *n_blocks, uint32_t *bins,
+                         uint32_t *n_bins, uint32_t *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ Every case is two_halves() at n = 1,300 columns, L = 602, blocks of 100 columns,
   * `pairs` pairs of types agree on [0, c) but for one column below `span` = 80, so the lists of block 6 hold dozens of
     distinct values below the threshold k + 2 - L: 34 to 40 at column 640, 65 to 81 at column 686 -- more than the default
     list capacity of 63, an open list.
-  * 10 R <= 7 m: red_plan (csrc/fseq_path_pass1.hip) sends a block with more representatives than 70 % of the rows to all rows.
+  * 10 R <= 7 m: plan_reduced (csrc/fseq_redplan.hpp) sends a block with more representatives than 70 % of the rows to all rows.
     m is the least such row count rounded up to a multiple of 50, so R > 7,884 means m > 11,264: streamed rows.
 
 The expected configurations are written BY HAND from FSEQ_RED_CONFIGS, as thresholds (PHASE_C, PASS_2) and again row by row
