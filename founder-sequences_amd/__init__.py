@@ -102,12 +102,12 @@ EXPORTS = [
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
-    "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan",
+    "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan"]
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -215,6 +215,8 @@ def load_library():
     L.fseq_debug_bipartite_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
     L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
+    L.fseq_debug_column_sources.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.fseq_debug_red_cls_direct.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)]
     L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.fseq_debug_red_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.c_int] + [vp] * 11
@@ -338,6 +340,17 @@ RED_NONE = 0xFFFFFFFF                       # csrc/fseq_redplan.hpp: a block tha
 RED_FORCE_FULL, RED_FORCE_WIDE = 1, 2       # ... the force marks
 RED_USE, RED_DECLINED, RED_NO_BLOCK_LIST = 0, 1, 2      # ... RedVerdict
 RED_CONFIGS_MAX = 64                        # include/fseq_debug.h, FSEQ_DEBUG_RED_CONFIGS
+
+
+def red_cls_direct_host(m, B, bits, cls_ld, config, resident_rows, resident_cls):
+    """The direct-or-gather rule of configuration `config` of the reduced column kernel (red_cls_direct, csrc/fseq_redplan.hpp) at
+    this geometry, given the workgroups per CU the device reports with either staged-column buffer: (lds_rows, lds_cls, direct).
+    No device is touched."""
+    a, b, d = C.c_uint64(), C.c_uint64(), C.c_int()
+    rc = load_library().fseq_debug_red_cls_direct(m, B, bits, cls_ld, config, resident_rows, resident_cls, C.byref(a), C.byref(b), C.byref(d))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, "red_cls_direct_host")
+    return a.value, b.value, bool(d.value)
 
 
 def red_plan_host(m, B, bits, direct, cnt, force=None, b_lo=0, b_hi=None, reduced_always=False, no_block_list=False):
@@ -920,6 +933,17 @@ class SegmentationContext:
         a, b = C.c_uint32(), C.c_uint32()
         self._check(self.L.fseq_debug_class_columns(self.h, C.byref(a), C.byref(b), 0xFFFFFFFF, None, None, None, None, 0))
         return {"from_classes": a.value, "from_alignment": b.value}
+
+    def column_sources(self, block=None):
+        """How the last run's listed blocks came by their columns: {staged, gathered} blocks -- phase A's class columns staged by the
+        reduced column kernel itself / the reduced alignment (gathered from the class columns or the alignment) -- and, for a block,
+        block_staged; all zero where the run had no reduced alignment to build (LDS-resident rows, no representatives)."""
+        a, b, s = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self.L.fseq_debug_column_sources(self.h, C.byref(a), C.byref(b), 0xFFFFFFFF if block is None else block, C.byref(s)))
+        out = {"staged": a.value, "gathered": b.value}
+        if block is not None:
+            out["block_staged"] = bool(s.value)
+        return out
 
     def class_columns(self, block):
         """Phase A's class columns of a block of the last run: (packed, ldc, nkeys) -- packed[j] the ldc bytes of the block's column j, row

@@ -74,6 +74,32 @@ int fseq_debug_class_columns(fseq_ctx *c, uint32_t *from_classes, uint32_t *from
 	return FSEQ_OK;
 }
 
+int fseq_debug_column_sources(fseq_ctx *c, uint32_t *staged, uint32_t *gathered, uint32_t block, uint32_t *block_staged)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	uint32_t const b_lo = c->sh.on ? c->sh.b_lo : 0u, b_hi = c->sh.on ? c->sh.b_hi : c->nblocks;
+	uint32_t n_staged = 0, n_gathered = 0, mine = 0;
+	RedPlan const &P = c->red.plan;
+	if (c->red_active && !c->red_direct && P.cnt.size() == c->nblocks)
+	{
+		std::vector<uint32_t> have(c->nblocks, 0u);
+		if (c->cls_staged && b_hi > b_lo) HIP_TRY(c, hipMemcpy(have.data() + b_lo, c->d_cls_have + b_lo, (size_t) (b_hi - b_lo) * 4, hipMemcpyDeviceToHost));
+		for (uint32_t b = b_lo; b < b_hi; ++b)
+		{
+			if (P.cnt[b] == RED_NONE) continue;
+			bool const st = c->cls_staged && P.from_cls[b] && have[b];
+			++(st ? n_staged : n_gathered);
+			if (b == block) mine = st ? 1u : 0u;
+		}
+	}
+	if (staged) *staged = n_staged;
+	if (gathered) *gathered = n_gathered;
+	if (block_staged) *block_staged = mine;
+	return FSEQ_OK;
+}
+
 int fseq_debug_dp(fseq_ctx *c, uint32_t *lb, uint32_t *max_size, uint32_t *size)
 {
 	if (!c) return FSEQ_E_ARG;

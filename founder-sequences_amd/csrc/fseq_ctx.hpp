@@ -134,6 +134,7 @@ struct Tuning {
 	bool reduced_always = false;         // FSEQ_REDUCED_ALWAYS: the representatives whenever some block has fewer of them than rows (tests of the mixed runs)
 	bool reduced_msa_gather = false;     // FSEQ_REDUCED_MSA_GATHER: the reduced alignment by gathers from memory (by itself: the column through LDS where it fits)
 	int  reduced_cap = 0;                // FSEQ_REDUCED_CAP: most representatives a block may have (tests: small values send blocks to the run on all rows)
+	bool class_gather = false;           // FSEQ_CLASS_GATHER: the class columns are gathered into the reduced alignment for every block (the form before the column kernel staged them itself)
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 
@@ -183,6 +184,7 @@ struct Tuning {
 			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
 			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
+			{"FSEQ_CLASS_GATHER", &Tuning::class_gather, nullptr, 0, 0, nullptr},
 		};
 		return table;
 	}
@@ -406,11 +408,16 @@ struct fseq_ctx {
 	bool cls_on = false;                     // this run's phase A wrote class columns
 	bool cls_every = false;                  // ... for every block of mine (the trie ran alone: it gave no block up in the run before on this input)
 	bool cls_read = false;                   // this run's reduced alignment took them where a block has them (fseq_debug_class_columns)
+	// [r10] ... or the reduced column kernel staged them itself (RedArgs::cls_have): d_red_src[block] = red.plan.from_cls, uploaded with the plan's
+	// block lists; cls_staged: this run's launches went so (FSEQ_CLASS_GATHER: never -- every block through the reduced alignment)
+	DevBuf<uint32_t> d_red_src;
+	bool cls_staged = false;
 	// the plan of the representatives (fseq_redplan.hpp; red_plan, csrc/fseq_path_reduced.hip): every result of a planning is in
 	// `plan`, everything a run remembers of this input for the next in `memory` (DESIGN.md section 1 has the table of what each
 	// forget_* clears, by the site that calls it)
 	struct Red {
 		fseq::RedPlan plan;                  // of the last planning: read where red_active says this run's phase C went by it
+		std::vector<uint8_t> cls_config;     // ... [configuration] RedConfig::cls as that planning saw it (the launches size their buffers by it)
 		struct Memory {
 			std::vector<uint8_t> force;      // [block] RED_FORCE_FULL / RED_FORCE_WIDE marks (RedPlanInput::force); of another input's size: none
 			// `plan` is the plan (which block on which configuration) of the last run on this input at capacity plan_X: the next run

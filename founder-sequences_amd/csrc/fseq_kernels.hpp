@@ -800,6 +800,15 @@ __device__ __forceinline__ void columns_body(char *smem,
 		if (red_snap) { t_first = red.wg_tasks[3u * blockIdx.x]; t_count = red.wg_tasks[3u * blockIdx.x + 1u]; }
 	}
 	bool const red_exact = RED && red_vmin <= 1u;
+	// [r10] this block's columns are phase A's class columns and the ids of its order block-key ranks (RedArgs; wave-uniform)
+	bool red_cls = false;
+	uint32_t red_nkeys = 0;
+	if constexpr (RED)
+	{
+		// (scalars by construction: the block is the workgroup's)
+		if (red.cls_have != nullptr) red_cls = __builtin_amdgcn_readfirstlane(red.cls_src[blk] & red.cls_have[blk]) != 0u;
+		if (red_cls) red_nkeys = __builtin_amdgcn_readfirstlane(red.nkeys[blk]);
+	}
 	// [a_l][d_l][sym0][sym1][cnt_l] are contiguous: the prologue's sort buffer (N2 < 2m words) overlays them
 	using AT = std::conditional_t<PK, uint16_t, uint32_t>;     // row ids < m, value ids < m + B
 	Carver cv{smem};
@@ -976,9 +985,12 @@ __device__ __forceinline__ void columns_body(char *smem,
 	// RED: the packed column straight into LDS (LDS-DMA, no registers: a column of the alignment itself may be several
 	// 16-byte pieces per thread); every lane loads -- a lane past the column's bytes re-reads its first piece into the
 	// buffer's padding
-	uint32_t const red_colbytes = RED ? (red.direct ? red.colbytes : sym_bytes(m, bsh)) : 0u;
+	// (a class column: the bytes of the block's keys in whole pieces, at most the column's pitch)
+	uint32_t const red_colbytes = RED ? (red.direct ? red.colbytes : red_cls ? min((uint32_t) red.cls_ld, (sym_bytes(red_nkeys, bsh) + 15u) & ~15u) : sym_bytes(m, bsh)) : 0u;
+	uint8_t const *const red_msa = red_cls ? red.cls_msa : msa;
+	size_t const red_ld = red_cls ? red.cls_ld : ld;
 	auto red_stage = [&](uint64_t k, uint8_t *dstb) {
-		uint8_t const *const col = msa + k * ld;
+		uint8_t const *const col = red_msa + k * red_ld;
 		for (uint32_t cb = 0; cb < red_colbytes; cb += (uint32_t) T * 16u)
 		{
 			uint32_t const off = cb + tid * 16u;
@@ -987,12 +999,21 @@ __device__ __forceinline__ void columns_body(char *smem,
 		}
 	};
 	if (RED && nb) { red_stage(k0, sym0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+	// [r10] from the class columns: the block's start state holds representative indices, the order carries their key ranks (a
+	// reduced stride state holds what a_l held then, ranks already).  In place, position by position: in registers next to the
+	// start state the look-ups cost the 32-bit kernels up to two VGPRs a row and the slim one a spill
+	if (RED && red_cls && k0 == kblk)
+	{
+		__syncthreads();
+		uint32_t const *const leaf = red.leaf + (size_t) blk * red.cap;
+		for (uint32_t idx = tid; idx < m; idx += T) a_l[idx] = (AT) leaf[a_l[idx]];
+	}
 	__syncthreads();
 
 	bool const zero_present = (V_l[0] == 0u);
 	// (see the pass loop; compiled into the nine-to-eleven-row kernels only -- the 512-thread 16-bit kernels, the slim one among them, have no register to spare)
 	constexpr bool CARRY_OK = PK && E >= 9 && !columns_slim(T, E, PK);
-	bool const carry = CARRY_OK && npass == 2u && bsh == 1u && ((RED && red.direct) ? red.m_true : m) <= 16384u;
+	bool const carry = CARRY_OK && npass == 2u && bsh == 1u && ((RED && red.direct) ? red.m_true : red_cls ? red_nkeys : m) <= 16384u;      // (the ids: rows of the alignment, key ranks, representatives)
 #ifdef FSEQ_KC_STAMPS
 	long long kc_work = 0, kc_wait = 0, kc_last = clock64();
 	KcStamps kcs{{0, 0, 0, 0, 0, 0, 0, 0}, clock64()};
@@ -1156,7 +1177,8 @@ __device__ __forceinline__ void columns_body(char *smem,
 				}
 				uint32_t total;
 				uint32_t r = block_excl_add<T>(nf, sscr, &total);
-				size_t const ot = (size_t) task * red.cap, ol = (size_t) blk * red.cap;
+				size_t const ot = (size_t) task * red.cap;
+				uint32_t const *const key_of = red.direct ? red.rank + (size_t) blk * red.m_true : red.leaf + (size_t) blk * red.cap;
 				if (rows)
 				{
 #pragma unroll
@@ -1168,7 +1190,9 @@ __device__ __forceinline__ void columns_body(char *smem,
 							uint32_t const vid = d_l[pos];
 							bool const first = vid >= id_in;
 							r += first ? 1u : 0u;
-							uint32_t const lf = red.direct ? red.rank[(size_t) blk * red.m_true + a_l[pos]] : red.leaf[ol + a_l[pos]];
+							// (the key rank of the row: looked up by row id or representative index, or -- from the class columns -- what the order carries)
+							uint32_t lf = a_l[pos];
+							if (!red_cls) lf = key_of[lf];
 							red.cls[ot + lf] = r - 1u;
 							if (first) red.headd[ot + r - 1u] = vid < D0 ? V_l[vid] : (uint32_t) (k0 + (vid - D0) + 1u);
 						}

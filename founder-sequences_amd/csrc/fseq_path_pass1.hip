@@ -234,7 +234,7 @@ int long_phase_a(fseq_ctx *c, LongRun &R)
 	                  && (c->ld & 3u) == 0 && (reinterpret_cast<uintptr_t>(c->d_msa) & 3u) == 0
 	                  && !(c->bt_given_up >= 0 && 2u * (uint32_t) c->bt_given_up > my_blocks);
 	bool const tree_after = tree && !(trie && c->bt_given_up == 0);
-	c->cls_on = c->cls_every = c->cls_read = false;
+	c->cls_on = c->cls_every = c->cls_read = c->cls_staged = false;
 	R.trie_ran = trie;
 	R.trie_alone = trie && !tree_after;
 	// my key blocks, and what the key-space tree works with; the trie hands the tree its blocks, the tree hands the sweep its own

@@ -8,10 +8,11 @@ namespace fseq {
 
 namespace {
 
-// bytes of each staged-column buffer of a reduced configuration
-uint32_t red_symcap(uint32_t m, uint32_t bsh, ReducedSet const &rs, bool direct)
+// bytes of each staged-column buffer of a reduced configuration: a column of the alignment (direct), of the reduced alignment at
+// the rows the configuration holds, or -- cls_ld, [r10] -- the larger of that and a class column of phase A
+uint32_t red_symcap(uint32_t m, uint32_t bsh, ReducedSet const &rs, bool direct, size_t cls_ld = 0)
 {
-	uint32_t const bytes = direct ? sym_bytes(m, bsh) : sym_bytes(rs.rows, bsh);
+	uint32_t const bytes = direct ? sym_bytes(m, bsh) : std::max<uint32_t>(sym_bytes(rs.rows, bsh), (uint32_t) cls_ld);
 	return (bytes + 1023u) & ~1023u;                           // whole kilobytes: a wave stages sixteen bytes per lane
 }
 
@@ -22,16 +23,39 @@ bool columns_fit_reduced(uint32_t m, uint32_t B, uint32_t bsh, ReducedSet const 
 }
 
 // the configurations as planning sees them, at this geometry
-std::vector<RedConfig> red_configs(uint32_t m, uint32_t B, uint32_t bsh, bool direct)
+// cls_ld (a run that may stage phase A's class columns itself; needs the device): which of them take buffers of that width at no
+// cost (red_cls_direct, fseq_redplan.hpp)
+std::vector<RedConfig> red_configs(uint32_t m, uint32_t B, uint32_t bsh, bool direct, size_t cls_ld = 0)
 {
 	std::vector<RedConfig> out;
 	for (int i = 0; i < reduced_config_count(); ++i)
 	{
 		ReducedSet rs;
 		(void) reduced_config(i, &rs);
-		out.push_back(RedConfig{rs.rows, rs.values, rs.T, rs.E, rs.ew, columns_fit_reduced(m, B, bsh, rs, direct)});
+		RedConfig f{rs.rows, rs.values, rs.T, rs.E, rs.ew, columns_fit_reduced(m, B, bsh, rs, direct)};
+		if (cls_ld && !direct && f.fits)
+		{
+			size_t const lds_rows = rs.lds(B, red_symcap(m, bsh, rs, false)), lds_cls = rs.lds(B, red_symcap(m, bsh, rs, false, cls_ld));
+			if (lds_cls == lds_rows) f.cls = true;
+			else if (lds_cls <= LDS_LIMIT && rs.prepare(lds_cls) == hipSuccess)
+				f.cls = red_cls_direct(lds_cls, LDS_LIMIT, rs.resident(lds_rows), rs.resident(lds_cls));
+		}
+		out.push_back(f);
 	}
 	return out;
+}
+
+// [r10] this run's reduced column kernels may stage phase A's class columns themselves: phase A wrote some, in ids the 16-bit
+// orders and the carried digit hold (at most 16,384 keys a block), and nobody asked for the gather
+bool red_cls_stageable(fseq_ctx const *c)
+{
+	return c->cls_on && !c->red_direct && !c->tune.class_gather && ((uint64_t) c->cls_ld << c->bsh) <= 16384u;
+}
+
+// ... and no listed block reads the reduced alignment: every one has class columns and runs on configurations that take their width
+bool red_needs_msa(fseq_ctx const *c)
+{
+	return !c->red_direct && !(red_cls_stageable(c) && c->cls_every && c->red.plan.gathered == 0u);
 }
 
 } // namespace
@@ -43,6 +67,8 @@ void red_fill_args(fseq_ctx *c, RedArgs &RA)
 	RA.direct = c->red_direct ? 1u : 0u; RA.colbytes = sym_bytes(c->p.m, c->bsh); RA.rank = c->d_rank;
 	RA.ss_a = c->d_red_ss_a; RA.ss_d = c->d_red_ss_d; RA.ss_stride = c->red_ss_stride; RA.ss_cap = c->red_ss_cap;
 	RA.blocks = c->d_red_blocks;                               // (the plan's block lists: red_launch_all indexes them; pass 2 brings its own)
+	// (the class columns, for the launches that stage them: red_launch_all sets cls_have where the configuration's buffers hold one)
+	RA.cls_src = c->d_red_src; RA.nkeys = c->d_nkeys; RA.cls_msa = c->d_cls; RA.cls_ld = c->cls_ld;
 }
 
 namespace {
@@ -62,6 +88,7 @@ int red_ensure_block_buffers(fseq_ctx *c, uint32_t cap)
 	if ((rc = c->d_red_vmin.alloc(c, nbk))) return rc;
 	if ((rc = c->d_red_invalid.alloc(c, nbk + 2))) return rc;
 	if ((rc = c->d_red_blocks.alloc(c, 3 * (size_t) nbk))) return rc;
+	if ((rc = c->d_red_src.alloc(c, nbk))) return rc;
 	if ((rc = c->d_red_rows.alloc_range(c, b_lo, b_hi, cap))) return rc;
 	if ((rc = c->d_red_leaf.alloc_range(c, b_lo, b_hi, cap))) return rc;
 	if ((rc = c->d_red_a.alloc_range(c, b_lo, b_hi, cap))) return rc;
@@ -74,7 +101,7 @@ int red_ensure_block_buffers(fseq_ctx *c, uint32_t cap)
 // ... and what lives as long as the context: the pinned staging of a planning's two copies, the events of the side streams
 int red_ensure_host(fseq_ctx *c)
 {
-	size_t const words = 4 * (size_t) c->nblocks + 64;
+	size_t const words = 6 * (size_t) c->nblocks + 64;      // (counts, the block lists, the class-column flags back, the blocks' sources out)
 	if (c->red_pin_words < words)
 	{
 		if (c->h_red_pin) (void) hipHostFree(c->h_red_pin);
@@ -109,14 +136,40 @@ int red_launch_prep(fseq_ctx *c, uint32_t X, uint32_t cap)
 // launches are queued -- and a later run launches by its plan without waiting --, so both launches take the whole list and a workgroup
 // of either leaves at once where the block is the other's; where the trie ran alone every block has class columns and the launch
 // on the alignment is not made.
-void red_reduce_msa(fseq_ctx *c)
+// [r10] Where the column kernels stage the class columns themselves (cls_staged), the gather from the class columns leaves out the blocks
+// the plan sends there (d_red_src) and is not launched when there is none left; the reduced alignment is sized here, and only when a
+// listed block reads it (a later run by the remembered plan may be the first that does: a block the trie gave up this time).
+int red_reduce_msa(fseq_ctx *c)
 {
-	hipStream_t st = c->stream;
+	FSEQ_LONG_LOCALS(c);
+	c->cls_staged = red_cls_stageable(c);
+	if (!red_needs_msa(c)) { c->cls_read = true; return FSEQ_OK; }
+	{
+		// the reduced alignment (my columns only): column k at d_red_msa + k * red_ld
+		uint32_t const max_rows = c->red.plan.max_rows;
+		size_t const ldr = ((size_t) sym_bytes(max_rows ? max_rows : 1u, c->bsh) + 15) & ~size_t(15);
+		uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
+		size_t const need = (size_t) (k_hi - k_lo) * ldr + 64;
+		if (c->red_ld != ldr || c->d_red_msa.cap < need)
+		{
+			if ((rc = c->d_red_msa.ensure(c, need))) return rc;
+			c->red_ld = ldr;
+		}
+		c->d_red_msa.rebase((ptrdiff_t) ((size_t) k_lo * c->red_ld));
+	}
 	ReducedMsaArgs D{c->d_red_msa, c->red_ld, c->d_red_cnt, c->d_red_rows, c->red_cap, c->d_red_blocks, c->red.plan.listed, c->red.plan.max_rows};
-	c->cls_read = c->cls_on && launch_reduce_cls(st, msa_args(c), D, ClassColumnArgs{c->d_cls, c->cls_ld, c->d_cls_have, c->d_red_leaf, c->d_rank});
-	if (c->cls_read && c->cls_every) return;
+	if (c->cls_staged && c->red.plan.gathered == 0u) c->cls_read = true;      // (every block with class columns stages them: only the others are gathered)
+	else
+	{
+		D.skip = c->cls_staged ? (uint32_t const *) c->d_red_src : nullptr;
+		c->cls_read = c->cls_on && launch_reduce_cls(st, msa_args(c), D, ClassColumnArgs{c->d_cls, c->cls_ld, c->d_cls_have, c->d_red_leaf, c->d_rank});
+		D.skip = nullptr;
+		if (!c->cls_read) c->cls_staged = false;               // (a shape the gather does not take: phase A's columns are not read at all)
+	}
+	if (c->cls_read && c->cls_every) return FSEQ_OK;
 	if (c->cls_read) { D.flag = c->d_cls_have; D.want = 0u; }
 	launch_reduce_msa(st, msa_args(c), D, c->tune.reduced_msa_gather);
+	return FSEQ_OK;
 }
 
 // stage 3: the remembered plan still holds: the device checks that the counts are the ones it was made from (the second of
@@ -125,8 +178,7 @@ int red_queue_remembered(fseq_ctx *c)
 {
 	FSEQ_LONG_LOCALS(c);
 	launch_reduce_check(st, c->d_red_cnt + b_lo, c->d_red_cnt_plan + b_lo, my_blocks, &red_flags(c)->unproven);      // (it sets the second word)
-	if (!c->red_direct)
-		red_reduce_msa(c);
+	if (!c->red_direct && (rc = red_reduce_msa(c))) return rc;
 	c->tm.reduced_blocks = c->red.plan.reduced_blocks; c->tm.reduced_rows_mean = c->red.plan.rows_mean;
 	return FSEQ_OK;
 }
@@ -142,16 +194,28 @@ int red_read_counts(fseq_ctx *c, RedPlanInput &in)
 	uint32_t *const h_cnt = c->h_red_pin;
 	HIP_TRY(c, hipMemcpyAsync(h_cnt + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(c, hipMemcpyAsync(c->d_red_cnt_plan + b_lo, c->d_red_cnt + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToDevice, st));
+	// [r10] (a planning waits for phase A anyway: which blocks the trie gave up is known here, not only in the run after -- where none
+	// lacks class columns the reduced alignment may not be needed at all)
+	uint32_t *const h_have = c->h_red_pin + 4 * (size_t) nbk;
+	bool const ask_have = c->cls_on && !c->cls_every;
+	if (ask_have) HIP_TRY(c, hipMemcpyAsync(h_have + b_lo, c->d_cls_have + b_lo, (size_t) my_blocks * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(c, hipStreamSynchronize(st));
+	if (ask_have) c->cls_every = std::all_of(h_have + b_lo, h_have + b_hi, [](uint32_t h) { return h != 0u; });
 	if (M.force.size() != nbk) M.force.assign(nbk, 0);
 	in.m = m; in.nblocks = nbk; in.b_lo = b_lo; in.b_hi = b_hi;
 	in.cnt.assign(nbk, RED_NONE);
 	std::copy(h_cnt + b_lo, h_cnt + b_hi, in.cnt.begin() + b_lo);
 	in.force = M.force;
-	in.configs = red_configs(m, c->B, c->bsh, c->red_direct);
+	in.configs = red_configs(m, c->B, c->bsh, c->red_direct, red_cls_stageable(c) ? c->cls_ld : 0);
 	in.reduced_always = c->tune.reduced_always;
 	in.no_block_list = c->use_stream && !c->s2.T;
 	return FSEQ_OK;
+}
+
+// [r10] the configuration's launches take staged-column buffers of the class width (the plan in force says so, and this run stages)
+bool red_config_cls(fseq_ctx const *c, int config)
+{
+	return red_cls_stageable(c) && (size_t) config < c->red.cls_config.size() && c->red.cls_config[(size_t) config];
 }
 
 // FSEQ_DEBUG: what was planned
@@ -166,28 +230,24 @@ void red_report(fseq_ctx const *c, RedPlan const &P)
 		for (uint32_t i = 0; i < bin.count; ++i) sr += P.cnt[P.blocks[bin.first + i]];
 		ReducedSet rs;
 		(void) reduced_config(bin.config, &rs);
-		size_t const lds = rs.lds(c->B, red_symcap(m, c->bsh, rs, c->red_direct));
+		bool const cls = red_config_cls(c, bin.config);
+		size_t const lds = rs.lds(c->B, red_symcap(m, c->bsh, rs, c->red_direct, cls ? c->cls_ld : 0));
 		uint32_t const res = rs.prepare(lds) == hipSuccess ? rs.resident(lds) : 0u;
-		fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU)\n",
-		        rs.rows, (size_t) bin.count, (unsigned long long) (sr / bin.count), rs.T, rs.E, rs.values, lds, res);
+		uint32_t staged = 0;
+		for (uint32_t i = 0; i < bin.count; ++i) staged += P.from_cls[P.blocks[bin.first + i]];
+		fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU); columns: %s (%u of its blocks)\n",
+		        rs.rows, (size_t) bin.count, (unsigned long long) (sr / bin.count), rs.T, rs.E, rs.values, lds, res,
+		        c->red_direct ? "the alignment's own" : cls ? "phase A's class columns, staged by the kernel" : c->cls_on && c->tune.class_columns ? "the reduced alignment, gathered from the class columns" : "the reduced alignment, gathered from the alignment",
+		        c->red_direct ? bin.count : cls ? staged : bin.count - staged);
 	}
 }
 
-// stage 7: the reduced alignment and the reduced stride states, sized for the most representatives of a block
+// stage 7: the reduced stride states, sized for the most representatives of a block
 int red_size_buffers(fseq_ctx *c)
 {
 	FSEQ_LONG_LOCALS(c);
 	uint32_t const max_rows = c->red.plan.max_rows;
-	if (!c->red_direct)
-	{
-		// the reduced alignment (my columns only): column k at d_red_msa + k * red_ld
-		size_t const ldr = ((size_t) sym_bytes(max_rows ? max_rows : 1u, c->bsh) + 15) & ~size_t(15);
-		uint64_t const k_lo = (uint64_t) b_lo * c->B, k_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B);
-		size_t const need = (size_t) (k_hi - k_lo) * ldr + 64;
-		if ((rc = c->d_red_msa.ensure(c, need))) return rc;
-		c->red_ld = ldr;
-		c->d_red_msa.rebase((ptrdiff_t) ((size_t) k_lo * ldr));
-	}
+	// (the reduced alignment: red_reduce_msa, where a listed block reads it)
 	{
 		// the reduced states for pass 2: every 16 columns (32: streamed rows), rows for the most representatives of a block
 		uint32_t const stride_ = c->use_stream ? 32u : 16u;
@@ -210,6 +270,10 @@ int red_upload_blocks(fseq_ctx *c)
 	uint32_t *const h_blocks = c->h_red_pin + c->nblocks;
 	std::copy(blocks.begin(), blocks.end(), h_blocks);
 	HIP_TRY(c, hipMemcpyAsync(c->d_red_blocks, h_blocks, blocks.size() * 4, hipMemcpyHostToDevice, c->stream));
+	// ... and every block's source
+	uint32_t *const h_src = c->h_red_pin + 5 * (size_t) c->nblocks;
+	std::copy(c->red.plan.from_cls.begin(), c->red.plan.from_cls.end(), h_src);
+	HIP_TRY(c, hipMemcpyAsync(c->d_red_src, h_src, (size_t) c->nblocks * 4, hipMemcpyHostToDevice, c->stream));
 	return FSEQ_OK;
 }
 
@@ -246,6 +310,8 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	RedPlanInput in;
 	if ((rc = red_read_counts(c, in))) return rc;
 	c->red.plan = plan_reduced(in);
+	c->red.cls_config.assign(in.configs.size(), 0);
+	for (size_t i = 0; i < in.configs.size(); ++i) c->red.cls_config[i] = in.configs[i].cls ? 1 : 0;
 	RedPlan const &plan = c->red.plan;
 	c->tm.reduced_blocks = plan.reduced_blocks; c->tm.reduced_rows_mean = plan.rows_mean;
 	if (c->tune.debug) red_report(c, plan);
@@ -264,8 +330,7 @@ int red_plan(fseq_ctx *c, uint32_t X, bool *use)
 	}
 	if ((rc = red_size_buffers(c))) return rc;
 	if ((rc = red_upload_blocks(c))) return rc;
-	if (!c->red_direct)
-		red_reduce_msa(c);
+	if (!c->red_direct && (rc = red_reduce_msa(c))) return rc;
 	M.plan_holds = true; M.plan_X = X;
 	*use = true;
 	return FSEQ_OK;
@@ -292,14 +357,17 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 	// the representatives' symbols: the alignment's own columns (LDS-resident row counts), or the reduced alignment
 	ColumnsArgs C;
 	C.A = msa_args(c);
-	if (!c->red_direct) { C.A.msa = c->d_red_msa; C.A.ld = c->red_ld; }
+	if (!c->red_direct) { C.A.msa = c->d_red_msa; C.A.ld = c->red_ld; }      // (not allocated where every block stages its class columns)
 	C.lists = lists;
 	for (size_t i = 0; i < ls.size(); ++i)
 	{
 		ReducedSet rs;
 		(void) reduced_config(ls[i].config, &rs);
 		RedArgs RA = base;
-		RA.symcap = red_symcap(m, c->bsh, rs, c->red_direct);
+		// [r10] a configuration that takes the class width stages the class columns of its blocks that have them (and are planned so)
+		bool const cls = c->cls_staged && red_config_cls(c, ls[i].config);
+		RA.symcap = red_symcap(m, c->bsh, rs, c->red_direct, cls ? c->cls_ld : 0);
+		RA.cls_have = cls ? (uint32_t const *) c->d_cls_have : nullptr;
 		size_t const lds = rs.lds(c->B, RA.symcap);
 		HIP_TRY(c, rs.prepare(lds));
 		RA.blocks = base.blocks + ls[i].first;
@@ -393,6 +461,20 @@ int fseq_debug_red_plan(uint32_t m, uint32_t B, uint32_t bits, int direct, uint3
 		uint32_t const s[6] = {P.full_at, P.nfull, P.listed, P.max_rows, P.reduced_blocks, P.rows_mean};
 		std::copy(s, s + 6, summary);
 	}
+	return FSEQ_OK;
+}
+
+int fseq_debug_red_cls_direct(uint32_t m, uint32_t B, uint32_t bits, uint64_t cls_ld, uint32_t config, uint32_t resident_rows, uint32_t resident_cls,
+                              uint64_t *lds_rows, uint64_t *lds_cls, int *direct)
+{
+	if (!m || !B || (bits != 2 && bits != 4 && bits != 8) || !cls_ld || cls_ld > (1u << 20) || config >= (uint32_t) reduced_config_count()) return FSEQ_E_ARG;
+	uint32_t const bsh = bits == 2 ? 2u : bits == 4 ? 1u : 0u;
+	ReducedSet rs;
+	(void) reduced_config((int) config, &rs);
+	size_t const lr = rs.lds(B, red_symcap(m, bsh, rs, false)), lc = rs.lds(B, red_symcap(m, bsh, rs, false, (size_t) cls_ld));
+	if (lds_rows) *lds_rows = lr;
+	if (lds_cls) *lds_cls = lc;
+	if (direct) *direct = (lc == lr || red_cls_direct(lc, LDS_LIMIT, resident_rows, resident_cls)) ? 1 : 0;
 	return FSEQ_OK;
 }
 

@@ -17,7 +17,16 @@ constexpr uint8_t RED_FORCE_FULL = 1, RED_FORCE_WIDE = 2;    // RedPlanInput::fo
 
 // what planning needs of a configuration (ReducedSet, fseq_ctx.hpp).  fits: it fits this run's geometry (the LDS at this block
 // length and symbol width, the 16-bit value ids: columns_fit_reduced)
-struct RedConfig { uint32_t rows, values, T, E; bool ew, fits; };
+// cls [r10]: its staged-column buffers may be sized for a class column of phase A at no cost (red_cls_direct below)
+struct RedConfig { uint32_t rows, values, T, E; bool ew, fits; bool cls = false; };
+
+// [r10] The direct-or-gather rule of a configuration: it stages phase A's class columns itself where buffers of the class width
+// still fit the LDS and leave as many of its workgroups resident on a CU as the buffers sized for its rows do (lds_*: its LDS with
+// either buffer, resident_*: workgroups per CU at that size); else its blocks are gathered into the reduced alignment as before.
+inline bool red_cls_direct(size_t lds_cls, size_t lds_limit, uint32_t resident_rows, uint32_t resident_cls)
+{
+	return lds_cls <= lds_limit && resident_cls >= 1u && resident_cls >= resident_rows;
+}
 
 struct RedPlanInput {
 	uint32_t m = 0, nblocks = 0;
@@ -44,6 +53,11 @@ struct RedPlan {
 	std::vector<uint8_t> full;               // [block] 1: phase C runs the block on all rows
 	std::vector<int> config_of;              // [block] configuration of a reduced block's phase C (-1: none)
 	std::vector<int> config_snap_of;         // ... and of its sweeps in pass 2 (no lists: no list wave); also for a block that is `full`
+	// [r10] [block] 1: the block's columns are staged from phase A's class columns where it has them -- every configuration it runs on
+	// (phase C's unless `full`, pass 2's) takes the class width: the same source in both, the reduced stride states are in its ids;
+	// gathered: listed blocks without it (the reduced alignment is needed for them)
+	std::vector<uint8_t> from_cls;
+	uint32_t gathered = 0;
 	// what goes to d_red_blocks: [0, listed) every block with a count, ascending; then the configurations in use in ascending
 	// index, each with its blocks ascending (bins); then [full_at, full_at + nfull) the blocks on all rows, ascending
 	std::vector<uint32_t> blocks;
@@ -63,6 +77,7 @@ inline RedPlan plan_reduced(RedPlanInput const &in)
 	P.full.assign(nbk, 0);
 	P.config_of.assign(nbk, -1);
 	P.config_snap_of.assign(nbk, -1);
+	P.from_cls.assign(nbk, 0);
 	std::vector<uint8_t> usable(nconf), usable_snap(nconf);
 	for (size_t i = 0; i < nconf; ++i)
 	{
@@ -93,6 +108,14 @@ inline RedPlan plan_reduced(RedPlanInput const &in)
 		bool const full = r == RED_NONE || P.config_of[b] < 0 || in.force[b] == RED_FORCE_FULL || (uint64_t) r * 10u > (uint64_t) m * 7u;
 		if (full) { P.full[b] = 1; ++n_full; }
 		else { per[(size_t) P.config_of[b]].push_back(b); sum_rows += r; }
+		if (r != RED_NONE)
+		{
+			bool const c_ok = full || in.configs[(size_t) P.config_of[b]].cls;
+			bool const s_ok = P.config_snap_of[b] < 0 || in.configs[(size_t) P.config_snap_of[b]].cls;
+			// (a block no configuration sweeps is read by nobody)
+			P.from_cls[b] = (c_ok && s_ok && !(full && P.config_snap_of[b] < 0)) ? 1 : 0;
+			if (!P.from_cls[b] && !(full && P.config_snap_of[b] < 0)) ++P.gathered;
+		}
 	}
 	P.listed = (uint32_t) P.blocks.size();
 	P.reduced_blocks = my_blocks - n_full;

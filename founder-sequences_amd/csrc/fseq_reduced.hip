@@ -115,7 +115,7 @@ static bool launch_reduce_msa_lds(hipStream_t st, MsaArgs const &A, ReducedMsaAr
 		prepared = true;
 	}
 	// (a quarter of a block's columns per workgroup: the rows are read four times, the blocks' columns are enough workgroups)
-	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(D.nlisted, 4), dim3(1024), lds, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, D.blocks, colbytes, D.flag, D.want, D.pad, D.pad_per);
+	hipLaunchKernelGGL((k_reduce_msa_lds<BSH, R>), dim3(D.nlisted, 4), dim3(1024), lds, st, A.msa, A.ld, D.red, D.ldr, D.cnt, D.rows, D.cap, A.n, A.B, D.blocks, colbytes, D.flag, D.want, D.pad, D.pad_per, D.skip);
 	return true;
 }
 

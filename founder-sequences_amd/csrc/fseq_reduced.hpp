@@ -19,6 +19,16 @@
 // BASELINE C3: ~190 of 2,504 rows per block; C4: ~10,000 of 100,000; C5: ~550 of 10,000 (tests/proto_reduced.py is the
 // numpy statement of this file, tests/test_proto_reduced.py its proof against the oracle).
 //
+// Where the representatives' symbols come from (k_columns_red stages a packed column in LDS and reads a row's symbol at its id):
+//   * LDS-resident row counts: the alignment's own column, the ids are row ids (RedArgs::direct);
+//   * [r10] streamed rows, a block phase A's trie ranked: the block's CLASS COLUMN (fseq_blocktrie.hpp, phase 3), the ids are the key
+//     ranks leaf[i] -- cls[k][leaf[i]] == msa[k][rows[i]] -- translated once from the start state's representative indices; the
+//     reduced stride states and pass 2's class-table write are in the same ids.  Taken where every configuration the block runs
+//     on holds staged-column buffers of the class width at no cost in resident workgroups (red_cls_direct, fseq_redplan.hpp);
+//   * else the REDUCED ALIGNMENT d_red_msa (the ids are representative indices), gathered by k_reduce_msa_lds below from the class
+//     columns (a configuration that must not grow; FSEQ_CLASS_GATHER: every block) or from the alignment (a block the trie gave
+//     up; FSEQ_CLASS_COLUMNS=0: every block).  It is neither sized nor allocated when no listed block reads it.
+//
 // Pass 2 (update_pbwt_task::execute, update_pbwt_task.cc:13-35): the state at a column k inside a block is one CHAIN STEP
 // from the block's boundary state -- stable sort of a0 by the class of the row's key prefix [k0, k), range maxima of d0
 // inside a class, the divergence in front of a class for its first row -- and the classes and their divergences at k are
@@ -287,11 +297,13 @@ static __global__ __launch_bounds__(256) void k_reduce_msa(
 // is 25 KB on BASELINE C4.  On that source the kernel is bound by its LDS byte gathers (192 wave instructions a column whose
 // lanes fall on the banks at random), not by memory or its two barriers a column: 9.2 ms a step on BASELINE C4, where a form that
 // staged eight class columns per barrier through registers and stored words took 10.0 ms and was not kept.
+// [r10] On BASELINE C4 that pass is gone: every configuration in use there stages the class columns itself (skip: the blocks that do).
 template <int BSH, int R>
 __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 	uint8_t const *__restrict__ msa, size_t ld, uint8_t *__restrict__ red, size_t ldr, uint32_t const *__restrict__ cnt,
 	uint32_t const *__restrict__ rows, uint32_t cap, uint64_t n, uint32_t B, uint32_t const *__restrict__ blocks, uint32_t colbytes,
-	uint32_t const *__restrict__ flag /* per block, or nullptr: every block */, uint32_t want, uint32_t const *__restrict__ pad, size_t pad_per)
+	uint32_t const *__restrict__ flag /* per block, or nullptr: every block */, uint32_t want, uint32_t const *__restrict__ pad, size_t pad_per,
+	uint32_t const *__restrict__ skip /* per block, or nullptr: not the blocks with skip[block] (the column kernel stages their class columns itself) */)
 {
 	constexpr uint32_t RPB = 1u << BSH, BITS = 8u >> BSH, CMASK = (1u << BITS) - 1u;
 	constexpr uint32_t NOUT = (12288u / RPB + 1023u) / 1024u;          // output bytes per thread: 12,288 representatives at most
@@ -301,6 +313,7 @@ __global__ __launch_bounds__(1024) void k_reduce_msa_lds(
 	uint32_t const Lr = cnt[blk];
 	if (Lr == RED_NONE) return;
 	if (flag && flag[blk] != want) return;
+	if (skip && skip[blk]) return;
 	uint32_t const tid = threadIdx.x;
 	uint32_t const nq = (Lr + RPB - 1u) >> BSH;
 	uint64_t const k0 = (uint64_t) blk * B;

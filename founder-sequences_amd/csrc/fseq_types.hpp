@@ -176,6 +176,7 @@ struct ReducedMsaArgs {
 	uint32_t want = 0;
 	uint32_t const *pad = nullptr;       // the row whose symbol fills the last byte behind the last representative: pad[block * pad_per] (nullptr: row 0)
 	size_t pad_per = 0;
+	uint32_t const *skip = nullptr;      // per block, or nullptr: the blocks with skip[block] are left out (from the class columns: the column kernel stages theirs itself)
 };
 
 // phase A's class columns (k_blocktrie, fseq_blocktrie.hpp), the other source of the reduced alignment: column k at cls + k * ldc holds at row rho the
@@ -208,6 +209,14 @@ struct RedArgs {
 	uint32_t symcap = 0;                // bytes of each of the two staged-column buffers in LDS (whole kilobytes)
 	uint32_t const *rank = nullptr;     // direct, pass 2: [block][m_true] block-key rank of every row (leaf[] is not used)
 	uint32_t *any_invalid = nullptr;    // one word: set with invalid[b]
+	// [r10] phase A's class columns staged directly (streamed rows; a launch whose staged-column buffers hold a class column: cls_have
+	// set): a block with cls_src[b] (the plan: both of its configurations take the class width) and cls_have[b] (this run's phase A
+	// wrote its columns) stages column k from cls_msa + k * cls_ld, ceil16(sym_bytes(nkeys[b])) bytes of it, and the ids of its order are
+	// leaf[] -- cls[k][leaf[i]] == msa[k][rows[i]] -- so a[] is translated once at the block's first column and the reduced stride
+	// states hold leaf ids; every other block reads the reduced alignment by representative index as before
+	uint32_t const *cls_have = nullptr, *cls_src = nullptr, *nkeys = nullptr;
+	uint8_t const *cls_msa = nullptr;
+	size_t cls_ld = 0;
 	// pass 2: instead of lists, the class tables at the task columns of the block
 	uint32_t const *wg_tasks = nullptr; // [workgroup][3] {first task, tasks, column of the start state (the block's first column, or a stride state's)}
 	// the reduced states phase C drops every ss_stride columns (the state at column q * ss_stride at [q][ss_cap], where that

@@ -96,6 +96,22 @@ int  fseq_debug_pass2_paths(fseq_ctx *ctx, uint32_t *by_runs, uint32_t *by_sort,
 int  fseq_debug_class_columns(fseq_ctx *ctx, uint32_t *from_classes, uint32_t *from_alignment, uint32_t block, uint32_t *have, uint32_t *nkeys,
                               uint64_t *ldc, uint8_t *out, uint64_t out_bytes);
 
+/* How the listed blocks of the last run (the blocks with representatives; streamed rows behind the reduced phase C) came by their
+ * columns: *staged blocks had phase A's class columns staged by the reduced column kernel itself, *gathered blocks read the reduced
+ * alignment (gathered from the class columns or from the alignment: fseq_debug_class_columns tells which).  A block is staged where it
+ * has class columns and every configuration it runs on takes staged-column buffers of the class width at no cost in LDS or resident
+ * workgroups; never with FSEQ_CLASS_GATHER=1 or FSEQ_CLASS_COLUMNS=0.  block != UINT32_MAX: *block_staged for that block as well.
+ * Both zero where the run built neither (LDS-resident rows, no representatives). */
+int  fseq_debug_column_sources(fseq_ctx *ctx, uint32_t *staged, uint32_t *gathered, uint32_t block, uint32_t *block_staged);
+
+/* The direct-or-gather rule of one configuration of the reduced column kernel (red_cls_direct, csrc/fseq_redplan.hpp), as a run of m
+ * rows in blocks of B columns at `bits` bits a symbol with class columns of cls_ld bytes applies it -- host arithmetic, no device:
+ * *lds_rows / *lds_cls the configuration's LDS with staged-column buffers for its rows / of the class width, *direct whether it stages
+ * the class columns itself given the workgroups per CU the device reports at either size (resident_rows, resident_cls: the run asks
+ * the occupancy query).  FSEQ_E_ARG: m, B, cls_ld >= 1, bits 2 / 4 / 8, config below the number fseq_debug_red_plan reports. */
+int  fseq_debug_red_cls_direct(uint32_t m, uint32_t B, uint32_t bits, uint64_t cls_ld, uint32_t config, uint32_t resident_rows, uint32_t resident_cls,
+                               uint64_t *lds_rows, uint64_t *lds_cls, int *direct);
+
 /* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
  * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
  * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
