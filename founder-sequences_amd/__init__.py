@@ -103,11 +103,13 @@ EXPORTS = [
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
     "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
+    "fseq_write_segments_device", "fseq_random_join_classes_host", "fseq_debug_segments_file", "fseq_debug_random_path",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct"]
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
+                 "fseq_debug_segments_file", "fseq_debug_random_path"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -220,6 +222,10 @@ def load_library():
     L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.fseq_debug_red_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.c_int] + [vp] * 11
+    L.fseq_write_segments_device.argtypes = [vp, C.c_int, C.c_char_p]
+    L.fseq_random_join_classes_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, vp]
+    L.fseq_debug_segments_file.argtypes = [vp] + [C.POINTER(u64)] * 4
+    L.fseq_debug_random_path.argtypes = [vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -505,6 +511,21 @@ def random_join_host(m, max_segment_size, lb, rb, a, d, seed):
     return perm
 
 
+def random_join_classes_host(m, max_segment_size, count, rep, size, seed):
+    """The random joiner from the runs on, on caller-supplied class tables (host only): count[s] classes of segment s in pBWT
+    order, rep / size [segments, max_segment_size] their first rows and row counts.  What join_random runs behind its device front."""
+    L = load_library()
+    count = np.ascontiguousarray(count, dtype=np.uint32)
+    rep = np.ascontiguousarray(rep, dtype=np.uint32)
+    size = np.ascontiguousarray(size, dtype=np.uint32)
+    assert rep.shape == (len(count), max_segment_size) and size.shape == rep.shape
+    perm = np.zeros((len(count), max_segment_size), dtype=np.uint32)
+    rc = L.fseq_random_join_classes_host(m, max_segment_size, len(count), count.ctypes.data, rep.ctypes.data, size.ctypes.data, seed, perm.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return perm
+
+
 class SegmentationContext:
     """Mirror of segmentation_lp_context / segmentation_sp_context behind the C ABI.
 
@@ -749,6 +770,23 @@ class SegmentationContext:
         assert msa.dtype == np.uint8 and msa.flags["C_CONTIGUOUS"] and msa.shape == (self.m, self.n)
         rows = (C.c_void_p * self.m)(*[msa.ctypes.data + r * msa.strides[0] for r in range(self.m)])
         self._check(self.L.fseq_write_segments(self.h, rows, joining, path.encode() if path else None))
+
+    def write_segments_device(self, joining, path):
+        """--output-segments from the alignment and the boundary states resident on the device (no host rows, no copy of the
+        boundary states): the bytes write_segments writes when given the rows of the alignment the context holds."""
+        self._check(self.L.fseq_write_segments_device(self.h, joining, path.encode() if path else None))
+
+    def segments_file_stats(self):
+        """The last file write_segments_device wrote: {batches, bytes, longest_line, lines} (header included, a line with its newline)."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self.L.fseq_debug_segments_file(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("batches", "bytes", "longest_line", "lines"), (x.value for x in v)))
+
+    def random_path(self):
+        """Which way the last join_random() went: 0 the host joiner, 1 the class tables from the device."""
+        path = C.c_int()
+        self._check(self.L.fseq_debug_random_path(self.h, C.byref(path)))
+        return path.value
 
     def write_founders_device(self, permutations, path):
         """--output-founders from the alignment resident on the device (no host rows)."""

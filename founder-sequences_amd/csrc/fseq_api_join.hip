@@ -11,6 +11,7 @@
 #include "fseq_joinprep.hpp"
 #include "fseq_joinbip.hpp"
 #include "fseq_joinbipw.hpp"
+#include "fseq_segfile.hpp"
 
 using namespace fseq;
 
@@ -155,6 +156,212 @@ static int join_bipartite_wide(fseq_ctx *c, uint32_t *permutations, bool *done)
 	double const t1 = now_ms();
 	c->jp = fseq_join_profile{0.0, 0.0, 0.0, t1 - t0, t1 - t0, (uint64_t) S * X * 4ull + (uint64_t) S * 4ull};
 	*done = true;
+	return FSEQ_OK;
+}
+
+// lb of a merged segment = rb of the one in front: what k_join_classes(_wide) goes by
+static bool segments_tile(fseq_ctx const *c)
+{
+	for (size_t i = 0; i < c->segments.size(); ++i)
+		if (c->segments[i].lb != (i ? c->segments[i - 1].rb : 0u)) return false;
+	return true;
+}
+
+// The class tables of every merged segment (k_join_classes_wide) for the callers that need nothing else of the boundary
+// states: fseq_join_random's device front and fseq_write_segments_device.  Temporaries of one call.
+struct ClassTables {
+	size_t S = 0, m = 0;
+	uint32_t X = 0;
+	DevTemp<uint16_t> d_of;
+	DevTemp<uint32_t> d_rep, d_size, d_count, d_start;
+	DevTemp<uint64_t> d_lb, d_rb;
+	explicit ClassTables(fseq_ctx *c) : d_of(c), d_rep(c), d_size(c), d_count(c), d_start(c), d_lb(c), d_rb(c) {}
+	int alloc(size_t S_, size_t m_, uint32_t X_)
+	{
+		S = S_; m = m_; X = X_;
+		int rc;
+		if ((rc = d_of.alloc(S * m)) || (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) ||
+		    (rc = d_start.alloc(S * ((size_t) X + 1))) || (rc = d_lb.alloc(S)) || (rc = d_rb.alloc(S)))
+			return rc;
+		return FSEQ_OK;
+	}
+	// count: the classes of every segment, on the host; *sane: every one of them in [1, X]
+	int run(fseq_ctx *c, std::vector<uint32_t> &count, bool *sane)
+	{
+		hipStream_t st = c->stream;
+		std::vector<uint64_t> b(2 * S);
+		for (size_t i = 0; i < S; ++i) { b[i] = c->segments[i].lb; b[S + i] = c->segments[i].rb; }
+		hipError_t e = hipMemcpyAsync(d_lb, b.data(), S * 8, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(d_rb, b.data() + S, S * 8, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, S * X * 4, st);
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "class tables", e);
+		hipLaunchKernelGGL(k_join_classes_wide, dim3((uint32_t) S), dim3(JW_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count, d_start);
+		count.resize(S);
+		e = hipMemcpyAsync(count.data(), d_count, S * 4, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);           // (b and count are read and written to here)
+		if (e == hipSuccess) e = hipGetLastError();
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "class tables", e);
+		*sane = true;
+		for (size_t i = 0; *sane && i < S; ++i) *sane = count[i] >= 1 && count[i] <= X;
+		return FSEQ_OK;
+	}
+	void release() { d_of.release(d_of.c); d_rep.release(d_rep.c); d_size.release(d_size.c); d_count.release(d_count.c); d_start.release(d_start.c); d_lb.release(d_lb.c); d_rb.release(d_rb.c); }
+};
+
+static char const SEGFILE_HEADER_BIP[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE\tSEQUENCES\tCOPIED_FROM\n";
+static char const SEGFILE_HEADER_COPIES[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE_NUMBER\tCOPY_NUMBER\tSUBSEQUENCE\n";
+static constexpr uint64_t SEGFILE_BATCH_BYTES = 256ull << 20;      // (what fseq_write_founders_device takes a batch)
+
+// The lines of the segments file behind its header, from the device (fseq_segfile.hpp).  The file is opened once everything that
+// can refuse has passed: the class counts, the allocations of the tables.
+static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *path, char const *header)
+{
+	(void) hipSetDevice(c->p.device);
+	hipStream_t st = c->stream;
+	size_t const m = c->p.m, S = c->segments.size();
+	uint32_t const X = c->res.max_segment_size;
+	size_t const X1 = (size_t) X + 1;
+	ClassTables T(c);
+	DevTemp<uint16_t> d_tpos(c), d_src(c);
+	DevTemp<uint32_t> d_min(c), d_reprow(c), d_members(c);
+	DevTemp<uint2> d_rline(c);
+	DevTemp<uint8_t> d_pool(c), d_lut(c), d_out(c);
+	DevTemp<uint64_t> d_ppos(c), d_loff(c), d_segoff(c);
+	int rc;
+	if ((rc = T.alloc(S, m, X))) return rc;
+	if (bip && ((rc = d_tpos.alloc(S * X)) || (rc = d_src.alloc(S * X)) || (rc = d_min.alloc(S * X)) || (rc = d_reprow.alloc(S * X)))) return rc;
+	if ((rc = d_ppos.alloc(S + 1)) || (rc = d_loff.alloc(S * X1)) || (rc = d_segoff.alloc(S + 1)) || (rc = d_lut.alloc(256))) return rc;
+	std::vector<uint32_t> count;
+	bool sane = false;
+	if ((rc = T.run(c, count, &sane))) return rc;
+	if (!sane) return fail(c, FSEQ_E_UNSUPPORTED, "the class tables of the device hold a class count outside [1, max_segment_size] (write the segments from host rows: fseq_write_segments)");
+	hipError_t e = hipSuccess;
+	if (bip)
+	{
+		size_t const lds_texts = bip_texts_wide_lds_bytes(X);
+		e = allow_lds(k_bip_texts_wide, lds_texts);
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "segments file preparation", e);
+		hipLaunchKernelGGL(k_bip_minrow_wide, dim3((uint32_t) S), dim3(JBW_T), 0, st, T.d_of, (uint32_t) m, X, d_min);
+		hipLaunchKernelGGL(k_bip_texts_wide, dim3((uint32_t) S), dim3(JBW_T), lds_texts, st, T.d_count, T.d_size, d_min, (uint32_t) m, X, d_tpos, d_src, d_reprow);
+	}
+	else
+	{
+		// the lines of a segment in the order prepare_copy_numbers(..., false) leaves them: the host's own std::sort on the
+		// vector the host writer sorts, built from the device's tables
+		std::vector<uint32_t> rep(S * X), size(S * X);
+		e = hipMemcpyAsync(rep.data(), T.d_rep, S * X * 4, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(size.data(), T.d_size, S * X * 4, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "segments file preparation", e);
+		release_all(c, T.d_of, T.d_rep, T.d_size, T.d_start);      // (the random file needs the counts only from here on)
+		std::vector<uint2> rline(S * X, make_uint2(0u, 0u));
+		for (size_t s = 0; s < S; ++s)
+		{
+			auto const cn = copy_numbers_from_runs(runs_from_classes(count[s], rep.data() + s * X, size.data() + s * X), X, false);
+			uint32_t prev = 0;
+			for (size_t j = 0; j < cn.size(); ++j) { rline[s * X + j] = make_uint2(cn[j].substring_idx, cn[j].copy_number - prev); prev = cn[j].copy_number; }
+		}
+		if ((rc = d_rline.alloc(S * X))) return rc;
+		HIP_TRY(c, hipMemcpy(d_rline, rline.data(), S * X * sizeof(uint2), hipMemcpyHostToDevice));
+	}
+	// the prefixes: write_segments_impl's "%zu\t%llu\t%llu\t%u\t"
+	std::string pool;
+	std::vector<uint64_t> ppos(S + 1);
+	for (size_t s = 0; s < S; ++s)
+	{
+		char buf[96];
+		ppos[s] = pool.size();
+		int const len = snprintf(buf, sizeof(buf), "%zu\t%llu\t%llu\t%u\t", s, (unsigned long long) c->segments[s].lb, (unsigned long long) c->segments[s].rb, c->segments[s].segment_size);
+		pool.append(buf, (size_t) len);
+	}
+	ppos[S] = pool.size();
+	if ((rc = d_pool.alloc(pool.size()))) return rc;
+	e = hipMemcpyAsync(d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_ppos, ppos.data(), (S + 1) * 8, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_lut, c->code_to_byte, 256, hipMemcpyHostToDevice, st);
+	size_t const lds_lines = segfile_lines_lds_bytes(X, bip), lds_members = segfile_members_lds_bytes(X), lds_write = segfile_write_lds_bytes(X, bip);
+	if (e == hipSuccess && bip) e = allow_lds(k_segfile_lines<true>, lds_lines);
+	if (e == hipSuccess && bip) e = allow_lds(k_segfile_members, lds_members);
+	if (e == hipSuccess && bip) e = allow_lds(k_segfile_write<true>, lds_write);
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "segments file preparation", e);
+	SegFileArgs A{};
+	A.seg_lb = T.d_lb; A.seg_rb = T.d_rb; A.pool = d_pool; A.ppos = d_ppos; A.count = T.d_count;
+	A.m = (uint32_t) m; A.X = X; A.S = (uint32_t) S;
+	A.of_row = T.d_of; A.tpos = d_tpos; A.src = d_src; A.reprow = d_reprow; A.rline = d_rline;
+	// every line's length, scanned: inside the segments, then over them
+	if (bip) hipLaunchKernelGGL(k_segfile_lines<true>, dim3((uint32_t) S), dim3(SF_T), lds_lines, st, A, (uint64_t *) d_loff);
+	else hipLaunchKernelGGL(k_segfile_lines<false>, dim3((uint32_t) S), dim3(SF_T), 0, st, A, (uint64_t *) d_loff);
+	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, d_loff, (uint32_t) S, X, d_segoff);
+	std::vector<uint64_t> loff, segoff(S + 1);
+	try { loff.resize(S * X1); } catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "segments file: the line offsets on the host"); }
+	e = hipMemcpyAsync(loff.data(), d_loff, S * X1 * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(segoff.data(), d_segoff, (S + 1) * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "segments file: line lengths", e);
+	// batches of whole lines in file order, FSEQ_SEGFILE_BATCH bytes at most; a line above the budget is a batch of its own
+	uint64_t const budget = c->tune.segfile_batch > 0 ? (uint64_t) c->tune.segfile_batch : SEGFILE_BATCH_BYTES;
+	std::vector<SegFileBatch> batches;
+	uint64_t longest = 0, lines = 0, most_bytes = 0, most_segs = 0;
+	{
+		SegFileBatch cur{};
+		bool open = false;
+		auto close = [&]() {
+			batches.push_back(cur);
+			most_bytes = std::max(most_bytes, cur.bytes);
+			most_segs = std::max<uint64_t>(most_segs, cur.s1 - cur.s0 + 1);
+			open = false;
+		};
+		for (size_t s = 0; s < S; ++s)
+		{
+			uint64_t const *lo = loff.data() + s * X1;
+			uint32_t const nl = bip ? X : count[s];
+			for (uint32_t j = 0; j < nl; ++j)
+			{
+				uint64_t const len = lo[j + 1] - lo[j];
+				if (open && cur.bytes + len > budget) close();
+				if (!open) { cur = SegFileBatch{(uint32_t) s, (uint32_t) s, j, j, segoff[s] + lo[j], 0}; open = true; }
+				cur.s1 = (uint32_t) s; cur.j_hi = j + 1; cur.bytes += len;
+				longest = std::max(longest, len);
+				++lines;
+			}
+		}
+		if (open) close();
+	}
+	if ((rc = d_out.alloc((size_t) most_bytes))) return rc;
+	if (bip && (rc = d_members.alloc((size_t) most_segs * m))) return rc;
+	uint8_t *h_out = nullptr;
+	if (hipHostMalloc(reinterpret_cast<void **>(&h_out), std::max<size_t>((size_t) most_bytes, 1), hipHostMallocDefault) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		return fail(c, FSEQ_E_OOM, "segments output buffer");
+	}
+	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+	if (!f) { (void) hipHostFree(h_out); return fail(c, FSEQ_E_ARG, "cannot open the segments output file"); }
+	bool ok = fputs(header, f) >= 0, hip_ok = true;
+	for (size_t b = 0; b < batches.size() && ok && hip_ok; ++b)
+	{
+		SegFileBatch const &B = batches[b];
+		uint32_t const nseg = B.s1 - B.s0 + 1;
+		if (bip)
+		{
+			hipLaunchKernelGGL(k_segfile_members, dim3(nseg), dim3(SF_T), lds_members, st, A, (uint32_t const *) T.d_size, B.s0, (uint32_t *) d_members);
+			hipLaunchKernelGGL(k_segfile_write<true>, dim3(nseg), dim3(SF_T), lds_write, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
+			                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) d_members, (uint8_t *) d_out);
+		}
+		else
+			hipLaunchKernelGGL(k_segfile_write<false>, dim3(nseg), dim3(SF_T), 0, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
+			                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) nullptr, (uint8_t *) d_out);
+		hip_ok = hipMemcpyAsync(h_out, d_out, (size_t) B.bytes, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
+		if (hip_ok) ok = fwrite(h_out, 1, (size_t) B.bytes, f) == (size_t) B.bytes;
+	}
+	if (fflush(f) != 0) ok = false;
+	if (f != stdout) fclose(f);
+	(void) hipHostFree(h_out);
+	if (!hip_ok) return fail(c, FSEQ_E_HIP, "writing the segments from the device failed");
+	if (!ok) return fail(c, FSEQ_E_ARG, "writing the segments output file failed");
+	uint64_t const hl = strlen(header);
+	c->segfile = fseq_ctx::SegFileStats{true, (uint64_t) batches.size(), hl + segoff[S], std::max(hl, longest), lines + 1};
 	return FSEQ_OK;
 }
 
@@ -369,9 +576,51 @@ int fseq_join_bipartite(fseq_ctx *c, uint32_t *permutations)
 	return FSEQ_OK;
 }
 
+int fseq_debug_random_path(fseq_ctx *c, int *path)
+{
+	if (!c || !path) return FSEQ_E_ARG;
+	if (c->rand_path < 0) return fail(c, FSEQ_E_ARG, "no fseq_join_random has finished on this context since its input was set");
+	*path = c->rand_path;
+	return FSEQ_OK;
+}
+
 int fseq_join_random(fseq_ctx *c, uint32_t seed, uint32_t *permutations)
 {
 	if (!c || !permutations) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to join (segmentation failed or was not run)");
+	// the class tables where the boundary states are (k_join_classes_wide): the joiner reads nothing of a boundary state but
+	// the classes' first rows and sizes, S x X x 8 + S x 4 bytes against S x m x 8.  No size threshold: the front moves at
+	// most X / m of the bytes and runs one kernel.  Falls through to the host joiner as the other device fronts do.
+	uint32_t const X = c->res.max_segment_size;
+	if (segments_tile(c) && !c->sh.on && X >= 1 && X <= 0xFFFFu && c->p.m <= 0x7FFFFFFFull && c->segments.size() <= 0x7FFFFFFFull && !c->tune.join_host)
+	{
+		(void) hipSetDevice(c->p.device);
+		double const t0 = now_ms();
+		size_t const S = c->segments.size();
+		ClassTables T(c);
+		std::vector<uint32_t> count;
+		bool sane = false;
+		int rc = T.alloc(S, c->p.m, X);
+		if (FSEQ_OK == rc) rc = T.run(c, count, &sane);
+		if (rc && rc != FSEQ_E_OOM) return rc;
+		if (FSEQ_E_OOM == rc) c->err.clear();                      // (the host joiner needs no device memory)
+		else if (sane)
+		{
+			std::vector<uint32_t> rep(S * X), size(S * X);
+			hipError_t e = hipMemcpyAsync(rep.data(), T.d_rep, S * X * 4, hipMemcpyDeviceToHost, c->stream);
+			if (e == hipSuccess) e = hipMemcpyAsync(size.data(), T.d_size, S * X * 4, hipMemcpyDeviceToHost, c->stream);
+			if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+			T.release();                                           // (not held through the host's part)
+			if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "random join preparation", e);
+			double const t1 = now_ms();
+			random_join_classes(X, S, count.data(), rep.data(), size.data(), seed, permutations);
+			double const t2 = now_ms();
+			c->jp = fseq_join_profile{t1 - t0, 0.0, 0.0, t2 - t1, t2 - t0, (uint64_t) S * X * 8ull + (uint64_t) S * 4ull};
+			c->rand_path = 1;
+			return FSEQ_OK;
+		}
+	}
 	std::vector<uint32_t> A, D;
 	std::vector<JoinSegment> segs;
 	int const rc = fetch_boundary_states(c, A, D, segs);
@@ -379,6 +628,17 @@ int fseq_join_random(fseq_ctx *c, uint32_t seed, uint32_t *permutations)
 	double const t0 = now_ms();
 	random_join(c->p.m, c->res.max_segment_size, segs, A.data(), D.data(), seed, permutations);
 	c->jp.ms_draw = now_ms() - t0; c->jp.ms_total = c->jp.ms_d2h + c->jp.ms_draw;
+	c->rand_path = 0;
+	return FSEQ_OK;
+}
+
+int fseq_random_join_classes_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint32_t const *count, uint32_t const *rep,
+                                  uint32_t const *size, uint32_t seed, uint32_t *permutations)
+{
+	if (!m || !max_segment_size || !count || !rep || !size || !permutations) return FSEQ_E_ARG;
+	for (uint64_t s = 0; s < n_segments; ++s)
+		if (count[s] < 1 || count[s] > max_segment_size) return FSEQ_E_ARG;      // (the slots are filled class by class: a table that does not fit them is no table)
+	random_join_classes(max_segment_size, n_segments, count, rep, size, seed, permutations);
 	return FSEQ_OK;
 }
 
@@ -435,6 +695,51 @@ int fseq_write_segments_host(fseq_ctx *c, uint8_t const *const *rows, int joinin
 		for (size_t i = 0; i < segs.size(); ++i) { segs[i].lb = c->segments[i].lb; segs[i].rb = c->segments[i].rb; }
 	}
 	return write_segments_impl(c, rows, joining, a, d, segs, path);
+}
+
+// --output-segments from the alignment and the boundary states the device holds (fseq_segfile.hpp): no host rows, no copy of
+// the boundary states.  The bytes are write_segments_impl's.
+int fseq_write_segments_device(fseq_ctx *c, int joining, char const *path)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	if (joining != FSEQ_JOIN_GREEDY && joining != FSEQ_JOIN_BIPARTITE && joining != FSEQ_JOIN_RANDOM)
+		return fail(c, FSEQ_E_ARG, "unknown joining method (FSEQ_JOIN_GREEDY, FSEQ_JOIN_BIPARTITE or FSEQ_JOIN_RANDOM)");
+	if (FSEQ_JOIN_GREEDY == joining)
+	{
+		// (the copy-number matrix of greedy joining is empty: the header alone)
+		FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+		if (!f) return fail(c, FSEQ_E_ARG, "cannot open the segments output file");
+		bool ok = fputs(SEGFILE_HEADER_COPIES, f) >= 0;
+		if (fflush(f) != 0) ok = false;
+		if (f != stdout) fclose(f);
+		if (!ok) return fail(c, FSEQ_E_ARG, "writing the segments output file failed");
+		uint64_t const hl = strlen(SEGFILE_HEADER_COPIES);
+		c->segfile = fseq_ctx::SegFileStats{true, 0, hl, hl, 1};
+		return FSEQ_OK;
+	}
+	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to write (segmentation failed or was not run)");
+	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: a rank holds its own columns and boundary states only (collect them and use fseq_write_segments_host)");
+	if (!segments_tile(c)) return fail(c, FSEQ_E_UNSUPPORTED, "the merged segments do not tile the columns (write the segments from host rows: fseq_write_segments)");
+	bool const bip = FSEQ_JOIN_BIPARTITE == joining;
+	uint32_t const X = c->res.max_segment_size;
+	if (X < 1) return fail(c, FSEQ_E_ARG, "no segments to write");
+	if (bip && X > JBW_MAX_TEXTS) return fail(c, FSEQ_E_UNSUPPORTED, "bipartite-matching segments file from the device: more than 4,096 texts a segment (write it from host rows: fseq_write_segments)");
+	if (!bip && X > 0xFFFFu) return fail(c, FSEQ_E_UNSUPPORTED, "random-joining segments file from the device: more than 65,535 classes a segment (write it from host rows: fseq_write_segments)");
+	if (c->p.m > 0x7FFFFFFFull || c->segments.size() > 0x7FFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "segments file from the device: 2^31 rows or segments or more");
+	return write_segments_device_lines(c, bip, path, bip ? SEGFILE_HEADER_BIP : SEGFILE_HEADER_COPIES);
+}
+
+int fseq_debug_segments_file(fseq_ctx *c, uint64_t *batches, uint64_t *bytes, uint64_t *longest_line, uint64_t *lines)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!c->segfile.have) return fail(c, FSEQ_E_ARG, "no fseq_write_segments_device has finished on this context");
+	if (batches) *batches = c->segfile.batches;
+	if (bytes) *bytes = c->segfile.bytes;
+	if (longest_line) *longest_line = c->segfile.longest_line;
+	if (lines) *lines = c->segfile.lines;
+	return FSEQ_OK;
 }
 
 static int write_segments_impl(fseq_ctx *c, uint8_t const *const *rows, int joining, uint32_t const *A_, uint32_t const *D_,

@@ -360,10 +360,12 @@ inline std::vector<SubstringCopyNumber> unique_substring_runs(uint32_t const m, 
 
 // join_context::join_segments_and_output, the copy-number preparation for the non-greedy joiners
 // (join_context.cc:63-126).  Returns the runs with copy_number turned into a cumulative sum.
-inline std::vector<SubstringCopyNumber> prepare_copy_numbers(
-	uint32_t const m, uint32_t const max_segment_size, uint64_t const lb, uint32_t const *a, uint32_t const *d, bool const bipartite)
+// ... from the runs on: what the device's class tables (rep, size, count of k_join_classes_wide, fseq_joinprep.hpp) feed as
+// well -- the same std::sort on the same vector, so the order of equal copy numbers is the host joiner's whatever the
+// standard library makes of it.
+inline std::vector<SubstringCopyNumber> copy_numbers_from_runs(
+	std::vector<SubstringCopyNumber> cn, uint32_t const max_segment_size, bool const bipartite)
 {
-	std::vector<SubstringCopyNumber> cn = unique_substring_runs(m, lb, a, d);
 	size_t const substring_count = cn.size();
 	for (uint32_t i = 0; i < cn.size(); ++i) cn[i].string_idx = i;                 // :82-86
 	if (!bipartite)
@@ -385,6 +387,20 @@ inline std::vector<SubstringCopyNumber> prepare_copy_numbers(
 	return cn;
 }
 
+inline std::vector<SubstringCopyNumber> prepare_copy_numbers(
+	uint32_t const m, uint32_t const max_segment_size, uint64_t const lb, uint32_t const *a, uint32_t const *d, bool const bipartite)
+{
+	return copy_numbers_from_runs(unique_substring_runs(m, lb, a, d), max_segment_size, bipartite);
+}
+
+// the runs of one segment from class tables: class c = (rep[c], size[c]), in pBWT order
+inline std::vector<SubstringCopyNumber> runs_from_classes(uint32_t const count, uint32_t const *rep, uint32_t const *size)
+{
+	std::vector<SubstringCopyNumber> out(count);
+	for (uint32_t c = 0; c < count; ++c) out[c] = SubstringCopyNumber{rep[c], size[c], 0u};
+	return out;
+}
+
 // join_context::join_random_order_and_output (join_context.cc:259-289): slots filled class by class, then
 // one std::shuffle per segment from a single std::mt19937(seed).
 inline void random_join(
@@ -404,6 +420,25 @@ inline void random_join(
 			for (; pos < x.copy_number; ++pos) perm[pos] = x.substring_idx;
 		std::shuffle(perm, perm + X, urbg);
 		if (copy_numbers_out) copy_numbers_out->push_back(std::move(cn));
+	}
+}
+
+// random_join's part behind the runs, on class tables built elsewhere (on the device: k_join_classes_wide): count[s] classes of
+// segment s with rep / size at [s * X + c].  The same vectors through the same calls as random_join: the same permutations.
+inline void random_join_classes(
+	uint32_t const max_segment_size, size_t const S, uint32_t const *count, uint32_t const *rep, uint32_t const *size,
+	uint32_t const seed, uint32_t *permutations)
+{
+	size_t const X = max_segment_size;
+	std::mt19937 urbg(seed);
+	for (size_t s = 0; s < S; ++s)
+	{
+		auto const cn = copy_numbers_from_runs(runs_from_classes(count[s], rep + s * X, size + s * X), max_segment_size, false);
+		uint32_t *perm = permutations + s * X;
+		size_t pos = 0;
+		for (auto const &x : cn)
+			for (; pos < x.copy_number; ++pos) perm[pos] = x.substring_idx;
+		std::shuffle(perm, perm + X, urbg);
 	}
 }
 

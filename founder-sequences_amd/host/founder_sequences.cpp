@@ -522,7 +522,18 @@ int main(int argc, char **argv)
 		// header is written (join_context.cc:57-61, greedy_matcher.cc:468-476)
 		std::cerr << "Outputting the segments…" << std::endl;
 		int const how = joining::GREEDY == join ? FSEQ_JOIN_GREEDY : (joining::RANDOM == join ? FSEQ_JOIN_RANDOM : FSEQ_JOIN_BIPARTITE);
-		if (remove_identity)
+		// (not sharded: the lines are put together where the alignment and the boundary states already are, on the device --
+		// no rows on the host needed, so --remove-identity-columns has its reduced rows without squeezing them here; what the
+		// device writer does not serve goes to the host writer while the rows are on the host; under --upload-memory, which
+		// reaches this point with greedy joining only, there are none)
+		bool from_device = false;
+		if (!sharded)
+		{
+			rc = fseq_write_segments_device(ctx, how, out_segments);
+			from_device = FSEQ_OK == rc;
+			if (!from_device && !(FSEQ_E_UNSUPPORTED == rc && !upload_given)) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+		}
+		if (!from_device && remove_identity)
 		{
 			// the segments are in reduced co-ordinates: the rows without their identity columns, as the chain of tools has them
 			std::vector<uint8_t> mask(seq_length);
@@ -535,8 +546,9 @@ int main(int argc, char **argv)
 			}
 			for (size_t i = 0; i < seqs.size(); ++i) rows[i] = reinterpret_cast<uint8_t const *>(seqs[i].data());
 		}
-		rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
-		             : fseq_write_segments(ctx, rows.data(), how, out_segments);
+		if (!from_device)
+			rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
+			             : fseq_write_segments(ctx, rows.data(), how, out_segments);
 		if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	}
 	if (out_matches)

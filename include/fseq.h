@@ -280,7 +280,13 @@ int  fseq_greedy_match_host(uint32_t m, uint32_t max_segment_size, uint64_t n_se
  * class counts (a sharded run is refused there, as before).  fseq_debug_bipartite_path (fseq_debug.h) tells which ran. */
 int  fseq_join_bipartite(fseq_ctx *ctx, uint32_t *permutations);
 /* replaces: join_context::join_random_order_and_output (join_context.cc:259-289): std::mt19937(seed),
- * one std::shuffle per segment. */
+ * one std::shuffle per segment.  The joiner reads nothing of a boundary state but its classes' first rows and sizes, so
+ * while the run is not sharded, the merged segments tile the columns and max_segment_size is at most 65,535 the class
+ * tables are made where the boundary states are (k_join_classes_wide) and segments x max_segment_size x 8 + segments x 4
+ * bytes come to the host instead of segments x m x 8; the host part -- copy numbers, slots, shuffles -- is the same code on
+ * the same vectors, so the permutations are the host joiner's entry for entry.  A failed device allocation or a class
+ * count outside [1, max_segment_size] goes through the host joiner (FSEQ_JOIN_HOST forces it), which refuses a sharded
+ * run.  fseq_debug_random_path (fseq_debug.h) tells which ran. */
 int  fseq_join_random(fseq_ctx *ctx, uint32_t seed, uint32_t *permutations);
 /* The same joiners on caller-supplied boundary states (no context, no device).  weights (optional):
  * n_segments - 1 total matching weights. */
@@ -288,6 +294,12 @@ int  fseq_bipartite_match_host(uint32_t m, uint32_t max_segment_size, uint64_t n
                                uint32_t const *a, uint32_t const *d, uint32_t *permutations, int64_t *weights);
 int  fseq_random_join_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint64_t const *lb, uint64_t const *rb,
                            uint32_t const *a, uint32_t const *d, uint32_t seed, uint32_t *permutations);
+/* The random joiner from the runs on (join_context.cc:259-289 behind unique_substring_count_idxs_lhs), on caller-supplied
+ * class tables (no context, no device): count[s] classes of segment s in pBWT order, rep / size [n_segments][max_segment_size]
+ * their first rows in that order and their row counts.  What fseq_join_random runs behind its device front.
+ * FSEQ_E_ARG: a null pointer, m or max_segment_size 0, a count outside [1, max_segment_size]. */
+int  fseq_random_join_classes_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint32_t const *count, uint32_t const *rep,
+                                   uint32_t const *size, uint32_t seed, uint32_t *permutations);
 /* replaces: join_context::output_segments -> output_segments (segmentation_dp_arg.cc:13-104): the
  * --output-segments text file for the given joining method (greedy: the header line only, SURVEY.md
  * F5; bipartite: one line per segment text; random: one line per distinct substring with its copy
@@ -297,6 +309,21 @@ int  fseq_write_segments(fseq_ctx *ctx, uint8_t const *const *rows, int joining,
 /* The same with the boundary states supplied by the caller (S' x m words each, segment-major): a sharded run, where
  * they sit on their owner ranks (fseq_shard_owner / fseq_boundary_state) and the host collects them. */
 int  fseq_write_segments_host(fseq_ctx *ctx, uint8_t const *const *rows, int joining, uint32_t const *a, uint32_t const *d, char const *path);
+/* replaces: the same (segmentation_dp_arg.cc:13-104) from what the device holds (csrc/fseq_segfile.hpp): the bytes are those
+ * fseq_write_segments writes when given the raw rows of the alignment the context holds -- uploaded, streamed, generated or
+ * borrowed (one code per byte or packed); on a context made by fseq_create_without_identity_columns the reduced
+ * co-ordinates and the reduced rows' bytes.  No host rows and no copy of the boundary states (segments x m x 8 bytes): the
+ * class tables, the texts, the sorted row list of every text, the decoded substrings and the decimal text are made where
+ * the boundary states are, and the file leaves in batches of whole lines of at most 256 MiB (FSEQ_SEGFILE_BATCH), one copy
+ * and one write a batch.  For random joining the lines' order is the host's own std::sort on the device's class tables.
+ * Greedy: the header line only, no device work.  Refuses, each with fseq_last_error set and no other bytes written:
+ * FSEQ_E_ARG -- no run since the input was set, no resident alignment, an unknown joining, an output file that cannot be
+ * opened; FSEQ_E_UNSUPPORTED -- a sharded context, merged segments that do not tile the columns, bipartite joining with
+ * more than 4,096 texts a segment, random joining with more than 65,535, a class count outside [1, max_segment_size] read
+ * back from the device (fseq_write_segments serves these from host rows); FSEQ_E_OOM -- a failed allocation, which leaves
+ * nothing behind and the context usable.  fseq_debug_segments_file (fseq_debug.h) reports the batches.
+ * path NULL or "-" = stdout. */
+int  fseq_write_segments_device(fseq_ctx *ctx, int joining, char const *path);
 /* replaces: join_context::output_in_permutation_order (join_context.cc:333-356): max_segment_size
  * lines; line r = concatenation over segments of rows[permutations[s][r]][lb_s, rb_s).  rows = the
  * raw input sequences.  path NULL or "-" = stdout. */

@@ -112,6 +112,15 @@ int  fseq_debug_column_sources(fseq_ctx *ctx, uint32_t *staged, uint32_t *gather
 int  fseq_debug_red_cls_direct(uint32_t m, uint32_t B, uint32_t bits, uint64_t cls_ld, uint32_t config, uint32_t resident_rows, uint32_t resident_cls,
                                uint64_t *lds_rows, uint64_t *lds_cls, int *direct);
 
+/* Which way the last fseq_join_random since the input was set went: 0 the host joiner (every boundary state copied), 1 the class
+ * tables from the device.  FSEQ_E_ARG while none has finished. */
+int  fseq_debug_random_path(fseq_ctx *ctx, int *path);
+
+/* The last file fseq_write_segments_device wrote on this context: the batches that left the device (0: greedy, the header
+ * alone), the file's bytes, the bytes of its longest line and its lines -- both with the header, a line with its newline.
+ * Each out pointer may be NULL.  FSEQ_E_ARG while none has been written. */
+int  fseq_debug_segments_file(fseq_ctx *ctx, uint64_t *batches, uint64_t *bytes, uint64_t *longest_line, uint64_t *lines);
+
 /* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
  * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
  * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
