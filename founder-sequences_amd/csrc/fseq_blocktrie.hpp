@@ -94,18 +94,13 @@ __device__ __forceinline__ uint32_t bt_hash(uint32_t parent, uint32_t word)
 	return (x >> 12) & (OVF - 1u);
 }
 
-// A row whose word is not what direct[] holds for its class: the class's first row of this group registers its word there and
-// keeps the id; every other word of the class goes through the pair table -- entry = {word, class | id << 14 | ready}: whoever
-// creates it draws the id (returned); who finds it gets BT_FLAG | slot and reads the id behind the group's barrier.
-// vars[5]: the next id; *full: no room (ids or slots).
+// A row whose word is not the one registered in direct[] for its class (the class's first row of this group registers its word
+// there and keeps the id: the slot loop does that with the look-up itself) goes through the pair table -- entry = {word,
+// class | id << 14 | ready}: whoever creates it draws the id (returned); who finds it gets BT_FLAG | slot and reads the id
+// behind the group's barrier.  vars[5]: the next id; *full: no room (ids or slots).
 template <int T>
-__device__ __forceinline__ uint32_t bt_other_word(uint32_t *direct, unsigned long long *pairs, uint32_t *vars, uint32_t p, uint32_t w, uint32_t e, uint32_t &full)
+__device__ __forceinline__ uint32_t bt_other_word(unsigned long long *pairs, uint32_t *vars, uint32_t p, uint32_t w, uint32_t &full)
 {
-	if (e == BT_SENT && w != BT_SENT)
-	{
-		uint32_t const old = atomicCAS(direct + p, BT_SENT, w);
-		if (old == BT_SENT || old == w) return p;
-	}
 	unsigned long long const fresh = ((unsigned long long) p << 32) | w;
 	constexpr uint32_t OVF = BtGeom<T>::OVF;
 	uint32_t h = bt_hash<OVF>(p, w);
@@ -137,17 +132,33 @@ __device__ __forceinline__ uint32_t bt_other_word(uint32_t *direct, unsigned lon
 #define BT_STAMP(i) do {} while (0)
 #endif
 
-// the N packed words of a slot's group (zero behind the block's last column) and the ids of its N rows
+// the N packed words of a slot's group (zero behind the block's last column) and the ids of its N rows.  whole: the group's N columns
+// lie in front of kend (every group but a block's last one), and w0 is the slot's first word (uniform; not read otherwise)
 template <int BITS>
-__device__ __forceinline__ void bt_fetch(uint8_t const *__restrict__ msa, size_t ld, uint64_t kc, uint64_t kend, uint32_t wi, uint32_t nwords,
+__device__ __forceinline__ void bt_fetch(uint8_t const *__restrict__ msa, size_t ld, uint64_t kc, uint64_t kend, bool whole, uint32_t w0, uint32_t wi, uint32_t nwords,
                                          uint32_t const *__restrict__ idw, bool with_ids, uint32_t (&x)[32 / BITS], uint32_t (&cur)[16 / BITS])
 {
 	constexpr int N = 32 / BITS, IW = N / 2;
 	if (wi < nwords)
 	{
+		if (whole)
+		{
+			// no test per column, and no address arithmetic per thread: a uniform pointer that steps from column to column plus the
+			// thread's place in the slot, one 32-bit offset that is the same for every column and slot
+			uint8_t const *colp = msa + kc * ld + 4ull * w0;
+			uint32_t off = 4u * (wi - w0);
+			// (the offset is taken as made here: widened to 64 bits outside the slot loop, as the compiler does with a value that never
+			// changes, it is no longer the 32-bit offset of a load with a scalar base, and every column costs a 64-bit vector add)
+			asm volatile("" : "+v"(off));
 #pragma unroll
-		for (int c = 0; c < N; ++c)
-			x[c] = (kc + (uint64_t) c < kend) ? *reinterpret_cast<uint32_t const *>(msa + (kc + (uint64_t) c) * ld + 4ull * wi) : 0u;
+			for (int c = 0; c < N; ++c) { x[c] = *reinterpret_cast<uint32_t const *>(colp + off); colp += ld; }
+		}
+		else
+		{
+#pragma unroll
+			for (int c = 0; c < N; ++c)
+				x[c] = (kc + (uint64_t) c < kend) ? *reinterpret_cast<uint32_t const *>(msa + (kc + (uint64_t) c) * ld + 4ull * wi) : 0u;
+		}
 		if (with_ids)
 		{
 			if constexpr (IW >= 4)
@@ -257,6 +268,7 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 {
 	using G = BtGeom<BT_T>;
 	constexpr int N = 32 / BITS, IW = N / 2;                               // rows per packed word = columns per group; id words per packed word
+	constexpr int BQ = 4;                                                  // rows per batch of look-ups in phase 1 (8 is as fast; 16 spills in the slot loop and is slower: DESIGN.md section 3 [r11])
 	constexpr uint32_t BT_NK_MAX = G::NK, BT_OVF = G::OVF, BT_LIST = G::LIST;
 	constexpr size_t BT_OFF_DIRECT = G::OFF_DIRECT, BT_OFF_PAIRS = G::OFF_PAIRS, BT_OFF_RP = G::OFF_RP, BT_OFF_RC = G::OFF_RC, BT_OFF_DP = G::OFF_DP,
 	                 BT_OFF_DC = G::OFF_DC, BT_OFF_CNT = G::OFF_CNT, BT_OFF_LIST = G::OFF_LIST, BT_OFF_VARS = G::OFF_VARS;
@@ -304,7 +316,8 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 			uint32_t xn[N], curn[IW];
 #pragma unroll
 			for (int q = 0; q < IW; ++q) curn[q] = 0u;
-			bt_fetch<BITS>(msa, ld, kc, kend, tid, nwords, idw, t != 0u, xn, curn);
+			bool const whole = kc + (uint64_t) N <= kend;     // (all but a block's last group, the first one handled)
+			bt_fetch<BITS>(msa, ld, kc, kend, whole, 0u, tid, nwords, idw, t != 0u, xn, curn);
 			{
 				uint4 *const t4 = reinterpret_cast<uint4 *>(smem);
 				uint4 const ones = make_uint4(~0u, ~0u, ~0u, ~0u);
@@ -326,7 +339,7 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 #pragma unroll
 				for (int q = 0; q < IW; ++q) cur[q] = curn[q];
 				// the next slot's words and ids are loaded while this one is looked up
-				if (s + 1u < nslots) bt_fetch<BITS>(msa, ld, kc, kend, wi + BT_T, nwords, idw, t != 0u, xn, curn);
+				if (s + 1u < nslots) bt_fetch<BITS>(msa, ld, kc, kend, whole, (s + 1u) * BT_T, wi + BT_T, nwords, idw, t != 0u, xn, curn);
 				if (wi < nwords)
 				{
 					bt_transpose<BITS>(x);
@@ -341,36 +354,46 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 					bool changed = t == 0u;
 					uint32_t fl = 0;
 #pragma unroll
-					for (int q4 = 0; q4 < N / 4; ++q4)
+					for (int q = 0; q < N / BQ; ++q)
 					{
-						// four rows at a time; no branch, and no new ids, while every row carries the word registered for its class
-						uint32_t par[4], e[4];
+						// BQ rows at a time.  The look-up registers: a row that finds nobody of its class in this group yet (once per class
+						// and level, but some row of nearly every batch) puts its word there by compare-and-swap -- all of the batch issued before
+						// any result is looked at, one wait -- and keeps its id like a row that carries the registered word.  The word
+						// BT_SENT cannot be registered (a swap of the sentinel for the sentinel says nothing): such a row is the pair table's.
+						uint32_t par[BQ], e[BQ];
 #pragma unroll
-						for (int u = 0; u < 4; ++u)
+						for (int u = 0; u < BQ; ++u)
 						{
-							int const r = q4 * 4 + u;
+							int const r = q * BQ + u;
 							par[u] = (r & 1) ? (cur[r >> 1] >> 16) : (cur[r >> 1] & 0xFFFFu);
 							e[u] = direct[par[u]];
 						}
-						bool miss = false;
 #pragma unroll
-						for (int u = 0; u < 4; ++u) miss |= e[u] != x[q4 * 4 + u] || e[u] == BT_SENT;
+						for (int u = 0; u < BQ; ++u)
+							if ((e[u] == BT_SENT) & (x[q * BQ + u] != BT_SENT)) e[u] = atomicCAS(direct + par[u], BT_SENT, x[q * BQ + u]);
+						// (e: what the class had registered before this row came -- nothing: the row's own word is there now)
+						bool other[BQ], miss = false;
+#pragma unroll
+						for (int u = 0; u < BQ; ++u)
+						{
+							uint32_t const w = x[q * BQ + u];
+							other[u] = (w == BT_SENT) | ((e[u] != BT_SENT) & (e[u] != w));
+							miss |= other[u];
+						}
+						// only the rows with another word than their class's, a few hundred in 100,000, take the pair table
 						if (miss)
 						{
 #pragma unroll
-							for (int u = 0; u < 4; ++u)
-							{
-								int const r = q4 * 4 + u;
-								if (e[u] != x[r] || e[u] == BT_SENT)
+							for (int u = 0; u < BQ; ++u)
+								if (other[u])
 								{
-									uint32_t const id = bt_other_word<BT_T>(direct, pairs, vars, par[u], x[r], e[u], full);
+									uint32_t const id = bt_other_word<BT_T>(pairs, vars, par[u], x[q * BQ + u], full);
 									changed |= id != par[u];
 									par[u] = id;
 									fl |= id & BT_FLAG;
 								}
-							}
-							cur[2 * q4] = par[0] | (par[1] << 16);
-							cur[2 * q4 + 1] = par[2] | (par[3] << 16);
+#pragma unroll
+							for (int u = 0; u < BQ; u += 2) cur[(q * BQ + u) >> 1] = par[u] | (par[u + 1] << 16);
 						}
 					}
 					if (changed) bt_store_ids<IW>(idw, wi, cur);
@@ -389,7 +412,7 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 				flagged &= flagged - 1u;
 				uint32_t const wi = s * BT_T + tid;
 				uint32_t xd[N], cur[IW];
-				bt_fetch<BITS>(msa, ld, kend, kend, wi, nwords, idw, true, xd, cur);      // (the ids only: no column in front of kend)
+				bt_fetch<BITS>(msa, ld, kend, kend, false, 0u, wi, nwords, idw, true, xd, cur);      // (the ids only: no column in front of kend)
 #pragma unroll
 				for (int q = 0; q < IW; ++q)
 				{
@@ -563,7 +586,7 @@ __global__ __launch_bounds__(BT_T) void k_blocktrie(
 		for (uint32_t wi = tid; wi < nwords; wi += BT_T)
 		{
 			uint32_t xd[N], cur[IW];
-			bt_fetch<BITS>(msa, ld, kend, kend, wi, nwords, idw, true, xd, cur);
+			bt_fetch<BITS>(msa, ld, kend, kend, false, 0u, wi, nwords, idw, true, xd, cur);
 			uint32_t const r0 = wi * (uint32_t) N;
 #pragma unroll
 			for (int r = 0; r < N; ++r)
