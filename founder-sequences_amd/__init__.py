@@ -80,6 +80,16 @@ class IdentitySummary(C.Structure):
     _fields_ = [("n", C.c_uint64), ("identity", C.c_uint64), ("kept", C.c_uint64), ("ms_device", C.c_double)]
 
 
+class LengthScanSummary(C.Structure):
+    _fields_ = [("lists_built", C.c_uint32), ("lists_folded", C.c_uint32), ("short_entries", C.c_uint32), ("retries", C.c_uint32),
+                ("ms_phase_a", C.c_double), ("ms_phase_b", C.c_double), ("ms_total", C.c_double)]
+
+
+# fseq_length_scan_entry (include/fseq.h), 40 bytes
+LENGTH_SCAN_DTYPE = np.dtype([("segment_length", "<u8"), ("max_segment_size", "<u4"), ("short_path", "<u4"), ("lists", "<u4"), ("list_cap", "<u4"),
+                              ("dp_chunks", "<u4"), ("reserved", "<u4"), ("ms_device", "<f8")])
+SCAN_LISTS_BUILT, SCAN_LISTS_FOLDED, SCAN_LISTS_NONE = 0, 1, 2
+
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
 
@@ -104,12 +114,13 @@ EXPORTS = [
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
     "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
     "fseq_write_segments_device", "fseq_random_join_classes_host", "fseq_debug_segments_file", "fseq_debug_random_path",
+    "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
-                 "fseq_debug_segments_file", "fseq_debug_random_path"]
+                 "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -226,6 +237,10 @@ def load_library():
     L.fseq_random_join_classes_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, vp]
     L.fseq_debug_segments_file.argtypes = [vp] + [C.POINTER(u64)] * 4
     L.fseq_debug_random_path.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fseq_set_segment_length.argtypes = [vp, u64]
+    L.fseq_scan_segment_lengths.argtypes = [vp, vp, sz, C.POINTER(LengthScanSummary)]
+    L.fseq_debug_scan_plan.argtypes = [u64, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32)]
+    L.fseq_debug_relump_lists.argtypes = [C.c_int, u64, C.c_uint32, C.c_uint32, u64, u64, vp, vp]
     _lib = L
     return L
 
@@ -395,6 +410,39 @@ def red_plan_host(m, B, bits, direct, cnt, force=None, b_lo=0, b_hi=None, reduce
                bins=[tuple(int(x) for x in row) for row in bins[:n_bins.value]],
                configs=[(int(r), int(v), int(T), int(E), bool(ew), bool(fits)) for r, v, T, E, ew, fits in configs[:n_configs.value]])
     return out
+
+
+def scan_plan_host(n, lengths):
+    """The order of work of a scan over segment lengths (plan_length_scan, csrc/fseq_scanplan.hpp) for n columns: (long_lengths,
+    slot, n_short) -- the distinct lengths of the long path (n >= 2L) ascending, for every given length its place among them
+    or -1 (the short path), and how many take the short path.  No device is touched."""
+    L = load_library()
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+    if lengths.ndim != 1:
+        raise FseqError(FSEQ_E_ARG, "scan_plan_host: one length per entry")
+    long_lengths = np.zeros(max(1, len(lengths)), dtype=np.uint64)
+    slot = np.zeros(max(1, len(lengths)), dtype=np.int32)
+    n_long, n_short = C.c_uint32(), C.c_uint32()
+    rc = L.fseq_debug_scan_plan(int(n), lengths.ctypes.data, len(lengths), long_lengths.ctypes.data, C.byref(n_long), slot.ctypes.data, C.byref(n_short))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return long_lengths[:n_long.value].copy(), slot[:len(lengths)].copy(), n_short.value
+
+
+def relump_lists(ent, hdr, k0, L_from, L_to, device=0):
+    """One launch of k_relump_lists on constructed lists: ent [ncols][stride][2] {value, count}, hdr [ncols][4] {entries, count of
+    value 0, complete, cumulative count}, the lists of the columns k0 .. k0 + ncols - 1 at segment length L_from.  Returns
+    (ent, hdr) folded to L_to.  FseqError(FSEQ_E_ARG), before a device is touched, where an input could take the kernel out of
+    bounds."""
+    L = load_library()
+    ent = np.array(ent, dtype=np.uint32, order="C")
+    hdr = np.array(hdr, dtype=np.uint32, order="C")
+    if ent.ndim != 3 or ent.shape[2] != 2 or hdr.shape != (ent.shape[0], 4):
+        raise FseqError(FSEQ_E_ARG, "relump_lists: ent is [ncols][stride][2], hdr [ncols][4]")
+    rc = L.fseq_debug_relump_lists(device, int(k0), ent.shape[0], ent.shape[1], int(L_from), int(L_to), ent.ctypes.data, hdr.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return ent, hdr
 
 
 class RowShard(C.Structure):
@@ -717,6 +765,24 @@ class SegmentationContext:
         self.result = res
         self._check(rc)
         return res
+
+    def set_segment_length(self, segment_length):
+        """Another segment length bound on the resident alignment (fseq_set_segment_length): the result and the last match are
+        dropped, the next run() gives what a fresh context with that length gives."""
+        self._check(self.L.fseq_set_segment_length(self.h, int(segment_length)))
+        self.segment_length = int(segment_length)
+        self.result = None
+
+    def scan_segment_lengths(self, lengths):
+        """The maximum segment size at every given segment length (fseq_scan_segment_lengths): (entries, summary) -- a structured
+        array (LENGTH_SCAN_DTYPE), one entry per given length in the given order, and the summary as a dict.  The context holds
+        no result afterwards and keeps its own segment length."""
+        entries = np.zeros(len(lengths), dtype=LENGTH_SCAN_DTYPE)
+        entries["segment_length"] = np.asarray(lengths, dtype=np.uint64)
+        sm = LengthScanSummary()
+        self._check(self.L.fseq_scan_segment_lengths(self.h, entries.ctypes.data, len(entries), C.byref(sm)))
+        self.result = None
+        return entries, {k: getattr(sm, k) for k, _ in LengthScanSummary._fields_}
 
     @property
     def max_segment_size(self):

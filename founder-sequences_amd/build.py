@@ -15,6 +15,7 @@ SRCS = [os.path.join(HERE, "csrc", name) for name in (
     "fseq_path_reduced.hip",
     "fseq_path_attempt.hip",
     "fseq_path_pass2.hip",
+    "fseq_lengthscan.hip",
     "fseq_api_join.hip",
     "fseq_api_match.hip",
     "fseq_api_identity.hip",

@@ -22,6 +22,7 @@ using namespace fseq;
 void fseq::forget_run_history(fseq_ctx *c)
 {
 	c->have_result = false;
+	c->scan_lists = false;
 	c->kernels_ready = false;
 	c->bk_given_up = -1; c->bt_given_up = -1; c->red.memory.forget_input();
 }
@@ -327,6 +328,7 @@ int fseq_run_segmentation(fseq_ctx *c, fseq_result *res)
 	if (!c->have_input) return fail(c, FSEQ_E_ARG, "no input set");
 	(void) hipSetDevice(c->p.device);
 	c->have_result = false;
+	c->scan_lists = false;
 	c->sh.closed = false;
 	c->lw.on = false; c->lw.merge_windows = 0;
 	if (!c->kernels_ready)

@@ -16,6 +16,8 @@ int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 	// plan the same partition -- the knobs of a sharded run are set (identically on every rank) before the input
 	if (c->sh.on && c->have_input) return fail(c, FSEQ_E_ARG, "sharded run: set tuning knobs before the input is set (identically on every rank)");
 	if (!c->tune.set(name, value)) return fail(c, FSEQ_E_ARG, "unknown tuning knob");
+	// (the scan's knob is read by fseq_scan_segment_lengths alone: no geometry, no kernel and no result depends on it)
+	if (!strcmp(name, "FSEQ_SCAN_REBUILD")) return FSEQ_OK;
 	// (the geometry and the kernel choice may depend on it: the work buffers of an earlier run were sized for the old one)
 	(void) hipSetDevice(c->p.device);
 	if (c->stream) (void) hipStreamSynchronize(c->stream);
@@ -182,7 +184,8 @@ int fseq_debug_block_state(fseq_ctx *c, uint64_t block_idx, uint32_t *a_out, uin
 int fseq_debug_column_list(fseq_ctx *c, uint64_t col, uint32_t *values, uint32_t *counts,
                            uint32_t *n_entries, uint32_t *cnt0, uint32_t *complete)
 {
-	if (!c || !c->have_result || c->res.short_path || col >= c->p.n) return FSEQ_E_ARG;
+	// (behind a scan over segment lengths there is no result, but the lists of its last long-path entry are held)
+	if (!c || !(c->scan_lists || (c->have_result && !c->res.short_path)) || col >= c->p.n) return FSEQ_E_ARG;
 	if (c->lw.on && (col < c->lw.col_lo || col >= c->lw.col_hi)) return fail(c, FSEQ_E_ARG, "the list of this column is not held: the run kept its lists in windows (fseq_set_list_memory)");
 	(void) hipSetDevice(c->p.device);
 	uint4 h;

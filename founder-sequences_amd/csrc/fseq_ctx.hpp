@@ -138,6 +138,7 @@ struct Tuning {
 	bool class_gather = false;           // FSEQ_CLASS_GATHER: the class columns are gathered into the reduced alignment for every block (the form before the column kernel staged them itself)
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
+	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -187,6 +188,7 @@ struct Tuning {
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
 			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
 			{"FSEQ_CLASS_GATHER", &Tuning::class_gather, nullptr, 0, 0, nullptr},
+			{"FSEQ_SCAN_REBUILD", &Tuning::scan_rebuild, nullptr, 0, 0, nullptr},
 		};
 		return table;
 	}
@@ -459,6 +461,7 @@ struct fseq_ctx {
 
 	// results
 	bool have_result = false;
+	bool scan_lists = false;                 // no result, but the lists of a scan's last long-path entry (fseq_scan_segment_lengths): fseq_debug_column_list answers
 	fseq_result res{};
 	DevBuf<uint4> d_tb;                      // the traceback kernels' output {entry, lb, key, size} per segment, window heads, counts
 	std::vector<fseq_dp_arg> traceback;

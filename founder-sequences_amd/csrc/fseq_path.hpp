@@ -12,6 +12,8 @@
 //   csrc/fseq_path_attempt.hip  one attempt at a list capacity as stages with one verdict, the list windows, the loop over attempts,
 //                             the short path (instantiates no kernel)
 //   csrc/fseq_path_pass2.hip  the boundary states at the merged boundaries
+//   csrc/fseq_lengthscan.hip  another segment length on a resident alignment, the scan over segment lengths (the one unit that
+//                             includes fseq_lengthscan.hpp: k_relump_lists)
 // A kernel template is instantiated, and a header that defines plain __global__ kernels (fseq_dpspec.hpp, fseq_chainsort.hpp,
 // fseq_rowshard.hpp) is included, by one unit only: the others reach those kernels through the launchers declared here.  A unit
 // may include a header of templates for the sizes and schedules it computes on the host (stream_lds_bytes, ...); the DP's round
@@ -196,6 +198,16 @@ void set_list_window(fseq_ctx *c, uint32_t lo_w);
 int window_phase_c(fseq_ctx *c, uint32_t lo, uint32_t hi);
 int run_long_path(fseq_ctx *c, fseq_result *res);
 int run_short_path(fseq_ctx *c, fseq_result *res);
+// what a scan over segment lengths shares with a run: the attempts up to a proven DP result (stages 1 to 5 of an attempt, the
+// capacity grown by the ordinary rule), and the DP alone on the lists the context holds (*unproven: a list was too short)
+struct DpProof { uint32_t max_segment_size = 0, dp_chunks = 0, dp_sweeps = 0; };
+int long_attempts_to_proof(fseq_ctx *c, LongRun &R, DpProof *proof);
+int long_dp_on_lists(fseq_ctx *c, DpProof *proof, bool *unproven);
+
+// ---- csrc/fseq_lengthscan.hip
+// another segment length on the context: dp_size and the DP arrays' sizes follow (grow-only; allocated where the geometry's buffers are)
+int apply_segment_length(fseq_ctx *c, uint64_t L);
+void launch_relump_lists(hipStream_t st, RelumpArgs const &lists);     // (k_relump_lists, fseq_lengthscan.hpp)
 
 // ---- csrc/fseq_path_pass2.hip
 int long_pass2(fseq_ctx *c, LongRun &R);

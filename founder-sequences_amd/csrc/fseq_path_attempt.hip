@@ -406,11 +406,11 @@ int attempt_dump_diagnostics(fseq_ctx *c)
 }
 #endif
 
-// the stages in turn; stage 7, behind a verdict that is not "again": the traceback and the merge (which may still find a list too short)
-int long_attempt(fseq_ctx *c, LongRun &R, Attempt *verdict)
+// stages 1 to 5 in turn: the attempt up to its verdict.  What a run (long_attempt) and a scan over segment lengths
+// (long_attempts_to_proof) share
+int attempt_to_verdict(fseq_ctx *c, LongRun &R, AttemptState &A, Attempt *verdict)
 {
 	FSEQ_LONG_LOCALS(c);
-	AttemptState A;
 	if ((rc = attempt_prepare(c, R, A))) return rc;
 	HIP_TRY(c, hipEventRecord(c->ev.c_begin, st));
 	RangeScope range_cd("fseq pass 1: phases C + D (column updates + lists, segmentation DP)");
@@ -429,12 +429,30 @@ int long_attempt(fseq_ctx *c, LongRun &R, Attempt *verdict)
 	HIP_TRY(c, hipEventRecord(c->ev.dp_end, st));
 	HIP_TRY(c, hipGetLastError());
 	mark(c, A, "DP queued");
-	if ((rc = attempt_decide(c, R, A, again, verdict))) return rc;
+	return attempt_decide(c, R, A, again, verdict);
+}
+
+// the ordinary retry rule behind a verdict of overflow: twice the capacity and one, at most every row
+int attempt_grow_capacity(fseq_ctx *c, LongRun &R)
+{
+	uint32_t const m = c->p.m;
+	if (R.X >= m) return fail(c, FSEQ_E_HIP, "internal: divergence lists complete but DP flagged overflow");
+	R.X = (uint32_t) std::min<uint64_t>(m, (uint64_t) R.X * 2 + 1);
+	++R.retries;
+	if (c->tune.debug) fprintf(stderr, "[fseq] divergence lists too short, retry %u with X = %u\n", R.retries, R.X);
+	return FSEQ_OK;
+}
+
+// the stages in turn; stage 7, behind a verdict that is not "again": the traceback and the merge (which may still find a list too short)
+int long_attempt(fseq_ctx *c, LongRun &R, Attempt *verdict)
+{
+	FSEQ_LONG_LOCALS(c);
+	AttemptState A;
+	if ((rc = attempt_to_verdict(c, R, A, verdict))) return rc;
 	if (*verdict == Attempt::Again) return FSEQ_OK;
 #if defined(FSEQ_DP_STAMPS) || defined(FSEQ_DP_STATS)
 	if ((rc = attempt_dump_diagnostics(c))) return rc;
 #endif
-	range_cd.end();
 	progress(c, FSEQ_STAGE_TRACEBACK, n, n);
 	RangeScope range_tb("fseq traceback + find_segments_greedy");
 	double const th0 = now_ms();
@@ -452,6 +470,49 @@ int long_attempt(fseq_ctx *c, LongRun &R, Attempt *verdict)
 }
 
 } // namespace
+
+// ---- what a scan over segment lengths shares with a run (csrc/fseq_lengthscan.hip)
+// Attempts at the context's segment length, from the capacity R.X on, until the DP's result is proven; they stop at the verdict:
+// no traceback, merge or pass 2.  Phases A and B of R are behind the stream.
+int long_attempts_to_proof(fseq_ctx *c, LongRun &R, DpProof *proof)
+{
+	int rc;
+	for (Attempt verdict = Attempt::Again; verdict != Attempt::Stands;)
+	{
+		AttemptState A;
+		if ((rc = attempt_to_verdict(c, R, A, &verdict))) return rc;
+		if (verdict == Attempt::Overflow && (rc = attempt_grow_capacity(c, R))) return rc;
+		proof->dp_chunks = A.use_spec ? A.spec.nchunks() : 0u;
+		proof->dp_sweeps = A.spec_sweeps;
+	}
+	HIP_TRY(c, hipMemcpy(&proof->max_segment_size, c->dp.M + (c->dp_size - 1), 4, hipMemcpyDeviceToHost));
+	return FSEQ_OK;
+}
+
+// The DP alone on the lists the context holds, in the form a run at the context's segment length chooses (the speculative sweeps,
+// or the serial kernel where the input is too short for three chunks): its words cleared, the schedule and the chunk plan of this
+// length, and the words and the final cell's entry back in one round trip.  *unproven: a list was too short to prove a cell.
+int long_dp_on_lists(fseq_ctx *c, DpProof *proof, bool *unproven)
+{
+	FSEQ_LONG_LOCALS(c);
+	HIP_TRY(c, hipMemsetAsync(path_words(c)->dp, 0, sizeof(PathWords::dp), st));
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	SpecPlan const spec = spec_plan(c, S);
+	uint32_t spec_overflow = 0;
+	proof->dp_chunks = spec.nchunks();
+	proof->dp_sweeps = 0;
+	if (spec.nchunks() > 0) { if ((rc = run_dp_spec(c, S, spec, st, &spec_overflow, &proof->dp_sweeps))) return rc; }
+	else launch_dp_serial(c, DP_WHOLE, st, 0u, S.nrounds);
+	HIP_TRY(c, hipGetLastError());
+	if ((rc = pin_reserve(c, 64))) return rc;
+	uint32_t *const h = pin_take<uint32_t>(c, 8);
+	HIP_TRY(c, hipMemcpyAsync(h, path_words(c)->dp, sizeof(PathWords::dp), hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(h + 4, c->dp.M + (c->dp_size - 1), 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	*unproven = (h[0] & 1u) != 0 || spec_overflow != 0;
+	proof->max_segment_size = h[4];
+	return FSEQ_OK;
+}
 
 int run_long_path(fseq_ctx *c, fseq_result *res)
 {
@@ -484,10 +545,7 @@ int run_long_path(fseq_ctx *c, fseq_result *res)
 		case Attempt::Stands: break;
 		case Attempt::Again: break;            // (the same capacity; the blocks that were flagged run on all rows now)
 		case Attempt::Overflow:
-			if (R.X >= m) return fail(c, FSEQ_E_HIP, "internal: divergence lists complete but DP flagged overflow");
-			R.X = (uint32_t) std::min<uint64_t>(m, (uint64_t) R.X * 2 + 1);
-			++R.retries;
-			if (c->tune.debug) fprintf(stderr, "[fseq] divergence lists too short, retry %u with X = %u\n", R.retries, R.X);
+			if ((rc = attempt_grow_capacity(c, R))) return rc;
 			break;
 		}
 	}

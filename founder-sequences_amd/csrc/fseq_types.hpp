@@ -85,6 +85,13 @@ struct ListArgs {
 	uint4 *hdr = nullptr;
 };
 
+// one launch of k_relump_lists (fseq_lengthscan.hpp): the lists of the columns [k0, k0 + ncols), built or folded at a segment length
+// <= lists.L, folded in place to what the DP reads at lists.L (lists.X is not used: the capacity stays what the lists were built at)
+struct RelumpArgs {
+	ListArgs lists;
+	uint64_t k0 = 0, ncols = 0;
+};
+
 // the stride states: the state at column q * snap_stride at ss_* + q * (words of a state); phase C drops them, pass 2 starts from them
 struct StrideStates {
 	uint32_t snap_stride = 0;

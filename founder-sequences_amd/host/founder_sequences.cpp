@@ -14,6 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cerrno>
 #include <cstdint>
@@ -54,6 +55,13 @@ char const *const USAGE =
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
+	"      --scan-segment-lengths=SPEC    Before anything else, write the maximum segment size at every segment length bound of SPEC --\n"
+	"                                     a comma list of lengths, or LO:HI:STEP -- as a table (SEGMENT_LENGTH, MAX_SEGMENT_SIZE; one line\n"
+	"                                     per distinct length, ascending) from the one resident alignment (one GPU only).  Alone: the\n"
+	"                                     table and nothing else; with --segment-length-bound: the table, then the ordinary run\n"
+	"      --output-scan=PATH             ... the table's path  (default: standard output)\n"
+	"      --max-founders=K               ... and go on with the largest scanned bound whose maximum segment size is at most K (requires\n"
+	"                                     --scan-segment-lengths; not together with --segment-length-bound)\n"
 	"\nRunning options:\n"
 	"  -m, --pbwt-sample-rate=q           On the first pass, store a PBWT sample every q*sqrt(n)-th position. Zero indicates no sampling.  (default=`4')\n"
 	"      --random-seed=LONG             Seed for the random number generator  (default=`0')\n"
@@ -186,6 +194,41 @@ std::ostream *open_out(char const *path, std::ofstream &file)
 	return &file;
 }
 
+// --scan-segment-lengths=SPEC: a comma list of positive lengths, or LO:HI:STEP (LO, LO + STEP, ... up to HI).  The distinct
+// lengths, ascending; false where SPEC is malformed
+bool parse_scan_spec(char const *spec, std::vector<uint64_t> &out)
+{
+	auto number = [](char const *&s, uint64_t &v) {
+		if (!isdigit((unsigned char) *s)) return false;
+		char *end = nullptr;
+		errno = 0;
+		v = strtoull(s, &end, 10);
+		s = end;
+		return errno != ERANGE && v > 0 && v < 0xFFFFFFF0ull;
+	};
+	char const *s = spec;
+	out.clear();
+	if (strchr(spec, ':'))
+	{
+		uint64_t lo = 0, hi = 0, step = 0;
+		if (!number(s, lo) || *s++ != ':' || !number(s, hi) || *s++ != ':' || !number(s, step) || *s != '\0' || hi < lo) return false;
+		if ((hi - lo) / step >= 1000000u) return false;
+		for (uint64_t L = lo; L <= hi; L += step) out.push_back(L);
+		return true;
+	}
+	while (true)
+	{
+		uint64_t v = 0;
+		if (!number(s, v) || out.size() >= 1000000u) return false;
+		out.push_back(v);
+		if (*s == '\0') break;
+		if (*s++ != ',') return false;
+	}
+	std::sort(out.begin(), out.end());
+	out.erase(std::unique(out.begin(), out.end()), out.end());
+	return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -204,6 +247,9 @@ int main(int argc, char **argv)
 	bool list_memory_bad = false;
 	unsigned long long upload_mib = 0;
 	bool upload_given = false, upload_bad = false;
+	char const *scan_spec = nullptr, *out_scan = nullptr;
+	unsigned long long max_founders = 0;
+	bool max_founders_given = false, max_founders_bad = false;
 
 	static option const longopts[] = {
 		{"help", no_argument, nullptr, 'h'}, {"version", no_argument, nullptr, 'V'},
@@ -216,6 +262,8 @@ int main(int argc, char **argv)
 		{"output-matches", required_argument, nullptr, 1005}, {"match-min-segment-length", required_argument, nullptr, 1006},
 		{"remove-identity-columns", no_argument, nullptr, 1007}, {"output-identity-columns", required_argument, nullptr, 1008},
 		{"output-restored-matches", required_argument, nullptr, 1009}, {"upload-memory", required_argument, nullptr, 1010},
+		{"scan-segment-lengths", required_argument, nullptr, 1011}, {"output-scan", required_argument, nullptr, 1012},
+		{"max-founders", required_argument, nullptr, 1013},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -275,6 +323,17 @@ int main(int argc, char **argv)
 				upload_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || 0 == upload_mib || upload_mib > (~0ull >> 20);
 				break;
 			}
+			case 1011: scan_spec = optarg; break;
+			case 1012: out_scan = optarg; break;
+			case 1013:
+			{
+				char *end = nullptr;
+				errno = 0;
+				max_founders = strtoull(optarg, &end, 10);
+				max_founders_given = true;
+				max_founders_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || 0 == max_founders;
+				break;
+			}
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -292,7 +351,14 @@ int main(int argc, char **argv)
 	{
 		if (seg_len <= 0) { std::cerr << "Segment length bound must be positive." << std::endl; return EXIT_FAILURE; }
 	}
-	else { std::cerr << "Segment length bound needs to be specified when generating a segmentation." << std::endl; return EXIT_FAILURE; }
+	else if (!scan_spec && !max_founders_given && !out_scan) { std::cerr << "Segment length bound needs to be specified when generating a segmentation." << std::endl; return EXIT_FAILURE; }
+	std::vector<uint64_t> scan_lengths;
+	if (scan_spec && !parse_scan_spec(scan_spec, scan_lengths))
+	{ std::cerr << "The segment lengths to scan must be a comma list of positive numbers or LO:HI:STEP with LO <= HI and STEP positive." << std::endl; return EXIT_FAILURE; }
+	if (out_scan && !scan_spec) { std::cerr << "--output-scan requires --scan-segment-lengths." << std::endl; return EXIT_FAILURE; }
+	if (max_founders_bad) { std::cerr << "The maximum number of founders must be a positive number." << std::endl; return EXIT_FAILURE; }
+	if (max_founders_given && !scan_spec) { std::cerr << "--max-founders requires --scan-segment-lengths (it chooses among the scanned segment length bounds)." << std::endl; return EXIT_FAILURE; }
+	if (max_founders_given && seg_len_given) { std::cerr << "--max-founders is not supported together with --segment-length-bound (it chooses the bound itself)." << std::endl; return EXIT_FAILURE; }
 	if (!(0 <= seed && (unsigned long) seed <= std::numeric_limits<std::uint_fast32_t>::max()))
 	{ std::cerr << "Random seed out of bounds." << std::endl; return EXIT_FAILURE; }
 	if (sample_rate <= 0) { std::cerr << "PBWT sample rate multiplier must be non-negative." << std::endl; return EXIT_FAILURE; }
@@ -309,6 +375,7 @@ int main(int argc, char **argv)
 	if (upload_given && input_format::FASTA == fmt) { std::cerr << "--upload-memory is not supported together with --input-format=FASTA (a FASTA file holds the sequences one after another, so a column chunk is not a range of its bytes; use list-file input)." << std::endl; return EXIT_FAILURE; }
 	if (upload_given && gpus > 1) { std::cerr << "--upload-memory is not supported together with --gpus > 1 (the chunked input does not exchange the ranks' alphabets)." << std::endl; return EXIT_FAILURE; }
 	if (upload_given && out_segments && joining::GREEDY != join) { std::cerr << "--upload-memory is not supported together with --output-segments under bipartite-matching or random joining (the segment texts need the raw rows on the host; greedy joining writes the header only)." << std::endl; return EXIT_FAILURE; }
+	if (scan_spec && gpus > 1) { std::cerr << "--scan-segment-lengths is not supported together with --gpus > 1 (a sharded context's block geometry depends on the segment length)." << std::endl; return EXIT_FAILURE; }
 
 	// generate_context.cc:64-106
 	std::cerr << "Loading the input…" << std::flush;
@@ -344,7 +411,9 @@ int main(int argc, char **argv)
 	fseq_params p{};
 	p.m = (uint32_t) lengths.size();
 	p.n = seq_length;
-	p.segment_length = (uint64_t) seg_len;
+	// (a scan without a bound of its own: the context is made at the smallest scanned length; --max-founders sets the chosen one)
+	p.segment_length = seg_len_given ? (uint64_t) seg_len : scan_lengths.front();
+	bool const scan_only = scan_spec && !seg_len_given && !max_founders_given;
 	p.pbwt_sample_rate = (uint64_t) sample_rate;
 	std::vector<uint8_t const *> rows(lengths.size(), nullptr);      // (--upload-memory: no rows on the host)
 	std::string io_err;
@@ -398,6 +467,38 @@ int main(int argc, char **argv)
 			if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(kept, (uint64_t) list_memory_mib << 20))) return rc_;
 			if (out_identity && FSEQ_OK != (rc_ = fseq_write_identity_columns(kept, out_identity))) return rc_;
 		}
+		if (scan_spec)
+		{
+			// the table from the resident alignment (with --remove-identity-columns: the reduced one, lengths count kept columns)
+			std::cerr << "Scanning " << scan_lengths.size() << " segment length bound(s)…" << std::endl;
+			std::vector<fseq_length_scan_entry> entries(scan_lengths.size());
+			for (size_t i = 0; i < entries.size(); ++i) entries[i].segment_length = scan_lengths[i];
+			fseq_length_scan_summary ssm{};
+			if (FSEQ_OK != (rc_ = fseq_scan_segment_lengths(ctxs[r], entries.data(), entries.size(), &ssm))) return rc_;
+			std::ofstream scan_file;
+			std::ostream &ts = *open_out(out_scan, scan_file);
+			ts << "SEGMENT_LENGTH\tMAX_SEGMENT_SIZE\n";
+			uint32_t smallest = ~0u;
+			uint64_t chosen = 0;
+			for (auto const &e : entries)                            // (ascending: parse_scan_spec)
+			{
+				ts << e.segment_length << '\t' << e.max_segment_size << '\n';
+				smallest = std::min(smallest, e.max_segment_size);
+				if (max_founders_given && e.max_segment_size <= max_founders) chosen = e.segment_length;
+			}
+			ts << std::flush;
+			if (scan_only) return FSEQ_OK;
+			if (max_founders_given)
+			{
+				if (!chosen)
+				{
+					io_err = "No scanned segment length bound gives at most " + std::to_string(max_founders) + " founders; the smallest maximum segment size seen was " + std::to_string(smallest) + ".";
+					return FSEQ_OK;
+				}
+				std::cerr << "segment length bound chosen: " << chosen << std::endl;
+				if (FSEQ_OK != (rc_ = fseq_set_segment_length(ctxs[r], chosen))) return rc_;
+			}
+		}
 		return fseq_run_segmentation(ctxs[r], &results[r]);
 	};
 	if (sharded)
@@ -426,6 +527,12 @@ int main(int argc, char **argv)
 	}
 	if (!io_err.empty()) { std::cerr << io_err << std::endl; return EXIT_FAILURE; }
 	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	if (scan_only)
+	{
+		std::cerr << "Done." << std::endl;
+		fseq_destroy(ctx);
+		return EXIT_SUCCESS;
+	}
 
 	std::ofstream founders_file, segments_file;
 	if (res.short_path)

@@ -125,7 +125,7 @@ char const *fseq_last_error(fseq_ctx const *ctx);
 /* ---- a new input on a live context ----
  * Every input setter -- fseq_set_rows, fseq_set_matrix, fseq_set_device_columns, fseq_set_device_columns_packed,
  * fseq_generate_synthetic and the chunked input (fseq_input_begin .. fseq_input_end, fseq_set_rows_streamed) -- may be called
- * again on a context that has run; m, n and the segment length stay those of fseq_create.  Once its arguments are in order the
+ * again on a context that has run; m and n stay those of fseq_create, the segment length that of fseq_create or of the last fseq_set_segment_length.  Once its arguments are in order the
  * call takes the context for the new alignment:
  *   - the result of the last run is dropped: until the next fseq_run_segmentation, fseq_get_traceback, fseq_get_segments,
  *     fseq_boundary_state, fseq_short_path_runs, the joiners, fseq_write_segments, fseq_write_founders(_device) and
@@ -504,6 +504,55 @@ int      fseq_input_end(fseq_ctx *ctx);
  * end, in chunks of fseq_input_chunk_columns rounded down to a multiple of 64 where that leaves at least 64.  Results are
  * those of fseq_set_rows on the same rows, bit for bit. */
 int      fseq_set_rows_streamed(fseq_ctx *ctx, uint8_t const *const *rows, uint64_t staging_bytes);
+
+/* Another segment length bound L on the alignment the context holds.  replaces: nothing of the reference, which is run once
+ * per L (generate_context.cc:121-124 reads the bound once); here a second L needs neither a second context nor a second
+ * upload.  The context keeps the resident alignment, its alphabet and -- a context made by
+ * fseq_create_without_identity_columns, on which the call is allowed -- its identity relation.  It drops the result and the
+ * last match as a new input does: the getters return FSEQ_E_ARG until the next fseq_run_segmentation.  What runs learnt that
+ * depends on L is forgotten (the list capacity that worked, the representatives' plan, the traceback's length); the block
+ * geometry of an unsharded context does not depend on L, so what phase A learnt stays.  No buffer that still fits is released:
+ * the DP arrays grow when L shrinks and never shrink, so a context cycled between two lengths settles on the larger arrays.
+ * The next fseq_run_segmentation gives, bit for bit, what a fresh context created with that L gives on the same rows; n < 2L
+ * takes the short path as there.  FSEQ_E_ARG and nothing changes: L == 0 (what fseq_create refuses for L), a chunked input
+ * under way (fseq_input_begin without its end).  FSEQ_E_UNSUPPORTED: a sharded context (fseq_set_shard, before or after) --
+ * its geometry and halo depend on L.  Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+int      fseq_set_segment_length(fseq_ctx *ctx, uint64_t segment_length);
+
+/* The maximum segment size at several segment length bounds in one call: "how many founders at which L".  replaces: nothing
+ * of the reference (one run of the program per L).  Phases A and B and the capacity estimate run once -- on an unsharded
+ * context they do not depend on L --; the lists are built (phase C) at the smallest long-path length, and for every further
+ * length, ascending, folded in place (the entries a larger L clips to the same cut bound join the list's first entry) and
+ * the DP alone runs again.  The DP itself tells where a folded list is too short to prove a cell: the lists are then built
+ * at that length (FSEQ_SCAN_LISTS_BUILT) and the scan goes on from there, so no value rests on the folding.  Measured (DESIGN.md
+ * section 7): folded lists prove whole lengths where the lists are complete (capacity >= m); lists cut at their capacity end at
+ * the first value that many rows share, and on the benchmark's inputs every length was built -- the scan then costs one phase C
+ * a length, what runs on the one context cost without their traceback, merge and pass 2.  All entries with
+ * n < 2L share one short-path sweep.  Under a list budget that puts the lists into windows (fseq_set_list_memory), and with
+ * the knob FSEQ_SCAN_REBUILD, every long-path entry is built.  No traceback, merge or pass 2 is run.
+ * Entries may come in any order and may repeat; every entry is filled in place (a repeat carries ms_device 0; the entries of
+ * the short path share one sweep, whose time the first of them carries).
+ * Afterwards the context keeps its own segment length and holds no result (the DP arrays and the lists are those of the last
+ * entry): the getters return FSEQ_E_ARG until the next fseq_run_segmentation, which gives what it gave before the scan.
+ * Refusals, each with fseq_last_error set and nothing written to the entries: no input, a NULL pointer, count == 0 or a
+ * segment_length of 0: FSEQ_E_ARG; a sharded context: FSEQ_E_UNSUPPORTED; a failed allocation: FSEQ_E_OOM, the context stays
+ * usable.  Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+enum { FSEQ_SCAN_LISTS_BUILT = 0, FSEQ_SCAN_LISTS_FOLDED = 1, FSEQ_SCAN_LISTS_NONE = 2 };
+typedef struct fseq_length_scan_entry {
+	uint64_t segment_length;    /* in */
+	uint32_t max_segment_size;  /* out: what fseq_run_segmentation reports at this L (m where the reference cannot reduce) */
+	uint32_t short_path;        /* out: 1 if n < 2L */
+	uint32_t lists;             /* out: BUILT (phase C ran at this L), FOLDED (from the previous entry's lists), NONE (short path) */
+	uint32_t list_cap;          /* out: X of the lists the value was proven on */
+	uint32_t dp_chunks;         /* out: as fseq_timings.dp_chunks */
+	uint32_t reserved;
+	double   ms_device;         /* out: event time spent on this entry alone */
+} fseq_length_scan_entry;        /* 40 bytes */
+typedef struct fseq_length_scan_summary {
+	uint32_t lists_built, lists_folded, short_entries, retries;     /* distinct lengths built / folded, entries on the short path, capacities doubled */
+	double ms_phase_a, ms_phase_b, ms_total;                         /* event times of the one phase A and B; host time of the call */
+} fseq_length_scan_summary;      /* 40 bytes */
+int      fseq_scan_segment_lengths(fseq_ctx *ctx, fseq_length_scan_entry *entries, size_t count, fseq_length_scan_summary *summary);
 
 #ifdef __cplusplus
 }

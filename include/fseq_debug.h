@@ -53,7 +53,7 @@ int  fseq_debug_clock(fseq_ctx *ctx, double *ghz, uint32_t *workgroups);
 /* The library's diagnostic knobs (FSEQ_* names, listed in csrc/fseq_ctx.hpp `struct Tuning`): a context reads them
  * from the environment once, at fseq_create; this sets one afterwards (value NULL = off).  Every knob selects among
  * exact alternatives; results never depend on them.  Call before the first fseq_run_segmentation (a later call drops the work buffers and
- * the result of the context: the geometry may change); on a sharded context before the input is set, identically on
+ * the result of the context: the geometry may change -- but for FSEQ_SCAN_REBUILD, which fseq_scan_segment_lengths alone reads); on a sharded context before the input is set, identically on
  * every rank (FSEQ_E_ARG afterwards: the input is laid out for the block partition in force when it was set). */
 int  fseq_debug_set_tuning(fseq_ctx *ctx, char const *name, char const *value);
 
@@ -166,6 +166,23 @@ int  fseq_debug_red_plan(uint32_t m, uint32_t B, uint32_t bits, int direct, uint
                          uint8_t const *force, int reduced_always, int no_block_list, uint32_t *configs, uint32_t *n_configs, int *verdict,
                          uint8_t *full, int32_t *config_of, int32_t *config_snap_of, uint32_t *blocks, uint32_t *n_blocks, uint32_t *bins,
                          uint32_t *n_bins, uint32_t *summary);
+
+/* The order of work of fseq_scan_segment_lengths (plan_length_scan, csrc/fseq_scanplan.hpp) for an alignment of n columns
+ * (debug / tests; touches no device): the distinct lengths of the long path (n >= 2L), ascending, into long_lengths[count] and
+ * *n_long; slot[i], the place of lengths[i] among them, or -1 where it takes the short path (n < 2L); *n_short, the entries that
+ * do.  FSEQ_E_ARG: a NULL pointer, count == 0, n == 0, a length of 0. */
+int  fseq_debug_scan_plan(uint64_t n, uint64_t const *lengths, uint32_t count, uint64_t *long_lengths, uint32_t *n_long, int32_t *slot,
+                          uint32_t *n_short);
+
+/* One launch of k_relump_lists (csrc/fseq_lengthscan.hpp) on caller-supplied lists (debug / tests; needs no context): the lists
+ * of the columns [k0, k0 + ncols) as phase C leaves them at segment length L_from -- ent[ncols][stride] {value, count} pairs,
+ * entry 0 the lump {k + 1, count of the values >= k + 2 - L_from}, then the distinct values below, descending; hdr[ncols][4] =
+ * {entries, count of value 0, complete, cumulative count} -- are folded in place to what the DP reads at L_to: the leading
+ * entries from index 1 on whose value is >= k + 2 - L_to (0 where k + 2 <= L_to) join the lump, the rest moves down, the header's
+ * first word falls by their number; the words behind the new end and the other header words stay.
+ * Refused before a device is touched, FSEQ_E_ARG: a NULL array, ncols == 0, stride == 0, L_from == 0, L_to < L_from, a header
+ * whose entries are 0 or more than stride, k0 + ncols beyond 2^32. */
+int  fseq_debug_relump_lists(int device, uint64_t k0, uint32_t ncols, uint32_t stride, uint64_t L_from, uint64_t L_to, uint32_t *ent, uint32_t *hdr);
 
 #ifdef __cplusplus
 }
