@@ -76,6 +76,11 @@ class MatchSummary(C.Structure):
                 ("n_founders", C.c_uint32), ("set_words", C.c_uint32), ("ms_device", C.c_double)]
 
 
+class MatchSplitInfo(C.Structure):
+    _fields_ = [("segments", C.c_uint32), ("row_groups", C.c_uint32), ("flagged_groups", C.c_uint32), ("reserved", C.c_uint32),
+                ("overlap", C.c_uint64), ("rows_not_standing", C.c_uint64)]
+
+
 class IdentitySummary(C.Structure):
     _fields_ = [("n", C.c_uint64), ("identity", C.c_uint64), ("kept", C.c_uint64), ("ms_device", C.c_double)]
 
@@ -115,12 +120,13 @@ EXPORTS = [
     "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
     "fseq_write_segments_device", "fseq_random_join_classes_host", "fseq_debug_segments_file", "fseq_debug_random_path",
     "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
+    "fseq_match_rows", "fseq_debug_match_split",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
-                 "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists"]
+                 "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -209,6 +215,8 @@ def load_library():
     L.fseq_match_founder_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
     L.fseq_get_match.argtypes = [vp, vp, vp]
     L.fseq_write_match.argtypes = [vp, C.c_char_p]
+    L.fseq_match_rows.argtypes = [vp, vp, C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
+    L.fseq_debug_match_split.argtypes = [vp, C.POINTER(MatchSplitInfo)]
     L.fseq_identity_columns.argtypes = [vp, vp, C.POINTER(IdentitySummary)]
     L.fseq_create_without_identity_columns.argtypes = [vp, C.POINTER(Params), C.POINTER(vp), C.POINTER(IdentitySummary)]
     L.fseq_get_identity_columns.argtypes = [vp, vp, vp]
@@ -889,6 +897,40 @@ class SegmentationContext:
             self._check(self.L.fseq_match_founder_rows(self.h, rows, K, int(min_segment_length), C.byref(sm)))
         self._match = sm
         return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    def match_rows(self, queries, permutations=None, founders=None, min_segment_length=0):
+        """Thread rows that are NOT the alignment's through the founders (fseq_match_rows): queries a C-contiguous uint8 array
+        [n_rows, n] of raw bytes (or a list of bytes objects of length n); permutations or founders as match_founders takes
+        them.  Returns the summary dict; the `row` of match_pieces() is the query index; match_split() tells how the walk
+        was split along the columns."""
+        if (permutations is None) == (founders is None):
+            raise ValueError("match_rows: give either permutations or founders")
+
+        def as_rows(a, what):
+            if not isinstance(a, np.ndarray):
+                a = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in a], dtype=np.uint8).reshape(len(a), -1)
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            if a.ndim != 2 or a.shape[1] != self.n:
+                raise ValueError("match_rows: %s must be rows of n = %d bytes" % (what, self.n))
+            return a, (C.c_void_p * max(a.shape[0], 1))(*[a.ctypes.data + r * a.strides[0] for r in range(a.shape[0])])
+
+        q, qrows = as_rows(queries, "queries")
+        sm = MatchSummary()
+        if permutations is not None:
+            perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+            self._check(self.L.fseq_match_rows(self.h, perm.ctypes.data, None, 0, qrows, q.shape[0], int(min_segment_length), C.byref(sm)))
+        else:
+            f, frows = as_rows(founders, "founders")
+            self._check(self.L.fseq_match_rows(self.h, None, frows, f.shape[0], qrows, q.shape[0], int(min_segment_length), C.byref(sm)))
+        self._match = sm
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    def match_split(self):
+        """How the last match walked (fseq_debug_match_split): dict(segments, overlap, row_groups, flagged_groups,
+        rows_not_standing)."""
+        info = MatchSplitInfo()
+        self._check(self.L.fseq_debug_match_split(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in MatchSplitInfo._fields_ if k != "reserved"}
 
     def match_pieces(self):
         """(pieces, sets) of the last match: pieces as MATCH_PIECE_DTYPE records ordered by row, then lb; sets[i] the founder

@@ -90,9 +90,106 @@ int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_sum
 	HIP_TRY(c, hipEventElapsedTime(&ms0, mt.ev[0], mt.ev[1]));
 	HIP_TRY(c, hipEventElapsedTime(&ms1, mt.ev[2], mt.ev[3]));
 	mt.sum = fseq_match_summary{tot[0], tot[1], tot[2], tot[3], s.K, s.W, (double) ms0 + (double) ms1};
+	mt.split_info = fseq_match_split_info{1u, (m + MT_T - 1u) / MT_T, 0u, 0u, 0u, 0u};
 	mt.have = true;
 	*out = mt.sum;
 	return FSEQ_OK;
+}
+
+// the rows a split match walks: the alignment's, or the queries of fseq_match_rows
+struct MatchRows { uint8_t const *cols; size_t ld; uint32_t m, bsh; };
+
+template <bool WRITE>
+hipError_t launch_split(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &A, dim3 grid)
+{
+	void (*k)(MatchSplitArgs) = nullptr;
+	switch (s.WR)
+	{
+		case 1: k = k_match_walk_split<1, WRITE>; break;
+		case 2: k = k_match_walk_split<2, WRITE>; break;
+		case 4: k = k_match_walk_split<4, WRITE>; break;
+		case 8: k = k_match_walk_split<8, WRITE>; break;
+		default: k = k_match_walk_split<0, WRITE>; break;
+	}
+	hipError_t const e = allow_lds(k, s.lds);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k, grid, dim3(MT_T), s.lds, c->stream, A);
+	return hipGetLastError();
+}
+
+// run_match with the columns split into plan.G segments (csrc/fseq_match.hpp): counting walk over (row groups x G), the check,
+// the counting walk of the flagged groups unsplit, the scan per (row, g); then both writing walks.  No launch depends on a
+// count the host has not read: the fall-back launches cover every group and the workgroups beyond the list return at once.
+// G = 1 is the unsplit walk through the same kernel, without the check.  ms_device as run_match.
+int run_match_split(fseq_ctx *c, MatchShape const &s, MatchRows const &R, MatchSplitPlan const &plan, uint64_t min_len, fseq_match_summary *out)
+{
+	auto &mt = c->match;
+	hipStream_t st = c->stream;
+	uint32_t const m = R.m, G = plan.G, groups = (m + MT_T - 1u) / MT_T;
+	size_t const slots = (size_t) m * G;
+	int rc;
+	if ((rc = mt.cnt.ensure(c, 3 * slots)) || (rc = mt.off.ensure(c, slots + 1 + 4)) || (rc = mt.split.ensure(c, 2 * slots + 2 * (size_t) groups + 2))) return rc;
+	uint64_t *const d_tot = mt.off + (slots + 1);
+	uint32_t *const d_head = mt.split, *const d_tail = d_head + slots, *const d_flag = d_tail + slots, *const d_list = d_flag + groups, *const d_info = d_list + groups;
+	MatchSplitArgs A{};
+	A.w.msa = R.cols; A.w.ld = R.ld; A.w.m = m; A.w.n = c->p.n; A.w.bsh = R.bsh; A.w.sigma = c->sigma;
+	A.w.fcols = mt.fcols; A.w.K = s.K; A.w.Kp = s.Kp; A.w.W = s.W; A.w.Wk = s.Wk; A.w.TC = s.TC; A.w.min_len = min_len;
+	A.w.cnt = mt.cnt; A.w.off = mt.off;
+	A.G = G; A.GS = G; A.overlap = plan.overlap; A.head = d_head; A.tail = d_tail;
+	MatchSplitArgs F = A;                                          // the fall-back: one segment, into slot 0 of the G
+	F.G = 1; F.list = d_list; F.nlist = d_info;
+	HIP_TRY(c, hipMemsetAsync(d_info, 0, 2 * sizeof(uint32_t), st));
+	hipError_t e = launch_split<false>(c, s, A, dim3(groups, G));
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: split counting walk", e);
+	if (G > 1)
+	{
+		hipLaunchKernelGGL(k_match_split_check, dim3(groups), dim3(MT_T), 0, st, d_head, d_tail, m, G, (uint32_t *) mt.cnt, d_flag, d_list, d_info);
+		HIP_TRY(c, hipGetLastError());
+		e = launch_split<false>(c, s, F, dim3(groups));
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: counting walk of the flagged groups", e);
+	}
+	hipLaunchKernelGGL(k_match_scan_split, dim3(1), dim3(MT_SCAN_T), 0, st, mt.cnt, m, G, mt.off, d_tot);
+	HIP_TRY(c, hipGetLastError());
+	uint64_t tot[4] = {0, 0, 0, 0};
+	uint32_t info[2] = {0, 0};
+	HIP_TRY(c, hipEventRecord(mt.ev[1], st));
+	HIP_TRY(c, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	HIP_TRY(c, hipGetLastError());
+	if ((rc = mt.pieces.ensure(c, (size_t) tot[0])) || (rc = mt.sets.ensure(c, (size_t) tot[0] * s.W))) return rc;
+	A.w.pieces = F.w.pieces = mt.pieces; A.w.sets = F.w.sets = mt.sets;
+	if (G > 1) A.flag = d_flag;
+	HIP_TRY(c, hipEventRecord(mt.ev[2], st));
+	if (info[0] < groups)
+	{
+		e = launch_split<true>(c, s, A, dim3(groups, G));
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: split writing walk", e);
+	}
+	if (info[0])
+	{
+		e = launch_split<true>(c, s, F, dim3(info[0]));
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: writing walk of the flagged groups", e);
+	}
+	HIP_TRY(c, hipEventRecord(mt.ev[3], st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	HIP_TRY(c, hipGetLastError());
+	float ms0 = 0.f, ms1 = 0.f;
+	HIP_TRY(c, hipEventElapsedTime(&ms0, mt.ev[0], mt.ev[1]));
+	HIP_TRY(c, hipEventElapsedTime(&ms1, mt.ev[2], mt.ev[3]));
+	mt.sum = fseq_match_summary{tot[0], tot[1], tot[2], tot[3], s.K, s.W, (double) ms0 + (double) ms1};
+	mt.split_info = fseq_match_split_info{G, groups, info[0], 0u, plan.overlap, info[1]};
+	mt.have = true;
+	*out = mt.sum;
+	return FSEQ_OK;
+}
+
+// FSEQ_MATCH_SPLIT set: fseq_match_founders and fseq_match_founder_rows walk the alignment's rows split as it says
+int run_match_as_tuned(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out)
+{
+	if (!c->tune.match_split) return run_match(c, s, min_len, out);
+	MatchSplitPlan const plan = match_split_plan(c->p.n, c->p.m, 0, (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, false);
+	return run_match_split(c, s, MatchRows{c->d_msa, c->ld, c->p.m, c->bsh}, plan, min_len, out);
 }
 
 int begin_match(fseq_ctx *c, MatchShape const &s)
@@ -114,12 +211,13 @@ inline char *put_u64(char *p, uint64_t v)
 	return p;
 }
 
-// fseq_match_founders and, restored, fseq_match_founders_restored: the founders' columns from the permutations of the run
-int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out, bool restored)
+// the refusals of a match by permutations; X: the founders
+int check_permutations(fseq_ctx *c, bool restored, size_t &X)
 {
 	if (c->sh.on) return refuse_common(c, 0);
 	if (!c->have_result || c->res.short_path) return fail(c, FSEQ_E_ARG, "match: permutations need a finished long-path run (short path: hand the rows of fseq_short_path_runs to fseq_match_founder_rows)");
-	size_t const X = c->res.max_segment_size, S = c->segments.size();
+	X = c->res.max_segment_size;
+	size_t const S = c->segments.size();
 	if (!X || !S) return fail(c, FSEQ_E_ARG, "match: no segments (segmentation failed or was not run)");
 	int rc = refuse_common(c, (uint32_t) X);
 	if (rc) return rc;
@@ -127,14 +225,29 @@ int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_s
 	for (size_t i = 0; i < S; ++i)
 		if (c->segments[i].lb != (i ? c->segments[i - 1].rb : 0u) || (i + 1 == S && c->segments[i].rb != c->p.n))
 			return fail(c, FSEQ_E_ARG, "match: the merged segments do not tile the columns");
-	(void) hipSetDevice(c->p.device);
-	MatchShape const s = match_shape((uint32_t) X, c->sigma, c->bsh);
-	if ((rc = begin_match(c, s))) return rc;
+	return FSEQ_OK;
+}
+
+// what the kernels that lay out the founders' columns read: the caller holds it until the walks behind them have run
+struct FounderTemps {
+	DevTemp<uint32_t> perm;
+	DevTemp<uint64_t> rb;
+	DevTemp<uint8_t> raw, lut;
+	std::vector<uint64_t> rbs;
+	explicit FounderTemps(fseq_ctx *c) : perm(c), rb(c), raw(c), lut(c) {}
+};
+
+// the founders' columns (c->match.fcols, after begin_match) from the permutations of the run; records ev[0] in front of the kernel
+int cols_from_permutations(fseq_ctx *c, uint32_t const *permutations, MatchShape const &s, FounderTemps &T)
+{
+	size_t const X = s.K, S = c->segments.size();
+	int rc;
 	hipStream_t st = c->stream;
-	DevTemp<uint32_t> d_perm(c);
-	DevTemp<uint64_t> d_rb(c);
+	auto &d_perm = T.perm;
+	auto &d_rb = T.rb;
 	if ((rc = d_perm.alloc(S * X)) || (rc = d_rb.alloc(S))) return rc;
-	std::vector<uint64_t> rbs(S);
+	auto &rbs = T.rbs;
+	rbs.resize(S);
 	for (size_t i = 0; i < S; ++i) rbs[i] = c->segments[i].rb;
 	// '-' as k_founders prints it for a slot without a row: its code if the alphabet has one, otherwise a code no row has
 	uint32_t gap = MT_NOCODE;
@@ -145,7 +258,79 @@ int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_s
 	hipLaunchKernelGGL(k_match_founders_cols, dim3((uint32_t) ((c->p.n + 63) / 64)), dim3(256), 0, st, c->d_msa, c->ld, c->p.m, (uint64_t) c->p.n, c->bsh,
 	                   d_perm, (uint32_t) X, d_rb, (uint32_t) S, gap, s.Kp, c->match.fcols);
 	HIP_TRY(c, hipGetLastError());
-	return run_match(c, s, min_segment_length, out, restored);
+	return FSEQ_OK;
+}
+
+// ... from K raw rows
+int cols_from_rows(fseq_ctx *c, uint8_t const *const *founders, MatchShape const &s, FounderTemps &T)
+{
+	hipStream_t st = c->stream;
+	uint64_t const n = c->p.n;
+	uint32_t const K = s.K;
+	int rc;
+	auto &d_raw = T.raw;
+	auto &d_lut = T.lut;
+	if ((rc = d_raw.alloc((size_t) K * n)) || (rc = d_lut.alloc(256))) return rc;
+	uint8_t code_of[256];
+	memset(code_of, (int) MT_NOCODE, sizeof(code_of));             // (a byte outside the alphabet matches nothing)
+	for (uint32_t k = 0; k < c->sigma; ++k) code_of[c->code_to_byte[k]] = (uint8_t) k;
+	for (uint32_t f = 0; f < K; ++f)
+		HIP_TRY(c, hipMemcpyAsync(d_raw + (size_t) f * n, founders[f], n, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(d_lut, code_of, 256, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));                         // (code_of and the caller's rows are read until here; not part of ms_device)
+	HIP_TRY(c, hipEventRecord(c->match.ev[0], st));
+	hipLaunchKernelGGL(k_match_founder_rows, dim3((uint32_t) ((n + 63) / 64)), dim3(256), 0, st, d_raw, n, K, s.Kp, d_lut, c->match.fcols);
+	HIP_TRY(c, hipGetLastError());
+	return FSEQ_OK;
+}
+
+// fseq_match_founders and, restored, fseq_match_founders_restored: the founders' columns from the permutations of the run
+int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out, bool restored)
+{
+	size_t X = 0;
+	int rc = check_permutations(c, restored, X);
+	if (rc) return rc;
+	(void) hipSetDevice(c->p.device);
+	MatchShape const s = match_shape((uint32_t) X, c->sigma, c->bsh);
+	FounderTemps T(c);
+	if ((rc = begin_match(c, s)) || (rc = cols_from_permutations(c, permutations, s, T))) return rc;
+	return restored ? run_match(c, s, min_segment_length, out, true) : run_match_as_tuned(c, s, min_segment_length, out);
+}
+
+// the queries of fseq_match_rows onto the device: column chunks of raw bytes through a bounded temporary, packed by
+// k_match_pack_rows into c->match.qrows at `bsh` / `ld`
+constexpr size_t MT_QUERY_STAGE_BYTES = (size_t) 64 << 20;
+
+int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld)
+{
+	hipStream_t st = c->stream;
+	uint64_t const n = c->p.n;
+	int rc;
+	if ((rc = c->match.qrows.ensure(c, (size_t) n * ld))) return rc;
+	// columns of a chunk: a multiple of 16 (the kernel loads 16 bytes of a row), of 64 where the rows leave the room
+	uint64_t cw = MT_QUERY_STAGE_BYTES / n_rows;
+	cw = cw >= 64 ? cw & ~uint64_t(63) : cw & ~uint64_t(15);
+	if (!cw) return fail(c, FSEQ_E_UNSUPPORTED, "match: more query rows than 16 columns of them fit the upload's 64 MiB");
+	cw = std::min<uint64_t>(cw, (n + 15) & ~uint64_t(15));
+	DevTemp<uint8_t> d_stage(c), d_lut(c);
+	if ((rc = d_stage.alloc((size_t) n_rows * cw)) || (rc = d_lut.alloc(256))) return rc;
+	uint8_t code_of[256];
+	memset(code_of, (int) (c->sigma & 0xFFu), sizeof(code_of));    // (a byte outside the alphabet: the code above the alphabet's; with 256 codes there is no such byte)
+	for (uint32_t k = 0; k < c->sigma; ++k) code_of[c->code_to_byte[k]] = (uint8_t) k;
+	std::vector<uint8_t> stage;
+	try { stage.assign((size_t) n_rows * cw, 0); } catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "match: host staging of the query rows"); }
+	HIP_TRY(c, hipMemcpyAsync(d_lut, code_of, 256, hipMemcpyHostToDevice, st));
+	for (uint64_t c0 = 0; c0 < n; c0 += cw)
+	{
+		uint32_t const w = (uint32_t) std::min<uint64_t>(cw, n - c0);
+		for (uint32_t q = 0; q < n_rows; ++q) memcpy(stage.data() + (size_t) q * cw, rows[q] + c0, w);
+		HIP_TRY(c, hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_match_pack_rows, dim3((w + MT_PACK_COLS - 1u) / MT_PACK_COLS, (n_rows + MT_T - 1u) / MT_T), dim3(MT_T), 0, st,
+		                   d_stage, (size_t) cw, n_rows, c0, w, d_lut, bsh, (uint8_t *) c->match.qrows, ld);
+		HIP_TRY(c, hipGetLastError());
+		HIP_TRY(c, hipStreamSynchronize(st));                     // (the staging is filled again)
+	}
+	return FSEQ_OK;
 }
 
 } // namespace
@@ -176,22 +361,46 @@ int fseq_match_founder_rows(fseq_ctx *c, uint8_t const *const *founders, uint32_
 	if (rc) return rc;
 	(void) hipSetDevice(c->p.device);
 	MatchShape const s = match_shape(K, c->sigma, c->bsh);
-	if ((rc = begin_match(c, s))) return rc;
-	hipStream_t st = c->stream;
-	uint64_t const n = c->p.n;
-	DevTemp<uint8_t> d_raw(c), d_lut(c);
-	if ((rc = d_raw.alloc((size_t) K * n)) || (rc = d_lut.alloc(256))) return rc;
-	uint8_t code_of[256];
-	memset(code_of, (int) MT_NOCODE, sizeof(code_of));             // (a byte outside the alphabet matches nothing)
-	for (uint32_t k = 0; k < c->sigma; ++k) code_of[c->code_to_byte[k]] = (uint8_t) k;
-	for (uint32_t f = 0; f < K; ++f)
-		HIP_TRY(c, hipMemcpyAsync(d_raw + (size_t) f * n, founders[f], n, hipMemcpyHostToDevice, st));
-	HIP_TRY(c, hipMemcpyAsync(d_lut, code_of, 256, hipMemcpyHostToDevice, st));
-	HIP_TRY(c, hipStreamSynchronize(st));                         // (code_of and the caller's rows are read until here; not part of ms_device)
-	HIP_TRY(c, hipEventRecord(c->match.ev[0], st));
-	hipLaunchKernelGGL(k_match_founder_rows, dim3((uint32_t) ((n + 63) / 64)), dim3(256), 0, st, d_raw, n, K, s.Kp, d_lut, c->match.fcols);
-	HIP_TRY(c, hipGetLastError());
-	return run_match(c, s, min_segment_length, out);
+	FounderTemps T(c);
+	if ((rc = begin_match(c, s)) || (rc = cols_from_rows(c, founders, s, T))) return rc;
+	return run_match_as_tuned(c, s, min_segment_length, out);
+}
+
+int fseq_match_rows(fseq_ctx *c, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K,
+                    uint8_t const *const *rows, uint32_t n_rows, uint64_t min_segment_length, fseq_match_summary *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if ((permutations != nullptr) == (founders != nullptr && K != 0)) return fail(c, FSEQ_E_ARG, "match: give either the permutations of the run or K founder rows");
+	if (permutations && (founders || K)) return fail(c, FSEQ_E_ARG, "match: give either the permutations of the run or K founder rows");
+	if (!rows || 0 == n_rows) return fail(c, FSEQ_E_ARG, "match: no query rows");
+	for (uint32_t q = 0; q < n_rows; ++q)
+		if (!rows[q]) return fail(c, FSEQ_E_ARG, "match: null query row");
+	for (uint32_t f = 0; founders && f < K; ++f)
+		if (!founders[f]) return fail(c, FSEQ_E_ARG, "match: null founder row");
+	if (c->idn.have) return fail(c, FSEQ_E_ARG, "match: query rows on a context made by fseq_create_without_identity_columns (its columns are the kept ones of a longer source)");
+	size_t X = K;
+	int rc = permutations ? check_permutations(c, false, X) : refuse_common(c, K);
+	if (rc) return rc;
+	(void) hipSetDevice(c->p.device);
+	// the queries' packing: the narrowest that leaves the code `sigma` free for a byte outside the alphabet
+	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
+	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
+	MatchShape const s = match_shape((uint32_t) X, sigma, bsh);
+	if ((rc = begin_match(c, s)) || (rc = upload_queries(c, rows, n_rows, bsh, ld))) return rc;
+	FounderTemps T(c);
+	if ((rc = permutations ? cols_from_permutations(c, permutations, s, T) : cols_from_rows(c, founders, s, T))) return rc;
+	int cus = 0;
+	(void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->p.device);
+	MatchSplitPlan const plan = match_split_plan(c->p.n, n_rows, (uint32_t) std::max(cus, 1), (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, true);
+	return run_match_split(c, s, MatchRows{c->match.qrows, ld, n_rows, bsh}, plan, min_segment_length, out);
+}
+
+int fseq_debug_match_split(fseq_ctx *c, fseq_match_split_info *info)
+{
+	if (!c || !info) return FSEQ_E_ARG;
+	if (!c->match.have) return fail(c, FSEQ_E_ARG, "no match on this context (fseq_match_founders / fseq_match_founder_rows / fseq_match_rows)");
+	*info = c->match.split_info;
+	return FSEQ_OK;
 }
 
 int fseq_get_match(fseq_ctx *c, fseq_match_piece *pieces, uint32_t *founder_sets)

@@ -139,6 +139,8 @@ struct Tuning {
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
+	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: fseq_match_rows chooses, the other entries walk unsplit)
+	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns a segment's cold walk starts in front of its range (by itself: 16,384)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -189,6 +191,8 @@ struct Tuning {
 			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
 			{"FSEQ_CLASS_GATHER", &Tuning::class_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_SCAN_REBUILD", &Tuning::scan_rebuild, nullptr, 0, 0, nullptr},
+			{"FSEQ_MATCH_SPLIT", nullptr, &Tuning::match_split, 1, 0, nullptr},
+			{"FSEQ_MATCH_OVERLAP", nullptr, &Tuning::match_overlap, 1, 0, nullptr},
 		};
 		return table;
 	}
@@ -489,13 +493,16 @@ struct fseq_ctx {
 		DevBuf<uint64_t> off;                // first piece of every row (+ the total), then the four totals of the summary
 		DevBuf<fseq_match_piece> pieces;     // the last match: pieces by row, then lb
 		DevBuf<uint32_t> sets;               // ... their founder sets, set_words each
+		DevBuf<uint8_t> qrows;               // fseq_match_rows: the query rows, column-major and packed like the alignment
+		DevBuf<uint32_t> split;              // the split walk: head and tail of every (row, g), flag and list of the row groups, {flagged groups, rows that do not stand}
 		bool have = false;
 		fseq_match_summary sum{};
+		fseq_match_split_info split_info{};  // how the last match walked (fseq_debug_match_split)
 		hipEvent_t ev[4]{};
 	} match;
 	void free_match()
 	{
-		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets);
+		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets, match.qrows, match.split);
 		for (auto &e : match.ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
 		match.have = false;
 	}

@@ -30,8 +30,25 @@
 //       the number of these closes from one division; the writing pass loops over the pieces it stores.  An empty gap costs one
 //       uniform compare.  The plain form (RST = false) is a kernel of its own and compiles as before.
 //
+//   k_match_pack_rows   rows that are not the alignment's (fseq_match_rows): a staged chunk of raw query bytes, one row after
+//       the other, is sent through the context's code table, transposed and packed like the alignment, at the narrowest of
+//       2 / 4 / 8 bits that leaves the code `sigma` free for a byte outside the alphabet (the walk sends code >= sigma to the
+//       empty set: an uncovered cell).  16-byte loads along the rows, the code table in LDS, 16-byte stores along the columns.
+//   k_match_walk_split<WR, WRITE>   the walk split along the columns: workgroup (256 rows, segment g of G) walks
+//       [s_g, c_{g+1}) cold from s_g = c_g - overlap and counts / stores only the closes in [c_g, c_{g+1}).  After a close at
+//       column k the state is lb = k, live = set[k][code]: a function of k and the row alone (a cold start at s_g is the
+//       state of a close at s_g).  Every walk keeps `last`, the column of its latest close; head[g] is `last` on reaching c_g,
+//       tail[g] is `last` behind c_{g+1} - 1.  A row STANDS iff head[g] == tail[g - 1] for every g >= 1: then walk g shared a
+//       close with walk g - 1 in front of its own range, and by induction from segment 0 (the true walk) every piece stored is
+//       the true walk's.  Nothing forces such a close to exist (DESIGN.md section 7 has the periodic counter-example), so
+//       k_match_split_check flags every 256-row group with a row that does not stand, and the flagged groups are walked
+//       again by the same kernel with one segment (G = 1 of the split kernel IS the unsplit walk) over the list of them; their
+//       workgroups in the split writing pass return at once.  The counts are [m x G]; k_match_scan_split gives the offsets
+//       per (row, g), so the pieces stay ordered by row, then lb.
+//
 // The walk is sequential along the columns: with m rows only ceil(m / 64) waves are in flight, and the time is a chain over n
-// columns, not throughput (DESIGN.md section 7 prices the split of a row's columns over workgroups; it is not built).
+// columns, not throughput.  fseq_match_founders / fseq_match_founder_rows walk unsplit unless FSEQ_MATCH_SPLIT is set;
+// fseq_match_rows chooses the split by itself (match_split_plan).
 #pragma once
 
 #include "../../include/fseq.h"
@@ -402,6 +419,340 @@ static __global__ __launch_bounds__(MT_SCAN_T) void k_match_scan(uint32_t const 
 	__syncthreads();
 	uint64_t run = s_p[t];
 	for (uint32_t r = lo; r < hi; ++r) { off[r] = run; run += cnt[r]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The split of the columns.  G segments with the bounds c_g = floor(g n / G) (G <= n: none is empty); the cold start of
+// segment g >= 1 is s_g = c_g - clamp(overlap, 1, c_g - c_{g-1}), s_0 = 0.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t MT_SPLIT_MAX = 4096;             // most segments (FSEQ_MATCH_SPLIT)
+// fseq_match_rows by itself: about MT_SPLIT_WG_PER_CU workgroups a CU, segments of at least MT_SPLIT_MIN_OVERLAPS overlaps of
+// MT_SPLIT_OVERLAP columns.  From one measurement (profiles/match_split_C3_overlap4096.txt): rows of C3's population held out of the
+// reconstruction stand at an overlap of 16,384 columns and none does at 4,096, the value this started from; a segment of one
+// overlap (G = 61 on C3's 1,000,000 columns) was the fastest shape measured.  No other input has been measured.
+constexpr uint32_t MT_SPLIT_WG_PER_CU = 2;
+constexpr uint64_t MT_SPLIT_OVERLAP = 16384;
+constexpr uint64_t MT_SPLIT_MIN_OVERLAPS = 1;
+
+__host__ __device__ inline uint64_t mt_seg_bound(uint64_t n, uint32_t G, uint32_t g) { return (uint64_t) g * n / G; }
+__host__ __device__ inline uint64_t mt_seg_start(uint64_t n, uint32_t G, uint32_t g, uint64_t overlap)
+{
+	if (0 == g) return 0;
+	uint64_t const c = mt_seg_bound(n, G, g);
+	return c - mt_max(1u, mt_min(overlap, c - mt_seg_bound(n, G, g - 1u)));
+}
+
+struct MatchSplitPlan { uint32_t G; uint64_t overlap; };
+
+// forced_g / forced_overlap: the knobs (0: not set).  by_itself: fseq_match_rows' own choice where forced_g is 0
+inline MatchSplitPlan match_split_plan(uint64_t n, uint32_t rows, uint32_t cus, uint32_t forced_g, uint64_t forced_overlap, bool by_itself)
+{
+	MatchSplitPlan p{1u, forced_overlap ? forced_overlap : MT_SPLIT_OVERLAP};
+	if (forced_g) p.G = forced_g;
+	else if (by_itself)
+	{
+		uint64_t const groups = ((uint64_t) rows + MT_T - 1u) / MT_T;
+		uint64_t const want = std::max<uint64_t>(1u, (uint64_t) MT_SPLIT_WG_PER_CU * std::max(cus, 1u) / groups);
+		p.G = (uint32_t) std::max<uint64_t>(1u, std::min<uint64_t>(want, n / (MT_SPLIT_MIN_OVERLAPS * p.overlap)));
+	}
+	p.G = (uint32_t) std::max<uint64_t>(1u, std::min<uint64_t>(std::min<uint32_t>(p.G, MT_SPLIT_MAX), n));
+	uint64_t const longest = (n + p.G - 1u) / p.G;
+	p.overlap = p.G > 1u ? mt_max(1u, mt_min(p.overlap, longest)) : 0u;
+	return p;
+}
+
+struct MatchSplitArgs {
+	MatchWalkArgs w;                                 // cnt: [3][m x GS]; off: [m x GS]
+	uint32_t G, GS;                                  // segments this launch walks; segments of the count arrays (the fall-back: G = 1 into slot 0 of GS)
+	uint64_t overlap;
+	uint32_t *head, *tail;                           // WRITE = false: [m x GS]
+	uint32_t const *flag;                            // the split launch, WRITE = true: groups that fell back return at once (or nullptr)
+	uint32_t const *list, *nlist;                    // the fall-back launch: the flagged groups and their number (or nullptr)
+};
+
+// LDS as k_match_walk's plain form.  grid: (row groups, G), or -- A.list -- (row groups) of which the first *A.nlist work
+template <uint32_t WR, bool WRITE>
+static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs const S)
+{
+	extern __shared__ uint4 mt_smem[];
+	MatchWalkArgs const &A = S.w;
+	uint32_t grp = blockIdx.x;
+	uint32_t const g = S.list ? 0u : blockIdx.y;
+	if (S.list)
+	{
+		if (blockIdx.x >= *S.nlist) return;
+		grp = S.list[blockIdx.x];
+	}
+	else if (S.flag && S.flag[grp]) return;
+	uint32_t const tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+	uint32_t const bsh = A.bsh, bits = 8u >> bsh, cmask = (1u << bits) - 1u, smask = (1u << bsh) - 1u;
+	uint32_t const rowbytes = MT_T >> bsh, cpc = rowbytes / 16u;
+	uint32_t const Kp = A.Kp, K = A.K, Wk = A.Wk, TC = A.TC, sigma = A.sigma, groups = Kp / 64u;
+	uint8_t *const fst = reinterpret_cast<uint8_t *>(mt_smem);
+	uint8_t *const syms = fst + (size_t) TC * Kp;
+	uint32_t *const sets = reinterpret_cast<uint32_t *>(syms + (size_t) TC * rowbytes);
+	uint32_t *const empty_set = sets + (size_t) TC * sigma * Wk;
+	uint32_t *const live_lds = empty_set + Wk + tid;
+	size_t const slice = (size_t) grp * rowbytes;
+	uint32_t const row = grp * MT_T + tid;
+	bool const active = row < A.m;
+	uint64_t const n = A.n, min_len = A.min_len;
+	uint64_t const c_lo = mt_seg_bound(n, S.G, g), c_hi = mt_seg_bound(n, S.G, g + 1u), s_lo = mt_seg_start(n, S.G, g, S.overlap);
+	size_t const slot = (size_t) row * S.GS + g, total = (size_t) A.m * S.GS;
+
+	for (uint32_t i = tid; i < Wk; i += MT_T) empty_set[i] = 0u;
+
+	MatchLive<WR> live(live_lds, Wk);
+	auto all_founders = [&]() {
+		for (uint32_t i = 0; i < live.words(); ++i)
+			live.set(i, K >= 32u * (i + 1u) ? ~0u : (K > 32u * i ? (1u << (K - 32u * i)) - 1u : 0u));
+	};
+	all_founders();
+	uint64_t lb = s_lo;
+	uint32_t last = (uint32_t) s_lo, head = (uint32_t) s_lo;
+	uint32_t npieces = 0, nunc = 0, nshort = 0;
+	bool alive = true;
+	uint64_t const out0 = (WRITE && active) ? A.off[slot] : 0;
+
+	auto emit = [&](uint64_t rb) {
+		if (WRITE)
+		{
+			uint64_t const at = out0 + npieces;
+			uint32_t pc = 0;
+			for (uint32_t i = 0; i < live.words(); ++i)
+			{
+				uint32_t const v = live.get(i);
+				pc += __popc(v);
+				if (i < A.W) A.sets[at * A.W + i] = v;
+			}
+			fseq_match_piece *const p = A.pieces + at;
+			p->lb = lb; p->rb = rb; p->row = row; p->n_founders = pc;
+		}
+		++npieces;
+	};
+
+	uint4 rf[MT_PREFETCH], rs[MT_PREFETCH];
+	auto prefetch = [&](uint64_t c0, uint32_t tc) {
+		uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
+		uint4 const *const fsrc = reinterpret_cast<uint4 const *>(A.fcols + c0 * Kp);
+#pragma unroll
+		for (uint32_t j = 0; j < MT_PREFETCH; ++j)
+		{
+			uint32_t const q = tid + j * MT_T;
+			rf[j] = q < nf ? fsrc[q] : make_uint4(0, 0, 0, 0);
+			uint32_t const col = q / cpc, ch = q - col * cpc;
+			size_t const at = slice + (size_t) ch * 16u;
+			rs[j] = (q < ns && at < A.ld) ? *reinterpret_cast<uint4 const *>(A.msa + (c0 + col) * A.ld + at) : make_uint4(0, 0, 0, 0);
+		}
+	};
+
+	prefetch(s_lo, (uint32_t) mt_min(TC, c_hi - s_lo));
+	for (uint64_t c0 = s_lo; c0 < c_hi; c0 += TC)
+	{
+		uint32_t const tc = (uint32_t) mt_min(TC, c_hi - c0);
+		{
+			uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
+#pragma unroll
+			for (uint32_t j = 0; j < MT_PREFETCH; ++j)
+			{
+				uint32_t const q = tid + j * MT_T;
+				if (q < nf) reinterpret_cast<uint4 *>(fst)[q] = rf[j];
+				if (q < ns) reinterpret_cast<uint4 *>(syms)[q] = rs[j];
+			}
+			for (uint32_t i = tid; i < tc * sigma * Wk; i += MT_T) sets[i] = 0u;
+		}
+		__syncthreads();
+		if (c0 + TC < c_hi) prefetch(c0 + TC, (uint32_t) mt_min(TC, c_hi - c0 - TC));
+		for (uint32_t it = wv; it < tc * groups; it += MT_T / 64u)
+		{
+			uint32_t const j = it / groups, fg = it - j * groups, f = fg * 64u + lane;
+			uint32_t const code = fst[j * Kp + f];
+			bool const todo = f < K && code < sigma;
+			unsigned long long rem = __ballot(todo);
+			while (rem)
+			{
+				uint32_t const s = (uint32_t) __shfl((int) code, (int) (__ffsll((long long) rem) - 1));
+				unsigned long long const b = __ballot(todo && code == s);
+				rem &= ~b;
+				uint32_t *const dst = sets + ((size_t) j * sigma + s) * Wk;
+				if (lane == 0 && 2u * fg < Wk) dst[2u * fg] = (uint32_t) b;
+				if (lane == 1 && 2u * fg + 1u < Wk) dst[2u * fg + 1u] = (uint32_t) (b >> 32);
+			}
+		}
+		__syncthreads();
+		if (active)
+			for (uint32_t j = 0; j < tc; ++j)
+			{
+				uint64_t const k = c0 + j;
+				bool const mine = k >= c_lo;                                 // (uniform: the closes in front of c_g belong to the segment before)
+				if (k == c_lo) head = last;
+				uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
+				uint32_t const *const M = code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set;
+				bool recheck = false;
+				uint32_t any = 0;
+				uint32_t nv[WR ? WR : 1];
+				if (min_len != 0 && min_len <= k - lb) recheck = true;
+				else
+				{
+					if (WR)
+					{
+						for (uint32_t i = 0; i < live.words(); ++i) { nv[i] = live.get(i) & M[i]; any |= nv[i]; }
+					}
+					else
+					{
+						for (uint32_t i = 0; i < live.words() && !any; ++i) any = live.get(i) & M[i];
+					}
+					if (!any) { if (min_len != 0 && mine) ++nshort; recheck = true; }
+				}
+				if (recheck)
+				{
+					if (mine) emit(k);
+					lb = k;
+					last = (uint32_t) k;
+					any = 0;
+					for (uint32_t i = 0; i < live.words(); ++i) { uint32_t const v = M[i]; live.set(i, v); any |= v; }
+					if (!any && mine) ++nunc;
+				}
+				else if (WR)
+				{
+					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, nv[i]);
+				}
+				else
+				{
+					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, live.get(i) & M[i]);
+				}
+				alive = any != 0;
+			}
+		__syncthreads();
+	}
+	if (active)
+	{
+		if (c_hi == n && alive) emit(n);
+		if (!WRITE)
+		{
+			A.cnt[slot] = npieces; A.cnt[total + slot] = nunc; A.cnt[2u * total + slot] = nshort;
+			S.head[slot] = head; S.tail[slot] = last;
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// The check of a split counting walk.  Workgroup: one group of 256 rows.  A row stands iff head[g] == tail[g - 1] for every
+// g >= 1.  A group with a row that does not stand is flagged and joins the list (in no particular order), and its counts are
+// cleared but for slot 0 of every row, which the fall-back walk writes.  info = {flagged groups, rows that do not stand};
+// both zero before the launch.
+// ------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(MT_T) void k_match_split_check(
+	uint32_t const *__restrict__ head, uint32_t const *__restrict__ tail, uint32_t m, uint32_t G, uint32_t *__restrict__ cnt,
+	uint32_t *__restrict__ flag, uint32_t *__restrict__ list, uint32_t *__restrict__ info)
+{
+	__shared__ uint32_t s_bad;
+	uint32_t const grp = blockIdx.x, row = grp * MT_T + threadIdx.x;
+	if (0 == threadIdx.x) s_bad = 0u;
+	__syncthreads();
+	bool bad = false;
+	if (row < m)
+		for (uint32_t g = 1; g < G && !bad; ++g) bad = head[(size_t) row * G + g] != tail[(size_t) row * G + g - 1u];
+	if (bad) atomicAdd(&s_bad, 1u);
+	__syncthreads();
+	uint32_t const nbad = s_bad;
+	if (0 == threadIdx.x)
+	{
+		flag[grp] = nbad ? 1u : 0u;
+		if (nbad) { list[atomicAdd(&info[0], 1u)] = grp; atomicAdd(&info[1], nbad); }
+	}
+	if (!nbad) return;
+	size_t const total = (size_t) m * G, lo = (size_t) grp * MT_T * G, hi = mt_min(total, lo + (size_t) MT_T * G);
+	for (size_t i = lo + threadIdx.x; i < hi; i += MT_T)
+		if (i % G) { cnt[i] = 0u; cnt[total + i] = 0u; cnt[2u * total + i] = 0u; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_match_scan for counts per (row, g), cnt[3][m x G]: off[0 .. m G] (off[m G] = all pieces) and the same four totals, the
+// most pieces of a ROW among them.  One workgroup; a thread sums a run of whole rows.
+// ------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(MT_SCAN_T) void k_match_scan_split(uint32_t const *__restrict__ cnt, uint32_t m, uint32_t G, uint64_t *__restrict__ off, uint64_t *__restrict__ tot)
+{
+	__shared__ uint64_t s_p[MT_SCAN_T], s_u[MT_SCAN_T], s_s[MT_SCAN_T], s_x[MT_SCAN_T];
+	uint32_t const t = threadIdx.x, per = (m + MT_SCAN_T - 1u) / MT_SCAN_T;
+	uint32_t const lo = min(m, t * per), hi = min(m, lo + per);
+	size_t const total = (size_t) m * G;
+	uint64_t p = 0, u = 0, s = 0, x = 0;
+	for (uint32_t r = lo; r < hi; ++r)
+	{
+		uint64_t mine = 0;
+		for (size_t i = (size_t) r * G; i < (size_t) (r + 1u) * G; ++i) { mine += cnt[i]; u += cnt[total + i]; s += cnt[2u * total + i]; }
+		p += mine;
+		x = mt_max(x, mine);
+	}
+	s_p[t] = p; s_u[t] = u; s_s[t] = s; s_x[t] = x;
+	__syncthreads();
+	if (t == 0)
+	{
+		uint64_t run = 0, su = 0, ss = 0, mx = 0;
+		for (uint32_t i = 0; i < MT_SCAN_T; ++i)
+		{
+			uint64_t const v = s_p[i];
+			s_p[i] = run; run += v;
+			su += s_u[i]; ss += s_s[i]; mx = mt_max(mx, s_x[i]);
+		}
+		off[total] = run;
+		tot[0] = run; tot[1] = su; tot[2] = ss; tot[3] = mx;
+	}
+	__syncthreads();
+	uint64_t run = s_p[t];
+	for (size_t i = (size_t) lo * G; i < (size_t) hi * G; ++i) { off[i] = run; run += cnt[i]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Query rows onto the device (fseq_match_rows).  raw: a staged chunk, row q's bytes of the columns [c0, c0 + cw) at
+// raw[q * stride .. ] (stride a multiple of 16, the base 16-byte aligned).  Workgroup: 64 columns x 256 rows.  Every byte goes
+// through lut (its code, or `sigma` for a byte outside the alphabet) into an LDS tile [column][row]; then a lane packs 16 output
+// bytes of one column (16 << bsh rows) and stores them.  Rows beyond n_rows are code 0: the padding fields and the bytes up to
+// ld are zeros (ld a multiple of 16 and at most the row groups' bytes: every byte of a column is written).
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t MT_PACK_COLS = 64;
+constexpr uint32_t MT_PACK_LD = MT_T + 16;          // bytes of a column of the tile (16-byte aligned rows of it)
+
+static __global__ __launch_bounds__(MT_T) void k_match_pack_rows(
+	uint8_t const *__restrict__ raw, size_t stride, uint32_t n_rows, uint64_t c0, uint32_t cw, uint8_t const *__restrict__ code_of, uint32_t bsh,
+	uint8_t *__restrict__ out, size_t ld)
+{
+	__shared__ uint8_t lut[256];
+	__shared__ __attribute__((aligned(16))) uint8_t tile[MT_PACK_COLS][MT_PACK_LD];
+	uint32_t const tid = threadIdx.x;
+	lut[tid] = code_of[tid];
+	__syncthreads();
+	uint32_t const j0 = blockIdx.x * MT_PACK_COLS, r0 = blockIdx.y * MT_T;
+	for (uint32_t i = tid; i < MT_T * (MT_PACK_COLS / 16u); i += MT_T)
+	{
+		uint32_t const r = i / (MT_PACK_COLS / 16u), part = i % (MT_PACK_COLS / 16u), j = j0 + part * 16u;
+		uint4 v = make_uint4(0, 0, 0, 0);
+		bool const in = r0 + r < n_rows && j < stride;
+		if (in) v = *reinterpret_cast<uint4 const *>(raw + (size_t) (r0 + r) * stride + j);
+		uint32_t const w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+		for (uint32_t b = 0; b < 16u; ++b)
+			tile[part * 16u + b][r] = in ? lut[(w[b / 4u] >> (8u * (b % 4u))) & 0xFFu] : (uint8_t) 0;
+	}
+	__syncthreads();
+	uint32_t const bits = 8u >> bsh, per = 1u << bsh, rowbytes = MT_T >> bsh, cpc = rowbytes / 16u;
+	for (uint32_t i = tid; i < MT_PACK_COLS * cpc; i += MT_T)
+	{
+		uint32_t const col = i / cpc, ch = i - col * cpc;
+		size_t const at = (size_t) blockIdx.y * rowbytes + (size_t) ch * 16u;
+		if (j0 + col >= cw || at >= ld) continue;
+		uint8_t const *const src = &tile[col][ch * 16u * per];
+		uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+		for (uint32_t b = 0; b < 16u; ++b)
+		{
+			uint32_t byte = 0;
+			for (uint32_t e = 0; e < per; ++e) byte |= (uint32_t) src[b * per + e] << (e * bits);
+			w[b / 4u] |= byte << (8u * (b % 4u));
+		}
+		*reinterpret_cast<uint4 *>(out + (c0 + j0 + col) * ld + at) = make_uint4(w[0], w[1], w[2], w[3]);
+	}
 }
 
 } // namespace fseq

@@ -45,6 +45,11 @@ char const *const USAGE =
 	"      --output-matches=PATH          Match the input against the founders on the device and write the report of\n"
 	"                                     match-sequences-to-founders (SEQUENCE_INDEX LB RB FOUNDER_INDICES; one GPU only)\n"
 	"      --match-min-segment-length=N   ... closing a piece as soon as it has N columns  (default=`0': only where no founder continues)\n"
+	"      --match-sequences=LIST         Match sequences that are not the input's -- a list file of sequences of the input's length, held\n"
+	"                                     out of the segmentation -- against the founders on the device (one GPU only; not together\n"
+	"                                     with --remove-identity-columns; requires --output-sequence-matches)\n"
+	"      --output-sequence-matches=PATH ... and write the report of match-sequences-to-founders for them (honours\n"
+	"                                     --match-min-segment-length; requires --match-sequences)\n"
 	"      --remove-identity-columns      Segment only the columns in which the sequences differ and put the others back into the\n"
 	"                                     founders from the first sequence (remove-identity-columns | founder_sequences |\n"
 	"                                     insert-identity-columns in one run; segments in reduced co-ordinates; one GPU only)\n"
@@ -186,6 +191,25 @@ bool report_match(fseq_ctx *ctx, int rc, fseq_match_summary const &sm, char cons
 	return true;
 }
 
+// --match-sequences: the held-out sequences against the founders the context has (permutations) or the rows given
+bool match_held_out(fseq_ctx *ctx, char const *list, size_t seq_length, uint32_t const *perm, uint8_t const *const *frows, uint32_t K,
+                    unsigned long long min_len, char const *path)
+{
+	std::cerr << "Matching the sequences of '" << list << "' against the founders…" << std::endl;
+	std::vector<std::string> queries;
+	if (!read_list_file(list, queries)) return false;
+	if (queries.empty() || queries.size() > 0xFFFFFFFFull) { std::cerr << "No sequences to match in '" << list << "'." << std::endl; return false; }
+	std::vector<uint8_t const *> qrows(queries.size());
+	for (size_t i = 0; i < queries.size(); ++i)
+	{
+		if (queries[i].size() != seq_length) { std::cerr << "The sequences to match must have the length of the input's (" << seq_length << ")." << std::endl; return false; }
+		qrows[i] = reinterpret_cast<uint8_t const *>(queries[i].data());
+	}
+	fseq_match_summary sm{};
+	int const rc(fseq_match_rows(ctx, perm, frows, K, qrows.data(), (uint32_t) qrows.size(), min_len, &sm));
+	return report_match(ctx, rc, sm, path);
+}
+
 std::ostream *open_out(char const *path, std::ofstream &file)
 {
 	if (!path || ('-' == path[0] && '\0' == path[1])) return &std::cout;
@@ -234,6 +258,7 @@ bool parse_scan_spec(char const *spec, std::vector<uint64_t> &out)
 int main(int argc, char **argv)
 {
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr;
+	char const *match_seqs = nullptr, *out_seq_matches = nullptr;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
 	bool match_min_len_bad = false;
@@ -264,6 +289,7 @@ int main(int argc, char **argv)
 		{"output-restored-matches", required_argument, nullptr, 1009}, {"upload-memory", required_argument, nullptr, 1010},
 		{"scan-segment-lengths", required_argument, nullptr, 1011}, {"output-scan", required_argument, nullptr, 1012},
 		{"max-founders", required_argument, nullptr, 1013},
+		{"match-sequences", required_argument, nullptr, 1014}, {"output-sequence-matches", required_argument, nullptr, 1015},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -334,6 +360,8 @@ int main(int argc, char **argv)
 				max_founders_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || 0 == max_founders;
 				break;
 			}
+			case 1014: match_seqs = optarg; break;
+			case 1015: out_seq_matches = optarg; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -367,6 +395,10 @@ int main(int argc, char **argv)
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
 	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (match_seqs && !out_seq_matches) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
+	if (out_seq_matches && !match_seqs) { std::cerr << "--output-sequence-matches requires --match-sequences." << std::endl; return EXIT_FAILURE; }
+	if (match_seqs && gpus > 1) { std::cerr << "--match-sequences is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (match_seqs && remove_identity) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
@@ -543,7 +575,7 @@ int main(int argc, char **argv)
 		std::cerr << "Outputting…" << std::endl;
 		std::ostream &os = *open_out(out_founders, founders_file);
 		// (--upload-memory: the founders are input rows, read now from the files the runs name, one at a time)
-		std::vector<std::string> named(upload_given && out_matches ? res.max_segment_size : 0);
+		std::vector<std::string> named(upload_given && (out_matches || match_seqs) ? res.max_segment_size : 0);
 		for (uint32_t i = 0; i < res.max_segment_size; ++i)
 		{
 			std::string one;
@@ -570,6 +602,12 @@ int main(int argc, char **argv)
 			fseq_match_summary sm{};
 			rc = fseq_match_founder_rows(ctx, frows.data(), res.max_segment_size, match_min_len, &sm);
 			if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
+		}
+		if (match_seqs)
+		{
+			std::vector<uint8_t const *> frows(res.max_segment_size);
+			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = upload_given ? reinterpret_cast<uint8_t const *>(named[i].data()) : rows[first[i]];
+			if (!match_held_out(ctx, match_seqs, seq_length, nullptr, frows.data(), res.max_segment_size, match_min_len, out_seq_matches)) return EXIT_FAILURE;
 		}
 		if (out_restored_matches)
 		{
@@ -665,6 +703,7 @@ int main(int argc, char **argv)
 		rc = fseq_match_founders(ctx, perm.data(), match_min_len, &sm);
 		if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
 	}
+	if (match_seqs && !match_held_out(ctx, match_seqs, seq_length, perm.data(), nullptr, 0, match_min_len, out_seq_matches)) return EXIT_FAILURE;
 	if (out_restored_matches)
 	{
 		// the last step of the chain: the full-length input against the founders just written, in the source's co-ordinates

@@ -362,6 +362,19 @@ int  fseq_get_match(fseq_ctx *ctx, fseq_match_piece *pieces, uint32_t *founder_s
 /* the tool's stdout, byte for byte (header line, then SEQUENCE_INDEX LB RB FOUNDER_INDICES per piece,
  * match_founder_sequences.cc:125-136, :220); path NULL or "-" = stdout */
 int  fseq_write_match(fseq_ctx *ctx, char const *path);
+/* Rows that are NOT the alignment's (held-out validation): n_rows query rows of n raw bytes each, rows[q] the bytes of query q,
+ * matched against the founders of the finished run (permutations, as fseq_match_founders) or against K raw founder rows
+ * (founders / K, as fseq_match_founder_rows) -- exactly one of the two is given, FSEQ_E_ARG otherwise.  The queries go through the
+ * context's code table; a byte outside the alignment's alphabet is an uncovered cell, as in the tool.  They are uploaded in
+ * column chunks through a temporary of at most 64 MiB and held packed like the alignment.  The walk is split along the
+ * columns over workgroups and checked for exactness (csrc/fseq_match.hpp; fseq_debug_match_split tells how it went).
+ * fseq_match_piece::row is the query index; the report of fseq_write_match is match-sequences-to-founders' stdout for these
+ * sequences and founders.  Refusals as the other entries (sharded context, no alignment, K > 2,048, n >= 2^32 - 1, permutations
+ * without a finished long-path run); FSEQ_E_ARG also for rows == NULL, a NULL row, n_rows == 0 and a context made by
+ * fseq_create_without_identity_columns.  The result replaces the context's last match.  Detected by symbol: FSEQ_ABI_VERSION
+ * stays 5. */
+int  fseq_match_rows(fseq_ctx *ctx, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K,
+                     uint8_t const *const *rows, uint32_t n_rows, uint64_t min_segment_length, fseq_match_summary *out);
 
 /* ---- identity columns dropped and put back on the device ----
  * replaces: remove-identity-columns (remove-identity-columns/main.cc:105-153 the comparison of a chunk of every text,

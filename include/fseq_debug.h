@@ -184,6 +184,18 @@ int  fseq_debug_scan_plan(uint64_t n, uint64_t const *lengths, uint32_t count, u
  * whose entries are 0 or more than stride, k0 + ncols beyond 2^32. */
 int  fseq_debug_relump_lists(int device, uint64_t k0, uint32_t ncols, uint32_t stride, uint64_t L_from, uint64_t L_to, uint32_t *ent, uint32_t *hdr);
 
+/* How the last match of the context walked (csrc/fseq_match.hpp, k_match_walk_split): the segments G the columns were split
+ * into (1: unsplit) and the overlap in use (clamped to the longest segment; 0 where G = 1), the groups of 256 rows, how many of
+ * them were flagged by the check and walked again unsplit, and the rows that did not stand (head[g] != tail[g - 1] for some g).
+ * FSEQ_MATCH_SPLIT=g (1..4,096) and FSEQ_MATCH_OVERLAP=columns force the shape for fseq_match_rows and, with FSEQ_MATCH_SPLIT
+ * set, for fseq_match_founders and fseq_match_founder_rows, which walk unsplit otherwise (fseq_debug_set_tuning takes both at any
+ * time: nothing of a run depends on them).  FSEQ_E_ARG before a match. */
+typedef struct fseq_match_split_info {
+	uint32_t segments, row_groups, flagged_groups, reserved;
+	uint64_t overlap, rows_not_standing;
+} fseq_match_split_info;
+int  fseq_debug_match_split(fseq_ctx *ctx, fseq_match_split_info *info);
+
 #ifdef __cplusplus
 }
 #endif
