@@ -85,6 +85,10 @@ class IdentitySummary(C.Structure):
     _fields_ = [("n", C.c_uint64), ("identity", C.c_uint64), ("kept", C.c_uint64), ("ms_device", C.c_double)]
 
 
+class HoldOutSummary(C.Structure):
+    _fields_ = [("m_src", C.c_uint32), ("held", C.c_uint32), ("kept", C.c_uint32), ("reserved", C.c_uint32), ("ms_device", C.c_double)]
+
+
 class LengthScanSummary(C.Structure):
     _fields_ = [("lists_built", C.c_uint32), ("lists_folded", C.c_uint32), ("short_entries", C.c_uint32), ("retries", C.c_uint32),
                 ("ms_phase_a", C.c_double), ("ms_phase_b", C.c_double), ("ms_total", C.c_double)]
@@ -121,12 +125,14 @@ EXPORTS = [
     "fseq_write_segments_device", "fseq_random_join_classes_host", "fseq_debug_segments_file", "fseq_debug_random_path",
     "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
     "fseq_match_rows", "fseq_debug_match_split",
+    "fseq_create_without_rows", "fseq_get_held_out", "fseq_match_held_out", "fseq_debug_held_out_columns", "fseq_debug_row_split_plan",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
-                 "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split"]
+                 "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
+                 "fseq_debug_held_out_columns", "fseq_debug_row_split_plan"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -249,6 +255,11 @@ def load_library():
     L.fseq_scan_segment_lengths.argtypes = [vp, vp, sz, C.POINTER(LengthScanSummary)]
     L.fseq_debug_scan_plan.argtypes = [u64, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32)]
     L.fseq_debug_relump_lists.argtypes = [C.c_int, u64, C.c_uint32, C.c_uint32, u64, u64, vp, vp]
+    L.fseq_create_without_rows.argtypes = [vp, vp, C.c_uint32, C.POINTER(Params), C.POINTER(vp), C.POINTER(HoldOutSummary)]
+    L.fseq_get_held_out.argtypes = [vp, vp, vp]
+    L.fseq_match_held_out.argtypes = [vp, vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
+    L.fseq_debug_held_out_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.fseq_debug_row_split_plan.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -435,6 +446,29 @@ def scan_plan_host(n, lengths):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return long_lengths[:n_long.value].copy(), slot[:len(lengths)].copy(), n_short.value
+
+
+def row_split_plan_host(m, bits, held):
+    """The plan of a split along the rows (row_split_plan, csrc/fseq_rowsplit_plan.hpp) for m rows at `bits` bits a code with the
+    rows of `held` set aside: (kept, base, keep, n_slow) -- the rows that stay, ascending, and one descriptor per 32-bit word of a
+    kept column (include/fseq_debug.h, fseq_debug_row_split_plan); n_slow words have keep = 0.  FseqError(FSEQ_E_ARG) for a list
+    without_rows() refuses.  No device is touched."""
+    L = load_library()
+    held = np.ascontiguousarray(held, dtype=np.uint32)
+    if held.ndim != 1:
+        raise FseqError(FSEQ_E_ARG, "row_split_plan_host: one row index per entry")
+    m, bits = int(m), int(bits)
+    n_kept = max(m - len(held), 0)
+    n_words = (n_kept + 32 // bits - 1) // (32 // bits) if bits in (2, 4, 8) else 0
+    kept = np.zeros(max(1, n_kept), dtype=np.uint32)
+    base = np.zeros(max(1, n_words), dtype=np.uint32)
+    keep = np.zeros(max(1, n_words), dtype=np.uint32)
+    nw, ns = C.c_uint32(), C.c_uint32()
+    rc = L.fseq_debug_row_split_plan(m, bits, held.ctypes.data if len(held) else None, len(held), kept.ctypes.data, base.ctypes.data, keep.ctypes.data,
+                                     C.byref(nw), C.byref(ns))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return kept[:n_kept].copy(), base[:nw.value].copy(), keep[:nw.value].copy(), ns.value
 
 
 def relump_lists(ent, hdr, k0, L_from, L_to, device=0):
@@ -945,6 +979,65 @@ class SegmentationContext:
     def write_match(self, path):
         """The report of match-sequences-to-founders for the last match (SEQUENCE_INDEX LB RB FOUNDER_INDICES)."""
         self._check(self.L.fseq_write_match(self.h, path.encode() if path else None))
+
+    # ---- rows held out of the resident alignment and matched on the device
+    def without_rows(self, held_rows, segment_length, block_len=0, list_cap=0, list_memory=0):
+        """A new SegmentationContext over the rows that are not in held_rows (fseq_create_without_rows): the kept rows in this
+        context's order, numbered 0 .. kept - 1, and the held-out rows aside on the device for match_held_out().  held_rows:
+        distinct row indices, any order.  This context may be closed afterwards, or serve the next fold."""
+        held = np.ascontiguousarray(held_rows, dtype=np.uint32).reshape(-1)
+        p = Params(0, 0, int(segment_length), 0, int(block_len), int(list_cap), int(self._device))
+        h = C.c_void_p()
+        sm = HoldOutSummary()
+        self._check(self.L.fseq_create_without_rows(self.h, held.ctypes.data if len(held) else None, len(held), C.byref(p), C.byref(h), C.byref(sm)))
+        new = SegmentationContext.__new__(SegmentationContext)
+        new.L, new.h = self.L, h
+        new.m, new.n, new.segment_length, new._device = int(sm.kept), self.n, int(segment_length), self._device
+        new.result, new._keep = None, None
+        new.source_m = int(sm.m_src)
+        new.n_held = int(sm.held)
+        new.held_out_summary = {k: getattr(sm, k) for k, _ in HoldOutSummary._fields_ if k != "reserved"}
+        if list_memory:
+            new.set_list_memory(list_memory)
+        return new
+
+    def held_out(self):
+        """On a context made by without_rows(): (kept_rows, held_rows) -- the source row of every row of this context, ascending,
+        and the held-out rows in the order they were given (the `row` of match_held_out()'s pieces indexes this list)."""
+        kept = np.zeros(self.m, dtype=np.uint32)
+        held = np.zeros(max(1, getattr(self, "n_held", 0)), dtype=np.uint32)
+        self._check(self.L.fseq_get_held_out(self.h, kept.ctypes.data, held.ctypes.data))
+        return kept, held[:getattr(self, "n_held", 0)]
+
+    def held_out_columns(self, c0=0, c1=None):
+        """... (bytes [c1 - c0, ld_h], bits): the held-out rows as they are stored, padding included (packed_columns()' twin)."""
+        c1 = self.n if c1 is None else c1
+        ld, bits = C.c_uint64(), C.c_uint32()
+        self._check(self.L.fseq_debug_held_out_columns(self.h, c0, c1, None, C.byref(ld), C.byref(bits)))
+        out = np.zeros((c1 - c0, ld.value), dtype=np.uint8)
+        self._check(self.L.fseq_debug_held_out_columns(self.h, c0, c1, out.ctypes.data, C.byref(ld), C.byref(bits)))
+        return out, bits.value
+
+    def match_held_out(self, permutations=None, founders=None, min_segment_length=0):
+        """... the held-out rows threaded through the founders (fseq_match_held_out): permutations or founders as match_rows
+        takes them; nothing is uploaded.  Returns the summary dict; match_pieces(), write_match() and match_split() serve the
+        result."""
+        if (permutations is None) == (founders is None):
+            raise ValueError("match_held_out: give either permutations or founders")
+        sm = MatchSummary()
+        if permutations is not None:
+            perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+            self._check(self.L.fseq_match_held_out(self.h, perm.ctypes.data, None, 0, int(min_segment_length), C.byref(sm)))
+        else:
+            if not isinstance(founders, np.ndarray):
+                founders = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in founders], dtype=np.uint8).reshape(len(founders), -1)
+            f = np.ascontiguousarray(founders, dtype=np.uint8)
+            if f.ndim != 2 or f.shape[1] != self.n:
+                raise ValueError("match_held_out: founders must be K rows of n = %d bytes" % self.n)
+            frows = (C.c_void_p * max(f.shape[0], 1))(*[f.ctypes.data + r * f.strides[0] for r in range(f.shape[0])])
+            self._check(self.L.fseq_match_held_out(self.h, None, frows, f.shape[0], int(min_segment_length), C.byref(sm)))
+        self._match = sm
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
 
     # ---- identity columns (remove-identity-columns / insert-identity-columns, on the device)
     def identity_columns(self):

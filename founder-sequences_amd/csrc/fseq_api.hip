@@ -8,8 +8,8 @@
 // The context and the helpers every translation unit shares are in fseq_ctx.hpp.  The orchestration behind these entry points
 // is in the path's units (fseq_path.hpp lists them: csrc/fseq_path_setup.hip, _dp, _pass1, _reduced, _attempt, _pass2), the debug entry points
 // and the row-sharded sweep in csrc/fseq_api_debug.hip; the host joiners, their device front and the output writers are
-// csrc/fseq_api_join.hip, the matcher csrc/fseq_api_match.hip, the identity columns csrc/fseq_api_identity.hip and the chunked
-// input csrc/fseq_api_input.hip.
+// csrc/fseq_api_join.hip, the matcher csrc/fseq_api_match.hip, the identity columns csrc/fseq_api_identity.hip, the rows held out of the
+// resident alignment csrc/fseq_api_rowsplit.hip and the chunked input csrc/fseq_api_input.hip.
 #include "fseq_path.hpp"
 #include "fseq_kernels.hpp"
 
@@ -46,6 +46,8 @@ int fseq::take_new_input(fseq_ctx *c)
 {
 	if (c->idn.have)
 		return fail(c, FSEQ_E_ARG, "a context made by fseq_create_without_identity_columns takes no other input (its identity relation belongs to the columns it was made from)");
+	if (c->hold.have)
+		return fail(c, FSEQ_E_ARG, "a context made by fseq_create_without_rows takes no other input (its held-out rows belong to the alignment it was made from)");
 	(void) hipSetDevice(c->p.device);
 	if (c->stream) (void) hipStreamSynchronize(c->stream);
 	free_work(c);
@@ -114,6 +116,7 @@ void fseq_destroy(fseq_ctx *c)
 	free_work(c);
 	c->free_match();
 	c->free_identity();
+	c->free_held_out();
 	c->free_input();
 	assert(c->alloc_sizes.empty() && c->alloc_total == 0);       // (a buffer free_work does not know of)
 	for (hipEvent_t *e : c->ev.timed()) if (*e) (void) hipEventDestroy(*e);

@@ -395,6 +395,32 @@ int fseq_match_rows(fseq_ctx *c, uint32_t const *permutations, uint8_t const *co
 	return run_match_split(c, s, MatchRows{c->match.qrows, ld, n_rows, bsh}, plan, min_segment_length, out);
 }
 
+// fseq_match_rows with the context's own held-out buffer (fseq_create_without_rows, csrc/fseq_api_rowsplit.hip) as the queries:
+// they are on the device already, column-major and packed at the alignment's width, so nothing is uploaded or packed
+int fseq_match_held_out(fseq_ctx *c, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K, uint64_t min_segment_length,
+                        fseq_match_summary *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if ((permutations != nullptr) == (founders != nullptr && K != 0)) return fail(c, FSEQ_E_ARG, "match: give either the permutations of the run or K founder rows");
+	if (permutations && (founders || K)) return fail(c, FSEQ_E_ARG, "match: give either the permutations of the run or K founder rows");
+	for (uint32_t f = 0; founders && f < K; ++f)
+		if (!founders[f]) return fail(c, FSEQ_E_ARG, "match: null founder row");
+	if (!c->hold.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
+	size_t X = K;
+	int rc = permutations ? check_permutations(c, false, X) : refuse_common(c, K);
+	if (rc) return rc;
+	(void) hipSetDevice(c->p.device);
+	MatchShape const s = match_shape((uint32_t) X, c->sigma, c->bsh);
+	if ((rc = begin_match(c, s))) return rc;
+	FounderTemps T(c);
+	if ((rc = permutations ? cols_from_permutations(c, permutations, s, T) : cols_from_rows(c, founders, s, T))) return rc;
+	int cus = 0;
+	(void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->p.device);
+	uint32_t const n_held = c->hold.n_held;
+	MatchSplitPlan const plan = match_split_plan(c->p.n, n_held, (uint32_t) std::max(cus, 1), (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, true);
+	return run_match_split(c, s, MatchRows{c->hold.cols, c->hold.ld, n_held, c->bsh}, plan, min_segment_length, out);
+}
+
 int fseq_debug_match_split(fseq_ctx *c, fseq_match_split_info *info)
 {
 	if (!c || !info) return FSEQ_E_ARG;

@@ -3,7 +3,7 @@
 // the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _reduced, _attempt, _pass2: geometry, buffers, phases, sharding; what
 // only they share is csrc/fseq_path.hpp), csrc/fseq_api_join.hip (the host joiners, their device front and the output
 // writers), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
-// and put back) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
+// and put back), csrc/fseq_api_rowsplit.hip (rows held out of the resident alignment) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
 #pragma once
 
 #include "../../include/fseq.h"
@@ -520,6 +520,21 @@ struct fseq_ctx {
 	{
 		fseq::release_all(this, idn.mask, idn.kept, idn.ref);
 		idn.have = false;
+	}
+
+	// a context over some rows of another (fseq_create_without_rows, csrc/fseq_api_rowsplit.hip): the rows that were held out,
+	// packed like the alignment, and the two maps back into the source's row numbers.  Empty on every other context
+	struct HeldOut {
+		bool have = false;
+		uint32_t m_src = 0, n_held = 0;      // rows of the source, rows held out of it
+		size_t ld = 0;                       // bytes of a held-out column: n_held fields rounded up to 16
+		DevBuf<uint8_t> cols;                // column k at cols + k * ld; row q of it is held_rows[q]
+		std::vector<uint32_t> kept_rows, held_rows;      // source row of this context's row j (ascending); the caller's list
+	} hold;
+	void free_held_out()
+	{
+		fseq::release_all(this, hold.cols);
+		hold.have = false;
 	}
 
 	// the input in column chunks (fseq_input_begin .. fseq_input_end, csrc/fseq_api_input.hip): alive between begin and end only

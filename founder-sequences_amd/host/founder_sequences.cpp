@@ -50,6 +50,8 @@ char const *const USAGE =
 	"                                     with --remove-identity-columns; requires --output-sequence-matches)\n"
 	"      --output-sequence-matches=PATH ... and write the report of match-sequences-to-founders for them (honours\n"
 	"                                     --match-min-segment-length; requires --match-sequences)\n"
+	"      --hold-out=LIST                Hold sequences out of the segmentation: a comma list of 0-based indices in input order and of LO:HI ranges, both ends included (one GPU only)\n"
+	"      --output-held-out-matches=PATH ... and match them against the founders on the device; the report's SEQUENCE_INDEX counts along LIST (requires --hold-out)\n"
 	"      --remove-identity-columns      Segment only the columns in which the sequences differ and put the others back into the\n"
 	"                                     founders from the first sequence (remove-identity-columns | founder_sequences |\n"
 	"                                     insert-identity-columns in one run; segments in reduced co-ordinates; one GPU only)\n"
@@ -210,6 +212,16 @@ bool match_held_out(fseq_ctx *ctx, char const *list, size_t seq_length, uint32_t
 	return report_match(ctx, rc, sm, path);
 }
 
+// --output-held-out-matches: the sequences --hold-out set aside, which the context holds on the device, against the founders the
+// context has (permutations) or the rows given
+bool match_context_held_out(fseq_ctx *ctx, uint32_t const *perm, uint8_t const *const *frows, uint32_t K, unsigned long long min_len, char const *path)
+{
+	std::cerr << "Matching the held-out sequences against the founders…" << std::endl;
+	fseq_match_summary sm{};
+	int const rc(fseq_match_held_out(ctx, perm, frows, K, min_len, &sm));
+	return report_match(ctx, rc, sm, path);
+}
+
 std::ostream *open_out(char const *path, std::ofstream &file)
 {
 	if (!path || ('-' == path[0] && '\0' == path[1])) return &std::cout;
@@ -253,10 +265,48 @@ bool parse_scan_spec(char const *spec, std::vector<uint64_t> &out)
 	return true;
 }
 
+// --hold-out=LIST: a comma list of 0-based sequence indices and of LO:HI ranges, both ends included, in the order given.  false,
+// with the reason in why, where LIST is malformed or names an index twice (whether the indices are below the sequence count is
+// the caller's check, once the input is read)
+bool parse_hold_out(char const *spec, std::vector<uint32_t> &out, std::string &why)
+{
+	auto number = [](char const *&s, uint64_t &v) {
+		if (!isdigit((unsigned char) *s)) return false;
+		char *end = nullptr;
+		errno = 0;
+		v = strtoull(s, &end, 10);
+		s = end;
+		return errno != ERANGE && v < 0xFFFFFFFFull;
+	};
+	char const *s = spec;
+	out.clear();
+	while (true)
+	{
+		uint64_t lo = 0, hi = 0;
+		if (!number(s, lo)) { why = "malformed (a comma list of indices and LO:HI ranges is expected)"; return false; }
+		hi = lo;
+		if (*s == ':')
+		{
+			++s;
+			if (!number(s, hi) || hi < lo) { why = "malformed (a range is LO:HI with LO <= HI)"; return false; }
+		}
+		if (hi - lo >= 0x7FFFFFFFull || out.size() + (hi - lo + 1) > 0x7FFFFFFFull) { why = "malformed (too many indices)"; return false; }
+		for (uint64_t v = lo; v <= hi; ++v) out.push_back((uint32_t) v);
+		if (*s == '\0') break;
+		if (*s++ != ',') { why = "malformed (a comma list of indices and LO:HI ranges is expected)"; return false; }
+	}
+	std::vector<uint32_t> sorted(out);
+	std::sort(sorted.begin(), sorted.end());
+	if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { why = "names a sequence twice"; return false; }
+	return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
+	char const *hold_out_spec = nullptr, *out_held_matches = nullptr;
+	std::vector<uint32_t> held_rows;
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr;
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr;
 	bool remove_identity = false;
@@ -290,6 +340,7 @@ int main(int argc, char **argv)
 		{"scan-segment-lengths", required_argument, nullptr, 1011}, {"output-scan", required_argument, nullptr, 1012},
 		{"max-founders", required_argument, nullptr, 1013},
 		{"match-sequences", required_argument, nullptr, 1014}, {"output-sequence-matches", required_argument, nullptr, 1015},
+		{"hold-out", required_argument, nullptr, 1016}, {"output-held-out-matches", required_argument, nullptr, 1017},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -362,6 +413,8 @@ int main(int argc, char **argv)
 			}
 			case 1014: match_seqs = optarg; break;
 			case 1015: out_seq_matches = optarg; break;
+			case 1016: hold_out_spec = optarg; break;
+			case 1017: out_held_matches = optarg; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -402,6 +455,16 @@ int main(int argc, char **argv)
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	if (out_held_matches && !hold_out_spec) { std::cerr << "--output-held-out-matches requires --hold-out." << std::endl; return EXIT_FAILURE; }
+	if (hold_out_spec)
+	{
+		std::string why;
+		if (!parse_hold_out(hold_out_spec, held_rows, why)) { std::cerr << "The list of sequences to hold out is " << why << '.' << std::endl; return EXIT_FAILURE; }
+		if (gpus > 1) { std::cerr << "--hold-out is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+		if (remove_identity) { std::cerr << "--hold-out is not supported together with --remove-identity-columns (the held-out sequences would have to lose the same columns)." << std::endl; return EXIT_FAILURE; }
+		if (scan_spec && !seg_len_given && !max_founders_given)
+		{ std::cerr << "--hold-out with --scan-segment-lengths needs a segment length to go on with (--segment-length-bound or --max-founders): a scan alone writes its table and nothing else." << std::endl; return EXIT_FAILURE; }
+	}
 
 	if (upload_bad) { std::cerr << "The upload memory must be a positive number of MiB." << std::endl; return EXIT_FAILURE; }
 	if (upload_given && input_format::FASTA == fmt) { std::cerr << "--upload-memory is not supported together with --input-format=FASTA (a FASTA file holds the sequences one after another, so a column chunk is not a range of its bytes; use list-file input)." << std::endl; return EXIT_FAILURE; }
@@ -439,6 +502,13 @@ int main(int argc, char **argv)
 		if (stop) return EXIT_FAILURE;
 	}
 	if (0 == seq_length) { std::cerr << "The sequences are empty." << std::endl; return EXIT_FAILURE; }
+	if (hold_out_spec)
+	{
+		for (uint32_t r : held_rows)
+			if (r >= lengths.size())
+			{ std::cerr << "The list of sequences to hold out names index " << r << ", which is out of range: the input has " << lengths.size() << " sequences." << std::endl; return EXIT_FAILURE; }
+		if (held_rows.size() >= lengths.size()) { std::cerr << "The list of sequences to hold out leaves no sequence to segment." << std::endl; return EXIT_FAILURE; }
+	}
 
 	fseq_params p{};
 	p.m = (uint32_t) lengths.size();
@@ -485,6 +555,33 @@ int main(int argc, char **argv)
 		if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(ctxs[r], (uint64_t) list_memory_mib << 20))) return rc_;
 		if (upload_given) { if (FSEQ_OK != (rc_ = upload_in_chunks(ctxs[r], paths, p.n, (uint64_t) upload_mib << 20, io_err))) return rc_; }
 		else if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
+		if (hold_out_spec)
+		{
+			// the uploaded alignment is the source; the run goes on on a context over the other sequences, which keeps the held-out
+			// ones aside on the device.  The source goes before the run: the two alignments and the lists need not fit the card together
+			fseq_params pk(pr);
+			pk.m = 0; pk.n = 0;
+			fseq_ctx *sub(nullptr);
+			fseq_hold_out_summary hs{};
+			if (FSEQ_OK != (rc_ = fseq_create_without_rows(ctxs[r], held_rows.data(), (uint32_t) held_rows.size(), &pk, &sub, &hs))) return rc_;
+			fseq_destroy(ctxs[r]);
+			ctxs[r] = sub;
+			std::cerr << "Held " << hs.held << " of " << hs.m_src << " sequences out of the segmentation." << std::endl;
+			if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(sub, (uint64_t) list_memory_mib << 20))) return rc_;
+			// what the host holds of the sequences follows the kept ones' numbering from here on
+			std::vector<uint32_t> kept(hs.kept);
+			if (FSEQ_OK != (rc_ = fseq_get_held_out(sub, kept.data(), nullptr))) return rc_;
+			for (size_t j = 0; j < kept.size(); ++j)               // (kept ascends: kept[j] >= j)
+			{
+				if (!seqs.empty() && kept[j] != j) seqs[j] = std::move(seqs[kept[j]]);
+				if (!paths.empty() && kept[j] != j) paths[j] = std::move(paths[kept[j]]);
+			}
+			if (!seqs.empty()) seqs.resize(kept.size());
+			if (!paths.empty()) paths.resize(kept.size());
+			rows.assign(kept.size(), nullptr);
+			for (size_t i = 0; i < seqs.size(); ++i) rows[i] = reinterpret_cast<uint8_t const *>(seqs[i].data());
+			p.m = hs.kept;
+		}
 		if (remove_identity)
 		{
 			// the uploaded alignment is the source; the run goes on on a context over the columns in which the sequences differ
@@ -575,7 +672,7 @@ int main(int argc, char **argv)
 		std::cerr << "Outputting…" << std::endl;
 		std::ostream &os = *open_out(out_founders, founders_file);
 		// (--upload-memory: the founders are input rows, read now from the files the runs name, one at a time)
-		std::vector<std::string> named(upload_given && (out_matches || match_seqs) ? res.max_segment_size : 0);
+		std::vector<std::string> named(upload_given && (out_matches || match_seqs || out_held_matches) ? res.max_segment_size : 0);
 		for (uint32_t i = 0; i < res.max_segment_size; ++i)
 		{
 			std::string one;
@@ -613,6 +710,13 @@ int main(int argc, char **argv)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
 			return EXIT_FAILURE;
+		}
+		if (out_held_matches)
+		{
+			// (last: the context holds one match at a time)
+			std::vector<uint8_t const *> frows(res.max_segment_size);
+			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = upload_given ? reinterpret_cast<uint8_t const *>(named[i].data()) : rows[first[i]];
+			if (!match_context_held_out(ctx, nullptr, frows.data(), res.max_segment_size, match_min_len, out_held_matches)) return EXIT_FAILURE;
 		}
 		std::cerr << "Done." << std::endl;
 		fseq_destroy(ctx);
@@ -712,6 +816,7 @@ int main(int argc, char **argv)
 		rc = fseq_match_founders_restored(ctx, perm.data(), match_min_len, &sm);
 		if (!report_match(ctx, rc, sm, out_restored_matches)) return EXIT_FAILURE;
 	}
+	if (out_held_matches && !match_context_held_out(ctx, perm.data(), nullptr, 0, match_min_len, out_held_matches)) return EXIT_FAILURE;      // (last: one match at a time)
 	std::cerr << "Done." << std::endl;
 	for (fseq_ctx *c_ : ctxs) if (c_) fseq_destroy(c_);
 	return EXIT_SUCCESS;

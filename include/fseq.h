@@ -434,6 +434,47 @@ int  fseq_write_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, c
  * entry points above. */
 int  fseq_match_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out);
 
+/* ---- rows held out of a resident alignment and matched on the device ----
+ * replaces: nothing of the reference, where a sequence is held out of a reconstruction by removing its line from the list file
+ * and running the chain again on the shorter file; here the alignment that is already resident -- uploaded, streamed, generated
+ * or borrowed, one code per byte or packed -- is split along its rows on the device (csrc/fseq_rowsplit.hpp): leave-rows-out and
+ * k-fold validation of a founder set cost one upload.  The entry points are detected by symbol; FSEQ_ABI_VERSION stays 5. */
+typedef struct fseq_hold_out_summary {
+	uint32_t m_src, held, kept, reserved;   /* rows of the source, rows held out, m_src - held */
+	double   ms_device;                      /* HIP event time of the split pass */
+} fseq_hold_out_summary;                     /* 24 bytes */
+/* A new, ordinary context on the source's device over the rows of src that are NOT in held_rows: the kept rows stay in the
+ * source's order and are numbered 0 .. kept - 1.  held_rows: n_held distinct row indices below the source's m, in any order,
+ * 1 <= n_held <= m - 1; anything else is FSEQ_E_ARG with a message (fseq_last_error(src)) before a device is touched.
+ * params->m must be 0 (it becomes `kept`), params->n 0 or the source's, params->device the source's device, segment_length
+ * positive; block_len, list_cap and pbwt_sample_rate are taken from params.  The new context owns its alignment (columns padded
+ * to 16 bytes, padding zeroed) and keeps the source's sigma, code table and code width as they are: a symbol that occurs only
+ * in held-out rows keeps its code, and since the order of the codes is unchanged every result is what a fresh upload of the
+ * kept rows gives.  Segments, traceback, boundary states, permutations, the founders writers and the segments file are all in
+ * the KEPT rows' numbering: exactly what the reference's chain produces from a list file with those lines removed;
+ * fseq_get_held_out maps the numbers back.  The held-out rows live in the new context as a second column-major buffer, n
+ * columns of ld_h bytes (n_held fields at the source's width, rounded up to 16, padding zeroed), in the order of held_rows: row
+ * q of it is held_rows[q].  The source may be destroyed as soon as the call returns; nothing of its segmentation state is read
+ * or written, and it may be the source of further calls (one per fold).  FSEQ_E_UNSUPPORTED: a sharded source (a rank holds its
+ * own columns only), a source made by fseq_create_without_identity_columns (its identity state would have to be carried along;
+ * the other way round works: a context made here may be the source of that call, which knows nothing of the held-out rows and
+ * makes a plain context).  FSEQ_E_ARG: no alignment resident.  A failed allocation returns FSEQ_E_OOM with the sizes, leaves
+ * nothing behind, *out NULL and src as it was.  The new context takes no other input (every input setter returns FSEQ_E_ARG, as
+ * on a context made by fseq_create_without_identity_columns); fseq_set_segment_length is allowed.  summary may be NULL. */
+int  fseq_create_without_rows(fseq_ctx *src, uint32_t const *held_rows, uint32_t n_held, fseq_params const *params, fseq_ctx **out,
+                              fseq_hold_out_summary *summary);
+/* On a context made by the call above (FSEQ_E_ARG on any other): the source row of every row of this context (`kept` entries,
+ * ascending) and the held-out rows in the caller's order (`held` entries); either may be NULL. */
+int  fseq_get_held_out(fseq_ctx *ctx, uint32_t *kept_rows /* [kept] or NULL */, uint32_t *held_rows /* [held] or NULL */);
+/* fseq_match_rows with the context's own held-out rows as the queries: how the rows that took no part in the reconstruction
+ * thread through its founders -- the permutations of the finished run or K raw founder rows, exactly one of the two.  Nothing
+ * is uploaded or packed: the split walk runs on the held-out buffer as it is.  fseq_match_piece::row is the index into
+ * held_rows.  Refusals and the limit of 2,048 founders as fseq_match_rows; FSEQ_E_ARG on a context not made by
+ * fseq_create_without_rows.  The result replaces the context's last match: fseq_get_match, fseq_write_match and
+ * fseq_debug_match_split serve it as they do after fseq_match_rows. */
+int  fseq_match_held_out(fseq_ctx *ctx, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K,
+                         uint64_t min_segment_length, fseq_match_summary *out);
+
 int  fseq_get_timings(fseq_ctx const *ctx, fseq_timings *out);
 
 /* Host time of the last fseq_join_* call on this context (wall, milliseconds): the boundary states' way to the host,

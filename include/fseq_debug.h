@@ -196,6 +196,22 @@ typedef struct fseq_match_split_info {
 } fseq_match_split_info;
 int  fseq_debug_match_split(fseq_ctx *ctx, fseq_match_split_info *info);
 
+/* The held-out rows of a context made by fseq_create_without_rows as they are stored (the twin of fseq_debug_packed_columns): the
+ * bytes of the columns [c0, c1), *ld bytes a column (padding included), codes of *bits bits; row q of a column is held_rows[q].
+ * out == NULL: *ld and *bits only.  FSEQ_E_ARG on any other context. */
+int  fseq_debug_held_out_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t *out, uint64_t *ld, uint32_t *bits);
+
+/* The plan of a split along the rows (row_split_plan, csrc/fseq_rowsplit_plan.hpp) for m rows at `bits` = 2, 4 or 8 bits a code
+ * with the n_held rows of `held` set aside (debug / tests; touches no device).  per = 32 / bits.  Out, each array or NULL:
+ * kept[m - n_held], the rows that stay, ascending; one descriptor per 32-bit word of a kept column, base / keep [*n_words],
+ * *n_words = ceil((m - n_held) / per): word w holds the kept rows w per .. w per + per - 1, base[w] is the source row of the first,
+ * and bit i of keep[w] is set iff source row base[w] + i is one of them -- the word is the 2 per fields from base[w] on compressed
+ * by keep[w].  A word whose rows span more than 2 per source rows has keep[w] = 0 (bit 0 is set otherwise) and is built field by
+ * field from kept; *n_slow counts those.  FSEQ_E_ARG, as fseq_create_without_rows refuses it: bits not 2, 4 or 8, held NULL,
+ * n_held outside 1 .. m - 1, an entry not below m, an entry twice; n_words or n_slow NULL. */
+int  fseq_debug_row_split_plan(uint32_t m, uint32_t bits, uint32_t const *held, uint32_t n_held, uint32_t *kept, uint32_t *base, uint32_t *keep,
+                               uint32_t *n_words, uint32_t *n_slow);
+
 #ifdef __cplusplus
 }
 #endif
