@@ -89,6 +89,10 @@ class HoldOutSummary(C.Structure):
     _fields_ = [("m_src", C.c_uint32), ("held", C.c_uint32), ("kept", C.c_uint32), ("reserved", C.c_uint32), ("ms_device", C.c_double)]
 
 
+class DpListsInfo(C.Structure):
+    _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
+
+
 class LengthScanSummary(C.Structure):
     _fields_ = [("lists_built", C.c_uint32), ("lists_folded", C.c_uint32), ("short_entries", C.c_uint32), ("retries", C.c_uint32),
                 ("ms_phase_a", C.c_double), ("ms_phase_b", C.c_double), ("ms_total", C.c_double)]
@@ -126,13 +130,14 @@ EXPORTS = [
     "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
     "fseq_match_rows", "fseq_debug_match_split",
     "fseq_create_without_rows", "fseq_get_held_out", "fseq_match_held_out", "fseq_debug_held_out_columns", "fseq_debug_row_split_plan",
+    "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
-                 "fseq_debug_held_out_columns", "fseq_debug_row_split_plan"]
+                 "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -260,6 +265,8 @@ def load_library():
     L.fseq_match_held_out.argtypes = [vp, vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
     L.fseq_debug_held_out_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_row_split_plan.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.fseq_debug_dp_lists_check.argtypes = [C.c_uint32, u64, u64, C.c_uint32, vp, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.fseq_debug_dp_on_lists.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(DpListsInfo)]
     _lib = L
     return L
 
@@ -485,6 +492,29 @@ def relump_lists(ent, hdr, k0, L_from, L_to, device=0):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return ent, hdr
+
+
+def _dp_lists(ent, hdr):
+    ent = np.ascontiguousarray(ent, dtype=np.uint32)
+    hdr = np.ascontiguousarray(hdr, dtype=np.uint32)
+    if ent.ndim != 3 or ent.shape[2] != 2 or hdr.shape != (ent.shape[0], 4):
+        raise FseqError(FSEQ_E_ARG, "DP lists: ent is [n][stride][2], hdr [n][4]")
+    return ent, hdr
+
+
+def dp_lists_check(m, segment_length, ent, hdr):
+    """The host's check of lists for SegmentationContext.debug_dp_on_lists (fseq_debug_dp_lists_check; no device): ent
+    [n][stride][2] {value, count}, hdr [n][4] {entries, count of value 0, complete, cumulative count}.  Returns None where the DP
+    may read them, else (column, rule) of the first list that breaks a rule (column -1: rule 0, the shapes)."""
+    L = load_library()
+    ent, hdr = _dp_lists(ent, hdr)
+    bad, rule = C.c_uint64(), C.c_uint32()
+    rc = L.fseq_debug_dp_lists_check(int(m), ent.shape[0], int(segment_length), ent.shape[1], ent.ctypes.data, hdr.ctypes.data, C.byref(bad), C.byref(rule))
+    if rc == FSEQ_OK:
+        return None
+    if rc != FSEQ_E_ARG:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return (-1 if bad.value == 2 ** 64 - 1 else bad.value), rule.value
 
 
 class RowShard(C.Structure):
@@ -1132,6 +1162,23 @@ class SegmentationContext:
         self._check(self.L.fseq_debug_column_list(self.h, col, v.ctypes.data, c.ctypes.data,
                                                   C.byref(ne), C.byref(c0), C.byref(comp)))
         return v[:ne.value].copy(), c[:ne.value].copy(), c0.value, bool(comp.value)
+
+    def debug_dp_on_lists(self, list_cap, ent, hdr, cuts=()):
+        """Phase D alone on constructed lists through the production launchers (fseq_debug_dp_on_lists): ent [n][stride][2] with
+        stride = (list_cap + 3) & ~1, hdr [n][4].  cuts empty: the DP as a run chooses it (the speculative sweeps; the serial
+        kernel under FSEQ_DP_SERIAL); else resumed launches of the serial kernel cut at those rounds.  Returns (lb, max_size,
+        size, info) with info = {unproven, dp_chunks, dp_sweeps, launches}; the context holds no result afterwards."""
+        ent, hdr = _dp_lists(ent, hdr)
+        if ent.shape[0] != self.n or ent.shape[1] != ((int(list_cap) + 3) & ~1):
+            raise FseqError(FSEQ_E_ARG, "DP on lists: ent is [n][(list_cap + 3) & ~1][2]")
+        cuts = np.ascontiguousarray(cuts, dtype=np.uint32)
+        k = self.n - self.segment_length + 1
+        lb, mx, sz = (np.zeros(k, dtype=np.uint32) for _ in range(3))
+        info = DpListsInfo()
+        self.result = None
+        self._check(self.L.fseq_debug_dp_on_lists(self.h, int(list_cap), ent.ctypes.data, hdr.ctypes.data, cuts.ctypes.data if len(cuts) else None,
+                                                  len(cuts), lb.ctypes.data, mx.ctypes.data, sz.ctypes.data, C.byref(info)))
+        return lb, mx, sz, {k_: getattr(info, k_) for k_, _ in DpListsInfo._fields_}
 
     def set_tuning(self, name, value="1"):
         """One of the library's FSEQ_* diagnostic knobs for this context (value None = off); the environment is only

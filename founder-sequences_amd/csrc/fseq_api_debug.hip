@@ -229,6 +229,123 @@ int fseq_debug_dp_schedule(uint64_t segment_length, uint64_t n, uint64_t col_hi,
 	return FSEQ_OK;
 }
 
+// ---- phase D on caller-supplied lists (tests/test_gpu_dp_lists.py): the host's check of the lists, then the production launchers
+int fseq_debug_dp_lists_check(uint32_t m, uint64_t n, uint64_t L, uint32_t stride, uint32_t const *ent, uint32_t const *hdr, uint64_t *bad_column,
+                              uint32_t *rule)
+{
+	auto refuse = [&](uint64_t k, uint32_t r) {
+		if (bad_column) *bad_column = k;
+		if (rule) *rule = r;
+		return FSEQ_E_ARG;
+	};
+	if (!ent || !hdr || 0 == m || 0 == L || n < 2 * L || n >= 0xFFFFFFF0ull || 0 == stride || n * stride > (1ull << 28)) return refuse(~0ull, 0u);
+	// the columns a cell reads: end - 1 of every cell end in [L, n - L], and n - 1 (the final cell)
+	for (uint64_t k = L - 1; k < n; k = (k + 1 == n - L ? n - 1 : k + 1))
+	{
+		uint32_t const *const h = hdr + 4 * k, *const e = ent + 2 * k * stride;
+		uint32_t const nent = h[0];
+		if (nent < 1 || nent > stride) return refuse(k, 1u);
+		if (e[0] != k + 1) return refuse(k, 2u);
+		uint64_t sum = e[1];
+		for (uint32_t i = 1; i < nent; ++i)
+		{
+			if (e[2 * i] >= e[2 * i - 2]) return refuse(k, 3u);
+			if (e[2 * i + 1] < 1) return refuse(k, 5u);
+			sum += e[2 * i + 1];
+		}
+		// (descending from k + 1 >= 1: a value 0 can only stand last)
+		bool const zero_last = e[2 * (nent - 1)] == 0;
+		bool const full = sum == m;
+		if (zero_last && (e[2 * (nent - 1) + 1] != h[1] || !full)) return refuse(k, 4u);
+		if (!zero_last && full && h[1] != 0) return refuse(k, 4u);
+		if (sum != h[3] || sum > m) return refuse(k, 6u);
+		if (h[2] > 1 || (h[2] == 1) != full || h[1] > m) return refuse(k, 7u);
+	}
+	if (bad_column) *bad_column = ~0ull;
+	if (rule) *rule = 0;
+	return FSEQ_OK;
+}
+
+int fseq_debug_dp_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *cuts, uint32_t n_cuts,
+                           uint32_t *lb, uint32_t *max_size, uint32_t *size, fseq_dp_lists_info *info)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!ent || !hdr || !info || (n_cuts && !cuts) || 0 == list_cap) return fail(c, FSEQ_E_ARG, "DP on lists: lists, a capacity and an info are needed");
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "DP on lists: not for sharded contexts (a rank holds the lists of its own columns)");
+	if (c->lw.budget) return fail(c, FSEQ_E_UNSUPPORTED, "DP on lists: not under a list memory budget (every list is held)");
+	if (!c->have_input) return fail(c, FSEQ_E_ARG, "no input set");
+	if (c->in.open) return fail(c, FSEQ_E_ARG, "a chunked input is under way (fseq_input_begin without fseq_input_end)");
+	fseq_params const &p = c->p;
+	uint64_t const n = p.n, L = p.segment_length;
+	if (n < 2 * L) return fail(c, FSEQ_E_ARG, "DP on lists: the short path (n < 2L) has no DP");
+	if (list_cap > 0x00FFFFFFu) return fail(c, FSEQ_E_ARG, "DP on lists: list capacity out of range");
+	uint32_t const stride = (list_cap + 3) & ~1u;
+	uint64_t bad = 0;
+	uint32_t rule = 0;
+	if (fseq_debug_dp_lists_check(p.m, n, L, stride, ent, hdr, &bad, &rule))
+	{
+		char what[160];
+		snprintf(what, sizeof(what), "DP on lists: the list of column %lld breaks rule %u of fseq_debug_dp_lists_check", (long long) bad, rule);
+		return fail(c, FSEQ_E_ARG, what);
+	}
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	for (uint32_t i = 0; i < n_cuts; ++i)
+		if (cuts[i] == 0 || cuts[i] >= S.nrounds || (i && cuts[i] <= cuts[i - 1]))
+			return fail(c, FSEQ_E_ARG, "DP on lists: the cut rounds ascend strictly inside (0, rounds)");
+	(void) hipSetDevice(p.device);
+	// the context holds no result from here on, and its lists are the caller's: nothing of a run may answer for them
+	c->have_result = false;
+	c->scan_lists = false;
+	c->free_match();
+	c->lw.on = false; c->lw.merge_windows = 0;
+	int rc;
+	if (!c->kernels_ready && (rc = prepare_geometry(c))) return rc;
+	if ((rc = ensure_work_buffers(c, list_cap, false))) return rc;
+	hipStream_t st = c->stream;
+	HIP_TRY(c, hipStreamSynchronize(st));
+	HIP_TRY(c, hipMemcpyAsync(c->d_ent, ent, (size_t) n * stride * sizeof(uint2), hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(c->d_hdr, hdr, (size_t) n * sizeof(uint4), hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemsetAsync(path_words(c)->dp, 0, sizeof(PathWords::dp), st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.SZ, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.K, 0, (c->dp_size + 64) * 8, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.Tb, 0, (size_t) 32 * c->dp.tstride * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.Tbv, 0, (size_t) 32 * c->dp.tstride * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->d_Mprev, 0, c->dp_size * 4, st));
+	*info = fseq_dp_lists_info{};
+	if (n_cuts == 0)
+	{
+		DpProof proof;
+		bool unproven = false;
+		if ((rc = long_dp_on_lists(c, &proof, &unproven))) return rc;
+		info->unproven = unproven ? 1u : 0u;
+		info->dp_chunks = proof.dp_chunks;
+		info->dp_sweeps = proof.dp_sweeps;
+		info->launches = proof.dp_chunks ? 0u : 1u;
+	}
+	else
+	{
+		uint32_t r_lo = 0;
+		for (uint32_t i = 0; i <= n_cuts; ++i)
+		{
+			uint32_t const r_hi = i < n_cuts ? cuts[i] : S.nrounds;
+			launch_dp_serial(c, DP_PARTIAL, st, r_lo, r_hi);
+			r_lo = r_hi;
+		}
+		HIP_TRY(c, hipGetLastError());
+		uint32_t words[4] = {0, 0, 0, 0};
+		HIP_TRY(c, hipMemcpyAsync(words, path_words(c)->dp, sizeof(PathWords::dp), hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipStreamSynchronize(st));
+		info->unproven = words[0] & 1u;
+		info->launches = n_cuts + 1u;
+	}
+	if (lb) HIP_TRY(c, hipMemcpy(lb, c->dp.LB, c->dp_size * 4, hipMemcpyDeviceToHost));
+	if (max_size) HIP_TRY(c, hipMemcpy(max_size, c->dp.M, c->dp_size * 4, hipMemcpyDeviceToHost));
+	if (size) HIP_TRY(c, hipMemcpy(size, c->dp.SZ, c->dp_size * 4, hipMemcpyDeviceToHost));
+	return FSEQ_OK;
+}
+
 // ---- row-sharded pBWT sweep: the north-star partition as a conformance path (fseq_rowshard.hpp) ------------------
 uint64_t fseq_rowshard_xbuf_words(uint32_t m, uint32_t bits, uint32_t world)
 {

@@ -234,9 +234,12 @@ __device__ __forceinline__ bool dp_strip(
 		st.best_lb = readlane_u32(idx, src) + L;
 		st.best_sz = readlane_u32(cum, src);
 	}
-	bool const last = s0 + 64u >= nent;                       // strip reaches the end of the list
+	// the next strip begins at entry s0 + ncand: behind the first strip's 63 candidates that is this strip's lane 63, whose count
+	// the next strip adds itself -- also where the list ends on that very entry (nent = 64: counted twice, an incomplete list
+	// of 64 entries passed the bound by its last count and a cell it did not prove went unflagged)
+	bool const more = s0 + ncand < nent;
 	st.cum_base = readlane_u32(cum, 63);
-	if (!last && ncand < 64u) st.cum_base = readlane_u32(cum, 62);
+	if (more && ncand < 64u) st.cum_base = readlane_u32(cum, 62);
 	return st.best_v != 0xFFFFFFFFu && st.cum_base > st.best_v;
 }
 

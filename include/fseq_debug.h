@@ -212,6 +212,40 @@ int  fseq_debug_held_out_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_
 int  fseq_debug_row_split_plan(uint32_t m, uint32_t bits, uint32_t const *held, uint32_t n_held, uint32_t *kept, uint32_t *base, uint32_t *keep,
                                uint32_t *n_words, uint32_t *n_slow);
 
+/* Whether the DP may read caller-supplied lists (debug / tests; touches no device): ent[n][stride] {value, count} pairs and
+ * hdr[n][4] = {entries, count of value 0, complete, cumulative count}, the format of k_columns (fseq_debug_relump_lists above),
+ * for m rows, n columns and segment length L, n >= 2L.  Checked for every column a cell reads, L - 1 .. n - L - 1 and n - 1
+ * -- what a kernel could form an index or a wrong proof from --, FSEQ_E_ARG at the first column that fails, *bad_column (or
+ * NULL) that column and *rule (or NULL) the rule it broke:
+ *   1  entries in 1 .. stride                          5  every count behind the lump >= 1
+ *   2  entry 0's value is k + 1                        6  the cumulative count is the sum of the counts, at most m
+ *   3  values strictly descending                      7  complete (0 or 1) iff the sum is m; the count of value 0 is at most m
+ *   4  value 0 in the last place only, its count the header's and the list complete; a complete list without it has a
+ *      header count of 0
+ * rule 0 (no column): a NULL array, m == 0, L == 0, n < 2L, n >= 2^32 - 16, stride == 0 or n * stride beyond 2^28 entries. */
+int  fseq_debug_dp_lists_check(uint32_t m, uint64_t n, uint64_t segment_length, uint32_t stride, uint32_t const *ent, uint32_t const *hdr,
+                               uint64_t *bad_column, uint32_t *rule);
+
+/* Phase D alone on caller-supplied lists, through the launchers a run uses (debug / tests): k_dp in its three modes and the
+ * kernels of the speculative sweeps (csrc/fseq_dp.hpp, csrc/fseq_dpspec.hpp).  ctx: an unsharded context without a list budget
+ * whose input is set (m x n at the context's segment length, n >= 2L; the bytes of the rows are never read).  ent / hdr as for
+ * fseq_debug_dp_lists_check with stride = (list_cap + 3) & ~1, which refuses them here before the device is touched.  The work
+ * buffers are made at capacity list_cap, the lists copied over the context's, the DP's words and arrays cleared.  Then
+ *   n_cuts == 0: the DP as a run at this length chooses it (long_dp_on_lists): the speculative sweeps under spec_plan's plan or
+ *     the one FSEQ_DP_SPEC_ROUNDS / _WIN / _MAX_SWEEPS force, one whole launch of the serial kernel under FSEQ_DP_SERIAL or
+ *     where the plan has fewer than three chunks;
+ *   n_cuts > 0: resumed launches of the serial kernel over the rounds [0, cuts[0]), [cuts[0], cuts[1]), ... [cuts[n_cuts - 1],
+ *     rounds), as a run under a list budget chains them; the cuts ascend strictly inside (0, rounds) (fseq_debug_dp_schedule).
+ * Out: lb / max_size / size, n - L + 1 words each (the entries 0 .. n - 2L and n - L are written, the others read 0), and
+ * info = {a list was too short to prove a cell, chunks of the sweeps' plan (0: serial), sweeps compared (1000 + the sweeps
+ * where the budget ran out and the serial kernel took over), launches of the serial kernel this call queued itself}.
+ * The context holds no result afterwards and no lists fseq_debug_column_list would answer for; a following run is unaffected. */
+typedef struct fseq_dp_lists_info {
+	uint32_t unproven, dp_chunks, dp_sweeps, launches;
+} fseq_dp_lists_info;
+int  fseq_debug_dp_on_lists(fseq_ctx *ctx, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *cuts, uint32_t n_cuts,
+                            uint32_t *lb, uint32_t *max_size, uint32_t *size, fseq_dp_lists_info *info);
+
 #ifdef __cplusplus
 }
 #endif
