@@ -131,6 +131,7 @@ EXPORTS = [
     "fseq_match_rows", "fseq_debug_match_split",
     "fseq_create_without_rows", "fseq_get_held_out", "fseq_match_held_out", "fseq_debug_held_out_columns", "fseq_debug_row_split_plan",
     "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
+    "fseq_create_without_identity_columns_held", "fseq_match_held_out_restored", "fseq_match_rows_restored", "fseq_get_match_exceptions",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -263,6 +264,10 @@ def load_library():
     L.fseq_create_without_rows.argtypes = [vp, vp, C.c_uint32, C.POINTER(Params), C.POINTER(vp), C.POINTER(HoldOutSummary)]
     L.fseq_get_held_out.argtypes = [vp, vp, vp]
     L.fseq_match_held_out.argtypes = [vp, vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
+    L.fseq_create_without_identity_columns_held.argtypes = [vp, C.POINTER(Params), C.POINTER(vp), C.POINTER(IdentitySummary)]
+    L.fseq_match_held_out_restored.argtypes = [vp, vp, u64, C.POINTER(MatchSummary)]
+    L.fseq_match_rows_restored.argtypes = [vp, vp, C.POINTER(vp), C.c_uint32, u64, C.POINTER(MatchSummary)]
+    L.fseq_get_match_exceptions.argtypes = [vp, vp, vp, C.POINTER(u64)]
     L.fseq_debug_held_out_columns.argtypes = [vp, u64, u64, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_row_split_plan.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.fseq_debug_dp_lists_check.argtypes = [C.c_uint32, u64, u64, C.c_uint32, vp, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -1078,18 +1083,24 @@ class SegmentationContext:
         self._check(self.L.fseq_identity_columns(self.h, mask.ctypes.data, C.byref(sm)))
         return mask.astype(bool), {k: getattr(sm, k) for k, _ in IdentitySummary._fields_}
 
-    def without_identity_columns(self, segment_length, block_len=0, list_cap=0, list_memory=0):
+    def without_identity_columns(self, segment_length, block_len=0, list_cap=0, list_memory=0, keep_held_out=False):
         """A new SegmentationContext over the columns that are not identity columns (fseq_create_without_identity_columns);
-        its results are in reduced co-ordinates (kept_columns() maps them back).  This context may be closed afterwards."""
+        its results are in reduced co-ordinates (kept_columns() maps them back).  This context may be closed afterwards.
+        keep_held_out: on a context made by without_rows(), carry its held-out rows along
+        (fseq_create_without_identity_columns_held): held_out() and match_held_out() (reduced co-ordinates) answer on the new
+        context, and match_held_out_restored() matches the full-length held-out rows against the restored founders."""
         p = Params(0, 0, int(segment_length), 0, int(block_len), int(list_cap), int(self._device))
         h = C.c_void_p()
         sm = IdentitySummary()
-        self._check(self.L.fseq_create_without_identity_columns(self.h, C.byref(p), C.byref(h), C.byref(sm)))
+        create = self.L.fseq_create_without_identity_columns_held if keep_held_out else self.L.fseq_create_without_identity_columns
+        self._check(create(self.h, C.byref(p), C.byref(h), C.byref(sm)))
         new = SegmentationContext.__new__(SegmentationContext)
         new.L, new.h = self.L, h
         new.m, new.n, new.segment_length, new._device = self.m, int(sm.kept), int(segment_length), self._device
         new.result, new._keep = None, None
         new.source_n = int(sm.n)
+        if keep_held_out:
+            new.source_m, new.n_held = self.source_m, self.n_held
         new.identity_summary = {k: getattr(sm, k) for k, _ in IdentitySummary._fields_}
         if list_memory:
             new.set_list_memory(list_memory)
@@ -1125,6 +1136,44 @@ class SegmentationContext:
         self._check(self.L.fseq_match_founders_restored(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
         self._match = sm
         return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    # ---- query rows against the restored founders (leave-rows-out validation with the identity columns removed)
+    def match_held_out_restored(self, permutations, min_segment_length=0):
+        """On a context made by without_identity_columns(keep_held_out=True): the full-length held-out rows matched against the
+        founders write_founders_restored would write (fseq_match_held_out_restored).  The summary dict of match_founders; the
+        pieces are in the source's co-ordinates, their `row` indexes held_out()[1]; match_pieces(), write_match() and
+        match_exceptions() serve the result."""
+        perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+        sm = MatchSummary()
+        self._check(self.L.fseq_match_held_out_restored(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
+        self._match, self._match_rows = sm, self.n_held
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    def match_rows_restored(self, queries, permutations, min_segment_length=0):
+        """On a context made by without_identity_columns(): queries, a C-contiguous uint8 array [n_rows, source_n] of raw
+        bytes (or a list of bytes objects of that length), matched against the restored founders (fseq_match_rows_restored)."""
+        q = queries
+        if not isinstance(q, np.ndarray):
+            q = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in q], dtype=np.uint8).reshape(len(q), -1)
+        q = np.ascontiguousarray(q, dtype=np.uint8)
+        if q.ndim != 2 or q.shape[1] != getattr(self, "source_n", -1):
+            raise ValueError("match_rows_restored: queries must be rows of the source's n = %d bytes" % getattr(self, "source_n", -1))
+        qrows = (C.c_void_p * max(q.shape[0], 1))(*[q.ctypes.data + r * q.strides[0] for r in range(q.shape[0])])
+        perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+        sm = MatchSummary()
+        self._check(self.L.fseq_match_rows_restored(self.h, perm.ctypes.data, qrows, q.shape[0], int(min_segment_length), C.byref(sm)))
+        self._match, self._match_rows = sm, q.shape[0]
+        return {k: getattr(sm, k) for k, _ in MatchSummary._fields_}
+
+    def match_exceptions(self):
+        """(offsets, columns) of the last restored match of query rows (fseq_get_match_exceptions): row r differs from row 0
+        of the reconstruction in the identity columns columns[offsets[r]:offsets[r + 1]] (source positions, ascending)."""
+        total = C.c_uint64()
+        self._check(self.L.fseq_get_match_exceptions(self.h, None, None, C.byref(total)))
+        offsets = np.zeros(int(getattr(self, "_match_rows", 0)) + 1, dtype=np.uint64)
+        columns = np.zeros(total.value, dtype=np.uint32)
+        self._check(self.L.fseq_get_match_exceptions(self.h, offsets.ctypes.data, columns.ctypes.data, None))
+        return offsets, columns
 
     # ---- debug / parity of intermediate state
     def debug_dp(self):

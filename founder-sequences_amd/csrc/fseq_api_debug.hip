@@ -19,7 +19,7 @@ int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 	// (the scan's knob is read by fseq_scan_segment_lengths alone: no geometry, no kernel and no result depends on it)
 	if (!strcmp(name, "FSEQ_SCAN_REBUILD")) return FSEQ_OK;
 	// (... and the matcher's by the match entries alone: the run, its result and its buffers stay)
-	if (!strcmp(name, "FSEQ_MATCH_SPLIT") || !strcmp(name, "FSEQ_MATCH_OVERLAP")) return FSEQ_OK;
+	if (!strcmp(name, "FSEQ_MATCH_SPLIT") || !strcmp(name, "FSEQ_MATCH_OVERLAP") || !strcmp(name, "FSEQ_MATCH_STAGE_BYTES")) return FSEQ_OK;
 	// (the geometry and the kernel choice may depend on it: the work buffers of an earlier run were sized for the old one)
 	(void) hipSetDevice(c->p.device);
 	if (c->stream) (void) hipStreamSynchronize(c->stream);

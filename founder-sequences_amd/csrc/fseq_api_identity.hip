@@ -7,6 +7,7 @@
 // called, and nothing of the source context's segmentation state is touched.
 #include "fseq_ctx.hpp"
 #include "fseq_identity.hpp"
+#include "fseq_exceptions.hpp"
 
 using namespace fseq;
 
@@ -78,13 +79,16 @@ int fseq_identity_columns(fseq_ctx *c, uint8_t *mask, fseq_identity_summary *out
 	return FSEQ_OK;
 }
 
-int fseq_create_without_identity_columns(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary)
+// fseq_create_without_identity_columns and -- held -- fseq_create_without_identity_columns_held, which carries the held-out rows
+// of a source made by fseq_create_without_rows along: their kept columns, the two row maps and their exception cells
+static int create_without_identity_columns(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary, bool held)
 {
 	if (!params || !out) return FSEQ_E_ARG;
 	*out = nullptr;
 	if (params->n != 0) return src ? fail(src, FSEQ_E_ARG, "without identity columns: params->n must be 0 (it becomes the number of kept columns)") : FSEQ_E_ARG;
 	if (!src) return FSEQ_E_ARG;
 	fseq_ctx *const c = src;
+	if (held && (!c->hold.have || c->idn.have)) return fail(c, FSEQ_E_ARG, "without identity columns, held-out rows kept: the source is not a context made by fseq_create_without_rows");
 	if (params->m != 0 && params->m != c->p.m) return fail(c, FSEQ_E_ARG, "without identity columns: params->m must be 0 or the source's");
 	if (params->device != c->p.device) return fail(c, FSEQ_E_ARG, "without identity columns: params->device must be the source's device");
 	if (0 == params->segment_length) return fail(c, FSEQ_E_ARG, "without identity columns: params->segment_length must be positive");
@@ -155,11 +159,59 @@ int fseq_create_without_identity_columns(fseq_ctx *src, fseq_params const *param
 	float ms0 = 0.f, ms1 = 0.f;
 	(void) hipEventElapsedTime(&ms0, E.ev[0], E.ev[1]);
 	(void) hipEventElapsedTime(&ms1, E.ev[2], E.ev[3]);
+	if (held)
+	{
+		// the held-out rows: their kept columns gathered as the alignment's were, and the identity columns in which one of them
+		// differs from row 0 marked in a bit matrix of this call, from which the lists are made (csrc/fseq_exceptions.hpp)
+		auto carry = [&]() -> int {
+			auto &H = d->hold;
+			uint32_t const n_held = c->hold.n_held;
+			IdShape const hs = id_shape(n_held, c->bsh);                  // (chunks * 16 is the source's hold.ld)
+			size_t const ld_h = (size_t) hs.chunks * 16u, nw = (size_t) ((n + 31u) / 32u);
+			try { H.kept_rows = c->hold.kept_rows; H.held_rows = c->hold.held_rows; }
+			catch (std::bad_alloc const &) { return fail(d, FSEQ_E_OOM, "the row maps (host)"); }
+			DevTemp<uint32_t> d_bits(d);
+			int rc2;
+			if ((rc2 = H.cols.alloc(d, ld_h * (size_t) kept + 16)) || (rc2 = d_bits.alloc((size_t) n_held * nw))) return rc2;
+			HIP_TRY(d, hipMemsetAsync(d_bits, 0, (size_t) n_held * nw * 4, st));
+			uint32_t const hcols_per_wg = std::max<uint32_t>(1u, 4096u / hs.chunks);
+			hipLaunchKernelGGL(k_identity_gather, dim3(grid_for((kept + hcols_per_wg - 1u) / hcols_per_wg)), dim3(ID_T), 0, st, (uint8_t const *) c->hold.cols, c->hold.ld,
+			                   (uint32_t const *) d->idn.kept, kept, c->bsh, hs, hcols_per_wg, (uint8_t *) H.cols);
+			hipLaunchKernelGGL(k_exc_bits_held, dim3(grid_for((n * hs.chunks + EX_T - 1u) / EX_T)), dim3(EX_T), 0, st, (uint8_t const *) c->hold.cols, c->hold.ld, n_held,
+			                   hs.chunks, (uint8_t const *) c->d_msa, c->ld, (uint8_t const *) d->idn.mask, n, c->bsh, (uint32_t *) d_bits, nw);
+			HIP_TRY(d, hipGetLastError());
+			if ((rc2 = exc_lists_from_bits(d, st, d_bits, nw, n_held, H.exc_off, H.exc_cols, &H.exc_total))) return rc2;
+			H.have = H.have_exc = true;
+			H.m_src = c->hold.m_src;
+			H.n_held = n_held;
+			H.ld = ld_h;
+			return FSEQ_OK;
+		};
+		if ((rc = carry()))
+		{
+			char what[400];
+			snprintf(what, sizeof(what), "without identity columns, held-out rows kept: %u held-out rows over %llu kept and %llu source columns: %s",
+			         c->hold.n_held, (unsigned long long) kept, (unsigned long long) n, d->err.c_str());
+			(void) hipStreamSynchronize(st);
+			fseq_destroy(d);
+			return fail(c, rc, what);
+		}
+	}
 	d->idn.have = true;
 	d->have_input = true;
 	if (summary) *summary = fseq_identity_summary{n, identity, kept, (double) ms0 + (double) ms1};
 	*out = d;
 	return FSEQ_OK;
+}
+
+int fseq_create_without_identity_columns(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary)
+{
+	return create_without_identity_columns(src, params, out, summary, false);
+}
+
+int fseq_create_without_identity_columns_held(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary)
+{
+	return create_without_identity_columns(src, params, out, summary, true);
 }
 
 int fseq_get_identity_columns(fseq_ctx *c, uint8_t *mask, uint64_t *kept_columns)

@@ -7,6 +7,7 @@
 // touches nothing of the segmentation's state.
 #include "fseq_ctx.hpp"
 #include "fseq_match.hpp"
+#include "fseq_exceptions.hpp"
 
 using namespace fseq;
 
@@ -26,48 +27,58 @@ int refuse_common(fseq_ctx *c, uint32_t K)
 	return FSEQ_OK;
 }
 
-// A.kept set: the restored form of the walk (source positions, gap steps), a kernel of its own per variant
-template <bool WRITE, bool RST>
+// A.kept set: the restored form of the walk (source positions, gap steps), a kernel of its own per variant; A.exc_off set as
+// well: the restored form for query rows, which reads their exception cells
+template <bool WRITE, bool RST, bool EXC>
 hipError_t launch_walk_as(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
 {
 	void (*k)(MatchWalkArgs) = nullptr;
 	switch (s.WR)
 	{
-		case 1: k = k_match_walk<1, WRITE, RST>; break;
-		case 2: k = k_match_walk<2, WRITE, RST>; break;
-		case 4: k = k_match_walk<4, WRITE, RST>; break;
-		case 8: k = k_match_walk<8, WRITE, RST>; break;
-		default: k = k_match_walk<0, WRITE, RST>; break;
+		case 1: k = k_match_walk<1, WRITE, RST, EXC>; break;
+		case 2: k = k_match_walk<2, WRITE, RST, EXC>; break;
+		case 4: k = k_match_walk<4, WRITE, RST, EXC>; break;
+		case 8: k = k_match_walk<8, WRITE, RST, EXC>; break;
+		default: k = k_match_walk<0, WRITE, RST, EXC>; break;
 	}
 	hipError_t const e = allow_lds(k, s.lds);
 	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(k, dim3((c->p.m + MT_T - 1u) / MT_T), dim3(MT_T), s.lds, c->stream, A);
+	hipLaunchKernelGGL(k, dim3((A.m + MT_T - 1u) / MT_T), dim3(MT_T), s.lds, c->stream, A);
 	return hipGetLastError();
 }
 
 template <bool WRITE>
 hipError_t launch_walk(fseq_ctx *c, MatchShape const &s, MatchWalkArgs const &A)
 {
-	return A.kept ? launch_walk_as<WRITE, true>(c, s, A) : launch_walk_as<WRITE, false>(c, s, A);
+	if (!A.kept) return launch_walk_as<WRITE, false, false>(c, s, A);
+	return A.exc_off ? launch_walk_as<WRITE, true, true>(c, s, A) : launch_walk_as<WRITE, true, false>(c, s, A);
 }
+
+// the rows a match walks where they are not the alignment's: the queries of fseq_match_rows, the held-out rows
+struct MatchRows { uint8_t const *cols; size_t ld; uint32_t m, bsh; };
+// ... and, for the restored walk of such rows, their exception cells (csrc/fseq_exceptions.hpp)
+struct MatchExceptions { uint64_t const *off; uint32_t const *cols; };
 
 // both walks over the founders' columns in c->match.fcols; ev[0] has been recorded in front of the kernel that wrote them.
 // ms_device = ev[0] .. ev[1] (the founders' columns, the counting walk, the scan) + ev[2] .. ev[3] (the writing walk): the host's
 // wait for the totals and the allocation of the output between the two are not in it.
-// restored: the pieces in the source's co-ordinates, the identity columns of c->idn between the kept columns accounted for
-int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out, bool restored = false)
+// restored: the pieces in the source's co-ordinates, the identity columns of c->idn between the kept columns accounted for.
+// R: the rows walked (nullptr: the alignment's); X: restored query rows' exception cells
+int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out, bool restored = false, MatchRows const *R = nullptr,
+              MatchExceptions const *X = nullptr)
 {
 	auto &mt = c->match;
 	hipStream_t st = c->stream;
-	uint32_t const m = c->p.m;
+	uint32_t const m = R ? R->m : c->p.m;
 	int rc;
 	if ((rc = mt.cnt.ensure(c, 3 * (size_t) m)) || (rc = mt.off.ensure(c, (size_t) m + 1 + 4))) return rc;
 	uint64_t *const d_tot = mt.off + (m + 1);
 	MatchWalkArgs A{};
-	A.msa = c->d_msa; A.ld = c->ld; A.m = m; A.n = c->p.n; A.bsh = c->bsh; A.sigma = c->sigma;
+	A.msa = R ? R->cols : c->d_msa; A.ld = R ? R->ld : c->ld; A.m = m; A.n = c->p.n; A.bsh = R ? R->bsh : c->bsh; A.sigma = c->sigma;
 	A.fcols = mt.fcols; A.K = s.K; A.Kp = s.Kp; A.W = s.W; A.Wk = s.Wk; A.TC = s.TC; A.min_len = min_len;
 	A.cnt = mt.cnt; A.off = mt.off;
 	if (restored) { A.kept = c->idn.kept; A.n_src = c->idn.n_src; }
+	if (restored && X) { A.exc_off = X->off; A.exc_cols = X->cols; }
 	hipError_t e = launch_walk<false>(c, s, A);
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "match: counting walk", e);
 	hipLaunchKernelGGL(k_match_scan, dim3(1), dim3(MT_SCAN_T), 0, st, mt.cnt, m, mt.off, d_tot);
@@ -95,9 +106,6 @@ int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_sum
 	*out = mt.sum;
 	return FSEQ_OK;
 }
-
-// the rows a split match walks: the alignment's, or the queries of fseq_match_rows
-struct MatchRows { uint8_t const *cols; size_t ld; uint32_t m, bsh; };
 
 template <bool WRITE>
 hipError_t launch_split(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &A, dim3 grid)
@@ -196,6 +204,7 @@ int begin_match(fseq_ctx *c, MatchShape const &s)
 {
 	auto &mt = c->match;
 	mt.have = false;                                              // (a failed match leaves no result behind)
+	mt.exc_from = 0;
 	for (auto &e : mt.ev)
 		if (!e) HIP_TRY(c, hipEventCreate(&e));
 	return mt.fcols.ensure(c, (size_t) c->p.n * s.Kp);
@@ -333,6 +342,66 @@ int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uin
 	return FSEQ_OK;
 }
 
+// the queries of fseq_match_rows_restored, n_src raw bytes each: column chunks of the SOURCE through the same bounded staging;
+// k_match_pack_rows_kept packs a chunk's kept columns into their reduced positions of c->match.qrows, k_exc_bits_rows marks
+// the chunk's identity columns in which a query differs from row 0 in a bit matrix of this call, from which
+// c->match.exc_off / exc_cols are made (csrc/fseq_exceptions.hpp).  Every query byte crosses to the device once
+int upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld)
+{
+	hipStream_t st = c->stream;
+	auto &mt = c->match;
+	uint64_t const n = c->p.n, n_src = c->idn.n_src;
+	size_t const nw = (size_t) ((n_src + 31u) / 32u);
+	int rc;
+	if ((rc = mt.qrows.ensure(c, (size_t) n * ld))) return rc;
+	// columns of a chunk: a multiple of 64 (a lane of k_exc_bits_rows owns a word of 32 columns; FSEQ_MATCH_STAGE_BYTES: at least 64)
+	uint64_t cw = ((c->tune.match_stage ? (size_t) c->tune.match_stage : MT_QUERY_STAGE_BYTES) / n_rows) & ~uint64_t(63);
+	if (c->tune.match_stage) cw = std::max<uint64_t>(cw, 64);
+	if (!cw) return fail(c, FSEQ_E_UNSUPPORTED, "match: more query rows than 64 columns of them fit the upload's 64 MiB");
+	cw = std::min<uint64_t>(cw, (n_src + 63) & ~uint64_t(63));
+	DevTemp<uint8_t> d_stage(c), d_lut(c);
+	DevTemp<uint32_t> d_bits(c);
+	if ((rc = d_stage.alloc((size_t) n_rows * cw)) || (rc = d_lut.alloc(256)) || (rc = d_bits.alloc((size_t) n_rows * nw))) return rc;
+	uint8_t code_of[256];
+	memset(code_of, (int) (c->sigma & 0xFFu), sizeof(code_of));    // (a byte outside the alphabet: the code above the alphabet's)
+	for (uint32_t k = 0; k < c->sigma; ++k) code_of[c->code_to_byte[k]] = (uint8_t) k;
+	std::vector<uint8_t> stage;
+	std::vector<uint32_t> kept;
+	try { stage.assign((size_t) n_rows * cw, 0); kept.resize((size_t) n); } catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "match: host staging of the query rows"); }
+	HIP_TRY(c, hipMemcpyAsync(kept.data(), c->idn.kept, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(d_lut, code_of, 256, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	for (uint64_t c0 = 0; c0 < n_src; c0 += cw)
+	{
+		uint32_t const w = (uint32_t) std::min<uint64_t>(cw, n_src - c0);
+		for (uint32_t q = 0; q < n_rows; ++q) memcpy(stage.data() + (size_t) q * cw, rows[q] + c0, w);
+		HIP_TRY(c, hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+		uint64_t const j_lo = (uint64_t) (std::lower_bound(kept.begin(), kept.end(), (uint32_t) c0) - kept.begin());
+		uint64_t const j_hi = (uint64_t) (std::lower_bound(kept.begin(), kept.end(), (uint32_t) (c0 + w)) - kept.begin());
+		if (j_hi > j_lo)
+			hipLaunchKernelGGL(k_match_pack_rows_kept, dim3((uint32_t) ((j_hi - j_lo + MT_PACK_COLS - 1u) / MT_PACK_COLS), (n_rows + MT_T - 1u) / MT_T), dim3(MT_T), 0, st,
+			                   (uint8_t const *) d_stage, (size_t) cw, n_rows, c0, j_lo, j_hi, (uint32_t const *) c->idn.kept, (uint8_t const *) d_lut, bsh, (uint8_t *) mt.qrows, ld);
+		uint64_t const lanes = (uint64_t) n_rows * ((w + 31u) / 32u);
+		hipLaunchKernelGGL(k_exc_bits_rows, dim3((uint32_t) ((lanes + EX_T - 1u) / EX_T)), dim3(EX_T), 0, st, (uint8_t const *) d_stage, (size_t) cw, n_rows, c0, w,
+		                   (uint8_t const *) c->idn.ref, (uint8_t const *) c->idn.mask, n_src, (uint32_t *) d_bits, nw);
+		HIP_TRY(c, hipGetLastError());
+		HIP_TRY(c, hipStreamSynchronize(st));                     // (the staging is filled again)
+	}
+	return exc_lists_from_bits(c, st, d_bits, nw, n_rows, mt.exc_off, mt.exc_cols, &mt.exc_total);
+}
+
+// fseq_match_held_out_restored / fseq_match_rows_restored behind their refusals: the unsplit restored walk over the query rows R
+int match_queries_restored(fseq_ctx *c, uint32_t const *permutations, MatchShape const &s, MatchRows const &R, MatchExceptions const &X, int from,
+                           uint64_t min_segment_length, fseq_match_summary *out)
+{
+	FounderTemps T(c);
+	int rc = cols_from_permutations(c, permutations, s, T);
+	if (rc || (rc = run_match(c, s, min_segment_length, out, true, &R, &X))) return rc;
+	c->match.exc_from = from;
+	c->match.exc_rows = R.m;
+	return FSEQ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -419,6 +488,57 @@ int fseq_match_held_out(fseq_ctx *c, uint32_t const *permutations, uint8_t const
 	uint32_t const n_held = c->hold.n_held;
 	MatchSplitPlan const plan = match_split_plan(c->p.n, n_held, (uint32_t) std::max(cus, 1), (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, true);
 	return run_match_split(c, s, MatchRows{c->hold.cols, c->hold.ld, n_held, c->bsh}, plan, min_segment_length, out);
+}
+
+// the held-out rows' kept columns (c->hold.cols) walked at their source positions, with the exception cells the context was made
+// with (fseq_create_without_identity_columns_held): nothing is uploaded, packed or scanned for
+int fseq_match_held_out_restored(fseq_ctx *c, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out)
+{
+	if (!c || !permutations || !out) return FSEQ_E_ARG;
+	if (!c->idn.have || !c->hold.have_exc) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns_held");
+	size_t X = 0;
+	int rc = check_permutations(c, true, X);
+	if (rc) return rc;
+	(void) hipSetDevice(c->p.device);
+	MatchShape const s = match_shape((uint32_t) X, c->sigma, c->bsh);
+	if ((rc = begin_match(c, s))) return rc;
+	return match_queries_restored(c, permutations, s, MatchRows{c->hold.cols, c->hold.ld, c->hold.n_held, c->bsh}, MatchExceptions{c->hold.exc_off, c->hold.exc_cols}, 1,
+	                              min_segment_length, out);
+}
+
+int fseq_match_rows_restored(fseq_ctx *c, uint32_t const *permutations, uint8_t const *const *rows, uint32_t n_rows, uint64_t min_segment_length,
+                             fseq_match_summary *out)
+{
+	if (!c || !permutations || !out) return FSEQ_E_ARG;
+	if (!rows || 0 == n_rows) return fail(c, FSEQ_E_ARG, "match: no query rows");
+	for (uint32_t q = 0; q < n_rows; ++q)
+		if (!rows[q]) return fail(c, FSEQ_E_ARG, "match: null query row");
+	if (!c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
+	size_t X = 0;
+	int rc = check_permutations(c, true, X);
+	if (rc) return rc;
+	(void) hipSetDevice(c->p.device);
+	// the queries' packing: the narrowest that leaves the code `sigma` free for a byte outside the alphabet
+	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
+	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
+	MatchShape const s = match_shape((uint32_t) X, sigma, bsh);
+	if ((rc = begin_match(c, s)) || (rc = upload_queries_restored(c, rows, n_rows, bsh, ld))) return rc;
+	return match_queries_restored(c, permutations, s, MatchRows{c->match.qrows, ld, n_rows, bsh}, MatchExceptions{c->match.exc_off, c->match.exc_cols}, 2,
+	                              min_segment_length, out);
+}
+
+int fseq_get_match_exceptions(fseq_ctx *c, uint64_t *offsets, uint32_t *columns, uint64_t *total)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!c->match.have || !c->match.exc_from)
+		return fail(c, FSEQ_E_ARG, "the last match on this context is not a restored match of query rows (fseq_match_held_out_restored / fseq_match_rows_restored)");
+	bool const own = c->match.exc_from == 2;
+	uint64_t const all = own ? c->match.exc_total : c->hold.exc_total;
+	(void) hipSetDevice(c->p.device);
+	if (offsets) HIP_TRY(c, hipMemcpy(offsets, own ? (uint64_t *) c->match.exc_off : (uint64_t *) c->hold.exc_off, ((size_t) c->match.exc_rows + 1) * 8, hipMemcpyDeviceToHost));
+	if (columns && all) HIP_TRY(c, hipMemcpy(columns, own ? (uint32_t *) c->match.exc_cols : (uint32_t *) c->hold.exc_cols, (size_t) all * 4, hipMemcpyDeviceToHost));
+	if (total) *total = all;
+	return FSEQ_OK;
 }
 
 int fseq_debug_match_split(fseq_ctx *c, fseq_match_split_info *info)

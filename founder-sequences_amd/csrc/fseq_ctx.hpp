@@ -141,6 +141,7 @@ struct Tuning {
 	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
 	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: fseq_match_rows chooses, the other entries walk unsplit)
 	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns a segment's cold walk starts in front of its range (by itself: 16,384)
+	int  match_stage = 0;                // FSEQ_MATCH_STAGE_BYTES: most bytes of a staged chunk of fseq_match_rows_restored's query rows (by itself: 64 MiB; tests: chunks of 64 columns)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -193,6 +194,7 @@ struct Tuning {
 			{"FSEQ_SCAN_REBUILD", &Tuning::scan_rebuild, nullptr, 0, 0, nullptr},
 			{"FSEQ_MATCH_SPLIT", nullptr, &Tuning::match_split, 1, 0, nullptr},
 			{"FSEQ_MATCH_OVERLAP", nullptr, &Tuning::match_overlap, 1, 0, nullptr},
+			{"FSEQ_MATCH_STAGE_BYTES", nullptr, &Tuning::match_stage, 64, 0, nullptr},
 		};
 		return table;
 	}
@@ -495,6 +497,11 @@ struct fseq_ctx {
 		DevBuf<uint32_t> sets;               // ... their founder sets, set_words each
 		DevBuf<uint8_t> qrows;               // fseq_match_rows: the query rows, column-major and packed like the alignment
 		DevBuf<uint32_t> split;              // the split walk: head and tail of every (row, g), flag and list of the row groups, {flagged groups, rows that do not stand}
+		DevBuf<uint64_t> exc_off;            // fseq_match_rows_restored: the queries' exception cells (csrc/fseq_exceptions.hpp), [rows + 1]
+		DevBuf<uint32_t> exc_cols;           // ... their source columns, exactly exc_total entries
+		uint64_t exc_total = 0;
+		int exc_from = 0;                    // whose exception cells the last match walked (fseq_get_match_exceptions): 0 none, 1 hold's, 2 the ones above
+		uint32_t exc_rows = 0;               // ... and of how many query rows
 		bool have = false;
 		fseq_match_summary sum{};
 		fseq_match_split_info split_info{};  // how the last match walked (fseq_debug_match_split)
@@ -502,9 +509,10 @@ struct fseq_ctx {
 	} match;
 	void free_match()
 	{
-		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets, match.qrows, match.split);
+		fseq::release_all(this, match.fcols, match.cnt, match.off, match.pieces, match.sets, match.qrows, match.split, match.exc_off, match.exc_cols);
 		for (auto &e : match.ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
 		match.have = false;
+		match.exc_from = 0;
 	}
 
 	// a context over the kept columns of another (fseq_create_without_identity_columns, csrc/fseq_api_identity.hip): what it
@@ -530,11 +538,17 @@ struct fseq_ctx {
 		size_t ld = 0;                       // bytes of a held-out column: n_held fields rounded up to 16
 		DevBuf<uint8_t> cols;                // column k at cols + k * ld; row q of it is held_rows[q]
 		std::vector<uint32_t> kept_rows, held_rows;      // source row of this context's row j (ascending); the caller's list
+		// fseq_create_without_identity_columns_held: cols holds the KEPT columns, and the held-out rows' exception cells (where one
+		// differs from row 0 in an identity column; csrc/fseq_exceptions.hpp) are kept beside them
+		bool have_exc = false;
+		DevBuf<uint64_t> exc_off;            // [n_held + 1]
+		DevBuf<uint32_t> exc_cols;           // source columns, ascending per row, exactly exc_total entries
+		uint64_t exc_total = 0;
 	} hold;
 	void free_held_out()
 	{
-		fseq::release_all(this, hold.cols);
-		hold.have = false;
+		fseq::release_all(this, hold.cols, hold.exc_off, hold.exc_cols);
+		hold.have = hold.have_exc = false;
 	}
 
 	// the input in column chunks (fseq_input_begin .. fseq_input_end, csrc/fseq_api_input.hip): alive between begin and end only

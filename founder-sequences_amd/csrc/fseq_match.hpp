@@ -28,7 +28,14 @@
 //       [lb, g_lo) and starts again from all founders; with min_len != 0 the piece is closed every min_len source columns
 //       while lb + min_len < g_hi, the first time with the live set as it is, then with all founders.  The counting pass takes
 //       the number of these closes from one division; the writing pass loops over the pieces it stores.  An empty gap costs one
-//       uniform compare.  The plain form (RST = false) is a kernel of its own and compiles as before.
+//       uniform compare.  The plain form (RST = false) is a kernel of its own.
+//   k_match_walk<WR, WRITE, true, true>   the restored form for QUERY rows (fseq_match_held_out_restored,
+//       fseq_match_rows_restored): a row that took no part in the reconstruction may differ from row 0 in an identity column,
+//       where every restored founder carries row 0's byte: an EXCEPTION cell, in which no founder agrees with the row.  That is
+//       the ordinary column step with the empty set.  Every lane carries a cursor into its row's ascending list of exception
+//       columns (csrc/fseq_exceptions.hpp) and, before a kept column k, drains the exceptions below k: the gap step up to the
+//       exception, the column step there, then on from the column behind it.  A row without exceptions pays one compare a
+//       kept column.  The walk is unsplit, as the restored walk of the input rows is.
 //
 //   k_match_pack_rows   rows that are not the alignment's (fseq_match_rows): a staged chunk of raw query bytes, one row after
 //       the other, is sent through the context's code table, transposed and packed like the alignment, at the narrowest of
@@ -68,6 +75,7 @@ constexpr uint32_t MT_SET_BYTES = 64 * 1024;        // the tile's founder sets
 constexpr size_t   MT_LDS_BYTES = 152 * 1024;       // what a workgroup may take in all
 constexpr uint32_t MT_NOCODE = 0xFF;                // a founder symbol outside the alphabet (sigma < 256; with 256 codes there is none)
 constexpr uint32_t MT_SCAN_T = 1024;
+constexpr uint32_t MT_NO_EXC = 0xFFFFFFFFu;          // no exception column left (a source has fewer than 2^32 - 1 columns)
 
 __host__ __device__ inline uint64_t mt_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __host__ __device__ inline uint64_t mt_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
@@ -186,13 +194,16 @@ struct MatchWalkArgs {
 	uint32_t *sets;
 	uint32_t const *kept;                            // RST: source position of every column, ascending; n_src source columns
 	uint64_t n_src;
+	uint64_t const *exc_off;                         // EXC: row r's exception columns are exc_cols[exc_off[r] .. exc_off[r + 1]), source
+	uint32_t const *exc_cols;                        //      positions, ascending
 };
 
 // LDS: [TC x Kp founder codes][TC x (MT_T >> bsh) bytes of alignment columns][(TC x sigma + 1) sets of Wk words; the last one
 // stays empty][WR = 0: Wk x MT_T words of live sets]; RST: the tile's source positions in 64 words of their own
-template <uint32_t WR, bool WRITE, bool RST = false>
+template <uint32_t WR, bool WRITE, bool RST = false, bool EXC = false>
 static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const A)
 {
+	static_assert(RST || !EXC, "exception columns are identity columns of a restored walk");
 	extern __shared__ uint4 mt_smem[];
 	__shared__ uint32_t mt_pos[RST ? MT_TILE_MAX : 1];
 	uint32_t const tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -220,8 +231,12 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 	uint64_t lb = 0;
 	uint32_t npieces = 0, nunc = 0, nshort = 0;
 	bool alive = true;
-	uint64_t src_next = 0;                                               // RST: the source column behind the last kept column walked
+	uint64_t src_next = 0;                                               // RST: the source column behind the last column walked
 	uint64_t const out0 = (WRITE && active) ? A.off[row] : 0;
+	// EXC: the cursor into the row's exception columns and the one it stands at (none left: beyond every source column)
+	uint64_t e_at = (EXC && active) ? A.exc_off[row] : 0;
+	uint64_t const e_end = (EXC && active) ? A.exc_off[row + 1u] : 0;
+	uint32_t e_col = (EXC && e_at < e_end) ? A.exc_cols[e_at] : MT_NO_EXC;
 
 	auto emit = [&](uint64_t rb) {
 		if (WRITE)
@@ -275,6 +290,57 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 					all_founders();
 				}
 			}
+		}
+	};
+
+	// the step of one column, match_founder_sequences.cc:166-208: k its position, M the founders that carry the row's symbol
+	// there.  The AND is made once: kept in registers where the set is (WR words), and for the sets in LDS written over the
+	// live set only when the piece goes on (a close prints the set as it was)
+	auto col_step = [&](uint64_t k, uint32_t const *const M) {
+		bool recheck = false;
+		uint32_t any = 0;
+		uint32_t nv[WR ? WR : 1];
+		if (min_len != 0 && min_len <= k - lb) recheck = true;
+		else
+		{
+			if (WR)
+			{
+				for (uint32_t i = 0; i < live.words(); ++i) { nv[i] = live.get(i) & M[i]; any |= nv[i]; }
+			}
+			else
+			{
+				// (only whether a founder is left: stops at the first word that keeps one)
+				for (uint32_t i = 0; i < live.words() && !any; ++i) any = live.get(i) & M[i];
+			}
+			if (!any) { if (min_len != 0) ++nshort; recheck = true; }
+		}
+		if (recheck)
+		{
+			emit(k);
+			lb = k;
+			any = 0;
+			for (uint32_t i = 0; i < live.words(); ++i) { uint32_t const v = M[i]; live.set(i, v); any |= v; }
+			if (!any) ++nunc;
+		}
+		else if (WR)
+		{
+			for (uint32_t i = 0; i < live.words(); ++i) live.set(i, nv[i]);
+		}
+		else
+		{
+			for (uint32_t i = 0; i < live.words(); ++i) live.set(i, live.get(i) & M[i]);
+		}
+		alive = any != 0;
+	};
+	// EXC: the row's exception columns below `upto`: each is the column step with no founder, between the gaps around it
+	auto drain = [&](uint64_t upto) {
+		while (e_col < upto)
+		{
+			gap_step(src_next, e_col);
+			col_step(e_col, empty_set);
+			src_next = (uint64_t) e_col + 1u;
+			++e_at;
+			e_col = e_at < e_end ? A.exc_cols[e_at] : MT_NO_EXC;
 		}
 	};
 
@@ -336,50 +402,16 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk(MatchWalkArgs const 
 			for (uint32_t j = 0; j < tc; ++j)
 			{
 				uint64_t const k = RST ? (uint64_t) mt_pos[j] : c0 + j;
+				if (EXC) drain(k);
 				if (RST) { gap_step(src_next, k); src_next = k + 1u; }
 				uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
-				uint32_t const *const M = code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set;
-				// match_founder_sequences.cc:166-208.  The AND is made once: kept in registers where the set is (WR words), and
-				// for the sets in LDS written over the live set only when the piece goes on (a close prints the set as it was)
-				bool recheck = false;
-				uint32_t any = 0;
-				uint32_t nv[WR ? WR : 1];
-				if (min_len != 0 && min_len <= k - lb) recheck = true;
-				else
-				{
-					if (WR)
-					{
-						for (uint32_t i = 0; i < live.words(); ++i) { nv[i] = live.get(i) & M[i]; any |= nv[i]; }
-					}
-					else
-					{
-						// (only whether a founder is left: stops at the first word that keeps one)
-						for (uint32_t i = 0; i < live.words() && !any; ++i) any = live.get(i) & M[i];
-					}
-					if (!any) { if (min_len != 0) ++nshort; recheck = true; }
-				}
-				if (recheck)
-				{
-					emit(k);
-					lb = k;
-					any = 0;
-					for (uint32_t i = 0; i < live.words(); ++i) { uint32_t const v = M[i]; live.set(i, v); any |= v; }
-					if (!any) ++nunc;
-				}
-				else if (WR)
-				{
-					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, nv[i]);
-				}
-				else
-				{
-					for (uint32_t i = 0; i < live.words(); ++i) live.set(i, live.get(i) & M[i]);
-				}
-				alive = any != 0;
+				col_step(k, code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set);
 			}
 		__syncthreads();
 	}
 	if (active)
 	{
+		if (EXC) drain(A.n_src);
 		if (RST) gap_step(src_next, A.n_src);
 		if (alive) emit(RST ? A.n_src : n);
 		if (!WRITE) { A.cnt[row] = npieces; A.cnt[A.m + row] = nunc; A.cnt[2u * (size_t) A.m + row] = nshort; }

@@ -59,6 +59,12 @@ char const *const USAGE =
 	"      --output-restored-matches=PATH ... and match the full-length input against the restored founders on the device: the report\n"
 	"                                     of match-sequences-to-founders on the output of insert-identity-columns (requires\n"
 	"                                     --remove-identity-columns; honours --match-min-segment-length)\n"
+	"      --output-held-out-restored-matches=PATH  With --hold-out and --remove-identity-columns: match the full-length held-out\n"
+	"                                     sequences against the restored founders on the device: the report of match-sequences-to-founders\n"
+	"                                     for them and the founders file (SEQUENCE_INDEX counts along the --hold-out LIST; source\n"
+	"                                     co-ordinates; honours --match-min-segment-length).  The two options combine only with this one\n"
+	"      --output-sequence-restored-matches=PATH  With --match-sequences and --remove-identity-columns: the same for the sequences\n"
+	"                                     of LIST, of the input's full length\n"
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
@@ -194,8 +200,9 @@ bool report_match(fseq_ctx *ctx, int rc, fseq_match_summary const &sm, char cons
 }
 
 // --match-sequences: the held-out sequences against the founders the context has (permutations) or the rows given
+// restored (--output-sequence-restored-matches): full-length sequences against the restored founders of the permutations
 bool match_held_out(fseq_ctx *ctx, char const *list, size_t seq_length, uint32_t const *perm, uint8_t const *const *frows, uint32_t K,
-                    unsigned long long min_len, char const *path)
+                    unsigned long long min_len, char const *path, bool restored = false)
 {
 	std::cerr << "Matching the sequences of '" << list << "' against the founders…" << std::endl;
 	std::vector<std::string> queries;
@@ -208,7 +215,8 @@ bool match_held_out(fseq_ctx *ctx, char const *list, size_t seq_length, uint32_t
 		qrows[i] = reinterpret_cast<uint8_t const *>(queries[i].data());
 	}
 	fseq_match_summary sm{};
-	int const rc(fseq_match_rows(ctx, perm, frows, K, qrows.data(), (uint32_t) qrows.size(), min_len, &sm));
+	int const rc(restored ? fseq_match_rows_restored(ctx, perm, qrows.data(), (uint32_t) qrows.size(), min_len, &sm)
+	                      : fseq_match_rows(ctx, perm, frows, K, qrows.data(), (uint32_t) qrows.size(), min_len, &sm));
 	return report_match(ctx, rc, sm, path);
 }
 
@@ -305,7 +313,7 @@ bool parse_hold_out(char const *spec, std::vector<uint32_t> &out, std::string &w
 
 int main(int argc, char **argv)
 {
-	char const *hold_out_spec = nullptr, *out_held_matches = nullptr;
+	char const *hold_out_spec = nullptr, *out_held_matches = nullptr, *out_held_restored = nullptr, *out_seq_restored = nullptr;
 	std::vector<uint32_t> held_rows;
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr;
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr;
@@ -341,6 +349,7 @@ int main(int argc, char **argv)
 		{"max-founders", required_argument, nullptr, 1013},
 		{"match-sequences", required_argument, nullptr, 1014}, {"output-sequence-matches", required_argument, nullptr, 1015},
 		{"hold-out", required_argument, nullptr, 1016}, {"output-held-out-matches", required_argument, nullptr, 1017},
+		{"output-held-out-restored-matches", required_argument, nullptr, 1018}, {"output-sequence-restored-matches", required_argument, nullptr, 1019},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -415,6 +424,8 @@ int main(int argc, char **argv)
 			case 1015: out_seq_matches = optarg; break;
 			case 1016: hold_out_spec = optarg; break;
 			case 1017: out_held_matches = optarg; break;
+			case 1018: out_held_restored = optarg; break;
+			case 1019: out_seq_restored = optarg; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -448,10 +459,13 @@ int main(int argc, char **argv)
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
 	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
-	if (match_seqs && !out_seq_matches) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
+	if (match_seqs && !out_seq_matches && !out_seq_restored) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_matches && !match_seqs) { std::cerr << "--output-sequence-matches requires --match-sequences." << std::endl; return EXIT_FAILURE; }
 	if (match_seqs && gpus > 1) { std::cerr << "--match-sequences is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
-	if (match_seqs && remove_identity) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	if (out_seq_restored && !(match_seqs && remove_identity)) { std::cerr << "--output-sequence-restored-matches requires --match-sequences and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
+	if (out_held_restored && !(hold_out_spec && remove_identity)) { std::cerr << "--output-held-out-restored-matches requires --hold-out and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
+	// (the two combine with --remove-identity-columns only for the restored match; the reports in reduced co-ordinates stay refused)
+	if (match_seqs && remove_identity && (!out_seq_restored || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
@@ -461,7 +475,7 @@ int main(int argc, char **argv)
 		std::string why;
 		if (!parse_hold_out(hold_out_spec, held_rows, why)) { std::cerr << "The list of sequences to hold out is " << why << '.' << std::endl; return EXIT_FAILURE; }
 		if (gpus > 1) { std::cerr << "--hold-out is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
-		if (remove_identity) { std::cerr << "--hold-out is not supported together with --remove-identity-columns (the held-out sequences would have to lose the same columns)." << std::endl; return EXIT_FAILURE; }
+		if (remove_identity && (!out_held_restored || out_held_matches)) { std::cerr << "--hold-out is not supported together with --remove-identity-columns (the held-out sequences would have to lose the same columns)." << std::endl; return EXIT_FAILURE; }
 		if (scan_spec && !seg_len_given && !max_founders_given)
 		{ std::cerr << "--hold-out with --scan-segment-lengths needs a segment length to go on with (--segment-length-bound or --max-founders): a scan alone writes its table and nothing else." << std::endl; return EXIT_FAILURE; }
 	}
@@ -589,7 +603,9 @@ int main(int argc, char **argv)
 			pk.m = 0; pk.n = 0;
 			fseq_ctx *kept(nullptr);
 			fseq_identity_summary is{};
-			if (FSEQ_OK != (rc_ = fseq_create_without_identity_columns(ctxs[r], &pk, &kept, &is))) return rc_;
+			// (--hold-out: the held-out sequences go along, their kept columns and the identity columns in which they differ)
+			rc_ = hold_out_spec ? fseq_create_without_identity_columns_held(ctxs[r], &pk, &kept, &is) : fseq_create_without_identity_columns(ctxs[r], &pk, &kept, &is);
+			if (FSEQ_OK != rc_) return rc_;
 			fseq_destroy(ctxs[r]);
 			ctxs[r] = kept;
 			std::cerr << "Removed " << is.identity << " of " << is.n << " columns in which all sequences agree." << std::endl;
@@ -700,11 +716,16 @@ int main(int argc, char **argv)
 			rc = fseq_match_founder_rows(ctx, frows.data(), res.max_segment_size, match_min_len, &sm);
 			if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
 		}
-		if (match_seqs)
+		if (match_seqs && out_seq_matches)
 		{
 			std::vector<uint8_t const *> frows(res.max_segment_size);
 			for (uint32_t i = 0; i < res.max_segment_size; ++i) frows[i] = upload_given ? reinterpret_cast<uint8_t const *>(named[i].data()) : rows[first[i]];
 			if (!match_held_out(ctx, match_seqs, seq_length, nullptr, frows.data(), res.max_segment_size, match_min_len, out_seq_matches)) return EXIT_FAILURE;
+		}
+		if (out_held_restored || out_seq_restored)
+		{
+			std::cerr << "A match against the restored founders needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
+			return EXIT_FAILURE;
 		}
 		if (out_restored_matches)
 		{
@@ -807,7 +828,8 @@ int main(int argc, char **argv)
 		rc = fseq_match_founders(ctx, perm.data(), match_min_len, &sm);
 		if (!report_match(ctx, rc, sm, out_matches)) return EXIT_FAILURE;
 	}
-	if (match_seqs && !match_held_out(ctx, match_seqs, seq_length, perm.data(), nullptr, 0, match_min_len, out_seq_matches)) return EXIT_FAILURE;
+	if (match_seqs && out_seq_matches && !match_held_out(ctx, match_seqs, seq_length, perm.data(), nullptr, 0, match_min_len, out_seq_matches)) return EXIT_FAILURE;
+	if (out_seq_restored && !match_held_out(ctx, match_seqs, seq_length, perm.data(), nullptr, 0, match_min_len, out_seq_restored, true)) return EXIT_FAILURE;
 	if (out_restored_matches)
 	{
 		// the last step of the chain: the full-length input against the founders just written, in the source's co-ordinates
@@ -817,6 +839,13 @@ int main(int argc, char **argv)
 		if (!report_match(ctx, rc, sm, out_restored_matches)) return EXIT_FAILURE;
 	}
 	if (out_held_matches && !match_context_held_out(ctx, perm.data(), nullptr, 0, match_min_len, out_held_matches)) return EXIT_FAILURE;      // (last: one match at a time)
+	if (out_held_restored)
+	{
+		std::cerr << "Matching the held-out sequences against the restored founders…" << std::endl;
+		fseq_match_summary sm{};
+		rc = fseq_match_held_out_restored(ctx, perm.data(), match_min_len, &sm);
+		if (!report_match(ctx, rc, sm, out_held_restored)) return EXIT_FAILURE;
+	}
 	std::cerr << "Done." << std::endl;
 	for (fseq_ctx *c_ : ctxs) if (c_) fseq_destroy(c_);
 	return EXIT_SUCCESS;

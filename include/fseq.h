@@ -371,8 +371,8 @@ int  fseq_write_match(fseq_ctx *ctx, char const *path);
  * fseq_match_piece::row is the query index; the report of fseq_write_match is match-sequences-to-founders' stdout for these
  * sequences and founders.  Refusals as the other entries (sharded context, no alignment, K > 2,048, n >= 2^32 - 1, permutations
  * without a finished long-path run); FSEQ_E_ARG also for rows == NULL, a NULL row, n_rows == 0 and a context made by
- * fseq_create_without_identity_columns.  The result replaces the context's last match.  Detected by symbol: FSEQ_ABI_VERSION
- * stays 5. */
+ * fseq_create_without_identity_columns (its columns are the kept ones of a longer source: fseq_match_rows_restored takes
+ * full-length queries there).  The result replaces the context's last match.  Detected by symbol: FSEQ_ABI_VERSION stays 5. */
 int  fseq_match_rows(fseq_ctx *ctx, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K,
                      uint8_t const *const *rows, uint32_t n_rows, uint64_t min_segment_length, fseq_match_summary *out);
 
@@ -458,7 +458,7 @@ typedef struct fseq_hold_out_summary {
  * or written, and it may be the source of further calls (one per fold).  FSEQ_E_UNSUPPORTED: a sharded source (a rank holds its
  * own columns only), a source made by fseq_create_without_identity_columns (its identity state would have to be carried along;
  * the other way round works: a context made here may be the source of that call, which knows nothing of the held-out rows and
- * makes a plain context).  FSEQ_E_ARG: no alignment resident.  A failed allocation returns FSEQ_E_OOM with the sizes, leaves
+ * makes a plain context, or of fseq_create_without_identity_columns_held, which carries them along).  FSEQ_E_ARG: no alignment resident.  A failed allocation returns FSEQ_E_OOM with the sizes, leaves
  * nothing behind, *out NULL and src as it was.  The new context takes no other input (every input setter returns FSEQ_E_ARG, as
  * on a context made by fseq_create_without_identity_columns); fseq_set_segment_length is allowed.  summary may be NULL. */
 int  fseq_create_without_rows(fseq_ctx *src, uint32_t const *held_rows, uint32_t n_held, fseq_params const *params, fseq_ctx **out,
@@ -474,6 +474,40 @@ int  fseq_get_held_out(fseq_ctx *ctx, uint32_t *kept_rows /* [kept] or NULL */, 
  * fseq_debug_match_split serve it as they do after fseq_match_rows. */
 int  fseq_match_held_out(fseq_ctx *ctx, uint32_t const *permutations, uint8_t const *const *founders, uint32_t K,
                          uint64_t min_segment_length, fseq_match_summary *out);
+
+/* ---- query rows matched against the RESTORED founders: leave-rows-out validation of a reconstruction made with the
+ * identity columns removed ----
+ * replaces: match-sequences-to-founders (match_founder_sequences.cc:108-259) run on the full-length query sequences and the
+ * file fseq_write_founders_restored writes: the report is byte for byte the tool's, lb and rb in SOURCE co-ordinates.  A match
+ * in reduced co-ordinates cannot give it: a column is an identity column among the rows of the reconstruction only, and a query
+ * that differs from row 0 there -- an EXCEPTION cell -- carries a byte no restored founder has: an uncovered cell that closes two
+ * pieces.  The walk is fseq_match_founders_restored's over the kept columns, merged with every row's own ascending list of
+ * exception columns (csrc/fseq_match.hpp, csrc/fseq_exceptions.hpp); it is not split along the columns.
+ * Founders are given by permutations only (K raw full-length rows need not agree with row 0 in the identity columns).
+ * Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+/* fseq_create_without_identity_columns for a source made by fseq_create_without_rows (FSEQ_E_ARG on any other source) that
+ * carries the held-out rows along.  The alignment, the identity state and every result of the new context are those of
+ * fseq_create_without_identity_columns(src, ...), bit for bit; it also holds the held-out rows' KEPT columns, the two row maps
+ * (fseq_get_held_out answers on it) and the held-out rows' exception cells.  fseq_match_held_out on it is the match in reduced
+ * co-ordinates, as fseq_match_founders is on a reduced context; fseq_set_segment_length is allowed (nothing carried depends on
+ * the segment length).  Refusals and the out-of-memory contract as the plain call: nothing is left behind, *out is NULL and src
+ * is as it was.  ms_device does not cover the held-out rows' part. */
+int  fseq_create_without_identity_columns_held(fseq_ctx *src, fseq_params const *params, fseq_ctx **out, fseq_identity_summary *summary);
+/* On a context made by the call above, after a long-path run: its held-out rows, full length, against the restored founders
+ * of these permutations.  fseq_match_piece::row indexes the hold-out list.  Nothing is uploaded.  Refusals as
+ * fseq_match_founders_restored, each before a device is touched, the context and its last match left as they were; FSEQ_E_ARG on
+ * a context of another kind.  The result replaces the context's last match: fseq_get_match and fseq_write_match serve it. */
+int  fseq_match_held_out_restored(fseq_ctx *ctx, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out);
+/* ... rows from the host, on a context made by either identity-column create call: rows[q] points at the SOURCE-n raw bytes of
+ * query q.  They go up in column chunks through a staging of at most 64 MiB, every byte once; the kept columns are held packed
+ * as fseq_match_rows holds its queries, the others are compared with row 0's byte.  A byte outside the alphabet is an uncovered
+ * cell in either kind of column.  FSEQ_E_ARG also for rows == NULL, a NULL row and n_rows == 0. */
+int  fseq_match_rows_restored(fseq_ctx *ctx, uint32_t const *permutations, uint8_t const *const *rows, uint32_t n_rows,
+                              uint64_t min_segment_length, fseq_match_summary *out);
+/* The exception cells of the last match, where it was made by one of the two calls above (FSEQ_E_ARG otherwise): offsets
+ * [rows + 1], row r's cells are columns[offsets[r] .. offsets[r + 1]), source columns in ascending order; *total = offsets[rows].
+ * These are the query rows' private variants in the reconstruction's identity columns.  Any pointer may be NULL. */
+int  fseq_get_match_exceptions(fseq_ctx *ctx, uint64_t *offsets, uint32_t *columns, uint64_t *total);
 
 int  fseq_get_timings(fseq_ctx const *ctx, fseq_timings *out);
 

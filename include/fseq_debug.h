@@ -189,7 +189,9 @@ int  fseq_debug_relump_lists(int device, uint64_t k0, uint32_t ncols, uint32_t s
  * them were flagged by the check and walked again unsplit, and the rows that did not stand (head[g] != tail[g - 1] for some g).
  * FSEQ_MATCH_SPLIT=g (1..4,096) and FSEQ_MATCH_OVERLAP=columns force the shape for fseq_match_rows and, with FSEQ_MATCH_SPLIT
  * set, for fseq_match_founders and fseq_match_founder_rows, which walk unsplit otherwise (fseq_debug_set_tuning takes both at any
- * time: nothing of a run depends on them).  FSEQ_E_ARG before a match. */
+ * time: nothing of a run depends on them; so it does FSEQ_MATCH_STAGE_BYTES=bytes, the most a staged chunk of
+ * fseq_match_rows_restored's query rows takes -- 64 MiB by itself, at least 64 columns).  The restored walks are unsplit and
+ * report one segment.  FSEQ_E_ARG before a match. */
 typedef struct fseq_match_split_info {
 	uint32_t segments, row_groups, flagged_groups, reserved;
 	uint64_t overlap, rows_not_standing;
