@@ -996,7 +996,7 @@ class SegmentationContext:
 
     def match_split(self):
         """How the last match walked (fseq_debug_match_split): dict(segments, overlap, row_groups, flagged_groups,
-        rows_not_standing)."""
+        rows_not_standing).  After a restored match the segments and the overlap count kept columns."""
         info = MatchSplitInfo()
         self._check(self.L.fseq_debug_match_split(self.h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in MatchSplitInfo._fields_ if k != "reserved"}
@@ -1130,7 +1130,8 @@ class SegmentationContext:
     def match_founders_restored(self, permutations, min_segment_length=0):
         """... the source's full-length rows matched against the founders write_founders_restored would write
         (fseq_match_founders_restored): the summary dict of match_founders, pieces in the source's co-ordinates;
-        match_pieces() and write_match() then serve this result."""
+        match_pieces() and write_match() then serve this result.  Unsplit unless FSEQ_MATCH_SPLIT is set (set_tuning); the
+        segments and FSEQ_MATCH_OVERLAP then count kept columns, and match_split() tells how the walk went."""
         perm = np.ascontiguousarray(permutations, dtype=np.uint32)
         sm = MatchSummary()
         self._check(self.L.fseq_match_founders_restored(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
@@ -1142,7 +1143,9 @@ class SegmentationContext:
         """On a context made by without_identity_columns(keep_held_out=True): the full-length held-out rows matched against the
         founders write_founders_restored would write (fseq_match_held_out_restored).  The summary dict of match_founders; the
         pieces are in the source's co-ordinates, their `row` indexes held_out()[1]; match_pieces(), write_match() and
-        match_exceptions() serve the result."""
+        match_exceptions() serve the result.  The walk is split along the kept columns, by itself as match_rows' is along the
+        columns (one segment under 32,768 kept columns) or as FSEQ_MATCH_SPLIT / FSEQ_MATCH_OVERLAP say, both in kept columns;
+        the result is the unsplit walk's either way, and match_split() tells how the walk went."""
         perm = np.ascontiguousarray(permutations, dtype=np.uint32)
         sm = MatchSummary()
         self._check(self.L.fseq_match_held_out_restored(self.h, perm.ctypes.data, int(min_segment_length), C.byref(sm)))
@@ -1151,7 +1154,8 @@ class SegmentationContext:
 
     def match_rows_restored(self, queries, permutations, min_segment_length=0):
         """On a context made by without_identity_columns(): queries, a C-contiguous uint8 array [n_rows, source_n] of raw
-        bytes (or a list of bytes objects of that length), matched against the restored founders (fseq_match_rows_restored)."""
+        bytes (or a list of bytes objects of that length), matched against the restored founders (fseq_match_rows_restored).
+        Split along the kept columns as match_held_out_restored is."""
         q = queries
         if not isinstance(q, np.ndarray):
             q = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in q], dtype=np.uint8).reshape(len(q), -1)

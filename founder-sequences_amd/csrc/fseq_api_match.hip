@@ -107,17 +107,17 @@ int run_match(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_sum
 	return FSEQ_OK;
 }
 
-template <bool WRITE>
-hipError_t launch_split(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &A, dim3 grid)
+template <bool WRITE, bool RST, bool EXC>
+hipError_t launch_split_as(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &A, dim3 grid)
 {
 	void (*k)(MatchSplitArgs) = nullptr;
 	switch (s.WR)
 	{
-		case 1: k = k_match_walk_split<1, WRITE>; break;
-		case 2: k = k_match_walk_split<2, WRITE>; break;
-		case 4: k = k_match_walk_split<4, WRITE>; break;
-		case 8: k = k_match_walk_split<8, WRITE>; break;
-		default: k = k_match_walk_split<0, WRITE>; break;
+		case 1: k = k_match_walk_split<1, WRITE, RST, EXC>; break;
+		case 2: k = k_match_walk_split<2, WRITE, RST, EXC>; break;
+		case 4: k = k_match_walk_split<4, WRITE, RST, EXC>; break;
+		case 8: k = k_match_walk_split<8, WRITE, RST, EXC>; break;
+		default: k = k_match_walk_split<0, WRITE, RST, EXC>; break;
 	}
 	hipError_t const e = allow_lds(k, s.lds);
 	if (e != hipSuccess) return e;
@@ -125,11 +125,22 @@ hipError_t launch_split(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &
 	return hipGetLastError();
 }
 
+// A.w.kept / A.w.exc_off set: the restored forms, as launch_walk
+template <bool WRITE>
+hipError_t launch_split(fseq_ctx *c, MatchShape const &s, MatchSplitArgs const &A, dim3 grid)
+{
+	if (!A.w.kept) return launch_split_as<WRITE, false, false>(c, s, A, grid);
+	return A.w.exc_off ? launch_split_as<WRITE, true, true>(c, s, A, grid) : launch_split_as<WRITE, true, false>(c, s, A, grid);
+}
+
 // run_match with the columns split into plan.G segments (csrc/fseq_match.hpp): counting walk over (row groups x G), the check,
 // the counting walk of the flagged groups unsplit, the scan per (row, g); then both writing walks.  No launch depends on a
 // count the host has not read: the fall-back launches cover every group and the workgroups beyond the list return at once.
 // G = 1 is the unsplit walk through the same kernel, without the check.  ms_device as run_match.
-int run_match_split(fseq_ctx *c, MatchShape const &s, MatchRows const &R, MatchSplitPlan const &plan, uint64_t min_len, fseq_match_summary *out)
+// restored: as run_match; the plan's segments and overlap are then counted in the context's (kept) columns, and head / tail
+// hold source positions.  X: restored query rows' exception cells
+int run_match_split(fseq_ctx *c, MatchShape const &s, MatchRows const &R, MatchSplitPlan const &plan, uint64_t min_len, fseq_match_summary *out,
+                    bool restored = false, MatchExceptions const *X = nullptr)
 {
 	auto &mt = c->match;
 	hipStream_t st = c->stream;
@@ -143,6 +154,8 @@ int run_match_split(fseq_ctx *c, MatchShape const &s, MatchRows const &R, MatchS
 	A.w.msa = R.cols; A.w.ld = R.ld; A.w.m = m; A.w.n = c->p.n; A.w.bsh = R.bsh; A.w.sigma = c->sigma;
 	A.w.fcols = mt.fcols; A.w.K = s.K; A.w.Kp = s.Kp; A.w.W = s.W; A.w.Wk = s.Wk; A.w.TC = s.TC; A.w.min_len = min_len;
 	A.w.cnt = mt.cnt; A.w.off = mt.off;
+	if (restored) { A.w.kept = c->idn.kept; A.w.n_src = c->idn.n_src; }
+	if (restored && X) { A.w.exc_off = X->off; A.w.exc_cols = X->cols; }
 	A.G = G; A.GS = G; A.overlap = plan.overlap; A.head = d_head; A.tail = d_tail;
 	MatchSplitArgs F = A;                                          // the fall-back: one segment, into slot 0 of the G
 	F.G = 1; F.list = d_list; F.nlist = d_info;
@@ -192,12 +205,13 @@ int run_match_split(fseq_ctx *c, MatchShape const &s, MatchRows const &R, MatchS
 	return FSEQ_OK;
 }
 
-// FSEQ_MATCH_SPLIT set: fseq_match_founders and fseq_match_founder_rows walk the alignment's rows split as it says
-int run_match_as_tuned(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out)
+// FSEQ_MATCH_SPLIT set: fseq_match_founders, fseq_match_founder_rows and fseq_match_founders_restored walk the alignment's rows
+// split as it says
+int run_match_as_tuned(fseq_ctx *c, MatchShape const &s, uint64_t min_len, fseq_match_summary *out, bool restored = false)
 {
-	if (!c->tune.match_split) return run_match(c, s, min_len, out);
+	if (!c->tune.match_split) return run_match(c, s, min_len, out, restored);
 	MatchSplitPlan const plan = match_split_plan(c->p.n, c->p.m, 0, (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, false);
-	return run_match_split(c, s, MatchRows{c->d_msa, c->ld, c->p.m, c->bsh}, plan, min_len, out);
+	return run_match_split(c, s, MatchRows{c->d_msa, c->ld, c->p.m, c->bsh}, plan, min_len, out, restored);
 }
 
 int begin_match(fseq_ctx *c, MatchShape const &s)
@@ -303,7 +317,7 @@ int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_s
 	MatchShape const s = match_shape((uint32_t) X, c->sigma, c->bsh);
 	FounderTemps T(c);
 	if ((rc = begin_match(c, s)) || (rc = cols_from_permutations(c, permutations, s, T))) return rc;
-	return restored ? run_match(c, s, min_segment_length, out, true) : run_match_as_tuned(c, s, min_segment_length, out);
+	return run_match_as_tuned(c, s, min_segment_length, out, restored);
 }
 
 // the queries of fseq_match_rows onto the device: column chunks of raw bytes through a bounded temporary, packed by
@@ -390,13 +404,20 @@ int upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_
 	return exc_lists_from_bits(c, st, d_bits, nw, n_rows, mt.exc_off, mt.exc_cols, &mt.exc_total);
 }
 
-// fseq_match_held_out_restored / fseq_match_rows_restored behind their refusals: the unsplit restored walk over the query rows R
+// fseq_match_held_out_restored / fseq_match_rows_restored behind their refusals: the restored walk over the query rows R, split
+// along the kept columns as the knobs say or, without them, as fseq_match_rows chooses by itself; where that choice is one
+// segment, the unsplit kernel walks
 int match_queries_restored(fseq_ctx *c, uint32_t const *permutations, MatchShape const &s, MatchRows const &R, MatchExceptions const &X, int from,
                            uint64_t min_segment_length, fseq_match_summary *out)
 {
 	FounderTemps T(c);
 	int rc = cols_from_permutations(c, permutations, s, T);
-	if (rc || (rc = run_match(c, s, min_segment_length, out, true, &R, &X))) return rc;
+	if (rc) return rc;
+	int cus = 0;
+	(void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->p.device);
+	MatchSplitPlan const plan = match_split_plan(c->p.n, R.m, (uint32_t) std::max(cus, 1), (uint32_t) c->tune.match_split, (uint64_t) c->tune.match_overlap, true);
+	rc = (c->tune.match_split || plan.G > 1u) ? run_match_split(c, s, R, plan, min_segment_length, out, true, &X) : run_match(c, s, min_segment_length, out, true, &R, &X);
+	if (rc) return rc;
 	c->match.exc_from = from;
 	c->match.exc_rows = R.m;
 	return FSEQ_OK;

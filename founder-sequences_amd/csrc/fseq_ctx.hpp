@@ -139,8 +139,8 @@ struct Tuning {
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
-	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: fseq_match_rows chooses, the other entries walk unsplit)
-	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns a segment's cold walk starts in front of its range (by itself: 16,384)
+	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: the entries that take query rows choose, those over the alignment's rows walk unsplit)
+	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns (of a restored match: kept columns) a segment's cold walk starts in front of its range (by itself: 16,384)
 	int  match_stage = 0;                // FSEQ_MATCH_STAGE_BYTES: most bytes of a staged chunk of fseq_match_rows_restored's query rows (by itself: 64 MiB; tests: chunks of 64 columns)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.

@@ -35,7 +35,7 @@
 //       the ordinary column step with the empty set.  Every lane carries a cursor into its row's ascending list of exception
 //       columns (csrc/fseq_exceptions.hpp) and, before a kept column k, drains the exceptions below k: the gap step up to the
 //       exception, the column step there, then on from the column behind it.  A row without exceptions pays one compare a
-//       kept column.  The walk is unsplit, as the restored walk of the input rows is.
+//       kept column.
 //
 //   k_match_pack_rows   rows that are not the alignment's (fseq_match_rows): a staged chunk of raw query bytes, one row after
 //       the other, is sent through the context's code table, transposed and packed like the alignment, at the narrowest of
@@ -52,10 +52,18 @@
 //       again by the same kernel with one segment (G = 1 of the split kernel IS the unsplit walk) over the list of them; their
 //       workgroups in the split writing pass return at once.  The counts are [m x G]; k_match_scan_split gives the offsets
 //       per (row, g), so the pieces stay ordered by row, then lb.
+//   k_match_walk_split<WR, WRITE, true> / <WR, WRITE, true, true>   the restored forms split the same way, the segments counted
+//       in kept columns.  After a close at SOURCE position p the state is lb = p and a live set that is a function of p and the
+//       row alone: set[p][code] at a kept column, the empty set at an exception column, all founders at any other identity
+//       column (the close in the gap step behind an uncovered cell, every forced min_len close in a gap).  Segment g owns the
+//       source positions [kept[c_g], kept[c_{g+1}]) (the first from 0, the last up to n_src), starts cold at kept[s_g] and walks
+//       on behind its last kept column up to the next segment's first position; head and tail are source positions, and the
+//       check, the fall-back and the scan are the plain form's.
 //
 // The walk is sequential along the columns: with m rows only ceil(m / 64) waves are in flight, and the time is a chain over n
-// columns, not throughput.  fseq_match_founders / fseq_match_founder_rows walk unsplit unless FSEQ_MATCH_SPLIT is set;
-// fseq_match_rows chooses the split by itself (match_split_plan).
+// columns, not throughput.  fseq_match_founders / fseq_match_founder_rows / fseq_match_founders_restored walk unsplit unless
+// FSEQ_MATCH_SPLIT is set; fseq_match_rows, fseq_match_held_out, fseq_match_held_out_restored and fseq_match_rows_restored choose
+// the split by themselves (match_split_plan; the restored two over the kept columns).
 #pragma once
 
 #include "../../include/fseq.h"
@@ -462,6 +470,8 @@ constexpr uint32_t MT_SPLIT_MAX = 4096;             // most segments (FSEQ_MATCH
 // MT_SPLIT_OVERLAP columns.  From one measurement (profiles/match_split_C3_overlap4096.txt): rows of C3's population held out of the
 // reconstruction stand at an overlap of 16,384 columns and none does at 4,096, the value this started from; a segment of one
 // overlap (G = 61 on C3's 1,000,000 columns) was the fastest shape measured.  No other input has been measured.
+// The restored query entries plan with the same constants over the KEPT columns (profiles/match_restored_split_C3.txt: C3 with
+// 400,293 kept columns, held-out rows stand at 16,384 kept columns and 18 of 256 do not at 4,096).
 constexpr uint32_t MT_SPLIT_WG_PER_CU = 2;
 constexpr uint64_t MT_SPLIT_OVERLAP = 16384;
 constexpr uint64_t MT_SPLIT_MIN_OVERLAPS = 1;
@@ -502,11 +512,19 @@ struct MatchSplitArgs {
 	uint32_t const *list, *nlist;                    // the fall-back launch: the flagged groups and their number (or nullptr)
 };
 
-// LDS as k_match_walk's plain form.  grid: (row groups, G), or -- A.list -- (row groups) of which the first *A.nlist work
-template <uint32_t WR, bool WRITE>
+// LDS as k_match_walk's.  grid: (row groups, G), or -- A.list -- (row groups) of which the first *A.nlist work.
+// RST / EXC: the restored forms, as k_match_walk has them.  The segments are counted in KEPT columns (n = n_kept); segment g owns
+// the source positions [P_g, P_{g+1}), P_0 = 0, P_g = kept[c_g], P_G = n_src, and a close at source position p is counted and
+// stored by the segment that owns p.  Segment g >= 1 starts cold at kept[s_g] (the exception cursor at the row's first exception
+// not below it, by binary search); behind its last kept column it drains and gap-steps up to P_{g+1}.  `mine` turns true on
+// reaching kept index c_g, after the drain and the gap step in front of it: a gap lies strictly between two kept or exception
+// columns, so it never straddles a P_g and the counting pass keeps its closed form.  head and tail are source positions.
+template <uint32_t WR, bool WRITE, bool RST = false, bool EXC = false>
 static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs const S)
 {
+	static_assert(RST || !EXC, "exception columns are identity columns of a restored walk");
 	extern __shared__ uint4 mt_smem[];
+	__shared__ uint32_t mt_pos[RST ? MT_TILE_MAX : 1];
 	MatchWalkArgs const &A = S.w;
 	uint32_t grp = blockIdx.x;
 	uint32_t const g = S.list ? 0u : blockIdx.y;
@@ -563,8 +581,119 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs
 		++npieces;
 	};
 
+	// RST: the state and the steps of k_match_walk's restored form, with the owner rule: every close sets `last`, and it is
+	// counted and stored only where `mine`
+	bool mine = s_lo == c_lo;                                            // (segment 0, and the fall-back's one segment)
+	uint64_t src_next = 0, p_hi = 0;
+	uint64_t e_at = 0, e_end = 0;
+	uint32_t e_col = MT_NO_EXC;
+	if (RST)
+	{
+		if (g) { lb = A.kept[s_lo]; last = head = (uint32_t) lb; }
+		src_next = lb;
+		p_hi = c_hi == n ? A.n_src : (uint64_t) A.kept[c_hi];
+		if (EXC && active)
+		{
+			e_at = A.exc_off[row];
+			e_end = A.exc_off[row + 1u];
+			if (g)
+			{
+				// the row's first exception at or behind the cold start (none is at a kept column)
+				uint64_t hi = e_end;
+				while (e_at < hi) { uint64_t const mid = e_at + (hi - e_at) / 2u; if (A.exc_cols[mid] < (uint32_t) lb) e_at = mid + 1u; else hi = mid; }
+			}
+			if (e_at < e_end) e_col = A.exc_cols[e_at];
+		}
+	}
+	auto gap_step = [&](uint64_t g_lo, uint64_t g_hi) {
+		if (g_lo >= g_hi) return;
+		if (!alive)
+		{
+			if (mine)
+			{
+				if (min_len != 0 && g_lo - lb < min_len) ++nshort;
+				emit(g_lo);
+			}
+			lb = g_lo;
+			last = (uint32_t) g_lo;
+			all_founders();
+			alive = true;
+		}
+		if (min_len != 0)
+		{
+			// closes at lb + i * min_len < g_hi, i = 1 ..: (g_hi - lb - 1) / min_len of them (lb < g_hi < 2^32)
+			uint32_t const room = (uint32_t) (g_hi - lb - 1u);
+			uint32_t const closes = min_len > room ? 0u : room / (uint32_t) min_len;
+			if (closes)
+			{
+				if (WRITE && mine)
+				{
+					emit(lb + min_len);
+					lb += min_len;
+					all_founders();
+					for (uint32_t i = 1; i < closes; ++i) { emit(lb + min_len); lb += min_len; }
+				}
+				else
+				{
+					if (mine) npieces += closes;
+					lb += (uint64_t) closes * min_len;
+					all_founders();
+				}
+				last = (uint32_t) lb;
+			}
+		}
+	};
+	auto col_step = [&](uint64_t k, uint32_t const *const M) {
+		bool recheck = false;
+		uint32_t any = 0;
+		uint32_t nv[WR ? WR : 1];
+		if (min_len != 0 && min_len <= k - lb) recheck = true;
+		else
+		{
+			if (WR)
+			{
+				for (uint32_t i = 0; i < live.words(); ++i) { nv[i] = live.get(i) & M[i]; any |= nv[i]; }
+			}
+			else
+			{
+				for (uint32_t i = 0; i < live.words() && !any; ++i) any = live.get(i) & M[i];
+			}
+			if (!any) { if (min_len != 0 && mine) ++nshort; recheck = true; }
+		}
+		if (recheck)
+		{
+			if (mine) emit(k);
+			lb = k;
+			last = (uint32_t) k;
+			any = 0;
+			for (uint32_t i = 0; i < live.words(); ++i) { uint32_t const v = M[i]; live.set(i, v); any |= v; }
+			if (!any && mine) ++nunc;
+		}
+		else if (WR)
+		{
+			for (uint32_t i = 0; i < live.words(); ++i) live.set(i, nv[i]);
+		}
+		else
+		{
+			for (uint32_t i = 0; i < live.words(); ++i) live.set(i, live.get(i) & M[i]);
+		}
+		alive = any != 0;
+	};
+	auto drain = [&](uint64_t upto) {
+		while (e_col < upto)
+		{
+			gap_step(src_next, e_col);
+			col_step(e_col, empty_set);
+			src_next = (uint64_t) e_col + 1u;
+			++e_at;
+			e_col = e_at < e_end ? A.exc_cols[e_at] : MT_NO_EXC;
+		}
+	};
+
 	uint4 rf[MT_PREFETCH], rs[MT_PREFETCH];
+	uint32_t rp = 0;
 	auto prefetch = [&](uint64_t c0, uint32_t tc) {
+		if (RST) rp = tid < tc ? A.kept[c0 + tid] : 0u;
 		uint32_t const nf = tc * Kp / 16u, ns = tc * cpc;
 		uint4 const *const fsrc = reinterpret_cast<uint4 const *>(A.fcols + c0 * Kp);
 #pragma unroll
@@ -591,6 +720,7 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs
 				if (q < nf) reinterpret_cast<uint4 *>(fst)[q] = rf[j];
 				if (q < ns) reinterpret_cast<uint4 *>(syms)[q] = rs[j];
 			}
+			if (RST && tid < MT_TILE_MAX) mt_pos[tid] = rp;
 			for (uint32_t i = tid; i < tc * sigma * Wk; i += MT_T) sets[i] = 0u;
 		}
 		__syncthreads();
@@ -612,11 +742,25 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs
 			}
 		}
 		__syncthreads();
-		if (active)
+		if (RST)
+		{
+			if (active)
+				for (uint32_t j = 0; j < tc; ++j)
+				{
+					uint64_t const k = mt_pos[j];
+					if (EXC) drain(k);
+					gap_step(src_next, k);
+					src_next = k + 1u;
+					if (c0 + j == c_lo) { head = last; mine = true; }        // (uniform: what closed in front of P_g belongs to the segment before)
+					uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
+					col_step(k, code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set);
+				}
+		}
+		else if (active)
 			for (uint32_t j = 0; j < tc; ++j)
 			{
 				uint64_t const k = c0 + j;
-				bool const mine = k >= c_lo;                                 // (uniform: the closes in front of c_g belong to the segment before)
+				mine = k >= c_lo;                                            // (uniform: the closes in front of c_g belong to the segment before)
 				if (k == c_lo) head = last;
 				uint32_t const code = (syms[j * rowbytes + (tid >> bsh)] >> ((tid & smask) * bits)) & cmask;
 				uint32_t const *const M = code < sigma ? sets + ((size_t) j * sigma + code) * Wk : empty_set;
@@ -659,7 +803,13 @@ static __global__ __launch_bounds__(MT_T) void k_match_walk_split(MatchSplitArgs
 	}
 	if (active)
 	{
-		if (c_hi == n && alive) emit(n);
+		if (RST)
+		{
+			// the exceptions and the identity columns up to the next segment's first position (the last segment: the source's end)
+			if (EXC) drain(p_hi);
+			gap_step(src_next, p_hi);
+		}
+		if (c_hi == n && alive) emit(RST ? A.n_src : n);
 		if (!WRITE)
 		{
 			A.cnt[slot] = npieces; A.cnt[total + slot] = nunc; A.cnt[2u * total + slot] = nshort;

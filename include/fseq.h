@@ -430,8 +430,9 @@ int  fseq_write_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, c
  * identity column follows, and with min_segment_length != 0 a piece closes once it has that many source columns, inside a run
  * of identity columns too.  Refusals as fseq_match_founders (before a run, short-path result, segments that do not tile the
  * columns: FSEQ_E_ARG; more than 2,048 founders, a source of 2^32 - 1 columns or more: FSEQ_E_UNSUPPORTED).  The result
- * replaces the context's last match: fseq_get_match and fseq_write_match serve it unchanged.  Detected by symbol, as the
- * entry points above. */
+ * replaces the context's last match: fseq_get_match and fseq_write_match serve it unchanged.  The walk is unsplit unless
+ * FSEQ_MATCH_SPLIT is set, as fseq_match_founders'; the segments and FSEQ_MATCH_OVERLAP are then counted in kept columns.
+ * Detected by symbol, as the entry points above. */
 int  fseq_match_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, uint64_t min_segment_length, fseq_match_summary *out);
 
 /* ---- rows held out of a resident alignment and matched on the device ----
@@ -482,7 +483,10 @@ int  fseq_match_held_out(fseq_ctx *ctx, uint32_t const *permutations, uint8_t co
  * in reduced co-ordinates cannot give it: a column is an identity column among the rows of the reconstruction only, and a query
  * that differs from row 0 there -- an EXCEPTION cell -- carries a byte no restored founder has: an uncovered cell that closes two
  * pieces.  The walk is fseq_match_founders_restored's over the kept columns, merged with every row's own ascending list of
- * exception columns (csrc/fseq_match.hpp, csrc/fseq_exceptions.hpp); it is not split along the columns.
+ * exception columns (csrc/fseq_match.hpp, csrc/fseq_exceptions.hpp).  It is split along the KEPT columns as
+ * fseq_match_rows' walk is split along the columns: by itself where the context has 32,768 kept columns or more, or as
+ * FSEQ_MATCH_SPLIT / FSEQ_MATCH_OVERLAP say, both counted in kept columns; the result is the unsplit walk's in every case and
+ * fseq_debug_match_split reports how it walked.
  * Founders are given by permutations only (K raw full-length rows need not agree with row 0 in the identity columns).
  * Detected by symbol; FSEQ_ABI_VERSION stays 5. */
 /* fseq_create_without_identity_columns for a source made by fseq_create_without_rows (FSEQ_E_ARG on any other source) that

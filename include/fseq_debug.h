@@ -187,11 +187,14 @@ int  fseq_debug_relump_lists(int device, uint64_t k0, uint32_t ncols, uint32_t s
 /* How the last match of the context walked (csrc/fseq_match.hpp, k_match_walk_split): the segments G the columns were split
  * into (1: unsplit) and the overlap in use (clamped to the longest segment; 0 where G = 1), the groups of 256 rows, how many of
  * them were flagged by the check and walked again unsplit, and the rows that did not stand (head[g] != tail[g - 1] for some g).
- * FSEQ_MATCH_SPLIT=g (1..4,096) and FSEQ_MATCH_OVERLAP=columns force the shape for fseq_match_rows and, with FSEQ_MATCH_SPLIT
- * set, for fseq_match_founders and fseq_match_founder_rows, which walk unsplit otherwise (fseq_debug_set_tuning takes both at any
- * time: nothing of a run depends on them; so it does FSEQ_MATCH_STAGE_BYTES=bytes, the most a staged chunk of
- * fseq_match_rows_restored's query rows takes -- 64 MiB by itself, at least 64 columns).  The restored walks are unsplit and
- * report one segment.  FSEQ_E_ARG before a match. */
+ * FSEQ_MATCH_SPLIT=g (1..4,096) and FSEQ_MATCH_OVERLAP=columns force the shape for the entries that take query rows --
+ * fseq_match_rows, fseq_match_held_out, fseq_match_held_out_restored, fseq_match_rows_restored, which otherwise choose it by
+ * themselves -- and, with FSEQ_MATCH_SPLIT set, for fseq_match_founders, fseq_match_founder_rows and fseq_match_founders_restored,
+ * which walk unsplit otherwise (fseq_debug_set_tuning takes both at any time: nothing of a run depends on them; so it does
+ * FSEQ_MATCH_STAGE_BYTES=bytes, the most a staged chunk of fseq_match_rows_restored's query rows takes -- 64 MiB by itself, at
+ * least 64 columns).  For the three restored entries the segments and the overlap, forced and reported, are counted in the
+ * context's columns, the kept ones of the source; a restored match of query rows that chooses one segment by itself (fewer than
+ * 32,768 kept columns) walks through the unsplit kernel and reports one segment.  FSEQ_E_ARG before a match. */
 typedef struct fseq_match_split_info {
 	uint32_t segments, row_groups, flagged_groups, reserved;
 	uint64_t overlap, rows_not_standing;
