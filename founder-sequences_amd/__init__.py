@@ -132,13 +132,15 @@ EXPORTS = [
     "fseq_create_without_rows", "fseq_get_held_out", "fseq_match_held_out", "fseq_debug_held_out_columns", "fseq_debug_row_split_plan",
     "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
     "fseq_create_without_identity_columns_held", "fseq_match_held_out_restored", "fseq_match_rows_restored", "fseq_get_match_exceptions",
+    "fseq_get_segments_restored", "fseq_write_segments_restored", "fseq_debug_restored_bounds",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
-                 "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists"]
+                 "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
+                 "fseq_debug_restored_bounds"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -272,6 +274,9 @@ def load_library():
     L.fseq_debug_row_split_plan.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.fseq_debug_dp_lists_check.argtypes = [C.c_uint32, u64, u64, C.c_uint32, vp, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_dp_on_lists.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(DpListsInfo)]
+    L.fseq_get_segments_restored.argtypes = [vp, vp]
+    L.fseq_write_segments_restored.argtypes = [vp, C.c_int, C.c_char_p]
+    L.fseq_debug_restored_bounds.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp]
     _lib = L
     return L
 
@@ -481,6 +486,27 @@ def row_split_plan_host(m, bits, held):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return kept[:n_kept].copy(), base[:nw.value].copy(), keep[:nw.value].copy(), ns.value
+
+
+def restored_bounds_host(kept, n_src, lb, rb):
+    """The merged segments [lb[s], rb[s]) of an identity-reduced context, given in its kept columns, in the source's co-ordinates
+    (restored_segment_bounds, csrc/fseq_restored_bounds.hpp): (src_lb, src_rb), uint64 arrays.  kept: the source column of every
+    kept column; n_src: the source's columns.  FseqError(FSEQ_E_ARG) where kept does not ascend strictly or names a column not
+    below n_src, where the segments do not tile the kept columns, and for no segments.  No device is touched."""
+    L = load_library()
+    kept = np.ascontiguousarray(kept, dtype=np.uint64)
+    lb = np.ascontiguousarray(lb, dtype=np.uint64)
+    rb = np.ascontiguousarray(rb, dtype=np.uint64)
+    if kept.ndim != 1 or lb.ndim != 1 or rb.shape != lb.shape:
+        raise FseqError(FSEQ_E_ARG, "restored_bounds_host: one column per entry of kept, one segment per entry of lb and rb")
+    S = len(lb)
+    src_lb = np.zeros(max(1, S), dtype=np.uint64)
+    src_rb = np.zeros(max(1, S), dtype=np.uint64)
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    rc = L.fseq_debug_restored_bounds(ptr(kept), len(kept), int(n_src), ptr(lb), ptr(rb), S, src_lb.ctypes.data, src_rb.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return src_lb[:S].copy(), src_rb[:S].copy()
 
 
 def relump_lists(ent, hdr, k0, L_from, L_to, device=0):
@@ -920,7 +946,7 @@ class SegmentationContext:
         self._check(self.L.fseq_write_segments_device(self.h, joining, path.encode() if path else None))
 
     def segments_file_stats(self):
-        """The last file write_segments_device wrote: {batches, bytes, longest_line, lines} (header included, a line with its newline)."""
+        """The last file write_segments_device or write_segments_restored wrote: {batches, bytes, longest_line, lines} (header included, a line with its newline)."""
         v = [C.c_uint64() for _ in range(4)]
         self._check(self.L.fseq_debug_segments_file(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("batches", "bytes", "longest_line", "lines"), (x.value for x in v)))
@@ -1126,6 +1152,21 @@ class SegmentationContext:
         """... --output-founders with the identity columns put back from input row 0 (lines of the source's length)."""
         perm = np.ascontiguousarray(permutations, dtype=np.uint32)
         self._check(self.L.fseq_write_founders_restored(self.h, perm.ctypes.data, path.encode() if path else None))
+
+    def segments_restored(self):
+        """... reduced_traceback() with lb / rb in the source's co-ordinates (fseq_get_segments_restored): segment s covers the
+        source columns from its first kept column up to the next segment's first kept column, the first from 0, the last to the
+        source's n."""
+        S = self.result.segment_count if self.result is not None else 0      # (before a run: the library refuses)
+        out = np.zeros(max(1, S), dtype=SEGMENT_DTYPE)
+        self._check(self.L.fseq_get_segments_restored(self.h, out.ctypes.data))
+        return out[:S]
+
+    def write_segments_restored(self, joining, path):
+        """... --output-segments in the source's co-ordinates (fseq_write_segments_restored): write_segments_device's file with
+        the bounds of segments_restored() and substrings of the source's length, input row 0's byte at the identity columns.
+        segments_file_stats() then reports this file."""
+        self._check(self.L.fseq_write_segments_restored(self.h, joining, path.encode() if path else None))
 
     def match_founders_restored(self, permutations, min_segment_length=0):
         """... the source's full-length rows matched against the founders write_founders_restored would write

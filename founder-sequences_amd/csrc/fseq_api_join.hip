@@ -12,6 +12,7 @@
 #include "fseq_joinbip.hpp"
 #include "fseq_joinbipw.hpp"
 #include "fseq_segfile.hpp"
+#include "fseq_restored_bounds.hpp"
 
 using namespace fseq;
 
@@ -212,9 +213,39 @@ static char const SEGFILE_HEADER_BIP[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE\tSE
 static char const SEGFILE_HEADER_COPIES[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE_NUMBER\tCOPY_NUMBER\tSUBSEQUENCE\n";
 static constexpr uint64_t SEGFILE_BATCH_BYTES = 256ull << 20;      // (what fseq_write_founders_device takes a batch)
 
+// What the restored form of the writer takes on top: the segments in the source's co-ordinates (host, [S] each) and the identity
+// state of the context (device).  nullptr: the reduced form.
+struct SegFileRestored {
+	uint64_t const *src_lb, *src_rb;
+	uint32_t const *kept;
+	uint8_t const *mask, *ref;
+	uint64_t n_src;
+};
+
+// The merged segments of an identity-reduced context in the source's co-ordinates (restored_segment_bounds on the kept columns,
+// which are copied to the host: 4 bytes a kept column).  Refuses what the pure function refuses.
+static int restored_bounds_of(fseq_ctx *c, std::vector<uint64_t> &src_lb, std::vector<uint64_t> &src_rb)
+{
+	size_t const S = c->segments.size();
+	std::vector<uint32_t> kept;
+	std::vector<uint64_t> lb, rb;
+	try { kept.resize((size_t) c->p.n); lb.resize(S); rb.resize(S); src_lb.resize(S); src_rb.resize(S); }
+	catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "restored segments: the kept columns on the host"); }
+	(void) hipSetDevice(c->p.device);
+	HIP_TRY(c, hipMemcpy(kept.data(), c->idn.kept, kept.size() * 4, hipMemcpyDeviceToHost));
+	for (size_t s = 0; s < S; ++s) { lb[s] = c->segments[s].lb; rb[s] = c->segments[s].rb; }
+	if (char const *why = restored_segment_bounds(kept.data(), (uint64_t) kept.size(), c->idn.n_src, lb.data(), rb.data(), (uint64_t) S, src_lb.data(), src_rb.data()))
+	{
+		std::string const what = std::string("restored segments: ") + why;
+		return fail(c, FSEQ_E_UNSUPPORTED, what.c_str());
+	}
+	return FSEQ_OK;
+}
+
 // The lines of the segments file behind its header, from the device (fseq_segfile.hpp).  The file is opened once everything that
-// can refuse has passed: the class counts, the allocations of the tables.
-static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *path, char const *header)
+// can refuse has passed: the class counts, the allocations of the tables.  R: the bounds a line prints and the identity columns its
+// substring gains (fseq_write_segments_restored); nullptr: the context's own co-ordinates.
+static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *path, char const *header, SegFileRestored const *R)
 {
 	(void) hipSetDevice(c->p.device);
 	hipStream_t st = c->stream;
@@ -226,9 +257,10 @@ static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *
 	DevTemp<uint32_t> d_min(c), d_reprow(c), d_members(c);
 	DevTemp<uint2> d_rline(c);
 	DevTemp<uint8_t> d_pool(c), d_lut(c), d_out(c);
-	DevTemp<uint64_t> d_ppos(c), d_loff(c), d_segoff(c);
+	DevTemp<uint64_t> d_ppos(c), d_loff(c), d_segoff(c), d_srcb(c);
 	int rc;
 	if ((rc = T.alloc(S, m, X))) return rc;
+	if (R && (rc = d_srcb.alloc(2 * S))) return rc;
 	if (bip && ((rc = d_tpos.alloc(S * X)) || (rc = d_src.alloc(S * X)) || (rc = d_min.alloc(S * X)) || (rc = d_reprow.alloc(S * X)))) return rc;
 	if ((rc = d_ppos.alloc(S + 1)) || (rc = d_loff.alloc(S * X1)) || (rc = d_segoff.alloc(S + 1)) || (rc = d_lut.alloc(256))) return rc;
 	std::vector<uint32_t> count;
@@ -264,14 +296,15 @@ static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *
 		if ((rc = d_rline.alloc(S * X))) return rc;
 		HIP_TRY(c, hipMemcpy(d_rline, rline.data(), S * X * sizeof(uint2), hipMemcpyHostToDevice));
 	}
-	// the prefixes: write_segments_impl's "%zu\t%llu\t%llu\t%u\t"
+	// the prefixes: write_segments_impl's "%zu\t%llu\t%llu\t%u\t" (restored: with the source's bounds)
 	std::string pool;
 	std::vector<uint64_t> ppos(S + 1);
 	for (size_t s = 0; s < S; ++s)
 	{
 		char buf[96];
 		ppos[s] = pool.size();
-		int const len = snprintf(buf, sizeof(buf), "%zu\t%llu\t%llu\t%u\t", s, (unsigned long long) c->segments[s].lb, (unsigned long long) c->segments[s].rb, c->segments[s].segment_size);
+		uint64_t const plb = R ? R->src_lb[s] : c->segments[s].lb, prb = R ? R->src_rb[s] : c->segments[s].rb;
+		int const len = snprintf(buf, sizeof(buf), "%zu\t%llu\t%llu\t%u\t", s, (unsigned long long) plb, (unsigned long long) prb, c->segments[s].segment_size);
 		pool.append(buf, (size_t) len);
 	}
 	ppos[S] = pool.size();
@@ -279,17 +312,22 @@ static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *
 	e = hipMemcpyAsync(d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_ppos, ppos.data(), (S + 1) * 8, hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_lut, c->code_to_byte, 256, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess && R) e = hipMemcpyAsync(d_srcb, R->src_lb, S * 8, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess && R) e = hipMemcpyAsync(d_srcb + S, R->src_rb, S * 8, hipMemcpyHostToDevice, st);
 	size_t const lds_lines = segfile_lines_lds_bytes(X, bip), lds_members = segfile_members_lds_bytes(X), lds_write = segfile_write_lds_bytes(X, bip);
-	if (e == hipSuccess && bip) e = allow_lds(k_segfile_lines<true>, lds_lines);
+	if (e == hipSuccess && bip) e = R ? allow_lds(k_segfile_lines<true, true>, lds_lines) : allow_lds(k_segfile_lines<true>, lds_lines);
 	if (e == hipSuccess && bip) e = allow_lds(k_segfile_members, lds_members);
-	if (e == hipSuccess && bip) e = allow_lds(k_segfile_write<true>, lds_write);
+	if (e == hipSuccess && bip) e = R ? allow_lds(k_segfile_write<true, true>, lds_write) : allow_lds(k_segfile_write<true>, lds_write);
 	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "segments file preparation", e);
 	SegFileArgs A{};
 	A.seg_lb = T.d_lb; A.seg_rb = T.d_rb; A.pool = d_pool; A.ppos = d_ppos; A.count = T.d_count;
 	A.m = (uint32_t) m; A.X = X; A.S = (uint32_t) S;
 	A.of_row = T.d_of; A.tpos = d_tpos; A.src = d_src; A.reprow = d_reprow; A.rline = d_rline;
+	if (R) { A.src_lb = d_srcb; A.src_rb = d_srcb + S; A.kept = R->kept; A.mask = R->mask; A.ref = R->ref; A.n_src = R->n_src; }
 	// every line's length, scanned: inside the segments, then over them
-	if (bip) hipLaunchKernelGGL(k_segfile_lines<true>, dim3((uint32_t) S), dim3(SF_T), lds_lines, st, A, (uint64_t *) d_loff);
+	if (bip && R) hipLaunchKernelGGL((k_segfile_lines<true, true>), dim3((uint32_t) S), dim3(SF_T), lds_lines, st, A, (uint64_t *) d_loff);
+	else if (bip) hipLaunchKernelGGL(k_segfile_lines<true>, dim3((uint32_t) S), dim3(SF_T), lds_lines, st, A, (uint64_t *) d_loff);
+	else if (R) hipLaunchKernelGGL((k_segfile_lines<false, true>), dim3((uint32_t) S), dim3(SF_T), 0, st, A, (uint64_t *) d_loff);
 	else hipLaunchKernelGGL(k_segfile_lines<false>, dim3((uint32_t) S), dim3(SF_T), 0, st, A, (uint64_t *) d_loff);
 	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, d_loff, (uint32_t) S, X, d_segoff);
 	std::vector<uint64_t> loff, segoff(S + 1);
@@ -346,9 +384,16 @@ static int write_segments_device_lines(fseq_ctx *c, bool const bip, char const *
 		if (bip)
 		{
 			hipLaunchKernelGGL(k_segfile_members, dim3(nseg), dim3(SF_T), lds_members, st, A, (uint32_t const *) T.d_size, B.s0, (uint32_t *) d_members);
-			hipLaunchKernelGGL(k_segfile_write<true>, dim3(nseg), dim3(SF_T), lds_write, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
-			                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) d_members, (uint8_t *) d_out);
+			if (R)
+				hipLaunchKernelGGL((k_segfile_write<true, true>), dim3(nseg), dim3(SF_T), lds_write, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
+				                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) d_members, (uint8_t *) d_out);
+			else
+				hipLaunchKernelGGL(k_segfile_write<true>, dim3(nseg), dim3(SF_T), lds_write, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
+				                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) d_members, (uint8_t *) d_out);
 		}
+		else if (R)
+			hipLaunchKernelGGL((k_segfile_write<false, true>), dim3(nseg), dim3(SF_T), 0, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
+			                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) nullptr, (uint8_t *) d_out);
 		else
 			hipLaunchKernelGGL(k_segfile_write<false>, dim3(nseg), dim3(SF_T), 0, st, A, B, (uint8_t const *) c->d_msa, c->ld, c->bsh, (uint8_t const *) d_lut,
 			                   (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint32_t const *) nullptr, (uint8_t *) d_out);
@@ -728,13 +773,72 @@ int fseq_write_segments_device(fseq_ctx *c, int joining, char const *path)
 	if (bip && X > JBW_MAX_TEXTS) return fail(c, FSEQ_E_UNSUPPORTED, "bipartite-matching segments file from the device: more than 4,096 texts a segment (write it from host rows: fseq_write_segments)");
 	if (!bip && X > 0xFFFFu) return fail(c, FSEQ_E_UNSUPPORTED, "random-joining segments file from the device: more than 65,535 classes a segment (write it from host rows: fseq_write_segments)");
 	if (c->p.m > 0x7FFFFFFFull || c->segments.size() > 0x7FFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "segments file from the device: 2^31 rows or segments or more");
-	return write_segments_device_lines(c, bip, path, bip ? SEGFILE_HEADER_BIP : SEGFILE_HEADER_COPIES);
+	return write_segments_device_lines(c, bip, path, bip ? SEGFILE_HEADER_BIP : SEGFILE_HEADER_COPIES, nullptr);
+}
+
+// what the restored entries refuse of a context, in the order of the other restored entries (csrc/fseq_api_identity.hip)
+static int need_restored_result(fseq_ctx *c)
+{
+	if (!c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
+	if (int const rc = need_result(c)) return rc;
+	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to write (segmentation failed or was not run)");
+	return FSEQ_OK;
+}
+
+// fseq_get_segments with lb / rb in the source's co-ordinates (restored_segment_bounds, csrc/fseq_restored_bounds.hpp)
+int fseq_get_segments_restored(fseq_ctx *c, fseq_segment *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if (int const rc = need_restored_result(c)) return rc;
+	std::vector<uint64_t> src_lb, src_rb;
+	if (int const rc = restored_bounds_of(c, src_lb, src_rb)) return rc;
+	for (size_t s = 0; s < c->segments.size(); ++s)
+	{
+		out[s] = c->segments[s];
+		out[s].lb = src_lb[s];
+		out[s].rb = src_rb[s];
+	}
+	return FSEQ_OK;
+}
+
+// fseq_write_segments_device in the source's co-ordinates: the bounds of restored_segment_bounds, and substrings of the source's
+// length with row 0's byte at every identity column (k_segfile_write<., true>, csrc/fseq_segfile.hpp).  Everything else is the
+// reduced writer's, byte for byte.
+int fseq_write_segments_restored(fseq_ctx *c, int joining, char const *path)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = need_restored_result(c)) return rc;
+	if (joining != FSEQ_JOIN_GREEDY && joining != FSEQ_JOIN_BIPARTITE && joining != FSEQ_JOIN_RANDOM)
+		return fail(c, FSEQ_E_ARG, "unknown joining method (FSEQ_JOIN_GREEDY, FSEQ_JOIN_BIPARTITE or FSEQ_JOIN_RANDOM)");
+	if (FSEQ_JOIN_GREEDY == joining) return fseq_write_segments_device(c, joining, path);      // (the header alone: no co-ordinates in it)
+	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: a rank holds its own columns and boundary states only");
+	if (!segments_tile(c)) return fail(c, FSEQ_E_UNSUPPORTED, "the merged segments do not tile the columns");
+	bool const bip = FSEQ_JOIN_BIPARTITE == joining;
+	uint32_t const X = c->res.max_segment_size;
+	if (X < 1) return fail(c, FSEQ_E_ARG, "no segments to write");
+	if (bip && X > JBW_MAX_TEXTS) return fail(c, FSEQ_E_UNSUPPORTED, "restored bipartite-matching segments file: more than 4,096 texts a segment");
+	if (!bip && X > 0xFFFFu) return fail(c, FSEQ_E_UNSUPPORTED, "restored random-joining segments file: more than 65,535 classes a segment");
+	if (c->p.m > 0x7FFFFFFFull || c->segments.size() > 0x7FFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "restored segments file: 2^31 rows or segments or more");
+	if (c->idn.n_src >= 0xFFFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "restored segments file: the kept columns' source positions are 32 bits wide (source n < 2^32 - 1)");
+	std::vector<uint64_t> src_lb, src_rb;
+	if (int const rc = restored_bounds_of(c, src_lb, src_rb)) return rc;
+	SegFileRestored const R{src_lb.data(), src_rb.data(), (uint32_t const *) c->idn.kept, (uint8_t const *) c->idn.mask, (uint8_t const *) c->idn.ref, c->idn.n_src};
+	return write_segments_device_lines(c, bip, path, bip ? SEGFILE_HEADER_BIP : SEGFILE_HEADER_COPIES, &R);
+}
+
+// fseq_debug_restored_bounds: restored_segment_bounds on caller-supplied columns and segments.  No device, no context.
+int fseq_debug_restored_bounds(uint64_t const *kept, uint64_t n, uint64_t n_src, uint64_t const *lb, uint64_t const *rb, uint64_t n_segments,
+                               uint64_t *src_lb, uint64_t *src_rb)
+{
+	if (!src_lb || !src_rb) return FSEQ_E_ARG;
+	return restored_segment_bounds(kept, n, n_src, lb, rb, n_segments, src_lb, src_rb) ? FSEQ_E_ARG : FSEQ_OK;
 }
 
 int fseq_debug_segments_file(fseq_ctx *c, uint64_t *batches, uint64_t *bytes, uint64_t *longest_line, uint64_t *lines)
 {
 	if (!c) return FSEQ_E_ARG;
-	if (!c->segfile.have) return fail(c, FSEQ_E_ARG, "no fseq_write_segments_device has finished on this context");
+	if (!c->segfile.have) return fail(c, FSEQ_E_ARG, "no fseq_write_segments_device or fseq_write_segments_restored has finished on this context");
 	if (batches) *batches = c->segfile.batches;
 	if (bytes) *bytes = c->segfile.bytes;
 	if (longest_line) *longest_line = c->segfile.longest_line;

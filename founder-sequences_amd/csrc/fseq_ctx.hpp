@@ -124,7 +124,7 @@ struct Tuning {
 	bool join_wide = false;              // FSEQ_JOIN_WIDE: ... through the wide device front (strips of left classes) at any max_segment_size; FSEQ_JOIN_HOST wins
 	bool join_bip_wide = false;          // FSEQ_JOIN_BIP_WIDE: fseq_join_bipartite through the wide device form (weights in slabs of device memory) at any max_segment_size up to 4,096; FSEQ_JOIN_HOST wins
 	int  join_bip_slabs = 0;             // FSEQ_JOIN_BIP_SLABS: most slabs (= persistent workgroups) of the wide form (by itself: from the CU count and the memory)
-	int  segfile_batch = 0;              // FSEQ_SEGFILE_BATCH: most bytes of a batch of fseq_write_segments_device (by itself: 256 MiB; tests: batches of a line or two)
+	int  segfile_batch = 0;              // FSEQ_SEGFILE_BATCH: most bytes of a batch of fseq_write_segments_device / fseq_write_segments_restored (by itself: 256 MiB; tests: batches of a line or two)
 	bool shard_dp_full = false;          // FSEQ_SHARD_DP_FULL: the sharded DP gathers the whole key array after every sweep (round 2-3 form)
 	int  shard_dp_window = 0;            // FSEQ_SHARD_DP_WINDOW: entries of the other ranks a rank holds in front of its own (tests: small windows)
 	int  inject_failure_rank = -1;       // FSEQ_INJECT_FAILURE_RANK: this rank of a sharded run fails after phase A
@@ -307,7 +307,7 @@ struct fseq_ctx {
 	int join_path = -1;                      // the last fseq_join_greedy (fseq_debug_join_path): 0 host, 1 the LDS front, 2 the wide front; -1: none yet
 	int bip_path = -1;                       // the last fseq_join_bipartite since the input was set (fseq_debug_bipartite_path): 0 host, 1 the LDS form, 2 the wide form; -1: none yet
 	int rand_path = -1;                      // the last fseq_join_random since the input was set (fseq_debug_random_path): 0 host, 1 the class tables from the device; -1: none yet
-	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device (fseq_debug_segments_file)
+	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device or fseq_write_segments_restored (fseq_debug_segments_file)
 	fseq_progress_fn progress_fn = nullptr;
 	void *progress_user = nullptr;
 	hipStream_t stream = nullptr;

@@ -22,6 +22,11 @@
 //                           scan of digits + 1 gives every member's offset in the segment's index bytes, the offset of a
 //                           text's first member is the smallest of its members' (an LDS minimum, order-independent), and a
 //                           member's digits go to the line's index field at the difference.
+// The RESTORED forms (fseq_write_segments_restored, on a context made by fseq_create_without_identity_columns) print a line in the
+// SOURCE's co-ordinates: its substring is src_rb - src_lb bytes (restored_segment_bounds, fseq_restored_bounds.hpp), filled in
+// two passes over disjoint bytes -- the reference row's byte at every identity column of the range, lanes along the source
+// positions, and the row's byte of every kept column c of [lb, rb) at kept[c] - src_lb, lanes along the kept columns.  The class
+// tables, the texts and the members stay in reduced co-ordinates, where the boundary states are.
 // No kernel waits on another workgroup.  Class counts are clipped to X, texts to X, rows to m, and every store is checked
 // against the batch buffer's size: a table value never indexes unchecked.
 // The index field is written with byte stores, one member (2 to 11 bytes) a lane: the lanes of a wave cover one contiguous
@@ -102,20 +107,38 @@ struct SegFileArgs {
 	uint32_t const *reprow;
 	// random: {substring_idx, copies} of line j of segment s at [s * X + j], j < count[s], in the file's order
 	uint2 const *rline;
+	// restored: the segments in the source's co-ordinates, [S] each; the source column of every kept column, [seg_rb[S - 1]];
+	// which source columns are identity columns and row 0 of the source as raw bytes, [n_src] each (nullptr / 0 otherwise)
+	uint64_t const *src_lb, *src_rb;
+	uint32_t const *kept;
+	uint8_t const *mask, *ref;
+	uint64_t n_src;
 };
+
+// bytes of a line's substring: the segment's columns, in the restored form its source positions
+template <bool RESTORED>
+__device__ __forceinline__ uint64_t sf_width(SegFileArgs const &A, uint32_t s)
+{
+	if (RESTORED)
+	{
+		uint64_t const a = A.src_lb[s], b = A.src_rb[s];
+		return b > a ? b - a : 0u;
+	}
+	return A.seg_rb[s] - A.seg_lb[s];
+}
 
 __host__ __device__ inline size_t segfile_lines_lds_bytes(uint32_t X, bool bip) { return bip ? (size_t) X * 8u : 0u; }
 
 // loff[s][j], j <= X (stride X + 1): bytes of the segment's lines in front of line j; a segment has X lines (bipartite) or
 // count[s] (random: the lines behind them have no bytes)
-template <bool BIP>
+template <bool BIP, bool RESTORED = false>
 static __global__ __launch_bounds__(SF_T) void k_segfile_lines(SegFileArgs A, uint64_t *__restrict__ loff)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned long long sf_dig[];      // [X] bipartite: digits + 1 over a text's rows
 	__shared__ uint64_t scratch[SF_NW];
 	uint32_t const s = blockIdx.x, tid = threadIdx.x, X = A.X, m = A.m;
 	uint32_t const nc = min(A.count[s], X);
-	uint64_t const fixed = (A.ppos[s + 1] - A.ppos[s]) + (A.seg_rb[s] - A.seg_lb[s]) + 1u;      // prefix, substring, one tab or the newline
+	uint64_t const fixed = (A.ppos[s + 1] - A.ppos[s]) + sf_width<RESTORED>(A, s) + 1u;      // prefix, substring, one tab or the newline
 	if (BIP)
 	{
 		for (uint32_t t = tid; t < X; t += SF_T) sf_dig[t] = 0;
@@ -242,7 +265,7 @@ struct SegFileBatch {
 	uint64_t begin, bytes;
 };
 
-template <bool BIP>
+template <bool BIP, bool RESTORED = false>
 static __global__ __launch_bounds__(SF_T) void k_segfile_write(
 	SegFileArgs A, SegFileBatch B, uint8_t const *__restrict__ msa, size_t ld, uint32_t bsh, uint8_t const *__restrict__ code_to_byte,
 	uint64_t const *__restrict__ loff, uint64_t const *__restrict__ seg_off, uint32_t const *__restrict__ members, uint8_t *__restrict__ out)
@@ -255,7 +278,8 @@ static __global__ __launch_bounds__(SF_T) void k_segfile_write(
 	lut[tid] = code_to_byte[tid];
 	uint32_t const nc = min(A.count[s], X), nl = BIP ? X : nc;
 	uint32_t const j_lo = s == B.s0 ? min(B.j_lo, nl) : 0u, j_hi = s == B.s1 ? min(B.j_hi, nl) : nl;
-	uint64_t const lb = A.seg_lb[s], rb = A.seg_rb[s], W = rb - lb;
+	uint64_t const lb = A.seg_lb[s], rb = A.seg_rb[s], W = sf_width<RESTORED>(A, s);
+	uint64_t const slb = RESTORED ? A.src_lb[s] : 0u;
 	uint64_t const p0 = A.ppos[s], plen = A.ppos[s + 1] - p0;
 	uint64_t const *lo = loff + (size_t) s * ((size_t) X + 1u);
 	uint64_t const seg_at = seg_off[s] - B.begin;                    // (mod 2^64 where the segment begins in front of the batch: only its lines inside are addressed)
@@ -303,8 +327,26 @@ static __global__ __launch_bounds__(SF_T) void k_segfile_write(
 		}
 		if (sub + W > end) continue;                                 // (never)
 		uint32_t const off = row >> bsh, sh = (row & ((1u << bsh) - 1u)) * bits;
-		for (uint64_t k = lane; k < W; k += 64u)
-			out[sub + k] = row < m ? lut[(msa[(lb + k) * ld + off] >> sh) & cmask] : (uint8_t) '-';
+		if (RESTORED)
+		{
+			// the identity columns of [src_lb, src_rb): row 0's byte, lanes along the source positions
+			for (uint64_t k = lane; k < W; k += 64u)
+			{
+				uint64_t const p = slb + k;
+				if (p < A.n_src && A.mask[p]) out[sub + k] = A.ref[p];
+			}
+			// the kept columns of [lb, rb) at their source positions, which the pass above left alone (mask is 0 at a kept
+			// column: k_identity_scatter made kept from it); one outside the range stores nothing
+			for (uint64_t c = lb + lane; c < rb; c += 64u)
+			{
+				uint64_t const p = A.kept[c];
+				if (p >= slb && p - slb < W)
+					out[sub + (p - slb)] = row < m ? lut[(msa[c * ld + off] >> sh) & cmask] : (uint8_t) '-';
+			}
+		}
+		else
+			for (uint64_t k = lane; k < W; k += 64u)
+				out[sub + k] = row < m ? lut[(msa[(lb + k) * ld + off] >> sh) & cmask] : (uint8_t) '-';
 	}
 	if (!BIP) return;
 	// the index fields: the segment's members in order, digits + 1 each

@@ -59,6 +59,10 @@ char const *const USAGE =
 	"      --output-restored-matches=PATH ... and match the full-length input against the restored founders on the device: the report\n"
 	"                                     of match-sequences-to-founders on the output of insert-identity-columns (requires\n"
 	"                                     --remove-identity-columns; honours --match-min-segment-length)\n"
+	"      --output-restored-segments=PATH ... and write the segments file in the input's co-ordinates on the device: LB / RB count the\n"
+	"                                     input's columns and every substring has its identity columns back, from the first sequence\n"
+	"                                     (requires --remove-identity-columns; every joining method; works under --upload-memory;\n"
+	"                                     --output-segments, if given as well, stays in reduced co-ordinates)\n"
 	"      --output-held-out-restored-matches=PATH  With --hold-out and --remove-identity-columns: match the full-length held-out\n"
 	"                                     sequences against the restored founders on the device: the report of match-sequences-to-founders\n"
 	"                                     for them and the founders file (SEQUENCE_INDEX counts along the --hold-out LIST; source\n"
@@ -315,7 +319,7 @@ int main(int argc, char **argv)
 {
 	char const *hold_out_spec = nullptr, *out_held_matches = nullptr, *out_held_restored = nullptr, *out_seq_restored = nullptr;
 	std::vector<uint32_t> held_rows;
-	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr;
+	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr, *out_restored_segments = nullptr;
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
@@ -350,6 +354,7 @@ int main(int argc, char **argv)
 		{"match-sequences", required_argument, nullptr, 1014}, {"output-sequence-matches", required_argument, nullptr, 1015},
 		{"hold-out", required_argument, nullptr, 1016}, {"output-held-out-matches", required_argument, nullptr, 1017},
 		{"output-held-out-restored-matches", required_argument, nullptr, 1018}, {"output-sequence-restored-matches", required_argument, nullptr, 1019},
+		{"output-restored-segments", required_argument, nullptr, 1020},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -426,6 +431,7 @@ int main(int argc, char **argv)
 			case 1017: out_held_matches = optarg; break;
 			case 1018: out_held_restored = optarg; break;
 			case 1019: out_seq_restored = optarg; break;
+			case 1020: out_restored_segments = optarg; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -466,6 +472,8 @@ int main(int argc, char **argv)
 	if (out_held_restored && !(hold_out_spec && remove_identity)) { std::cerr << "--output-held-out-restored-matches requires --hold-out and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
 	// (the two combine with --remove-identity-columns only for the restored match; the reports in reduced co-ordinates stay refused)
 	if (match_seqs && remove_identity && (!out_seq_restored || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	if (out_restored_segments && gpus > 1) { std::cerr << "--output-restored-segments is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
+	if (out_restored_segments && !remove_identity) { std::cerr << "--output-restored-segments requires --remove-identity-columns (without it --output-segments is in the input's co-ordinates already)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_matches && !remove_identity) { std::cerr << "--output-restored-matches requires --remove-identity-columns (without it the founders are matched with --output-matches)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && out_matches) { std::cerr << "--remove-identity-columns is not supported together with --output-matches (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
@@ -727,6 +735,11 @@ int main(int argc, char **argv)
 			std::cerr << "A match against the restored founders needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_restored_segments)
+		{
+			std::cerr << "--output-restored-segments needs the segments of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_restored_matches)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
@@ -820,6 +833,14 @@ int main(int argc, char **argv)
 			rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
 			             : fseq_write_segments(ctx, rows.data(), how, out_segments);
 		if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	}
+	if (out_restored_segments)
+	{
+		// the same file in the input's co-ordinates, from what the device holds of the reduced context: no rows on the host, so
+		// every joining method is served under --upload-memory too
+		std::cerr << "Outputting the restored segments…" << std::endl;
+		int const how = joining::GREEDY == join ? FSEQ_JOIN_GREEDY : (joining::RANDOM == join ? FSEQ_JOIN_RANDOM : FSEQ_JOIN_BIPARTITE);
+		if (FSEQ_OK != (rc = fseq_write_segments_restored(ctx, how, out_restored_segments))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	}
 	if (out_matches)
 	{

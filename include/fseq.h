@@ -418,6 +418,26 @@ int  fseq_write_identity_columns(fseq_ctx *ctx, char const *path);
  * an identity column row 0's byte.  Needs a finished long-path run (FSEQ_E_ARG before one and on a short-path result, whose
  * founders are input rows).  path NULL or "-" = stdout. */
 int  fseq_write_founders_restored(fseq_ctx *ctx, uint32_t const *permutations, char const *path);
+/* replaces: segmentation_container::reduced_traceback mapped through the identity-column string, which the reference's chain
+ * leaves to the user: fseq_get_segments with lb / rb in the SOURCE's co-ordinates, segment_size unchanged.  Segment s covers
+ * the source columns from its first kept column up to the next segment's first kept column; segment 0 begins at 0 and the last
+ * one ends at the source's n, so the ranges tile the source and the identity columns behind a segment's last kept column are
+ * that segment's (csrc/fseq_restored_bounds.hpp).  These are the ranges whose bytes a line of fseq_write_founders_restored
+ * takes from one row.  FSEQ_E_ARG on a context not made by fseq_create_without_identity_columns, before a run and on a
+ * short-path result. */
+int  fseq_get_segments_restored(fseq_ctx *ctx, fseq_segment *out);
+/* replaces: the --output-segments file (segmentation_dp_arg.cc:13-104) of a run on the FULL-LENGTH alignment's columns, which
+ * the reference's chain does not give (its file is in reduced co-ordinates): fseq_write_segments_device with LB / RB those of
+ * fseq_get_segments_restored and every substring at the source's length -- the line's row at the kept columns of the segment,
+ * input row 0's byte at the identity columns of its range.  Header, SEGMENT, SIZE, the row lists, COPIED_FROM, the copy numbers
+ * and the order of the lines are those of fseq_write_segments_device on the same context, byte for byte; greedy joining writes
+ * the header alone.  Written where the alignment, the boundary states and the identity state are: no host rows, the same
+ * batches (FSEQ_SEGFILE_BATCH).  Refuses, each with fseq_last_error set and no file created: FSEQ_E_ARG -- a context not made
+ * by fseq_create_without_identity_columns, no finished long-path run, no resident alignment, an unknown joining, an output
+ * file that cannot be opened; FSEQ_E_UNSUPPORTED -- merged segments that do not tile the columns, bipartite joining with more
+ * than 4,096 texts a segment, random joining with more than 65,535, a source of 2^32 - 1 columns or more.  path NULL or
+ * "-" = stdout. */
+int  fseq_write_segments_restored(fseq_ctx *ctx, int joining, char const *path);
 /* replaces: match-sequences-to-founders (match_founder_sequences.cc:108-259) as the last step of the reference's chain
  * remove-identity-columns | founder_sequences | insert-identity-columns | match-sequences-to-founders: the FULL-LENGTH input
  * rows matched against the FULL-LENGTH founders, on a context made by fseq_create_without_identity_columns (FSEQ_E_ARG on any

@@ -116,7 +116,15 @@ int  fseq_debug_red_cls_direct(uint32_t m, uint32_t B, uint32_t bits, uint64_t c
  * tables from the device.  FSEQ_E_ARG while none has finished. */
 int  fseq_debug_random_path(fseq_ctx *ctx, int *path);
 
-/* The last file fseq_write_segments_device wrote on this context: the batches that left the device (0: greedy, the header
+/* The bounds of merged segments in the source's co-ordinates (restored_segment_bounds, csrc/fseq_restored_bounds.hpp), as
+ * fseq_get_segments_restored and fseq_write_segments_restored apply them -- host arithmetic, no device, no context.  kept[n]: the
+ * source column of every kept column; lb / rb [n_segments]: the merged segments in kept columns.  Out: src_lb / src_rb
+ * [n_segments]: src_lb[0] = 0, else kept[lb[s]]; src_rb[last] = n_src, else kept[rb[s]].  FSEQ_E_ARG, with nothing written: a
+ * NULL array, no segment, kept not strictly ascending or an entry not below n_src, segments that do not tile [0, n). */
+int  fseq_debug_restored_bounds(uint64_t const *kept, uint64_t n, uint64_t n_src, uint64_t const *lb, uint64_t const *rb, uint64_t n_segments,
+                                uint64_t *src_lb, uint64_t *src_rb);
+
+/* The last file fseq_write_segments_device or fseq_write_segments_restored wrote on this context: the batches that left the device (0: greedy, the header
  * alone), the file's bytes, the bytes of its longest line and its lines -- both with the header, a line with its newline.
  * Each out pointer may be NULL.  FSEQ_E_ARG while none has been written. */
 int  fseq_debug_segments_file(fseq_ctx *ctx, uint64_t *batches, uint64_t *bytes, uint64_t *longest_line, uint64_t *lines);
