@@ -133,6 +133,8 @@ EXPORTS = [
     "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
     "fseq_create_without_identity_columns_held", "fseq_match_held_out_restored", "fseq_match_rows_restored", "fseq_get_match_exceptions",
     "fseq_get_segments_restored", "fseq_write_segments_restored", "fseq_debug_restored_bounds",
+    "fseq_input_scan_identity", "fseq_input_reduce", "fseq_input_kept_columns", "fseq_input_columns_kept", "fseq_input_end_kept",
+    "fseq_set_rows_streamed_without_identity_columns", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -140,7 +142,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
-                 "fseq_debug_restored_bounds"]
+                 "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -277,6 +279,14 @@ def load_library():
     L.fseq_get_segments_restored.argtypes = [vp, vp]
     L.fseq_write_segments_restored.argtypes = [vp, C.c_int, C.c_char_p]
     L.fseq_debug_restored_bounds.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp]
+    L.fseq_input_scan_identity.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.fseq_input_reduce.argtypes = [vp, C.POINTER(Params), C.POINTER(IdentitySummary)]
+    L.fseq_input_kept_columns.argtypes = [vp, u64, u64, C.POINTER(u64)]
+    L.fseq_input_columns_kept.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.fseq_input_end_kept.argtypes = [vp, C.POINTER(vp)]
+    L.fseq_set_rows_streamed_without_identity_columns.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(Params), C.POINTER(vp), C.POINTER(IdentitySummary)]
+    L.fseq_debug_alphabet.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
+    L.fseq_debug_input_kept_range.argtypes = [vp, u64, u64, u64, C.POINTER(u64), C.POINTER(u64)]
     _lib = L
     return L
 
@@ -507,6 +517,18 @@ def restored_bounds_host(kept, n_src, lb, rb):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return src_lb[:S].copy(), src_rb[:S].copy()
+
+
+def input_kept_range_host(kept, c0, ncols):
+    """(k0, k1): the entries of the ascending list kept with c0 <= kept[k] < c0 + ncols (input_kept_range,
+    csrc/fseq_input_kept_range.hpp, through fseq_debug_input_kept_range; no device)."""
+    L = load_library()
+    kept = np.ascontiguousarray(kept, dtype=np.uint64)
+    k0, k1 = C.c_uint64(), C.c_uint64()
+    rc = L.fseq_debug_input_kept_range(kept.ctypes.data if len(kept) else None, len(kept), int(c0), int(ncols), C.byref(k0), C.byref(k1))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return k0.value, k1.value
 
 
 def relump_lists(ent, hdr, k0, L_from, L_to, device=0):
@@ -827,6 +849,72 @@ class SegmentationContext:
     def input_end(self):
         self._check(self.L.fseq_input_end(self.h))
 
+    # ---- ... with the identity columns dropped on the way (fseq_input_scan_identity .. fseq_input_end_kept)
+    def input_scan_identity(self, c0, chunk):
+        """input_scan's chunk, finding the identity columns besides the alphabet (also after a supplied alphabet)."""
+        chunk = self._chunk(chunk)
+        self._check(self.L.fseq_input_scan_identity(self.h, int(c0), chunk.shape[1], self._row_pointers(chunk)))
+
+    def input_reduce(self, segment_length, block_len=0, list_cap=0):
+        """After the identity scan has covered every column: makes the kept-column list and the context over the kept columns
+        (handed out by input_end_kept).  Returns the summary {n, identity, kept, ms_device}."""
+        p = Params(0, 0, int(segment_length), 0, int(block_len), int(list_cap), int(self._device))
+        sm = IdentitySummary()
+        self._check(self.L.fseq_input_reduce(self.h, C.byref(p), C.byref(sm)))
+        self._reduce = (int(segment_length), {k: getattr(sm, k) for k, _ in IdentitySummary._fields_})
+        return dict(self._reduce[1])
+
+    def input_kept_columns(self, c0, ncols):
+        """How many kept columns lie in [c0, c0 + ncols) (host only, after input_reduce)."""
+        count = C.c_uint64()
+        self._check(self.L.fseq_input_kept_columns(self.h, int(c0), int(ncols), C.byref(count)))
+        return count.value
+
+    def input_columns_kept(self, c0, chunk):
+        """The second pass.  chunk: uint8 [m, w], or -- for a chunk without a kept column -- None or the width w alone."""
+        if chunk is None or isinstance(chunk, (int, np.integer)):
+            w = self.input_chunk_columns() if chunk is None else int(chunk)
+            self._check(self.L.fseq_input_columns_kept(self.h, int(c0), min(w, self.n - int(c0)), None))
+            return
+        chunk = self._chunk(chunk)
+        self._check(self.L.fseq_input_columns_kept(self.h, int(c0), chunk.shape[1], self._row_pointers(chunk)))
+
+    def _reduced_context(self, h, segment_length, sm, list_memory=0):
+        new = SegmentationContext.__new__(SegmentationContext)
+        new.L, new.h = self.L, h
+        new.m, new.n, new.segment_length, new._device = self.m, int(sm["kept"]), int(segment_length), self._device
+        new.result, new._keep = None, None
+        new.source_n = int(sm["n"])
+        new.identity_summary = dict(sm)
+        if list_memory:
+            new.set_list_memory(list_memory)
+        return new
+
+    def input_end_kept(self, list_memory=0):
+        """Ends the reduced input: the SegmentationContext over the kept columns, as without_identity_columns() returns it."""
+        h = C.c_void_p()
+        self._check(self.L.fseq_input_end_kept(self.h, C.byref(h)))
+        return self._reduced_context(h, self._reduce[0], self._reduce[1], list_memory)
+
+    def set_sequences_without_identity_columns(self, msa, segment_length, staging_bytes=0, block_len=0, list_cap=0, list_memory=0):
+        """set_sequences(msa, staging_bytes) followed by without_identity_columns(segment_length, ...) in one call that never
+        holds msa's packed form on the device (fseq_set_rows_streamed_without_identity_columns).  msa: uint8 [m, n], or a
+        sequence of m uint8 rows of n bytes each (rows that are not one matrix).  Returns the new context."""
+        if isinstance(msa, np.ndarray):
+            assert msa.dtype == np.uint8 and msa.shape == (self.m, self.n)
+            if msa.strides[1] != 1:
+                msa = np.ascontiguousarray(msa)
+            rows = self._row_pointers(msa)
+        else:
+            msa = [np.ascontiguousarray(r, dtype=np.uint8) for r in msa]
+            assert len(msa) == self.m and all(r.shape == (self.n,) for r in msa)
+            rows = (C.c_void_p * self.m)(*[r.ctypes.data for r in msa])
+        p = Params(0, 0, int(segment_length), 0, int(block_len), int(list_cap), int(self._device))
+        h = C.c_void_p()
+        sm = IdentitySummary()
+        self._check(self.L.fseq_set_rows_streamed_without_identity_columns(self.h, rows, int(staging_bytes), C.byref(p), C.byref(h), C.byref(sm)))
+        return self._reduced_context(h, segment_length, {k: getattr(sm, k) for k, _ in IdentitySummary._fields_}, list_memory)
+
     def packed_columns(self, c0=0, c1=None):
         """(bytes [c1 - c0, ld], bits): the columns of the resident alignment as they are stored, padding included."""
         c1 = self.n if c1 is None else c1
@@ -835,6 +923,13 @@ class SegmentationContext:
         out = np.zeros((c1 - c0, ld.value), dtype=np.uint8)
         self._check(self.L.fseq_debug_packed_columns(self.h, c0, c1, out.ctypes.data, C.byref(ld), C.byref(bits)))
         return out, bits.value
+
+    def alphabet(self):
+        """(sigma, bits, bytes): the codes of the resident input, their width and the byte each of them stands for, in code order."""
+        sigma, bits = C.c_uint32(), C.c_uint32()
+        table = np.zeros(256, dtype=np.uint8)
+        self._check(self.L.fseq_debug_alphabet(self.h, C.byref(sigma), C.byref(bits), table.ctypes.data))
+        return sigma.value, bits.value, table[:sigma.value].tobytes()
 
     def device_bytes(self, reset_peak=False):
         """(now, peak): device bytes this context's buffers hold and the most they have held (since the last reset_peak).

@@ -451,6 +451,16 @@ int fseq_rowshard_pbwt(fseq_rowshard const *A, uint32_t *a_out, uint32_t *d_out,
 	return ok ? FSEQ_OK : FSEQ_E_HIP;
 }
 
+int fseq_debug_alphabet(fseq_ctx *c, uint32_t *sigma, uint32_t *bits, uint8_t *code_to_byte)
+{
+	if (!c || !sigma || !bits) return FSEQ_E_ARG;
+	if (!c->have_input) return fail(c, FSEQ_E_ARG, "alphabet: the context holds no input");
+	*sigma = c->sigma;
+	*bits = 8u >> c->bsh;
+	if (code_to_byte) memcpy(code_to_byte, c->code_to_byte, 256);
+	return FSEQ_OK;
+}
+
 int fseq_debug_device_bytes(fseq_ctx *c, uint64_t *now, uint64_t *peak, int reset_peak)
 {
 	if (!c || !now || !peak) return FSEQ_E_ARG;

@@ -564,10 +564,20 @@ struct fseq_ctx {
 		DevBuf<uint32_t> words;              // [0, 8): bytes the scans found; [8, 16): bytes outside the alphabet the encode met
 		DevBuf<uint8_t> table;               // [256] code of a byte (0xFF: not in the alphabet, where sigma < 256)
 		hipEvent_t copied[2]{}, used[2]{};   // per half: its copies are done; the kernel that read it is done
+		// the identity columns dropped on the way (fseq_input_scan_identity .. fseq_input_end_kept): the packed form of the source never exists
+		int scan_mode = 0;                   // which scan entry this input uses: 0 none yet, 1 fseq_input_scan, 2 fseq_input_scan_identity
+		DevBuf<uint8_t> id_mask, id_ref;     // [n] each, filled chunk by chunk; fseq_input_reduce hands them to the new context (idn.mask, idn.ref)
+		DevBuf<uint32_t> id_acc;             // the chunk under way: OR over the rows of (piece ^ row 0's piece), 4 words a 16-column piece; zero between chunks
+		bool reduced = false;                // fseq_input_reduce has made `half`
+		fseq_ctx *half = nullptr;            // the context over the kept columns while it is filled: this input's until fseq_input_end_kept hands it out
+		std::vector<uint32_t> kept;          // host copy of half->idn.kept (csrc/fseq_input_kept_range.hpp searches it)
 	} in;
 	void free_input()
 	{
-		fseq::release_all(this, in.stage, in.words, in.table);
+		if (in.half) { fseq_destroy(in.half); in.half = nullptr; }
+		fseq::release_all(this, in.stage, in.words, in.table, in.id_mask, in.id_ref, in.id_acc);
+		in.kept = std::vector<uint32_t>();
+		in.reduced = false;
 		for (auto &e : in.copied) if (e) { (void) hipEventDestroy(e); e = nullptr; }
 		for (auto &e : in.used) if (e) { (void) hipEventDestroy(e); e = nullptr; }
 		in.open = false;

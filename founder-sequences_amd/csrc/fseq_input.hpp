@@ -8,6 +8,12 @@
 //                   alphabet before the first column is encoded: consecutive_alphabet_as_builder, generate_context.cc:135-147)
 // k_input_encode    bytes -> codes -> packed columns [c0, c0 + ncols) of the resident alignment, in their final place: columns
 //                   are packed on their own (whole bytes, ld bytes a column), so a chunk touches no other chunk's bytes
+// and, for the input that drops its identity columns on the way (fseq_input_scan_identity .. fseq_input_end_kept), in
+// fseq_input_reduced.hpp:
+// k_input_identity         k_input_presence's words and, per 16-column piece, the OR over the rows of (piece ^ row 0's piece): the
+//                          grid is pieces x row slabs, the slabs meet through atomicOr
+// k_input_identity_finish  mask[c0 + j], ref[c0 + j] of the chunk from that accumulator, which it clears for the next chunk
+// k_input_encode_kept      k_input_encode on the kept columns of the chunk alone, into an alignment of exactly their number
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -89,7 +89,10 @@ char const *const USAGE =
 	"                                     (one GPU only; results are the same)  (default=`0': every list held)\n"
 	"      --upload-memory=MIB            Read the sequence files of a list-file input in column chunks through at most MIB MiB of host\n"
 	"                                     memory and as much device staging instead of loading them whole (list-file only; one GPU\n"
-	"                                     only; results are the same; --output-segments then needs greedy joining)\n";
+	"                                     only; results are the same; --output-segments then needs greedy joining)\n"
+	"      --reduce-on-upload             With --upload-memory and --remove-identity-columns: find the columns in which all sequences agree\n"
+	"                                     while the files are read and pack only the others, so that the device never holds the\n"
+	"                                     full-length alignment (results are the same; not together with --hold-out)\n";
 
 bool read_file(std::string const &path, std::string &out)
 {
@@ -174,6 +177,38 @@ int upload_in_chunks(fseq_ctx *ctx, std::vector<std::string> const &paths, uint6
 			if (FSEQ_OK != rc) return rc;
 		}
 	return fseq_input_end(ctx);
+}
+
+// --reduce-on-upload: the same two passes with the identity columns dropped on the way.  The scan pass finds them, the context over
+// the other columns is made between the passes (*kept; it is src's until the end), and the second pass reads only the chunks that
+// hold one of its columns
+int upload_reduced_in_chunks(fseq_ctx *src, std::vector<std::string> const &paths, uint64_t n, uint64_t bytes, fseq_params const &pk, fseq_ctx **kept,
+                             fseq_identity_summary *is, std::string &io_err)
+{
+	int rc(fseq_input_begin(src, nullptr, 0, bytes));
+	if (FSEQ_OK != rc) return rc;
+	size_t const m(paths.size());
+	uint64_t width(fseq_input_chunk_columns(src));
+	if ((width & ~63ull) >= 64) width &= ~63ull;
+	if (width > n) width = n;
+	std::vector<uint8_t> buf(m * (size_t) width);
+	std::vector<uint8_t const *> at(m);
+	for (int pass = 0; pass < 2; ++pass)
+	{
+		for (uint64_t c0 = 0; c0 < n; c0 += width)
+		{
+			size_t const w((size_t) (n - c0 < width ? n - c0 : width));
+			uint64_t here(1);
+			if (pass && FSEQ_OK != (rc = fseq_input_kept_columns(src, c0, w, &here))) return rc;
+			if (!here) { if (FSEQ_OK != (rc = fseq_input_columns_kept(src, c0, w, nullptr))) return rc; continue; }
+			if (!read_chunk(paths, c0, w, buf.data(), io_err)) return FSEQ_E_ARG;
+			for (size_t r = 0; r < m; ++r) at[r] = buf.data() + r * w;
+			rc = pass ? fseq_input_columns_kept(src, c0, w, at.data()) : fseq_input_scan_identity(src, c0, w, at.data());
+			if (FSEQ_OK != rc) return rc;
+		}
+		if (!pass && FSEQ_OK != (rc = fseq_input_reduce(src, &pk, is))) return rc;
+	}
+	return fseq_input_end_kept(src, kept);
 }
 
 // FASTA: '>' header lines, sequence lines concatenated (README.md:80)
@@ -333,7 +368,7 @@ int main(int argc, char **argv)
 	unsigned long long list_memory_mib = 0;
 	bool list_memory_bad = false;
 	unsigned long long upload_mib = 0;
-	bool upload_given = false, upload_bad = false;
+	bool upload_given = false, upload_bad = false, reduce_on_upload = false;
 	char const *scan_spec = nullptr, *out_scan = nullptr;
 	unsigned long long max_founders = 0;
 	bool max_founders_given = false, max_founders_bad = false;
@@ -354,7 +389,7 @@ int main(int argc, char **argv)
 		{"match-sequences", required_argument, nullptr, 1014}, {"output-sequence-matches", required_argument, nullptr, 1015},
 		{"hold-out", required_argument, nullptr, 1016}, {"output-held-out-matches", required_argument, nullptr, 1017},
 		{"output-held-out-restored-matches", required_argument, nullptr, 1018}, {"output-sequence-restored-matches", required_argument, nullptr, 1019},
-		{"output-restored-segments", required_argument, nullptr, 1020},
+		{"output-restored-segments", required_argument, nullptr, 1020}, {"reduce-on-upload", no_argument, nullptr, 1021},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -432,6 +467,7 @@ int main(int argc, char **argv)
 			case 1018: out_held_restored = optarg; break;
 			case 1019: out_seq_restored = optarg; break;
 			case 1020: out_restored_segments = optarg; break;
+			case 1021: reduce_on_upload = true; break;
 			default: return EXIT_FAILURE;
 		}
 	}
@@ -461,6 +497,13 @@ int main(int argc, char **argv)
 	{ std::cerr << "Random seed out of bounds." << std::endl; return EXIT_FAILURE; }
 	if (sample_rate <= 0) { std::cerr << "PBWT sample rate multiplier must be non-negative." << std::endl; return EXIT_FAILURE; }
 	if (gpus < 1 || gpus > 64) { std::cerr << "The number of GPUs must be positive." << std::endl; return EXIT_FAILURE; }
+	if (reduce_on_upload)
+	{
+		if (!upload_given) { std::cerr << "--reduce-on-upload requires --upload-memory (it drops the identity columns while the sequence files are read in chunks)." << std::endl; return EXIT_FAILURE; }
+		if (!remove_identity) { std::cerr << "--reduce-on-upload requires --remove-identity-columns (it is another way to the same reduced run)." << std::endl; return EXIT_FAILURE; }
+		if (hold_out_spec) { std::cerr << "--reduce-on-upload is not supported together with --hold-out (carrying the held-out sequences along needs the full-length alignment on the device)." << std::endl; return EXIT_FAILURE; }
+		if (gpus > 1) { std::cerr << "--reduce-on-upload is not supported together with --gpus > 1 (the chunked input does not exchange the ranks' alphabets)." << std::endl; return EXIT_FAILURE; }
+	}
 	if (list_memory_bad) { std::cerr << "The list memory must be a non-negative number of MiB." << std::endl; return EXIT_FAILURE; }
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
@@ -575,7 +618,8 @@ int main(int argc, char **argv)
 		}
 		else if (FSEQ_OK != rc_) return rc_;
 		if (list_memory_mib && FSEQ_OK != (rc_ = fseq_set_list_memory(ctxs[r], (uint64_t) list_memory_mib << 20))) return rc_;
-		if (upload_given) { if (FSEQ_OK != (rc_ = upload_in_chunks(ctxs[r], paths, p.n, (uint64_t) upload_mib << 20, io_err))) return rc_; }
+		if (reduce_on_upload) {}                                   // (the input goes up where the identity columns are removed, below)
+		else if (upload_given) { if (FSEQ_OK != (rc_ = upload_in_chunks(ctxs[r], paths, p.n, (uint64_t) upload_mib << 20, io_err))) return rc_; }
 		else if (FSEQ_OK != (rc_ = fseq_set_rows(ctxs[r], rows.data()))) return rc_;     // (sharded: posts its own failures)
 		if (hold_out_spec)
 		{
@@ -612,7 +656,9 @@ int main(int argc, char **argv)
 			fseq_ctx *kept(nullptr);
 			fseq_identity_summary is{};
 			// (--hold-out: the held-out sequences go along, their kept columns and the identity columns in which they differ)
-			rc_ = hold_out_spec ? fseq_create_without_identity_columns_held(ctxs[r], &pk, &kept, &is) : fseq_create_without_identity_columns(ctxs[r], &pk, &kept, &is);
+			// (--reduce-on-upload: the source context never holds an alignment; the kept columns are packed as the files are read)
+			rc_ = reduce_on_upload ? upload_reduced_in_chunks(ctxs[r], paths, p.n, (uint64_t) upload_mib << 20, pk, &kept, &is, io_err)
+			    : hold_out_spec ? fseq_create_without_identity_columns_held(ctxs[r], &pk, &kept, &is) : fseq_create_without_identity_columns(ctxs[r], &pk, &kept, &is);
 			if (FSEQ_OK != rc_) return rc_;
 			fseq_destroy(ctxs[r]);
 			ctxs[r] = kept;

@@ -617,6 +617,54 @@ int      fseq_input_end(fseq_ctx *ctx);
  * those of fseq_set_rows on the same rows, bit for bit. */
 int      fseq_set_rows_streamed(fseq_ctx *ctx, uint8_t const *const *rows, uint64_t staging_bytes);
 
+/* The chunked input with the identity columns dropped on the way: the context fseq_set_rows_streamed followed by
+ * fseq_create_without_identity_columns gives, bit for bit, without the source's packed alignment (ld x n bytes) ever existing.
+ * replaces: remove-identity-columns in front of founder_sequences for an alignment whose packed form exceeds the card while its
+ * variable columns fit.  src is an ordinary fseq_create context with n = the source's columns; it never holds an alignment.
+ *   fseq_input_begin    as above.
+ *   fseq_input_scan_identity   the scan pass: fseq_input_scan's chunks (same rules), finding besides the byte values, for every
+ *                       column, whether all m rows carry row 0's byte, and row 0's byte.  Allowed, and needed for this path, with a
+ *                       supplied alphabet too.  One scan entry per input: after fseq_input_scan this one returns FSEQ_E_ARG, and
+ *                       the other way round.
+ *   fseq_input_reduce   after the scan has covered [0, n): fixes the code table -- alphabet, sigma and code width are those of the
+ *                       WHOLE source, so a byte that occurs only in identity columns takes a code, as in the chain above; a found
+ *                       byte outside a supplied alphabet is refused here with fseq_input_end's message and effect, wherever it
+ *                       lies --, makes the kept-column list and creates the context over the kept columns with its alignment of
+ *                       ld x kept bytes.  params as for fseq_create_without_identity_columns (n must be 0, m 0 or the source's,
+ *                       device the source's); summary may be NULL (ms_device: the scan of the mask).  Every column an identity
+ *                       column: FSEQ_E_ARG ("every column is an identity column"), no context is made and what the identity scan
+ *                       allocated is released; src holds what fseq_input_begin allocated, and the input may go on as an ordinary
+ *                       one (fseq_input_columns) or give way to a new one.  A failed allocation: FSEQ_E_OOM with the sizes, src
+ *                       stays usable (the call may be repeated).  The new context belongs to src's input until
+ *                       fseq_input_end_kept: a new fseq_input_begin, any other input set on src and fseq_destroy(src) destroy it.
+ *   fseq_input_kept_columns    *count = the kept columns in [c0, c0 + ncols).  Host only, after the reduce: a caller may skip
+ *                       reading a chunk that holds none.
+ *   fseq_input_columns_kept    the second pass: the same tiling of [0, n), ascending.  Only the kept columns of a chunk are
+ *                       encoded, into their final place in the new alignment (padding written as zeros).  A chunk without a
+ *                       kept column returns without a copy or a launch, and rows may be NULL for it.
+ *   fseq_input_end_kept after column n: *out is the finished context -- it has its input and answers as one made by
+ *                       fseq_create_without_identity_columns everywhere (the run, the joiners, the restored writers and matchers,
+ *                       fseq_set_segment_length, the length scan; no other input) --, the staging is released and src is left
+ *                       without an input.  A byte outside a supplied alphabet in a kept cell: FSEQ_E_ARG as fseq_input_end, *out
+ *                       NULL, the new context destroyed.
+ * Device memory, by the accounts of the two contexts (fseq_debug_device_bytes): src holds the staging, 320 bytes of tables and
+ * during the scan 2 n bytes (mask, reference row), min(n, chunk columns) + at most 256 bytes of accumulators and, inside
+ * fseq_input_reduce, 4 bytes per 2,048 columns; the new context ld x kept + 16, 4 x kept and the 2 n bytes src hands over.  The
+ * peaks of both together stay within staging + ld x kept + 16 + 4 x kept + 6 n for n >= 1,024.
+ * Wrong order -- a reduce before the scan is complete or a second one, columns or an end before the reduce, an end before the
+ * columns are complete, fseq_input_columns or fseq_input_end after a reduce -- returns FSEQ_E_ARG and names the step.  Sharded
+ * contexts: FSEQ_E_UNSUPPORTED.  Sources of 2^32 - 1 columns or more are refused (fseq_create).  Not served: held-out rows
+ * (they need the resident source: fseq_create_without_identity_columns_held).  Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+int      fseq_input_scan_identity(fseq_ctx *src, uint64_t c0, uint64_t ncols, uint8_t const *const *rows);
+int      fseq_input_reduce(fseq_ctx *src, fseq_params const *params, fseq_identity_summary *summary);
+int      fseq_input_kept_columns(fseq_ctx *src, uint64_t c0, uint64_t ncols, uint64_t *count);
+int      fseq_input_columns_kept(fseq_ctx *src, uint64_t c0, uint64_t ncols, uint8_t const *const *rows);
+int      fseq_input_end_kept(fseq_ctx *src, fseq_ctx **out);
+/* All of the above for rows that are in host memory, in fseq_set_rows_streamed's chunks: both passes, the reduce between them
+ * and the end.  On any failure *out is NULL and src is left without an input. */
+int      fseq_set_rows_streamed_without_identity_columns(fseq_ctx *src, uint8_t const *const *rows, uint64_t staging_bytes, fseq_params const *params,
+                                                         fseq_ctx **out, fseq_identity_summary *summary);
+
 /* Another segment length bound L on the alignment the context holds.  replaces: nothing of the reference, which is run once
  * per L (generate_context.cc:121-124 reads the bound once); here a second L needs neither a second context nor a second
  * upload.  The context keeps the resident alignment, its alphabet and -- a context made by

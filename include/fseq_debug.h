@@ -73,6 +73,10 @@ int  fseq_debug_bipartite_path(fseq_ctx *ctx, int *path);
  * context's allocations, not a measurement of the device: borrowed columns and the runtime's own memory are not in it. */
 int  fseq_debug_device_bytes(fseq_ctx *ctx, uint64_t *now, uint64_t *peak, int reset_peak);
 
+/* The alphabet of the input the context holds: *sigma codes of *bits bits, code_to_byte[code] (256 bytes, or NULL) the byte a
+ * code stands for (entries from *sigma on are not defined).  FSEQ_E_ARG while the context holds no input. */
+int  fseq_debug_alphabet(fseq_ctx *ctx, uint32_t *sigma, uint32_t *bits, uint8_t *code_to_byte);
+
 /* The resident alignment as it is stored: the bytes of the columns [c0, c1), *ld bytes a column (padding included), codes of
  * *bits bits.  out == NULL: *ld and *bits only.  Not for sharded contexts (a rank holds its own columns only). */
 int  fseq_debug_packed_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t *out, uint64_t *ld, uint32_t *bits);
@@ -123,6 +127,12 @@ int  fseq_debug_random_path(fseq_ctx *ctx, int *path);
  * NULL array, no segment, kept not strictly ascending or an entry not below n_src, segments that do not tile [0, n). */
 int  fseq_debug_restored_bounds(uint64_t const *kept, uint64_t n, uint64_t n_src, uint64_t const *lb, uint64_t const *rb, uint64_t n_segments,
                                 uint64_t *src_lb, uint64_t *src_rb);
+
+/* Which entries of a kept-column list fall inside a chunk of source columns (debug / tests; no device, no context): the pure
+ * host function behind fseq_input_kept_columns and fseq_input_columns_kept (input_kept_range, csrc/fseq_input_kept_range.hpp).
+ * kept[0 .. n_kept) ascend strictly; [*k0, *k1) are the entries with c0 <= kept[k] < c0 + ncols, *k0 == *k1 (where one would
+ * stand) if there is none.  FSEQ_E_ARG: a NULL out pointer, or kept NULL with n_kept > 0. */
+int  fseq_debug_input_kept_range(uint64_t const *kept, uint64_t n_kept, uint64_t c0, uint64_t ncols, uint64_t *k0, uint64_t *k1);
 
 /* The last file fseq_write_segments_device or fseq_write_segments_restored wrote on this context: the batches that left the device (0: greedy, the header
  * alone), the file's bytes, the bytes of its longest line and its lines -- both with the header, a line with its newline.
