@@ -89,6 +89,12 @@ class HoldOutSummary(C.Structure):
     _fields_ = [("m_src", C.c_uint32), ("held", C.c_uint32), ("kept", C.c_uint32), ("reserved", C.c_uint32), ("ms_device", C.c_double)]
 
 
+class JoinScoreSummary(C.Structure):
+    _fields_ = [("junctions", C.c_uint64), ("supported", C.c_uint64), ("unsupported", C.c_uint64), ("gaps", C.c_uint64), ("rows_through", C.c_uint64),
+                ("weight", C.c_uint64), ("min_rows_through_junction", C.c_uint64), ("min_rows_through", C.c_uint32), ("max_breaks", C.c_uint32),
+                ("ms_device", C.c_double)]
+
+
 class DpListsInfo(C.Structure):
     _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
 
@@ -102,6 +108,11 @@ class LengthScanSummary(C.Structure):
 LENGTH_SCAN_DTYPE = np.dtype([("segment_length", "<u8"), ("max_segment_size", "<u4"), ("short_path", "<u4"), ("lists", "<u4"), ("list_cap", "<u4"),
                               ("dp_chunks", "<u4"), ("reserved", "<u4"), ("ms_device", "<f8")])
 SCAN_LISTS_BUILT, SCAN_LISTS_FOLDED, SCAN_LISTS_NONE = 0, 1, 2
+
+# fseq_join_score_entry (include/fseq.h), 32 bytes
+JOIN_SCORE_DTYPE = np.dtype([("rb", "<u8"), ("weight", "<u8"), ("supported", "<u4"), ("unsupported", "<u4"), ("gaps", "<u4"), ("rows_through", "<u4")])
+JOIN_SCORE_MAX_SLOTS = 4096    # csrc/fseq_joinscore.hpp, JS_MAX_SLOTS: the device form's cap on max_segment_size
+JOIN_SCORE_GAP = 0xFFFF        # ... JS_GAP: a slot's class where its row is a gap (debug_join_score)
 
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
@@ -135,6 +146,7 @@ EXPORTS = [
     "fseq_get_segments_restored", "fseq_write_segments_restored", "fseq_debug_restored_bounds",
     "fseq_input_scan_identity", "fseq_input_reduce", "fseq_input_kept_columns", "fseq_input_columns_kept", "fseq_input_end_kept",
     "fseq_set_rows_streamed_without_identity_columns", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
+    "fseq_join_score", "fseq_join_score_host", "fseq_debug_join_score_path", "fseq_debug_join_score",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -142,7 +154,8 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
-                 "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet"]
+                 "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
+                 "fseq_debug_join_score_path", "fseq_debug_join_score"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -287,6 +300,10 @@ def load_library():
     L.fseq_set_rows_streamed_without_identity_columns.argtypes = [vp, C.POINTER(vp), u64, C.POINTER(Params), C.POINTER(vp), C.POINTER(IdentitySummary)]
     L.fseq_debug_alphabet.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     L.fseq_debug_input_kept_range.argtypes = [vp, u64, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.fseq_join_score.argtypes = [vp, vp, vp, vp, vp, C.POINTER(JoinScoreSummary)]
+    L.fseq_join_score_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(JoinScoreSummary)]
+    L.fseq_debug_join_score_path.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fseq_debug_join_score.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.POINTER(JoinScoreSummary)]
     _lib = L
     return L
 
@@ -699,6 +716,57 @@ def random_join_classes_host(m, max_segment_size, count, rep, size, seed):
     return perm
 
 
+def _join_score_result(junctions, breaks, support, sm):
+    return {"junctions": junctions, "breaks": breaks, "support": support, "summary": {k: getattr(sm, k) for k, _ in JoinScoreSummary._fields_}}
+
+
+def join_score_host(m, max_segment_size, lb, rb, a, d, permutations, want_support=False):
+    """The junction support of permutations [segments, max_segment_size] on caller-supplied boundary states (host only, no GPU
+    needed; fseq_join_score_host): what SegmentationContext.join_score returns."""
+    L = load_library()
+    lb = np.ascontiguousarray(lb, dtype=np.uint64)
+    rb = np.ascontiguousarray(rb, dtype=np.uint64)
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    d = np.ascontiguousarray(d, dtype=np.uint32)
+    perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+    S = len(lb)
+    if perm.shape != (S, max_segment_size) or a.size != S * m or d.size != S * m or len(rb) != S:
+        raise FseqError(FSEQ_E_ARG, "join_score_host: shapes disagree")
+    junctions = np.zeros(max(S - 1, 0), dtype=JOIN_SCORE_DTYPE)
+    breaks = np.zeros(max_segment_size, dtype=np.uint32)
+    support = np.zeros((max(S - 1, 0), max_segment_size), dtype=np.uint32) if want_support else None
+    sm = JoinScoreSummary()
+    rc = L.fseq_join_score_host(m, max_segment_size, S, lb.ctypes.data, rb.ctypes.data, a.ctypes.data, d.ctypes.data, perm.ctypes.data,
+                                junctions.ctypes.data, breaks.ctypes.data, None if support is None else support.ctypes.data, C.byref(sm))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return _join_score_result(junctions, breaks, support, sm)
+
+
+def debug_join_score(of, perm_cls_left, perm_cls_right, want_support=True, device=0):
+    """k_join_score and k_join_score_founders on caller-built class arrays (fseq_debug_join_score): of [S][m] the class of every row
+    in every segment, perm_cls_left / perm_cls_right [S - 1][X] the classes of every slot's two rows at every junction,
+    JOIN_SCORE_GAP a gap.  Returns what join_score returns (rb is 0).  FseqError(FSEQ_E_ARG), before a device is touched, where an
+    input could take a kernel out of bounds or form the empty key."""
+    L = load_library()
+    of = np.ascontiguousarray(np.atleast_2d(of), dtype=np.uint16)
+    cl = np.ascontiguousarray(np.atleast_2d(perm_cls_left), dtype=np.uint16)
+    cr = np.ascontiguousarray(np.atleast_2d(perm_cls_right), dtype=np.uint16)
+    S, m = of.shape
+    if cl.shape != cr.shape or cl.shape[0] != max(S - 1, 0):
+        raise FseqError(FSEQ_E_ARG, "debug_join_score: shapes disagree")
+    X = cl.shape[1]
+    junctions = np.zeros(max(S - 1, 0), dtype=JOIN_SCORE_DTYPE)
+    breaks = np.zeros(X, dtype=np.uint32)
+    support = np.zeros(cl.shape, dtype=np.uint32) if want_support else None
+    sm = JoinScoreSummary()
+    rc = L.fseq_debug_join_score(device, m, X, S, of.ctypes.data, cl.ctypes.data, cr.ctypes.data, junctions.ctypes.data, breaks.ctypes.data,
+                                 None if support is None else support.ctypes.data, C.byref(sm))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return _join_score_result(junctions, breaks, support, sm)
+
+
 class SegmentationContext:
     """Mirror of segmentation_lp_context / segmentation_sp_context behind the C ABI.
 
@@ -1050,6 +1118,29 @@ class SegmentationContext:
         """Which way the last join_random() went: 0 the host joiner, 1 the class tables from the device."""
         path = C.c_int()
         self._check(self.L.fseq_debug_random_path(self.h, C.byref(path)))
+        return path.value
+
+    def join_score(self, permutations, want_support=False):
+        """What a join is worth (fseq_join_score): for permutations [segments, max_segment_size] -- a joiner's or any other, an entry
+        >= m a gap -- {"junctions": a structured array (JOIN_SCORE_DTYPE), one entry per adjacent segment pair; "breaks": per founder
+        slot the junctions at which no input row carries its substrings on both sides; "support": [segments - 1, max_segment_size]
+        with want_support, else None; "summary": a dict}."""
+        S, X = self.result.segment_count, self.result.max_segment_size
+        perm = np.ascontiguousarray(permutations, dtype=np.uint32)
+        if perm.shape != (S, X):
+            raise FseqError(FSEQ_E_ARG, "join_score: permutations are [segments, max_segment_size]")
+        junctions = np.zeros(max(S - 1, 0), dtype=JOIN_SCORE_DTYPE)
+        breaks = np.zeros(X, dtype=np.uint32)
+        support = np.zeros((max(S - 1, 0), X), dtype=np.uint32) if want_support else None
+        sm = JoinScoreSummary()
+        self._check(self.L.fseq_join_score(self.h, perm.ctypes.data, junctions.ctypes.data, breaks.ctypes.data,
+                                           None if support is None else support.ctypes.data, C.byref(sm)))
+        return _join_score_result(junctions, breaks, support, sm)
+
+    def join_score_path(self):
+        """Which way the last join_score() went: 0 the host form, 1 the device form."""
+        path = C.c_int()
+        self._check(self.L.fseq_debug_join_score_path(self.h, C.byref(path)))
         return path.value
 
     def write_founders_device(self, permutations, path):

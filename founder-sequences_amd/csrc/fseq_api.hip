@@ -35,6 +35,7 @@ void fseq::forget_input_history(fseq_ctx *c)
 	c->colmask_ready = false; c->shard_dp_full_sticky = false;
 	c->bip_path = -1;
 	c->rand_path = -1;
+	c->score_path = -1;
 }
 
 // A new input takes this context: every input setter calls this once its arguments are in order and before it touches the

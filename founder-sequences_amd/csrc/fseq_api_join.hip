@@ -4,13 +4,15 @@
 // (bipartite_matcher.cc:17-151, create_segment_texts_task.cc, merge_segments_task.cc) and the random joiner, and the writers
 // of --output-founders / --output-segments (join_context.cc:333-356, segmentation_dp_arg.cc:13-104).  Host C++ as in the
 // reference (fseq_join.hpp), with the greedy joiner's data-parallel front -- class tables and co-occurrence edges -- on the
-// device where the boundary states are (fseq_joinprep.hpp).  A translation unit of its own since round 4: nothing here
+// device where the boundary states are (fseq_joinprep.hpp), and the score of a join (fseq_joinscore.hpp).  A translation unit of its own since round 4: nothing here
 // touches the column kernels, and csrc/fseq_api.hip no longer carries the joiners.
 #include "fseq_ctx.hpp"
 #include "fseq_join.hpp"
 #include "fseq_joinprep.hpp"
 #include "fseq_joinbip.hpp"
 #include "fseq_joinbipw.hpp"
+#include "fseq_joinscore.hpp"
+#include "fseq_joinscore_host.hpp"
 #include "fseq_segfile.hpp"
 #include "fseq_restored_bounds.hpp"
 
@@ -208,6 +210,67 @@ struct ClassTables {
 	}
 	void release() { d_of.release(d_of.c); d_rep.release(d_rep.c); d_size.release(d_size.c); d_count.release(d_count.c); d_start.release(d_start.c); d_lb.release(d_lb.c); d_rb.release(d_rb.c); }
 };
+
+// a junction's record as k_join_score leaves it (JS_FIELDS words)
+static JoinScoreJunction junction_from_words(uint32_t const *w)
+{
+	JoinScoreJunction j;
+	j.supported = w[0]; j.unsupported = w[1]; j.gaps = w[2]; j.rows_through = w[3];
+	j.weight = (uint64_t) w[5] << 32 | w[4];
+	return j;
+}
+
+// what the three entries of the join score hand back: the junctions with their borders rb[p], the breaks, the summary
+static void join_score_outputs(uint32_t m, uint32_t X, uint64_t S, uint64_t const *rb, std::vector<JoinScoreJunction> const &J, uint32_t const *br,
+                               double ms, fseq_join_score_entry *junctions, uint32_t *breaks, fseq_join_score_summary *summary)
+{
+	uint64_t const pairs = S - 1;
+	for (uint64_t p = 0; junctions && p < pairs; ++p)
+		junctions[p] = fseq_join_score_entry{rb[p], J[p].weight, J[p].supported, J[p].unsupported, J[p].gaps, J[p].rows_through};
+	if (breaks) std::copy(br, br + X, breaks);
+	if (summary)
+	{
+		JoinScoreTotals const t = join_score_totals(m, X, pairs, J.data(), br);
+		*summary = fseq_join_score_summary{t.junctions, t.supported, t.unsupported, t.gaps, t.rows_through, t.weight, t.min_junction,
+		                                   t.min_rows_through, t.max_breaks, ms};
+	}
+}
+
+// The device form of fseq_join_score (fseq_joinscore.hpp): J [S - 1], breaks [X], support [(S - 1) x X] or nullptr.
+// *done = false with FSEQ_OK: the caller goes on to the host form (a failed device allocation, implausible class counts),
+// with the error text cleared.
+static int join_score_device(fseq_ctx *c, uint32_t const *permutations, std::vector<JoinScoreJunction> &J, uint32_t *breaks, uint32_t *support, bool *done)
+{
+	*done = false;
+	hipStream_t st = c->stream;
+	size_t const m = c->p.m, S = c->segments.size(), pairs = S - 1;
+	uint32_t const X = c->res.max_segment_size;
+	ClassTables T(c);
+	DevTemp<uint32_t> d_perm(c), d_junc(c), d_sup(c), d_breaks(c);
+	auto no_room = [&](int rc) { if (rc == FSEQ_E_OOM) { c->err.clear(); return (int) FSEQ_OK; } return rc; };      // (the host form needs no device memory)
+	int rc;
+	if ((rc = T.alloc(S, m, X)) || (rc = d_perm.alloc(S * X)) || (rc = d_junc.alloc(pairs * JS_FIELDS)) || (rc = d_sup.alloc(pairs * X)) || (rc = d_breaks.alloc(X)))
+		return no_room(rc);
+	std::vector<uint32_t> count;
+	bool sane = false;
+	if ((rc = T.run(c, count, &sane))) return rc;
+	if (!sane) return FSEQ_OK;                                 // (the host form builds its own classes from the boundary states)
+	JoinScoreArgs A{};
+	A.of_row = T.d_of; A.perm = d_perm; A.m = (uint32_t) m; A.X = X; A.S = (uint32_t) S; A.junctions = d_junc; A.support = d_sup;
+	std::vector<uint32_t> words(pairs * JS_FIELDS);
+	hipError_t e = hipMemcpyAsync(d_perm, permutations, S * X * 4, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = launch_join_score(st, A, d_breaks);
+	if (e == hipSuccess) e = hipMemcpyAsync(words.data(), d_junc, words.size() * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(breaks, d_breaks, (size_t) X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && support) e = hipMemcpyAsync(support, d_sup, pairs * X * 4, hipMemcpyDeviceToHost, st);
+	hipError_t const es = hipStreamSynchronize(st);             // (the host arrays are read and written to here, whatever was queued)
+	if (e == hipSuccess) e = es;
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "join score", e);
+	for (size_t p = 0; p < pairs; ++p) J[p] = junction_from_words(words.data() + p * JS_FIELDS);
+	*done = true;
+	return FSEQ_OK;
+}
 
 static char const SEGFILE_HEADER_BIP[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE\tSEQUENCES\tCOPIED_FROM\n";
 static char const SEGFILE_HEADER_COPIES[] = "SEGMENT\tLB\tRB\tSIZE\tSUBSEQUENCE_NUMBER\tCOPY_NUMBER\tSUBSEQUENCE\n";
@@ -684,6 +747,115 @@ int fseq_random_join_classes_host(uint32_t m, uint32_t max_segment_size, uint64_
 	for (uint64_t s = 0; s < n_segments; ++s)
 		if (count[s] < 1 || count[s] > max_segment_size) return FSEQ_E_ARG;      // (the slots are filled class by class: a table that does not fit them is no table)
 	random_join_classes(max_segment_size, n_segments, count, rep, size, seed, permutations);
+	return FSEQ_OK;
+}
+
+int fseq_debug_join_score_path(fseq_ctx *c, int *path)
+{
+	if (!c || !path) return FSEQ_E_ARG;
+	if (c->score_path < 0) return fail(c, FSEQ_E_ARG, "no fseq_join_score has finished on this context since its input was set");
+	*path = c->score_path;
+	return FSEQ_OK;
+}
+
+// The score of caller-supplied permutations (fseq_joinscore.hpp on the device, fseq_joinscore_host.hpp on the host).  Touches
+// nothing a joiner or a writer left on the context: the temporaries are this call's, the join profile stays the last joiner's.
+int fseq_join_score(fseq_ctx *c, uint32_t const *permutations, fseq_join_score_entry *junctions, uint32_t *breaks, uint32_t *support,
+                    fseq_join_score_summary *summary)
+{
+	if (!c || !permutations) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to score (segmentation failed or was not run)");
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: collect the boundary states (fseq_boundary_state on their owners) and use fseq_join_score_host");
+	(void) hipSetDevice(c->p.device);
+	double const t0 = now_ms();
+	size_t const m = c->p.m, S = c->segments.size();
+	uint32_t const X = c->res.max_segment_size;
+	if (X < 1) return fail(c, FSEQ_E_ARG, "no segments to score");
+	std::vector<JoinScoreJunction> J;
+	std::vector<uint32_t> br;
+	try { J.resize(S - 1); br.resize(X); }
+	catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "join score: the junctions on the host"); }
+	// the device form: what ClassTables serves (tiling segments, 2^31 rows and segments at most) and a table of 64 KiB
+	bool const device = segments_tile(c) && X <= JS_MAX_SLOTS && m <= 0x7FFFFFFFull && S <= 0x7FFFFFFFull && !c->tune.join_host;
+	bool done = device && S < 2;                                 // (one segment: no junction, nothing to launch)
+	if (device && !done)
+		if (int const rc = join_score_device(c, permutations, J, br.data(), support, &done)) return rc;
+	if (!done)
+	{
+		std::vector<uint32_t> A, D;
+		std::vector<uint64_t> lb;
+		try { A.resize(S * m); D.resize(S * m); lb.resize(S); }
+		catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "join score: the boundary states on the host"); }
+		HIP_TRY(c, hipMemcpy(A.data(), c->d_snap_a, S * m * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(c, hipMemcpy(D.data(), c->d_snap_d, S * m * 4, hipMemcpyDeviceToHost));
+		for (size_t s = 0; s < S; ++s) lb[s] = c->segments[s].lb;
+		if (!join_score_host((uint32_t) m, X, S, lb.data(), A.data(), D.data(), permutations, J.data(), br.data(), support))
+			return fail(c, FSEQ_E_HIP, "join score: a boundary state names a row that is none");
+	}
+	std::vector<uint64_t> rb(S);
+	for (size_t s = 0; s < S; ++s) rb[s] = c->segments[s].rb;
+	join_score_outputs((uint32_t) m, X, S, rb.data(), J, br.data(), now_ms() - t0, junctions, breaks, summary);
+	c->score_path = done ? 1 : 0;
+	return FSEQ_OK;
+}
+
+int fseq_join_score_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint64_t const *lb, uint64_t const *rb,
+                         uint32_t const *a, uint32_t const *d, uint32_t const *permutations, fseq_join_score_entry *junctions,
+                         uint32_t *breaks, uint32_t *support, fseq_join_score_summary *summary)
+{
+	if (!m || !max_segment_size || !n_segments || !lb || !rb || !a || !d || !permutations) return FSEQ_E_ARG;
+	double const t0 = now_ms();
+	std::vector<JoinScoreJunction> J(n_segments - 1);
+	std::vector<uint32_t> br(max_segment_size);
+	if (!join_score_host(m, max_segment_size, n_segments, lb, a, d, permutations, J.data(), br.data(), support)) return FSEQ_E_ARG;
+	join_score_outputs(m, max_segment_size, n_segments, rb, J, br.data(), now_ms() - t0, junctions, breaks, summary);
+	return FSEQ_OK;
+}
+
+int fseq_debug_join_score(int device, uint32_t m, uint32_t X, uint32_t S, uint16_t const *of, uint16_t const *perm_cls_left,
+                          uint16_t const *perm_cls_right, fseq_join_score_entry *junctions, uint32_t *breaks, uint32_t *support,
+                          fseq_join_score_summary *summary)
+{
+	// ---- everything an index or a key is formed from, before the first HIP call
+	if (!of || !perm_cls_left || !perm_cls_right) return FSEQ_E_ARG;
+	if (!m || m > 0x7FFFFFFFu || !X || X > JS_MAX_SLOTS || S < 2u || S > 65536u) return FSEQ_E_ARG;
+	for (size_t i = 0; i < (size_t) S * m; ++i)
+		if (of[i] >= JS_GAP) return FSEQ_E_ARG;
+	double const t0 = now_ms();
+	size_t const pairs = S - 1u, slots = pairs * X;
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	struct Held {
+		std::vector<void *> held;
+		~Held() { for (void *p : held) (void) hipFree(p); }
+		void *get(size_t bytes, void const *from)
+		{
+			void *p = nullptr;
+			if (hipMalloc(&p, std::max<size_t>(bytes, 4)) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
+			held.push_back(p);
+			if (from && hipMemcpy(p, from, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+			return p;
+		}
+	} B;
+	JoinScoreArgs A{};
+	A.of_row = static_cast<uint16_t const *>(B.get((size_t) S * m * 2, of));
+	A.cls_left = static_cast<uint16_t const *>(B.get(slots * 2, perm_cls_left));
+	A.cls_right = static_cast<uint16_t const *>(B.get(slots * 2, perm_cls_right));
+	A.m = m; A.X = X; A.S = S;
+	A.junctions = static_cast<uint32_t *>(B.get(pairs * JS_FIELDS * 4, nullptr));
+	A.support = static_cast<uint32_t *>(B.get(slots * 4, nullptr));
+	uint32_t *d_breaks = static_cast<uint32_t *>(B.get((size_t) X * 4, nullptr));
+	if (!A.of_row || !A.cls_left || !A.cls_right || !A.junctions || !A.support || !d_breaks) return FSEQ_E_OOM;
+	if (launch_join_score(0, A, d_breaks) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
+	std::vector<uint32_t> words(pairs * JS_FIELDS), br(X);
+	if (hipMemcpy(words.data(), A.junctions, words.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+	    hipMemcpy(br.data(), d_breaks, (size_t) X * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+	    (support && hipMemcpy(support, A.support, slots * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
+	std::vector<JoinScoreJunction> J(pairs);
+	for (size_t p = 0; p < pairs; ++p) J[p] = junction_from_words(words.data() + p * JS_FIELDS);
+	std::vector<uint64_t> rb(S, 0);
+	join_score_outputs(m, X, S, rb.data(), J, br.data(), now_ms() - t0, junctions, breaks, summary);
 	return FSEQ_OK;
 }
 

@@ -120,7 +120,7 @@ struct Tuning {
 	bool ss_unpacked = false;            // FSEQ_SS_UNPACKED: 8-byte stride states in the streamed regime
 	bool ss_absolute = false;            // FSEQ_SS_ABSOLUTE: stride states hold divergences and pass 2 runs the first form's tile step (the form before round 4)
 	bool poison_lists = false;           // FSEQ_POISON_LISTS: lists and headers filled with 0xFF before phase C
-	bool join_host = false;              // FSEQ_JOIN_HOST: the greedy joiner's class tables and edges on the host
+	bool join_host = false;              // FSEQ_JOIN_HOST: the joiners' class tables and edges, and the join score, on the host
 	bool join_wide = false;              // FSEQ_JOIN_WIDE: ... through the wide device front (strips of left classes) at any max_segment_size; FSEQ_JOIN_HOST wins
 	bool join_bip_wide = false;          // FSEQ_JOIN_BIP_WIDE: fseq_join_bipartite through the wide device form (weights in slabs of device memory) at any max_segment_size up to 4,096; FSEQ_JOIN_HOST wins
 	int  join_bip_slabs = 0;             // FSEQ_JOIN_BIP_SLABS: most slabs (= persistent workgroups) of the wide form (by itself: from the CU count and the memory)
@@ -307,6 +307,7 @@ struct fseq_ctx {
 	int join_path = -1;                      // the last fseq_join_greedy (fseq_debug_join_path): 0 host, 1 the LDS front, 2 the wide front; -1: none yet
 	int bip_path = -1;                       // the last fseq_join_bipartite since the input was set (fseq_debug_bipartite_path): 0 host, 1 the LDS form, 2 the wide form; -1: none yet
 	int rand_path = -1;                      // the last fseq_join_random since the input was set (fseq_debug_random_path): 0 host, 1 the class tables from the device; -1: none yet
+	int score_path = -1;                     // the last fseq_join_score since the input was set (fseq_debug_join_score_path): 0 host, 1 the device form; -1: none yet
 	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device or fseq_write_segments_restored (fseq_debug_segments_file)
 	fseq_progress_fn progress_fn = nullptr;
 	void *progress_user = nullptr;

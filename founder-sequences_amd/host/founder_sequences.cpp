@@ -71,6 +71,10 @@ char const *const USAGE =
 	"                                     of LIST, of the input's full length\n"
 	"\nAlgorithm parameters:\n"
 	"  -s, --segment-length-bound=SIZE    Segment length bound\n"
+	"      --output-join-score=PATH       Score the join on the device and write, per border between two segments, how many founders\n"
+	"                                     continue a substring that some sequence continues too, and per founder its breaks\n"
+	"                                     (every joining method; works under --upload-memory, --hold-out and\n"
+	"                                     --remove-identity-columns, there in reduced co-ordinates as --output-segments; one GPU only)\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
 	"      --scan-segment-lengths=SPEC    Before anything else, write the maximum segment size at every segment length bound of SPEC --\n"
 	"                                     a comma list of lengths, or LO:HI:STEP -- as a table (SEGMENT_LENGTH, MAX_SEGMENT_SIZE; one line\n"
@@ -312,6 +316,32 @@ bool parse_scan_spec(char const *spec, std::vector<uint64_t> &out)
 	return true;
 }
 
+// --output-join-score: fseq_join_score on the permutations just made.  Tab-separated: a '#' line with the summary, one line per
+// junction, a blank line, one line per founder.
+bool write_join_score(fseq_ctx *ctx, fseq_result const &res, std::vector<uint32_t> const &perm, char const *path)
+{
+	size_t const pairs = res.segment_count ? (size_t) res.segment_count - 1 : 0;
+	std::vector<fseq_join_score_entry> junctions(pairs);
+	std::vector<uint32_t> breaks(res.max_segment_size);
+	fseq_join_score_summary sm{};
+	if (FSEQ_OK != fseq_join_score(ctx, perm.data(), junctions.data(), breaks.data(), nullptr, &sm)) { std::cerr << fseq_last_error(ctx) << std::endl; return false; }
+	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+	if (!f) { std::cerr << "Unable to open the join score output file." << std::endl; return false; }
+	fprintf(f, "# JUNCTIONS=%llu\tSUPPORTED=%llu\tUNSUPPORTED=%llu\tGAPS=%llu\tROWS_THROUGH=%llu\tWEIGHT=%llu\tMIN_ROWS_THROUGH=%u\tMIN_ROWS_THROUGH_JUNCTION=%llu\tMAX_BREAKS=%u\n",
+	        (unsigned long long) sm.junctions, (unsigned long long) sm.supported, (unsigned long long) sm.unsupported, (unsigned long long) sm.gaps,
+	        (unsigned long long) sm.rows_through, (unsigned long long) sm.weight, sm.min_rows_through, (unsigned long long) sm.min_rows_through_junction, sm.max_breaks);
+	fputs("JUNCTION\tRB\tSUPPORTED\tUNSUPPORTED\tGAPS\tROWS_THROUGH\tWEIGHT\n", f);
+	for (size_t p = 0; p < pairs; ++p)
+		fprintf(f, "%zu\t%llu\t%u\t%u\t%u\t%u\t%llu\n", p, (unsigned long long) junctions[p].rb, junctions[p].supported, junctions[p].unsupported, junctions[p].gaps,
+		        junctions[p].rows_through, (unsigned long long) junctions[p].weight);
+	fputs("\nFOUNDER\tBREAKS\n", f);
+	for (size_t r = 0; r < breaks.size(); ++r) fprintf(f, "%zu\t%u\n", r, breaks[r]);
+	bool ok = !ferror(f) && 0 == fflush(f);
+	if (f != stdout && 0 != fclose(f)) ok = false;
+	if (!ok) std::cerr << "Writing the join score output file failed." << std::endl;
+	return ok;
+}
+
 // --hold-out=LIST: a comma list of 0-based sequence indices and of LO:HI ranges, both ends included, in the order given.  false,
 // with the reason in why, where LIST is malformed or names an index twice (whether the indices are below the sequence count is
 // the caller's check, once the input is read)
@@ -355,7 +385,7 @@ int main(int argc, char **argv)
 	char const *hold_out_spec = nullptr, *out_held_matches = nullptr, *out_held_restored = nullptr, *out_seq_restored = nullptr;
 	std::vector<uint32_t> held_rows;
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr, *out_restored_segments = nullptr;
-	char const *match_seqs = nullptr, *out_seq_matches = nullptr;
+	char const *match_seqs = nullptr, *out_seq_matches = nullptr, *out_join_score = nullptr;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
 	bool match_min_len_bad = false;
@@ -390,6 +420,7 @@ int main(int argc, char **argv)
 		{"hold-out", required_argument, nullptr, 1016}, {"output-held-out-matches", required_argument, nullptr, 1017},
 		{"output-held-out-restored-matches", required_argument, nullptr, 1018}, {"output-sequence-restored-matches", required_argument, nullptr, 1019},
 		{"output-restored-segments", required_argument, nullptr, 1020}, {"reduce-on-upload", no_argument, nullptr, 1021},
+		{"output-join-score", required_argument, nullptr, 1022},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -439,6 +470,7 @@ int main(int argc, char **argv)
 			case 1007: remove_identity = true; break;
 			case 1008: out_identity = optarg; remove_identity = true; break;
 			case 1009: out_restored_matches = optarg; break;
+			case 1022: out_join_score = optarg; break;
 			case 1010:
 			{
 				// as --list-memory, but a positive number: 0 MiB hold no chunk
@@ -515,6 +547,7 @@ int main(int argc, char **argv)
 	if (out_held_restored && !(hold_out_spec && remove_identity)) { std::cerr << "--output-held-out-restored-matches requires --hold-out and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
 	// (the two combine with --remove-identity-columns only for the restored match; the reports in reduced co-ordinates stay refused)
 	if (match_seqs && remove_identity && (!out_seq_restored || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	if (out_join_score && gpus > 1) { std::cerr << "--output-join-score is not supported together with --gpus > 1 (a rank holds its own boundary states only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && gpus > 1) { std::cerr << "--output-restored-segments is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && !remove_identity) { std::cerr << "--output-restored-segments requires --remove-identity-columns (without it --output-segments is in the input's co-ordinates already)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
@@ -786,6 +819,11 @@ int main(int argc, char **argv)
 			std::cerr << "--output-restored-segments needs the segments of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_join_score)
+		{
+			std::cerr << "--output-join-score needs the permutations of a segmentation; the sequences are shorter than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_restored_matches)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
@@ -879,6 +917,12 @@ int main(int argc, char **argv)
 			rc = sharded ? fseq_write_segments_host(ctx, rows.data(), how, all_a.data(), all_d.data(), out_segments)
 			             : fseq_write_segments(ctx, rows.data(), how, out_segments);
 		if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	}
+	if (out_join_score)
+	{
+		// what the join is worth, from the context alone (no rows on the host): in the co-ordinates --output-segments has
+		std::cerr << "Scoring the join…" << std::endl;
+		if (!write_join_score(ctx, res, perm, out_join_score)) return EXIT_FAILURE;
 	}
 	if (out_restored_segments)
 	{

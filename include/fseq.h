@@ -300,6 +300,48 @@ int  fseq_random_join_host(uint32_t m, uint32_t max_segment_size, uint64_t n_seg
  * FSEQ_E_ARG: a null pointer, m or max_segment_size 0, a count outside [1, max_segment_size]. */
 int  fseq_random_join_classes_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint32_t const *count, uint32_t const *rep,
                                    uint32_t const *size, uint32_t seed, uint32_t *permutations);
+/* ---- what a join is worth: junction support per adjacent segment pair and founder slot (no counterpart in the reference) ----
+ * A finished run has S merged segments that tile the columns; X is max_segment_size; permutations is [S][X], an entry < m the
+ * input row whose substring the founder of that slot takes in that segment, an entry >= m a gap (fseq_write_founders_device
+ * prints '-').  cls_s(i) is the class of row i in segment s: two rows are in one class iff they agree on [lb_s, rb_s).  At the
+ * junction p = (s, s + 1) slot r has L = permutations[s][r] and R = permutations[s + 1][r], and
+ *   support[p][r] = the rows i with cls_s(i) = cls_s(L) and cls_{s+1}(i) = cls_{s+1}(R); 0 where L or R is a gap
+ * -- the input rows that carry the founder's substring on both sides of the border, the quantity every joiner works on.
+ * A junction's entry: supported -- slots with support > 0; unsupported -- slots with support 0 that are no gaps; gaps -- slots
+ * where L or R is a gap (the three add up to X); weight -- the sum of support over the slots; rows_through -- the rows i for
+ * which some slot has (cls_s(L), cls_{s+1}(R)) = (cls_s(i), cls_{s+1}(i)): the rows that can cross the junction without
+ * changing founder, a pair of classes that several slots share counted once; rb -- the border's column, rb_s.
+ * breaks[r]: the junctions at which slot r is unsupported.  The summary: the totals of the five fields over the junctions, the
+ * smallest rows_through and the first junction it is at (m and 0 where S = 1), the largest breaks, and the call's wall time. */
+typedef struct {
+	uint64_t rb;
+	uint64_t weight;
+	uint32_t supported, unsupported, gaps, rows_through;
+} fseq_join_score_entry;
+typedef struct {
+	uint64_t junctions;                     /* S - 1 */
+	uint64_t supported, unsupported, gaps, rows_through, weight;
+	uint64_t min_rows_through_junction;
+	uint32_t min_rows_through, max_breaks;
+	double   ms_device;
+} fseq_join_score_summary;
+/* The score of any permutations -- a joiner's or the caller's own -- on the context of a finished run.  junctions [S - 1],
+ * breaks [X], support [(S - 1) x X] and summary may each be NULL.  While the merged segments tile the columns, X <= 4,096,
+ * m and S < 2^31 and FSEQ_JOIN_HOST is not set, the score is computed where the boundary states are (csrc/fseq_joinscore.hpp):
+ * the class tables of k_join_classes_wide, then one workgroup per junction with the slots' class pairs in an LDS table and
+ * one pass over the rows' classes; permutations go to the device (S x X x 4 bytes), the results come back.  Everything else --
+ * X > 4,096, a failed device allocation, class counts outside [1, X] read back -- copies every boundary state and runs the
+ * host form below, with the same results entry for entry (fseq_debug_join_score_path, fseq_debug.h, tells which ran).
+ * FSEQ_E_ARG: no permutations, no finished run; FSEQ_E_UNSUPPORTED: a sharded context (collect the boundary states and use
+ * fseq_join_score_host).  Existing results and buffers of the context are left as they are. */
+int  fseq_join_score(fseq_ctx *ctx, uint32_t const *permutations, fseq_join_score_entry *junctions, uint32_t *breaks, uint32_t *support,
+                     fseq_join_score_summary *summary);
+/* The same on caller-supplied boundary states (no context, no device), the arguments of fseq_greedy_match_host and the
+ * permutations: classes by the rule of the joiners' host forms (a pBWT position i starts a class iff i = 0 or d[i] > lb).
+ * Any max_segment_size.  FSEQ_E_ARG: a NULL input, m or max_segment_size 0, no segment, an entry of a that is no row. */
+int  fseq_join_score_host(uint32_t m, uint32_t max_segment_size, uint64_t n_segments, uint64_t const *lb, uint64_t const *rb,
+                          uint32_t const *a, uint32_t const *d, uint32_t const *permutations, fseq_join_score_entry *junctions,
+                          uint32_t *breaks, uint32_t *support, fseq_join_score_summary *summary);
 /* replaces: join_context::output_segments -> output_segments (segmentation_dp_arg.cc:13-104): the
  * --output-segments text file for the given joining method (greedy: the header line only, SURVEY.md
  * F5; bipartite: one line per segment text; random: one line per distinct substring with its copy

@@ -120,6 +120,21 @@ int  fseq_debug_red_cls_direct(uint32_t m, uint32_t B, uint32_t bits, uint64_t c
  * tables from the device.  FSEQ_E_ARG while none has finished. */
 int  fseq_debug_random_path(fseq_ctx *ctx, int *path);
 
+/* Which way the last fseq_join_score since the input was set went: 0 the host form (every boundary state copied), 1 the device
+ * form.  FSEQ_E_ARG while none has finished. */
+int  fseq_debug_join_score_path(fseq_ctx *ctx, int *path);
+
+/* k_join_score and k_join_score_founders (csrc/fseq_joinscore.hpp) on caller-built class arrays, through the launcher
+ * fseq_join_score itself uses (debug / tests; needs no context): of[S][m] the class of every row in every segment;
+ * perm_cls_left / perm_cls_right [S - 1][X] the classes of every slot's left and right row at every junction, 0xFFFF a gap.
+ * Out, each may be NULL: junctions [S - 1] (rb is 0), breaks [X], support [(S - 1) x X], summary.  Everything an index or a key
+ * is formed from is checked on the host before the first call of the runtime, FSEQ_E_ARG otherwise: the three arrays given;
+ * 1 <= m < 2^31; 1 <= X <= 4,096; 2 <= S <= 65,536; every class in of below 0xFFFF (a slot's class may be any value: one that
+ * no row has finds no row). */
+int  fseq_debug_join_score(int device, uint32_t m, uint32_t X, uint32_t S, uint16_t const *of, uint16_t const *perm_cls_left,
+                           uint16_t const *perm_cls_right, fseq_join_score_entry *junctions, uint32_t *breaks, uint32_t *support,
+                           fseq_join_score_summary *summary);
+
 /* The bounds of merged segments in the source's co-ordinates (restored_segment_bounds, csrc/fseq_restored_bounds.hpp), as
  * fseq_get_segments_restored and fseq_write_segments_restored apply them -- host arithmetic, no device, no context.  kept[n]: the
  * source column of every kept column; lb / rb [n_segments]: the merged segments in kept columns.  Out: src_lb / src_rb
