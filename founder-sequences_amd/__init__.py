@@ -95,6 +95,14 @@ class JoinScoreSummary(C.Structure):
                 ("ms_device", C.c_double)]
 
 
+class GraphSummary(C.Structure):
+    _fields_ = [("segments", C.c_uint64), ("nodes", C.c_uint64), ("edges", C.c_uint64), ("ms_device", C.c_double)]
+
+
+class GraphFileStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64 * 3), ("lines", C.c_uint64 * 3), ("bytes", C.c_uint64 * 3)]
+
+
 class DpListsInfo(C.Structure):
     _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
 
@@ -113,6 +121,11 @@ SCAN_LISTS_BUILT, SCAN_LISTS_FOLDED, SCAN_LISTS_NONE = 0, 1, 2
 JOIN_SCORE_DTYPE = np.dtype([("rb", "<u8"), ("weight", "<u8"), ("supported", "<u4"), ("unsupported", "<u4"), ("gaps", "<u4"), ("rows_through", "<u4")])
 JOIN_SCORE_MAX_SLOTS = 4096    # csrc/fseq_joinscore.hpp, JS_MAX_SLOTS: the device form's cap on max_segment_size
 JOIN_SCORE_GAP = 0xFFFF        # ... JS_GAP: a slot's class where its row is a gap (debug_join_score)
+
+# fseq_graph_node (include/fseq.h), 32 bytes, and fseq_graph_edge, 16 bytes
+GRAPH_NODE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("segment", "<u4"), ("cls", "<u4"), ("rep_row", "<u4"), ("rows", "<u4")])
+GRAPH_EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("rows", "<u4"), ("junction", "<u4")])
+GRAPH_PATHS = 1                # fseq_write_block_graph's flag: the P lines
 
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
@@ -147,6 +160,7 @@ EXPORTS = [
     "fseq_input_scan_identity", "fseq_input_reduce", "fseq_input_kept_columns", "fseq_input_columns_kept", "fseq_input_end_kept",
     "fseq_set_rows_streamed_without_identity_columns", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
     "fseq_join_score", "fseq_join_score_host", "fseq_debug_join_score_path", "fseq_debug_join_score",
+    "fseq_block_graph", "fseq_write_block_graph", "fseq_debug_graph_file",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -155,7 +169,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
-                 "fseq_debug_join_score_path", "fseq_debug_join_score"]
+                 "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -304,6 +318,9 @@ def load_library():
     L.fseq_join_score_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(JoinScoreSummary)]
     L.fseq_debug_join_score_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_join_score.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.POINTER(JoinScoreSummary)]
+    L.fseq_block_graph.argtypes = [vp, vp, vp, vp, C.POINTER(GraphSummary)]
+    L.fseq_write_block_graph.argtypes = [vp, C.c_uint32, C.c_int, C.c_char_p]
+    L.fseq_debug_graph_file.argtypes = [vp, C.POINTER(GraphFileStats)]
     _lib = L
     return L
 
@@ -1142,6 +1159,35 @@ class SegmentationContext:
         path = C.c_int()
         self._check(self.L.fseq_debug_join_score_path(self.h, C.byref(path)))
         return path.value
+
+    def block_graph(self, want_row_nodes=False):
+        """The founder block graph of the finished run (fseq_block_graph): {"nodes": a structured array (GRAPH_NODE_DTYPE), one
+        entry per class of every merged segment, in id order; "edges": a structured array (GRAPH_EDGE_DTYPE), one entry per pair
+        of classes of adjacent segments that some row carries, by junction, then (from, to) ascending; "row_nodes": [segments, m],
+        the node of every row in every segment, with want_row_nodes, else None; "summary": a dict}."""
+        sm = GraphSummary()
+        self._check(self.L.fseq_block_graph(self.h, None, None, None, C.byref(sm)))
+        nodes = np.zeros(sm.nodes, dtype=GRAPH_NODE_DTYPE)
+        edges = np.zeros(sm.edges, dtype=GRAPH_EDGE_DTYPE)
+        row_nodes = np.zeros((sm.segments, self.m), dtype=np.uint32) if want_row_nodes else None
+        self._check(self.L.fseq_block_graph(self.h, nodes.ctypes.data, edges.ctypes.data, None if row_nodes is None else row_nodes.ctypes.data, C.byref(sm)))
+        return {"nodes": nodes, "edges": edges, "row_nodes": row_nodes,
+                "summary": {"segments": sm.segments, "nodes": sm.nodes, "edges": sm.edges, "ms_device": sm.ms_device}}
+
+    def write_block_graph(self, path, paths=False, gap=b"-"):
+        """The founder block graph as a GFA 1.0 file, written from the device (fseq_write_block_graph): S lines with the classes'
+        substrings without the byte `gap` (None or b"": every byte stays), L lines with the rows two classes share, and with
+        paths a P line per input row.  path None or "-": stdout."""
+        if gap is not None and len(gap) > 1:
+            raise FseqError(FSEQ_E_ARG, "write_block_graph: the gap is one byte, or None")
+        self._check(self.L.fseq_write_block_graph(self.h, GRAPH_PATHS if paths else 0, gap[0] if gap else -1, path.encode() if path else None))
+
+    def graph_file_stats(self):
+        """The last file write_block_graph wrote, by section: {"nodes" / "links" / "paths": {batches, lines, bytes}} (a line with its
+        newline; the header line, 11 bytes, is in no section)."""
+        st = GraphFileStats()
+        self._check(self.L.fseq_debug_graph_file(self.h, C.byref(st)))
+        return {name: {"batches": st.batches[k], "lines": st.lines[k], "bytes": st.bytes[k]} for k, name in enumerate(("nodes", "links", "paths"))}
 
     def write_founders_device(self, permutations, path):
         """--output-founders from the alignment resident on the device (no host rows)."""

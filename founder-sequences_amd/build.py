@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # translation units of the library: the ABI's entry points, the segmentation path by phase (csrc/fseq_path.hpp lists what each holds),
-# the joiners / writers, the matcher, the identity columns, the split along the rows, the chunked input, and the kernel configurations
+# the joiners / writers, the block graph, the matcher, the identity columns, the split along the rows, the chunked input, and the kernel configurations
 SRCS = [os.path.join(HERE, "csrc", name) for name in (
     "fseq_api.hip",
     "fseq_api_debug.hip",
@@ -17,6 +17,7 @@ SRCS = [os.path.join(HERE, "csrc", name) for name in (
     "fseq_path_pass2.hip",
     "fseq_lengthscan.hip",
     "fseq_api_join.hip",
+    "fseq_api_graph.hip",
     "fseq_api_match.hip",
     "fseq_api_identity.hip",
     "fseq_api_rowsplit.hip",

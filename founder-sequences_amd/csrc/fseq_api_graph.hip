@@ -1,0 +1,331 @@
+// fseq_api_graph.hip -- the part of the C ABI (include/fseq.h) behind the founder block graph: fseq_block_graph (the graph as
+// arrays), fseq_write_block_graph (the GFA 1.0 file from the device, csrc/fseq_graph.hpp) and fseq_debug_graph_file.
+//
+// No counterpart in the reference.  Both entries build on the device front of fseq_join_greedy (fseq_joinprep.hpp, unchanged):
+// k_join_classes_wide numbers the classes of every merged segment, k_join_edges_wide<false> / k_join_scan / <true> leave the
+// weighted edges of every adjacent pair in ascending (l, r) order.  Everything here is a temporary of one call: nothing a run, a
+// joiner, a writer or a match left on the context is touched, and nothing is allocated or launched unless one of the entries is
+// called.  There is no host form: what the device form does not serve is refused.
+#include "fseq_ctx.hpp"
+#include "fseq_joinprep.hpp"
+#include "fseq_graph.hpp"
+
+using namespace fseq;
+
+static constexpr uint64_t GRAPH_BATCH_BYTES = 256ull << 20;      // (what fseq_write_segments_device takes a batch)
+static char const GRAPH_HEADER[] = "H\tVN:Z:1.0\n";
+
+// The class tables of every merged segment and the edges of every adjacent pair, on the device, with the counts on the host.
+struct GraphTables {
+	fseq_ctx *c;
+	size_t S = 0, m = 0;
+	uint32_t X = 0, pairs = 0;
+	DevTemp<uint16_t> d_of;
+	DevTemp<uint32_t> d_rep, d_size, d_count, d_start, d_off, d_ne, d_noff;
+	DevTemp<uint64_t> d_lb, d_rb;
+	DevTemp<unsigned long long> d_total;
+	DevTemp<uint2> d_edges;
+	std::vector<uint32_t> count, noff;       // [S], [S + 1]
+	uint64_t nodes = 0, edges = 0;
+	explicit GraphTables(fseq_ctx *c_) : c(c_), d_of(c_), d_rep(c_), d_size(c_), d_count(c_), d_start(c_), d_off(c_), d_ne(c_), d_noff(c_), d_lb(c_), d_rb(c_), d_total(c_), d_edges(c_) {}
+
+	// write_edges: the edges themselves (else their number only)
+	int build(bool write_edges)
+	{
+		S = c->segments.size(); m = c->p.m; X = c->res.max_segment_size; pairs = (uint32_t) (S - 1);
+		hipStream_t st = c->stream;
+		int rc;
+		if ((rc = d_of.alloc(S * m)) || (rc = d_rep.alloc(S * X)) || (rc = d_size.alloc(S * X)) || (rc = d_count.alloc(S)) ||
+		    (rc = d_start.alloc(S * ((size_t) X + 1))) || (rc = d_off.alloc(S)) || (rc = d_ne.alloc(S)) || (rc = d_noff.alloc(S + 1)) ||
+		    (rc = d_lb.alloc(S)) || (rc = d_rb.alloc(S)) || (rc = d_total.alloc(1)))
+			return rc;
+		std::vector<uint64_t> b;
+		try { b.resize(2 * S); count.resize(S); noff.resize(S + 1); }
+		catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "block graph: the segments on the host"); }
+		for (size_t i = 0; i < S; ++i) { b[i] = c->segments[i].lb; b[S + i] = c->segments[i].rb; }
+		size_t const lds = (size_t) JW_CELLS * 4;
+		hipError_t e = hipMemcpyAsync(d_lb, b.data(), S * 8, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(d_rb, b.data() + S, S * 8, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, S * X * 4, st);
+		if (e == hipSuccess) e = allow_lds(k_join_edges_wide<false>, lds);
+		if (e == hipSuccess) e = allow_lds(k_join_edges_wide<true>, lds);
+		if (e != hipSuccess) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_HIP, "block graph: class tables", e); }
+		hipLaunchKernelGGL(k_join_classes_wide, dim3((uint32_t) S), dim3(JW_T), 0, st, c->d_snap_a, c->d_snap_d, d_rb, (uint32_t) m, X, d_of, d_rep, d_size, d_count, d_start);
+		if (pairs)
+			hipLaunchKernelGGL(k_join_edges_wide<false>, dim3(pairs), dim3(JW_T), lds, st, c->d_snap_a, d_of, d_count, d_start, (uint32_t) m, X, d_ne, d_off, (uint2 *) nullptr, (uint64_t) 0);
+		hipLaunchKernelGGL(k_join_scan, dim3(1), dim3(JW_T), 0, st, d_ne, pairs, d_off, d_total);
+		unsigned long long total = 0;
+		e = hipMemcpyAsync(count.data(), d_count, S * 4, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st);
+		hipError_t const es = hipStreamSynchronize(st);              // (b, count and total are read and written to here, whatever was queued)
+		if (e == hipSuccess) e = es;
+		if (e == hipSuccess) e = hipGetLastError();
+		if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "block graph: class tables", e);
+		nodes = 0;
+		for (size_t i = 0; i < S; ++i)
+		{
+			if (count[i] < 1 || count[i] > X) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: the class tables of the device hold a class count outside [1, max_segment_size]");
+			if (i && count[i] > JW_CELLS) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: a right segment of more than 32,768 classes (the edge kernel reports no edges for it)");
+			noff[i] = (uint32_t) nodes;
+			nodes += count[i];
+			if (nodes > 0xFFFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: 2^32 nodes or more");
+		}
+		noff[S] = (uint32_t) nodes;
+		edges = total;
+		if (edges > 0xFFFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: 2^32 edges or more");
+		HIP_TRY(c, hipMemcpyAsync(d_noff, noff.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));      // (noff lives as long as the tables: every caller synchronises before it lets go of them)
+		if (write_edges && pairs && edges)
+		{
+			if ((rc = d_edges.alloc((size_t) edges))) { (void) hipStreamSynchronize(st); return rc; }
+			hipLaunchKernelGGL(k_join_edges_wide<true>, dim3(pairs), dim3(JW_T), lds, st, c->d_snap_a, d_of, d_count, d_start, (uint32_t) m, X, d_ne, d_off, (uint2 *) d_edges, (uint64_t) edges);
+		}
+		return FSEQ_OK;
+	}
+
+	GraphArgs args(int gap) const
+	{
+		GraphArgs A{};
+		A.seg_lb = d_lb; A.seg_rb = d_rb; A.count = d_count; A.rep = d_rep; A.size = d_size; A.noff = d_noff; A.of_row = d_of;
+		A.m = (uint32_t) m; A.X = X; A.S = (uint32_t) S; A.gap = gap < 0 ? -1 : gap;
+		A.msa = c->d_msa; A.ld = c->ld; A.bsh = c->bsh;
+		A.edges = d_edges; A.offset = d_off; A.pairs = pairs; A.n_edges = d_edges.base ? edges : 0u;
+		return A;
+	}
+};
+
+// what both entries refuse of a context before a device is touched
+static int graph_refusals(fseq_ctx *c)
+{
+	if (int const rc = need_result(c)) return rc;
+	if (c->segments.empty()) return fail(c, FSEQ_E_ARG, "no segments to build the block graph from (segmentation failed or was not run)");
+	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "sharded run: a rank holds its own columns and boundary states only (the block graph needs them all on one device)");
+	for (size_t i = 0; i < c->segments.size(); ++i)
+		if (c->segments[i].lb != (i ? c->segments[i - 1].rb : 0u)) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: the merged segments do not tile the columns");
+	uint32_t const X = c->res.max_segment_size;
+	if (X < 1) return fail(c, FSEQ_E_ARG, "no segments to build the block graph from");
+	if (X > 0xFFFFu) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: more than 65,535 classes a segment");
+	if (c->p.m > 0x7FFFFFFFull || c->segments.size() > 0x7FFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: 2^31 rows or segments or more");
+	return FSEQ_OK;
+}
+
+extern "C" {
+
+int fseq_block_graph(fseq_ctx *c, fseq_graph_node *nodes, fseq_graph_edge *edges, uint32_t *row_nodes, fseq_graph_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (int const rc = graph_refusals(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	double const t0 = now_ms();
+	hipStream_t st = c->stream;
+	GraphTables T(c);
+	if (int const rc = T.build(edges != nullptr)) return rc;
+	size_t const S = T.S, m = T.m;
+	uint32_t const X = T.X;
+	hipError_t e = hipSuccess;
+	std::vector<uint32_t> rep, size, off, ne;
+	std::vector<uint2> ew;
+	try
+	{
+		if (nodes) { rep.resize(S * X); size.resize(S * X); }
+		if (edges) { off.resize(S); ne.resize(S); ew.resize((size_t) T.edges); }
+	}
+	catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "block graph: the tables on the host"); }
+	DevTemp<uint32_t> d_rown(c);
+	if (row_nodes)
+	{
+		if (int const rc = d_rown.alloc(S * m)) { (void) hipStreamSynchronize(st); return rc; }
+		uint32_t const tiles = (uint32_t) std::min<size_t>((m + GR_T - 1) / GR_T, 1024);
+		hipLaunchKernelGGL(k_graph_row_nodes, dim3((uint32_t) S, tiles), dim3(GR_T), 0, st, T.args(-1), (uint32_t *) d_rown);
+		e = hipMemcpyAsync(row_nodes, d_rown, S * m * 4, hipMemcpyDeviceToHost, st);
+	}
+	if (e == hipSuccess && nodes) e = hipMemcpyAsync(rep.data(), T.d_rep, S * X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && nodes) e = hipMemcpyAsync(size.data(), T.d_size, S * X * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && edges && T.pairs) e = hipMemcpyAsync(off.data(), T.d_off, (size_t) T.pairs * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && edges && T.pairs) e = hipMemcpyAsync(ne.data(), T.d_ne, (size_t) T.pairs * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && edges && T.edges) e = hipMemcpyAsync(ew.data(), T.d_edges, (size_t) T.edges * 8, hipMemcpyDeviceToHost, st);
+	hipError_t const es = hipStreamSynchronize(st);                  // (the host arrays are written to here, whatever was queued)
+	if (e == hipSuccess) e = es;
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "block graph", e);
+	if (nodes)
+		for (size_t s = 0; s < S; ++s)
+			for (uint32_t j = 0; j < T.count[s]; ++j)
+				nodes[(size_t) T.noff[s] + j] = fseq_graph_node{c->segments[s].lb, c->segments[s].rb, (uint32_t) s, j, rep[s * X + j], size[s * X + j]};
+	if (edges)
+		for (size_t p = 0; p < T.pairs; ++p)
+		{
+			if ((uint64_t) off[p] + ne[p] > T.edges) return fail(c, FSEQ_E_HIP, "block graph: an edge offset past the edges");
+			for (uint32_t k = 0; k < ne[p]; ++k)
+			{
+				uint2 const w = ew[(size_t) off[p] + k];
+				edges[(size_t) off[p] + k] = fseq_graph_edge{T.noff[p] + (w.x >> 16), T.noff[p + 1] + (w.x & 0xFFFFu), w.y, (uint32_t) p};
+			}
+		}
+	if (summary) *summary = fseq_graph_summary{(uint64_t) S, T.nodes, T.edges, now_ms() - t0};
+	return FSEQ_OK;
+}
+
+int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const *path)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (flags & ~(uint32_t) FSEQ_GRAPH_PATHS) return fail(c, FSEQ_E_ARG, "block graph file: unknown flag bits (FSEQ_GRAPH_PATHS)");
+	if (gap_byte > 255) return fail(c, FSEQ_E_ARG, "block graph file: the gap byte is a byte (0 .. 255) or negative for none");
+	if (int const rc = graph_refusals(c)) return rc;
+	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
+	(void) hipSetDevice(c->p.device);
+	hipStream_t st = c->stream;
+	bool const paths = (flags & FSEQ_GRAPH_PATHS) != 0;
+	GraphTables T(c);
+	if (int const rc = T.build(true)) return rc;
+	T.d_start.release(c);                                            // (the edge kernel's: not needed from here on)
+	size_t const S = T.S, m = T.m;
+	uint32_t const X = T.X;
+	size_t const X1 = (size_t) X + 1;
+	uint64_t const E = T.d_edges.base ? T.edges : 0u;
+	size_t const nb = (size_t) ((E + GR_T - 1) / GR_T);              // workgroups of the links
+	DevTemp<uint8_t> d_lut(c), d_out(c);
+	DevTemp<uint32_t> d_lab(c), d_lens(c);
+	DevTemp<uint64_t> d_loff(c), d_segoff(c), d_btot(c), d_boff(c), d_plen(c), d_poff(c);
+	int rc;
+	if ((rc = d_lut.alloc(256)) || (rc = d_lab.alloc(S * X)) || (rc = d_loff.alloc(S * X1)) || (rc = d_segoff.alloc(S + 1)) ||
+	    (rc = d_btot.alloc(nb)) || (rc = d_boff.alloc(nb + 1)) || (rc = d_lens.alloc(GR_T)) ||
+	    (paths && ((rc = d_plen.alloc(m)) || (rc = d_poff.alloc(m + 1)))))
+	{ (void) hipStreamSynchronize(st); return rc; }
+	std::vector<uint64_t> loff, segoff, boff, poff;
+	try { loff.resize(S * X1); segoff.resize(S + 1); boff.resize(nb + 1); poff.resize(paths ? m + 1 : 1); }
+	catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "block graph file: the line offsets on the host"); }
+	hipError_t e = hipMemcpyAsync(d_lut, c->code_to_byte, 256, hipMemcpyHostToDevice, st);
+	if (e != hipSuccess) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_HIP, "block graph file preparation", e); }
+	GraphArgs A = T.args(gap_byte);
+	A.code_to_byte = d_lut;
+	// every line's length, scanned: the nodes inside the segments, then over them; the links inside their workgroups, then over
+	// them; the paths over the rows
+	hipLaunchKernelGGL(k_graph_node_lines, dim3((uint32_t) S), dim3(GR_T), 0, st, A, (uint32_t *) d_lab, (uint64_t *) d_loff);
+	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, (uint64_t const *) d_loff, (uint32_t) S, X, (uint64_t *) d_segoff);
+	if (nb) hipLaunchKernelGGL(k_graph_link_lines, dim3((uint32_t) nb), dim3(GR_T), 0, st, A, 0u, (uint64_t *) d_btot, (uint32_t *) nullptr);
+	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, (uint64_t const *) d_btot, (uint32_t) nb, 0u, (uint64_t *) d_boff);
+	if (paths)
+	{
+		hipLaunchKernelGGL(k_graph_path_lines, dim3((uint32_t) ((m + GR_T - 1) / GR_T)), dim3(GR_T), 0, st, A, (uint64_t *) d_plen);
+		hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, (uint64_t const *) d_plen, (uint32_t) m, 0u, (uint64_t *) d_poff);
+	}
+	e = hipMemcpyAsync(loff.data(), d_loff, S * X1 * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(segoff.data(), d_segoff, (S + 1) * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(boff.data(), d_boff, (nb + 1) * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && paths) e = hipMemcpyAsync(poff.data(), d_poff, (m + 1) * 8, hipMemcpyDeviceToHost, st);
+	hipError_t const es = hipStreamSynchronize(st);
+	if (e == hipSuccess) e = es;
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "block graph file: line lengths", e);
+	release_all(c, d_btot, d_plen);
+	// batches of whole lines in file order, FSEQ_GRAPH_BATCH bytes at most; a line above the budget is a batch of its own.
+	// The nodes' and the paths' are cut here from the lines' offsets; the links' while they are written (a cut inside a
+	// workgroup's lines asks the device for their lengths)
+	uint64_t const budget = c->tune.graph_batch > 0 ? (uint64_t) c->tune.graph_batch : GRAPH_BATCH_BYTES;
+	fseq_ctx::GraphFileStats stats;
+	stats.have = true;
+	std::vector<SegFileBatch> nbatches;
+	std::vector<GraphBatch> pbatches;
+	uint64_t most_bytes = 1;
+	try
+	{
+		SegFileBatch cur{};
+		bool open = false;
+		auto close = [&]() { nbatches.push_back(cur); most_bytes = std::max(most_bytes, cur.bytes); open = false; };
+		for (size_t s = 0; s < S; ++s)
+		{
+			uint64_t const *lo = loff.data() + s * X1;
+			for (uint32_t j = 0; j < T.count[s]; ++j)
+			{
+				uint64_t const len = lo[j + 1] - lo[j];
+				if (open && cur.bytes + len > budget) close();
+				if (!open) { cur = SegFileBatch{(uint32_t) s, (uint32_t) s, j, j, segoff[s] + lo[j], 0}; open = true; }
+				cur.s1 = (uint32_t) s; cur.j_hi = j + 1; cur.bytes += len;
+				++stats.lines[0];
+			}
+		}
+		if (open) close();
+		for (uint64_t row = 0; paths && row < m;)
+		{
+			GraphBatch B{row, row, poff[row], 0};
+			while (B.last < m && (B.last == B.first || poff[B.last + 1] - B.begin <= budget)) ++B.last;
+			B.bytes = poff[B.last] - B.begin;
+			most_bytes = std::max(most_bytes, B.bytes);
+			pbatches.push_back(B);
+			row = B.last;
+		}
+	}
+	catch (std::bad_alloc const &) { return fail(c, FSEQ_E_OOM, "block graph file: the batches on the host"); }
+	stats.bytes[0] = segoff[S]; stats.bytes[1] = boff[nb]; stats.bytes[2] = paths ? poff[m] : 0u; stats.lines[1] = E; stats.lines[2] = paths ? m : 0u;
+	if (E) most_bytes = std::max<uint64_t>(most_bytes, std::max<uint64_t>(std::min(budget, boff[nb]), GR_LINK_MAX));
+	if ((rc = d_out.alloc((size_t) most_bytes))) return rc;
+	uint8_t *h_out = nullptr;
+	if (hipHostMalloc(reinterpret_cast<void **>(&h_out), (size_t) most_bytes, hipHostMallocDefault) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		return fail(c, FSEQ_E_OOM, "block graph output buffer");
+	}
+	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+	if (!f) { (void) hipHostFree(h_out); return fail(c, FSEQ_E_ARG, "cannot open the block graph output file"); }
+	bool ok = fputs(GRAPH_HEADER, f) >= 0, hip_ok = true;
+	// one copy and one write a batch
+	auto leave = [&](uint64_t bytes, int section) {
+		hip_ok = hipMemcpyAsync(h_out, d_out, (size_t) bytes, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
+		if (hip_ok) ok = fwrite(h_out, 1, (size_t) bytes, f) == (size_t) bytes;
+		++stats.batches[section];
+	};
+	for (size_t b = 0; b < nbatches.size() && ok && hip_ok; ++b)
+	{
+		SegFileBatch const &B = nbatches[b];
+		hipLaunchKernelGGL(k_graph_write_nodes, dim3(B.s1 - B.s0 + 1), dim3(GR_T), 0, st, A, B, (uint32_t const *) d_lab, (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint8_t *) d_out);
+		leave(B.bytes, 0);
+	}
+	uint32_t lens[GR_T];
+	for (uint64_t first = 0, pos = 0; first < E && ok && hip_ok;)
+	{
+		// the workgroup whose lines the budget ends in: whole workgroups in front of it, its lines one by one
+		uint64_t const target = pos + budget;
+		size_t const bb = (size_t) (std::upper_bound(boff.begin(), boff.end(), target) - boff.begin()) - 1;      // boff[bb] <= target (boff[block of first] <= pos)
+		GraphBatch B{first, E, pos, boff[nb] - pos};
+		if (bb < nb)
+		{
+			hipLaunchKernelGGL(k_graph_link_lines, dim3(1), dim3(GR_T), 0, st, A, (uint32_t) bb, (uint64_t *) nullptr, (uint32_t *) d_lens);
+			hip_ok = hipMemcpyAsync(lens, d_lens, sizeof(lens), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
+			if (!hip_ok) break;
+			uint64_t i = std::max<uint64_t>(first, (uint64_t) bb * GR_T), p = i == first ? pos : boff[bb];
+			uint64_t const i_end = std::min<uint64_t>(E, ((uint64_t) bb + 1) * GR_T);
+			while (i < i_end && p + lens[i - (uint64_t) bb * GR_T] <= target) p += lens[i++ - (uint64_t) bb * GR_T];
+			if (i == first) p += lens[i++ - (uint64_t) bb * GR_T];      // (a line above the budget: a batch of its own)
+			B.last = i; B.bytes = p - pos;
+		}
+		if (B.bytes > most_bytes || B.last <= B.first) { hip_ok = false; break; }      // (never: a line has at most GR_LINK_MAX bytes)
+		uint32_t const g = (uint32_t) ((B.last - 1) / GR_T - B.first / GR_T + 1);
+		hipLaunchKernelGGL(k_graph_write_links, dim3(g), dim3(GR_T), 0, st, A, B, (uint64_t const *) d_boff, (uint8_t *) d_out);
+		leave(B.bytes, 1);
+		first = B.last; pos += B.bytes;
+	}
+	for (size_t b = 0; b < pbatches.size() && ok && hip_ok; ++b)
+	{
+		GraphBatch const &B = pbatches[b];
+		uint32_t const g = (uint32_t) ((B.last - B.first + GR_TILE - 1) / GR_TILE);
+		hipLaunchKernelGGL(k_graph_write_paths, dim3(g), dim3(GR_T), 0, st, A, B, (uint64_t const *) d_poff, (uint8_t *) d_out);
+		leave(B.bytes, 2);
+	}
+	if (fflush(f) != 0) ok = false;
+	if (f != stdout) fclose(f);
+	(void) hipHostFree(h_out);
+	if (!hip_ok) return fail(c, FSEQ_E_HIP, "writing the block graph from the device failed");
+	if (!ok) return fail(c, FSEQ_E_ARG, "writing the block graph output file failed");
+	c->graphfile = stats;
+	return FSEQ_OK;
+}
+
+int fseq_debug_graph_file(fseq_ctx *c, fseq_graph_file_stats *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if (!c->graphfile.have) return fail(c, FSEQ_E_ARG, "no fseq_write_block_graph has finished on this context");
+	for (int k = 0; k < 3; ++k) { out->batches[k] = c->graphfile.batches[k]; out->lines[k] = c->graphfile.lines[k]; out->bytes[k] = c->graphfile.bytes[k]; }
+	return FSEQ_OK;
+}
+
+} // extern "C"

@@ -2,7 +2,7 @@
 // shares: csrc/fseq_api.hip (the ABI's entry points) and csrc/fseq_api_debug.hip (the debug entry points, the row-sharded sweep),
 // the units of the segmentation path (csrc/fseq_path_setup.hip, _dp, _pass1, _reduced, _attempt, _pass2: geometry, buffers, phases, sharding; what
 // only they share is csrc/fseq_path.hpp), csrc/fseq_api_join.hip (the host joiners, their device front and the output
-// writers), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
+// writers), csrc/fseq_api_graph.hip (the founder block graph), csrc/fseq_api_match.hip (the rows matched against founders), csrc/fseq_api_identity.hip (identity columns dropped
 // and put back), csrc/fseq_api_rowsplit.hip (rows held out of the resident alignment) and csrc/fseq_api_input.hip (the input rows in column chunks).  Internal: nothing here is part of the boundary.
 #pragma once
 
@@ -125,6 +125,7 @@ struct Tuning {
 	bool join_bip_wide = false;          // FSEQ_JOIN_BIP_WIDE: fseq_join_bipartite through the wide device form (weights in slabs of device memory) at any max_segment_size up to 4,096; FSEQ_JOIN_HOST wins
 	int  join_bip_slabs = 0;             // FSEQ_JOIN_BIP_SLABS: most slabs (= persistent workgroups) of the wide form (by itself: from the CU count and the memory)
 	int  segfile_batch = 0;              // FSEQ_SEGFILE_BATCH: most bytes of a batch of fseq_write_segments_device / fseq_write_segments_restored (by itself: 256 MiB; tests: batches of a line or two)
+	int  graph_batch = 0;                // FSEQ_GRAPH_BATCH: most bytes of a batch of fseq_write_block_graph (by itself: 256 MiB; tests: batches of a line or two)
 	bool shard_dp_full = false;          // FSEQ_SHARD_DP_FULL: the sharded DP gathers the whole key array after every sweep (round 2-3 form)
 	int  shard_dp_window = 0;            // FSEQ_SHARD_DP_WINDOW: entries of the other ranks a rank holds in front of its own (tests: small windows)
 	int  inject_failure_rank = -1;       // FSEQ_INJECT_FAILURE_RANK: this rank of a sharded run fails after phase A
@@ -178,6 +179,7 @@ struct Tuning {
 			{"FSEQ_JOIN_BIP_WIDE", &Tuning::join_bip_wide, nullptr, 0, 0, nullptr},
 			{"FSEQ_JOIN_BIP_SLABS", nullptr, &Tuning::join_bip_slabs, 1, 0, nullptr},
 			{"FSEQ_SEGFILE_BATCH", nullptr, &Tuning::segfile_batch, 1, 0, nullptr},
+			{"FSEQ_GRAPH_BATCH", nullptr, &Tuning::graph_batch, 1, 0, nullptr},
 			{"FSEQ_SHARD_DP_FULL", &Tuning::shard_dp_full, nullptr, 0, 0, nullptr},
 			{"FSEQ_SHARD_DP_WINDOW", nullptr, &Tuning::shard_dp_window, 64, 0, nullptr},
 			{"FSEQ_INJECT_FAILURE_RANK", nullptr, &Tuning::inject_failure_rank, INT_MIN, -1, nullptr},
@@ -309,6 +311,7 @@ struct fseq_ctx {
 	int rand_path = -1;                      // the last fseq_join_random since the input was set (fseq_debug_random_path): 0 host, 1 the class tables from the device; -1: none yet
 	int score_path = -1;                     // the last fseq_join_score since the input was set (fseq_debug_join_score_path): 0 host, 1 the device form; -1: none yet
 	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device or fseq_write_segments_restored (fseq_debug_segments_file)
+	struct GraphFileStats { bool have = false; uint64_t batches[3] = {}, lines[3] = {}, bytes[3] = {}; } graphfile;      // the last fseq_write_block_graph (fseq_debug_graph_file): the S, L and P sections
 	fseq_progress_fn progress_fn = nullptr;
 	void *progress_user = nullptr;
 	hipStream_t stream = nullptr;

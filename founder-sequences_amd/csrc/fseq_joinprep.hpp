@@ -23,7 +23,7 @@ constexpr uint32_t JP_T = 256;
 constexpr uint32_t JP_MAX_CLASSES = 181;                 // LDS matrix of 181 x 181 counters = 128 KiB
 
 // of_row[s][row] (u16), rep[s][c], size[s][c] (stride X), count[s]
-__global__ __launch_bounds__(JP_T) void k_join_classes(
+static __global__ __launch_bounds__(JP_T) void k_join_classes(
 	uint32_t const *__restrict__ snap_a, uint32_t const *__restrict__ snap_d, uint64_t const *__restrict__ seg_rb, uint32_t m, uint32_t X,
 	uint16_t *__restrict__ of_row, uint32_t *__restrict__ rep, uint32_t *__restrict__ size, uint32_t *__restrict__ count)
 {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(JP_T) void k_join_classes(
 }
 
 // pair p = (segment p, segment p + 1): edges[offset[p] .. offset[p] + nedges[p]) = {l << 16 | r, rows}, ascending (l, r)
-__global__ __launch_bounds__(JP_T) void k_join_edges(
+static __global__ __launch_bounds__(JP_T) void k_join_edges(
 	uint16_t const *__restrict__ of_row, uint32_t const *__restrict__ count, uint32_t m, uint32_t X,
 	uint2 *__restrict__ edges, uint64_t cap_total, uint32_t *__restrict__ offset, uint32_t *__restrict__ nedges, unsigned long long *__restrict__ cursor)
 {
@@ -123,7 +123,7 @@ constexpr uint32_t JW_T = 1024;
 constexpr uint32_t JW_CELLS = 32768;                      // counters of a strip: the 128 KiB of LDS k_join_edges is granted
 
 // as k_join_classes, and start[s][c] (stride X + 1): pBWT position at which class c begins, start[s][count] = m
-__global__ __launch_bounds__(JW_T) void k_join_classes_wide(
+static __global__ __launch_bounds__(JW_T) void k_join_classes_wide(
 	uint32_t const *__restrict__ snap_a, uint32_t const *__restrict__ snap_d, uint64_t const *__restrict__ seg_rb, uint32_t m, uint32_t X,
 	uint16_t *__restrict__ of_row, uint32_t *__restrict__ rep, uint32_t *__restrict__ size, uint32_t *__restrict__ count, uint32_t *__restrict__ start)
 {
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(JW_T) void k_join_edges_wide(
 }
 
 // offset[p] = edges of the pairs before p (the 32-bit word the host takes it as), *total = edges of all pairs
-__global__ __launch_bounds__(JW_T) void k_join_scan(
+static __global__ __launch_bounds__(JW_T) void k_join_scan(
 	uint32_t const *__restrict__ nedges, uint32_t pairs, uint32_t *__restrict__ offset, unsigned long long *__restrict__ total)
 {
 	__shared__ uint32_t scratch[JW_T / WAVE + 1];

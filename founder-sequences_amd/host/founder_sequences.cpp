@@ -75,6 +75,13 @@ char const *const USAGE =
 	"                                     continue a substring that some sequence continues too, and per founder its breaks\n"
 	"                                     (every joining method; works under --upload-memory, --hold-out and\n"
 	"                                     --remove-identity-columns, there in reduced co-ordinates as --output-segments; one GPU only)\n"
+	"      --output-graph=PATH            Write the founder block graph as GFA 1.0 from the device: an S line per distinct substring of every\n"
+	"                                     segment, an L line per pair of substrings of adjacent segments that some sequence carries, with\n"
+	"                                     the number of those sequences (needs the segmentation only: every joining method; works under\n"
+	"                                     --upload-memory, --hold-out, --list-memory and --remove-identity-columns, there in reduced\n"
+	"                                     co-ordinates as --output-segments; one GPU only)\n"
+	"      --graph-paths                  ... with a P line per input sequence\n"
+	"      --graph-gap-character=C        ... the character the S lines' substrings leave out; empty: every character stays  (default=`-')\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
 	"      --scan-segment-lengths=SPEC    Before anything else, write the maximum segment size at every segment length bound of SPEC --\n"
 	"                                     a comma list of lengths, or LO:HI:STEP -- as a table (SEGMENT_LENGTH, MAX_SEGMENT_SIZE; one line\n"
@@ -386,6 +393,8 @@ int main(int argc, char **argv)
 	std::vector<uint32_t> held_rows;
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr, *out_restored_segments = nullptr;
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr, *out_join_score = nullptr;
+	char const *out_graph = nullptr, *graph_gap = nullptr;
+	bool graph_paths = false;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
 	bool match_min_len_bad = false;
@@ -421,6 +430,8 @@ int main(int argc, char **argv)
 		{"output-held-out-restored-matches", required_argument, nullptr, 1018}, {"output-sequence-restored-matches", required_argument, nullptr, 1019},
 		{"output-restored-segments", required_argument, nullptr, 1020}, {"reduce-on-upload", no_argument, nullptr, 1021},
 		{"output-join-score", required_argument, nullptr, 1022},
+		{"output-graph", required_argument, nullptr, 1023}, {"graph-paths", no_argument, nullptr, 1024},
+		{"graph-gap-character", required_argument, nullptr, 1025},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -471,6 +482,9 @@ int main(int argc, char **argv)
 			case 1008: out_identity = optarg; remove_identity = true; break;
 			case 1009: out_restored_matches = optarg; break;
 			case 1022: out_join_score = optarg; break;
+			case 1023: out_graph = optarg; break;
+			case 1024: graph_paths = true; break;
+			case 1025: graph_gap = optarg; break;
 			case 1010:
 			{
 				// as --list-memory, but a positive number: 0 MiB hold no chunk
@@ -548,6 +562,9 @@ int main(int argc, char **argv)
 	// (the two combine with --remove-identity-columns only for the restored match; the reports in reduced co-ordinates stay refused)
 	if (match_seqs && remove_identity && (!out_seq_restored || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 	if (out_join_score && gpus > 1) { std::cerr << "--output-join-score is not supported together with --gpus > 1 (a rank holds its own boundary states only)." << std::endl; return EXIT_FAILURE; }
+	if (out_graph && gpus > 1) { std::cerr << "--output-graph is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
+	if ((graph_paths || graph_gap) && !out_graph) { std::cerr << (graph_paths ? "--graph-paths" : "--graph-gap-character") << " requires --output-graph." << std::endl; return EXIT_FAILURE; }
+	if (graph_gap && strlen(graph_gap) > 1) { std::cerr << "The gap character of the graph must be one character, or empty to keep every character." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && gpus > 1) { std::cerr << "--output-restored-segments is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && !remove_identity) { std::cerr << "--output-restored-segments requires --remove-identity-columns (without it --output-segments is in the input's co-ordinates already)." << std::endl; return EXIT_FAILURE; }
 	if (remove_identity && gpus > 1) { std::cerr << "--remove-identity-columns is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
@@ -824,6 +841,11 @@ int main(int argc, char **argv)
 			std::cerr << "--output-join-score needs the permutations of a segmentation; the sequences are shorter than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_graph)
+		{
+			std::cerr << "--output-graph needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_restored_matches)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
@@ -844,6 +866,13 @@ int main(int argc, char **argv)
 	// generate_context.cc:224-228
 	std::cerr << "After calculating the traceback there were " << res.dp_segment_count
 	          << " segments the maximum size of which was " << res.max_segment_size << '.' << std::endl;
+	if (out_graph)
+	{
+		// the segmentation's own graph, from the context alone (no rows on the host, no join): in the co-ordinates --output-segments has
+		std::cerr << "Outputting the block graph…" << std::endl;
+		int const gap = graph_gap ? (graph_gap[0] ? (int) (unsigned char) graph_gap[0] : -1) : (int) '-';
+		if (FSEQ_OK != (rc = fseq_write_block_graph(ctx, graph_paths ? FSEQ_GRAPH_PATHS : 0u, gap, out_graph))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	}
 	std::cerr << "Joining the remaining segments…" << std::endl;
 	std::vector<uint32_t> perm((size_t) res.segment_count * res.max_segment_size);
 	std::vector<uint32_t> all_a, all_d;                         // sharded: the boundary states, collected from their owners

@@ -366,6 +366,45 @@ int  fseq_write_segments_host(fseq_ctx *ctx, uint8_t const *const *rows, int joi
  * nothing behind and the context usable.  fseq_debug_segments_file (fseq_debug.h) reports the batches.
  * path NULL or "-" = stdout. */
 int  fseq_write_segments_device(fseq_ctx *ctx, int joining, char const *path);
+/* ---- the founder block graph of a finished run (no counterpart in the reference) ----
+ * A finished run has S merged segments that tile the columns.  The graph's nodes are the classes of every segment -- the
+ * distinct substrings of the rows over [lb_s, rb_s) --, its edges join class l of segment s to class r of segment s + 1 and
+ * weigh the input rows that carry both; every input row is a path of S nodes.  Node ids are 0-based, id(s, c) = the classes of
+ * the segments in front of s plus c, where c is the class number the joiners, the segments file and the join score share
+ * (k_join_classes_wide, csrc/fseq_joinprep.hpp: the classes in the order of their first pBWT position at rb_s).  A node:
+ * its segment and class, the segment's [lb, rb), rep_row -- the first row of the class in that order, whose bytes the
+ * label is taken from --, rows -- the size of the class.  An edge: from / to are node ids, rows its weight, junction = the left
+ * segment; the edges are ordered by junction, then (l, r) ascending.  The weights of a junction add up to m, and so do the
+ * rows of a segment's nodes. */
+typedef struct { uint64_t lb, rb; uint32_t segment, cls, rep_row, rows; } fseq_graph_node;      /* 32 bytes */
+typedef struct { uint32_t from, to, rows, junction; } fseq_graph_edge;                           /* 16 bytes */
+typedef struct { uint64_t segments, nodes, edges; double ms_device; } fseq_graph_summary;
+/* The graph as arrays, computed where the boundary states are (the class tables and the edge kernel of fseq_join_greedy's
+ * device front): nodes [summary.nodes], edges [summary.edges], row_nodes [S][m] -- the node of every row in every segment --
+ * and summary may each be NULL; with the three arrays NULL the call counts, so that a caller can size them.  On a context
+ * made by fseq_create_without_identity_columns lb / rb are in reduced co-ordinates, as fseq_write_segments_device's.
+ * Refuses, each with fseq_last_error set and the context and its results left as they were: FSEQ_E_ARG -- no finished
+ * long-path run; FSEQ_E_UNSUPPORTED -- a sharded context, merged segments that do not tile the columns, more than 65,535
+ * classes in a segment, a right segment of more than 32,768 (the edge kernel reports none), 2^32 nodes or edges or more, 2^31
+ * rows or segments or more, a class count outside [1, max_segment_size] read back; FSEQ_E_OOM -- a failed allocation, with
+ * nothing left behind.  There is no host form. */
+int  fseq_block_graph(fseq_ctx *ctx, fseq_graph_node *nodes, fseq_graph_edge *edges, uint32_t *row_nodes, fseq_graph_summary *summary);
+/* The graph as a GFA 1.0 file, written from the device (csrc/fseq_graph.hpp).  Tab-separated, '\n'-terminated:
+ *   H	VN:Z:1.0
+ *   S	<id+1>	<label>	LN:i:<len>	RC:i:<rows>	sg:i:<segment>	lb:i:<lb>	rb:i:<rb>     one per node, in id order
+ *   L	<from+1>	+	<to+1>	+	0M	RC:i:<rows>                                      one per edge, in edge order
+ *   P	<row>	<id+1>+,<id+1>+,...	*                                                one per input row 0 .. m - 1, with FSEQ_GRAPH_PATHS
+ * <label> is the representative row's bytes over [lb, rb) without every byte equal to gap_byte (gap_byte < 0: every byte
+ * stays); <len> its length; an empty label prints '*' with LN:i:0.  The bytes are the alignment's own, decoded through the
+ * context's code table: keeping them inside GFA's sequence alphabet is the caller's business.  The concatenated labels of a P
+ * line spell the row without its gap bytes.  The file leaves in batches of whole lines of at most 256 MiB (FSEQ_GRAPH_BATCH),
+ * one copy and one write a batch (fseq_debug_graph_file, fseq_debug.h, reports them).  Needs the alignment resident on the
+ * device and no rows on the host: contexts filled in chunks, made by fseq_create_without_rows or by
+ * fseq_create_without_identity_columns (reduced co-ordinates and the reduced rows' bytes) are served.
+ * Refuses as fseq_block_graph, and FSEQ_E_ARG for no resident alignment, gap_byte > 255, a flag bit other than
+ * FSEQ_GRAPH_PATHS and an output file that cannot be opened -- each with no byte written.  path NULL or "-" = stdout. */
+enum { FSEQ_GRAPH_PATHS = 1 };
+int  fseq_write_block_graph(fseq_ctx *ctx, uint32_t flags, int gap_byte, char const *path);
 /* replaces: join_context::output_in_permutation_order (join_context.cc:333-356): max_segment_size
  * lines; line r = concatenation over segments of rows[permutations[s][r]][lb_s, rb_s).  rows = the
  * raw input sequences.  path NULL or "-" = stdout. */

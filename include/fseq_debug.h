@@ -154,6 +154,16 @@ int  fseq_debug_input_kept_range(uint64_t const *kept, uint64_t n_kept, uint64_t
  * Each out pointer may be NULL.  FSEQ_E_ARG while none has been written. */
 int  fseq_debug_segments_file(fseq_ctx *ctx, uint64_t *batches, uint64_t *bytes, uint64_t *longest_line, uint64_t *lines);
 
+/* The last file fseq_write_block_graph wrote on this context, by section -- [0] the S lines, [1] the L lines, [2] the P lines
+ * (all zero without FSEQ_GRAPH_PATHS): the batches that left the device, the lines and their bytes, a line with its newline.
+ * The header line (11 bytes) goes through no batch and is in no count: the file has 11 + bytes[0] + bytes[1] + bytes[2] bytes.
+ * FSEQ_GRAPH_BATCH=bytes sets the most a batch holds (a longer line is a batch of its own; fseq_debug_set_tuning takes it at any
+ * time: nothing of a run depends on it).  FSEQ_E_ARG while none has been written. */
+typedef struct fseq_graph_file_stats {
+	uint64_t batches[3], lines[3], bytes[3];
+} fseq_graph_file_stats;
+int  fseq_debug_graph_file(fseq_ctx *ctx, fseq_graph_file_stats *stats);
+
 /* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
  * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
  * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
