@@ -107,6 +107,10 @@ class DpListsInfo(C.Structure):
     _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
 
 
+class MergeListsInfo(C.Structure):
+    _fields_ = [("overflow", C.c_uint32), ("tau_separate", C.c_uint32), ("threshold_launches", C.c_uint32), ("count_launches", C.c_uint32)]
+
+
 class LengthScanSummary(C.Structure):
     _fields_ = [("lists_built", C.c_uint32), ("lists_folded", C.c_uint32), ("short_entries", C.c_uint32), ("retries", C.c_uint32),
                 ("ms_phase_a", C.c_double), ("ms_phase_b", C.c_double), ("ms_total", C.c_double)]
@@ -154,7 +158,7 @@ EXPORTS = [
     "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
     "fseq_match_rows", "fseq_debug_match_split",
     "fseq_create_without_rows", "fseq_get_held_out", "fseq_match_held_out", "fseq_debug_held_out_columns", "fseq_debug_row_split_plan",
-    "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
+    "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists", "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
     "fseq_create_without_identity_columns_held", "fseq_match_held_out_restored", "fseq_match_rows_restored", "fseq_get_match_exceptions",
     "fseq_get_segments_restored", "fseq_write_segments_restored", "fseq_debug_restored_bounds",
     "fseq_input_scan_identity", "fseq_input_reduce", "fseq_input_kept_columns", "fseq_input_columns_kept", "fseq_input_end_kept",
@@ -168,6 +172,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
+                 "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
                  "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file"]
 
@@ -303,6 +308,9 @@ def load_library():
     L.fseq_debug_row_split_plan.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.fseq_debug_dp_lists_check.argtypes = [C.c_uint32, u64, u64, C.c_uint32, vp, vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.fseq_debug_dp_on_lists.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(DpListsInfo)]
+    L.fseq_debug_merge_on_lists.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(u64), vp, C.POINTER(u64), vp,
+                                            C.POINTER(u64), C.POINTER(MergeListsInfo)]
+    L.fseq_debug_traceback_parts.argtypes = [C.c_int, u64, u64, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(u64), vp, vp, C.POINTER(u64)]
     L.fseq_get_segments_restored.argtypes = [vp, vp]
     L.fseq_write_segments_restored.argtypes = [vp, C.c_int, C.c_char_p]
     L.fseq_debug_restored_bounds.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp]
@@ -602,6 +610,41 @@ def dp_lists_check(m, segment_length, ent, hdr):
     if rc != FSEQ_E_ARG:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return (-1 if bad.value == 2 ** 64 - 1 else bad.value), rule.value
+
+
+def _dp_arrays(n, segment_length, lb, max_size, size):
+    out = [np.ascontiguousarray(a, dtype=np.uint32) for a in (lb, max_size, size)]
+    if int(segment_length) < 1 or any(a.shape != (int(n) - int(segment_length) + 1,) for a in out):
+        raise FseqError(FSEQ_E_ARG, "DP arrays: lb, max_size and size have n - L + 1 words each")
+    return out
+
+
+def traceback_parts(n, segment_length, lb, max_size, size, part_lo, foreign=None, device=0):
+    """The traceback of caller-supplied DP arrays followed part by part, as a sharded run in window mode follows it rank by rank
+    (fseq_debug_traceback_parts; one process, no context): part g holds the entries [part_lo[g], part_lo[g + 1]), the last one up
+    to n - L + 1, and sees `foreign` (or 0xFFFFFFFF) in every other entry of lb.  Returns (traceback as DPARG_DTYPE, first segment
+    first; entries of the chain per part; windows per part).  FseqError(FSEQ_E_ARG), before a device is touched, for part borders
+    out of order and for a chain from entry n - L that does not descend to lb == 0 (the message names the entry)."""
+    L = load_library()
+    lb, max_size, size = _dp_arrays(n, segment_length, lb, max_size, size)
+    part_lo = np.ascontiguousarray(part_lo, dtype=np.uint32)
+    if foreign is not None:
+        foreign = np.ascontiguousarray(foreign, dtype=np.uint32)
+        if foreign.shape != lb.shape:
+            raise FseqError(FSEQ_E_ARG, "traceback by parts: foreign has n - L + 1 words")
+    tb = np.zeros(int(n) // int(segment_length) + 2, dtype=DPARG_DTYPE)
+    ents = np.zeros(max(1, len(part_lo)), dtype=np.uint32)
+    wins = np.zeros(max(1, len(part_lo)), dtype=np.uint32)
+    count, bad = C.c_uint64(), C.c_uint64()
+    rc = L.fseq_debug_traceback_parts(device, int(n), int(segment_length), lb.ctypes.data, max_size.ctypes.data, size.ctypes.data,
+                                      part_lo.ctypes.data if len(part_lo) else None, len(part_lo), None if foreign is None else foreign.ctypes.data,
+                                      tb.ctypes.data, C.byref(count), ents.ctypes.data, wins.ctypes.data, C.byref(bad))
+    if rc != FSEQ_OK:
+        what = L.fseq_strerror(rc).decode()
+        if bad.value != 2 ** 64 - 1:
+            what += ": chain entry %d" % bad.value
+        raise FseqError(rc, what)
+    return tb[:count.value].copy(), ents[:len(part_lo)], wins[:len(part_lo)]
 
 
 class RowShard(C.Structure):
@@ -1505,6 +1548,32 @@ class SegmentationContext:
         self._check(self.L.fseq_debug_dp_on_lists(self.h, int(list_cap), ent.ctypes.data, hdr.ctypes.data, cuts.ctypes.data if len(cuts) else None,
                                                   len(cuts), lb.ctypes.data, mx.ctypes.data, sz.ctypes.data, C.byref(info)))
         return lb, mx, sz, {k_: getattr(info, k_) for k_, _ in DpListsInfo._fields_}
+
+    def debug_merge_on_lists(self, list_cap, ent, hdr, lb, max_size, size, separate=False, col_splits=()):
+        """The traceback and the greedy merge alone on constructed DP arrays and lists, through the functions a run calls
+        (fseq_debug_merge_on_lists): ent / hdr as for debug_dp_on_lists, lb / max_size / size n - L + 1 words each.  separate: the
+        thresholds come from launches of their own instead of riding with the traceback, they and the merged sizes once per column
+        range cut at col_splits and summed on the host.  Returns (traceback, tau, segments, info): DPARG_DTYPE, [count][2] {tau,
+        kind} in the traceback's order (empty where none were taken), SEGMENT_DTYPE, {overflow, tau_separate, threshold_launches,
+        count_launches}; the context holds no result afterwards."""
+        ent, hdr = _dp_lists(ent, hdr)
+        if ent.shape[0] != self.n or ent.shape[1] != ((int(list_cap) + 3) & ~1):
+            raise FseqError(FSEQ_E_ARG, "merge on lists: ent is [n][(list_cap + 3) & ~1][2]")
+        lb, max_size, size = _dp_arrays(self.n, self.segment_length, lb, max_size, size)
+        splits = np.ascontiguousarray(col_splits, dtype=np.uint64)
+        room = self.n // self.segment_length + 2
+        tb = np.zeros(room, dtype=DPARG_DTYPE)
+        tau = np.zeros((room, 2), dtype=np.uint32)
+        seg = np.zeros(room, dtype=SEGMENT_DTYPE)
+        n_tb, n_tau, n_seg = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        info = MergeListsInfo()
+        self.result = None
+        self._check(self.L.fseq_debug_merge_on_lists(self.h, int(list_cap), ent.ctypes.data, hdr.ctypes.data, lb.ctypes.data, max_size.ctypes.data,
+                                                     size.ctypes.data, 1 if separate else 0, splits.ctypes.data if len(splits) else None, len(splits),
+                                                     tb.ctypes.data, C.byref(n_tb), tau.ctypes.data, C.byref(n_tau), seg.ctypes.data, C.byref(n_seg),
+                                                     C.byref(info)))
+        return (tb[:n_tb.value].copy(), tau[:n_tau.value].copy(), seg[:n_seg.value].copy(),
+                {k_: getattr(info, k_) for k_, _ in MergeListsInfo._fields_})
 
     def set_tuning(self, name, value="1"):
         """One of the library's FSEQ_* diagnostic knobs for this context (value None = off); the environment is only

@@ -4,6 +4,7 @@
 #include "fseq_path.hpp"
 #include "fseq_dp.hpp"           // the round schedule (fseq_debug_dp_schedule)
 #include "fseq_rowshard.hpp"
+#include "fseq_tbcheck.hpp"      // the chain a caller's lb array must hold (fseq_debug_merge_on_lists)
 
 using namespace fseq;
 
@@ -268,34 +269,37 @@ int fseq_debug_dp_lists_check(uint32_t m, uint64_t n, uint64_t L, uint32_t strid
 	return FSEQ_OK;
 }
 
-int fseq_debug_dp_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *cuts, uint32_t n_cuts,
-                           uint32_t *lb, uint32_t *max_size, uint32_t *size, fseq_dp_lists_info *info)
+namespace {
+
+// what the entries on caller-supplied lists refuse before the device is touched (who: "DP on lists", "merge on lists")
+int lists_refused(fseq_ctx *c, char const *who, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr)
 {
-	if (!c) return FSEQ_E_ARG;
-	if (!ent || !hdr || !info || (n_cuts && !cuts) || 0 == list_cap) return fail(c, FSEQ_E_ARG, "DP on lists: lists, a capacity and an info are needed");
-	if (c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "DP on lists: not for sharded contexts (a rank holds the lists of its own columns)");
-	if (c->lw.budget) return fail(c, FSEQ_E_UNSUPPORTED, "DP on lists: not under a list memory budget (every list is held)");
+	char what[200];
+	auto no = [&](int code, char const *why) {
+		snprintf(what, sizeof(what), "%s: %s", who, why);
+		return fail(c, code, what);
+	};
+	if (c->sh.on) return no(FSEQ_E_UNSUPPORTED, "not for sharded contexts (a rank holds the lists of its own columns)");
+	if (c->lw.budget) return no(FSEQ_E_UNSUPPORTED, "not under a list memory budget (every list is held)");
 	if (!c->have_input) return fail(c, FSEQ_E_ARG, "no input set");
 	if (c->in.open) return fail(c, FSEQ_E_ARG, "a chunked input is under way (fseq_input_begin without fseq_input_end)");
 	fseq_params const &p = c->p;
-	uint64_t const n = p.n, L = p.segment_length;
-	if (n < 2 * L) return fail(c, FSEQ_E_ARG, "DP on lists: the short path (n < 2L) has no DP");
-	if (list_cap > 0x00FFFFFFu) return fail(c, FSEQ_E_ARG, "DP on lists: list capacity out of range");
-	uint32_t const stride = (list_cap + 3) & ~1u;
+	if (p.n < 2 * p.segment_length) return no(FSEQ_E_ARG, "the short path (n < 2L) has no DP");
+	if (list_cap > 0x00FFFFFFu) return no(FSEQ_E_ARG, "list capacity out of range");
 	uint64_t bad = 0;
 	uint32_t rule = 0;
-	if (fseq_debug_dp_lists_check(p.m, n, L, stride, ent, hdr, &bad, &rule))
+	if (fseq_debug_dp_lists_check(p.m, p.n, p.segment_length, (list_cap + 3) & ~1u, ent, hdr, &bad, &rule))
 	{
-		char what[160];
-		snprintf(what, sizeof(what), "DP on lists: the list of column %lld breaks rule %u of fseq_debug_dp_lists_check", (long long) bad, rule);
+		snprintf(what, sizeof(what), "%s: the list of column %lld breaks rule %u of fseq_debug_dp_lists_check", who, (long long) bad, rule);
 		return fail(c, FSEQ_E_ARG, what);
 	}
-	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
-	for (uint32_t i = 0; i < n_cuts; ++i)
-		if (cuts[i] == 0 || cuts[i] >= S.nrounds || (i && cuts[i] <= cuts[i - 1]))
-			return fail(c, FSEQ_E_ARG, "DP on lists: the cut rounds ascend strictly inside (0, rounds)");
-	(void) hipSetDevice(p.device);
-	// the context holds no result from here on, and its lists are the caller's: nothing of a run may answer for them
+	return FSEQ_OK;
+}
+
+// the context holds no result from here on, and its lists are the caller's: nothing of a run may answer for them
+int lists_onto_context(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr)
+{
+	(void) hipSetDevice(c->p.device);
 	c->have_result = false;
 	c->scan_lists = false;
 	c->free_match();
@@ -305,8 +309,28 @@ int fseq_debug_dp_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, 
 	if ((rc = ensure_work_buffers(c, list_cap, false))) return rc;
 	hipStream_t st = c->stream;
 	HIP_TRY(c, hipStreamSynchronize(st));
-	HIP_TRY(c, hipMemcpyAsync(c->d_ent, ent, (size_t) n * stride * sizeof(uint2), hipMemcpyHostToDevice, st));
-	HIP_TRY(c, hipMemcpyAsync(c->d_hdr, hdr, (size_t) n * sizeof(uint4), hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(c->d_ent, ent, (size_t) c->p.n * c->stride * sizeof(uint2), hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(c->d_hdr, hdr, (size_t) c->p.n * sizeof(uint4), hipMemcpyHostToDevice, st));
+	return FSEQ_OK;
+}
+
+} // namespace
+
+int fseq_debug_dp_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *cuts, uint32_t n_cuts,
+                           uint32_t *lb, uint32_t *max_size, uint32_t *size, fseq_dp_lists_info *info)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!ent || !hdr || !info || (n_cuts && !cuts) || 0 == list_cap) return fail(c, FSEQ_E_ARG, "DP on lists: lists, a capacity and an info are needed");
+	int rc;
+	if ((rc = lists_refused(c, "DP on lists", list_cap, ent, hdr))) return rc;
+	fseq_params const &p = c->p;
+	uint64_t const n = p.n, L = p.segment_length;
+	DpSchedule const S = dp_schedule((uint32_t) L, (uint32_t) n);
+	for (uint32_t i = 0; i < n_cuts; ++i)
+		if (cuts[i] == 0 || cuts[i] >= S.nrounds || (i && cuts[i] <= cuts[i - 1]))
+			return fail(c, FSEQ_E_ARG, "DP on lists: the cut rounds ascend strictly inside (0, rounds)");
+	if ((rc = lists_onto_context(c, list_cap, ent, hdr))) return rc;
+	hipStream_t st = c->stream;
 	HIP_TRY(c, hipMemsetAsync(path_words(c)->dp, 0, sizeof(PathWords::dp), st));
 	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
 	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
@@ -345,6 +369,67 @@ int fseq_debug_dp_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, 
 	if (lb) HIP_TRY(c, hipMemcpy(lb, c->dp.LB, c->dp_size * 4, hipMemcpyDeviceToHost));
 	if (max_size) HIP_TRY(c, hipMemcpy(max_size, c->dp.M, c->dp_size * 4, hipMemcpyDeviceToHost));
 	if (size) HIP_TRY(c, hipMemcpy(size, c->dp.SZ, c->dp_size * 4, hipMemcpyDeviceToHost));
+	return FSEQ_OK;
+}
+
+// ---- the traceback and the greedy merge on caller-supplied DP arrays and lists (tests/test_gpu_merge_lists.py): the host's
+// checks of the lists and of the chain (fseq_tbcheck.hpp), then follow_traceback and the merge as a run calls them
+int fseq_debug_merge_on_lists(fseq_ctx *c, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *lb, uint32_t const *max_size,
+                              uint32_t const *size, uint32_t flags, uint64_t const *col_splits, uint32_t n_splits, fseq_dp_arg *traceback,
+                              uint64_t *n_traceback, uint32_t *tau, uint64_t *n_tau, fseq_segment *segments, uint64_t *n_segments, fseq_merge_lists_info *info)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!ent || !hdr || !lb || !max_size || !size || 0 == list_cap) return fail(c, FSEQ_E_ARG, "merge on lists: lists, a capacity and the three DP arrays are needed");
+	int rc;
+	if ((rc = lists_refused(c, "merge on lists", list_cap, ent, hdr))) return rc;
+	uint64_t const n = c->p.n, L = c->p.segment_length;
+	uint64_t bad = 0;
+	if (int const why = tb_chain_check(lb, n, L, &bad, nullptr))
+	{
+		char what[200];
+		if (why == TB_CHAIN_LB) snprintf(what, sizeof(what), "merge on lists: the lb of chain entry %lld is neither 0 nor in L .. the entry", (long long) bad);
+		else snprintf(what, sizeof(what), "merge on lists: the chain from entry n - L has not ended at entry %lld, n / L + 2 entries on", (long long) bad);
+		return fail(c, FSEQ_E_ARG, what);
+	}
+	if (flags & ~1u) return fail(c, FSEQ_E_ARG, "merge on lists: unknown flags");
+	MergeProbe probe;
+	probe.separate = (flags & 1u) != 0;
+	if (n_splits && (!col_splits || !probe.separate)) return fail(c, FSEQ_E_ARG, "merge on lists: column splits go with flag bit 0 (thresholds from launches of their own)");
+	probe.bounds.push_back(0);
+	for (uint32_t i = 0; i < n_splits; ++i)
+	{
+		if (col_splits[i] <= probe.bounds.back() || col_splits[i] >= n) return fail(c, FSEQ_E_ARG, "merge on lists: the column splits ascend strictly inside (0, n)");
+		probe.bounds.push_back(col_splits[i]);
+	}
+	probe.bounds.push_back(n);
+	if ((rc = lists_onto_context(c, list_cap, ent, hdr))) return rc;
+	hipStream_t st = c->stream;
+	HIP_TRY(c, hipMemcpyAsync(c->dp.LB, lb, c->dp_size * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(c->dp.M, max_size, c->dp_size * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(c->dp.SZ, size, c->dp_size * 4, hipMemcpyHostToDevice, st));
+	bool overflow = false;
+	rc = probe_traceback_and_merge(c, &probe, &overflow);
+	if (FSEQ_OK == rc)
+	{
+		size_t const S = c->traceback.size(), R = overflow ? 0 : c->segments.size();
+		if (n_traceback) *n_traceback = S;
+		if (traceback) std::copy(c->traceback.begin(), c->traceback.end(), traceback);
+		if (n_tau) *n_tau = probe.tau.size();
+		for (size_t j = 0; tau && j < probe.tau.size(); ++j) { tau[2 * j] = probe.tau[j].x; tau[2 * j + 1] = probe.tau[j].y; }
+		if (n_segments) *n_segments = R;
+		if (segments) std::copy(c->segments.begin(), c->segments.begin() + R, segments);
+		if (info) *info = fseq_merge_lists_info{overflow ? 1u : 0u, probe.separate ? 1u : 0u, probe.threshold_launches, probe.count_launches};
+	}
+	// nothing of this call is a run's: no result, no traceback, no segments (the size of the traceback's first copy alone stays, as after a run)
+	c->traceback.clear();
+	c->segments.clear();
+	c->tau_host.clear();
+	if (rc) return rc;
+	// (a run writes the entries its cells own and finds 0 in the others, n - 2L + 1 .. n - L - 1: the caller's words go)
+	HIP_TRY(c, hipMemsetAsync(c->dp.LB, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.M, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipMemsetAsync(c->dp.SZ, 0, c->dp_size * 4, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
 	return FSEQ_OK;
 }
 

@@ -163,6 +163,17 @@ int prepare_dp_kernels(fseq_ctx *c);         // prepare_geometry: the LDS of eve
 // the serial DP over the rounds [r_lo, r_hi): k_dp<DP_WHOLE> or k_dp<DP_PARTIAL> (fseq_dp.hpp)
 void launch_dp_serial(fseq_ctx *c, int mode, hipStream_t st, uint32_t r_lo, uint32_t r_hi);
 int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out);
+// The two halves of long_traceback_and_merge on DP arrays and lists a caller laid over the context (fseq_debug_merge_on_lists).
+// separate: the thresholds do not ride with the traceback (k_seg_tau_tb) but come from launches of their own, they and the
+// merged sizes once per column range [bounds[r], bounds[r + 1]) and summed on the host.  Out: the thresholds in the host's
+// order (empty where none were taken) and the launches made.
+struct MergeProbe {
+	bool separate = false;
+	std::vector<uint64_t> bounds;
+	std::vector<uint2> tau;
+	uint32_t threshold_launches = 0, count_launches = 0;
+};
+int probe_traceback_and_merge(fseq_ctx *c, MergeProbe *probe, bool *overflow_out);
 
 // ---- csrc/fseq_path_pass1.hip
 uint32_t scan_keyed(fseq_ctx const *c);

@@ -1,15 +1,64 @@
 // fseq_path_dp.hip -- the segmentation path, phase D and what follows it: the chunk-speculative DP driver and the serial DP's
-// launcher, the tracebacks, the greedy merge of the traceback's segments (whole lists, or list windows), and the range-minimum
-// query's debug entry point.  The one unit that instantiates k_dp<> and includes fseq_dpspec.hpp.
+// launcher, the tracebacks, the greedy merge of the traceback's segments (whole lists, or list windows), and the debug entry
+// points of the range-minimum query and of the traceback by parts.  The one unit that instantiates k_dp<> and includes
+// fseq_dpspec.hpp.
 // (The units of the path and what crosses them: fseq_path.hpp.)
 #include "fseq_path.hpp"
 #include "fseq_kernels.hpp"
 #include "fseq_dp.hpp"
 #include "fseq_dpspec.hpp"
+#include "fseq_tbcheck.hpp"
 
 namespace fseq {
 
 namespace {
+
+// one launcher per traceback kernel, on plain pointers (a run's buffers, or fseq_debug_traceback_parts' own)
+void launch_tb_windows(hipStream_t st, uint32_t const *LB, uint32_t dp_size, uint32_t L, uint32_t *exit_next, uint32_t *exit_cnt, uint32_t vlo, uint32_t vhi)
+{
+	uint32_t const nwin = (dp_size + TB_WIN - 1u) / TB_WIN;
+	hipLaunchKernelGGL(k_tb_windows, dim3(nwin), dim3(256), 0, st, LB, dp_size, L, exit_next, exit_cnt, vlo, vhi);
+}
+
+void launch_tb_chain_part(hipStream_t st, uint32_t const *exit_next, uint32_t const *exit_cnt, uint32_t start, uint32_t off0, uint32_t vlo, uint2 *head, uint32_t nwin,
+                          uint32_t *count, uint32_t *word)
+{
+	hipLaunchKernelGGL(k_tb_chain_part, dim3(1), dim3(64), 0, st, exit_next, exit_cnt, start, off0, vlo, head, nwin, count, word);
+}
+
+void launch_tb_emit(hipStream_t st, uint32_t const *LB, uint32_t const *M, uint32_t const *SZ, uint32_t dp_size, uint32_t L, uint2 const *head, uint32_t *count,
+                    uint4 *out, uint32_t cap, uint32_t vlo)
+{
+	uint32_t const nwin = (dp_size + TB_WIN - 1u) / TB_WIN;
+	hipLaunchKernelGGL(k_tb_emit, dim3(nwin), dim3(256), 0, st, LB, M, SZ, dp_size, L, head, count, out, cap, vlo);
+}
+
+// The host's side of a traceback followed part by part: which part the chain stands in, the running offset into the whole
+// list, and what a part's two words (k_tb_chain_part) may say.  lo[g] = part g's first entry, ascending.
+struct TbPartWalk {
+	uint32_t const *lo;
+	uint32_t parts;
+	size_t cap;
+	uint32_t cur, off = 0, hops = 0;
+	bool ended = false;
+	TbPartWalk(uint32_t const *lo_, uint32_t parts_, uint32_t start, size_t cap_) : lo(lo_), parts(parts_), cap(cap_), cur(start) {}
+	uint32_t owner() const
+	{
+		uint32_t g = parts - 1u;
+		while (g > 0 && cur < lo[g]) --g;
+		return g;
+	}
+	// part g reported w = {1 + the entry the chain continues at (0: it ended there), its entries}: nullptr, or why the walk ends here
+	char const *take(uint32_t g, uint32_t const *w)
+	{
+		off += w[1];
+		if (w[1] == 0 || off > cap || ++hops > parts) return "internal: the sharded traceback chain does not descend";
+		if (w[0] == 0) { ended = true; return nullptr; }
+		if (w[0] - 1u >= lo[g]) return "internal: the sharded traceback chain left a rank upwards";
+		cur = w[0] - 1u;
+		return nullptr;
+	}
+};
 
 // follow_traceback (segmentation_lp_context.cc:191-224): the lb chain is followed on the device, window by window
 // (k_tb_windows / k_tb_chain / k_tb_emit, fseq_kernels.hpp); the S visited entries come back in one small copy.
@@ -34,30 +83,22 @@ int follow_traceback_sharded(fseq_ctx *c, hipStream_t st)
 	bool const have = sh.rank < sh.active && c->own_hi[sh.rank] > c->own_lo[sh.rank];
 	uint32_t const vlo = have ? c->own_lo[sh.rank] : 0u, vhi = have ? (sh.rank + 1u == sh.active ? dp_size : c->own_hi[sh.rank]) : 0u;
 	HIP_TRY(c, hipMemsetAsync(d_count, 0, 16, st));
-	if (have) hipLaunchKernelGGL(k_tb_windows, dim3(nwin), dim3(256), 0, st, c->dp.LB, dp_size, L, d_exit_next, d_exit_cnt, vlo, vhi);
-	auto owner_of = [&](uint32_t t) {
-		uint32_t g = sh.active - 1u;
-		while (g > 0 && t < c->own_lo[g]) --g;
-		return g;
-	};
-	uint32_t cur = dp_size - 1u, off = 0, my_cnt = 0, my_off = 0, hops = 0;
-	while (true)
+	if (have) launch_tb_windows(st, c->dp.LB, dp_size, L, d_exit_next, d_exit_cnt, vlo, vhi);
+	TbPartWalk walk(c->own_lo.data(), sh.active, dp_size - 1u, cap);
+	uint32_t my_cnt = 0, my_off = 0;
+	while (!walk.ended)
 	{
-		uint32_t const g = owner_of(cur);
+		uint32_t const g = walk.owner();
 		HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, 16, st));
-		if (g == sh.rank) hipLaunchKernelGGL(k_tb_chain_part, dim3(1), dim3(64), 0, st, d_exit_next, d_exit_cnt, cur, off, vlo, d_head, nwin, d_count, sh.xbuf);
+		if (g == sh.rank) launch_tb_chain_part(st, d_exit_next, d_exit_cnt, walk.cur, walk.off, vlo, d_head, nwin, d_count, sh.xbuf);
 		if ((rc = shard_exchange(c, 4, 0))) return rc;
 		uint32_t w[4];
 		HIP_TRY(c, hipMemcpy(w, sh.xbuf, 16, hipMemcpyDeviceToHost));
-		if (g == sh.rank) { my_cnt = w[1]; my_off = off; }
-		off += w[1];
-		if (w[1] == 0 || off > cap || ++hops > sh.active) return fail(c, FSEQ_E_HIP, "internal: the sharded traceback chain does not descend");
-		if (w[0] == 0) break;                                       // the chain ended on rank g
-		if (w[0] - 1u >= c->own_lo[g]) return fail(c, FSEQ_E_HIP, "internal: the sharded traceback chain left a rank upwards");
-		cur = w[0] - 1u;
+		if (g == sh.rank) { my_cnt = w[1]; my_off = walk.off; }
+		if (char const *why = walk.take(g, w)) return fail(c, FSEQ_E_HIP, why);   // (ended: the chain ended on rank g)
 	}
-	size_t const S = off;
-	if (my_cnt) hipLaunchKernelGGL(k_tb_emit, dim3(nwin), dim3(256), 0, st, c->dp.LB, c->dp.M, c->dp.SZ, dp_size, L, d_head, d_count, c->d_tb, (uint32_t) cap, vlo);
+	size_t const S = walk.off;
+	if (my_cnt) launch_tb_emit(st, c->dp.LB, c->dp.M, c->dp.SZ, dp_size, L, d_head, d_count, c->d_tb, (uint32_t) cap, vlo);
 	// gather: every rank's entries sit at their final offsets of its own d_tb; word 4 S: "the chain ended in lb == 0"
 	if (4 * S + 2 > sh.xwords) return fail(c, FSEQ_E_ARG, "exchange buffer too small (fseq_shard_xbuf_words)");
 	HIP_TRY(c, hipMemsetAsync(sh.xbuf, 0, (4 * S + 1) * 4, st));
@@ -98,9 +139,9 @@ int follow_traceback(fseq_ctx *c, hipStream_t st)
 	uint32_t *d_count = reinterpret_cast<uint32_t *>(d_head + nwin);
 	uint32_t *d_exit_next = c->d_Mprev, *d_exit_cnt = c->dp.K.as<uint32_t>();
 	HIP_TRY(c, hipMemsetAsync(d_count, 0, 16, st));
-	hipLaunchKernelGGL(k_tb_windows, dim3(nwin), dim3(256), 0, st, c->dp.LB, dp_size, L, d_exit_next, d_exit_cnt);
+	launch_tb_windows(st, c->dp.LB, dp_size, L, d_exit_next, d_exit_cnt, 0u, 0xFFFFFFFFu);            // (the whole array is one part)
 	hipLaunchKernelGGL(k_tb_chain, dim3(1), dim3(64), 0, st, d_exit_next, d_exit_cnt, dp_size, d_head, nwin, d_count);
-	hipLaunchKernelGGL(k_tb_emit, dim3(nwin), dim3(256), 0, st, c->dp.LB, c->dp.M, c->dp.SZ, dp_size, L, d_head, d_count, c->d_tb, (uint32_t) cap);
+	launch_tb_emit(st, c->dp.LB, c->dp.M, c->dp.SZ, dp_size, L, d_head, d_count, c->d_tb, (uint32_t) cap, 0u);
 	// the count and -- in the same round trip -- as many entries as the last run of this context had (a second copy
 	// only when there are more this time)
 	size_t const guess = std::min(cap, c->tb_guess ? c->tb_guess + 16 : (size_t) 4096);
@@ -643,17 +684,11 @@ int merge_windowed(fseq_ctx *c, bool *overflow)
 	return FSEQ_OK;
 }
 
-} // namespace
-
-// ---- follow_traceback and find_segments_greedy for one attempt (the lists held their own so far): the traceback on
-// the device, the merge walk over one threshold per traceback boundary on the host.  *overflow_out: a threshold or a merged
-// size needed more of a list than it holds.
-int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out)
+// find_segments_greedy over the traceback follow_traceback left on the context: the second half of long_traceback_and_merge.
+// probe (fseq_debug_merge_on_lists alone; a run passes none): where the thresholds and counts are taken from, and what was taken.
+int merge_traceback(fseq_ctx *c, bool *overflow_out, MergeProbe *probe)
 {
 	FSEQ_LONG_LOCALS(c);
-	*overflow_out = false;
-	if ((rc = follow_traceback(c, st))) return rc;
-	if (c->tune.debug) fprintf(stderr, "[fseq] host: traceback walk + gather %.3f ms\n", now_ms() - th0);
 	uint32_t const max_seg = c->traceback.back().segment_max_size;
 	c->res.max_segment_size = max_seg;
 	c->res.dp_segment_count = c->traceback.size();
@@ -667,7 +702,8 @@ int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out)
 	if (c->lw.on) return merge_windowed(c, overflow_out);
 	uint64_t const own_lo = held_lo(c), own_hi = sharded ? sh.c_hi : n;      // columns whose lists I answer for
 	std::vector<uint2> tau(S);
-	if (S > 1 && c->tau_host.size() == S)
+	bool const separate = probe && probe->separate;
+	if (S > 1 && c->tau_host.size() == S && !separate)
 		tau = c->tau_host;                                          // came back with the traceback
 	else if (S > 1)
 	{
@@ -676,18 +712,35 @@ int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out)
 		std::vector<uint64_t> cols(S);
 		for (size_t j = 0; j < S; ++j) cols[j] = c->traceback[j].rb - 1;
 		HIP_TRY(c, hipMemcpyAsync(c->d_cols, cols.data(), S * 8, hipMemcpyHostToDevice, st));
-		launch_seg_tau(c, S, own_lo, own_hi, max_seg);
-		if (sharded)
+		if (separate)
 		{
-			HIP_TRY(c, hipMemcpyAsync(sh.xbuf, c->d_tau, S * 8, hipMemcpyDeviceToDevice, st));
-			if ((rc = shard_exchange(c, 2 * S, 0))) return rc;
-			HIP_TRY(c, hipMemcpyAsync(tau.data(), sh.xbuf, S * 8, hipMemcpyDeviceToHost, st));
+			// one launch per column range, summed word by word: what the exchange of a sharded run does with the ownership rule's zeros
+			std::vector<uint2> part(S);
+			for (size_t r = 0; r + 1 < probe->bounds.size(); ++r)
+			{
+				launch_seg_tau(c, S, probe->bounds[r], probe->bounds[r + 1], max_seg);
+				HIP_TRY(c, hipMemcpyAsync(part.data(), c->d_tau, S * 8, hipMemcpyDeviceToHost, st));
+				HIP_TRY(c, hipStreamSynchronize(st));
+				for (size_t j = 0; j < S; ++j) { tau[j].x += part[j].x; tau[j].y += part[j].y; }
+				++probe->threshold_launches;
+			}
 		}
 		else
-			HIP_TRY(c, hipMemcpyAsync(tau.data(), c->d_tau, S * 8, hipMemcpyDeviceToHost, st));
+		{
+			launch_seg_tau(c, S, own_lo, own_hi, max_seg);
+			if (sharded)
+			{
+				HIP_TRY(c, hipMemcpyAsync(sh.xbuf, c->d_tau, S * 8, hipMemcpyDeviceToDevice, st));
+				if ((rc = shard_exchange(c, 2 * S, 0))) return rc;
+				HIP_TRY(c, hipMemcpyAsync(tau.data(), sh.xbuf, S * 8, hipMemcpyDeviceToHost, st));
+			}
+			else
+				HIP_TRY(c, hipMemcpyAsync(tau.data(), c->d_tau, S * 8, hipMemcpyDeviceToHost, st));
+		}
 		HIP_TRY(c, hipStreamSynchronize(st));
 		HIP_TRY(c, hipGetLastError());
 	}
+	if (separate) probe->tau = tau;
 	// the walk itself; the merged sizes are asked for afterwards
 	MergeWalk walk(c);
 	for (size_t j = 1; j < S; ++j)
@@ -702,19 +755,56 @@ int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out)
 	if ((rc = c->d_cols.ensure(c, 2 * Q))) return rc;
 	if ((rc = c->d_tau.ensure(c, Q))) return rc;
 	HIP_TRY(c, hipMemcpyAsync(c->d_cols, qc, 2 * Q * 8, hipMemcpyHostToDevice, st));
-	uint32_t *const d_cnt = launch_seg_count(c, Q, own_lo, own_hi);
-	if (sharded)
+	if (separate)
 	{
-		HIP_TRY(c, hipMemcpyAsync(sh.xbuf, d_cnt, Q * 4, hipMemcpyDeviceToDevice, st));
-		if ((rc = shard_exchange(c, Q, 0))) return rc;
-		HIP_TRY(c, hipMemcpyAsync(cnt, sh.xbuf, Q * 4, hipMemcpyDeviceToHost, st));
+		std::vector<uint32_t> sum(Q, 0u);
+		for (size_t r = 0; r + 1 < probe->bounds.size(); ++r)
+		{
+			HIP_TRY(c, hipMemcpyAsync(cnt, launch_seg_count(c, Q, probe->bounds[r], probe->bounds[r + 1]), Q * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipStreamSynchronize(st));
+			for (size_t i = 0; i < Q; ++i) sum[i] += cnt[i];
+			++probe->count_launches;
+		}
+		std::copy(sum.begin(), sum.end(), cnt);
 	}
 	else
-		HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, Q * 4, hipMemcpyDeviceToHost, st));
+	{
+		uint32_t *const d_cnt = launch_seg_count(c, Q, own_lo, own_hi);
+		if (sharded)
+		{
+			HIP_TRY(c, hipMemcpyAsync(sh.xbuf, d_cnt, Q * 4, hipMemcpyDeviceToDevice, st));
+			if ((rc = shard_exchange(c, Q, 0))) return rc;
+			HIP_TRY(c, hipMemcpyAsync(cnt, sh.xbuf, Q * 4, hipMemcpyDeviceToHost, st));
+		}
+		else
+			HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, Q * 4, hipMemcpyDeviceToHost, st));
+	}
 	HIP_TRY(c, hipStreamSynchronize(st));
 	HIP_TRY(c, hipGetLastError());
 	for (size_t i = 0; i < Q; ++i) c->segments[walk.ask[i].seg].segment_size = cnt[i];
 	return FSEQ_OK;
+}
+
+} // namespace
+
+// ---- follow_traceback and find_segments_greedy for one attempt (the lists held their own so far): the traceback on
+// the device, the merge walk over one threshold per traceback boundary on the host.  *overflow_out: a threshold or a merged
+// size needed more of a list than it holds.
+int long_traceback_and_merge(fseq_ctx *c, double th0, bool *overflow_out)
+{
+	*overflow_out = false;
+	if (int const rc = follow_traceback(c, c->stream)) return rc;
+	if (c->tune.debug) fprintf(stderr, "[fseq] host: traceback walk + gather %.3f ms\n", now_ms() - th0);
+	return merge_traceback(c, overflow_out, nullptr);
+}
+
+// the same two halves on the DP arrays and lists a caller laid over the context (fseq_debug_merge_on_lists)
+int probe_traceback_and_merge(fseq_ctx *c, MergeProbe *probe, bool *overflow_out)
+{
+	*overflow_out = false;
+	if (int const rc = follow_traceback(c, c->stream)) return rc;
+	if (!probe->separate) probe->tau = c->tau_host;          // what rode with the traceback, whether or not a merge reads it
+	return merge_traceback(c, overflow_out, probe);
 }
 
 } // namespace fseq
@@ -772,6 +862,89 @@ int fseq_debug_rmq(int device, uint32_t const *keys, uint32_t count, uint32_t co
 		rc = FSEQ_OK;
 	} while (false);
 	A_free();
+	return rc;
+}
+
+// The traceback as a sharded run in window mode follows it, part by part in one process: follow_traceback_sharded's launchers
+// and walk; in place of the exchange, part g's two words are read back and handed to the walk.  The chain only descends, so
+// the parts are served from the last one down: each makes its view and its windows, the one the chain stands in follows its
+// share and emits it.
+int fseq_debug_traceback_parts(int device, uint64_t n, uint64_t segment_length, uint32_t const *lb, uint32_t const *max_size, uint32_t const *size,
+                               uint32_t const *part_lo, uint32_t n_parts, uint32_t const *foreign, fseq_dp_arg *traceback, uint64_t *n_traceback,
+                               uint32_t *part_entries, uint32_t *part_windows, uint64_t *bad_entry)
+{
+	if (bad_entry) *bad_entry = ~0ull;
+	if (!lb || !max_size || !size || !part_lo || 0 == n_parts || n_parts > 64) return FSEQ_E_ARG;
+	if (tb_chain_check(lb, n, segment_length, bad_entry, nullptr) != TB_CHAIN_OK) return FSEQ_E_ARG;
+	uint32_t const L = (uint32_t) segment_length, dp_size = (uint32_t) (n - segment_length + 1);
+	if (part_lo[0] != 0) return FSEQ_E_ARG;
+	for (uint32_t g = 1; g < n_parts; ++g)
+		if (part_lo[g] <= part_lo[g - 1] || part_lo[g] >= dp_size) return FSEQ_E_ARG;
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	size_t const cap = (size_t) (n / L + 2);
+	uint32_t const nwin = (dp_size + TB_WIN - 1u) / TB_WIN;
+	uint32_t *d_view = nullptr, *d_M = nullptr, *d_SZ = nullptr, *d_next = nullptr, *d_cnt = nullptr, *d_count = nullptr, *d_word = nullptr;
+	uint2 *d_head = nullptr;
+	uint4 *d_out = nullptr;
+	auto free_all = [&]() {
+		(void) hipFree(d_view); (void) hipFree(d_M); (void) hipFree(d_SZ); (void) hipFree(d_next); (void) hipFree(d_cnt); (void) hipFree(d_count);
+		(void) hipFree(d_word); (void) hipFree(d_head); (void) hipFree(d_out);
+	};
+	std::vector<uint32_t> view(dp_size), ents(n_parts, 0u), wins(n_parts, 0u);
+	std::vector<uint4> h(cap);
+	TbPartWalk walk(part_lo, n_parts, dp_size - 1u, cap);
+	uint32_t ended_in_zero = 0;
+	int rc = FSEQ_E_HIP;
+	do
+	{
+		size_t const words = (size_t) dp_size * 4;
+		if (hipMalloc((void **) &d_view, words) != hipSuccess || hipMalloc((void **) &d_M, words) != hipSuccess || hipMalloc((void **) &d_SZ, words) != hipSuccess) break;
+		if (hipMalloc((void **) &d_next, words) != hipSuccess || hipMalloc((void **) &d_cnt, words) != hipSuccess) break;
+		if (hipMalloc((void **) &d_count, 16) != hipSuccess || hipMalloc((void **) &d_word, 16) != hipSuccess) break;
+		if (hipMalloc((void **) &d_head, (size_t) nwin * sizeof(uint2)) != hipSuccess || hipMalloc((void **) &d_out, cap * sizeof(uint4)) != hipSuccess) break;
+		if (hipMemcpy(d_M, max_size, words, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_SZ, size, words, hipMemcpyHostToDevice) != hipSuccess) break;
+		bool failed = false;
+		for (uint32_t g = n_parts; g-- > 0 && !failed;)
+		{
+			failed = true;
+			uint32_t const vlo = part_lo[g], vhi = g + 1u < n_parts ? part_lo[g + 1u] : dp_size;
+			// the part's view: its own entries, and what it holds of the others' (nothing it may follow)
+			for (uint32_t t = 0; t < dp_size; ++t) view[t] = (t >= vlo && t < vhi) ? lb[t] : foreign ? foreign[t] : 0xFFFFFFFFu;
+			if (hipMemcpy(d_view, view.data(), words, hipMemcpyHostToDevice) != hipSuccess) break;
+			if (hipMemset(d_count, 0, 16) != hipSuccess || hipMemset(d_word, 0, 16) != hipSuccess) break;
+			launch_tb_windows(nullptr, d_view, dp_size, L, d_next, d_cnt, vlo, vhi);
+			bool const mine = !walk.ended && walk.owner() == g;
+			uint32_t const off0 = walk.off;
+			if (mine)
+			{
+				launch_tb_chain_part(nullptr, d_next, d_cnt, walk.cur, off0, vlo, d_head, nwin, d_count, d_word);
+				launch_tb_emit(nullptr, d_view, d_M, d_SZ, dp_size, L, d_head, d_count, d_out, (uint32_t) cap, vlo);
+			}
+			if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+			if (mine)
+			{
+				uint32_t w[4], cnt[4];
+				if (hipMemcpy(w, d_word, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cnt, d_count, 16, hipMemcpyDeviceToHost) != hipSuccess) break;
+				if (walk.take(g, w)) break;                                   // (the refusals of a sharded run)
+				if (hipMemcpy(h.data() + off0, d_out + off0, (size_t) w[1] * sizeof(uint4), hipMemcpyDeviceToHost) != hipSuccess) break;
+				ents[g] = w[1]; wins[g] = cnt[2];
+				ended_in_zero |= cnt[1];
+			}
+			failed = false;
+		}
+		if (failed || !walk.ended || ended_in_zero != 1u || walk.off == 0) break;
+		size_t const S = walk.off;
+		if (n_traceback) *n_traceback = S;
+		for (size_t j = 0; traceback && j < S; ++j)
+		{
+			uint4 const e = h[S - 1 - j];                             // the kernels list the last segment first
+			traceback[j] = fseq_dp_arg{e.y, (uint64_t) e.x + L, e.z, e.w};
+		}
+		if (part_entries) std::copy(ents.begin(), ents.end(), part_entries);
+		if (part_windows) std::copy(wins.begin(), wins.end(), part_windows);
+		rc = FSEQ_OK;
+	} while (false);
+	free_all();
 	return rc;
 }
 

@@ -294,6 +294,44 @@ typedef struct fseq_dp_lists_info {
 int  fseq_debug_dp_on_lists(fseq_ctx *ctx, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *cuts, uint32_t n_cuts,
                             uint32_t *lb, uint32_t *max_size, uint32_t *size, fseq_dp_lists_info *info);
 
+/* The traceback and the greedy merge alone on caller-supplied DP arrays and lists, through follow_traceback and the merge half
+ * of long_traceback_and_merge as an unsharded run calls them (debug / tests): k_tb_windows, k_tb_chain, k_tb_emit, k_seg_tau_tb,
+ * k_seg_tau, k_seg_count (csrc/fseq_kernels.hpp).  ctx, list_cap, ent and hdr as for fseq_debug_dp_on_lists, with the same
+ * refusals and the same fseq_debug_dp_lists_check.  lb / max_size / size: n - L + 1 words each, copied over the DP's arrays.  Of
+ * lb only the chain from entry n - L is checked, on the host before any runtime call (csrc/fseq_tbcheck.hpp): an entry t on it has
+ * lb == 0 or L <= lb <= t, and the chain ends in lb == 0 within n / L + 2 entries; FSEQ_E_ARG with a message naming the entry
+ * otherwise.  Entries off the chain may hold anything.
+ *   flags bit 0 clear: the thresholds ride with the traceback (k_seg_tau_tb), as an unsharded run takes them; col_splits are refused;
+ *   flags bit 0 set: they come from launches of k_seg_tau of their own, and the merged sizes from k_seg_count, once per column range
+ *     [0, s0), [s0, s1), ... [s_last, n) of col_splits[n_splits] (strictly ascending inside (0, n); none: one range), summed element
+ *     by element on the host -- what the exchange of a sharded run does with the zeros the ownership rule leaves.
+ * Out, each or NULL: the traceback (room for n / L + 2), first segment first, and its count; the thresholds tau[count][2] =
+ * {tau, kind} in the traceback's order and *n_tau, how many were taken (entry 0 is the first segment's own column, which no
+ * boundary reads; flag set: 0 where the traceback has one entry or max_size[n - L] >= m, and no launch was made); the merged
+ * segments (room for n / L + 2) and their count (0 where max_size[n - L] >= m, and on overflow); info = {a list ended before a
+ * threshold could be told, flags bit 0, launches of k_seg_tau, launches of k_seg_count}.
+ * The context holds no result afterwards and no lists fseq_debug_column_list would answer for; a following run is unaffected. */
+typedef struct fseq_merge_lists_info {
+	uint32_t overflow, tau_separate, threshold_launches, count_launches;
+} fseq_merge_lists_info;
+int  fseq_debug_merge_on_lists(fseq_ctx *ctx, uint32_t list_cap, uint32_t const *ent, uint32_t const *hdr, uint32_t const *lb, uint32_t const *max_size,
+                               uint32_t const *size, uint32_t flags, uint64_t const *col_splits, uint32_t n_splits, fseq_dp_arg *traceback,
+                               uint64_t *n_traceback, uint32_t *tau, uint64_t *n_tau, fseq_segment *segments, uint64_t *n_segments,
+                               fseq_merge_lists_info *info);
+
+/* The traceback as a sharded run in window mode follows it, part by part in one process without ranks (debug / tests; no
+ * context).  lb / max_size / size: n - L + 1 words each (the chain check of fseq_debug_merge_on_lists runs first; *bad_entry, or
+ * NULL, the entry it names).  part_lo[n_parts], n_parts <= 64, strictly ascending from part_lo[0] == 0: part g holds the entries
+ * [part_lo[g], part_lo[g + 1]), the last one up to n - L + 1.  Every part makes its view of lb -- its own entries, every other entry
+ * from foreign[n - L + 1], or 0xFFFFFFFF where foreign is NULL -- and runs k_tb_windows(vlo, vhi) on it; the part the chain stands
+ * in runs k_tb_chain_part and k_tb_emit(vlo), and its two words go to the host walk a sharded run drives (in place of the
+ * exchange).  Out, each or NULL: the whole traceback (room for n / L + 2), first segment first, and its count; part_entries /
+ * part_windows [n_parts]: the entries and windows of the chain in each part (0: not visited).  FSEQ_E_HIP where the walk
+ * refuses what a part reports, as a sharded run would.  Everything is freed on every exit. */
+int  fseq_debug_traceback_parts(int device, uint64_t n, uint64_t segment_length, uint32_t const *lb, uint32_t const *max_size, uint32_t const *size,
+                                uint32_t const *part_lo, uint32_t n_parts, uint32_t const *foreign, fseq_dp_arg *traceback, uint64_t *n_traceback,
+                                uint32_t *part_entries, uint32_t *part_windows, uint64_t *bad_entry);
+
 #ifdef __cplusplus
 }
 #endif
