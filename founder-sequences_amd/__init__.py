@@ -165,6 +165,7 @@ EXPORTS = [
     "fseq_set_rows_streamed_without_identity_columns", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
     "fseq_join_score", "fseq_join_score_host", "fseq_debug_join_score_path", "fseq_debug_join_score",
     "fseq_block_graph", "fseq_write_block_graph", "fseq_debug_graph_file",
+    "fseq_debug_local_pass",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -174,7 +175,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
                  "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
-                 "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file"]
+                 "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -311,6 +312,7 @@ def load_library():
     L.fseq_debug_merge_on_lists.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(u64), vp, C.POINTER(u64), vp,
                                             C.POINTER(u64), C.POINTER(MergeListsInfo)]
     L.fseq_debug_traceback_parts.argtypes = [C.c_int, u64, u64, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(u64), vp, vp, C.POINTER(u64)]
+    L.fseq_debug_local_pass.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.fseq_get_segments_restored.argtypes = [vp, vp]
     L.fseq_write_segments_restored.argtypes = [vp, C.c_int, C.c_char_p]
     L.fseq_debug_restored_bounds.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp]
@@ -595,6 +597,23 @@ def _dp_lists(ent, hdr):
     if ent.ndim != 3 or ent.shape[2] != 2 or hdr.shape != (ent.shape[0], 4):
         raise FseqError(FSEQ_E_ARG, "DP lists: ent is [n][stride][2], hdr [n][4]")
     return ent, hdr
+
+
+def local_pass_packed(d, s, device=0):
+    """The packed local pass of phase C's partition step on one workgroup (fseq_debug_local_pass): d, s [threads][E] values below
+    2^16 and symbols 0 .. 4 (4: an unused position, value 0), threads a multiple of 64 up to 1024, E one of 11, 12, 15.  Returns
+    (dnew [threads][E], tails [threads][4]) as uint32."""
+    L = load_library()
+    d = np.ascontiguousarray(d, dtype=np.uint32)
+    s = np.ascontiguousarray(s, dtype=np.uint32)
+    if d.ndim != 2 or d.shape != s.shape:
+        raise ValueError("d and s: [threads][rows per thread]")
+    dnew = np.zeros(d.shape, dtype=np.uint32)
+    tails = np.zeros((d.shape[0], 4), dtype=np.uint32)
+    rc = L.fseq_debug_local_pass(int(device), d.shape[0], d.shape[1], d.ctypes.data, s.ctypes.data, dnew.ctypes.data, tails.ctypes.data)
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return dnew, tails
 
 
 def dp_lists_check(m, segment_length, ent, hdr):

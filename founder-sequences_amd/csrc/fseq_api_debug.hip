@@ -8,7 +8,54 @@
 
 using namespace fseq;
 
+namespace {
+
+// one workgroup of the packed local pass (fseq_localpass.hpp, what partition_step's PL branch runs): thread t takes the
+// positions [t * E, (t + 1) * E) and writes their new values and its four tail maxima
+template <int E>
+__global__ __launch_bounds__(1024) void k_local_pass_debug(uint32_t const *d_in, uint32_t const *s_in, uint32_t *dnew_out, uint32_t *tails_out)
+{
+	uint32_t const t = threadIdx.x;
+	uint32_t d[E], s[E], dnew[E], run[4];
+#pragma unroll
+	for (int e = 0; e < E; ++e) { d[e] = d_in[t * E + e]; s[e] = s_in[t * E + e]; }
+	local_pass_packed<E>(d, s, dnew, run);
+#pragma unroll
+	for (int e = 0; e < E; ++e) dnew_out[t * E + e] = dnew[e];
+#pragma unroll
+	for (int x = 0; x < 4; ++x) tails_out[t * 4 + x] = run[x];
+}
+
+} // namespace
+
 extern "C" {
+
+int fseq_debug_local_pass(int device, uint32_t threads, uint32_t rows_per_thread, uint32_t const *d, uint32_t const *s, uint32_t *dnew, uint32_t *tails)
+{
+	uint32_t const E = rows_per_thread;
+	if (!d || !s || !dnew || !tails || threads == 0 || threads > 1024 || threads % 64 != 0 || (E != 11 && E != 12 && E != 15)) return FSEQ_E_ARG;
+	size_t const n = (size_t) threads * E;
+	// what the kernels guarantee the pass: values below 2^16, symbols 0 .. 4, an unused position (4) with the value 0
+	for (size_t i = 0; i < n; ++i)
+		if (d[i] > 0xFFFFu || s[i] > 4u || (s[i] == 4u && d[i] != 0u)) return FSEQ_E_ARG;
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	uint32_t *g_d = nullptr, *g_s = nullptr, *g_o = nullptr, *g_t = nullptr;
+	int rc = FSEQ_E_HIP;
+	do
+	{
+		if (hipMalloc((void **) &g_d, n * 4) != hipSuccess || hipMalloc((void **) &g_s, n * 4) != hipSuccess) break;
+		if (hipMalloc((void **) &g_o, n * 4) != hipSuccess || hipMalloc((void **) &g_t, (size_t) threads * 16) != hipSuccess) break;
+		if (hipMemcpy(g_d, d, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(g_s, s, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+		if (E == 11) hipLaunchKernelGGL(k_local_pass_debug<11>, dim3(1), dim3(threads), 0, 0, g_d, g_s, g_o, g_t);
+		else if (E == 12) hipLaunchKernelGGL(k_local_pass_debug<12>, dim3(1), dim3(threads), 0, 0, g_d, g_s, g_o, g_t);
+		else hipLaunchKernelGGL(k_local_pass_debug<15>, dim3(1), dim3(threads), 0, 0, g_d, g_s, g_o, g_t);
+		if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+		if (hipMemcpy(dnew, g_o, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(tails, g_t, (size_t) threads * 16, hipMemcpyDeviceToHost) != hipSuccess) break;
+		rc = FSEQ_OK;
+	} while (false);
+	(void) hipFree(g_d); (void) hipFree(g_s); (void) hipFree(g_o); (void) hipFree(g_t);
+	return rc;
+}
 
 int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 {

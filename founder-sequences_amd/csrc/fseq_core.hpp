@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fseq_localpass.hpp"
+
 namespace fseq {
 
 constexpr int WAVE = 64;
@@ -293,7 +295,9 @@ struct TileCarry {
 // waves of the workgroup that do (at most 64 + 16: 7 bits) -- so the values may be anything below 2^25 whatever T * E is
 // (phase B and pass 2 scan absolute column numbers: C5's (1024, 10) had 18 bits for them, the streamed rows none).  All a
 // key's count has to do is grow wherever the bucket occurs; the rows in front of a thread come from the count scan.
-template <int T, int E, int SIGMA, bool TILE = false, bool IDLE0 = false, int KS = 0, bool PW = false, bool FM = false, bool KO = false>
+// PL ("packed local"; four symbols, KS = 16, not PW): the plain local pass with the four running maxima as 16-bit halves of
+// two registers (fseq_localpass.hpp): eleven instead of sixteen vector instructions a row, the same outputs.
+template <int T, int E, int SIGMA, bool TILE = false, bool IDLE0 = false, int KS = 0, bool PW = false, bool FM = false, bool KO = false, bool PL = false>
 __device__ __forceinline__ void partition_step(
 	uint32_t const (&d)[E], uint32_t const (&s)[E], uint32_t const first_val,
 	StepScratch<T, SIGMA> &scr, uint32_t (&dst)[E], uint32_t (&dnew)[E], TileCarry *tc = nullptr, uint32_t *runs = nullptr
@@ -478,11 +482,15 @@ __device__ __forceinline__ void partition_step(
 	}
 	else
 	{
+	static_assert(!PL || (SIGMA == 4 && KS == 16 && !PW), "packed local pass: four symbols, values below 2^16, not pairwise");
+	if constexpr (PL) local_pass_packed<E>(d, s, dnew, run);
 #pragma unroll
 	for (int e = 0; e < E; ++e)
 	{
 		uint32_t const c = s[e];
 		bool const act = c < (uint32_t) SIGMA;
+		if constexpr (!PL)
+		{
 		uint32_t const de = d[e];
 		uint32_t o = 0;
 #pragma unroll
@@ -497,6 +505,7 @@ __device__ __forceinline__ void partition_step(
 		// (the value is needed only behind the barrier; left alone, the compiler sinks the four selects there and keeps
 		// the four (c == x) conditions of every row alive in SGPR pairs instead -- in kernels that already spill them)
 		asm volatile("" : "+v"(dnew[e]));
+		}
 		if constexpr (SIGMA == 4)
 		{
 			uint32_t const sh = c * 4u;                        // (c <= 4)

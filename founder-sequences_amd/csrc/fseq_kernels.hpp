@@ -696,6 +696,15 @@ __host__ __device__ constexpr bool columns_pairwise(int T, int E, int SIGMA, boo
 	return SIGMA == 4 && ((E >= 2 && E <= FSEQ_PW_MAX_E && !(T >= 1024 && E >= 7 && !PK)) || (PK && E >= 9 && T * E <= 10240));
 }
 
+// the plain local pass with packed 16-bit running maxima (partition_step's PL, fseq_localpass.hpp): every four-symbol configuration
+// that does not take the pairwise pass.  (Not 1024 x 7 with 32-bit rows: 96 -> 98 VGPRs there, one register past five waves per
+// SIMD in the compiler's count.  Every other instantiation keeps its scratch of 0 and its occupancy: profiles/r13_kernel_resource_usage.txt.)
+__host__ __device__ constexpr bool columns_packed(int T, int E, int SIGMA, bool PK)
+{
+	if (!PK && T >= 1024 && E == 7) return false;
+	return SIGMA == 4 && !columns_pairwise(T, E, SIGMA, PK);
+}
+
 // the resolve of a step as a read of per-thread run slots (partition_step's FM): wherever 4 * T more words of LDS are to be had
 __host__ __device__ constexpr bool columns_lookup(int T, int E, int SIGMA, bool PK) { return columns_pairwise(T, E, SIGMA, PK) || (SIGMA == 4 && PK && T * E <= 10240); }
 // (five slots per thread where a thread may hold an unused position, symbol 4: the pairwise pass writes it, the slim configuration's lookup reads it)
@@ -822,6 +831,7 @@ __device__ __forceinline__ void columns_body(char *smem,
 	uint32_t *sscr = cv.take<uint32_t>(T / WAVE + 1);
 	constexpr bool PW = columns_pairwise(T, E, SIGMA, PK);
 	constexpr bool LU = columns_lookup(T, E, SIGMA, PK);
+	constexpr bool PL = columns_packed(T, E, SIGMA, PK);
 	uint32_t *runs = LU ? cv.take<uint32_t>(columns_run_words(T, E, SIGMA, PK)) : nullptr;
 	uint32_t const tid = threadIdx.x;
 	uint32_t const p0 = EW ? (tid >= 64u ? (tid - 64u) * E : 0x7FFF0000u) : tid * E;     // 0x7FFF0000: owns nothing (every p0 + e >= m)
@@ -1090,9 +1100,9 @@ __device__ __forceinline__ void columns_body(char *smem,
 			// (value ids: D0 + nb <= m + B < 65536 -- the LDS of the id histogram bounds B long before -- so the keyed scan)
 #ifdef FSEQ_KC_STAMPS
 			kcs.last = clock64();
-			partition_step<T, E, SIGMA, false, EW, 16, PW, LU>(d, s, D0 + j, scr, dst, dnew, nullptr, runs, &kcs);
+			partition_step<T, E, SIGMA, false, EW, 16, PW, LU, false, PL>(d, s, D0 + j, scr, dst, dnew, nullptr, runs, &kcs);
 #else
-			partition_step<T, E, SIGMA, false, EW, 16, PW, LU>(d, s, D0 + j, scr, dst, dnew, nullptr, runs);
+			partition_step<T, E, SIGMA, false, EW, 16, PW, LU, false, PL>(d, s, D0 + j, scr, dst, dnew, nullptr, runs);
 #endif
 
 #pragma unroll

@@ -332,6 +332,13 @@ int  fseq_debug_traceback_parts(int device, uint64_t n, uint64_t segment_length,
                                 uint32_t const *part_lo, uint32_t n_parts, uint32_t const *foreign, fseq_dp_arg *traceback, uint64_t *n_traceback,
                                 uint32_t *part_entries, uint32_t *part_windows, uint64_t *bad_entry);
 
+/* The packed local pass of phase C's partition step alone (csrc/fseq_localpass.hpp; debug / tests; no context): one workgroup of
+ * `threads` threads (a multiple of 64, at most 1024), thread t over the positions [t * E, (t + 1) * E), E = rows_per_thread one of
+ * 11, 12, 15.  d / s: threads * E values below 2^16 and symbols 0 .. 4, an unused position (symbol 4) with the value 0;
+ * FSEQ_E_ARG otherwise, before the device is touched.  Out: dnew[threads * E], the rows' new values (0 for an unused position),
+ * and tails[threads * 4], every thread's maximum behind its last row of each symbol (over all its rows where the symbol is absent). */
+int  fseq_debug_local_pass(int device, uint32_t threads, uint32_t rows_per_thread, uint32_t const *d, uint32_t const *s, uint32_t *dnew, uint32_t *tails);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,12 @@ __device__ __forceinline__ uint64_t memtime()
 #define I_87(R) "v_max_u16 " R ", " R ", %16\n\tv_max_u32 " R ", " R ", %17\n\t"
 #define I_88(R) "v_add_u32 " R ", " R ", %16\n\tv_max_u32 " R ", " R ", %17\n\t"
 #define I_89(R) "v_add_u32 " R ", " R ", %16\n\tv_max_u32_dpp " R ", " R ", " R " row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+// the packed local pass (csrc/fseq_localpass.hpp) and the forms weighed against it
+#define I_92(R) "v_pk_mul_lo_u16 " R ", " R ", %16\n\t"
+#define I_93(R) "v_pk_max_u16 " R ", " R ", %16 op_sel_hi:[1,0]\n\t"
+#define I_94(R) "v_perm_b32 " R ", -1, %18, " R "\n\t"
+#define I_95(R) "v_mad_u32_u24 " R ", " R ", %18, %18\n\t"
+#define I_96(R) "v_mul_lo_u32 " R ", " R ", %18\n\t"
 
 #define CLASSES(X)                                                                           \
 	X(0, "v_max_u32 (VOP2)", I_0)                                         \
@@ -180,7 +186,10 @@ __device__ __forceinline__ uint64_t memtime()
 	X(82, "[v_cmp -> vcc, v_cndmask vcc, v_max_u32, v_cndmask vcc] (cost per QUAD)", I_82) X(83, "[v_cndmask vcc, v_max_u32] (cost per PAIR)", I_83) \
 	X(84, "[v_cndmask vcc, v_cndmask_e64 SGPR pair] (cost per PAIR)", I_84) X(85, "[v_cndmask vcc, s_nop 0] x2 (cost per two cndmask)", I_85) \
 	X(86, "[v_cndmask vcc x3, v_add_u32] (cost per QUAD)", I_86) X(87, "[v_max_u16, v_max_u32] (cost per PAIR)", I_87) X(88, "[v_add_u32, v_max_u32] (cost per PAIR)", I_88) \
-	X(89, "[v_add_u32, v_max_u32_dpp] (cost per PAIR)", I_89)
+	X(89, "[v_add_u32, v_max_u32_dpp] (cost per PAIR)", I_89) \
+	X(90, "v_lshlrev_b64 (register shift)", I_NONE) X(91, "v_lshrrev_b64 (register shift)", I_NONE) X(92, "v_pk_mul_lo_u16 (VOP3P)", I_92) \
+	X(93, "v_pk_max_u16 (VOP3P, op_sel_hi:[1,0])", I_93) X(94, "v_perm_b32 (inline constant, SGPR, register selector)", I_94) \
+	X(95, "v_mad_u32_u24 (two SGPR operands)", I_95) X(96, "v_mul_lo_u32 (SGPR operand)", I_96)
 
 template <int CLS>
 __global__ __launch_bounds__(1024) void k_rate(uint64_t *ticks, uint32_t *sink, uint32_t seed)
@@ -215,6 +224,18 @@ __global__ __launch_bounds__(1024) void k_rate(uint64_t *ticks, uint32_t *sink, 
 			for (int rep = 0; rep < 2; ++rep)
 #pragma unroll
 				for (int i = 0; i < 8; ++i) asm volatile("v_lshlrev_b64 %0, 1, %0" : "+v"(q[i]));
+		}
+		else if constexpr (CLS == 90 || CLS == 91)
+		{
+			uint64_t *q = reinterpret_cast<uint64_t *>(r);
+#pragma unroll
+			for (int rep = 0; rep < 2; ++rep)
+#pragma unroll
+				for (int i = 0; i < 8; ++i)
+				{
+					if constexpr (CLS == 90) asm volatile("v_lshlrev_b64 %0, %1, %0" : "+v"(q[i]) : "v"(a));
+					else asm volatile("v_lshrrev_b64 %0, %1, %0" : "+v"(q[i]) : "v"(a));
+				}
 		}
 		else if constexpr (CLS == 32)
 		{
