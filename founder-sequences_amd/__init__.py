@@ -103,6 +103,16 @@ class GraphFileStats(C.Structure):
     _fields_ = [("batches", C.c_uint64 * 3), ("lines", C.c_uint64 * 3), ("bytes", C.c_uint64 * 3)]
 
 
+class GraphThreadSummary(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("segments", C.c_uint64), ("segments_matched", C.c_uint64), ("junctions_linked", C.c_uint64),
+                ("junctions_novel", C.c_uint64), ("walks", C.c_uint64), ("rows_on_graph", C.c_uint64), ("ms_device", C.c_double)]
+
+
+class GraphThreadInfo(C.Structure):
+    _fields_ = [("key_bits", C.c_uint32), ("table_slots", C.c_uint32), ("candidates_verified", C.c_uint64), ("candidates_rejected", C.c_uint64),
+                ("queries_out_of_alphabet", C.c_uint64)]
+
+
 class DpListsInfo(C.Structure):
     _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
 
@@ -130,6 +140,12 @@ JOIN_SCORE_GAP = 0xFFFF        # ... JS_GAP: a slot's class where its row is a g
 GRAPH_NODE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("segment", "<u4"), ("cls", "<u4"), ("rep_row", "<u4"), ("rows", "<u4")])
 GRAPH_EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("rows", "<u4"), ("junction", "<u4")])
 GRAPH_PATHS = 1                # fseq_write_block_graph's flag: the P lines
+GRAPH_NONE = 0xFFFFFFFF        # FSEQ_GRAPH_NONE: no node of a segment carries the query's substring / no edge joins the two nodes
+# fseq_graph_thread_row (include/fseq.h), 40 bytes, and fseq_graph_thread_segment, 16 bytes
+GRAPH_THREAD_ROW_DTYPE = np.dtype([("columns_matched", "<u8"), ("longest_walk_columns", "<u8"), ("segments_matched", "<u4"), ("junctions_linked", "<u4"),
+                                   ("junctions_novel", "<u4"), ("walks", "<u4"), ("longest_walk_segments", "<u4"), ("reserved", "<u4")])
+GRAPH_THREAD_SEGMENT_DTYPE = np.dtype([("matched", "<u4"), ("linked", "<u4"), ("novel", "<u4"), ("reserved", "<u4")])
+GRAPH_THREAD_MAX_CLASSES = 4096    # csrc/fseq_graphthread.hpp, GT_MAX_CLASSES
 
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
@@ -166,6 +182,7 @@ EXPORTS = [
     "fseq_join_score", "fseq_join_score_host", "fseq_debug_join_score_path", "fseq_debug_join_score",
     "fseq_block_graph", "fseq_write_block_graph", "fseq_debug_graph_file",
     "fseq_debug_local_pass",
+    "fseq_graph_thread_rows", "fseq_graph_thread_held_out", "fseq_debug_graph_thread",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -175,7 +192,8 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
                  "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
-                 "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass"]
+                 "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass",
+                 "fseq_debug_graph_thread"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -331,6 +349,9 @@ def load_library():
     L.fseq_block_graph.argtypes = [vp, vp, vp, vp, C.POINTER(GraphSummary)]
     L.fseq_write_block_graph.argtypes = [vp, C.c_uint32, C.c_int, C.c_char_p]
     L.fseq_debug_graph_file.argtypes = [vp, C.POINTER(GraphFileStats)]
+    L.fseq_graph_thread_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
+    L.fseq_graph_thread_held_out.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
+    L.fseq_debug_graph_thread.argtypes = [vp, C.POINTER(GraphThreadInfo)]
     _lib = L
     return L
 
@@ -1250,6 +1271,48 @@ class SegmentationContext:
         st = GraphFileStats()
         self._check(self.L.fseq_debug_graph_file(self.h, C.byref(st)))
         return {name: {"batches": st.batches[k], "lines": st.lines[k], "bytes": st.bytes[k]} for k, name in enumerate(("nodes", "links", "paths"))}
+
+    # ---- rows that are not the graph's own threaded through it
+    def _graph_thread(self, call, n_rows, want_nodes, want_steps):
+        S = int(self.result.segment_count) if self.result is not None else 0
+        nodes = np.zeros((S, n_rows), dtype=np.uint32) if want_nodes else None
+        steps = np.zeros((max(S, 1) - 1, n_rows), dtype=np.uint32) if want_steps else None
+        per_row = np.zeros(n_rows, dtype=GRAPH_THREAD_ROW_DTYPE)
+        per_segment = np.zeros(S, dtype=GRAPH_THREAD_SEGMENT_DTYPE)
+        sm = GraphThreadSummary()
+        self._check(call(None if nodes is None else nodes.ctypes.data, None if steps is None else steps.ctypes.data, per_row.ctypes.data,
+                         per_segment.ctypes.data if S else None, C.byref(sm)))
+        return {"nodes": nodes, "steps": steps, "per_row": per_row, "per_segment": per_segment,
+                "summary": {k: getattr(sm, k) for k, _ in GraphThreadSummary._fields_}}
+
+    def graph_thread_rows(self, queries, want_nodes=True, want_steps=True):
+        """Thread rows that are NOT the alignment's through the founder block graph of the finished run (fseq_graph_thread_rows):
+        queries a C-contiguous uint8 array [n_rows, n] of raw bytes (or a list of bytes objects of length n).  Returns {"nodes":
+        [segments, n_rows], the node (block_graph()'s ids) whose substring query q carries in segment s, or GRAPH_NONE; "steps":
+        [segments - 1, n_rows], the index into block_graph()["edges"] of the edge between the two nodes of a junction, or
+        GRAPH_NONE (both nodes there and no edge: a novel junction); "per_row" (GRAPH_THREAD_ROW_DTYPE); "per_segment"
+        (GRAPH_THREAD_SEGMENT_DTYPE); "summary": a dict}.  Without want_nodes / want_steps only the statistics leave the device
+        and the entry is None.  The run's results and the last match stay as they were."""
+        a = queries
+        if not isinstance(a, np.ndarray):
+            a = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in a], dtype=np.uint8).reshape(len(a), -1)
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2 or (a.shape[0] and a.shape[1] != self.n):
+            raise ValueError("graph_thread_rows: queries must be rows of n = %d bytes" % self.n)
+        rows = (C.c_void_p * max(a.shape[0], 1))(*[a.ctypes.data + r * a.strides[0] for r in range(a.shape[0])])
+        return self._graph_thread(lambda *out: self.L.fseq_graph_thread_rows(self.h, rows, a.shape[0], *out), a.shape[0], want_nodes, want_steps)
+
+    def graph_thread_held_out(self, want_nodes=True, want_steps=True):
+        """... the held-out rows of a context made by without_rows(), where they lie on the device (fseq_graph_thread_held_out):
+        nothing is uploaded; query q is held_out()[1][q]."""
+        return self._graph_thread(lambda *out: self.L.fseq_graph_thread_held_out(self.h, *out), int(getattr(self, "n_held", 0)), want_nodes, want_steps)
+
+    def graph_thread_info(self):
+        """How the last graph_thread_rows() / graph_thread_held_out() found its nodes (fseq_debug_graph_thread): dict(key_bits,
+        table_slots, candidates_verified, candidates_rejected, queries_out_of_alphabet)."""
+        info = GraphThreadInfo()
+        self._check(self.L.fseq_debug_graph_thread(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in GraphThreadInfo._fields_}
 
     def write_founders_device(self, permutations, path):
         """--output-founders from the alignment resident on the device (no host rows)."""

@@ -1,5 +1,7 @@
 // fseq_api_graph.hip -- the part of the C ABI (include/fseq.h) behind the founder block graph: fseq_block_graph (the graph as
-// arrays), fseq_write_block_graph (the GFA 1.0 file from the device, csrc/fseq_graph.hpp) and fseq_debug_graph_file.
+// arrays), fseq_write_block_graph (the GFA 1.0 file from the device, csrc/fseq_graph.hpp) and fseq_debug_graph_file; and
+// fseq_graph_thread_rows / fseq_graph_thread_held_out (rows that are not the graph's own threaded through it,
+// csrc/fseq_graphthread.hpp) with fseq_debug_graph_thread.
 //
 // No counterpart in the reference.  Both entries build on the device front of fseq_join_greedy (fseq_joinprep.hpp, unchanged):
 // k_join_classes_wide numbers the classes of every merged segment, k_join_edges_wide<false> / k_join_scan / <true> leave the
@@ -9,6 +11,7 @@
 #include "fseq_ctx.hpp"
 #include "fseq_joinprep.hpp"
 #include "fseq_graph.hpp"
+#include "fseq_graphthread.hpp"
 
 using namespace fseq;
 
@@ -107,6 +110,127 @@ static int graph_refusals(fseq_ctx *c)
 	if (c->p.m > 0x7FFFFFFFull || c->segments.size() > 0x7FFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "block graph: 2^31 rows or segments or more");
 	return FSEQ_OK;
 }
+
+// what the threading refuses beyond the block graph's refusals
+static int graph_thread_refusals(fseq_ctx *c)
+{
+	if (int const rc = graph_refusals(c)) return rc;
+	if (c->idn.have) return fail(c, FSEQ_E_UNSUPPORTED, "graph threading: a context made by fseq_create_without_identity_columns (queries in source co-ordinates, with their exception cells, are not served)");
+	if (c->res.max_segment_size > GT_MAX_CLASSES) return fail(c, FSEQ_E_UNSUPPORTED, "graph threading: more than 4,096 classes in a segment (there is no host form)");
+	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
+	return FSEQ_OK;
+}
+
+// both entries behind their refusals: the Q queries at q (column-major, packed at qbsh, qld bytes a column) through the graph
+static int graph_thread(fseq_ctx *c, uint8_t const *q, size_t qld, uint32_t qbsh, uint32_t Q, uint32_t *nodes, uint32_t *steps,
+                        fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary)
+{
+	double const t0 = now_ms();
+	hipStream_t st = c->stream;
+	GraphTables T(c);
+	if (int const rc = T.build(true)) return rc;
+	size_t const S = T.S;
+	uint32_t const X = T.X;
+	uint32_t slots = GT_MIN_SLOTS;
+	while (slots < 2u * X) slots *= 2u;
+	size_t const lds = (size_t) slots * (sizeof(uint64_t) + sizeof(uint32_t));
+	uint32_t const key_bits = c->tune.graph_thread_key_bits > 0 ? (uint32_t) std::min(c->tune.graph_thread_key_bits, 64) : 64u;
+	DevTemp<uint64_t> d_keys(c);
+	DevTemp<uint32_t> d_nodes(c), d_steps(c);
+	DevTemp<fseq_graph_thread_row> d_rows(c);
+	DevTemp<fseq_graph_thread_segment> d_segs(c);
+	DevTemp<unsigned long long> d_stats(c);
+	int rc;
+	if ((rc = d_keys.alloc(S * X)) || (rc = d_nodes.alloc(S * Q)) || (rc = d_steps.alloc(std::max<size_t>(T.pairs, 1) * Q)) ||
+	    (rc = d_rows.alloc(Q)) || (rc = d_segs.alloc(S)) || (rc = d_stats.alloc(3)))
+	{ (void) hipStreamSynchronize(st); return rc; }
+	std::vector<fseq_graph_thread_row> rows;
+	try { rows.resize(Q); }
+	catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "graph threading: the rows' statistics on the host"); }
+	GraphThreadArgs A{};
+	A.seg_lb = T.d_lb; A.seg_rb = T.d_rb; A.count = T.d_count; A.rep = T.d_rep; A.noff = T.d_noff;
+	A.m = (uint32_t) T.m; A.X = X; A.S = (uint32_t) S; A.n = c->p.n;
+	A.msa = c->d_msa; A.ld = c->ld; A.bsh = c->bsh;
+	A.q = q; A.qld = qld; A.qbsh = qbsh; A.Q = Q; A.sigma = c->sigma;
+	A.key_bits = key_bits; A.slots = slots;
+	A.keys = d_keys; A.nodes = d_nodes; A.steps = d_steps;
+	A.edges = T.d_edges; A.offset = T.d_off; A.nedges = T.d_ne; A.pairs = T.pairs; A.n_edges = T.d_edges.base ? T.edges : 0u;
+	A.stats = d_stats;
+	hipError_t e = hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), st);
+	if (e == hipSuccess) e = allow_lds(k_gt_thread, lds);
+	if (e != hipSuccess) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_HIP, "graph threading: preparation", e); }
+	uint32_t const tiles = (uint32_t) std::min<size_t>(((size_t) Q + GT_T - 1) / GT_T, 1024);
+	hipLaunchKernelGGL(k_gt_keys, dim3((uint32_t) S, (X + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A);
+	hipLaunchKernelGGL(k_gt_thread, dim3((uint32_t) S, tiles), dim3(GT_T), lds, st, A);
+	if (T.pairs) hipLaunchKernelGGL(k_gt_steps, dim3(T.pairs, tiles), dim3(GT_T), 0, st, A);
+	hipLaunchKernelGGL(k_gt_rows, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A, (fseq_graph_thread_row *) d_rows);
+	if (per_segment) hipLaunchKernelGGL(k_gt_segments, dim3((uint32_t) S), dim3(GT_T), 0, st, A, (fseq_graph_thread_segment *) d_segs);
+	unsigned long long stats[3] = {0, 0, 0};
+	e = hipMemcpyAsync(rows.data(), d_rows, (size_t) Q * sizeof(fseq_graph_thread_row), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && nodes) e = hipMemcpyAsync(nodes, d_nodes, S * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && steps && T.pairs) e = hipMemcpyAsync(steps, d_steps, (size_t) T.pairs * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && per_segment) e = hipMemcpyAsync(per_segment, d_segs, S * sizeof(fseq_graph_thread_segment), hipMemcpyDeviceToHost, st);
+	hipError_t const es = hipStreamSynchronize(st);                  // (the host arrays are written to here, whatever was queued)
+	if (e == hipSuccess) e = es;
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "graph threading", e);
+	fseq_graph_thread_summary sm{};
+	sm.rows = Q; sm.segments = S;
+	for (fseq_graph_thread_row const &r : rows)
+	{
+		sm.segments_matched += r.segments_matched; sm.junctions_linked += r.junctions_linked; sm.junctions_novel += r.junctions_novel; sm.walks += r.walks;
+		sm.rows_on_graph += r.walks == 1u && r.longest_walk_segments == S;
+	}
+	if (per_row) memcpy(per_row, rows.data(), (size_t) Q * sizeof(fseq_graph_thread_row));
+	sm.ms_device = now_ms() - t0;
+	if (summary) *summary = sm;
+	c->graphthread.have = true;
+	c->graphthread.info = fseq_graph_thread_info{key_bits, slots, stats[0], stats[1], stats[2]};
+	return FSEQ_OK;
+}
+
+extern "C" {
+
+int fseq_graph_thread_rows(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t *nodes, uint32_t *steps,
+                           fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!rows || 0 == n_rows) return fail(c, FSEQ_E_ARG, "graph threading: no query rows");
+	for (uint32_t i = 0; i < n_rows; ++i)
+		if (!rows[i]) return fail(c, FSEQ_E_ARG, "graph threading: null query row");
+	if (int const rc = graph_thread_refusals(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	// the queries' packing: the narrowest that leaves the code `sigma` free for a byte outside the alphabet (as fseq_match_rows)
+	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
+	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
+	DevTemp<uint8_t> d_q(c);                                         // (the call's own: the last match keeps its queries)
+	if (int const rc = upload_queries(c, rows, n_rows, bsh, ld, d_q)) return rc;
+	return graph_thread(c, d_q, ld, bsh, n_rows, nodes, steps, per_row, per_segment, summary);
+}
+
+// the held-out rows (fseq_create_without_rows, csrc/fseq_api_rowsplit.hip) are on the device already, column-major and packed
+// at the alignment's width: nothing is uploaded or packed
+int fseq_graph_thread_held_out(fseq_ctx *c, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment,
+                               fseq_graph_thread_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!c->hold.have && !c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
+	if (int const rc = graph_thread_refusals(c)) return rc;
+	if (!c->hold.have || !c->hold.n_held || !c->hold.cols) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
+	(void) hipSetDevice(c->p.device);
+	return graph_thread(c, c->hold.cols, c->hold.ld, c->bsh, c->hold.n_held, nodes, steps, per_row, per_segment, summary);
+}
+
+int fseq_debug_graph_thread(fseq_ctx *c, fseq_graph_thread_info *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if (!c->graphthread.have) return fail(c, FSEQ_E_ARG, "no fseq_graph_thread_rows / fseq_graph_thread_held_out has finished on this context");
+	*out = c->graphthread.info;
+	return FSEQ_OK;
+}
+
+} // extern "C"
 
 extern "C" {
 

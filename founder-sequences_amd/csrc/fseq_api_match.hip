@@ -320,16 +320,18 @@ int match_permutations(fseq_ctx *c, uint32_t const *permutations, uint64_t min_s
 	return run_match_as_tuned(c, s, min_segment_length, out, restored);
 }
 
-// the queries of fseq_match_rows onto the device: column chunks of raw bytes through a bounded temporary, packed by
-// k_match_pack_rows into c->match.qrows at `bsh` / `ld`
 constexpr size_t MT_QUERY_STAGE_BYTES = (size_t) 64 << 20;
 
-int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld)
+} // namespace
+
+// the queries of fseq_match_rows (and of fseq_graph_thread_rows, csrc/fseq_api_graph.hip) onto the device: column chunks of raw
+// bytes through a bounded temporary, packed by k_match_pack_rows into dst at `bsh` / `ld`
+int fseq::upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld, DevBuf<uint8_t> &dst)
 {
 	hipStream_t st = c->stream;
 	uint64_t const n = c->p.n;
 	int rc;
-	if ((rc = c->match.qrows.ensure(c, (size_t) n * ld))) return rc;
+	if ((rc = dst.ensure(c, (size_t) n * ld))) return rc;
 	// columns of a chunk: a multiple of 16 (the kernel loads 16 bytes of a row), of 64 where the rows leave the room
 	uint64_t cw = MT_QUERY_STAGE_BYTES / n_rows;
 	cw = cw >= 64 ? cw & ~uint64_t(63) : cw & ~uint64_t(15);
@@ -349,12 +351,14 @@ int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uin
 		for (uint32_t q = 0; q < n_rows; ++q) memcpy(stage.data() + (size_t) q * cw, rows[q] + c0, w);
 		HIP_TRY(c, hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
 		hipLaunchKernelGGL(k_match_pack_rows, dim3((w + MT_PACK_COLS - 1u) / MT_PACK_COLS, (n_rows + MT_T - 1u) / MT_T), dim3(MT_T), 0, st,
-		                   d_stage, (size_t) cw, n_rows, c0, w, d_lut, bsh, (uint8_t *) c->match.qrows, ld);
+		                   d_stage, (size_t) cw, n_rows, c0, w, d_lut, bsh, (uint8_t *) dst, ld);
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipStreamSynchronize(st));                     // (the staging is filled again)
 	}
 	return FSEQ_OK;
 }
+
+namespace {
 
 // the queries of fseq_match_rows_restored, n_src raw bytes each: column chunks of the SOURCE through the same bounded staging;
 // k_match_pack_rows_kept packs a chunk's kept columns into their reduced positions of c->match.qrows, k_exc_bits_rows marks
@@ -476,7 +480,7 @@ int fseq_match_rows(fseq_ctx *c, uint32_t const *permutations, uint8_t const *co
 	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
 	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
 	MatchShape const s = match_shape((uint32_t) X, sigma, bsh);
-	if ((rc = begin_match(c, s)) || (rc = upload_queries(c, rows, n_rows, bsh, ld))) return rc;
+	if ((rc = begin_match(c, s)) || (rc = upload_queries(c, rows, n_rows, bsh, ld, c->match.qrows))) return rc;
 	FounderTemps T(c);
 	if ((rc = permutations ? cols_from_permutations(c, permutations, s, T) : cols_from_rows(c, founders, s, T))) return rc;
 	int cus = 0;

@@ -143,6 +143,7 @@ struct Tuning {
 	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: the entries that take query rows choose, those over the alignment's rows walk unsplit)
 	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns (of a restored match: kept columns) a segment's cold walk starts in front of its range (by itself: 16,384)
 	int  match_stage = 0;                // FSEQ_MATCH_STAGE_BYTES: most bytes of a staged chunk of fseq_match_rows_restored's query rows (by itself: 64 MiB; tests: chunks of 64 columns)
+	int  graph_thread_key_bits = 0;      // FSEQ_GRAPH_THREAD_KEY_BITS: bits of a node key of fseq_graph_thread_rows / _held_out (1..64; by itself: 64; tests: a bit or two, so that classes share keys)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -197,6 +198,7 @@ struct Tuning {
 			{"FSEQ_MATCH_SPLIT", nullptr, &Tuning::match_split, 1, 0, nullptr},
 			{"FSEQ_MATCH_OVERLAP", nullptr, &Tuning::match_overlap, 1, 0, nullptr},
 			{"FSEQ_MATCH_STAGE_BYTES", nullptr, &Tuning::match_stage, 64, 0, nullptr},
+			{"FSEQ_GRAPH_THREAD_KEY_BITS", nullptr, &Tuning::graph_thread_key_bits, 1, 0, nullptr},
 		};
 		return table;
 	}
@@ -312,6 +314,7 @@ struct fseq_ctx {
 	int score_path = -1;                     // the last fseq_join_score since the input was set (fseq_debug_join_score_path): 0 host, 1 the device form; -1: none yet
 	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device or fseq_write_segments_restored (fseq_debug_segments_file)
 	struct GraphFileStats { bool have = false; uint64_t batches[3] = {}, lines[3] = {}, bytes[3] = {}; } graphfile;      // the last fseq_write_block_graph (fseq_debug_graph_file): the S, L and P sections
+	struct GraphThreadStats { bool have = false; fseq_graph_thread_info info{}; } graphthread;      // the last fseq_graph_thread_rows / fseq_graph_thread_held_out (fseq_debug_graph_thread)
 	fseq_progress_fn progress_fn = nullptr;
 	void *progress_user = nullptr;
 	hipStream_t stream = nullptr;
@@ -626,6 +629,11 @@ inline int need_result(fseq_ctx *c, bool long_path = true)
 		return fail(c, FSEQ_E_ARG, "the last run took the short path (n < 2L): this call serves a long-path result");
 	return FSEQ_OK;
 }
+
+// csrc/fseq_api_match.hip: n_rows query rows of n raw bytes onto the device -- column chunks through a bounded temporary, through
+// the context's code table (a byte outside the alphabet: the code `sigma`), packed at `bsh` / `ld` into dst, which is grown to
+// n * ld bytes (fseq_match_rows: the match's own buffer; fseq_graph_thread_rows: a temporary of the call)
+int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld, DevBuf<uint8_t> &dst);
 
 #define HIP_TRY(c, expr)                                                   \
 	do {                                                                   \

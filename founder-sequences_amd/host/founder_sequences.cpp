@@ -82,6 +82,12 @@ char const *const USAGE =
 	"                                     co-ordinates as --output-segments; one GPU only)\n"
 	"      --graph-paths                  ... with a P line per input sequence\n"
 	"      --graph-gap-character=C        ... the character the S lines' substrings leave out; empty: every character stays  (default=`-')\n"
+	"      --output-held-out-graph-threads=PATH  With --hold-out: thread the held-out sequences through the founder block graph on the\n"
+	"                                     device and write, per sequence, the segments in which it carries a substring of the graph, the\n"
+	"                                     borders it crosses along an edge and those it crosses as no input sequence does, and its walks\n"
+	"                                     (needs the segmentation only: every joining method; works under --upload-memory and\n"
+	"                                     --list-memory; one GPU only; not together with --remove-identity-columns)\n"
+	"      --output-sequence-graph-threads=PATH  With --match-sequences: the same for the sequences of LIST\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
 	"      --scan-segment-lengths=SPEC    Before anything else, write the maximum segment size at every segment length bound of SPEC --\n"
 	"                                     a comma list of lengths, or LO:HI:STEP -- as a table (SEGMENT_LENGTH, MAX_SEGMENT_SIZE; one line\n"
@@ -349,6 +355,54 @@ bool write_join_score(fseq_ctx *ctx, fseq_result const &res, std::vector<uint32_
 	return ok;
 }
 
+// --output-held-out-graph-threads (list == nullptr: the sequences --hold-out set aside, which the context holds on the device) and
+// --output-sequence-graph-threads (the sequences of `list`; n_held: the sequences held out): fseq_graph_thread_held_out / fseq_graph_thread_rows, statistics only.
+// Tab-separated: a header, one line per sequence in the list's order, a last line '#' with the summary.
+bool write_graph_threads(fseq_ctx *ctx, char const *list, size_t n_held, size_t seq_length, char const *path)
+{
+	std::vector<std::string> queries;
+	std::vector<uint8_t const *> qrows;
+	size_t count = 0;
+	if (list)
+	{
+		std::cerr << "Threading the sequences of '" << list << "' through the block graph…" << std::endl;
+		if (!read_list_file(list, queries)) return false;
+		if (queries.empty() || queries.size() > 0xFFFFFFFFull) { std::cerr << "No sequences to thread in '" << list << "'." << std::endl; return false; }
+		qrows.resize(queries.size());
+		for (size_t i = 0; i < queries.size(); ++i)
+		{
+			if (queries[i].size() != seq_length) { std::cerr << "The sequences to thread must have the length of the input's (" << seq_length << ")." << std::endl; return false; }
+			qrows[i] = reinterpret_cast<uint8_t const *>(queries[i].data());
+		}
+		count = queries.size();
+	}
+	else
+	{
+		std::cerr << "Threading the held-out sequences through the block graph…" << std::endl;
+		count = n_held;
+	}
+	std::vector<fseq_graph_thread_row> per_row(count);
+	fseq_graph_thread_summary sm{};
+	int const rc(list ? fseq_graph_thread_rows(ctx, qrows.data(), (uint32_t) count, nullptr, nullptr, per_row.data(), nullptr, &sm)
+	                  : fseq_graph_thread_held_out(ctx, nullptr, nullptr, per_row.data(), nullptr, &sm));
+	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return false; }
+	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+	if (!f) { std::cerr << "Unable to open the graph threads output file." << std::endl; return false; }
+	fputs("SEQUENCE_INDEX\tSEGMENTS\tMATCHED\tLINKED\tNOVEL\tWALKS\tLONGEST_WALK\tLONGEST_WALK_COLUMNS\tMATCHED_COLUMNS\n", f);
+	for (size_t q = 0; q < count; ++q)
+		fprintf(f, "%zu\t%llu\t%u\t%u\t%u\t%u\t%u\t%llu\t%llu\n", q, (unsigned long long) sm.segments, per_row[q].segments_matched, per_row[q].junctions_linked,
+		        per_row[q].junctions_novel, per_row[q].walks, per_row[q].longest_walk_segments, (unsigned long long) per_row[q].longest_walk_columns,
+		        (unsigned long long) per_row[q].columns_matched);
+	fprintf(f, "#\tROWS=%llu\tSEGMENTS=%llu\tSEGMENTS_MATCHED=%llu\tJUNCTIONS_LINKED=%llu\tJUNCTIONS_NOVEL=%llu\tWALKS=%llu\tROWS_ON_GRAPH=%llu\n",
+	        (unsigned long long) sm.rows, (unsigned long long) sm.segments, (unsigned long long) sm.segments_matched, (unsigned long long) sm.junctions_linked,
+	        (unsigned long long) sm.junctions_novel, (unsigned long long) sm.walks, (unsigned long long) sm.rows_on_graph);
+	bool ok = !ferror(f) && 0 == fflush(f);
+	if (f != stdout && 0 != fclose(f)) ok = false;
+	if (!ok) std::cerr << "Writing the graph threads output file failed." << std::endl;
+	else std::cerr << "Threaded " << sm.rows << " sequences through the block graph: " << sm.rows_on_graph << " on the graph, " << sm.junctions_novel << " novel junctions." << std::endl;
+	return ok;
+}
+
 // --hold-out=LIST: a comma list of 0-based sequence indices and of LO:HI ranges, both ends included, in the order given.  false,
 // with the reason in why, where LIST is malformed or names an index twice (whether the indices are below the sequence count is
 // the caller's check, once the input is read)
@@ -394,6 +448,7 @@ int main(int argc, char **argv)
 	char const *input = nullptr, *out_segments = nullptr, *out_founders = nullptr, *out_matches = nullptr, *out_identity = nullptr, *out_restored_matches = nullptr, *out_restored_segments = nullptr;
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr, *out_join_score = nullptr;
 	char const *out_graph = nullptr, *graph_gap = nullptr;
+	char const *out_held_threads = nullptr, *out_seq_threads = nullptr;
 	bool graph_paths = false;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
@@ -432,6 +487,7 @@ int main(int argc, char **argv)
 		{"output-join-score", required_argument, nullptr, 1022},
 		{"output-graph", required_argument, nullptr, 1023}, {"graph-paths", no_argument, nullptr, 1024},
 		{"graph-gap-character", required_argument, nullptr, 1025},
+		{"output-held-out-graph-threads", required_argument, nullptr, 1026}, {"output-sequence-graph-threads", required_argument, nullptr, 1027},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -485,6 +541,8 @@ int main(int argc, char **argv)
 			case 1023: out_graph = optarg; break;
 			case 1024: graph_paths = true; break;
 			case 1025: graph_gap = optarg; break;
+			case 1026: out_held_threads = optarg; break;
+			case 1027: out_seq_threads = optarg; break;
 			case 1010:
 			{
 				// as --list-memory, but a positive number: 0 MiB hold no chunk
@@ -554,7 +612,15 @@ int main(int argc, char **argv)
 	if (list_memory_mib && gpus > 1) { std::cerr << "--list-memory is not supported together with --gpus > 1." << std::endl; return EXIT_FAILURE; }
 	if (match_min_len_bad) { std::cerr << "The minimum segment length of the match must be a non-negative number." << std::endl; return EXIT_FAILURE; }   // match-sequences-to-founders/main.cc:38-42
 	if (out_matches && gpus > 1) { std::cerr << "--output-matches is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
-	if (match_seqs && !out_seq_matches && !out_seq_restored) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
+	for (int k = 0; k < 2; ++k)
+	{
+		char const *const name = k ? "--output-sequence-graph-threads" : "--output-held-out-graph-threads";
+		if (!(k ? out_seq_threads : out_held_threads)) continue;
+		if (!(k ? match_seqs : hold_out_spec)) { std::cerr << name << " requires " << (k ? "--match-sequences." : "--hold-out.") << std::endl; return EXIT_FAILURE; }
+		if (gpus > 1) { std::cerr << name << " is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
+		if (remove_identity) { std::cerr << name << " is not supported together with --remove-identity-columns (the sequences would be threaded in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	}
+	if (match_seqs && !out_seq_matches && !out_seq_restored && !out_seq_threads) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_matches && !match_seqs) { std::cerr << "--output-sequence-matches requires --match-sequences." << std::endl; return EXIT_FAILURE; }
 	if (match_seqs && gpus > 1) { std::cerr << "--match-sequences is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_restored && !(match_seqs && remove_identity)) { std::cerr << "--output-sequence-restored-matches requires --match-sequences and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
@@ -846,6 +912,11 @@ int main(int argc, char **argv)
 			std::cerr << "--output-graph needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_held_threads || out_seq_threads)
+		{
+			std::cerr << (out_held_threads ? "--output-held-out-graph-threads" : "--output-sequence-graph-threads") << " needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_restored_matches)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
@@ -873,6 +944,9 @@ int main(int argc, char **argv)
 		int const gap = graph_gap ? (graph_gap[0] ? (int) (unsigned char) graph_gap[0] : -1) : (int) '-';
 		if (FSEQ_OK != (rc = fseq_write_block_graph(ctx, graph_paths ? FSEQ_GRAPH_PATHS : 0u, gap, out_graph))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	}
+	// sequences that took no part in the segmentation through its graph, from the context alone (no join)
+	if (out_held_threads && !write_graph_threads(ctx, nullptr, held_rows.size(), seq_length, out_held_threads)) return EXIT_FAILURE;
+	if (out_seq_threads && !write_graph_threads(ctx, match_seqs, 0, seq_length, out_seq_threads)) return EXIT_FAILURE;
 	std::cerr << "Joining the remaining segments…" << std::endl;
 	std::vector<uint32_t> perm((size_t) res.segment_count * res.max_segment_size);
 	std::vector<uint32_t> all_a, all_d;                         // sharded: the boundary states, collected from their owners

@@ -405,6 +405,42 @@ int  fseq_block_graph(fseq_ctx *ctx, fseq_graph_node *nodes, fseq_graph_edge *ed
  * FSEQ_GRAPH_PATHS and an output file that cannot be opened -- each with no byte written.  path NULL or "-" = stdout. */
 enum { FSEQ_GRAPH_PATHS = 1 };
 int  fseq_write_block_graph(fseq_ctx *ctx, uint32_t flags, int gap_byte, char const *path);
+/* ---- rows that are NOT the graph's own threaded through it (no counterpart in the reference) ----
+ * For query row q and segment s, node[s][q] is the id (fseq_block_graph's numbering) of the node of segment s whose rows' codes
+ * over [lb_s, rb_s) equal the query's there -- code by code, a gap a symbol like any other, a query byte outside the
+ * alignment's alphabet equal to nothing --, or FSEQ_GRAPH_NONE where the segment has no such node.  For junction p (segments p
+ * and p + 1), step[p][q] is the index into fseq_block_graph's edges of the edge (node[p][q], node[p + 1][q]), or
+ * FSEQ_GRAPH_NONE where either side is unmatched or the graph has no such edge; both sides matched and no edge is a NOVEL
+ * junction: the row recombines there as no input row does.  A WALK is a maximal run of consecutive matched segments with every
+ * junction between them linked; a row is ON THE GRAPH iff it is one walk of S segments.
+ * Per row: the matched segments and their columns, the linked and the novel junctions, the walks, and the most segments and the
+ * most columns a walk of the row has (each its own maximum).  Per segment: the queries matched in it and, for the junction
+ * behind it, those linked and those novel (0 for the last segment).  The summary adds up the rows'; its ms_device is the wall time
+ * of the call behind the upload: the class tables and edges, the kernels, the copies back.
+ * nodes is [S][n_rows] (row_nodes' layout), steps [S - 1][n_rows]; every output pointer may be NULL, and with nodes and steps
+ * NULL only the statistics leave the device.  fseq_graph_thread_rows takes n raw bytes per query; they go up in column chunks
+ * through at most 64 MiB of staging into a buffer of the call's own, through the context's code table, packed at the narrowest
+ * of 2 / 4 / 8 bits that leaves the code `sigma` for a byte outside the alphabet.  fseq_graph_thread_held_out threads the
+ * held-out rows of a context made by fseq_create_without_rows where they lie on the device: nothing is uploaded, query q is
+ * held_rows[q].  Everything is a temporary of the call: the run's results and the context's last match (fseq_get_match,
+ * fseq_write_match) stay as they were.  The node of a (query, segment) is found through a 64-bit key of the codes, and every
+ * candidate is compared code by code with the class's representative row: the result is exact whatever the keys do
+ * (FSEQ_GRAPH_THREAD_KEY_BITS truncates them; fseq_debug_graph_thread, fseq_debug.h, counts the candidates).
+ * Refuses, each with fseq_last_error set and nothing left behind: as fseq_block_graph, with its codes; FSEQ_E_UNSUPPORTED --
+ * more than 4,096 classes in a segment (there is no host form), a context made by fseq_create_without_identity_columns or its
+ * _held form (source co-ordinates with exception cells are not served); FSEQ_E_ARG -- rows NULL, a NULL row, n_rows = 0, no
+ * alignment resident on the device, fseq_graph_thread_held_out on a context not made by fseq_create_without_rows. */
+enum { FSEQ_GRAPH_NONE = 0xFFFFFFFFu };
+typedef struct { uint64_t columns_matched, longest_walk_columns;
+                 uint32_t segments_matched, junctions_linked, junctions_novel, walks, longest_walk_segments, reserved; } fseq_graph_thread_row;      /* 40 bytes */
+typedef struct { uint32_t matched, linked, novel, reserved; } fseq_graph_thread_segment;   /* 16 bytes; linked / novel: the junction behind the segment, 0 for the last */
+typedef struct { uint64_t rows, segments, segments_matched, junctions_linked, junctions_novel, walks, rows_on_graph; double ms_device; } fseq_graph_thread_summary;
+int  fseq_graph_thread_rows(fseq_ctx *ctx, uint8_t const *const *rows, uint32_t n_rows,
+                            uint32_t *nodes /* [S][n_rows] */, uint32_t *steps /* [S-1][n_rows] */,
+                            fseq_graph_thread_row *per_row /* [n_rows] */, fseq_graph_thread_segment *per_segment /* [S] */,
+                            fseq_graph_thread_summary *summary);
+int  fseq_graph_thread_held_out(fseq_ctx *ctx, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row,
+                                fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary);
 /* replaces: join_context::output_in_permutation_order (join_context.cc:333-356): max_segment_size
  * lines; line r = concatenation over segments of rows[permutations[s][r]][lb_s, rb_s).  rows = the
  * raw input sequences.  path NULL or "-" = stdout. */

@@ -164,6 +164,18 @@ typedef struct fseq_graph_file_stats {
 } fseq_graph_file_stats;
 int  fseq_debug_graph_file(fseq_ctx *ctx, fseq_graph_file_stats *stats);
 
+/* The last fseq_graph_thread_rows / fseq_graph_thread_held_out that finished on this context: the bits of a node key
+ * (FSEQ_GRAPH_THREAD_KEY_BITS=b, 1 .. 64, by itself 64, truncates the keys; fseq_debug_set_tuning takes it at any time: nothing
+ * of a run depends on it, and the threading's results never do), the slots of a workgroup's LDS table, the candidates -- table
+ * entries whose key equals a query's -- that were compared code by code and those among them that failed the comparison, and the
+ * (query, segment) cells left unmatched because the query carries a byte outside the alphabet there.  A probe runs to the empty
+ * slot that ends its chain, so the counts do not depend on where the entries lie.  FSEQ_E_ARG while no call has finished. */
+typedef struct fseq_graph_thread_info {
+	uint32_t key_bits, table_slots;
+	uint64_t candidates_verified, candidates_rejected, queries_out_of_alphabet;
+} fseq_graph_thread_info;
+int  fseq_debug_graph_thread(fseq_ctx *ctx, fseq_graph_thread_info *info);
+
 /* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
  * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
  * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
