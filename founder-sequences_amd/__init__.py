@@ -183,6 +183,7 @@ EXPORTS = [
     "fseq_block_graph", "fseq_write_block_graph", "fseq_debug_graph_file",
     "fseq_debug_local_pass",
     "fseq_graph_thread_rows", "fseq_graph_thread_held_out", "fseq_debug_graph_thread",
+    "fseq_write_block_graph_restored", "fseq_graph_thread_rows_restored", "fseq_graph_thread_held_out_restored",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -352,6 +353,9 @@ def load_library():
     L.fseq_graph_thread_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_graph_thread_held_out.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_debug_graph_thread.argtypes = [vp, C.POINTER(GraphThreadInfo)]
+    L.fseq_write_block_graph_restored.argtypes = [vp, C.c_uint32, C.c_int, C.c_char_p]
+    L.fseq_graph_thread_rows_restored.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
+    L.fseq_graph_thread_held_out_restored.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     _lib = L
     return L
 
@@ -1576,6 +1580,36 @@ class SegmentationContext:
         columns = np.zeros(total.value, dtype=np.uint32)
         self._check(self.L.fseq_get_match_exceptions(self.h, offsets.ctypes.data, columns.ctypes.data, None))
         return offsets, columns
+
+    # ---- the block graph in the source's co-ordinates
+    def write_block_graph_restored(self, path, paths=False, gap=b"-"):
+        """On a context made by without_identity_columns() (or set_sequences_without_identity_columns()): write_block_graph's
+        file with every S line in the source's co-ordinates (fseq_write_block_graph_restored) -- the label runs over the
+        segment's source range of segments_restored(), input row 0's byte at the identity columns, lb / rb are that range.  The
+        L and P lines are write_block_graph's; the labels of a P line spell the source's row.  graph_file_stats() then
+        reports this file."""
+        if gap is not None and len(gap) > 1:
+            raise FseqError(FSEQ_E_ARG, "write_block_graph_restored: the gap is one byte, or None")
+        self._check(self.L.fseq_write_block_graph_restored(self.h, GRAPH_PATHS if paths else 0, gap[0] if gap else -1, path.encode() if path else None))
+
+    def graph_thread_rows_restored(self, queries, want_nodes=True, want_steps=True):
+        """... graph_thread_rows with queries of the source's length, a C-contiguous uint8 array [n_rows, source_n] (or a list
+        of bytes objects of that length) (fseq_graph_thread_rows_restored): a query carries a node iff it equals it on the
+        segment's kept columns and differs from input row 0 in no identity column of the segment's source range.  Returns what
+        graph_thread_rows returns; the column counts are the source's.  The last match and its match_exceptions() stay."""
+        a = queries
+        if not isinstance(a, np.ndarray):
+            a = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in a], dtype=np.uint8).reshape(len(a), -1)
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2 or (a.shape[0] and a.shape[1] != getattr(self, "source_n", -1)):
+            raise ValueError("graph_thread_rows_restored: queries must be rows of the source's n = %d bytes" % getattr(self, "source_n", -1))
+        rows = (C.c_void_p * max(a.shape[0], 1))(*[a.ctypes.data + r * a.strides[0] for r in range(a.shape[0])])
+        return self._graph_thread(lambda *out: self.L.fseq_graph_thread_rows_restored(self.h, rows, a.shape[0], *out), a.shape[0], want_nodes, want_steps)
+
+    def graph_thread_held_out_restored(self, want_nodes=True, want_steps=True):
+        """... the full-length held-out rows of a context made by without_identity_columns(keep_held_out=True), where they lie on
+        the device with the exception cells the context was made with (fseq_graph_thread_held_out_restored)."""
+        return self._graph_thread(lambda *out: self.L.fseq_graph_thread_held_out_restored(self.h, *out), int(getattr(self, "n_held", 0)), want_nodes, want_steps)
 
     # ---- debug / parity of intermediate state
     def debug_dp(self):

@@ -1,7 +1,8 @@
 // fseq_api_graph.hip -- the part of the C ABI (include/fseq.h) behind the founder block graph: fseq_block_graph (the graph as
 // arrays), fseq_write_block_graph (the GFA 1.0 file from the device, csrc/fseq_graph.hpp) and fseq_debug_graph_file; and
 // fseq_graph_thread_rows / fseq_graph_thread_held_out (rows that are not the graph's own threaded through it,
-// csrc/fseq_graphthread.hpp) with fseq_debug_graph_thread.
+// csrc/fseq_graphthread.hpp) with fseq_debug_graph_thread; and the three in the SOURCE's co-ordinates on an identity-reduced
+// context: fseq_write_block_graph_restored, fseq_graph_thread_rows_restored, fseq_graph_thread_held_out_restored.
 //
 // No counterpart in the reference.  Both entries build on the device front of fseq_join_greedy (fseq_joinprep.hpp, unchanged):
 // k_join_classes_wide numbers the classes of every merged segment, k_join_edges_wide<false> / k_join_scan / <true> leave the
@@ -111,19 +112,52 @@ static int graph_refusals(fseq_ctx *c)
 	return FSEQ_OK;
 }
 
-// what the threading refuses beyond the block graph's refusals
-static int graph_thread_refusals(fseq_ctx *c)
+// what the threading refuses beyond the block graph's refusals; restored: the entries that take an identity-reduced context
+static int graph_thread_refusals(fseq_ctx *c, bool restored = false)
 {
 	if (int const rc = graph_refusals(c)) return rc;
-	if (c->idn.have) return fail(c, FSEQ_E_UNSUPPORTED, "graph threading: a context made by fseq_create_without_identity_columns (queries in source co-ordinates, with their exception cells, are not served)");
+	if (c->idn.have && !restored) return fail(c, FSEQ_E_UNSUPPORTED, "graph threading: a context made by fseq_create_without_identity_columns (queries in source co-ordinates, with their exception cells, are not served)");
 	if (c->res.max_segment_size > GT_MAX_CLASSES) return fail(c, FSEQ_E_UNSUPPORTED, "graph threading: more than 4,096 classes in a segment (there is no host form)");
 	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
 	return FSEQ_OK;
 }
 
+// The segments' source ranges of an identity-reduced context on the device, for the restored entries (restored_bounds_of: the
+// bounds fseq_get_segments_restored reports).  Refuses what that entry refuses, before a device buffer exists.
+struct RestoredBounds {
+	std::vector<uint64_t> src_lb, src_rb;
+	DevTemp<uint64_t> d_lb, d_rb;
+	explicit RestoredBounds(fseq_ctx *c) : d_lb(c), d_rb(c) {}
+	int build(fseq_ctx *c, char const *what)
+	{
+		if (c->idn.n_src >= 0xFFFFFFFFull)
+		{
+			std::string const why = std::string(what) + ": the kept columns' source positions are 32 bits wide (source n < 2^32 - 1)";
+			return fail(c, FSEQ_E_UNSUPPORTED, why.c_str());
+		}
+		if (int const rc = restored_bounds_of(c, src_lb, src_rb)) return rc;
+		size_t const S = src_lb.size();
+		int rc;
+		if ((rc = d_lb.alloc(S)) || (rc = d_rb.alloc(S))) return rc;
+		// (blocking copies: the vectors may go before the stream gets to them)
+		HIP_TRY(c, hipMemcpy(d_lb, src_lb.data(), S * 8, hipMemcpyHostToDevice));
+		HIP_TRY(c, hipMemcpy(d_rb, src_rb.data(), S * 8, hipMemcpyHostToDevice));
+		return FSEQ_OK;
+	}
+};
+
+// the exception cells of the queries of a restored threading, on the device
+struct ThreadExceptions {
+	uint64_t const *off;
+	uint32_t const *cols;
+	uint64_t total;
+};
+
 // both entries behind their refusals: the Q queries at q (column-major, packed at qbsh, qld bytes a column) through the graph
+// (R / E: the restored form -- the queries are the kept columns of rows of the source's length, E their exception cells)
 static int graph_thread(fseq_ctx *c, uint8_t const *q, size_t qld, uint32_t qbsh, uint32_t Q, uint32_t *nodes, uint32_t *steps,
-                        fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary)
+                        fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary,
+                        RestoredBounds const *R = nullptr, ThreadExceptions const *E = nullptr)
 {
 	double const t0 = now_ms();
 	hipStream_t st = c->stream;
@@ -156,14 +190,22 @@ static int graph_thread(fseq_ctx *c, uint8_t const *q, size_t qld, uint32_t qbsh
 	A.keys = d_keys; A.nodes = d_nodes; A.steps = d_steps;
 	A.edges = T.d_edges; A.offset = T.d_off; A.nedges = T.d_ne; A.pairs = T.pairs; A.n_edges = T.d_edges.base ? T.edges : 0u;
 	A.stats = d_stats;
+	bool const restored = R && E;
+	if (restored)
+	{
+		A.src_lb = R->d_lb; A.src_rb = R->d_rb; A.n_src = c->idn.n_src;
+		A.exc_off = E->off; A.exc_cols = E->cols; A.n_exc = E->total;
+	}
 	hipError_t e = hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), st);
 	if (e == hipSuccess) e = allow_lds(k_gt_thread, lds);
 	if (e != hipSuccess) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_HIP, "graph threading: preparation", e); }
 	uint32_t const tiles = (uint32_t) std::min<size_t>(((size_t) Q + GT_T - 1) / GT_T, 1024);
 	hipLaunchKernelGGL(k_gt_keys, dim3((uint32_t) S, (X + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A);
 	hipLaunchKernelGGL(k_gt_thread, dim3((uint32_t) S, tiles), dim3(GT_T), lds, st, A);
+	if (restored && E->total) hipLaunchKernelGGL(k_gt_exceptions, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A);
 	if (T.pairs) hipLaunchKernelGGL(k_gt_steps, dim3(T.pairs, tiles), dim3(GT_T), 0, st, A);
-	hipLaunchKernelGGL(k_gt_rows, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A, (fseq_graph_thread_row *) d_rows);
+	if (restored) hipLaunchKernelGGL(k_gt_rows<true>, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A, (fseq_graph_thread_row *) d_rows);
+	else hipLaunchKernelGGL(k_gt_rows<false>, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A, (fseq_graph_thread_row *) d_rows);
 	if (per_segment) hipLaunchKernelGGL(k_gt_segments, dim3((uint32_t) S), dim3(GT_T), 0, st, A, (fseq_graph_thread_segment *) d_segs);
 	unsigned long long stats[3] = {0, 0, 0};
 	e = hipMemcpyAsync(rows.data(), d_rows, (size_t) Q * sizeof(fseq_graph_thread_row), hipMemcpyDeviceToHost, st);
@@ -220,6 +262,48 @@ int fseq_graph_thread_held_out(fseq_ctx *c, uint32_t *nodes, uint32_t *steps, fs
 	if (!c->hold.have || !c->hold.n_held || !c->hold.cols) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
 	(void) hipSetDevice(c->p.device);
 	return graph_thread(c, c->hold.cols, c->hold.ld, c->bsh, c->hold.n_held, nodes, steps, per_row, per_segment, summary);
+}
+
+// fseq_graph_thread_rows on an identity-reduced context with queries of the source's length: their kept columns and their
+// exception cells go into temporaries of the call (the last match keeps its queries and its exception lists)
+int fseq_graph_thread_rows_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t *nodes, uint32_t *steps,
+                                    fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!rows || 0 == n_rows) return fail(c, FSEQ_E_ARG, "graph threading: no query rows");
+	for (uint32_t i = 0; i < n_rows; ++i)
+		if (!rows[i]) return fail(c, FSEQ_E_ARG, "graph threading: null query row");
+	if (!c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
+	if (int const rc = graph_thread_refusals(c, true)) return rc;
+	(void) hipSetDevice(c->p.device);
+	RestoredBounds R(c);
+	if (int const rc = R.build(c, "restored graph threading")) return rc;
+	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
+	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
+	DevTemp<uint8_t> d_q(c);
+	DevTemp<uint64_t> d_off(c);
+	DevTemp<uint32_t> d_cols(c);
+	uint64_t total = 0;
+	if (int const rc = upload_queries_restored(c, rows, n_rows, bsh, ld, d_q, d_off, d_cols, &total)) return rc;
+	ThreadExceptions const E{d_off, d_cols, total};
+	return graph_thread(c, d_q, ld, bsh, n_rows, nodes, steps, per_row, per_segment, summary, &R, &E);
+}
+
+// the held-out rows of a context made by fseq_create_without_identity_columns_held: their kept columns and their exception cells
+// are on the device already
+int fseq_graph_thread_held_out_restored(fseq_ctx *c, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row, fseq_graph_thread_segment *per_segment,
+                                        fseq_graph_thread_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
+	if (!c->hold.have_exc) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns_held");
+	if (int const rc = graph_thread_refusals(c, true)) return rc;
+	if (!c->hold.have || !c->hold.n_held || !c->hold.cols) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns_held");
+	(void) hipSetDevice(c->p.device);
+	RestoredBounds R(c);
+	if (int const rc = R.build(c, "restored graph threading")) return rc;
+	ThreadExceptions const E{c->hold.exc_off, c->hold.exc_cols, c->hold.exc_total};
+	return graph_thread(c, c->hold.cols, c->hold.ld, c->bsh, c->hold.n_held, nodes, steps, per_row, per_segment, summary, &R, &E);
 }
 
 int fseq_debug_graph_thread(fseq_ctx *c, fseq_graph_thread_info *out)
@@ -289,16 +373,26 @@ int fseq_block_graph(fseq_ctx *c, fseq_graph_node *nodes, fseq_graph_edge *edges
 	return FSEQ_OK;
 }
 
-int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const *path)
+} // extern "C"
+
+// fseq_write_block_graph and, restored, fseq_write_block_graph_restored: the same file but for the S lines' labels, LN, lb and rb
+static int write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const *path, bool restored)
 {
-	if (!c) return FSEQ_E_ARG;
 	if (flags & ~(uint32_t) FSEQ_GRAPH_PATHS) return fail(c, FSEQ_E_ARG, "block graph file: unknown flag bits (FSEQ_GRAPH_PATHS)");
 	if (gap_byte > 255) return fail(c, FSEQ_E_ARG, "block graph file: the gap byte is a byte (0 .. 255) or negative for none");
+	if (restored && !c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_identity_columns");
 	if (int const rc = graph_refusals(c)) return rc;
 	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
 	(void) hipSetDevice(c->p.device);
 	hipStream_t st = c->stream;
 	bool const paths = (flags & FSEQ_GRAPH_PATHS) != 0;
+	RestoredBounds RB(c);
+	GraphRestored R{};
+	if (restored)
+	{
+		if (int const rc = RB.build(c, "restored block graph file")) return rc;
+		R = GraphRestored{RB.d_lb, RB.d_rb, c->idn.mask, c->idn.ref, c->idn.n_src};
+	}
 	GraphTables T(c);
 	if (int const rc = T.build(true)) return rc;
 	T.d_start.release(c);                                            // (the edge kernel's: not needed from here on)
@@ -324,7 +418,8 @@ int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const
 	A.code_to_byte = d_lut;
 	// every line's length, scanned: the nodes inside the segments, then over them; the links inside their workgroups, then over
 	// them; the paths over the rows
-	hipLaunchKernelGGL(k_graph_node_lines, dim3((uint32_t) S), dim3(GR_T), 0, st, A, (uint32_t *) d_lab, (uint64_t *) d_loff);
+	if (restored) hipLaunchKernelGGL(k_graph_node_lines<true>, dim3((uint32_t) S), dim3(GR_T), 0, st, A, R, (uint32_t *) d_lab, (uint64_t *) d_loff);
+	else hipLaunchKernelGGL(k_graph_node_lines<false>, dim3((uint32_t) S), dim3(GR_T), 0, st, A, R, (uint32_t *) d_lab, (uint64_t *) d_loff);
 	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, (uint64_t const *) d_loff, (uint32_t) S, X, (uint64_t *) d_segoff);
 	if (nb) hipLaunchKernelGGL(k_graph_link_lines, dim3((uint32_t) nb), dim3(GR_T), 0, st, A, 0u, (uint64_t *) d_btot, (uint32_t *) nullptr);
 	hipLaunchKernelGGL(k_segfile_scan, dim3(1), dim3(SF_T), 0, st, (uint64_t const *) d_btot, (uint32_t) nb, 0u, (uint64_t *) d_boff);
@@ -401,7 +496,8 @@ int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const
 	for (size_t b = 0; b < nbatches.size() && ok && hip_ok; ++b)
 	{
 		SegFileBatch const &B = nbatches[b];
-		hipLaunchKernelGGL(k_graph_write_nodes, dim3(B.s1 - B.s0 + 1), dim3(GR_T), 0, st, A, B, (uint32_t const *) d_lab, (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint8_t *) d_out);
+		if (restored) hipLaunchKernelGGL(k_graph_write_nodes<true>, dim3(B.s1 - B.s0 + 1), dim3(GR_T), 0, st, A, R, B, (uint32_t const *) d_lab, (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint8_t *) d_out);
+		else hipLaunchKernelGGL(k_graph_write_nodes<false>, dim3(B.s1 - B.s0 + 1), dim3(GR_T), 0, st, A, R, B, (uint32_t const *) d_lab, (uint64_t const *) d_loff, (uint64_t const *) d_segoff, (uint8_t *) d_out);
 		leave(B.bytes, 0);
 	}
 	uint32_t lens[GR_T];
@@ -442,6 +538,22 @@ int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const
 	if (!ok) return fail(c, FSEQ_E_ARG, "writing the block graph output file failed");
 	c->graphfile = stats;
 	return FSEQ_OK;
+}
+
+extern "C" {
+
+int fseq_write_block_graph(fseq_ctx *c, uint32_t flags, int gap_byte, char const *path)
+{
+	if (!c) return FSEQ_E_ARG;
+	return write_block_graph(c, flags, gap_byte, path, false);
+}
+
+// the S lines in the source's co-ordinates (k_graph_node_lines<true> / k_graph_write_nodes<true>, csrc/fseq_graph.hpp): the
+// classes, ids, L and P lines are the reduced graph's -- rows that agree on a segment's kept columns agree on its source range
+int fseq_write_block_graph_restored(fseq_ctx *c, uint32_t flags, int gap_byte, char const *path)
+{
+	if (!c) return FSEQ_E_ARG;
+	return write_block_graph(c, flags, gap_byte, path, true);
 }
 
 int fseq_debug_graph_file(fseq_ctx *c, fseq_graph_file_stats *out)

@@ -287,7 +287,7 @@ struct SegFileRestored {
 
 // The merged segments of an identity-reduced context in the source's co-ordinates (restored_segment_bounds on the kept columns,
 // which are copied to the host: 4 bytes a kept column).  Refuses what the pure function refuses.
-static int restored_bounds_of(fseq_ctx *c, std::vector<uint64_t> &src_lb, std::vector<uint64_t> &src_rb)
+int fseq::restored_bounds_of(fseq_ctx *c, std::vector<uint64_t> &src_lb, std::vector<uint64_t> &src_rb)
 {
 	size_t const S = c->segments.size();
 	std::vector<uint32_t> kept;

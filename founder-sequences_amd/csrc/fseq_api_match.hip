@@ -358,20 +358,19 @@ int fseq::upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_row
 	return FSEQ_OK;
 }
 
-namespace {
-
-// the queries of fseq_match_rows_restored, n_src raw bytes each: column chunks of the SOURCE through the same bounded staging;
-// k_match_pack_rows_kept packs a chunk's kept columns into their reduced positions of c->match.qrows, k_exc_bits_rows marks
-// the chunk's identity columns in which a query differs from row 0 in a bit matrix of this call, from which
-// c->match.exc_off / exc_cols are made (csrc/fseq_exceptions.hpp).  Every query byte crosses to the device once
-int upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld)
+// the queries of fseq_match_rows_restored (and of fseq_graph_thread_rows_restored, csrc/fseq_api_graph.hip), n_src raw bytes
+// each: column chunks of the SOURCE through the same bounded staging; k_match_pack_rows_kept packs a chunk's kept columns into
+// their reduced positions of dst, k_exc_bits_rows marks the chunk's identity columns in which a query differs from row 0 in a
+// bit matrix of this call, from which exc_off / exc_cols are made (csrc/fseq_exceptions.hpp).  Every query byte crosses to the
+// device once
+int fseq::upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld, DevBuf<uint8_t> &dst,
+                                  DevBuf<uint64_t> &exc_off, DevBuf<uint32_t> &exc_cols, uint64_t *exc_total)
 {
 	hipStream_t st = c->stream;
-	auto &mt = c->match;
 	uint64_t const n = c->p.n, n_src = c->idn.n_src;
 	size_t const nw = (size_t) ((n_src + 31u) / 32u);
 	int rc;
-	if ((rc = mt.qrows.ensure(c, (size_t) n * ld))) return rc;
+	if ((rc = dst.ensure(c, (size_t) n * ld))) return rc;
 	// columns of a chunk: a multiple of 64 (a lane of k_exc_bits_rows owns a word of 32 columns; FSEQ_MATCH_STAGE_BYTES: at least 64)
 	uint64_t cw = ((c->tune.match_stage ? (size_t) c->tune.match_stage : MT_QUERY_STAGE_BYTES) / n_rows) & ~uint64_t(63);
 	if (c->tune.match_stage) cw = std::max<uint64_t>(cw, 64);
@@ -398,15 +397,17 @@ int upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_
 		uint64_t const j_hi = (uint64_t) (std::lower_bound(kept.begin(), kept.end(), (uint32_t) (c0 + w)) - kept.begin());
 		if (j_hi > j_lo)
 			hipLaunchKernelGGL(k_match_pack_rows_kept, dim3((uint32_t) ((j_hi - j_lo + MT_PACK_COLS - 1u) / MT_PACK_COLS), (n_rows + MT_T - 1u) / MT_T), dim3(MT_T), 0, st,
-			                   (uint8_t const *) d_stage, (size_t) cw, n_rows, c0, j_lo, j_hi, (uint32_t const *) c->idn.kept, (uint8_t const *) d_lut, bsh, (uint8_t *) mt.qrows, ld);
+			                   (uint8_t const *) d_stage, (size_t) cw, n_rows, c0, j_lo, j_hi, (uint32_t const *) c->idn.kept, (uint8_t const *) d_lut, bsh, (uint8_t *) dst, ld);
 		uint64_t const lanes = (uint64_t) n_rows * ((w + 31u) / 32u);
 		hipLaunchKernelGGL(k_exc_bits_rows, dim3((uint32_t) ((lanes + EX_T - 1u) / EX_T)), dim3(EX_T), 0, st, (uint8_t const *) d_stage, (size_t) cw, n_rows, c0, w,
 		                   (uint8_t const *) c->idn.ref, (uint8_t const *) c->idn.mask, n_src, (uint32_t *) d_bits, nw);
 		HIP_TRY(c, hipGetLastError());
 		HIP_TRY(c, hipStreamSynchronize(st));                     // (the staging is filled again)
 	}
-	return exc_lists_from_bits(c, st, d_bits, nw, n_rows, mt.exc_off, mt.exc_cols, &mt.exc_total);
+	return exc_lists_from_bits(c, st, d_bits, nw, n_rows, exc_off, exc_cols, exc_total);
 }
+
+namespace {
 
 // fseq_match_held_out_restored / fseq_match_rows_restored behind their refusals: the restored walk over the query rows R, split
 // along the kept columns as the knobs say or, without them, as fseq_match_rows chooses by itself; where that choice is one
@@ -547,7 +548,7 @@ int fseq_match_rows_restored(fseq_ctx *c, uint32_t const *permutations, uint8_t 
 	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
 	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
 	MatchShape const s = match_shape((uint32_t) X, sigma, bsh);
-	if ((rc = begin_match(c, s)) || (rc = upload_queries_restored(c, rows, n_rows, bsh, ld))) return rc;
+	if ((rc = begin_match(c, s)) || (rc = upload_queries_restored(c, rows, n_rows, bsh, ld, c->match.qrows, c->match.exc_off, c->match.exc_cols, &c->match.exc_total))) return rc;
 	return match_queries_restored(c, permutations, s, MatchRows{c->match.qrows, ld, n_rows, bsh}, MatchExceptions{c->match.exc_off, c->match.exc_cols}, 2,
 	                              min_segment_length, out);
 }

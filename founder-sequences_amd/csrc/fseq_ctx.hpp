@@ -634,6 +634,15 @@ inline int need_result(fseq_ctx *c, bool long_path = true)
 // the context's code table (a byte outside the alphabet: the code `sigma`), packed at `bsh` / `ld` into dst, which is grown to
 // n * ld bytes (fseq_match_rows: the match's own buffer; fseq_graph_thread_rows: a temporary of the call)
 int upload_queries(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld, DevBuf<uint8_t> &dst);
+// ... and n_rows query rows of n_src raw bytes onto an identity-reduced context: their kept columns packed into dst the same
+// way, and their exception cells (csrc/fseq_exceptions.hpp) into exc_off [n_rows + 1] / exc_cols [*exc_total], each grown or
+// replaced as the lists need (fseq_match_rows_restored: the match's own buffers; fseq_graph_thread_rows_restored: temporaries of
+// the call)
+int upload_queries_restored(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t bsh, size_t ld, DevBuf<uint8_t> &dst,
+                            DevBuf<uint64_t> &exc_off, DevBuf<uint32_t> &exc_cols, uint64_t *exc_total);
+// csrc/fseq_api_join.hip: the merged segments of an identity-reduced context in the source's co-ordinates (restored_segment_bounds,
+// csrc/fseq_restored_bounds.hpp, on the kept columns copied to the host); FSEQ_E_UNSUPPORTED where the pure function refuses
+int restored_bounds_of(fseq_ctx *c, std::vector<uint64_t> &src_lb, std::vector<uint64_t> &src_rb);
 
 #define HIP_TRY(c, expr)                                                   \
 	do {                                                                   \

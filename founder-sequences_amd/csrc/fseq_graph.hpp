@@ -29,6 +29,13 @@
 //                           (lanes along the rows), then writes 16 rows' steps (lanes along the segments: a wave scan of the
 //                           steps' lengths gives each its place, the 64 steps are one contiguous stretch of the line).  The
 //                           other choice, a lane a row in the write as well, stores single bytes S x 6 bytes apart.
+// The S section in the SOURCE's co-ordinates on an identity-reduced context (fseq_write_block_graph_restored): the two S kernels
+// with RESTORED set.  The layout stays -- a workgroup a segment, a wave a node --, the lanes go along the source positions of
+// the segment's range [src_lb, src_rb) (fseq_restored_bounds.hpp) in strips of 64, and a strip has two running cursors: the kept
+// column (the segment's lb + the positions in front that are no identity columns: mbcnt / popcount of the ballot of !mask[p]) and
+// the label (mbcnt / popcount of the ballot of "not the gap", as in the reduced form).  A lane at an identity column takes row 0's
+// byte (ref[p]), a lane at a kept column the representative row's code at its column; a strip may hold no kept column, or 64.
+// The lines' lb / rb are the source range.  The L and P sections are the reduced graph's: nothing of them has a restored form.
 // Every store is checked against the batch buffer's size; every table value is clipped before it indexes (class < count <= X,
 // row < m), as in the segfile kernels.  The bytes of a label are the alignment's, decoded through the context's code table.
 #pragma once
@@ -91,6 +98,15 @@ struct GraphArgs {
 	uint64_t n_edges;
 };
 
+// the restored form of the S section (fseq_write_block_graph_restored): the segments' ranges in the SOURCE's co-ordinates
+// (restored_segment_bounds, fseq_restored_bounds.hpp) and the identity columns of the context (fseq_identity.hpp).  Unread by
+// the reduced form
+struct GraphRestored {
+	uint64_t const *src_lb, *src_rb;         // [S]
+	uint8_t const *mask, *ref;               // [n_src]: 1 = identity column; row 0 of the source as raw bytes
+	uint64_t n_src;
+};
+
 // a batch of the links or the paths: the lines [first, last) in file order, which begin `begin` bytes into their section;
 // out holds `bytes` of them
 struct GraphBatch {
@@ -105,8 +121,35 @@ __device__ __forceinline__ uint64_t gr_node_tags_len(uint32_t lab, uint32_t rows
 	return 6u + sf_digits(lab) + 6u + sf_digits(rows) + 6u + sf_digits(s) + 6u + gr_digits64(lb) + 6u + gr_digits64(rb) + 1u;
 }
 
+// One strip of 64 SOURCE positions of a restored label, [base, base + 64) inside [base, srb): a lane at an identity column takes
+// row 0's byte, a lane at a kept column the representative row's code at column kc + (kept columns of the strip below the
+// lane) -- the kept columns of a segment's source range are its [lb, rb) in order, so two cursors run along the strips: kc, which
+// moves on by the strip's kept columns here, and the caller's label cursor.  A strip may hold no kept column, or 64.
+// Returns whether the lane has a byte (b) at all; a column past rb (never: mask and kept are one context's) has none.
+__device__ __forceinline__ bool gr_restored_byte(GraphArgs const &A, GraphRestored const &R, uint8_t const *lut, uint64_t base, uint64_t srb, uint64_t &kc, uint64_t rb,
+                                                 uint32_t off, uint32_t sh, uint32_t cmask, uint32_t lane, uint8_t &b)
+{
+	uint64_t const p = base + lane;
+	bool const in = p < srb && p < R.n_src;
+	bool const ident = in && R.mask[p] != 0;
+	uint64_t const kmask = __ballot(in && !ident);
+	uint64_t const col = kc + __builtin_amdgcn_mbcnt_hi((uint32_t) (kmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) kmask, 0u));
+	kc += (uint32_t) __popcll(kmask);
+	bool have = ident;
+	b = 0;
+	if (ident) b = R.ref[p];
+	else if (in && col < rb)
+	{
+		b = lut[(A.msa[col * A.ld + off] >> sh) & cmask];
+		have = true;
+	}
+	return have;
+}
+
 // lab[s][j] (stride X): the bytes of node j's label; loff[s][j], j <= X (stride X + 1): bytes of the segment's lines in front of line j
-static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, uint32_t *__restrict__ lab, uint64_t *__restrict__ loff)
+// RESTORED: the label over the segment's source range (gr_restored_byte), the line's lb / rb the source's
+template <bool RESTORED>
+static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, GraphRestored R, uint32_t *__restrict__ lab, uint64_t *__restrict__ loff)
 {
 	__shared__ uint8_t lut[256];
 	__shared__ uint64_t scratch[GR_NW];
@@ -116,6 +159,7 @@ static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, u
 	__syncthreads();
 	uint32_t const nc = min(A.count[s], X);
 	uint64_t const lb = A.seg_lb[s], rb = A.seg_rb[s], W = rb > lb ? rb - lb : 0u;
+	uint64_t const plb = RESTORED ? R.src_lb[s] : lb, prb = RESTORED ? R.src_rb[s] : rb;      // what the line prints
 	uint32_t const bits = 8u >> A.bsh, cmask = (1u << bits) - 1u;
 	for (uint32_t j = wv; j < nc; j += GR_NW)
 	{
@@ -124,6 +168,17 @@ static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, u
 		if (row < m)
 		{
 			uint32_t const off = row >> A.bsh, sh = (row & ((1u << A.bsh) - 1u)) * bits;
+			if constexpr (RESTORED)
+			{
+				uint64_t kc = lb;
+				for (uint64_t base = plb; base < prb; base += WAVE)
+				{
+					uint8_t b;
+					bool const have = gr_restored_byte(A, R, lut, base, prb, kc, rb, off, sh, cmask, lane, b);
+					n += (uint32_t) __popcll(__ballot(have && (A.gap < 0 || (int32_t) b != A.gap)));
+				}
+			}
+			else
 			for (uint64_t base = 0; base < W; base += WAVE)
 			{
 				uint64_t const k = base + lane;
@@ -149,7 +204,7 @@ static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, u
 		if (j < nc)
 		{
 			uint32_t const n = lab[(size_t) s * X + j];
-			len = 2u + sf_digits(id0 + j + 1u) + 1u + max(n, 1u) + gr_node_tags_len(n, A.size[(size_t) s * X + j], s, lb, rb);
+			len = 2u + sf_digits(id0 + j + 1u) + 1u + max(n, 1u) + gr_node_tags_len(n, A.size[(size_t) s * X + j], s, plb, prb);
 		}
 		uint64_t total;
 		uint64_t const before = sf_block_excl_add64(len, scratch, &total);
@@ -160,8 +215,9 @@ static __global__ __launch_bounds__(GR_T) void k_graph_node_lines(GraphArgs A, u
 }
 
 // the S lines of a batch (SegFileBatch: from line j_lo of segment s0 to line j_hi - 1 of segment s1)
+template <bool RESTORED>
 static __global__ __launch_bounds__(GR_T) void k_graph_write_nodes(
-	GraphArgs A, SegFileBatch B, uint32_t const *__restrict__ lab, uint64_t const *__restrict__ loff, uint64_t const *__restrict__ seg_off, uint8_t *__restrict__ out)
+	GraphArgs A, GraphRestored R, SegFileBatch B, uint32_t const *__restrict__ lab, uint64_t const *__restrict__ loff, uint64_t const *__restrict__ seg_off, uint8_t *__restrict__ out)
 {
 	__shared__ uint8_t lut[256];
 	uint32_t const s = B.s0 + blockIdx.x, tid = threadIdx.x, X = A.X, m = A.m, lane = lane_id();
@@ -173,8 +229,9 @@ static __global__ __launch_bounds__(GR_T) void k_graph_write_nodes(
 	uint64_t const lb = A.seg_lb[s], rb = A.seg_rb[s], W = rb > lb ? rb - lb : 0u;
 	uint64_t const *lo = loff + (size_t) s * ((size_t) X + 1u);
 	uint64_t const seg_at = seg_off[s] - B.begin;                    // (mod 2^64 where the segment begins in front of the batch: only its lines inside are addressed)
+	uint64_t const plb = RESTORED ? R.src_lb[s] : lb, prb = RESTORED ? R.src_rb[s] : rb;      // what the lines print
 	uint32_t const bits = 8u >> A.bsh, cmask = (1u << bits) - 1u, id0 = A.noff[s];
-	uint32_t const dsg = sf_digits(s), dlb = gr_digits64(lb), drb = gr_digits64(rb);
+	uint32_t const dsg = sf_digits(s), dlb = gr_digits64(plb), drb = gr_digits64(prb);
 	for (uint32_t j = j_lo + wv; j < j_hi; j += GR_NW)
 	{
 		uint64_t const at = seg_at + lo[j], end = seg_at + lo[j + 1u];
@@ -182,7 +239,7 @@ static __global__ __launch_bounds__(GR_T) void k_graph_write_nodes(
 		uint32_t const id1 = id0 + j + 1u, n = lab[(size_t) s * X + j], rows = A.size[(size_t) s * X + j], row = A.rep[(size_t) s * X + j];
 		uint32_t const did = sf_digits(id1), dn = sf_digits(n), drw = sf_digits(rows);
 		uint64_t const sub = at + 2u + did + 1u, tag = sub + max(n, 1u);
-		if (tag + gr_node_tags_len(n, rows, s, lb, rb) != end) continue;      // (never: the lengths are k_graph_node_lines')
+		if (tag + gr_node_tags_len(n, rows, s, plb, prb) != end) continue;      // (never: the lengths are k_graph_node_lines')
 		if (lane == 0)
 		{
 			gr_put(out, at, B.bytes, (uint8_t) 'S'); gr_put(out, at + 1u, B.bytes, (uint8_t) '\t');
@@ -193,15 +250,30 @@ static __global__ __launch_bounds__(GR_T) void k_graph_write_nodes(
 		else if (lane == 1) gr_put_tag(out, tag, B.bytes, 'L', 'N', n, dn);
 		else if (lane == 2) gr_put_tag(out, tag + 6u + dn, B.bytes, 'R', 'C', rows, drw);
 		else if (lane == 3) gr_put_tag(out, tag + 12u + dn + drw, B.bytes, 's', 'g', s, dsg);
-		else if (lane == 4) gr_put_tag(out, tag + 18u + dn + drw + dsg, B.bytes, 'l', 'b', lb, dlb);
+		else if (lane == 4) gr_put_tag(out, tag + 18u + dn + drw + dsg, B.bytes, 'l', 'b', plb, dlb);
 		else if (lane == 5)
 		{
-			gr_put_tag(out, tag + 24u + dn + drw + dsg + dlb, B.bytes, 'r', 'b', rb, drb);
+			gr_put_tag(out, tag + 24u + dn + drw + dsg + dlb, B.bytes, 'r', 'b', prb, drb);
 			gr_put(out, end - 1u, B.bytes, (uint8_t) '\n');
 		}
 		if (row >= m || 0 == n) continue;
 		uint32_t const off = row >> A.bsh, sh = (row & ((1u << A.bsh) - 1u)) * bits;
 		uint32_t run = 0;                                            // bytes of the label in front of this strip
+		if constexpr (RESTORED)
+		{
+			uint64_t kc = lb;
+			for (uint64_t base = plb; base < prb; base += WAVE)
+			{
+				uint8_t b;
+				bool const have = gr_restored_byte(A, R, lut, base, prb, kc, rb, off, sh, cmask, lane, b);
+				bool const keep = have && (A.gap < 0 || (int32_t) b != A.gap);
+				uint64_t const mask = __ballot(keep);
+				uint32_t const pos = run + __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
+				if (keep && pos < n) gr_put(out, sub + pos, B.bytes, b);
+				run += (uint32_t) __popcll(mask);
+			}
+		}
+		else
 		for (uint64_t base = 0; base < W; base += WAVE)
 		{
 			uint64_t const k = base + lane;

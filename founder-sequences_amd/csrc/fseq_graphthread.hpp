@@ -26,6 +26,10 @@
 //   k_gt_steps      one lane per (junction, query): l << 16 | r is searched in the junction's slice of k_join_edges_wide<true>'s
 //                   output, ascending by construction; the step is offset[p] + k, the index of the edge in fseq_block_graph's
 //                   edges.
+//   k_gt_exceptions the restored form alone (a context over the kept columns of a longer source, queries of the source's length):
+//                   k_gt_keys / k_gt_thread run on the kept columns as they are, then one lane per query walks the query's
+//                   exception cells -- the identity columns in which it differs from row 0 -- and unmatches the segment
+//                   whose source range holds one, before k_gt_steps looks for the edges
 //   k_gt_rows       one lane per query walks the S segments: the loads of a wave are contiguous in [S][Q]
 //   k_gt_segments   one workgroup per segment counts along the queries; integer sums, which do not depend on the order of
 //                   their atomics
@@ -63,6 +67,13 @@ struct GraphThreadArgs {
 	uint32_t pairs;
 	uint64_t n_edges;
 	unsigned long long *stats;               // candidates verified, candidates rejected, cells with a byte outside the alphabet
+	// the restored form alone (fseq_graph_thread_rows_restored / _held_out_restored): the segments' source ranges, and the
+	// queries' exception cells (csrc/fseq_exceptions.hpp): query q's are exc_cols[exc_off[q] .. exc_off[q + 1]), ascending
+	uint64_t const *src_lb, *src_rb;         // [S]
+	uint64_t n_src;
+	uint64_t const *exc_off;                 // [Q + 1]
+	uint32_t const *exc_cols;                // [n_exc]
+	uint64_t n_exc;
 };
 
 // the code of `row` in a packed column
@@ -169,6 +180,34 @@ static __global__ __launch_bounds__(GT_T) void k_gt_thread(GraphThreadArgs A)
 	if (tid < 3u && sums[tid]) atomicAdd(&A.stats[tid], (unsigned long long) sums[tid]);
 }
 
+// The restored form, between k_gt_thread and k_gt_steps: a query with an exception cell in a segment's source range carries no
+// node of it.  One lane per query walks the query's ascending cells; the segment of a cell is the last s with src_lb[s] <= cell
+// (the ranges tile [0, n_src)), and the cells up to that segment's src_rb are skipped.  A lane stores into its own query's
+// column of nodes[][] only, so nothing races.
+static __global__ __launch_bounds__(GT_T) void k_gt_exceptions(GraphThreadArgs A)
+{
+	uint64_t const q = (uint64_t) blockIdx.x * GT_T + threadIdx.x;
+	uint32_t const Q = A.Q, S = A.S;
+	if (q >= Q || 0 == S) return;
+	uint64_t at = A.exc_off[q];
+	uint64_t const end = min(A.exc_off[q + 1u], A.n_exc);
+	uint64_t done = 0;                       // the source positions below this are dealt with
+	while (at < end)
+	{
+		uint64_t const cell = A.exc_cols[at++];
+		if (cell < done || cell >= A.n_src) continue;
+		uint32_t lo = 0, hi = S;             // src_lb[lo] <= cell (src_lb[0] = 0)
+		while (hi - lo > 1u)
+		{
+			uint32_t const mid = lo + (hi - lo) / 2u;
+			if (A.src_lb[mid] <= cell) lo = mid;
+			else hi = mid;
+		}
+		A.nodes[(size_t) lo * Q + q] = GT_NONE;
+		done = max(A.src_rb[lo], cell + 1u);
+	}
+}
+
 // workgroup (p, y): junction p, the query tiles y, y + gridDim.y, ...
 static __global__ __launch_bounds__(GT_T) void k_gt_steps(GraphThreadArgs A)
 {
@@ -197,7 +236,20 @@ static __global__ __launch_bounds__(GT_T) void k_gt_steps(GraphThreadArgs A)
 	}
 }
 
-// per_row[q]: one lane per query
+// the columns the statistics count for segment s: SRC: its source range, inside the source
+template <bool SRC>
+__device__ __forceinline__ void gt_counted_columns(GraphThreadArgs const &A, uint32_t s, uint64_t &lb, uint64_t &rb)
+{
+	if constexpr (SRC)
+	{
+		rb = min(A.src_rb[s], A.n_src);
+		lb = min(A.src_lb[s], rb);
+	}
+	else gt_columns(A, s, lb, rb);
+}
+
+// per_row[q]: one lane per query.  SRC: the column counts are the source's (the restored form)
+template <bool SRC>
 static __global__ __launch_bounds__(GT_T) void k_gt_rows(GraphThreadArgs A, fseq_graph_thread_row *__restrict__ per_row)
 {
 	uint64_t const q = (uint64_t) blockIdx.x * GT_T + threadIdx.x;
@@ -211,7 +263,7 @@ static __global__ __launch_bounds__(GT_T) void k_gt_rows(GraphThreadArgs A, fseq
 	{
 		bool const matched = A.nodes[(size_t) s * Q + q] != GT_NONE;
 		uint64_t lb, rb;
-		gt_columns(A, s, lb, rb);
+		gt_counted_columns<SRC>(A, s, lb, rb);
 		if (matched)
 		{
 			++R.segments_matched;

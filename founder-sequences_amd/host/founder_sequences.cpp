@@ -88,6 +88,16 @@ char const *const USAGE =
 	"                                     (needs the segmentation only: every joining method; works under --upload-memory and\n"
 	"                                     --list-memory; one GPU only; not together with --remove-identity-columns)\n"
 	"      --output-sequence-graph-threads=PATH  With --match-sequences: the same for the sequences of LIST\n"
+	"      --output-restored-graph=PATH   With --remove-identity-columns: the block graph in the input's co-ordinates -- the same L and P\n"
+	"                                     lines, every S line's substring with its identity columns back, from the first sequence, and\n"
+	"                                     lb / rb counting the input's columns (honours --graph-paths and --graph-gap-character; works\n"
+	"                                     under --upload-memory and --reduce-on-upload; --output-graph, if given as well, stays in\n"
+	"                                     reduced co-ordinates; one GPU only)\n"
+	"      --output-held-out-restored-graph-threads=PATH  With --hold-out and --remove-identity-columns: thread the full-length held-out\n"
+	"                                     sequences through that graph (the table of --output-held-out-graph-threads; columns count the\n"
+	"                                     input's; one GPU only)\n"
+	"      --output-sequence-restored-graph-threads=PATH  With --match-sequences and --remove-identity-columns: the same for the sequences\n"
+	"                                     of LIST, of the input's full length (works under --reduce-on-upload)\n"
 	"  -j, --segment-joining=METHOD       Segment joining method  (possible values=\"bipartite-matching\", \"greedy\", \"random\" default=`bipartite-matching')\n"
 	"      --scan-segment-lengths=SPEC    Before anything else, write the maximum segment size at every segment length bound of SPEC --\n"
 	"                                     a comma list of lengths, or LO:HI:STEP -- as a table (SEGMENT_LENGTH, MAX_SEGMENT_SIZE; one line\n"
@@ -357,8 +367,10 @@ bool write_join_score(fseq_ctx *ctx, fseq_result const &res, std::vector<uint32_
 
 // --output-held-out-graph-threads (list == nullptr: the sequences --hold-out set aside, which the context holds on the device) and
 // --output-sequence-graph-threads (the sequences of `list`; n_held: the sequences held out): fseq_graph_thread_held_out / fseq_graph_thread_rows, statistics only.
+// restored (--output-held-out-restored-graph-threads, --output-sequence-restored-graph-threads): the full-length sequences on a
+// context over the columns in which the input's differ (fseq_graph_thread_held_out_restored / fseq_graph_thread_rows_restored).
 // Tab-separated: a header, one line per sequence in the list's order, a last line '#' with the summary.
-bool write_graph_threads(fseq_ctx *ctx, char const *list, size_t n_held, size_t seq_length, char const *path)
+bool write_graph_threads(fseq_ctx *ctx, char const *list, size_t n_held, size_t seq_length, char const *path, bool restored = false)
 {
 	std::vector<std::string> queries;
 	std::vector<uint8_t const *> qrows;
@@ -383,8 +395,10 @@ bool write_graph_threads(fseq_ctx *ctx, char const *list, size_t n_held, size_t 
 	}
 	std::vector<fseq_graph_thread_row> per_row(count);
 	fseq_graph_thread_summary sm{};
-	int const rc(list ? fseq_graph_thread_rows(ctx, qrows.data(), (uint32_t) count, nullptr, nullptr, per_row.data(), nullptr, &sm)
-	                  : fseq_graph_thread_held_out(ctx, nullptr, nullptr, per_row.data(), nullptr, &sm));
+	int const rc(restored ? (list ? fseq_graph_thread_rows_restored(ctx, qrows.data(), (uint32_t) count, nullptr, nullptr, per_row.data(), nullptr, &sm)
+	                              : fseq_graph_thread_held_out_restored(ctx, nullptr, nullptr, per_row.data(), nullptr, &sm))
+	             : list ? fseq_graph_thread_rows(ctx, qrows.data(), (uint32_t) count, nullptr, nullptr, per_row.data(), nullptr, &sm)
+	                    : fseq_graph_thread_held_out(ctx, nullptr, nullptr, per_row.data(), nullptr, &sm));
 	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return false; }
 	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
 	if (!f) { std::cerr << "Unable to open the graph threads output file." << std::endl; return false; }
@@ -449,6 +463,7 @@ int main(int argc, char **argv)
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr, *out_join_score = nullptr;
 	char const *out_graph = nullptr, *graph_gap = nullptr;
 	char const *out_held_threads = nullptr, *out_seq_threads = nullptr;
+	char const *out_restored_graph = nullptr, *out_held_restored_threads = nullptr, *out_seq_restored_threads = nullptr;
 	bool graph_paths = false;
 	bool remove_identity = false;
 	unsigned long long match_min_len = 0;
@@ -488,6 +503,8 @@ int main(int argc, char **argv)
 		{"output-graph", required_argument, nullptr, 1023}, {"graph-paths", no_argument, nullptr, 1024},
 		{"graph-gap-character", required_argument, nullptr, 1025},
 		{"output-held-out-graph-threads", required_argument, nullptr, 1026}, {"output-sequence-graph-threads", required_argument, nullptr, 1027},
+		{"output-restored-graph", required_argument, nullptr, 1028},
+		{"output-held-out-restored-graph-threads", required_argument, nullptr, 1029}, {"output-sequence-restored-graph-threads", required_argument, nullptr, 1030},
 		{nullptr, 0, nullptr, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "hVi:f:e:o:s:j:m:", longopts, nullptr)) != -1)
@@ -543,6 +560,9 @@ int main(int argc, char **argv)
 			case 1025: graph_gap = optarg; break;
 			case 1026: out_held_threads = optarg; break;
 			case 1027: out_seq_threads = optarg; break;
+			case 1028: out_restored_graph = optarg; break;
+			case 1029: out_held_restored_threads = optarg; break;
+			case 1030: out_seq_restored_threads = optarg; break;
 			case 1010:
 			{
 				// as --list-memory, but a positive number: 0 MiB hold no chunk
@@ -620,16 +640,25 @@ int main(int argc, char **argv)
 		if (gpus > 1) { std::cerr << name << " is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
 		if (remove_identity) { std::cerr << name << " is not supported together with --remove-identity-columns (the sequences would be threaded in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 	}
-	if (match_seqs && !out_seq_matches && !out_seq_restored && !out_seq_threads) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
+	for (int k = 0; k < 2; ++k)
+	{
+		char const *const name = k ? "--output-sequence-restored-graph-threads" : "--output-held-out-restored-graph-threads";
+		if (!(k ? out_seq_restored_threads : out_held_restored_threads)) continue;
+		if (!((k ? match_seqs : hold_out_spec) && remove_identity)) { std::cerr << name << " requires " << (k ? "--match-sequences" : "--hold-out") << " and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
+		if (gpus > 1) { std::cerr << name << " is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
+	}
+	if (match_seqs && !out_seq_matches && !out_seq_restored && !out_seq_threads && !out_seq_restored_threads) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_matches && !match_seqs) { std::cerr << "--output-sequence-matches requires --match-sequences." << std::endl; return EXIT_FAILURE; }
 	if (match_seqs && gpus > 1) { std::cerr << "--match-sequences is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_restored && !(match_seqs && remove_identity)) { std::cerr << "--output-sequence-restored-matches requires --match-sequences and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
 	if (out_held_restored && !(hold_out_spec && remove_identity)) { std::cerr << "--output-held-out-restored-matches requires --hold-out and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
 	// (the two combine with --remove-identity-columns only for the restored match; the reports in reduced co-ordinates stay refused)
-	if (match_seqs && remove_identity && (!out_seq_restored || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	if (match_seqs && remove_identity && (!(out_seq_restored || out_seq_restored_threads) || out_seq_matches)) { std::cerr << "--match-sequences is not supported together with --remove-identity-columns (the match would be in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
 	if (out_join_score && gpus > 1) { std::cerr << "--output-join-score is not supported together with --gpus > 1 (a rank holds its own boundary states only)." << std::endl; return EXIT_FAILURE; }
 	if (out_graph && gpus > 1) { std::cerr << "--output-graph is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
-	if ((graph_paths || graph_gap) && !out_graph) { std::cerr << (graph_paths ? "--graph-paths" : "--graph-gap-character") << " requires --output-graph." << std::endl; return EXIT_FAILURE; }
+	if (out_restored_graph && gpus > 1) { std::cerr << "--output-restored-graph is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
+	if (out_restored_graph && !remove_identity) { std::cerr << "--output-restored-graph requires --remove-identity-columns (without it --output-graph is in the input's co-ordinates already)." << std::endl; return EXIT_FAILURE; }
+	if ((graph_paths || graph_gap) && !out_graph && !out_restored_graph) { std::cerr << (graph_paths ? "--graph-paths" : "--graph-gap-character") << " requires --output-graph." << std::endl; return EXIT_FAILURE; }
 	if (graph_gap && strlen(graph_gap) > 1) { std::cerr << "The gap character of the graph must be one character, or empty to keep every character." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && gpus > 1) { std::cerr << "--output-restored-segments is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_restored_segments && !remove_identity) { std::cerr << "--output-restored-segments requires --remove-identity-columns (without it --output-segments is in the input's co-ordinates already)." << std::endl; return EXIT_FAILURE; }
@@ -642,7 +671,7 @@ int main(int argc, char **argv)
 		std::string why;
 		if (!parse_hold_out(hold_out_spec, held_rows, why)) { std::cerr << "The list of sequences to hold out is " << why << '.' << std::endl; return EXIT_FAILURE; }
 		if (gpus > 1) { std::cerr << "--hold-out is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
-		if (remove_identity && (!out_held_restored || out_held_matches)) { std::cerr << "--hold-out is not supported together with --remove-identity-columns (the held-out sequences would have to lose the same columns)." << std::endl; return EXIT_FAILURE; }
+		if (remove_identity && (!(out_held_restored || out_held_restored_threads) || out_held_matches)) { std::cerr << "--hold-out is not supported together with --remove-identity-columns (the held-out sequences would have to lose the same columns)." << std::endl; return EXIT_FAILURE; }
 		if (scan_spec && !seg_len_given && !max_founders_given)
 		{ std::cerr << "--hold-out with --scan-segment-lengths needs a segment length to go on with (--segment-length-bound or --max-founders): a scan alone writes its table and nothing else." << std::endl; return EXIT_FAILURE; }
 	}
@@ -912,6 +941,17 @@ int main(int argc, char **argv)
 			std::cerr << "--output-graph needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_restored_graph)
+		{
+			std::cerr << "--output-restored-graph needs the segments of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
+		if (out_held_restored_threads || out_seq_restored_threads)
+		{
+			std::cerr << (out_held_restored_threads ? "--output-held-out-restored-graph-threads" : "--output-sequence-restored-graph-threads")
+			          << " needs the segments of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_held_threads || out_seq_threads)
 		{
 			std::cerr << (out_held_threads ? "--output-held-out-graph-threads" : "--output-sequence-graph-threads") << " needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
@@ -944,9 +984,19 @@ int main(int argc, char **argv)
 		int const gap = graph_gap ? (graph_gap[0] ? (int) (unsigned char) graph_gap[0] : -1) : (int) '-';
 		if (FSEQ_OK != (rc = fseq_write_block_graph(ctx, graph_paths ? FSEQ_GRAPH_PATHS : 0u, gap, out_graph))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
 	}
+	if (out_restored_graph)
+	{
+		// the same graph with its S lines in the input's co-ordinates, from what the device holds of the reduced context
+		std::cerr << "Outputting the restored block graph…" << std::endl;
+		int const gap = graph_gap ? (graph_gap[0] ? (int) (unsigned char) graph_gap[0] : -1) : (int) '-';
+		if (FSEQ_OK != (rc = fseq_write_block_graph_restored(ctx, graph_paths ? FSEQ_GRAPH_PATHS : 0u, gap, out_restored_graph))) { std::cerr << fseq_last_error(ctx) << std::endl; return EXIT_FAILURE; }
+	}
 	// sequences that took no part in the segmentation through its graph, from the context alone (no join)
 	if (out_held_threads && !write_graph_threads(ctx, nullptr, held_rows.size(), seq_length, out_held_threads)) return EXIT_FAILURE;
 	if (out_seq_threads && !write_graph_threads(ctx, match_seqs, 0, seq_length, out_seq_threads)) return EXIT_FAILURE;
+	// ... the full-length ones on a context over the columns in which the input's differ (seq_length is the input's)
+	if (out_held_restored_threads && !write_graph_threads(ctx, nullptr, held_rows.size(), seq_length, out_held_restored_threads, true)) return EXIT_FAILURE;
+	if (out_seq_restored_threads && !write_graph_threads(ctx, match_seqs, 0, seq_length, out_seq_restored_threads, true)) return EXIT_FAILURE;
 	std::cerr << "Joining the remaining segments…" << std::endl;
 	std::vector<uint32_t> perm((size_t) res.segment_count * res.max_segment_size);
 	std::vector<uint32_t> all_a, all_d;                         // sharded: the boundary states, collected from their owners

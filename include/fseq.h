@@ -441,6 +441,40 @@ int  fseq_graph_thread_rows(fseq_ctx *ctx, uint8_t const *const *rows, uint32_t 
                             fseq_graph_thread_summary *summary);
 int  fseq_graph_thread_held_out(fseq_ctx *ctx, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row,
                                 fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary);
+/* ---- the block graph in the SOURCE's co-ordinates on an identity-reduced context (no counterpart in the reference) ----
+ * ctx was made by fseq_create_without_identity_columns, its _held form or the reduce-on-upload input
+ * (fseq_set_rows_streamed_without_identity_columns, fseq_input_end_kept), and has a finished long-path run whose S merged
+ * segments tile the kept columns.  Segment s owns the source range [src_lb_s, src_rb_s) of fseq_get_segments_restored.  The
+ * classes, node ids, edges, row_nodes and the P and L lines are the reduced graph's, unchanged: rows that agree on the kept
+ * columns of a segment agree on its whole source range, and identity columns do not move the pBWT order.  So fseq_block_graph
+ * serves these contexts as it is; the `segment` of its nodes indexes fseq_get_segments_restored, whose lb / rb are the node's
+ * source range.
+ * The RESTORED LABEL of node (s, j) has, for p ascending over [src_lb_s, src_rb_s): row 0's byte of the source where p is an
+ * identity column, otherwise the representative row's byte at the kept column c with kept[c] == p; bytes equal to the gap
+ * byte left out; '*' if nothing is left.
+ * fseq_write_block_graph_restored writes fseq_write_block_graph's file -- the header, every L line and every P line equal
+ * that call's byte for byte -- with the restored label, its LN and lb / rb = src_lb_s / src_rb_s in every S line: the
+ * concatenated labels of a P line spell the source's row without its gap bytes.  Batches, FSEQ_GRAPH_BATCH and
+ * fseq_debug_graph_file as there.
+ * A query of n_src bytes CARRIES node (s, j) iff its codes at the kept columns of the segment equal the node's (the rule of
+ * fseq_graph_thread_rows: a byte outside the alphabet equals nothing) and it has no exception cell in [src_lb_s, src_rb_s) --
+ * an identity column in which it differs from row 0, by a byte outside the alphabet as by any other.
+ * fseq_graph_thread_rows_restored takes n_src raw bytes per query (uploaded once: the kept columns packed, the exception cells
+ * listed, both in temporaries of the call); fseq_graph_thread_held_out_restored threads the held-out rows a context made by
+ * fseq_create_without_identity_columns_held carries, with the exception cells it was made with.  Outputs as their twins';
+ * columns_matched and longest_walk_columns count SOURCE columns.  Both leave the run's results and the context's last match
+ * as they were, the exception lists of a restored match included (fseq_get_match_exceptions answers as before).
+ * Refuse, each with nothing written and nothing left behind: what the reduced twin refuses, with its code (but that the context
+ * is identity-reduced); FSEQ_E_ARG -- a context that is not identity-reduced, the held-out form on a context without carried
+ * held-out rows; FSEQ_E_UNSUPPORTED -- where fseq_get_segments_restored refuses (a source of 2^32 - 1 columns or more), for
+ * the threads more than 4,096 classes in a segment.  Not for sharded contexts; there is no host form. */
+int  fseq_write_block_graph_restored(fseq_ctx *ctx, uint32_t flags, int gap_byte, char const *path);
+int  fseq_graph_thread_rows_restored(fseq_ctx *ctx, uint8_t const *const *rows /* n_src bytes each */, uint32_t n_rows,
+                                     uint32_t *nodes /* [S][n_rows] */, uint32_t *steps /* [S-1][n_rows] */,
+                                     fseq_graph_thread_row *per_row /* [n_rows] */, fseq_graph_thread_segment *per_segment /* [S] */,
+                                     fseq_graph_thread_summary *summary);
+int  fseq_graph_thread_held_out_restored(fseq_ctx *ctx, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row,
+                                         fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary);
 /* replaces: join_context::output_in_permutation_order (join_context.cc:333-356): max_segment_size
  * lines; line r = concatenation over segments of rows[permutations[s][r]][lb_s, rb_s).  rows = the
  * raw input sequences.  path NULL or "-" = stdout. */
