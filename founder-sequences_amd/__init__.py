@@ -113,6 +113,16 @@ class GraphThreadInfo(C.Structure):
                 ("queries_out_of_alphabet", C.c_uint64)]
 
 
+class GraphNearestSummary(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("segments", C.c_uint64), ("segments_admitted", C.c_uint64), ("segments_exact", C.c_uint64),
+                ("junctions_linked", C.c_uint64), ("junctions_novel", C.c_uint64), ("walks", C.c_uint64), ("rows_on_graph", C.c_uint64),
+                ("mismatches", C.c_uint64), ("ms_device", C.c_double)]
+
+
+class GraphNearestInfo(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("packed_words", C.c_uint64), ("query_words", C.c_uint64), ("bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class DpListsInfo(C.Structure):
     _fields_ = [("unproven", C.c_uint32), ("dp_chunks", C.c_uint32), ("dp_sweeps", C.c_uint32), ("launches", C.c_uint32)]
 
@@ -146,6 +156,13 @@ GRAPH_THREAD_ROW_DTYPE = np.dtype([("columns_matched", "<u8"), ("longest_walk_co
                                    ("junctions_novel", "<u4"), ("walks", "<u4"), ("longest_walk_segments", "<u4"), ("reserved", "<u4")])
 GRAPH_THREAD_SEGMENT_DTYPE = np.dtype([("matched", "<u4"), ("linked", "<u4"), ("novel", "<u4"), ("reserved", "<u4")])
 GRAPH_THREAD_MAX_CLASSES = 4096    # csrc/fseq_graphthread.hpp, GT_MAX_CLASSES
+# fseq_graph_nearest_row (include/fseq.h), 64 bytes, and fseq_graph_nearest_segment, 32 bytes
+GRAPH_NEAREST_ROW_DTYPE = np.dtype([("columns_admitted", "<u8"), ("longest_walk_columns", "<u8"), ("mismatches_admitted", "<u8"), ("mismatches", "<u8"),
+                                    ("segments_admitted", "<u4"), ("segments_exact", "<u4"), ("junctions_linked", "<u4"), ("junctions_novel", "<u4"),
+                                    ("walks", "<u4"), ("longest_walk_segments", "<u4"), ("max_distance", "<u4"), ("reserved", "<u4")])
+GRAPH_NEAREST_SEGMENT_DTYPE = np.dtype([("mismatches", "<u8"), ("admitted", "<u4"), ("exact", "<u4"), ("linked", "<u4"), ("novel", "<u4"),
+                                        ("max_distance", "<u4"), ("reserved", "<u4")])
+GRAPH_NEAREST_BATCH_BYTES = 256 << 20   # csrc/fseq_graphnearest_plan.hpp, GN_BATCH_BYTES
 
 MATCH_PIECE_DTYPE = np.dtype([("lb", "<u8"), ("rb", "<u8"), ("row", "<u4"), ("n_founders", "<u4")])
 MATCH_MAX_FOUNDERS = 2048      # csrc/fseq_match.hpp, MT_MAX_FOUNDERS
@@ -183,6 +200,7 @@ EXPORTS = [
     "fseq_block_graph", "fseq_write_block_graph", "fseq_debug_graph_file",
     "fseq_debug_local_pass",
     "fseq_graph_thread_rows", "fseq_graph_thread_held_out", "fseq_debug_graph_thread",
+    "fseq_graph_nearest_rows", "fseq_graph_nearest_held_out", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
     "fseq_write_block_graph_restored", "fseq_graph_thread_rows_restored", "fseq_graph_thread_held_out_restored",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
@@ -194,7 +212,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
                  "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass",
-                 "fseq_debug_graph_thread"]
+                 "fseq_debug_graph_thread", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -353,6 +371,12 @@ def load_library():
     L.fseq_graph_thread_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_graph_thread_held_out.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_debug_graph_thread.argtypes = [vp, C.POINTER(GraphThreadInfo)]
+    L.fseq_graph_nearest_rows.argtypes = [vp, C.POINTER(vp), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.POINTER(GraphNearestSummary)]
+    L.fseq_graph_nearest_held_out.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.POINTER(GraphNearestSummary)]
+    L.fseq_debug_graph_nearest_info.argtypes = [vp, C.POINTER(GraphNearestInfo)]
+    L.fseq_debug_graph_nearest_plan.argtypes = [vp, vp, vp, u64, C.c_uint32, u64, vp, vp, C.POINTER(u64)]
+    L.fseq_debug_graph_nearest.argtypes = [C.c_int, vp, u64, C.c_uint32, u64, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, u64, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.POINTER(GraphNearestInfo)]
     L.fseq_write_block_graph_restored.argtypes = [vp, C.c_uint32, C.c_int, C.c_char_p]
     L.fseq_graph_thread_rows_restored.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_graph_thread_held_out_restored.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
@@ -586,6 +610,67 @@ def restored_bounds_host(kept, n_src, lb, rb):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return src_lb[:S].copy(), src_rb[:S].copy()
+
+
+def graph_nearest_plan_host(lb, rb, count, bits, budget_bytes=GRAPH_NEAREST_BATCH_BYTES):
+    """How graph_nearest_rows() lays out its packed class representatives and cuts the segments into batches (graph_nearest_words
+    and graph_nearest_plan, csrc/fseq_graphnearest_plan.hpp, through fseq_debug_graph_nearest_plan; no device): segments
+    [lb[s], rb[s]) of count[s] classes at `bits` bits a code.  Returns (words, first): words[s] the representatives' words in
+    front of segment s (S + 1 entries), batch b the segments [first[b], first[b + 1])."""
+    L = load_library()
+    lb = np.ascontiguousarray(lb, dtype=np.uint64)
+    rb = np.ascontiguousarray(rb, dtype=np.uint64)
+    count = np.ascontiguousarray(count, dtype=np.uint32)
+    if lb.ndim != 1 or rb.shape != lb.shape or count.shape != lb.shape:
+        raise FseqError(FSEQ_E_ARG, "graph_nearest_plan_host: one entry of lb, rb and count per segment")
+    S = len(lb)
+    words = np.zeros(S + 1, dtype=np.uint64)
+    first = np.zeros(S + 1, dtype=np.uint64)
+    nb = C.c_uint64()
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    rc = L.fseq_debug_graph_nearest_plan(ptr(lb), ptr(rb), ptr(count), S, int(bits), int(budget_bytes), words.ctypes.data, first.ctypes.data, C.byref(nb))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return words, first[:nb.value + 1].copy()
+
+
+def debug_graph_nearest(codes, bits, seg_lb, seg_rb, count, rep, query_codes, qbits, sigma, batch_bytes=None, device=0, want_info=False):
+    """The pack and distance kernels of graph_nearest_rows() through the production launcher on caller-supplied tables
+    (fseq_debug_graph_nearest; needs no context): codes [m][n] the alignment's codes, packed here at `bits` with pack_columns;
+    segments [seg_lb[s], seg_rb[s]) with count[s] classes whose representative rows are rep[s][:count[s]] (rep is [S][X]);
+    query_codes [Q][n] packed at qbits; sigma: the alphabet's size (a query code at or above it is a byte outside the alphabet).
+    Returns (nodes as CLASS indices, distances, ties), each [S][Q] (with want_info, also fseq_debug_graph_nearest_info's dict).
+    FseqError(FSEQ_E_ARG), before a device is touched, for whatever a kernel could form an index from: rep >= m, count > X or 0,
+    bounds outside n or out of order, bits / qbits not in {2, 4, 8}, qbits < bits, a code at or above 2^bits or sigma, a query
+    code at or above 2^qbits."""
+    L = load_library()
+    codes = np.ascontiguousarray(codes)
+    query_codes = np.ascontiguousarray(query_codes)
+    seg_lb = np.ascontiguousarray(seg_lb, dtype=np.uint64)
+    seg_rb = np.ascontiguousarray(seg_rb, dtype=np.uint64)
+    count = np.ascontiguousarray(count, dtype=np.uint32)
+    rep = np.ascontiguousarray(rep, dtype=np.uint32)
+    if bits not in (2, 4, 8) or qbits not in (2, 4, 8) or qbits < bits:
+        raise FseqError(FSEQ_E_ARG, "debug_graph_nearest: bits and qbits are 2, 4 or 8, and qbits is not below bits")
+    if codes.ndim != 2 or query_codes.ndim != 2 or 0 in codes.shape or query_codes.shape[0] == 0 or query_codes.shape[1] != codes.shape[1]:
+        raise FseqError(FSEQ_E_ARG, "debug_graph_nearest: codes is [m][n], query_codes [Q][n]")
+    if seg_lb.ndim != 1 or len(seg_lb) == 0 or seg_rb.shape != seg_lb.shape or count.shape != seg_lb.shape or rep.ndim != 2 or rep.shape[0] != len(seg_lb) or rep.shape[1] == 0:
+        raise FseqError(FSEQ_E_ARG, "debug_graph_nearest: seg_lb, seg_rb and count have S entries, rep is [S][X]")
+    if int(codes.max()) >= min(1 << bits, max(int(sigma), 1)) or int(codes.min()) < 0 or int(query_codes.max()) >= (1 << qbits) or int(query_codes.min()) < 0:
+        raise FseqError(FSEQ_E_ARG, "debug_graph_nearest: a code at or above 2^bits (or sigma), or a query code at or above 2^qbits")
+    (m, n), Q, (S, X) = codes.shape, query_codes.shape[0], rep.shape
+    cols, ld = pack_columns(codes.astype(np.uint8), bits)
+    qcols, qld = pack_columns(query_codes.astype(np.uint8), qbits)
+    out = np.zeros((3, S, Q), dtype=np.uint32)
+    info = GraphNearestInfo()
+    rc = L.fseq_debug_graph_nearest(int(device), cols.ctypes.data, ld, m, n, bits, seg_lb.ctypes.data, seg_rb.ctypes.data, count.ctypes.data, rep.ctypes.data,
+                                    S, X, qcols.ctypes.data, qld, Q, qbits, int(sigma), int(batch_bytes or 0), out[0].ctypes.data, out[1].ctypes.data,
+                                    out[2].ctypes.data, C.byref(info))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    if want_info:
+        return out[0], out[1], out[2], {k: getattr(info, k) for k, _ in GraphNearestInfo._fields_ if k != "reserved"}
+    return out[0], out[1], out[2]
 
 
 def input_kept_range_host(kept, c0, ncols):
@@ -1317,6 +1402,52 @@ class SegmentationContext:
         info = GraphThreadInfo()
         self._check(self.L.fseq_debug_graph_thread(self.h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in GraphThreadInfo._fields_}
+
+    # ---- the nearest node of every segment, and how far it is
+    def _graph_nearest(self, call, n_rows, want):
+        S = int(self.result.segment_count) if self.result is not None else 0
+        arrays = {k: (np.zeros((S if k != "steps" else max(S, 1) - 1, n_rows), dtype=np.uint32) if on else None) for k, on in want}
+        per_row = np.zeros(n_rows, dtype=GRAPH_NEAREST_ROW_DTYPE)
+        per_segment = np.zeros(S, dtype=GRAPH_NEAREST_SEGMENT_DTYPE)
+        sm = GraphNearestSummary()
+        self._check(call(*[None if arrays[k] is None else arrays[k].ctypes.data for k, _ in want], per_row.ctypes.data,
+                         per_segment.ctypes.data if S else None, C.byref(sm)))
+        arrays.update({"per_row": per_row, "per_segment": per_segment, "summary": {k: getattr(sm, k) for k, _ in GraphNearestSummary._fields_}})
+        return arrays
+
+    def graph_nearest_rows(self, queries, max_distance=0, want_nodes=True, want_distances=True, want_ties=True, want_steps=True):
+        """For rows that are NOT the alignment's, the NEAREST node of every segment of the founder block graph and how far it is
+        (fseq_graph_nearest_rows): queries as graph_thread_rows() takes them.  Returns {"nodes": [segments, n_rows], the node
+        (block_graph()'s ids) of segment s with the fewest columns in which its representative row's code differs from query
+        q's, the smallest class among equals; "distances": that number; "ties": the classes of the segment that attain it;
+        "steps": [segments - 1, n_rows], the index into block_graph()["edges"] of the edge between the two nodes of a junction
+        where both distances are at most max_distance and the edge exists, else GRAPH_NONE; "per_row"
+        (GRAPH_NEAREST_ROW_DTYPE); "per_segment" (GRAPH_NEAREST_SEGMENT_DTYPE); "summary": a dict}.  An array that is not wanted
+        stays on the device and its entry is None.  With max_distance = 0, nodes where the distance is 0, steps and the walk
+        statistics are graph_thread_rows()'.  The run's results, the last match and graph_thread_info() stay as they were.  Not
+        for identity-reduced or sharded contexts; there is no host form."""
+        a = queries
+        if not isinstance(a, np.ndarray):
+            a = np.array([np.frombuffer(bytes(f), dtype=np.uint8) for f in a], dtype=np.uint8).reshape(len(a), -1)
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2 or (a.shape[0] and a.shape[1] != self.n):
+            raise ValueError("graph_nearest_rows: queries must be rows of n = %d bytes" % self.n)
+        rows = (C.c_void_p * max(a.shape[0], 1))(*[a.ctypes.data + r * a.strides[0] for r in range(a.shape[0])])
+        want = (("nodes", want_nodes), ("distances", want_distances), ("ties", want_ties), ("steps", want_steps))
+        return self._graph_nearest(lambda *out: self.L.fseq_graph_nearest_rows(self.h, rows, a.shape[0], int(max_distance), *out), a.shape[0], want)
+
+    def graph_nearest_held_out(self, max_distance=0, want_nodes=True, want_distances=True, want_ties=True, want_steps=True):
+        """... the held-out rows of a context made by without_rows(), where they lie on the device (fseq_graph_nearest_held_out):
+        nothing is uploaded; query q is held_out()[1][q]."""
+        want = (("nodes", want_nodes), ("distances", want_distances), ("ties", want_ties), ("steps", want_steps))
+        return self._graph_nearest(lambda *out: self.L.fseq_graph_nearest_held_out(self.h, int(max_distance), *out), int(getattr(self, "n_held", 0)), want)
+
+    def graph_nearest_info(self):
+        """How the last graph_nearest_rows() / graph_nearest_held_out() packed its words (fseq_debug_graph_nearest_info):
+        dict(batches, packed_words, query_words, bits)."""
+        info = GraphNearestInfo()
+        self._check(self.L.fseq_debug_graph_nearest_info(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in GraphNearestInfo._fields_ if k != "reserved"}
 
     def write_founders_device(self, permutations, path):
         """--output-founders from the alignment resident on the device (no host rows)."""

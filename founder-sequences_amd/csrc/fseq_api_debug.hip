@@ -72,6 +72,8 @@ int fseq_debug_set_tuning(fseq_ctx *c, char const *name, char const *value)
 	if (!strcmp(name, "FSEQ_GRAPH_BATCH")) return FSEQ_OK;
 	// (... and the key width of the graph threading by fseq_graph_thread_rows / fseq_graph_thread_held_out alone)
 	if (!strcmp(name, "FSEQ_GRAPH_THREAD_KEY_BITS")) return FSEQ_OK;
+	// (... and the batch of packed representatives by fseq_graph_nearest_rows / fseq_graph_nearest_held_out alone)
+	if (!strcmp(name, "FSEQ_GRAPH_NEAREST_BATCH")) return FSEQ_OK;
 	// (the geometry and the kernel choice may depend on it: the work buffers of an earlier run were sized for the old one)
 	(void) hipSetDevice(c->p.device);
 	if (c->stream) (void) hipStreamSynchronize(c->stream);

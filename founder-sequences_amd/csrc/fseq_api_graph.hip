@@ -2,7 +2,9 @@
 // arrays), fseq_write_block_graph (the GFA 1.0 file from the device, csrc/fseq_graph.hpp) and fseq_debug_graph_file; and
 // fseq_graph_thread_rows / fseq_graph_thread_held_out (rows that are not the graph's own threaded through it,
 // csrc/fseq_graphthread.hpp) with fseq_debug_graph_thread; and the three in the SOURCE's co-ordinates on an identity-reduced
-// context: fseq_write_block_graph_restored, fseq_graph_thread_rows_restored, fseq_graph_thread_held_out_restored.
+// context: fseq_write_block_graph_restored, fseq_graph_thread_rows_restored, fseq_graph_thread_held_out_restored; and
+// fseq_graph_nearest_rows / fseq_graph_nearest_held_out (the nearest node of every segment and its distance,
+// csrc/fseq_graphnearest.hpp) with fseq_debug_graph_nearest, fseq_debug_graph_nearest_info and fseq_debug_graph_nearest_plan.
 //
 // No counterpart in the reference.  Both entries build on the device front of fseq_join_greedy (fseq_joinprep.hpp, unchanged):
 // k_join_classes_wide numbers the classes of every merged segment, k_join_edges_wide<false> / k_join_scan / <true> leave the
@@ -13,6 +15,7 @@
 #include "fseq_joinprep.hpp"
 #include "fseq_graph.hpp"
 #include "fseq_graphthread.hpp"
+#include "fseq_graphnearest.hpp"
 
 using namespace fseq;
 
@@ -312,6 +315,261 @@ int fseq_debug_graph_thread(fseq_ctx *c, fseq_graph_thread_info *out)
 	if (!c->graphthread.have) return fail(c, FSEQ_E_ARG, "no fseq_graph_thread_rows / fseq_graph_thread_held_out has finished on this context");
 	*out = c->graphthread.info;
 	return FSEQ_OK;
+}
+
+} // extern "C"
+
+// ---- the nearest node of every segment (csrc/fseq_graphnearest.hpp)
+
+// The layout of the packed words and the batches, on the host (csrc/fseq_graphnearest_plan.hpp), and what the largest batch takes.
+struct GraphNearestPlan {
+	std::vector<uint64_t> qoff, roff, first;             // [S + 1], [S + 1], [batches + 1]
+	uint64_t batches = 0, most_rw = 0, most_qw = 0;      // the largest batch: representatives' words, words of one query
+	// nullptr, or why not (what: FSEQ_E_ARG or FSEQ_E_UNSUPPORTED)
+	char const *build(uint64_t const *lb, uint64_t const *rb, uint32_t const *count, uint64_t S, uint32_t bits, uint64_t budget, int *what)
+	{
+		*what = FSEQ_E_ARG;
+		try { qoff.assign(S + 1, 0); roff.assign(S + 1, 0); first.assign(S + 1, 0); }
+		catch (std::bad_alloc const &) { *what = FSEQ_E_OOM; return "the plan on the host"; }
+		for (uint64_t s = 0; lb && rb && s < S; ++s)
+			if (rb[s] > lb[s] && rb[s] - lb[s] >= 0xFFFFFFFFull) { *what = FSEQ_E_UNSUPPORTED; return "a segment of 2^32 - 1 columns or more (distances are 32-bit)"; }
+		if (char const *why = graph_nearest_words(lb, rb, count, S, bits, qoff.data(), roff.data())) return why;
+		if (char const *why = graph_nearest_plan(roff.data(), S, budget, first.data(), &batches)) return why;
+		for (uint64_t b = 0; b < batches; ++b)
+		{
+			most_rw = std::max(most_rw, roff[first[b + 1]] - roff[first[b]]);
+			most_qw = std::max(most_qw, qoff[first[b + 1]] - qoff[first[b]]);
+		}
+		return nullptr;
+	}
+};
+
+// The production launcher, for the entries and for fseq_debug_graph_nearest alike: batch by batch the two pack kernels and the
+// distance kernel.  A holds everything but the batch; A.rw / A.qw have room for the plan's largest batch.
+static void graph_nearest_launch(hipStream_t st, GraphNearestArgs A, GraphNearestPlan const &P)
+{
+	uint32_t const Q = A.G.Q, X = A.G.X;
+	uint32_t const tiles = (uint32_t) std::min<size_t>(((size_t) Q + GT_T - 1) / GT_T, 1024);
+	uint32_t const ctiles = (uint32_t) std::min<size_t>(((size_t) X + GT_T - 1) / GT_T, 1024);
+	uint32_t const w = 8u >> A.G.qbsh;
+	for (uint64_t b = 0; b < P.batches; ++b)
+	{
+		A.s0 = (uint32_t) P.first[b]; A.s1 = (uint32_t) P.first[b + 1];
+		uint32_t const ns = A.s1 - A.s0;
+		hipLaunchKernelGGL(k_gn_pack<false>, dim3(ns, ctiles), dim3(GT_T), 0, st, A);
+		hipLaunchKernelGGL(k_gn_pack<true>, dim3(ns, tiles), dim3(GT_T), 0, st, A);
+		if (w == 2u) hipLaunchKernelGGL(k_gn_distance<2>, dim3(ns, tiles), dim3(GT_T), 0, st, A, (uint32_t const *) A.rw, (uint32_t const *) A.qw);
+		else if (w == 4u) hipLaunchKernelGGL(k_gn_distance<4>, dim3(ns, tiles), dim3(GT_T), 0, st, A, (uint32_t const *) A.rw, (uint32_t const *) A.qw);
+		else hipLaunchKernelGGL(k_gn_distance<8>, dim3(ns, tiles), dim3(GT_T), 0, st, A, (uint32_t const *) A.rw, (uint32_t const *) A.qw);
+	}
+}
+
+// both entries behind their refusals: the Q queries at q (column-major, packed at qbsh, qld bytes a column)
+static int graph_nearest(fseq_ctx *c, uint8_t const *q, size_t qld, uint32_t qbsh, uint32_t Q, uint32_t max_distance, uint32_t *nodes, uint32_t *distances,
+                         uint32_t *ties, uint32_t *steps, fseq_graph_nearest_row *per_row, fseq_graph_nearest_segment *per_segment, fseq_graph_nearest_summary *summary)
+{
+	double const t0 = now_ms();
+	hipStream_t st = c->stream;
+	if (qbsh > c->bsh) return fail(c, FSEQ_E_ARG, "nearest nodes: queries packed narrower than the alignment");
+	GraphTables T(c);
+	if (int const rc = T.build(true)) return rc;
+	size_t const S = T.S;
+	std::vector<uint64_t> lb, rb;
+	try { lb.resize(S); rb.resize(S); }
+	catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "nearest nodes: the segments on the host"); }
+	for (size_t i = 0; i < S; ++i) { lb[i] = c->segments[i].lb; rb[i] = c->segments[i].rb; }
+	GraphNearestPlan P;
+	uint64_t const budget = c->tune.graph_nearest_batch > 0 ? (uint64_t) c->tune.graph_nearest_batch : GN_BATCH_BYTES;
+	int what = FSEQ_E_ARG;
+	if (char const *why = P.build(lb.data(), rb.data(), T.count.data(), S, 8u >> qbsh, budget, &what))
+	{
+		(void) hipStreamSynchronize(st);
+		std::string const msg = std::string("nearest nodes: ") + why;
+		return fail(c, what, msg.c_str());
+	}
+	DevTemp<uint64_t> d_qoff(c), d_roff(c);
+	DevTemp<uint32_t> d_rw(c), d_qw(c), d_nodes(c), d_dist(c), d_ties(c), d_adm(c), d_steps(c);
+	DevTemp<fseq_graph_nearest_row> d_rows(c);
+	DevTemp<fseq_graph_nearest_segment> d_segs(c);
+	int rc;
+	if ((rc = d_qoff.alloc(S + 1)) || (rc = d_roff.alloc(S + 1)) || (rc = d_rw.alloc((size_t) P.most_rw)) || (rc = d_qw.alloc((size_t) P.most_qw * Q)) ||
+	    (rc = d_nodes.alloc(S * Q)) || (rc = d_dist.alloc(S * Q)) || (rc = d_ties.alloc(S * Q)) || (rc = d_adm.alloc(S * Q)) ||
+	    (rc = d_steps.alloc(std::max<size_t>(T.pairs, 1) * Q)) || (rc = d_rows.alloc(Q)) || (rc = d_segs.alloc(S)))
+	{ (void) hipStreamSynchronize(st); return rc; }
+	std::vector<fseq_graph_nearest_row> rows;
+	try { rows.resize(Q); }
+	catch (std::bad_alloc const &) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_OOM, "nearest nodes: the rows' statistics on the host"); }
+	GraphNearestArgs A{};
+	GraphThreadArgs &G = A.G;
+	G.seg_lb = T.d_lb; G.seg_rb = T.d_rb; G.count = T.d_count; G.rep = T.d_rep; G.noff = T.d_noff;
+	G.m = (uint32_t) T.m; G.X = T.X; G.S = (uint32_t) S; G.n = c->p.n;
+	G.msa = c->d_msa; G.ld = c->ld; G.bsh = c->bsh;
+	G.q = q; G.qld = qld; G.qbsh = qbsh; G.Q = Q; G.sigma = c->sigma;
+	G.nodes = d_adm; G.steps = d_steps;
+	G.edges = T.d_edges; G.offset = T.d_off; G.nedges = T.d_ne; G.pairs = T.pairs; G.n_edges = T.d_edges.base ? T.edges : 0u;
+	A.qoff = d_qoff; A.roff = d_roff; A.rw = d_rw; A.qw = d_qw; A.rw_cap = P.most_rw; A.qw_cap = P.most_qw * Q;
+	A.max_distance = max_distance; A.nodes = d_nodes; A.distances = d_dist; A.ties = d_ties;
+	hipError_t e = hipMemcpyAsync(d_qoff, P.qoff.data(), (S + 1) * 8, hipMemcpyHostToDevice, st);      // (P lives until the synchronisation below)
+	if (e == hipSuccess) e = hipMemcpyAsync(d_roff, P.roff.data(), (S + 1) * 8, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_adm, 0xFF, S * Q * 4, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_nodes, 0, S * Q * 4, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_dist, 0, S * Q * 4, st);
+	if (e == hipSuccess) e = hipMemsetAsync(d_ties, 0, S * Q * 4, st);
+	if (e != hipSuccess) { (void) hipStreamSynchronize(st); return fail(c, FSEQ_E_HIP, "nearest nodes: preparation", e); }
+	graph_nearest_launch(st, A, P);
+	uint32_t const tiles = (uint32_t) std::min<size_t>(((size_t) Q + GT_T - 1) / GT_T, 1024);
+	if (T.pairs) hipLaunchKernelGGL(k_gt_steps, dim3(T.pairs, tiles), dim3(GT_T), 0, st, G);
+	hipLaunchKernelGGL(k_gn_rows, dim3((Q + GT_T - 1u) / GT_T), dim3(GT_T), 0, st, A, (fseq_graph_nearest_row *) d_rows);
+	if (per_segment) hipLaunchKernelGGL(k_gn_segments, dim3((uint32_t) S), dim3(GT_T), 0, st, A, (fseq_graph_nearest_segment *) d_segs);
+	e = hipMemcpyAsync(rows.data(), d_rows, (size_t) Q * sizeof(fseq_graph_nearest_row), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && nodes) e = hipMemcpyAsync(nodes, d_nodes, S * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && distances) e = hipMemcpyAsync(distances, d_dist, S * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && ties) e = hipMemcpyAsync(ties, d_ties, S * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && steps && T.pairs) e = hipMemcpyAsync(steps, d_steps, (size_t) T.pairs * Q * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && per_segment) e = hipMemcpyAsync(per_segment, d_segs, S * sizeof(fseq_graph_nearest_segment), hipMemcpyDeviceToHost, st);
+	hipError_t const es = hipStreamSynchronize(st);                  // (the host arrays are written to here, whatever was queued)
+	if (e == hipSuccess) e = es;
+	if (e == hipSuccess) e = hipGetLastError();
+	if (e != hipSuccess) return fail(c, FSEQ_E_HIP, "nearest nodes", e);
+	fseq_graph_nearest_summary sm{};
+	sm.rows = Q; sm.segments = S;
+	for (fseq_graph_nearest_row const &r : rows)
+	{
+		sm.segments_admitted += r.segments_admitted; sm.segments_exact += r.segments_exact; sm.junctions_linked += r.junctions_linked;
+		sm.junctions_novel += r.junctions_novel; sm.walks += r.walks; sm.mismatches += r.mismatches;
+		sm.rows_on_graph += r.walks == 1u && r.longest_walk_segments == S;
+	}
+	if (per_row) memcpy(per_row, rows.data(), (size_t) Q * sizeof(fseq_graph_nearest_row));
+	sm.ms_device = now_ms() - t0;
+	if (summary) *summary = sm;
+	c->graphnearest.have = true;
+	c->graphnearest.info = fseq_graph_nearest_info{P.batches, P.roff[S], P.qoff[S], 8u >> qbsh, 0u};
+	return FSEQ_OK;
+}
+
+// what the nearest-node entries refuse: the threading's refusals but for its cap of 4,096 classes a segment
+static int graph_nearest_refusals(fseq_ctx *c)
+{
+	if (int const rc = graph_refusals(c)) return rc;
+	if (c->idn.have) return fail(c, FSEQ_E_UNSUPPORTED, "nearest nodes: a context made by fseq_create_without_identity_columns (queries in source co-ordinates, with their exception cells, are not served)");
+	if (!c->have_input || !c->d_msa) return fail(c, FSEQ_E_ARG, "no alignment resident on the device");
+	for (size_t i = 0; i < c->segments.size(); ++i)
+		if (c->segments[i].rb - c->segments[i].lb >= 0xFFFFFFFFull) return fail(c, FSEQ_E_UNSUPPORTED, "nearest nodes: a segment of 2^32 - 1 columns or more (distances are 32-bit)");
+	return FSEQ_OK;
+}
+
+extern "C" {
+
+int fseq_graph_nearest_rows(fseq_ctx *c, uint8_t const *const *rows, uint32_t n_rows, uint32_t max_distance, uint32_t *nodes, uint32_t *distances, uint32_t *ties,
+                            uint32_t *steps, fseq_graph_nearest_row *per_row, fseq_graph_nearest_segment *per_segment, fseq_graph_nearest_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!rows || 0 == n_rows) return fail(c, FSEQ_E_ARG, "nearest nodes: no query rows");
+	for (uint32_t i = 0; i < n_rows; ++i)
+		if (!rows[i]) return fail(c, FSEQ_E_ARG, "nearest nodes: null query row");
+	if (int const rc = graph_nearest_refusals(c)) return rc;
+	(void) hipSetDevice(c->p.device);
+	// the queries' packing: the narrowest that leaves the code `sigma` free for a byte outside the alphabet (as fseq_graph_thread_rows)
+	uint32_t const sigma = c->sigma, bsh = sigma + 1u <= 4u ? 2u : sigma + 1u <= 16u ? 1u : 0u;
+	size_t const ld = ((((size_t) n_rows + (1u << bsh) - 1u) >> bsh) + 15) & ~size_t(15);
+	DevTemp<uint8_t> d_q(c);                                         // (the call's own: the last match keeps its queries)
+	if (int const rc = upload_queries(c, rows, n_rows, bsh, ld, d_q)) return rc;
+	return graph_nearest(c, d_q, ld, bsh, n_rows, max_distance, nodes, distances, ties, steps, per_row, per_segment, summary);
+}
+
+// the held-out rows are on the device already, column-major and packed at the alignment's width: nothing is uploaded
+int fseq_graph_nearest_held_out(fseq_ctx *c, uint32_t max_distance, uint32_t *nodes, uint32_t *distances, uint32_t *ties, uint32_t *steps,
+                                fseq_graph_nearest_row *per_row, fseq_graph_nearest_segment *per_segment, fseq_graph_nearest_summary *summary)
+{
+	if (!c) return FSEQ_E_ARG;
+	if (!c->hold.have && !c->idn.have) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
+	if (int const rc = graph_nearest_refusals(c)) return rc;
+	if (!c->hold.have || !c->hold.n_held || !c->hold.cols) return fail(c, FSEQ_E_ARG, "not a context made by fseq_create_without_rows");
+	(void) hipSetDevice(c->p.device);
+	return graph_nearest(c, c->hold.cols, c->hold.ld, c->bsh, c->hold.n_held, max_distance, nodes, distances, ties, steps, per_row, per_segment, summary);
+}
+
+int fseq_debug_graph_nearest_info(fseq_ctx *c, fseq_graph_nearest_info *out)
+{
+	if (!c || !out) return FSEQ_E_ARG;
+	if (!c->graphnearest.have) return fail(c, FSEQ_E_ARG, "no fseq_graph_nearest_rows / fseq_graph_nearest_held_out has finished on this context");
+	*out = c->graphnearest.info;
+	return FSEQ_OK;
+}
+
+int fseq_debug_graph_nearest_plan(uint64_t const *lb, uint64_t const *rb, uint32_t const *count, uint64_t n_segments, uint32_t bits, uint64_t budget_bytes,
+                                  uint64_t *words, uint64_t *first, uint64_t *n_batches)
+{
+	if (!words || !first || !n_batches || 0 == budget_bytes) return FSEQ_E_ARG;
+	GraphNearestPlan P;
+	int what = FSEQ_E_ARG;
+	if (P.build(lb, rb, count, n_segments, bits, budget_bytes, &what)) return what;
+	std::copy(P.roff.begin(), P.roff.end(), words);
+	std::copy(P.first.begin(), P.first.begin() + (size_t) P.batches + 1, first);
+	*n_batches = P.batches;
+	return FSEQ_OK;
+}
+
+int fseq_debug_graph_nearest(int device, uint8_t const *cols, uint64_t ld, uint32_t m, uint64_t n, uint32_t bits, uint64_t const *seg_lb, uint64_t const *seg_rb,
+                             uint32_t const *count, uint32_t const *rep, uint32_t S, uint32_t X, uint8_t const *qcols, uint64_t qld, uint32_t Q, uint32_t qbits,
+                             uint32_t sigma, uint64_t batch_bytes, uint32_t *nodes, uint32_t *distances, uint32_t *ties, fseq_graph_nearest_info *info)
+{
+	// whatever a kernel could form an index from, before a device is touched
+	if (!cols || !seg_lb || !seg_rb || !count || !rep || !qcols || !nodes || !distances || !ties) return FSEQ_E_ARG;
+	if (0 == m || 0 == n || 0 == S || 0 == X || 0 == Q || m > 0x7FFFFFFFu || S > 0x7FFFFFFFu || X > 0xFFFFu) return FSEQ_E_ARG;
+	if ((bits != 2 && bits != 4 && bits != 8) || (qbits != 2 && qbits != 4 && qbits != 8) || qbits < bits) return FSEQ_E_ARG;
+	uint32_t const bsh = bits == 2 ? 2u : bits == 4 ? 1u : 0u, qbsh = qbits == 2 ? 2u : qbits == 4 ? 1u : 0u;
+	if (ld < (((uint64_t) m + (1u << bsh) - 1u) >> bsh) || qld < (((uint64_t) Q + (1u << qbsh) - 1u) >> qbsh)) return FSEQ_E_ARG;
+	if (n > (1ull << 40) || ld > (1ull << 32) || qld > (1ull << 32) || (uint64_t) S * Q > (1ull << 34) || (uint64_t) S * X > (1ull << 34)) return FSEQ_E_ARG;
+	for (uint32_t s = 0; s < S; ++s)
+	{
+		if (seg_lb[s] >= seg_rb[s] || seg_rb[s] > n || 0 == count[s] || count[s] > X) return FSEQ_E_ARG;
+		for (uint32_t j = 0; j < count[s]; ++j)
+			if (rep[(size_t) s * X + j] >= m) return FSEQ_E_ARG;
+	}
+	GraphNearestPlan P;
+	int what = FSEQ_E_ARG;
+	if (P.build(seg_lb, seg_rb, count, S, qbits, batch_bytes ? batch_bytes : GN_BATCH_BYTES, &what)) return what;
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	size_t const cells = (size_t) S * Q;
+	void *bufs[12] = {};
+	size_t const bytes[12] = {(size_t) (n * ld), (size_t) (n * qld), (size_t) S * 8, (size_t) S * 8, (size_t) S * 4, (size_t) S * X * 4, ((size_t) S + 1) * 4,
+	                          ((size_t) S + 1) * 8, ((size_t) S + 1) * 8, (size_t) P.most_rw * 4, (size_t) P.most_qw * Q * 4, cells * 16};
+	int rc = FSEQ_E_HIP;
+	do
+	{
+		bool ok = true;
+		for (int i = 0; i < 12 && ok; ++i) ok = hipMalloc(&bufs[i], bytes[i]) == hipSuccess;
+		if (!ok) { rc = FSEQ_E_OOM; break; }
+		if (hipMemcpy(bufs[0], cols, bytes[0], hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bufs[1], qcols, bytes[1], hipMemcpyHostToDevice) != hipSuccess ||
+		    hipMemcpy(bufs[2], seg_lb, bytes[2], hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bufs[3], seg_rb, bytes[3], hipMemcpyHostToDevice) != hipSuccess ||
+		    hipMemcpy(bufs[4], count, bytes[4], hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bufs[5], rep, bytes[5], hipMemcpyHostToDevice) != hipSuccess ||
+		    hipMemset(bufs[6], 0, bytes[6]) != hipSuccess ||             // (noff = 0: the nodes come back as class indices)
+		    hipMemcpy(bufs[7], P.qoff.data(), bytes[7], hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bufs[8], P.roff.data(), bytes[8], hipMemcpyHostToDevice) != hipSuccess ||
+		    hipMemset(bufs[11], 0, bytes[11]) != hipSuccess)
+			break;
+		GraphNearestArgs A{};
+		GraphThreadArgs &G = A.G;
+		G.seg_lb = (uint64_t const *) bufs[2]; G.seg_rb = (uint64_t const *) bufs[3]; G.count = (uint32_t const *) bufs[4]; G.rep = (uint32_t const *) bufs[5];
+		G.noff = (uint32_t const *) bufs[6];
+		G.m = m; G.X = X; G.S = S; G.n = n;
+		G.msa = (uint8_t const *) bufs[0]; G.ld = (size_t) ld; G.bsh = bsh;
+		G.q = (uint8_t const *) bufs[1]; G.qld = (size_t) qld; G.qbsh = qbsh; G.Q = Q; G.sigma = sigma;
+		uint32_t *const out = (uint32_t *) bufs[11];
+		A.nodes = out; A.distances = out + cells; A.ties = out + 2 * cells; G.nodes = out + 3 * cells;
+		A.qoff = (uint64_t const *) bufs[7]; A.roff = (uint64_t const *) bufs[8];
+		A.rw = (uint32_t *) bufs[9]; A.qw = (uint32_t *) bufs[10]; A.rw_cap = P.most_rw; A.qw_cap = P.most_qw * Q;
+		A.max_distance = 0;
+		graph_nearest_launch(nullptr, A, P);
+		if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+		if (hipMemcpy(nodes, A.nodes, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(distances, A.distances, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+		    hipMemcpy(ties, A.ties, cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
+			break;
+		if (info) *info = fseq_graph_nearest_info{P.batches, P.roff[S], P.qoff[S], qbits, 0u};
+		rc = FSEQ_OK;
+	} while (false);
+	for (void *p : bufs) (void) hipFree(p);
+	return rc;
 }
 
 } // extern "C"

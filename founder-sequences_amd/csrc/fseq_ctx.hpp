@@ -144,6 +144,7 @@ struct Tuning {
 	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns (of a restored match: kept columns) a segment's cold walk starts in front of its range (by itself: 16,384)
 	int  match_stage = 0;                // FSEQ_MATCH_STAGE_BYTES: most bytes of a staged chunk of fseq_match_rows_restored's query rows (by itself: 64 MiB; tests: chunks of 64 columns)
 	int  graph_thread_key_bits = 0;      // FSEQ_GRAPH_THREAD_KEY_BITS: bits of a node key of fseq_graph_thread_rows / _held_out (1..64; by itself: 64; tests: a bit or two, so that classes share keys)
+	int  graph_nearest_batch = 0;        // FSEQ_GRAPH_NEAREST_BATCH: most bytes of packed class representatives in a batch of fseq_graph_nearest_rows / _held_out (by itself: 256 MiB; tests: a segment a batch)
 
 	// Every knob once, by name: a flag (set = on), a number (set: at least lo; unset: off) or a string.
 	struct Knob {
@@ -199,6 +200,7 @@ struct Tuning {
 			{"FSEQ_MATCH_OVERLAP", nullptr, &Tuning::match_overlap, 1, 0, nullptr},
 			{"FSEQ_MATCH_STAGE_BYTES", nullptr, &Tuning::match_stage, 64, 0, nullptr},
 			{"FSEQ_GRAPH_THREAD_KEY_BITS", nullptr, &Tuning::graph_thread_key_bits, 1, 0, nullptr},
+			{"FSEQ_GRAPH_NEAREST_BATCH", nullptr, &Tuning::graph_nearest_batch, 1, 0, nullptr},
 		};
 		return table;
 	}
@@ -315,6 +317,7 @@ struct fseq_ctx {
 	struct SegFileStats { bool have = false; uint64_t batches = 0, bytes = 0, longest_line = 0, lines = 0; } segfile;      // the last fseq_write_segments_device or fseq_write_segments_restored (fseq_debug_segments_file)
 	struct GraphFileStats { bool have = false; uint64_t batches[3] = {}, lines[3] = {}, bytes[3] = {}; } graphfile;      // the last fseq_write_block_graph (fseq_debug_graph_file): the S, L and P sections
 	struct GraphThreadStats { bool have = false; fseq_graph_thread_info info{}; } graphthread;      // the last fseq_graph_thread_rows / fseq_graph_thread_held_out (fseq_debug_graph_thread)
+	struct GraphNearestStats { bool have = false; fseq_graph_nearest_info info{}; } graphnearest;      // the last fseq_graph_nearest_rows / fseq_graph_nearest_held_out (fseq_debug_graph_nearest_info)
 	fseq_progress_fn progress_fn = nullptr;
 	void *progress_user = nullptr;
 	hipStream_t stream = nullptr;

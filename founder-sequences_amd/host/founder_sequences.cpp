@@ -88,6 +88,13 @@ char const *const USAGE =
 	"                                     (needs the segmentation only: every joining method; works under --upload-memory and\n"
 	"                                     --list-memory; one GPU only; not together with --remove-identity-columns)\n"
 	"      --output-sequence-graph-threads=PATH  With --match-sequences: the same for the sequences of LIST\n"
+	"      --output-held-out-graph-nearest=PATH  With --hold-out: for the held-out sequences, the nearest node of the founder block graph in\n"
+	"                                     every segment and its distance in mismatched characters, on the device; per sequence the segments\n"
+	"                                     admitted (at most --graph-nearest-max-distance mismatches) and exact, the borders crossed along an\n"
+	"                                     edge and as no input sequence does, the walks and the mismatches (requirements and refusals of\n"
+	"                                     --output-held-out-graph-threads; not for --remove-identity-columns or --gpus > 1)\n"
+	"      --output-sequence-graph-nearest=PATH  With --match-sequences: the same for the sequences of LIST\n"
+	"      --graph-nearest-max-distance=D ... the mismatches a segment may have and still be admitted to a walk  (default=`0')\n"
 	"      --output-restored-graph=PATH   With --remove-identity-columns: the block graph in the input's co-ordinates -- the same L and P\n"
 	"                                     lines, every S line's substring with its identity columns back, from the first sequence, and\n"
 	"                                     lb / rb counting the input's columns (honours --graph-paths and --graph-gap-character; works\n"
@@ -417,6 +424,58 @@ bool write_graph_threads(fseq_ctx *ctx, char const *list, size_t n_held, size_t 
 	return ok;
 }
 
+// --output-held-out-graph-nearest (list == nullptr) and --output-sequence-graph-nearest: fseq_graph_nearest_held_out /
+// fseq_graph_nearest_rows, statistics only.  Tab-separated: a header, one line per sequence, a last line '#' with the summary.
+bool write_graph_nearest(fseq_ctx *ctx, char const *list, size_t n_held, size_t seq_length, uint32_t max_distance, char const *path)
+{
+	std::vector<std::string> queries;
+	std::vector<uint8_t const *> qrows;
+	size_t count = 0;
+	if (list)
+	{
+		std::cerr << "Looking for the nearest nodes of the block graph for the sequences of '" << list << "'…" << std::endl;
+		if (!read_list_file(list, queries)) return false;
+		if (queries.empty() || queries.size() > 0xFFFFFFFFull) { std::cerr << "No sequences to thread in '" << list << "'." << std::endl; return false; }
+		qrows.resize(queries.size());
+		for (size_t i = 0; i < queries.size(); ++i)
+		{
+			if (queries[i].size() != seq_length) { std::cerr << "The sequences to thread must have the length of the input's (" << seq_length << ")." << std::endl; return false; }
+			qrows[i] = reinterpret_cast<uint8_t const *>(queries[i].data());
+		}
+		count = queries.size();
+	}
+	else
+	{
+		std::cerr << "Looking for the nearest nodes of the block graph for the held-out sequences…" << std::endl;
+		count = n_held;
+	}
+	std::vector<fseq_graph_nearest_row> per_row(count);
+	fseq_graph_nearest_summary sm{};
+	int const rc(list ? fseq_graph_nearest_rows(ctx, qrows.data(), (uint32_t) count, max_distance, nullptr, nullptr, nullptr, nullptr, per_row.data(), nullptr, &sm)
+	                  : fseq_graph_nearest_held_out(ctx, max_distance, nullptr, nullptr, nullptr, nullptr, per_row.data(), nullptr, &sm));
+	if (FSEQ_OK != rc) { std::cerr << fseq_last_error(ctx) << std::endl; return false; }
+	FILE *f = (path && strcmp(path, "-") != 0) ? fopen(path, "wb") : stdout;
+	if (!f) { std::cerr << "Unable to open the graph nearest output file." << std::endl; return false; }
+	fputs("SEQUENCE_INDEX\tSEGMENTS\tADMITTED\tEXACT\tLINKED\tNOVEL\tWALKS\tLONGEST_WALK\tLONGEST_WALK_COLUMNS\tADMITTED_COLUMNS\tMISMATCHES_ADMITTED\tMISMATCHES\tMAX_DISTANCE\n", f);
+	for (size_t q = 0; q < count; ++q)
+	{
+		fseq_graph_nearest_row const &r = per_row[q];
+		fprintf(f, "%zu\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%llu\t%llu\t%llu\t%llu\t%u\n", q, (unsigned long long) sm.segments, r.segments_admitted, r.segments_exact,
+		        r.junctions_linked, r.junctions_novel, r.walks, r.longest_walk_segments, (unsigned long long) r.longest_walk_columns,
+		        (unsigned long long) r.columns_admitted, (unsigned long long) r.mismatches_admitted, (unsigned long long) r.mismatches, r.max_distance);
+	}
+	fprintf(f, "#\tMAX_DISTANCE_ALLOWED=%u\tROWS=%llu\tSEGMENTS=%llu\tSEGMENTS_ADMITTED=%llu\tSEGMENTS_EXACT=%llu\tJUNCTIONS_LINKED=%llu\tJUNCTIONS_NOVEL=%llu\tWALKS=%llu\t"
+	        "ROWS_ON_GRAPH=%llu\tMISMATCHES=%llu\n", max_distance, (unsigned long long) sm.rows, (unsigned long long) sm.segments, (unsigned long long) sm.segments_admitted,
+	        (unsigned long long) sm.segments_exact, (unsigned long long) sm.junctions_linked, (unsigned long long) sm.junctions_novel, (unsigned long long) sm.walks,
+	        (unsigned long long) sm.rows_on_graph, (unsigned long long) sm.mismatches);
+	bool ok = !ferror(f) && 0 == fflush(f);
+	if (f != stdout && 0 != fclose(f)) ok = false;
+	if (!ok) std::cerr << "Writing the graph nearest output file failed." << std::endl;
+	else std::cerr << "Nearest nodes of " << sm.rows << " sequences: " << sm.segments_exact << " of " << sm.rows * sm.segments << " segments exact, " << sm.mismatches << " mismatches, "
+	               << sm.rows_on_graph << " sequences on the graph at " << max_distance << " mismatches a segment." << std::endl;
+	return ok;
+}
+
 // --hold-out=LIST: a comma list of 0-based sequence indices and of LO:HI ranges, both ends included, in the order given.  false,
 // with the reason in why, where LIST is malformed or names an index twice (whether the indices are below the sequence count is
 // the caller's check, once the input is read)
@@ -463,6 +522,9 @@ int main(int argc, char **argv)
 	char const *match_seqs = nullptr, *out_seq_matches = nullptr, *out_join_score = nullptr;
 	char const *out_graph = nullptr, *graph_gap = nullptr;
 	char const *out_held_threads = nullptr, *out_seq_threads = nullptr;
+	char const *out_held_nearest = nullptr, *out_seq_nearest = nullptr;
+	unsigned long long nearest_max_distance = 0;
+	bool nearest_max_distance_bad = false;
 	char const *out_restored_graph = nullptr, *out_held_restored_threads = nullptr, *out_seq_restored_threads = nullptr;
 	bool graph_paths = false;
 	bool remove_identity = false;
@@ -503,6 +565,8 @@ int main(int argc, char **argv)
 		{"output-graph", required_argument, nullptr, 1023}, {"graph-paths", no_argument, nullptr, 1024},
 		{"graph-gap-character", required_argument, nullptr, 1025},
 		{"output-held-out-graph-threads", required_argument, nullptr, 1026}, {"output-sequence-graph-threads", required_argument, nullptr, 1027},
+		{"output-held-out-graph-nearest", required_argument, nullptr, 1040}, {"output-sequence-graph-nearest", required_argument, nullptr, 1041},
+		{"graph-nearest-max-distance", required_argument, nullptr, 1042},
 		{"output-restored-graph", required_argument, nullptr, 1028},
 		{"output-held-out-restored-graph-threads", required_argument, nullptr, 1029}, {"output-sequence-restored-graph-threads", required_argument, nullptr, 1030},
 		{nullptr, 0, nullptr, 0}};
@@ -560,6 +624,16 @@ int main(int argc, char **argv)
 			case 1025: graph_gap = optarg; break;
 			case 1026: out_held_threads = optarg; break;
 			case 1027: out_seq_threads = optarg; break;
+			case 1040: out_held_nearest = optarg; break;
+			case 1041: out_seq_nearest = optarg; break;
+			case 1042:
+			{
+				char *end = nullptr;
+				errno = 0;
+				nearest_max_distance = strtoull(optarg, &end, 10);
+				nearest_max_distance_bad = !isdigit((unsigned char) optarg[0]) || *end != '\0' || errno == ERANGE || nearest_max_distance > 0xFFFFFFFFull;
+				break;
+			}
 			case 1028: out_restored_graph = optarg; break;
 			case 1029: out_held_restored_threads = optarg; break;
 			case 1030: out_seq_restored_threads = optarg; break;
@@ -647,7 +721,16 @@ int main(int argc, char **argv)
 		if (!((k ? match_seqs : hold_out_spec) && remove_identity)) { std::cerr << name << " requires " << (k ? "--match-sequences" : "--hold-out") << " and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
 		if (gpus > 1) { std::cerr << name << " is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
 	}
-	if (match_seqs && !out_seq_matches && !out_seq_restored && !out_seq_threads && !out_seq_restored_threads) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
+	if (nearest_max_distance_bad) { std::cerr << "--graph-nearest-max-distance must be a number from 0 to 4294967295." << std::endl; return EXIT_FAILURE; }
+	for (int k = 0; k < 2; ++k)
+	{
+		char const *const name = k ? "--output-sequence-graph-nearest" : "--output-held-out-graph-nearest";
+		if (!(k ? out_seq_nearest : out_held_nearest)) continue;
+		if (!(k ? match_seqs : hold_out_spec)) { std::cerr << name << " requires " << (k ? "--match-sequences." : "--hold-out.") << std::endl; return EXIT_FAILURE; }
+		if (gpus > 1) { std::cerr << name << " is not supported together with --gpus > 1 (a rank holds its own columns and boundary states only)." << std::endl; return EXIT_FAILURE; }
+		if (remove_identity) { std::cerr << name << " is not supported together with --remove-identity-columns (the sequences would be compared in reduced co-ordinates)." << std::endl; return EXIT_FAILURE; }
+	}
+	if (match_seqs && !out_seq_matches && !out_seq_restored && !out_seq_threads && !out_seq_restored_threads && !out_seq_nearest) { std::cerr << "--match-sequences requires --output-sequence-matches." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_matches && !match_seqs) { std::cerr << "--output-sequence-matches requires --match-sequences." << std::endl; return EXIT_FAILURE; }
 	if (match_seqs && gpus > 1) { std::cerr << "--match-sequences is not supported together with --gpus > 1 (a rank holds its own columns only)." << std::endl; return EXIT_FAILURE; }
 	if (out_seq_restored && !(match_seqs && remove_identity)) { std::cerr << "--output-sequence-restored-matches requires --match-sequences and --remove-identity-columns." << std::endl; return EXIT_FAILURE; }
@@ -957,6 +1040,11 @@ int main(int argc, char **argv)
 			std::cerr << (out_held_threads ? "--output-held-out-graph-threads" : "--output-sequence-graph-threads") << " needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
 			return EXIT_FAILURE;
 		}
+		if (out_held_nearest || out_seq_nearest)
+		{
+			std::cerr << (out_held_nearest ? "--output-held-out-graph-nearest" : "--output-sequence-graph-nearest") << " needs the segments of a segmentation; the sequences are shorter than two segments." << std::endl;
+			return EXIT_FAILURE;
+		}
 		if (out_restored_matches)
 		{
 			std::cerr << "--output-restored-matches needs the permutations of a segmentation; the columns in which the sequences differ are fewer than two segments." << std::endl;
@@ -994,6 +1082,8 @@ int main(int argc, char **argv)
 	// sequences that took no part in the segmentation through its graph, from the context alone (no join)
 	if (out_held_threads && !write_graph_threads(ctx, nullptr, held_rows.size(), seq_length, out_held_threads)) return EXIT_FAILURE;
 	if (out_seq_threads && !write_graph_threads(ctx, match_seqs, 0, seq_length, out_seq_threads)) return EXIT_FAILURE;
+	if (out_held_nearest && !write_graph_nearest(ctx, nullptr, held_rows.size(), seq_length, (uint32_t) nearest_max_distance, out_held_nearest)) return EXIT_FAILURE;
+	if (out_seq_nearest && !write_graph_nearest(ctx, match_seqs, 0, seq_length, (uint32_t) nearest_max_distance, out_seq_nearest)) return EXIT_FAILURE;
 	// ... the full-length ones on a context over the columns in which the input's differ (seq_length is the input's)
 	if (out_held_restored_threads && !write_graph_threads(ctx, nullptr, held_rows.size(), seq_length, out_held_restored_threads, true)) return EXIT_FAILURE;
 	if (out_seq_restored_threads && !write_graph_threads(ctx, match_seqs, 0, seq_length, out_seq_restored_threads, true)) return EXIT_FAILURE;

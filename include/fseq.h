@@ -475,6 +475,51 @@ int  fseq_graph_thread_rows_restored(fseq_ctx *ctx, uint8_t const *const *rows /
                                      fseq_graph_thread_summary *summary);
 int  fseq_graph_thread_held_out_restored(fseq_ctx *ctx, uint32_t *nodes, uint32_t *steps, fseq_graph_thread_row *per_row,
                                          fseq_graph_thread_segment *per_segment, fseq_graph_thread_summary *summary);
+/* ---- the NEAREST node of every segment, and how far it is, for rows threaded through the graph (no counterpart in the reference) ----
+ * The threading above is all or nothing per (row, segment): a query with one private variant in a segment is reported like one
+ * that matches nothing there.  These entries answer how far the row is from the graph, which node it is nearest to, whether that
+ * node is unique, and how the row walks if up to max_distance mismatches a segment are forgiven.  The context is one
+ * fseq_graph_thread_rows accepts: a finished long-path run, unsharded, not identity-reduced, merged segments tiling the columns;
+ * node ids, classes, representative rows and edges are fseq_block_graph's.
+ *   dist(q, s, j)    the number of columns k in [lb_s, rb_s) where the code of query q differs from the code of the
+ *                    representative row of class j of segment s -- by code, as in the threading: a gap is a symbol like any
+ *                    other, a query byte outside the alignment's alphabet differs from every code
+ *   distance[s][q]   min over j of dist(q, s, j)
+ *   nodes[s][q]      noff[s] + the smallest j that attains the minimum (noff[s]: the id of the segment's class 0)
+ *   ties[s][q]       the number of classes of segment s that attain the minimum, at least 1
+ * Every segment has a class, so all three are always defined: none is ever FSEQ_GRAPH_NONE.  Cell (s, q) is ADMITTED iff
+ * distance[s][q] <= max_distance, and EXACT iff the distance is 0.  steps[p][q] is the index into fseq_block_graph's edges of the
+ * edge (nodes[p][q], nodes[p + 1][q]) if both cells are admitted and the edge exists, FSEQ_GRAPH_NONE otherwise.  Novel junction,
+ * walk and on-the-graph are the threading's with "matched" read as "admitted".  With max_distance = 0, nodes where the distance
+ * is 0 (FSEQ_GRAPH_NONE elsewhere), steps and every walk statistic equal fseq_graph_thread_rows' entry for entry.
+ * Per row: the admitted cells' columns, the most columns and the most segments of a walk, the sum of the distances over the
+ * admitted cells and over all cells, the admitted and the exact cells, the linked and the novel junctions, the walks and the
+ * row's largest distance.  Per segment: the sum of the distances over the queries, the queries admitted and exact in it, those
+ * linked and novel at the junction behind it (0 for the last), and the largest distance.  The summary adds up the rows'; its
+ * ms_device is measured as the threading's.  nodes, distances and ties are [S][n_rows], steps [S - 1][n_rows]; every output
+ * pointer may be NULL, and with the four arrays NULL only statistics leave the device.
+ * The rows form uploads its queries as fseq_graph_thread_rows does (the narrowest of 2 / 4 / 8 bits that leaves the code `sigma`
+ * free); the held-out form reads the held-out rows where they lie.  The class representatives of a batch of whole segments and
+ * the queries are packed into row-major words at the queries' width, every segment on a word boundary, and compared 32 / width
+ * codes an operation (csrc/fseq_graphnearest.hpp); a batch holds at most FSEQ_GRAPH_NEAREST_BATCH bytes (by itself 256 MiB) of
+ * representative words, a segment above that is a batch of its own (fseq_debug_graph_nearest_info, fseq_debug.h).  Everything
+ * is a temporary of the call: the run's results, the last match and fseq_debug_graph_thread's record stay as they were.
+ * Refuses, each with fseq_last_error set, nothing written and nothing left behind: what fseq_graph_thread_rows / _held_out
+ * refuse, but for the 4,096 classes a segment (there is no table in LDS here: the limits are fseq_block_graph's), and
+ * FSEQ_E_UNSUPPORTED a segment of 2^32 - 1 columns or more (distances are 32-bit).  Out of scope: identity-reduced contexts
+ * (source co-ordinates with exception cells), sharded contexts and a host form.  Detected by symbol; FSEQ_ABI_VERSION stays 5. */
+typedef struct { uint64_t columns_admitted, longest_walk_columns, mismatches_admitted, mismatches;
+                 uint32_t segments_admitted, segments_exact, junctions_linked, junctions_novel, walks, longest_walk_segments,
+                          max_distance, reserved; } fseq_graph_nearest_row;                 /* 64 bytes */
+typedef struct { uint64_t mismatches; uint32_t admitted, exact, linked, novel, max_distance, reserved; } fseq_graph_nearest_segment;   /* 32 bytes */
+typedef struct { uint64_t rows, segments, segments_admitted, segments_exact, junctions_linked, junctions_novel, walks, rows_on_graph,
+                          mismatches; double ms_device; } fseq_graph_nearest_summary;
+int  fseq_graph_nearest_rows(fseq_ctx *ctx, uint8_t const *const *rows, uint32_t n_rows, uint32_t max_distance,
+                             uint32_t *nodes /* [S][n_rows] */, uint32_t *distances /* [S][n_rows] */, uint32_t *ties /* [S][n_rows] */,
+                             uint32_t *steps /* [S-1][n_rows] */, fseq_graph_nearest_row *per_row /* [n_rows] */,
+                             fseq_graph_nearest_segment *per_segment /* [S] */, fseq_graph_nearest_summary *summary);
+int  fseq_graph_nearest_held_out(fseq_ctx *ctx, uint32_t max_distance, uint32_t *nodes, uint32_t *distances, uint32_t *ties, uint32_t *steps,
+                                 fseq_graph_nearest_row *per_row, fseq_graph_nearest_segment *per_segment, fseq_graph_nearest_summary *summary);
 /* replaces: join_context::output_in_permutation_order (join_context.cc:333-356): max_segment_size
  * lines; line r = concatenation over segments of rows[permutations[s][r]][lb_s, rb_s).  rows = the
  * raw input sequences.  path NULL or "-" = stdout. */

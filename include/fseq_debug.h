@@ -176,6 +176,38 @@ typedef struct fseq_graph_thread_info {
 } fseq_graph_thread_info;
 int  fseq_debug_graph_thread(fseq_ctx *ctx, fseq_graph_thread_info *info);
 
+/* The last fseq_graph_nearest_rows / fseq_graph_nearest_held_out that finished on this context: the batches of whole segments
+ * its class representatives were packed in, the representatives' packed words over all batches, the packed words of ONE query,
+ * and the bits of a packed code (the queries' width).  FSEQ_GRAPH_NEAREST_BATCH=bytes sets the most representative words a
+ * batch holds (by itself 256 MiB; a segment above it is a batch of its own; fseq_debug_set_tuning takes it at any time: nothing
+ * of a run depends on it, and the results never do).  FSEQ_E_ARG while no call has finished. */
+typedef struct fseq_graph_nearest_info {
+	uint64_t batches, packed_words, query_words;
+	uint32_t bits, reserved;
+} fseq_graph_nearest_info;
+int  fseq_debug_graph_nearest_info(fseq_ctx *ctx, fseq_graph_nearest_info *info);
+/* The batch cut alone (graph_nearest_words and graph_nearest_plan, csrc/fseq_graphnearest_plan.hpp; no device, no context):
+ * n_segments segments [lb[s], rb[s]) of count[s] classes at `bits` bits a code.  words[s] (n_segments + 1 entries) is the sum of
+ * count * ceil(columns / (32 / bits)) over the segments in front of s; batch b is the segments [first[b], first[b + 1]), of
+ * first's n_segments + 1 entries *n_batches + 1 are written.  FSEQ_E_ARG, with nothing written, for a NULL array, no segments,
+ * bits not 2, 4 or 8, a budget of 0 bytes, an empty or backward segment and a segment without a class; FSEQ_E_UNSUPPORTED for a
+ * segment of 2^32 - 1 columns or more. */
+int  fseq_debug_graph_nearest_plan(uint64_t const *lb, uint64_t const *rb, uint32_t const *count, uint64_t n_segments, uint32_t bits,
+                                   uint64_t budget_bytes, uint64_t *words, uint64_t *first, uint64_t *n_batches);
+/* The pack and distance kernels through the production launcher on caller-supplied tables (debug / tests; needs no context).
+ * cols: an alignment of m rows and n columns, column-major and packed at `bits` bits a code, ld bytes a column (pack_columns);
+ * qcols: n_queries queries the same way at qbits, qld bytes a column.  n_segments segments [seg_lb[s], seg_rb[s]) with count[s]
+ * classes whose representative rows are rep[s][0 .. count[s]) (rep is [n_segments][X]): the caller's, so duplicate or equidistant
+ * representatives can be planted.  nodes (as CLASS indices), distances and ties are [n_segments][n_queries]; info as
+ * fseq_debug_graph_nearest_info's; batch_bytes 0: the budget by itself.  Refuses with FSEQ_E_ARG, before a device is touched,
+ * whatever a kernel could form an index from: a NULL array, m, n, n_segments, X or n_queries = 0, rep >= m, count = 0 or > X,
+ * bounds outside n or out of order, bits / qbits not in {2, 4, 8}, qbits < bits, ld or qld too short for the rows. */
+int  fseq_debug_graph_nearest(int device, uint8_t const *cols, uint64_t ld, uint32_t m, uint64_t n, uint32_t bits,
+                              uint64_t const *seg_lb, uint64_t const *seg_rb, uint32_t const *count, uint32_t const *rep,
+                              uint32_t n_segments, uint32_t X, uint8_t const *qcols, uint64_t qld, uint32_t n_queries, uint32_t qbits,
+                              uint32_t sigma, uint64_t batch_bytes, uint32_t *nodes, uint32_t *distances, uint32_t *ties,
+                              fseq_graph_nearest_info *info);
+
 /* One launch of pass 2's chain step on streamed rows (k_chain_snap_grouped, csrc/fseq_chainsort.hpp) on caller-supplied states
  * (debug / tests; needs no context).  nblocks boundary states a0 / d0 [nblocks][m] with the block-key rank of every row,
  * rank[nblocks][m] < cap; ntasks tasks, task t one step from the state of block task_blk[t], the key of a row cls[t][rank[row]],
