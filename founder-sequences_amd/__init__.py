@@ -186,7 +186,7 @@ EXPORTS = [
     "fseq_identity_columns", "fseq_create_without_identity_columns", "fseq_get_identity_columns", "fseq_write_identity_columns", "fseq_write_founders_restored", "fseq_match_founders_restored",
     "fseq_input_begin", "fseq_input_chunk_columns", "fseq_input_scan", "fseq_input_columns", "fseq_input_end", "fseq_set_rows_streamed", "fseq_debug_device_bytes", "fseq_debug_packed_columns",
     "fseq_debug_join_path", "fseq_debug_pass2_paths", "fseq_debug_class_columns", "fseq_debug_bipartite_path",
-    "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
+    "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_chain_launch_wg", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
     "fseq_write_segments_device", "fseq_random_join_classes_host", "fseq_debug_segments_file", "fseq_debug_random_path",
     "fseq_set_segment_length", "fseq_scan_segment_lengths", "fseq_debug_scan_plan", "fseq_debug_relump_lists",
     "fseq_match_rows", "fseq_debug_match_split",
@@ -206,7 +206,7 @@ EXPORTS = [
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
                  "fseq_debug_list_windows", "fseq_debug_device_bytes", "fseq_debug_packed_columns", "fseq_debug_join_path", "fseq_debug_pass2_paths",
-                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
+                 "fseq_debug_class_columns", "fseq_debug_bipartite_path", "fseq_debug_pass2_step", "fseq_debug_chain_launch", "fseq_debug_chain_launch_wg", "fseq_debug_red_plan", "fseq_debug_column_sources", "fseq_debug_red_cls_direct",
                  "fseq_debug_segments_file", "fseq_debug_random_path", "fseq_debug_scan_plan", "fseq_debug_relump_lists", "fseq_debug_match_split",
                  "fseq_debug_held_out_columns", "fseq_debug_row_split_plan", "fseq_debug_dp_lists_check", "fseq_debug_dp_on_lists",
                  "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
@@ -216,6 +216,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
+CW_RUN_CAP = 16384      # ... and FSEQ_CHAIN_RUN_CAP (chain_launch_wg)
 STAGE_TRACEBACK, STAGE_MERGE, STAGE_SAMPLES = 0, 1, 2
 # fseq_progress_fn (include/fseq.h): (user, stage, current_step, step_max)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64)
@@ -326,6 +327,7 @@ def load_library():
     L.fseq_debug_red_cls_direct.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)]
     L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+    L.fseq_debug_chain_launch_wg.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.fseq_debug_red_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.c_int] + [vp] * 11
     L.fseq_write_segments_device.argtypes = [vp, C.c_int, C.c_char_p]
     L.fseq_random_join_classes_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, vp]
@@ -458,7 +460,8 @@ def pass2_step(a0, d0, rank, task_blk, cls, headd, ncls, run_cap=P2_RUN_CAP, wor
     return snap_a, snap_d, stats
 
 
-def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0):
+def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0,
+                 _wg=None):
     """One chain launch of phase B on streamed rows (k_cm_*) on constructed key blocks rank / keyd [nb_total][m], nkeys[nb_total]:
     the chains first_chain .. first_chain + chains - 1 (default: all behind first_chain) of G blocks, from start_a / start_d
     [chains][m] (None: the identity).  Returns a dict with state_a / state_d [nb_total + 1][m] where states, rank / keyd
@@ -488,12 +491,31 @@ def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=Non
         out["keyd"] = np.zeros((chains, m), dtype=np.uint32)
         out["nkeys"] = np.zeros(chains, dtype=np.uint32)
     ptr = lambda name: out[name].ctypes.data if name in out else None
-    rc = L.fseq_debug_chain_launch(device, m, nb_total, G, cols_per_block, rank.ctypes.data, keyd.ctypes.data, nkeys.ctypes.data, first_chain, chains,
-                                   None if start_a is None else start_a.ctypes.data, None if start_a is None else start_d.ctypes.data,
-                                   ptr("state_a"), ptr("state_d"), ptr("rank"), ptr("keyd"), ptr("nkeys"))
+    head = (device, m, nb_total, G, cols_per_block, rank.ctypes.data, keyd.ctypes.data, nkeys.ctypes.data, first_chain, chains,
+            None if start_a is None else start_a.ctypes.data, None if start_a is None else start_d.ctypes.data)
+    tail = (ptr("state_a"), ptr("state_d"), ptr("rank"), ptr("keyd"), ptr("nkeys"))
+    if _wg is None:
+        rc = L.fseq_debug_chain_launch(*head, *tail)
+    else:
+        stats = np.zeros(CW_STATS, dtype=np.uint32)
+        rc = L.fseq_debug_chain_launch_wg(*head, _wg[0], _wg[1], *tail, stats.ctypes.data)
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
+    if _wg is not None:
+        out["stats"] = stats
     return out
+
+
+CW_STATS = 23          # csrc/fseq_types.hpp: by runs, by sort, from the identity, the most runs, 19 words of the run counts' histogram
+
+
+def chain_launch_wg(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0,
+                    run_cap=CW_RUN_CAP, workgroups=1):
+    """The launch of chain_launch with a chain per workgroup (k_chain_wg): `workgroups` workgroups take the chains by a fixed stride;
+    a step goes from the identity, by runs of equal key (at most run_cap of them) or by the sort of its rows.  Returns chain_launch's
+    dict plus "stats", the kernel's CW_STATS counters."""
+    return chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=first_chain, chains=chains, start_a=start_a, start_d=start_d, states=states,
+                        keys=keys, device=device, _wg=(run_cap, workgroups))
 
 
 RED_NONE = 0xFFFFFFFF                       # csrc/fseq_redplan.hpp: a block that is not reduced

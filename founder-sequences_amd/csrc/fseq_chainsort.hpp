@@ -146,8 +146,10 @@ __device__ __forceinline__ void pass2_digits(uint32_t D, uint32_t &npass, uint32
 
 // The stable LSD radix sort of cnt items by key_of(item), npass passes of db bits.  Item i of the first pass is load0(i); the last
 // pass lands in bufB (pass p writes bufB where npass - p is odd, else bufA, and reads the other).  Ends with a barrier.
-template <typename PairT, typename Load0, typename KeyOf>
-__device__ __forceinline__ void pass2_sort(uint32_t cnt, uint32_t npass, uint32_t db, Load0 load0, KeyOf key_of, PairT none, PairT *bufA, PairT *bufB, Pass2Lds &S)
+// (Lds: Pass2Lds, or the chain kernel's ChainWgLds -- scan, hist and total)
+// (U: groups of 64 a wave keeps in flight in a sweep)
+template <typename PairT, uint32_t U = 4, typename Load0, typename KeyOf, typename Lds>
+__device__ __forceinline__ void pass2_sort(uint32_t cnt, uint32_t npass, uint32_t db, Load0 load0, KeyOf key_of, PairT none, PairT *bufA, PairT *bufB, Lds &S)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -166,7 +168,6 @@ __device__ __forceinline__ void pass2_sort(uint32_t cnt, uint32_t npass, uint32_
 		auto load = [&](uint32_t i) -> PairT { return first ? load0(i) : src[i]; };
 		for (uint32_t b = lane; b < nbins; b += 64u) S.hist[wave][b] = 0;
 		// (a wave's histogram row is its own: no barrier between clearing and counting; LDS operations of a wave stay in order)
-		constexpr uint32_t U = 4;
 		for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * U)
 		{
 			PairT pr[U];
@@ -405,38 +406,23 @@ __device__ __forceinline__ bool pass2_runs(
 	return true;
 }
 
-// One task by the sort of all its rows: (a0, d0) -> (a1, d1), keys S.cls[r[i]], D classes with divergences kd[class].  Ends with a barrier.
+// The new order from the sorted pairs perm[p] = (key, old position) and the records of (a0, d0): position p takes the row of its
+// record; the first of a key takes kd[key], any other the maximum of d0(lo .. hi] = max(suffix max at lo, the blocks between, prefix
+// max at hi), or a scan of at most 63 values where lo and hi share a 64-block.  The positions of a wave are consecutive: the record
+// of p - 1 is the lane below.  P4: a pair is ONE word, key << pb | position.  Ends with a barrier.
 template <bool P4>
-__device__ __forceinline__ void pass2_step(
-	uint32_t m, uint32_t const *__restrict__ kd, uint32_t D, Pass2Ws const &W, Pass2Lds &S,
+__device__ __forceinline__ void pass2_place(
+	uint32_t m, uint32_t const *__restrict__ kd, std::conditional_t<P4, uint32_t, uint2> const *perm, uint4 const *rec, uint32_t const *tab,
 	uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
-	// P4: a pair is ONE word, key << pb | position (the caller has checked that the bits fit)
 	using PairT = std::conditional_t<P4, uint32_t, uint2>;
 	uint32_t pb = 1;
 	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
 	uint32_t const pmask = pb < 32u ? (1u << pb) - 1u : 0xFFFFFFFFu;
-	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
 	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
 	auto pos_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr & pmask; else return pr.y; };
-	uint16_t const *__restrict__ r = W.r;
-	uint4 const *const rec = W.rec;
-	uint32_t const *const tab = W.tab;
 	uint32_t const nblk = (m + 63u) / 64u;
-
-	// ---- 1. the sort: the pairs are made on the way from r and the class table in LDS
-	uint32_t npass, db;
-	pass2_digits(D, npass, db);
-	pass2_sort<PairT>(m, npass, db, [&](uint32_t i) -> PairT { return mk((uint32_t) S.cls[r[i]], i); }, key_of, mk(0u, 0u),
-	                  reinterpret_cast<PairT *>(W.bufA), reinterpret_cast<PairT *>(W.bufB), S);
-	PairT const *perm = reinterpret_cast<PairT const *>(W.bufB);
-
-	// ---- 2. (the records: pass2_records, once for the block)
-
-	// ---- 3. the new order: position p takes the row of its record; the first of a class takes the class's divergence, any
-	// other the maximum of d0(lo .. hi] = max(suffix max at lo, the blocks between, prefix max at hi), or a scan of at most 63
-	// values where lo and hi share a 64-block.  The positions of a wave are consecutive: the record of p - 1 is the lane below.
 	{
 		constexpr uint32_t U = 4;
 		for (uint32_t p0 = tid; p0 < m; p0 += ST * U)
@@ -510,6 +496,30 @@ __device__ __forceinline__ void pass2_step(
 		}
 	}
 	__syncthreads();
+}
+
+// One task by the sort of all its rows: (a0, d0) -> (a1, d1), keys S.cls[r[i]], D classes with divergences kd[class].  Ends with a barrier.
+template <bool P4>
+__device__ __forceinline__ void pass2_step(
+	uint32_t m, uint32_t const *__restrict__ kd, uint32_t D, Pass2Ws const &W, Pass2Lds &S,
+	uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+{
+	// P4: a pair is ONE word, key << pb | position (the caller has checked that the bits fit)
+	using PairT = std::conditional_t<P4, uint32_t, uint2>;
+	uint32_t pb = 1;
+	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
+	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
+	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
+	uint16_t const *__restrict__ r = W.r;
+
+	// ---- 1. the sort: the pairs are made on the way from r and the class table in LDS
+	uint32_t npass, db;
+	pass2_digits(D, npass, db);
+	pass2_sort<PairT>(m, npass, db, [&](uint32_t i) -> PairT { return mk((uint32_t) S.cls[r[i]], i); }, key_of, mk(0u, 0u),
+	                  reinterpret_cast<PairT *>(W.bufA), reinterpret_cast<PairT *>(W.bufB), S);
+	// ---- 2. (the records: pass2_records, once for the block)
+	// ---- 3. the new order
+	pass2_place<P4>(m, kd, reinterpret_cast<PairT const *>(W.bufB), W.rec, W.tab, d0, a1, d1);
 }
 
 // stats (P2_STATS words, fseq_types.hpp): tasks on the run path, tasks on the radix path, border copies, the most runs a task had
@@ -964,7 +974,463 @@ __global__ __launch_bounds__(ST) void k_cm_emit(ChainMultiArgs const A, uint32_t
 	uint32_t const *w = A.ws + (size_t) chain * chainsort_ws_words(m);
 	uint32_t const *a = w + (size_t) cur * 2u * m, *d = a + m;
 	uint32_t const kstart = (uint32_t) ((uint64_t) b0 * A.cols_per_block);
-	stream_emit_ranks(m, a, d, kstart, A.out_rank + (size_t) grp * m, A.out_keyd + (size_t) grp * m, A.out_nkeys + grp, L);
+	stream_emit_ranks(m, a, d, kstart, A.out_rank + (size_t) grp * m, A.out_keyd + (size_t) grp * m, A.out_nkeys + grp, L.red);
+}
+
+// ================================================================================================
+// [r14] A wide level's chains on ONE workgroup each.  Where a launch has a chain per CU and more (level 0 of phase B's
+// recursion: BASELINE C4, 256 chains of 24 blocks) the chip is full without spreading a step over it, and a workgroup that
+// owns its chain can do what the spread kernels cannot without chip-wide hand-overs: look at the step's data and move RUNS.
+// The order in front of a block is a pBWT order, so behind the chain's first step the rows of one key lie in a few runs of
+// consecutive positions (C4: ~8,000 runs of ~12 rows a step, but for the block with a recombination point of the founders).
+// k_chain_wg walks a chain's steps in one launch, chains taken by a fixed stride, and decides per step on device data:
+//   * from the identity (the first step of a chain without a start state): a0[i] = i, d0 = kstart -- the rows are sorted by
+//     rank[i] itself, the first row of a key takes keyd[key], every other kstart: no gather through a0, no range maxima;
+//   * by runs, where a key and a position share a word and the step has at most run_cap runs: the keys rank[a0[i]] are gathered
+//     once; one descriptor per run {key << pb | start, run index}, the run's start and -- in the sweep that reads d0 -- its
+//     maximum of d0; the descriptors sorted by key (pass2_sort), prefix sums of their lengths, the new order written run by run:
+//     inside a run a' and d' are copies of consecutive old positions, a head takes keyd[key] or max(d0[its own position], the
+//     maxima of the whole runs between the previous run of its key and itself) -- a range maximum over RUN indices: prefix /
+//     suffix maxima inside blocks of 64 runs and a sparse table over the blocks (a few hundred KB of the workspace);
+//   * by sorting the rows otherwise: pass 2's radix step (pass2_records, pass2_sort, pass2_place) on the gathered keys.
+// An expansion writes a step's output once, into out_state, and the next step reads it there; a composition ping-pongs in the
+// workspace and emits the chain's composite key block itself.
+// ================================================================================================
+// One workgroup of ST = 1,024 threads a CU: the step's code (pass 2's, for ST threads) takes up to 128 registers a thread without
+// scratch, which is what sixteen waves a CU leave each of them; two such workgroups a CU would have to live in 64 (180 registers
+// spilled, profiles/r14_kernel_resource_usage.txt).  The one workgroup has the CU's 160 KiB of LDS to itself: 16,384 runs take 128 KiB.
+constexpr uint32_t CW_RUN_CAP = 16384;           // most runs of a step on the run path (off + dlt: 8 bytes a run)
+constexpr uint32_t CW_RBLK = CW_RUN_CAP / 64;    // blocks of 64 runs
+constexpr uint32_t CW_RLEVELS = 9;               // sparse table over at most 2^8 blocks of runs: levels 0 .. 8
+static_assert(CW_RUN_CAP % 64u == 0u && CW_RBLK <= (1u << (CW_RLEVELS - 1u)), "the table over the blocks of runs");
+
+struct ChainWgLds {
+	uint32_t scan[ST / WAVE + 1];
+	union {
+		struct {
+			uint32_t hist[ST / WAVE][CS_BINS];   // per wave: digit counts, then the wave's write offsets
+			uint32_t total[CS_BINS];
+		};
+		struct {                                 // the run path's output sweep
+			uint32_t off[CW_RUN_CAP + 1];        // first new position of the run, runs by (key, start); m behind the last
+			uint32_t dlt[CW_RUN_CAP];            // its first old position less its first new one (modulo 2^32)
+		};
+	};
+};
+static_assert(sizeof(ChainWgLds) + 16u <= 160u * 1024u, "a workgroup a CU");
+
+__host__ __device__ inline size_t chainwg_lds_bytes() { return carve_bytes(1, sizeof(ChainWgLds)); }
+
+// workspace words of one workgroup, every part 16-byte aligned: records (4 words a row) | pairs B | pairs A (2 words a row each) |
+// the state, twice (a, d) | keys | the table over the 64-blocks of d0 | the runs: start, maximum, prefix and suffix maxima, the heads'
+// divergences, table
+__host__ __device__ inline size_t chainwg_ws_rows(uint32_t m) { return ((size_t) m + 3) & ~size_t(3); }
+__host__ __device__ inline size_t chainwg_ws_tab(uint32_t m) { return (CS_LEVELS * (((size_t) m + 63) / 64) + 64 + 3) & ~size_t(3); }
+__host__ __device__ inline size_t chainwg_ws_words(uint32_t m)
+{
+	return 13 * chainwg_ws_rows(m) + chainwg_ws_tab(m) + 5 * (size_t) (CW_RUN_CAP + 64) + (size_t) CW_RLEVELS * CW_RBLK;
+}
+struct ChainWgWs {
+	uint4 *rec;
+	uint32_t *bufB, *bufA, *state, *keys, *tab;       // state: a, d, a, d of chainwg_ws_rows(m) words each
+	uint32_t *rstart, *rmax, *rpre, *rsuf, *rhead, *rtab;
+};
+__device__ __forceinline__ ChainWgWs chainwg_ws(uint32_t *w, uint32_t m)
+{
+	size_t const M = chainwg_ws_rows(m);
+	ChainWgWs W;
+	W.rec = reinterpret_cast<uint4 *>(w);
+	W.bufB = w + 4 * M; W.bufA = w + 6 * M;
+	W.state = w + 8 * M;
+	W.keys = w + 12 * M;
+	W.tab = w + 13 * M;
+	W.rstart = W.tab + chainwg_ws_tab(m);
+	W.rmax = W.rstart + (CW_RUN_CAP + 64); W.rpre = W.rmax + (CW_RUN_CAP + 64); W.rsuf = W.rpre + (CW_RUN_CAP + 64);
+	W.rhead = W.rsuf + (CW_RUN_CAP + 64);
+	W.rtab = W.rhead + (CW_RUN_CAP + 64);
+	return W;
+}
+
+// a run's maximum: the word the sweep's atomics built in L2 (a load that does not stop at the CU's vector cache, which may still
+// hold the word's line from the step before)
+__device__ __forceinline__ uint32_t chainwg_rmax(uint32_t const *rmax, uint32_t k)
+{
+	return __hip_atomic_load(rmax + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// max of rmax[lo .. hi] (run indices, lo <= hi < R)
+__device__ __forceinline__ uint32_t chainwg_run_max(uint32_t lo, uint32_t hi, uint32_t R, ChainWgWs const &W)
+{
+	uint32_t const bl = lo >> 6, bh = hi >> 6;
+	if (bl == bh)
+	{
+		if ((lo & 63u) == 0u) return W.rpre[hi];
+		if ((hi & 63u) == 63u || hi + 1u == R) return W.rsuf[lo];
+		uint32_t v = 0;
+		for (uint32_t k = lo; k <= hi; ++k) v = max(v, chainwg_rmax(W.rmax, k));
+		return v;
+	}
+	uint32_t v = max(W.rsuf[lo], W.rpre[hi]);
+	if (bh > bl + 1u)
+	{
+		uint32_t const k = 31u - (uint32_t) __builtin_clz(bh - bl - 1u);
+		uint32_t const *t = W.rtab + (size_t) k * CW_RBLK;
+		v = max(v, max(t[bl + 1u], t[bh - (1u << k)]));
+	}
+	return v;
+}
+
+
+// A workgroup's sweeps go to memory (the workspaces of a chip's worth of workgroups are far beyond the caches), sixteen waves a
+// CU: what a step takes is the round trips of its sweeps, so the kernel's own sweeps keep CW_U groups of 64 positions in flight a wave
+constexpr uint32_t CW_U = 8;
+
+// The keys of the old positions, W.keys[i] = rk[a0[i]], and the runs they form, counted on the way: position i starts a run where
+// its key is not the key at i - 1.  A wave sweeps its chunk in order (the key in front of a group of 64: the last lane of the group
+// before; in front of the chunk: looked up).  *R: the runs of the step; returns the runs in front of this wave's chunk.  Ends with
+// a barrier.
+__device__ __forceinline__ uint32_t chainwg_keys(uint32_t m, uint32_t const *__restrict__ rk, uint32_t const *a0, ChainWgWs const &W, ChainWgLds &S, uint32_t *R)
+{
+	uint32_t const tid = threadIdx.x, lane = lane_id();
+	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	constexpr uint32_t NW = ST / WAVE;
+	uint32_t const per = ((m + NW - 1u) / NW + 63u) & ~63u;
+	uint32_t const c_lo = min(m, wave * per), c_hi = min(m, c_lo + per);
+	uint32_t prev = 0xFFFFFFFFu;                                          // (no key: position 0 starts a run)
+	if (c_lo > 0u && c_lo < c_hi) prev = rk[a0[c_lo - 1u]];
+	uint32_t k0 = 0;
+	for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * CW_U)
+	{
+		uint32_t av[CW_U], kv[CW_U];
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u) { uint32_t const i = i0 + u * 64u + lane; av[u] = i < c_hi ? a0[i] : 0u; }
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u) { uint32_t const i = i0 + u * 64u + lane; kv[u] = i < c_hi ? rk[av[u]] : 0u; }
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u)
+		{
+			uint32_t const i = i0 + u * 64u + lane;
+			if (i0 + u * 64u >= c_hi) break;
+			bool const in = i < c_hi;
+			if (in) W.keys[i] = kv[u];
+			uint32_t const up = shfl_up_u32(kv[u], 1);
+			k0 += (uint32_t) __popcll(__ballot(in && kv[u] != (lane ? up : prev)));
+			prev = readlane_u32(kv[u], 63);                               // (a group that is not whole is the chunk's last)
+		}
+	}
+	uint32_t const before = block_excl_add<ST>(lane == 0u ? k0 : 0u, S.scan, R);
+	__syncthreads();                                                      // (the keys are whole)
+	return __builtin_amdgcn_readfirstlane(before);
+}
+
+// One step by runs: (a0, d0) -> (a1, d1), the keys of the old positions in W.keys (chainwg_keys: they form R <= CW_RUN_CAP runs, wbase of
+// them in front of this wave's chunk), nk keys with divergences kd[key]; the caller has checked that a key and a position share a
+// word.  Ends with a barrier.
+__device__ __forceinline__ void chainwg_runs(
+	uint32_t m, uint32_t const *__restrict__ kd, uint32_t nk, ChainWgWs const &W, ChainWgLds &S, uint32_t R, uint32_t wbase,
+	uint32_t const *a0, uint32_t const *d0, uint32_t *a1, uint32_t *d1)
+{
+	uint32_t const tid = threadIdx.x, lane = lane_id();
+	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	constexpr uint32_t NW = ST / WAVE;
+	uint32_t const *keys = W.keys;
+	uint32_t pb = 1;
+	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
+	uint32_t const pmask = (1u << pb) - 1u;                               // (pb < 32: a key shares the word)
+	uint32_t const per = ((m + NW - 1u) / NW + 63u) & ~63u;
+	uint32_t const c_lo = min(m, wave * per), c_hi = min(m, c_lo + per);
+	uint32_t npass, db;
+	pass2_digits(nk, npass, db);
+	uint2 *const bufA = reinterpret_cast<uint2 *>(W.bufA), *const bufB = reinterpret_cast<uint2 *>(W.bufB);
+	uint2 *const pos_order = (npass & 1u) ? bufA : bufB;                  // (the buffer the first pass of the sort does not write)
+
+	// ---- a. one descriptor per run, {key << pb | start, run}, in position order, the runs' starts, and the runs' maxima of d0: a
+	// scan inside the group of 64 that does not cross a start, the last lane of every piece to the run's word
+	for (uint32_t k = tid; k < R; k += ST) W.rmax[k] = 0u;
+	__syncthreads();
+	{
+		uint32_t prev = 0xFFFFFFFFu;
+		if (c_lo > 0u && c_lo < c_hi) prev = keys[c_lo - 1u];
+		uint32_t k0 = wbase;
+		for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * CW_U)
+		{
+			uint32_t kv[CW_U], dv[CW_U];
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u)
+			{
+				uint32_t const i = i0 + u * 64u + lane;
+				kv[u] = i < c_hi ? keys[i] : 0u;
+				dv[u] = i < c_hi ? d0[i] : 0u;
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u)
+			{
+				uint32_t const i = i0 + u * 64u + lane;
+				if (i0 + u * 64u >= c_hi) break;
+				bool const in = i < c_hi;
+				uint32_t const up = shfl_up_u32(kv[u], 1);
+				bool const head = in && kv[u] != (lane ? up : prev);
+				uint64_t const heads = __ballot(head);
+				// the run of this lane: starts counted up to and including it, less one (a group that does not begin with a
+				// start continues run k0 - 1: position 0 is a start, so k0 >= 1 there)
+				uint32_t const k = k0 + cs_below(heads) + (head ? 1u : 0u) - 1u;
+				if (head) { pos_order[k] = make_uint2((kv[u] << pb) | i, k); W.rstart[k] = i; }
+				// the lane this lane's piece of its run starts at: the highest start at or below it, else lane 0
+				uint64_t const upto = heads & (lane == 63u ? ~0ull : ((2ull << lane) - 1ull));
+				uint32_t const s0 = upto ? 63u - (uint32_t) __builtin_clzll(upto) : 0u;
+				uint32_t v = dv[u];
+#pragma unroll
+				for (uint32_t o = 1; o < 64u; o <<= 1)
+				{
+					uint32_t const t = shfl_up_u32(v, (int) o);
+					if (lane >= s0 + o) v = max(v, t);
+				}
+				uint64_t const ins = __ballot(in);
+				bool const last = in && (lane == 63u || !((ins >> (lane + 1u)) & 1ull) || ((heads >> (lane + 1u)) & 1ull));
+				if (last) atomicMax(&W.rmax[k], v);
+				k0 += (uint32_t) __popcll(heads);
+				prev = readlane_u32(kv[u], 63);
+			}
+		}
+	}
+	if (tid == 0u) W.rstart[R] = m;
+	__syncthreads();
+
+	// ---- b. prefix and suffix maxima of the runs' maxima inside blocks of 64 runs, a sparse table over the blocks
+	uint32_t const nrb = (R + 63u) / 64u;
+	for (uint32_t blk = wave; blk < nrb; blk += NW)
+	{
+		uint32_t const k = blk * 64u + lane;
+		uint32_t const v = k < R ? chainwg_rmax(W.rmax, k) : 0u;
+		uint32_t const pre = wave_incl_max(v);
+		uint32_t const rev = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((63u - lane) << 2), (int) v);
+		uint32_t const sufr = wave_incl_max(rev);
+		uint32_t const suf = (uint32_t) __builtin_amdgcn_ds_bpermute((int) ((63u - lane) << 2), (int) sufr);
+		if (k < R) { W.rpre[k] = pre; W.rsuf[k] = suf; }
+		if (lane == 63u) W.rtab[blk] = pre;
+	}
+	__syncthreads();
+	for (uint32_t k = 1; k < CW_RLEVELS && (1u << k) <= nrb; ++k)
+	{
+		uint32_t const *lo = W.rtab + (size_t) (k - 1u) * CW_RBLK;
+		uint32_t *hi = W.rtab + (size_t) k * CW_RBLK;
+		for (uint32_t j = tid; j + (1u << k) <= nrb; j += ST) hi[j] = max(lo[j], lo[j + (1u << (k - 1u))]);
+		__syncthreads();
+	}
+
+	// ---- c. the runs by (key, start): a stable sort by key of descriptors that are in start order
+	pass2_sort<uint2>(R, npass, db, [&](uint32_t i) -> uint2 { return pos_order[i]; }, [&](uint2 x) -> uint32_t { return x.x >> pb; },
+	                  make_uint2(0u, 0u), bufA, bufB, S);
+	// their first new positions: the prefix sum of their lengths (a thread takes consecutive runs, all its loads at once)
+	{
+		constexpr uint32_t Q = CW_RUN_CAP / ST;
+		static_assert(Q * ST == CW_RUN_CAP, "a thread's runs");
+		uint32_t const q = (R + ST - 1u) / ST, j0 = min(R, tid * q), j1 = min(R, j0 + q);
+		uint32_t st[Q], len[Q];
+#pragma unroll
+		for (uint32_t t = 0; t < Q; ++t)
+		{
+			uint2 const x = j0 + t < j1 ? bufB[j0 + t] : make_uint2(0u, 0u);
+			st[t] = x.x & pmask; len[t] = x.y;
+		}
+#pragma unroll
+		for (uint32_t t = 0; t < Q; ++t) len[t] = j0 + t < j1 ? W.rstart[len[t] + 1u] - st[t] : 0u;
+		uint32_t sum = 0;
+#pragma unroll
+		for (uint32_t t = 0; t < Q; ++t) sum += len[t];
+		uint32_t all;
+		uint32_t at = block_excl_add<ST>(sum, S.scan, &all);
+		// (the sort's last barrier is behind every use of the histograms, which these arrays lie over)
+#pragma unroll
+		for (uint32_t t = 0; t < Q; ++t)
+			if (j0 + t < j1) { S.off[j0 + t] = at; S.dlt[j0 + t] = st[t] - at; at += len[t]; }
+		if (tid == 0u) S.off[R] = m;
+	}
+
+	// ---- d. the divergence of every run's head: the key's where the run is the key's first, else the maximum of its own d0 and of
+	// the whole runs between the run before it (same key) and itself
+	{
+		constexpr uint32_t UH = 4;
+		for (uint32_t j0 = tid; j0 < R; j0 += ST * UH)
+		{
+			uint2 me[UH], pv[UH];
+			uint32_t hv[UH];
+#pragma unroll
+			for (uint32_t u = 0; u < UH; ++u)
+			{
+				uint32_t const j = min(j0 + u * ST, R - 1u);
+				me[u] = bufB[j]; pv[u] = bufB[j ? j - 1u : 0u];
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < UH; ++u)
+			{
+				uint32_t const j = j0 + u * ST;
+				hv[u] = 0u;
+				if (j >= R) continue;
+				if (j == 0u || (pv[u].x >> pb) != (me[u].x >> pb)) hv[u] = kd[me[u].x >> pb];
+				else
+				{
+					hv[u] = d0[me[u].x & pmask];
+					uint32_t const k_lo = pv[u].y + 1u, k_me = me[u].y;          // (k_lo < k_me: neighbouring runs differ in key)
+					if (k_lo < k_me) hv[u] = max(hv[u], chainwg_run_max(k_lo, k_me - 1u, R, W));
+				}
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < UH; ++u) { uint32_t const j = j0 + u * ST; if (j < R) W.rhead[j] = hv[u]; }
+		}
+	}
+	__syncthreads();
+
+	// ---- e. the new order: position p lies in the run j with off[j] <= p < off[j + 1] and takes the row at old position
+	// p + dlt[j]; behind the run's head its divergence too, the head the one of d.
+	uint32_t top = 1;
+	while (top * 2u < R) top *= 2u;
+	for (uint32_t p0 = tid; p0 < m; p0 += ST * CW_U)
+	{
+		uint32_t jh[CW_U], hh[CW_U], av[CW_U], dv[CW_U];
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u)
+		{
+			uint32_t const p = min(p0 + u * ST, m - 1u);
+			uint32_t j = 0;
+			for (uint32_t step = top; step; step >>= 1) { uint32_t const t = j + step; if (t < R && S.off[t] <= p) j = t; }
+			hh[u] = p + S.dlt[j];
+			jh[u] = S.off[j] == p ? j : 0xFFFFFFFFu;
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u) { av[u] = a0[hh[u]]; dv[u] = jh[u] != 0xFFFFFFFFu ? W.rhead[jh[u]] : d0[hh[u]]; }
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u)
+		{
+			uint32_t const p = p0 + u * ST;
+			if (p < m) { a1[p] = av[u]; d1[p] = dv[u]; }
+		}
+	}
+	__syncthreads();
+}
+
+// One step by the sort of all its rows: the keys from W.keys (ident: from rk itself -- the order is the identity, every divergence
+// kstart, and neither records nor range maxima are needed).  Ends with a barrier.
+template <bool P4>
+__device__ __forceinline__ void chainwg_sort(
+	uint32_t m, uint32_t const *__restrict__ rk, uint32_t const *__restrict__ kd, uint32_t nk, ChainWgWs const &W, ChainWgLds &S, bool ident, uint32_t kstart,
+	uint32_t const *a0, uint32_t const *d0, uint32_t *a1, uint32_t *d1)
+{
+	using PairT = std::conditional_t<P4, uint32_t, uint2>;
+	uint32_t pb = 1;
+	while (pb < 32u && ((m - 1u) >> pb) != 0u) ++pb;
+	uint32_t const pmask = pb < 32u ? (1u << pb) - 1u : 0xFFFFFFFFu;
+	auto mk = [&](uint32_t key, uint32_t pos) -> PairT { if constexpr (P4) return (key << pb) | pos; else return make_uint2(key, pos); };
+	auto key_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr >> pb; else return pr.x; };
+	auto pos_of = [&](PairT pr) -> uint32_t { if constexpr (P4) return pr & pmask; else return pr.y; };
+	uint32_t npass, db;
+	pass2_digits(nk, npass, db);
+	PairT *const bufA = reinterpret_cast<PairT *>(W.bufA), *const bufB = reinterpret_cast<PairT *>(W.bufB);
+	if (ident)
+	{
+		pass2_sort<PairT, CW_U>(m, npass, db, [&](uint32_t i) -> PairT { return mk(rk[i], i); }, key_of, mk(0u, 0u), bufA, bufB, S);
+		for (uint32_t p0 = threadIdx.x; p0 < m; p0 += ST * CW_U)
+		{
+			PairT me[CW_U], pv[CW_U];
+			uint32_t dv[CW_U];
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u) { uint32_t const p = min(p0 + u * ST, m - 1u); me[u] = bufB[p]; pv[u] = bufB[p ? p - 1u : 0u]; }
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u)
+			{
+				uint32_t const p = p0 + u * ST;
+				dv[u] = (p < m && (p == 0u || key_of(pv[u]) != key_of(me[u]))) ? kd[key_of(me[u])] : kstart;
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u) { uint32_t const p = p0 + u * ST; if (p < m) { a1[p] = pos_of(me[u]); d1[p] = dv[u]; } }
+		}
+		__syncthreads();
+		return;
+	}
+	uint32_t const *keys = W.keys;
+	pass2_records(m, a0, d0, W.rec, W.tab);
+	pass2_sort<PairT, CW_U>(m, npass, db, [&](uint32_t i) -> PairT { return mk(keys[i], i); }, key_of, mk(0u, 0u), bufA, bufB, S);
+	pass2_place<P4>(m, kd, bufB, W.rec, W.tab, d0, a1, d1);
+}
+
+// stats (CW_STATS words, fseq_types.hpp; nullptr: none kept): steps by runs, steps by the sort of the rows, steps from the identity,
+// the most runs a step had (of the steps that may go by runs: the knob is not 0, a key and a position share a word), those steps
+// by the power of two their run count reaches
+__global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_t *ws, uint32_t run_cap, uint32_t *stats)
+{
+	extern __shared__ __attribute__((aligned(16))) char smem[];
+	ChainWgLds &S = *reinterpret_cast<ChainWgLds *>(smem);
+	uint32_t const tid = threadIdx.x, m = A.m;
+	ChainWgWs const W = chainwg_ws(ws + (size_t) blockIdx.x * chainwg_ws_words(m), m);
+	uint32_t pbits = 1;
+	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
+	for (uint32_t chain = blockIdx.x; chain < A.nchains; chain += gridDim.x)
+	{
+		uint32_t const grp = chain + A.grp0;
+		uint32_t const b0 = grp * A.G;
+		if (b0 >= A.nb_total) continue;
+		uint32_t const b1 = min(A.nb_total, b0 + A.G);
+		uint32_t const kstart = (uint32_t) ((uint64_t) b0 * A.cols_per_block);
+		// the state in front of the chain: the caller's, or the identity (never stored unless out_state asks for it)
+		bool ident = A.start_a == nullptr;
+		uint32_t const *a0 = ident ? nullptr : A.start_a + (size_t) grp * m, *d0 = ident ? nullptr : A.start_d + (size_t) grp * m;
+		if (A.out_state_a)
+			for (uint32_t i = tid; i < m; i += ST)
+			{
+				A.out_state_a[(size_t) b0 * m + i] = ident ? i : a0[i];
+				A.out_state_d[(size_t) b0 * m + i] = ident ? kstart : d0[i];
+			}
+		uint32_t pp = 0;
+		for (uint32_t b = b0; b < b1; ++b)
+		{
+			// (an expansion -- states wanted, no composite keys -- does not step through a chain's last block unless that is the last
+			// of all: the state behind it is the next chain's start state, chainmulti_geom)
+			bool const keep = b + 1u < b1 || b + 1u == A.nb_total;
+			if (!A.out_rank && !keep) break;
+			uint32_t *a1, *d1;
+			if (A.out_state_a && keep) { a1 = A.out_state_a + (size_t) (b + 1u) * m; d1 = A.out_state_d + (size_t) (b + 1u) * m; }
+			else { a1 = W.state + (size_t) pp * 2u * chainwg_ws_rows(m); d1 = a1 + chainwg_ws_rows(m); pp ^= 1u; }
+			uint32_t const *rk = A.rank + (size_t) b * m, *kd = A.keyd + (size_t) b * m;
+			uint32_t const nk = A.nkeys[b];
+			uint32_t kb = 1;
+			while (kb < 32u && ((nk - 1u) >> kb) != 0u) ++kb;
+			bool const p4 = kb + pbits <= 32u;
+			uint32_t nrun = 0;
+			bool by_runs = false;
+			if (!ident)
+			{
+				// the keys in the order in front of the block, once for the step, and their runs
+				uint32_t R = 0;
+				uint32_t const wbase = chainwg_keys(m, rk, a0, W, S, &R);
+				bool const may = run_cap != 0u && p4;
+				nrun = may ? R : 0u;
+				by_runs = may && R <= run_cap;
+				if (by_runs) chainwg_runs(m, kd, nk, W, S, R, wbase, a0, d0, a1, d1);
+			}
+			if (!by_runs)
+			{
+				if (p4) chainwg_sort<true>(m, rk, kd, nk, W, S, ident, kstart, a0, d0, a1, d1);
+				else chainwg_sort<false>(m, rk, kd, nk, W, S, ident, kstart, a0, d0, a1, d1);
+			}
+			if (stats && tid == 0)
+			{
+				atomicAdd(stats + (ident ? 2 : by_runs ? 0 : 1), 1u);
+				if (nrun)
+				{
+					atomicMax(stats + 3, nrun);
+					atomicAdd(stats + 4 + min(P2_HIST - 1u, nrun > 1u ? 32u - (uint32_t) __builtin_clz(nrun - 1u) : 0u), 1u);
+				}
+			}
+			ident = false;
+			a0 = a1; d0 = d1;
+		}
+		// the chain's composite key block (a composition steps through every block: a0 is the order behind the last)
+		if (A.out_rank)
+		{
+			stream_emit_ranks(m, a0, d0, kstart, A.out_rank + (size_t) grp * m, A.out_keyd + (size_t) grp * m, A.out_nkeys + grp, S.scan);
+			__syncthreads();
+		}
+	}
 }
 
 } // namespace fseq

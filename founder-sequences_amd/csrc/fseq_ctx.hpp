@@ -139,6 +139,8 @@ struct Tuning {
 	bool class_gather = false;           // FSEQ_CLASS_GATHER: the class columns are gathered into the reduced alignment for every block (the form before the column kernel staged them itself)
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
+	int  chain_run_cap = -1;             // FSEQ_CHAIN_RUN_CAP: most runs of equal key a step of phase B's chain-per-workgroup kernel moves by runs (0: every step sorts its rows; clamped to CW_RUN_CAP)
+	int  chain_wg = 0;                   // FSEQ_CHAIN_WG: streamed phase B's chains on one workgroup each (k_chain_wg): unset or 0: launches of at least a chain per CU; 1: every launch; 2: none
 	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
 	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: the entries that take query rows choose, those over the alignment's rows walk unsplit)
 	int  match_overlap = 0;              // FSEQ_MATCH_OVERLAP: columns (of a restored match: kept columns) a segment's cold walk starts in front of its range (by itself: 16,384)
@@ -193,6 +195,8 @@ struct Tuning {
 			{"FSEQ_REDUCED_MSA_GATHER", &Tuning::reduced_msa_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
+			{"FSEQ_CHAIN_RUN_CAP", nullptr, &Tuning::chain_run_cap, 0, -1, nullptr},
+			{"FSEQ_CHAIN_WG", nullptr, &Tuning::chain_wg, 0, 0, nullptr},
 			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
 			{"FSEQ_CLASS_GATHER", &Tuning::class_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_SCAN_REBUILD", &Tuning::scan_rebuild, nullptr, 0, 0, nullptr},
@@ -379,6 +383,9 @@ struct fseq_ctx {
 	DevBuf<uint32_t> d_rank, d_keyd, d_nkeys;
 	DevBuf<uint32_t> d_bstate_a, d_bstate_d;
 	DevBuf<uint32_t> d_cshist;               // streamed phase B spread over the chip (fseq_chainsort.hpp): digit histograms [chain][part][bin]
+	int dev_cus = -1;                        // the device's CUs (device_cus: asked once a context)
+	int cw_resident = 0;                     // workgroups of k_chain_wg a CU holds at once (prepare_stream_kernels)
+	DevBuf<uint32_t> d_cw_stats;             // FSEQ_DEBUG: the counters of phase B's chain-per-workgroup kernel (CW_STATS words; empty otherwise: the kernel keeps none)
 	DevBuf<uint32_t> d_hrank, d_hkeyd, d_hnkeys, d_hstate_a, d_hstate_d;
 	// not sharded: phase B over any number of levels (levels[i - 1] = the composites of chain_fan level-(i - 1) key blocks)
 	struct ChainLevel { uint32_t count = 0; uint64_t cols = 0; DevBuf<uint32_t> rank, keyd, nkeys, state_a, state_d; };
@@ -596,6 +603,13 @@ struct fseq_ctx {
 
 
 namespace fseq {
+
+// the CUs of the context's device (0 where the runtime does not say)
+inline int device_cus(fseq_ctx *c)
+{
+	if (c->dev_cus < 0 && hipDeviceGetAttribute(&c->dev_cus, hipDeviceAttributeMultiprocessorCount, c->p.device) != hipSuccess) c->dev_cus = 0;
+	return c->dev_cus;
+}
 
 inline int fail(fseq_ctx *c, int code, char const *what, hipError_t e = hipSuccess)
 {

@@ -102,12 +102,56 @@ void launch_chain_stream(hipStream_t st, uint32_t grid, ChainMultiArgs A)
 	if (A.out_rank) hipLaunchKernelGGL(k_cm_emit, dim3(grid), dim3(ST), stream_lds_bytes(0, false), st, A, A.G);
 }
 
+// the same launch with a chain per workgroup (k_chain_wg, fseq_chainsort.hpp): `wgs` workgroups with a workspace of
+// chainwg_ws_words(m) words each take the `grid` chains by a fixed stride; A as for launch_chain_stream (ws and hist are not used);
+// stats: CW_STATS device words the kernel adds to, or nullptr
+void launch_chain_wg(hipStream_t st, uint32_t grid, uint32_t wgs, ChainMultiArgs A, uint32_t *ws, uint32_t run_cap, uint32_t *stats)
+{
+	A.step = 0; A.pass = 0;
+	A.nchains = grid;
+	hipLaunchKernelGGL(k_chain_wg, dim3(wgs), dim3(ST), chainwg_lds_bytes(), st, A, ws, run_cap, stats);
+}
+
+// FSEQ_CHAIN_RUN_CAP: the most runs of equal key a step of k_chain_wg may form and still be moved by runs (0: every step sorts
+// its rows; unset: what the kernel's LDS holds)
+uint32_t chain_run_cap(fseq_ctx const *c)
+{
+	return c->tune.chain_run_cap < 0 ? CW_RUN_CAP : std::min<uint32_t>((uint32_t) c->tune.chain_run_cap, CW_RUN_CAP);
+}
+
+// How many workgroups of k_chain_wg a launch of `grid` chains gets; 0: the launch takes the spread kernels.  The rule: at least
+// a chain per CU.  Below that the spread kernels fill the chip and a chain per workgroup does not (the upper levels of the
+// recursion, the top chain, a sharded rank's 64 chains, BASELINE C4cols50k and C4slice at round 5's fan, which they keep:
+// block_geometry); from there on every CU has a chain of
+// its own, a step costs no launch, and the kernel moves runs.  FSEQ_CHAIN_WG: 1 every streamed launch, 2 none.
+uint32_t chain_wg_groups(fseq_ctx *c, uint32_t grid)
+{
+	if (c->tune.chain_wg >= 2) return 0;
+	int const ncu = std::max(device_cus(c), 1);
+	if (c->tune.chain_wg != 1 && grid < (uint32_t) ncu) return 0;
+	// as many as are resident at once (one a CU: its LDS) and as the workspace holds.  d_ws is a workspace of 9 m + B + 16 words per
+	// block, a launch by the rule has CUs x fan blocks below it and fan >= 2: it holds a workgroup a CU (13 m + 90,000 words each)
+	// from 18,000 rows on, and below that the launch takes fewer workgroups and more turns; only a forced launch on a few blocks
+	// can find room for none, and takes the spread kernels
+	size_t const fit = c->d_ws.cap / chainwg_ws_words(c->p.m);
+	return (uint32_t) std::min<size_t>(std::min<size_t>(grid, fit), (size_t) ncu * (size_t) std::max(c->cw_resident, 1));
+}
+
 // one chain launch of phase B (A: the level's key blocks, the start states, what comes out -- ChainMultiArgs); the launch
 // adds the rows and, streamed rows, its workspace
 void launch_chain(fseq_ctx *c, uint32_t grid, ChainMultiArgs A)
 {
 	if (!grid) return;
 	A.m = c->p.m;
+	if (c->use_stream)
+		if (uint32_t const wgs = chain_wg_groups(c, grid))
+		{
+			if (c->tune.debug)
+				fprintf(stderr, "[fseq] phase B: %u chains of %u blocks on %u workgroups of their own (%zu bytes of LDS, at most %u runs)\n", grid, A.G, wgs,
+				        chainwg_lds_bytes(), chain_run_cap(c));
+			launch_chain_wg(c->stream, grid, wgs, A, c->d_ws.base, chain_run_cap(c), c->d_cw_stats.base);
+			return;
+		}
 	// streamed rows: ensure_work_buffers sized d_ws and d_cshist for the widest launch of phase B (a chain per chain_fan blocks,
 	// plus one, in d_cshist; chainsort_ws_words(m) <= 8.25 m + 80 words <= the 9 m + B + 16 of every block's workspace)
 	if (c->use_stream)
@@ -131,6 +175,8 @@ int prepare_stream_kernels(fseq_ctx *c, size_t lds)
 	HIP_TRY(c, allow_lds(k_columns_stream<0>, lds));
 	HIP_TRY(c, allow_lds(k_chain_snap_grouped, pass2_lds_bytes()));
 	HIP_TRY(c, allow_lds(k_cm_emit, stream_lds_bytes(0, false)));
+	HIP_TRY(c, allow_lds(k_chain_wg, chainwg_lds_bytes()));
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->cw_resident, k_chain_wg, (int) ST, chainwg_lds_bytes()) != hipSuccess) c->cw_resident = 1;
 	return FSEQ_OK;
 }
 int prepare_stream2_prologue(fseq_ctx *c)
@@ -444,6 +490,13 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		A.out_state_a = sa_of(i); A.out_state_d = sd_of(i);
 		return A;
 	};
+	// FSEQ_DEBUG: the chain-per-workgroup kernel keeps its counters (zeroed here, read and printed below); else it keeps none
+	if (c->use_stream && c->tune.debug && c->tune.chain_wg < 2)
+	{
+		if ((rc = c->d_cw_stats.ensure(c, CW_STATS))) return rc;
+		HIP_TRY(c, hipMemsetAsync(c->d_cw_stats.base, 0, CW_STATS * 4, st));
+	}
+	else if (c->d_cw_stats.base) c->d_cw_stats.release(c);
 	if (!sharded)
 	{
 		// phase B: up the levels -- compose groups of G key blocks of a level into one key block of the next
@@ -510,6 +563,15 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 	FSEQ_RANGE_POP();
 	R.range_ab_open = false;
 	progress(c, FSEQ_STAGE_TRACEBACK, n / 5, n);                  // (phases A and B queued: about a fifth of pass 1)
+	if (c->d_cw_stats.base)
+	{
+		uint32_t s[CW_STATS] = {};
+		HIP_TRY(c, hipMemcpyAsync(s, c->d_cw_stats.base, sizeof(s), hipMemcpyDeviceToHost, st));
+		HIP_TRY(c, hipStreamSynchronize(st));
+		fprintf(stderr, "[fseq] phase B chain steps on a workgroup of their own: %u by runs, %u by the sort of the rows, %u from the identity; most runs %u; by run count (<= 2^b):", s[0], s[1], s[2], s[3]);
+		for (uint32_t b = 0; b < P2_HIST; ++b) fprintf(stderr, " %u", s[4 + b]);
+		fprintf(stderr, "\n");
+	}
 	if (sync_at(c, 'B')) { fprintf(stderr, "[fseq] phase B queued\n"); HIP_TRY(c, hipStreamSynchronize(st)); fprintf(stderr, "[fseq] phase B done\n"); }
 	return FSEQ_OK;
 }
@@ -638,6 +700,80 @@ bool rows_are_permutations(uint32_t const *a, size_t count, uint32_t m)
 	return true;
 }
 
+// one chain launch on constructed key blocks: the spread kernels (workgroups == 0), or k_chain_wg on `workgroups` workgroups
+int debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
+                       uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
+                       uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd,
+                       uint32_t *out_nkeys, uint32_t *stats)
+{
+	// ---- everything an index is formed from, before the first HIP call
+	bool const want_states = out_state_a != nullptr, want_keys = out_rank != nullptr;
+	if (!rank || !keyd || !nkeys || (!want_states && !want_keys)) return FSEQ_E_ARG;
+	if (want_states != (out_state_d != nullptr) || want_keys != (out_keyd != nullptr) || want_keys != (out_nkeys != nullptr)) return FSEQ_E_ARG;
+	if ((start_a != nullptr) != (start_d != nullptr)) return FSEQ_E_ARG;
+	if (m < DEBUG_M_MIN || m > DEBUG_M_MAX || !nb_total || nb_total > 4096u) return FSEQ_E_ARG;
+	if (!G || G > nb_total) return FSEQ_E_ARG;                            // (a chain of more steps than blocks only queues idle launches)
+	uint32_t const nchains_all = (nb_total + G - 1u) / G;
+	if (!chains || first_chain >= nchains_all || chains > nchains_all - first_chain) return FSEQ_E_ARG;
+	for (uint32_t b = 0; b < nb_total; ++b)
+	{
+		if (!nkeys[b] || nkeys[b] > m) return FSEQ_E_ARG;
+		for (uint32_t i = 0; i < m; ++i)
+			if (rank[(size_t) b * m + i] >= nkeys[b]) return FSEQ_E_ARG;
+	}
+	if (start_a && !rows_are_permutations(start_a, chains, m)) return FSEQ_E_ARG;
+
+	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
+	DebugBuffers B;
+	// (the kernels index start states and composite key blocks by the chain's number in the level, first_chain + its number in the launch)
+	size_t const blocks = (size_t) nb_total * m, per_chain = (size_t) (first_chain + chains) * m, at = (size_t) first_chain * m;
+	ChainMultiArgs A{};
+	A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block; A.grp0 = first_chain;
+	A.rank = B.copy(rank, blocks); A.keyd = B.copy(keyd, blocks); A.nkeys = B.copy(nkeys, nb_total);
+	uint32_t *d_wg_ws = nullptr, *d_stats = nullptr;
+	if (workgroups)
+	{
+		d_wg_ws = B.words((size_t) workgroups * chainwg_ws_words(m), 0); d_stats = B.words(CW_STATS, 0);
+		if (!d_wg_ws || !d_stats) return FSEQ_E_OOM;
+		if (allow_lds(k_chain_wg, chainwg_lds_bytes()) != hipSuccess) return FSEQ_E_HIP;
+	}
+	else
+	{
+		A.ws = B.words((size_t) chains * chainsort_ws_words(m), 0);
+		A.hist = B.words((size_t) chains * chainmulti_parts(m) * CS_BINS, 0);
+		if (!A.ws || !A.hist) return FSEQ_E_OOM;
+	}
+	if (!A.rank || !A.keyd || !A.nkeys) return FSEQ_E_OOM;
+	if (start_a)
+	{
+		A.start_a = B.copy(start_a, (size_t) chains * m, at); A.start_d = B.copy(start_d, (size_t) chains * m, at);
+		if (!A.start_a || !A.start_d) return FSEQ_E_OOM;
+	}
+	if (want_states)
+	{
+		A.out_state_a = B.words(blocks + m, 0xFF); A.out_state_d = B.words(blocks + m, 0xFF);
+		if (!A.out_state_a || !A.out_state_d) return FSEQ_E_OOM;
+	}
+	if (want_keys)
+	{
+		A.out_rank = B.words(per_chain, 0xFF); A.out_keyd = B.words(per_chain, 0xFF); A.out_nkeys = B.words(first_chain + chains, 0xFF);
+		if (!A.out_rank || !A.out_keyd || !A.out_nkeys) return FSEQ_E_OOM;
+		if (allow_lds(k_cm_emit, stream_lds_bytes(0, false)) != hipSuccess) return FSEQ_E_HIP;
+	}
+	if (workgroups) launch_chain_wg(0, chains, workgroups, A, d_wg_ws, run_cap, d_stats);
+	else launch_chain_stream(0, chains, A);
+	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
+	if (workgroups && hipMemcpy(stats, d_stats, CW_STATS * 4, hipMemcpyDeviceToHost) != hipSuccess) return FSEQ_E_HIP;
+	if (want_states && (hipMemcpy(out_state_a, A.out_state_a, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                    || hipMemcpy(out_state_d, A.out_state_d, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
+	if (want_keys && (hipMemcpy(out_rank, A.out_rank + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                  || hipMemcpy(out_keyd, A.out_keyd + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
+	                  || hipMemcpy(out_nkeys, A.out_nkeys + first_chain, (size_t) chains * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
+	return FSEQ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -704,59 +840,18 @@ int fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t 
                             uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
                             uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys)
 {
-	// ---- everything an index is formed from, before the first HIP call
-	bool const want_states = out_state_a != nullptr, want_keys = out_rank != nullptr;
-	if (!rank || !keyd || !nkeys || (!want_states && !want_keys)) return FSEQ_E_ARG;
-	if (want_states != (out_state_d != nullptr) || want_keys != (out_keyd != nullptr) || want_keys != (out_nkeys != nullptr)) return FSEQ_E_ARG;
-	if ((start_a != nullptr) != (start_d != nullptr)) return FSEQ_E_ARG;
-	if (m < DEBUG_M_MIN || m > DEBUG_M_MAX || !nb_total || nb_total > 4096u) return FSEQ_E_ARG;
-	if (!G || G > nb_total) return FSEQ_E_ARG;                            // (a chain of more steps than blocks only queues idle launches)
-	uint32_t const nchains_all = (nb_total + G - 1u) / G;
-	if (!chains || first_chain >= nchains_all || chains > nchains_all - first_chain) return FSEQ_E_ARG;
-	for (uint32_t b = 0; b < nb_total; ++b)
-	{
-		if (!nkeys[b] || nkeys[b] > m) return FSEQ_E_ARG;
-		for (uint32_t i = 0; i < m; ++i)
-			if (rank[(size_t) b * m + i] >= nkeys[b]) return FSEQ_E_ARG;
-	}
-	if (start_a && !rows_are_permutations(start_a, chains, m)) return FSEQ_E_ARG;
+	return debug_chain_launch(device, m, nb_total, G, cols_per_block, rank, keyd, nkeys, first_chain, chains, start_a, start_d, 0, 0,
+	                          out_state_a, out_state_d, out_rank, out_keyd, out_nkeys, nullptr);
+}
 
-	if (hipSetDevice(device) != hipSuccess) return FSEQ_E_HIP;
-	DebugBuffers B;
-	// (the kernels index start states and composite key blocks by the chain's number in the level, first_chain + its number in the launch)
-	size_t const blocks = (size_t) nb_total * m, per_chain = (size_t) (first_chain + chains) * m, at = (size_t) first_chain * m;
-	ChainMultiArgs A{};
-	A.m = m; A.nb_total = nb_total; A.G = G; A.cols_per_block = cols_per_block; A.grp0 = first_chain;
-	A.rank = B.copy(rank, blocks); A.keyd = B.copy(keyd, blocks); A.nkeys = B.copy(nkeys, nb_total);
-	A.ws = B.words((size_t) chains * chainsort_ws_words(m), 0);
-	A.hist = B.words((size_t) chains * chainmulti_parts(m) * CS_BINS, 0);
-	if (!A.rank || !A.keyd || !A.nkeys || !A.ws || !A.hist) return FSEQ_E_OOM;
-	if (start_a)
-	{
-		A.start_a = B.copy(start_a, (size_t) chains * m, at); A.start_d = B.copy(start_d, (size_t) chains * m, at);
-		if (!A.start_a || !A.start_d) return FSEQ_E_OOM;
-	}
-	if (want_states)
-	{
-		A.out_state_a = B.words(blocks + m, 0xFF); A.out_state_d = B.words(blocks + m, 0xFF);
-		if (!A.out_state_a || !A.out_state_d) return FSEQ_E_OOM;
-	}
-	if (want_keys)
-	{
-		A.out_rank = B.words(per_chain, 0xFF); A.out_keyd = B.words(per_chain, 0xFF); A.out_nkeys = B.words(first_chain + chains, 0xFF);
-		if (!A.out_rank || !A.out_keyd || !A.out_nkeys) return FSEQ_E_OOM;
-		if (allow_lds(k_cm_emit, stream_lds_bytes(0, false)) != hipSuccess) return FSEQ_E_HIP;
-	}
-	launch_chain_stream(0, chains, A);
-	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
-	if (want_states && (hipMemcpy(out_state_a, A.out_state_a, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess
-	                    || hipMemcpy(out_state_d, A.out_state_d, (blocks + m) * 4, hipMemcpyDeviceToHost) != hipSuccess))
-		return FSEQ_E_HIP;
-	if (want_keys && (hipMemcpy(out_rank, A.out_rank + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
-	                  || hipMemcpy(out_keyd, A.out_keyd + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
-	                  || hipMemcpy(out_nkeys, A.out_nkeys + first_chain, (size_t) chains * 4, hipMemcpyDeviceToHost) != hipSuccess))
-		return FSEQ_E_HIP;
-	return FSEQ_OK;
+int fseq_debug_chain_launch_wg(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
+                               uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
+                               uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank,
+                               uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t *stats)
+{
+	if (!stats || run_cap > CW_RUN_CAP || !workgroups || workgroups > 1024u) return FSEQ_E_ARG;
+	return debug_chain_launch(device, m, nb_total, G, cols_per_block, rank, keyd, nkeys, first_chain, chains, start_a, start_d, run_cap, workgroups,
+	                          out_state_a, out_state_d, out_rank, out_keyd, out_nkeys, stats);
 }
 
 } // extern "C"

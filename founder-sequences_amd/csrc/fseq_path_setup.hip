@@ -151,20 +151,51 @@ void block_geometry(fseq_ctx *c)
 		KernelSet probe;
 		if (!select_kernels(p.m, c->sigma, &probe) && c->nblocks > 8)
 		{
-			double best = 1e300;
-			for (uint32_t g = 2; g <= 64 && g < c->nblocks; ++g)
-			{
-				double steps = 0, rounds = 0;
+			// cost of fan g by round 5's model; own: level 0 on k_chain_wg instead ([r14], below), `turns` turns of workgroups
+			auto cost_of = [&](uint32_t g, uint64_t turns) {
+				double steps = 0, rounds = 0, own = 0;
 				uint64_t cnt = c->nblocks;
+				bool level0 = true;
 				while (cnt > g)
 				{
-					steps += (double) cnt * (2.0 * g - 1.0) / g;       // up: every item; down: all but the last of every group
-					rounds += 2.0 * g - 1.0;
+					if (level0 && turns) own = (double) turns * ((2.0 * g - 1.0) * 0.5 + 0.4) * ((double) p.m / 1e5);
+					else
+					{
+						steps += (double) cnt * (2.0 * g - 1.0) / g;   // up: every item; down: all but the last of every group
+						rounds += 2.0 * g - 1.0;
+					}
+					level0 = false;
 					cnt = (cnt + g - 1) / g;
 				}
 				steps += (double) cnt; rounds += (double) cnt;           // the top chain
-				double const cost = steps * 3.5e-3 * ((double) p.m / 1e5) + rounds * 0.05;
+				return own + steps * 3.5e-3 * ((double) p.m / 1e5) + rounds * 0.05;
+			};
+			double best = 1e300;
+			for (uint32_t g = 2; g <= 64 && g < c->nblocks; ++g)
+			{
+				double const cost = cost_of(g, 0);
 				if (cost < best) { best = cost; best_g = g; }
+			}
+			// [r14] Where that fan's level 0 has at least a chain per CU, the level goes to k_chain_wg (launch_chain, fseq_path_pass1.hip):
+			// a workgroup a CU walks its chains one after the other, so the level takes ceil(chains / CUs) turns of 2g - 1 steps, and a
+			// fan that leaves the last turn nearly empty pays for it.  Only then, and only among the wider fans that keep level 0 on
+			// that kernel, the turns are counted: a step 0.5 ms at 100,000 rows, a chain's step from the identity 0.4 more (BASELINE
+			// C4, measured: 0.5 ms by runs, 0.8 by the sort of the rows, 0.9 from the identity; the step is bound by the bytes it moves,
+			// which go with the rows).  Measured on C4, phase B: fan 11 (round 5's; 559 chains, 3 turns) 43.0 ms, 12 (512, 2 turns)
+			// 38.0, 24 (256, one turn) 36.8 -- the model's order.  Every other shape keeps round 5's fan: with fewer than 2 x CUs x
+			// fan blocks (C4slice, C4cols50k, a sharded rank) no level reaches the kernel.  FSEQ_CHAIN_WG=1 or 2 (tests): round 5's fan.
+			int const ncu = c->tune.chain_wg == 0 ? device_cus(c) : 0;
+			if (ncu > 0 && ((uint64_t) c->nblocks + best_g - 1) / best_g >= (uint64_t) ncu && c->nblocks > best_g)
+			{
+				uint32_t const g5 = best_g;
+				best = 1e300;
+				for (uint32_t g = g5; g <= 64 && g < c->nblocks; ++g)
+				{
+					uint64_t const chains = ((uint64_t) c->nblocks + g - 1) / g;
+					if (chains < (uint64_t) ncu) break;
+					double const cost = cost_of(g, (chains + ncu - 1) / ncu);
+					if (cost < best) { best = cost; best_g = g; }
+				}
 			}
 		}
 		if (c->nblocks <= 8) best_g = std::max(1u, c->nblocks);        // one chain
@@ -492,7 +523,7 @@ void free_work(fseq_ctx *c)
 	release_levels(c);
 	release_all(c, c->d_ent, c->d_hdr, c->d_flags, c->d_recent, c->d_chunk_r0, c->d_tau, c->d_bk, c->d_bkws, c->d_todo, c->d_colmask, c->d_btws, c->d_only, c->d_tb);
 	release_all(c, c->dp.M, c->dp.LB, c->dp.SZ, c->dp.K, c->dp.Tb, c->dp.Tbv, c->d_Mprev, c->d_spec);
-	release_all(c, c->d_cols, c->d_grp, c->d_src, c->d_ss_a, c->d_ss_d, c->d_bs_w, c->d_bs_h, c->d_wgblk, c->d_wggrp, c->d_snap_a, c->d_snap_d, c->d_ws, c->d_cshist);
+	release_all(c, c->d_cols, c->d_grp, c->d_src, c->d_ss_a, c->d_ss_d, c->d_bs_w, c->d_bs_h, c->d_wgblk, c->d_wggrp, c->d_snap_a, c->d_snap_d, c->d_ws, c->d_cshist, c->d_cw_stats);
 	release_all(c, c->d_red_cnt, c->d_red_cnt_plan, c->d_red_vmin, c->d_red_rows, c->d_red_leaf, c->d_red_a, c->d_red_d, c->d_red_invalid, c->d_red_blocks, c->d_red_msa, c->d_cls, c->d_cls_have, c->d_red_src);
 	release_all(c, c->d_red_ss_a, c->d_red_ss_d, c->d_red_cls, c->d_red_headd, c->d_red_ncls, c->d_red_taskblk, c->d_red_wgtasks, c->d_red_p2grp);
 	// what was planned for the buffers that are gone

@@ -232,9 +232,10 @@ __device__ __forceinline__ void stage_column(uint8_t *sym, uint8_t const *col, u
 }
 
 // rank / keyd / nkeys of the order in (a, d): a row starts a new key iff d > dlow (position 0 always).
+// red: ST / WAVE + 1 words of LDS for the scan
 __device__ __forceinline__ void stream_emit_ranks(
 	uint32_t m, uint32_t const *a, uint32_t const *d, uint32_t dlow, uint32_t *rank_out, uint32_t *keyd_out, uint32_t *nkeys_out,
-	StreamLds &L)
+	uint32_t *red)
 {
 	uint32_t const tid = threadIdx.x;
 	uint32_t running = 0;
@@ -250,7 +251,7 @@ __device__ __forceinline__ void stream_emit_ranks(
 			nf += (pos < m && (pos == 0 || dv[e] > dlow)) ? 1u : 0u;
 		}
 		uint32_t total;
-		uint32_t r = running + block_excl_add<ST>(nf, L.red, &total);
+		uint32_t r = running + block_excl_add<ST>(nf, red, &total);
 #pragma unroll
 		for (int e = 0; e < SE; ++e)
 		{
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(ST, MODE == MODE_SNAP ? 8 : 1) void k_colblock_stre
 	}
 	if (MODE == MODE_RANK)
 		stream_emit_ranks(m, buf[cur][0], buf[cur][1], (uint32_t) k0, rank + (size_t) blockIdx.x * m, keyd + (size_t) blockIdx.x * m,
-		                  nkeys + blockIdx.x, L);
+		                  nkeys + blockIdx.x, L.red);
 }
 
 // ------------------------------------------------------------------------------------------------

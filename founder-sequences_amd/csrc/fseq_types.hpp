@@ -198,6 +198,7 @@ struct ClassColumnArgs {
 // [r5] Phase C on a block's REPRESENTATIVE rows (fseq_reduced.hpp): what k_reduce_prep left for every block and where a
 // workgroup of the reduced column kernel finds it.  Plain pointers into device memory.
 constexpr uint32_t P2_HIST = 19;                 // ... tasks by run count: bucket b counts those with more than 2^(b - 1) and at most 2^b runs (bucket 0: one run)
+constexpr uint32_t CW_STATS = 4 + P2_HIST;       // counters of phase B's chain-per-workgroup kernel (k_chain_wg): steps by runs, by the sort of the rows, from the identity, the most runs, steps by run count
 constexpr uint32_t P2_STATS = 4 + P2_HIST;       // counters of pass 2's streamed chain step (k_chain_snap_grouped; fseq_debug_pass2_paths)
 constexpr uint32_t RED_WIDE = 2u;               // invalid[b]: the block has more distinct start values than its configuration's table holds
 struct RedArgs {

@@ -238,6 +238,18 @@ int  fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t
                              uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
                              uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys);
 
+/* The same launch with a chain per workgroup (k_chain_wg, csrc/fseq_chainsort.hpp: the form phase B takes for launches of at least
+ * a chain per CU): `workgroups` workgroups take the chains by a fixed stride and walk each through its steps -- a step from the
+ * identity, by runs of equal key (at most run_cap of them, and a key and a position in one 32-bit word) or by the sort of its rows.
+ * Arguments, outputs and checks as for fseq_debug_chain_launch, and: run_cap <= 16,384 (0: no step goes by runs),
+ * 1 <= workgroups <= 1,024, and the kernel's counters, stats[23]: steps by runs, steps by the sort of their rows, steps from the
+ * identity, the most runs of a step that counted its runs, 19 words of those steps by run count (bucket b: more than 2^(b - 1) and
+ * at most 2^b runs; bucket 0: one run). */
+int  fseq_debug_chain_launch_wg(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
+                                uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
+                                uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank,
+                                uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t *stats);
+
 /* The plan of phase C on representative rows (plan_reduced, csrc/fseq_redplan.hpp) on caller-supplied counts (debug / tests; touches
  * no device).  The configurations are the library's, judged as a run of m rows in blocks of B columns at `bits` bits a symbol would
  * judge them (direct != 0: LDS-resident rows, which stage the alignment's own columns).  cnt[nblocks]: the representatives of every
