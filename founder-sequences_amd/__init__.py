@@ -202,6 +202,7 @@ EXPORTS = [
     "fseq_graph_thread_rows", "fseq_graph_thread_held_out", "fseq_debug_graph_thread",
     "fseq_graph_nearest_rows", "fseq_graph_nearest_held_out", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
     "fseq_write_block_graph_restored", "fseq_graph_thread_rows_restored", "fseq_graph_thread_held_out_restored",
+    "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -212,7 +213,8 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_merge_on_lists", "fseq_debug_traceback_parts",
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
                  "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass",
-                 "fseq_debug_graph_thread", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest"]
+                 "fseq_debug_graph_thread", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
+                 "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -328,6 +330,8 @@ def load_library():
     L.fseq_debug_pass2_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.fseq_debug_chain_launch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.fseq_debug_chain_launch_wg.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.fseq_debug_chain_launch_wg_keys.argtypes = L.fseq_debug_chain_launch_wg.argtypes + [vp, vp]
+    L.fseq_debug_pass2_step_keys.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.fseq_debug_red_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.c_int] + [vp] * 11
     L.fseq_write_segments_device.argtypes = [vp, C.c_int, C.c_char_p]
     L.fseq_random_join_classes_host.argtypes = [C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, vp]
@@ -434,10 +438,12 @@ P2_STATS = 23          # csrc/fseq_types.hpp: by runs, by sort, copies, the most
 NOT_WRITTEN = 0xFFFFFFFF
 
 
-def pass2_step(a0, d0, rank, task_blk, cls, headd, ncls, run_cap=P2_RUN_CAP, workgroups=1, device=0):
+def pass2_step(a0, d0, rank, task_blk, cls, headd, ncls, run_cap=P2_RUN_CAP, workgroups=1, device=0, hand_keys=None, hand_flag=None):
     """One launch of pass 2's streamed chain step (k_chain_snap_grouped) on constructed states: a0 / d0 / rank [nblocks][m],
     task_blk / ncls [ntasks], cls / headd [ntasks][cap].  Returns (snap_a, snap_d) [ntasks][m] (NOT_WRITTEN where the kernel wrote
-    nothing) and the kernel's P2_STATS counters.  FseqError(FSEQ_E_ARG) where an input could take the kernel out of bounds."""
+    nothing) and the kernel's P2_STATS counters.  FseqError(FSEQ_E_ARG) where an input could take the kernel out of bounds.
+    hand_keys [nblocks][m] (16 bits) and hand_flag [nblocks]: phase B's hand-over (fseq_debug_pass2_step_keys) -- a block with its flag
+    set takes its ranks by position from hand_keys; a fourth value comes back, (groups that took them, groups that gathered)."""
     L = load_library()
     a0 = np.ascontiguousarray(np.atleast_2d(a0), dtype=np.uint32)
     d0 = np.ascontiguousarray(np.atleast_2d(d0), dtype=np.uint32)
@@ -453,15 +459,29 @@ def pass2_step(a0, d0, rank, task_blk, cls, headd, ncls, run_cap=P2_RUN_CAP, wor
     snap_a = np.zeros((ntasks, m), dtype=np.uint32)
     snap_d = np.zeros((ntasks, m), dtype=np.uint32)
     stats = np.zeros(P2_STATS, dtype=np.uint32)
-    rc = L.fseq_debug_pass2_step(device, m, nblocks, a0.ctypes.data, d0.ctypes.data, rank.ctypes.data, cap, ntasks, task_blk.ctypes.data, cls.ctypes.data,
-                                 headd.ctypes.data, ncls.ctypes.data, run_cap, workgroups, snap_a.ctypes.data, snap_d.ctypes.data, stats.ctypes.data)
+    if (hand_keys is None) != (hand_flag is None):
+        raise FseqError(FSEQ_E_ARG, "pass2_step: hand_keys and hand_flag go together")
+    if hand_keys is not None:
+        hand_keys = np.ascontiguousarray(np.atleast_2d(hand_keys), dtype=np.uint16)
+        hand_flag = np.ascontiguousarray(hand_flag, dtype=np.uint32)
+        if hand_keys.shape != a0.shape or hand_flag.shape != (nblocks,):
+            raise FseqError(FSEQ_E_ARG, "pass2_step: hand_keys is [nblocks][m], hand_flag [nblocks]")
+        hand_stats = np.zeros(2, dtype=np.uint32)
+        rc = L.fseq_debug_pass2_step_keys(device, m, nblocks, a0.ctypes.data, d0.ctypes.data, rank.ctypes.data, cap, ntasks, task_blk.ctypes.data,
+                                          cls.ctypes.data, headd.ctypes.data, ncls.ctypes.data, run_cap, workgroups, hand_keys.ctypes.data,
+                                          hand_flag.ctypes.data, snap_a.ctypes.data, snap_d.ctypes.data, stats.ctypes.data, hand_stats.ctypes.data)
+    else:
+        rc = L.fseq_debug_pass2_step(device, m, nblocks, a0.ctypes.data, d0.ctypes.data, rank.ctypes.data, cap, ntasks, task_blk.ctypes.data, cls.ctypes.data,
+                                     headd.ctypes.data, ncls.ctypes.data, run_cap, workgroups, snap_a.ctypes.data, snap_d.ctypes.data, stats.ctypes.data)
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
+    if hand_keys is not None:
+        return snap_a, snap_d, stats, hand_stats
     return snap_a, snap_d, stats
 
 
 def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0,
-                 _wg=None):
+                 _wg=None, _hand=None):
     """One chain launch of phase B on streamed rows (k_cm_*) on constructed key blocks rank / keyd [nb_total][m], nkeys[nb_total]:
     the chains first_chain .. first_chain + chains - 1 (default: all behind first_chain) of G blocks, from start_a / start_d
     [chains][m] (None: the identity).  Returns a dict with state_a / state_d [nb_total + 1][m] where states, rank / keyd
@@ -498,11 +518,18 @@ def chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=Non
         rc = L.fseq_debug_chain_launch(*head, *tail)
     else:
         stats = np.zeros(CW_STATS, dtype=np.uint32)
-        rc = L.fseq_debug_chain_launch_wg(*head, _wg[0], _wg[1], *tail, stats.ctypes.data)
+        if _hand is None:
+            rc = L.fseq_debug_chain_launch_wg(*head, _wg[0], _wg[1], *tail, stats.ctypes.data)
+        else:
+            hand_keys = np.full((nb_total, m), _hand, dtype=np.uint16)
+            hand_flag = np.zeros(nb_total, dtype=np.uint32)
+            rc = L.fseq_debug_chain_launch_wg_keys(*head, _wg[0], _wg[1], *tail, stats.ctypes.data, hand_keys.ctypes.data, hand_flag.ctypes.data)
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     if _wg is not None:
         out["stats"] = stats
+        if _hand is not None:
+            out["hand_keys"], out["hand_flag"] = hand_keys, hand_flag
     return out
 
 
@@ -516,6 +543,18 @@ def chain_launch_wg(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=
     dict plus "stats", the kernel's CW_STATS counters."""
     return chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=first_chain, chains=chains, start_a=start_a, start_d=start_d, states=states,
                         keys=keys, device=device, _wg=(run_cap, workgroups))
+
+
+HAND_FILL = 0xA5C3     # what chain_launch_wg_keys fills the hand-over array with in front of the launch
+
+
+def chain_launch_wg_keys(rank, keyd, nkeys, G, cols_per_block, first_chain=0, chains=None, start_a=None, start_d=None, states=True, keys=False, device=0,
+                         run_cap=CW_RUN_CAP, workgroups=1, fill=HAND_FILL):
+    """chain_launch_wg with the hand-over to pass 2 (fseq_debug_chain_launch_wg_keys): the dict also holds "hand_keys" [nb_total][m]
+    (16 bits, every word `fill` in front of the launch) and "hand_flag" [nb_total].  Where a flag is set, the block's row of hand_keys
+    is rank[b] in the order in front of block b.  Takes m from 65 on."""
+    return chain_launch(rank, keyd, nkeys, G, cols_per_block, first_chain=first_chain, chains=chains, start_a=start_a, start_d=start_d, states=states,
+                        keys=keys, device=device, _wg=(run_cap, workgroups), _hand=fill)
 
 
 RED_NONE = 0xFFFFFFFF                       # csrc/fseq_redplan.hpp: a block that is not reduced

@@ -524,17 +524,20 @@ __device__ __forceinline__ void pass2_step(
 
 // stats (P2_STATS words, fseq_types.hpp): tasks on the run path, tasks on the radix path, border copies, the most runs a task had
 // (of the tasks that counted theirs), those tasks by the power of two their run count reaches (P2_HIST buckets)
+// [r15] hand_keys / hand_flag (or nullptr): phase B's hand-over (ChainMultiArgs) -- a group whose block has its flag set reads the
+// block's r from hand_keys[block][m] and gathers nothing; hand_stats (or nullptr): two words, the groups that took handed-over keys
+// and the groups that did not
 __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 	uint32_t const *__restrict__ bstate_a, uint32_t const *__restrict__ bstate_d, uint32_t const *__restrict__ rank, uint32_t m,
 	uint32_t const *__restrict__ task_blk, uint32_t const *__restrict__ cls, uint32_t const *__restrict__ headd, uint32_t const *__restrict__ ncls,
 	uint32_t cap, uint2 const *__restrict__ grps, uint32_t ngrp, uint32_t *__restrict__ grp_next, uint32_t *__restrict__ snap_a,
-	uint32_t *__restrict__ snap_d, uint32_t *ws, uint32_t run_cap, uint32_t *__restrict__ stats)
+	uint32_t *__restrict__ snap_d, uint32_t *ws, uint32_t run_cap, uint32_t *__restrict__ stats,
+	uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *hand_stats)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	Pass2Lds &S = *reinterpret_cast<Pass2Lds *>(smem);
 	uint32_t const tid = threadIdx.x;
-	Pass2Ws const W = pass2_ws(ws + (size_t) blockIdx.x * pass2_ws_words(m), m);
-	uint16_t *const r = W.r;
+	Pass2Ws const W0 = pass2_ws(ws + (size_t) blockIdx.x * pass2_ws_words(m), m);
 	uint32_t pbits = 1;
 	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
 	for (;;)
@@ -545,8 +548,14 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 		__syncthreads();                                                  // (S.grp is read by all before it is taken again)
 		if (g >= ngrp) break;
 		uint2 const gr = grps[g];
-		size_t const sb = (size_t) task_blk[gr.x] * m;
+		uint32_t const blk = task_blk[gr.x];
+		size_t const sb = (size_t) blk * m;
 		uint32_t const *a0 = bstate_a + sb, *d0 = bstate_d + sb;
+		// the block's r: phase B's, where it handed the block's keys over, else gathered into the workspace below
+		bool const handed = hand_keys != nullptr && hand_flag[blk] != 0u;
+		Pass2Ws W = W0;
+		if (handed) W.r = const_cast<uint16_t *>(hand_keys) + sb;               // (read only from here on)
+		if (hand_stats && tid == 0) atomicAdd(hand_stats + (handed ? 0 : 1), 1u);
 		bool have_r = false;
 		for (uint32_t task = gr.x; task < gr.x + gr.y; ++task)
 		{
@@ -563,14 +572,15 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 			{
 				// the block's ranks in the order in front of its boundaries, once for all of them (U loads in flight per thread)
 				constexpr uint32_t U = 4;
-				for (uint32_t i0 = tid; i0 < m; i0 += ST * U)
-				{
-					uint32_t rv[U];
+				if (!handed)
+					for (uint32_t i0 = tid; i0 < m; i0 += ST * U)
+					{
+						uint32_t rv[U];
 #pragma unroll
-					for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; rv[u] = i < m ? rank[sb + a0[i]] : 0u; }
+						for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; rv[u] = i < m ? rank[sb + a0[i]] : 0u; }
 #pragma unroll
-					for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; if (i < m) r[i] = (uint16_t) rv[u]; }
-				}
+						for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; if (i < m) W.r[i] = (uint16_t) rv[u]; }
+					}
 				// ... and the records and the table of its boundary state
 				pass2_records(m, a0, d0, W.rec, W.tab);
 				have_r = true;
@@ -1088,8 +1098,9 @@ constexpr uint32_t CW_U = 8;
 // The keys of the old positions, W.keys[i] = rk[a0[i]], and the runs they form, counted on the way: position i starts a run where
 // its key is not the key at i - 1.  A wave sweeps its chunk in order (the key in front of a group of 64: the last lane of the group
 // before; in front of the chunk: looked up).  *R: the runs of the step; returns the runs in front of this wave's chunk.  Ends with
-// a barrier.
-__device__ __forceinline__ uint32_t chainwg_keys(uint32_t m, uint32_t const *__restrict__ rk, uint32_t const *a0, ChainWgWs const &W, ChainWgLds &S, uint32_t *R)
+// a barrier.  hk (or nullptr): where the step hands its keys over to pass 2, 16 bits a row, beside W.keys.
+__device__ __forceinline__ uint32_t chainwg_keys(uint32_t m, uint32_t const *__restrict__ rk, uint32_t const *a0, ChainWgWs const &W, ChainWgLds &S, uint16_t *hk,
+                                                 uint32_t *R)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1113,6 +1124,7 @@ __device__ __forceinline__ uint32_t chainwg_keys(uint32_t m, uint32_t const *__r
 			if (i0 + u * 64u >= c_hi) break;
 			bool const in = i < c_hi;
 			if (in) W.keys[i] = kv[u];
+			if (hk && in) hk[i] = (uint16_t) kv[u];
 			uint32_t const up = shfl_up_u32(kv[u], 1);
 			k0 += (uint32_t) __popcll(__ballot(in && kv[u] != (lane ? up : prev)));
 			prev = readlane_u32(kv[u], 63);                               // (a group that is not whole is the chunk's last)
@@ -1397,11 +1409,15 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 			bool const p4 = kb + pbits <= 32u;
 			uint32_t nrun = 0;
 			bool by_runs = false;
+			// [r15] the hand-over to pass 2 (A.hand_keys: the host sets it for the expansion of the alignment's own blocks alone): this step
+			// goes through block b from the exact state in front of it, so its keys rk[a0[i]] are pass 2's r of the block, word for
+			// word.  Not from the identity (the keys are rk itself) and not where a key does not fit 16 bits: the flag stays clear
+			uint16_t *const hk = A.hand_keys && A.out_state_a && !A.out_rank && !ident && nk <= 65536u ? A.hand_keys + (size_t) b * m : nullptr;
 			if (!ident)
 			{
 				// the keys in the order in front of the block, once for the step, and their runs
 				uint32_t R = 0;
-				uint32_t const wbase = chainwg_keys(m, rk, a0, W, S, &R);
+				uint32_t const wbase = chainwg_keys(m, rk, a0, W, S, hk, &R);
 				bool const may = run_cap != 0u && p4;
 				nrun = may ? R : 0u;
 				by_runs = may && R <= run_cap;
@@ -1412,6 +1428,7 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 				if (p4) chainwg_sort<true>(m, rk, kd, nk, W, S, ident, kstart, a0, d0, a1, d1);
 				else chainwg_sort<false>(m, rk, kd, nk, W, S, ident, kstart, a0, d0, a1, d1);
 			}
+			if (hk && tid == 0u) A.hand_flag[b] = 1u;                         // (behind the step's last barrier: the keys are whole)
 			if (stats && tid == 0)
 			{
 				atomicAdd(stats + (ident ? 2 : by_runs ? 0 : 1), 1u);

@@ -140,6 +140,7 @@ struct Tuning {
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
 	int  p2_run_cap = -1;                // FSEQ_P2_RUN_CAP: most runs of equal class a task of the streamed pass 2 moves by runs (0: every task sorts its rows; clamped to P2_RUN_CAP)
 	int  chain_run_cap = -1;             // FSEQ_CHAIN_RUN_CAP: most runs of equal key a step of phase B's chain-per-workgroup kernel moves by runs (0: every step sorts its rows; clamped to CW_RUN_CAP)
+	int  p2_keys = 0;                    // FSEQ_P2_KEYS: unset or 0: phase B's chain-per-workgroup kernel hands the keys of the blocks it steps through to pass 2's streamed chain step; 2: it writes none and pass 2 gathers its own
 	int  chain_wg = 0;                   // FSEQ_CHAIN_WG: streamed phase B's chains on one workgroup each (k_chain_wg): unset or 0: launches of at least a chain per CU; 1: every launch; 2: none
 	bool scan_rebuild = false;           // FSEQ_SCAN_REBUILD: fseq_scan_segment_lengths builds the lists at every length (by itself: folds them from the length before, builds where the DP asks)
 	int  match_split = 0;                // FSEQ_MATCH_SPLIT: segments the matcher's walk is split into along the columns (1..4,096; 1 = unsplit; by itself: the entries that take query rows choose, those over the alignment's rows walk unsplit)
@@ -197,6 +198,7 @@ struct Tuning {
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
 			{"FSEQ_CHAIN_RUN_CAP", nullptr, &Tuning::chain_run_cap, 0, -1, nullptr},
 			{"FSEQ_CHAIN_WG", nullptr, &Tuning::chain_wg, 0, 0, nullptr},
+			{"FSEQ_P2_KEYS", nullptr, &Tuning::p2_keys, 0, 0, nullptr},
 			{"FSEQ_CLASS_COLUMNS", nullptr, &Tuning::class_columns, 0, 1, nullptr},
 			{"FSEQ_CLASS_GATHER", &Tuning::class_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_SCAN_REBUILD", &Tuning::scan_rebuild, nullptr, 0, 0, nullptr},
@@ -385,6 +387,12 @@ struct fseq_ctx {
 	DevBuf<uint32_t> d_cshist;               // streamed phase B spread over the chip (fseq_chainsort.hpp): digit histograms [chain][part][bin]
 	int dev_cus = -1;                        // the device's CUs (device_cus: asked once a context)
 	int cw_resident = 0;                     // workgroups of k_chain_wg a CU holds at once (prepare_stream_kernels)
+	// [r15] phase B's hand-over to pass 2 (ChainMultiArgs::hand_keys): the keys of block b in the order in front of it at
+	// d_p2keys + b * m where d_p2keys_flag[b] is set.  Buffers the run can do without (empty: pass 2 gathers its own)
+	DevBuf<uint16_t> d_p2keys;
+	DevBuf<uint32_t> d_p2keys_flag;
+	bool p2keys_live = false;                // the flags are those of the boundary states the context holds (phase B cleared and set them)
+	uint32_t p2_hand[2]{};                   // pass 2's groups of the last run that took handed-over keys, and those that gathered
 	DevBuf<uint32_t> d_cw_stats;             // FSEQ_DEBUG: the counters of phase B's chain-per-workgroup kernel (CW_STATS words; empty otherwise: the kernel keeps none)
 	DevBuf<uint32_t> d_hrank, d_hkeyd, d_hnkeys, d_hstate_a, d_hstate_d;
 	// not sharded: phase B over any number of levels (levels[i - 1] = the composites of chain_fan level-(i - 1) key blocks)

@@ -200,7 +200,7 @@ uint32_t pass2_run_cap(fseq_ctx const *c)
 
 // streamed rows: pass 2's chain step by runs or as a radix sort, + range maxima, in a workspace per workgroup (fseq_chainsort.hpp),
 // a block's tasks on one workgroup, the ngrp groups of d_red_p2grp taken from the counter behind them; stats: P2_STATS zeroed
-// device words (fseq_debug_pass2_paths)
+// device words (fseq_debug_pass2_paths) and P2_HAND more behind them (the groups that took phase B's keys, the groups that gathered)
 int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats)
 {
 	uint32_t const m = c->p.m;
@@ -218,9 +218,12 @@ int launch_chain_snap_grouped(fseq_ctx *c, uint32_t ngrp, uint32_t *stats)
 		fprintf(stderr, "[fseq] pass 2 chain steps: %u groups on %u workgroups (the workspace holds %zu, a CU %d), %zu bytes of LDS, at most %u runs\n", ngrp, grid, fit,
 		        resident, pass2_lds_bytes(), pass2_run_cap(c));
 	}
+	// phase B's keys where it handed them over for the boundary states in force (FSEQ_P2_KEYS=2: none)
+	bool const hand = c->p2keys_live && c->tune.p2_keys != 2 && c->d_p2keys.base && c->d_p2keys_flag.base;
 	hipLaunchKernelGGL(k_chain_snap_grouped, dim3(grid), dim3(ST), pass2_lds_bytes(), st, c->d_bstate_a, c->d_bstate_d, c->d_rank, m, c->d_red_taskblk, c->d_red_cls,
 	                   c->d_red_headd, c->d_red_ncls, c->red_cap, c->d_red_p2grp.as<uint2 const>(), ngrp, c->d_red_p2grp + 2 * (size_t) ngrp,
-	                   c->d_snap_a, c->d_snap_d, c->d_ws.base, pass2_run_cap(c), stats);
+	                   c->d_snap_a, c->d_snap_d, c->d_ws.base, pass2_run_cap(c), stats, hand ? c->d_p2keys.base : (uint16_t const *) nullptr,
+	                   hand ? c->d_p2keys_flag.base : (uint32_t const *) nullptr, stats + P2_STATS);
 	return FSEQ_OK;
 }
 
@@ -462,6 +465,7 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 {
 	FSEQ_LONG_LOCALS(c);
 	(void) R;
+	bool hand = false;                                            // phase B hands the keys of level 0's expansion to pass 2 (below)
 	// level 0: my key blocks and boundary states; level i: the composites of chain_fan key blocks of level i - 1 (fseq_ctx::levels)
 	auto rank_of = [&](size_t i) { return i ? c->levels[i - 1].rank : c->d_rank; };
 	auto keyd_of = [&](size_t i) { return i ? c->levels[i - 1].keyd : c->d_keyd; };
@@ -488,8 +492,24 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		ChainMultiArgs A = chains_of(i, G, grp0);
 		if (i < c->levels.size()) { A.start_a = sa_of(i + 1); A.start_d = sd_of(i + 1); }
 		A.out_state_a = sa_of(i); A.out_state_d = sd_of(i);
+		// (the alignment's own blocks: the kernel that walks a chain on one workgroup hands its keys to pass 2)
+		if (i == 0 && hand) { A.hand_keys = c->d_p2keys.base; A.hand_flag = c->d_p2keys_flag.base; }
 		return A;
 	};
+	// [r15] The expansion of level 0 steps through block b from bstate_a[b] with rank[b]: its keys are the r pass 2's streamed chain
+	// step gathers for the block, so k_chain_wg stores them (16 bits a row, a flag per block) and pass 2 reads them.  Only where both
+	// ends exist -- streamed rows on one GPU, that launch on k_chain_wg by the rule, pass 2 (as far as known here) on the blocks'
+	// representatives -- and where the device has room: a failed allocation is no error, pass 2 then gathers as before.  The flags are
+	// cleared in front of every phase B: a context is reused across inputs, lengths and identity-reduced uploads
+	c->p2keys_live = false;
+	if (c->use_stream && !sharded && c->tune.p2_keys != 2 && !c->tune.no_reduced && n >= 2 * L && !(c->red.memory.declined && !c->tune.reduced_always)
+	    && chain_wg_groups(c, c->levels.empty() ? 1u : count_of(1)))
+	{
+		size_t const need = (size_t) c->nblocks * m;
+		hand = (c->d_p2keys.cap >= need || c->d_p2keys.try_alloc(c, need)) && (c->d_p2keys_flag.cap >= c->nblocks || c->d_p2keys_flag.try_alloc(c, c->nblocks));
+		if (hand) HIP_TRY(c, hipMemsetAsync(c->d_p2keys_flag.base, 0, (size_t) c->nblocks * 4, st));
+		else if (c->tune.debug) fprintf(stderr, "[fseq] phase B: no room for the keys it could hand to pass 2 (%zu bytes): pass 2 gathers its own\n", need * 2);
+	}
 	// FSEQ_DEBUG: the chain-per-workgroup kernel keeps its counters (zeroed here, read and printed below); else it keeps none
 	if (c->use_stream && c->tune.debug && c->tune.chain_wg < 2)
 	{
@@ -558,6 +578,7 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 			}
 		}
 	}
+	c->p2keys_live = hand;
 	HIP_TRY(c, hipEventRecord(c->ev.b_end, st));
 	HIP_TRY(c, hipGetLastError());
 	FSEQ_RANGE_POP();
@@ -704,14 +725,16 @@ bool rows_are_permutations(uint32_t const *a, size_t count, uint32_t m)
 int debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
                        uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,
                        uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank, uint32_t *out_keyd,
-                       uint32_t *out_nkeys, uint32_t *stats)
+                       uint32_t *out_nkeys, uint32_t *stats, uint16_t *hand_keys = nullptr, uint32_t *hand_flag = nullptr)
 {
 	// ---- everything an index is formed from, before the first HIP call
 	bool const want_states = out_state_a != nullptr, want_keys = out_rank != nullptr;
 	if (!rank || !keyd || !nkeys || (!want_states && !want_keys)) return FSEQ_E_ARG;
 	if (want_states != (out_state_d != nullptr) || want_keys != (out_keyd != nullptr) || want_keys != (out_nkeys != nullptr)) return FSEQ_E_ARG;
 	if ((start_a != nullptr) != (start_d != nullptr)) return FSEQ_E_ARG;
-	if (m < DEBUG_M_MIN || m > DEBUG_M_MAX || !nb_total || nb_total > 4096u) return FSEQ_E_ARG;
+	// (the entry that hands keys over takes any m from 65 on: the kernel's sweeps at a few rows a wave, and waves without any)
+	if (m < (hand_keys ? 65u : DEBUG_M_MIN) || m > DEBUG_M_MAX || !nb_total || nb_total > 4096u) return FSEQ_E_ARG;
+	if ((hand_keys != nullptr) != (hand_flag != nullptr) || (hand_keys && !workgroups)) return FSEQ_E_ARG;
 	if (!G || G > nb_total) return FSEQ_E_ARG;                            // (a chain of more steps than blocks only queues idle launches)
 	uint32_t const nchains_all = (nb_total + G - 1u) / G;
 	if (!chains || first_chain >= nchains_all || chains > nchains_all - first_chain) return FSEQ_E_ARG;
@@ -760,6 +783,16 @@ int debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, ui
 		if (!A.out_rank || !A.out_keyd || !A.out_nkeys) return FSEQ_E_OOM;
 		if (allow_lds(k_cm_emit, stream_lds_bytes(0, false)) != hipSuccess) return FSEQ_E_HIP;
 	}
+	if (hand_keys)
+	{
+		// the caller's array goes up as it is (what the kernel leaves alone comes back unchanged), the flags start clear
+		size_t const bytes = blocks * 2;
+		void *p = B.words((bytes + 3) / 4, 0);
+		A.hand_flag = B.words(nb_total, 0);
+		if (!p || !A.hand_flag) return FSEQ_E_OOM;
+		A.hand_keys = static_cast<uint16_t *>(p);
+		if (hipMemcpy(A.hand_keys, hand_keys, bytes, hipMemcpyHostToDevice) != hipSuccess) return FSEQ_E_HIP;
+	}
 	if (workgroups) launch_chain_wg(0, chains, workgroups, A, d_wg_ws, run_cap, d_stats);
 	else launch_chain_stream(0, chains, A);
 	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
@@ -771,8 +804,17 @@ int debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, ui
 	                  || hipMemcpy(out_keyd, A.out_keyd + at, (size_t) chains * m * 4, hipMemcpyDeviceToHost) != hipSuccess
 	                  || hipMemcpy(out_nkeys, A.out_nkeys + first_chain, (size_t) chains * 4, hipMemcpyDeviceToHost) != hipSuccess))
 		return FSEQ_E_HIP;
+	if (hand_keys && (hipMemcpy(hand_keys, A.hand_keys, blocks * 2, hipMemcpyDeviceToHost) != hipSuccess
+	                  || hipMemcpy(hand_flag, A.hand_flag, (size_t) nb_total * 4, hipMemcpyDeviceToHost) != hipSuccess))
+		return FSEQ_E_HIP;
 	return FSEQ_OK;
 }
+
+// one launch of pass 2's streamed chain step on constructed states; hand_keys / hand_flag (both or neither): phase B's hand-over
+int debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                     uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                     uint32_t run_cap, uint32_t workgroups, uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *snap_a, uint32_t *snap_d,
+                     uint32_t *stats, uint32_t *hand_stats);
 
 } // namespace
 
@@ -781,6 +823,39 @@ extern "C" {
 int fseq_debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
                           uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
                           uint32_t run_cap, uint32_t workgroups, uint32_t *snap_a, uint32_t *snap_d, uint32_t *stats)
+{
+	return debug_pass2_step(device, m, nblocks, a0, d0, rank, cap, ntasks, task_blk, cls, headd, ncls, run_cap, workgroups, nullptr, nullptr, snap_a, snap_d,
+	                        stats, nullptr);
+}
+
+int fseq_debug_pass2_step_keys(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                               uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                               uint32_t run_cap, uint32_t workgroups, uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *snap_a,
+                               uint32_t *snap_d, uint32_t *stats, uint32_t *hand_stats)
+{
+	if (!hand_keys || !hand_flag || !hand_stats) return FSEQ_E_ARG;
+	return debug_pass2_step(device, m, nblocks, a0, d0, rank, cap, ntasks, task_blk, cls, headd, ncls, run_cap, workgroups, hand_keys, hand_flag, snap_a,
+	                        snap_d, stats, hand_stats);
+}
+
+int fseq_debug_chain_launch_wg_keys(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank,
+                                    uint32_t const *keyd, uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a,
+                                    uint32_t const *start_d, uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d,
+                                    uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t *stats, uint16_t *hand_keys, uint32_t *hand_flag)
+{
+	if (!stats || run_cap > CW_RUN_CAP || !workgroups || workgroups > 1024u || !hand_keys || !hand_flag) return FSEQ_E_ARG;
+	return debug_chain_launch(device, m, nb_total, G, cols_per_block, rank, keyd, nkeys, first_chain, chains, start_a, start_d, run_cap, workgroups,
+	                          out_state_a, out_state_d, out_rank, out_keyd, out_nkeys, stats, hand_keys, hand_flag);
+}
+
+} // extern "C"
+
+namespace {
+
+int debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                     uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                     uint32_t run_cap, uint32_t workgroups, uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *snap_a, uint32_t *snap_d,
+                     uint32_t *stats, uint32_t *hand_stats)
 {
 	// ---- everything an index is formed from, before the first HIP call
 	if (!a0 || !d0 || !rank || !task_blk || !cls || !headd || !ncls || !snap_a || !snap_d || !stats) return FSEQ_E_ARG;
@@ -811,6 +886,11 @@ int fseq_debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t con
 		for (uint32_t j = 0; j < cap; ++j)
 			if (cls[(size_t) t * cap + j] >= D) return FSEQ_E_ARG;
 	}
+	// (a handed-over key is a rank of the block: the class table is looked up at it.  Only behind a set flag: what lies behind a
+	// clear one is never read, whatever it holds)
+	for (uint32_t b = 0; hand_keys && b < nblocks; ++b)
+		for (size_t i = 0; hand_flag[b] && i < m; ++i)
+			if (hand_keys[(size_t) b * m + i] >= cap) return FSEQ_E_ARG;
 	// largest first, the counter behind them (long_pass2_reduced)
 	std::stable_sort(groups.begin(), groups.end(), [](uint2 x, uint2 y) { return x.y > y.y; });
 	uint32_t const ngrp = (uint32_t) groups.size();
@@ -825,16 +905,31 @@ int fseq_debug_pass2_step(int device, uint32_t m, uint32_t nblocks, uint32_t con
 	uint32_t *d_grp = B.copy(grp_words.data(), grp_words.size());
 	uint32_t *d_sa = B.words(outs, 0xFF), *d_sd = B.words(outs, 0xFF), *d_stats = B.words(P2_STATS, 0);
 	uint32_t *d_ws = B.words((size_t) workgroups * pass2_ws_words(m), 0);
+	uint16_t *d_hk = nullptr;
+	uint32_t *d_hf = nullptr, *d_hs = nullptr;
+	if (hand_keys)
+	{
+		void *p = B.words((states * 2 + 3) / 4, 0);
+		d_hf = B.copy(hand_flag, nblocks); d_hs = B.words(P2_HAND, 0);
+		if (!p || !d_hf || !d_hs) return FSEQ_E_OOM;
+		d_hk = static_cast<uint16_t *>(p);
+		if (hipMemcpy(d_hk, hand_keys, states * 2, hipMemcpyHostToDevice) != hipSuccess) return FSEQ_E_HIP;
+	}
 	if (!d_a0 || !d_d0 || !d_rank || !d_blk || !d_cls || !d_headd || !d_ncls || !d_grp || !d_sa || !d_sd || !d_stats || !d_ws) return FSEQ_E_OOM;
 	if (allow_lds(k_chain_snap_grouped, pass2_lds_bytes()) != hipSuccess) return FSEQ_E_HIP;
 	hipLaunchKernelGGL(k_chain_snap_grouped, dim3(workgroups), dim3(ST), pass2_lds_bytes(), 0, d_a0, d_d0, d_rank, m, d_blk, d_cls, d_headd, d_ncls, cap,
-	                   reinterpret_cast<uint2 const *>(d_grp), ngrp, d_grp + 2 * (size_t) ngrp, d_sa, d_sd, d_ws, run_cap, d_stats);
+	                   reinterpret_cast<uint2 const *>(d_grp), ngrp, d_grp + 2 * (size_t) ngrp, d_sa, d_sd, d_ws, run_cap, d_stats, d_hk, d_hf, d_hs);
 	if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FSEQ_E_HIP;
 	if (hipMemcpy(snap_a, d_sa, outs * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(snap_d, d_sd, outs * 4, hipMemcpyDeviceToHost) != hipSuccess
 	    || hipMemcpy(stats, d_stats, P2_STATS * 4, hipMemcpyDeviceToHost) != hipSuccess)
 		return FSEQ_E_HIP;
+	if (hand_stats && hipMemcpy(hand_stats, d_hs, P2_HAND * 4, hipMemcpyDeviceToHost) != hipSuccess) return FSEQ_E_HIP;
 	return FSEQ_OK;
 }
+
+} // namespace
+
+extern "C" {
 
 int fseq_debug_chain_launch(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank, uint32_t const *keyd,
                             uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a, uint32_t const *start_d,

@@ -98,7 +98,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	if ((rc = c->d_red_ncls.ensure(c, S2))) return rc;
 	if ((rc = c->d_red_taskblk.ensure(c, S2))) return rc;
 	if ((rc = c->d_red_wgtasks.ensure(c, 4 * S2 + 64))) return rc;
-	if ((rc = c->d_red_p2grp.ensure(c, 2 * S2 + 2 + P2_STATS))) return rc;
+	if ((rc = c->d_red_p2grp.ensure(c, 2 * S2 + 2 + P2_STATS + P2_HAND))) return rc;
 	if ((rc = c->d_cols.ensure(c, S2))) return rc;
 	// streamed rows: the groups of the chain-step kernel, a block's tasks each (blocks with tasks of that kernel only), the
 	// largest first, and behind them the counter the workgroups take them by
@@ -122,7 +122,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		std::stable_sort(g.begin(), g.end(), [](uint2 const &x, uint2 const &y) { return x.y > y.y; });
 		for (auto const &x : g) { p2grp.push_back(x.x); p2grp.push_back(x.y); }
 		p2grp.push_back(0u);
-		p2grp.insert(p2grp.end(), P2_STATS, 0u);                   // (the kernel's counters, zeroed with the counter)
+		p2grp.insert(p2grp.end(), P2_STATS + P2_HAND, 0u);                   // (the kernel's counters, zeroed with the counter)
 	}
 	// the task lists through pinned memory of their own (live until the synchronisation behind the kernels)
 	std::vector<uint32_t> hb, hw;
@@ -148,7 +148,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 	}
 	{
-		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256 + P2_STATS * 4;
+		size_t const need = S2 * 16 + hb.size() * 16 + p2grp.size() * 4 + 256 + (P2_STATS + P2_HAND) * 4;
 		if (c->red_pin2_bytes < need)
 		{
 			if (c->h_red_pin2) (void) hipHostFree(c->h_red_pin2);
@@ -169,7 +169,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 			HIP_TRY(c, hipMemcpyAsync(c->d_red_wgtasks, put(hw.data(), hw.size() * 4), hw.size() * 4, hipMemcpyHostToDevice, st));
 		}
 	}
-	uint32_t *const pin_stats = reinterpret_cast<uint32_t *>(c->h_red_pin2 + c->red_pin2_bytes - P2_STATS * 4);      // (behind the task lists)
+	uint32_t *const pin_stats = reinterpret_cast<uint32_t *>(c->h_red_pin2 + c->red_pin2_bytes - (P2_STATS + P2_HAND) * 4);      // (behind the task lists)
 	c->p2_stats_have = false;
 	HIP_TRY(c, hipEventRecord(c->ev.pass2_begin, st));
 	progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
@@ -196,13 +196,13 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	else
 	{
 		// streamed rows: a block's tasks on one workgroup, the groups taken from a counter
-		uint32_t const ngrp = (uint32_t) ((p2grp.size() - 1 - P2_STATS) / 2);
+		uint32_t const ngrp = (uint32_t) ((p2grp.size() - 1 - P2_STATS - P2_HAND) / 2);
 		if (ngrp)
 		{
 			uint32_t *const stats = c->d_red_p2grp + 2 * (size_t) ngrp + 1;
 			if ((rc = launch_chain_snap_grouped(c, ngrp, stats))) return rc;
 			// (its counters come back with the synchronisation behind pass 2)
-			HIP_TRY(c, hipMemcpyAsync(pin_stats, stats, P2_STATS * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipMemcpyAsync(pin_stats, stats, (P2_STATS + P2_HAND) * 4, hipMemcpyDeviceToHost, st));
 			c->p2_stats_have = true;
 		}
 	}
@@ -236,7 +236,12 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(st));
 	range_p2.end();
-	if (c->p2_stats_have) memcpy(c->p2_stats, pin_stats, sizeof(c->p2_stats));
+	if (c->p2_stats_have)
+	{
+		memcpy(c->p2_stats, pin_stats, sizeof(c->p2_stats));
+		memcpy(c->p2_hand, pin_stats + P2_STATS, sizeof(c->p2_hand));
+		if (c->tune.debug) fprintf(stderr, "[fseq] pass 2 chain steps: %u groups took the keys phase B handed over, %u gathered their own\n", c->p2_hand[0], c->p2_hand[1]);
+	}
 	progress(c, FSEQ_STAGE_SAMPLES, S2, S2);
 	float f = 0;
 	HIP_TRY(c, hipEventElapsedTime(&f, c->ev.pass2_begin, c->ev.pass2_end)); R.ms_p2 = f;

@@ -523,7 +523,7 @@ void free_work(fseq_ctx *c)
 	release_levels(c);
 	release_all(c, c->d_ent, c->d_hdr, c->d_flags, c->d_recent, c->d_chunk_r0, c->d_tau, c->d_bk, c->d_bkws, c->d_todo, c->d_colmask, c->d_btws, c->d_only, c->d_tb);
 	release_all(c, c->dp.M, c->dp.LB, c->dp.SZ, c->dp.K, c->dp.Tb, c->dp.Tbv, c->d_Mprev, c->d_spec);
-	release_all(c, c->d_cols, c->d_grp, c->d_src, c->d_ss_a, c->d_ss_d, c->d_bs_w, c->d_bs_h, c->d_wgblk, c->d_wggrp, c->d_snap_a, c->d_snap_d, c->d_ws, c->d_cshist, c->d_cw_stats);
+	release_all(c, c->d_cols, c->d_grp, c->d_src, c->d_ss_a, c->d_ss_d, c->d_bs_w, c->d_bs_h, c->d_wgblk, c->d_wggrp, c->d_snap_a, c->d_snap_d, c->d_ws, c->d_cshist, c->d_cw_stats, c->d_p2keys, c->d_p2keys_flag);
 	release_all(c, c->d_red_cnt, c->d_red_cnt_plan, c->d_red_vmin, c->d_red_rows, c->d_red_leaf, c->d_red_a, c->d_red_d, c->d_red_invalid, c->d_red_blocks, c->d_red_msa, c->d_cls, c->d_cls_have, c->d_red_src);
 	release_all(c, c->d_red_ss_a, c->d_red_ss_d, c->d_red_cls, c->d_red_headd, c->d_red_ncls, c->d_red_taskblk, c->d_red_wgtasks, c->d_red_p2grp);
 	// what was planned for the buffers that are gone
@@ -533,6 +533,7 @@ void free_work(fseq_ctx *c)
 	c->red.memory.forget_verdicts();
 	c->red_cap = 0; c->red_ld = 0;
 	c->red_active = false;
+	c->p2keys_live = false;
 	c->cls_on = c->cls_every = c->cls_read = c->cls_staged = false; c->cls_ld = 0;
 }
 

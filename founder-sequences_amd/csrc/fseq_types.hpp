@@ -169,6 +169,10 @@ struct ChainMultiArgs {
 	uint32_t step;                               // block b0 + step of every chain
 	uint32_t pass;                               // radix pass of the sweep kernels
 	uint32_t nchains;                            // chains of the launch (the grid's y is rounded up to the XCDs: cm_wg)
+	// the hand-over to pass 2 (k_chain_wg alone; nullptr: none): hand_keys[b][m], 16 bits a row, the keys of block b in the order in
+	// front of it where hand_flag[b] is set (k_chain_snap_grouped takes them for its r)
+	uint16_t *hand_keys;
+	uint32_t *hand_flag;
 };
 
 // the reduced alignment k_reduce_msa writes: the listed blocks' representative rows (rows[block][cap], cnt[block] of them), column k at red + k * ldr
@@ -200,6 +204,7 @@ struct ClassColumnArgs {
 constexpr uint32_t P2_HIST = 19;                 // ... tasks by run count: bucket b counts those with more than 2^(b - 1) and at most 2^b runs (bucket 0: one run)
 constexpr uint32_t CW_STATS = 4 + P2_HIST;       // counters of phase B's chain-per-workgroup kernel (k_chain_wg): steps by runs, by the sort of the rows, from the identity, the most runs, steps by run count
 constexpr uint32_t P2_STATS = 4 + P2_HIST;       // counters of pass 2's streamed chain step (k_chain_snap_grouped; fseq_debug_pass2_paths)
+constexpr uint32_t P2_HAND = 2;                  // ... and behind them in the path's buffers: the groups that took phase B's keys, the groups that gathered their own
 constexpr uint32_t RED_WIDE = 2u;               // invalid[b]: the block has more distinct start values than its configuration's table holds
 struct RedArgs {
 	uint32_t const *cnt = nullptr;      // [block] representatives of the block

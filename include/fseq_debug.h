@@ -250,6 +250,24 @@ int  fseq_debug_chain_launch_wg(int device, uint32_t m, uint32_t nb_total, uint3
                                 uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d, uint32_t *out_rank,
                                 uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t *stats);
 
+/* fseq_debug_chain_launch_wg with the hand-over to pass 2: hand_keys[nb_total][m] (16 bits a row; in: any pattern, out: what the
+ * launch left of it) and hand_flag[nb_total] (out).  Where hand_flag[b] is set, hand_keys[b][i] = rank[b][a[i]] for the state a
+ * in front of block b: an expansion's run or sort step through b whose keys fit 16 bits.  Every other block keeps its pattern and
+ * a clear flag -- a composition hands nothing over.  Takes m from 65 on (the other entries: the streamed regime's 11,265). */
+int  fseq_debug_chain_launch_wg_keys(int device, uint32_t m, uint32_t nb_total, uint32_t G, uint64_t cols_per_block, uint32_t const *rank,
+                                     uint32_t const *keyd, uint32_t const *nkeys, uint32_t first_chain, uint32_t chains, uint32_t const *start_a,
+                                     uint32_t const *start_d, uint32_t run_cap, uint32_t workgroups, uint32_t *out_state_a, uint32_t *out_state_d,
+                                     uint32_t *out_rank, uint32_t *out_keyd, uint32_t *out_nkeys, uint32_t *stats, uint16_t *hand_keys,
+                                     uint32_t *hand_flag);
+
+/* fseq_debug_pass2_step with phase B's hand-over: hand_keys[nblocks][m] and hand_flag[nblocks]; a group whose block has its flag set
+ * reads the block's ranks in the order of its state from hand_keys and gathers none (FSEQ_E_ARG where such a key is not below cap).
+ * hand_stats[2] (out): the groups that took handed-over keys, the groups that gathered their own. */
+int  fseq_debug_pass2_step_keys(int device, uint32_t m, uint32_t nblocks, uint32_t const *a0, uint32_t const *d0, uint32_t const *rank, uint32_t cap,
+                                uint32_t ntasks, uint32_t const *task_blk, uint32_t const *cls, uint32_t const *headd, uint32_t const *ncls,
+                                uint32_t run_cap, uint32_t workgroups, uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *snap_a,
+                                uint32_t *snap_d, uint32_t *stats, uint32_t *hand_stats);
+
 /* The plan of phase C on representative rows (plan_reduced, csrc/fseq_redplan.hpp) on caller-supplied counts (debug / tests; touches
  * no device).  The configurations are the library's, judged as a run of m rows in blocks of B columns at `bits` bits a symbol would
  * judge them (direct != 0: LDS-resident rows, which stage the alignment's own columns).  cnt[nblocks]: the representatives of every
