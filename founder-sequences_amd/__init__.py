@@ -62,6 +62,26 @@ class Timings(C.Structure):
                 ("reduced_blocks", C.c_uint32), ("reduced_rows_mean", C.c_uint32), ("reduced_redone", C.c_uint32)]
 
 
+CHAIN_LEVELS_MAX, CHAIN_LAUNCHES_MAX = 40, 80      # include/fseq_debug.h, FSEQ_DEBUG_CHAIN_LEVELS / _LAUNCHES
+CHAIN_COMPOSE, CHAIN_TOP, CHAIN_EXPAND = 0, 1, 2    # fseq_chain_launch_info.kind
+
+
+class ChainLaunchInfo(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("level", "kind", "chains", "blocks", "first_chain", "workgroups")]
+
+
+class ChainPlan(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("fan", "fan_round5", "turns", "shard_k", "shard_q", "blocks_per_rank", "n_hyper", "b_lo", "b_hi",
+                                          "n_levels", "n_launches", "reserved")] + \
+               [("level_items", C.c_uint32 * CHAIN_LEVELS_MAX), ("launches", ChainLaunchInfo * CHAIN_LAUNCHES_MAX)]
+
+
+class PhaseBInfo(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("cus", "nblocks", "fan", "n_launches", "resident", "hand_armed", "stats_kept", "reserved")] + \
+               [("fit", C.c_uint64)] + [(f, C.c_uint32) for f in ("p2_groups", "p2_groups_took_keys", "p2_groups_gathered", "reserved2")] + \
+               [("cw_stats", C.c_uint32 * 23), ("reserved3", C.c_uint32), ("launches", ChainLaunchInfo * CHAIN_LAUNCHES_MAX)]
+
+
 class JoinProfile(C.Structure):
     _fields_ = [("ms_d2h", C.c_double), ("ms_classes", C.c_double), ("ms_edges", C.c_double), ("ms_draw", C.c_double), ("ms_total", C.c_double),
                 ("bytes_d2h", C.c_uint64)]
@@ -203,6 +223,7 @@ EXPORTS = [
     "fseq_graph_nearest_rows", "fseq_graph_nearest_held_out", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
     "fseq_write_block_graph_restored", "fseq_graph_thread_rows_restored", "fseq_graph_thread_held_out_restored",
     "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys",
+    "fseq_debug_chain_plan", "fseq_debug_chain_plan_sharded", "fseq_debug_phase_b",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -214,7 +235,8 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_restored_bounds", "fseq_debug_input_kept_range", "fseq_debug_alphabet",
                  "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass",
                  "fseq_debug_graph_thread", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
-                 "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys"]
+                 "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys",
+                 "fseq_debug_chain_plan", "fseq_debug_chain_plan_sharded", "fseq_debug_phase_b"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -383,6 +405,9 @@ def load_library():
     L.fseq_debug_graph_nearest_plan.argtypes = [vp, vp, vp, u64, C.c_uint32, u64, vp, vp, C.POINTER(u64)]
     L.fseq_debug_graph_nearest.argtypes = [C.c_int, vp, u64, C.c_uint32, u64, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, u64, C.c_uint32,
                                            C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.POINTER(GraphNearestInfo)]
+    L.fseq_debug_chain_plan.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u64, C.c_uint32, C.POINTER(ChainPlan)]
+    L.fseq_debug_chain_plan_sharded.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, u64, C.c_uint32, C.POINTER(ChainPlan)]
+    L.fseq_debug_phase_b.argtypes = [vp, C.POINTER(PhaseBInfo)]
     L.fseq_write_block_graph_restored.argtypes = [vp, C.c_uint32, C.c_int, C.c_char_p]
     L.fseq_graph_thread_rows_restored.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
     L.fseq_graph_thread_held_out_restored.argtypes = [vp, vp, vp, vp, vp, C.POINTER(GraphThreadSummary)]
@@ -627,6 +652,44 @@ def scan_plan_host(n, lengths):
     if rc != FSEQ_OK:
         raise FseqError(rc, L.fseq_strerror(rc).decode())
     return long_lengths[:n_long.value].copy(), slot[:len(lengths)].copy(), n_short.value
+
+
+CHAIN_FIT_ANY = 0xFFFFFFFFFFFFFFFF      # chain_plan_host: a workspace that holds any number of workgroups
+
+
+def _chain_launches(launches, n):
+    return [tuple(int(getattr(launches[i], f)) for f in ("level", "kind", "chains", "blocks", "first_chain", "workgroups")) for i in range(n)]
+
+
+def _chain_plan_dict(p):
+    out = {f: int(getattr(p, f)) for f in ("fan", "fan_round5", "turns", "shard_k", "shard_q", "blocks_per_rank", "n_hyper", "b_lo", "b_hi")}
+    out["level_items"] = [int(p.level_items[i]) for i in range(p.n_levels)]
+    out["launches"] = _chain_launches(p.launches, p.n_launches)
+    return out
+
+
+def chain_plan_host(m, nblocks, cus, streamed=None, chain_wg=0, chain_fan=0, fit=CHAIN_FIT_ANY, resident=1):
+    """The plan of phase B on one GPU (csrc/fseq_chainplan.hpp, fseq_debug_chain_plan) for m rows in nblocks blocks on a device of
+    `cus` CUs; streamed: whether the rows take the streamed kernels (None: more than 11,264 rows); chain_wg / chain_fan: the knobs
+    FSEQ_CHAIN_WG / FSEQ_CHAIN_FAN; fit, resident: the cap on the workgroups of a launch on k_chain_wg.  No device is touched.
+    Returns a dict: fan, fan_round5, turns, level_items, launches [(level, kind, chains, blocks, first_chain, workgroups)]."""
+    L = load_library()
+    p = ChainPlan()
+    rc = L.fseq_debug_chain_plan(m, int(m > 11264 if streamed is None else bool(streamed)), nblocks, cus, chain_wg, chain_fan, fit, resident, C.byref(p))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return _chain_plan_dict(p)
+
+
+def chain_plan_sharded_host(nblocks, world, rank, cus, chain_fan=0, streamed=True, chain_wg=0, fit=CHAIN_FIT_ANY, resident=1):
+    """The plan of a sharded rank's phase B (fseq_debug_chain_plan_sharded): chain_plan_host's dict with shard_k, shard_q,
+    blocks_per_rank, n_hyper and the rank's blocks [b_lo, b_hi); level_items are the rank's items of the levels 0 .. shard_k."""
+    L = load_library()
+    p = ChainPlan()
+    rc = L.fseq_debug_chain_plan_sharded(nblocks, world, rank, chain_fan, int(bool(streamed)), cus, chain_wg, fit, resident, C.byref(p))
+    if rc != FSEQ_OK:
+        raise FseqError(rc, L.fseq_strerror(rc).decode())
+    return _chain_plan_dict(p)
 
 
 def row_split_plan_host(m, bits, held):
@@ -1914,6 +1977,19 @@ class SegmentationContext:
         self._check(self.L.fseq_debug_pass2_paths(self.h, *[C.byref(x) for x in v], hist.ctypes.data))
         out = dict(zip(("by_runs", "by_sort", "copies", "max_runs"), (x.value for x in v)))
         out["runs_hist"] = [int(x) for x in hist]
+        return out
+
+    def phase_b(self):
+        """What phase B of the last run did (fseq_debug_phase_b): dict(cus, nblocks, fan, resident, fit, hand_armed, stats_kept,
+        p2_groups, p2_groups_took_keys, p2_groups_gathered, launches [(level, kind, chains, blocks, first_chain, workgroups)], and
+        cw_stats -- by_runs, by_sort, from_identity, max_runs, runs_hist -- or None where k_chain_wg kept no counters)."""
+        info = PhaseBInfo()
+        self._check(self.L.fseq_debug_phase_b(self.h, C.byref(info)))
+        out = {f: int(getattr(info, f)) for f in ("cus", "nblocks", "fan", "resident", "fit", "p2_groups", "p2_groups_took_keys", "p2_groups_gathered")}
+        out["hand_armed"], out["stats_kept"] = bool(info.hand_armed), bool(info.stats_kept)
+        out["launches"] = _chain_launches(info.launches, info.n_launches)
+        s = [int(x) for x in info.cw_stats]
+        out["cw_stats"] = dict(by_runs=s[0], by_sort=s[1], from_identity=s[2], max_runs=s[3], runs_hist=s[4:]) if info.stats_kept else None
         return out
 
     def class_column_sources(self):

@@ -97,6 +97,78 @@ int fseq_debug_pass2_paths(fseq_ctx *c, uint32_t *by_runs, uint32_t *by_sort, ui
 	return FSEQ_OK;
 }
 
+namespace {
+
+bool put_launches(std::vector<ChainLaunch> const &ls, fseq_chain_launch_info *out, uint32_t *n)
+{
+	if (ls.size() > FSEQ_DEBUG_CHAIN_LAUNCHES) return false;
+	for (size_t i = 0; i < ls.size(); ++i) out[i] = fseq_chain_launch_info{ls[i].level, ls[i].kind, ls[i].chains, ls[i].blocks, ls[i].first_chain, ls[i].workgroups};
+	*n = (uint32_t) ls.size();
+	return true;
+}
+
+} // namespace
+
+int fseq_debug_chain_plan(uint32_t m, int streamed, uint32_t nblocks, uint32_t cus, int chain_wg, uint32_t chain_fan, uint64_t fit, uint32_t resident,
+                          fseq_chain_plan *plan)
+{
+	if (!plan || 0 == m || 0 == nblocks || chain_wg < 0 || chain_wg > 2 || 1 == chain_fan || cus > 0x7FFFFFFFu || resident > 0x7FFFFFFFu) return FSEQ_E_ARG;
+	*plan = fseq_chain_plan{};
+	// (as block_geometry asks: the CUs count only where the turns could be looked at)
+	ChainFan const f = plan_chain_fan(m, streamed != 0, nblocks, (int) cus, chain_wg, chain_fan);
+	std::vector<uint32_t> const items = chain_level_items(nblocks, f.fan);
+	if (items.size() > FSEQ_DEBUG_CHAIN_LEVELS) return FSEQ_E_ARG;
+	plan->fan = f.fan; plan->fan_round5 = f.fan5; plan->turns = f.turns;
+	plan->n_levels = (uint32_t) items.size();
+	std::copy(items.begin(), items.end(), plan->level_items);
+	size_t const fit_ = (size_t) std::min<uint64_t>(fit, SIZE_MAX);
+	if (!put_launches(chain_launches(items, f.fan, streamed != 0, (int) cus, chain_wg, fit_, (int) resident), plan->launches, &plan->n_launches)) return FSEQ_E_ARG;
+	return FSEQ_OK;
+}
+
+int fseq_debug_chain_plan_sharded(uint32_t nblocks, uint32_t world, uint32_t rank, uint32_t chain_fan, int streamed, uint32_t cus, int chain_wg, uint64_t fit,
+                                  uint32_t resident, fseq_chain_plan *plan)
+{
+	if (!plan || 0 == nblocks || 0 == world || world > 4096u || rank >= world || chain_wg < 0 || chain_wg > 2 || 1 == chain_fan || cus > 0x7FFFFFFFu
+	    || resident > 0x7FFFFFFFu)
+		return FSEQ_E_ARG;
+	*plan = fseq_chain_plan{};
+	ShardChainPlan const S = plan_chain_sharded(nblocks, world, chain_fan ? chain_fan : CHAIN_SHARD_FAN);
+	if (S.k + 1 > FSEQ_DEBUG_CHAIN_LEVELS) return FSEQ_E_ARG;
+	plan->fan = plan->fan_round5 = S.F;
+	plan->shard_k = S.k; plan->shard_q = S.q; plan->blocks_per_rank = S.bpr; plan->n_hyper = S.n_hyper;
+	shard_block_range(S, nblocks, rank, &plan->b_lo, &plan->b_hi);
+	std::vector<uint32_t> lo, hi;
+	shard_level_ranges(S, plan->b_lo, plan->b_hi, lo, hi);
+	plan->n_levels = S.k + 1;
+	for (uint32_t i = 0; i <= S.k; ++i) plan->level_items[i] = hi[i] - lo[i];
+	size_t const fit_ = (size_t) std::min<uint64_t>(fit, SIZE_MAX);
+	if (!put_launches(shard_chain_launches(S, nblocks, rank, streamed != 0, (int) cus, chain_wg, fit_, (int) resident), plan->launches, &plan->n_launches))
+		return FSEQ_E_ARG;
+	return FSEQ_OK;
+}
+
+int fseq_debug_phase_b(fseq_ctx *c, fseq_phase_b_info *info)
+{
+	if (!c || !info) return FSEQ_E_ARG;
+	if (int const rc = need_result(c)) return rc;
+	static_assert(sizeof(info->cw_stats) == CW_STATS * 4, "fseq_phase_b_info::cw_stats holds the counters of k_chain_wg");
+	*info = fseq_phase_b_info{};
+	info->cus = (uint32_t) std::max(device_cus(c), 0);
+	info->nblocks = c->nblocks; info->fan = c->chain_fan;
+	if (!put_launches(c->pb_launches, info->launches, &info->n_launches)) return fail(c, FSEQ_E_UNSUPPORTED, "fseq_debug_phase_b: more launches than the report holds");
+	info->resident = c->use_stream ? (uint32_t) std::max(c->cw_resident, 0) : 0u;
+	info->fit = c->pb_fit;
+	info->hand_armed = c->pb_hand;
+	info->stats_kept = c->pb_cw_stats_have;
+	if (c->pb_cw_stats_have) std::copy(c->pb_cw_stats, c->pb_cw_stats + CW_STATS, info->cw_stats);
+	if (c->p2_stats_have)
+	{
+		info->p2_groups = c->p2_groups; info->p2_groups_took_keys = c->p2_hand[0]; info->p2_groups_gathered = c->p2_hand[1];
+	}
+	return FSEQ_OK;
+}
+
 int fseq_debug_class_columns(fseq_ctx *c, uint32_t *from_classes, uint32_t *from_alignment, uint32_t block, uint32_t *have, uint32_t *nkeys, uint64_t *ldc,
                              uint8_t *out, uint64_t out_bytes)
 {

@@ -9,6 +9,7 @@
 #include "../../include/fseq.h"
 #include "../../include/fseq_debug.h"
 #include "fseq_types.hpp"
+#include "fseq_chainplan.hpp"    // ChainLaunch: what a context remembers of its last phase B
 
 #include <hip/hip_runtime.h>
 
@@ -394,6 +395,14 @@ struct fseq_ctx {
 	bool p2keys_live = false;                // the flags are those of the boundary states the context holds (phase B cleared and set them)
 	uint32_t p2_hand[2]{};                   // pass 2's groups of the last run that took handed-over keys, and those that gathered
 	DevBuf<uint32_t> d_cw_stats;             // FSEQ_DEBUG: the counters of phase B's chain-per-workgroup kernel (CW_STATS words; empty otherwise: the kernel keeps none)
+	// what the last phase B did (fseq_debug_phase_b): its chain launches in the order they were queued, the counters of k_chain_wg where
+	// they were kept, whether the hand-over to pass 2 was armed, and the groups pass 2's streamed chain step then ran
+	std::vector<fseq::ChainLaunch> pb_launches;
+	uint32_t pb_cw_stats[fseq::CW_STATS]{};
+	bool pb_cw_stats_have = false;
+	bool pb_hand = false;
+	uint64_t pb_fit = 0;                     // workgroups of k_chain_wg the workspace held (streamed rows; chain_wg_groups)
+	uint32_t p2_groups = 0;
 	DevBuf<uint32_t> d_hrank, d_hkeyd, d_hnkeys, d_hstate_a, d_hstate_d;
 	// not sharded: phase B over any number of levels (levels[i - 1] = the composites of chain_fan level-(i - 1) key blocks)
 	struct ChainLevel { uint32_t count = 0; uint64_t cols = 0; DevBuf<uint32_t> rank, keyd, nkeys, state_a, state_d; };

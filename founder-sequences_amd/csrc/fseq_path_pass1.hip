@@ -120,31 +120,36 @@ uint32_t chain_run_cap(fseq_ctx const *c)
 }
 
 // How many workgroups of k_chain_wg a launch of `grid` chains gets; 0: the launch takes the spread kernels.  The rule: at least
-// a chain per CU.  Below that the spread kernels fill the chip and a chain per workgroup does not (the upper levels of the
-// recursion, the top chain, a sharded rank's 64 chains, BASELINE C4cols50k and C4slice at round 5's fan, which they keep:
-// block_geometry); from there on every CU has a chain of
-// its own, a step costs no launch, and the kernel moves runs.  FSEQ_CHAIN_WG: 1 every streamed launch, 2 none.
+// a chain per CU (chain_wg_rule, fseq_chainplan.hpp).  Below that the spread kernels fill the chip and a chain per workgroup does not
+// (the upper levels of the recursion, the top chain, BASELINE C4cols50k and C4slice at round 5's fan, which they keep:
+// block_geometry); from there on every CU has a chain of its own, a step costs no launch, and the kernel moves runs.  A sharded
+// rank's level 0 reaches the rule as well where the rank has at least 4 x CUs blocks (fan 4): BASELINE C4 on 2, 4 and 8 ranks of
+// 256 CUs launches 768, 384 and 256 chains there (fseq_debug_chain_plan_sharded).  FSEQ_CHAIN_WG: 1 every streamed launch, 2 none.
 uint32_t chain_wg_groups(fseq_ctx *c, uint32_t grid)
 {
-	if (c->tune.chain_wg >= 2) return 0;
-	int const ncu = std::max(device_cus(c), 1);
-	if (c->tune.chain_wg != 1 && grid < (uint32_t) ncu) return 0;
+	if (c->tune.chain_wg >= 2) return 0;             // (no device is asked)
 	// as many as are resident at once (one a CU: its LDS) and as the workspace holds.  d_ws is a workspace of 9 m + B + 16 words per
 	// block, a launch by the rule has CUs x fan blocks below it and fan >= 2: it holds a workgroup a CU (13 m + 90,000 words each)
 	// from 18,000 rows on, and below that the launch takes fewer workgroups and more turns; only a forced launch on a few blocks
 	// can find room for none, and takes the spread kernels
 	size_t const fit = c->d_ws.cap / chainwg_ws_words(c->p.m);
-	return (uint32_t) std::min<size_t>(std::min<size_t>(grid, fit), (size_t) ncu * (size_t) std::max(c->cw_resident, 1));
+	return chain_wg_workgroups(grid, device_cus(c), c->tune.chain_wg, fit, c->cw_resident);
 }
 
 // one chain launch of phase B (A: the level's key blocks, the start states, what comes out -- ChainMultiArgs); the launch
-// adds the rows and, streamed rows, its workspace
-void launch_chain(fseq_ctx *c, uint32_t grid, ChainMultiArgs A)
+// adds the rows and, streamed rows, its workspace.  level, kind: for the context's record of the launch (fseq_debug_phase_b)
+void launch_chain(fseq_ctx *c, uint32_t grid, ChainMultiArgs A, uint32_t level, ChainLaunchKind kind)
 {
 	if (!grid) return;
 	A.m = c->p.m;
+	uint32_t const wgs = c->use_stream ? chain_wg_groups(c, grid) : 0u;
+	{
+		ChainLaunch rec;
+		rec.level = level; rec.kind = kind; rec.chains = grid; rec.blocks = A.G; rec.first_chain = A.grp0; rec.workgroups = wgs;
+		c->pb_launches.push_back(rec);
+	}
 	if (c->use_stream)
-		if (uint32_t const wgs = chain_wg_groups(c, grid))
+		if (wgs)
 		{
 			if (c->tune.debug)
 				fprintf(stderr, "[fseq] phase B: %u chains of %u blocks on %u workgroups of their own (%zu bytes of LDS, at most %u runs)\n", grid, A.G, wgs,
@@ -502,6 +507,8 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 	// representatives -- and where the device has room: a failed allocation is no error, pass 2 then gathers as before.  The flags are
 	// cleared in front of every phase B: a context is reused across inputs, lengths and identity-reduced uploads
 	c->p2keys_live = false;
+	c->pb_launches.clear(); c->pb_hand = false; c->pb_cw_stats_have = false;
+	c->pb_fit = c->use_stream ? c->d_ws.cap / chainwg_ws_words(m) : 0;
 	if (c->use_stream && !sharded && c->tune.p2_keys != 2 && !c->tune.no_reduced && n >= 2 * L && !(c->red.memory.declined && !c->tune.reduced_always)
 	    && chain_wg_groups(c, c->levels.empty() ? 1u : count_of(1)))
 	{
@@ -524,9 +531,9 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		// expand every group from the boundary state the level above gave it (parallel)
 		uint32_t const G = c->chain_fan;
 		size_t const top = c->levels.size();
-		for (size_t i = 0; i < top; ++i) launch_chain(c, count_of(i + 1), compose(i, G));
-		launch_chain(c, 1, expand(top, count_of(top)));
-		for (size_t i = top; i-- > 0;) launch_chain(c, count_of(i + 1), expand(i, G));
+		for (size_t i = 0; i < top; ++i) launch_chain(c, count_of(i + 1), compose(i, G), (uint32_t) i, CHAIN_COMPOSE);
+		launch_chain(c, 1, expand(top, count_of(top)), (uint32_t) top, CHAIN_TOP);
+		for (size_t i = top; i-- > 0;) launch_chain(c, count_of(i + 1), expand(i, G), (uint32_t) i, CHAIN_EXPAND);
 	}
 	else
 	{
@@ -544,8 +551,8 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 		mine.out_rank = c->d_hrank; mine.out_keyd = c->d_hkeyd; mine.out_nkeys = c->d_hnkeys;
 		hyper.rank = c->d_hrank; hyper.keyd = c->d_hkeyd; hyper.nkeys = c->d_hnkeys; hyper.nb_total = hyper.G = NH; hyper.cols_per_block = (uint64_t) sh.bpr * c->B;
 		hyper.out_state_a = c->d_hstate_a; hyper.out_state_d = c->d_hstate_d;
-		for (uint32_t i = 0; have && i < K; ++i) launch_chain(c, hi[i + 1] - lo[i + 1], compose(i, F, lo[i + 1]));
-		if (have) launch_chain(c, 1, mine);
+		for (uint32_t i = 0; have && i < K; ++i) launch_chain(c, hi[i + 1] - lo[i + 1], compose(i, F, lo[i + 1]), i, CHAIN_COMPOSE);
+		if (have) launch_chain(c, 1, mine, K, CHAIN_COMPOSE);
 		{
 			// xbuf: [hrank NH x m][hkeyd NH x m][hnkeys NH]
 			size_t const w = (size_t) NH * m;
@@ -561,14 +568,14 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 			HIP_TRY(c, hipMemcpyAsync(c->d_hkeyd, sh.xbuf + w, w * 4, hipMemcpyDeviceToDevice, st));
 			HIP_TRY(c, hipMemcpyAsync(c->d_hnkeys, sh.xbuf + 2 * w, (size_t) NH * 4, hipMemcpyDeviceToDevice, st));
 		}
-		launch_chain(c, 1, hyper);
+		launch_chain(c, 1, hyper, K + 1, CHAIN_TOP);
 		if (have)
 		{
 			// (my hyper-block starts from the state the chain over the hyper key blocks left in front of it)
 			ChainMultiArgs top = expand(K, Q, sh.rank);
 			top.start_a = c->d_hstate_a; top.start_d = c->d_hstate_d;
-			launch_chain(c, 1, top);
-			for (uint32_t i = K; i-- > 0;) launch_chain(c, hi[i + 1] - lo[i + 1], expand(i, F, lo[i + 1]));
+			launch_chain(c, 1, top, K, CHAIN_EXPAND);
+			for (uint32_t i = K; i-- > 0;) launch_chain(c, hi[i + 1] - lo[i + 1], expand(i, F, lo[i + 1]), i, CHAIN_EXPAND);
 			// the state behind my last block = in front of the next rank's hyper-block (or behind the whole alignment,
 			// which the expansion has written itself): my halo block starts from it
 			if (b_hi < c->nblocks)
@@ -578,7 +585,7 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 			}
 		}
 	}
-	c->p2keys_live = hand;
+	c->p2keys_live = c->pb_hand = hand;
 	HIP_TRY(c, hipEventRecord(c->ev.b_end, st));
 	HIP_TRY(c, hipGetLastError());
 	FSEQ_RANGE_POP();
@@ -586,9 +593,10 @@ int long_phase_b(fseq_ctx *c, LongRun &R)
 	progress(c, FSEQ_STAGE_TRACEBACK, n / 5, n);                  // (phases A and B queued: about a fifth of pass 1)
 	if (c->d_cw_stats.base)
 	{
-		uint32_t s[CW_STATS] = {};
+		uint32_t (&s)[CW_STATS] = c->pb_cw_stats;
 		HIP_TRY(c, hipMemcpyAsync(s, c->d_cw_stats.base, sizeof(s), hipMemcpyDeviceToHost, st));
 		HIP_TRY(c, hipStreamSynchronize(st));
+		c->pb_cw_stats_have = true;
 		fprintf(stderr, "[fseq] phase B chain steps on a workgroup of their own: %u by runs, %u by the sort of the rows, %u from the identity; most runs %u; by run count (<= 2^b):", s[0], s[1], s[2], s[3]);
 		for (uint32_t b = 0; b < P2_HIST; ++b) fprintf(stderr, " %u", s[4 + b]);
 		fprintf(stderr, "\n");

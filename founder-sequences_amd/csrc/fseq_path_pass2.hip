@@ -170,7 +170,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		}
 	}
 	uint32_t *const pin_stats = reinterpret_cast<uint32_t *>(c->h_red_pin2 + c->red_pin2_bytes - (P2_STATS + P2_HAND) * 4);      // (behind the task lists)
-	c->p2_stats_have = false;
+	c->p2_stats_have = false; c->p2_groups = 0;
 	HIP_TRY(c, hipEventRecord(c->ev.pass2_begin, st));
 	progress(c, FSEQ_STAGE_SAMPLES, 0, S2);
 	RangeScope range_p2("fseq pass 2: boundary states (update_pbwt_task)");
@@ -203,7 +203,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 			if ((rc = launch_chain_snap_grouped(c, ngrp, stats))) return rc;
 			// (its counters come back with the synchronisation behind pass 2)
 			HIP_TRY(c, hipMemcpyAsync(pin_stats, stats, (P2_STATS + P2_HAND) * 4, hipMemcpyDeviceToHost, st));
-			c->p2_stats_have = true;
+			c->p2_stats_have = true; c->p2_groups = ngrp;
 		}
 	}
 	for (size_t i = 0; i < S2; ++i)

@@ -6,6 +6,7 @@
 #include "fseq_dp.hpp"           // dp_schedule (the halo of a sharded rank)
 #include "fseq_stream.hpp"       // the sizes of the streamed kernels' LDS, workspaces and stride states
 #include "fseq_blockkeys.hpp"    // ... and of phase A in key space
+#include "fseq_chainplan.hpp"    // the fan of phase B and a sharded rank's (k, q)
 
 namespace fseq {
 
@@ -96,33 +97,14 @@ void block_geometry(fseq_ctx *c)
 	c->nblocks = (uint32_t) ((p.n + c->B - 1) / c->B);
 	if (sh.on)
 	{
-		// A rank is one hyper-block of phase B: q groups of F^k blocks, composed level by level with fan F (k launches of
-		// <= F serial steps up, the q composites into the hyper key block, and the same down again).  q F^k >= the
-		// blocks a rank needs; (k, q) with the fewest serial steps among those that keep every rank busy.
-		uint32_t const per = (c->nblocks + sh.world - 1) / sh.world;
-		uint32_t F = 4;
-		if (c->tune.chain_fan) F = (uint32_t) c->tune.chain_fan;
-		uint32_t best_k = 0, best_q = std::max(1u, per), best_cost = ~0u;
-		{
-			uint64_t pw = 1;
-			for (uint32_t k = 0; pw <= per; ++k, pw *= F)
-			{
-				uint32_t const q = (uint32_t) ((per + pw - 1) / pw);
-				uint64_t const bpr = (uint64_t) q * pw;
-				bool const all_busy = bpr == per || bpr * (sh.world - 1) < c->nblocks;      // the last rank still owns blocks
-				uint32_t const cost = F * k + q;
-				if ((all_busy || k == 0) && cost < best_cost) { best_cost = cost; best_k = k; best_q = q; }
-			}
-		}
-		c->chain_fan = F; c->shard_k = best_k; c->shard_q = best_q;
-		{
-			uint64_t pw = 1;
-			for (uint32_t i = 0; i < best_k; ++i) pw *= F;
-			sh.bpr = (uint32_t) (best_q * pw);
-			c->chain_G = (uint32_t) pw; c->chain_G2 = best_q;          // (diagnostics: a rank = chain_G2 groups of chain_G blocks)
-		}
-		c->n_super = (c->nblocks + c->chain_G - 1) / c->chain_G;
-		c->n_hyper = (c->nblocks + sh.bpr - 1) / sh.bpr;
+		// A rank is one hyper-block of phase B: q groups of F^k blocks, composed level by level with fan F; (k, q) with the fewest
+		// serial steps among those that keep every rank busy (plan_chain_sharded, fseq_chainplan.hpp)
+		ShardChainPlan const S = plan_chain_sharded(c->nblocks, sh.world, c->tune.chain_fan ? (uint32_t) c->tune.chain_fan : CHAIN_SHARD_FAN);
+		c->chain_fan = S.F; c->shard_k = S.k; c->shard_q = S.q;
+		sh.bpr = S.bpr;
+		c->chain_G = S.group; c->chain_G2 = S.q;                   // (diagnostics: a rank = chain_G2 groups of chain_G blocks)
+		c->n_super = S.n_super;
+		c->n_hyper = S.n_hyper;
 		sh.active = c->n_hyper;                                 // <= world
 		sh.b_lo = std::min<uint64_t>(c->nblocks, (uint64_t) sh.rank * sh.bpr);
 		sh.b_hi = std::min<uint64_t>(c->nblocks, (uint64_t) (sh.rank + 1) * sh.bpr);
@@ -132,74 +114,20 @@ void block_geometry(fseq_ctx *c)
 		return;
 	}
 	{
-		// Phase B is serial over key blocks, so it is applied recursively: compose groups of G blocks from the identity
-		// (parallel), groups of G of those, ... until at most G are left, chain them, expand level by level.  Serial depth
-		// = G steps per launch, 2 levels - 1 launches (+ about half a step of launch gap each): G = 4 for 100..10^4
-		// blocks (1024 blocks: 9 launches of <= 4 steps instead of the 5 x 11 of a three-level chain).
-		uint32_t best_g = c->nblocks, best_cost = ~0u;
-		for (uint32_t g = 2; g <= 64 && g < std::max(3u, c->nblocks); ++g)
-		{
-			uint32_t lv = 1;
-			for (uint64_t cap = g; cap < c->nblocks; cap *= g) ++lv;
-			uint32_t const cost = (2u * lv - 1u) * (2u * g + 1u);
-			if (cost < best_cost) { best_cost = cost; best_g = g; }
-		}
-		// [r5] streamed rows: a step is a launch sequence over all the chains of a level (fseq_chainsort.hpp), bound by what it
-		// moves, not by its depth -- so the fan weighs the steps in all (the blocks of every level once on the way up, all but
-		// every chain's last on the way down: ~N (2g - 1) / (g - 1)) against the rounds of launches, (2g - 1) per level.
-		// BASELINE C4 (6,143 blocks, 100,000 rows), phase B: fan 3: 69.6 ms, 4: 61.6, 6: 56.5, 8: 54.1, 12: 50.9, 16: 53.7, 32: 57.5
+		// Phase B is serial over key blocks, so it is applied recursively: compose groups of G blocks from the identity (parallel),
+		// groups of G of those, ... until at most G are left, chain them, expand level by level.  The fan G is plan_chain_fan's
+		// (fseq_chainplan.hpp): by the serial depth on LDS-resident rows, by round 5's cost model on streamed rows, and [r14] among the
+		// wider fans by turns of workgroups where level 0 has at least a chain per CU and goes to k_chain_wg (launch_chain,
+		// fseq_path_pass1.hip).
+		// BASELINE C4 (6,143 blocks, 100,000 rows), phase B by round 5's kernels: fan 3: 69.6 ms, 4: 61.6, 6: 56.5, 8: 54.1, 12: 50.9, 16: 53.7,
+		// 32: 57.5.  With level 0 on k_chain_wg (measured: a step 0.5 ms by runs, 0.8 by the sort of the rows, 0.9 from the identity; the
+		// step is bound by the bytes it moves, which go with the rows): fan 11 (round 5's; 559 chains, 3 turns) 43.0 ms, 12 (512, 2 turns)
+		// 38.0, 24 (256, one turn) 36.8 -- the model's order.  Every other shape on one GPU keeps round 5's fan: with fewer than CUs x fan
+		// blocks (C4slice, C4cols50k) no level reaches the kernel.  FSEQ_CHAIN_WG=1 or 2 (tests): round 5's fan.
 		KernelSet probe;
-		if (!select_kernels(p.m, c->sigma, &probe) && c->nblocks > 8)
-		{
-			// cost of fan g by round 5's model; own: level 0 on k_chain_wg instead ([r14], below), `turns` turns of workgroups
-			auto cost_of = [&](uint32_t g, uint64_t turns) {
-				double steps = 0, rounds = 0, own = 0;
-				uint64_t cnt = c->nblocks;
-				bool level0 = true;
-				while (cnt > g)
-				{
-					if (level0 && turns) own = (double) turns * ((2.0 * g - 1.0) * 0.5 + 0.4) * ((double) p.m / 1e5);
-					else
-					{
-						steps += (double) cnt * (2.0 * g - 1.0) / g;   // up: every item; down: all but the last of every group
-						rounds += 2.0 * g - 1.0;
-					}
-					level0 = false;
-					cnt = (cnt + g - 1) / g;
-				}
-				steps += (double) cnt; rounds += (double) cnt;           // the top chain
-				return own + steps * 3.5e-3 * ((double) p.m / 1e5) + rounds * 0.05;
-			};
-			double best = 1e300;
-			for (uint32_t g = 2; g <= 64 && g < c->nblocks; ++g)
-			{
-				double const cost = cost_of(g, 0);
-				if (cost < best) { best = cost; best_g = g; }
-			}
-			// [r14] Where that fan's level 0 has at least a chain per CU, the level goes to k_chain_wg (launch_chain, fseq_path_pass1.hip):
-			// a workgroup a CU walks its chains one after the other, so the level takes ceil(chains / CUs) turns of 2g - 1 steps, and a
-			// fan that leaves the last turn nearly empty pays for it.  Only then, and only among the wider fans that keep level 0 on
-			// that kernel, the turns are counted: a step 0.5 ms at 100,000 rows, a chain's step from the identity 0.4 more (BASELINE
-			// C4, measured: 0.5 ms by runs, 0.8 by the sort of the rows, 0.9 from the identity; the step is bound by the bytes it moves,
-			// which go with the rows).  Measured on C4, phase B: fan 11 (round 5's; 559 chains, 3 turns) 43.0 ms, 12 (512, 2 turns)
-			// 38.0, 24 (256, one turn) 36.8 -- the model's order.  Every other shape keeps round 5's fan: with fewer than 2 x CUs x
-			// fan blocks (C4slice, C4cols50k, a sharded rank) no level reaches the kernel.  FSEQ_CHAIN_WG=1 or 2 (tests): round 5's fan.
-			int const ncu = c->tune.chain_wg == 0 ? device_cus(c) : 0;
-			if (ncu > 0 && ((uint64_t) c->nblocks + best_g - 1) / best_g >= (uint64_t) ncu && c->nblocks > best_g)
-			{
-				uint32_t const g5 = best_g;
-				best = 1e300;
-				for (uint32_t g = g5; g <= 64 && g < c->nblocks; ++g)
-				{
-					uint64_t const chains = ((uint64_t) c->nblocks + g - 1) / g;
-					if (chains < (uint64_t) ncu) break;
-					double const cost = cost_of(g, (chains + ncu - 1) / ncu);
-					if (cost < best) { best = cost; best_g = g; }
-				}
-			}
-		}
-		if (c->nblocks <= 8) best_g = std::max(1u, c->nblocks);        // one chain
-		if (c->tune.chain_fan) best_g = (uint32_t) c->tune.chain_fan;
+		bool const stream_model = !select_kernels(p.m, c->sigma, &probe);
+		uint32_t const best_g = plan_chain_fan(p.m, stream_model, c->nblocks, stream_model && c->tune.chain_wg == 0 && c->nblocks > 8 ? device_cus(c) : 0, c->tune.chain_wg,
+		                                       (uint32_t) c->tune.chain_fan).fan;
 		c->chain_fan = best_g;
 		c->chain_G = best_g; c->n_super = (c->nblocks + best_g - 1) / best_g;      // (diagnostics)
 		c->chain_G2 = 0; c->n_hyper = 0;
@@ -366,13 +294,15 @@ int alloc_geometry_buffers(fseq_ctx *c)
 	{
 		// the composites of phase B, level by level: until at most chain_fan are left, or -- sharded -- shard_k levels below
 		// the hyper key blocks (indexed like the blocks: by their place in the whole alignment; a rank holds its own range)
+		// (the items of the levels on one GPU: chain_level_items, fseq_chainplan.hpp -- the plan the tests read)
+		std::vector<uint32_t> const items = c->sh.on ? std::vector<uint32_t>() : chain_level_items(c->nblocks, c->chain_fan);
 		uint32_t cnt = c->nblocks;
 		uint64_t cols = c->B;
 		size_t lo = bl, hi = bh;
-		for (uint32_t i = 0; c->sh.on ? i < c->shard_k : cnt > c->chain_fan; ++i)
+		for (uint32_t i = 0; c->sh.on ? i < c->shard_k : i + 1 < items.size(); ++i)
 		{
 			fseq_ctx::ChainLevel lv;
-			lv.count = (cnt + c->chain_fan - 1) / c->chain_fan;
+			lv.count = c->sh.on ? (cnt + c->chain_fan - 1) / c->chain_fan : items[i + 1];
 			lv.cols = cols * c->chain_fan;
 			lo = lo / c->chain_fan; hi = (hi + c->chain_fan - 1) / c->chain_fan;
 			c->levels.push_back(lv);                               // (pushed at once: release_levels releases what is there)

@@ -268,6 +268,63 @@ int  fseq_debug_pass2_step_keys(int device, uint32_t m, uint32_t nblocks, uint32
                                 uint32_t run_cap, uint32_t workgroups, uint16_t const *hand_keys, uint32_t const *hand_flag, uint32_t *snap_a,
                                 uint32_t *snap_d, uint32_t *stats, uint32_t *hand_stats);
 
+/* The plan of phase B (csrc/fseq_chainplan.hpp; debug / tests; touches no device): the fan of the recursion over the key blocks, the
+ * items of every level, and every chain launch in the order a run queues it -- up the levels, the top chain, down the levels -- with the
+ * kernel the rule gives it.  A launch: the level whose key blocks its chains walk (0: the alignment's own blocks), its kind (0 a
+ * composition from the identity, 1 the top chain, 2 an expansion), its chains, the key blocks of a chain (the last chain of a level may
+ * hold fewer), its first chain among the level's, and the workgroups of k_chain_wg it runs on -- 0: the spread kernels (k_cm_*), or,
+ * LDS-resident rows, the chain kernel of those rows. */
+typedef struct fseq_chain_launch_info {
+	uint32_t level, kind, chains, blocks, first_chain, workgroups;
+} fseq_chain_launch_info;
+#define FSEQ_DEBUG_CHAIN_LEVELS 40
+#define FSEQ_DEBUG_CHAIN_LAUNCHES 80
+typedef struct fseq_chain_plan {
+	uint32_t fan;                 /* the fan in force */
+	uint32_t fan_round5;          /* the fan before turns of workgroups were looked at (round 5's cost model on streamed rows) */
+	uint32_t turns;               /* the turns of workgroups the model counted for level 0 at `fan`; 0: it counted none */
+	uint32_t shard_k, shard_q;    /* sharded: a rank is shard_q groups of fan^shard_k blocks ... */
+	uint32_t blocks_per_rank;     /* ... = this many blocks; */
+	uint32_t n_hyper;             /* the ranks that own blocks; */
+	uint32_t b_lo, b_hi;          /* the blocks of the rank asked for */
+	uint32_t n_levels, n_launches, reserved;
+	/* one GPU: the items of level 0 .. n_levels - 1 ([0] = nblocks; the top chain takes the last).  Sharded: the rank's items of the
+	 * levels 0 .. shard_k, n_levels = shard_k + 1 */
+	uint32_t level_items[FSEQ_DEBUG_CHAIN_LEVELS];
+	fseq_chain_launch_info launches[FSEQ_DEBUG_CHAIN_LAUNCHES];
+} fseq_chain_plan;
+/* One GPU: m rows in nblocks blocks; streamed != 0: the rows take the streamed kernels (more than 11,264 rows); cus: the device's
+ * CUs; chain_wg: FSEQ_CHAIN_WG (0 the rule: a launch of at least a chain per CU goes to k_chain_wg; 1 every streamed launch; 2 none --
+ * 1 and 2 keep round 5's fan); chain_fan: FSEQ_CHAIN_FAN (0: none; a forced fan reports no turns); fit, resident: the cap on the
+ * workgroups of a launch on k_chain_wg, min(chains, fit, max(cus, 1) x max(resident, 1)) -- the workgroups whose workspaces the run's
+ * workspace holds and the workgroups a CU holds at once (fseq_debug_phase_b reports both; fit == 0: the launch takes the spread
+ * kernels).  FSEQ_E_ARG: plan NULL, m or nblocks 0, chain_wg not 0, 1 or 2, chain_fan 1. */
+int  fseq_debug_chain_plan(uint32_t m, int streamed, uint32_t nblocks, uint32_t cus, int chain_wg, uint32_t chain_fan, uint64_t fit, uint32_t resident,
+                           fseq_chain_plan *plan);
+/* A rank of a sharded run: nblocks blocks over `world` ranks at fan chain_fan (0: the 4 a sharded run takes by itself): (k, q) with
+ * the fewest serial steps among those that keep every rank busy, the blocks of rank `rank`, its items a level and its launches -- up
+ * its own range, its q composites into its hyper key block (level shard_k, one chain), the chain over the n_hyper hyper key blocks
+ * (level shard_k + 1, kind 1; every rank, also one without blocks), and down again.  fan and fan_round5 are the fan, turns is 0.
+ * FSEQ_E_ARG: plan NULL, nblocks 0, world 0 or above 4,096, rank >= world, chain_wg not 0, 1 or 2, chain_fan 1. */
+int  fseq_debug_chain_plan_sharded(uint32_t nblocks, uint32_t world, uint32_t rank, uint32_t chain_fan, int streamed, uint32_t cus, int chain_wg,
+                                   uint64_t fit, uint32_t resident, fseq_chain_plan *plan);
+/* What phase B of the last run on this context did (a sharded rank: its own): the CUs it saw, the blocks and the fan, the chain
+ * launches it queued, in order (n_launches of them), `fit` and `resident` as chain_wg_groups applied them (fseq_debug_chain_plan;
+ * both 0 on LDS-resident rows), whether the hand-over of level 0's keys to pass 2 was armed, the counters of k_chain_wg where they
+ * were kept (stats_kept: FSEQ_DEBUG was set and FSEQ_CHAIN_WG is not 2; cw_stats as fseq_debug_chain_launch_wg's stats), and of pass
+ * 2's streamed chain step the groups it ran, those that took the keys phase B handed over and those that gathered their own (all 0
+ * where the run did not go through that kernel).  FSEQ_E_ARG while the context holds no result of the long path. */
+typedef struct fseq_phase_b_info {
+	uint32_t cus, nblocks, fan, n_launches;
+	uint32_t resident, hand_armed, stats_kept, reserved;
+	uint64_t fit;
+	uint32_t p2_groups, p2_groups_took_keys, p2_groups_gathered, reserved2;
+	uint32_t cw_stats[23];
+	uint32_t reserved3;
+	fseq_chain_launch_info launches[FSEQ_DEBUG_CHAIN_LAUNCHES];
+} fseq_phase_b_info;
+int  fseq_debug_phase_b(fseq_ctx *ctx, fseq_phase_b_info *info);
+
 /* The plan of phase C on representative rows (plan_reduced, csrc/fseq_redplan.hpp) on caller-supplied counts (debug / tests; touches
  * no device).  The configurations are the library's, judged as a run of m rows in blocks of B columns at `bits` bits a symbol would
  * judge them (direct != 0: LDS-resident rows, which stage the alignment's own columns).  cnt[nblocks]: the representatives of every
