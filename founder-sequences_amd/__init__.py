@@ -224,6 +224,7 @@ EXPORTS = [
     "fseq_write_block_graph_restored", "fseq_graph_thread_rows_restored", "fseq_graph_thread_held_out_restored",
     "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys",
     "fseq_debug_chain_plan", "fseq_debug_chain_plan_sharded", "fseq_debug_phase_b",
+    "fseq_debug_class_tables",
 ]
 # ... of which include/fseq_debug.h declares these (intermediate state for tests, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fseq_debug_ranges", "fseq_debug_block_state", "fseq_debug_column_list", "fseq_debug_rmq", "fseq_debug_dp_schedule", "fseq_debug_set_tuning",
@@ -236,7 +237,7 @@ DEBUG_EXPORTS = ["fseq_debug_dp", "fseq_debug_dp_owned", "fseq_debug_clock", "fs
                  "fseq_debug_join_score_path", "fseq_debug_join_score", "fseq_debug_graph_file", "fseq_debug_local_pass",
                  "fseq_debug_graph_thread", "fseq_debug_graph_nearest_info", "fseq_debug_graph_nearest_plan", "fseq_debug_graph_nearest",
                  "fseq_debug_chain_launch_wg_keys", "fseq_debug_pass2_step_keys",
-                 "fseq_debug_chain_plan", "fseq_debug_chain_plan_sharded", "fseq_debug_phase_b"]
+                 "fseq_debug_chain_plan", "fseq_debug_chain_plan_sharded", "fseq_debug_phase_b", "fseq_debug_class_tables"]
 
 FSEQ_E_PEER = 6
 P2_RUN_CAP = 8832       # csrc/fseq_chainsort.hpp: the most runs FSEQ_P2_RUN_CAP admits (pass2_paths)
@@ -346,6 +347,7 @@ def load_library():
     L.fseq_debug_join_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_bipartite_path.argtypes = [vp, C.POINTER(C.c_int)]
     L.fseq_debug_pass2_paths.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4 + [vp]
+    L.fseq_debug_class_tables.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
     L.fseq_debug_class_columns.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64), vp, u64]
     L.fseq_debug_column_sources.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
     L.fseq_debug_red_cls_direct.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)]
@@ -1978,6 +1980,17 @@ class SegmentationContext:
         out = dict(zip(("by_runs", "by_sort", "copies", "max_runs"), (x.value for x in v)))
         out["runs_hist"] = [int(x) for x in hist]
         return out
+
+    def class_tables(self, columns):
+        """Pass 2's sweeps of the last run (on representatives) at the given ascending columns, each strictly inside a block:
+        (cls, headd, ncls) -- cls[i][r] the class of row r at columns[i], headd[i][:ncls[i]] the divergence in front of every class
+        (0xFFFFFFFF behind them)."""
+        cols = np.ascontiguousarray(columns, dtype=np.uint64)
+        cls = np.empty((len(cols), self.m), dtype=np.uint32)
+        headd = np.empty((len(cols), self.m), dtype=np.uint32)
+        ncls = np.empty(len(cols), dtype=np.uint32)
+        self._check(self.L.fseq_debug_class_tables(self.h, cols.ctypes.data, len(cols), cls.ctypes.data, headd.ctypes.data, ncls.ctypes.data))
+        return cls, headd, ncls
 
     def phase_b(self):
         """What phase B of the last run did (fseq_debug_phase_b): dict(cus, nblocks, fan, resident, fit, hand_armed, stats_kept,

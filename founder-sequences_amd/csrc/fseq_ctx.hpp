@@ -60,11 +60,18 @@ struct Stream2Config { uint32_t T, E, key_shift; size_t (*lds)(uint32_t colbytes
 struct ReducedSet {
 	uint32_t T, E, rows, values;             // rows: representatives a workgroup holds; values: distinct start values (fewer than rows: the slim configuration)
 	bool pk, ew;
-	size_t (*lds)(uint32_t B, uint32_t symcap);   // symcap: bytes of each staged-column buffer (RedArgs)
-	hipError_t (*prepare)(size_t lds);
-	// (cols: the alignment the representatives' symbols are read from -- RedArgs::direct -- and the lists; the rest comes with red)
-	void (*launch)(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &cols, RedArgs const &red);
-	uint32_t (*resident)(size_t lds);
+	size_t (*lds)(uint32_t B, uint32_t symcap);   // symcap: bytes of each staged-column buffer (RedArgs).  Phase C's form: what planning counts with
+	// [r16] pass 2's sweep form (k_columns_red<.., SW>: no value table, no id histogram) asks for less.  A configuration has the forms
+	// the plan can send it: phase C's with a list wave or at most 128 threads, the sweep form without a list wave
+	size_t (*lds_sweep)(uint32_t B, uint32_t symcap);
+	// sweep: the form asked for (an error where the configuration does not have it)
+	hipError_t (*prepare)(size_t lds, bool sweep);
+	// (cols: the alignment the representatives' symbols are read from -- RedArgs::direct -- and the lists; the rest comes with red:
+	// the sweep form where red.cls is set)
+	// hipErrorInvalidDeviceFunction, and nothing launched, for a form the configuration does not have
+	hipError_t (*launch)(hipStream_t st, uint32_t grid, size_t lds, ColumnsArgs const &cols, RedArgs const &red);
+	uint32_t (*resident)(size_t lds);          // (of phase C's form where the configuration has it, else of the sweep form: see LaunchRed)
+	bool phase_form() const { return T <= 128u || ew; }
 };
 // the smallest configuration that holds `rows` representatives (index into the list; -1: none)
 int reduced_config_count();
@@ -136,6 +143,7 @@ struct Tuning {
 	int  reduced_margin = -1;            // FSEQ_REDUCED_MARGIN: counts beyond the list capacity the choice of vmin allows for (tests: 0 makes lists dig below it)
 	bool reduced_always = false;         // FSEQ_REDUCED_ALWAYS: the representatives whenever some block has fewer of them than rows (tests of the mixed runs)
 	bool reduced_msa_gather = false;     // FSEQ_REDUCED_MSA_GATHER: the reduced alignment by gathers from memory (by itself: the column through LDS where it fits)
+	int  red_ss_stride = 0;              // FSEQ_RED_SS_STRIDE: columns between the reduced states phase C drops for pass 2's sweeps (a power of two, 4..64; by itself: 16 streamed, 8 LDS-resident)
 	int  reduced_cap = 0;                // FSEQ_REDUCED_CAP: most representatives a block may have (tests: small values send blocks to the run on all rows)
 	bool class_gather = false;           // FSEQ_CLASS_GATHER: the class columns are gathered into the reduced alignment for every block (the form before the column kernel staged them itself)
 	int  class_columns = 1;              // FSEQ_CLASS_COLUMNS=0: the reduced alignment is gathered from the alignment (a second read of it: the form before phase A wrote class columns)
@@ -196,6 +204,7 @@ struct Tuning {
 			{"FSEQ_REDUCED_ALWAYS", &Tuning::reduced_always, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_MSA_GATHER", &Tuning::reduced_msa_gather, nullptr, 0, 0, nullptr},
 			{"FSEQ_REDUCED_CAP", nullptr, &Tuning::reduced_cap, 1, 0, nullptr},
+			{"FSEQ_RED_SS_STRIDE", nullptr, &Tuning::red_ss_stride, 4, 0, nullptr},
 			{"FSEQ_P2_RUN_CAP", nullptr, &Tuning::p2_run_cap, 0, -1, nullptr},
 			{"FSEQ_CHAIN_RUN_CAP", nullptr, &Tuning::chain_run_cap, 0, -1, nullptr},
 			{"FSEQ_CHAIN_WG", nullptr, &Tuning::chain_wg, 0, 0, nullptr},
@@ -483,7 +492,7 @@ struct fseq_ctx {
 	DevBuf<uint32_t> d_red_p2grp;            // streamed pass 2: its groups {first task, count}, the counter they are taken by and the kernel's counters
 	uint32_t p2_stats[fseq::P2_STATS]{};                // ... of the last run (fseq_debug_pass2_paths): tasks by runs, tasks by the sort of all rows, border copies, most runs, tasks by run count
 	bool p2_stats_have = false;              // the last run went through that kernel
-	DevBuf<uint32_t> d_red_ss_a, d_red_ss_d; // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap])
+	DevBuf<uint16_t> d_red_ss_a, d_red_ss_d; // the reduced states phase C drops every red_ss_stride columns ([q][red_ss_cap] halfwords: RedArgs)
 	uint32_t red_ss_stride = 0, red_ss_cap = 0;
 	uint32_t *h_red_pin = nullptr;           // pinned host staging of a planning's two copies (counts back, red.plan.blocks out): nothing reads it afterwards
 	size_t red_pin_words = 0;

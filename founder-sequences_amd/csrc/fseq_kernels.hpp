@@ -782,7 +782,12 @@ __device__ __forceinline__ void bitonic_sort_lds(uint32_t *sb, uint32_t N2)
 // workgroup emits, instead of lists, the class tables at its task columns: the class of every block key (rank among the
 // distinct key prefixes up to that column) and the divergence in front of every class -- what one chain step from the
 // block's boundary state needs (k_chain_snap).
-template <int T, int E, int SIGMA, bool PK, bool EW, bool DENSE, bool RED>
+// SWEEP [r16] (RED only): pass 2's form, compiled apart from phase C's -- no lists, so no value table and no id histogram.  A sweep
+// needs of a divergence its order under max, the test "inside the block" (v > kblk) and, where that holds, the value itself for
+// headd: the monotone map v <= kblk -> 0, v > kblk -> v - kblk keeps all three, so the ids ARE the columns into the block.  A
+// sweep from column k0 sets D0 = k0 - kblk + 1: the partition step's new id D0 + j is column k0 + j + 1 under the same map.
+// The reduced stride states hold exactly these ids (below); a sweep from the block's first column starts from zeros.
+template <int T, int E, int SIGMA, bool PK, bool EW, bool DENSE, bool RED, bool SWEEP = false>
 __device__ __forceinline__ void columns_body(char *smem,
 	uint8_t const *__restrict__ msa, size_t ld, uint32_t m, uint64_t n, uint32_t B, uint32_t N2,
 	uint32_t const *__restrict__ bstate_a, uint32_t const *__restrict__ bstate_d,
@@ -796,9 +801,9 @@ __device__ __forceinline__ void columns_body(char *smem,
 	FSEQ_CLOCK_STAMP(blockIdx.x, 0);
 	constexpr uint32_t CAP = T * E, VCAP = (uint32_t) columns_value_cap(T, E, PK);
 	static_assert(VCAP == CAP || RED, "a value table smaller than the rows: the reduced kernel, which can refuse a block");
+	static_assert(!SWEEP || (RED && !EW && !DENSE), "the sweep form: representatives, no list wave");
 	uint32_t const blk = RED ? red.blocks[blockIdx.x] : (blocklist ? blocklist[blockIdx.x] : blockIdx.x + block0);
 	uint32_t red_vmin = 0, red_deficit = 0, t_first = 0, t_count = 0, t_next = 0;
-	bool const red_snap = RED && red.cls != nullptr;
 	if constexpr (RED)
 	{
 		m = red.cnt[blk];
@@ -806,7 +811,7 @@ __device__ __forceinline__ void columns_body(char *smem,
 		red_vmin = red.vmin[blk];
 		red_deficit = red.m_true - m;
 		N2 = 2; while (N2 < m + 1u) N2 <<= 1;
-		if (red_snap) { t_first = red.wg_tasks[3u * blockIdx.x]; t_count = red.wg_tasks[3u * blockIdx.x + 1u]; }
+		if constexpr (SWEEP) { t_first = red.wg_tasks[3u * blockIdx.x]; t_count = red.wg_tasks[3u * blockIdx.x + 1u]; }
 	}
 	bool const red_exact = RED && red_vmin <= 1u;
 	// [r10] this block's columns are phase A's class columns and the ids of its order block-key ranks (RedArgs; wave-uniform)
@@ -819,14 +824,15 @@ __device__ __forceinline__ void columns_body(char *smem,
 		if (red_cls) red_nkeys = __builtin_amdgcn_readfirstlane(red.nkeys[blk]);
 	}
 	// [a_l][d_l][sym0][sym1][cnt_l] are contiguous: the prologue's sort buffer (N2 < 2m words) overlays them
+	// (the sweep form has neither cnt_l nor V_l)
 	using AT = std::conditional_t<PK, uint16_t, uint32_t>;     // row ids < m, value ids < m + B
 	Carver cv{smem};
 	AT *a_l = cv.take<AT>(CAP);
 	AT *d_l = cv.take<AT>(CAP);
 	uint8_t *sym0 = cv.take<uint8_t>(RED ? red.symcap : CAP);
 	uint8_t *sym1 = cv.take<uint8_t>(RED ? red.symcap : CAP);
-	uint32_t *cnt_l = cv.take<uint32_t>(PK ? (VCAP + B + 9) / 2 : VCAP + B + 8);
-	uint32_t *V_l = cv.take<uint32_t>(VCAP);
+	uint32_t *cnt_l = SWEEP ? nullptr : cv.take<uint32_t>(PK ? (VCAP + B + 9) / 2 : VCAP + B + 8);
+	uint32_t *V_l = SWEEP ? nullptr : cv.take<uint32_t>(VCAP);
 	StepScratch<T, SIGMA> &scr = *cv.take<StepScratch<T, SIGMA>>(1);
 	uint32_t *sscr = cv.take<uint32_t>(T / WAVE + 1);
 	constexpr bool PW = columns_pairwise(T, E, SIGMA, PK);
@@ -838,30 +844,54 @@ __device__ __forceinline__ void columns_body(char *smem,
 	bool const rows = !EW || tid >= 64u;
 	// (pass 2 on the representatives: the sweep starts at the block's first column or at one of the states phase C dropped)
 	uint64_t const kblk = (uint64_t) blk * B;
-	uint64_t const k0 = red_snap ? (uint64_t) red.wg_tasks[3u * blockIdx.x + 2u] : kblk;
-	uint64_t const kend = red_snap ? (uint64_t) red.task_rb[t_first + t_count - 1u] : ((k0 + B < n) ? k0 + B : n);
+	uint64_t const k0 = SWEEP ? (uint64_t) red.wg_tasks[3u * blockIdx.x + 2u] : kblk;
+	uint64_t const kend = SWEEP ? (uint64_t) red.task_rb[t_first + t_count - 1u] : ((k0 + B < n) ? k0 + B : n);
 	uint32_t const nb = (uint32_t) (kend - k0);
 
 	// ---- prologue
+#ifdef FSEQ_KC_STAMPS
+	// [r16] a reduced workgroup's sections: start, state loaded, value table built, ids and histogram done, columns done; kc_tab: the class tables
+	long long kc_p[5], kc_tab = 0, kc_tab0 = 0;
+	kc_p[0] = clock64();
+#endif
 	// boundary state straight into registers (chunk ownership: positions tid*E .. tid*E+E-1)
+	// (the sweep form: d[] holds ids from the start -- a reduced stride state's, or zeros at the block's first column, where every
+	// divergence is <= kblk and red.d is not read)
 	uint32_t a[E], d[E];
+	if (SWEEP && k0 != kblk)
 	{
-		bool const from_ss = RED && k0 != kblk;
-		size_t const ob = from_ss ? (size_t) (k0 / red.ss_stride) * red.ss_cap : RED ? (size_t) blk * red.cap : (size_t) blk * m;
-		uint32_t const *const sa = from_ss ? red.ss_a : RED ? red.a : bstate_a, *const sd = from_ss ? red.ss_d : RED ? red.d : bstate_d;
+		size_t const ob = (size_t) (k0 / red.ss_stride) * red.ss_cap;
+#pragma unroll
+		for (int e = 0; e < E; ++e)
+		{
+			uint32_t const pos = p0 + e;
+			a[e] = pos < m ? (uint32_t) red.ss_a[ob + pos] : 0u;
+			d[e] = pos < m ? (uint32_t) red.ss_d[ob + pos] : 0u;
+		}
+	}
+	else
+	{
+		size_t const ob = RED ? (size_t) blk * red.cap : (size_t) blk * m;
+		uint32_t const *const sa = RED ? red.a : bstate_a, *const sd = RED ? red.d : bstate_d;
 #pragma unroll
 		for (int e = 0; e < E; ++e)
 		{
 			uint32_t const pos = p0 + e;
 			a[e] = pos < m ? sa[ob + pos] : 0u;
-			d[e] = pos < m ? sd[ob + pos] : 0u;
+			d[e] = (!SWEEP && pos < m) ? sd[ob + pos] : 0u;
 		}
 	}
 
+#ifdef FSEQ_KC_STAMPS
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the stamp build waits for the state here: its loads would land in the next section)
+	kc_p[1] = clock64();
+#endif
 	// ---- sorted distinct divergence values -> V_l[0..D0)
 	uint32_t *sb = reinterpret_cast<uint32_t *>(a_l);   // N2 < 2m words, overlays a_l .. cnt_l
-	uint32_t D0 = 0;
+	uint32_t D0 = SWEEP ? (uint32_t) (k0 - kblk) + 1u : 0u;
 	bool have_values = false;
+	if constexpr (!SWEEP)
+	{
 	if constexpr (RED)
 	{
 		// [r5] the distinct values first, by hashing, then the sort of THOSE: a block's representatives hold a few thousand rows
@@ -961,14 +991,18 @@ __device__ __forceinline__ void columns_body(char *smem,
 	__syncthreads();                          // the sort buffer (overlaying cnt_l) is dead from here
 	for (uint32_t i = tid; i < (PK ? (D0 + nb + 9u) / 2u : D0 + nb + 8u); i += T) cnt_l[i] = 0;     // (+8: the list reads aligned groups of ids)
 	__syncthreads();
+	}
 
+#ifdef FSEQ_KC_STAMPS
+	kc_p[2] = clock64();
+#endif
 	// ---- ids + initial histogram
 	uint32_t id[E];
 #pragma unroll
 	for (int e = 0; e < E; ++e)
 	{
-		id[e] = 0;
-		if (p0 + e < m)
+		id[e] = SWEEP ? d[e] : 0u;
+		if (!SWEEP && p0 + e < m)
 		{
 			uint32_t lo = 0, hi = D0;
 			uint32_t const key = d[e];
@@ -1020,11 +1054,12 @@ __device__ __forceinline__ void columns_body(char *smem,
 	}
 	__syncthreads();
 
-	bool const zero_present = (V_l[0] == 0u);
+	bool const zero_present = !SWEEP && (V_l[0] == 0u);
 	// (see the pass loop; compiled into the nine-to-eleven-row kernels only -- the 512-thread 16-bit kernels, the slim one among them, have no register to spare)
 	constexpr bool CARRY_OK = PK && E >= 9 && !columns_slim(T, E, PK);
 	bool const carry = CARRY_OK && npass == 2u && bsh == 1u && ((RED && red.direct) ? red.m_true : red_cls ? red_nkeys : m) <= 16384u;      // (the ids: rows of the alignment, key ranks, representatives)
 #ifdef FSEQ_KC_STAMPS
+	kc_p[3] = clock64();
 	long long kc_work = 0, kc_wait = 0, kc_last = clock64();
 	KcStamps kcs{{0, 0, 0, 0, 0, 0, 0, 0}, clock64()};
 #endif
@@ -1112,7 +1147,7 @@ __device__ __forceinline__ void columns_body(char *smem,
 				{
 					a_l[dst[e]] = (AT) (CARRY_OK ? (a[e] | (hi[CARRY_OK ? e : 0] << 14)) : a[e]);
 					d_l[dst[e]] = (AT) dnew[e];
-					if (dnew[e] != d[e])
+					if (!SWEEP && dnew[e] != d[e])
 					{
 						cnt_dec<PK>(cnt_l, d[e]);
 						cnt_inc<PK>(cnt_l, dnew[e]);
@@ -1133,7 +1168,8 @@ __device__ __forceinline__ void columns_body(char *smem,
 		}
 
 		// ---- every snap_stride columns: drop the exact (a, d) for pass 2 (ids back to divergence values)
-		if (ss_a && (k0 + j + 1) % snap_stride == 0)
+		// (the run on all rows only: the reduced forms drop their own states below, and the sweep form has no V_l)
+		if constexpr (!RED) if (ss_a && (k0 + j + 1) % snap_stride == 0)
 		{
 			size_t const ob = (size_t) ((k0 + j + 1) / snap_stride) * m;
 #pragma unroll
@@ -1153,32 +1189,51 @@ __device__ __forceinline__ void columns_body(char *smem,
 		}
 
 		// ---- [r5] the reduced state every ss_stride columns (the columns strictly inside the block): pass 2's sweeps start there
-		if (RED && !red_snap && red.ss_a && (k0 + j + 1u) % red.ss_stride == 0u && j + 1u < nb)
+		// [r16] as two 16-bit arrays, one format whatever configuration writes or reads it: a_l as it stands (row ids, representative
+		// indices and key ranks are below 65,536) and the divergences as columns into the block -- at the block's first column every
+		// divergence is <= kblk, so every id below D0 is "outside" (0) and every other id is vid - D0 + 1.  Eight positions a piece:
+		// 16 bytes of each array (ss_cap is a multiple of 64: a state is 128-byte aligned; the pieces past m are padding)
+		if constexpr (RED && !SWEEP)
 		{
-			size_t const ob = (size_t) ((k0 + j + 1u) / red.ss_stride) * red.ss_cap;
-			for (uint32_t idx = tid; idx < m; idx += T)
+			if (red.ss_a && (k0 + j + 1u) % red.ss_stride == 0u && j + 1u < nb)
 			{
-				uint32_t const vid = d_l[idx];
-				red.ss_a[ob + idx] = a_l[idx];
-				red.ss_d[ob + idx] = vid < D0 ? V_l[vid] : (uint32_t) (k0 + (vid - D0) + 1u);
+				size_t const ob = (size_t) ((k0 + j + 1u) / red.ss_stride) * red.ss_cap;
+				auto into = [&](uint32_t vid) { return vid < D0 ? 0u : vid - D0 + 1u; };
+				for (uint32_t idx = tid * 8u; idx < m; idx += (uint32_t) T * 8u)
+				{
+					uint4 aw, dw;
+					if constexpr (PK)
+					{
+						aw = *reinterpret_cast<uint4 const *>(a_l + idx);
+						uint4 const w = *reinterpret_cast<uint4 const *>(d_l + idx);
+						dw.x = into(w.x & 0xFFFFu) | (into(w.x >> 16) << 16); dw.y = into(w.y & 0xFFFFu) | (into(w.y >> 16) << 16);
+						dw.z = into(w.z & 0xFFFFu) | (into(w.z >> 16) << 16); dw.w = into(w.w & 0xFFFFu) | (into(w.w >> 16) << 16);
+					}
+					else
+					{
+						uint4 const a0 = *reinterpret_cast<uint4 const *>(a_l + idx), a1 = *reinterpret_cast<uint4 const *>(a_l + idx + 4u);
+						uint4 const d0 = *reinterpret_cast<uint4 const *>(d_l + idx), d1 = *reinterpret_cast<uint4 const *>(d_l + idx + 4u);
+						aw = make_uint4(a0.x | (a0.y << 16), a0.z | (a0.w << 16), a1.x | (a1.y << 16), a1.z | (a1.w << 16));
+						dw = make_uint4(into(d0.x) | (into(d0.y) << 16), into(d0.z) | (into(d0.w) << 16), into(d1.x) | (into(d1.y) << 16), into(d1.z) | (into(d1.w) << 16));
+					}
+					*reinterpret_cast<uint4 *>(red.ss_a + ob + idx) = aw;
+					*reinterpret_cast<uint4 *>(red.ss_d + ob + idx) = dw;
+				}
 			}
 		}
 		// ---- [r5] pass 2 on the representatives: the class tables at a task column.  A position starts a class iff its
 		// divergence lies inside the block (> the block's first column); the class of a block key is the class of any
 		// representative that carries it.
-		if (RED && red_snap)
+		if constexpr (SWEEP)
 		{
 			if (t_next < t_count && red.task_rb[t_first + t_next] == k0 + j + 1u)
 			{
 				uint32_t const task = t_first + t_next;
-				// (ids of this sweep's own columns are inside the block; of its start values those that are -- V_l ascends -- from id_in on)
-				uint32_t id_in = D0;
-				if (k0 != kblk)
-				{
-					uint32_t lo = 0, hi = D0;
-					while (lo < hi) { uint32_t const mid = (lo + hi) >> 1; if (V_l[mid] <= (uint32_t) kblk) lo = mid + 1; else hi = mid; }
-					id_in = lo;
-				}
+#ifdef FSEQ_KC_STAMPS
+				kc_tab0 = clock64();
+#endif
+				// (an id is the column into the block: inside it from 1 on)
+				constexpr uint32_t id_in = 1u;
 				uint32_t nf = 0;
 				if (rows)
 				{
@@ -1204,14 +1259,16 @@ __device__ __forceinline__ void columns_body(char *smem,
 							uint32_t lf = a_l[pos];
 							if (!red_cls) lf = key_of[lf];
 							red.cls[ot + lf] = r - 1u;
-							if (first) red.headd[ot + r - 1u] = vid < D0 ? V_l[vid] : (uint32_t) (k0 + (vid - D0) + 1u);
+							if (first) red.headd[ot + r - 1u] = (uint32_t) kblk + vid;
 						}
 					}
 				}
 				if (tid == 0) red.ncls[task] = total;
 				++t_next;
+#ifdef FSEQ_KC_STAMPS
+				kc_tab += clock64() - kc_tab0;
+#endif
 			}
-			continue;
 		}
 
 		// ---- emit the top of the histogram for column k0+j (wave 0; the others run ahead into
@@ -1220,7 +1277,7 @@ __device__ __forceinline__ void columns_body(char *smem,
 		// cut bound (lp.cc:444-445), so only their total count matters.  Then the distinct values
 		// below thr, descending, until their cumulative count exceeds X (every DP cell is >= the lump's
 		// count, so the list always reaches X counts past the smallest value the cell can take).
-		if (wave_id() == 0)
+		else if (wave_id() == 0)
 		{
 			// The list is one wave's serial chain (LDS reads -> scan -> ballots -> stores) on every column's critical
 			// path: issue priority over the other waves of the SIMD, and four ids per lane (256 per step) -- the id
@@ -1367,6 +1424,10 @@ __device__ __forceinline__ void columns_body(char *smem,
 		}
 	}
 #ifdef FSEQ_KC_STAMPS
+	kc_p[4] = clock64();
+	if (RED && tid == 0 && (blockIdx.x == 100 || blockIdx.x == 1000))
+		printf("kc stamps reduced workgroup %u (%d x %d, %u rows, %u columns from column %llu, %u tasks): state load %lld, value table %lld, ids and histogram %lld, column loop %lld cycles, of which class tables %lld\n",
+		       blockIdx.x, T, E, m, nb, (unsigned long long) k0, t_count, kc_p[1] - kc_p[0], kc_p[2] - kc_p[1], kc_p[3] - kc_p[2], kc_p[4] - kc_p[3], kc_tab);
 	if (lane_id() == 0 && (blockIdx.x == 100 || blockIdx.x == 3000))
 		printf("kc stamps block %u wave %u: work %lld wait %lld cycles per column (%u columns); step: to barrier 1 %lld, wait %lld, between %lld, wait 1b %lld\n",
 		       blockIdx.x, wave_id(), kc_work / nb, kc_wait / nb, nb, kcs.acc[0] / nb, kcs.acc[1] / nb, kcs.acc[2] / nb, kcs.acc[3] / nb);
@@ -1392,13 +1453,14 @@ __global__ __launch_bounds__(T, (PK && T == 512) ? 6 : 4) void k_columns(
 }
 
 // [r5] the same on a block's representative rows (msa / ld: the reduced alignment; red: fseq_types.hpp)
-template <int T, int E, int SIGMA, bool PK, bool EW = false>
+// SW [r16]: pass 2's sweep form (columns_body; the launcher takes it where red.cls is set)
+template <int T, int E, int SIGMA, bool PK, bool EW = false, bool SW = false>
 __global__ __launch_bounds__(T, columns_min_waves(T, E, PK)) void k_columns_red(
 	uint8_t const *__restrict__ msa, size_t ld, uint64_t n, uint32_t B,
 	uint32_t L, uint32_t X, uint32_t stride, uint2 *__restrict__ ent, uint4 *__restrict__ hdr, uint32_t npass, uint32_t bsh, RedArgs const red)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	columns_body<T, E, SIGMA, PK, EW, false, true>(smem, msa, ld, 0u, n, B, 0u, nullptr, nullptr, L, X, stride, ent, hdr, npass, bsh, 0u, nullptr, nullptr, 0u,
+	columns_body<T, E, SIGMA, PK, EW, false, true, SW>(smem, msa, ld, 0u, n, B, 0u, nullptr, nullptr, L, X, stride, ent, hdr, npass, bsh, 0u, nullptr, nullptr, 0u,
 	                                                nullptr, 0u, nullptr, red);
 }
 

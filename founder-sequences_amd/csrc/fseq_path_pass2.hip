@@ -27,6 +27,46 @@ int pass2_sum_cells(fseq_ctx *c, LongRun &R, hipStream_t st)
 	return FSEQ_OK;
 }
 
+// ---- the sweeps' tasks (long_pass2_reduced below and fseq_debug_class_tables): a workgroup sweeps the tasks of one block that share a
+// start column, on the configuration the plan sweeps the block with
+struct SweepWg { uint32_t blk, first, count, start; };
+
+// task i, column rb strictly inside block blk: onto the last workgroup of its configuration or a new one (the tasks come in ascending
+// columns).  false: no configuration sweeps the block (it has no representatives)
+bool sweep_add_task(fseq_ctx const *c, std::vector<std::vector<SweepWg>> &wgs, uint32_t blk, uint64_t rb, uint32_t i)
+{
+	RedPlan const &plan = c->red.plan;
+	int const cf = blk < plan.config_snap_of.size() ? plan.config_snap_of[blk] : -1;
+	if (cf < 0 || plan.cnt[blk] == RED_NONE) return false;
+	// the sweep starts at the last state phase C dropped in front of the boundary (or at the block's first column)
+	uint64_t start = c->red_ss_stride ? (rb - 1u) / c->red_ss_stride * c->red_ss_stride : 0u;
+	// (a block that ran on all rows dropped none)
+	if (start <= (uint64_t) blk * c->B || plan.full[blk]) start = (uint64_t) blk * c->B;
+	auto &v = wgs[(size_t) cf];
+	if (!v.empty() && v.back().blk == blk && v.back().start == (uint32_t) start) ++v.back().count;
+	else v.push_back(SweepWg{blk, i, 1u, (uint32_t) start});
+	return true;
+}
+
+// the launches of the configurations in use and what their workgroups read: hb[w] the block, hw[3 w ..] {first task, tasks, start column}
+void sweep_launch_lists(std::vector<std::vector<SweepWg>> const &wgs, std::vector<RedLaunch> &ls, std::vector<uint32_t> &hb, std::vector<uint32_t> &hw)
+{
+	for (size_t cf = 0; cf < wgs.size(); ++cf)
+	{
+		if (wgs[cf].empty()) continue;
+		ls.push_back(RedLaunch{(int) cf, (uint32_t) hb.size(), (uint32_t) wgs[cf].size()});
+		for (auto const &w : wgs[cf]) { hb.push_back(w.blk); hw.push_back(w.first); hw.push_back(w.count); hw.push_back(w.start); }
+	}
+}
+
+// the class tables at the task columns, configuration by configuration (RA: the tasks and the tables set by the caller)
+int sweep_class_tables(fseq_ctx *c, std::vector<RedLaunch> ls, RedArgs const &RA)
+{
+	if (ls.empty()) return FSEQ_OK;
+	std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
+	return red_launch_all(c, ls, RA, ListArgs{(uint32_t) c->p.segment_length});       // (no lists: the segment length alone)
+}
+
 // ---- [r5] pass 2 behind the reduced phase C: a boundary inside a block is ONE chain step from the block's boundary state
 // (k_chain_snap), keyed by the classes the block's representatives form at that column (k_columns_red with the class
 // tables as its output); a boundary on a block border is that border's state.  Blocks without representatives (more than a
@@ -48,8 +88,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	std::vector<uint64_t> rbs;
 	std::vector<uint32_t> task_blk, ncls0;
 	// tasks of reduced blocks by configuration: workgroups {block, first task, count, start column}; tasks of the other blocks: old groups
-	struct Wg { uint32_t blk, first, count, start; };
-	std::vector<std::vector<Wg>> wgs((size_t) reduced_config_count());
+	std::vector<std::vector<SweepWg>> wgs((size_t) reduced_config_count());
 	std::vector<uint64_t> o_rbs, o_srcs;
 	std::vector<uint2> o_grp;
 	std::vector<uint32_t> o_slot;
@@ -70,18 +109,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 		task_blk.push_back(blk);
 		ncls0.push_back(0u);                                       // a border: the copy; else the sweep fills it in
 		if (border) continue;
-		int const cf = blk < plan.config_snap_of.size() ? plan.config_snap_of[blk] : -1;
-		if (cf >= 0 && plan.cnt[blk] != RED_NONE)
-		{
-			// the sweep starts at the last state phase C dropped in front of the boundary (or at the block's first column)
-			uint64_t start = c->red_ss_stride ? (rb - 1u) / c->red_ss_stride * c->red_ss_stride : 0u;
-			// (a block that ran on all rows dropped none)
-			if (start <= (uint64_t) blk * c->B || plan.full[blk]) start = (uint64_t) blk * c->B;
-			auto &v = wgs[(size_t) cf];
-			if (!v.empty() && v.back().blk == blk && v.back().start == (uint32_t) start) ++v.back().count;
-			else v.push_back(Wg{blk, (uint32_t) i, 1u, (uint32_t) start});
-		}
-		else
+		if (!sweep_add_task(c, wgs, blk, rb, (uint32_t) i))
 		{
 			ncls0[i] = 0xFFFFFFFFu;                                // not this kernel's
 			if (!o_srcs.empty() && o_srcs.back() == blk) ++o_grp.back().y;
@@ -127,15 +155,11 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	// the task lists through pinned memory of their own (live until the synchronisation behind the kernels)
 	std::vector<uint32_t> hb, hw;
 	std::vector<RedLaunch> ls;
+	sweep_launch_lists(wgs, ls, hb, hw);
 	for (size_t cf = 0; cf < wgs.size(); ++cf)
 	{
 		if (wgs[cf].empty()) continue;
-		ls.push_back(RedLaunch{(int) cf, (uint32_t) hb.size(), (uint32_t) wgs[cf].size()});
-		for (auto const &w : wgs[cf])
-		{
-			hb.push_back(w.blk); hw.push_back(w.first); hw.push_back(w.count); hw.push_back(w.start);
-			cells += (rbs[w.first + w.count - 1u] - (uint64_t) w.start) * plan.cnt[w.blk];
-		}
+		for (auto const &w : wgs[cf]) cells += (rbs[w.first + w.count - 1u] - (uint64_t) w.start) * plan.cnt[w.blk];
 		if (c->tune.debug)
 		{
 			// (worded like red_plan's report of phase C; a workgroup sweeps one block's tasks that share a start column)
@@ -180,11 +204,7 @@ int long_pass2_reduced(fseq_ctx *c, LongRun &R)
 	RA.task_rb = c->d_cols.as<unsigned long long const>();
 	RA.cls = c->d_red_cls; RA.headd = c->d_red_headd; RA.ncls = c->d_red_ncls;
 	RA.blocks = c->d_red_wgtasks + 3 * S2; RA.wg_tasks = c->d_red_wgtasks;
-	if (!ls.empty())
-	{
-		std::stable_sort(ls.begin(), ls.end(), [](RedLaunch const &x, RedLaunch const &y) { return x.count > y.count; });
-		if ((rc = red_launch_all(c, ls, RA, ListArgs{(uint32_t) L}))) return rc;       // (no lists: the segment length alone)
-	}
+	if ((rc = sweep_class_tables(c, ls, RA))) return rc;
 	// the states at my boundaries, from the blocks' boundary states
 	SnapArgs tasks;
 	tasks.A = msa_args(c);
@@ -368,3 +388,63 @@ int long_pass2(fseq_ctx *c, LongRun &R)
 }
 
 } // namespace fseq
+
+using namespace fseq;
+
+extern "C" {
+
+// pass 2's sweeps at caller-chosen columns of the last run (include/fseq_debug.h): the same task construction and launches as
+// long_pass2_reduced, on buffers of this call's own
+int fseq_debug_class_tables(fseq_ctx *c, uint64_t const *columns, uint32_t count, uint32_t *cls, uint32_t *headd, uint32_t *ncls)
+{
+	if (!c || !columns || !count || !cls || !headd || !ncls) return FSEQ_E_ARG;
+	if (int const rc0 = need_result(c, true)) return rc0;
+	if (!c->red_active || c->sh.on) return fail(c, FSEQ_E_UNSUPPORTED, "class tables: the last run did not go through the representatives on one rank");
+	FSEQ_LONG_LOCALS(c);
+	(void) hipSetDevice(p.device);
+	uint32_t const cap = c->red_cap;
+	std::vector<std::vector<SweepWg>> wgs((size_t) reduced_config_count());
+	std::vector<uint32_t> task_blk(count);
+	for (uint32_t i = 0; i < count; ++i)
+	{
+		uint64_t const rb = columns[i];
+		if (rb == 0 || rb >= n || rb % c->B == 0 || (i && rb <= columns[i - 1])) return fail(c, FSEQ_E_ARG, "class tables: ascending columns strictly inside blocks");
+		task_blk[i] = (uint32_t) (rb / c->B);
+		if (!sweep_add_task(c, wgs, task_blk[i], rb, i)) return fail(c, FSEQ_E_UNSUPPORTED, "class tables: a column of a block without representatives");
+	}
+	std::vector<RedLaunch> ls;
+	std::vector<uint32_t> hb, hw;
+	sweep_launch_lists(wgs, ls, hb, hw);
+	DevTemp<uint64_t> d_rb(c);
+	DevTemp<uint32_t> d_wg(c), d_blk(c), d_cls(c), d_headd(c), d_ncls(c);
+	if ((rc = d_rb.alloc(count)) || (rc = d_wg.alloc(hw.size())) || (rc = d_blk.alloc(hb.size())) || (rc = d_cls.alloc((size_t) count * cap)) ||
+	    (rc = d_headd.alloc((size_t) count * cap)) || (rc = d_ncls.alloc(count))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(d_rb, columns, (size_t) count * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(d_wg, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(d_blk, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemsetAsync(d_cls, 0xFF, (size_t) count * cap * 4, st));
+	HIP_TRY(c, hipMemsetAsync(d_headd, 0xFF, (size_t) count * cap * 4, st));
+	HIP_TRY(c, hipMemsetAsync(d_ncls, 0, (size_t) count * 4, st));
+	HIP_TRY(c, hipStreamSynchronize(st));                         // (the lists are pageable memory of this call)
+	RedArgs RA;
+	red_fill_args(c, RA);
+	RA.task_rb = d_rb.as<unsigned long long const>();
+	RA.cls = d_cls; RA.headd = d_headd; RA.ncls = d_ncls;
+	RA.blocks = d_blk; RA.wg_tasks = d_wg;
+	if ((rc = sweep_class_tables(c, ls, RA))) return rc;
+	HIP_TRY(c, hipStreamSynchronize(st));
+	// by rows: the class of a row is the class of its block key (phase A's rank of the row in the block)
+	std::vector<uint32_t> tab(cap), hd(cap), rank(m);
+	HIP_TRY(c, hipMemcpy(ncls, d_ncls, (size_t) count * 4, hipMemcpyDeviceToHost));
+	for (uint32_t i = 0; i < count; ++i)
+	{
+		if (i == 0 || task_blk[i] != task_blk[i - 1]) HIP_TRY(c, hipMemcpy(rank.data(), c->d_rank + (size_t) task_blk[i] * m, (size_t) m * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(c, hipMemcpy(tab.data(), d_cls + (size_t) i * cap, (size_t) cap * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(c, hipMemcpy(hd.data(), d_headd + (size_t) i * cap, (size_t) cap * 4, hipMemcpyDeviceToHost));
+		for (uint32_t r = 0; r < m; ++r) cls[(size_t) i * m + r] = rank[r] < cap ? tab[rank[r]] : 0xFFFFFFFFu;
+		for (uint32_t r = 0; r < m; ++r) headd[(size_t) i * m + r] = r < cap ? hd[r] : 0xFFFFFFFFu;
+	}
+	return FSEQ_OK;
+}
+
+} // extern "C"

@@ -37,7 +37,7 @@ std::vector<RedConfig> red_configs(uint32_t m, uint32_t B, uint32_t bsh, bool di
 		{
 			size_t const lds_rows = rs.lds(B, red_symcap(m, bsh, rs, false)), lds_cls = rs.lds(B, red_symcap(m, bsh, rs, false, cls_ld));
 			if (lds_cls == lds_rows) f.cls = true;
-			else if (lds_cls <= LDS_LIMIT && rs.prepare(lds_cls) == hipSuccess)
+			else if (lds_cls <= LDS_LIMIT && rs.prepare(lds_cls, !rs.phase_form()) == hipSuccess)
 				f.cls = red_cls_direct(lds_cls, LDS_LIMIT, rs.resident(lds_rows), rs.resident(lds_cls));
 		}
 		out.push_back(f);
@@ -232,7 +232,7 @@ void red_report(fseq_ctx const *c, RedPlan const &P)
 		(void) reduced_config(bin.config, &rs);
 		bool const cls = red_config_cls(c, bin.config);
 		size_t const lds = rs.lds(c->B, red_symcap(m, c->bsh, rs, c->red_direct, cls ? c->cls_ld : 0));
-		uint32_t const res = rs.prepare(lds) == hipSuccess ? rs.resident(lds) : 0u;
+		uint32_t const res = rs.prepare(lds, !rs.phase_form()) == hipSuccess ? rs.resident(lds) : 0u;
 		uint32_t staged = 0;
 		for (uint32_t i = 0; i < bin.count; ++i) staged += P.from_cls[P.blocks[bin.first + i]];
 		fprintf(stderr, "[fseq]   configuration of %u rows: %zu blocks, %llu representatives on average (%u threads x %u rows, %u distinct values, %zu bytes of LDS, %u workgroups per CU); columns: %s (%u of its blocks)\n",
@@ -249,13 +249,15 @@ int red_size_buffers(fseq_ctx *c)
 	uint32_t const max_rows = c->red.plan.max_rows;
 	// (the reduced alignment: red_reduce_msa, where a listed block reads it)
 	{
-		// the reduced states for pass 2: every 16 columns (32: streamed rows), rows for the most representatives of a block
-		uint32_t const stride_ = c->use_stream ? 32u : 16u;
+		// the reduced states for pass 2: every 8 columns (16: streamed rows), halfwords for the most representatives of a block
+		// ([r16] two 16-bit arrays: the memory of the 32-bit states at twice these strides; FSEQ_RED_SS_STRIDE: a power of two, 4..64)
+		uint32_t stride_ = c->use_stream ? 16u : 8u;
+		if (c->tune.red_ss_stride) { stride_ = 4u; while (stride_ * 2u <= (uint32_t) std::min(c->tune.red_ss_stride, 64)) stride_ *= 2u; }
 		uint32_t const scap = (std::max(max_rows, 1u) + 63u) & ~63u;
 		uint64_t const q_lo = (uint64_t) b_lo * c->B / stride_, q_hi = std::min<uint64_t>(n, (uint64_t) b_hi * c->B) / stride_;
-		size_t const words = ((size_t) (q_hi - q_lo) + 2) * scap;
-		if ((rc = c->d_red_ss_a.ensure(c, words))) return rc;
-		if ((rc = c->d_red_ss_d.ensure(c, words))) return rc;
+		size_t const halfwords = ((size_t) (q_hi - q_lo) + 2) * scap;
+		if ((rc = c->d_red_ss_a.ensure(c, halfwords))) return rc;
+		if ((rc = c->d_red_ss_d.ensure(c, halfwords))) return rc;
 		c->red_ss_stride = stride_; c->red_ss_cap = scap;
 		c->d_red_ss_a.rebase((ptrdiff_t) ((size_t) q_lo * scap));         // (the state at column q * stride at [q][scap])
 		c->d_red_ss_d.rebase((ptrdiff_t) ((size_t) q_lo * scap));
@@ -368,8 +370,10 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 		bool const cls = c->cls_staged && red_config_cls(c, ls[i].config);
 		RA.symcap = red_symcap(m, c->bsh, rs, c->red_direct, cls ? c->cls_ld : 0);
 		RA.cls_have = cls ? (uint32_t const *) c->d_cls_have : nullptr;
-		size_t const lds = rs.lds(c->B, RA.symcap);
-		HIP_TRY(c, rs.prepare(lds));
+		// [r16] pass 2's launches (the class tables asked for) take the sweep form
+		bool const sweep = RA.cls != nullptr;
+		size_t const lds = sweep ? rs.lds_sweep(c->B, RA.symcap) : rs.lds(c->B, RA.symcap);
+		HIP_TRY(c, rs.prepare(lds, sweep));
 		RA.blocks = base.blocks + ls[i].first;
 		if (base.wg_tasks) RA.wg_tasks = base.wg_tasks + 3 * (size_t) ls[i].first;
 		hipStream_t s_ = st;
@@ -380,7 +384,7 @@ int red_launch_all(fseq_ctx *c, std::vector<RedLaunch> const &ls, RedArgs const 
 			s_ = slot == 0 ? c->stream2 : c->red_st[slot - 1];
 			HIP_TRY(c, hipStreamWaitEvent(s_, c->red_ev.fork, 0));
 		}
-		rs.launch(s_, ls[i].count, lds, C, RA);
+		HIP_TRY(c, rs.launch(s_, ls[i].count, lds, C, RA));
 		if (slot < nside) HIP_TRY(c, hipEventRecord(*joins[slot], s_));
 	}
 	for (size_t i = 0; i < nside; ++i) HIP_TRY(c, hipStreamWaitEvent(st, *joins[i], 0));

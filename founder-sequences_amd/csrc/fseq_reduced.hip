@@ -13,20 +13,58 @@ struct LaunchRed {
 	{
 		return columns_lds_bytes<T, E, 4, PK>(B) - 2 * carve_bytes((size_t) T * E, 1) + 2 * carve_bytes(symcap, 1);
 	}
-	static hipError_t prepare(size_t bytes) { return allow_lds(k_columns_red<T, E, 4, PK, EW>, bytes); }
-	static void launch(hipStream_t st, uint32_t grid, size_t bytes, ColumnsArgs const &C, RedArgs const &red)
+	// [r16] the forms compiled: phase C's where the plan sends phase C (plan_reduced: T <= 128 || ew), the sweep form where it sends
+	// pass 2 (!ew) -- only the 64-thread configurations have both
+	static constexpr bool PHASE = T <= 128 || EW, SWEEP = !EW;
+	static size_t lds_sweep(uint32_t, uint32_t symcap)
+	{
+		size_t const runs = columns_run_words(T, E, 4, PK);
+		return 2 * carve_bytes((size_t) T * E, PK ? 2 : 4) + 2 * carve_bytes(symcap, 1) + carve_bytes(1, sizeof(StepScratch<T, 4>)) + carve_bytes(T / WAVE + 1, 4)
+		     + (runs ? carve_bytes(runs, 4) : 0);
+	}
+	static hipError_t prepare(size_t bytes, bool sweep)
+	{
+		if constexpr (SWEEP) { if (sweep) return allow_lds(k_columns_red<T, E, 4, PK, EW, true>, bytes); }
+		if constexpr (PHASE) { if (!sweep) return allow_lds(k_columns_red<T, E, 4, PK, EW>, bytes); }
+		return hipErrorInvalidDeviceFunction;               // (a form this configuration is never planned for)
+	}
+	static hipError_t launch(hipStream_t st, uint32_t grid, size_t bytes, ColumnsArgs const &C, RedArgs const &red)
 	{
 		MsaArgs const &A = C.A;
-		hipLaunchKernelGGL((k_columns_red<T, E, 4, PK, EW>), dim3(grid), dim3(T), bytes, st, A.msa, A.ld, A.n, A.B, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr,
-		                   A.npass, A.bsh, red);
+		bool launched = false;
+		if constexpr (SWEEP)
+		{
+			if (red.cls)
+			{
+				launched = true;
+				hipLaunchKernelGGL((k_columns_red<T, E, 4, PK, EW, true>), dim3(grid), dim3(T), bytes, st, A.msa, A.ld, A.n, A.B, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent,
+				                   C.lists.hdr, A.npass, A.bsh, red);
+			}
+		}
+		if constexpr (PHASE)
+		{
+			if (!red.cls)
+			{
+				launched = true;
+				hipLaunchKernelGGL((k_columns_red<T, E, 4, PK, EW>), dim3(grid), dim3(T), bytes, st, A.msa, A.ld, A.n, A.B, C.lists.L, C.lists.X, C.lists.stride, C.lists.ent, C.lists.hdr,
+				                   A.npass, A.bsh, red);
+			}
+		}
+		return launched ? hipSuccess : hipErrorInvalidDeviceFunction;      // (a form this configuration does not have: nothing was launched)
 	}
+	// (a configuration that has the sweep form only answers for that kernel at the bytes asked for.  Planning asks with phase C's LDS
+	// figure -- red_configs' class-column rule and red_report's line --, which is more than a sweep requests: the answer is a lower
+	// bound of the sweeps' residents, kept so that which blocks stage their class columns does not move with [r16])
 	static uint32_t resident(size_t bytes)
 	{
 		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_columns_red<T, E, 4, PK, EW>, T, bytes) != hipSuccess || nb < 1) nb = 1;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_columns_red<T, E, 4, PK, EW, !PHASE>, T, bytes) != hipSuccess || nb < 1) nb = 1;
 		return (uint32_t) nb;
 	}
-	static ReducedSet make() { return ReducedSet{(uint32_t) T, (uint32_t) E, EW ? (uint32_t) (T - 64) * E : (uint32_t) T * E, (uint32_t) columns_value_cap(T, E, PK), PK, EW, &lds, &prepare, &launch, &resident}; }
+	static ReducedSet make()
+	{
+		return ReducedSet{(uint32_t) T, (uint32_t) E, EW ? (uint32_t) (T - 64) * E : (uint32_t) T * E, (uint32_t) columns_value_cap(T, E, PK), PK, EW, &lds, &lds_sweep, &prepare, &launch, &resident};
+	}
 };
 
 // ascending by the rows they hold.  EW: wave 0 holds no rows and emits the lists while the row waves are in the next column (from 256

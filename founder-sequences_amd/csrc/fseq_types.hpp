@@ -233,8 +233,9 @@ struct RedArgs {
 	// pass 2: instead of lists, the class tables at the task columns of the block
 	uint32_t const *wg_tasks = nullptr; // [workgroup][3] {first task, tasks, column of the start state (the block's first column, or a stride state's)}
 	// the reduced states phase C drops every ss_stride columns (the state at column q * ss_stride at [q][ss_cap], where that
-	// column lies strictly inside a block): where pass 2's sweeps start from
-	uint32_t *ss_a = nullptr, *ss_d = nullptr;
+	// column lies strictly inside a block): where pass 2's sweeps start from.  [r16] Two 16-bit arrays: the order as the column
+	// kernel holds it, and every divergence as its column into the block (0: at or in front of the block's first column)
+	uint16_t *ss_a = nullptr, *ss_d = nullptr;
 	uint32_t ss_stride = 0, ss_cap = 0;
 	unsigned long long const *task_rb = nullptr;   // [task] column (ascending inside a workgroup)
 	uint32_t *cls = nullptr;            // [task][cap] class (rank among the distinct key prefixes) of every block key

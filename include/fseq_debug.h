@@ -89,6 +89,15 @@ int  fseq_debug_packed_columns(fseq_ctx *ctx, uint64_t c0, uint64_t c1, uint8_t 
  * runs ([0]: one run).  All zero where the last run did not go through that kernel (LDS-resident rows, no representatives). */
 int  fseq_debug_pass2_paths(fseq_ctx *ctx, uint32_t *by_runs, uint32_t *by_sort, uint32_t *copies, uint32_t *max_runs, uint32_t *runs_hist);
 
+/* Pass 2's sweeps of the last run at caller-chosen columns: after a finished run whose phase C went through the blocks'
+ * representatives, the class tables (k_columns_red in its sweep form, from the reduced state phase C dropped in front of the column
+ * or from the block's first column) at columns[0 .. count), ascending and each strictly inside a block -- the task construction and
+ * the launches of pass 2 itself, on buffers of this call.  By rows of the alignment, m words a column: cls[i * m + r] the class of
+ * row r at columns[i] (the class of its block key), headd[i * m + c] the divergence in front of class c for c < ncls[i] (0xFFFFFFFF
+ * behind them), ncls[i] the classes.  FSEQ_E_UNSUPPORTED where the last run was not reduced (or sharded), or a column lies in a block
+ * without representatives; FSEQ_E_ARG for columns on a block border, out of order or outside the alignment. */
+int  fseq_debug_class_tables(fseq_ctx *ctx, uint64_t const *columns, uint32_t count, uint32_t *cls, uint32_t *headd, uint32_t *ncls);
+
 /* Where the reduced alignment of the last run came from (streamed rows behind the reduced phase C): *from_classes blocks took their
  * representatives' columns from phase A's class columns (the block trie's, csrc/fseq_blocktrie.hpp), *from_alignment blocks
  * from the alignment itself (blocks the trie gave up; every block with FSEQ_CLASS_COLUMNS=0, or where the class columns did not
