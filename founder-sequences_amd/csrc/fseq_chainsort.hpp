@@ -60,6 +60,26 @@ __device__ __forceinline__ uint32_t cs_below(uint64_t mask)
 	return (uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
 }
 
+// -DFSEQ_RUN_STAMPS: [r17] where a run step's time goes.  s_memrealtime stamps (100 MHz: units of 10 ns) behind the parts of
+// pass2_runs and chainwg_runs, every part ending at a barrier; thread 0 of every 64th workgroup prints the sums over the run steps
+// of the first blocks / the first chain it takes (k_chain_snap_grouped, k_chain_wg).
+#ifdef FSEQ_RUN_STAMPS
+struct RunStamps {
+	unsigned long long last, acc[8];
+	uint32_t steps;
+	__device__ __forceinline__ void clear() { for (int i = 0; i < 8; ++i) acc[i] = 0; steps = 0; }
+	__device__ __forceinline__ void start() { last = __builtin_amdgcn_s_memrealtime(); }
+	__device__ __forceinline__ void mark(int part) { unsigned long long const t = __builtin_amdgcn_s_memrealtime(); acc[part] += t - last; last = t; }
+};
+#define FSEQ_RS_PARAM , RunStamps &rs
+#define FSEQ_RS_ARG , rs
+#define FSEQ_RS_MARK(part) rs.mark(part)
+#else
+#define FSEQ_RS_PARAM
+#define FSEQ_RS_ARG
+#define FSEQ_RS_MARK(part)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // Pass 2 behind the reduced phase C, streamed rows (fseq_reduced.hpp): a boundary inside a block is ONE such step from
 // the block's boundary state, keyed by the classes the block's representatives form at the boundary's column (the tables of
@@ -91,6 +111,59 @@ constexpr uint32_t P2_RUN_CAP = 8832;            // most runs of a task on the r
 constexpr uint32_t P2_CLS_BITS = 14;             // bits of a class in a run's descriptor, class << position bits | start: up to 2^18 rows
 static_assert(P2_CLS_CAP <= (1u << P2_CLS_BITS), "a class of a reduced block fits a descriptor");
 
+// A workgroup's sweeps go to memory (the workspaces of a chip's worth of workgroups are far beyond the caches), sixteen waves a
+// CU: what a step takes is the round trips of its sweeps, so the run steps' own sweeps (pass2_runs, chainwg_*) keep CW_U groups of 64 positions in flight a wave
+constexpr uint32_t CW_U = 8;
+
+// [r17] The run of a new position without a search.  The sorted runs' first new positions as a bitmap (bit p & 31 of word p >> 5:
+// position p starts a run) and pre[w], the starts in front of the 64 positions w: a wave's 64 positions of the output sweep are
+// consecutive and 64-aligned, so the run of position p is pre[p >> 6] + (the starts of its 64 up to and including p) - 1 -- two
+// wave-uniform LDS reads and an mbcnt pair -- and p is a head where its own bit is set.  Sized for 2^18 rows; a step's runs are at
+// most 16,384, so 16 bits hold a count of starts.
+constexpr uint32_t SEL_ROWS = 1u << 18;
+struct RunSelect {
+	uint32_t bits[SEL_ROWS / 32];
+	uint16_t pre[SEL_ROWS / 64];
+};
+
+// Clears the words of m positions.  The caller puts a barrier between this and sel_set.
+__device__ __forceinline__ void sel_clear(RunSelect &B, uint32_t m)
+{
+	for (uint32_t w = threadIdx.x; w < 2u * ((m + 63u) / 64u); w += ST) B.bits[w] = 0u;
+}
+__device__ __forceinline__ void sel_set(RunSelect &B, uint32_t p) { atomicOr(&B.bits[p >> 5], 1u << (p & 31u)); }
+// pre from the bits every thread has set (barriers before and inside; the caller puts one behind)
+__device__ __forceinline__ void sel_scan(RunSelect &B, uint32_t m, uint32_t *scan)
+{
+	__syncthreads();
+	constexpr uint32_t Q = SEL_ROWS / 64u / ST;
+	uint32_t const nw = (m + 63u) / 64u, w0 = threadIdx.x * Q;
+	uint32_t c[Q], sum = 0;
+#pragma unroll
+	for (uint32_t t = 0; t < Q; ++t)
+	{
+		c[t] = w0 + t < nw ? (uint32_t) __popc(B.bits[2u * (w0 + t)]) + (uint32_t) __popc(B.bits[2u * (w0 + t) + 1u]) : 0u;
+		sum += c[t];
+	}
+	uint32_t all;
+	uint32_t at = block_excl_add<ST>(sum, scan, &all);
+#pragma unroll
+	for (uint32_t t = 0; t < Q; ++t)
+		if (w0 + t < nw) { B.pre[w0 + t] = (uint16_t) at; at += c[t]; }
+}
+// The run of new position p (its wave's positions: the 64 of p >> 6, lane = p & 63, or all of them at or behind m) and whether p is
+// the run's head.  A position at or behind m gets a run of the step (of the last 64 positions) and is no head's business.
+__device__ __forceinline__ uint32_t sel_run(RunSelect const &B, uint32_t p, uint32_t m, bool *head)
+{
+	uint32_t const w = __builtin_amdgcn_readfirstlane(min(p, m - 1u) >> 6);
+	uint32_t const lo = __builtin_amdgcn_readfirstlane(B.bits[2u * w]), hi = __builtin_amdgcn_readfirstlane(B.bits[2u * w + 1u]);
+	uint32_t const lane = lane_id();
+	bool const h = (((lane < 32u ? lo : hi) >> (lane & 31u)) & 1u) != 0u;
+	*head = h;
+	// (position 0 starts a run: the count is at least one wherever p < m)
+	return (uint32_t) B.pre[w] + (uint32_t) __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u)) + (h ? 1u : 0u) - 1u;
+}
+
 struct Pass2Lds {
 	uint32_t scan[ST / WAVE + 1];
 	uint32_t grp;                                // the group the workgroup took
@@ -101,8 +174,8 @@ struct Pass2Lds {
 			uint16_t cls[P2_CLS_CAP];            // the task's class of a rank
 		};
 		struct {                                 // the run path's output sweep (the sort is done, the classes are in the descriptors)
-			uint32_t off[P2_RUN_CAP + 1];        // first new position of the run, runs by (class, start); m behind the last
-			uint32_t dsc[P2_RUN_CAP];            // its descriptor, class << position bits | start
+			uint32_t dlt[P2_RUN_CAP];            // the run's first old position less its first new one (modulo 2^32), runs by (class, start)
+			RunSelect sel;                       // the runs' first new positions
 		};
 	};
 };
@@ -288,7 +361,7 @@ __device__ __forceinline__ uint32_t pass2_range_max(uint32_t lo, uint32_t hi, ui
 // (*nrun: how many); else ends with a barrier.  LDS: the class table is gone afterwards.
 __device__ __forceinline__ bool pass2_runs(
 	uint32_t m, uint32_t const *__restrict__ kd, uint32_t D, Pass2Ws const &W, Pass2Lds &S, uint32_t run_cap, uint32_t *nrun,
-	uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1)
+	uint32_t const *__restrict__ a0, uint32_t const *__restrict__ d0, uint32_t *__restrict__ a1, uint32_t *__restrict__ d1 FSEQ_RS_PARAM)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -304,7 +377,13 @@ __device__ __forceinline__ bool pass2_runs(
 
 	// ---- a. the runs: position i starts one where its class is not the class at i - 1.  A wave sweeps its chunk in order (the
 	// class in front of a group of 64: the last lane of the group before, in front of the chunk: looked up); sweep 0 counts the
-	// starts, sweep 1 writes the descriptors {class << pb | start, end} in position order
+	// starts, sweep 1 writes the descriptors {class << pb | start, end} in position order.
+	// [r17] Where r is 16-byte aligned (the workspace's always; a block's handed-over keys where block x m is a multiple of 8) a lane
+	// takes a piece of PC = 8 consecutive ranks in one load, UV pieces in flight: a position is a start where its class differs from
+	// the one in front -- inside the piece, or the last class of the lane below (of the group before, of the chunk before) -- and
+	// the starts of a group of 64 pieces are placed by one wave scan of their counts.  The same descriptors in the same order.
+	bool const vec = (reinterpret_cast<uintptr_t>(r) & 15u) == 0u;
+	constexpr uint32_t PC = 8, UV = 4;
 	uint32_t npass, db;
 	pass2_digits(D, npass, db);
 	uint2 *const bufA = reinterpret_cast<uint2 *>(W.bufA), *const bufB = reinterpret_cast<uint2 *>(W.bufB);
@@ -315,7 +394,60 @@ __device__ __forceinline__ bool pass2_runs(
 		uint32_t prev = 0xFFFFFFFFu;                                      // (no class: position 0 starts a run)
 		if (c_lo > 0u && c_lo < c_hi) prev = (uint32_t) S.cls[r[c_lo - 1u]];
 		uint32_t k0 = wbase;
-		for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 64u * U)
+		for (uint32_t i0 = c_lo; vec && i0 < c_hi; i0 += 64u * PC * UV)
+		{
+			uint4 rv[UV];
+#pragma unroll
+			for (uint32_t u = 0; u < UV; ++u)
+			{
+				uint32_t const ib = i0 + (u * 64u + lane) * PC;
+				rv[u] = make_uint4(0u, 0u, 0u, 0u);
+				if (ib + PC <= c_hi) rv[u] = *reinterpret_cast<uint4 const *>(r + ib);
+				else if (ib < c_hi)
+				{
+					// the chunk's last piece: nothing behind c_hi is read
+					uint32_t x[PC / 2u] = {0u, 0u, 0u, 0u};
+#pragma unroll
+					for (uint32_t e = 0; e < PC; ++e)
+						if (ib + e < c_hi) x[e >> 1] |= (uint32_t) r[ib + e] << (16u * (e & 1u));
+					rv[u] = make_uint4(x[0], x[1], x[2], x[3]);
+				}
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < UV; ++u)
+			{
+				if (i0 + u * 64u * PC >= c_hi) break;
+				uint32_t const ib = i0 + (u * 64u + lane) * PC;
+				uint32_t const x[PC / 2u] = {rv[u].x, rv[u].y, rv[u].z, rv[u].w};
+				uint32_t cl[PC];
+#pragma unroll
+				for (uint32_t e = 0; e < PC; ++e) cl[e] = (uint32_t) S.cls[(x[e >> 1] >> (16u * (e & 1u))) & 0xFFFFu];
+				uint32_t const up = shfl_up_u32(cl[PC - 1u], 1);
+				uint32_t front = lane ? up : prev, hm = 0;
+#pragma unroll
+				for (uint32_t e = 0; e < PC; ++e)
+				{
+					if (ib + e < c_hi && cl[e] != front) hm |= 1u << e;
+					front = cl[e];
+				}
+				uint32_t const cnt = (uint32_t) __popc(hm), inc = wave_incl_add(cnt);
+				if (sweep)
+				{
+					uint32_t k = k0 + inc - cnt;
+#pragma unroll
+					for (uint32_t e = 0; e < PC; ++e)
+						if ((hm >> e) & 1u)
+						{
+							pos_order[2u * k] = (cl[e] << pb) | (ib + e);
+							if (k) pos_order[2u * k - 1u] = ib + e;           // (the run before ends here)
+							++k;
+						}
+				}
+				k0 += readlane_u32(inc, 63);
+				prev = readlane_u32(cl[PC - 1u], 63);                         // (a group that is not whole is the chunk's last)
+			}
+		}
+		for (uint32_t i0 = c_lo; !vec && i0 < c_hi; i0 += 64u * U)
 		{
 			uint32_t rv[U];
 #pragma unroll
@@ -348,61 +480,96 @@ __device__ __forceinline__ bool pass2_runs(
 		wbase = __builtin_amdgcn_readfirstlane(before);
 		*nrun = R;
 		if (R > run_cap) return false;
+		FSEQ_RS_MARK(1);
 	}
 	if (tid == 0u) pos_order[2u * R - 1u] = m;
 	__syncthreads();
+	FSEQ_RS_MARK(2);
 
 	// ---- b. the runs by (class, start): a stable sort by class of descriptors that are in start order
 	pass2_sort<uint2>(R, npass, db, [&](uint32_t i) -> uint2 { return reinterpret_cast<uint2 const *>(pos_order)[i]; },
 	                  [&](uint2 x) -> uint32_t { return x.x >> pb; }, make_uint2(0u, 0u), bufA, bufB, S);
+	FSEQ_RS_MARK(3);
 	// their first new positions: the prefix sum of their lengths (a thread takes consecutive runs)
 	{
 		uint32_t const q = (R + ST - 1u) / ST, j0 = min(R, tid * q), j1 = min(R, j0 + q);
 		uint32_t sum = 0;
 		for (uint32_t j = j0; j < j1; ++j) { uint2 const x = bufB[j]; sum += x.y - (x.x & pmask); }
+		// (the sort's last barrier is behind every use of the histograms and of the class table, which these arrays lie over)
+		sel_clear(S.sel, m);
 		uint32_t all;
 		uint32_t at = block_excl_add<ST>(sum, S.scan, &all);
-		// (the sort's last barrier is behind every use of the histograms and of the class table, which these arrays lie over)
-		for (uint32_t j = j0; j < j1; ++j) { uint2 const x = bufB[j]; S.off[j] = at; S.dsc[j] = x.x; at += x.y - (x.x & pmask); }
-		if (tid == 0u) S.off[R] = m;
+		for (uint32_t j = j0; j < j1; ++j)
+		{
+			uint2 const x = bufB[j];
+			S.dlt[j] = (x.x & pmask) - at; sel_set(S.sel, at);
+			at += x.y - (x.x & pmask);
+		}
+		sel_scan(S.sel, m, S.scan);
 	}
+	// (the barrier behind the heads' pass is behind pre too)
+#ifdef FSEQ_RUN_STAMPS
 	__syncthreads();
+#endif
+	FSEQ_RS_MARK(4);
 
-	// ---- c. the new order: position p lies in the run j with off[j] <= p < off[j + 1] and takes the row at old position
-	// hi = start + (p - off[j]); behind the run's head its divergence too.  A head takes the class's divergence where the run is
-	// the class's first, else the maximum of d0 from behind the end of the run before it (same class) up to hi
-	uint32_t top = 1;
-	while (top * 2u < R) top *= 2u;
-	for (uint32_t p0 = tid; p0 < m; p0 += ST * U)
+	// ---- c. the divergence of every run's head, in a pass of its own (as chainwg_runs d): the class's where the run is its class's
+	// first, else the maximum of d0 from behind the end of the run before it (same class) up to its own first position.  The sort
+	// has ended in bufB: the other pair buffer is free
+	uint32_t *const rhead = reinterpret_cast<uint32_t *>(bufA);
 	{
-		uint32_t jj[U], hh[U], av[U], dv[U];
-#pragma unroll
-		for (uint32_t u = 0; u < U; ++u)
+		constexpr uint32_t UH = 4;
+		for (uint32_t j0 = tid; j0 < R; j0 += ST * UH)
 		{
-			uint32_t const p = min(p0 + u * ST, m - 1u);
-			uint32_t j = 0;
-			for (uint32_t step = top; step; step >>= 1) { uint32_t const t = j + step; if (t < R && S.off[t] <= p) j = t; }
-			jj[u] = j;
-			hh[u] = (S.dsc[j] & pmask) + (p - S.off[j]);
-		}
+			uint2 me[UH], pv[UH];
+			uint32_t hv[UH];
 #pragma unroll
-		for (uint32_t u = 0; u < U; ++u) { av[u] = a0[hh[u]]; dv[u] = d0[hh[u]]; }
-#pragma unroll
-		for (uint32_t u = 0; u < U; ++u)
-		{
-			uint32_t const p = p0 + u * ST, j = jj[u];
-			if (p >= m) break;
-			if (S.off[j] == p)
+			for (uint32_t u = 0; u < UH; ++u)
 			{
-				uint32_t const me = S.dsc[j], pv = j ? S.dsc[j - 1u] : 0u;
-				if (j == 0u || (pv >> pb) != (me >> pb)) dv[u] = kd[me >> pb];
-				else dv[u] = pass2_range_max((pv & pmask) + (p - S.off[j - 1u]), hh[u], W.rec, W.tab, nblk, d0);
+				uint32_t const j = min(j0 + u * ST, R - 1u);
+				me[u] = bufB[j]; pv[u] = bufB[j ? j - 1u : 0u];
 			}
-			a1[p] = av[u];
-			d1[p] = dv[u];
+#pragma unroll
+			for (uint32_t u = 0; u < UH; ++u)
+			{
+				uint32_t const j = j0 + u * ST;
+				hv[u] = 0u;
+				if (j >= R) continue;
+				if (j == 0u || (pv[u].x >> pb) != (me[u].x >> pb)) hv[u] = kd[me[u].x >> pb];
+				else hv[u] = pass2_range_max(pv[u].y, me[u].x & pmask, W.rec, W.tab, nblk, d0);   // (runs of one class are not neighbours: lo < hi)
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < UH; ++u) { uint32_t const j = j0 + u * ST; if (j < R) rhead[j] = hv[u]; }
 		}
 	}
 	__syncthreads();
+	FSEQ_RS_MARK(7);
+
+	// ---- d. the new order: position p lies in the run j the bitmap gives and takes the row at old position p + dlt[j]; behind the
+	// run's head its divergence too, the head the one of c.
+	for (uint32_t p0 = tid; p0 < m; p0 += ST * CW_U)
+	{
+		uint32_t jh[CW_U], hh[CW_U], av[CW_U], dv[CW_U];
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u)
+		{
+			uint32_t const p = p0 + u * ST;
+			bool head;
+			uint32_t const j = sel_run(S.sel, p, m, &head);
+			hh[u] = p < m ? p + S.dlt[j] : 0u;
+			jh[u] = head && p < m ? j : 0xFFFFFFFFu;
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u) { av[u] = a0[hh[u]]; dv[u] = jh[u] != 0xFFFFFFFFu ? rhead[jh[u]] : d0[hh[u]]; }
+#pragma unroll
+		for (uint32_t u = 0; u < CW_U; ++u)
+		{
+			uint32_t const p = p0 + u * ST;
+			if (p < m) { a1[p] = av[u]; d1[p] = dv[u]; }
+		}
+	}
+	__syncthreads();
+	FSEQ_RS_MARK(5);
 	return true;
 }
 
@@ -540,6 +707,10 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 	Pass2Ws const W0 = pass2_ws(ws + (size_t) blockIdx.x * pass2_ws_words(m), m);
 	uint32_t pbits = 1;
 	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
+#ifdef FSEQ_RUN_STAMPS
+	RunStamps rs;
+	uint32_t rs_groups = 0;
+#endif
 	for (;;)
 	{
 		if (tid == 0) S.grp = atomicAdd(grp_next, 1u);
@@ -557,6 +728,11 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 		if (handed) W.r = const_cast<uint16_t *>(hand_keys) + sb;               // (read only from here on)
 		if (hand_stats && tid == 0) atomicAdd(hand_stats + (handed ? 0 : 1), 1u);
 		bool have_r = false;
+#ifdef FSEQ_RUN_STAMPS
+		rs.clear();
+		uint32_t rs_sorted = 0;
+		unsigned long long rs_runs = 0;
+#endif
 		for (uint32_t task = gr.x; task < gr.x + gr.y; ++task)
 		{
 			uint32_t const D = ncls[task];
@@ -582,11 +758,21 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 						for (uint32_t u = 0; u < U; ++u) { uint32_t const i = i0 + u * ST; if (i < m) W.r[i] = (uint16_t) rv[u]; }
 					}
 				// ... and the records and the table of its boundary state
+#ifdef FSEQ_RUN_STAMPS
+				__syncthreads();
+				rs.start();
+#endif
 				pass2_records(m, a0, d0, W.rec, W.tab);
+				FSEQ_RS_MARK(6);
 				have_r = true;
 			}
+#ifdef FSEQ_RUN_STAMPS
+			RunStamps const rs_before = rs;
+			rs.start();
+#endif
 			for (uint32_t j = tid; j < cap; j += ST) S.cls[j] = (uint16_t) cls[(size_t) task * cap + j];
 			__syncthreads();
+			FSEQ_RS_MARK(0);
 			// (the classes and the positions share a word where their bits fit: at most 11,264 classes, 2^18 rows)
 			uint32_t kb = 1;
 			while (kb < 32u && ((D - 1u) >> kb) != 0u) ++kb;
@@ -594,7 +780,11 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 			uint32_t const *kd = headd + (size_t) task * cap;
 			uint32_t nrun = 0;
 			// (a run's descriptor is a word of P2_CLS_BITS class bits over a position: with more than 2^18 rows every task sorts its rows)
-			bool const by_runs = run_cap != 0u && P2_CLS_BITS + pbits <= 32u && pass2_runs(m, kd, D, W, S, run_cap, &nrun, a0, d0, snap_a + ob, snap_d + ob);
+			bool const by_runs = run_cap != 0u && P2_CLS_BITS + pbits <= 32u && pass2_runs(m, kd, D, W, S, run_cap, &nrun, a0, d0, snap_a + ob, snap_d + ob FSEQ_RS_ARG);
+#ifdef FSEQ_RUN_STAMPS
+			if (by_runs) { ++rs.steps; rs_runs += nrun; }
+			else { rs = rs_before; ++rs_sorted; }                         // (a task that sorts its rows: not in the sums)
+#endif
 			if (!by_runs)
 			{
 				if (p4) pass2_step<true>(m, kd, D, W, S, d0, snap_a + ob, snap_d + ob);
@@ -610,6 +800,13 @@ __global__ __launch_bounds__(ST) void k_chain_snap_grouped(
 				}
 			}
 		}
+#ifdef FSEQ_RUN_STAMPS
+		if (tid == 0 && (blockIdx.x & 63u) == 0u && rs.steps != 0u && rs_groups++ < 3u)
+			printf("p2 run stamps workgroup %u block %u (%u rows, %s keys, %u tasks by runs of %llu runs on average, %u sorted): records %llu, per task by runs: class table %llu, "
+			       "sweep 0 %llu, sweep 1 %llu, descriptor sort %llu, prefix sums %llu, heads %llu, output sweep %llu (x 10 ns)\n",
+			       blockIdx.x, blk, m, handed ? "handed-over" : "gathered", rs.steps, rs_runs / rs.steps, rs_sorted, rs.acc[6], rs.acc[0] / rs.steps, rs.acc[1] / rs.steps,
+			       rs.acc[2] / rs.steps, rs.acc[3] / rs.steps, rs.acc[4] / rs.steps, rs.acc[7] / rs.steps, rs.acc[5] / rs.steps);
+#endif
 	}
 }
 
@@ -1022,8 +1219,11 @@ struct ChainWgLds {
 			uint32_t total[CS_BINS];
 		};
 		struct {                                 // the run path's output sweep
-			uint32_t off[CW_RUN_CAP + 1];        // first new position of the run, runs by (key, start); m behind the last
-			uint32_t dlt[CW_RUN_CAP];            // its first old position less its first new one (modulo 2^32)
+			union {
+				RunSelect sel;                   // the runs' first new positions, runs by (key, start): up to SEL_ROWS rows a bitmap ...
+				uint32_t off[CW_RUN_CAP + 1];    // ... above, the positions themselves, m behind the last: a search per position
+			};
+			uint32_t dlt[CW_RUN_CAP];            // a run's first old position less its first new one (modulo 2^32)
 		};
 	};
 };
@@ -1091,9 +1291,6 @@ __device__ __forceinline__ uint32_t chainwg_run_max(uint32_t lo, uint32_t hi, ui
 }
 
 
-// A workgroup's sweeps go to memory (the workspaces of a chip's worth of workgroups are far beyond the caches), sixteen waves a
-// CU: what a step takes is the round trips of its sweeps, so the kernel's own sweeps keep CW_U groups of 64 positions in flight a wave
-constexpr uint32_t CW_U = 8;
 
 // The keys of the old positions, W.keys[i] = rk[a0[i]], and the runs they form, counted on the way: position i starts a run where
 // its key is not the key at i - 1.  A wave sweeps its chunk in order (the key in front of a group of 64: the last lane of the group
@@ -1140,7 +1337,7 @@ __device__ __forceinline__ uint32_t chainwg_keys(uint32_t m, uint32_t const *__r
 // word.  Ends with a barrier.
 __device__ __forceinline__ void chainwg_runs(
 	uint32_t m, uint32_t const *__restrict__ kd, uint32_t nk, ChainWgWs const &W, ChainWgLds &S, uint32_t R, uint32_t wbase,
-	uint32_t const *a0, uint32_t const *d0, uint32_t *a1, uint32_t *d1)
+	uint32_t const *a0, uint32_t const *d0, uint32_t *a1, uint32_t *d1 FSEQ_RS_PARAM)
 {
 	uint32_t const tid = threadIdx.x, lane = lane_id();
 	uint32_t const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1155,6 +1352,7 @@ __device__ __forceinline__ void chainwg_runs(
 	pass2_digits(nk, npass, db);
 	uint2 *const bufA = reinterpret_cast<uint2 *>(W.bufA), *const bufB = reinterpret_cast<uint2 *>(W.bufB);
 	uint2 *const pos_order = (npass & 1u) ? bufA : bufB;                  // (the buffer the first pass of the sort does not write)
+	bool const by_select = m <= SEL_ROWS;                                 // (the debug entry takes more rows than the bitmap holds)
 
 	// ---- a. one descriptor per run, {key << pb | start, run}, in position order, the runs' starts, and the runs' maxima of d0: a
 	// scan inside the group of 64 that does not cross a start, the last lane of every piece to the run's word
@@ -1207,6 +1405,7 @@ __device__ __forceinline__ void chainwg_runs(
 	}
 	if (tid == 0u) W.rstart[R] = m;
 	__syncthreads();
+	FSEQ_RS_MARK(1);
 
 	// ---- b. prefix and suffix maxima of the runs' maxima inside blocks of 64 runs, a sparse table over the blocks
 	uint32_t const nrb = (R + 63u) / 64u;
@@ -1229,10 +1428,12 @@ __device__ __forceinline__ void chainwg_runs(
 		for (uint32_t j = tid; j + (1u << k) <= nrb; j += ST) hi[j] = max(lo[j], lo[j + (1u << (k - 1u))]);
 		__syncthreads();
 	}
+	FSEQ_RS_MARK(2);
 
 	// ---- c. the runs by (key, start): a stable sort by key of descriptors that are in start order
 	pass2_sort<uint2>(R, npass, db, [&](uint32_t i) -> uint2 { return pos_order[i]; }, [&](uint2 x) -> uint32_t { return x.x >> pb; },
 	                  make_uint2(0u, 0u), bufA, bufB, S);
+	FSEQ_RS_MARK(3);
 	// their first new positions: the prefix sum of their lengths (a thread takes consecutive runs, all its loads at once)
 	{
 		constexpr uint32_t Q = CW_RUN_CAP / ST;
@@ -1250,14 +1451,24 @@ __device__ __forceinline__ void chainwg_runs(
 		uint32_t sum = 0;
 #pragma unroll
 		for (uint32_t t = 0; t < Q; ++t) sum += len[t];
+		// (the sort's last barrier is behind every use of the histograms, which these arrays lie over)
+		if (by_select) sel_clear(S.sel, m);
 		uint32_t all;
 		uint32_t at = block_excl_add<ST>(sum, S.scan, &all);
-		// (the sort's last barrier is behind every use of the histograms, which these arrays lie over)
 #pragma unroll
 		for (uint32_t t = 0; t < Q; ++t)
-			if (j0 + t < j1) { S.off[j0 + t] = at; S.dlt[j0 + t] = st[t] - at; at += len[t]; }
-		if (tid == 0u) S.off[R] = m;
+			if (j0 + t < j1)
+			{
+				if (by_select) sel_set(S.sel, at); else S.off[j0 + t] = at;
+				S.dlt[j0 + t] = st[t] - at; at += len[t];
+			}
+		if (by_select) sel_scan(S.sel, m, S.scan);
+		else if (tid == 0u) S.off[R] = m;
 	}
+#ifdef FSEQ_RUN_STAMPS
+	__syncthreads();
+#endif
+	FSEQ_RS_MARK(4);
 
 	// ---- d. the divergence of every run's head: the key's where the run is the key's first, else the maximum of its own d0 and of
 	// the whole runs between the run before it (same key) and itself
@@ -1292,22 +1503,38 @@ __device__ __forceinline__ void chainwg_runs(
 		}
 	}
 	__syncthreads();
+	FSEQ_RS_MARK(5);
 
-	// ---- e. the new order: position p lies in the run j with off[j] <= p < off[j + 1] and takes the row at old position
-	// p + dlt[j]; behind the run's head its divergence too, the head the one of d.
+	// ---- e. the new order: position p lies in the run j the bitmap gives (more than SEL_ROWS rows: the one with off[j] <= p <
+	// off[j + 1]) and takes the row at old position p + dlt[j]; behind the run's head its divergence too, the head the one of d.
 	uint32_t top = 1;
 	while (top * 2u < R) top *= 2u;
 	for (uint32_t p0 = tid; p0 < m; p0 += ST * CW_U)
 	{
 		uint32_t jh[CW_U], hh[CW_U], av[CW_U], dv[CW_U];
-#pragma unroll
-		for (uint32_t u = 0; u < CW_U; ++u)
+		if (by_select)
 		{
-			uint32_t const p = min(p0 + u * ST, m - 1u);
-			uint32_t j = 0;
-			for (uint32_t step = top; step; step >>= 1) { uint32_t const t = j + step; if (t < R && S.off[t] <= p) j = t; }
-			hh[u] = p + S.dlt[j];
-			jh[u] = S.off[j] == p ? j : 0xFFFFFFFFu;
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u)
+			{
+				uint32_t const p = p0 + u * ST;
+				bool head;
+				uint32_t const j = sel_run(S.sel, p, m, &head);
+				hh[u] = p < m ? p + S.dlt[j] : 0u;
+				jh[u] = head && p < m ? j : 0xFFFFFFFFu;
+			}
+		}
+		else
+		{
+#pragma unroll
+			for (uint32_t u = 0; u < CW_U; ++u)
+			{
+				uint32_t const p = min(p0 + u * ST, m - 1u);
+				uint32_t j = 0;
+				for (uint32_t step = top; step; step >>= 1) { uint32_t const t = j + step; if (t < R && S.off[t] <= p) j = t; }
+				hh[u] = p + S.dlt[j];
+				jh[u] = S.off[j] == p ? j : 0xFFFFFFFFu;
+			}
 		}
 #pragma unroll
 		for (uint32_t u = 0; u < CW_U; ++u) { av[u] = a0[hh[u]]; dv[u] = jh[u] != 0xFFFFFFFFu ? W.rhead[jh[u]] : d0[hh[u]]; }
@@ -1319,6 +1546,7 @@ __device__ __forceinline__ void chainwg_runs(
 		}
 	}
 	__syncthreads();
+	FSEQ_RS_MARK(6);
 }
 
 // One step by the sort of all its rows: the keys from W.keys (ident: from rk itself -- the order is the identity, every divergence
@@ -1376,6 +1604,9 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 	ChainWgWs const W = chainwg_ws(ws + (size_t) blockIdx.x * chainwg_ws_words(m), m);
 	uint32_t pbits = 1;
 	while (pbits < 32u && ((m - 1u) >> pbits) != 0u) ++pbits;
+#ifdef FSEQ_RUN_STAMPS
+	RunStamps rs;
+#endif
 	for (uint32_t chain = blockIdx.x; chain < A.nchains; chain += gridDim.x)
 	{
 		uint32_t const grp = chain + A.grp0;
@@ -1383,6 +1614,10 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 		if (b0 >= A.nb_total) continue;
 		uint32_t const b1 = min(A.nb_total, b0 + A.G);
 		uint32_t const kstart = (uint32_t) ((uint64_t) b0 * A.cols_per_block);
+#ifdef FSEQ_RUN_STAMPS
+		rs.clear();
+		unsigned long long rs_runs = 0;
+#endif
 		// the state in front of the chain: the caller's, or the identity (never stored unless out_state asks for it)
 		bool ident = A.start_a == nullptr;
 		uint32_t const *a0 = ident ? nullptr : A.start_a + (size_t) grp * m, *d0 = ident ? nullptr : A.start_d + (size_t) grp * m;
@@ -1417,11 +1652,20 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 			{
 				// the keys in the order in front of the block, once for the step, and their runs
 				uint32_t R = 0;
+#ifdef FSEQ_RUN_STAMPS
+				RunStamps const rs_before = rs;
+				rs.start();
+#endif
 				uint32_t const wbase = chainwg_keys(m, rk, a0, W, S, hk, &R);
+				FSEQ_RS_MARK(0);
 				bool const may = run_cap != 0u && p4;
 				nrun = may ? R : 0u;
 				by_runs = may && R <= run_cap;
-				if (by_runs) chainwg_runs(m, kd, nk, W, S, R, wbase, a0, d0, a1, d1);
+				if (by_runs) chainwg_runs(m, kd, nk, W, S, R, wbase, a0, d0, a1, d1 FSEQ_RS_ARG);
+#ifdef FSEQ_RUN_STAMPS
+				if (by_runs) { ++rs.steps; rs_runs += R; }
+				else rs = rs_before;                                          // (a step that sorts its rows: not in the sums)
+#endif
 			}
 			if (!by_runs)
 			{
@@ -1441,6 +1685,13 @@ __global__ __launch_bounds__(ST) void k_chain_wg(ChainMultiArgs const A, uint32_
 			ident = false;
 			a0 = a1; d0 = d1;
 		}
+#ifdef FSEQ_RUN_STAMPS
+		if (tid == 0 && (blockIdx.x & 63u) == 0u && chain == blockIdx.x && rs.steps != 0u)
+			printf("cw run stamps workgroup %u chain %u (%u rows, %s, %u steps by runs of %llu runs on average), per step by runs: keys and run count %llu, "
+			       "a descriptors and maxima %llu, b table %llu, c descriptor sort %llu, prefix sums %llu, d heads %llu, e new order %llu (x 10 ns)\n",
+			       blockIdx.x, chain, m, A.out_rank ? "composition" : "expansion", rs.steps, rs_runs / rs.steps, rs.acc[0] / rs.steps, rs.acc[1] / rs.steps,
+			       rs.acc[2] / rs.steps, rs.acc[3] / rs.steps, rs.acc[4] / rs.steps, rs.acc[5] / rs.steps, rs.acc[6] / rs.steps);
+#endif
 		// the chain's composite key block (a composition steps through every block: a0 is the order behind the last)
 		if (A.out_rank)
 		{
